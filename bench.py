@@ -12,6 +12,12 @@ fresh random data every step (global frame index keys the Philox streams), follo
 all-reduce of the error counters.  Weak scaling: every rank simulates its own 62,500 frames per
 cell per step.  value = OFDM symbols (pilot included) simulated by all ranks / wall time.
 
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds the CPU
+baseline legs (the oracle timed on a sample of the same workload) and the BER check against the
+oracle on the same frames (`cpu_baseline`, `ber_vs_reference`).  --dump-outputs DIR writes the
+counters of the timed sweep and their BER as DIR/counts.npy and DIR/ber.npy (float64); the inputs
+depend on the arguments only, so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -86,7 +92,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    # everything beyond the headline figure: the CPU baseline legs and the BER check against the oracle
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true")    # with --full: skip those extras again
+    # after the timed steps: write the counters the last timed step left (and their BER) as DIR/<name>.npy
+    ap.add_argument("--dump-outputs", metavar="DIR")
     ap.add_argument("--frames-per-step", type=int, default=FRAMES_PER_STEP)
     # first frame of the run (per cell): lets a one-rank run cover exactly the frames an N-rank run covered (bit-identical counters)
     ap.add_argument("--frame-offset", type=int, default=0)
@@ -229,7 +239,14 @@ def main():
             "ber": ber, "snr_db": SNR_DB.tolist(),
             "bit_errors": [int(x) for x in host[0, :, 0, 0]], "bits": [int(x) for x in host[0, :, 0, 1]],
         }
-        if not a.no_cpu_baseline and world == 1:       # CPU leg: rank 0 at N=1 only
+        if a.dump_outputs:
+            # what a caller of the timed path holds after its last step: the counter tensor
+            # [pairs][snr][channels][bit errors, bits, symbol errors, symbols] (running sums over the timed
+            # steps, reduced over the ranks) and the BER per SNR point; float64 keeps the counts exact
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            np.save(os.path.join(a.dump_outputs, "counts.npy"), host.astype(np.float64))
+            np.save(os.path.join(a.dump_outputs, "ber.npy"), np.asarray(ber, dtype=np.float64))
+        if a.full and not a.no_cpu_baseline and world == 1:       # CPU leg: rank 0 at N=1 only
             base, fsamp, ocounts = cpu_baseline(W, st, w_tx, w_rx, h, seed)
             out["cpu_baseline"] = base
             # BER vs the reference algorithm on the very same frames (same Philox streams)
