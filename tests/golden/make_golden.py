@@ -12,7 +12,8 @@ The reference imports `numba` (absent from this image) only for its
 throw-away module created in a temp dir, so the reference's *own* Python code
 runs unmodified, just un-jitted.
 
-Usage:  python tests/golden/make_golden.py
+Usage:  python tests/golden/make_golden.py [timefreq | window_design | interference_sizes | psd_slices]
+        (no argument: every fixture except interference_sizes and psd_slices)
 """
 import os
 import sys
@@ -283,9 +284,96 @@ def fixture_timefreq():
     np.savez_compressed(os.path.join(HERE, "timefreq.npz"), **out)
 
 
+def fixture_interference_sizes(ch):
+    """interf_power (interf_calc.py:20-113) of all seven structures at N = 128 / 256 / 512 / 1024, at
+    one CP below L - 1 = 20 (material interference) and at CP 32 (next to none), with the RC pair
+    (P_rc) and a non-RC pair from tail_vectors() (P_opt) in the same call.  The reference averages
+    channels/vehicularA.npy over its columns; the file holds one realisation (ch[:, 9], stored as
+    h), so the mean is that channel, as in fixture_interference."""
+    out = {}
+    cwd = os.getcwd()
+    work = os.path.join(_tmp, "interf_sizes")
+    os.makedirs(os.path.join(work, "channels"))
+    np.save(os.path.join(work, "channels", "vehicularA.npy"), ch[:, 9:10])
+    os.chdir(work)
+    rs = np.random.RandomState(31)
+    cases = []
+    try:
+        for n_fft, cp_low in ((128, 16), (256, 12), (512, 16), (1024, 12)):
+            for cp in (cp_low, 32):
+                for system in SYSTEMS:
+                    btx, brx = TAILS[system]
+                    m = build_system(system, n_fft, cp, work)
+                    key = "case%d" % len(cases)
+                    cases.append(key)
+                    out[key + "_system"] = system
+                    out[key + "_cfg"] = np.array([n_fft, cp, m.cs_len, btx, brx, m.rm_len, m.shift_len])
+                    if system == "CP":
+                        out[key + "_P_rc"] = interf_power(system, [], n_fft, cp, btx, brx)
+                        continue
+                    xt, xr = tail_vectors(system, rs)
+                    wtx, wrx = windows_for(m, xt, xr)
+                    p_opt, p_rc = interf_power(system, [wtx, wrx], n_fft, cp, btx, brx)
+                    out[key + "_xt"] = xt
+                    out[key + "_xr"] = xr
+                    out[key + "_P_opt"] = p_opt
+                    out[key + "_P_rc"] = p_rc
+                    print(key, system, n_fft, cp, flush=True)
+        out["h"] = ch[:, 9].copy()
+        out["n_cases"] = len(cases)
+    finally:
+        os.chdir(cwd)
+    np.savez_compressed(os.path.join(HERE, "interference_sizes.npz"), **out)
+
+
+def fixture_psd_slices():
+    """The reference's own periodogram (wOFDMSystem.__psd_estimate, timefreq_simulation.py:104-124)
+    on seeded complex Gaussian waveforms at FL = 512 / 1024 / 2048 (N = 64 / 128 / 256, FL = 8 N).
+    Every length is a multiple of N; per FL: an exact multiple of FL (numpy pads the empty remainder,
+    so the divisor counts one all-zero slice), a multiple of FL plus N, and a long run.  A waveform
+    shorter than FL is outside the reference's domain (no full slice: NameError on `no_slice`) and
+    has no fixture.  Plus estimate_obr at N = 256, CP 12, with the recipe of fixture_timefreq (the
+periodograms and OBR figures; the main-band samples are a slice of the periodogram)."""
+    from ofdm_utils import timefreq_simulation as tf
+    psd = tf.wOFDMSystem._wOFDMSystem__psd_estimate
+    rs = np.random.RandomState(91)
+    out = {}
+    for n_fft in (64, 128, 256):
+        fl = 8 * n_fft
+        for tag, length in (("exact", 2 * fl), ("plusN", fl + n_fft), ("long", 5 * fl + 3 * n_fft)):
+            x = (rs.randn(length) + 1j * rs.randn(length)) / np.sqrt(2)
+            key = "N%d_%s" % (n_fft, tag)
+            out[key + "_x"] = x.astype(np.complex64)
+            out[key + "_psd"] = psd(out[key + "_x"].astype(np.complex128), fl)
+    rs = np.random.RandomState(78)
+    n_fft, cp = 256, 12
+    out["obr_cfg"] = np.array([n_fft, cp])
+    for i, system in enumerate(("wtx", "CPW", "wrx", "CPwtx")):
+        btx, brx = TAILS[system]
+        xt, _ = tail_vectors(system, rs)
+        m = tf.wOFDMSystem(system, n_fft, cp, btx, brx, _tmp)
+        win = np.diagflat(reduce_variable_tx(n_fft, cp, m.cs_len, btx) @ xt.reshape(-1, 1))
+        np.random.seed(2000 + i)
+        opt, rc, cpd = m.estimate_obr(win, 200e-9)
+        out["obr_" + system + "_seed"] = np.array(2000 + i)
+        out["obr_" + system + "_xt"] = xt
+        for d in (opt, rc, cpd):
+            for k, v in d.items():
+                if k == "f_axis" or k.startswith("S_") or k.startswith("mf_band_"):
+                    continue                 # closed form / a slice of X_est (pinned at N = 128 by timefreq.npz)
+                out["obr_" + system + "_" + k] = np.asarray(v)
+    np.savez_compressed(os.path.join(HERE, "psd_slices.npz"), **out)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["timefreq"]:
         fixture_timefreq()
+        sys.exit(0)
+    if sys.argv[1:] == ["interference_sizes"]:
+        fixture_interference_sizes(np.load(os.path.join(HERE, "channels_vehA.npz"))["h"].T)
+        sys.exit(0)
+    if sys.argv[1:] == ["psd_slices"]:
+        fixture_psd_slices()
         sys.exit(0)
     if sys.argv[1:] == ["window_design"]:
         fixture_window_design(np.load(os.path.join(HERE, "channels_vehA.npz"))["h"].T)

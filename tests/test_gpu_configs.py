@@ -276,6 +276,20 @@ def test_reference_workflow_windows_then_ber_then_mask(channels, tmp_path):
     assert os.path.exists(tmp_path / "pysim" / "ser" / "rc_CPwtx_16.npy")
 
 
+def _interference_fp32_floor(st, w_tx, w_rx, h):
+    """10 x the deviation of the host mirror evaluated in complex64 from the fp64 one: the fp32 floor of
+    the per-subcarrier power (tests/test_gpu_aux_kernels.py, module docstring), capped at the former
+    absolute 1e-9.  Where there is no interference it comes out at ~1e-12 of the wanted power."""
+    I = W.interference
+    p = []
+    for dt in (np.complex128, np.complex64):
+        A = (I.rx_matrix(st, w_rx).astype(dt) @ I.channel_tensor(st, np.asarray(h).astype(dt)).astype(dt)
+             @ I.tx_matrix(st, w_tx).astype(dt))
+        off = A[0] - np.diag(np.diag(A[0]))
+        p.append((np.abs(off) ** 2).sum(axis=1, dtype=np.float64) + (np.abs(A[1:]) ** 2).sum(axis=(0, 2), dtype=np.float64))
+    return min(10 * np.abs(p[1] - p[0]).max(), 1e-9)      # never looser than the former rule
+
+
 def test_interference_closed_form_on_gpu(golden, channels):
     """Row f2 on the GPU (wofdm_interference): against the reference's own interf_power output
     (tests/golden/interference.npz, N = 64, all seven structures), and at N = 256 / 512 / 1024, batched over
@@ -287,7 +301,8 @@ def test_interference_closed_form_on_gpu(golden, channels):
         st = V.Structure(system, n_fft, cp, ttx, trx, cs, rm, shift)
         got = W.interference.interf_power_gpu(st, V.tx_rc_window(st), V.rx_rc_window(st), g["h"])[0, 0]
         want = g[system + "_P_rc"]
-        assert np.abs(got - want).max() < 2e-5 * np.abs(want).max() + 1e-9, system
+        floor = _interference_fp32_floor(st, V.tx_rc_window(st), V.rx_rc_window(st), g["h"])
+        assert np.abs(got - want).max() < 2e-5 * np.abs(want).max() + floor, system
     rs = np.random.RandomState(2)
     for system, n_fft, cp in (("WOLA", 256, 32), ("CPW", 256, 10), ("wtx", 512, 24), ("wrx", 1024, 32), ("CP", 256, 16)):
         st = W.make_structure(system, n_fft, cp)
@@ -300,7 +315,8 @@ def test_interference_closed_form_on_gpu(golden, channels):
         for pi in range(2):
             for ci in range(3):
                 want = W.interference.interf_power(st, w_tx[pi], w_rx[pi], h[ci])
-                assert np.abs(got[pi, ci] - want).max() < 5e-5 * np.abs(want).max() + 1e-9, (system, pi, ci)
+                floor = _interference_fp32_floor(st, w_tx[pi], w_rx[pi], h[ci])
+                assert np.abs(got[pi, ci] - want).max() < 5e-5 * np.abs(want).max() + floor, (system, pi, ci)
 
 
 @pytest.mark.parametrize("system", ["wtx", "CPW", "wrx", "CPwtx"])
