@@ -2,7 +2,7 @@
 
 The guards of DESIGN.md section 4 are properties of the GENERATED code: every run of MFMAs of a kernel that holds op_sel-swizzled
 packed arithmetic is six long, back to back, inside one 64-byte instruction-cache line; the kernels whose MFMAs are compiler builtins
-scheduled among the vector instructions (layouts 10 ... 15) hold no such instruction; no MFMA has its destination on top of one of
+scheduled among the vector instructions (layouts 10 ... 16: wofdm_layout_info in csrc/wofdm_kernel.h) hold no such instruction; no MFMA has its destination on top of one of
 its own operands; no vector instruction writes an MFMA operand within the 12 wait states behind the MFMA, or fewer than two wait
 states in front of it; no kernel contains a flat instruction.  The scan lives in w-ofdm-optimization_amd/csrc/verify_code_layout.py and
 is a step of the BUILD (`make` runs it behind the link and does not put a failing library in place); this file runs it once more on

@@ -43,7 +43,7 @@ def test_device_present_and_philox_kat():
 
 
 def _expected_layout(st, n_fft, S):
-    """Layout id wofdm_plan_create picks for a plain plan (wofdm_spw in csrc/wofdm_kernel.h)."""
+    """Layout id wofdm_plan_create picks for a plain plan (wofdm_pick_layout in csrc/wofdm_kernel.h)."""
     B = st.stride
     if n_fft <= 128 and S % (1024 // n_fft) == 0 and B >= n_fft:
         if (1024 // n_fft) * B <= 128 * 10:

@@ -112,7 +112,7 @@ struct wofdm_plan {
     uint32_t *audit = nullptr;
     uint32_t audit_items = 0;
 #endif
-    int occ = 1, cus = 1, spw = 1;     // spw: layout id of the kernels in use (wofdm_spw)
+    int occ = 1, cus = 1, layout = 1;  // layout id of the kernels in use (wofdm_pick_layout)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -137,24 +137,24 @@ int configure(wofdm_plan *pl)
     const bool masked = var == WOFDM_VAR_TXMASK || var == WOFDM_VAR_TXFFT;
     const bool firm = !pl->fir_valu;
     const bool mdft = !pl->dft_valu;
-    int spw = masked ? wofdm_spw_masked(g.N, g.B, firm) : wofdm_spw(g.N, g.S, g.B, true, firm, mdft);
+    int layout = masked ? wofdm_pick_layout_masked(g.N, g.B, firm) : wofdm_pick_layout(g.N, g.S, g.B, true, firm, mdft);
     // (layout 15: the fast-convolution mask at N = 256 with all four transforms on the matrix pipe)
-    if (var == WOFDM_VAR_TXFFT && g.N == 256 && spw == 9 && mdft && WOFDM_TXFFT_LEN == 1024) spw = 15;
-    if (pl->max_spw > 0 && wofdm_nsym(spw, g.N) > pl->max_spw)
-        spw = (pl->max_spw == 1) ? 1 : wofdm_spw(g.N, g.S, g.B, false);
+    if (var == WOFDM_VAR_TXFFT && g.N == 256 && layout == 9 && mdft && WOFDM_TXFFT_LEN == 1024) layout = 15;
+    if (pl->max_spw > 0 && wofdm_layout_info(layout, g.N).spw > pl->max_spw)
+        layout = (pl->max_spw == 1) ? 1 : wofdm_pick_layout(g.N, g.S, g.B, false);
     // (WOFDM_DEV_LDS_PAD: developer builds only -- unused LDS bytes per workgroup, to measure how the rate depends on the
     // number of workgroups a CU holds; never defined in the shipped library)
 #ifndef WOFDM_DEV_LDS_PAD
 #define WOFDM_DEV_LDS_PAD 0
 #endif
-    const unsigned lds = wofdm_lds_bytes(g.N, g.T, spw, g.S, g.B)
+    const unsigned lds = wofdm_lds_bytes(g.N, g.T, layout, g.S, g.B)
                          + (var == WOFDM_VAR_TXMASK ? wofdm_txmask_lds_bytes(g.N) : 0u)
-                         + (var == WOFDM_VAR_TXFFT && spw != 15 ? wofdm_txfft_lds_bytes() : 0u) + (unsigned)(WOFDM_DEV_LDS_PAD);
+                         + (var == WOFDM_VAR_TXFFT && layout != 15 ? wofdm_txfft_lds_bytes() : 0u) + (unsigned)(WOFDM_DEV_LDS_PAD);
     if (lds > 160u * 1024u)
         return fail(WOFDM_E_UNSUPPORTED, "frame needs %u bytes of LDS (160 KiB per workgroup)", lds);
     wofdm_kernel_fn fn[4];
     for (int m = 0; m < 4; ++m) {
-        fn[m] = wofdm_select_kernel(g.N, g.k, spw, m, var);
+        fn[m] = wofdm_select_kernel(g.N, g.k, layout, m, var);
         if (!fn[m])
             return fail(WOFDM_E_UNSUPPORTED, "no kernel for n_fft=%d bits_per_sc=%d variant %d%s", g.N, g.k,
                         var, masked ? " (the Tx mask needs n_fft <= 512)" : "");
@@ -163,19 +163,19 @@ int configure(wofdm_plan *pl)
     }
     int occ = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &occ, reinterpret_cast<const void *>(fn[WOFDM_MODE_GEN]), 64 * wofdm_waves(spw, g.N, g.S, g.B), lds));
+        &occ, reinterpret_cast<const void *>(fn[WOFDM_MODE_GEN]), 64 * wofdm_waves(layout, g.N, g.S, g.B), lds));
     if (occ < 1) return fail(WOFDM_E_UNSUPPORTED, "kernel does not fit a CU (LDS %u bytes)", lds);
     // (the LDS goes in units of 5 120 bytes, which the occupancy API does not know: wofdm_lds_workgroups_per_cu)
     if (occ > wofdm_lds_workgroups_per_cu(lds)) occ = wofdm_lds_workgroups_per_cu(lds);
-    const int fbuf = wofdm_fbuf_len(g.N, g.T, spw, g.S, g.B);
+    const int fbuf = wofdm_fbuf_len(g.N, g.T, layout, g.S, g.B);
     HIP_TRY(hipMemcpy(pl->d_geo + WOFDM_G_FBUF, &fbuf, sizeof(int), hipMemcpyHostToDevice));
-    const int spwr = wofdm_spwr(spw, g.N, g.S, g.B);
+    const int spwr = wofdm_spwr(layout, g.N, g.S, g.B);
     HIP_TRY(hipMemcpy(pl->d_geo + WOFDM_G_SPWR, &spwr, sizeof(int), hipMemcpyHostToDevice));
     for (int m = 0; m < 4; ++m) pl->fn[m] = fn[m];
-    pl->var = var; pl->spw = spw; pl->occ = occ; pl->base.lds_bytes = lds;
+    pl->var = var; pl->layout = layout; pl->occ = occ; pl->base.lds_bytes = lds;
     // scale of the on-air samples inside the kernel (wofdm_kparams): 1/N of the IDFT, times the
     // f16 centring of the matrix-pipe layouts
-    const bool fm = wofdm_is_firm(spw);
+    const bool fm = wofdm_layout_info(layout, g.N).fir != WOFDM_FIR_VALU;
     pl->base.tx_scale = (fm ? pl->firm_sx : 1.0f) / (float)g.N;
     pl->base.dump_unscale_tx = fm ? 1.0f / pl->firm_sx : 1.0f;
     pl->base.dump_unscale_rx = fm ? 1.0f / (pl->firm_sx * pl->firm_sh) : 1.0f;
@@ -201,7 +201,7 @@ int launch(wofdm_plan *pl, int mode, wofdm_kparams &kp, uint64_t total_items, in
 #endif
     if (grid > total_items) grid = total_items;
     if (force_grid > 0) grid = (uint64_t)force_grid;
-    const size_t row = wofdm_noise_scratch_len(pl->g.N, pl->spw);
+    const size_t row = wofdm_noise_scratch_len(pl->g.N, pl->layout);
     if (row && grid * row > pl->nscr_elems) {       // only a forced grid can outgrow the plan's scratch
         HIP_TRY(hipDeviceSynchronize());
         if (pl->d_nscr) (void)hipFree(pl->d_nscr);
@@ -216,7 +216,7 @@ int launch(wofdm_plan *pl, int mode, wofdm_kparams &kp, uint64_t total_items, in
     kp.items_q = total_items / grid;
     kp.items_r = total_items % grid;
     kp.lds_bytes = pl->base.lds_bytes;
-    float2 *tm = pl->var == WOFDM_VAR_TXFFT ? (pl->spw == 15 ? reinterpret_cast<float2 *>(pl->d_tspec4) : pl->d_tspec) : pl->d_tmask;
+    float2 *tm = pl->var == WOFDM_VAR_TXFFT ? (pl->layout == 15 ? reinterpret_cast<float2 *>(pl->d_tspec4) : pl->d_tspec) : pl->d_tmask;
     kp.tx_scale = pl->base.tx_scale;
     kp.dump_unscale_tx = pl->base.dump_unscale_tx;
     kp.dump_unscale_rx = pl->base.dump_unscale_rx;
@@ -240,8 +240,9 @@ int launch(wofdm_plan *pl, int mode, wofdm_kparams &kp, uint64_t total_items, in
     // on its own, so nothing is lost.
     // (What the library can NOT order is work it does not launch: kernels of the caller's own -- torch, rocBLAS, RCCL -- on other
     // streams of the device, or another process's.  include/wofdm.h and INTEGRATION.md state the requirement: nothing else runs
-    // on the device while a launch of layouts 10 ... 15 is in flight, or the plan is switched to the VALU transforms -- option
-    // dft_valu, whose kernels issue one cache-line-aligned chain at a time: hazard 1's safe shape.)
+    // on the device while a launch of layouts 10 ... 16 (transforms on the matrix pipe: wofdm_layout_info) is in flight, or the
+    // plan is switched to the VALU transforms -- option dft_valu, whose kernels issue one cache-line-aligned chain at a time:
+    // hazard 1's safe shape.)
     {
         std::lock_guard<std::mutex> lock(g_gate_mu);
         hipEvent_t *last = g_gate_last;
@@ -249,7 +250,7 @@ int launch(wofdm_plan *pl, int mode, wofdm_kparams &kp, uint64_t total_items, in
         if (last[dev]) HIP_TRY(hipStreamWaitEvent(stream, last[dev], 0));
         else HIP_TRY(hipEventCreateWithFlags(&last[dev], hipEventDisableTiming));
         HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3((unsigned)grid),
-                                dim3(64u * (unsigned)wofdm_waves(pl->spw, pl->g.N, pl->g.S, pl->g.B)), args, kp.lds_bytes, stream));
+                                dim3(64u * (unsigned)wofdm_waves(pl->layout, pl->g.N, pl->g.S, pl->g.B)), args, kp.lds_bytes, stream));
         HIP_TRY(hipEventRecord(last[dev], stream));
     }
     return WOFDM_OK;
@@ -485,7 +486,7 @@ int wofdm_plan_create(wofdm_plan **out, const wofdm_cfg *cfg, int device, const 
         return rc;
     }
     const int occ = pl->occ;
-    if (const size_t row = wofdm_noise_scratch_len(g.N, pl->spw)) {
+    if (const size_t row = wofdm_noise_scratch_len(g.N, pl->layout)) {
         pl->nscr_elems = (uint64_t)pl->cus * (uint64_t)occ * row;
         PLAN_TRY(hipMalloc(&pl->d_nscr, pl->nscr_elems * sizeof(float2)));
         PLAN_TRY(hipMemset(pl->d_nscr, 0, pl->nscr_elems * sizeof(float2)));
@@ -672,7 +673,7 @@ int wofdm_plan_set_option(wofdm_plan *pl, int32_t option, int32_t value)
     if (rc != WOFDM_OK) { pl->force_direct_mask = direct; pl->fir_valu = valu; pl->max_spw = cap; pl->dft_valu = dvalu; }
     // (the noise scratch rows are sized per layout: a forced grid in launch() regrows them, a new layout here)
     if (rc == WOFDM_OK) {
-        const size_t row = wofdm_noise_scratch_len(pl->g.N, pl->spw);
+        const size_t row = wofdm_noise_scratch_len(pl->g.N, pl->layout);
         const uint64_t wgs = (uint64_t)pl->cus * (uint64_t)pl->occ;
         if (row && wgs * row > pl->nscr_elems) {
             if (pl->d_nscr) (void)hipFree(pl->d_nscr);
@@ -695,7 +696,7 @@ int wofdm_plan_status(wofdm_plan *pl)
 int wofdm_plan_info(wofdm_plan *pl, int32_t info[5])
 {
     if (!pl || !info) return fail(WOFDM_E_INVALID, "NULL argument");
-    info[0] = wofdm_waves(pl->spw, pl->g.N, pl->g.S, pl->g.B);
+    info[0] = wofdm_waves(pl->layout, pl->g.N, pl->g.S, pl->g.B);
     info[1] = (int32_t)pl->base.lds_bytes;
     info[2] = pl->cus * pl->occ;
     info[3] = pl->occ;
@@ -715,7 +716,7 @@ extern "C" int wofdm_plan_set_audit(wofdm_plan *pl, void *dev, uint32_t items)
 int wofdm_plan_kernel_id(wofdm_plan *pl, int32_t id[2])
 {
     if (!pl || !id) return fail(WOFDM_E_INVALID, "NULL argument");
-    id[0] = pl->spw;
+    id[0] = pl->layout;
     id[1] = pl->var;
     return WOFDM_OK;
 }

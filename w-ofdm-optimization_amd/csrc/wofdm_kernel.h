@@ -98,48 +98,70 @@ struct wofdm_kparams {
 // largest cp + cs the Tx window table of the kernel holds (wofdm_lds<N>::CPCS_MAX)
 static inline int wofdm_cpcs_max(int n_fft) { return n_fft >= 1024 ? 64 : 128; }
 static inline int wofdm_kslot(int k) { return k == 6 ? 8 : k; }
-// FIR outputs per lane for `spw` symbols per wave (fir_geo in wofdm_kernel.hip)
-// (spw is the kernel's layout id: symbols per wave, or 5 = four symbols with 20 outputs per lane)
-// 6 / 7 = four symbols per wave with the FIR on the matrix pipe (wofdm_firm_tiles tiles of 128
-// samples per wave, two samples per lane and tile)
-// 8 = one symbol per wave with the FIR on the matrix pipe (N >= 512; wofdm_fir8_tiles tiles per wave)
-// 10 / 11 = 6 / 7 with both 256-point transforms on the matrix pipe as well (lane l holds elements l + 64 j of each of the
-// wave's four symbols)
-// 12 = 8 with both transforms on the matrix pipe as well (N = 512, 1024: 16 . 16 . N/256, the last stage in registers)
-// 13 / 14 = N = 64, 128 with the FIR and both transforms on the matrix pipe: 16 / 8 symbols per wave (one MFMA stage over the stride-N/16
-// index, the radix-N/16 stage in registers), 10 / 11 FIR tiles per wave
-// 16 = 13 with a RUN-TIME number of symbols per wave (even, <= 1024 / N) and a partly filled last wave: the N = 64, 128 geometries
-// layouts 13 / 14 do not take -- S not a multiple of 16 / 8, strides beyond their tiles (N = 64 at CP 32: two waves of eight
-// symbols) -- which ran layout 2 before (round 4)
-static inline bool wofdm_is_mdft(int spw) { return spw == 10 || spw == 11 || spw == 13 || spw == 14 || spw == 16; }
-static inline bool wofdm_is_small(int spw) { return spw == 13 || spw == 14 || spw == 16; }
-// 9 = one symbol per wave, FIR on the matrix pipe, for the Tx-mask variants (any N <= 512): layout 8's frame format; the mask
-// stage works on the rows as fp32, phase B turns them into the f16 planes in place
-// 15 = 9 at N = 256 for the fast-convolution Tx mask with every transform on the matrix pipe: the symbol's own two as in layout 12
-// (one set), the mask's two 1024-point ones as four sets each with no exchange in between (no mask scratch in LDS)
-static inline bool wofdm_is_fir8(int spw) { return spw == 8 || spw == 9 || spw == 12 || spw == 15; }
-static inline bool wofdm_is_firm(int spw) { return (spw >= 6 && spw <= 9) || wofdm_is_mdft(spw) || spw == 12 || spw == 15; }
-static inline int wofdm_firm_tiles(int spw) { return spw == 14 ? 11 : ((spw == 7 || spw == 11 || spw == 13 || spw == 16) ? 10 : 9); }
 static constexpr int wofdm_fir8_tiles(int n_fft) { return n_fft >= 1024 ? 9 : (n_fft >= 512 ? 5 : 3); }
-#ifndef WOFDM_SMALL_PARTIAL
-#define WOFDM_SMALL_PARTIAL 1 // layout 16 (N = 64, 128 with a run-time number of symbols per wave); 0: layout 2 there, as before round 4
-#endif
-#ifndef WOFDM_ODD_STRIDES
-#define WOFDM_ODD_STRIDES 1   // odd strides on the matrix pipe with one symbol per wave (layout 12); 0: layout 1 as before round 4
-#endif
+
+// ---- Layouts of the frame kernel ----
+// The template parameter LAY of wofdm_frames_kernel, also the plan's kernel id (wofdm_plan_kernel_id).  Everything that depends
+// on it is read from wofdm_layout_info: the host's sizing here, the kernel's prologue, its __launch_bounds__ and the set of
+// instantiations (wofdm_layout_built).  Which layout a geometry gets is wofdm_pick_layout / wofdm_pick_layout_masked.
+//    1, 2   one / two symbols per wave, FIR and transforms on the VALU
+//    4, 5   four symbols per wave (quarter-wave layout, N = 256), VALU; 5 has 20 FIR outputs per lane instead of 18 (B <= 320)
+//    6, 7   4 / 5 with the FIR on the matrix pipe (9 / 10 tiles of 128 samples per wave, two samples per lane and tile)
+//    8      one symbol per wave with the FIR on the matrix pipe (N >= 512; wofdm_fir8_tiles tiles per wave)
+//    9      8's frame format for the Tx-mask variants (any N <= 512): the mask stage works on the rows as fp32, phase B turns them
+//           into the f16 planes in place
+//    10, 11 6 / 7 with both 256-point transforms on the matrix pipe as well (lane l holds elements l + 64 j of each of the wave's
+//           four symbols)
+//    12     8 with both transforms on the matrix pipe as well (N = 512, 1024: 16 . 16 . N/256, the last stage in registers)
+//    13, 14 N = 64, 128 with the FIR and both transforms on the matrix pipe: 16 / 8 symbols per wave (one MFMA stage over the
+//           stride-N/16 index, the radix-N/16 stage in registers), 10 / 11 FIR tiles per wave
+//    15     9 at N = 256 for the fast-convolution Tx mask with every transform on the matrix pipe: the symbol's own two as in
+//           layout 12 (one set), the mask's two 1024-point ones as four sets each with no exchange in between (no mask scratch
+//           in LDS)
+//    16     13 with a RUN-TIME number of symbols per wave (even, <= 1024 / N, wofdm_small_spwr) and a partly filled last wave:
+//           the N = 64, 128 geometries layouts 13 / 14 do not take -- S not a multiple of 16 / 8, strides beyond their tiles
+//           (N = 64 at CP 32: two waves of eight symbols) -- which ran layout 2 before (round 4)
+enum { WOFDM_FIR_VALU, WOFDM_FIR_QUARTER, WOFDM_FIR_ONE };          // VALU / matrix pipe, a wave's symbols as one row / one symbol per wave
+enum { WOFDM_DFT_VALU, WOFDM_DFT_MDFT, WOFDM_DFT_BIG, WOFDM_DFT_SMALL };  // VALU / matrix pipe: 256-point (mdft_fwd), mdft_big, one stage
+struct wofdm_layout {
+    int spw;            // symbol slots per wave, fixed at compile time (layout 16: the most; its run-time count is wofdm_spwr); 0: no layout
+    int fir, dft;       // WOFDM_FIR_*, WOFDM_DFT_*
+    bool partial;       // run-time number of symbols per wave (gm[WOFDM_G_SPWR])
+    bool masked;        // built for the Tx-mask variants only
+    int nt;             // FIR tiles of 128 samples per wave (matrix-pipe FIR)
+    int rb;             // FIR outputs per lane (fir_geo)
+    int wg, min_waves;  // __launch_bounds__: workgroup size, waves per SIMD (4: one 16-wave workgroup per CU -> 128 VGPRs per lane)
+    int n_min, n_max;   // DFT lengths it is built for
+    unsigned vars;      // variants it is built for (bit WOFDM_VAR_*; wofdm_layout_built)
+};
+#define WOFDM_LAYOUT_COUNT 17   // ids 0 .. 16
+static constexpr wofdm_layout wofdm_layout_info(int id, int n_fft)
+{
+    const int f8 = wofdm_fir8_tiles(n_fft), sm = 1024 / n_fft;
+    const unsigned PA = 3u, MASKS = 12u;   // plain + allocation; the two Tx-mask variants
+    switch (id) {
+    //               spw  fir                dft              part   mask   nt  rb                   wg     minw  N          vars
+    case 1:  return {1,  WOFDM_FIR_VALU,    WOFDM_DFT_VALU,  false, false, 0,  n_fft / 64 + 1,      1024,  4,    64, 1024,  PA | MASKS};
+    case 2:  return {2,  WOFDM_FIR_VALU,    WOFDM_DFT_VALU,  false, false, 0,  2 * (n_fft / 64) + 2, 512,  4,    64, 256,   PA};
+    case 4:  return {4,  WOFDM_FIR_VALU,    WOFDM_DFT_VALU,  false, false, 0,  4 * (n_fft / 64) + 2, 256,  3,    256, 256,  PA};
+    case 5:  return {4,  WOFDM_FIR_VALU,    WOFDM_DFT_VALU,  false, false, 0,  20,                  256,   3,    256, 256,  PA};
+    case 6:  return {4,  WOFDM_FIR_QUARTER, WOFDM_DFT_VALU,  false, false, 9,  18,                  256,   3,    256, 256,  PA};
+    case 7:  return {4,  WOFDM_FIR_QUARTER, WOFDM_DFT_VALU,  false, false, 10, 20,                  256,   3,    256, 256,  PA};
+    case 8:  return {1,  WOFDM_FIR_ONE,     WOFDM_DFT_VALU,  false, false, f8, 2 * f8,              1024,  4,    512, 1024, PA};
+    case 9:  return {1,  WOFDM_FIR_ONE,     WOFDM_DFT_VALU,  false, true,  f8, 2 * f8,              1024,  4,    64, 1024,  MASKS};
+    case 10: return {4,  WOFDM_FIR_QUARTER, WOFDM_DFT_MDFT,  false, false, 9,  18,                  256,   3,    256, 256,  PA};
+    case 11: return {4,  WOFDM_FIR_QUARTER, WOFDM_DFT_MDFT,  false, false, 10, 20,                  256,   3,    256, 256,  PA};
+    case 12: return {1,  WOFDM_FIR_ONE,     WOFDM_DFT_BIG,   false, false, f8, 2 * f8,              1024,  4,    512, 1024, PA};
+    case 13: return {sm, WOFDM_FIR_QUARTER, WOFDM_DFT_SMALL, false, false, 10, 20,                  n_fft, 3,    64, 128,   PA};
+    case 14: return {sm, WOFDM_FIR_QUARTER, WOFDM_DFT_SMALL, false, false, 11, 22,                  n_fft, 3,    64, 128,   PA};
+    case 15: return {1,  WOFDM_FIR_ONE,     WOFDM_DFT_BIG,   false, true,  f8, 2 * f8,              1024,  4,    256, 256,  8u};
+    case 16: return {sm, WOFDM_FIR_QUARTER, WOFDM_DFT_SMALL, true,  false, 10, 20,                  256,   3,    64, 128,   PA};
+    }
+    return {};
+}
 #define WOFDM_FIR8_VT 48      // words per plane of layout 8's virtual row behind the last symbol
 #define WOFDM_FIRM_PRE 24     // zero samples in front of the frame in the f16 planes (taps - 1 <= 24, 16-byte rows)
-static inline int wofdm_rb(int n_fft, int spw = 1)
-{
-    if (wofdm_is_fir8(spw)) return 2 * wofdm_fir8_tiles(n_fft);
-    if (wofdm_is_firm(spw)) return 2 * wofdm_firm_tiles(spw);
-    return spw == 1 ? n_fft / 64 + 1 : (spw == 5 ? 20 : spw * (n_fft / 64) + 2);
-}
-static inline int wofdm_nsym(int spw, int n_fft = 256)
-{
-    if (wofdm_is_small(spw)) return 1024 / n_fft;           // 16 symbols per wave at N = 64, 8 at N = 128 (layout 16: at most)
-    return wofdm_is_fir8(spw) ? 1 : ((spw == 5 || wofdm_is_firm(spw)) ? 4 : spw);
-}
+static inline int wofdm_rb(int n_fft, int layout = 1) { return wofdm_layout_info(layout, n_fft).rb; }
 // Layout 16: the symbols a wave takes -- the frame spread evenly over the fewest waves (at most four) whose share, rounded up to
 // an even count (a wave's rows are split between the two f16 planes), fits the 1024 / N symbol slots and the ten tiles of a
 // wave; 0: none fits.  The last wave takes what is left (S - (W - 1) spwr symbols, any count >= 1).
@@ -152,76 +174,77 @@ static inline int wofdm_small_spwr(int n_fft, int S, int B)
     }
     return 0;
 }
-// symbols per wave as the kernel of layout `spw` runs this geometry, and the waves of its workgroup
-static inline int wofdm_spwr(int spw, int n_fft, int S, int B)
+// symbols per wave as the kernel of `layout` runs this geometry, and the waves of its workgroup
+static inline int wofdm_spwr(int layout, int n_fft, int S, int B)
 {
-    return spw == 16 ? wofdm_small_spwr(n_fft, S, B) : wofdm_nsym(spw, n_fft);
+    const wofdm_layout li = wofdm_layout_info(layout, n_fft);
+    return li.partial ? wofdm_small_spwr(n_fft, S, B) : li.spw;
 }
-static inline int wofdm_waves(int spw, int n_fft, int S, int B)
+static inline int wofdm_waves(int layout, int n_fft, int S, int B)
 {
-    const int r = wofdm_spwr(spw, n_fft, S, B);
+    const int r = wofdm_spwr(layout, n_fft, S, B);
     return r > 0 ? (S + r - 1) / r : 0;
 }
-// symbols per wave: four at N = 256 without Tx mask (quarter-wave layout, S a multiple of 4,
-// four symbols within the 64 x 18 FIR outputs of a wave), else two where the register budget allows
-// it (N <= 256) and S is even, else one.  WOFDM_MAX_SPW (developer switch) caps it.
-#ifndef WOFDM_MAX_SPW
-#define WOFDM_MAX_SPW 4
-#endif
-static inline int wofdm_spw(int n_fft, int S, int B, bool plain = false, bool firm = true, bool mdft = true)
+// Layout of the plain and allocation variants: four symbols per wave at N = 256 (quarter-wave layouts, S a multiple of 4,
+// four symbols within the FIR outputs of a wave), the matrix-pipe layouts 13 / 14 / 16 at N = 64, 128 and 12 / 8 at N >= 512
+// where they fit, else two symbols per wave where the register budget allows it (N <= 256) and S is even, else one.
+static inline int wofdm_pick_layout(int n_fft, int S, int B, bool plain = false, bool firm = true, bool mdft = true)
 {
     // (the matrix-pipe kernels take a stride of at least n_fft for granted: their tiles below SPW n_fft
     // samples carry no validity tests)
     firm = firm && B >= n_fft;
-    if (WOFDM_MAX_SPW >= 4 && plain && mdft && firm && n_fft <= 128 && S % (1024 / n_fft) == 0) {
-        if ((1024 / n_fft) * B <= 128 * wofdm_firm_tiles(13)) return 13;
-        if ((1024 / n_fft) * B <= 128 * wofdm_firm_tiles(14)) return 14;
+    if (plain && mdft && firm && n_fft <= 128 && S % (1024 / n_fft) == 0) {
+        if ((1024 / n_fft) * B <= 128 * wofdm_layout_info(13, n_fft).nt) return 13;
+        if ((1024 / n_fft) * B <= 128 * wofdm_layout_info(14, n_fft).nt) return 14;
     }
-    if (WOFDM_MAX_SPW >= 4 && WOFDM_SMALL_PARTIAL && plain && mdft && firm && n_fft <= 128 && wofdm_small_spwr(n_fft, S, B) > 0) return 16;
-    if (WOFDM_MAX_SPW >= 4 && plain && n_fft == 256 && S % 4 == 0) {
-        if (firm && 4 * B <= 128 * wofdm_firm_tiles(6)) return mdft ? 10 : 6;
-        if (firm && 4 * B <= 128 * wofdm_firm_tiles(7)) return mdft ? 11 : 7;
+    if (plain && mdft && firm && n_fft <= 128 && wofdm_small_spwr(n_fft, S, B) > 0) return 16;
+    if (plain && n_fft == 256 && S % 4 == 0) {
+        if (firm && 4 * B <= 128 * wofdm_layout_info(6, n_fft).nt) return mdft ? 10 : 6;
+        if (firm && 4 * B <= 128 * wofdm_layout_info(7, n_fft).nt) return mdft ? 11 : 7;
         if (4 * B <= 64 * wofdm_rb(n_fft, 4)) return 4;
         if (4 * B <= 64 * wofdm_rb(n_fft, 5)) return 5;       // 288 < B <= 320: 20 outputs per lane
     }
     // one symbol per wave, matrix-pipe FIR: every stride (a 16-byte operand row that straddles the end of a symbol is cut word by
     // word, fir_load; with an odd stride the rows of the odd symbols start on an odd sample of the frame: their noise pairs take
     // two Philox blocks, their last pair holds one sample -- round 4; the LDS takes 16-byte accesses at any 4-byte alignment)
-    if (firm && plain && n_fft >= 512 && (B % 2 == 0 || (mdft && WOFDM_ODD_STRIDES)) && B <= 128 * wofdm_fir8_tiles(n_fft)) return mdft ? 12 : 8;
+    if (firm && plain && n_fft >= 512 && (B % 2 == 0 || mdft) && B <= 128 * wofdm_fir8_tiles(n_fft)) return mdft ? 12 : 8;
     return (n_fft <= 256 && S % 2 == 0 && 2 * B <= 64 * wofdm_rb(n_fft, 2)) ? 2 : 1;
 }
 
 // layout of the Tx-mask variants: 9 where the matrix-pipe FIR fits (B >= n_fft, B within its tiles; every stride since round 4 --
 // the rows of these layouts keep the stride itself as their pitch, so odd strides put planes on 4- and 8-byte boundaries, which
 // the LDS takes at a price: CPW N = 256 masked 2.63e8 symbols/s against 2.85e8 at an even stride, 1.99e8 in layout 1), else 1
-static inline int wofdm_spw_masked(int n_fft, int B, bool firm)
+static inline int wofdm_pick_layout_masked(int n_fft, int B, bool firm)
 {
-    return (firm && B >= n_fft && (B % 2 == 0 || WOFDM_ODD_STRIDES) && B <= 128 * wofdm_fir8_tiles(n_fft)) ? 9 : 1;
+    return (firm && B >= n_fft && B <= 128 * wofdm_fir8_tiles(n_fft)) ? 9 : 1;
 }
 
 // float2 elements of noise scratch per workgroup (0: not used for this DFT length)
-static inline size_t wofdm_noise_scratch_len(int n_fft, int spw)
+static inline size_t wofdm_noise_scratch_len(int n_fft, int layout)
 {
-    return n_fft >= WOFDM_NOISE_SCRATCH_MIN_N ? (size_t)16 * 64 * wofdm_rb(n_fft, spw) : 0;
+    return n_fft >= WOFDM_NOISE_SCRATCH_MIN_N ? (size_t)16 * 64 * wofdm_rb(n_fft, layout) : 0;
 }
 
-// words per plane between the LDS rows of two symbols, one symbol per wave: the stride itself in the Tx-mask layouts (9, 15: the row
-// holds the masked symbol as fp32 first), rounded up to whole 16-byte operand rows in layouts 8 / 12 -- every row and both of its
-// planes then start on 16 bytes whatever the stride (round 4: strides of 2 mod 4 ran on 8-byte-aligned planes before, odd ones not
-// at all)
-static inline int wofdm_row_stride(int spw, int B) { return (spw == 8 || spw == 12) ? ((B + 3) & ~3) : B; }
 // float2 elements of the frame buffer.  Matrix-pipe layouts: the same bytes hold two planes of
 // packed-f16 words (hi and lo halves of every sample), each `len` words long: 24 zeros, the frame,
 // and zeros up to the end of the tile that covers the trailing samples behind the last wave.
-static inline int wofdm_fbuf_len(int N, int T, int spw, int S = 0, int B = 0)
+static inline int wofdm_fbuf_len(int N, int T, int layout, int S = 0, int B = 0)
 {
+    const wofdm_layout li = wofdm_layout_info(layout, N);
     // (behind the last wave's first sample: its tiles and one more of zeros; layout 16: the last wave starts at (W - 1) spwr B)
-    if (wofdm_is_small(spw))
-        return (WOFDM_FIRM_PRE + (wofdm_waves(spw, N, S, B) - 1) * wofdm_spwr(spw, N, S, B) * B + 128 * (wofdm_firm_tiles(spw) + 1) + 3) / 4 * 4;
-    if (wofdm_is_fir8(spw)) return (8 + 2 * S * wofdm_row_stride(spw, B) + 2 * WOFDM_FIR8_VT) / 2;
-    if (wofdm_is_firm(spw))
-        return (WOFDM_FIRM_PRE + (S - 4) * B + 128 * (wofdm_firm_tiles(spw) + 1) + 3) / 4 * 4;
-    return ((WOFDM_LT - 1) + T + (WOFDM_LT - 1) + wofdm_rb(N, spw) + 8 + 1) / 2 * 2;
+    if (li.dft == WOFDM_DFT_SMALL)
+        return (WOFDM_FIRM_PRE + (wofdm_waves(layout, N, S, B) - 1) * wofdm_spwr(layout, N, S, B) * B + 128 * (li.nt + 1) + 3) / 4 * 4;
+    if (li.fir == WOFDM_FIR_ONE) {
+        // words per plane between the LDS rows of two symbols: the stride itself in the Tx-mask layouts (9, 15: the row holds the
+        // masked symbol as fp32 first), rounded up to whole 16-byte operand rows in layouts 8 / 12 -- every row and both of its
+        // planes then start on 16 bytes whatever the stride (round 4: strides of 2 mod 4 ran on 8-byte-aligned planes before, odd
+        // ones not at all)
+        const int row_stride = li.masked ? B : (B + 3) & ~3;
+        return (8 + 2 * S * row_stride + 2 * WOFDM_FIR8_VT) / 2;
+    }
+    if (li.fir == WOFDM_FIR_QUARTER)
+        return (WOFDM_FIRM_PRE + (S - 4) * B + 128 * (li.nt + 1) + 3) / 4 * 4;
+    return ((WOFDM_LT - 1) + T + (WOFDM_LT - 1) + li.rb + 8 + 1) / 2 * 2;
 }
 // The LDS of a CU is handed out in units of 1 280 bytes (160 KiB / 128) on this GPU -- measured, round 4: with 15 808 bytes per
 // one-wave workgroup (thirteen units) a CU holds NINE workgroups, not the ten the occupancy API reports (158 080 bytes do fit
@@ -234,13 +257,13 @@ static inline int wofdm_lds_workgroups_per_cu(unsigned lds_bytes)
     const unsigned units = (lds_bytes + WOFDM_LDS_GRANULE - 1) / WOFDM_LDS_GRANULE;
     return units ? (int)(160u * 1024u / WOFDM_LDS_GRANULE / units) : 32;
 }
-static inline unsigned wofdm_lds_bytes(int N, int T, int spw, int S, int B)
+static inline unsigned wofdm_lds_bytes(int N, int T, int layout, int S, int B)
 {
-    const int fixed = (wofdm_is_small(spw) ? 0 : (N == 256 || N == 512 ? 6 * 64 * 16 : 8 * N)) + 8 * N + 4 * 64 + 4 * 64 + 4 * (N + wofdm_cpcs_max(N)) + 4 * (N + 64) + 8 * 64;
+    const int fixed = (wofdm_layout_info(layout, N).dft == WOFDM_DFT_SMALL ? 0 : (N == 256 || N == 512 ? 6 * 64 * 16 : 8 * N)) + 8 * N + 4 * 64 + 4 * 64 + 4 * (N + wofdm_cpcs_max(N)) + 4 * (N + 64) + 8 * 64;
     const int beta = T - S * B;
     // (layout 15, behind the fall tails: 16 bytes of alignment, a row of 344 samples per wave for the mask stage's spill, and 64 spare
     // bytes at the very end -- the target of the mask stage's stores that have no output)
-    return (unsigned)(fixed + 8 * wofdm_fbuf_len(N, T, spw, S, B) + 8 * S * beta + (spw == 15 ? 16 + S * 344 * 8 + 64 : 0));
+    return (unsigned)(fixed + 8 * wofdm_fbuf_len(N, T, layout, S, B) + 8 * S * beta + (layout == 15 ? 16 + S * 344 * 8 + 64 : 0));
 }
 
 // kernel registry (wofdm_kernel.hip)
@@ -260,6 +283,13 @@ enum { WOFDM_VAR_PLAIN = 0, WOFDM_VAR_ALLOC = 1, WOFDM_VAR_TXMASK = 2, WOFDM_VAR
 #define WOFDM_TXFFT_MAX_N 256
 #define WOFDM_TXFFT_LEN 1024
 #define WOFDM_TXFFT_SLOTS 8
+// the (layout, N, variant) combinations the library instantiates (wofdm_kernel.hip, pick_layout)
+static constexpr bool wofdm_layout_built(int layout, int n_fft, int var)
+{
+    const wofdm_layout li = wofdm_layout_info(layout, n_fft);
+    return li.spw > 0 && n_fft >= li.n_min && n_fft <= li.n_max && ((li.vars >> var) & 1u)
+           && (var != WOFDM_VAR_TXMASK || n_fft <= WOFDM_TXMASK_MAX_N) && (var != WOFDM_VAR_TXFFT || n_fft <= WOFDM_TXFFT_MAX_N);
+}
 // LDS behind the frame buffer in the FFT form: twiddles + scratch rows
 static inline unsigned wofdm_txfft_lds_bytes(void)
 {
@@ -275,38 +305,38 @@ static inline unsigned wofdm_txmask_lds_bytes(int n_fft)
 }
 // one translation unit per (DFT length, bits per subcarrier): wofdm_kernel.hip with
 // -DWOFDM_TU_N=<N> -DWOFDM_TU_K=<k>
-wofdm_kernel_fn wofdm_select_kernel_n64_k2(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n64_k4(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n64_k6(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n128_k2(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n128_k4(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n128_k6(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n256_k2(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n256_k4(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n256_k6(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n512_k2(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n512_k4(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n512_k6(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n1024_k2(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n1024_k4(int spw, int mode, int var);
-wofdm_kernel_fn wofdm_select_kernel_n1024_k6(int spw, int mode, int var);
-static inline wofdm_kernel_fn wofdm_select_kernel(int n_fft, int bits_per_sc, int spw, int mode, int var)
+wofdm_kernel_fn wofdm_select_kernel_n64_k2(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n64_k4(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n64_k6(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n128_k2(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n128_k4(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n128_k6(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n256_k2(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n256_k4(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n256_k6(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n512_k2(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n512_k4(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n512_k6(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n1024_k2(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n1024_k4(int layout, int mode, int var);
+wofdm_kernel_fn wofdm_select_kernel_n1024_k6(int layout, int mode, int var);
+static inline wofdm_kernel_fn wofdm_select_kernel(int n_fft, int bits_per_sc, int layout, int mode, int var)
 {
-    if (n_fft == 64 && bits_per_sc == 2) return wofdm_select_kernel_n64_k2(spw, mode, var);
-    if (n_fft == 64 && bits_per_sc == 4) return wofdm_select_kernel_n64_k4(spw, mode, var);
-    if (n_fft == 64 && bits_per_sc == 6) return wofdm_select_kernel_n64_k6(spw, mode, var);
-    if (n_fft == 128 && bits_per_sc == 2) return wofdm_select_kernel_n128_k2(spw, mode, var);
-    if (n_fft == 128 && bits_per_sc == 4) return wofdm_select_kernel_n128_k4(spw, mode, var);
-    if (n_fft == 128 && bits_per_sc == 6) return wofdm_select_kernel_n128_k6(spw, mode, var);
-    if (n_fft == 256 && bits_per_sc == 2) return wofdm_select_kernel_n256_k2(spw, mode, var);
-    if (n_fft == 256 && bits_per_sc == 4) return wofdm_select_kernel_n256_k4(spw, mode, var);
-    if (n_fft == 256 && bits_per_sc == 6) return wofdm_select_kernel_n256_k6(spw, mode, var);
-    if (n_fft == 512 && bits_per_sc == 2) return wofdm_select_kernel_n512_k2(spw, mode, var);
-    if (n_fft == 512 && bits_per_sc == 4) return wofdm_select_kernel_n512_k4(spw, mode, var);
-    if (n_fft == 512 && bits_per_sc == 6) return wofdm_select_kernel_n512_k6(spw, mode, var);
-    if (n_fft == 1024 && bits_per_sc == 2) return wofdm_select_kernel_n1024_k2(spw, mode, var);
-    if (n_fft == 1024 && bits_per_sc == 4) return wofdm_select_kernel_n1024_k4(spw, mode, var);
-    if (n_fft == 1024 && bits_per_sc == 6) return wofdm_select_kernel_n1024_k6(spw, mode, var);
+    if (n_fft == 64 && bits_per_sc == 2) return wofdm_select_kernel_n64_k2(layout, mode, var);
+    if (n_fft == 64 && bits_per_sc == 4) return wofdm_select_kernel_n64_k4(layout, mode, var);
+    if (n_fft == 64 && bits_per_sc == 6) return wofdm_select_kernel_n64_k6(layout, mode, var);
+    if (n_fft == 128 && bits_per_sc == 2) return wofdm_select_kernel_n128_k2(layout, mode, var);
+    if (n_fft == 128 && bits_per_sc == 4) return wofdm_select_kernel_n128_k4(layout, mode, var);
+    if (n_fft == 128 && bits_per_sc == 6) return wofdm_select_kernel_n128_k6(layout, mode, var);
+    if (n_fft == 256 && bits_per_sc == 2) return wofdm_select_kernel_n256_k2(layout, mode, var);
+    if (n_fft == 256 && bits_per_sc == 4) return wofdm_select_kernel_n256_k4(layout, mode, var);
+    if (n_fft == 256 && bits_per_sc == 6) return wofdm_select_kernel_n256_k6(layout, mode, var);
+    if (n_fft == 512 && bits_per_sc == 2) return wofdm_select_kernel_n512_k2(layout, mode, var);
+    if (n_fft == 512 && bits_per_sc == 4) return wofdm_select_kernel_n512_k4(layout, mode, var);
+    if (n_fft == 512 && bits_per_sc == 6) return wofdm_select_kernel_n512_k6(layout, mode, var);
+    if (n_fft == 1024 && bits_per_sc == 2) return wofdm_select_kernel_n1024_k2(layout, mode, var);
+    if (n_fft == 1024 && bits_per_sc == 4) return wofdm_select_kernel_n1024_k4(layout, mode, var);
+    if (n_fft == 1024 && bits_per_sc == 6) return wofdm_select_kernel_n1024_k6(layout, mode, var);
     return nullptr;
 }
 hipError_t wofdm_philox_kat_launch(const uint32_t *ctr_key_dev, uint32_t *out_dev, hipStream_t s);

@@ -4,7 +4,7 @@
 // cell-major (cell, frame) work items); one 64-lane wavefront owns one, two, four, eight or sixteen OFDM symbols of
 // the frame (layout ids: wofdm_kernel.h):
 //
-//   A  Philox bits -> Gray QAM (registers) -> N-point IFFT (layouts 10 ... 15: both 16-point DFT stages as split-f16 products on the
+//   A  Philox bits -> Gray QAM (registers) -> N-point IFFT (layouts 10 ... 16: both 16-point DFT stages as split-f16 products on the
 //      matrix pipe, registers to registers; the others: in-register 8/16-point DFT stages with one or two exchanges through the
 //      wave's own slice of the LDS frame buffer) -> CP/CS copy x Tx window written straight from the last stage, in the
 //      matrix-pipe layouts split into two packed-f16 words per sample; the beta-sample fall tail goes to a side buffer
@@ -31,46 +31,28 @@
 #include "wofdm_kernel.h"
 #include "philox.h"
 #include <type_traits>
+#include <utility>
 
-// Relaxed synchronisation (default): of the three workgroup barriers of a frame only the one in
+// Relaxed synchronisation: of the three workgroup barriers of a frame only the one in
 // front of the noise scaling is a true all-to-all (total powers).  Barrier 1 is "my predecessor
 // wave has written its symbols" and barrier 3 "the pilot wave has published the equaliser": both
 // become LDS flags carrying the loop iteration number, so that early waves run on into the next
-// phase instead of idling at the end of each one.  -DWOFDM_RELAXED_SYNC=0 restores the barriers.
-#ifndef WOFDM_RELAXED_SYNC
-#define WOFDM_RELAXED_SYNC 1
-#endif
+// phase instead of idling at the end of each one.
 // The flag waits spin a bounded number of times, so a protocol error can never hang the GPU; a wave
 // that runs out of budget marks an LDS word, which becomes bit 0 of the plan's status word when the
 // workgroup retires: wofdm_plan_status and the synchronous entry points then fail with WOFDM_E_HIP
-// instead of returning counters built on stale samples.  (-DWOFDM_CHECKED_SYNC=0 drops the mark.)
-#ifndef WOFDM_CHECKED_SYNC
-#define WOFDM_CHECKED_SYNC 1
-#endif
+// instead of returning counters built on stale samples.
 // Fault injection for tests/test_gpu_parity.py::test_lost_flag_is_reported (libwofdm_hip_fault.so
 // only): wave 1 of every workgroup "forgets" to publish its symbols in its third frame.
 #ifndef WOFDM_FAULT_SKIP_FLAG
 #define WOFDM_FAULT_SKIP_FLAG 0
 #endif
 
-// N = 512 / 1024: FFT as 8.8.8 / 16.4.16 with the outer stages in registers (fft_big); 0 = the
-// radix-4/2 ladder through LDS used for the small sizes
-#ifndef WOFDM_FFT_BIG_RADIX
-#define WOFDM_FFT_BIG_RADIX 1
-#endif
-
-// Received samples stored swizzled against the four-way bank conflicts of the noise-scaling stores (layouts 10 / 11 / 12, phase C)
-#ifndef WOFDM_RX_SWIZZLE
-#define WOFDM_RX_SWIZZLE 1
-#endif
-// N = 1024: tiles whose unit noise stays in registers instead of being parked in the HBM scratch row (see phase B).  All nine since
-// the end of round 4: with the transforms on the matrix pipe the kernel holds FIR outputs and noise of all tiles at 128 registers
+// N = 1024: the unit noise of every tile stays in registers instead of being parked in the HBM scratch row (see phase B), since
+// the end of round 4: with the transforms on the matrix pipe the kernel holds FIR outputs and noise of all nine tiles at 128 registers
 // with seven of them spilled (28 bytes of scratch per lane), and that beats parking any tile's noise in HBM -- 6 kept: 2.62e8,
 // 7: 2.70, 8: 2.72, 9: 2.74e8 symbols/s, C4 at full size 7.65 -> 7.30 s (interleaved A/Bs, profiles/r04_noise_keep_ab.txt).  (Round 2
 // parked all nine, round 3 three of nine: those kernels, with their transforms on the vector pipe, spilled dozens.)
-#ifndef WOFDM_NOISE_KEEP_TILES
-#define WOFDM_NOISE_KEEP_TILES 9
-#endif
 
 // Issue priority of a wave by the phase it is in (s_setprio, 0 .. 3; round 4).  The SIMD's arbiter picks by priority, then age.  The
 // tile loop of phase B is one long run of vector instructions (Philox, Box-Muller) that is always ready to issue; every other
@@ -81,45 +63,10 @@
 // labels, overlap-add, power sums and barrier, gain and noise scaling, Rx loads, demapping) 2, the transforms and the Tx write 1, the
 // tile loop 0 (the transforms at 0 as well: 12.2 ms; at 2: no better than 1; every level above the tile loop alike: +0.8 %).  The
 // layouts with one symbol per wave keep their transforms at the upper level: at the middle one N = 512 / 1024 lose 4 % / 8 %.
-#ifndef WOFDM_PRIO_A
-#define WOFDM_PRIO_A 2
-#endif
-#ifndef WOFDM_PRIO_TILES
-#define WOFDM_PRIO_TILES 0
-#endif
-#ifndef WOFDM_PRIO_B3
-#define WOFDM_PRIO_B3 2
-#endif
-#ifndef WOFDM_PRIO_C
-#define WOFDM_PRIO_C 2
-#endif
-#ifndef WOFDM_PRIO_D
-#define WOFDM_PRIO_D 2
-#endif
-#ifndef WOFDM_PRIO_X                                 /* the transforms and the Tx write (layouts with four symbols per wave) */
-#define WOFDM_PRIO_X 1
-#endif
-#ifndef WOFDM_PRIO_ON
-#define WOFDM_PRIO_ON 1
-#endif
-#define WAVE_PRIO(x) do { if (WOFDM_PRIO_ON) __builtin_amdgcn_s_setprio(x); } while (0)
-// layouts 10 ... 15, generate mode: the FIR tile as a hand-placed pipeline (MFMAs between the Philox rounds; see phase B)
-#ifndef WOFDM_TILE_PIPELINE
-#define WOFDM_TILE_PIPELINE 1
-#endif
-
-// one symbol per wave: the frame's trailing samples ride in the last wave's last tile instead of a tile of their own (phase B)
-#ifndef WOFDM_FOLD_TAIL
-#define WOFDM_FOLD_TAIL 1
-#endif
-// layouts 10, 11: the 256-point transforms as a pipeline over the wave's four symbols (phases A and C)
-#ifndef WOFDM_MDFT_PIPELINE
-#define WOFDM_MDFT_PIPELINE 1
-#endif
-
-#ifndef WOFDM_MIN_WAVES_PER_SIMD
-#define WOFDM_MIN_WAVES_PER_SIMD 4      // one 16-wave workgroup per CU -> 128 VGPRs per lane
-#endif
+#define PRIO_LATENCY 2
+#define PRIO_TRANSFORM 1                             /* the transforms and the Tx write (layouts with four symbols per wave) */
+#define PRIO_TILES 0
+#define WAVE_PRIO(x) __builtin_amdgcn_s_setprio(x)
 
 namespace {
 
@@ -198,9 +145,6 @@ __device__ __forceinline__ v2f mk(float x, float y) { return (v2f){x, y}; }
 // 2^-21, four times coarser than an fp32 product -- on whole frames, against fp64 arithmetic, conv is off by 1.3e-7
 // (rms) of the frame's rms, the fp32 VALU form by 1.1e-7: both at the rounding floor of the fp32 stages around them
 // (tests/test_gpu_parity.py::test_fir_precision_matrix_pipe_vs_valu).
-#ifndef WOFDM_SPLIT_MIX32
-#define WOFDM_SPLIT_MIX32 1
-#endif
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef h2 hpair;                  // (phase C has a local named h2)
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -212,7 +156,6 @@ __device__ __forceinline__ void split_h(v2f y, uint32_t &hi, uint32_t &lo)
     hi = __builtin_bit_cast(uint32_t, h);
     // lo = f16(y - float(hi)), one mixed-precision fma per half (the difference is exact in fp32, rounded once):
     // three instructions per sample instead of five (two converts back, a packed subtract, a packed convert)
-#if WOFDM_SPLIT_MIX32
     // (round 4) the two differences as v_fma_mix_f32 -- 4.3 cycles of vector issue each, where the f16-destination forms
     // v_fma_mixlo / mixhi_f16 take 8.3 like a transcendental and read their own destination (tools/ubench/valu_dep.hip) --
     // and one more packed convert: four instructions, 17 cycles instead of three and 21, and a dependent chain of three, not
@@ -221,12 +164,6 @@ __device__ __forceinline__ void split_h(v2f y, uint32_t &hi, uint32_t &lo)
     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(dx) : "v"(hi), "v"(y.x));
     asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(dy) : "v"(hi), "v"(y.y));
     lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(mk(dx, dy), h2));
-#else
-    uint32_t l;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(hi), "v"(y.x));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(hi), "v"(y.y));
-    lo = l;
-#endif
 }
 // A matrix operand built from split_h words must not reach its MFMA straight from the vector instruction that wrote it: an operand
 // written inside inline asm needs its wait states spelled out (documented: cdna_hip_programming.md 5.7, item 2; measured:
@@ -914,37 +851,31 @@ template <int N, int DIR, int SPW>
 __device__ __forceinline__ void fft_wave(v2f (&v)[SPW][geo<N>::BPL][4], v2f *fb, int sb, const v2f *tw,
                                          int lane)
 {
-    if constexpr ((N == 512 || N == 1024) && WOFDM_FFT_BIG_RADIX) {
+    // N = 512 / 1024: 8.8.8 / 16.4.16 with the outer stages in registers (fft_big); the smaller sizes: the radix-4/2 ladder
+    // through LDS
+    if constexpr (N == 512 || N == 1024) {
         static_assert(SPW == 1, "one symbol per wave at N >= 512");
         fft_big<N, DIR>(v, fb, tw, lane);
-        return;
-    }
-    fft_first<N, DIR, SPW>(v, fb, sb, lane);
-    if constexpr (N == 64) {
-        fft_mid4<N, 4, DIR, SPW>(fb, sb, tw, lane);
-    } else if constexpr (N == 128) {
-        fft_mid2<N, 4, DIR, SPW>(fb, sb, tw, lane);
-        fft_mid4<N, 8, DIR, SPW>(fb, sb, tw, lane);
-    } else if constexpr (N == 256) {
-        fft_mid4<N, 4, DIR, SPW>(fb, sb, tw, lane);
-        fft_mid4<N, 16, DIR, SPW>(fb, sb, tw, lane);
-    } else if constexpr (N == 512) {
-        fft_mid4<N, 4, DIR, SPW>(fb, sb, tw, lane);
-        fft_mid2<N, 16, DIR, SPW>(fb, sb, tw, lane);
-        fft_mid4<N, 32, DIR, SPW>(fb, sb, tw, lane);
     } else {
-        static_assert(N == 1024, "unsupported DFT length");
-        fft_mid4<N, 4, DIR, SPW>(fb, sb, tw, lane);
-        fft_mid4<N, 16, DIR, SPW>(fb, sb, tw, lane);
-        fft_mid4<N, 64, DIR, SPW>(fb, sb, tw, lane);
+        fft_first<N, DIR, SPW>(v, fb, sb, lane);
+        if constexpr (N == 64) {
+            fft_mid4<N, 4, DIR, SPW>(fb, sb, tw, lane);
+        } else if constexpr (N == 128) {
+            fft_mid2<N, 4, DIR, SPW>(fb, sb, tw, lane);
+            fft_mid4<N, 8, DIR, SPW>(fb, sb, tw, lane);
+        } else {
+            static_assert(N == 256, "unsupported DFT length");
+            fft_mid4<N, 4, DIR, SPW>(fb, sb, tw, lane);
+            fft_mid4<N, 16, DIR, SPW>(fb, sb, tw, lane);
+        }
+        fft_last<N, DIR, SPW>(v, fb, sb, tw, lane);
     }
-    fft_last<N, DIR, SPW>(v, fb, sb, tw, lane);
 }
 
 // Fill the per-stage twiddle tables (once per workgroup).
 template <int N> __device__ __forceinline__ void fill_twiddles(v2f *tw, int tid, int nthreads)
 {
-    if constexpr ((N == 512 || N == 1024) && WOFDM_FFT_BIG_RADIX) {
+    if constexpr (N == 512 || N == 1024) {
         // tables of fft_big
         constexpr int R = N / 64, T2 = N == 1024 ? 48 : 56;
         for (int i = tid; i < T2 + (R - 1) * 64; i += nthreads) {
@@ -1104,7 +1035,7 @@ __device__ __forceinline__ void wait_flag(const lds_vint *flag, int target, lds_
     int budget = 1 << 22;
     while (__builtin_amdgcn_readfirstlane(*flag) < target) {
         if (__builtin_expect(--budget == 0, 0)) {
-            if (WOFDM_CHECKED_SYNC) *gave_up = 1;
+            *gave_up = 1;
             break;
         }
         __builtin_amdgcn_s_sleep(1);
@@ -1139,11 +1070,9 @@ struct maskfft_geo {
 // FIR outputs per lane: one wave covers SPW symbols = SPW*B consecutive samples.  For SPW = 2
 // the count is even and every lane starts on an even sample, so its unit noise is exactly
 // RB/2 Philox blocks (2.5 per symbol instead of 3).
-// (LAY = layout id = symbols per wave, except 5 = four symbols with 20 instead of 18 outputs per
-// lane, for strides of up to 320 samples)
+// (RB per layout: wofdm_layout_info)
 template <int N, int LAY> struct fir_geo {
-    static constexpr int RB = (LAY == 8 || LAY == 9 || LAY == 12 || LAY == 15) ? 2 * wofdm_fir8_tiles(N) : LAY >= 6 ? (LAY == 14 ? 22 : ((LAY == 7 || LAY == 11 || LAY == 13 || LAY == 16) ? 20 : 18))
-                              : (LAY == 1 ? N / 64 + 1 : (LAY == 5 ? 20 : LAY * (N / 64) + 2));
+    static constexpr int RB = wofdm_layout_info(LAY, N).rb;
     static constexpr bool EVEN = (LAY != 1) && (RB % 2 == 0);
     static constexpr int NBK = EVEN ? RB / 2 : RB / 2 + 1;      // Philox blocks per lane
     static constexpr int CH = RB <= 6 ? RB : (RB % 5 == 0 ? 5 : 6);
@@ -1163,27 +1092,29 @@ __device__ __forceinline__ void fir_lane(const v2f *w, const v2f *__restrict__ t
 // (main_channel_mask.m:387-390, 367-371); 2 = allocation + the per-symbol spectral Tx mask
 // dft_rc_filt (main_channel_mask.m:398-417), g_tmask = its length-(2P-1) circular impulse response
 template <int N, int K, int LAY, bool INJECT, bool DUMP, int VAR>
-__global__ void __launch_bounds__((LAY == 8 || LAY == 9 || LAY == 12 || LAY == 15) ? 1024 : ((LAY == 13 || LAY == 14) ? N : (LAY >= 4 ? 256 : 1024 / LAY)),
-                                   (LAY >= 4 && LAY != 8 && LAY != 9 && LAY != 12 && LAY != 15) ? 3 : WOFDM_MIN_WAVES_PER_SIMD)
+__global__ void __launch_bounds__(wofdm_layout_info(LAY, N).wg, wofdm_layout_info(LAY, N).min_waves)
 wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                     const float *__restrict__ g_wrx, const float2 *__restrict__ g_h_,
                     const float *__restrict__ g_nlin, const int *__restrict__ gm,
                     const uint32_t *__restrict__ g_amask, const float2 *__restrict__ g_tmask,
                     const uint4 *__restrict__ g_fira)
 {
+    // The layout (wofdm_kernel.h, wofdm_layout_info) decides the shape of the kernel:
+    constexpr wofdm_layout LI = wofdm_layout_info(LAY, N);
+    static_assert(wofdm_layout_built(LAY, N, VAR), "not a (layout, N, variant) the library is built for");
     // layouts 6, 7 (quarter-wave, four symbols per wave) and 8 (one symbol per wave, N >= 512): the
     // 21-tap FIR on the matrix pipe as a block-Toeplitz product, NT tiles of 128 samples per wave (phase B)
     // layouts 10, 11: 6, 7 with both 256-point transforms on the matrix pipe too (mdft_fwd): four symbols per wave, lane l
     // holds elements l + 64 j of each
-    constexpr bool MDFT = LAY == 10 || LAY == 11;
+    constexpr bool MDFT = LI.dft == WOFDM_DFT_MDFT;
     // layout 12: 8 with both transforms on the matrix pipe (N = 512, 1024: 16 . 16 . NC, NC = N / 256, the last stage in
     // registers; mdft_big): lane (b = lane % 16, g = lane / 16) holds the INPUT elements N/16 (g + 4 j) + NC b + c and the
     // OUTPUT elements lane + 64 j + 256 c, j < 4, c < NC
-    constexpr bool MD8 = LAY == 12;
+    constexpr bool MD8 = LI.dft == WOFDM_DFT_BIG && !LI.masked;
     // layout 15: the Tx mask's fast-convolution form at N = 256 with EVERYTHING on the matrix pipe: layout 9's frame handling (rows as fp32
     // through the mask stage, f16 planes from phase B on), the symbol's own transforms as in layout 12 with NC = 1, and the mask's
     // two 1024-point transforms as mdft_big<4> with one exchange between them
-    constexpr bool MDM = LAY == 15;
+    constexpr bool MDM = LI.dft == WOFDM_DFT_BIG && LI.masked;
     constexpr bool MDX = MD8 || MDM;                       // one symbol per wave, transforms by mdft_big
     // layouts 13, 14: N = 64 / 128, sixteen / eight symbols per wave, ONE matrix stage + the radix-N/16 stage in registers (radix4_elems)
     // layout 16: 13 with a RUN-TIME number of symbols per wave, SPWR <= SPW (even; gm[WOFDM_G_SPWR], wofdm_small_spwr), and a partly
@@ -1191,31 +1122,28 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
     // fill (slot u = 4 group + lane group >= nreal) compute along but store nothing -- what lies behind a wave's samples is the next
     // wave's, or the zeros behind the frame.  For the geometries layouts 13 / 14 do not take: S not a multiple of 16 / 8, strides
     // beyond their tiles (N = 64 at CP 32: two waves of eight symbols); they ran layout 2 before (round 4).
-    constexpr bool PART = LAY == 16;
-    constexpr bool MDS = LAY == 13 || LAY == 14 || PART;
+    constexpr bool PART = LI.partial;
+    constexpr bool MDS = LI.dft == WOFDM_DFT_SMALL;
     constexpr int SC = N / 16, SCS = MDS ? SC / 4 : 1, SGR = 4 / SCS;      // elements per lane and symbol, sets per group, groups
     constexpr bool MPIPE = MDFT || MD8 || MDS || MDM;                    // kernels without op_sel-swizzled packed arithmetic (see mma33)
     constexpr int NC = MD8 ? N / 256 : 1;                  // (layout 15: one set)
     // layout 9: the Tx-mask variants with the FIR on the matrix pipe -- layout 8's frame format; the windowed symbols and the
     // mask stage live in the rows as fp32, phase B converts each row to the two f16 planes in place
-    constexpr bool FIR8M = LAY == 9 || LAY == 15;
-    constexpr bool FIRQ = LAY == 6 || LAY == 7 || MDFT || MDS, FIR8 = LAY == 8 || MD8 || FIR8M, FIRM = FIRQ || FIR8;
-    constexpr int SPW = MDS ? 1024 / N : (FIR8 ? 1 : (LAY >= 5 ? 4 : LAY));     // symbols per wave
-    constexpr int NT = FIR8 ? wofdm_fir8_tiles(N) : (LAY == 14 ? 11 : ((LAY == 7 || LAY == 11 || LAY == 13 || PART) ? 10 : 9)), PRE = WOFDM_FIRM_PRE;
+    constexpr bool FIR8M = LI.masked;
+    constexpr bool FIRQ = LI.fir == WOFDM_FIR_QUARTER, FIR8 = LI.fir == WOFDM_FIR_ONE, FIRM = FIRQ || FIR8;
+    constexpr int SPW = LI.spw;                            // symbols per wave
+    constexpr int NT = LI.nt, PRE = WOFDM_FIRM_PRE;
     constexpr int VT = WOFDM_FIR8_VT;
-    static_assert(!FIR8 || FIR8M || (N >= 512 && VAR <= 1), "layout 8 is built for N >= 512 without Tx mask");
-    static_assert(!FIR8M || VAR >= 2, "layout 9 is the Tx-mask variants' matrix-pipe FIR layout");
-    static_assert(!MDM || (N == 256 && VAR == 3), "layout 15 is the fast-convolution Tx mask at N = 256");
     constexpr bool ALLOC = VAR >= 1, TXMASK = VAR == 2, TXFFT = VAR == 3;
     // flags instead of barriers 1 and 3 (not in the instrumented and masked variants, whose extra
     // stages have their own workgroup barriers)
-    constexpr bool RELAX = WOFDM_RELAXED_SYNC && !DUMP && VAR < 2;
+    constexpr bool RELAX = !DUMP && VAR < 2;
     // The Tx-mask variants (one symbol per wave) have one more hand-over: symbol s adds the second half of its
     // masked output onto the row of symbol s + 1 (dft_rc_filt's overlap, m:411-415).  Flags as well: [32 + s] = "my own
     // row holds my masked symbol", then [s] = "... and my spill is on my successor's row".  Phase B of wave w needs its
     // own row (complete once w - 1 has spilled: flag w - 1) and the end of its predecessor's (complete once w - 2
     // has: flag w - 2).
-    constexpr bool RELAXM = WOFDM_RELAXED_SYNC && !DUMP && VAR >= 2;
+    constexpr bool RELAXM = !DUMP && VAR >= 2;
     constexpr bool RELAXF = RELAX || RELAXM;         // flags instead of barriers 1 and 3
     static_assert(!(TXMASK || TXFFT) || SPW == 1, "the Tx mask stage runs one symbol per wave");
     constexpr int LT = WOFDM_LT;
@@ -1224,15 +1152,14 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
     // SPW = 4: quarter-wave layout (fft_qw): 16 lanes per symbol, 16 subcarriers per lane, 4-wave
     // workgroups, three of them per CU at up to 168 VGPRs
     constexpr bool QW = SPW == 4 && !MDFT && !MDS;
-    static_assert(!(QW || MDFT) || (N == 256 && VAR <= 1), "the four-symbol layouts are built for N = 256 without Tx mask");
-    static_assert(!MDS || ((N == 64 || N == 128) && VAR <= 1), "layouts 13 / 14 / 16 are built for N = 64, 128, without Tx mask");
     constexpr int VS = QW ? 1 : (MDS ? 1 : SPW), VB = QW ? 4 : BPL;      // register arrays [VS][VB][4]
     constexpr int RB = fir_geo<N, LAY>::RB, NBK = fir_geo<N, LAY>::NBK;
     constexpr bool EVEN = fir_geo<N, LAY>::EVEN;
     // Large DFTs would keep RB = N/64+1 noise samples AND FIR outputs per lane alive across
     // barrier 2 (68 VGPRs at N = 1024) and spill.  There the unit noise is parked in a per-workgroup
     // HBM scratch row ([wave][r][lane]: 512-byte coalesced rows, written and read back by the
-    // same lane, L2-resident) instead of registers; with injected noise it is simply re-read.
+    // same lane, L2-resident) instead of registers; with injected noise it is simply re-read.  (The matrix-pipe FIR layouts
+    // keep generated noise in registers and only re-read the injected one: see phase B.)
     constexpr bool RENOISE = N >= WOFDM_NOISE_SCRATCH_MIN_N;
     // Kernels at their VGPR limit make the lane id opaque again at every phase: otherwise per-lane index
     // vectors of one phase's FFT are kept for the next phase's -- in scratch (N = 1024: 20 spilled VGPRs
@@ -1262,7 +1189,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
 
     // LDS carve with compile-time offsets (wofdm_lds<N>): only the frame buffer, last, has a
     // run-time length.  Fewer live scalars = fewer SGPR spills in the frame loop.
-    using L = wofdm_lds<N, (LAY == 13 || LAY == 14 || LAY == 16)>;
+    using L = wofdm_lds<N, MDS>;
     v2f *tw = reinterpret_cast<v2f *>(smem + L::off_tw);
     v2f *G = reinterpret_cast<v2f *>(smem + L::off_g);
     float *sums = reinterpret_cast<float *>(smem + L::off_sums);
@@ -1393,7 +1320,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
     // Error counters of the cell in progress: per-lane partial sums, or -- at N >= 512, where the
     // kernels are at their VGPR limit and per-lane accumulators ended up in scratch, re-read and
     // re-written every frame -- wave totals in scalar registers (one DPP reduction per frame).
-    constexpr bool SCALAR_ACC = N >= 512 || LAY == 15;
+    constexpr bool SCALAR_ACC = N >= 512 || MDM;
     uint32_t bit_err = 0, sym_err = 0, nfr = 0;
     float nlin = 0.f;
 
@@ -1419,7 +1346,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
 #endif
     for (; n_items != 0; --n_items) {
         STAMP(7);                                   // loop control, cell changes
-        WAVE_PRIO(WOFDM_PRIO_A);
+        WAVE_PRIO(PRIO_LATENCY);
         // the 32-bit per-lane and per-wave error sums are flushed every 2^14 frames at the latest (a wave
         // counts at most 6144 bit errors per frame)
         if (cell != cur_cell || nfr == (1u << 14)) {
@@ -1555,7 +1482,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         GEO_PHASE();
         const int S = gq[WOFDM_G_S], B = gq[WOFDM_G_B], mu = gq[WOFDM_G_MU], rho = gq[WOFDM_G_RHO];
         // one symbol per wave with the FIR on the matrix pipe (layouts 8, 12): the LDS rows are BR >= B words per plane apart, BR a
-        // multiple of 4, so that every row and both of its planes start on 16 bytes whatever the stride (wofdm_row_stride)
+        // multiple of 4, so that every row and both of its planes start on 16 bytes whatever the stride (wofdm_fbuf_len)
         const int BR = (FIR8 && !FIR8M) ? ((B + 3) & ~3) : B;
         (void)BR;
         const int plen = FIRQ ? gq[WOFDM_G_FBUF] : 0;
@@ -2050,8 +1977,8 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         }
         wave_sync();
         STAMPF(9);
-        WAVE_PRIO(WOFDM_PRIO_X);
-        if constexpr (MDFT && WOFDM_MDFT_PIPELINE) {
+        WAVE_PRIO(PRIO_TRANSFORM);
+        if constexpr (MDFT) {
             // The transform as a pipeline over the wave's four symbols (round 4): the sixteen MFMAs of stage 1 are issued at once,
             // then every group is "the six MFMAs of symbol u's second stage, and BEHIND them the twiddle and the f16 split of symbol
             // u + 1" (26 vector instructions, 110 cycles, while the chain takes 96 on the matrix pipe) -- the guard behind that work
@@ -2081,21 +2008,6 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                 } else {
                     asm volatile(WOFDM_MMA_TAIL : "+v"(xr[u]), "+v"(xi[u]) : "v"(th[u]), "v"(tl[u]), "v"(dc.arh), "v"(dc.arl), "v"(dc.aih), "v"(dc.ail));
                 }
-            }
-        } else if constexpr (MDFT) {
-            const mdft_consts dc = mdft_load(dce);
-            f4 tr[4], ti[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const h8 xa = __builtin_bit_cast(h8, (u4){xw[u][0], xw[u][1], xw[u][2], xw[u][3]});
-                mma22(tr[u], ti[u], xa, dc.brl, dc.brh, dc.bil, dc.bih);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                mdft_twiddle(tr[u], ti[u], dc.twr, dc.twi);
-                h8 th, tl;
-                mdft_split4(tr[u], ti[u], th, tl);
-                mma33(xr[u], xi[u], dc.arh, tl, dc.arl, th, dc.arh, th, dc.aih, tl, dc.ail, th, dc.aih, th);
             }
         } else if constexpr (QW) fft_qw<+1>(v, row(usq), tw, llq);
         else fft_wave<N, +1, SPW>(v, fbw, B, tw, lane);     // v = N x[t]
@@ -2512,7 +2424,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         }
         DELAY_AT(2);
         STAMP(0);
-        WAVE_PRIO(WOFDM_PRIO_B3);
+        WAVE_PRIO(PRIO_LATENCY);
         if constexpr (RELAXF) {
             // ---- "barrier" 1: publish "my symbols are written"; phase B waits for the
             // predecessor wave only (its last L-1 samples and its fall tail)
@@ -2679,7 +2591,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         // waves waited 22 % of theirs at barrier 2 (profiles/r03_stamp_report.txt).  Needs rows of whole 16-byte operand words and an
         // even number of trailing samples (a lane's two samples of a tile count or do not count together).
         const int tail_total = NL - S * B;                  // beta+L-1 (MATLAB order) or 0
-        const bool fold_tail = FIR8 && !FIR8M && WOFDM_FOLD_TAIL && tail_total > 0 && (tail_total & 1) == 0 && (B & 3) == 0 && LW - 128 * (NT - 1) + tail_total <= 128
+        const bool fold_tail = FIR8 && !FIR8M && tail_total > 0 && (tail_total & 1) == 0 && (B & 3) == 0 && LW - 128 * (NT - 1) + tail_total <= 128
                                && tail_total <= VT - 12;
         const bool fold_here = fold_tail && wv == W - 1;
         const int LWS = LW + (fold_here ? tail_total : 0);      // samples of this wave that count in the power sums
@@ -2829,14 +2741,10 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                          : "v"(A[1]), "v"(A[3]), "v"(A[0]), "v"(A[2]), "v"(o.h0), "v"(o.h1), "v"(o.l0), "v"(o.l1));
             return d;
         };
-        // (large DFTs: the unit noise of the tiles from NKEEP on is parked in HBM scratch; the first NKEEP tiles' stays in
-        // registers -- as many as the 128-VGPR budget allows: what is parked has to FIT the XCD's 4 MB of L2 together with
-        // the other 31 workgroups' rows, or every access of the cyclic write / read-back pattern misses; with all nine tiles
-        // parked (4.7 MB per XCD) the N = 1024 kernel drew 250 W more, ran at the 1 400 W cap and 5 % slower)
-        constexpr int NKEEP = WOFDM_NOISE_KEEP_TILES;
-        f4 *nscr = nullptr;
-        if constexpr (RENOISE)
-            nscr = reinterpret_cast<f4 *>(p.noise_scratch) + ((size_t)blockIdx.x * 16 + wv) * (NT * 64) + lane;
+        // (large DFTs: the generated unit noise of every tile stays in registers, none is parked in HBM scratch -- what is parked
+        // has to FIT the XCD's 4 MB of L2 together with the other 31 workgroups' rows, or every access of the cyclic write /
+        // read-back pattern misses; with all nine tiles parked (4.7 MB per XCD) the N = 1024 kernel drew 250 W more, ran at the
+        // 1 400 W cap and 5 % slower.  Injected noise is re-read behind the tile loop.)
         // (two instantiations of the tile loop: with every lane of every tile in use -- C2 -- the
         // validity selects are not even emitted)
         auto tiles = [&](auto full_c, auto odd_c) {
@@ -2873,7 +2781,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
             // compiler's own order is 1.5 % faster there -- interleaved A/B, profiles/r04_other_configs.txt)
             // (odd strides take the compiler's order: the pipeline with both Philox blocks of an odd row between the MFMAs was built
             // and measured -- CPW N = 512 3.55 against 3.63e8, nothing gained)
-            if constexpr (MPIPE && !INJECT && WOFDM_TILE_PIPELINE && N < 1024 && !ODDB) {
+            if constexpr (MPIPE && !INJECT && N < 1024 && !ODDB) {
                 // The tile as a hand-placed pipeline (round 4).  A wave issues a DEPENDENT vector instruction every 8.3 cycles
                 // at best and an independent one every 4.3 (tools/ubench/valu_dep.hip); the six MFMAs of the chain are dependent
                 // (16 cycles apart), their operand rows take an LDS round trip, and a vector instruction must neither read the
@@ -2954,9 +2862,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
             }
             }
             const v2f c0 = mk(d.x, d.y), c1 = mk(d.z, d.w);
-            if (RENOISE && (INJECT || G >= NKEEP)) {
-                if (!INJECT) nscr[64 * G] = (f4){n0.x, n0.y, n1.x, n1.y};
-            } else {
+            if (!(RENOISE && INJECT)) {
                 nz[2 * G] = n0; nz[2 * G + 1] = n1;
             }
             acc[2 * G] = c0; acc[2 * G + 1] = c1;
@@ -2984,7 +2890,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         };
         DELAY_AT(4);
         STAMPF(11);
-        WAVE_PRIO(WOFDM_PRIO_TILES);
+        WAVE_PRIO(PRIO_TILES);
         if constexpr (FIR8) {
             if (B & 1) tiles(std::false_type{}, std::true_type{});
             else if (all_full) tiles(std::true_type{}, std::false_type{});
@@ -2993,7 +2899,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
             if (all_full) tiles(std::true_type{}, std::false_type{});
             else tiles(std::false_type{}, std::false_type{});
         }
-        WAVE_PRIO(WOFDM_PRIO_B3);
+        WAVE_PRIO(PRIO_LATENCY);
         STAMPF(12);
         DELAY_AT(5);
         if (tail_total > 0 && wv == 0 && !fold_tail) {
@@ -3032,19 +2938,14 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         float ps = ps2.x + ps2.y, pn = pn2.x + pn2.y;
         ps = wave_sum(ps); pn = wave_sum(pn);
         if (lane == 0) { sums_it[wv] = ps; sums_it[16 + wv] = pn; }
-        if constexpr (RENOISE) {
-            // the parked noise comes back HERE, after the FIR's registers have died: the HBM/L2
+        if constexpr (RENOISE && INJECT) {
+            // the injected noise comes back HERE, after the FIR's registers have died: the HBM/L2
             // latency of the reload runs under the wait at barrier 2 instead of opening phase C
 #pragma unroll
             for (int G = 0; G < NT; ++G) {
-                if (INJECT) {
-                    bool valid = 128 * G + jl < LW;
-                    if constexpr (LW_MIN > 0) valid = valid || 128 * (G + 1) <= LW_MIN;
-                    noise_pair(jw + 128 * G + jl, valid, valid, nz[2 * G], nz[2 * G + 1]);
-                } else if (G >= NKEEP) {
-                    const f4 t = nscr[64 * G];
-                    nz[2 * G] = mk(t.x, t.y); nz[2 * G + 1] = mk(t.z, t.w);
-                }
+                bool valid = 128 * G + jl < LW;
+                if constexpr (LW_MIN > 0) valid = valid || 128 * (G + 1) <= LW_MIN;
+                noise_pair(jw + 128 * G + jl, valid, valid, nz[2 * G], nz[2 * G + 1]);
             }
         }
         } else {
@@ -3203,7 +3104,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         STAMP(2);
         __syncthreads();                                                     // ---- barrier 2
         STAMP(3);
-        WAVE_PRIO(WOFDM_PRIO_C);
+        WAVE_PRIO(PRIO_LATENCY);
         DELAY_AT(7);
 
         // ------------------------------------------------------------ C: noise scale, Rx, FFT
@@ -3232,7 +3133,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         // for it in instantiations / branches of their own, the strides of C2, C4 and C5 carry none of it).
         // (Layout 15 -- the Tx-mask kernel, whose time goes into the mask stage -- measured nothing with it, -1 % at strides with an
         // incomplete group: it keeps its rows in order.  profiles/r04_rx_swizzle_ab.txt)
-        constexpr bool RXSWZ = (MDFT || MD8) && WOFDM_RX_SWIZZLE;
+        constexpr bool RXSWZ = MDFT || MD8;
         constexpr int rx_sw = RXSWZ ? 6 : 0;
         const int rx_len = FIR8 ? B : 2 * B, rx_xb = rx_len & ~7;
         const bool rx_part = RXSWZ && (rx_len & 7) != 0;
@@ -3661,7 +3562,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         }
         wave_sync();
         STAMPC(14);
-        WAVE_PRIO(WOFDM_PRIO_X);
+        WAVE_PRIO(PRIO_TRANSFORM);
         // the pilot is symbol slot 0 of wave 0, four subcarriers per lane; G = X0 / Y0 (X0 as the table's small integers:
         // the demapper's levels are scaled to match) goes out as one 16-byte row of real and one of imaginary parts
         auto pilot_mdft = [&]() {
@@ -3687,8 +3588,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                 post_flag(&flags[16], iter, lane);
             }
         };
-        (void)pilot_mdft;
-        if constexpr (MDFT && WOFDM_MDFT_PIPELINE) {
+        if constexpr (MDFT) {
             // the same pipeline as in phase A, one stage longer: behind the first-stage chain of symbol u the split of symbol u + 1's
             // received samples, behind that of symbol 3 the twiddle and split of symbol 0, then the second stage as there
             const mdft_consts dc = mdft_load(dce);
@@ -3735,30 +3635,10 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                     asm volatile(WOFDM_MMA_TAIL : "+v"(yr[u]), "+v"(yi[u]) : "v"(th[u]), "v"(tl[u]), "v"(dc.arh), "v"(dc.arl), "v"(dc.aih), "v"(dc.ail));
                 }
             }
-        } else if constexpr (MDFT) {
-            const mdft_consts dc = mdft_load(dce);
-            f4 tr[4], ti[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                uint32_t h[4], l[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) split_h(v[u][0][r], h[r], l[r]);
-                h8 xh = __builtin_bit_cast(h8, (u4){h[0], h[1], h[2], h[3]});
-                h8 xl = __builtin_bit_cast(h8, (u4){l[0], l[1], l[2], l[3]});
-                mma_operand_fence(xh, xl);
-                mma33(tr[u], ti[u], xl, dc.brh, xh, dc.brl, xh, dc.brh, xl, dc.bih, xh, dc.bil, xh, dc.bih);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                mdft_twiddle(tr[u], ti[u], dc.twr, dc.twi);
-                h8 th, tl;
-                mdft_split4(tr[u], ti[u], th, tl);
-                mma33(yr[u], yi[u], dc.arh, tl, dc.arl, th, dc.arh, th, dc.aih, tl, dc.ail, th, dc.aih, th);
-            }
         } else if constexpr (QW) fft_qw<-1>(v, row(usq), tw, llq);
         else fft_wave<N, -1, SPW>(v, fbw, B, tw, lane);     // v = Y[n]
         STAMPC(15);
-        WAVE_PRIO(WOFDM_PRIO_C);
+        WAVE_PRIO(PRIO_LATENCY);
 
         if constexpr (MDFT) {
             if (DUMP && p.dump.Y) {
@@ -3783,8 +3663,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                 }
         }
         if constexpr (MDFT) {
-            // (with the transforms as a pipeline the pilot wave has published its equaliser already: see the second stage above)
-            if (wv == 0 && !WOFDM_MDFT_PIPELINE) pilot_mdft();
+            // (the pilot wave has published its equaliser already: see the second stage above)
         } else if (QW && wv == 0) {
             // quarter-wave layout: the pilot symbol sits in lanes 0..15 of wave 0, and every other
             // wave waits for its equaliser.  Those 16 lanes only hand their Y0 and packed labels
@@ -3842,14 +3721,14 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         }
         DELAY_AT(8);
         STAMP(4);
-        WAVE_PRIO(WOFDM_PRIO_C);
+        WAVE_PRIO(PRIO_LATENCY);
         if constexpr (RELAXF) {
             if (wv != 0) wait_flag(&flags[16], iter, &flags[20]);                        // ---- "barrier" 3
         } else {
             __syncthreads();                                                 // ---- barrier 3
         }
         STAMP(5);
-        WAVE_PRIO(WOFDM_PRIO_D);
+        WAVE_PRIO(PRIO_LATENCY);
         DELAY_AT(9);
 
         // ------------------------------------------------------------ D: equalise, demap, count
@@ -4009,7 +3888,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         if (++fidx == F) { fidx = 0; next_cell(); }
     }
     if (cur_cell != 0xFFFFFFFFu) flush(cur_cell);
-    if constexpr (RELAXF && WOFDM_CHECKED_SYNC) {
+    if constexpr (RELAXF) {
         __syncthreads();
         if (tid == 0 && flags[20] != 0) atomicOr(p.status, 1u);   // host: results not to be used
     }
@@ -4285,81 +4164,44 @@ __global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
     }
 }
 
-template <int N, int K, int SPW, int VAR> wofdm_kernel_fn pick_mode(int mode)
+template <int N, int K, int LAY, int VAR> wofdm_kernel_fn pick_mode(int mode)
 {
-    switch (mode) {
-    case WOFDM_MODE_GEN: return wofdm_frames_kernel<N, K, SPW, false, false, VAR>;
-    case WOFDM_MODE_INJECT: return wofdm_frames_kernel<N, K, SPW, true, false, VAR>;
-    case WOFDM_MODE_DUMP_GEN: return wofdm_frames_kernel<N, K, SPW, false, true, VAR>;
-    case WOFDM_MODE_DUMP_INJECT: return wofdm_frames_kernel<N, K, SPW, true, true, VAR>;
+    if constexpr (wofdm_layout_built(LAY, N, VAR)) {
+        switch (mode) {
+        case WOFDM_MODE_GEN: return wofdm_frames_kernel<N, K, LAY, false, false, VAR>;
+        case WOFDM_MODE_INJECT: return wofdm_frames_kernel<N, K, LAY, true, false, VAR>;
+        case WOFDM_MODE_DUMP_GEN: return wofdm_frames_kernel<N, K, LAY, false, true, VAR>;
+        case WOFDM_MODE_DUMP_INJECT: return wofdm_frames_kernel<N, K, LAY, true, true, VAR>;
+        }
     }
     return nullptr;
 }
 
-template <int N, int K, int SPW> wofdm_kernel_fn pick_var(int mode, int var)
+template <int N, int K, int LAY> wofdm_kernel_fn pick_var(int mode, int var)
 {
     switch (var) {
-    case WOFDM_VAR_PLAIN: return pick_mode<N, K, SPW, WOFDM_VAR_PLAIN>(mode);
-    case WOFDM_VAR_ALLOC: return pick_mode<N, K, SPW, WOFDM_VAR_ALLOC>(mode);
-    case WOFDM_VAR_TXMASK:
-        if constexpr (SPW == 1 && N <= WOFDM_TXMASK_MAX_N) return pick_mode<N, K, SPW, WOFDM_VAR_TXMASK>(mode);
-        break;
-    case WOFDM_VAR_TXFFT:
-        if constexpr (SPW == 1 && N <= WOFDM_TXFFT_MAX_N) return pick_mode<N, K, SPW, WOFDM_VAR_TXFFT>(mode);
-        break;
+    case WOFDM_VAR_PLAIN: return pick_mode<N, K, LAY, WOFDM_VAR_PLAIN>(mode);
+    case WOFDM_VAR_ALLOC: return pick_mode<N, K, LAY, WOFDM_VAR_ALLOC>(mode);
+    case WOFDM_VAR_TXMASK: return pick_mode<N, K, LAY, WOFDM_VAR_TXMASK>(mode);
+    case WOFDM_VAR_TXFFT: return pick_mode<N, K, LAY, WOFDM_VAR_TXFFT>(mode);
     }
     return nullptr;
 }
 
-template <int N, int K> wofdm_kernel_fn pick_spw(int spw, int mode, int var)
+// every (layout, variant) wofdm_layout_built names for this N, and nothing else
+template <int N, int K, int... LAYS>
+wofdm_kernel_fn pick_layout(int layout, int mode, int var, std::integer_sequence<int, LAYS...>)
 {
-    if (spw == 1) return pick_var<N, K, 1>(mode, var);
-    if constexpr (N == 64 || N == 128) {
-        if (spw == 13 && var <= WOFDM_VAR_ALLOC)
-            return var ? pick_mode<N, K, 13, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 13, WOFDM_VAR_PLAIN>(mode);
-        if (spw == 14 && var <= WOFDM_VAR_ALLOC)
-            return var ? pick_mode<N, K, 14, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 14, WOFDM_VAR_PLAIN>(mode);
-        if (spw == 16 && var <= WOFDM_VAR_ALLOC)
-            return var ? pick_mode<N, K, 16, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 16, WOFDM_VAR_PLAIN>(mode);
-    }
-    if (spw == 9) {
-        if constexpr (N <= WOFDM_TXMASK_MAX_N) {
-            if (var == WOFDM_VAR_TXMASK) return pick_mode<N, K, 9, WOFDM_VAR_TXMASK>(mode);
-        }
-        if constexpr (N <= WOFDM_TXFFT_MAX_N) {
-            if (var == WOFDM_VAR_TXFFT) return pick_mode<N, K, 9, WOFDM_VAR_TXFFT>(mode);
-        }
-        return nullptr;
-    }
-    if constexpr (N <= 256) {
-        if (spw == 2) return pick_var<N, K, 2>(mode, var);
-    }
-    if constexpr (N >= 512) {
-        if (spw == 12 && var <= WOFDM_VAR_ALLOC)
-            return var ? pick_mode<N, K, 12, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 12, WOFDM_VAR_PLAIN>(mode);
-        if (spw == 8 && var <= WOFDM_VAR_ALLOC)
-            return var ? pick_mode<N, K, 8, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 8, WOFDM_VAR_PLAIN>(mode);
-    }
-    if constexpr (N == 256) {
-        if (spw == 15) return var == WOFDM_VAR_TXFFT ? pick_mode<N, K, 15, WOFDM_VAR_TXFFT>(mode) : nullptr;
-        if ((spw == 10 || spw == 11) && var <= WOFDM_VAR_ALLOC) {
-            if (spw == 10) return var ? pick_mode<N, K, 10, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 10, WOFDM_VAR_PLAIN>(mode);
-            return var ? pick_mode<N, K, 11, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 11, WOFDM_VAR_PLAIN>(mode);
-        }
-        if (spw >= 4 && spw <= 7 && var <= WOFDM_VAR_ALLOC) {
-            if (spw == 4) return var ? pick_mode<N, K, 4, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 4, WOFDM_VAR_PLAIN>(mode);
-            if (spw == 5) return var ? pick_mode<N, K, 5, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 5, WOFDM_VAR_PLAIN>(mode);
-            if (spw == 6) return var ? pick_mode<N, K, 6, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 6, WOFDM_VAR_PLAIN>(mode);
-            return var ? pick_mode<N, K, 7, WOFDM_VAR_ALLOC>(mode) : pick_mode<N, K, 7, WOFDM_VAR_PLAIN>(mode);
-        }
-    }
-    return nullptr;
+    wofdm_kernel_fn fn = nullptr;
+    ((layout == LAYS ? (void)(fn = pick_var<N, K, LAYS>(mode, var)) : (void)0), ...);
+    return fn;
 }
 
-template <int N> wofdm_kernel_fn pick(int k, int spw, int mode, int var)
+template <int N> wofdm_kernel_fn pick(int k, int layout, int mode, int var)
 {
     // (one constellation size per translation unit, see below)
-    return k == WOFDM_TU_K ? pick_spw<N, WOFDM_TU_K>(spw, mode, var) : nullptr;
+    if (k != WOFDM_TU_K) return nullptr;
+    return pick_layout<N, WOFDM_TU_K>(layout, mode, var, std::make_integer_sequence<int, WOFDM_LAYOUT_COUNT>{});
 }
 
 }  // namespace
@@ -4373,9 +4215,9 @@ template <int N> wofdm_kernel_fn pick(int k, int spw, int mode, int var)
 #define WOFDM_CAT2(a, b) a##b
 #define WOFDM_CAT(a, b) WOFDM_CAT2(a, b)
 
-wofdm_kernel_fn WOFDM_CAT(WOFDM_CAT(WOFDM_CAT(wofdm_select_kernel_n, WOFDM_TU_N), _k), WOFDM_TU_K)(int spw, int mode, int var)
+wofdm_kernel_fn WOFDM_CAT(WOFDM_CAT(WOFDM_CAT(wofdm_select_kernel_n, WOFDM_TU_N), _k), WOFDM_TU_K)(int layout, int mode, int var)
 {
-    return pick<WOFDM_TU_N>(WOFDM_TU_K, spw, mode, var);
+    return pick<WOFDM_TU_N>(WOFDM_TU_K, layout, mode, var);
 }
 
 #if WOFDM_TU_K == 2
