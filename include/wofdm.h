@@ -111,7 +111,7 @@ int wofdm_plan_destroy(wofdm_plan *plan);
  * us -- unconfirmed outside these measurements).  They contain no such instruction themselves.  What the library
  * does: every launch waits (on the device, through an event) for the previous launch this process made on that
  * GPU, whatever plan or stream; the synchronous entry points that run other kernels (wofdm_interference,
- * wofdm_tx_psd) hold the same gate.  What the CALLER must ensure: no kernel of its own (other libraries, other
+ * wofdm_tx_psd, wofdm_tx_psd_batch) hold the same gate.  What the CALLER must ensure: no kernel of its own (other libraries, other
  * streams) and no other process runs on the device while a frame launch is in flight -- one process per GPU,
  * synchronise before handing the GPU to other work (bench.py, distributed.py do).  Where that cannot be
  * guaranteed (a shared GPU), select the VALU transforms, wofdm_plan_set_option(plan, WOFDM_OPT_DFT_VALU, 1): those
@@ -223,6 +223,21 @@ int wofdm_interference(const wofdm_cfg *cfg, int device, const float *w_tx, cons
  * count (full slices + 1).  Uses n_fft, cp, cs of cfg; n_fft in {64, 128, 256}.  Synchronous. */
 int wofdm_tx_psd(const wofdm_cfg *cfg, int device, const float *w_tx, const float *X, int no_symbols,
                  int overlap, float *psd);
+
+/* The same estimate for a batch of jobs in one call, n_fft in {64, 128, 256, 512, 1024} (transform length
+ * 8 n_fft up to 8192).  Job j transmits symbol block jobs[j].block of X[n_blocks][no_symbols][n_fft][2] (host)
+ * with its own cp, cs (P_j = n_fft + cp + cs), overlap (0 <= 2 overlap <= P_j) and Tx window; w_tx holds the
+ * jobs' windows concatenated (P_0 values, then P_1, ...).  psd[n_jobs][8 n_fft] (host): per job the undivided
+ * slice sums, fftshift-ed, as wofdm_tx_psd (the caller divides by full slices + 1).  The sums are formed in a
+ * fixed order: repeated calls give identical results.  Synchronous; holds the gate of the entry points above. */
+typedef struct wofdm_psd_job {
+    int32_t block;            /* symbol block of X this job transmits */
+    int32_t cp, cs;           /* P_j = n_fft + cp + cs */
+    int32_t overlap;          /* overlapping tail samples: tail_tx or 0 */
+} wofdm_psd_job;
+int wofdm_tx_psd_batch(int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs,
+                       const float *w_tx, int32_t n_blocks, int32_t no_symbols, const float *X,
+                       float *psd);
 
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

@@ -29,7 +29,7 @@ EXPORTS = (
     "wofdm_plan_launch_injected", "wofdm_plan_dump_frame", "wofdm_plan_info", "wofdm_run",
     "wofdm_run_injected", "wofdm_philox_kat", "wofdm_plan_set_allocation",
     "wofdm_plan_set_tx_mask", "wofdm_plan_status", "wofdm_plan_kernel_id", "wofdm_plan_set_option",
-    "wofdm_interference", "wofdm_tx_psd",
+    "wofdm_interference", "wofdm_tx_psd", "wofdm_tx_psd_batch",
 )
 
 
@@ -62,6 +62,11 @@ class Cfg(C.Structure):
     @property
     def n_cells(self):
         return self.n_window_pairs * self.n_snr * self.n_channels
+
+
+class PsdJob(C.Structure):
+    """Mirror of ``wofdm_psd_job``."""
+    _fields_ = [(n, C.c_int32) for n in ("block", "cp", "cs", "overlap")]
 
 
 class Dump(C.Structure):
@@ -127,6 +132,8 @@ def load():
     L.wofdm_philox_kat.argtypes = [C.c_int, vp, vp, vp]
     L.wofdm_interference.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp]
     L.wofdm_tx_psd.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, C.c_int, C.c_int, vp]
+    i32 = C.c_int32
+    L.wofdm_tx_psd_batch.argtypes = [i32, C.c_int, i32, vp, vp, i32, i32, vp, vp]
     _LIB = L
     return L
 

@@ -3,6 +3,7 @@
 #include "../../include/wofdm.h"
 #include "wofdm_kernel.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1017,6 +1018,89 @@ int wofdm_tx_psd(const wofdm_cfg *cfg, int device, const float *w_tx, const floa
     if (d_X) (void)hipFree(d_X);
     if (d_x) (void)hipFree(d_x);
     if (d_psd) (void)hipFree(d_psd);
+    return rc;
+}
+
+int wofdm_tx_psd_batch(int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs, const float *w_tx,
+                       int32_t n_blocks, int32_t no_symbols, const float *X, float *psd)
+{
+    if (!jobs || !w_tx || !X || !psd) return fail(WOFDM_E_INVALID, "NULL argument");
+    const int N = n_fft;
+    if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
+        return fail(WOFDM_E_UNSUPPORTED, "wofdm_tx_psd_batch is built for n_fft in {64,128,256,512,1024}");
+    if (n_jobs < 1 || n_jobs > 65535 || n_blocks < 1 || no_symbols < 1)
+        return fail(WOFDM_E_INVALID, "bad n_jobs / n_blocks / no_symbols");
+    const int FL = 8 * N, per_item = wofdm_psd_batch_slices(N);
+    std::vector<wofdm_bjob> hj((size_t)n_jobs);
+    std::vector<wofdm_bitem> hi;
+    int64_t n_w = 0, n_x = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const wofdm_psd_job &q = jobs[j];
+        const int P = N + q.cp + q.cs;
+        if (q.block < 0 || q.block >= n_blocks || q.cp < 0 || q.cs < 0 || q.cp > N || q.cs > N || q.overlap < 0 ||
+            2 * q.overlap > P)
+            return fail(WOFDM_E_INVALID, "job %d: bad block / cp / cs / overlap", j);
+        const int64_t len = q.overlap + (int64_t)no_symbols * (P - q.overlap);
+        if (len > INT32_MAX - 2 * (int64_t)FL) return fail(WOFDM_E_INVALID, "job %d: waveform of %lld samples", j, (long long)len);
+        wofdm_bjob &b = hj[(size_t)j];
+        b.block = q.block; b.cp = q.cp; b.cs = q.cs; b.overlap = q.overlap;
+        b.w_off = (int32_t)n_w; b.len = (int32_t)len; b.x_off = n_x;
+        const int n_sl = (int)((len + FL - 1) / FL);
+        b.item0 = (int32_t)hi.size();
+        for (int s0 = 0; s0 < n_sl; s0 += per_item) hi.push_back({j, s0, std::min(per_item, n_sl - s0), 0});
+        b.n_items = (int32_t)hi.size() - b.item0;
+        n_w += P; n_x += len;
+        if (n_w > INT32_MAX) return fail(WOFDM_E_INVALID, "windows too long");
+    }
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev)
+        return fail(WOFDM_E_HIP, "device %d not available (%d visible); there is no CPU fallback", device, ndev);
+    HIP_TRY(hipSetDevice(device));
+    const size_t n_X = (size_t)n_blocks * no_symbols * N, n_items = hi.size();
+    float *d_w = nullptr, *d_part = nullptr, *d_psd = nullptr;
+    float2 *d_X = nullptr, *d_x = nullptr;
+    wofdm_bjob *d_jobs = nullptr;
+    wofdm_bitem *d_items = nullptr;
+    int rc = WOFDM_OK;
+    do {
+        if (hipMalloc(&d_w, (size_t)n_w * 4) != hipSuccess || hipMalloc(&d_X, n_X * 8) != hipSuccess ||
+            hipMalloc(&d_x, (size_t)n_x * 8) != hipSuccess || hipMalloc(&d_part, n_items * FL * 4) != hipSuccess ||
+            hipMalloc(&d_psd, (size_t)n_jobs * FL * 4) != hipSuccess ||
+            hipMalloc(&d_jobs, hj.size() * sizeof(wofdm_bjob)) != hipSuccess ||
+            hipMalloc(&d_items, n_items * sizeof(wofdm_bitem)) != hipSuccess) {
+            rc = fail(WOFDM_E_NOMEM, "device allocation failed"); break;
+        }
+        if (hipMemcpy(d_w, w_tx, (size_t)n_w * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_X, X, n_X * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_jobs, hj.data(), hj.size() * sizeof(wofdm_bjob), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_items, hi.data(), n_items * sizeof(wofdm_bitem), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemset(d_x, 0, (size_t)n_x * 8) != hipSuccess) {
+            rc = fail(WOFDM_E_HIP, "upload failed"); break;
+        }
+        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        (void)hipDeviceSynchronize();
+        hipError_t e = hipErrorInvalidValue;
+        const int ni = (int)n_items;
+        if (N == 64) e = wofdm_psd_batch_launch_n64(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+        if (N == 128) e = wofdm_psd_batch_launch_n128(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+        if (N == 256) e = wofdm_psd_batch_launch_n256(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+        if (N == 512) e = wofdm_psd_batch_launch_n512(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+        if (N == 1024) e = wofdm_psd_batch_launch_n1024(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+        if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(psd, d_psd, (size_t)n_jobs * FL * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+            rc = fail(WOFDM_E_HIP, "PSD kernels or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
+            break;
+        }
+    } while (0);
+    if (d_w) (void)hipFree(d_w);
+    if (d_X) (void)hipFree(d_X);
+    if (d_x) (void)hipFree(d_x);
+    if (d_part) (void)hipFree(d_part);
+    if (d_psd) (void)hipFree(d_psd);
+    if (d_jobs) (void)hipFree(d_jobs);
+    if (d_items) (void)hipFree(d_items);
     return rc;
 }
 

@@ -357,3 +357,29 @@ WOFDM_INTERF_DECL(1024);
 WOFDM_PSD_DECL(64);
 WOFDM_PSD_DECL(128);
 WOFDM_PSD_DECL(256);
+
+// Tx waveform + averaged periodogram for a batch of jobs (wofdm_tx_psd_batch), every N.  A job's waveform sits at
+// x + x_off (len samples); its periodogram is summed by the work items item0 ... item0 + n_items - 1 (one workgroup
+// each, consecutive slices), whose partial spectra a second pass adds in that order.
+struct wofdm_bjob {
+    int32_t block, cp, cs, overlap;   // symbol block of X, CP, CS, overlapping tail samples
+    int32_t w_off, len;               // offset of the job's Tx window in w_tx; waveform length overlap + S (P - overlap)
+    int32_t item0, n_items;
+    int64_t x_off;
+};
+struct wofdm_bitem {
+    int32_t job, slice0, n_slices, pad;
+};
+// transforms of 1024 points (FL = 8 N > 1024: R = FL / 1024 decimated sub-sequences of a slice, one wave each) or of FL
+// points (R = 1); 8 waves per workgroup = 8 / R slices at a time, 4 rounds per work item
+__host__ __device__ constexpr int wofdm_psd_batch_r(int n_fft) { return 8 * n_fft > 1024 ? 8 * n_fft / 1024 : 1; }
+__host__ __device__ constexpr int wofdm_psd_batch_slices(int n_fft) { return 4 * (8 / wofdm_psd_batch_r(n_fft)); }
+#define WOFDM_PSD_BATCH_DECL(n)                                                                                       \
+    hipError_t wofdm_psd_batch_launch_n##n(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs,           \
+                                           const wofdm_bitem *items, const float *wtx, const float2 *X, float2 *x,    \
+                                           float *partial, float *psd, hipStream_t s)
+WOFDM_PSD_BATCH_DECL(64);
+WOFDM_PSD_BATCH_DECL(128);
+WOFDM_PSD_BATCH_DECL(256);
+WOFDM_PSD_BATCH_DECL(512);
+WOFDM_PSD_BATCH_DECL(1024);

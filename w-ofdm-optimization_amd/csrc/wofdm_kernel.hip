@@ -4156,6 +4156,200 @@ __global__ void __launch_bounds__(512) wofdm_psd_kernel(const float2 *__restrict
     }
 }
 
+// The same two steps for a batch of jobs at every N (wofdm_tx_psd_batch).  The waveform kernel: grid (symbol groups,
+// jobs), one wave per symbol of the job's block, each job with its own cp, cs, overlap, window and waveform row; the
+// overlapping samples as above (two addends onto a zeroed row).  LDS: twiddles [N] + one scratch row [N] per wave
+// (N = 1024: 9 x 8 KB).
+template <int N> struct bwave_geo {
+    static constexpr int WAVES = N >= 512 ? 8 : 16;
+};
+template <int N>
+__global__ void __launch_bounds__(bwave_geo<N>::WAVES * 64)
+wofdm_txwave_batch_kernel(const wofdm_bjob *__restrict__ jobs, int no_symbols, const float *__restrict__ g_wtx,
+                          const float2 *__restrict__ X, float2 *__restrict__ x)
+{
+    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ, WAVES = bwave_geo<N>::WAVES;
+    constexpr bool FULL = geo<N>::FULL;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    v2f *scr = tw + N + (size_t)wv * N;
+    fill_twiddles<N>(tw, tid, WAVES * 64);
+    __syncthreads();
+    const wofdm_bjob jb = jobs[blockIdx.y];
+    const int s = blockIdx.x * WAVES + wv;
+    if (s >= no_symbols) return;
+    const float2 *Xs = X + ((size_t)jb.block * no_symbols + s) * N;
+    v2f v[1][BPL][4];
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            v[0][q][r] = mk(0.f, 0.f);
+            if (FULL || lane + 64 * q < NQ) v[0][q][r] = ldg2(Xs + lane + 64 * q + r * NQ);
+        }
+    fft_wave<N, +1, 1>(v, scr, 0, tw, lane);                    // N x[t]
+    const int Bo = N + jb.cp + jb.cs - jb.overlap;
+    const float *wtx = g_wtx + jb.w_off;
+    float2 *out = x + jb.x_off + (size_t)s * Bo;
+    auto put = [&](int i, v2f val) {
+        val = val * (wtx[i] * (1.0f / (float)N));
+        if (i < jb.overlap || i >= Bo) {                         // shared with a neighbour symbol
+            atomicAdd(&out[i].x, val.x);
+            atomicAdd(&out[i].y, val.y);
+        } else {
+            out[i] = make_float2(val.x, val.y);
+        }
+    };
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (!(FULL || lane + 64 * q < NQ)) continue;
+            const int t = lane + 64 * q + r * NQ;
+            put(t + jb.cp, v[0][q][r]);
+            if (t >= N - jb.cp) put(t + jb.cp - N, v[0][q][r]);
+            if (t < jb.cs) put(t + jb.cp + N, v[0][q][r]);
+        }
+}
+
+// Periodogram of a batch: one workgroup (8 waves) per work item, i.e. up to wofdm_psd_batch_slices(N) consecutive
+// FL-sample slices of one job.  FL <= 1024 (R = 1): a wave transforms a whole slice, 8 slices at a time.  FL = 1024 R,
+// R = 2, 4, 8: the R waves of a group transform the decimated sub-sequences x[R m + h] of one slice (1024 points each,
+// E_h), put E_h into their scratch rows and, behind a barrier, combine them:  X[k' + 1024 c] = sum_h W_R^(h c)
+// (W_FL^(h k') E_h[k']).  Wave h of the group owns k' = h 1024 / R + lane + 64 j (j < 16 / R), i.e. 16 outputs per lane,
+// whose twiddles it keeps in registers; its loads of the R rows are consecutive 8-byte words across the lanes, as are the
+// stores of E_h (ds_read_b64 / ds_write_b64 without bank conflicts).  Every lane adds |X|^2 over its slices in a fixed
+// order, the groups' sums are added in group order, and the workgroup writes one unshifted partial spectrum [FL];
+// wofdm_psd_reduce_kernel adds a job's partials in item order -- no atomics: bitwise repeatable.
+template <int FL>
+__global__ void __launch_bounds__(512) wofdm_psd_batch_kernel(const wofdm_bjob *__restrict__ jobs,
+                                                              const wofdm_bitem *__restrict__ items,
+                                                              const float2 *__restrict__ x, float *__restrict__ partial)
+{
+    constexpr int R = wofdm_psd_batch_r(FL / 8), M = FL / R, G = 8 / R, ROUNDS = wofdm_psd_batch_slices(FL / 8) / G;
+    constexpr int BPL = geo<M>::BPL, NQ = geo<M>::NQ, JJ = M / (64 * R), NACC = R > 1 ? JJ * R : 4 * BPL;
+    static_assert(geo<M>::FULL && (R == 1 || M == 1024), "512- or 1024-point transforms");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    v2f *rows = tw + M;                                           // [8][M]: scratch of wave w = E_h of group w / R
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = wv / R, h = wv % R;
+    fill_twiddles<M>(tw, tid, 512);
+    const wofdm_bitem it = items[blockIdx.x];
+    const wofdm_bjob jb = jobs[it.job];
+    const float2 *xj = x + jb.x_off;
+    v2f cw[JJ][R > 1 ? R - 1 : 1];                                // W_FL^(t k'), t = 1 .. R-1
+    if constexpr (R > 1) {
+#pragma unroll
+        for (int j = 0; j < JJ; ++j)
+#pragma unroll
+            for (int t = 1; t < R; ++t) {
+                const int kp = h * (M / R) + lane + 64 * j;
+                float sv, cv;
+                sincospif(-2.0f * (float)(t * kp) / (float)FL, &sv, &cv);
+                cw[j][t - 1] = mk(cv, sv);
+            }
+    }
+    float acc[NACC];
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) acc[a] = 0.f;
+    __syncthreads();
+    v2f *own = rows + (size_t)wv * M;
+    for (int rd = 0; rd < ROUNDS; ++rd) {
+        const int sl = rd * G + g;
+        const bool live = sl < it.n_slices;                       // uniform over the group
+        if (live) {
+            const int base = (it.slice0 + sl) * FL + h;
+            v2f v[1][BPL][4];
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int idx = base + R * (lane + 64 * q + r * NQ);
+                    v[0][q][r] = idx < jb.len ? ldg2(xj + idx) : mk(0.f, 0.f);
+                }
+            fft_wave<M, -1, 1>(v, own, 0, tw, lane);
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if constexpr (R == 1) acc[4 * q + r] += v[0][q][r].x * v[0][q][r].x + v[0][q][r].y * v[0][q][r].y;
+                    else own[lane + 64 * q + r * NQ] = v[0][q][r];
+                }
+        }
+        if constexpr (R > 1) {
+            __syncthreads();
+            if (live) {
+                const v2f *gs = rows + (size_t)g * R * M;
+#pragma unroll
+                for (int j = 0; j < JJ; ++j) {
+                    const int kp = h * (M / R) + lane + 64 * j;
+                    v2f y[R];
+#pragma unroll
+                    for (int t = 0; t < R; ++t) y[t] = gs[t * M + kp];
+#pragma unroll
+                    for (int t = 1; t < R; ++t) y[t] = cmul(y[t], cw[j][t - 1]);
+                    v2f X_[R];
+                    if constexpr (R == 2) {
+                        X_[0] = y[0] + y[1];
+                        X_[1] = y[0] - y[1];
+                    } else if constexpr (R == 4) {
+                        v2f u[4] = {y[0], y[1], y[2], y[3]};
+                        radix4<-1>(u);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) X_[c] = u[c];
+                    } else {
+                        v2f u[2][4];                              // u[q][r] = y_t, t = q + 2 r
+#pragma unroll
+                        for (int t = 0; t < 8; ++t) u[t & 1][t >> 1] = y[t];
+                        dft8<-1>(u);                              // u[q][r] = X_c, c = r + 4 q
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) X_[c] = u[c >> 2][c & 3];
+                    }
+#pragma unroll
+                    for (int c = 0; c < R; ++c) acc[j * R + c] += X_[c].x * X_[c].x + X_[c].y * X_[c].y;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    float *red = reinterpret_cast<float *>(rows);                 // [G][FL] floats over the scratch rows
+    if constexpr (R == 1) {
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[g * FL + lane + 64 * q + r * NQ] = acc[4 * q + r];
+    } else {
+#pragma unroll
+        for (int j = 0; j < JJ; ++j)
+#pragma unroll
+            for (int c = 0; c < R; ++c) red[g * FL + h * (M / R) + lane + 64 * j + M * c] = acc[j * R + c];
+    }
+    __syncthreads();
+    for (int k = tid; k < FL; k += 512) {
+        float t = 0.f;
+        for (int gg = 0; gg < G; ++gg) t += red[gg * FL + k];
+        partial[(size_t)blockIdx.x * FL + k] = t;
+    }
+}
+
+// psd[job][8 N] = sum over the job's work items, in item order, of their partial spectra; fftshift-ed
+template <int FL>
+__global__ void __launch_bounds__(256) wofdm_psd_reduce_kernel(const wofdm_bjob *__restrict__ jobs,
+                                                               const float *__restrict__ partial, float *__restrict__ psd)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= FL) return;
+    const wofdm_bjob jb = jobs[blockIdx.y];
+    float t = 0.f;
+    for (int i = 0; i < jb.n_items; ++i) t += partial[(size_t)(jb.item0 + i) * FL + k];
+    psd[(size_t)blockIdx.y * FL + ((k + FL / 2) & (FL - 1))] = t;
+}
+
 __global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
 {
     if (threadIdx.x == 0) {
@@ -4255,6 +4449,31 @@ hipError_t WOFDM_CAT(wofdm_psd_launch_n, WOFDM_TU_N)(int P, int mu, int rho, int
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(wofdm_txwave_kernel<N>, dim3((no_symbols + 15) / 16), dim3(1024), lds_a, s, wp, wtx, X);
     hipLaunchKernelGGL(wofdm_psd_kernel<FL>, dim3(1), dim3(512), lds_b, s, (const float2 *)x, len, (len + FL - 1) / FL, psd);
+    return hipGetLastError();
+}
+#endif
+
+#if WOFDM_TU_K == 2
+// the same for a batch of jobs (wofdm_tx_psd_batch), every DFT length, in the k = 2 translation units; x zeroed by the
+// caller, partial [n_items][8 N]
+hipError_t WOFDM_CAT(wofdm_psd_batch_launch_n, WOFDM_TU_N)(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs,
+                                                           const wofdm_bitem *items, const float *wtx, const float2 *X,
+                                                           float2 *x, float *partial, float *psd, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N, FL = 8 * N, M = FL / wofdm_psd_batch_r(N), WW = bwave_geo<N>::WAVES;
+    const size_t lds_a = 8 * (size_t)N * (1 + WW), lds_b = 8 * (size_t)M * 9;
+    static_assert(8 * N * (1 + WW) <= 160 * 1024 && 8 * M * 9 <= 160 * 1024, "LDS");
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txwave_batch_kernel<N>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_psd_batch_kernel<FL>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_txwave_batch_kernel<N>, dim3((no_symbols + WW - 1) / WW, n_jobs), dim3(WW * 64), lds_a, s, jobs,
+                       no_symbols, wtx, X, x);
+    hipLaunchKernelGGL(wofdm_psd_batch_kernel<FL>, dim3(n_items), dim3(512), lds_b, s, jobs, items, (const float2 *)x, partial);
+    hipLaunchKernelGGL(wofdm_psd_reduce_kernel<FL>, dim3((FL + 255) / 256, n_jobs), dim3(256), 0, s, jobs,
+                       (const float *)partial, psd);
     return hipGetLastError();
 }
 #endif

@@ -66,25 +66,65 @@ def psd_estimate(x, fft_len):
     return np.fft.fftshift(acc) / (n_full + 1)
 
 
+def _full_grid(n, X, guard_band=GUARD_BAND):
+    """[N - 2 gb, S] symbols -> [S, N] complex64 grid, zeros on the unloaded bins"""
+    X = np.asarray(X)
+    grid = np.zeros((X.shape[1], n), dtype=np.complex64)
+    grid[:, allocation_index(n, guard_band)] = X.T
+    return grid
+
+
 def psd_estimate_gpu(st, X, w_tx, overlap, guard_band=GUARD_BAND, device=0):
     """``psd_estimate(overlap_and_add(tx_symbols(st, X, w_tx), overlap), 8 N)`` on the GPU
     (``wofdm_tx_psd``: the frame kernel's Tx half on the given symbols + the averaged periodogram).
-    X: [N - 2 gb, no_symbols] like ``draw_symbols``.  No CPU fallback; N in {64, 128, 256}."""
+    X: [N - 2 gb, no_symbols] like ``draw_symbols``.  No CPU fallback; N in {64, 128, 256} by
+    ``wofdm_tx_psd``, N = 512 / 1024 by ``wofdm_tx_psd_batch`` (one job)."""
     import ctypes as C
     from . import _lib
     from .simulation import make_cfg
     n = st.n_fft
-    X = np.asarray(X)
-    grid = np.zeros((X.shape[1], n), dtype=np.complex64)
-    grid[:, allocation_index(n, guard_band)] = X.T
+    grid = _full_grid(n, X, guard_band)
+    if n > 256:
+        return tx_psd_batch_gpu(n, grid[None], [(0, st.cp, st.cs, overlap, w_tx)], device)[0]
     w = _lib.f32(np.asarray(w_tx).reshape(-1), (st.sym_len,))
     cfg = make_cfg(st, 4, 16, 1, 1, 1, 1)
     out = np.zeros(8 * n, dtype=np.float32)
     gf = _lib.c64_as_f32(grid)
     _lib.check(_lib.load().wofdm_tx_psd(C.byref(cfg), int(device), w.ctypes.data, gf.ctypes.data,
-                                        int(X.shape[1]), int(overlap), out.ctypes.data))
-    length = overlap + X.shape[1] * (st.sym_len - overlap)
+                                        int(grid.shape[0]), int(overlap), out.ctypes.data))
+    length = overlap + grid.shape[0] * (st.sym_len - overlap)
     return out.astype(np.float64) / (length // (8 * n) + 1)
+
+
+def tx_psd_batch_gpu(n_fft, grids, jobs, device=0, divide=True):
+    """Averaged periodograms of many Tx waveforms in one ``wofdm_tx_psd_batch`` call, any N in
+    {64, ..., 1024}.  grids: [n_blocks, no_symbols, N] complex symbols on every bin (as given);
+    jobs: sequence of (block, cp, cs, overlap, w_tx), w_tx of length N + cp + cs.  Returns
+    [n_jobs, 8 N] float64: ``psd_estimate(overlap_and_add(...), 8 N)`` of each job's waveform, i.e.
+    the kernel's slice sums divided by the reference's slice count (length // 8 N + 1); with
+    divide=False the undivided float32 sums.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    n = int(n_fft)
+    grids = np.asarray(grids)
+    if grids.ndim != 3 or grids.shape[2] != n:
+        raise ValueError("grids must be [n_blocks, no_symbols, %d], got %s" % (n, grids.shape))
+    n_blocks, no_symbols = grids.shape[:2]
+    jobs = list(jobs)
+    cj = (_lib.PsdJob * max(1, len(jobs)))()
+    wins, lengths = [], []
+    for j, (block, cp, cs, overlap, w) in enumerate(jobs):
+        cj[j].block, cj[j].cp, cj[j].cs, cj[j].overlap = int(block), int(cp), int(cs), int(overlap)
+        wins.append(_lib.f32(np.asarray(w).reshape(-1), (n + cp + cs,)))
+        lengths.append(overlap + no_symbols * (n + cp + cs - overlap))
+    w_all = _lib.f32(np.concatenate(wins) if wins else np.zeros(1))
+    gf = _lib.c64_as_f32(grids)
+    out = np.zeros((max(1, len(jobs)), 8 * n), dtype=np.float32)
+    _lib.check(_lib.load().wofdm_tx_psd_batch(n, int(device), len(jobs), C.addressof(cj), w_all.ctypes.data,
+                                              int(n_blocks), int(no_symbols), gf.ctypes.data, out.ctypes.data))
+    if not divide:
+        return out
+    return out.astype(np.float64) / (np.array(lengths, dtype=np.int64) // (8 * n) + 1)[:, None]
 
 
 def analytical_psd(st, w_tx, sampling_period, guard_band=GUARD_BAND, fft_len=None):
@@ -113,25 +153,23 @@ def analytical_psd(st, w_tx, sampling_period, guard_band=GUARD_BAND, fft_len=Non
             spectrum(np.ones(st.sym_len), n + cp, (n + cp, cp, 0.0)))
 
 
-def estimate_obr(st, w_tx, samp_period=200e-9, X=None, rng=None, gpu=False):
-    """``wOFDMSystem.estimate_obr`` (lines 216-296): three dicts (optimised window, RC window,
-    plain CP-OFDM) with the reference's keys.  gpu=True: waveform and periodogram by ``wofdm_tx_psd``."""
+def _obr_windows(st, w_tx):
+    """(window, overlap) of the three estimates of estimate_obr: optimised, RC, plain CP-OFDM"""
+    overlap = st.tail_tx if st.system in ("wtx", "CPwtx", "WOLA", "CPW") else 0
+    return ((np.asarray(w_tx, dtype=np.float64), overlap), (V.tx_rc_window(st), overlap),
+            (np.ones(st.sym_len), 0))
+
+
+def _obr_dicts(st, w_tx, samp_period, ests):
+    """the three result dicts of estimate_obr from the three periodograms"""
     n = st.n_fft
     fft_len = 8 * n
-    X = draw_symbols(n, rng) if X is None else np.asarray(X)
-    w_tx = np.asarray(w_tx, dtype=np.float64)
-    overlap = st.tail_tx if st.system in ("wtx", "CPwtx", "WOLA", "CPW") else 0
-    x_opt = overlap_and_add(tx_symbols(st, X, w_tx), overlap)
-    x_rc = overlap_and_add(tx_symbols(st, X, V.tx_rc_window(st)), overlap)
-    x_cp = tx_symbols(st, X, np.ones(st.sym_len)).reshape(-1)
     f_axis = np.linspace(-.5, .5 - 1 / fft_len, fft_len) / 200e-9
     interp = fft_len / n
     gb = int(interp * GUARD_BAND)
-    S = analytical_psd(st, w_tx, samp_period, GUARD_BAND, fft_len)
+    S = analytical_psd(st, np.asarray(w_tx, dtype=np.float64), samp_period, GUARD_BAND, fft_len)
     out = []
-    wins = {"opt": (w_tx, overlap), "rc": (V.tx_rc_window(st), overlap), "cp": (np.ones(st.sym_len), 0)}
-    for tag, x, s in (("opt", x_opt, S[0]), ("rc", x_rc, S[1]), ("cp", x_cp, S[2])):
-        est = psd_estimate_gpu(st, X, *wins[tag]) if gpu else psd_estimate(x, fft_len)
+    for tag, est, s in zip(("opt", "rc", "cp"), ests, S):
         out.append({"X_est_" + tag: est, "S_" + tag: s, "f_axis": f_axis,
                     "obr_" + tag: np.mean(np.hstack((est[:gb], est[-gb:]))),
                     "mf_band_" + tag: np.hstack((est[gb:fft_len // 2],
@@ -139,10 +177,26 @@ def estimate_obr(st, w_tx, samp_period=200e-9, X=None, rng=None, gpu=False):
     return tuple(out)
 
 
-def timefreq_fun(data, rng=None):
-    """Work item of ``-m run_timefreq`` (lines 17-76): data = (system, dft_len, cp_len, tail_tx,
-    tail_rx, window_path, folder_path)."""
-    system, n_fft, cp, tail_tx, tail_rx, window_path, folder_path = data
+def estimate_obr(st, w_tx, samp_period=200e-9, X=None, rng=None, gpu=False):
+    """``wOFDMSystem.estimate_obr`` (lines 216-296): three dicts (optimised window, RC window,
+    plain CP-OFDM) with the reference's keys.  gpu=True: waveform and periodogram on the GPU,
+    ``wofdm_tx_psd`` per window at N <= 256, one ``wofdm_tx_psd_batch`` call for the three at
+    N = 512 / 1024."""
+    n = st.n_fft
+    fft_len = 8 * n
+    X = draw_symbols(n, rng) if X is None else np.asarray(X)
+    wins = _obr_windows(st, w_tx)
+    if not gpu:
+        ests = [psd_estimate(overlap_and_add(tx_symbols(st, X, w), ov), fft_len) for w, ov in wins]
+    elif n <= 256:
+        ests = [psd_estimate_gpu(st, X, w, ov) for w, ov in wins]
+    else:
+        ests = list(tx_psd_batch_gpu(n, _full_grid(n, X)[None], [(0, st.cp, st.cs, ov, w) for w, ov in wins]))
+    return _obr_dicts(st, w_tx, samp_period, ests)
+
+
+def _timefreq_setup(system, n_fft, cp, tail_tx, tail_rx, window_path):
+    """structure and Tx window of a ``-m run_timefreq`` work item (lines 17-61)"""
     st = V.make_structure(system, n_fft, cp, tail_tx if system in V.TX_WINDOWED else 0,
                           tail_rx if system in V.RX_WINDOWED else 0)
     if system in V.TX_WINDOWED:
@@ -151,10 +205,50 @@ def timefreq_fun(data, rng=None):
         w_tx = V.expand_tx_window(st, xt)
     else:
         w_tx = np.ones(st.sym_len)
-    opt, rc, cpd = estimate_obr(st, w_tx, 200e-9, rng=rng)
+    return st, w_tx
+
+
+def _timefreq_save(folder_path, system, cp, opt, rc, cpd):
     path = os.path.join(folder_path, "timefreq")
     os.makedirs(path, exist_ok=True)
     np.savez(os.path.join(path, "opt_%s_%d.npz" % (system, cp)), **opt)
     np.savez(os.path.join(path, "rc_%s_%d.npz" % (system, cp)), **rc)
     np.savez(os.path.join(path, "CP_%d.npz" % cp), **cpd)
+
+
+def timefreq_fun(data, rng=None):
+    """Work item of ``-m run_timefreq`` (lines 17-76): data = (system, dft_len, cp_len, tail_tx,
+    tail_rx, window_path, folder_path)."""
+    system, n_fft, cp, tail_tx, tail_rx, window_path, folder_path = data
+    st, w_tx = _timefreq_setup(system, n_fft, cp, tail_tx, tail_rx, window_path)
+    opt, rc, cpd = estimate_obr(st, w_tx, 200e-9, rng=rng)
+    _timefreq_save(folder_path, system, cp, opt, rc, cpd)
     return opt, rc, cpd
+
+
+def run_timefreq(cp_list, sys_list, window_path, folder_path, n_fft=256, rng=None, gpu=False):
+    """``-m run_timefreq`` (wofdm_optimization.py:133-154): the work item of every (system, CP),
+    systems outer, tails 8 / 10, the same ``timefreq/`` files.  The symbols are drawn per item in
+    that order from ``rng``, as successive ``timefreq_fun`` calls with it would.  gpu=True: all
+    3 x len(sys_list) x len(cp_list) periodograms in ONE ``wofdm_tx_psd_batch`` call.  Returns
+    {(system, cp): (opt, rc, cp_dict)}."""
+    items = [(system, cp) for system in sys_list for cp in cp_list]
+    out = {}
+    if not gpu:
+        for system, cp in items:
+            data = (system, n_fft, cp, 8 if system in V.TX_WINDOWED else 0,
+                    10 if system in V.RX_WINDOWED else 0, window_path, folder_path)
+            out[(system, cp)] = timefreq_fun(data, rng)
+        return out
+    setups, grids, jobs = [], [], []
+    for b, (system, cp) in enumerate(items):
+        st, w_tx = _timefreq_setup(system, n_fft, cp, 8, 10, window_path)
+        grids.append(_full_grid(n_fft, draw_symbols(n_fft, rng)))
+        jobs += [(b, st.cp, st.cs, ov, w) for w, ov in _obr_windows(st, w_tx)]
+        setups.append((st, w_tx))
+    ests = tx_psd_batch_gpu(n_fft, np.stack(grids), jobs)
+    for b, ((system, cp), (st, w_tx)) in enumerate(zip(items, setups)):
+        dicts = _obr_dicts(st, w_tx, 200e-9, list(ests[3 * b:3 * b + 3]))
+        _timefreq_save(folder_path, system, cp, *dicts)
+        out[(system, cp)] = dicts
+    return out
