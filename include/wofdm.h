@@ -239,6 +239,26 @@ int wofdm_tx_psd_batch(int32_t n_fft, int device, int32_t n_jobs, const wofdm_ps
                        const float *w_tx, int32_t n_blocks, int32_t no_symbols, const float *X,
                        float *psd);
 
+/* wofdm_tx_psd_batch with an optional spectral Tx mask per job (dft_rc_filt, main_channel_mask.m:398-417;
+ * semantics of wofdm_plan_set_tx_mask).  job_mask[n_jobs]: index into the mask table, or -1 = job unmasked
+ * (NULL = all unmasked).  mask_len[n_masks]: 2 P - 1 of the jobs that use the mask (checked against every such
+ * job); mask_gain: the tables' real DFT-domain gains, natural bin order, concatenated.
+ * A masked job's windowed symbols are each zero-padded to 2 P - 1 samples, multiplied by the gains in the DFT
+ * domain and transformed back; the first P samples replace the symbol, the other P - 1 are added to the first
+ * P - 1 samples of the next symbol's row (the first symbol receives no spill, the last one's is dropped); then
+ * the overlap-add and the periodogram as for an unmasked job.  The mask runs as fast convolution over 8 n_fft
+ * points, so a masked job needs 3 P - 2 <= 8 n_fft (every cp + cs <= n_fft / 2 fits), else WOFDM_E_UNSUPPORTED;
+ * non-finite gains, a job_mask entry outside [-1, n_masks) or a mask_len other than 2 P_j - 1 are
+ * WOFDM_E_INVALID.  Each mask in use is prepared once per call (host, double precision; its spectrum is stored
+ * in single precision), and a masked job keeps no_symbols (2 P - 1) filtered samples in device memory.  An unmasked
+ * job gives the bits wofdm_tx_psd_batch gives for it; every sum is formed in a fixed order: repeated calls give
+ * identical results.  Synchronous; holds the same gate as wofdm_tx_psd_batch from its device synchronisation to
+ * the end of its kernels. */
+int wofdm_tx_psd_batch_masked(int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs,
+                              const float *w_tx, int32_t n_masks, const int32_t *mask_len,
+                              const float *mask_gain, const int32_t *job_mask,
+                              int32_t n_blocks, int32_t no_symbols, const float *X, float *psd);
+
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

@@ -10,6 +10,13 @@ Host wall clock around each whole route (every call ends in a device synchronise
 warm-up.  Prints one JSON line.
 
     python tools/bench_tx_psd.py [--reps 5]
+
+--masked: wofdm_tx_psd_batch_masked instead.  Two sets -- the N = 256 `run_timefreq`-sized one (6 systems x 4 CPs x 3
+windows = 72 jobs x 256 symbols) and an N = 1024 one (the same 72 jobs at N = 1024) -- each timed once unmasked
+(wofdm_tx_psd_batch) and once with every job masked by the reference's mask of its P; wall time per call, the host
+preparation of the masks, hipMalloc / hipFree and the copies included, one JSON line per set.  The kernel times come
+from the same run under `rocprofv3 --kernel-trace --stats -- python tools/bench_tx_psd.py --masked`
+(profiles/tx_psd_masked.txt holds both).
 """
 import argparse
 import json
@@ -48,10 +55,35 @@ def best(fn, reps):
     return min(t)
 
 
+def masked_sets(reps):
+    from wofdm_amd import channel_mask as CM
+    for n in (256, 1024):
+        rs = np.random.RandomState(1)
+        grids, jobs = [], []
+        for system in SYSTEMS:
+            for cp in (10, 16, 24, 32):
+                st = V.make_structure(system, n, cp)
+                for w, ov in T._obr_windows(st, V.tx_rc_window(st)):
+                    jobs.append((len(grids), st.cp, st.cs, ov, w))
+                grids.append(T._full_grid(n, T.draw_symbols(n, rs)))
+        grids = np.stack(grids)
+        assert len(jobs) == 72
+        masked = [j + (CM.tx_mask(n + j[1] + j[2]),) for j in jobs]
+        res = {"what": "N=%d, 72 jobs x 256 symbols" % n, "when": time.strftime("%Y-%m-%d %H:%M:%S %Z"),
+               "distinct_masks": len({n + j[1] + j[2] for j in jobs}),
+               "unmasked_wall_s": best(lambda: T.tx_psd_batch_gpu(n, grids, jobs), reps),
+               "masked_wall_s": best(lambda: T.tx_psd_batch_gpu(n, grids, masked), reps)}
+        res["masked_over_unmasked"] = res["masked_wall_s"] / res["unmasked_wall_s"]
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--masked", action="store_true")
     args = ap.parse_args()
+    if args.masked:
+        return masked_sets(args.reps)
     n = 256
     items = sweep(n)
     grids = np.stack([T._full_grid(n, X) for _, X, _ in items])

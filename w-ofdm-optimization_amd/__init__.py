@@ -27,7 +27,8 @@ from .simulation import (Plan, ber_for_window_file, error_rates, make_cfg,  # no
                          results_from_counts, run_counts, run_counts_injected, run_simulation,
                          save_ber_results, simulation_fun, wOFDMSystem)
 from ._lib import kernel_source_hash  # noqa: F401
-from .timefreq import run_timefreq  # noqa: F401
+from .timefreq import run_timefreq, tx_psd_batch_gpu, tx_waveform  # noqa: F401
+from .channel_mask import spectrum_for_window_file  # noqa: F401
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

@@ -4,7 +4,9 @@ The BER experiment of main_BER_calculation.m run twice on the same data: as is, 
 windowed symbol passed through a DFT-domain raised-cosine "channel mask" before the overlap-add;
 in both only the centre half of the spectrum carries data.  The frame loop runs on the GPU:
 ``Plan.set_allocation`` (zero padding + ifftshift of lines 387-390, bin selection of 367-369) and
-``Plan.set_tx_mask`` (``dft_rc_filt``, 398-417).
+``Plan.set_tx_mask`` (``dft_rc_filt``, 398-417).  ``spectrum_for_window_file`` is the spectrum side of the same
+experiment: the periodogram and out-of-band radiation of the plain and of the masked waveform
+(``wofdm_tx_psd_batch_masked``).
 
 BER is accumulated over the whole ensemble here as there (lines 341-359).  The reference sends
 the same data bits through both runs with independent noise (two ``add_wgn`` calls); here the
@@ -104,6 +106,51 @@ def ber_for_window_file(type_ofdm, cp, windows, channels, snr_db, num_subcar=256
                                bits_per_subcar, symbols_per_tx, st.tail_tx, st.tail_rx, seed=seed,
                                device=device, frame_range=frame_range)
     return results_from_counts(names, masked, plain), (masked, plain)
+
+
+def spectrum_for_window_file(type_ofdm, cp, windows, num_subcar=256, symbols=None, rng=None, roll_off=ROLL_OFF,
+                             gpu=True, device=0, tail_tx=8, tail_rx=10):
+    """Spectrum companion of ``ber_for_window_file``: what the mask buys.  Every window pair of the file
+    + the RC pair, half-band loading, 256 symbols of 16-QAM (``timefreq.draw_symbols``' draw on the loaded
+    bins; or ``symbols`` [N/2, S]); per pair the averaged periodogram [8N] of the plain and of the masked
+    waveform, all of them in ONE ``wofdm_tx_psd_batch_masked`` call (gpu=False: the fp64 host mirror
+    ``timefreq.tx_waveform`` + ``psd_estimate``).  OBR = mean of the periodogram over the bins of the 8N grid
+    that belong to unloaded subcarriers (bin f to subcarrier f // 8: ``estimate_obr``'s figure with the
+    allocation in place of the guard band).  Returns {name: {"psd", "psd_masked", "obr", "obr_masked",
+    "f_axis"}} with the names of ``V.matlab_pair_plan``."""
+    from . import timefreq as T
+    n = num_subcar
+    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
+                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
+    alloc = half_band_allocation(n)
+    if symbols is None:
+        rng = np.random.RandomState() if rng is None else rng
+        symbols = rng.choice(T.SYMBOLS_16QAM, size=(int(alloc.sum()), T.NO_SYMBOLS), replace=True)
+    symbols = np.asarray(symbols)
+    grid = np.zeros((n, symbols.shape[1]), dtype=np.complex128)
+    grid[alloc] = symbols
+    rc_tx = V.tx_rc_window(st)
+    plan = V.matlab_pair_plan(type_ofdm)
+    wins = [rc_tx if k[0] == "rc" else np.asarray(windows[k[0]], dtype=np.float64) for _, k in plan]
+    mask = tx_mask(st.sym_len, roll_off)
+    overlap = st.tail_tx
+    fft_len = 8 * n
+    if gpu:
+        jobs = []
+        for w in wins:
+            jobs += [(0, st.cp, st.cs, overlap, w), (0, st.cp, st.cs, overlap, w, mask)]
+        ests = T.tx_psd_batch_gpu(n, grid.T.astype(np.complex64)[None], jobs, device)
+    else:
+        ests = [T.psd_estimate(T.tx_waveform(st, grid, w, overlap, m, guard_band=None), fft_len)
+                for w in wins for m in (None, mask)]
+    unloaded = np.fft.fftshift(np.repeat(~alloc, fft_len // n))
+    f_axis = np.linspace(-.5, .5 - 1 / fft_len, fft_len) / 200e-9
+    out = {}
+    for i, (name, _) in enumerate(plan):
+        plain, masked = np.asarray(ests[2 * i]), np.asarray(ests[2 * i + 1])
+        out[name] = {"psd": plain, "psd_masked": masked, "obr": plain[unloaded].mean(),
+                     "obr_masked": masked[unloaded].mean(), "f_axis": f_axis}
+    return out
 
 
 def results_from_counts(names, masked, plain):

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <complex>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -181,6 +182,70 @@ int configure(wofdm_plan *pl)
     pl->base.dump_unscale_tx = fm ? 1.0f / pl->firm_sx : 1.0f;
     pl->base.dump_unscale_rx = fm ? 1.0f / (pl->firm_sx * pl->firm_sh) : 1.0f;
     return WOFDM_OK;
+}
+
+// Host transforms for the masks of wofdm_tx_psd_batch_masked, fp64, O(M log M).  fft_pow2: in place, sign = -1 forward,
+// +1 inverse (unnormalised), twiddles straight from cos / sin.
+using cplx = std::complex<double>;
+void fft_pow2(std::vector<cplx> &a, int sign)
+{
+    const size_t n = a.size();
+    for (size_t i = 1, j = 0; i < n; ++i) {
+        size_t bit = n >> 1;
+        for (; j & bit; bit >>= 1) j ^= bit;
+        j ^= bit;
+        if (i < j) std::swap(a[i], a[j]);
+    }
+    std::vector<cplx> w(n / 2 ? n / 2 : 1);
+    for (size_t k = 0; k < n / 2; ++k) {
+        const double ang = sign * 2.0 * M_PI * (double)k / (double)n;
+        w[k] = cplx(std::cos(ang), std::sin(ang));
+    }
+    for (size_t len = 2; len <= n; len <<= 1) {
+        const size_t half = len / 2, step = n / len;
+        for (size_t i = 0; i < n; i += len)
+            for (size_t k = 0; k < half; ++k) {
+                const cplx u = a[i + k], v = a[i + k + half] * w[k * step];
+                a[i + k] = u + v;
+                a[i + k + half] = u - v;
+            }
+    }
+}
+
+// g = IDFT_L(mask) for any L (Bluestein: k n = (k^2 + n^2 - (n - k)^2) / 2, chirp e^{i pi k^2 / L} from k^2 mod 2 L)
+std::vector<cplx> idft_any(const float *mask, int L)
+{
+    size_t Mb = 1;
+    while (Mb < (size_t)(2 * L - 1)) Mb <<= 1;
+    std::vector<cplx> c((size_t)L), a(Mb, cplx(0.0, 0.0)), b(Mb, cplx(0.0, 0.0));
+    for (int k = 0; k < L; ++k) {
+        const double ang = M_PI * (double)(((long long)k * k) % (2LL * L)) / (double)L;
+        c[(size_t)k] = cplx(std::cos(ang), std::sin(ang));
+    }
+    for (int k = 0; k < L; ++k) a[(size_t)k] = (double)mask[k] * c[(size_t)k];
+    b[0] = std::conj(c[0]);
+    for (int k = 1; k < L; ++k) b[(size_t)k] = b[Mb - (size_t)k] = std::conj(c[(size_t)k]);
+    fft_pow2(a, -1);
+    fft_pow2(b, -1);
+    for (size_t i = 0; i < Mb; ++i) a[i] *= b[i];
+    fft_pow2(a, +1);
+    std::vector<cplx> g((size_t)L);
+    for (int n = 0; n < L; ++n) g[(size_t)n] = a[(size_t)n] * c[(size_t)n] / ((double)Mb * (double)L);
+    return g;
+}
+
+// Fast-convolution spectrum of a mask of L = 2 P - 1 gains (the recipe of wofdm_plan_set_tx_mask): FFT_MF of
+// gt[t] = g[(t - (P-1)) mod L], t < 3 P - 2 <= MF, with the 1 / MF of the inverse transform folded in; rounded to fp32
+// only when stored.
+void mask_fastconv_spectrum(const float *mask, int L, int MF, float2 *spec)
+{
+    const int P = (L + 1) / 2, G = 3 * P - 2;
+    const std::vector<cplx> g = idft_any(mask, L);
+    std::vector<cplx> gt((size_t)MF, cplx(0.0, 0.0));
+    for (int t = 0; t < G && t < MF; ++t) gt[(size_t)t] = g[(size_t)(((t - (P - 1)) % L + L) % L)];
+    fft_pow2(gt, -1);
+    for (int f = 0; f < MF; ++f)
+        spec[f] = make_float2((float)(gt[(size_t)f].real() / MF), (float)(gt[(size_t)f].imag() / MF));
 }
 
 // The gate of launch() below: one mutex and one "last launch" event per device for the whole process.  The two synchronous
@@ -1021,19 +1086,36 @@ int wofdm_tx_psd(const wofdm_cfg *cfg, int device, const float *w_tx, const floa
     return rc;
 }
 
-int wofdm_tx_psd_batch(int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs, const float *w_tx,
-                       int32_t n_blocks, int32_t no_symbols, const float *X, float *psd)
+// wofdm_tx_psd_batch (n_masks = 0, job_mask = NULL) and wofdm_tx_psd_batch_masked.  Every argument is checked before
+// the first HIP call.
+static int psd_batch(const char *who, int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs, const float *w_tx,
+                     int32_t n_masks, const int32_t *mask_len, const float *mask_gain, const int32_t *job_mask,
+                     int32_t n_blocks, int32_t no_symbols, const float *X, float *psd)
 {
-    if (!jobs || !w_tx || !X || !psd) return fail(WOFDM_E_INVALID, "NULL argument");
+    if (!jobs || !w_tx || !X || !psd || (n_masks > 0 && (!mask_len || !mask_gain)))
+        return fail(WOFDM_E_INVALID, "NULL argument");
     const int N = n_fft;
     if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
-        return fail(WOFDM_E_UNSUPPORTED, "wofdm_tx_psd_batch is built for n_fft in {64,128,256,512,1024}");
+        return fail(WOFDM_E_UNSUPPORTED, "%s is built for n_fft in {64,128,256,512,1024}", who);
     if (n_jobs < 1 || n_jobs > 65535 || n_blocks < 1 || no_symbols < 1)
         return fail(WOFDM_E_INVALID, "bad n_jobs / n_blocks / no_symbols");
+    if (n_masks < 0 || n_masks > 65535) return fail(WOFDM_E_INVALID, "bad n_masks");
+    std::vector<int64_t> gain_off((size_t)n_masks);
+    int64_t n_gain = 0;
+    for (int m = 0; m < n_masks; ++m) {
+        if (mask_len[m] < 1) return fail(WOFDM_E_INVALID, "mask %d: length %d", m, mask_len[m]);
+        gain_off[(size_t)m] = n_gain;
+        n_gain += mask_len[m];
+    }
+    for (int64_t i = 0; i < n_gain; ++i)
+        if (!std::isfinite(mask_gain[i])) return fail(WOFDM_E_INVALID, "mask gains must be finite");
     const int FL = 8 * N, per_item = wofdm_psd_batch_slices(N);
-    std::vector<wofdm_bjob> hj((size_t)n_jobs);
+    std::vector<wofdm_bjob> hj((size_t)n_jobs), hplain;
+    std::vector<wofdm_mjob> hm;
     std::vector<wofdm_bitem> hi;
-    int64_t n_w = 0, n_x = 0;
+    std::vector<int> spec_of((size_t)n_masks, -1), spec_mask;       // masks in use -> spectrum slot, and back
+    int64_t n_w = 0, n_x = 0, n_y = 0;
+    int max_len = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const wofdm_psd_job &q = jobs[j];
         const int P = N + q.cp + q.cs;
@@ -1051,16 +1133,42 @@ int wofdm_tx_psd_batch(int32_t n_fft, int device, int32_t n_jobs, const wofdm_ps
         b.n_items = (int32_t)hi.size() - b.item0;
         n_w += P; n_x += len;
         if (n_w > INT32_MAX) return fail(WOFDM_E_INVALID, "windows too long");
+        const int m = job_mask ? job_mask[j] : -1;
+        if (m < -1 || m >= n_masks) return fail(WOFDM_E_INVALID, "job %d: mask index %d outside [-1, %d)", j, m, n_masks);
+        if (m >= 0) {
+            if (mask_len[m] != 2 * P - 1)
+                return fail(WOFDM_E_INVALID, "job %d: mask %d has %d gains, the job needs 2 P - 1 = %d", j, m, mask_len[m], 2 * P - 1);
+            if (P > wofdm_txmask_batch_pmax(N))
+                return fail(WOFDM_E_UNSUPPORTED, "job %d: a masked job needs 3 P - 2 <= 8 n_fft, i.e. P = n_fft + cp + cs <= %d "
+                            "at n_fft = %d (P = %d)", j, wofdm_txmask_batch_pmax(N), N, P);
+            if (spec_of[(size_t)m] < 0) {
+                spec_of[(size_t)m] = (int)spec_mask.size();
+                spec_mask.push_back(m);
+            }
+            hm.push_back({j, spec_of[(size_t)m], n_y});
+            n_y += (int64_t)no_symbols * (2 * P - 1);
+            max_len = std::max(max_len, (int)len);
+        }
     }
+    for (int j = 0; j < n_jobs; ++j)
+        if (!(job_mask && job_mask[j] >= 0)) hplain.push_back(hj[(size_t)j]);
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev)
         return fail(WOFDM_E_HIP, "device %d not available (%d visible); there is no CPU fallback", device, ndev);
     HIP_TRY(hipSetDevice(device));
+    // one fast-convolution spectrum per mask in use (host, fp64, O(M log M)), whatever the number of jobs that share it
+    std::vector<float2> hspec(spec_mask.size() * (size_t)FL);
+    for (size_t k = 0; k < spec_mask.size(); ++k) {
+        const int m = spec_mask[k];
+        mask_fastconv_spectrum(mask_gain + gain_off[(size_t)m], mask_len[m], FL, hspec.data() + k * (size_t)FL);
+    }
     const size_t n_X = (size_t)n_blocks * no_symbols * N, n_items = hi.size();
+    const bool masked = !hm.empty();
     float *d_w = nullptr, *d_part = nullptr, *d_psd = nullptr;
-    float2 *d_X = nullptr, *d_x = nullptr;
-    wofdm_bjob *d_jobs = nullptr;
+    float2 *d_X = nullptr, *d_x = nullptr, *d_spec = nullptr, *d_Y = nullptr;
+    wofdm_bjob *d_jobs = nullptr, *d_plain = nullptr;
+    wofdm_mjob *d_mjobs = nullptr;
     wofdm_bitem *d_items = nullptr;
     int rc = WOFDM_OK;
     do {
@@ -1071,6 +1179,11 @@ int wofdm_tx_psd_batch(int32_t n_fft, int device, int32_t n_jobs, const wofdm_ps
             hipMalloc(&d_items, n_items * sizeof(wofdm_bitem)) != hipSuccess) {
             rc = fail(WOFDM_E_NOMEM, "device allocation failed"); break;
         }
+        if (masked && (hipMalloc(&d_spec, hspec.size() * 8) != hipSuccess || hipMalloc(&d_Y, (size_t)n_y * 8) != hipSuccess ||
+                       hipMalloc(&d_mjobs, hm.size() * sizeof(wofdm_mjob)) != hipSuccess ||
+                       (!hplain.empty() && hipMalloc(&d_plain, hplain.size() * sizeof(wofdm_bjob)) != hipSuccess))) {
+            rc = fail(WOFDM_E_NOMEM, "device allocation failed (masked jobs keep %lld filtered samples)", (long long)n_y); break;
+        }
         if (hipMemcpy(d_w, w_tx, (size_t)n_w * 4, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(d_X, X, n_X * 8, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(d_jobs, hj.data(), hj.size() * sizeof(wofdm_bjob), hipMemcpyHostToDevice) != hipSuccess ||
@@ -1078,16 +1191,33 @@ int wofdm_tx_psd_batch(int32_t n_fft, int device, int32_t n_jobs, const wofdm_ps
             hipMemset(d_x, 0, (size_t)n_x * 8) != hipSuccess) {
             rc = fail(WOFDM_E_HIP, "upload failed"); break;
         }
+        if (masked && (hipMemcpy(d_spec, hspec.data(), hspec.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                       hipMemcpy(d_mjobs, hm.data(), hm.size() * sizeof(wofdm_mjob), hipMemcpyHostToDevice) != hipSuccess ||
+                       (d_plain && hipMemcpy(d_plain, hplain.data(), hplain.size() * sizeof(wofdm_bjob), hipMemcpyHostToDevice) != hipSuccess))) {
+            rc = fail(WOFDM_E_HIP, "upload failed"); break;
+        }
         // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
         std::lock_guard<std::mutex> gate(g_gate_mu);
         (void)hipDeviceSynchronize();
         hipError_t e = hipErrorInvalidValue;
-        const int ni = (int)n_items;
-        if (N == 64) e = wofdm_psd_batch_launch_n64(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
-        if (N == 128) e = wofdm_psd_batch_launch_n128(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
-        if (N == 256) e = wofdm_psd_batch_launch_n256(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
-        if (N == 512) e = wofdm_psd_batch_launch_n512(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
-        if (N == 1024) e = wofdm_psd_batch_launch_n1024(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+        const int ni = (int)n_items, np = (int)hplain.size(), nm = (int)hm.size();
+        if (!masked) {
+            if (N == 64) e = wofdm_psd_batch_launch_n64(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+            if (N == 128) e = wofdm_psd_batch_launch_n128(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+            if (N == 256) e = wofdm_psd_batch_launch_n256(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+            if (N == 512) e = wofdm_psd_batch_launch_n512(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+            if (N == 1024) e = wofdm_psd_batch_launch_n1024(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+        } else {
+#define WOFDM_MASKED_LAUNCH(n)                                                                                              \
+    if (N == n) e = wofdm_psd_batch_masked_launch_n##n(n_jobs, no_symbols, ni, d_jobs, d_items, np, d_plain, nm, d_mjobs,     \
+                                                       max_len, d_spec, d_Y, d_w, d_X, d_x, d_part, d_psd, nullptr)
+            WOFDM_MASKED_LAUNCH(64);
+            WOFDM_MASKED_LAUNCH(128);
+            WOFDM_MASKED_LAUNCH(256);
+            WOFDM_MASKED_LAUNCH(512);
+            WOFDM_MASKED_LAUNCH(1024);
+#undef WOFDM_MASKED_LAUNCH
+        }
         if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
             hipMemcpy(psd, d_psd, (size_t)n_jobs * FL * 4, hipMemcpyDeviceToHost) != hipSuccess) {
             rc = fail(WOFDM_E_HIP, "PSD kernels or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1101,7 +1231,26 @@ int wofdm_tx_psd_batch(int32_t n_fft, int device, int32_t n_jobs, const wofdm_ps
     if (d_psd) (void)hipFree(d_psd);
     if (d_jobs) (void)hipFree(d_jobs);
     if (d_items) (void)hipFree(d_items);
+    if (d_spec) (void)hipFree(d_spec);
+    if (d_Y) (void)hipFree(d_Y);
+    if (d_mjobs) (void)hipFree(d_mjobs);
+    if (d_plain) (void)hipFree(d_plain);
     return rc;
+}
+
+int wofdm_tx_psd_batch(int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs, const float *w_tx,
+                       int32_t n_blocks, int32_t no_symbols, const float *X, float *psd)
+{
+    return psd_batch("wofdm_tx_psd_batch", n_fft, device, n_jobs, jobs, w_tx, 0, nullptr, nullptr, nullptr, n_blocks,
+                     no_symbols, X, psd);
+}
+
+int wofdm_tx_psd_batch_masked(int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs, const float *w_tx,
+                              int32_t n_masks, const int32_t *mask_len, const float *mask_gain, const int32_t *job_mask,
+                              int32_t n_blocks, int32_t no_symbols, const float *X, float *psd)
+{
+    return psd_batch("wofdm_tx_psd_batch_masked", n_fft, device, n_jobs, jobs, w_tx, n_masks, mask_len, mask_gain, job_mask,
+                     n_blocks, no_symbols, X, psd);
 }
 
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])

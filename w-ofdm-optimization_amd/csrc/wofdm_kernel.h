@@ -383,3 +383,25 @@ WOFDM_PSD_BATCH_DECL(128);
 WOFDM_PSD_BATCH_DECL(256);
 WOFDM_PSD_BATCH_DECL(512);
 WOFDM_PSD_BATCH_DECL(1024);
+
+// Masked jobs of wofdm_tx_psd_batch_masked: the spectral Tx mask as fast convolution over 8 n_fft points (3 P - 2 of them
+// in use), so P <= (8 n_fft + 2) / 3 -- every cp + cs <= n_fft / 2 and more.  A masked job keeps the whole filtered symbols
+// y_s[2 P - 1] at Y + y_off before the gather that forms its waveform; its mask spectrum is spec[spec][8 n_fft].
+struct wofdm_mjob {
+    int32_t job, spec;                // index into the job table; index of the mask's fast-convolution spectrum
+    int64_t y_off;
+};
+__host__ __device__ constexpr int wofdm_txmask_batch_pmax(int n_fft) { return (8 * n_fft + 2) / 3; }
+// plain_jobs: the n_plain unmasked jobs (waveform by wofdm_txwave_batch_kernel, as wofdm_psd_batch_launch); mjobs: the
+// n_masked masked ones; max_len: longest masked waveform.  Periodogram and reduction over the whole table `jobs`.
+#define WOFDM_PSD_BATCH_MASKED_DECL(n)                                                                                \
+    hipError_t wofdm_psd_batch_masked_launch_n##n(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs,    \
+                                                  const wofdm_bitem *items, int n_plain, const wofdm_bjob *plain_jobs, \
+                                                  int n_masked, const wofdm_mjob *mjobs, int max_len,                 \
+                                                  const float2 *spec, float2 *Y, const float *wtx, const float2 *X,   \
+                                                  float2 *x, float *partial, float *psd, hipStream_t s)
+WOFDM_PSD_BATCH_MASKED_DECL(64);
+WOFDM_PSD_BATCH_MASKED_DECL(128);
+WOFDM_PSD_BATCH_MASKED_DECL(256);
+WOFDM_PSD_BATCH_MASKED_DECL(512);
+WOFDM_PSD_BATCH_MASKED_DECL(1024);

@@ -4350,6 +4350,210 @@ __global__ void __launch_bounds__(256) wofdm_psd_reduce_kernel(const wofdm_bjob 
     psd[(size_t)blockIdx.y * FL + ((k + FL / 2) & (FL - 1))] = t;
 }
 
+// Waveform step of a MASKED job (wofdm_tx_psd_batch_masked): per symbol the row r_s[P] of wofdm_txwave_batch_kernel
+// (IDFT, CP/CS copy, Tx window), then the spectral Tx mask of wofdm_plan_set_tx_mask as fast convolution over FL = 8 N
+// points (3 P - 2 <= FL):  y_s[i] = IFFT_FL( FFT_FL(r_s) . H )[i + P - 1], i < 2 P - 1, with H the transform of the mask's
+// impulse response laid out as in the frame kernel's TXFFT variant, 1 / FL folded in (host, fp64; stored in fp32).
+// The FL-point transforms are the R-way split of wofdm_psd_batch_kernel (R waves, M = FL / R points each) and its
+// transpose:  forward  X[k' + M c] = sum_h W_R^(h c) (W_FL^(h k') E_h[k']),  E_h = FFT_M(r[R m + h]);
+//             inverse  y[R m + h] = IFFT_M(F_h)[m],  F_h[k'] = W_FL^(-h k') sum_c W_R^(-h c) Z[k' + M c].
+// Wave h of a group owns k' = h M / R + lane + 64 j in the combination, takes all R bins k' + M c, multiplies them by H
+// and runs the inverse combination in registers -- the spectrum never leaves the workgroup.  8 waves = 8 / R symbols
+// per workgroup.  LDS: twiddles [M] (+ [N] where N != M) | rows [8][M] | symbol rows [8 / R][PMAX].
+// Output: the WHOLE y_s (2 P - 1 samples) by plain stores at Y + y_off + s (2 P - 1); the spill of symbol s onto s + 1
+// and the overlap-add are the gather of wofdm_txmask_ola_kernel -- no atomics, a fixed order of additions.
+template <int N> struct bmask_geo {
+    static constexpr int FL = 8 * N, R = wofdm_psd_batch_r(N), M = FL / R, G = 8 / R;
+    static constexpr int PMAX = wofdm_txmask_batch_pmax(N);
+    static constexpr int TWN = N == M ? 0 : N;                    // a twiddle table of its own for the N-point IDFT
+    static constexpr size_t LDS = 8 * (size_t)(M + TWN + 8 * M + G * PMAX);
+    static_assert(LDS <= 160 * 1024 && N <= M && 3 * PMAX - 2 <= FL, "LDS / transform length");
+};
+template <int N>
+__global__ void __launch_bounds__(512)
+wofdm_txmask_batch_kernel(const wofdm_bjob *__restrict__ jobs, const wofdm_mjob *__restrict__ mjobs, int no_symbols,
+                          const float *__restrict__ g_wtx, const float2 *__restrict__ X, const float2 *__restrict__ spec,
+                          float2 *__restrict__ Y)
+{
+    using MG = bmask_geo<N>;
+    constexpr int FL = MG::FL, R = MG::R, M = MG::M, G = MG::G, PMAX = MG::PMAX;
+    constexpr int BPL = geo<M>::BPL, NQ = geo<M>::NQ, JJ = M / (64 * R);
+    constexpr int BPLN = geo<N>::BPL, NQN = geo<N>::NQ;
+    constexpr bool FULLN = geo<N>::FULL;
+    static_assert(geo<M>::FULL, "512- or 1024-point transforms");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *twm = reinterpret_cast<v2f *>(smem);
+    v2f *twn = N == M ? twm : twm + M;
+    v2f *rows = twm + M + MG::TWN;                                // [8][M]
+    v2f *srows = rows + 8 * M;                                    // [G][PMAX]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = wv / R, h = wv % R;
+    fill_twiddles<M>(twm, tid, 512);
+    if constexpr (N != M) fill_twiddles<N>(twn, tid, 512);
+    const wofdm_mjob mj = mjobs[blockIdx.y];
+    const wofdm_bjob jb = jobs[mj.job];
+    const int P = N + jb.cp + jb.cs, L = 2 * P - 1;
+    const int s = blockIdx.x * G + g;
+    const bool live = s < no_symbols;                             // uniform over the group
+    v2f cw[JJ][R > 1 ? R - 1 : 1];                                // W_FL^(t k'), t = 1 .. R-1
+    if constexpr (R > 1) {
+#pragma unroll
+        for (int j = 0; j < JJ; ++j)
+#pragma unroll
+            for (int t = 1; t < R; ++t) {
+                const int kp = h * (M / R) + lane + 64 * j;
+                float sv, cv;
+                sincospif(-2.0f * (float)(t * kp) / (float)FL, &sv, &cv);
+                cw[j][t - 1] = mk(cv, sv);
+            }
+    }
+    __syncthreads();
+    v2f *own = rows + (size_t)wv * M;
+    v2f *srow = srows + (size_t)g * PMAX;
+    if (live && h == 0) {                                         // r_s: as wofdm_txwave_batch_kernel, into LDS
+        const float2 *Xs = X + ((size_t)jb.block * no_symbols + s) * N;
+        v2f v[1][BPLN][4];
+#pragma unroll
+        for (int q = 0; q < BPLN; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v[0][q][r] = mk(0.f, 0.f);
+                if (FULLN || lane + 64 * q < NQN) v[0][q][r] = ldg2(Xs + lane + 64 * q + r * NQN);
+            }
+        fft_wave<N, +1, 1>(v, own, 0, twn, lane);                 // N x[t]
+        const float *wtx = g_wtx + jb.w_off;
+        auto put = [&](int i, v2f val) { srow[i] = val * (wtx[i] * (1.0f / (float)N)); };
+#pragma unroll
+        for (int q = 0; q < BPLN; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (!(FULLN || lane + 64 * q < NQN)) continue;
+                const int t = lane + 64 * q + r * NQN;
+                put(t + jb.cp, v[0][q][r]);
+                if (t >= N - jb.cp) put(t + jb.cp - N, v[0][q][r]);
+                if (t < jb.cs) put(t + jb.cp + N, v[0][q][r]);
+            }
+    }
+    __syncthreads();
+    v2f v[1][BPL][4];
+    if (live) {
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int idx = R * (lane + 64 * q + r * NQ) + h;
+                v[0][q][r] = idx < P ? srow[idx] : mk(0.f, 0.f);
+            }
+        fft_wave<M, -1, 1>(v, own, 0, twm, lane);
+        if constexpr (R == 1) {
+            const float2 *H = spec + (size_t)mj.spec * FL;
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[0][q][r] = cmul(v[0][q][r], ldg2(H + lane + 64 * q + r * NQ));
+        } else {
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) own[lane + 64 * q + r * NQ] = v[0][q][r];
+        }
+    }
+    if constexpr (R > 1) {
+        __syncthreads();
+        v2f F[JJ][R];                                             // F_t[k'] of this wave's k', t < R
+        if (live) {
+            const v2f *gs = rows + (size_t)g * R * M;
+            const float2 *H = spec + (size_t)mj.spec * FL;
+#pragma unroll
+            for (int j = 0; j < JJ; ++j) {
+                const int kp = h * (M / R) + lane + 64 * j;
+                v2f y[R];
+#pragma unroll
+                for (int t = 0; t < R; ++t) y[t] = gs[t * M + kp];
+#pragma unroll
+                for (int t = 1; t < R; ++t) y[t] = cmul(y[t], cw[j][t - 1]);
+                if constexpr (R == 2) {
+                    const v2f z0 = cmul(y[0] + y[1], ldg2(H + kp)), z1 = cmul(y[0] - y[1], ldg2(H + kp + M));
+                    F[j][0] = z0 + z1;
+                    F[j][1] = z0 - z1;
+                } else if constexpr (R == 4) {
+                    v2f u[4] = {y[0], y[1], y[2], y[3]};
+                    radix4<-1>(u);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) u[c] = cmul(u[c], ldg2(H + kp + M * c));
+                    radix4<+1>(u);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) F[j][t] = u[t];
+                } else {
+                    v2f u[2][4], w[2][4];                         // u[q][r] = y_t, t = q + 2 r
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) u[t & 1][t >> 1] = y[t];
+                    dft8<-1>(u);                                  // u[q][r] = X_c, c = r + 4 q
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) w[c & 1][c >> 1] = cmul(u[c >> 2][c & 3], ldg2(H + kp + M * c));
+                    dft8<+1>(w);                                  // w[q][r] = F_t, t = r + 4 q
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) F[j][t] = w[t >> 2][t & 3];
+                }
+#pragma unroll
+                for (int t = 1; t < R; ++t) F[j][t] = cmul_conj(F[j][t], cw[j][t - 1]);
+            }
+        }
+        __syncthreads();                                          // every wave has read the E rows
+        if (live) {
+            v2f *gs = rows + (size_t)g * R * M;
+#pragma unroll
+            for (int j = 0; j < JJ; ++j)
+#pragma unroll
+                for (int t = 0; t < R; ++t) gs[t * M + h * (M / R) + lane + 64 * j] = F[j][t];
+        }
+        __syncthreads();
+        if (live) {
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[0][q][r] = own[lane + 64 * q + r * NQ];
+        }
+    }
+    if (!live) return;
+    fft_wave<M, +1, 1>(v, own, 0, twm, lane);                     // y[R m + h + (P - 1)], the 1 / FL sits in H
+    float2 *out = Y + mj.y_off + (size_t)s * L;
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = R * (lane + 64 * q + r * NQ) + h - (P - 1);
+            if (i >= 0 && i < L) out[i] = make_float2(v[0][q][r].x, v[0][q][r].y);
+        }
+}
+
+// Filtered rows and overlap-add of a masked job, as a gather in a fixed order (no atomics):
+//   row_s[i] = y_s[i] + y_{s-1}[P + i] (i < P - 1, s > 0),  row_s[P - 1] = y_s[P - 1]
+//   x[s (P - overlap) + i] = row_s[i] (s < S) + row_{s-1}[i + P - overlap] (s > 0, i < overlap)
+template <int N>
+__global__ void __launch_bounds__(256)
+wofdm_txmask_ola_kernel(const wofdm_bjob *__restrict__ jobs, const wofdm_mjob *__restrict__ mjobs, int no_symbols,
+                        const float2 *__restrict__ Y, float2 *__restrict__ x)
+{
+    const wofdm_mjob mj = mjobs[blockIdx.y];
+    const wofdm_bjob jb = jobs[mj.job];
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= jb.len) return;
+    const int P = N + jb.cp + jb.cs, L = 2 * P - 1, Bo = P - jb.overlap;
+    const float2 *y = Y + mj.y_off;
+    auto row = [&](int ss, int i) {
+        v2f a = ldg2(y + (size_t)ss * L + i);
+        if (ss > 0 && i < P - 1) a = a + ldg2(y + (size_t)(ss - 1) * L + P + i);
+        return a;
+    };
+    const int s = n / Bo, i = n - s * Bo;
+    v2f val = mk(0.f, 0.f);
+    if (s < no_symbols) val = row(s, i);
+    if (s > 0 && i < jb.overlap) val = s < no_symbols ? val + row(s - 1, i + Bo) : row(s - 1, i + Bo);
+    x[jb.x_off + n] = make_float2(val.x, val.y);
+}
+
 __global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
 {
     if (threadIdx.x == 0) {
@@ -4391,28 +4595,34 @@ wofdm_kernel_fn pick_layout(int layout, int mode, int var, std::integer_sequence
     return fn;
 }
 
+#if WOFDM_TU_K != 0
 template <int N> wofdm_kernel_fn pick(int k, int layout, int mode, int var)
 {
     // (one constellation size per translation unit, see below)
     if (k != WOFDM_TU_K) return nullptr;
     return pick_layout<N, WOFDM_TU_K>(layout, mode, var, std::make_integer_sequence<int, WOFDM_LAYOUT_COUNT>{});
 }
+#endif
 
 }  // namespace
 
 // This file is compiled once per (DFT length, bits per subcarrier) (-DWOFDM_TU_N=<N>
 // -DWOFDM_TU_K=<k>, see the Makefile) so that the kernel family builds in parallel;
-// wofdm_kernel.h dispatches on n_fft and bits_per_sc.
+// wofdm_kernel.h dispatches on n_fft and bits_per_sc.  -DWOFDM_TU_K=0: no frame kernel, only the waveform kernels of
+// wofdm_tx_psd_batch_masked for this DFT length -- units of their own, so that the frame kernels' units hold exactly
+// the functions they held before (their register allocation answers to what else is compiled beside them).
 #if !defined(WOFDM_TU_N) || !defined(WOFDM_TU_K)
-#error "compile with -DWOFDM_TU_N=<64|128|256|512|1024> -DWOFDM_TU_K=<2|4|6>"
+#error "compile with -DWOFDM_TU_N=<64|128|256|512|1024> -DWOFDM_TU_K=<2|4|6|0>"
 #endif
 #define WOFDM_CAT2(a, b) a##b
 #define WOFDM_CAT(a, b) WOFDM_CAT2(a, b)
 
+#if WOFDM_TU_K != 0
 wofdm_kernel_fn WOFDM_CAT(WOFDM_CAT(WOFDM_CAT(wofdm_select_kernel_n, WOFDM_TU_N), _k), WOFDM_TU_K)(int layout, int mode, int var)
 {
     return pick<WOFDM_TU_N>(WOFDM_TU_K, layout, mode, var);
 }
+#endif
 
 #if WOFDM_TU_K == 2
 // one interference kernel per DFT length, compiled in the k = 2 translation units
@@ -4471,6 +4681,42 @@ hipError_t WOFDM_CAT(wofdm_psd_batch_launch_n, WOFDM_TU_N)(int n_jobs, int no_sy
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(wofdm_txwave_batch_kernel<N>, dim3((no_symbols + WW - 1) / WW, n_jobs), dim3(WW * 64), lds_a, s, jobs,
                        no_symbols, wtx, X, x);
+    hipLaunchKernelGGL(wofdm_psd_batch_kernel<FL>, dim3(n_items), dim3(512), lds_b, s, jobs, items, (const float2 *)x, partial);
+    hipLaunchKernelGGL(wofdm_psd_reduce_kernel<FL>, dim3((FL + 255) / 256, n_jobs), dim3(256), 0, s, jobs,
+                       (const float *)partial, psd);
+    return hipGetLastError();
+}
+#endif
+
+#if WOFDM_TU_K == 0
+// wofdm_tx_psd_batch_masked: the unmasked jobs' waveforms by wofdm_txwave_batch_kernel, the masked ones by the fast-convolution
+// kernel and its gather, then periodogram and reduction of all jobs as in wofdm_psd_batch_launch; the -DWOFDM_TU_K=0 units
+hipError_t WOFDM_CAT(wofdm_psd_batch_masked_launch_n, WOFDM_TU_N)(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs,
+                                                                  const wofdm_bitem *items, int n_plain, const wofdm_bjob *plain_jobs,
+                                                                  int n_masked, const wofdm_mjob *mjobs, int max_len,
+                                                                  const float2 *spec, float2 *Y, const float *wtx, const float2 *X,
+                                                                  float2 *x, float *partial, float *psd, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N, FL = 8 * N, M = FL / wofdm_psd_batch_r(N), WW = bwave_geo<N>::WAVES, G = bmask_geo<N>::G;
+    const size_t lds_a = 8 * (size_t)N * (1 + WW), lds_b = 8 * (size_t)M * 9, lds_m = bmask_geo<N>::LDS;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txwave_batch_kernel<N>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_psd_batch_kernel<FL>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txmask_batch_kernel<N>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
+    if (e != hipSuccess) return e;
+    if (n_plain > 0)
+        hipLaunchKernelGGL(wofdm_txwave_batch_kernel<N>, dim3((no_symbols + WW - 1) / WW, n_plain), dim3(WW * 64), lds_a, s,
+                           plain_jobs, no_symbols, wtx, X, x);
+    if (n_masked > 0) {
+        hipLaunchKernelGGL(wofdm_txmask_batch_kernel<N>, dim3((no_symbols + G - 1) / G, n_masked), dim3(512), lds_m, s, jobs,
+                           mjobs, no_symbols, wtx, X, spec, Y);
+        hipLaunchKernelGGL(wofdm_txmask_ola_kernel<N>, dim3((max_len + 255) / 256, n_masked), dim3(256), 0, s, jobs, mjobs,
+                           no_symbols, (const float2 *)Y, x);
+    }
     hipLaunchKernelGGL(wofdm_psd_batch_kernel<FL>, dim3(n_items), dim3(512), lds_b, s, jobs, items, (const float2 *)x, partial);
     hipLaunchKernelGGL(wofdm_psd_reduce_kernel<FL>, dim3((FL + 255) / 256, n_jobs), dim3(256), 0, s, jobs,
                        (const float *)partial, psd);

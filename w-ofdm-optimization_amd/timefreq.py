@@ -55,6 +55,37 @@ def overlap_and_add(x, beta):
     return np.concatenate([x[0, :beta], body.reshape(-1)])
 
 
+def mask_rows(rows, mask):
+    """Spectral Tx mask on [S, P] rows (``dft_rc_filt``, main_channel_mask.m:398-417, for any gain vector; the
+    semantics of ``wofdm_plan_set_tx_mask``): every row zero-padded to L = 2P-1, its DFT times ``mask`` [L]
+    (real gains, natural bin order), back; the first P samples replace the row, the other P-1 are added to
+    the head of the NEXT row (no spill into the first row, the last row's spill is dropped)."""
+    rows = np.asarray(rows, dtype=np.complex128)
+    P = rows.shape[1]
+    L = 2 * P - 1
+    mask = np.asarray(mask, dtype=np.float64).reshape(-1)
+    if mask.shape != (L,):
+        raise ValueError("mask must hold 2 P - 1 = %d gains, got %s" % (L, mask.shape))
+    y = np.fft.ifft(np.fft.fft(rows, L, axis=1) * mask[None, :], axis=1)
+    out = y[:, :P].copy()
+    out[1:, :P - 1] += y[:-1, P:]
+    return out
+
+
+def tx_waveform(st, X, w_tx, overlap, mask=None, guard_band=GUARD_BAND):
+    """fp64 host mirror of the waveform the spectrum kernels transmit: ``overlap_and_add`` of the
+    ``tx_symbols``, each passed through ``mask_rows`` first when ``mask`` [2P-1] is given.  X as
+    ``draw_symbols`` gives it, or [N, S] on every bin with guard_band=None."""
+    if guard_band is None:
+        t = np.fft.ifft(np.asarray(X, dtype=np.complex128), axis=0)
+        rows = (np.asarray(w_tx)[:, None] * t[(np.arange(st.sym_len) - st.cp) % st.n_fft]).T
+    else:
+        rows = tx_symbols(st, X, w_tx, guard_band)
+    if mask is not None:
+        rows = mask_rows(rows, mask)
+    return overlap_and_add(rows, overlap)
+
+
 def psd_estimate(x, fft_len):
     """Mean of |fftshift(FFT)|^2 over consecutive length-``fft_len`` slices, the zero-padded
     remainder included as one more slice (lines 101-123)."""
@@ -74,16 +105,19 @@ def _full_grid(n, X, guard_band=GUARD_BAND):
     return grid
 
 
-def psd_estimate_gpu(st, X, w_tx, overlap, guard_band=GUARD_BAND, device=0):
-    """``psd_estimate(overlap_and_add(tx_symbols(st, X, w_tx), overlap), 8 N)`` on the GPU
+def psd_estimate_gpu(st, X, w_tx, overlap, guard_band=GUARD_BAND, device=0, mask=None):
+    """``psd_estimate(tx_waveform(st, X, w_tx, overlap, mask), 8 N)`` on the GPU
     (``wofdm_tx_psd``: the frame kernel's Tx half on the given symbols + the averaged periodogram).
     X: [N - 2 gb, no_symbols] like ``draw_symbols``.  No CPU fallback; N in {64, 128, 256} by
-    ``wofdm_tx_psd``, N = 512 / 1024 by ``wofdm_tx_psd_batch`` (one job)."""
+    ``wofdm_tx_psd``, N = 512 / 1024 by ``wofdm_tx_psd_batch`` (one job); with a spectral Tx mask
+    ([2P-1] gains) by ``wofdm_tx_psd_batch_masked`` at every N."""
     import ctypes as C
     from . import _lib
     from .simulation import make_cfg
     n = st.n_fft
     grid = _full_grid(n, X, guard_band)
+    if mask is not None:
+        return tx_psd_batch_gpu(n, grid[None], [(0, st.cp, st.cs, overlap, w_tx, mask)], device)[0]
     if n > 256:
         return tx_psd_batch_gpu(n, grid[None], [(0, st.cp, st.cs, overlap, w_tx)], device)[0]
     w = _lib.f32(np.asarray(w_tx).reshape(-1), (st.sym_len,))
@@ -99,8 +133,11 @@ def psd_estimate_gpu(st, X, w_tx, overlap, guard_band=GUARD_BAND, device=0):
 def tx_psd_batch_gpu(n_fft, grids, jobs, device=0, divide=True):
     """Averaged periodograms of many Tx waveforms in one ``wofdm_tx_psd_batch`` call, any N in
     {64, ..., 1024}.  grids: [n_blocks, no_symbols, N] complex symbols on every bin (as given);
-    jobs: sequence of (block, cp, cs, overlap, w_tx), w_tx of length N + cp + cs.  Returns
-    [n_jobs, 8 N] float64: ``psd_estimate(overlap_and_add(...), 8 N)`` of each job's waveform, i.e.
+    jobs: sequence of (block, cp, cs, overlap, w_tx) or (block, cp, cs, overlap, w_tx, mask), w_tx of
+    length P = N + cp + cs, mask None or the [2P-1] DFT-domain gains of a spectral Tx mask
+    (``mask_rows``).  A call with any mask goes through ``wofdm_tx_psd_batch_masked`` (equal masks
+    share one table entry; masked jobs need 3P-2 <= 8N), the others through ``wofdm_tx_psd_batch``.
+    Returns [n_jobs, 8 N] float64: ``psd_estimate(tx_waveform(...), 8 N)`` of each job's waveform, i.e.
     the kernel's slice sums divided by the reference's slice count (length // 8 N + 1); with
     divide=False the undivided float32 sums.  No CPU fallback."""
     import ctypes as C
@@ -110,18 +147,31 @@ def tx_psd_batch_gpu(n_fft, grids, jobs, device=0, divide=True):
     if grids.ndim != 3 or grids.shape[2] != n:
         raise ValueError("grids must be [n_blocks, no_symbols, %d], got %s" % (n, grids.shape))
     n_blocks, no_symbols = grids.shape[:2]
-    jobs = list(jobs)
+    jobs = [tuple(j) + (None,) * (6 - len(j)) for j in jobs]
     cj = (_lib.PsdJob * max(1, len(jobs)))()
-    wins, lengths = [], []
-    for j, (block, cp, cs, overlap, w) in enumerate(jobs):
+    wins, lengths, tables, table_of = [], [], [], {}
+    job_mask = np.full(max(1, len(jobs)), -1, dtype=np.int32)
+    for j, (block, cp, cs, overlap, w, mask) in enumerate(jobs):
         cj[j].block, cj[j].cp, cj[j].cs, cj[j].overlap = int(block), int(cp), int(cs), int(overlap)
         wins.append(_lib.f32(np.asarray(w).reshape(-1), (n + cp + cs,)))
         lengths.append(overlap + no_symbols * (n + cp + cs - overlap))
+        if mask is not None:
+            m = _lib.f32(np.asarray(mask).reshape(-1), (2 * (n + cp + cs) - 1,))
+            job_mask[j] = table_of.setdefault(m.tobytes(), len(tables))
+            if job_mask[j] == len(tables):
+                tables.append(m)
     w_all = _lib.f32(np.concatenate(wins) if wins else np.zeros(1))
     gf = _lib.c64_as_f32(grids)
     out = np.zeros((max(1, len(jobs)), 8 * n), dtype=np.float32)
-    _lib.check(_lib.load().wofdm_tx_psd_batch(n, int(device), len(jobs), C.addressof(cj), w_all.ctypes.data,
-                                              int(n_blocks), int(no_symbols), gf.ctypes.data, out.ctypes.data))
+    if tables:
+        mask_len = np.array([t.size for t in tables], dtype=np.int32)
+        gains = _lib.f32(np.concatenate(tables))
+        _lib.check(_lib.load().wofdm_tx_psd_batch_masked(
+            n, int(device), len(jobs), C.addressof(cj), w_all.ctypes.data, len(tables), mask_len.ctypes.data,
+            gains.ctypes.data, job_mask.ctypes.data, int(n_blocks), int(no_symbols), gf.ctypes.data, out.ctypes.data))
+    else:
+        _lib.check(_lib.load().wofdm_tx_psd_batch(n, int(device), len(jobs), C.addressof(cj), w_all.ctypes.data,
+                                                  int(n_blocks), int(no_symbols), gf.ctypes.data, out.ctypes.data))
     if not divide:
         return out
     return out.astype(np.float64) / (np.array(lengths, dtype=np.int64) // (8 * n) + 1)[:, None]
@@ -177,17 +227,20 @@ def _obr_dicts(st, w_tx, samp_period, ests):
     return tuple(out)
 
 
-def estimate_obr(st, w_tx, samp_period=200e-9, X=None, rng=None, gpu=False):
+def estimate_obr(st, w_tx, samp_period=200e-9, X=None, rng=None, gpu=False, mask=None):
     """``wOFDMSystem.estimate_obr`` (lines 216-296): three dicts (optimised window, RC window,
     plain CP-OFDM) with the reference's keys.  gpu=True: waveform and periodogram on the GPU,
     ``wofdm_tx_psd`` per window at N <= 256, one ``wofdm_tx_psd_batch`` call for the three at
-    N = 512 / 1024."""
+    N = 512 / 1024.  mask: [2P-1] gains of a spectral Tx mask (``mask_rows``) applied to all three
+    waveforms; the host route is ``tx_waveform``, the GPU route one ``wofdm_tx_psd_batch_masked`` call."""
     n = st.n_fft
     fft_len = 8 * n
     X = draw_symbols(n, rng) if X is None else np.asarray(X)
     wins = _obr_windows(st, w_tx)
     if not gpu:
-        ests = [psd_estimate(overlap_and_add(tx_symbols(st, X, w), ov), fft_len) for w, ov in wins]
+        ests = [psd_estimate(tx_waveform(st, X, w, ov, mask), fft_len) for w, ov in wins]
+    elif mask is not None:
+        ests = list(tx_psd_batch_gpu(n, _full_grid(n, X)[None], [(0, st.cp, st.cs, ov, w, mask) for w, ov in wins]))
     elif n <= 256:
         ests = [psd_estimate_gpu(st, X, w, ov) for w, ov in wins]
     else:
