@@ -95,7 +95,11 @@ int         wofdm_noise_len(const wofdm_cfg *cfg);/* unit-noise samples per fram
 
 /* Upload windows [pairs][P] / [pairs][N+delta], channels [n_channels][L][2] and SNR points
  * [n_snr] (dB) to `device` and select the kernel.  frames_per_cell / frame_offset of cfg are
- * ignored here (given per launch). */
+ * ignored here (given per launch).  A frame whose LDS image exceeds 160 KiB is WOFDM_E_UNSUPPORTED
+ * (n_fft = 1024 with 16 symbols near cp + cs = 48).  Just below that limit the kernel class can change
+ * with the stride: the matrix-pipe kernels with one symbol per wave pad their LDS rows to multiples of
+ * four samples, and where only the padding overflows the plan runs the one-symbol VALU kernel instead
+ * (same results, lower rate; wofdm_plan_kernel_id reports layout 1). */
 int wofdm_plan_create(wofdm_plan **plan, const wofdm_cfg *cfg, int device,
                       const float *w_tx, const float *w_rx, const float *h,
                       const float *snr_db);

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import wofdm_amd as W
+from kernel_cases import expected_kernel_id, geometry_for as _geometry_for, spilling_rows
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -43,32 +44,9 @@ def test_device_present_and_philox_kat():
 
 
 def _expected_layout(st, n_fft, S):
-    """Layout id wofdm_plan_create picks for a plain plan (wofdm_pick_layout in csrc/wofdm_kernel.h)."""
-    B = st.stride
-    if n_fft <= 128 and S % (1024 // n_fft) == 0 and B >= n_fft:
-        if (1024 // n_fft) * B <= 128 * 10:
-            return 13
-        if (1024 // n_fft) * B <= 128 * 11:
-            return 14
-    if n_fft <= 128 and B >= n_fft:
-        # layout 16: a run-time number of symbols per wave (wofdm_small_spwr): the frame spread evenly over at most four waves
-        for waves in range(1, 5):
-            spwr = (-(-S // waves) + 1) & ~1
-            if spwr <= 1024 // n_fft and spwr * B <= 128 * 10 and (waves - 1) * spwr < S:
-                return 16
-    if n_fft == 256 and S % 4 == 0 and B >= n_fft:
-        if 4 * B <= 128 * 9:
-            return 10
-        if 4 * B <= 128 * 10:
-            return 11
-    if n_fft == 256 and S % 4 == 0:
-        if 4 * B <= 64 * 18:
-            return 4
-        if 4 * B <= 64 * 20:
-            return 5
-    if n_fft >= 512 and B >= n_fft and B <= 128 * (9 if n_fft == 1024 else 5):      # (every stride, odd ones since round 4)
-        return 12
-    return 2 if (n_fft <= 256 and S % 2 == 0 and 2 * B <= 64 * (2 * (n_fft // 64) + 2)) else 1
+    """Layout id wofdm_plan_create picks for a plain plan (kernel_cases.expected_kernel_id: wofdm_pick_layout in csrc/wofdm_kernel.h)."""
+    assert st.n_fft == n_fft
+    return expected_kernel_id(st, S)[0]
 
 
 CASES = [(s, 64, 16, 2, 1) for s in SYSTEMS] + [
@@ -655,15 +633,6 @@ def test_production_kernels_sharp_parity(channels, system, n_fft, cp, k, S):
 # regions of these kernels are the hazard DESIGN.md section 4 records, and a reload of the wrong lanes
 # would move the error count by hundreds.  Generate and injected mode, plain / allocation / both
 # Tx-mask forms; the plan must really have picked the instantiation (wofdm_plan_kernel_id).
-def _spilling_kernels():
-    import json
-    import os
-    path = os.path.join(os.path.dirname(__file__), "..", "profiles", "kernel_table.json")
-    rows = json.load(open(path))["kernels"]
-    return [(r["n_fft"], r["k"], r["layout"], r["inject"], r["var"]) for r in rows
-            if not r["dump"] and r["private_segment_fixed_size"] > 0]
-
-
 def _poison():
     import ctypes
     import os
@@ -687,43 +656,11 @@ def test_scratch_poison_tool_works():
     assert (out == 0x7FC0DEAD).all()
 
 
-def _geometry_for(n_fft, layout, var):
-    """(system, cp, S, plan options) that make the plan pick `layout`."""
-    env = {}
-    if layout == 1:
-        if n_fft >= 512:
-            env["fir_valu"] = 1
-            return "WOLA", 32, 16, env
-        if var >= 2:
-            env["fir_valu"] = 1                                                   # (else the masked variants run layout 9)
-        return ("wtx", 32 if n_fft == 256 else 16, 16 if var >= 2 else 9, env)   # a mask forces one symbol per wave
-    if layout in (9, 15):                                                         # Tx mask + matrix-pipe FIR: strides 4 | B, B >= N
-        if layout == 9 and n_fft == 256 and var == 3:
-            env["dft_valu"] = 1                                                   # (else the fast-convolution mask runs layout 15)
-        return ("wtx" if n_fft >= 256 else "WOLA"), 32 if n_fft >= 256 else 16, 16, env
-    if layout == 2:
-        env.update(fir_valu=1, max_spw=2)
-        return "wtx", 32 if n_fft == 256 else 16, 16, env
-    if layout in (4, 5):
-        env["fir_valu"] = 1
-        return ("wtx" if layout == 4 else "CPW"), 32, 16, env        # strides 288 / 293
-    if layout in (6, 7, 10, 11):
-        if layout in (6, 7):
-            env["dft_valu"] = 1
-        return "wtx", (32 if layout in (6, 10) else 48), 16, env        # strides 288 / 304
-    assert layout in (8, 12)
-    if layout == 8:
-        env["dft_valu"] = 1
-    return "WOLA", 32, 16, env
-
-
-@pytest.mark.parametrize("n_fft,k,layout,inject,var", _spilling_kernels())
+@pytest.mark.parametrize("n_fft,k,layout,inject,var", spilling_rows())
 def test_every_spilling_production_kernel(channels, n_fft, k, layout, inject, var):
     import torch
     from wofdm_amd import channel_mask as CM
-    system, cp, S, env = _geometry_for(n_fft, layout, var)
-    if var == 2 and n_fft <= 256:
-        env["txmask_direct"] = 1
+    system, cp, S, env = _geometry_for(n_fft, layout, var)        # (with txmask_direct for the direct-form mask at N <= 256)
     st = W.make_structure(system, n_fft, cp)
     w_tx, w_rx = W.tx_rc_window(st).astype(np.float32), W.rx_rc_window(st).astype(np.float32)
     snrs = np.array([5.0, 15.0, 25.0], np.float32) + (k - 4) * 3.0     # BER 0.3 ... 0.01 for every k

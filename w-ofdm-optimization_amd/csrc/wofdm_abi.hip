@@ -149,9 +149,17 @@ int configure(wofdm_plan *pl)
 #ifndef WOFDM_DEV_LDS_PAD
 #define WOFDM_DEV_LDS_PAD 0
 #endif
-    const unsigned lds = wofdm_lds_bytes(g.N, g.T, layout, g.S, g.B)
-                         + (var == WOFDM_VAR_TXMASK ? wofdm_txmask_lds_bytes(g.N) : 0u)
-                         + (var == WOFDM_VAR_TXFFT && layout != 15 ? wofdm_txfft_lds_bytes() : 0u) + (unsigned)(WOFDM_DEV_LDS_PAD);
+    const auto lds_of = [&](int lay) {
+        return wofdm_lds_bytes(g.N, g.T, lay, g.S, g.B)
+               + (var == WOFDM_VAR_TXMASK ? wofdm_txmask_lds_bytes(g.N) : 0u)
+               + (var == WOFDM_VAR_TXFFT && lay != 15 ? wofdm_txfft_lds_bytes() : 0u) + (unsigned)(WOFDM_DEV_LDS_PAD);
+    };
+    // (layouts 8 / 12 pitch their LDS rows by (B + 3) & ~3 words: at N = 1024 a stride that is no multiple of four can need more
+    // than the 160 KiB where the VALU kernel with one symbol per wave, which keeps the frame as it is on air, still fits)
+    if (!masked && layout != 1 && wofdm_layout_info(layout, g.N).fir == WOFDM_FIR_ONE && lds_of(layout) > 160u * 1024u
+        && lds_of(1) <= 160u * 1024u)
+        layout = 1;
+    const unsigned lds = lds_of(layout);
     if (lds > 160u * 1024u)
         return fail(WOFDM_E_UNSUPPORTED, "frame needs %u bytes of LDS (160 KiB per workgroup)", lds);
     wofdm_kernel_fn fn[4];
