@@ -218,6 +218,30 @@ int wofdm_run_injected(const wofdm_cfg *cfg, int device, const float *w_tx, cons
 int wofdm_interference(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx,
                        const float *h, float *power);
 
+/* The same closed form for the system of main_channel_mask.m: only the bins flagged in active[n_fft] carry data
+ * (zero padding + ifftshift, matlab/main_channel_mask.m:387-390; NULL = every bin loaded) and every windowed symbol
+ * passes the spectral Tx mask tx_mask[2P-1] (dft_rc_filt, main_channel_mask.m:398-417; the semantics of
+ * wofdm_plan_set_tx_mask; NULL = no mask), inside calculate_interference (matlab/main_interference_calculation.m:177-225).
+ * The mask's spill into the next symbol's row lengthens the on-air pulse of a symbol to B + P - 1 samples, so three
+ * symbol periods carry energy: power[pairs][n_channels][n_fft] = sum_{n' != n} |A_0[n,n']|^2 + sum_{m=1,2} sum_{n'}
+ * |A_m[n,n']|^2 over the loaded bins n' and wanted[pairs][n_channels][n_fft] (or NULL) = |A_0[n,n]|^2, which the mask
+ * attenuates too; both are 0 on unloaded bins n.  The masked pulses are formed on the device once per window pair, not
+ * per channel (they take pairs * n_fft * (B + P - 1) complex samples of device memory); the mask's impulse response is
+ * prepared once per call (host, double precision, stored in single).  Uses the cfg fields wofdm_interference uses,
+ * every n_fft in {64, 128, 256, 512, 1024}, under the same geometry limits and no further one: cp + cs - tail_tx <= 64,
+ * tail_tx <= 16, tail_rx <= 64, n_taps <= 21, and cp + cs <= 64 at n_fft = 1024 -- within them the pulse with the
+ * channel always ends inside the three periods; outside them, or with more than 65535 window pairs,
+ * WOFDM_E_UNSUPPORTED.  Non-finite gains or an allocation without a loaded bin are WOFDM_E_INVALID.  Every argument is
+ * checked before the device is touched, and a failed call leaves power and wanted as they were.  With active == NULL and
+ * tx_mask == NULL power holds the bits wofdm_interference gives; every sum is formed in a fixed order: repeated
+ * calls give identical results.  Synchronous; host pointers; holds the same gate as wofdm_interference from its device
+ * synchronisation to the end of its kernels. */
+int wofdm_interference_masked(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx,
+                              const float *h, const uint8_t *active /* [n_fft] or NULL */,
+                              const float *tx_mask /* [2P-1] or NULL */,
+                              float *power  /* [pairs][n_channels][n_fft] */,
+                              float *wanted /* same shape, or NULL */);
+
 /* Tx-side spectrum estimate: the waveform of no_symbols consecutive symbols X[no_symbols][n_fft][2] (host,
  * complex values on the bins, zeros on unloaded ones) through IDFT, CP/CS copy, Tx window w_tx[P] and the
  * overlap-add of `overlap` tail samples (tail_tx for the Tx-windowed structures, 0 otherwise), then the sum

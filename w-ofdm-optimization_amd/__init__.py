@@ -28,7 +28,7 @@ from .simulation import (Plan, ber_for_window_file, error_rates, make_cfg,  # no
                          save_ber_results, simulation_fun, wOFDMSystem)
 from ._lib import kernel_source_hash  # noqa: F401
 from .timefreq import run_timefreq, tx_psd_batch_gpu, tx_waveform  # noqa: F401
-from .channel_mask import spectrum_for_window_file  # noqa: F401
+from .channel_mask import interference_for_window_file, spectrum_for_window_file  # noqa: F401
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

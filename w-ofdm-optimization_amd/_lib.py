@@ -30,6 +30,7 @@ EXPORTS = (
     "wofdm_run_injected", "wofdm_philox_kat", "wofdm_plan_set_allocation",
     "wofdm_plan_set_tx_mask", "wofdm_plan_status", "wofdm_plan_kernel_id", "wofdm_plan_set_option",
     "wofdm_interference", "wofdm_tx_psd", "wofdm_tx_psd_batch", "wofdm_tx_psd_batch_masked",
+    "wofdm_interference_masked",
 )
 
 
@@ -131,6 +132,7 @@ def load():
     L.wofdm_run_injected.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_philox_kat.argtypes = [C.c_int, vp, vp, vp]
     L.wofdm_interference.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp]
+    L.wofdm_interference_masked.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_tx_psd.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, C.c_int, C.c_int, vp]
     i32 = C.c_int32
     L.wofdm_tx_psd_batch.argtypes = [i32, C.c_int, i32, vp, vp, i32, i32, vp, vp]

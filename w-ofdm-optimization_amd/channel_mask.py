@@ -6,7 +6,8 @@ in both only the centre half of the spectrum carries data.  The frame loop runs 
 ``Plan.set_allocation`` (zero padding + ifftshift of lines 387-390, bin selection of 367-369) and
 ``Plan.set_tx_mask`` (``dft_rc_filt``, 398-417).  ``spectrum_for_window_file`` is the spectrum side of the same
 experiment: the periodogram and out-of-band radiation of the plain and of the masked waveform
-(``wofdm_tx_psd_batch_masked``).
+(``wofdm_tx_psd_batch_masked``); ``interference_for_window_file`` is its deterministic side, the closed-form ICI +
+ISI power of the same two systems (``wofdm_interference_masked``): what the mask costs next to what it buys.
 
 BER is accumulated over the whole ensemble here as there (lines 341-359).  The reference sends
 the same data bits through both runs with independent noise (two ``add_wgn`` calls); here the
@@ -151,6 +152,43 @@ def spectrum_for_window_file(type_ofdm, cp, windows, num_subcar=256, symbols=Non
         out[name] = {"psd": plain, "psd_masked": masked, "obr": plain[unloaded].mean(),
                      "obr_masked": masked[unloaded].mean(), "f_axis": f_axis}
     return out
+
+
+def interference_for_window_file(type_ofdm, cp, windows, channels, num_subcar=256, roll_off=ROLL_OFF, gpu=True,
+                                 device=0, tail_tx=8, tail_rx=10):
+    """Interference companion of ``ber_for_window_file`` and ``spectrum_for_window_file``: what the mask costs.
+    Every window pair of the file + the RC pair under half-band loading, for every channel [n_channels][taps]:
+    the closed-form ICI + ISI power per subcarrier and the wanted power |A_0[n, n]|^2, plain and masked -- on the
+    GPU two ``wofdm_interference_masked`` calls over all pairs and channels (one with the mask, one with the
+    allocation alone; gpu=False: the fp64 host mirror ``interference.interf_power_masked``).  Returns {name:
+    {"power", "power_masked", "wanted", "wanted_masked"}}, each [n_channels][N], with the names of
+    ``V.matlab_pair_plan``; SIR per subcarrier = wanted / power on the loaded bins (both are 0 on the others)."""
+    from . import interference as I
+    n = num_subcar
+    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
+                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
+    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
+    plan = V.matlab_pair_plan(type_ofdm)
+
+    def pick(key, side):
+        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
+
+    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
+    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
+    h = np.atleast_2d(np.asarray(channels))
+    alloc = half_band_allocation(n)
+    mask = tx_mask(st.sym_len, roll_off)
+    if gpu:
+        plain = I.interf_power_masked_gpu(st, w_tx, w_rx, h, active=alloc, device=device)
+        masked = I.interf_power_masked_gpu(st, w_tx, w_rx, h, active=alloc, mask=mask, device=device)
+    else:
+        def host(m):
+            res = [[I.interf_power_masked(st, wt, wr, hc, active=alloc, mask=m) for hc in h]
+                   for wt, wr in zip(w_tx, w_rx)]
+            return (np.array([[r[0] for r in row] for row in res]), np.array([[r[1] for r in row] for row in res]))
+        plain, masked = host(None), host(mask)
+    return {name: {"power": plain[0][i], "wanted": plain[1][i], "power_masked": masked[0][i],
+                   "wanted_masked": masked[1][i]} for i, (name, _) in enumerate(plan)}
 
 
 def results_from_counts(names, masked, plain):

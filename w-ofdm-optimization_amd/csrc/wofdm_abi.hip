@@ -1045,6 +1045,101 @@ int wofdm_interference(const wofdm_cfg *cfg, int device, const float *w_tx, cons
     return rc;
 }
 
+// Every argument is checked before the first HIP call.
+int wofdm_interference_masked(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx,
+                              const float *h, const uint8_t *active, const float *tx_mask, float *power,
+                              float *wanted)
+{
+    if (!cfg || !w_tx || !w_rx || !h || !power) return fail(WOFDM_E_INVALID, "NULL argument");
+    if (!active && !tx_mask && !wanted) return wofdm_interference(cfg, device, w_tx, w_rx, h, power);
+    geom g;
+    int rc = check_cfg(cfg, &g);
+    if (rc) return rc;
+    if (cfg->n_window_pairs > 65535) return fail(WOFDM_E_UNSUPPORTED, "more than 65535 window pairs");
+    const int Lm = 2 * g.P - 1, J = g.B + g.P - 1, JP = (J + 1) & ~1;
+    // (check_cfg leaves tail_tx <= 16 and n_taps <= 21 against B >= 64: the filtered pulse ends within three periods)
+    if (J + WOFDM_LT - 1 > 3 * g.B)
+        return fail(WOFDM_E_UNSUPPORTED, "the masked pulse with the channel exceeds three symbol periods");
+    std::vector<uint8_t> hact;
+    if (active) {
+        hact.resize((size_t)g.N);
+        int n_act = 0;
+        for (int n = 0; n < g.N; ++n) n_act += (hact[(size_t)n] = active[n] ? 1 : 0);
+        if (n_act == 0) return fail(WOFDM_E_INVALID, "the allocation loads no subcarrier");
+    }
+    if (tx_mask)
+        for (int i = 0; i < Lm; ++i)
+            if (!std::isfinite(tx_mask[i])) return fail(WOFDM_E_INVALID, "mask gains must be finite");
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev)
+        return fail(WOFDM_E_HIP, "device %d not available (%d visible); there is no CPU fallback", device, ndev);
+    HIP_TRY(hipSetDevice(device));
+    // impulse response of the mask, g = IDFT_{2P-1}(gains): host, double precision, stored in single
+    std::vector<float2> hg;
+    if (tx_mask) {
+        const std::vector<cplx> gd = idft_any(tx_mask, Lm);
+        hg.resize((size_t)Lm);
+        for (int i = 0; i < Lm; ++i) hg[(size_t)i] = make_float2((float)gd[(size_t)i].real(), (float)gd[(size_t)i].imag());
+    }
+    const int pairs = cfg->n_window_pairs, jobs = pairs * cfg->n_channels;
+    const size_t n_wtx = (size_t)pairs * g.P, n_wrx = (size_t)pairs * (g.N + g.delta);
+    const size_t n_cols = (size_t)pairs * g.N * JP, n_out = (size_t)jobs * g.N;
+    std::vector<float2> hp((size_t)cfg->n_channels * WOFDM_LT, make_float2(0.f, 0.f));
+    for (int c = 0; c < cfg->n_channels; ++c)
+        for (int l = 0; l < g.L; ++l)
+            hp[(size_t)c * WOFDM_LT + l] = make_float2(h[2 * ((size_t)c * g.L + l)], h[2 * ((size_t)c * g.L + l) + 1]);
+    float *d_wtx = nullptr, *d_wrx = nullptr, *d_pow = nullptr, *d_want = nullptr;
+    float2 *d_h = nullptr, *d_g = nullptr, *d_cols = nullptr;
+    uint8_t *d_act = nullptr;
+    do {
+        if (hipMalloc(&d_wtx, n_wtx * 4) != hipSuccess || hipMalloc(&d_wrx, n_wrx * 4) != hipSuccess ||
+            hipMalloc(&d_h, hp.size() * 8) != hipSuccess || hipMalloc(&d_pow, n_out * 4) != hipSuccess ||
+            (wanted && hipMalloc(&d_want, n_out * 4) != hipSuccess) || hipMalloc(&d_cols, n_cols * 8) != hipSuccess ||
+            (tx_mask && hipMalloc(&d_g, hg.size() * 8) != hipSuccess) ||
+            (active && hipMalloc(&d_act, hact.size()) != hipSuccess)) {
+            rc = fail(WOFDM_E_NOMEM, "device allocation failed (the pulses of %d pairs take %lld bytes)", pairs,
+                      (long long)(n_cols * 8));
+            break;
+        }
+        if (hipMemcpy(d_wtx, w_tx, n_wtx * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_wrx, w_rx, n_wrx * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_h, hp.data(), hp.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            (tx_mask && hipMemcpy(d_g, hg.data(), hg.size() * 8, hipMemcpyHostToDevice) != hipSuccess) ||
+            (active && hipMemcpy(d_act, hact.data(), hact.size(), hipMemcpyHostToDevice) != hipSuccess)) {
+            rc = fail(WOFDM_E_HIP, "upload failed"); break;
+        }
+        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        (void)hipDeviceSynchronize();
+        hipError_t e = hipErrorInvalidValue;
+#define WOFDM_INTERF_MASKED_LAUNCH(n)                                                                                    \
+    if (g.N == n) e = wofdm_interf_masked_launch_n##n(pairs, cfg->n_channels, g.P, g.B, g.mu, g.delta, g.gamma, g.kappa, \
+                                                      JP, d_wtx, d_wrx, d_h, d_g, d_act, d_cols, d_pow, d_want, nullptr)
+        WOFDM_INTERF_MASKED_LAUNCH(64);
+        WOFDM_INTERF_MASKED_LAUNCH(128);
+        WOFDM_INTERF_MASKED_LAUNCH(256);
+        WOFDM_INTERF_MASKED_LAUNCH(512);
+        WOFDM_INTERF_MASKED_LAUNCH(1024);
+#undef WOFDM_INTERF_MASKED_LAUNCH
+        if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(power, d_pow, n_out * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            (wanted && hipMemcpy(wanted, d_want, n_out * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
+            rc = fail(WOFDM_E_HIP, "masked interference kernels or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
+            break;
+        }
+    } while (0);
+    if (d_wtx) (void)hipFree(d_wtx);
+    if (d_wrx) (void)hipFree(d_wrx);
+    if (d_h) (void)hipFree(d_h);
+    if (d_pow) (void)hipFree(d_pow);
+    if (d_want) (void)hipFree(d_want);
+    if (d_g) (void)hipFree(d_g);
+    if (d_cols) (void)hipFree(d_cols);
+    if (d_act) (void)hipFree(d_act);
+    return rc;
+}
+
 int wofdm_tx_psd(const wofdm_cfg *cfg, int device, const float *w_tx, const float *X, int no_symbols,
                  int overlap, float *psd)
 {

@@ -405,3 +405,18 @@ WOFDM_PSD_BATCH_MASKED_DECL(128);
 WOFDM_PSD_BATCH_MASKED_DECL(256);
 WOFDM_PSD_BATCH_MASKED_DECL(512);
 WOFDM_PSD_BATCH_MASKED_DECL(1024);
+
+// Closed-form ICI/ISI power of the half-band, masked system (wofdm_interference_masked; the -DWOFDM_TU_K=0 units): the masked
+// on-air pulses of every loaded bin once per window pair into cols[pairs][n_fft][JP] (J = B + P - 1 samples each, JP >= J the
+// row pitch), then one workgroup per (pair, channel) job.  g: the mask's circular impulse response [2P - 1], or null = no
+// mask; amask: [n_fft] 0 / 1, or null = every bin loaded; wanted may be null.
+#define WOFDM_INTERF_MASKED_DECL(n)                                                                                    \
+    hipError_t wofdm_interf_masked_launch_n##n(int pairs, int n_ch, int P, int B, int mu, int delta, int gam, int kap,  \
+                                               int JP, const float *wtx, const float *wrx, const float2 *h,             \
+                                               const float2 *g, const uint8_t *amask, float2 *cols, float *power,       \
+                                               float *wanted, hipStream_t s)
+WOFDM_INTERF_MASKED_DECL(64);
+WOFDM_INTERF_MASKED_DECL(128);
+WOFDM_INTERF_MASKED_DECL(256);
+WOFDM_INTERF_MASKED_DECL(512);
+WOFDM_INTERF_MASKED_DECL(1024);

@@ -4554,6 +4554,212 @@ wofdm_txmask_ola_kernel(const wofdm_bjob *__restrict__ jobs, const wofdm_mjob *_
     x[jb.x_off + n] = make_float2(val.x, val.y);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Closed-form ICI + ISI power of the half-band, spectrally masked system (wofdm_interference_masked):
+//   zero padding + ifftshift  matlab/main_channel_mask.m:387-390
+//   dft_rc_filt               matlab/main_channel_mask.m:398-417
+//   calculate_interference    matlab/main_interference_calculation.m:177-225
+// The mask turns the Tx column of bin n' into y = g (*) x (circular, length 2P - 1, g = the mask's impulse response);
+// y[0, P) stays in the symbol's row and y[P, 2P - 1) goes into the next one, B samples later, so the on-air pulse is
+//   u[j] = [j < P] y[j] + [B <= j < B + P - 1] y[P + j - B],   j < J = B + P - 1,
+// and with the channel it covers three symbol periods: A_m, m = 0, 1, 2 (J + L - 1 <= 3 B for every supported
+// geometry: tail_tx + L - 2 <= 35 < 64 <= B).
+//
+// Stage 1, once per window pair (the pulses do not depend on the channel): u is linear in x[c] = w_tx[c]
+// e^{2 pi i ((c - mu) mod N) n' / N} / N, so for a fixed j the pulses of ALL bins are one N-point inverse DFT,
+//   u[j][n'] = 1/N sum_t q_j[t] e^{2 pi i t n' / N},   q_j[t] = sum_{c < P, c = t + mu (mod N)} G[j][c] w_tx[c],
+//   G[j][c] = [j < P] g[(j - c) mod (2P - 1)] + [B <= j < B + P - 1] g[j - B + P - c]
+// -- a wave per sample j: it folds row j of G onto the N points and transforms; O(J (P + N log N)) per pair instead
+// of O(J P N).  No mask (g == nullptr): u[j][n'] = x[j] itself, from the exponential table as wofdm_interf_kernel
+// forms it.  cols[pair][n'][JP] holds the pulses, a row per bin; rows of unloaded bins are not written (nor read).
+struct wofdm_mparams {
+    int P, B, mu, delta, gam, kap, n_ch, J, JP;    // J = B + P - 1 pulse samples, JP = row pitch of cols
+    float *power, *wanted;                         // [pairs][n_ch][N]; wanted may be null
+};
+template <int N> struct interfm_geo {
+    // (the waves of wofdm_interf_kernel: the same columns per wave and the same order of the sums, so that without mask and
+    // allocation the power comes out bit for bit as there)
+    static constexpr int WAVES = interf_geo<N>::WAVES;
+    static constexpr int RB3 = 3 * (N / 64 + 1);                      // FIR outputs per lane over 3B <= 3N + 192 samples
+    static constexpr int CH = RB3 <= 6 ? RB3 : (RB3 % 5 == 0 ? 5 : 6);
+    // 24 zeros (>= LT - 1 of history) + 64 RB3 samples: the last lane's FIR window ends at 64 RB3 + 23
+    static constexpr int ROWLEN = 24 + 64 * RB3;
+    // FFT stage twiddles [N] | w_rx [N + 64] | per wave: row [ROWLEN] + scratch [N]
+    static constexpr int LDS = 8 * N + 4 * (N + 64) + WAVES * 8 * (ROWLEN + N);
+    static_assert(LDS <= 160 * 1024 && WAVES * N * 4 <= WAVES * 8 * (ROWLEN + N), "LDS");
+    static constexpr int PWAVES = N >= 512 ? 8 : 16;                  // pulse kernel: twiddles + e^{..} table + scratch rows
+    static constexpr int PLDS = 8 * N * (2 + PWAVES);
+};
+
+template <int N>
+__global__ void __launch_bounds__(interfm_geo<N>::PWAVES * 64)
+wofdm_interf_pulse_kernel(const wofdm_mparams p, const float *__restrict__ g_wtx, const float2 *__restrict__ g,
+                          const uint8_t *__restrict__ amask, float2 *__restrict__ cols)
+{
+    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ, WAVES = interfm_geo<N>::PWAVES;
+    constexpr bool FULL = geo<N>::FULL;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    v2f *wn = tw + N;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    v2f *scr = wn + N + (size_t)wv * N;
+    fill_twiddles<N>(tw, tid, WAVES * 64);
+    for (int i = tid; i < N; i += WAVES * 64) {
+        float sv, cv;
+        sincospif(2.0f * (float)i / (float)N, &sv, &cv);
+        wn[i] = mk(cv, sv);
+    }
+    __syncthreads();
+    const int pair = blockIdx.y, j = blockIdx.x * WAVES + wv;
+    const int P = p.P, B = p.B, L = 2 * P - 1;
+    if (j >= p.J) return;
+    const float *__restrict__ wtx = g_wtx + (size_t)pair * P;
+    v2f v[1][BPL][4];
+    if (g == nullptr) {
+        // u[j][n'] = x[j] = w_tx[j] e^{2 pi i ((j - mu) mod N) n' / N} / N (j < P), as wofdm_interf_kernel's Tx column
+        const int t = (j - p.mu) & (N - 1);
+        const float w = j < P ? wtx[j] * (1.0f / (float)N) : 0.f;
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[0][q][r] = wn[(t * (lane + 64 * q + r * NQ)) & (N - 1)] * w;
+    } else {
+        const bool own = j < P, spill = j >= B;                  // (j < J = B + P - 1 here)
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v2f a = mk(0.f, 0.f);
+                if (FULL || lane + 64 * q < NQ) {
+                    for (int c = (lane + 64 * q + r * NQ + p.mu) & (N - 1); c < P; c += N) {
+                        v2f gg = mk(0.f, 0.f);
+                        if (own) {
+                            const int i = j - c;
+                            gg = ldg2(g + (i < 0 ? i + L : i));
+                        }
+                        if (spill) gg = gg + ldg2(g + (j - B + P - c));     // in [1, 2P - 2]
+                        a = a + gg * wtx[c];
+                    }
+                }
+                v[0][q][r] = a;
+            }
+        fft_wave<N, +1, 1>(v, scr, 0, tw, lane);                 // N u[j][n']
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[0][q][r] = v[0][q][r] * (1.0f / (float)N);
+    }
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int np = lane + 64 * q + r * NQ;
+            if (!(FULL || lane + 64 * q < NQ) || (amask != nullptr && amask[np] == 0)) continue;
+            cols[((size_t)pair * N + np) * p.JP + j] = make_float2(v[0][q][r].x, v[0][q][r].y);
+        }
+}
+
+// Stage 2, one workgroup per (window pair, channel): wofdm_interf_kernel's pattern over the pulses of stage 1 -- FIR over
+// three periods, per period Rx window / fold / shift + DFT, |.|^2 row sums in registers -- with the wanted term
+// |A_0[n, n]|^2 kept apart and written out, the columns of unloaded bins skipped and the rows of unloaded bins zero.
+template <int N>
+__global__ void __launch_bounds__(interfm_geo<N>::WAVES * 64)
+wofdm_interf_masked_kernel(const wofdm_mparams p, const float *__restrict__ g_wrx, const float2 *__restrict__ g_h_,
+                           const uint8_t *__restrict__ amask, const float2 *__restrict__ cols)
+{
+    constexpr int WAVES = interfm_geo<N>::WAVES, RB3 = interfm_geo<N>::RB3, ROWLEN = interfm_geo<N>::ROWLEN, LT = WOFDM_LT;
+    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ;
+    constexpr bool FULL = geo<N>::FULL;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    float *wrx = reinterpret_cast<float *>(tw + N);
+    v2f *rows = reinterpret_cast<v2f *>(wrx + N + 64);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int job = blockIdx.x, pair = job / p.n_ch, ch = job - pair * p.n_ch;
+    const int B = p.B;
+    fill_twiddles<N>(tw, tid, WAVES * 64);
+    for (int i = tid; i < N + p.delta; i += WAVES * 64) wrx[i] = g_wrx[(size_t)pair * (N + p.delta) + i];
+    v2f *row = rows + (size_t)wv * (ROWLEN + N);
+    v2f *scr = row + ROWLEN;
+    for (int i = lane; i < ROWLEN; i += 64) row[i] = mk(0.f, 0.f);
+    __syncthreads();
+    const v2f *__restrict__ taps = reinterpret_cast<const v2f *>(g_h_) + (size_t)ch * LT;
+    float pw[BPL][4], ww[BPL][4];
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pw[q][r] = ww[q][r] = 0.f;
+    const int h2 = p.delta >> 1;
+    for (int np = wv; np < N; np += WAVES) {
+        if (amask != nullptr && amask[np] == 0) continue;          // (wave-uniform) an unloaded bin transmits nothing
+        const float2 *__restrict__ col = cols + ((size_t)pair * N + np) * p.JP;
+        for (int j = lane; j < p.J; j += 64) row[24 + j] = ldg2(col + j);
+        for (int j = p.J + lane; j < ROWLEN - 24; j += 64) row[24 + j] = mk(0.f, 0.f);
+        wave_sync();
+        // z = conv(h, u) over three symbol periods: lane -> RB3 consecutive outputs from j0
+        v2f acc[RB3];
+        const int j0 = lane * RB3;
+        fir_lane<RB3, interfm_geo<N>::CH>(row + 24 - (LT - 1) + j0, taps, acc);
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < RB3; ++r)
+            if (j0 + r < 3 * B) row[24 + j0 + r] = acc[r];
+        wave_sync();
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            // Rx window, fold, circular shift (m:297-355) of period m, then the DFT
+            const v2f *fb = row + 24 + m * B;
+            v2f v[1][BPL][4];
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    v[0][q][r] = mk(0.f, 0.f);
+                    if (!(FULL || lane + 64 * q < NQ)) continue;
+                    const int m0 = (lane + 64 * q + r * NQ + p.kap + h2) & (N - 1);
+                    v2f z = fb[p.gam + m0] * wrx[m0];
+                    if (m0 < p.delta) {
+                        const float w2 = wrx[m0 + N];
+                        z = __builtin_elementwise_fma(mk(w2, w2), fb[p.gam + m0 + N], z);
+                    }
+                    v[0][q][r] = z;
+                }
+            fft_wave<N, -1, 1>(v, scr, 0, tw, lane);
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int n = lane + 64 * q + r * NQ;
+                    const float e = v[0][q][r].x * v[0][q][r].x + v[0][q][r].y * v[0][q][r].y;
+                    if (!(FULL || lane + 64 * q < NQ)) continue;
+                    if (m == 0 && n == np) ww[q][r] += e;          // the wanted term A_0[n, n]
+                    else pw[q][r] += e;
+                }
+        }
+        wave_sync();
+    }
+    // sums over the waves in wave order (each wave's row is free now): float [WAVES][N] in the rows area, power then wanted
+    float *red = reinterpret_cast<float *>(rows);
+    for (int pass = 0; pass < 2; ++pass) {
+        float *dst = pass == 0 ? p.power : p.wanted;
+        if (dst == nullptr) break;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (FULL || lane + 64 * q < NQ) red[wv * N + lane + 64 * q + r * NQ] = pass == 0 ? pw[q][r] : ww[q][r];
+        __syncthreads();
+        for (int n = tid; n < N; n += WAVES * 64) {
+            float t = 0.f;
+            for (int w = 0; w < WAVES; ++w) t += red[w * N + n];
+            dst[(size_t)job * N + n] = (amask != nullptr && amask[n] == 0) ? 0.f : t;
+        }
+    }
+}
+
 __global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
 {
     if (threadIdx.x == 0) {
@@ -4720,6 +4926,34 @@ hipError_t WOFDM_CAT(wofdm_psd_batch_masked_launch_n, WOFDM_TU_N)(int n_jobs, in
     hipLaunchKernelGGL(wofdm_psd_batch_kernel<FL>, dim3(n_items), dim3(512), lds_b, s, jobs, items, (const float2 *)x, partial);
     hipLaunchKernelGGL(wofdm_psd_reduce_kernel<FL>, dim3((FL + 255) / 256, n_jobs), dim3(256), 0, s, jobs,
                        (const float *)partial, psd);
+    return hipGetLastError();
+}
+#endif
+
+#if WOFDM_TU_K == 0
+// wofdm_interference_masked: the pulses of every pair, then the (pair, channel) jobs; the -DWOFDM_TU_K=0 units
+hipError_t WOFDM_CAT(wofdm_interf_masked_launch_n, WOFDM_TU_N)(int pairs, int n_ch, int P, int B, int mu, int delta, int gam,
+                                                               int kap, int JP, const float *wtx, const float *wrx,
+                                                               const float2 *h, const float2 *g, const uint8_t *amask,
+                                                               float2 *cols, float *power, float *wanted, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N, W = interfm_geo<N>::WAVES, PW = interfm_geo<N>::PWAVES;
+    wofdm_mparams mp;
+    mp.P = P; mp.B = B; mp.mu = mu; mp.delta = delta; mp.gam = gam; mp.kap = kap; mp.n_ch = n_ch;
+    mp.J = B + P - 1; mp.JP = JP;
+    mp.power = power; mp.wanted = wanted;
+    // the row of a wave holds three periods: 3 B <= 64 RB3, and the pulse with the channel ends within them
+    if (3 * B > 64 * interfm_geo<N>::RB3 || mp.J + WOFDM_LT - 1 > 3 * B || JP < mp.J || delta > 64) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_interf_pulse_kernel<N>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, interfm_geo<N>::PLDS);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_interf_masked_kernel<N>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, interfm_geo<N>::LDS);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_interf_pulse_kernel<N>, dim3((mp.J + PW - 1) / PW, pairs), dim3(PW * 64), interfm_geo<N>::PLDS, s,
+                       mp, wtx, g, amask, cols);
+    hipLaunchKernelGGL(wofdm_interf_masked_kernel<N>, dim3(pairs * n_ch), dim3(W * 64), interfm_geo<N>::LDS, s, mp, wrx, h,
+                       amask, (const float2 *)cols);
     return hipGetLastError();
 }
 #endif
