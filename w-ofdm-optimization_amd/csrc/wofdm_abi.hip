@@ -348,6 +348,40 @@ int check_launch_args(wofdm_plan *pl, uint64_t frames_per_cell)
     return WOFDM_OK;
 }
 
+// ---- the auxiliary entry points (wofdm_interference*, wofdm_tx_psd*) ----
+
+// Owner of a device allocation: whichever way its entry point returns, everything is freed.
+template <typename T> struct dev_buf {
+    T *p = nullptr;
+    dev_buf() = default;
+    dev_buf(dev_buf &&o) noexcept : p(o.p) { o.p = nullptr; }      // (move-only: the copy operations are deleted with it)
+    ~dev_buf() { if (p) (void)hipFree(p); }
+    bool alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)) == hipSuccess; }
+    bool upload(const void *host, size_t count) { return hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice) == hipSuccess; }
+    operator T *() const { return p; }
+};
+
+// the device an auxiliary entry point runs on, made current
+int use_device(int device)
+{
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev)
+        return fail(WOFDM_E_HIP, "device %d not available (%d visible); there is no CPU fallback", device, ndev);
+    HIP_TRY(hipSetDevice(device));
+    return WOFDM_OK;
+}
+
+// the channels' taps as the kernels read them: [n_channels][WOFDM_LT] float2, zero padded
+std::vector<float2> pack_taps(const wofdm_cfg *cfg, const geom &g, const float *h)
+{
+    std::vector<float2> hp((size_t)cfg->n_channels * WOFDM_LT, make_float2(0.f, 0.f));
+    for (int c = 0; c < cfg->n_channels; ++c)
+        for (int l = 0; l < g.L; ++l)
+            hp[(size_t)c * WOFDM_LT + l] = make_float2(h[2 * ((size_t)c * g.L + l)], h[2 * ((size_t)c * g.L + l) + 1]);
+    return hp;
+}
+
 }  // namespace
 
 extern "C" {
@@ -999,50 +1033,28 @@ int wofdm_interference(const wofdm_cfg *cfg, int device, const float *w_tx, cons
     geom g;
     int rc = check_cfg(cfg, &g);
     if (rc) return rc;
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev)
-        return fail(WOFDM_E_HIP, "device %d not available (%d visible); there is no CPU fallback", device, ndev);
-    HIP_TRY(hipSetDevice(device));
+    if ((rc = use_device(device)) != WOFDM_OK) return rc;
     const int jobs = cfg->n_window_pairs * cfg->n_channels;
     const size_t n_wtx = (size_t)cfg->n_window_pairs * g.P, n_wrx = (size_t)cfg->n_window_pairs * (g.N + g.delta);
-    std::vector<float2> hp((size_t)cfg->n_channels * WOFDM_LT, make_float2(0.f, 0.f));
-    for (int c = 0; c < cfg->n_channels; ++c)
-        for (int l = 0; l < g.L; ++l)
-            hp[(size_t)c * WOFDM_LT + l] = make_float2(h[2 * ((size_t)c * g.L + l)], h[2 * ((size_t)c * g.L + l) + 1]);
-    float *d_wtx = nullptr, *d_wrx = nullptr, *d_pow = nullptr;
-    float2 *d_h = nullptr;
-    rc = WOFDM_OK;
-    do {
-        if (hipMalloc(&d_wtx, n_wtx * 4) != hipSuccess || hipMalloc(&d_wrx, n_wrx * 4) != hipSuccess ||
-            hipMalloc(&d_h, hp.size() * 8) != hipSuccess || hipMalloc(&d_pow, (size_t)jobs * g.N * 4) != hipSuccess) {
-            rc = fail(WOFDM_E_NOMEM, "device allocation failed"); break;
-        }
-        if (hipMemcpy(d_wtx, w_tx, n_wtx * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_wrx, w_rx, n_wrx * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_h, hp.data(), hp.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-            rc = fail(WOFDM_E_HIP, "upload failed"); break;
-        }
-        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
-        std::lock_guard<std::mutex> gate(g_gate_mu);
-        (void)hipDeviceSynchronize();
-        hipError_t e = hipErrorInvalidValue;
-        if (g.N == 64) e = wofdm_interf_launch_n64(jobs, g.P, g.B, g.mu, g.delta, g.gamma, g.kappa, cfg->n_channels, d_wtx, d_wrx, d_h, d_pow, nullptr);
-        if (g.N == 128) e = wofdm_interf_launch_n128(jobs, g.P, g.B, g.mu, g.delta, g.gamma, g.kappa, cfg->n_channels, d_wtx, d_wrx, d_h, d_pow, nullptr);
-        if (g.N == 256) e = wofdm_interf_launch_n256(jobs, g.P, g.B, g.mu, g.delta, g.gamma, g.kappa, cfg->n_channels, d_wtx, d_wrx, d_h, d_pow, nullptr);
-        if (g.N == 512) e = wofdm_interf_launch_n512(jobs, g.P, g.B, g.mu, g.delta, g.gamma, g.kappa, cfg->n_channels, d_wtx, d_wrx, d_h, d_pow, nullptr);
-        if (g.N == 1024) e = wofdm_interf_launch_n1024(jobs, g.P, g.B, g.mu, g.delta, g.gamma, g.kappa, cfg->n_channels, d_wtx, d_wrx, d_h, d_pow, nullptr);
-        if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(power, d_pow, (size_t)jobs * g.N * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-            rc = fail(WOFDM_E_HIP, "interference kernel or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
-            break;
-        }
-    } while (0);
-    if (d_wtx) (void)hipFree(d_wtx);
-    if (d_wrx) (void)hipFree(d_wrx);
-    if (d_h) (void)hipFree(d_h);
-    if (d_pow) (void)hipFree(d_pow);
-    return rc;
+    const size_t n_out = (size_t)jobs * g.N;
+    const std::vector<float2> hp = pack_taps(cfg, g, h);
+    dev_buf<float> d_wtx, d_wrx, d_pow;
+    dev_buf<float2> d_h;
+    if (!d_wtx.alloc(n_wtx) || !d_wrx.alloc(n_wrx) || !d_h.alloc(hp.size()) || !d_pow.alloc(n_out))
+        return fail(WOFDM_E_NOMEM, "device allocation failed");
+    if (!d_wtx.upload(w_tx, n_wtx) || !d_wrx.upload(w_rx, n_wrx) || !d_h.upload(hp.data(), hp.size()))
+        return fail(WOFDM_E_HIP, "upload failed");
+    // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
+    std::lock_guard<std::mutex> gate(g_gate_mu);
+    (void)hipDeviceSynchronize();
+    const wofdm_aux_fns *ax = wofdm_aux(g.N);
+    const hipError_t e = !ax ? hipErrorInvalidValue
+                             : ax->interf(jobs, g.P, g.B, g.mu, g.delta, g.gamma, g.kappa, cfg->n_channels, d_wtx, d_wrx, d_h,
+                                          d_pow, nullptr);
+    if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(power, d_pow, n_out * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(WOFDM_E_HIP, "interference kernel or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
+    return WOFDM_OK;
 }
 
 // Every argument is checked before the first HIP call.
@@ -1070,11 +1082,7 @@ int wofdm_interference_masked(const wofdm_cfg *cfg, int device, const float *w_t
     if (tx_mask)
         for (int i = 0; i < Lm; ++i)
             if (!std::isfinite(tx_mask[i])) return fail(WOFDM_E_INVALID, "mask gains must be finite");
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev)
-        return fail(WOFDM_E_HIP, "device %d not available (%d visible); there is no CPU fallback", device, ndev);
-    HIP_TRY(hipSetDevice(device));
+    if ((rc = use_device(device)) != WOFDM_OK) return rc;
     // impulse response of the mask, g = IDFT_{2P-1}(gains): host, double precision, stored in single
     std::vector<float2> hg;
     if (tx_mask) {
@@ -1085,59 +1093,30 @@ int wofdm_interference_masked(const wofdm_cfg *cfg, int device, const float *w_t
     const int pairs = cfg->n_window_pairs, jobs = pairs * cfg->n_channels;
     const size_t n_wtx = (size_t)pairs * g.P, n_wrx = (size_t)pairs * (g.N + g.delta);
     const size_t n_cols = (size_t)pairs * g.N * JP, n_out = (size_t)jobs * g.N;
-    std::vector<float2> hp((size_t)cfg->n_channels * WOFDM_LT, make_float2(0.f, 0.f));
-    for (int c = 0; c < cfg->n_channels; ++c)
-        for (int l = 0; l < g.L; ++l)
-            hp[(size_t)c * WOFDM_LT + l] = make_float2(h[2 * ((size_t)c * g.L + l)], h[2 * ((size_t)c * g.L + l) + 1]);
-    float *d_wtx = nullptr, *d_wrx = nullptr, *d_pow = nullptr, *d_want = nullptr;
-    float2 *d_h = nullptr, *d_g = nullptr, *d_cols = nullptr;
-    uint8_t *d_act = nullptr;
-    do {
-        if (hipMalloc(&d_wtx, n_wtx * 4) != hipSuccess || hipMalloc(&d_wrx, n_wrx * 4) != hipSuccess ||
-            hipMalloc(&d_h, hp.size() * 8) != hipSuccess || hipMalloc(&d_pow, n_out * 4) != hipSuccess ||
-            (wanted && hipMalloc(&d_want, n_out * 4) != hipSuccess) || hipMalloc(&d_cols, n_cols * 8) != hipSuccess ||
-            (tx_mask && hipMalloc(&d_g, hg.size() * 8) != hipSuccess) ||
-            (active && hipMalloc(&d_act, hact.size()) != hipSuccess)) {
-            rc = fail(WOFDM_E_NOMEM, "device allocation failed (the pulses of %d pairs take %lld bytes)", pairs,
-                      (long long)(n_cols * 8));
-            break;
-        }
-        if (hipMemcpy(d_wtx, w_tx, n_wtx * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_wrx, w_rx, n_wrx * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_h, hp.data(), hp.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            (tx_mask && hipMemcpy(d_g, hg.data(), hg.size() * 8, hipMemcpyHostToDevice) != hipSuccess) ||
-            (active && hipMemcpy(d_act, hact.data(), hact.size(), hipMemcpyHostToDevice) != hipSuccess)) {
-            rc = fail(WOFDM_E_HIP, "upload failed"); break;
-        }
-        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
-        std::lock_guard<std::mutex> gate(g_gate_mu);
-        (void)hipDeviceSynchronize();
-        hipError_t e = hipErrorInvalidValue;
-#define WOFDM_INTERF_MASKED_LAUNCH(n)                                                                                    \
-    if (g.N == n) e = wofdm_interf_masked_launch_n##n(pairs, cfg->n_channels, g.P, g.B, g.mu, g.delta, g.gamma, g.kappa, \
-                                                      JP, d_wtx, d_wrx, d_h, d_g, d_act, d_cols, d_pow, d_want, nullptr)
-        WOFDM_INTERF_MASKED_LAUNCH(64);
-        WOFDM_INTERF_MASKED_LAUNCH(128);
-        WOFDM_INTERF_MASKED_LAUNCH(256);
-        WOFDM_INTERF_MASKED_LAUNCH(512);
-        WOFDM_INTERF_MASKED_LAUNCH(1024);
-#undef WOFDM_INTERF_MASKED_LAUNCH
-        if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(power, d_pow, n_out * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            (wanted && hipMemcpy(wanted, d_want, n_out * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
-            rc = fail(WOFDM_E_HIP, "masked interference kernels or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
-            break;
-        }
-    } while (0);
-    if (d_wtx) (void)hipFree(d_wtx);
-    if (d_wrx) (void)hipFree(d_wrx);
-    if (d_h) (void)hipFree(d_h);
-    if (d_pow) (void)hipFree(d_pow);
-    if (d_want) (void)hipFree(d_want);
-    if (d_g) (void)hipFree(d_g);
-    if (d_cols) (void)hipFree(d_cols);
-    if (d_act) (void)hipFree(d_act);
-    return rc;
+    const std::vector<float2> hp = pack_taps(cfg, g, h);
+    dev_buf<float> d_wtx, d_wrx, d_pow, d_want;
+    dev_buf<float2> d_h, d_g, d_cols;
+    dev_buf<uint8_t> d_act;
+    if (!d_wtx.alloc(n_wtx) || !d_wrx.alloc(n_wrx) || !d_h.alloc(hp.size()) || !d_pow.alloc(n_out) ||
+        (wanted && !d_want.alloc(n_out)) || !d_cols.alloc(n_cols) || (tx_mask && !d_g.alloc(hg.size())) ||
+        (active && !d_act.alloc(hact.size())))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (the pulses of %d pairs take %lld bytes)", pairs,
+                    (long long)(n_cols * 8));
+    if (!d_wtx.upload(w_tx, n_wtx) || !d_wrx.upload(w_rx, n_wrx) || !d_h.upload(hp.data(), hp.size()) ||
+        (tx_mask && !d_g.upload(hg.data(), hg.size())) || (active && !d_act.upload(hact.data(), hact.size())))
+        return fail(WOFDM_E_HIP, "upload failed");
+    // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
+    std::lock_guard<std::mutex> gate(g_gate_mu);
+    (void)hipDeviceSynchronize();
+    const wofdm_aux_fns *ax = wofdm_aux(g.N);
+    const hipError_t e = !ax ? hipErrorInvalidValue
+                             : ax->interf_masked(pairs, cfg->n_channels, g.P, g.B, g.mu, g.delta, g.gamma, g.kappa, JP, d_wtx,
+                                                 d_wrx, d_h, d_g, d_act, d_cols, d_pow, d_want, nullptr);
+    if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(power, d_pow, n_out * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        (wanted && hipMemcpy(wanted, d_want, n_out * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(WOFDM_E_HIP, "masked interference kernels or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
+    return WOFDM_OK;
 }
 
 int wofdm_tx_psd(const wofdm_cfg *cfg, int device, const float *w_tx, const float *X, int no_symbols,
@@ -1150,43 +1129,27 @@ int wofdm_tx_psd(const wofdm_cfg *cfg, int device, const float *w_tx, const floa
     const int P = N + cfg->cp + cfg->cs;
     if (cfg->cp < 0 || cfg->cs < 0 || cfg->cp > N || cfg->cs > N || overlap < 0 || 2 * overlap > P || no_symbols < 1)
         return fail(WOFDM_E_INVALID, "bad cp / cs / overlap / no_symbols");
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev)
-        return fail(WOFDM_E_HIP, "device %d not available (%d visible); there is no CPU fallback", device, ndev);
-    HIP_TRY(hipSetDevice(device));
+    const int rc = use_device(device);
+    if (rc != WOFDM_OK) return rc;
     const int FL = 8 * N, len = overlap + no_symbols * (P - overlap);
-    float *d_w = nullptr, *d_psd = nullptr;
-    float2 *d_X = nullptr, *d_x = nullptr;
-    int rc = WOFDM_OK;
-    do {
-        if (hipMalloc(&d_w, (size_t)P * 4) != hipSuccess || hipMalloc(&d_X, (size_t)no_symbols * N * 8) != hipSuccess ||
-            hipMalloc(&d_x, (size_t)len * 8) != hipSuccess || hipMalloc(&d_psd, (size_t)FL * 4) != hipSuccess) {
-            rc = fail(WOFDM_E_NOMEM, "device allocation failed"); break;
-        }
-        if (hipMemcpy(d_w, w_tx, (size_t)P * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_X, X, (size_t)no_symbols * N * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemset(d_x, 0, (size_t)len * 8) != hipSuccess) {
-            rc = fail(WOFDM_E_HIP, "upload failed"); break;
-        }
-        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
-        std::lock_guard<std::mutex> gate(g_gate_mu);
-        (void)hipDeviceSynchronize();
-        hipError_t e = hipErrorInvalidValue;
-        if (N == 64) e = wofdm_psd_launch_n64(P, cfg->cp, cfg->cs, overlap, no_symbols, d_w, d_X, d_x, len, d_psd, nullptr);
-        if (N == 128) e = wofdm_psd_launch_n128(P, cfg->cp, cfg->cs, overlap, no_symbols, d_w, d_X, d_x, len, d_psd, nullptr);
-        if (N == 256) e = wofdm_psd_launch_n256(P, cfg->cp, cfg->cs, overlap, no_symbols, d_w, d_X, d_x, len, d_psd, nullptr);
-        if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(psd, d_psd, (size_t)FL * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-            rc = fail(WOFDM_E_HIP, "PSD kernels or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
-            break;
-        }
-    } while (0);
-    if (d_w) (void)hipFree(d_w);
-    if (d_X) (void)hipFree(d_X);
-    if (d_x) (void)hipFree(d_x);
-    if (d_psd) (void)hipFree(d_psd);
-    return rc;
+    const size_t n_X = (size_t)no_symbols * N;
+    dev_buf<float> d_w, d_psd;
+    dev_buf<float2> d_X, d_x;
+    if (!d_w.alloc((size_t)P) || !d_X.alloc(n_X) || !d_x.alloc((size_t)len) || !d_psd.alloc((size_t)FL))
+        return fail(WOFDM_E_NOMEM, "device allocation failed");
+    if (!d_w.upload(w_tx, (size_t)P) || !d_X.upload(X, n_X) ||
+        hipMemset(d_x, 0, (size_t)len * 8) != hipSuccess)
+        return fail(WOFDM_E_HIP, "upload failed");
+    // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
+    std::lock_guard<std::mutex> gate(g_gate_mu);
+    (void)hipDeviceSynchronize();
+    const wofdm_aux_fns *ax = wofdm_aux(N);
+    const hipError_t e = !(ax && ax->psd) ? hipErrorInvalidValue
+                                          : ax->psd(P, cfg->cp, cfg->cs, overlap, no_symbols, d_w, d_X, d_x, len, d_psd, nullptr);
+    if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(psd, d_psd, (size_t)FL * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(WOFDM_E_HIP, "PSD kernels or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
+    return WOFDM_OK;
 }
 
 // wofdm_tx_psd_batch (n_masks = 0, job_mask = NULL) and wofdm_tx_psd_batch_masked.  Every argument is checked before
@@ -1255,11 +1218,8 @@ static int psd_batch(const char *who, int32_t n_fft, int device, int32_t n_jobs,
     }
     for (int j = 0; j < n_jobs; ++j)
         if (!(job_mask && job_mask[j] >= 0)) hplain.push_back(hj[(size_t)j]);
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev)
-        return fail(WOFDM_E_HIP, "device %d not available (%d visible); there is no CPU fallback", device, ndev);
-    HIP_TRY(hipSetDevice(device));
+    const int rc = use_device(device);
+    if (rc != WOFDM_OK) return rc;
     // one fast-convolution spectrum per mask in use (host, fp64, O(M log M)), whatever the number of jobs that share it
     std::vector<float2> hspec(spec_mask.size() * (size_t)FL);
     for (size_t k = 0; k < spec_mask.size(); ++k) {
@@ -1268,77 +1228,37 @@ static int psd_batch(const char *who, int32_t n_fft, int device, int32_t n_jobs,
     }
     const size_t n_X = (size_t)n_blocks * no_symbols * N, n_items = hi.size();
     const bool masked = !hm.empty();
-    float *d_w = nullptr, *d_part = nullptr, *d_psd = nullptr;
-    float2 *d_X = nullptr, *d_x = nullptr, *d_spec = nullptr, *d_Y = nullptr;
-    wofdm_bjob *d_jobs = nullptr, *d_plain = nullptr;
-    wofdm_mjob *d_mjobs = nullptr;
-    wofdm_bitem *d_items = nullptr;
-    int rc = WOFDM_OK;
-    do {
-        if (hipMalloc(&d_w, (size_t)n_w * 4) != hipSuccess || hipMalloc(&d_X, n_X * 8) != hipSuccess ||
-            hipMalloc(&d_x, (size_t)n_x * 8) != hipSuccess || hipMalloc(&d_part, n_items * FL * 4) != hipSuccess ||
-            hipMalloc(&d_psd, (size_t)n_jobs * FL * 4) != hipSuccess ||
-            hipMalloc(&d_jobs, hj.size() * sizeof(wofdm_bjob)) != hipSuccess ||
-            hipMalloc(&d_items, n_items * sizeof(wofdm_bitem)) != hipSuccess) {
-            rc = fail(WOFDM_E_NOMEM, "device allocation failed"); break;
-        }
-        if (masked && (hipMalloc(&d_spec, hspec.size() * 8) != hipSuccess || hipMalloc(&d_Y, (size_t)n_y * 8) != hipSuccess ||
-                       hipMalloc(&d_mjobs, hm.size() * sizeof(wofdm_mjob)) != hipSuccess ||
-                       (!hplain.empty() && hipMalloc(&d_plain, hplain.size() * sizeof(wofdm_bjob)) != hipSuccess))) {
-            rc = fail(WOFDM_E_NOMEM, "device allocation failed (masked jobs keep %lld filtered samples)", (long long)n_y); break;
-        }
-        if (hipMemcpy(d_w, w_tx, (size_t)n_w * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_X, X, n_X * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_jobs, hj.data(), hj.size() * sizeof(wofdm_bjob), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_items, hi.data(), n_items * sizeof(wofdm_bitem), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemset(d_x, 0, (size_t)n_x * 8) != hipSuccess) {
-            rc = fail(WOFDM_E_HIP, "upload failed"); break;
-        }
-        if (masked && (hipMemcpy(d_spec, hspec.data(), hspec.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-                       hipMemcpy(d_mjobs, hm.data(), hm.size() * sizeof(wofdm_mjob), hipMemcpyHostToDevice) != hipSuccess ||
-                       (d_plain && hipMemcpy(d_plain, hplain.data(), hplain.size() * sizeof(wofdm_bjob), hipMemcpyHostToDevice) != hipSuccess))) {
-            rc = fail(WOFDM_E_HIP, "upload failed"); break;
-        }
-        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
-        std::lock_guard<std::mutex> gate(g_gate_mu);
-        (void)hipDeviceSynchronize();
-        hipError_t e = hipErrorInvalidValue;
-        const int ni = (int)n_items, np = (int)hplain.size(), nm = (int)hm.size();
-        if (!masked) {
-            if (N == 64) e = wofdm_psd_batch_launch_n64(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
-            if (N == 128) e = wofdm_psd_batch_launch_n128(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
-            if (N == 256) e = wofdm_psd_batch_launch_n256(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
-            if (N == 512) e = wofdm_psd_batch_launch_n512(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
-            if (N == 1024) e = wofdm_psd_batch_launch_n1024(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
-        } else {
-#define WOFDM_MASKED_LAUNCH(n)                                                                                              \
-    if (N == n) e = wofdm_psd_batch_masked_launch_n##n(n_jobs, no_symbols, ni, d_jobs, d_items, np, d_plain, nm, d_mjobs,     \
-                                                       max_len, d_spec, d_Y, d_w, d_X, d_x, d_part, d_psd, nullptr)
-            WOFDM_MASKED_LAUNCH(64);
-            WOFDM_MASKED_LAUNCH(128);
-            WOFDM_MASKED_LAUNCH(256);
-            WOFDM_MASKED_LAUNCH(512);
-            WOFDM_MASKED_LAUNCH(1024);
-#undef WOFDM_MASKED_LAUNCH
-        }
-        if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(psd, d_psd, (size_t)n_jobs * FL * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-            rc = fail(WOFDM_E_HIP, "PSD kernels or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
-            break;
-        }
-    } while (0);
-    if (d_w) (void)hipFree(d_w);
-    if (d_X) (void)hipFree(d_X);
-    if (d_x) (void)hipFree(d_x);
-    if (d_part) (void)hipFree(d_part);
-    if (d_psd) (void)hipFree(d_psd);
-    if (d_jobs) (void)hipFree(d_jobs);
-    if (d_items) (void)hipFree(d_items);
-    if (d_spec) (void)hipFree(d_spec);
-    if (d_Y) (void)hipFree(d_Y);
-    if (d_mjobs) (void)hipFree(d_mjobs);
-    if (d_plain) (void)hipFree(d_plain);
-    return rc;
+    dev_buf<float> d_w, d_part, d_psd;
+    dev_buf<float2> d_X, d_x, d_spec, d_Y;
+    dev_buf<wofdm_bjob> d_jobs, d_plain;
+    dev_buf<wofdm_mjob> d_mjobs;
+    dev_buf<wofdm_bitem> d_items;
+    if (!d_w.alloc((size_t)n_w) || !d_X.alloc(n_X) || !d_x.alloc((size_t)n_x) || !d_part.alloc(n_items * FL) ||
+        !d_psd.alloc((size_t)n_jobs * FL) || !d_jobs.alloc(hj.size()) || !d_items.alloc(n_items))
+        return fail(WOFDM_E_NOMEM, "device allocation failed");
+    if (masked && (!d_spec.alloc(hspec.size()) || !d_Y.alloc((size_t)n_y) || !d_mjobs.alloc(hm.size()) ||
+                   (!hplain.empty() && !d_plain.alloc(hplain.size()))))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (masked jobs keep %lld filtered samples)", (long long)n_y);
+    if (!d_w.upload(w_tx, (size_t)n_w) || !d_X.upload(X, n_X) || !d_jobs.upload(hj.data(), hj.size()) ||
+        !d_items.upload(hi.data(), n_items) || hipMemset(d_x, 0, (size_t)n_x * 8) != hipSuccess)
+        return fail(WOFDM_E_HIP, "upload failed");
+    if (masked && (!d_spec.upload(hspec.data(), hspec.size()) || !d_mjobs.upload(hm.data(), hm.size()) ||
+                   (!hplain.empty() && !d_plain.upload(hplain.data(), hplain.size()))))
+        return fail(WOFDM_E_HIP, "upload failed");
+    // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
+    std::lock_guard<std::mutex> gate(g_gate_mu);
+    (void)hipDeviceSynchronize();
+    const wofdm_aux_fns *ax = wofdm_aux(N);
+    const int ni = (int)n_items, np = (int)hplain.size(), nm = (int)hm.size();
+    hipError_t e = hipErrorInvalidValue;
+    if (ax && !masked) e = ax->psd_batch(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+    if (ax && masked)
+        e = ax->psd_batch_masked(n_jobs, no_symbols, ni, d_jobs, d_items, np, d_plain, nm, d_mjobs, max_len, d_spec, d_Y, d_w, d_X,
+                                 d_x, d_part, d_psd, nullptr);
+    if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(psd, d_psd, (size_t)n_jobs * FL * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(WOFDM_E_HIP, "PSD kernels or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
+    return WOFDM_OK;
 }
 
 int wofdm_tx_psd_batch(int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs, const float *w_tx,

@@ -1,0 +1,997 @@
+// wofdm_aux.hip -- the auxiliary kernels beside the frame kernel: closed-form ICI/ISI power (wofdm_interference,
+// wofdm_interference_masked) and Tx waveform + averaged periodogram (wofdm_tx_psd, wofdm_tx_psd_batch,
+// wofdm_tx_psd_batch_masked).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
+// on n_fft through the unit's table of launchers (wofdm_aux_fns).
+#include "wofdm_kernel.h"
+#include "wofdm_device.h"
+#include "philox.h"
+
+#if !defined(WOFDM_TU_N)
+#error "compile with -DWOFDM_TU_N=<64|128|256|512|1024>"
+#endif
+#define WOFDM_CAT2(a, b) a##b
+#define WOFDM_CAT(a, b) WOFDM_CAT2(a, b)
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// Closed-form ICI + ISI power of a structure:
+//   calculate_interference  matlab/main_interference_calculation.m:177-225
+//   interf_power            python/ofdm_utils/interf_calc.py:20-113
+//     A_m = W K P V_rx R  H_m  V_tx Gamma W^-1,   H_m[b, c] = h[m B + b - c],   m = 0, 1
+//     P[n] = sum_{n' != n} |A_0[n, n']|^2 + sum_{n'} |A_1[n, n']|^2
+// Column n' of A_m is the frame pipeline's own answer to a unit symbol on subcarrier n': the windowed,
+// CP/CS-extended complex exponential x (the Tx matrix applied to e_n'), the 21-tap convolution over two
+// symbol periods, and per period the Rx window / fold / shift + DFT of the frame kernel -- no dense
+// matrices, no RNG.  One workgroup per (window pair, channel) job; a wave takes the columns
+// n' = wave, wave + W, ... and keeps |A|^2 row sums of its subcarriers (FFT output layout) in registers;
+// one LDS reduction over the waves at the end.  (M = 1 + ceil((L - 1 + beta) / B) = 2 for every
+// supported structure: B >= 64 > 36.)
+struct wofdm_iparams {
+    int P, B, mu, delta, gam, kap, n_ch, rowlen;   // rowlen: float2 per wave row (24 + 2B + 24 rounded up)
+    float *power;                                  // [pairs][n_ch][N]
+};
+template <int N> struct interf_geo {
+    static constexpr int WAVES = N <= 256 ? 16 : (N == 512 ? 8 : 4);
+    static constexpr int RB2 = 2 * (N / 64 + 1);                      // FIR outputs per lane over 2B samples
+    static constexpr int CH = RB2 % 6 == 0 ? 6 : (RB2 % 5 == 0 ? 5 : (RB2 % 4 == 0 ? 4 : 2));
+};
+
+template <int N>
+__global__ void __launch_bounds__(interf_geo<N>::WAVES * 64)
+wofdm_interf_kernel(const wofdm_iparams p, const float *__restrict__ g_wtx, const float *__restrict__ g_wrx,
+                    const float2 *__restrict__ g_h_)
+{
+    constexpr int WAVES = interf_geo<N>::WAVES, RB2 = interf_geo<N>::RB2, LT = WOFDM_LT;
+    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ;
+    constexpr bool FULL = geo<N>::FULL;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // LDS: FFT stage twiddles [N] | e^{+2 pi i k / N} [N] | w_rx [N + 64] | per wave: row [rowlen] + scratch [N]
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    v2f *wn = tw + N;
+    float *wrx = reinterpret_cast<float *>(wn + N);
+    v2f *rows = reinterpret_cast<v2f *>(wrx + N + 64);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int job = blockIdx.x, pair = job / p.n_ch, ch = job - pair * p.n_ch;
+    const int P = p.P, B = p.B;
+    fill_twiddles<N>(tw, tid, WAVES * 64);
+    for (int i = tid; i < N; i += WAVES * 64) {
+        float sv, cv;
+        sincospif(2.0f * (float)i / (float)N, &sv, &cv);
+        wn[i] = mk(cv, sv);
+    }
+    for (int i = tid; i < N + p.delta; i += WAVES * 64) wrx[i] = g_wrx[(size_t)pair * (N + p.delta) + i];
+    v2f *row = rows + (size_t)wv * (p.rowlen + N);
+    v2f *scr = row + p.rowlen;
+    for (int i = lane; i < p.rowlen; i += 64) row[i] = mk(0.f, 0.f);
+    __syncthreads();
+    const v2f *__restrict__ taps = reinterpret_cast<const v2f *>(g_h_) + (size_t)ch * LT;
+    const float *__restrict__ wtx = g_wtx + (size_t)pair * P;
+    float pw[BPL][4];
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pw[q][r] = 0.f;
+    const int h2 = p.delta >> 1;
+    for (int np = wv; np < N; np += WAVES) {
+        // x[c] = w_tx[c] e^{2 pi i ((c - mu) mod N) n' / N} / N at row[24 + c]  (tx matrix column, m:358-376)
+        for (int c = lane; c < P; c += 64) {
+            const int t = (c - p.mu) & (N - 1);
+            row[24 + c] = wn[(t * np) & (N - 1)] * (wtx[c] * (1.0f / (float)N));
+        }
+        for (int c = P + lane; c < 2 * B + 24; c += 64) row[24 + c] = mk(0.f, 0.f);
+        wave_sync();
+        // z = conv(h, x) over two symbol periods (m:260): lane -> RB2 consecutive outputs from j0
+        v2f acc[RB2];
+        const int j0 = lane * RB2;
+        fir_lane<RB2, interf_geo<N>::CH>(row + 24 - (LT - 1) + j0, taps, acc);
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < RB2; ++r)
+            if (j0 + r < 2 * B) row[24 + j0 + r] = acc[r];
+        wave_sync();
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            // Rx window, fold, circular shift (m:297-355) of period m, then the DFT
+            const v2f *fb = row + 24 + m * B;
+            v2f v[1][BPL][4];
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    v[0][q][r] = mk(0.f, 0.f);
+                    if (!(FULL || lane + 64 * q < NQ)) continue;
+                    const int m0 = (lane + 64 * q + r * NQ + p.kap + h2) & (N - 1);
+                    v2f z = fb[p.gam + m0] * wrx[m0];
+                    if (m0 < p.delta) {
+                        const float w2 = wrx[m0 + N];
+                        z = __builtin_elementwise_fma(mk(w2, w2), fb[p.gam + m0 + N], z);
+                    }
+                    v[0][q][r] = z;
+                }
+            fft_wave<N, -1, 1>(v, scr, 0, tw, lane);
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int n = lane + 64 * q + r * NQ;
+                    const float e = v[0][q][r].x * v[0][q][r].x + v[0][q][r].y * v[0][q][r].y;
+                    if (FULL || lane + 64 * q < NQ)
+                        pw[q][r] += (m == 0 && n == np) ? 0.f : e;    // the wanted term A_0[n, n] is no interference
+                }
+        }
+        wave_sync();
+    }
+    // sum over the waves (each wave's row is free now): float [WAVES][N] in the rows area
+    __syncthreads();
+    float *red = reinterpret_cast<float *>(rows);
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (FULL || lane + 64 * q < NQ) red[wv * N + lane + 64 * q + r * NQ] = pw[q][r];
+    __syncthreads();
+    for (int n = tid; n < N; n += WAVES * 64) {
+        float t = 0.f;
+        for (int w = 0; w < WAVES; ++w) t += red[w * N + n];
+        p.power[(size_t)job * N + n] = t;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tx-side spectrum estimate: the transmitted waveform of a long run of symbols
+// and its averaged periodogram,
+//   wOFDMSystem.estimate_obr   python/ofdm_utils/timefreq_simulation.py:216-296 (Tx chain 242-258)
+//   psd_estimate               timefreq_simulation.py:101-123
+// The waveform kernel is phase A of the frame kernel fed with given symbols X[s][n] (any complex values,
+// zeros on unloaded bins): IDFT, CP/CS copy, Tx window, overlap-add of the `overlap` tail samples --
+// one wave per symbol, the overlapping samples by float atomics (two addends: order-independent).
+struct wofdm_wparams {
+    int P, mu, rho, overlap, no_symbols;
+    float2 *x;                         // [overlap + no_symbols * (P - overlap)], zeroed by the host
+};
+// The symbol of both waveform kernels: X -> IDFT -> CP / CS copy x Tx window onto the waveform row `out` (the symbol's first
+// sample); Bo = P - overlap samples further the next symbol starts.
+template <int N>
+__device__ __forceinline__ void txwave_symbol(const float2 *Xs, const float *wtx, float2 *out, int cp, int cs, int overlap,
+                                              int Bo, int lane, v2f *scr, const v2f *tw)
+{
+    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ;
+    constexpr bool FULL = geo<N>::FULL;
+    v2f v[1][BPL][4];
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            v[0][q][r] = mk(0.f, 0.f);
+            if (FULL || lane + 64 * q < NQ) v[0][q][r] = ldg2(Xs + lane + 64 * q + r * NQ);
+        }
+    fft_wave<N, +1, 1>(v, scr, 0, tw, lane);                    // N x[t]
+    auto put = [&](int i, v2f val) {
+        val = val * (wtx[i] * (1.0f / (float)N));
+        if (i < overlap || i >= Bo) {                            // shared with a neighbour symbol
+            atomicAdd(&out[i].x, val.x);
+            atomicAdd(&out[i].y, val.y);
+        } else {
+            out[i] = make_float2(val.x, val.y);
+        }
+    };
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (!(FULL || lane + 64 * q < NQ)) continue;
+            const int t = lane + 64 * q + r * NQ;
+            put(t + cp, v[0][q][r]);
+            if (t >= N - cp) put(t + cp - N, v[0][q][r]);
+            if (t < cs) put(t + cp + N, v[0][q][r]);
+        }
+}
+template <int N>
+__global__ void __launch_bounds__(1024) wofdm_txwave_kernel(const wofdm_wparams p, const float *__restrict__ g_wtx,
+                                                            const float2 *__restrict__ X)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    v2f *scr = tw + N + (size_t)wv * N;
+    fill_twiddles<N>(tw, tid, 1024);
+    __syncthreads();
+    const int s = blockIdx.x * 16 + wv;
+    if (s >= p.no_symbols) return;
+    const int Bo = p.P - p.overlap;
+    txwave_symbol<N>(X + (size_t)s * N, g_wtx, p.x + (size_t)s * Bo, p.mu, p.rho, p.overlap, Bo, lane, scr, tw);
+}
+
+// Sum over consecutive FL-sample slices of x (the zero-padded remainder included) of |FFT_FL|^2, written
+// fftshift-ed; the caller divides by the reference's slice count.  FL = 2048 runs as two 1024-point
+// transforms of the even and odd samples and one radix-2 combination in registers.
+template <int FL>
+__global__ void __launch_bounds__(512) wofdm_psd_kernel(const float2 *__restrict__ x, int len, int n_slices,
+                                                        float *__restrict__ psd)
+{
+    constexpr int M = FL == 2048 ? 1024 : FL, H = FL / M;        // transform length, transforms per slice
+    constexpr int BPL = geo<M>::BPL, NQ = geo<M>::NQ, WAVES = 8;
+    static_assert(geo<M>::FULL, "at least 256 points");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    v2f *scr = tw + M + (size_t)wv * M;
+    fill_twiddles<M>(tw, tid, WAVES * 64);
+    __syncthreads();
+    float acc[H][BPL][4];
+#pragma unroll
+    for (int h = 0; h < H; ++h)
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[h][q][r] = 0.f;
+    for (int sl = wv; sl < n_slices; sl += WAVES) {
+        v2f e[1][BPL][4], o[1][BPL][4];
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+            v2f (&dst)[1][BPL][4] = h == 0 ? e : o;
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int idx = sl * FL + H * (lane + 64 * q + r * NQ) + h;       // even / odd samples
+                    dst[0][q][r] = idx < len ? ldg2(x + idx) : mk(0.f, 0.f);
+                }
+            fft_wave<M, -1, 1>(dst, scr, 0, tw, lane);
+        }
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (H == 2) {
+                    const int k = lane + 64 * q + r * NQ;
+                    float sv, cv;
+                    sincospif(-2.0f * (float)k / (float)FL, &sv, &cv);
+                    const v2f wo = cmul(o[0][q][r], mk(cv, sv));
+                    const v2f a = e[0][q][r] + wo, b = e[0][q][r] - wo;
+                    acc[0][q][r] += a.x * a.x + a.y * a.y;
+                    acc[1][q][r] += b.x * b.x + b.y * b.y;
+                } else {
+                    acc[0][q][r] += e[0][q][r].x * e[0][q][r].x + e[0][q][r].y * e[0][q][r].y;
+                }
+            }
+    }
+    __syncthreads();
+    float *red = reinterpret_cast<float *>(tw + M);                 // [WAVES][FL] over the scratch rows
+#pragma unroll
+    for (int h = 0; h < H; ++h)
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[wv * FL + h * M + lane + 64 * q + r * NQ] = acc[h][q][r];
+    __syncthreads();
+    for (int k = tid; k < FL; k += WAVES * 64) {
+        float t = 0.f;
+        for (int w = 0; w < WAVES; ++w) t += red[w * FL + k];
+        psd[(k + FL / 2) & (FL - 1)] = t;
+    }
+}
+
+// The same two steps for a batch of jobs at every N (wofdm_tx_psd_batch).  The waveform kernel: grid (symbol groups,
+// jobs), one wave per symbol of the job's block, each job with its own cp, cs, overlap, window and waveform row; the
+// overlapping samples as above (two addends onto a zeroed row).  LDS: twiddles [N] + one scratch row [N] per wave
+// (N = 1024: 9 x 8 KB).
+template <int N> struct bwave_geo {
+    static constexpr int WAVES = N >= 512 ? 8 : 16;
+};
+template <int N>
+__global__ void __launch_bounds__(bwave_geo<N>::WAVES * 64)
+wofdm_txwave_batch_kernel(const wofdm_bjob *__restrict__ jobs, int no_symbols, const float *__restrict__ g_wtx,
+                          const float2 *__restrict__ X, float2 *__restrict__ x)
+{
+    constexpr int WAVES = bwave_geo<N>::WAVES;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    v2f *scr = tw + N + (size_t)wv * N;
+    fill_twiddles<N>(tw, tid, WAVES * 64);
+    __syncthreads();
+    const wofdm_bjob jb = jobs[blockIdx.y];
+    const int s = blockIdx.x * WAVES + wv;
+    if (s >= no_symbols) return;
+    const int Bo = N + jb.cp + jb.cs - jb.overlap;
+    txwave_symbol<N>(X + ((size_t)jb.block * no_symbols + s) * N, g_wtx + jb.w_off, x + jb.x_off + (size_t)s * Bo, jb.cp, jb.cs,
+                     jb.overlap, Bo, lane, scr, tw);
+}
+
+// Periodogram of a batch: one workgroup (8 waves) per work item, i.e. up to wofdm_psd_batch_slices(N) consecutive
+// FL-sample slices of one job.  FL <= 1024 (R = 1): a wave transforms a whole slice, 8 slices at a time.  FL = 1024 R,
+// R = 2, 4, 8: the R waves of a group transform the decimated sub-sequences x[R m + h] of one slice (1024 points each,
+// E_h), put E_h into their scratch rows and, behind a barrier, combine them:  X[k' + 1024 c] = sum_h W_R^(h c)
+// (W_FL^(h k') E_h[k']).  Wave h of the group owns k' = h 1024 / R + lane + 64 j (j < 16 / R), i.e. 16 outputs per lane,
+// whose twiddles it keeps in registers; its loads of the R rows are consecutive 8-byte words across the lanes, as are the
+// stores of E_h (ds_read_b64 / ds_write_b64 without bank conflicts).  Every lane adds |X|^2 over its slices in a fixed
+// order, the groups' sums are added in group order, and the workgroup writes one unshifted partial spectrum [FL];
+// wofdm_psd_reduce_kernel adds a job's partials in item order -- no atomics: bitwise repeatable.
+template <int FL>
+__global__ void __launch_bounds__(512) wofdm_psd_batch_kernel(const wofdm_bjob *__restrict__ jobs,
+                                                              const wofdm_bitem *__restrict__ items,
+                                                              const float2 *__restrict__ x, float *__restrict__ partial)
+{
+    constexpr int R = wofdm_psd_batch_r(FL / 8), M = FL / R, G = 8 / R, ROUNDS = wofdm_psd_batch_slices(FL / 8) / G;
+    constexpr int BPL = geo<M>::BPL, NQ = geo<M>::NQ, JJ = M / (64 * R), NACC = R > 1 ? JJ * R : 4 * BPL;
+    static_assert(geo<M>::FULL && (R == 1 || M == 1024), "512- or 1024-point transforms");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    v2f *rows = tw + M;                                           // [8][M]: scratch of wave w = E_h of group w / R
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = wv / R, h = wv % R;
+    fill_twiddles<M>(tw, tid, 512);
+    const wofdm_bitem it = items[blockIdx.x];
+    const wofdm_bjob jb = jobs[it.job];
+    const float2 *xj = x + jb.x_off;
+    v2f cw[JJ][R > 1 ? R - 1 : 1];                                // W_FL^(t k'), t = 1 .. R-1
+    if constexpr (R > 1) {
+#pragma unroll
+        for (int j = 0; j < JJ; ++j)
+#pragma unroll
+            for (int t = 1; t < R; ++t) {
+                const int kp = h * (M / R) + lane + 64 * j;
+                float sv, cv;
+                sincospif(-2.0f * (float)(t * kp) / (float)FL, &sv, &cv);
+                cw[j][t - 1] = mk(cv, sv);
+            }
+    }
+    float acc[NACC];
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) acc[a] = 0.f;
+    __syncthreads();
+    v2f *own = rows + (size_t)wv * M;
+    for (int rd = 0; rd < ROUNDS; ++rd) {
+        const int sl = rd * G + g;
+        const bool live = sl < it.n_slices;                       // uniform over the group
+        if (live) {
+            const int base = (it.slice0 + sl) * FL + h;
+            v2f v[1][BPL][4];
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int idx = base + R * (lane + 64 * q + r * NQ);
+                    v[0][q][r] = idx < jb.len ? ldg2(xj + idx) : mk(0.f, 0.f);
+                }
+            fft_wave<M, -1, 1>(v, own, 0, tw, lane);
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if constexpr (R == 1) acc[4 * q + r] += v[0][q][r].x * v[0][q][r].x + v[0][q][r].y * v[0][q][r].y;
+                    else own[lane + 64 * q + r * NQ] = v[0][q][r];
+                }
+        }
+        if constexpr (R > 1) {
+            __syncthreads();
+            if (live) {
+                const v2f *gs = rows + (size_t)g * R * M;
+#pragma unroll
+                for (int j = 0; j < JJ; ++j) {
+                    const int kp = h * (M / R) + lane + 64 * j;
+                    v2f y[R];
+#pragma unroll
+                    for (int t = 0; t < R; ++t) y[t] = gs[t * M + kp];
+#pragma unroll
+                    for (int t = 1; t < R; ++t) y[t] = cmul(y[t], cw[j][t - 1]);
+                    v2f X_[R];
+                    if constexpr (R == 2) {
+                        X_[0] = y[0] + y[1];
+                        X_[1] = y[0] - y[1];
+                    } else if constexpr (R == 4) {
+                        v2f u[4] = {y[0], y[1], y[2], y[3]};
+                        radix4<-1>(u);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) X_[c] = u[c];
+                    } else {
+                        v2f u[2][4];                              // u[q][r] = y_t, t = q + 2 r
+#pragma unroll
+                        for (int t = 0; t < 8; ++t) u[t & 1][t >> 1] = y[t];
+                        dft8<-1>(u);                              // u[q][r] = X_c, c = r + 4 q
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) X_[c] = u[c >> 2][c & 3];
+                    }
+#pragma unroll
+                    for (int c = 0; c < R; ++c) acc[j * R + c] += X_[c].x * X_[c].x + X_[c].y * X_[c].y;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    float *red = reinterpret_cast<float *>(rows);                 // [G][FL] floats over the scratch rows
+    if constexpr (R == 1) {
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[g * FL + lane + 64 * q + r * NQ] = acc[4 * q + r];
+    } else {
+#pragma unroll
+        for (int j = 0; j < JJ; ++j)
+#pragma unroll
+            for (int c = 0; c < R; ++c) red[g * FL + h * (M / R) + lane + 64 * j + M * c] = acc[j * R + c];
+    }
+    __syncthreads();
+    for (int k = tid; k < FL; k += 512) {
+        float t = 0.f;
+        for (int gg = 0; gg < G; ++gg) t += red[gg * FL + k];
+        partial[(size_t)blockIdx.x * FL + k] = t;
+    }
+}
+
+// psd[job][8 N] = sum over the job's work items, in item order, of their partial spectra; fftshift-ed
+template <int FL>
+__global__ void __launch_bounds__(256) wofdm_psd_reduce_kernel(const wofdm_bjob *__restrict__ jobs,
+                                                               const float *__restrict__ partial, float *__restrict__ psd)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= FL) return;
+    const wofdm_bjob jb = jobs[blockIdx.y];
+    float t = 0.f;
+    for (int i = 0; i < jb.n_items; ++i) t += partial[(size_t)(jb.item0 + i) * FL + k];
+    psd[(size_t)blockIdx.y * FL + ((k + FL / 2) & (FL - 1))] = t;
+}
+
+// Waveform step of a MASKED job (wofdm_tx_psd_batch_masked): per symbol the row r_s[P] of wofdm_txwave_batch_kernel
+// (IDFT, CP/CS copy, Tx window), then the spectral Tx mask of wofdm_plan_set_tx_mask as fast convolution over FL = 8 N
+// points (3 P - 2 <= FL):  y_s[i] = IFFT_FL( FFT_FL(r_s) . H )[i + P - 1], i < 2 P - 1, with H the transform of the mask's
+// impulse response laid out as in the frame kernel's TXFFT variant, 1 / FL folded in (host, fp64; stored in fp32).
+// The FL-point transforms are the R-way split of wofdm_psd_batch_kernel (R waves, M = FL / R points each) and its
+// transpose:  forward  X[k' + M c] = sum_h W_R^(h c) (W_FL^(h k') E_h[k']),  E_h = FFT_M(r[R m + h]);
+//             inverse  y[R m + h] = IFFT_M(F_h)[m],  F_h[k'] = W_FL^(-h k') sum_c W_R^(-h c) Z[k' + M c].
+// Wave h of a group owns k' = h M / R + lane + 64 j in the combination, takes all R bins k' + M c, multiplies them by H
+// and runs the inverse combination in registers -- the spectrum never leaves the workgroup.  8 waves = 8 / R symbols
+// per workgroup.  LDS: twiddles [M] (+ [N] where N != M) | rows [8][M] | symbol rows [8 / R][PMAX].
+// Output: the WHOLE y_s (2 P - 1 samples) by plain stores at Y + y_off + s (2 P - 1); the spill of symbol s onto s + 1
+// and the overlap-add are the gather of wofdm_txmask_ola_kernel -- no atomics, a fixed order of additions.
+template <int N> struct bmask_geo {
+    static constexpr int FL = 8 * N, R = wofdm_psd_batch_r(N), M = FL / R, G = 8 / R;
+    static constexpr int PMAX = wofdm_txmask_batch_pmax(N);
+    static constexpr int TWN = N == M ? 0 : N;                    // a twiddle table of its own for the N-point IDFT
+    static constexpr size_t LDS = 8 * (size_t)(M + TWN + 8 * M + G * PMAX);
+    static_assert(LDS <= 160 * 1024 && N <= M && 3 * PMAX - 2 <= FL, "LDS / transform length");
+};
+template <int N>
+__global__ void __launch_bounds__(512)
+wofdm_txmask_batch_kernel(const wofdm_bjob *__restrict__ jobs, const wofdm_mjob *__restrict__ mjobs, int no_symbols,
+                          const float *__restrict__ g_wtx, const float2 *__restrict__ X, const float2 *__restrict__ spec,
+                          float2 *__restrict__ Y)
+{
+    using MG = bmask_geo<N>;
+    constexpr int FL = MG::FL, R = MG::R, M = MG::M, G = MG::G, PMAX = MG::PMAX;
+    constexpr int BPL = geo<M>::BPL, NQ = geo<M>::NQ, JJ = M / (64 * R);
+    constexpr int BPLN = geo<N>::BPL, NQN = geo<N>::NQ;
+    constexpr bool FULLN = geo<N>::FULL;
+    static_assert(geo<M>::FULL, "512- or 1024-point transforms");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *twm = reinterpret_cast<v2f *>(smem);
+    v2f *twn = N == M ? twm : twm + M;
+    v2f *rows = twm + M + MG::TWN;                                // [8][M]
+    v2f *srows = rows + 8 * M;                                    // [G][PMAX]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = wv / R, h = wv % R;
+    fill_twiddles<M>(twm, tid, 512);
+    if constexpr (N != M) fill_twiddles<N>(twn, tid, 512);
+    const wofdm_mjob mj = mjobs[blockIdx.y];
+    const wofdm_bjob jb = jobs[mj.job];
+    const int P = N + jb.cp + jb.cs, L = 2 * P - 1;
+    const int s = blockIdx.x * G + g;
+    const bool live = s < no_symbols;                             // uniform over the group
+    v2f cw[JJ][R > 1 ? R - 1 : 1];                                // W_FL^(t k'), t = 1 .. R-1
+    if constexpr (R > 1) {
+#pragma unroll
+        for (int j = 0; j < JJ; ++j)
+#pragma unroll
+            for (int t = 1; t < R; ++t) {
+                const int kp = h * (M / R) + lane + 64 * j;
+                float sv, cv;
+                sincospif(-2.0f * (float)(t * kp) / (float)FL, &sv, &cv);
+                cw[j][t - 1] = mk(cv, sv);
+            }
+    }
+    __syncthreads();
+    v2f *own = rows + (size_t)wv * M;
+    v2f *srow = srows + (size_t)g * PMAX;
+    if (live && h == 0) {                                         // r_s: as wofdm_txwave_batch_kernel, into LDS
+        const float2 *Xs = X + ((size_t)jb.block * no_symbols + s) * N;
+        v2f v[1][BPLN][4];
+#pragma unroll
+        for (int q = 0; q < BPLN; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v[0][q][r] = mk(0.f, 0.f);
+                if (FULLN || lane + 64 * q < NQN) v[0][q][r] = ldg2(Xs + lane + 64 * q + r * NQN);
+            }
+        fft_wave<N, +1, 1>(v, own, 0, twn, lane);                 // N x[t]
+        const float *wtx = g_wtx + jb.w_off;
+        auto put = [&](int i, v2f val) { srow[i] = val * (wtx[i] * (1.0f / (float)N)); };
+#pragma unroll
+        for (int q = 0; q < BPLN; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (!(FULLN || lane + 64 * q < NQN)) continue;
+                const int t = lane + 64 * q + r * NQN;
+                put(t + jb.cp, v[0][q][r]);
+                if (t >= N - jb.cp) put(t + jb.cp - N, v[0][q][r]);
+                if (t < jb.cs) put(t + jb.cp + N, v[0][q][r]);
+            }
+    }
+    __syncthreads();
+    v2f v[1][BPL][4];
+    if (live) {
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int idx = R * (lane + 64 * q + r * NQ) + h;
+                v[0][q][r] = idx < P ? srow[idx] : mk(0.f, 0.f);
+            }
+        fft_wave<M, -1, 1>(v, own, 0, twm, lane);
+        if constexpr (R == 1) {
+            const float2 *H = spec + (size_t)mj.spec * FL;
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[0][q][r] = cmul(v[0][q][r], ldg2(H + lane + 64 * q + r * NQ));
+        } else {
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) own[lane + 64 * q + r * NQ] = v[0][q][r];
+        }
+    }
+    if constexpr (R > 1) {
+        __syncthreads();
+        v2f F[JJ][R];                                             // F_t[k'] of this wave's k', t < R
+        if (live) {
+            const v2f *gs = rows + (size_t)g * R * M;
+            const float2 *H = spec + (size_t)mj.spec * FL;
+#pragma unroll
+            for (int j = 0; j < JJ; ++j) {
+                const int kp = h * (M / R) + lane + 64 * j;
+                v2f y[R];
+#pragma unroll
+                for (int t = 0; t < R; ++t) y[t] = gs[t * M + kp];
+#pragma unroll
+                for (int t = 1; t < R; ++t) y[t] = cmul(y[t], cw[j][t - 1]);
+                if constexpr (R == 2) {
+                    const v2f z0 = cmul(y[0] + y[1], ldg2(H + kp)), z1 = cmul(y[0] - y[1], ldg2(H + kp + M));
+                    F[j][0] = z0 + z1;
+                    F[j][1] = z0 - z1;
+                } else if constexpr (R == 4) {
+                    v2f u[4] = {y[0], y[1], y[2], y[3]};
+                    radix4<-1>(u);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) u[c] = cmul(u[c], ldg2(H + kp + M * c));
+                    radix4<+1>(u);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) F[j][t] = u[t];
+                } else {
+                    v2f u[2][4], w[2][4];                         // u[q][r] = y_t, t = q + 2 r
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) u[t & 1][t >> 1] = y[t];
+                    dft8<-1>(u);                                  // u[q][r] = X_c, c = r + 4 q
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) w[c & 1][c >> 1] = cmul(u[c >> 2][c & 3], ldg2(H + kp + M * c));
+                    dft8<+1>(w);                                  // w[q][r] = F_t, t = r + 4 q
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) F[j][t] = w[t >> 2][t & 3];
+                }
+#pragma unroll
+                for (int t = 1; t < R; ++t) F[j][t] = cmul_conj(F[j][t], cw[j][t - 1]);
+            }
+        }
+        __syncthreads();                                          // every wave has read the E rows
+        if (live) {
+            v2f *gs = rows + (size_t)g * R * M;
+#pragma unroll
+            for (int j = 0; j < JJ; ++j)
+#pragma unroll
+                for (int t = 0; t < R; ++t) gs[t * M + h * (M / R) + lane + 64 * j] = F[j][t];
+        }
+        __syncthreads();
+        if (live) {
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[0][q][r] = own[lane + 64 * q + r * NQ];
+        }
+    }
+    if (!live) return;
+    fft_wave<M, +1, 1>(v, own, 0, twm, lane);                     // y[R m + h + (P - 1)], the 1 / FL sits in H
+    float2 *out = Y + mj.y_off + (size_t)s * L;
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = R * (lane + 64 * q + r * NQ) + h - (P - 1);
+            if (i >= 0 && i < L) out[i] = make_float2(v[0][q][r].x, v[0][q][r].y);
+        }
+}
+
+// Filtered rows and overlap-add of a masked job, as a gather in a fixed order (no atomics):
+//   row_s[i] = y_s[i] + y_{s-1}[P + i] (i < P - 1, s > 0),  row_s[P - 1] = y_s[P - 1]
+//   x[s (P - overlap) + i] = row_s[i] (s < S) + row_{s-1}[i + P - overlap] (s > 0, i < overlap)
+template <int N>
+__global__ void __launch_bounds__(256)
+wofdm_txmask_ola_kernel(const wofdm_bjob *__restrict__ jobs, const wofdm_mjob *__restrict__ mjobs, int no_symbols,
+                        const float2 *__restrict__ Y, float2 *__restrict__ x)
+{
+    const wofdm_mjob mj = mjobs[blockIdx.y];
+    const wofdm_bjob jb = jobs[mj.job];
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= jb.len) return;
+    const int P = N + jb.cp + jb.cs, L = 2 * P - 1, Bo = P - jb.overlap;
+    const float2 *y = Y + mj.y_off;
+    auto row = [&](int ss, int i) {
+        v2f a = ldg2(y + (size_t)ss * L + i);
+        if (ss > 0 && i < P - 1) a = a + ldg2(y + (size_t)(ss - 1) * L + P + i);
+        return a;
+    };
+    const int s = n / Bo, i = n - s * Bo;
+    v2f val = mk(0.f, 0.f);
+    if (s < no_symbols) val = row(s, i);
+    if (s > 0 && i < jb.overlap) val = s < no_symbols ? val + row(s - 1, i + Bo) : row(s - 1, i + Bo);
+    x[jb.x_off + n] = make_float2(val.x, val.y);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Closed-form ICI + ISI power of the half-band, spectrally masked system (wofdm_interference_masked):
+//   zero padding + ifftshift  matlab/main_channel_mask.m:387-390
+//   dft_rc_filt               matlab/main_channel_mask.m:398-417
+//   calculate_interference    matlab/main_interference_calculation.m:177-225
+// The mask turns the Tx column of bin n' into y = g (*) x (circular, length 2P - 1, g = the mask's impulse response);
+// y[0, P) stays in the symbol's row and y[P, 2P - 1) goes into the next one, B samples later, so the on-air pulse is
+//   u[j] = [j < P] y[j] + [B <= j < B + P - 1] y[P + j - B],   j < J = B + P - 1,
+// and with the channel it covers three symbol periods: A_m, m = 0, 1, 2 (J + L - 1 <= 3 B for every supported
+// geometry: tail_tx + L - 2 <= 35 < 64 <= B).
+//
+// Stage 1, once per window pair (the pulses do not depend on the channel): u is linear in x[c] = w_tx[c]
+// e^{2 pi i ((c - mu) mod N) n' / N} / N, so for a fixed j the pulses of ALL bins are one N-point inverse DFT,
+//   u[j][n'] = 1/N sum_t q_j[t] e^{2 pi i t n' / N},   q_j[t] = sum_{c < P, c = t + mu (mod N)} G[j][c] w_tx[c],
+//   G[j][c] = [j < P] g[(j - c) mod (2P - 1)] + [B <= j < B + P - 1] g[j - B + P - c]
+// -- a wave per sample j: it folds row j of G onto the N points and transforms; O(J (P + N log N)) per pair instead
+// of O(J P N).  No mask (g == nullptr): u[j][n'] = x[j] itself, from the exponential table as wofdm_interf_kernel
+// forms it.  cols[pair][n'][JP] holds the pulses, a row per bin; rows of unloaded bins are not written (nor read).
+struct wofdm_mparams {
+    int P, B, mu, delta, gam, kap, n_ch, J, JP;    // J = B + P - 1 pulse samples, JP = row pitch of cols
+    float *power, *wanted;                         // [pairs][n_ch][N]; wanted may be null
+};
+template <int N> struct interfm_geo {
+    // (the waves of wofdm_interf_kernel: the same columns per wave and the same order of the sums, so that without mask and
+    // allocation the power comes out bit for bit as there)
+    static constexpr int WAVES = interf_geo<N>::WAVES;
+    static constexpr int RB3 = 3 * (N / 64 + 1);                      // FIR outputs per lane over 3B <= 3N + 192 samples
+    static constexpr int CH = RB3 <= 6 ? RB3 : (RB3 % 5 == 0 ? 5 : 6);
+    // 24 zeros (>= LT - 1 of history) + 64 RB3 samples: the last lane's FIR window ends at 64 RB3 + 23
+    static constexpr int ROWLEN = 24 + 64 * RB3;
+    // FFT stage twiddles [N] | w_rx [N + 64] | per wave: row [ROWLEN] + scratch [N]
+    static constexpr int LDS = 8 * N + 4 * (N + 64) + WAVES * 8 * (ROWLEN + N);
+    static_assert(LDS <= 160 * 1024 && WAVES * N * 4 <= WAVES * 8 * (ROWLEN + N), "LDS");
+    static constexpr int PWAVES = N >= 512 ? 8 : 16;                  // pulse kernel: twiddles + e^{..} table + scratch rows
+    static constexpr int PLDS = 8 * N * (2 + PWAVES);
+};
+
+template <int N>
+__global__ void __launch_bounds__(interfm_geo<N>::PWAVES * 64)
+wofdm_interf_pulse_kernel(const wofdm_mparams p, const float *__restrict__ g_wtx, const float2 *__restrict__ g,
+                          const uint8_t *__restrict__ amask, float2 *__restrict__ cols)
+{
+    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ, WAVES = interfm_geo<N>::PWAVES;
+    constexpr bool FULL = geo<N>::FULL;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    v2f *wn = tw + N;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    v2f *scr = wn + N + (size_t)wv * N;
+    fill_twiddles<N>(tw, tid, WAVES * 64);
+    for (int i = tid; i < N; i += WAVES * 64) {
+        float sv, cv;
+        sincospif(2.0f * (float)i / (float)N, &sv, &cv);
+        wn[i] = mk(cv, sv);
+    }
+    __syncthreads();
+    const int pair = blockIdx.y, j = blockIdx.x * WAVES + wv;
+    const int P = p.P, B = p.B, L = 2 * P - 1;
+    if (j >= p.J) return;
+    const float *__restrict__ wtx = g_wtx + (size_t)pair * P;
+    v2f v[1][BPL][4];
+    if (g == nullptr) {
+        // u[j][n'] = x[j] = w_tx[j] e^{2 pi i ((j - mu) mod N) n' / N} / N (j < P), as wofdm_interf_kernel's Tx column
+        const int t = (j - p.mu) & (N - 1);
+        const float w = j < P ? wtx[j] * (1.0f / (float)N) : 0.f;
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[0][q][r] = wn[(t * (lane + 64 * q + r * NQ)) & (N - 1)] * w;
+    } else {
+        const bool own = j < P, spill = j >= B;                  // (j < J = B + P - 1 here)
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v2f a = mk(0.f, 0.f);
+                if (FULL || lane + 64 * q < NQ) {
+                    for (int c = (lane + 64 * q + r * NQ + p.mu) & (N - 1); c < P; c += N) {
+                        v2f gg = mk(0.f, 0.f);
+                        if (own) {
+                            const int i = j - c;
+                            gg = ldg2(g + (i < 0 ? i + L : i));
+                        }
+                        if (spill) gg = gg + ldg2(g + (j - B + P - c));     // in [1, 2P - 2]
+                        a = a + gg * wtx[c];
+                    }
+                }
+                v[0][q][r] = a;
+            }
+        fft_wave<N, +1, 1>(v, scr, 0, tw, lane);                 // N u[j][n']
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[0][q][r] = v[0][q][r] * (1.0f / (float)N);
+    }
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int np = lane + 64 * q + r * NQ;
+            if (!(FULL || lane + 64 * q < NQ) || (amask != nullptr && amask[np] == 0)) continue;
+            cols[((size_t)pair * N + np) * p.JP + j] = make_float2(v[0][q][r].x, v[0][q][r].y);
+        }
+}
+
+// Stage 2, one workgroup per (window pair, channel): wofdm_interf_kernel's pattern over the pulses of stage 1 -- FIR over
+// three periods, per period Rx window / fold / shift + DFT, |.|^2 row sums in registers -- with the wanted term
+// |A_0[n, n]|^2 kept apart and written out, the columns of unloaded bins skipped and the rows of unloaded bins zero.
+template <int N>
+__global__ void __launch_bounds__(interfm_geo<N>::WAVES * 64)
+wofdm_interf_masked_kernel(const wofdm_mparams p, const float *__restrict__ g_wrx, const float2 *__restrict__ g_h_,
+                           const uint8_t *__restrict__ amask, const float2 *__restrict__ cols)
+{
+    constexpr int WAVES = interfm_geo<N>::WAVES, RB3 = interfm_geo<N>::RB3, ROWLEN = interfm_geo<N>::ROWLEN, LT = WOFDM_LT;
+    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ;
+    constexpr bool FULL = geo<N>::FULL;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    v2f *tw = reinterpret_cast<v2f *>(smem);
+    float *wrx = reinterpret_cast<float *>(tw + N);
+    v2f *rows = reinterpret_cast<v2f *>(wrx + N + 64);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int job = blockIdx.x, pair = job / p.n_ch, ch = job - pair * p.n_ch;
+    const int B = p.B;
+    fill_twiddles<N>(tw, tid, WAVES * 64);
+    for (int i = tid; i < N + p.delta; i += WAVES * 64) wrx[i] = g_wrx[(size_t)pair * (N + p.delta) + i];
+    v2f *row = rows + (size_t)wv * (ROWLEN + N);
+    v2f *scr = row + ROWLEN;
+    for (int i = lane; i < ROWLEN; i += 64) row[i] = mk(0.f, 0.f);
+    __syncthreads();
+    const v2f *__restrict__ taps = reinterpret_cast<const v2f *>(g_h_) + (size_t)ch * LT;
+    float pw[BPL][4], ww[BPL][4];
+#pragma unroll
+    for (int q = 0; q < BPL; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pw[q][r] = ww[q][r] = 0.f;
+    const int h2 = p.delta >> 1;
+    for (int np = wv; np < N; np += WAVES) {
+        if (amask != nullptr && amask[np] == 0) continue;          // (wave-uniform) an unloaded bin transmits nothing
+        const float2 *__restrict__ col = cols + ((size_t)pair * N + np) * p.JP;
+        for (int j = lane; j < p.J; j += 64) row[24 + j] = ldg2(col + j);
+        for (int j = p.J + lane; j < ROWLEN - 24; j += 64) row[24 + j] = mk(0.f, 0.f);
+        wave_sync();
+        // z = conv(h, u) over three symbol periods: lane -> RB3 consecutive outputs from j0
+        v2f acc[RB3];
+        const int j0 = lane * RB3;
+        fir_lane<RB3, interfm_geo<N>::CH>(row + 24 - (LT - 1) + j0, taps, acc);
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < RB3; ++r)
+            if (j0 + r < 3 * B) row[24 + j0 + r] = acc[r];
+        wave_sync();
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            // Rx window, fold, circular shift (m:297-355) of period m, then the DFT
+            const v2f *fb = row + 24 + m * B;
+            v2f v[1][BPL][4];
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    v[0][q][r] = mk(0.f, 0.f);
+                    if (!(FULL || lane + 64 * q < NQ)) continue;
+                    const int m0 = (lane + 64 * q + r * NQ + p.kap + h2) & (N - 1);
+                    v2f z = fb[p.gam + m0] * wrx[m0];
+                    if (m0 < p.delta) {
+                        const float w2 = wrx[m0 + N];
+                        z = __builtin_elementwise_fma(mk(w2, w2), fb[p.gam + m0 + N], z);
+                    }
+                    v[0][q][r] = z;
+                }
+            fft_wave<N, -1, 1>(v, scr, 0, tw, lane);
+#pragma unroll
+            for (int q = 0; q < BPL; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int n = lane + 64 * q + r * NQ;
+                    const float e = v[0][q][r].x * v[0][q][r].x + v[0][q][r].y * v[0][q][r].y;
+                    if (!(FULL || lane + 64 * q < NQ)) continue;
+                    if (m == 0 && n == np) ww[q][r] += e;          // the wanted term A_0[n, n]
+                    else pw[q][r] += e;
+                }
+        }
+        wave_sync();
+    }
+    // sums over the waves in wave order (each wave's row is free now): float [WAVES][N] in the rows area, power then wanted
+    float *red = reinterpret_cast<float *>(rows);
+    for (int pass = 0; pass < 2; ++pass) {
+        float *dst = pass == 0 ? p.power : p.wanted;
+        if (dst == nullptr) break;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < BPL; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (FULL || lane + 64 * q < NQ) red[wv * N + lane + 64 * q + r * NQ] = pass == 0 ? pw[q][r] : ww[q][r];
+        __syncthreads();
+        for (int n = tid; n < N; n += WAVES * 64) {
+            float t = 0.f;
+            for (int w = 0; w < WAVES; ++w) t += red[w * N + n];
+            dst[(size_t)job * N + n] = (amask != nullptr && amask[n] == 0) ? 0.f : t;
+        }
+    }
+}
+
+#if WOFDM_TU_N == 64
+// Philox known-answer kernel (wofdm_philox_kat): in one unit only
+__global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
+{
+    if (threadIdx.x == 0) {
+        const philox_out o = philox4x32_10(ck[0], ck[1], ck[2], ck[3], ck[4], ck[5]);
+        for (int i = 0; i < 4; ++i) out[i] = o.w[i];
+    }
+}
+#endif
+
+// The launchers of this unit's DFT length (wofdm_aux_fns, wofdm_kernel.h)
+hipError_t interf_launch(int jobs, int P, int B, int mu, int delta, int gam, int kap, int n_ch, const float *wtx,
+                         const float *wrx, const float2 *h, float *power, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N, W = interf_geo<N>::WAVES;
+    wofdm_iparams ip;
+    ip.P = P; ip.B = B; ip.mu = mu; ip.delta = delta; ip.gam = gam; ip.kap = kap; ip.n_ch = n_ch;
+    ip.rowlen = (24 + 2 * B + 24 + 64 * interf_geo<N>::RB2 - 2 * B + 1) / 2 * 2;   // covers every lane's FIR window
+    ip.power = power;
+    const size_t lds = 8 * (size_t)N * 2 + 4 * (size_t)(N + 64) + (size_t)W * 8 * (ip.rowlen + N);
+    if (lds > 160u * 1024u) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_interf_kernel<N>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_interf_kernel<N>, dim3(jobs), dim3(W * 64), lds, s, ip, wtx, wrx, h);
+    return hipGetLastError();
+}
+
+#if WOFDM_TU_N <= 256
+// Tx waveform + periodogram (row f4)
+hipError_t psd_launch(int P, int mu, int rho, int overlap, int no_symbols, const float *wtx, const float2 *X, float2 *x,
+                      int len, float *psd, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N, FL = 8 * N, M = FL == 2048 ? 1024 : FL;
+    wofdm_wparams wp;
+    wp.P = P; wp.mu = mu; wp.rho = rho; wp.overlap = overlap; wp.no_symbols = no_symbols; wp.x = x;
+    const size_t lds_a = 8 * (size_t)N * 17, lds_b = 8 * (size_t)M * 9;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_psd_kernel<FL>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_txwave_kernel<N>, dim3((no_symbols + 15) / 16), dim3(1024), lds_a, s, wp, wtx, X);
+    hipLaunchKernelGGL(wofdm_psd_kernel<FL>, dim3(1), dim3(512), lds_b, s, (const float2 *)x, len, (len + FL - 1) / FL, psd);
+    return hipGetLastError();
+}
+#endif
+
+// the same for a batch of jobs (wofdm_tx_psd_batch), every DFT length; x zeroed by the caller, partial [n_items][8 N]
+hipError_t psd_batch_launch(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs, const wofdm_bitem *items,
+                            const float *wtx, const float2 *X, float2 *x, float *partial, float *psd, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N, FL = 8 * N, M = FL / wofdm_psd_batch_r(N), WW = bwave_geo<N>::WAVES;
+    const size_t lds_a = 8 * (size_t)N * (1 + WW), lds_b = 8 * (size_t)M * 9;
+    static_assert(8 * N * (1 + WW) <= 160 * 1024 && 8 * M * 9 <= 160 * 1024, "LDS");
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txwave_batch_kernel<N>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_psd_batch_kernel<FL>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_txwave_batch_kernel<N>, dim3((no_symbols + WW - 1) / WW, n_jobs), dim3(WW * 64), lds_a, s, jobs,
+                       no_symbols, wtx, X, x);
+    hipLaunchKernelGGL(wofdm_psd_batch_kernel<FL>, dim3(n_items), dim3(512), lds_b, s, jobs, items, (const float2 *)x, partial);
+    hipLaunchKernelGGL(wofdm_psd_reduce_kernel<FL>, dim3((FL + 255) / 256, n_jobs), dim3(256), 0, s, jobs,
+                       (const float *)partial, psd);
+    return hipGetLastError();
+}
+
+// wofdm_tx_psd_batch_masked: the unmasked jobs' waveforms by wofdm_txwave_batch_kernel, the masked ones by the fast-convolution
+// kernel and its gather, then periodogram and reduction of all jobs as in psd_batch_launch
+hipError_t psd_batch_masked_launch(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs, const wofdm_bitem *items,
+                                   int n_plain, const wofdm_bjob *plain_jobs, int n_masked, const wofdm_mjob *mjobs, int max_len,
+                                   const float2 *spec, float2 *Y, const float *wtx, const float2 *X, float2 *x, float *partial,
+                                   float *psd, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N, FL = 8 * N, M = FL / wofdm_psd_batch_r(N), WW = bwave_geo<N>::WAVES, G = bmask_geo<N>::G;
+    const size_t lds_a = 8 * (size_t)N * (1 + WW), lds_b = 8 * (size_t)M * 9, lds_m = bmask_geo<N>::LDS;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txwave_batch_kernel<N>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_psd_batch_kernel<FL>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txmask_batch_kernel<N>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
+    if (e != hipSuccess) return e;
+    if (n_plain > 0)
+        hipLaunchKernelGGL(wofdm_txwave_batch_kernel<N>, dim3((no_symbols + WW - 1) / WW, n_plain), dim3(WW * 64), lds_a, s,
+                           plain_jobs, no_symbols, wtx, X, x);
+    if (n_masked > 0) {
+        hipLaunchKernelGGL(wofdm_txmask_batch_kernel<N>, dim3((no_symbols + G - 1) / G, n_masked), dim3(512), lds_m, s, jobs,
+                           mjobs, no_symbols, wtx, X, spec, Y);
+        hipLaunchKernelGGL(wofdm_txmask_ola_kernel<N>, dim3((max_len + 255) / 256, n_masked), dim3(256), 0, s, jobs, mjobs,
+                           no_symbols, (const float2 *)Y, x);
+    }
+    hipLaunchKernelGGL(wofdm_psd_batch_kernel<FL>, dim3(n_items), dim3(512), lds_b, s, jobs, items, (const float2 *)x, partial);
+    hipLaunchKernelGGL(wofdm_psd_reduce_kernel<FL>, dim3((FL + 255) / 256, n_jobs), dim3(256), 0, s, jobs,
+                       (const float *)partial, psd);
+    return hipGetLastError();
+}
+
+// wofdm_interference_masked: the pulses of every pair, then the (pair, channel) jobs
+hipError_t interf_masked_launch(int pairs, int n_ch, int P, int B, int mu, int delta, int gam, int kap, int JP, const float *wtx,
+                                const float *wrx, const float2 *h, const float2 *g, const uint8_t *amask, float2 *cols,
+                                float *power, float *wanted, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N, W = interfm_geo<N>::WAVES, PW = interfm_geo<N>::PWAVES;
+    wofdm_mparams mp;
+    mp.P = P; mp.B = B; mp.mu = mu; mp.delta = delta; mp.gam = gam; mp.kap = kap; mp.n_ch = n_ch;
+    mp.J = B + P - 1; mp.JP = JP;
+    mp.power = power; mp.wanted = wanted;
+    // the row of a wave holds three periods: 3 B <= 64 RB3, and the pulse with the channel ends within them
+    if (3 * B > 64 * interfm_geo<N>::RB3 || mp.J + WOFDM_LT - 1 > 3 * B || JP < mp.J || delta > 64) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_interf_pulse_kernel<N>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, interfm_geo<N>::PLDS);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_interf_masked_kernel<N>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, interfm_geo<N>::LDS);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_interf_pulse_kernel<N>, dim3((mp.J + PW - 1) / PW, pairs), dim3(PW * 64), interfm_geo<N>::PLDS, s,
+                       mp, wtx, g, amask, cols);
+    hipLaunchKernelGGL(wofdm_interf_masked_kernel<N>, dim3(pairs * n_ch), dim3(W * 64), interfm_geo<N>::LDS, s, mp, wrx, h,
+                       amask, (const float2 *)cols);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+const wofdm_aux_fns *WOFDM_CAT(wofdm_aux_n, WOFDM_TU_N)(void)
+{
+#if WOFDM_TU_N <= 256
+    static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, psd_launch, psd_batch_launch, psd_batch_masked_launch};
+#else
+    static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, nullptr, psd_batch_launch, psd_batch_masked_launch};
+#endif
+    return &fns;
+}
+
+#if WOFDM_TU_N == 64
+hipError_t wofdm_philox_kat_launch(const uint32_t *ctr_key_dev, uint32_t *out_dev, hipStream_t s)
+{
+    hipLaunchKernelGGL(philox_kat_kernel, dim3(1), dim3(64), 0, s, ctr_key_dev, out_dev);
+    return hipGetLastError();
+}
+#endif

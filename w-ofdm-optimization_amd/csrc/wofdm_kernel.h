@@ -340,23 +340,8 @@ static inline wofdm_kernel_fn wofdm_select_kernel(int n_fft, int bits_per_sc, in
     return nullptr;
 }
 hipError_t wofdm_philox_kat_launch(const uint32_t *ctr_key_dev, uint32_t *out_dev, hipStream_t s);
-// closed-form ICI/ISI power kernels (wofdm_kernel.hip, k = 2 translation units)
-#define WOFDM_INTERF_DECL(n)                                                                                  \
-    hipError_t wofdm_interf_launch_n##n(int jobs, int P, int B, int mu, int delta, int gam, int kap, int n_ch, \
-                                        const float *wtx, const float *wrx, const float2 *h, float *power,     \
-                                        hipStream_t s)
-WOFDM_INTERF_DECL(64);
-WOFDM_INTERF_DECL(128);
-WOFDM_INTERF_DECL(256);
-WOFDM_INTERF_DECL(512);
-WOFDM_INTERF_DECL(1024);
-// Tx waveform + averaged periodogram (row f4), N <= 256 (transform length 8 N <= 2048)
-#define WOFDM_PSD_DECL(n)                                                                                         \
-    hipError_t wofdm_psd_launch_n##n(int P, int mu, int rho, int overlap, int no_symbols, const float *wtx,        \
-                                     const float2 *X, float2 *x, int len, float *psd, hipStream_t s)
-WOFDM_PSD_DECL(64);
-WOFDM_PSD_DECL(128);
-WOFDM_PSD_DECL(256);
+
+// ---- The auxiliary kernels (wofdm_aux.hip, one translation unit per DFT length: -DWOFDM_TU_N=<N>) ----
 
 // Tx waveform + averaged periodogram for a batch of jobs (wofdm_tx_psd_batch), every N.  A job's waveform sits at
 // x + x_off (len samples); its periodogram is summed by the work items item0 ... item0 + n_items - 1 (one workgroup
@@ -374,15 +359,6 @@ struct wofdm_bitem {
 // points (R = 1); 8 waves per workgroup = 8 / R slices at a time, 4 rounds per work item
 __host__ __device__ constexpr int wofdm_psd_batch_r(int n_fft) { return 8 * n_fft > 1024 ? 8 * n_fft / 1024 : 1; }
 __host__ __device__ constexpr int wofdm_psd_batch_slices(int n_fft) { return 4 * (8 / wofdm_psd_batch_r(n_fft)); }
-#define WOFDM_PSD_BATCH_DECL(n)                                                                                       \
-    hipError_t wofdm_psd_batch_launch_n##n(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs,           \
-                                           const wofdm_bitem *items, const float *wtx, const float2 *X, float2 *x,    \
-                                           float *partial, float *psd, hipStream_t s)
-WOFDM_PSD_BATCH_DECL(64);
-WOFDM_PSD_BATCH_DECL(128);
-WOFDM_PSD_BATCH_DECL(256);
-WOFDM_PSD_BATCH_DECL(512);
-WOFDM_PSD_BATCH_DECL(1024);
 
 // Masked jobs of wofdm_tx_psd_batch_masked: the spectral Tx mask as fast convolution over 8 n_fft points (3 P - 2 of them
 // in use), so P <= (8 n_fft + 2) / 3 -- every cp + cs <= n_fft / 2 and more.  A masked job keeps the whole filtered symbols
@@ -392,31 +368,44 @@ struct wofdm_mjob {
     int64_t y_off;
 };
 __host__ __device__ constexpr int wofdm_txmask_batch_pmax(int n_fft) { return (8 * n_fft + 2) / 3; }
-// plain_jobs: the n_plain unmasked jobs (waveform by wofdm_txwave_batch_kernel, as wofdm_psd_batch_launch); mjobs: the
-// n_masked masked ones; max_len: longest masked waveform.  Periodogram and reduction over the whole table `jobs`.
-#define WOFDM_PSD_BATCH_MASKED_DECL(n)                                                                                \
-    hipError_t wofdm_psd_batch_masked_launch_n##n(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs,    \
-                                                  const wofdm_bitem *items, int n_plain, const wofdm_bjob *plain_jobs, \
-                                                  int n_masked, const wofdm_mjob *mjobs, int max_len,                 \
-                                                  const float2 *spec, float2 *Y, const float *wtx, const float2 *X,   \
-                                                  float2 *x, float *partial, float *psd, hipStream_t s)
-WOFDM_PSD_BATCH_MASKED_DECL(64);
-WOFDM_PSD_BATCH_MASKED_DECL(128);
-WOFDM_PSD_BATCH_MASKED_DECL(256);
-WOFDM_PSD_BATCH_MASKED_DECL(512);
-WOFDM_PSD_BATCH_MASKED_DECL(1024);
 
-// Closed-form ICI/ISI power of the half-band, masked system (wofdm_interference_masked; the -DWOFDM_TU_K=0 units): the masked
-// on-air pulses of every loaded bin once per window pair into cols[pairs][n_fft][JP] (J = B + P - 1 samples each, JP >= J the
-// row pitch), then one workgroup per (pair, channel) job.  g: the mask's circular impulse response [2P - 1], or null = no
-// mask; amask: [n_fft] 0 / 1, or null = every bin loaded; wanted may be null.
-#define WOFDM_INTERF_MASKED_DECL(n)                                                                                    \
-    hipError_t wofdm_interf_masked_launch_n##n(int pairs, int n_ch, int P, int B, int mu, int delta, int gam, int kap,  \
-                                               int JP, const float *wtx, const float *wrx, const float2 *h,             \
-                                               const float2 *g, const uint8_t *amask, float2 *cols, float *power,       \
-                                               float *wanted, hipStream_t s)
-WOFDM_INTERF_MASKED_DECL(64);
-WOFDM_INTERF_MASKED_DECL(128);
-WOFDM_INTERF_MASKED_DECL(256);
-WOFDM_INTERF_MASKED_DECL(512);
-WOFDM_INTERF_MASKED_DECL(1024);
+// the launchers of one DFT length
+struct wofdm_aux_fns {
+    // closed-form ICI/ISI power kernels
+    hipError_t (*interf)(int jobs, int P, int B, int mu, int delta, int gam, int kap, int n_ch, const float *wtx,
+                         const float *wrx, const float2 *h, float *power, hipStream_t s);
+    // Closed-form ICI/ISI power of the half-band, masked system (wofdm_interference_masked): the masked on-air pulses of every
+    // loaded bin once per window pair into cols[pairs][n_fft][JP] (J = B + P - 1 samples each, JP >= J the row pitch), then one
+    // workgroup per (pair, channel) job.  g: the mask's circular impulse response [2P - 1], or null = no mask; amask: [n_fft]
+    // 0 / 1, or null = every bin loaded; wanted may be null.
+    hipError_t (*interf_masked)(int pairs, int n_ch, int P, int B, int mu, int delta, int gam, int kap, int JP, const float *wtx,
+                                const float *wrx, const float2 *h, const float2 *g, const uint8_t *amask, float2 *cols,
+                                float *power, float *wanted, hipStream_t s);
+    // Tx waveform + averaged periodogram (row f4), N <= 256 (transform length 8 N <= 2048); null above
+    hipError_t (*psd)(int P, int mu, int rho, int overlap, int no_symbols, const float *wtx, const float2 *X, float2 *x, int len,
+                      float *psd, hipStream_t s);
+    hipError_t (*psd_batch)(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs, const wofdm_bitem *items,
+                            const float *wtx, const float2 *X, float2 *x, float *partial, float *psd, hipStream_t s);
+    // plain_jobs: the n_plain unmasked jobs (waveform by wofdm_txwave_batch_kernel, as psd_batch); mjobs: the n_masked masked
+    // ones; max_len: longest masked waveform.  Periodogram and reduction over the whole table `jobs`.
+    hipError_t (*psd_batch_masked)(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs, const wofdm_bitem *items,
+                                   int n_plain, const wofdm_bjob *plain_jobs, int n_masked, const wofdm_mjob *mjobs, int max_len,
+                                   const float2 *spec, float2 *Y, const float *wtx, const float2 *X, float2 *x, float *partial,
+                                   float *psd, hipStream_t s);
+};
+const wofdm_aux_fns *wofdm_aux_n64(void);
+const wofdm_aux_fns *wofdm_aux_n128(void);
+const wofdm_aux_fns *wofdm_aux_n256(void);
+const wofdm_aux_fns *wofdm_aux_n512(void);
+const wofdm_aux_fns *wofdm_aux_n1024(void);
+static inline const wofdm_aux_fns *wofdm_aux(int n_fft)
+{
+    switch (n_fft) {
+    case 64: return wofdm_aux_n64();
+    case 128: return wofdm_aux_n128();
+    case 256: return wofdm_aux_n256();
+    case 512: return wofdm_aux_n512();
+    case 1024: return wofdm_aux_n1024();
+    }
+    return nullptr;
+}

@@ -29,6 +29,7 @@
 // subcarrier allocation and the per-symbol spectral Tx mask of main_channel_mask.m (VAR), injected
 // randomness (INJECT) and stage dumps (DUMP).
 #include "wofdm_kernel.h"
+#include "wofdm_device.h"
 #include "philox.h"
 #include <type_traits>
 #include <utility>
@@ -131,14 +132,6 @@ namespace {
 #define DELAY_AT(pt) do { } while (0)
 #endif
 
-// Complex samples are 2-wide float vectors: gfx950 issues one wave64 VALU instruction per
-// ~4 cycles per SIMD whether it is v_fma_f32 or v_pk_fma_f32 (tools/ubench/valu_rate.hip:
-// 4.5 vs 5.1 cycles), so the fp32 peak is only reachable with packed math, and complex
-// arithmetic packs naturally as (re, im).
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ v2f mk(float x, float y) { return (v2f){x, y}; }
-
 // Matrix-pipe FIR (layouts 6, 7, 8): samples travel through LDS as two packed-f16 words, y = hi + lo with both
 // halves rounded to nearest: two 11-bit significands, |y - hi - lo| <= 2^-22 |y|.  Three f16 MFMA terms
 // (h_hi x_hi + h_hi x_lo + h_lo x_hi, fp32 accumulation) drop h_lo x_lo, another 2^-22: a product is good to about
@@ -181,336 +174,6 @@ __device__ __forceinline__ v2f join_h(uint32_t hi, uint32_t lo)
 {
     return __builtin_convertvector(__builtin_bit_cast(h2, hi), v2f)
            + __builtin_convertvector(__builtin_bit_cast(h2, lo), v2f);
-}
-
-__device__ __forceinline__ void wave_sync()
-{
-    // LDS traffic between lanes of ONE wave: DS ops execute in issue order, so only the
-    // compiler has to be kept from reordering across this point.
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// a * w  (2 packed instructions; swizzle and sign live in the VOP3P modifiers)
-__device__ __forceinline__ v2f cmul(v2f a, v2f w)
-{
-    v2f t, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(t) : "v"(a), "v"(w));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]"
-        : "=v"(r) : "v"(a), "v"(w), "v"(t));
-    return r;
-}
-// a * conj(w)
-__device__ __forceinline__ v2f cmul_conj(v2f a, v2f w)
-{
-    v2f t, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(t) : "v"(a), "v"(w));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1]"
-        : "=v"(r) : "v"(a), "v"(w), "v"(t));
-    return r;
-}
-// a + (-i) d = (a.x + d.y, a.y - d.x)   and   a + (+i) d = (a.x - d.y, a.y + d.x)
-__device__ __forceinline__ v2f add_mi(v2f a, v2f d)
-{
-    v2f r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(d));
-    return r;
-}
-__device__ __forceinline__ v2f add_pi(v2f a, v2f d)
-{
-    v2f r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(d));
-    return r;
-}
-// tw tables hold exp(-2 pi i ...): the forward DFT multiplies by them, the inverse by the conjugate
-template <int DIR> __device__ __forceinline__ v2f twid(v2f a, v2f w)
-{
-    return DIR < 0 ? cmul(a, w) : cmul_conj(a, w);
-}
-
-template <int DIR> __device__ __forceinline__ void radix4(v2f (&u)[4])
-{
-    const v2f a0 = u[0] + u[2], a1 = u[0] - u[2];
-    const v2f a2 = u[1] + u[3], d = u[1] - u[3];
-    u[0] = a0 + a2;
-    u[2] = a0 - a2;
-    u[1] = DIR < 0 ? add_mi(a1, d) : add_pi(a1, d);      // a1 + (-+ i) d
-    u[3] = DIR < 0 ? add_pi(a1, d) : add_mi(a1, d);      // a1 - (-+ i) d
-}
-
-template <int N> struct geo {
-    static constexpr int NQ = N / 4;                 // radix-4 butterflies per stage
-    static constexpr int BPL = (NQ + 63) / 64;       // ... per lane
-    static constexpr int RB = N / 64 + 1;            // FIR outputs per lane
-    static constexpr bool FULL = NQ >= 64 * BPL;     // every lane owns BPL butterflies
-    // Twiddle tables, one per stage after the first, laid out [k][r-1] so that the three
-    // factors of a butterfly are adjacent and lanes hit distinct banks:
-    //   radix-4 stage NS: 3*NS entries exp(-2 pi i r k / (4 NS));  radix-2 stage NS: NS entries.
-    static constexpr int tw_off(int stage_ns)
-    {
-        // stages in execution order for this N (after the twiddle-free first stage)
-        int off = 0, ns = 4;
-        while (ns < stage_ns) {
-            const bool r2 = (N == 128 && ns == 4) || (N == 512 && ns == 16);
-            off += r2 ? ns : 3 * ns;
-            ns *= r2 ? 2 : 4;
-        }
-        return off;
-    }
-};
-
-// Stockham autosort stages on the wave's LDS slices.  Lane data v[u][q][r] always means element
-// (lane + 64 q) + r N/4 of the wave's u-th symbol, both as the first stage's input and the last
-// stage's output.  Every stage handles the wave's SPW symbols together (slices `sb` apart), so
-// the independent transforms share one write->read turnaround per stage instead of queueing
-// behind each other's fences.
-template <int N, int DIR, int SPW>
-__device__ __forceinline__ void fft_first(v2f (&v)[SPW][geo<N>::BPL][4], v2f *fb, int sb, int lane)
-{
-#pragma unroll
-    for (int u = 0; u < SPW; ++u) {
-#pragma unroll
-        for (int q = 0; q < geo<N>::BPL; ++q) {
-            const int j = lane + 64 * q;
-            if (geo<N>::FULL || j < geo<N>::NQ) {
-                radix4<DIR>(v[u][q]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) fb[u * sb + 4 * j + r] = v[u][q][r];
-            }
-        }
-    }
-    wave_sync();
-}
-
-template <int N, int NS, int DIR, int SPW>
-__device__ __forceinline__ void fft_mid4(v2f *fb, int sb, const v2f *tw, int lane)
-{
-    v2f u4[SPW][geo<N>::BPL][4];
-    const v2f *t = tw + geo<N>::tw_off(NS);
-#pragma unroll
-    for (int u = 0; u < SPW; ++u) {
-#pragma unroll
-        for (int q = 0; q < geo<N>::BPL; ++q) {
-            const int j = lane + 64 * q;
-            if (geo<N>::FULL || j < geo<N>::NQ) {
-                const int k = j & (NS - 1);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) u4[u][q][r] = fb[u * sb + j + r * geo<N>::NQ];
-#pragma unroll
-                for (int r = 1; r < 4; ++r) u4[u][q][r] = twid<DIR>(u4[u][q][r], t[3 * k + r - 1]);
-                radix4<DIR>(u4[u][q]);
-            }
-        }
-    }
-    wave_sync();
-#pragma unroll
-    for (int u = 0; u < SPW; ++u) {
-#pragma unroll
-        for (int q = 0; q < geo<N>::BPL; ++q) {
-            const int j = lane + 64 * q;
-            if (geo<N>::FULL || j < geo<N>::NQ) {
-                const int k = j & (NS - 1);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) fb[u * sb + ((j - k) << 2) + k + r * NS] = u4[u][q][r];
-            }
-        }
-    }
-    wave_sync();
-}
-
-template <int N, int NS, int DIR, int SPW>
-__device__ __forceinline__ void fft_mid2(v2f *fb, int sb, const v2f *tw, int lane)
-{
-    constexpr int NB = N / 2, PER = (NB + 63) / 64;
-    v2f y0[SPW][PER], y1[SPW][PER];
-    const v2f *t = tw + geo<N>::tw_off(NS);
-#pragma unroll
-    for (int u = 0; u < SPW; ++u) {
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int j = lane + 64 * q;
-            if (j < NB) {
-                const int k = j & (NS - 1);
-                const v2f a = fb[u * sb + j];
-                const v2f b = twid<DIR>(fb[u * sb + j + NB], t[k]);
-                y0[u][q] = a + b; y1[u][q] = a - b;
-            }
-        }
-    }
-    wave_sync();
-#pragma unroll
-    for (int u = 0; u < SPW; ++u) {
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int j = lane + 64 * q;
-            if (j < NB) {
-                const int k = j & (NS - 1);
-                fb[u * sb + ((j - k) << 1) + k] = y0[u][q];
-                fb[u * sb + ((j - k) << 1) + k + NS] = y1[u][q];
-            }
-        }
-    }
-    wave_sync();
-}
-
-template <int N, int DIR, int SPW>
-__device__ __forceinline__ void fft_last(v2f (&v)[SPW][geo<N>::BPL][4], const v2f *fb, int sb,
-                                         const v2f *tw, int lane)
-{
-    const v2f *t = tw + geo<N>::tw_off(geo<N>::NQ);
-#pragma unroll
-    for (int u = 0; u < SPW; ++u) {
-#pragma unroll
-        for (int q = 0; q < geo<N>::BPL; ++q) {
-            const int j = lane + 64 * q;
-            if (geo<N>::FULL || j < geo<N>::NQ) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[u][q][r] = fb[u * sb + j + r * geo<N>::NQ];
-#pragma unroll
-                for (int r = 1; r < 4; ++r) v[u][q][r] = twid<DIR>(v[u][q][r], t[3 * j + r - 1]);
-                radix4<DIR>(v[u][q]);
-            }
-        }
-    }
-    wave_sync();
-}
-
-// ---------------------------------------------------------------------------------------------
-// N = 512 / 1024: three Stockham stages  R . R2 . R  with R = 8 / 16 points held by one lane
-// (N = 8.8.8 = 16.4.16), i.e. two LDS round trips instead of four.  A lane owns elements
-// lane + 64 t, t = q + BPL r -- exactly the inputs of butterfly `lane` of a first stage of radix
-// R = 4 BPL (Ns = 1) and the outputs of butterfly `lane` of a last stage of radix R (Ns = 64),
-// so natural order in and out survives.  The in-register R-point DFT is a radix-4 pass over r,
-// constant twiddles, and a radix-4 (radix-2) pass over q.
-//
-// Twiddle table (fill_twiddles):  N = 1024: [0,48) stage 2 exp(-2 pi i r k/64) at [3k + r-1];
-// [48,1008) stage 3 exp(-2 pi i t j/1024) at [48 + 15 j + t-1].  N = 512: [0,56) stage 2
-// exp(-2 pi i t k/64) at [7k + t-1]; [56,504) stage 3 exp(-2 pi i t j/512) at [56 + 7j + t-1].
-//
-// Stage 1 stores R consecutive outputs per lane (stride R v2f across lanes: every lane on the same
-// banks); the position inside each group of R is XOR-swizzled with the group number so that a
-// store instruction spreads over all banks, and stage 2 undoes it when it loads.
-template <int R> __device__ __forceinline__ int swz(int idx)
-{
-    constexpr int LG = R == 16 ? 4 : 3;
-    const int a = idx >> LG;
-    return idx ^ ((a ^ (a >> LG)) & (R - 1));
-}
-
-// x[q][r] = x_t, t = q + 4 r   ->   x[q][r] = X_u, u = r + 4 q     (16 points)
-template <int DIR> __device__ __forceinline__ void dft16(v2f (&x)[4][4])
-{
-    constexpr float c1 = 0.92387953251128674f, s1 = 0.38268343236508977f, h = 0.70710678118654752f;
-    // exp(-2 pi i m/16) for m = q c
-    const v2f w1 = mk(c1, -s1), w2 = mk(h, -h), w3 = mk(s1, -c1), w4 = mk(0.f, -1.f), w6 = mk(-h, -h),
-              w9 = mk(-c1, s1);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) radix4<DIR>(x[q]);
-    x[1][1] = twid<DIR>(x[1][1], w1); x[1][2] = twid<DIR>(x[1][2], w2); x[1][3] = twid<DIR>(x[1][3], w3);
-    x[2][1] = twid<DIR>(x[2][1], w2); x[2][2] = twid<DIR>(x[2][2], w4); x[2][3] = twid<DIR>(x[2][3], w6);
-    x[3][1] = twid<DIR>(x[3][1], w3); x[3][2] = twid<DIR>(x[3][2], w6); x[3][3] = twid<DIR>(x[3][3], w9);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        v2f col[4] = {x[0][c], x[1][c], x[2][c], x[3][c]};
-        radix4<DIR>(col);
-#pragma unroll
-        for (int d = 0; d < 4; ++d) x[d][c] = col[d];
-    }
-}
-// x[q][r] = x_t, t = q + 2 r   ->   x[q][r] = X_u, u = r + 4 q     (8 points)
-template <int DIR> __device__ __forceinline__ void dft8(v2f (&x)[2][4])
-{
-    constexpr float h = 0.70710678118654752f;
-    radix4<DIR>(x[0]);
-    radix4<DIR>(x[1]);
-    x[1][1] = twid<DIR>(x[1][1], mk(h, -h));
-    x[1][2] = twid<DIR>(x[1][2], mk(0.f, -1.f));
-    x[1][3] = twid<DIR>(x[1][3], mk(-h, -h));
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const v2f a = x[0][c], b = x[1][c];
-        x[0][c] = a + b;
-        x[1][c] = a - b;
-    }
-}
-template <int N, int DIR> __device__ __forceinline__ void dft_lane(v2f (&x)[geo<N>::BPL][4])
-{
-    if constexpr (N == 1024) dft16<DIR>(x);
-    else dft8<DIR>(x);
-}
-
-template <int N, int DIR>
-__device__ __forceinline__ void fft_big(v2f (&v)[1][geo<N>::BPL][4], v2f *fb, const v2f *tw, int lane)
-{
-    static_assert(N == 512 || N == 1024, "fft_big is the 8.8.8 / 16.4.16 scheme");
-    constexpr int BPL = geo<N>::BPL, R = 4 * BPL;             // 2, 8  or  4, 16
-    constexpr int T2 = N == 1024 ? 48 : 56;                    // start of the stage-3 twiddles
-    // ---- stage 1: radix R, Ns = 1, from registers; out[R lane + u]
-    dft_lane<N, DIR>(v[0]);
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) fb[swz<R>(R * lane + r + 4 * q)] = v[0][q][r];
-    wave_sync();
-    if constexpr (N == 1024) {
-        // ---- stage 2: radix 4, Ns = 16: butterflies j = lane + 64 q
-        v2f u4[4][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int j = lane + 64 * q, k = j & 15;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) u4[q][r] = fb[swz<16>(j + 256 * r)];
-#pragma unroll
-            for (int r = 1; r < 4; ++r) u4[q][r] = twid<DIR>(u4[q][r], tw[3 * k + r - 1]);
-            radix4<DIR>(u4[q]);
-        }
-        wave_sync();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int j = lane + 64 * q, k = j & 15;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) fb[((j - k) << 2) + k + 16 * r] = u4[q][r];
-        }
-    } else {
-        // ---- stage 2: radix 8, Ns = 8: butterfly j = lane
-        v2f u8[2][4];
-        const int k = lane & 7;
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int t = q + 2 * r;
-                u8[q][r] = fb[swz<8>(lane + 64 * t)];
-                if (t > 0) u8[q][r] = twid<DIR>(u8[q][r], tw[7 * k + t - 1]);
-            }
-        dft8<DIR>(u8);
-        wave_sync();
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) fb[((lane - k) << 3) + k + 8 * (r + 4 * q)] = u8[q][r];
-    }
-    wave_sync();
-    // ---- stage 3: radix R, Ns = 64, to registers: in[lane + 64 t], twiddle^(t lane), out lane + 64 u
-    v2f x[BPL][4];
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int t = q + BPL * r;
-            x[q][r] = fb[lane + 64 * t];
-            if (t > 0) x[q][r] = twid<DIR>(x[q][r], tw[T2 + (R - 1) * lane + t - 1]);
-        }
-    dft_lane<N, DIR>(x);
-    // x[q'][r'] = X_u with u = r' + 4 q';  the lane owns u = q + BPL r
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int u = q + BPL * r;
-            v[0][q][r] = x[u >> 2][u & 3];
-        }
-    wave_sync();
 }
 
 // The same 1024-point transform with a 512-entry (4 KB) exchange buffer: both exchanges run in two
@@ -846,93 +509,6 @@ __device__ __forceinline__ void radix8_elems(f4 &r0, f4 &i0, f4 &r1, f4 &i1)
     r1 = pr; i1 = pi;
 }
 
-// registers -> (LDS stages) -> registers, natural order in and out, SPW symbols at once
-template <int N, int DIR, int SPW>
-__device__ __forceinline__ void fft_wave(v2f (&v)[SPW][geo<N>::BPL][4], v2f *fb, int sb, const v2f *tw,
-                                         int lane)
-{
-    // N = 512 / 1024: 8.8.8 / 16.4.16 with the outer stages in registers (fft_big); the smaller sizes: the radix-4/2 ladder
-    // through LDS
-    if constexpr (N == 512 || N == 1024) {
-        static_assert(SPW == 1, "one symbol per wave at N >= 512");
-        fft_big<N, DIR>(v, fb, tw, lane);
-    } else {
-        fft_first<N, DIR, SPW>(v, fb, sb, lane);
-        if constexpr (N == 64) {
-            fft_mid4<N, 4, DIR, SPW>(fb, sb, tw, lane);
-        } else if constexpr (N == 128) {
-            fft_mid2<N, 4, DIR, SPW>(fb, sb, tw, lane);
-            fft_mid4<N, 8, DIR, SPW>(fb, sb, tw, lane);
-        } else {
-            static_assert(N == 256, "unsupported DFT length");
-            fft_mid4<N, 4, DIR, SPW>(fb, sb, tw, lane);
-            fft_mid4<N, 16, DIR, SPW>(fb, sb, tw, lane);
-        }
-        fft_last<N, DIR, SPW>(v, fb, sb, tw, lane);
-    }
-}
-
-// Fill the per-stage twiddle tables (once per workgroup).
-template <int N> __device__ __forceinline__ void fill_twiddles(v2f *tw, int tid, int nthreads)
-{
-    if constexpr (N == 512 || N == 1024) {
-        // tables of fft_big
-        constexpr int R = N / 64, T2 = N == 1024 ? 48 : 56;
-        for (int i = tid; i < T2 + (R - 1) * 64; i += nthreads) {
-            float num, den;
-            if (i < T2) {
-                const int per = N == 1024 ? 3 : 7;
-                num = (float)((i / per) * (1 + i % per)); den = 64.0f;                   // r k / 64
-            } else {
-                const int e = i - T2;
-                num = (float)((e / (R - 1)) * (1 + e % (R - 1))); den = (float)N;        // t j / N
-            }
-            float sv, cv;
-            sincospif(-2.0f * num / den, &sv, &cv);
-            tw[i] = mk(cv, sv);
-        }
-        return;
-    }
-    int off = 0, ns = 4;
-    while (ns <= N / 4) {
-        const bool r2 = (N == 128 && ns == 4) || (N == 512 && ns == 16);
-        const int cnt = r2 ? ns : 3 * ns;
-        for (int i = tid; i < cnt; i += nthreads) {
-            const int k = r2 ? i : i / 3, r = r2 ? 1 : 1 + i % 3;
-            float sv, cv;
-            sincospif(-2.0f * (float)(r * k) / (float)((r2 ? 2 : 4) * ns), &sv, &cv);
-            tw[off + i] = mk(cv, sv);
-        }
-        off += cnt;
-        ns *= r2 ? 2 : 4;
-    }
-}
-
-// CNT consecutive FIR outputs starting at window base w (w[i] = tx[j0 - (LT-1) + i]).
-// The taps are wave-uniform and read through a noalias kernel argument, so they arrive by
-// scalar loads as SGPR pairs and feed v_pk_fma_f32 directly: 2 instructions per complex MAC.
-template <int CNT>
-__device__ __forceinline__ void fir_chunk(const v2f *w, const v2f *__restrict__ taps, v2f *acc)
-{
-    constexpr int LT = WOFDM_LT;
-    v2f win[CNT + LT - 1];
-#pragma unroll
-    for (int i = 0; i < CNT + LT - 1; ++i) win[i] = w[i];
-#pragma unroll
-    for (int r = 0; r < CNT; ++r) acc[r] = mk(0.f, 0.f);
-#pragma unroll
-    for (int l = 0; l < LT; ++l) {
-        const v2f t = taps[l];
-        const v2f tn = mk(-t.y, t.y);
-#pragma unroll
-        for (int r = 0; r < CNT; ++r) {
-            const v2f x = win[r + LT - 1 - l];
-            acc[r] = __builtin_elementwise_fma(t.xx, x, acc[r]);
-            acc[r] = __builtin_elementwise_fma(tn, x.yx, acc[r]);
-        }
-    }
-}
-
 // one complex unit normal from two Philox words (philox.h).  The angle uses the top 23 bits of b as the
 // mantissa of a float in [1, 2): v_sin / v_cos take revolutions, so the integer part drops out and no
 // convert + scale is needed.  UNIT = false leaves out the factor sqrt(2 ln 2) of the radius
@@ -1048,8 +624,6 @@ __device__ __forceinline__ void post_flag(lds_vint *flag, int value, int lane)
     if (lane == 0) *flag = value;
 }
 
-__device__ __forceinline__ v2f ldg2(const float2 *p) { const float2 t = *p; return mk(t.x, t.y); }
-
 // Tx mask stage (VAR 2): a lane owns NO consecutive outputs of the 2P-1 <= 2(N+128)-1 samples of
 // the filtered symbol; the inputs are walked MB at a time.  rg[] is the periodic extension of the
 // mask's impulse response (complex: the reference's mask is not even around bin 0 when P is odd),
@@ -1077,15 +651,6 @@ template <int N, int LAY> struct fir_geo {
     static constexpr int NBK = EVEN ? RB / 2 : RB / 2 + 1;      // Philox blocks per lane
     static constexpr int CH = RB <= 6 ? RB : (RB % 5 == 0 ? 5 : 6);
 };
-
-template <int RB, int CH>
-__device__ __forceinline__ void fir_lane(const v2f *w, const v2f *__restrict__ taps, v2f (&acc)[RB])
-{
-    constexpr int FULL = RB / CH, REM = RB % CH;
-#pragma unroll
-    for (int c = 0; c < FULL; ++c) fir_chunk<CH>(w + c * CH, taps, &acc[c * CH]);
-    if constexpr (REM != 0) fir_chunk<REM>(w + FULL * CH, taps, &acc[FULL * CH]);
-}
 
 // VAR: 0 = every subcarrier loaded (main_BER_calculation.m); 1 = subcarrier allocation: only the
 // bins flagged in g_amask carry data, the others transmit zero and are not counted
@@ -3901,873 +3466,6 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
 #endif
 }
 
-// ---------------------------------------------------------------------------------------------
-// Closed-form ICI + ISI power of a structure:
-//   calculate_interference  matlab/main_interference_calculation.m:177-225
-//   interf_power            python/ofdm_utils/interf_calc.py:20-113
-//     A_m = W K P V_rx R  H_m  V_tx Gamma W^-1,   H_m[b, c] = h[m B + b - c],   m = 0, 1
-//     P[n] = sum_{n' != n} |A_0[n, n']|^2 + sum_{n'} |A_1[n, n']|^2
-// Column n' of A_m is the frame pipeline's own answer to a unit symbol on subcarrier n': the windowed,
-// CP/CS-extended complex exponential x (the Tx matrix applied to e_n'), the 21-tap convolution over two
-// symbol periods, and per period the Rx window / fold / shift + DFT of the kernels above -- no dense
-// matrices, no RNG.  One workgroup per (window pair, channel) job; a wave takes the columns
-// n' = wave, wave + W, ... and keeps |A|^2 row sums of its subcarriers (FFT output layout) in registers;
-// one LDS reduction over the waves at the end.  (M = 1 + ceil((L - 1 + beta) / B) = 2 for every
-// supported structure: B >= 64 > 36.)
-struct wofdm_iparams {
-    int P, B, mu, delta, gam, kap, n_ch, rowlen;   // rowlen: float2 per wave row (24 + 2B + 24 rounded up)
-    float *power;                                  // [pairs][n_ch][N]
-};
-template <int N> struct interf_geo {
-    static constexpr int WAVES = N <= 256 ? 16 : (N == 512 ? 8 : 4);
-    static constexpr int RB2 = 2 * (N / 64 + 1);                      // FIR outputs per lane over 2B samples
-    static constexpr int CH = RB2 % 6 == 0 ? 6 : (RB2 % 5 == 0 ? 5 : (RB2 % 4 == 0 ? 4 : 2));
-};
-
-template <int N>
-__global__ void __launch_bounds__(interf_geo<N>::WAVES * 64)
-wofdm_interf_kernel(const wofdm_iparams p, const float *__restrict__ g_wtx, const float *__restrict__ g_wrx,
-                    const float2 *__restrict__ g_h_)
-{
-    constexpr int WAVES = interf_geo<N>::WAVES, RB2 = interf_geo<N>::RB2, LT = WOFDM_LT;
-    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ;
-    constexpr bool FULL = geo<N>::FULL;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // LDS: FFT stage twiddles [N] | e^{+2 pi i k / N} [N] | w_rx [N + 64] | per wave: row [rowlen] + scratch [N]
-    v2f *tw = reinterpret_cast<v2f *>(smem);
-    v2f *wn = tw + N;
-    float *wrx = reinterpret_cast<float *>(wn + N);
-    v2f *rows = reinterpret_cast<v2f *>(wrx + N + 64);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int job = blockIdx.x, pair = job / p.n_ch, ch = job - pair * p.n_ch;
-    const int P = p.P, B = p.B;
-    fill_twiddles<N>(tw, tid, WAVES * 64);
-    for (int i = tid; i < N; i += WAVES * 64) {
-        float sv, cv;
-        sincospif(2.0f * (float)i / (float)N, &sv, &cv);
-        wn[i] = mk(cv, sv);
-    }
-    for (int i = tid; i < N + p.delta; i += WAVES * 64) wrx[i] = g_wrx[(size_t)pair * (N + p.delta) + i];
-    v2f *row = rows + (size_t)wv * (p.rowlen + N);
-    v2f *scr = row + p.rowlen;
-    for (int i = lane; i < p.rowlen; i += 64) row[i] = mk(0.f, 0.f);
-    __syncthreads();
-    const v2f *__restrict__ taps = reinterpret_cast<const v2f *>(g_h_) + (size_t)ch * LT;
-    const float *__restrict__ wtx = g_wtx + (size_t)pair * P;
-    float pw[BPL][4];
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pw[q][r] = 0.f;
-    const int h2 = p.delta >> 1;
-    for (int np = wv; np < N; np += WAVES) {
-        // x[c] = w_tx[c] e^{2 pi i ((c - mu) mod N) n' / N} / N at row[24 + c]  (tx matrix column, m:358-376)
-        for (int c = lane; c < P; c += 64) {
-            const int t = (c - p.mu) & (N - 1);
-            row[24 + c] = wn[(t * np) & (N - 1)] * (wtx[c] * (1.0f / (float)N));
-        }
-        for (int c = P + lane; c < 2 * B + 24; c += 64) row[24 + c] = mk(0.f, 0.f);
-        wave_sync();
-        // z = conv(h, x) over two symbol periods (m:260): lane -> RB2 consecutive outputs from j0
-        v2f acc[RB2];
-        const int j0 = lane * RB2;
-        fir_lane<RB2, interf_geo<N>::CH>(row + 24 - (LT - 1) + j0, taps, acc);
-        wave_sync();
-#pragma unroll
-        for (int r = 0; r < RB2; ++r)
-            if (j0 + r < 2 * B) row[24 + j0 + r] = acc[r];
-        wave_sync();
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            // Rx window, fold, circular shift (m:297-355) of period m, then the DFT
-            const v2f *fb = row + 24 + m * B;
-            v2f v[1][BPL][4];
-#pragma unroll
-            for (int q = 0; q < BPL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[0][q][r] = mk(0.f, 0.f);
-                    if (!(FULL || lane + 64 * q < NQ)) continue;
-                    const int m0 = (lane + 64 * q + r * NQ + p.kap + h2) & (N - 1);
-                    v2f z = fb[p.gam + m0] * wrx[m0];
-                    if (m0 < p.delta) {
-                        const float w2 = wrx[m0 + N];
-                        z = __builtin_elementwise_fma(mk(w2, w2), fb[p.gam + m0 + N], z);
-                    }
-                    v[0][q][r] = z;
-                }
-            fft_wave<N, -1, 1>(v, scr, 0, tw, lane);
-#pragma unroll
-            for (int q = 0; q < BPL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int n = lane + 64 * q + r * NQ;
-                    const float e = v[0][q][r].x * v[0][q][r].x + v[0][q][r].y * v[0][q][r].y;
-                    if (FULL || lane + 64 * q < NQ)
-                        pw[q][r] += (m == 0 && n == np) ? 0.f : e;    // the wanted term A_0[n, n] is no interference
-                }
-        }
-        wave_sync();
-    }
-    // sum over the waves (each wave's row is free now): float [WAVES][N] in the rows area
-    __syncthreads();
-    float *red = reinterpret_cast<float *>(rows);
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (FULL || lane + 64 * q < NQ) red[wv * N + lane + 64 * q + r * NQ] = pw[q][r];
-    __syncthreads();
-    for (int n = tid; n < N; n += WAVES * 64) {
-        float t = 0.f;
-        for (int w = 0; w < WAVES; ++w) t += red[w * N + n];
-        p.power[(size_t)job * N + n] = t;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Tx-side spectrum estimate: the transmitted waveform of a long run of symbols
-// and its averaged periodogram,
-//   wOFDMSystem.estimate_obr   python/ofdm_utils/timefreq_simulation.py:216-296 (Tx chain 242-258)
-//   psd_estimate               timefreq_simulation.py:101-123
-// The waveform kernel is phase A of the frame kernel fed with given symbols X[s][n] (any complex values,
-// zeros on unloaded bins): IDFT, CP/CS copy, Tx window, overlap-add of the `overlap` tail samples --
-// one wave per symbol, the overlapping samples by float atomics (two addends: order-independent).
-struct wofdm_wparams {
-    int P, mu, rho, overlap, no_symbols;
-    float2 *x;                         // [overlap + no_symbols * (P - overlap)], zeroed by the host
-};
-template <int N>
-__global__ void __launch_bounds__(1024) wofdm_txwave_kernel(const wofdm_wparams p, const float *__restrict__ g_wtx,
-                                                            const float2 *__restrict__ X)
-{
-    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ;
-    constexpr bool FULL = geo<N>::FULL;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    v2f *tw = reinterpret_cast<v2f *>(smem);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    v2f *scr = tw + N + (size_t)wv * N;
-    fill_twiddles<N>(tw, tid, 1024);
-    __syncthreads();
-    const int s = blockIdx.x * 16 + wv;
-    if (s >= p.no_symbols) return;
-    v2f v[1][BPL][4];
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            v[0][q][r] = mk(0.f, 0.f);
-            if (FULL || lane + 64 * q < NQ) v[0][q][r] = ldg2(X + (size_t)s * N + lane + 64 * q + r * NQ);
-        }
-    fft_wave<N, +1, 1>(v, scr, 0, tw, lane);                    // N x[t]
-    const int Bo = p.P - p.overlap;
-    float2 *out = p.x + (size_t)s * Bo;
-    auto put = [&](int i, v2f val) {
-        val = val * (g_wtx[i] * (1.0f / (float)N));
-        if (i < p.overlap || i >= Bo) {                          // shared with a neighbour symbol
-            atomicAdd(&out[i].x, val.x);
-            atomicAdd(&out[i].y, val.y);
-        } else {
-            out[i] = make_float2(val.x, val.y);
-        }
-    };
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (!(FULL || lane + 64 * q < NQ)) continue;
-            const int t = lane + 64 * q + r * NQ;
-            put(t + p.mu, v[0][q][r]);
-            if (t >= N - p.mu) put(t + p.mu - N, v[0][q][r]);
-            if (t < p.rho) put(t + p.mu + N, v[0][q][r]);
-        }
-}
-
-// Sum over consecutive FL-sample slices of x (the zero-padded remainder included) of |FFT_FL|^2, written
-// fftshift-ed; the caller divides by the reference's slice count.  FL = 2048 runs as two 1024-point
-// transforms of the even and odd samples and one radix-2 combination in registers.
-template <int FL>
-__global__ void __launch_bounds__(512) wofdm_psd_kernel(const float2 *__restrict__ x, int len, int n_slices,
-                                                        float *__restrict__ psd)
-{
-    constexpr int M = FL == 2048 ? 1024 : FL, H = FL / M;        // transform length, transforms per slice
-    constexpr int BPL = geo<M>::BPL, NQ = geo<M>::NQ, WAVES = 8;
-    static_assert(geo<M>::FULL, "at least 256 points");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    v2f *tw = reinterpret_cast<v2f *>(smem);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    v2f *scr = tw + M + (size_t)wv * M;
-    fill_twiddles<M>(tw, tid, WAVES * 64);
-    __syncthreads();
-    float acc[H][BPL][4];
-#pragma unroll
-    for (int h = 0; h < H; ++h)
-#pragma unroll
-        for (int q = 0; q < BPL; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[h][q][r] = 0.f;
-    for (int sl = wv; sl < n_slices; sl += WAVES) {
-        v2f e[1][BPL][4], o[1][BPL][4];
-#pragma unroll
-        for (int h = 0; h < H; ++h) {
-            v2f (&dst)[1][BPL][4] = h == 0 ? e : o;
-#pragma unroll
-            for (int q = 0; q < BPL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int idx = sl * FL + H * (lane + 64 * q + r * NQ) + h;       // even / odd samples
-                    dst[0][q][r] = idx < len ? ldg2(x + idx) : mk(0.f, 0.f);
-                }
-            fft_wave<M, -1, 1>(dst, scr, 0, tw, lane);
-        }
-#pragma unroll
-        for (int q = 0; q < BPL; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if constexpr (H == 2) {
-                    const int k = lane + 64 * q + r * NQ;
-                    float sv, cv;
-                    sincospif(-2.0f * (float)k / (float)FL, &sv, &cv);
-                    const v2f wo = cmul(o[0][q][r], mk(cv, sv));
-                    const v2f a = e[0][q][r] + wo, b = e[0][q][r] - wo;
-                    acc[0][q][r] += a.x * a.x + a.y * a.y;
-                    acc[1][q][r] += b.x * b.x + b.y * b.y;
-                } else {
-                    acc[0][q][r] += e[0][q][r].x * e[0][q][r].x + e[0][q][r].y * e[0][q][r].y;
-                }
-            }
-    }
-    __syncthreads();
-    float *red = reinterpret_cast<float *>(tw + M);                 // [WAVES][FL] over the scratch rows
-#pragma unroll
-    for (int h = 0; h < H; ++h)
-#pragma unroll
-        for (int q = 0; q < BPL; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[wv * FL + h * M + lane + 64 * q + r * NQ] = acc[h][q][r];
-    __syncthreads();
-    for (int k = tid; k < FL; k += WAVES * 64) {
-        float t = 0.f;
-        for (int w = 0; w < WAVES; ++w) t += red[w * FL + k];
-        psd[(k + FL / 2) & (FL - 1)] = t;
-    }
-}
-
-// The same two steps for a batch of jobs at every N (wofdm_tx_psd_batch).  The waveform kernel: grid (symbol groups,
-// jobs), one wave per symbol of the job's block, each job with its own cp, cs, overlap, window and waveform row; the
-// overlapping samples as above (two addends onto a zeroed row).  LDS: twiddles [N] + one scratch row [N] per wave
-// (N = 1024: 9 x 8 KB).
-template <int N> struct bwave_geo {
-    static constexpr int WAVES = N >= 512 ? 8 : 16;
-};
-template <int N>
-__global__ void __launch_bounds__(bwave_geo<N>::WAVES * 64)
-wofdm_txwave_batch_kernel(const wofdm_bjob *__restrict__ jobs, int no_symbols, const float *__restrict__ g_wtx,
-                          const float2 *__restrict__ X, float2 *__restrict__ x)
-{
-    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ, WAVES = bwave_geo<N>::WAVES;
-    constexpr bool FULL = geo<N>::FULL;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    v2f *tw = reinterpret_cast<v2f *>(smem);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    v2f *scr = tw + N + (size_t)wv * N;
-    fill_twiddles<N>(tw, tid, WAVES * 64);
-    __syncthreads();
-    const wofdm_bjob jb = jobs[blockIdx.y];
-    const int s = blockIdx.x * WAVES + wv;
-    if (s >= no_symbols) return;
-    const float2 *Xs = X + ((size_t)jb.block * no_symbols + s) * N;
-    v2f v[1][BPL][4];
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            v[0][q][r] = mk(0.f, 0.f);
-            if (FULL || lane + 64 * q < NQ) v[0][q][r] = ldg2(Xs + lane + 64 * q + r * NQ);
-        }
-    fft_wave<N, +1, 1>(v, scr, 0, tw, lane);                    // N x[t]
-    const int Bo = N + jb.cp + jb.cs - jb.overlap;
-    const float *wtx = g_wtx + jb.w_off;
-    float2 *out = x + jb.x_off + (size_t)s * Bo;
-    auto put = [&](int i, v2f val) {
-        val = val * (wtx[i] * (1.0f / (float)N));
-        if (i < jb.overlap || i >= Bo) {                         // shared with a neighbour symbol
-            atomicAdd(&out[i].x, val.x);
-            atomicAdd(&out[i].y, val.y);
-        } else {
-            out[i] = make_float2(val.x, val.y);
-        }
-    };
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (!(FULL || lane + 64 * q < NQ)) continue;
-            const int t = lane + 64 * q + r * NQ;
-            put(t + jb.cp, v[0][q][r]);
-            if (t >= N - jb.cp) put(t + jb.cp - N, v[0][q][r]);
-            if (t < jb.cs) put(t + jb.cp + N, v[0][q][r]);
-        }
-}
-
-// Periodogram of a batch: one workgroup (8 waves) per work item, i.e. up to wofdm_psd_batch_slices(N) consecutive
-// FL-sample slices of one job.  FL <= 1024 (R = 1): a wave transforms a whole slice, 8 slices at a time.  FL = 1024 R,
-// R = 2, 4, 8: the R waves of a group transform the decimated sub-sequences x[R m + h] of one slice (1024 points each,
-// E_h), put E_h into their scratch rows and, behind a barrier, combine them:  X[k' + 1024 c] = sum_h W_R^(h c)
-// (W_FL^(h k') E_h[k']).  Wave h of the group owns k' = h 1024 / R + lane + 64 j (j < 16 / R), i.e. 16 outputs per lane,
-// whose twiddles it keeps in registers; its loads of the R rows are consecutive 8-byte words across the lanes, as are the
-// stores of E_h (ds_read_b64 / ds_write_b64 without bank conflicts).  Every lane adds |X|^2 over its slices in a fixed
-// order, the groups' sums are added in group order, and the workgroup writes one unshifted partial spectrum [FL];
-// wofdm_psd_reduce_kernel adds a job's partials in item order -- no atomics: bitwise repeatable.
-template <int FL>
-__global__ void __launch_bounds__(512) wofdm_psd_batch_kernel(const wofdm_bjob *__restrict__ jobs,
-                                                              const wofdm_bitem *__restrict__ items,
-                                                              const float2 *__restrict__ x, float *__restrict__ partial)
-{
-    constexpr int R = wofdm_psd_batch_r(FL / 8), M = FL / R, G = 8 / R, ROUNDS = wofdm_psd_batch_slices(FL / 8) / G;
-    constexpr int BPL = geo<M>::BPL, NQ = geo<M>::NQ, JJ = M / (64 * R), NACC = R > 1 ? JJ * R : 4 * BPL;
-    static_assert(geo<M>::FULL && (R == 1 || M == 1024), "512- or 1024-point transforms");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    v2f *tw = reinterpret_cast<v2f *>(smem);
-    v2f *rows = tw + M;                                           // [8][M]: scratch of wave w = E_h of group w / R
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = wv / R, h = wv % R;
-    fill_twiddles<M>(tw, tid, 512);
-    const wofdm_bitem it = items[blockIdx.x];
-    const wofdm_bjob jb = jobs[it.job];
-    const float2 *xj = x + jb.x_off;
-    v2f cw[JJ][R > 1 ? R - 1 : 1];                                // W_FL^(t k'), t = 1 .. R-1
-    if constexpr (R > 1) {
-#pragma unroll
-        for (int j = 0; j < JJ; ++j)
-#pragma unroll
-            for (int t = 1; t < R; ++t) {
-                const int kp = h * (M / R) + lane + 64 * j;
-                float sv, cv;
-                sincospif(-2.0f * (float)(t * kp) / (float)FL, &sv, &cv);
-                cw[j][t - 1] = mk(cv, sv);
-            }
-    }
-    float acc[NACC];
-#pragma unroll
-    for (int a = 0; a < NACC; ++a) acc[a] = 0.f;
-    __syncthreads();
-    v2f *own = rows + (size_t)wv * M;
-    for (int rd = 0; rd < ROUNDS; ++rd) {
-        const int sl = rd * G + g;
-        const bool live = sl < it.n_slices;                       // uniform over the group
-        if (live) {
-            const int base = (it.slice0 + sl) * FL + h;
-            v2f v[1][BPL][4];
-#pragma unroll
-            for (int q = 0; q < BPL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int idx = base + R * (lane + 64 * q + r * NQ);
-                    v[0][q][r] = idx < jb.len ? ldg2(xj + idx) : mk(0.f, 0.f);
-                }
-            fft_wave<M, -1, 1>(v, own, 0, tw, lane);
-#pragma unroll
-            for (int q = 0; q < BPL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if constexpr (R == 1) acc[4 * q + r] += v[0][q][r].x * v[0][q][r].x + v[0][q][r].y * v[0][q][r].y;
-                    else own[lane + 64 * q + r * NQ] = v[0][q][r];
-                }
-        }
-        if constexpr (R > 1) {
-            __syncthreads();
-            if (live) {
-                const v2f *gs = rows + (size_t)g * R * M;
-#pragma unroll
-                for (int j = 0; j < JJ; ++j) {
-                    const int kp = h * (M / R) + lane + 64 * j;
-                    v2f y[R];
-#pragma unroll
-                    for (int t = 0; t < R; ++t) y[t] = gs[t * M + kp];
-#pragma unroll
-                    for (int t = 1; t < R; ++t) y[t] = cmul(y[t], cw[j][t - 1]);
-                    v2f X_[R];
-                    if constexpr (R == 2) {
-                        X_[0] = y[0] + y[1];
-                        X_[1] = y[0] - y[1];
-                    } else if constexpr (R == 4) {
-                        v2f u[4] = {y[0], y[1], y[2], y[3]};
-                        radix4<-1>(u);
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) X_[c] = u[c];
-                    } else {
-                        v2f u[2][4];                              // u[q][r] = y_t, t = q + 2 r
-#pragma unroll
-                        for (int t = 0; t < 8; ++t) u[t & 1][t >> 1] = y[t];
-                        dft8<-1>(u);                              // u[q][r] = X_c, c = r + 4 q
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) X_[c] = u[c >> 2][c & 3];
-                    }
-#pragma unroll
-                    for (int c = 0; c < R; ++c) acc[j * R + c] += X_[c].x * X_[c].x + X_[c].y * X_[c].y;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    float *red = reinterpret_cast<float *>(rows);                 // [G][FL] floats over the scratch rows
-    if constexpr (R == 1) {
-#pragma unroll
-        for (int q = 0; q < BPL; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[g * FL + lane + 64 * q + r * NQ] = acc[4 * q + r];
-    } else {
-#pragma unroll
-        for (int j = 0; j < JJ; ++j)
-#pragma unroll
-            for (int c = 0; c < R; ++c) red[g * FL + h * (M / R) + lane + 64 * j + M * c] = acc[j * R + c];
-    }
-    __syncthreads();
-    for (int k = tid; k < FL; k += 512) {
-        float t = 0.f;
-        for (int gg = 0; gg < G; ++gg) t += red[gg * FL + k];
-        partial[(size_t)blockIdx.x * FL + k] = t;
-    }
-}
-
-// psd[job][8 N] = sum over the job's work items, in item order, of their partial spectra; fftshift-ed
-template <int FL>
-__global__ void __launch_bounds__(256) wofdm_psd_reduce_kernel(const wofdm_bjob *__restrict__ jobs,
-                                                               const float *__restrict__ partial, float *__restrict__ psd)
-{
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= FL) return;
-    const wofdm_bjob jb = jobs[blockIdx.y];
-    float t = 0.f;
-    for (int i = 0; i < jb.n_items; ++i) t += partial[(size_t)(jb.item0 + i) * FL + k];
-    psd[(size_t)blockIdx.y * FL + ((k + FL / 2) & (FL - 1))] = t;
-}
-
-// Waveform step of a MASKED job (wofdm_tx_psd_batch_masked): per symbol the row r_s[P] of wofdm_txwave_batch_kernel
-// (IDFT, CP/CS copy, Tx window), then the spectral Tx mask of wofdm_plan_set_tx_mask as fast convolution over FL = 8 N
-// points (3 P - 2 <= FL):  y_s[i] = IFFT_FL( FFT_FL(r_s) . H )[i + P - 1], i < 2 P - 1, with H the transform of the mask's
-// impulse response laid out as in the frame kernel's TXFFT variant, 1 / FL folded in (host, fp64; stored in fp32).
-// The FL-point transforms are the R-way split of wofdm_psd_batch_kernel (R waves, M = FL / R points each) and its
-// transpose:  forward  X[k' + M c] = sum_h W_R^(h c) (W_FL^(h k') E_h[k']),  E_h = FFT_M(r[R m + h]);
-//             inverse  y[R m + h] = IFFT_M(F_h)[m],  F_h[k'] = W_FL^(-h k') sum_c W_R^(-h c) Z[k' + M c].
-// Wave h of a group owns k' = h M / R + lane + 64 j in the combination, takes all R bins k' + M c, multiplies them by H
-// and runs the inverse combination in registers -- the spectrum never leaves the workgroup.  8 waves = 8 / R symbols
-// per workgroup.  LDS: twiddles [M] (+ [N] where N != M) | rows [8][M] | symbol rows [8 / R][PMAX].
-// Output: the WHOLE y_s (2 P - 1 samples) by plain stores at Y + y_off + s (2 P - 1); the spill of symbol s onto s + 1
-// and the overlap-add are the gather of wofdm_txmask_ola_kernel -- no atomics, a fixed order of additions.
-template <int N> struct bmask_geo {
-    static constexpr int FL = 8 * N, R = wofdm_psd_batch_r(N), M = FL / R, G = 8 / R;
-    static constexpr int PMAX = wofdm_txmask_batch_pmax(N);
-    static constexpr int TWN = N == M ? 0 : N;                    // a twiddle table of its own for the N-point IDFT
-    static constexpr size_t LDS = 8 * (size_t)(M + TWN + 8 * M + G * PMAX);
-    static_assert(LDS <= 160 * 1024 && N <= M && 3 * PMAX - 2 <= FL, "LDS / transform length");
-};
-template <int N>
-__global__ void __launch_bounds__(512)
-wofdm_txmask_batch_kernel(const wofdm_bjob *__restrict__ jobs, const wofdm_mjob *__restrict__ mjobs, int no_symbols,
-                          const float *__restrict__ g_wtx, const float2 *__restrict__ X, const float2 *__restrict__ spec,
-                          float2 *__restrict__ Y)
-{
-    using MG = bmask_geo<N>;
-    constexpr int FL = MG::FL, R = MG::R, M = MG::M, G = MG::G, PMAX = MG::PMAX;
-    constexpr int BPL = geo<M>::BPL, NQ = geo<M>::NQ, JJ = M / (64 * R);
-    constexpr int BPLN = geo<N>::BPL, NQN = geo<N>::NQ;
-    constexpr bool FULLN = geo<N>::FULL;
-    static_assert(geo<M>::FULL, "512- or 1024-point transforms");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    v2f *twm = reinterpret_cast<v2f *>(smem);
-    v2f *twn = N == M ? twm : twm + M;
-    v2f *rows = twm + M + MG::TWN;                                // [8][M]
-    v2f *srows = rows + 8 * M;                                    // [G][PMAX]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = wv / R, h = wv % R;
-    fill_twiddles<M>(twm, tid, 512);
-    if constexpr (N != M) fill_twiddles<N>(twn, tid, 512);
-    const wofdm_mjob mj = mjobs[blockIdx.y];
-    const wofdm_bjob jb = jobs[mj.job];
-    const int P = N + jb.cp + jb.cs, L = 2 * P - 1;
-    const int s = blockIdx.x * G + g;
-    const bool live = s < no_symbols;                             // uniform over the group
-    v2f cw[JJ][R > 1 ? R - 1 : 1];                                // W_FL^(t k'), t = 1 .. R-1
-    if constexpr (R > 1) {
-#pragma unroll
-        for (int j = 0; j < JJ; ++j)
-#pragma unroll
-            for (int t = 1; t < R; ++t) {
-                const int kp = h * (M / R) + lane + 64 * j;
-                float sv, cv;
-                sincospif(-2.0f * (float)(t * kp) / (float)FL, &sv, &cv);
-                cw[j][t - 1] = mk(cv, sv);
-            }
-    }
-    __syncthreads();
-    v2f *own = rows + (size_t)wv * M;
-    v2f *srow = srows + (size_t)g * PMAX;
-    if (live && h == 0) {                                         // r_s: as wofdm_txwave_batch_kernel, into LDS
-        const float2 *Xs = X + ((size_t)jb.block * no_symbols + s) * N;
-        v2f v[1][BPLN][4];
-#pragma unroll
-        for (int q = 0; q < BPLN; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[0][q][r] = mk(0.f, 0.f);
-                if (FULLN || lane + 64 * q < NQN) v[0][q][r] = ldg2(Xs + lane + 64 * q + r * NQN);
-            }
-        fft_wave<N, +1, 1>(v, own, 0, twn, lane);                 // N x[t]
-        const float *wtx = g_wtx + jb.w_off;
-        auto put = [&](int i, v2f val) { srow[i] = val * (wtx[i] * (1.0f / (float)N)); };
-#pragma unroll
-        for (int q = 0; q < BPLN; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (!(FULLN || lane + 64 * q < NQN)) continue;
-                const int t = lane + 64 * q + r * NQN;
-                put(t + jb.cp, v[0][q][r]);
-                if (t >= N - jb.cp) put(t + jb.cp - N, v[0][q][r]);
-                if (t < jb.cs) put(t + jb.cp + N, v[0][q][r]);
-            }
-    }
-    __syncthreads();
-    v2f v[1][BPL][4];
-    if (live) {
-#pragma unroll
-        for (int q = 0; q < BPL; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int idx = R * (lane + 64 * q + r * NQ) + h;
-                v[0][q][r] = idx < P ? srow[idx] : mk(0.f, 0.f);
-            }
-        fft_wave<M, -1, 1>(v, own, 0, twm, lane);
-        if constexpr (R == 1) {
-            const float2 *H = spec + (size_t)mj.spec * FL;
-#pragma unroll
-            for (int q = 0; q < BPL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[0][q][r] = cmul(v[0][q][r], ldg2(H + lane + 64 * q + r * NQ));
-        } else {
-#pragma unroll
-            for (int q = 0; q < BPL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) own[lane + 64 * q + r * NQ] = v[0][q][r];
-        }
-    }
-    if constexpr (R > 1) {
-        __syncthreads();
-        v2f F[JJ][R];                                             // F_t[k'] of this wave's k', t < R
-        if (live) {
-            const v2f *gs = rows + (size_t)g * R * M;
-            const float2 *H = spec + (size_t)mj.spec * FL;
-#pragma unroll
-            for (int j = 0; j < JJ; ++j) {
-                const int kp = h * (M / R) + lane + 64 * j;
-                v2f y[R];
-#pragma unroll
-                for (int t = 0; t < R; ++t) y[t] = gs[t * M + kp];
-#pragma unroll
-                for (int t = 1; t < R; ++t) y[t] = cmul(y[t], cw[j][t - 1]);
-                if constexpr (R == 2) {
-                    const v2f z0 = cmul(y[0] + y[1], ldg2(H + kp)), z1 = cmul(y[0] - y[1], ldg2(H + kp + M));
-                    F[j][0] = z0 + z1;
-                    F[j][1] = z0 - z1;
-                } else if constexpr (R == 4) {
-                    v2f u[4] = {y[0], y[1], y[2], y[3]};
-                    radix4<-1>(u);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) u[c] = cmul(u[c], ldg2(H + kp + M * c));
-                    radix4<+1>(u);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) F[j][t] = u[t];
-                } else {
-                    v2f u[2][4], w[2][4];                         // u[q][r] = y_t, t = q + 2 r
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) u[t & 1][t >> 1] = y[t];
-                    dft8<-1>(u);                                  // u[q][r] = X_c, c = r + 4 q
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) w[c & 1][c >> 1] = cmul(u[c >> 2][c & 3], ldg2(H + kp + M * c));
-                    dft8<+1>(w);                                  // w[q][r] = F_t, t = r + 4 q
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) F[j][t] = w[t >> 2][t & 3];
-                }
-#pragma unroll
-                for (int t = 1; t < R; ++t) F[j][t] = cmul_conj(F[j][t], cw[j][t - 1]);
-            }
-        }
-        __syncthreads();                                          // every wave has read the E rows
-        if (live) {
-            v2f *gs = rows + (size_t)g * R * M;
-#pragma unroll
-            for (int j = 0; j < JJ; ++j)
-#pragma unroll
-                for (int t = 0; t < R; ++t) gs[t * M + h * (M / R) + lane + 64 * j] = F[j][t];
-        }
-        __syncthreads();
-        if (live) {
-#pragma unroll
-            for (int q = 0; q < BPL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[0][q][r] = own[lane + 64 * q + r * NQ];
-        }
-    }
-    if (!live) return;
-    fft_wave<M, +1, 1>(v, own, 0, twm, lane);                     // y[R m + h + (P - 1)], the 1 / FL sits in H
-    float2 *out = Y + mj.y_off + (size_t)s * L;
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = R * (lane + 64 * q + r * NQ) + h - (P - 1);
-            if (i >= 0 && i < L) out[i] = make_float2(v[0][q][r].x, v[0][q][r].y);
-        }
-}
-
-// Filtered rows and overlap-add of a masked job, as a gather in a fixed order (no atomics):
-//   row_s[i] = y_s[i] + y_{s-1}[P + i] (i < P - 1, s > 0),  row_s[P - 1] = y_s[P - 1]
-//   x[s (P - overlap) + i] = row_s[i] (s < S) + row_{s-1}[i + P - overlap] (s > 0, i < overlap)
-template <int N>
-__global__ void __launch_bounds__(256)
-wofdm_txmask_ola_kernel(const wofdm_bjob *__restrict__ jobs, const wofdm_mjob *__restrict__ mjobs, int no_symbols,
-                        const float2 *__restrict__ Y, float2 *__restrict__ x)
-{
-    const wofdm_mjob mj = mjobs[blockIdx.y];
-    const wofdm_bjob jb = jobs[mj.job];
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= jb.len) return;
-    const int P = N + jb.cp + jb.cs, L = 2 * P - 1, Bo = P - jb.overlap;
-    const float2 *y = Y + mj.y_off;
-    auto row = [&](int ss, int i) {
-        v2f a = ldg2(y + (size_t)ss * L + i);
-        if (ss > 0 && i < P - 1) a = a + ldg2(y + (size_t)(ss - 1) * L + P + i);
-        return a;
-    };
-    const int s = n / Bo, i = n - s * Bo;
-    v2f val = mk(0.f, 0.f);
-    if (s < no_symbols) val = row(s, i);
-    if (s > 0 && i < jb.overlap) val = s < no_symbols ? val + row(s - 1, i + Bo) : row(s - 1, i + Bo);
-    x[jb.x_off + n] = make_float2(val.x, val.y);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Closed-form ICI + ISI power of the half-band, spectrally masked system (wofdm_interference_masked):
-//   zero padding + ifftshift  matlab/main_channel_mask.m:387-390
-//   dft_rc_filt               matlab/main_channel_mask.m:398-417
-//   calculate_interference    matlab/main_interference_calculation.m:177-225
-// The mask turns the Tx column of bin n' into y = g (*) x (circular, length 2P - 1, g = the mask's impulse response);
-// y[0, P) stays in the symbol's row and y[P, 2P - 1) goes into the next one, B samples later, so the on-air pulse is
-//   u[j] = [j < P] y[j] + [B <= j < B + P - 1] y[P + j - B],   j < J = B + P - 1,
-// and with the channel it covers three symbol periods: A_m, m = 0, 1, 2 (J + L - 1 <= 3 B for every supported
-// geometry: tail_tx + L - 2 <= 35 < 64 <= B).
-//
-// Stage 1, once per window pair (the pulses do not depend on the channel): u is linear in x[c] = w_tx[c]
-// e^{2 pi i ((c - mu) mod N) n' / N} / N, so for a fixed j the pulses of ALL bins are one N-point inverse DFT,
-//   u[j][n'] = 1/N sum_t q_j[t] e^{2 pi i t n' / N},   q_j[t] = sum_{c < P, c = t + mu (mod N)} G[j][c] w_tx[c],
-//   G[j][c] = [j < P] g[(j - c) mod (2P - 1)] + [B <= j < B + P - 1] g[j - B + P - c]
-// -- a wave per sample j: it folds row j of G onto the N points and transforms; O(J (P + N log N)) per pair instead
-// of O(J P N).  No mask (g == nullptr): u[j][n'] = x[j] itself, from the exponential table as wofdm_interf_kernel
-// forms it.  cols[pair][n'][JP] holds the pulses, a row per bin; rows of unloaded bins are not written (nor read).
-struct wofdm_mparams {
-    int P, B, mu, delta, gam, kap, n_ch, J, JP;    // J = B + P - 1 pulse samples, JP = row pitch of cols
-    float *power, *wanted;                         // [pairs][n_ch][N]; wanted may be null
-};
-template <int N> struct interfm_geo {
-    // (the waves of wofdm_interf_kernel: the same columns per wave and the same order of the sums, so that without mask and
-    // allocation the power comes out bit for bit as there)
-    static constexpr int WAVES = interf_geo<N>::WAVES;
-    static constexpr int RB3 = 3 * (N / 64 + 1);                      // FIR outputs per lane over 3B <= 3N + 192 samples
-    static constexpr int CH = RB3 <= 6 ? RB3 : (RB3 % 5 == 0 ? 5 : 6);
-    // 24 zeros (>= LT - 1 of history) + 64 RB3 samples: the last lane's FIR window ends at 64 RB3 + 23
-    static constexpr int ROWLEN = 24 + 64 * RB3;
-    // FFT stage twiddles [N] | w_rx [N + 64] | per wave: row [ROWLEN] + scratch [N]
-    static constexpr int LDS = 8 * N + 4 * (N + 64) + WAVES * 8 * (ROWLEN + N);
-    static_assert(LDS <= 160 * 1024 && WAVES * N * 4 <= WAVES * 8 * (ROWLEN + N), "LDS");
-    static constexpr int PWAVES = N >= 512 ? 8 : 16;                  // pulse kernel: twiddles + e^{..} table + scratch rows
-    static constexpr int PLDS = 8 * N * (2 + PWAVES);
-};
-
-template <int N>
-__global__ void __launch_bounds__(interfm_geo<N>::PWAVES * 64)
-wofdm_interf_pulse_kernel(const wofdm_mparams p, const float *__restrict__ g_wtx, const float2 *__restrict__ g,
-                          const uint8_t *__restrict__ amask, float2 *__restrict__ cols)
-{
-    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ, WAVES = interfm_geo<N>::PWAVES;
-    constexpr bool FULL = geo<N>::FULL;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    v2f *tw = reinterpret_cast<v2f *>(smem);
-    v2f *wn = tw + N;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    v2f *scr = wn + N + (size_t)wv * N;
-    fill_twiddles<N>(tw, tid, WAVES * 64);
-    for (int i = tid; i < N; i += WAVES * 64) {
-        float sv, cv;
-        sincospif(2.0f * (float)i / (float)N, &sv, &cv);
-        wn[i] = mk(cv, sv);
-    }
-    __syncthreads();
-    const int pair = blockIdx.y, j = blockIdx.x * WAVES + wv;
-    const int P = p.P, B = p.B, L = 2 * P - 1;
-    if (j >= p.J) return;
-    const float *__restrict__ wtx = g_wtx + (size_t)pair * P;
-    v2f v[1][BPL][4];
-    if (g == nullptr) {
-        // u[j][n'] = x[j] = w_tx[j] e^{2 pi i ((j - mu) mod N) n' / N} / N (j < P), as wofdm_interf_kernel's Tx column
-        const int t = (j - p.mu) & (N - 1);
-        const float w = j < P ? wtx[j] * (1.0f / (float)N) : 0.f;
-#pragma unroll
-        for (int q = 0; q < BPL; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[0][q][r] = wn[(t * (lane + 64 * q + r * NQ)) & (N - 1)] * w;
-    } else {
-        const bool own = j < P, spill = j >= B;                  // (j < J = B + P - 1 here)
-#pragma unroll
-        for (int q = 0; q < BPL; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v2f a = mk(0.f, 0.f);
-                if (FULL || lane + 64 * q < NQ) {
-                    for (int c = (lane + 64 * q + r * NQ + p.mu) & (N - 1); c < P; c += N) {
-                        v2f gg = mk(0.f, 0.f);
-                        if (own) {
-                            const int i = j - c;
-                            gg = ldg2(g + (i < 0 ? i + L : i));
-                        }
-                        if (spill) gg = gg + ldg2(g + (j - B + P - c));     // in [1, 2P - 2]
-                        a = a + gg * wtx[c];
-                    }
-                }
-                v[0][q][r] = a;
-            }
-        fft_wave<N, +1, 1>(v, scr, 0, tw, lane);                 // N u[j][n']
-#pragma unroll
-        for (int q = 0; q < BPL; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[0][q][r] = v[0][q][r] * (1.0f / (float)N);
-    }
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int np = lane + 64 * q + r * NQ;
-            if (!(FULL || lane + 64 * q < NQ) || (amask != nullptr && amask[np] == 0)) continue;
-            cols[((size_t)pair * N + np) * p.JP + j] = make_float2(v[0][q][r].x, v[0][q][r].y);
-        }
-}
-
-// Stage 2, one workgroup per (window pair, channel): wofdm_interf_kernel's pattern over the pulses of stage 1 -- FIR over
-// three periods, per period Rx window / fold / shift + DFT, |.|^2 row sums in registers -- with the wanted term
-// |A_0[n, n]|^2 kept apart and written out, the columns of unloaded bins skipped and the rows of unloaded bins zero.
-template <int N>
-__global__ void __launch_bounds__(interfm_geo<N>::WAVES * 64)
-wofdm_interf_masked_kernel(const wofdm_mparams p, const float *__restrict__ g_wrx, const float2 *__restrict__ g_h_,
-                           const uint8_t *__restrict__ amask, const float2 *__restrict__ cols)
-{
-    constexpr int WAVES = interfm_geo<N>::WAVES, RB3 = interfm_geo<N>::RB3, ROWLEN = interfm_geo<N>::ROWLEN, LT = WOFDM_LT;
-    constexpr int BPL = geo<N>::BPL, NQ = geo<N>::NQ;
-    constexpr bool FULL = geo<N>::FULL;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    v2f *tw = reinterpret_cast<v2f *>(smem);
-    float *wrx = reinterpret_cast<float *>(tw + N);
-    v2f *rows = reinterpret_cast<v2f *>(wrx + N + 64);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int job = blockIdx.x, pair = job / p.n_ch, ch = job - pair * p.n_ch;
-    const int B = p.B;
-    fill_twiddles<N>(tw, tid, WAVES * 64);
-    for (int i = tid; i < N + p.delta; i += WAVES * 64) wrx[i] = g_wrx[(size_t)pair * (N + p.delta) + i];
-    v2f *row = rows + (size_t)wv * (ROWLEN + N);
-    v2f *scr = row + ROWLEN;
-    for (int i = lane; i < ROWLEN; i += 64) row[i] = mk(0.f, 0.f);
-    __syncthreads();
-    const v2f *__restrict__ taps = reinterpret_cast<const v2f *>(g_h_) + (size_t)ch * LT;
-    float pw[BPL][4], ww[BPL][4];
-#pragma unroll
-    for (int q = 0; q < BPL; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pw[q][r] = ww[q][r] = 0.f;
-    const int h2 = p.delta >> 1;
-    for (int np = wv; np < N; np += WAVES) {
-        if (amask != nullptr && amask[np] == 0) continue;          // (wave-uniform) an unloaded bin transmits nothing
-        const float2 *__restrict__ col = cols + ((size_t)pair * N + np) * p.JP;
-        for (int j = lane; j < p.J; j += 64) row[24 + j] = ldg2(col + j);
-        for (int j = p.J + lane; j < ROWLEN - 24; j += 64) row[24 + j] = mk(0.f, 0.f);
-        wave_sync();
-        // z = conv(h, u) over three symbol periods: lane -> RB3 consecutive outputs from j0
-        v2f acc[RB3];
-        const int j0 = lane * RB3;
-        fir_lane<RB3, interfm_geo<N>::CH>(row + 24 - (LT - 1) + j0, taps, acc);
-        wave_sync();
-#pragma unroll
-        for (int r = 0; r < RB3; ++r)
-            if (j0 + r < 3 * B) row[24 + j0 + r] = acc[r];
-        wave_sync();
-#pragma unroll
-        for (int m = 0; m < 3; ++m) {
-            // Rx window, fold, circular shift (m:297-355) of period m, then the DFT
-            const v2f *fb = row + 24 + m * B;
-            v2f v[1][BPL][4];
-#pragma unroll
-            for (int q = 0; q < BPL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[0][q][r] = mk(0.f, 0.f);
-                    if (!(FULL || lane + 64 * q < NQ)) continue;
-                    const int m0 = (lane + 64 * q + r * NQ + p.kap + h2) & (N - 1);
-                    v2f z = fb[p.gam + m0] * wrx[m0];
-                    if (m0 < p.delta) {
-                        const float w2 = wrx[m0 + N];
-                        z = __builtin_elementwise_fma(mk(w2, w2), fb[p.gam + m0 + N], z);
-                    }
-                    v[0][q][r] = z;
-                }
-            fft_wave<N, -1, 1>(v, scr, 0, tw, lane);
-#pragma unroll
-            for (int q = 0; q < BPL; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int n = lane + 64 * q + r * NQ;
-                    const float e = v[0][q][r].x * v[0][q][r].x + v[0][q][r].y * v[0][q][r].y;
-                    if (!(FULL || lane + 64 * q < NQ)) continue;
-                    if (m == 0 && n == np) ww[q][r] += e;          // the wanted term A_0[n, n]
-                    else pw[q][r] += e;
-                }
-        }
-        wave_sync();
-    }
-    // sums over the waves in wave order (each wave's row is free now): float [WAVES][N] in the rows area, power then wanted
-    float *red = reinterpret_cast<float *>(rows);
-    for (int pass = 0; pass < 2; ++pass) {
-        float *dst = pass == 0 ? p.power : p.wanted;
-        if (dst == nullptr) break;
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < BPL; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (FULL || lane + 64 * q < NQ) red[wv * N + lane + 64 * q + r * NQ] = pass == 0 ? pw[q][r] : ww[q][r];
-        __syncthreads();
-        for (int n = tid; n < N; n += WAVES * 64) {
-            float t = 0.f;
-            for (int w = 0; w < WAVES; ++w) t += red[w * N + n];
-            dst[(size_t)job * N + n] = (amask != nullptr && amask[n] == 0) ? 0.f : t;
-        }
-    }
-}
-
-__global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
-{
-    if (threadIdx.x == 0) {
-        const philox_out o = philox4x32_10(ck[0], ck[1], ck[2], ck[3], ck[4], ck[5]);
-        for (int i = 0; i < 4; ++i) out[i] = o.w[i];
-    }
-}
-
 template <int N, int K, int LAY, int VAR> wofdm_kernel_fn pick_mode(int mode)
 {
     if constexpr (wofdm_layout_built(LAY, N, VAR)) {
@@ -4801,167 +3499,26 @@ wofdm_kernel_fn pick_layout(int layout, int mode, int var, std::integer_sequence
     return fn;
 }
 
-#if WOFDM_TU_K != 0
 template <int N> wofdm_kernel_fn pick(int k, int layout, int mode, int var)
 {
     // (one constellation size per translation unit, see below)
     if (k != WOFDM_TU_K) return nullptr;
     return pick_layout<N, WOFDM_TU_K>(layout, mode, var, std::make_integer_sequence<int, WOFDM_LAYOUT_COUNT>{});
 }
-#endif
 
 }  // namespace
 
 // This file is compiled once per (DFT length, bits per subcarrier) (-DWOFDM_TU_N=<N>
 // -DWOFDM_TU_K=<k>, see the Makefile) so that the kernel family builds in parallel;
-// wofdm_kernel.h dispatches on n_fft and bits_per_sc.  -DWOFDM_TU_K=0: no frame kernel, only the waveform kernels of
-// wofdm_tx_psd_batch_masked for this DFT length -- units of their own, so that the frame kernels' units hold exactly
-// the functions they held before (their register allocation answers to what else is compiled beside them).
+// wofdm_kernel.h dispatches on n_fft and bits_per_sc.  Nothing but the frame kernel is compiled here (its register allocation
+// answers to what else is compiled beside it): the auxiliary kernels have units of their own, wofdm_aux.hip.
 #if !defined(WOFDM_TU_N) || !defined(WOFDM_TU_K)
-#error "compile with -DWOFDM_TU_N=<64|128|256|512|1024> -DWOFDM_TU_K=<2|4|6|0>"
+#error "compile with -DWOFDM_TU_N=<64|128|256|512|1024> -DWOFDM_TU_K=<2|4|6>"
 #endif
 #define WOFDM_CAT2(a, b) a##b
 #define WOFDM_CAT(a, b) WOFDM_CAT2(a, b)
 
-#if WOFDM_TU_K != 0
 wofdm_kernel_fn WOFDM_CAT(WOFDM_CAT(WOFDM_CAT(wofdm_select_kernel_n, WOFDM_TU_N), _k), WOFDM_TU_K)(int layout, int mode, int var)
 {
     return pick<WOFDM_TU_N>(WOFDM_TU_K, layout, mode, var);
 }
-#endif
-
-#if WOFDM_TU_K == 2
-// one interference kernel per DFT length, compiled in the k = 2 translation units
-hipError_t WOFDM_CAT(wofdm_interf_launch_n, WOFDM_TU_N)(int jobs, int P, int B, int mu, int delta, int gam, int kap,
-                                                        int n_ch, const float *wtx, const float *wrx, const float2 *h,
-                                                        float *power, hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N, W = interf_geo<N>::WAVES;
-    wofdm_iparams ip;
-    ip.P = P; ip.B = B; ip.mu = mu; ip.delta = delta; ip.gam = gam; ip.kap = kap; ip.n_ch = n_ch;
-    ip.rowlen = (24 + 2 * B + 24 + 64 * interf_geo<N>::RB2 - 2 * B + 1) / 2 * 2;   // covers every lane's FIR window
-    ip.power = power;
-    const size_t lds = 8 * (size_t)N * 2 + 4 * (size_t)(N + 64) + (size_t)W * 8 * (ip.rowlen + N);
-    if (lds > 160u * 1024u) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_interf_kernel<N>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_interf_kernel<N>, dim3(jobs), dim3(W * 64), lds, s, ip, wtx, wrx, h);
-    return hipGetLastError();
-}
-#endif
-
-#if WOFDM_TU_K == 2 && WOFDM_TU_N <= 256
-// Tx waveform + periodogram (row f4), per DFT length, in the k = 2 translation units
-hipError_t WOFDM_CAT(wofdm_psd_launch_n, WOFDM_TU_N)(int P, int mu, int rho, int overlap, int no_symbols, const float *wtx,
-                                                     const float2 *X, float2 *x, int len, float *psd, hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N, FL = 8 * N, M = FL == 2048 ? 1024 : FL;
-    wofdm_wparams wp;
-    wp.P = P; wp.mu = mu; wp.rho = rho; wp.overlap = overlap; wp.no_symbols = no_symbols; wp.x = x;
-    const size_t lds_a = 8 * (size_t)N * 17, lds_b = 8 * (size_t)M * 9;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_psd_kernel<FL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_txwave_kernel<N>, dim3((no_symbols + 15) / 16), dim3(1024), lds_a, s, wp, wtx, X);
-    hipLaunchKernelGGL(wofdm_psd_kernel<FL>, dim3(1), dim3(512), lds_b, s, (const float2 *)x, len, (len + FL - 1) / FL, psd);
-    return hipGetLastError();
-}
-#endif
-
-#if WOFDM_TU_K == 2
-// the same for a batch of jobs (wofdm_tx_psd_batch), every DFT length, in the k = 2 translation units; x zeroed by the
-// caller, partial [n_items][8 N]
-hipError_t WOFDM_CAT(wofdm_psd_batch_launch_n, WOFDM_TU_N)(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs,
-                                                           const wofdm_bitem *items, const float *wtx, const float2 *X,
-                                                           float2 *x, float *partial, float *psd, hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N, FL = 8 * N, M = FL / wofdm_psd_batch_r(N), WW = bwave_geo<N>::WAVES;
-    const size_t lds_a = 8 * (size_t)N * (1 + WW), lds_b = 8 * (size_t)M * 9;
-    static_assert(8 * N * (1 + WW) <= 160 * 1024 && 8 * M * 9 <= 160 * 1024, "LDS");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txwave_batch_kernel<N>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_psd_batch_kernel<FL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_txwave_batch_kernel<N>, dim3((no_symbols + WW - 1) / WW, n_jobs), dim3(WW * 64), lds_a, s, jobs,
-                       no_symbols, wtx, X, x);
-    hipLaunchKernelGGL(wofdm_psd_batch_kernel<FL>, dim3(n_items), dim3(512), lds_b, s, jobs, items, (const float2 *)x, partial);
-    hipLaunchKernelGGL(wofdm_psd_reduce_kernel<FL>, dim3((FL + 255) / 256, n_jobs), dim3(256), 0, s, jobs,
-                       (const float *)partial, psd);
-    return hipGetLastError();
-}
-#endif
-
-#if WOFDM_TU_K == 0
-// wofdm_tx_psd_batch_masked: the unmasked jobs' waveforms by wofdm_txwave_batch_kernel, the masked ones by the fast-convolution
-// kernel and its gather, then periodogram and reduction of all jobs as in wofdm_psd_batch_launch; the -DWOFDM_TU_K=0 units
-hipError_t WOFDM_CAT(wofdm_psd_batch_masked_launch_n, WOFDM_TU_N)(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs,
-                                                                  const wofdm_bitem *items, int n_plain, const wofdm_bjob *plain_jobs,
-                                                                  int n_masked, const wofdm_mjob *mjobs, int max_len,
-                                                                  const float2 *spec, float2 *Y, const float *wtx, const float2 *X,
-                                                                  float2 *x, float *partial, float *psd, hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N, FL = 8 * N, M = FL / wofdm_psd_batch_r(N), WW = bwave_geo<N>::WAVES, G = bmask_geo<N>::G;
-    const size_t lds_a = 8 * (size_t)N * (1 + WW), lds_b = 8 * (size_t)M * 9, lds_m = bmask_geo<N>::LDS;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txwave_batch_kernel<N>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_psd_batch_kernel<FL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txmask_batch_kernel<N>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
-    if (e != hipSuccess) return e;
-    if (n_plain > 0)
-        hipLaunchKernelGGL(wofdm_txwave_batch_kernel<N>, dim3((no_symbols + WW - 1) / WW, n_plain), dim3(WW * 64), lds_a, s,
-                           plain_jobs, no_symbols, wtx, X, x);
-    if (n_masked > 0) {
-        hipLaunchKernelGGL(wofdm_txmask_batch_kernel<N>, dim3((no_symbols + G - 1) / G, n_masked), dim3(512), lds_m, s, jobs,
-                           mjobs, no_symbols, wtx, X, spec, Y);
-        hipLaunchKernelGGL(wofdm_txmask_ola_kernel<N>, dim3((max_len + 255) / 256, n_masked), dim3(256), 0, s, jobs, mjobs,
-                           no_symbols, (const float2 *)Y, x);
-    }
-    hipLaunchKernelGGL(wofdm_psd_batch_kernel<FL>, dim3(n_items), dim3(512), lds_b, s, jobs, items, (const float2 *)x, partial);
-    hipLaunchKernelGGL(wofdm_psd_reduce_kernel<FL>, dim3((FL + 255) / 256, n_jobs), dim3(256), 0, s, jobs,
-                       (const float *)partial, psd);
-    return hipGetLastError();
-}
-#endif
-
-#if WOFDM_TU_K == 0
-// wofdm_interference_masked: the pulses of every pair, then the (pair, channel) jobs; the -DWOFDM_TU_K=0 units
-hipError_t WOFDM_CAT(wofdm_interf_masked_launch_n, WOFDM_TU_N)(int pairs, int n_ch, int P, int B, int mu, int delta, int gam,
-                                                               int kap, int JP, const float *wtx, const float *wrx,
-                                                               const float2 *h, const float2 *g, const uint8_t *amask,
-                                                               float2 *cols, float *power, float *wanted, hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N, W = interfm_geo<N>::WAVES, PW = interfm_geo<N>::PWAVES;
-    wofdm_mparams mp;
-    mp.P = P; mp.B = B; mp.mu = mu; mp.delta = delta; mp.gam = gam; mp.kap = kap; mp.n_ch = n_ch;
-    mp.J = B + P - 1; mp.JP = JP;
-    mp.power = power; mp.wanted = wanted;
-    // the row of a wave holds three periods: 3 B <= 64 RB3, and the pulse with the channel ends within them
-    if (3 * B > 64 * interfm_geo<N>::RB3 || mp.J + WOFDM_LT - 1 > 3 * B || JP < mp.J || delta > 64) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_interf_pulse_kernel<N>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, interfm_geo<N>::PLDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_interf_masked_kernel<N>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, interfm_geo<N>::LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_interf_pulse_kernel<N>, dim3((mp.J + PW - 1) / PW, pairs), dim3(PW * 64), interfm_geo<N>::PLDS, s,
-                       mp, wtx, g, amask, cols);
-    hipLaunchKernelGGL(wofdm_interf_masked_kernel<N>, dim3(pairs * n_ch), dim3(W * 64), interfm_geo<N>::LDS, s, mp, wrx, h,
-                       amask, (const float2 *)cols);
-    return hipGetLastError();
-}
-#endif
-
-#if WOFDM_TU_N == 64 && WOFDM_TU_K == 2
-hipError_t wofdm_philox_kat_launch(const uint32_t *ctr_key_dev, uint32_t *out_dev, hipStream_t s)
-{
-    hipLaunchKernelGGL(philox_kat_kernel, dim3(1), dim3(64), 0, s, ctr_key_dev, out_dev);
-    return hipGetLastError();
-}
-#endif
