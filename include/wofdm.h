@@ -67,6 +67,11 @@ typedef struct wofdm_cfg {
     uint64_t frames_per_cell;  /* frames [frame_offset, frame_offset+frames_per_cell)       */
     uint64_t frame_offset;     /*   of every cell (global frame index keys the RNG)         */
     uint64_t seed;
+    /* All 64 bits of seed and of the global frame index frame_offset + f key the random streams (csrc/philox.h: key =
+     * (seed lo, seed hi), counter = (block, frame lo, frame hi, stream << 28 | cell)): two seeds, or two frame ranges, that
+     * differ in any bit are independent experiments, and frame_offset + frames_per_cell may cross 2^32.  The cell index
+     * shares its counter word with the stream id, so n_channels * n_snr * n_window_pairs must stay below 2^28
+     * (WOFDM_E_UNSUPPORTED otherwise). */
 } wofdm_cfg;
 
 /* Optional stage dump of ONE frame (host float buffers, complex = interleaved re,im;
