@@ -292,6 +292,52 @@ int wofdm_tx_psd_batch_masked(int32_t n_fft, int device, int32_t n_jobs, const w
                               const float *mask_gain, const int32_t *job_mask,
                               int32_t n_blocks, int32_t no_symbols, const float *X, float *psd);
 
+/* Peak-to-average power ratio (PAPR) of the on-air frames, per symbol period, as a histogram -- for exactly the frames the
+ * BER loop transmits.  The reference has no PAPR figure: this entry point replaces no line of it; it completes the
+ * window / Tx-mask study beside the BER, interference and spectrum entry points above.
+ *   Frames: window pair p transmits the frames [frame_offset, frame_offset + frames_per_cell) of cell = p as a plan with
+ * n_snr = n_channels = 1 draws them (label stream of philox.h, all 64 bits of seed and of the frame index; MATLAB Gray QAM at
+ * bits_per_sc bits; symbol 0, the pilot, is an ordinary random symbol), with the allocation active[n_fft] (semantics of
+ * wofdm_plan_set_allocation; NULL = every bin loaded) and the spectral Tx mask tx_mask[2P-1] (semantics of
+ * wofdm_plan_set_tx_mask: no spill into symbol 0, the last symbol's spill dropped; NULL = no mask): IDFT, CP/CS copy, Tx
+ * window w_tx[pairs][P], mask, overlap-add of the tail_tx tail samples -- tx[tail_tx + S B], B = P - tail_tx.
+ *   Periods: symbol period s = 0 .. S-1 is tx[s B, (s + 1) B); the trailing tail_tx samples (the last symbol's ramp-down)
+ * belong to no period.  peak = max |tx|^2 and energy = sum |tx|^2 over the period, PAPR = B peak / energy (linear), and
+ *   bin = clamp(floor((10 log10(PAPR) - lo_db) / step_db), 0, n_bins - 1):
+ * values outside the range land in the end bins; a period without energy counts in bin 0 and takes no part in the maximum.
+ *   Outputs (host): hist[pairs][n_bins] is ACCUMULATED into; max_papr[pairs] (or NULL) becomes max(old, largest PAPR of the
+ * call); periods[pairs][frames_per_cell][S][2] = {peak, energy} (or NULL) is a test and diagnostic aid, refused with
+ * WOFDM_E_UNSUPPORTED above WOFDM_TX_PAPR_MAX_PERIODS periods in total.  Counts are integers and max_papr a maximum: neither
+ * depends on the order of the additions, and {peak, energy} are reduced in a fixed order -- repeated calls give identical
+ * results, and a frame range split over several calls gives the histogram of one call.
+ *   Uses n_fft, bits_per_sc, syms_per_frame, cp, cs, tail_tx, n_window_pairs, seed, frame_offset, frames_per_cell of cfg and
+ * nothing else.  n_fft in {64, 128, 256, 512, 1024}, S in 2 .. 16, k in {2, 4, 6}, cp, cs <= n_fft, 2 tail_tx <= P; with a
+ * mask 3 P - 2 <= 8 n_fft as for wofdm_tx_psd_batch_masked (the mask runs as fast convolution over 8 n_fft points) -- so
+ * n_fft = 1024 is served here although the BER kernels' mask stops at 512; n_bins <= 8192; fewer than 2^28 pairs.  Outside:
+ * WOFDM_E_UNSUPPORTED.  WOFDM_E_INVALID: NULL cfg, w_tx or hist, n_bins < 1, step_db not positive or not finite, lo_db not
+ * finite, non-finite mask gains, an allocation without a loaded bin.  Every argument is checked before the device is
+ * touched, and a failed call leaves hist, max_papr and periods as they were.
+ *   Device memory is bounded whatever frames_per_cell is: the (pair, frame) items, pair-major, are processed in chunks of
+ *     min(65535, WOFDM_TX_PAPR_CHUNK_BYTES / (8 (S n_fft + T + [mask] S (2P-1))))  frames, T = tail_tx + S B
+ * -- symbol grid, waveform and (masked) filtered symbols of a frame in single-precision complex -- plus 64 bytes of job
+ * tables per frame, the windows, pairs * n_bins counters and, if asked for, periods.  The mask's spectrum is prepared once per
+ * call (host, double precision, stored in single).  Synchronous; host pointers; holds the same gate as the other synchronous
+ * entry points from its device synchronisation to the end of its kernels. */
+#define WOFDM_TX_PAPR_CHUNK_BYTES (256u << 20)
+#define WOFDM_TX_PAPR_MAX_PERIODS (1 << 20)
+int wofdm_tx_papr(const wofdm_cfg *cfg, int device,
+                  const float *w_tx,        /* [pairs][P] */
+                  const uint8_t *active,    /* [n_fft] or NULL */
+                  const float *tx_mask,     /* [2P-1] or NULL */
+                  float lo_db, float step_db, int32_t n_bins,
+                  uint64_t *hist,           /* [pairs][n_bins], ACCUMULATED into */
+                  float *max_papr,          /* [pairs], linear; max(old, new); or NULL */
+                  float *periods);          /* [pairs][frames][S][2] = {peak, energy}, or NULL */
+
+/* *ms = milliseconds (HIP events) the kernels of the calling thread's last successful wofdm_tx_papr call took, first chunk
+ * to last; 0 before any.  Measurement aid (tools/bench_tx_papr.py). */
+int wofdm_tx_papr_kernel_ms(float *ms);
+
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

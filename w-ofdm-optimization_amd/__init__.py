@@ -27,8 +27,10 @@ from .simulation import (Plan, ber_for_window_file, error_rates, make_cfg,  # no
                          results_from_counts, run_counts, run_counts_injected, run_simulation,
                          save_ber_results, simulation_fun, wOFDMSystem)
 from ._lib import kernel_source_hash  # noqa: F401
-from .timefreq import run_timefreq, tx_psd_batch_gpu, tx_waveform  # noqa: F401
-from .channel_mask import interference_for_window_file, spectrum_for_window_file  # noqa: F401
+from .timefreq import (frame_papr, papr_ccdf, papr_hist, run_timefreq, tx_papr_gpu,  # noqa: F401
+                       tx_psd_batch_gpu, tx_waveform)
+from .channel_mask import (interference_for_window_file, papr_for_window_file,  # noqa: F401
+                           spectrum_for_window_file)
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

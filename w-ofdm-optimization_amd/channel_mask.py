@@ -8,6 +8,8 @@ in both only the centre half of the spectrum carries data.  The frame loop runs 
 experiment: the periodogram and out-of-band radiation of the plain and of the masked waveform
 (``wofdm_tx_psd_batch_masked``); ``interference_for_window_file`` is its deterministic side, the closed-form ICI +
 ISI power of the same two systems (``wofdm_interference_masked``): what the mask costs next to what it buys.
+``papr_for_window_file`` is the envelope side: the PAPR histogram and CCDF of the plain and of the masked frames
+(``wofdm_tx_papr``).
 
 BER is accumulated over the whole ensemble here as there (lines 341-359).  The reference sends
 the same data bits through both runs with independent noise (two ``add_wgn`` calls); here the
@@ -189,6 +191,54 @@ def interference_for_window_file(type_ofdm, cp, windows, channels, num_subcar=25
         plain, masked = host(None), host(mask)
     return {name: {"power": plain[0][i], "wanted": plain[1][i], "power_masked": masked[0][i],
                    "wanted_masked": masked[1][i]} for i, (name, _) in enumerate(plan)}
+
+
+def papr_for_window_file(type_ofdm, cp, windows, num_subcar=256, bits_per_subcar=4, symbols_per_tx=16, ensemble=1000,
+                         roll_off=ROLL_OFF, lo_db=0.0, step_db=0.25, n_bins=64, seed=0, frame_range=None, gpu=True,
+                         device=0, tail_tx=8, tail_rx=10):
+    """PAPR companion of ``ber_for_window_file``, ``spectrum_for_window_file`` and ``interference_for_window_file``: what
+    the mask and the window do to the envelope.  Every window pair of the file + the RC pair under half-band loading; per
+    pair the PAPR histogram of the symbol periods of the frames its BER cell transmits (``ensemble`` frames of
+    ``symbols_per_tx`` symbols, or ``frame_range`` = (first, count); same seed -> same frames as a plan with one SNR point
+    and one channel), plain and masked (``tx_mask(P)``) -- on the GPU two ``wofdm_tx_papr`` calls over all pairs (one
+    with the mask, one with the allocation alone; gpu=False: the fp64 host mirror ``timefreq.frame_papr`` on random
+    symbols of its own draw, for small ensembles).  Returns {name: {"hist", "hist_masked", "ccdf", "ccdf_masked",
+    "max_db", "max_db_masked", "edges_db"}} with the names of ``V.matlab_pair_plan``; ccdf[i] = Pr(PAPR >= edges_db[i])."""
+    from . import timefreq as T
+    n = num_subcar
+    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
+                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
+    rc_tx = V.tx_rc_window(st)
+    plan = V.matlab_pair_plan(type_ofdm)
+    w_tx = np.stack([rc_tx if k[0] == "rc" else np.asarray(windows[k[0]], dtype=np.float64) for _, k in plan])
+    alloc = half_band_allocation(n)
+    mask = tx_mask(st.sym_len, roll_off)
+    first, count = (0, ensemble) if frame_range is None else frame_range
+    if gpu:
+        plain = T.tx_papr_gpu(st, bits_per_subcar, symbols_per_tx, w_tx, seed, first, count, active=alloc, lo_db=lo_db,
+                              step_db=step_db, n_bins=n_bins, device=device)
+        masked = T.tx_papr_gpu(st, bits_per_subcar, symbols_per_tx, w_tx, seed, first, count, active=alloc, mask=mask,
+                               lo_db=lo_db, step_db=step_db, n_bins=n_bins, device=device)
+    else:
+        rs = np.random.RandomState(seed)
+        tab = T.qam_table(bits_per_subcar)
+        B = st.sym_len - st.tail_tx
+
+        def host(m):
+            hists, peaks = [], []
+            for w in w_tx:
+                grids = tab[rs.randint(0, tab.size, size=(count, symbols_per_tx, n))] * alloc[None, None, :]
+                per = T.frame_papr(st, grids, w, m)
+                hists.append(T.papr_hist(per, B, lo_db, step_db, n_bins))
+                peaks.append((B * per[..., 0] / per[..., 1]).max())
+            return np.stack(hists), np.asarray(peaks)
+        plain, masked = host(None), host(mask)
+    edges = lo_db + step_db * np.arange(n_bins)
+    with np.errstate(divide="ignore"):
+        db = [10.0 * np.log10(np.asarray(r[1], dtype=np.float64)) for r in (plain, masked)]
+    return {name: {"hist": plain[0][i], "hist_masked": masked[0][i], "ccdf": T.papr_ccdf(plain[0][i]),
+                   "ccdf_masked": T.papr_ccdf(masked[0][i]), "max_db": db[0][i], "max_db_masked": db[1][i],
+                   "edges_db": edges} for i, (name, _) in enumerate(plan)}
 
 
 def results_from_counts(names, masked, plain):

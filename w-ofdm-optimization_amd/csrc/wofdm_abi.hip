@@ -17,6 +17,7 @@
 namespace {
 
 thread_local char g_err[512] = "";
+thread_local float g_papr_ms = 0.f;    // wofdm_tx_papr_kernel_ms
 
 int fail(int code, const char *fmt, ...)
 {
@@ -1274,6 +1275,134 @@ int wofdm_tx_psd_batch_masked(int32_t n_fft, int device, int32_t n_jobs, const w
 {
     return psd_batch("wofdm_tx_psd_batch_masked", n_fft, device, n_jobs, jobs, w_tx, n_masks, mask_len, mask_gain, job_mask,
                      n_blocks, no_symbols, X, psd);
+}
+
+// Every argument is checked before the first HIP call; the caller's arrays are written only after everything has succeeded.
+int wofdm_tx_papr(const wofdm_cfg *cfg, int device, const float *w_tx, const uint8_t *active, const float *tx_mask,
+                  float lo_db, float step_db, int32_t n_bins, uint64_t *hist, float *max_papr, float *periods)
+{
+    if (!cfg || !w_tx || !hist) return fail(WOFDM_E_INVALID, "NULL argument");
+    const int N = cfg->n_fft, k = cfg->bits_per_sc, S = cfg->syms_per_frame;
+    if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
+        return fail(WOFDM_E_UNSUPPORTED, "n_fft=%d not in {64,128,256,512,1024}", N);
+    if (k != 2 && k != 4 && k != 6) return fail(WOFDM_E_UNSUPPORTED, "bits_per_sc=%d not in {2,4,6}", k);
+    if (S < 2 || S > WOFDM_MAX_SYMS) return fail(WOFDM_E_UNSUPPORTED, "syms_per_frame=%d not in [2,%d]", S, WOFDM_MAX_SYMS);
+    const int P = N + cfg->cp + cfg->cs, beta = cfg->tail_tx;
+    if (cfg->cp < 0 || cfg->cs < 0 || cfg->cp > N || cfg->cs > N || beta < 0 || 2 * beta > P)
+        return fail(WOFDM_E_INVALID, "bad cp / cs / tail_tx");
+    if (cfg->n_window_pairs < 1) return fail(WOFDM_E_INVALID, "n_window_pairs must be >= 1");
+    if (n_bins < 1) return fail(WOFDM_E_INVALID, "n_bins=%d", n_bins);
+    if (!(step_db > 0.f) || !std::isfinite(step_db) || !std::isfinite(lo_db))
+        return fail(WOFDM_E_INVALID, "step_db must be positive and finite, lo_db finite");
+    const uint64_t pairs = (uint64_t)cfg->n_window_pairs, frames = cfg->frames_per_cell;
+    // (the pair is the cell of the label stream and shares its counter word with the stream id; w_off of the job tables is 32-bit)
+    if (pairs >= (1u << 28) || pairs * (uint64_t)P > (uint64_t)INT32_MAX)
+        return fail(WOFDM_E_UNSUPPORTED, "too many window pairs (2^28 cells, 2^31 window samples)");
+    if (n_bins > WOFDM_PAPR_MAX_BINS) return fail(WOFDM_E_UNSUPPORTED, "n_bins=%d exceeds %d", n_bins, WOFDM_PAPR_MAX_BINS);
+    if (frames > (UINT64_MAX >> 6) / pairs) return fail(WOFDM_E_UNSUPPORTED, "pairs * frames_per_cell * syms_per_frame overflows");
+    if (tx_mask && P > wofdm_txmask_batch_pmax(N))
+        return fail(WOFDM_E_UNSUPPORTED, "the Tx mask needs 3 P - 2 <= 8 n_fft, i.e. P = n_fft + cp + cs <= %d at n_fft = %d (P = %d)",
+                    wofdm_txmask_batch_pmax(N), N, P);
+    const uint64_t items = pairs * frames, n_periods = items * (uint64_t)S;
+    if (periods && n_periods > WOFDM_TX_PAPR_MAX_PERIODS)
+        return fail(WOFDM_E_UNSUPPORTED, "periods is a diagnostic output: at most %d periods (%llu asked for)",
+                    WOFDM_TX_PAPR_MAX_PERIODS, (unsigned long long)n_periods);
+    const int Lm = 2 * P - 1, FL = 8 * N, B = P - beta, T = beta + S * B;
+    std::vector<uint8_t> hact;
+    if (active) {
+        hact.resize((size_t)N);
+        int n_act = 0;
+        for (int n = 0; n < N; ++n) n_act += (hact[(size_t)n] = active[n] ? 1 : 0);
+        if (n_act == 0) return fail(WOFDM_E_INVALID, "the allocation loads no subcarrier");
+    }
+    if (tx_mask)
+        for (int i = 0; i < Lm; ++i)
+            if (!std::isfinite(tx_mask[i])) return fail(WOFDM_E_INVALID, "mask gains must be finite");
+    int rc = use_device(device);
+    if (rc != WOFDM_OK) return rc;
+    g_papr_ms = 0.f;
+    if (items == 0) return WOFDM_OK;
+    // frames per chunk: what the budget holds (symbol grid + waveform + filtered symbols of a frame), as the header documents it
+    const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull));
+    const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
+                                                                       std::max<uint64_t>(1, WOFDM_TX_PAPR_CHUNK_BYTES / job_bytes)));
+    std::vector<float2> hspec;
+    if (tx_mask) {
+        hspec.resize((size_t)FL);
+        mask_fastconv_spectrum(tx_mask, Lm, FL, hspec.data());
+    }
+    const size_t n_w = (size_t)pairs * P, n_hist = (size_t)pairs * n_bins;
+    dev_buf<float> d_w;
+    dev_buf<uint8_t> d_act;
+    dev_buf<float2> d_spec, d_X, d_x, d_Y, d_per;
+    dev_buf<wofdm_bjob> d_jobs;
+    dev_buf<wofdm_mjob> d_mjobs;
+    dev_buf<unsigned long long> d_hist;
+    dev_buf<uint32_t> d_max;
+    if (!d_w.alloc(n_w) || !d_X.alloc((size_t)chunk * S * N) || !d_x.alloc((size_t)chunk * T) || !d_jobs.alloc((size_t)chunk) ||
+        !d_hist.alloc(n_hist) || !d_max.alloc((size_t)pairs) || (active && !d_act.alloc(hact.size())) ||
+        (tx_mask && (!d_spec.alloc(hspec.size()) || !d_Y.alloc((size_t)chunk * S * Lm) || !d_mjobs.alloc((size_t)chunk))) ||
+        (periods && !d_per.alloc((size_t)n_periods)))
+        return fail(WOFDM_E_NOMEM, "device allocation failed");
+    if (!d_w.upload(w_tx, n_w) || (active && !d_act.upload(hact.data(), hact.size())) ||
+        (tx_mask && !d_spec.upload(hspec.data(), hspec.size())) || hipMemset(d_hist, 0, n_hist * 8) != hipSuccess ||
+        hipMemset(d_max, 0, (size_t)pairs * 4) != hipSuccess)
+        return fail(WOFDM_E_HIP, "upload failed");
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) {
+        if (ev[0]) (void)hipEventDestroy(ev[0]);
+        return fail(WOFDM_E_HIP, "event creation failed");
+    }
+    wofdm_pparams pp{};
+    pp.S = S; pp.k = k; pp.P = P; pp.cp = cfg->cp; pp.cs = cfg->cs; pp.beta = beta; pp.n_bins = n_bins;
+    pp.lo_db = lo_db; pp.step_db = step_db;
+    pp.seed_lo = (uint32_t)cfg->seed; pp.seed_hi = (uint32_t)(cfg->seed >> 32);
+    pp.frames = frames; pp.frame_offset = cfg->frame_offset;
+    pp.wtx = d_w; pp.amask = d_act; pp.spec = d_spec; pp.jobs = d_jobs; pp.mjobs = d_mjobs;
+    pp.X = d_X; pp.x = d_x; pp.Y = d_Y; pp.hist = d_hist; pp.max_bits = d_max; pp.periods = d_per;
+    std::vector<unsigned long long> hh(n_hist);
+    std::vector<uint32_t> hmax((size_t)pairs);
+    std::vector<float> hper(periods ? (size_t)n_periods * 2 : 0);
+    float ms = 0.f;
+    hipError_t e = hipSuccess;
+    {
+        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        (void)hipDeviceSynchronize();
+        const wofdm_aux_fns *ax = wofdm_aux(N);
+        e = ax ? hipEventRecord(ev[0], nullptr) : hipErrorInvalidValue;
+        for (uint64_t i0 = 0; e == hipSuccess && i0 < items; i0 += chunk) {
+            pp.item0 = i0;
+            pp.n_jobs = (int32_t)std::min<uint64_t>(chunk, items - i0);
+            e = ax->papr(&pp, nullptr);
+        }
+        if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    }
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    if (e != hipSuccess || hipMemcpy(hh.data(), d_hist, n_hist * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(hmax.data(), d_max, (size_t)pairs * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        (periods && hipMemcpy(hper.data(), d_per, (size_t)n_periods * 8, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(WOFDM_E_HIP, "PAPR kernels or copy-back failed: %s", hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
+    for (size_t i = 0; i < n_hist; ++i) hist[i] += hh[i];
+    if (max_papr)
+        for (size_t p = 0; p < (size_t)pairs; ++p) {
+            float v;
+            memcpy(&v, &hmax[p], 4);
+            max_papr[p] = std::max(max_papr[p], v);
+        }
+    if (periods) memcpy(periods, hper.data(), hper.size() * 4);
+    g_papr_ms = ms;
+    return WOFDM_OK;
+}
+
+int wofdm_tx_papr_kernel_ms(float *ms)
+{
+    if (!ms) return fail(WOFDM_E_INVALID, "NULL argument");
+    *ms = g_papr_ms;
+    return WOFDM_OK;
 }
 
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])

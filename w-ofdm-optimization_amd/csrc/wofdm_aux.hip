@@ -850,6 +850,172 @@ wofdm_interf_masked_kernel(const wofdm_mparams p, const float *__restrict__ g_wr
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Tx PAPR and its histogram, for the frames the BER loop transmits (wofdm_tx_papr; the reference has no PAPR figure).
+// Three steps per chunk of frames (wofdm_pparams): the symbol grids of the chunk from the Philox label streams -- what phase A
+// of the frame kernel feeds its IDFT --, their waveforms by the waveform kernels above with one job per frame, and {peak,
+// energy} of every symbol period of those waveforms with its histogram bin.
+//
+// Generation: thread = one Philox block of the label stream (stream 0 of philox.h: counter (s bps + blk, frame lo, frame hi,
+// pair), key = seed), 256 blocks per workgroup into LDS; they are 256 * 128 / kslot consecutive subcarriers of X, which the
+// workgroup then maps (qam_point, zero on unloaded bins) and stores side by side.  The first n_jobs threads of the grid also
+// write the chunk's job tables: job j = frame (item0 + j) % frames of pair (item0 + j) / frames.
+template <int N>
+__global__ void __launch_bounds__(256) wofdm_papr_gen_kernel(const wofdm_pparams p)
+{
+    __shared__ uint32_t words[256 * 4];
+    __shared__ v2f lut[64];
+    const int tid = threadIdx.x, S = p.S;
+    const int ks = p.k == 6 ? 8 : p.k, bps = N * ks / 128, per = 128 / ks;      // (wofdm_kslot)
+    if (tid < (1 << p.k)) lut[tid] = qam_point(p.k, (uint32_t)tid);
+    const uint32_t gid = blockIdx.x * 256u + (uint32_t)tid;           // (n_jobs S bps <= 65535 * 16 * 64)
+    if (gid < (uint32_t)p.n_jobs) {
+        const uint64_t pair = (p.item0 + gid) / p.frames;
+        const int T = p.beta + S * (p.P - p.beta);
+        wofdm_bjob jb;
+        jb.block = (int32_t)gid; jb.cp = p.cp; jb.cs = p.cs; jb.overlap = p.beta;
+        jb.w_off = (int32_t)(pair * (uint64_t)p.P); jb.len = T; jb.item0 = 0; jb.n_items = 0;
+        jb.x_off = (int64_t)gid * T;
+        p.jobs[gid] = jb;
+        if (p.mjobs != nullptr) {
+            wofdm_mjob mj;
+            mj.job = (int32_t)gid; mj.spec = 0; mj.y_off = (int64_t)gid * S * (2 * p.P - 1);
+            p.mjobs[gid] = mj;
+        }
+    }
+    if (gid < (uint32_t)p.n_jobs * (uint32_t)(S * bps)) {
+        const uint32_t sym = gid / (uint32_t)bps, blk = gid - sym * (uint32_t)bps;
+        const uint32_t j = sym / (uint32_t)S, s = sym - j * (uint32_t)S;
+        const uint64_t item = p.item0 + j, pair = item / p.frames, frame = p.frame_offset + (item - pair * p.frames);
+        const philox_out o = philox4x32_10(s * (uint32_t)bps + blk, (uint32_t)frame, (uint32_t)(frame >> 32),
+                                           (WOFDM_STREAM_BITS << 28) | (uint32_t)pair, p.seed_lo, p.seed_hi);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) words[4 * tid + i] = o.w[i];
+    }
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * 256u * (uint32_t)per, total = (uint64_t)p.n_jobs * S * N;
+    const uint32_t lmask = (1u << p.k) - 1u;
+    for (int i = tid; i < 256 * per; i += 256) {
+        const uint64_t e = base + (uint32_t)i;
+        if (e >= total) break;
+        const uint32_t bit = (uint32_t)i * (uint32_t)ks;
+        const uint32_t lab = (words[bit >> 5] >> (bit & 31u)) & lmask;
+        v2f v = lut[lab];
+        if (p.amask != nullptr && p.amask[e & (uint64_t)(N - 1)] == 0) v = mk(0.f, 0.f);
+        p.X[e] = make_float2(v.x, v.y);
+    }
+}
+
+// Sum / maximum over the 64 lanes of a wave in a fixed order: four DPP steps inside each row of 16 lanes (two quad permutes,
+// half-row mirror, row mirror), then the four row totals by lane reads.  The result is wave-uniform.
+template <bool MAX> __device__ __forceinline__ float papr_wave_reduce(float v)
+{
+#define WOFDM_DPP_STEP(ctrl)                                                                                               \
+    {                                                                                                                      \
+        const float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, false)); \
+        v = MAX ? fmaxf(v, o) : v + o;                                                                                     \
+    }
+    WOFDM_DPP_STEP(0xB1)         // quad_perm [1, 0, 3, 2]
+    WOFDM_DPP_STEP(0x4E)         // quad_perm [2, 3, 0, 1]
+    WOFDM_DPP_STEP(0x141)        // row_half_mirror
+    WOFDM_DPP_STEP(0x140)        // row_mirror
+#undef WOFDM_DPP_STEP
+    const int b = __builtin_bit_cast(int, v);
+    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0));
+    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
+    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32));
+    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
+    return MAX ? fmaxf(fmaxf(r0, r1), fmaxf(r2, r3)) : (r0 + r1) + (r2 + r3);
+}
+
+// Periods: period q = (job q / S, symbol q % S) of the chunk is the samples [s B, (s + 1) B) of the job's waveform.  A
+// workgroup (16 waves) takes a contiguous run of batches of 256 periods; in a batch wave w reduces the periods 16 w ... 16 w + 15
+// one after the other (lanes stride the samples, then papr_wave_reduce) and lane i < 16 keeps {peak, energy} of the i-th, so
+// that the bins -- a log10 each -- are formed by 16 lanes of every wave side by side.  Counts go into a workgroup-local histogram in LDS
+// (32-bit atomics) that belongs to ONE pair, the pair of the batch's first period; it is flushed to the 64-bit counters in
+// global memory (one atomic per non-empty bin) when that pair changes and at the end.  A period of another pair than the
+// batch's first -- frames * S no multiple of 256 -- adds to global memory directly.  The largest PAPR travels the same way as
+// the bit pattern of a non-negative float under an integer maximum.  Integer counts and a maximum: no result depends on the
+// order of the atomics.
+#define WOFDM_PAPR_PER_WAVE 16
+#define WOFDM_PAPR_WAVES 16
+__global__ void __launch_bounds__(WOFDM_PAPR_WAVES * 64) wofdm_papr_period_kernel(const wofdm_pparams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *lh = reinterpret_cast<uint32_t *>(smem);                // [n_bins] counts | [1] maximum
+    constexpr int PW = WOFDM_PAPR_PER_WAVE, NT = WOFDM_PAPR_WAVES * 64, BATCH = WOFDM_PAPR_WAVES * PW;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int S = p.S, B = p.P - p.beta, T = p.beta + S * B, nb = p.n_bins;
+    const uint32_t n_per = (uint32_t)p.n_jobs * (uint32_t)S;
+    const uint32_t n_batches = (n_per + BATCH - 1) / BATCH, per_wg = (n_batches + gridDim.x - 1) / gridDim.x;
+    const uint32_t b0 = blockIdx.x * per_wg, b1 = min(n_batches, b0 + per_wg);
+    for (int i = tid; i <= nb; i += NT) lh[i] = 0u;
+    __syncthreads();
+    auto flush = [&](uint64_t pair) {                                 // (called by the whole workgroup)
+        __syncthreads();
+        for (int i = tid; i < nb; i += NT) {
+            const uint32_t c = lh[i];
+            if (c != 0u) {
+                atomicAdd(&p.hist[pair * (uint64_t)nb + (uint32_t)i], (unsigned long long)c);
+                lh[i] = 0u;
+            }
+        }
+        if (tid == 0) {
+            atomicMax(&p.max_bits[pair], lh[nb]);
+            lh[nb] = 0u;
+        }
+        __syncthreads();
+    };
+    bool have = false;
+    uint64_t cur = 0;
+    for (uint32_t b = b0; b < b1; ++b) {
+        const uint32_t q0 = b * BATCH;
+        const uint64_t pair0 = (p.item0 + q0 / (uint32_t)S) / p.frames;
+        if (have && pair0 != cur) flush(cur);
+        cur = pair0;
+        have = true;
+        float pk = 0.f, en = 0.f;
+        for (int i = 0; i < PW; ++i) {
+            const uint32_t q = q0 + (uint32_t)(wv * PW + i);
+            if (q >= n_per) break;                                    // (wave-uniform)
+            const uint32_t j = q / (uint32_t)S, s = q - j * (uint32_t)S;
+            const float2 *__restrict__ src = p.x + (size_t)j * T + (size_t)s * B;
+            float m = 0.f, e = 0.f;
+            for (int t = lane; t < B; t += 64) {
+                const float2 v = src[t];
+                const float a = v.x * v.x + v.y * v.y;
+                m = fmaxf(m, a);
+                e += a;
+            }
+            m = papr_wave_reduce<true>(m);
+            e = papr_wave_reduce<false>(e);
+            if (lane == i) {
+                pk = m;
+                en = e;
+            }
+        }
+        const uint32_t q = q0 + (uint32_t)(wv * PW + lane);
+        if (lane < PW && q < n_per) {
+            const uint64_t item = p.item0 + q / (uint32_t)S, pair = item / p.frames;
+            if (p.periods != nullptr) p.periods[item * (uint64_t)S + q % (uint32_t)S] = make_float2(pk, en);
+            // PAPR = B peak / energy; bin = clamp(floor((10 log10 PAPR - lo) / step)); no energy: PAPR 0, bin 0
+            const float papr = en > 0.f ? (float)B * pk / en : 0.f;
+            const double t = papr > 0.f ? (10.0 * log10((double)papr) - (double)p.lo_db) / (double)p.step_db : -1.0;
+            const int bin = t >= (double)nb ? nb - 1 : (t > 0.0 ? (int)t : 0);
+            const uint32_t bits = __builtin_bit_cast(uint32_t, papr);
+            if (pair == cur) {
+                atomicAdd(&lh[bin], 1u);
+                atomicMax(&lh[nb], bits);
+            } else {
+                atomicAdd(&p.hist[pair * (uint64_t)nb + (uint32_t)bin], 1ull);
+                atomicMax(&p.max_bits[pair], bits);
+            }
+        }
+    }
+    if (have) flush(cur);
+}
+
 #if WOFDM_TU_N == 64
 // Philox known-answer kernel (wofdm_philox_kat): in one unit only
 __global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
@@ -976,14 +1142,54 @@ hipError_t interf_masked_launch(int pairs, int n_ch, int P, int B, int mu, int d
     return hipGetLastError();
 }
 
+// wofdm_tx_papr, one chunk: grids and job tables, the jobs' waveforms (wofdm_txwave_batch_kernel onto a zeroed x, or the
+// fast-convolution kernel and its gather, which writes every sample of x), then the periods
+hipError_t papr_launch(const wofdm_pparams *pp, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N, WW = bwave_geo<N>::WAVES, G = bmask_geo<N>::G;
+    const wofdm_pparams &p = *pp;
+    const int S = p.S, T = p.beta + S * (p.P - p.beta), bps = N * wofdm_kslot(p.k) / 128;
+    const bool masked = p.spec != nullptr;
+    if (p.n_jobs < 1 || p.n_jobs > WOFDM_PAPR_MAX_JOBS || p.n_bins < 1 || p.n_bins > WOFDM_PAPR_MAX_BINS || p.frames < 1 ||
+        p.cp > N || p.cs > N || 2 * p.beta > p.P || (masked && (p.P > bmask_geo<N>::PMAX || p.mjobs == nullptr || p.Y == nullptr)))
+        return hipErrorInvalidValue;
+    const size_t lds_a = 8 * (size_t)N * (1 + WW), lds_m = bmask_geo<N>::LDS;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txwave_batch_kernel<N>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_txmask_batch_kernel<N>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
+    if (e == hipSuccess && !masked) e = hipMemsetAsync(p.x, 0, (size_t)p.n_jobs * T * sizeof(float2), s);
+    if (e != hipSuccess) return e;
+    const unsigned n_blk = (unsigned)p.n_jobs * (unsigned)(S * bps);
+    hipLaunchKernelGGL(wofdm_papr_gen_kernel<N>, dim3((n_blk + 255) / 256), dim3(256), 0, s, p);
+    if (!masked) {
+        hipLaunchKernelGGL(wofdm_txwave_batch_kernel<N>, dim3((S + WW - 1) / WW, p.n_jobs), dim3(WW * 64), lds_a, s,
+                           (const wofdm_bjob *)p.jobs, S, p.wtx, (const float2 *)p.X, p.x);
+    } else {
+        hipLaunchKernelGGL(wofdm_txmask_batch_kernel<N>, dim3((S + G - 1) / G, p.n_jobs), dim3(512), lds_m, s,
+                           (const wofdm_bjob *)p.jobs, (const wofdm_mjob *)p.mjobs, S, p.wtx, (const float2 *)p.X, p.spec, p.Y);
+        hipLaunchKernelGGL(wofdm_txmask_ola_kernel<N>, dim3((T + 255) / 256, p.n_jobs), dim3(256), 0, s,
+                           (const wofdm_bjob *)p.jobs, (const wofdm_mjob *)p.mjobs, S, (const float2 *)p.Y, p.x);
+    }
+    // (at most two workgroups per CU's worth: a workgroup then flushes its histogram once per 256 periods or more)
+    constexpr unsigned BATCH = WOFDM_PAPR_WAVES * WOFDM_PAPR_PER_WAVE;
+    const unsigned n_batches = ((unsigned)p.n_jobs * (unsigned)S + BATCH - 1) / BATCH;
+    hipLaunchKernelGGL(wofdm_papr_period_kernel, dim3(n_batches < 512u ? n_batches : 512u), dim3(WOFDM_PAPR_WAVES * 64),
+                       4 * (size_t)(p.n_bins + 1), s, p);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 const wofdm_aux_fns *WOFDM_CAT(wofdm_aux_n, WOFDM_TU_N)(void)
 {
 #if WOFDM_TU_N <= 256
-    static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, psd_launch, psd_batch_launch, psd_batch_masked_launch};
+    static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, psd_launch, psd_batch_launch, psd_batch_masked_launch,
+                                      papr_launch};
 #else
-    static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, nullptr, psd_batch_launch, psd_batch_masked_launch};
+    static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, nullptr, psd_batch_launch, psd_batch_masked_launch,
+                                      papr_launch};
 #endif
     return &fns;
 }

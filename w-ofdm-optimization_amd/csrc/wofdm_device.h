@@ -60,6 +60,17 @@ template <int DIR> __device__ __forceinline__ v2f twid(v2f a, v2f w)
     return DIR < 0 ? cmul(a, w) : cmul_conj(a, w);
 }
 
+// qammod(label) of the frame kernel's constellation table (Gray, unit average power; main_BER_calculation.m:248-249) for k = 2,
+// 4, 6 bits: the same integers times the same fp32 scale, so the same bits.
+__device__ __forceinline__ v2f qam_point(int k, uint32_t label)
+{
+    const int hb = k >> 1, mm = (1 << hb) - 1;
+    const float qs = k == 2 ? 0.70710678118654752f : (k == 4 ? 0.31622776601683794f : 0.15430334996209191f);
+    const uint32_t gi = label >> hb, gq = label & (uint32_t)mm;
+    const int li = (int)(gi ^ (gi >> 1) ^ (gi >> 2)), lq = (int)(gq ^ (gq >> 1) ^ (gq >> 2));
+    return mk((float)(2 * li - mm), (float)(mm - 2 * lq)) * qs;
+}
+
 template <int DIR> __device__ __forceinline__ void radix4(v2f (&u)[4])
 {
     const v2f a0 = u[0] + u[2], a1 = u[0] - u[2];

@@ -369,6 +369,27 @@ struct wofdm_mjob {
 };
 __host__ __device__ constexpr int wofdm_txmask_batch_pmax(int n_fft) { return (8 * n_fft + 2) / 3; }
 
+// Tx PAPR (wofdm_tx_papr): one chunk of n_jobs consecutive (pair, frame) items, item = pair * frames + f, from item0 on.  A job
+// is one frame: its symbol grid X[job][S][n_fft], its waveform x[job][T] (T = beta + S B) and, masked, its filtered symbols
+// Y[job][S][2P - 1]; the job tables are written on the device by the generation kernel.  A period is (item, symbol).
+#define WOFDM_PAPR_MAX_JOBS 65535          // a chunk's jobs are the y dimension of the waveform kernels' grids
+#define WOFDM_PAPR_MAX_BINS 8192           // the workgroup-local histogram is 4 n_bins bytes of LDS
+struct wofdm_pparams {
+    int32_t S, k, P, cp, cs, beta, n_jobs, n_bins;
+    float lo_db, step_db;
+    uint32_t seed_lo, seed_hi;
+    uint64_t item0, frames, frame_offset;
+    const float *wtx;                 // [pairs][P]
+    const uint8_t *amask;             // [n_fft] 0 / 1, or null = every bin loaded
+    const float2 *spec;               // [8 n_fft] fast-convolution spectrum of the Tx mask, or null = no mask
+    wofdm_bjob *jobs;                 // [n_jobs]
+    wofdm_mjob *mjobs;                // [n_jobs] (masked)
+    float2 *X, *x, *Y;
+    unsigned long long *hist;         // [pairs][n_bins], accumulated into
+    uint32_t *max_bits;               // [pairs] bit pattern of the largest PAPR so far (non-negative floats order as integers)
+    float2 *periods;                  // [pairs * frames * S] {peak, energy}, or null
+};
+
 // the launchers of one DFT length
 struct wofdm_aux_fns {
     // closed-form ICI/ISI power kernels
@@ -392,6 +413,9 @@ struct wofdm_aux_fns {
                                    int n_plain, const wofdm_bjob *plain_jobs, int n_masked, const wofdm_mjob *mjobs, int max_len,
                                    const float2 *spec, float2 *Y, const float *wtx, const float2 *X, float2 *x, float *partial,
                                    float *psd, hipStream_t s);
+    // Tx PAPR of one chunk of frames (wofdm_pparams): symbol grids from the Philox label streams, the waveforms by the kernels of
+    // psd_batch / psd_batch_masked with one job per frame, then {peak, energy} of every symbol period and its histogram bin.
+    hipError_t (*papr)(const wofdm_pparams *p, hipStream_t s);
 };
 const wofdm_aux_fns *wofdm_aux_n64(void);
 const wofdm_aux_fns *wofdm_aux_n128(void);

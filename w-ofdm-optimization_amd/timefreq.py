@@ -305,3 +305,114 @@ def run_timefreq(cp_list, sys_list, window_path, folder_path, n_fft=256, rng=Non
         _timefreq_save(folder_path, system, cp, *dicts)
         out[(system, cp)] = dicts
     return out
+
+
+# ---- Tx PAPR of the frames the BER loop transmits (wofdm_tx_papr; the reference has no PAPR figure) ----
+
+def qam_table(bits_per_sc):
+    """Constellation point of every label: MATLAB ``qammod`` with Gray labels and unit average power, label = first bit
+    in the top position (the table of the frame kernels), k = 2, 4, 6."""
+    k = int(bits_per_sc)
+    if k not in (2, 4, 6):
+        raise ValueError("bits_per_sc must be 2, 4 or 6")
+    half = k // 2
+    m = 1 << half
+    lab = np.arange(1 << k)
+
+    def gray_dec(g):
+        b = g.copy()
+        for sh in (1, 2):
+            b ^= g >> sh
+        return b
+    scale = 1.0 / np.sqrt(2.0 * (m * m - 1) / 3.0)
+    return scale * ((2.0 * gray_dec(lab >> half) - (m - 1)) + 1j * ((m - 1) - 2.0 * gray_dec(lab & (m - 1))))
+
+
+def frame_papr(st, grids, w_tx, mask=None):
+    """fp64 host mirror of ``wofdm_tx_papr``'s periods.  grids: [frames, S, N] symbols on every bin (zeros on the
+    unloaded ones); each frame through ``tx_waveform`` with overlap ``st.tail_tx`` (and ``mask`` [2P-1]); symbol period
+    s is tx[s B, (s + 1) B), B = P - tail_tx -- the trailing tail_tx samples belong to no period.  Returns
+    [frames, S, 2] = {peak, energy} = {max |tx|^2, sum |tx|^2} over the period."""
+    grids = np.asarray(grids, dtype=np.complex128)
+    if grids.ndim != 3 or grids.shape[2] != st.n_fft:
+        raise ValueError("grids must be [frames, S, %d], got %s" % (st.n_fft, grids.shape))
+    n_sym, stride = grids.shape[1], st.sym_len - st.tail_tx
+    out = np.empty(grids.shape[:2] + (2,))
+    for f, grid in enumerate(grids):
+        x = tx_waveform(st, grid.T, w_tx, st.tail_tx, mask, guard_band=None)
+        p = np.abs(x[:n_sym * stride].reshape(n_sym, stride)) ** 2
+        out[f, :, 0], out[f, :, 1] = p.max(axis=1), p.sum(axis=1)
+    return out
+
+
+def papr_db(periods, B):
+    """10 log10(B peak / energy) of [..., 2] = {peak, energy}; -inf for a period without energy."""
+    periods = np.asarray(periods, dtype=np.float64)
+    peak, energy = periods[..., 0], periods[..., 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(energy > 0, 10.0 * np.log10(B * peak / np.where(energy > 0, energy, 1.0)), -np.inf)
+
+
+def papr_hist(periods, B, lo_db, step_db, n_bins):
+    """The binning rule of ``wofdm_tx_papr`` on [..., 2] = {peak, energy}: bin = clamp(floor((10 log10(B peak /
+    energy) - lo_db) / step_db), 0, n_bins - 1), a period without energy in bin 0.  Returns the counts [n_bins]
+    (uint64) over all the periods given."""
+    db = papr_db(periods, B).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        t = np.floor((db - lo_db) / step_db)
+    bins = np.clip(np.where(np.isnan(t), -1.0, t), 0, n_bins - 1).astype(np.int64)
+    return np.bincount(bins, minlength=n_bins).astype(np.uint64)
+
+
+def papr_ccdf(hist):
+    """Complementary CDF from histogram counts [..., n_bins]: ccdf[..., i] = share of the periods in the bins i and
+    above, i.e. Pr(PAPR >= lower edge of bin i); ccdf[..., 0] = 1 (zeros for an empty histogram)."""
+    hist = np.asarray(hist, dtype=np.float64)
+    tail = np.cumsum(hist[..., ::-1], axis=-1)[..., ::-1]
+    total = hist.sum(axis=-1, keepdims=True)
+    return tail / np.where(total > 0, total, 1.0)
+
+
+def tx_papr_chunk_frames(st, syms, masked):
+    """Frames one chunk of ``wofdm_tx_papr`` holds (include/wofdm.h: WOFDM_TX_PAPR_CHUNK_BYTES over the bytes of a
+    frame's symbol grid, waveform and -- masked -- filtered symbols; at most 65535)."""
+    from . import _lib
+    P = st.sym_len
+    T = st.tail_tx + syms * (P - st.tail_tx)
+    per_frame = 8 * (syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0))
+    return min(65535, max(1, _lib.TX_PAPR_CHUNK_BYTES // per_frame))
+
+
+def tx_papr_gpu(st, bits_per_sc, syms, w_tx_pairs, seed, frame_offset, frames, active=None, mask=None, lo_db=0.0,
+                step_db=0.25, n_bins=64, periods=False, device=0, hist=None, max_papr=None):
+    """``wofdm_tx_papr``: PAPR histogram of the symbol periods of the frames [frame_offset, frame_offset + frames) that
+    window pair p transmits as cell p of a plan with one SNR point and one channel (same seed, allocation ``active``
+    [N] and Tx mask ``mask`` [2P-1]).  w_tx_pairs: [pairs, P].  lo_db and step_db are taken in single precision.
+    Returns (hist [pairs, n_bins] uint64, max_papr [pairs] float32 -- linear), and with periods=True also
+    [pairs, frames, S, 2] float32 = {peak, energy}.  ``hist`` / ``max_papr`` given: accumulated into (and returned).
+    No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    from .simulation import make_cfg
+    w = _lib.f32(np.atleast_2d(w_tx_pairs))
+    pairs = w.shape[0]
+    if w.shape[1] != st.sym_len:
+        raise ValueError("w_tx_pairs must be [pairs, %d], got %s" % (st.sym_len, w.shape))
+    cfg = make_cfg(st, int(bits_per_sc), int(syms), 1, 1, 1, pairs, seed=int(seed), frames_per_cell=int(frames),
+                   frame_offset=int(frame_offset))
+    act = None if active is None else np.ascontiguousarray(np.asarray(active).reshape(-1) != 0, dtype=np.uint8)
+    if act is not None and act.shape != (st.n_fft,):
+        raise ValueError("active must hold %d flags" % st.n_fft)
+    m = None if mask is None else _lib.f32(np.asarray(mask).reshape(-1), (2 * st.sym_len - 1,))
+    hist = np.zeros((pairs, int(n_bins)), dtype=np.uint64) if hist is None else hist
+    max_papr = np.zeros(pairs, dtype=np.float32) if max_papr is None else max_papr
+    if hist.dtype != np.uint64 or hist.shape != (pairs, int(n_bins)) or not hist.flags.c_contiguous:
+        raise ValueError("hist must be a contiguous uint64 array [pairs, n_bins]")
+    if max_papr.dtype != np.float32 or max_papr.shape != (pairs,) or not max_papr.flags.c_contiguous:
+        raise ValueError("max_papr must be a contiguous float32 array [pairs]")
+    per = np.zeros((pairs, int(frames), int(syms), 2), dtype=np.float32) if periods else None
+    _lib.check(_lib.load().wofdm_tx_papr(
+        C.byref(cfg), int(device), w.ctypes.data, None if act is None else act.ctypes.data,
+        None if m is None else m.ctypes.data, float(lo_db), float(step_db), int(n_bins), hist.ctypes.data,
+        max_papr.ctypes.data, None if per is None else per.ctypes.data))
+    return (hist, max_papr, per) if periods else (hist, max_papr)
