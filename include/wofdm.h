@@ -338,6 +338,52 @@ int wofdm_tx_papr(const wofdm_cfg *cfg, int device,
  * to last; 0 before any.  Measurement aid (tools/bench_tx_papr.py). */
 int wofdm_tx_papr_kernel_ms(float *ms);
 
+/* Per-subcarrier error profile of the frames the BER loop runs: where in the band the bit errors, the symbol errors and the
+ * error-vector power sit.  The call simulates the frames [frame_offset, frame_offset + frames_per_cell) of every cell exactly
+ * as a plan draws them (label and noise streams of philox.h, all 64 bits of seed and of the frame index, cell = (pair n_snr +
+ * snr) n_channels + channel) through a second, unfused implementation of the frame pipeline: the Tx chain of wofdm_tx_papr
+ * (allocation active[n_fft], semantics of wofdm_plan_set_allocation; spectral Tx mask tx_mask[2P-1], semantics of
+ * wofdm_plan_set_tx_mask, as fast convolution over 8 n_fft points -- so n_fft = 1024 is served), then per cell conv(channel,
+ * .), add_wgn with Ps and Pn measured over the same wofdm_noise_len samples in either noise_before_truncate order, truncation,
+ * and per symbol prefix removal, Rx window, fold, circular shift and DFT, the pilot LS estimate H = Y0 / X0 of symbol 0, Xhat
+ * = Y_s / H for s >= 1, the hard decision and the comparison with the transmitted labels.  Replaces, per subcarrier instead
+ * of per frame, matlab/main_BER_calculation.m:260-272 (with 277-355) and the `offset+1:end-offset` bookkeeping of
+ * matlab/main_channel_mask.m:367-369; python/ofdm_utils/wofdm_simulation.py:205-235.  The reference has no per-bin
+ * figure.
+ *   Outputs (host), ACCUMULATED into: errs[cells][n_fft][2] = {bit errors, symbol errors} and err_power[cells][n_fft] = sum
+ * |Xhat - X|^2 (or NULL) over the frames_per_cell (S - 1) decisions a loaded bin takes in the call; unloaded bins receive
+ * nothing.  Summed over the bins, errs gives counts[cell][0] and counts[cell][2] of wofdm_plan_launch on the same cfg up to
+ * decisions that fp32 rounding tips (the kernels share no transform, FIR or slicer code with the frame kernels).  Integer
+ * counts do not depend on the order of additions, and every float sum is formed in a fixed order -- per frame over the
+ * symbols and waves in order, fp32; over the frames of a cell in frame order, fp64 -- so repeated calls give identical
+ * results, and a frame range split over several calls gives the integer counters of one call.
+ *   Limits: n_fft in {64, 128, 256, 512, 1024}, S in 2 .. 16, k in {2, 4, 6}, n_taps <= 21, tail_rx even and <= 64, n_fft +
+ * tail_rx + prefix_rm == P - tail_tx, cp, cs <= n_fft, 2 tail_tx <= P, with a mask 3 P - 2 <= 8 n_fft, fewer than 2^28
+ * cells; outside: WOFDM_E_UNSUPPORTED.  No frame image lives in LDS, so the 160 KiB limit of wofdm_plan_create does not
+ * apply.  WOFDM_E_INVALID: a NULL cfg, w_tx, w_rx, h, snr_db or errs, counts below 1, negative lengths, non-finite windows,
+ * taps, SNR points or mask gains, an allocation without a loaded bin.  Every argument is checked before the device is
+ * touched, and a failed call leaves errs and err_power as they were.
+ *   Device memory is bounded whatever frames_per_cell is: the (cell, frame) items, cell-major, are processed in chunks of
+ *     min(65535, WOFDM_RX_PROFILE_CHUNK_BYTES / (8 (S n_fft + T + [mask] S (2P-1) + n_fft)))  frames, T = tail_tx + S B
+ * -- symbol grid, waveform, (masked) filtered symbols and the per-bin partial sums of a frame -- plus 64 bytes of job tables
+ * per frame, the windows, taps and 24 bytes per (cell, bin) of totals.  Synchronous; host pointers; holds the same gate as the
+ * other synchronous entry points from its device synchronisation to the end of its kernels.  This is a diagnostic route,
+ * not the hot path: a workgroup per frame, no matrix-pipe arithmetic. */
+#define WOFDM_RX_PROFILE_CHUNK_BYTES (256u << 20)
+int wofdm_rx_profile(const wofdm_cfg *cfg, int device,
+                     const float *w_tx,      /* [pairs][P] */
+                     const float *w_rx,      /* [pairs][N+tail_rx] */
+                     const float *h,         /* [n_channels][n_taps][2] */
+                     const float *snr_db,    /* [n_snr] */
+                     const uint8_t *active,  /* [n_fft] or NULL */
+                     const float *tx_mask,   /* [2P-1] or NULL */
+                     uint64_t *errs,         /* [cells][n_fft][2] = {bit errors, symbol errors}, ACCUMULATED into */
+                     double *err_power);     /* [cells][n_fft] = sum |Xhat - X|^2, ACCUMULATED into; or NULL */
+
+/* *ms = milliseconds (HIP events) the kernels of the calling thread's last successful wofdm_rx_profile call took, first chunk
+ * to last; 0 before any.  Measurement aid (tools/bench_rx_profile.py). */
+int wofdm_rx_profile_kernel_ms(float *ms);
+
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

@@ -12,6 +12,7 @@ as ``wofdm_amd`` through the shim module at the repository root.
   window_design  interference Hessians + QP -> optimised windows (optimizers.py / window_optimization.m)
   timefreq     Tx-side PSD / out-of-band-radiation estimate (timefreq_simulation.py)
   channel_mask main_channel_mask.m: half-band loading + spectral Tx mask (GPU: allocation / tx_mask)
+  rx_profile   per-subcarrier BER / EVM of the frames the BER loop runs (GPU: wofdm_rx_profile; fp64 host mirror)
   _lib         ctypes binding of libwofdm_hip.so (include/wofdm.h)
 """
 from . import variants  # noqa: F401
@@ -23,6 +24,7 @@ from . import interference  # noqa: F401
 from . import window_design  # noqa: F401
 from . import timefreq  # noqa: F401
 from . import channel_mask  # noqa: F401
+from . import rx_profile  # noqa: F401
 from .simulation import (Plan, ber_for_window_file, error_rates, make_cfg,  # noqa: F401
                          results_from_counts, run_counts, run_counts_injected, run_simulation,
                          save_ber_results, simulation_fun, wOFDMSystem)
@@ -30,7 +32,9 @@ from ._lib import kernel_source_hash  # noqa: F401
 from .timefreq import (frame_papr, papr_ccdf, papr_hist, run_timefreq, tx_papr_gpu,  # noqa: F401
                        tx_psd_batch_gpu, tx_waveform)
 from .channel_mask import (interference_for_window_file, papr_for_window_file,  # noqa: F401
-                           spectrum_for_window_file)
+                           profile_for_window_file, spectrum_for_window_file)
+from .rx_profile import (RxProfile, ber_per_bin, evm_db, frame_profile, rx_profile_gpu,  # noqa: F401
+                         rx_profile_host)
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

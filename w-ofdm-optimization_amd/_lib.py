@@ -24,6 +24,8 @@ MAX_SYMS = 16
 #: wofdm_tx_papr (include/wofdm.h): device-memory budget of a chunk of frames, most periods the `periods` output takes
 TX_PAPR_CHUNK_BYTES = 256 << 20
 TX_PAPR_MAX_PERIODS = 1 << 20
+#: wofdm_rx_profile (include/wofdm.h): device-memory budget of a chunk of frames
+RX_PROFILE_CHUNK_BYTES = 256 << 20
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -34,6 +36,7 @@ EXPORTS = (
     "wofdm_plan_set_tx_mask", "wofdm_plan_status", "wofdm_plan_kernel_id", "wofdm_plan_set_option",
     "wofdm_interference", "wofdm_tx_psd", "wofdm_tx_psd_batch", "wofdm_tx_psd_batch_masked",
     "wofdm_interference_masked", "wofdm_tx_papr", "wofdm_tx_papr_kernel_ms",
+    "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms",
 )
 
 
@@ -142,6 +145,8 @@ def load():
     L.wofdm_tx_psd_batch_masked.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]
     L.wofdm_tx_papr.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp]
     L.wofdm_tx_papr_kernel_ms.argtypes = [C.POINTER(C.c_float)]
+    L.wofdm_rx_profile.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.wofdm_rx_profile_kernel_ms.argtypes = [C.POINTER(C.c_float)]
     _LIB = L
     return L
 

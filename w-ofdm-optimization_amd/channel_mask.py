@@ -9,7 +9,8 @@ experiment: the periodogram and out-of-band radiation of the plain and of the ma
 (``wofdm_tx_psd_batch_masked``); ``interference_for_window_file`` is its deterministic side, the closed-form ICI +
 ISI power of the same two systems (``wofdm_interference_masked``): what the mask costs next to what it buys.
 ``papr_for_window_file`` is the envelope side: the PAPR histogram and CCDF of the plain and of the masked frames
-(``wofdm_tx_papr``).
+(``wofdm_tx_papr``).  ``profile_for_window_file`` shows where in the band the errors of the two systems sit: bit errors,
+symbol errors and error-vector power per subcarrier (``wofdm_rx_profile``).
 
 BER is accumulated over the whole ensemble here as there (lines 341-359).  The reference sends
 the same data bits through both runs with independent noise (two ``add_wgn`` calls); here the
@@ -239,6 +240,47 @@ def papr_for_window_file(type_ofdm, cp, windows, num_subcar=256, bits_per_subcar
     return {name: {"hist": plain[0][i], "hist_masked": masked[0][i], "ccdf": T.papr_ccdf(plain[0][i]),
                    "ccdf_masked": T.papr_ccdf(masked[0][i]), "max_db": db[0][i], "max_db_masked": db[1][i],
                    "edges_db": edges} for i, (name, _) in enumerate(plan)}
+
+
+def profile_for_window_file(type_ofdm, cp, windows, channels, snr_db, num_subcar=256, bits_per_subcar=4, symbols_per_tx=16,
+                            ensemble=100, roll_off=ROLL_OFF, seed=0, frame_range=None, gpu=True, device=0, tail_tx=8,
+                            tail_rx=10):
+    """Per-subcarrier companion of ``ber_for_window_file``: where in the band the errors sit.  Every window pair of the
+    file + the RC pair under half-band loading, for every SNR point and channel [n_channels][taps]: bit errors, symbol
+    errors and error power sum |Xhat - X|^2 per subcarrier of the frames the BER cells run (``ensemble`` frames, or
+    ``frame_range`` = (first, count); same seed -> the frames of a plan with the same pairs, SNR points and channels),
+    plain and masked (``tx_mask(P)``) -- on the GPU two ``wofdm_rx_profile`` calls (gpu=False: the fp64 host route
+    ``rx_profile.rx_profile_host`` on the same Philox streams, for small ensembles).  Unlike ``run_sim_mc`` both runs
+    cover the SAME frame range: bits and noise are those of the cell, so the two profiles differ by the mask alone.
+    Returns {name: {"profile", "profile_masked"}} with the names of ``V.matlab_pair_plan``; each is an
+    ``rx_profile.RxProfile`` of that pair, arrays [n_snr, n_channels, N] (``rx_profile.ber_per_bin``, ``evm_db``)."""
+    from . import rx_profile as R
+    n = num_subcar
+    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
+                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
+    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
+    plan = V.matlab_pair_plan(type_ofdm)
+
+    def pick(key, side):
+        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
+
+    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
+    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
+    h = np.atleast_2d(np.asarray(channels))
+    alloc = half_band_allocation(n)
+    mask = tx_mask(st.sym_len, roll_off)
+    first, count = (0, ensemble) if frame_range is None else frame_range
+    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, h, snr_db, seed, first, count)
+    if gpu:
+        plain = R.rx_profile_gpu(*args, active=alloc, device=device)
+        masked = R.rx_profile_gpu(*args, active=alloc, mask=mask, device=device)
+    else:
+        plain = R.rx_profile_host(*args, active=alloc)
+        masked = R.rx_profile_host(*args, active=alloc, mask=mask)
+
+    def of_pair(prof, i):
+        return R.RxProfile(prof.bit_err[i], prof.sym_err[i], prof.err_power[i], prof.decisions)
+    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
 
 
 def results_from_counts(names, masked, plain):

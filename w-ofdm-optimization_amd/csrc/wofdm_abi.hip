@@ -18,6 +18,7 @@ namespace {
 
 thread_local char g_err[512] = "";
 thread_local float g_papr_ms = 0.f;    // wofdm_tx_papr_kernel_ms
+thread_local float g_rxprof_ms = 0.f;  // wofdm_rx_profile_kernel_ms
 
 int fail(int code, const char *fmt, ...)
 {
@@ -1357,7 +1358,7 @@ int wofdm_tx_papr(const wofdm_cfg *cfg, int device, const float *w_tx, const uin
     pp.S = S; pp.k = k; pp.P = P; pp.cp = cfg->cp; pp.cs = cfg->cs; pp.beta = beta; pp.n_bins = n_bins;
     pp.lo_db = lo_db; pp.step_db = step_db;
     pp.seed_lo = (uint32_t)cfg->seed; pp.seed_hi = (uint32_t)(cfg->seed >> 32);
-    pp.frames = frames; pp.frame_offset = cfg->frame_offset;
+    pp.frames = frames; pp.frame_offset = cfg->frame_offset; pp.wdiv = 1;
     pp.wtx = d_w; pp.amask = d_act; pp.spec = d_spec; pp.jobs = d_jobs; pp.mjobs = d_mjobs;
     pp.X = d_X; pp.x = d_x; pp.Y = d_Y; pp.hist = d_hist; pp.max_bits = d_max; pp.periods = d_per;
     std::vector<unsigned long long> hh(n_hist);
@@ -1402,6 +1403,148 @@ int wofdm_tx_papr_kernel_ms(float *ms)
 {
     if (!ms) return fail(WOFDM_E_INVALID, "NULL argument");
     *ms = g_papr_ms;
+    return WOFDM_OK;
+}
+
+// Every argument is checked before the first HIP call; the caller's arrays are written only after everything has succeeded.
+int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
+                     const float *snr_db, const uint8_t *active, const float *tx_mask, uint64_t *errs, double *err_power)
+{
+    if (!cfg || !w_tx || !w_rx || !h || !snr_db || !errs) return fail(WOFDM_E_INVALID, "NULL argument");
+    const int N = cfg->n_fft, k = cfg->bits_per_sc, S = cfg->syms_per_frame, L = cfg->n_taps;
+    if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
+        return fail(WOFDM_E_UNSUPPORTED, "n_fft=%d not in {64,128,256,512,1024}", N);
+    if (k != 2 && k != 4 && k != 6) return fail(WOFDM_E_UNSUPPORTED, "bits_per_sc=%d not in {2,4,6}", k);
+    if (S < 2 || S > WOFDM_MAX_SYMS) return fail(WOFDM_E_UNSUPPORTED, "syms_per_frame=%d not in [2,%d]", S, WOFDM_MAX_SYMS);
+    if (cfg->n_channels < 1 || cfg->n_snr < 1 || cfg->n_window_pairs < 1)
+        return fail(WOFDM_E_INVALID, "n_channels, n_snr, n_window_pairs must be >= 1");
+    if (cfg->cp < 0 || cfg->cs < 0 || cfg->tail_tx < 0 || cfg->tail_rx < 0 || cfg->prefix_rm < 0 || cfg->circ_shift < 0 ||
+        cfg->circ_shift >= N || L < 1)
+        return fail(WOFDM_E_INVALID, "negative length, n_taps < 1 or circ_shift >= n_fft");
+    if (L > WOFDM_MAX_TAPS) return fail(WOFDM_E_UNSUPPORTED, "n_taps=%d exceeds %d", L, WOFDM_MAX_TAPS);
+    const int P = N + cfg->cp + cfg->cs, beta = cfg->tail_tx, delta = cfg->tail_rx, gam = cfg->prefix_rm;
+    if ((delta & 1) || delta > 64) return fail(WOFDM_E_UNSUPPORTED, "tail_rx=%d must be even and <= 64", delta);
+    if (cfg->cp > N || cfg->cs > N || 2 * beta > P) return fail(WOFDM_E_UNSUPPORTED, "cp, cs <= n_fft and 2 tail_tx <= P required");
+    if (N + delta + gam != P - beta)
+        return fail(WOFDM_E_UNSUPPORTED, "n_fft+tail_rx+prefix_rm (%d) != n_fft+cp+cs-tail_tx (%d)", N + delta + gam, P - beta);
+    if (tx_mask && P > wofdm_txmask_batch_pmax(N))
+        return fail(WOFDM_E_UNSUPPORTED, "the Tx mask needs 3 P - 2 <= 8 n_fft, i.e. P = n_fft + cp + cs <= %d at n_fft = %d (P = %d)",
+                    wofdm_txmask_batch_pmax(N), N, P);
+    const uint64_t pairs = (uint64_t)cfg->n_window_pairs, cpp = (uint64_t)cfg->n_snr * (uint64_t)cfg->n_channels;
+    const uint64_t cells = pairs * cpp, frames = cfg->frames_per_cell;
+    // (the cell shares its counter word with the stream id; w_off of the job tables is 32-bit)
+    if (cells >= (1u << 28) || pairs * (uint64_t)P > (uint64_t)INT32_MAX)
+        return fail(WOFDM_E_UNSUPPORTED, "too many cells (2^28) or window samples (2^31)");
+    if (frames > (UINT64_MAX >> 6) / cells) return fail(WOFDM_E_UNSUPPORTED, "cells * frames_per_cell * syms_per_frame overflows");
+    const int Lm = 2 * P - 1, FL = 8 * N, B = P - beta, T = beta + S * B, NW = N + delta;
+    const auto finite = [](const float *a, size_t n) {
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(a[i])) return false;
+        return true;
+    };
+    if (!finite(w_tx, (size_t)pairs * P) || !finite(w_rx, (size_t)pairs * NW)) return fail(WOFDM_E_INVALID, "windows must be finite");
+    if (!finite(h, (size_t)cfg->n_channels * L * 2)) return fail(WOFDM_E_INVALID, "channel taps must be finite");
+    if (!finite(snr_db, (size_t)cfg->n_snr)) return fail(WOFDM_E_INVALID, "SNR points must be finite");
+    if (tx_mask && !finite(tx_mask, (size_t)Lm)) return fail(WOFDM_E_INVALID, "mask gains must be finite");
+    std::vector<uint8_t> hact;
+    if (active) {
+        hact.resize((size_t)N);
+        int n_act = 0;
+        for (int n = 0; n < N; ++n) n_act += (hact[(size_t)n] = active[n] ? 1 : 0);
+        if (n_act == 0) return fail(WOFDM_E_INVALID, "the allocation loads no subcarrier");
+    }
+    int rc = use_device(device);
+    if (rc != WOFDM_OK) return rc;
+    g_rxprof_ms = 0.f;
+    const uint64_t items = cells * frames;
+    if (items == 0) return WOFDM_OK;
+    // frames per chunk: what the budget holds (symbol grid + waveform + filtered symbols + partials of a frame), as the header documents it
+    const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) + (uint64_t)N);
+    const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
+                                                                       std::max<uint64_t>(1, WOFDM_RX_PROFILE_CHUNK_BYTES / job_bytes)));
+    std::vector<float2> hspec;
+    if (tx_mask) {
+        hspec.resize((size_t)FL);
+        mask_fastconv_spectrum(tx_mask, Lm, FL, hspec.data());
+    }
+    geom g{};
+    g.L = L;
+    const std::vector<float2> hp = pack_taps(cfg, g, h);
+    std::vector<float> nlin((size_t)cfg->n_snr);
+    for (int i = 0; i < cfg->n_snr; ++i) nlin[(size_t)i] = (float)std::pow(10.0, -0.1 * (double)snr_db[i]);
+    const size_t n_w = (size_t)pairs * P, n_wr = (size_t)pairs * NW, n_out = (size_t)cells * N;
+    dev_buf<float> d_w, d_wr, d_nlin, d_ppow;
+    dev_buf<uint8_t> d_act;
+    dev_buf<float2> d_h, d_spec, d_X, d_x, d_Y;
+    dev_buf<wofdm_bjob> d_jobs;
+    dev_buf<wofdm_mjob> d_mjobs;
+    dev_buf<uint32_t> d_pcnt;
+    dev_buf<unsigned long long> d_errs;
+    dev_buf<double> d_pow;
+    if (!d_w.alloc(n_w) || !d_wr.alloc(n_wr) || !d_nlin.alloc(nlin.size()) || !d_h.alloc(hp.size()) ||
+        !d_X.alloc((size_t)chunk * S * N) || !d_x.alloc((size_t)chunk * T) || !d_jobs.alloc((size_t)chunk) ||
+        !d_ppow.alloc((size_t)chunk * N) || !d_pcnt.alloc((size_t)chunk * N) || !d_errs.alloc(2 * n_out) || !d_pow.alloc(n_out) ||
+        (active && !d_act.alloc(hact.size())) ||
+        (tx_mask && (!d_spec.alloc(hspec.size()) || !d_Y.alloc((size_t)chunk * S * Lm) || !d_mjobs.alloc((size_t)chunk))))
+        return fail(WOFDM_E_NOMEM, "device allocation failed");
+    if (!d_w.upload(w_tx, n_w) || !d_wr.upload(w_rx, n_wr) || !d_nlin.upload(nlin.data(), nlin.size()) ||
+        !d_h.upload(hp.data(), hp.size()) || (active && !d_act.upload(hact.data(), hact.size())) ||
+        (tx_mask && !d_spec.upload(hspec.data(), hspec.size())) || hipMemset(d_errs, 0, 2 * n_out * 8) != hipSuccess ||
+        hipMemset(d_pow, 0, n_out * 8) != hipSuccess)
+        return fail(WOFDM_E_HIP, "upload failed");
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) {
+        if (ev[0]) (void)hipEventDestroy(ev[0]);
+        return fail(WOFDM_E_HIP, "event creation failed");
+    }
+    wofdm_pparams pp{};
+    pp.S = S; pp.k = k; pp.P = P; pp.cp = cfg->cp; pp.cs = cfg->cs; pp.beta = beta; pp.n_bins = 1;
+    pp.seed_lo = (uint32_t)cfg->seed; pp.seed_hi = (uint32_t)(cfg->seed >> 32);
+    pp.frames = frames; pp.frame_offset = cfg->frame_offset; pp.wdiv = (uint32_t)cpp;
+    pp.wtx = d_w; pp.amask = d_act; pp.spec = d_spec; pp.jobs = d_jobs; pp.mjobs = d_mjobs;
+    pp.X = d_X; pp.x = d_x; pp.Y = d_Y;
+    wofdm_rparams rp{};
+    rp.S = S; rp.k = k; rp.B = B; rp.T = T; rp.NL = cfg->noise_before_truncate ? T + L - 1 : S * B;
+    rp.delta = delta; rp.gam = gam; rp.kap = cfg->circ_shift; rp.n_ch = cfg->n_channels; rp.n_snr = cfg->n_snr;
+    rp.seed_lo = pp.seed_lo; rp.seed_hi = pp.seed_hi; rp.frames = frames; rp.frame_offset = cfg->frame_offset;
+    rp.X = d_X; rp.x = d_x; rp.wrx = d_wr; rp.h = d_h; rp.nlin = d_nlin; rp.amask = d_act;
+    rp.part_pow = d_ppow; rp.part_cnt = d_pcnt; rp.errs = d_errs; rp.pow = d_pow;
+    std::vector<unsigned long long> herr(2 * n_out);
+    std::vector<double> hpow(n_out);
+    float ms = 0.f;
+    hipError_t e = hipSuccess;
+    {
+        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        (void)hipDeviceSynchronize();
+        const wofdm_aux_fns *ax = wofdm_aux(N);
+        e = ax ? hipEventRecord(ev[0], nullptr) : hipErrorInvalidValue;
+        for (uint64_t i0 = 0; e == hipSuccess && i0 < items; i0 += chunk) {
+            pp.item0 = rp.item0 = i0;
+            pp.n_jobs = rp.n_jobs = (int32_t)std::min<uint64_t>(chunk, items - i0);
+            e = ax->rx_profile(&pp, &rp, nullptr);
+        }
+        if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    }
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    if (e != hipSuccess || hipMemcpy(herr.data(), d_errs, 2 * n_out * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(hpow.data(), d_pow, n_out * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(WOFDM_E_HIP, "receive-profile kernels or copy-back failed: %s",
+                    hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
+    for (size_t i = 0; i < 2 * n_out; ++i) errs[i] += herr[i];
+    if (err_power)
+        for (size_t i = 0; i < n_out; ++i) err_power[i] += hpow[i];
+    g_rxprof_ms = ms;
+    return WOFDM_OK;
+}
+
+int wofdm_rx_profile_kernel_ms(float *ms)
+{
+    if (!ms) return fail(WOFDM_E_INVALID, "NULL argument");
+    *ms = g_rxprof_ms;
     return WOFDM_OK;
 }
 

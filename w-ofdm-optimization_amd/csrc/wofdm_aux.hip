@@ -1,6 +1,6 @@
 // wofdm_aux.hip -- the auxiliary kernels beside the frame kernel: closed-form ICI/ISI power (wofdm_interference,
 // wofdm_interference_masked) and Tx waveform + averaged periodogram (wofdm_tx_psd, wofdm_tx_psd_batch,
-// wofdm_tx_psd_batch_masked).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
+// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
 // on n_fft through the unit's table of launchers (wofdm_aux_fns).
 #include "wofdm_kernel.h"
 #include "wofdm_device.h"
@@ -874,7 +874,7 @@ __global__ void __launch_bounds__(256) wofdm_papr_gen_kernel(const wofdm_pparams
         const int T = p.beta + S * (p.P - p.beta);
         wofdm_bjob jb;
         jb.block = (int32_t)gid; jb.cp = p.cp; jb.cs = p.cs; jb.overlap = p.beta;
-        jb.w_off = (int32_t)(pair * (uint64_t)p.P); jb.len = T; jb.item0 = 0; jb.n_items = 0;
+        jb.w_off = (int32_t)(pair / p.wdiv * (uint64_t)p.P); jb.len = T; jb.item0 = 0; jb.n_items = 0;
         jb.x_off = (int64_t)gid * T;
         p.jobs[gid] = jb;
         if (p.mjobs != nullptr) {
@@ -1016,6 +1016,252 @@ __global__ void __launch_bounds__(WOFDM_PAPR_WAVES * 64) wofdm_papr_period_kerne
     if (have) flush(cur);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-subcarrier BER and EVM of the frames the BER loop runs (wofdm_rx_profile): a second, unfused implementation of the
+// whole frame pipeline behind the Tx chain above,
+//   conv, add_wgn, truncate        matlab/main_BER_calculation.m:260-261, 277-294
+//   wofdm_rx                       main_BER_calculation.m:297-355 (Rx window, fold, circular shift, DFT)
+//   LS estimate, equaliser, slicer main_BER_calculation.m:266-272
+// (the semantics of the CPU checker's frame).  The chunk's items are (cell, frame) here: every cell draws its own
+// labels, so the generation kernel runs with wdiv = n_snr n_channels cells per window pair.
+//
+// One workgroup per item.  Pass 1: Ps = sum |conv|^2 and Pn = sum |unit noise|^2 over the same NL samples (thread-strided
+// partials, the wave sum of papr_wave_reduce, the waves in order: a fixed order), g = sqrt(Ps 10^(-snr/10) / Pn).  Pass 2: a
+// wave per symbol, symbols wave, wave + W, ...: the N + delta + 20 samples of x under the symbol's receive window go into the
+// wave's LDS row, every lane forms the received samples of its DFT inputs from them -- the 21-tap sum and the unit normal of
+// that sample (stream 1 of philox.h, one block per sample: half of each block is drawn twice, which keeps the frame out of
+// LDS) --, windows, folds and shifts them (literally, as the reference does), and the wave transforms its row: radix-2,
+// decimation in time over bit-reversed stores, plain fp32 complex arithmetic -- not the transform of the frame kernels.
+// Wave 0 publishes the pilot equaliser X0 / Y0 behind the first round's barrier; every lane keeps the counters of its bins
+// n = lane + 64 j in registers over the wave's symbols.  The waves' sums are added in wave order into the item's partials
+// part_pow[job][N] (fp32) and part_cnt[job][N] (bit errors | symbol errors << 16), and wofdm_rxprof_reduce_kernel adds a
+// cell's items in frame order (fp64) onto the call's totals: no float atomics anywhere, repeated calls give identical bits.
+// LDS does not grow with S or cp + cs: twiddles [N / 2] | G [N] | w_rx [N + 64] | 64 floats | per wave: row [N] + x [N + 88].
+template <int N> struct rxp_geo {
+    static constexpr int WAVES = N >= 1024 ? 4 : 8, BINS = N / 64;
+    static constexpr int LOG2 = N == 64 ? 6 : (N == 128 ? 7 : (N == 256 ? 8 : (N == 512 ? 9 : 10)));
+    static constexpr int XROW = N + 64 + 24;                          // tail_rx <= 64, WOFDM_LT - 1 <= 24 samples of history
+    static constexpr int LDS = 8 * (N / 2) + 8 * N + 4 * (N + 64) + 4 * 64 + WAVES * 8 * (N + XROW);
+    static_assert(LDS <= 160 * 1024 && WAVES * 8 * N <= WAVES * 8 * (N + XROW) && (1 << LOG2) == N, "LDS");
+};
+
+// the complex unit normal of sample a of (seed, cell, frame): philox.h, block a / 2, words 2 (a % 2) and 2 (a % 2) + 1
+__device__ __forceinline__ v2f rxp_noise(uint32_t a, uint32_t f_lo, uint32_t f_hi, uint32_t cell, uint32_t k0, uint32_t k1, int which)
+{
+    const philox_out o = philox4x32_10(a, f_lo, f_hi, (WOFDM_STREAM_NOISE << 28) | cell, k0, k1);
+    const uint32_t wa = which ? o.w[2] : o.w[0], wb = which ? o.w[3] : o.w[1];
+    const float u1 = fmaf((float)wa, 2.3283064365386963e-10f, 1.1641532182693481e-10f);
+    const float u2 = (float)(wb >> 9) * 1.1920928955078125e-07f;
+    const float rad = sqrtf(-2.0f * logf(u1));
+    float sv, cv;
+    sincospif(2.0f * u2, &sv, &cv);
+    return mk(rad * cv, rad * sv);
+}
+// qamdemod, hard decision (main_BER_calculation.m:269-270): MATLAB Gray label of the nearest point
+__device__ __forceinline__ uint32_t rxp_slice(int k, float re, float im)
+{
+    const int hb = k >> 1, mm = (1 << hb) - 1;
+    const float a = k == 2 ? 1.4142135623730951f : (k == 4 ? 3.1622776601683795f : 6.4807406984078604f);
+    int ii = (int)floorf((re * a + (float)mm) * 0.5f + 0.5f), qi = (int)floorf(((float)mm - im * a) * 0.5f + 0.5f);
+    ii = ii < 0 ? 0 : (ii > mm ? mm : ii);
+    qi = qi < 0 ? 0 : (qi > mm ? mm : qi);
+    return ((uint32_t)(ii ^ (ii >> 1)) << hb) | (uint32_t)(qi ^ (qi >> 1));
+}
+
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(const wofdm_rparams p)
+{
+    using RG = rxp_geo<N>;
+    constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float2 *tw = reinterpret_cast<float2 *>(smem);                    // e^{-2 pi i k / N}, k < N / 2
+    float2 *G = tw + N / 2;                                           // pilot equaliser X0 / Y0
+    float *wrx = reinterpret_cast<float *>(G + N);
+    float *red = wrx + N + 64;                                        // [2][W] power partials
+    float2 *rows = reinterpret_cast<float2 *>(red + 64);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int S = p.S, B = p.B, T = p.T, NL = p.NL, delta = p.delta;
+    const uint32_t job = blockIdx.x;
+    const uint64_t item = p.item0 + job, cell64 = item / p.frames, frame = p.frame_offset + (item - cell64 * p.frames);
+    const uint32_t cell = (uint32_t)cell64, f_lo = (uint32_t)frame, f_hi = (uint32_t)(frame >> 32);
+    const int ch = (int)(cell % (uint32_t)p.n_ch), sn = (int)((cell / (uint32_t)p.n_ch) % (uint32_t)p.n_snr);
+    const int pair = (int)(cell / ((uint32_t)p.n_ch * (uint32_t)p.n_snr));
+    const float2 *__restrict__ x = p.x + (size_t)job * T;
+    const float2 *__restrict__ Xg = p.X + (size_t)job * S * N;
+    const float2 *__restrict__ taps = p.h + (size_t)ch * LT;
+    for (int i = tid; i < N / 2; i += NT) {
+        float sv, cv;
+        sincospif(-2.0f * (float)i / (float)N, &sv, &cv);
+        tw[i] = make_float2(cv, sv);
+    }
+    for (int i = tid; i < N + delta; i += NT) wrx[i] = p.wrx[(size_t)pair * (N + delta) + i];
+    // pass 1: signal and noise power over the same NL samples (add_wgn, m:277-294); a thread takes whole Philox blocks
+    float ps = 0.f, pn = 0.f;
+    for (int q = tid; 2 * q < NL; q += NT) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int jj = 2 * q + e;
+            if (jj >= NL) break;
+            float cr = 0.f, ci = 0.f;
+            for (int l = 0; l < LT; ++l) {
+                const int t = jj - l;
+                if (t < 0 || t >= T) continue;
+                const float2 xv = x[t], hv = taps[l];
+                cr += hv.x * xv.x - hv.y * xv.y;
+                ci += hv.x * xv.y + hv.y * xv.x;
+            }
+            const v2f nz = rxp_noise((uint32_t)q, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, e);
+            ps += cr * cr + ci * ci;
+            pn += nz.x * nz.x + nz.y * nz.y;
+        }
+    }
+    ps = papr_wave_reduce<false>(ps);
+    pn = papr_wave_reduce<false>(pn);
+    if (lane == 0) {
+        red[wv] = ps;
+        red[W + wv] = pn;
+    }
+    __syncthreads();
+    float Ps = 0.f, Pn = 0.f;
+    for (int w = 0; w < W; ++w) {
+        Ps += red[w];
+        Pn += red[W + w];
+    }
+    const float g = sqrtf(Ps * p.nlin[sn] / Pn);
+    // pass 2
+    float2 *buf = rows + (size_t)wv * (N + RG::XROW);
+    float2 *xr = buf + N;
+    float pw[BINS];
+    uint32_t cnt[BINS];
+#pragma unroll
+    for (int j = 0; j < BINS; ++j) {
+        pw[j] = 0.f;
+        cnt[j] = 0u;
+    }
+    const int h2 = delta >> 1;
+    for (int s0 = 0; s0 < S; s0 += W) {
+        const int s = s0 + wv;
+        const bool live = s < S;                                      // (wave-uniform)
+        if (live) {
+            const int a0 = s * B + p.gam;                             // first sample under the Rx window (m:442-454)
+            for (int i = lane; i < N + delta + LT - 1; i += 64) {
+                const int t = a0 - (LT - 1) + i;
+                xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
+            }
+            wave_sync();
+            // r[a] = conv[a] + g n[a] (m:260-261, 290-293) of the sample m under the window
+            auto rxs = [&](int m) {
+                float cr = 0.f, ci = 0.f;
+#pragma unroll
+                for (int l = 0; l < LT; ++l) {
+                    const float2 xv = xr[m + (LT - 1) - l], hv = taps[l];
+                    cr += hv.x * xv.x - hv.y * xv.y;
+                    ci += hv.x * xv.y + hv.y * xv.x;
+                }
+                const uint32_t a = (uint32_t)(a0 + m);
+                const v2f nz = rxp_noise(a >> 1, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, (int)(a & 1u));
+                return make_float2(cr + g * nz.x, ci + g * nz.y);
+            };
+#pragma unroll 1
+            for (int j = 0; j < BINS; ++j) {
+                // Rx window, fold, circular shift (m:297-355): z[t] = sum_{m = t + kappa + delta/2 (mod N)} w[m] r[gamma + m]
+                const int t = lane + 64 * j, m0 = (t + p.kap + h2) & (N - 1);
+                float2 z = rxs(m0);
+                z.x *= wrx[m0];
+                z.y *= wrx[m0];
+                if (m0 < delta) {
+                    const float2 z2 = rxs(m0 + N);
+                    z.x += wrx[m0 + N] * z2.x;
+                    z.y += wrx[m0 + N] * z2.y;
+                }
+                buf[__brev((uint32_t)t) >> (32 - LOG2)] = z;
+            }
+            wave_sync();
+            // DFT (dftmtx(N), m:306): radix-2 stages in place
+            for (int len = 2, sh = LOG2 - 1; len <= N; len <<= 1, --sh) {
+                const int half = len >> 1;
+                for (int b = lane; b < N / 2; b += 64) {
+                    const int kk = b & (half - 1), i = ((b - kk) << 1) | kk;
+                    const float2 w = tw[kk << sh], a = buf[i], c = buf[i + half];
+                    const float tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
+                    buf[i] = make_float2(a.x + tr, a.y + ti);
+                    buf[i + half] = make_float2(a.x - tr, a.y - ti);
+                }
+                wave_sync();
+            }
+        }
+        if (s0 == 0) {
+            // pilot LS estimate (m:266-267): G = X0 / Y0 on the loaded bins
+            if (wv == 0)
+                for (int n = lane; n < N; n += 64) {
+                    const float2 y = buf[n], x0 = Xg[n];
+                    const float d = y.x * y.x + y.y * y.y;
+                    const bool on = p.amask == nullptr || p.amask[n] != 0;
+                    G[n] = on ? make_float2((x0.x * y.x + x0.y * y.y) / d, (x0.y * y.x - x0.x * y.y) / d) : make_float2(0.f, 0.f);
+                }
+            __syncthreads();
+        }
+        if (live && s >= 1) {
+#pragma unroll
+            for (int j = 0; j < BINS; ++j) {
+                const int n = lane + 64 * j;
+                if (p.amask != nullptr && p.amask[n] == 0) continue;
+                const float2 y = buf[n], gq = G[n], xs = Xg[(size_t)s * N + n];
+                const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;       // equaliser (m:268)
+                const uint32_t d = rxp_slice(p.k, xs.x, xs.y) ^ rxp_slice(p.k, er, ei);        // (X is the point of its own label)
+                cnt[j] += (uint32_t)__popc(d) + (d != 0u ? 0x10000u : 0u);
+                pw[j] += (er - xs.x) * (er - xs.x) + (ei - xs.y) * (ei - xs.y);
+            }
+        }
+        wave_sync();
+    }
+    // the waves' sums in wave order (their rows are free now): float [W][N], then uint32 [W][N]
+    __syncthreads();
+    float *redp = reinterpret_cast<float *>(rows);
+    uint32_t *redc = reinterpret_cast<uint32_t *>(redp + W * N);
+#pragma unroll
+    for (int j = 0; j < BINS; ++j) {
+        redp[wv * N + lane + 64 * j] = pw[j];
+        redc[wv * N + lane + 64 * j] = cnt[j];
+    }
+    __syncthreads();
+    for (int n = tid; n < N; n += NT) {
+        float t = 0.f;
+        uint32_t c = 0u;
+        for (int w = 0; w < W; ++w) {
+            t += redp[w * N + n];
+            c += redc[w * N + n];
+        }
+        p.part_pow[(size_t)job * N + n] = t;
+        p.part_cnt[(size_t)job * N + n] = c;
+    }
+}
+
+// totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
+template <int N>
+__global__ void __launch_bounds__(64) wofdm_rxprof_reduce_kernel(const wofdm_rparams p, uint64_t cell0)
+{
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    const uint64_t cell = cell0 + blockIdx.y, end = p.item0 + (uint64_t)p.n_jobs;
+    const uint64_t lo = cell * p.frames > p.item0 ? cell * p.frames : p.item0;
+    const uint64_t hi = (cell + 1) * p.frames < end ? (cell + 1) * p.frames : end;
+    double acc = 0.0;
+    unsigned long long be = 0ull, se = 0ull;
+    for (uint64_t i = lo; i < hi; ++i) {
+        const size_t idx = (size_t)(i - p.item0) * N + n;
+        const uint32_t c = p.part_cnt[idx];
+        acc += (double)p.part_pow[idx];
+        be += c & 0xFFFFu;
+        se += c >> 16;
+    }
+    if (lo < hi) {
+        p.errs[2 * (cell * N + n)] += be;
+        p.errs[2 * (cell * N + n) + 1] += se;
+        p.pow[cell * N + n] += acc;
+    }
+}
+
 #if WOFDM_TU_N == 64
 // Philox known-answer kernel (wofdm_philox_kat): in one unit only
 __global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
@@ -1142,15 +1388,14 @@ hipError_t interf_masked_launch(int pairs, int n_ch, int P, int B, int mu, int d
     return hipGetLastError();
 }
 
-// wofdm_tx_papr, one chunk: grids and job tables, the jobs' waveforms (wofdm_txwave_batch_kernel onto a zeroed x, or the
-// fast-convolution kernel and its gather, which writes every sample of x), then the periods
-hipError_t papr_launch(const wofdm_pparams *pp, hipStream_t s)
+// The Tx chain of one chunk (wofdm_tx_papr, wofdm_rx_profile): grids and job tables, then the jobs' waveforms
+// (wofdm_txwave_batch_kernel onto a zeroed x, or the fast-convolution kernel and its gather, which writes every sample of x)
+hipError_t tx_chain_launch(const wofdm_pparams &p, hipStream_t s)
 {
     constexpr int N = WOFDM_TU_N, WW = bwave_geo<N>::WAVES, G = bmask_geo<N>::G;
-    const wofdm_pparams &p = *pp;
     const int S = p.S, T = p.beta + S * (p.P - p.beta), bps = N * wofdm_kslot(p.k) / 128;
     const bool masked = p.spec != nullptr;
-    if (p.n_jobs < 1 || p.n_jobs > WOFDM_PAPR_MAX_JOBS || p.n_bins < 1 || p.n_bins > WOFDM_PAPR_MAX_BINS || p.frames < 1 ||
+    if (p.n_jobs < 1 || p.n_jobs > WOFDM_PAPR_MAX_JOBS || p.frames < 1 || p.wdiv < 1 ||
         p.cp > N || p.cs > N || 2 * p.beta > p.P || (masked && (p.P > bmask_geo<N>::PMAX || p.mjobs == nullptr || p.Y == nullptr)))
         return hipErrorInvalidValue;
     const size_t lds_a = 8 * (size_t)N * (1 + WW), lds_m = bmask_geo<N>::LDS;
@@ -1172,11 +1417,41 @@ hipError_t papr_launch(const wofdm_pparams *pp, hipStream_t s)
         hipLaunchKernelGGL(wofdm_txmask_ola_kernel<N>, dim3((T + 255) / 256, p.n_jobs), dim3(256), 0, s,
                            (const wofdm_bjob *)p.jobs, (const wofdm_mjob *)p.mjobs, S, (const float2 *)p.Y, p.x);
     }
+    return hipGetLastError();
+}
+
+// wofdm_tx_papr, one chunk: the Tx chain, then the periods
+hipError_t papr_launch(const wofdm_pparams *pp, hipStream_t s)
+{
+    const wofdm_pparams &p = *pp;
+    if (p.n_bins < 1 || p.n_bins > WOFDM_PAPR_MAX_BINS) return hipErrorInvalidValue;
+    const hipError_t e = tx_chain_launch(p, s);
+    if (e != hipSuccess) return e;
+    const int S = p.S;
     // (at most two workgroups per CU's worth: a workgroup then flushes its histogram once per 256 periods or more)
     constexpr unsigned BATCH = WOFDM_PAPR_WAVES * WOFDM_PAPR_PER_WAVE;
     const unsigned n_batches = ((unsigned)p.n_jobs * (unsigned)S + BATCH - 1) / BATCH;
     hipLaunchKernelGGL(wofdm_papr_period_kernel, dim3(n_batches < 512u ? n_batches : 512u), dim3(WOFDM_PAPR_WAVES * 64),
                        4 * (size_t)(p.n_bins + 1), s, p);
+    return hipGetLastError();
+}
+
+// wofdm_rx_profile, one chunk: the Tx chain of the chunk's (cell, frame) items, their receive profiles, and the ordered sums
+hipError_t rx_profile_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N;
+    const wofdm_rparams &r = *rp;
+    if (r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
+        r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 || r.n_snr < 1)
+        return hipErrorInvalidValue;
+    hipError_t e = tx_chain_launch(*pp, s);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                rxp_geo<N>::LDS);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_rxprof_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r);
+    const uint64_t cell0 = r.item0 / r.frames, cell1 = (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames;
+    hipLaunchKernelGGL(wofdm_rxprof_reduce_kernel<N>, dim3(N / 64, (unsigned)(cell1 - cell0 + 1)), dim3(64), 0, s, r, cell0);
     return hipGetLastError();
 }
 
@@ -1186,10 +1461,10 @@ const wofdm_aux_fns *WOFDM_CAT(wofdm_aux_n, WOFDM_TU_N)(void)
 {
 #if WOFDM_TU_N <= 256
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, psd_launch, psd_batch_launch, psd_batch_masked_launch,
-                                      papr_launch};
+                                      papr_launch, rx_profile_launch};
 #else
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, nullptr, psd_batch_launch, psd_batch_masked_launch,
-                                      papr_launch};
+                                      papr_launch, rx_profile_launch};
 #endif
     return &fns;
 }

@@ -379,6 +379,8 @@ struct wofdm_pparams {
     float lo_db, step_db;
     uint32_t seed_lo, seed_hi;
     uint64_t item0, frames, frame_offset;
+    uint32_t wdiv;                    // cells per window pair: the item's "pair" is its CELL of the label stream, its window that
+                                      // of pair / wdiv (wofdm_tx_papr: 1; wofdm_rx_profile: n_snr n_channels)
     const float *wtx;                 // [pairs][P]
     const uint8_t *amask;             // [n_fft] 0 / 1, or null = every bin loaded
     const float2 *spec;               // [8 n_fft] fast-convolution spectrum of the Tx mask, or null = no mask
@@ -388,6 +390,23 @@ struct wofdm_pparams {
     unsigned long long *hist;         // [pairs][n_bins], accumulated into
     uint32_t *max_bits;               // [pairs] bit pattern of the largest PAPR so far (non-negative floats order as integers)
     float2 *periods;                  // [pairs * frames * S] {peak, energy}, or null
+};
+
+// Receive profile (wofdm_rx_profile): the chunk of wofdm_pparams with items = (cell, frame), item = cell * frames + f -- the
+// Tx chain leaves X[job][S][n_fft] and x[job][T] --, one workgroup per item, then the ordered sums of the chunk onto the totals.
+struct wofdm_rparams {
+    int32_t S, k, B, T, NL, delta, gam, kap, n_ch, n_snr, n_jobs;
+    uint32_t seed_lo, seed_hi;
+    uint64_t item0, frames, frame_offset;
+    const float2 *X, *x;              // the chunk's symbol grids and waveforms
+    const float *wrx;                 // [pairs][n_fft + delta]
+    const float2 *h;                  // [n_ch][WOFDM_LT], zero padded
+    const float *nlin;                // [n_snr] 10^(-snr / 10)
+    const uint8_t *amask;             // [n_fft] 0 / 1, or null = every bin loaded
+    float *part_pow;                  // [n_jobs][n_fft] sum |Xhat - X|^2 of the item
+    uint32_t *part_cnt;               // [n_jobs][n_fft] bit errors | symbol errors << 16 of the item
+    unsigned long long *errs;         // [cells][n_fft][2], accumulated into
+    double *pow;                      // [cells][n_fft], accumulated into
 };
 
 // the launchers of one DFT length
@@ -416,6 +435,9 @@ struct wofdm_aux_fns {
     // Tx PAPR of one chunk of frames (wofdm_pparams): symbol grids from the Philox label streams, the waveforms by the kernels of
     // psd_batch / psd_batch_masked with one job per frame, then {peak, energy} of every symbol period and its histogram bin.
     hipError_t (*papr)(const wofdm_pparams *p, hipStream_t s);
+    // Receive profile of one chunk of (cell, frame) items: the Tx chain of papr (p->wdiv = cells per window pair), one
+    // workgroup per item for its per-bin error counts and error power, and the sums of the chunk in frame order.
+    hipError_t (*rx_profile)(const wofdm_pparams *p, const wofdm_rparams *r, hipStream_t s);
 };
 const wofdm_aux_fns *wofdm_aux_n64(void);
 const wofdm_aux_fns *wofdm_aux_n128(void);

@@ -1,0 +1,261 @@
+"""Per-subcarrier BER and EVM of the frames the BER loop runs (``wofdm_rx_profile``).
+
+Where in the band the errors sit: for every cell (window pair, SNR, channel) and every subcarrier the bit errors, the
+symbol errors and the error-vector power sum |Xhat - X|^2 over the decisions of the frames [frame_offset, frame_offset +
+frames) -- the frames a ``Plan`` with the same cfg and seed simulates, so the bins add up to its counters.  The reference
+reduces every frame to one BER (matlab/main_BER_calculation.m:272); for the half-band, spectrally masked system of
+matlab/main_channel_mask.m the per-bin picture is the interesting one.
+
+``rx_profile_gpu`` runs on the GPU (no CPU fallback); ``frame_profile`` is the fp64 numpy mirror of ONE frame with the
+randomness given, ``rx_profile_host`` draws the same Philox streams on the host (csrc/philox.h) and runs it frame by frame
+-- for small ensembles, the check of the GPU route.
+"""
+import collections
+
+import numpy as np
+
+RxProfile = collections.namedtuple("RxProfile", "bit_err sym_err err_power decisions")
+RxProfile.__doc__ = """bit_err, sym_err (uint64), err_power (float64): [pairs, n_snr, n_ch, N]; decisions [N]: hard decisions a
+bin took per cell = frames * (S - 1) on the loaded bins, 0 on the others."""
+
+NEAR_TOL = 1e-4
+
+
+# ---- the slicer and the helpers on the counters ----
+
+def slice_labels(bits_per_sc, z):
+    """``qamdemod`` hard decision (main_BER_calculation.m:269-270): MATLAB Gray label of the nearest point of the unit-power
+    constellation, the first bit of the subcarrier on top (``timefreq.qam_table`` is its inverse)."""
+    k = int(bits_per_sc)
+    half = k // 2
+    m = 1 << half
+    a = np.sqrt(2.0 * (m * m - 1) / 3.0)
+    z = np.asarray(z, dtype=np.complex128)
+    ii = np.clip(np.floor((z.real * a + (m - 1)) * 0.5 + 0.5), 0, m - 1).astype(np.int64)
+    qi = np.clip(np.floor(((m - 1) - z.imag * a) * 0.5 + 0.5), 0, m - 1).astype(np.int64)
+    return ((ii ^ (ii >> 1)) << half) | (qi ^ (qi >> 1))
+
+
+def threshold_distance(bits_per_sc, z):
+    """Distance of the nearer component of z to the nearest slicer threshold that matters (the outer regions have none
+    beyond the last threshold), in constellation units."""
+    k = int(bits_per_sc)
+    m = 1 << (k // 2)
+    a = np.sqrt(2.0 * (m * m - 1) / 3.0)
+    z = np.asarray(z, dtype=np.complex128)
+
+    def comp(v):
+        t = (v * a + (m - 1)) * 0.5 + 0.5           # thresholds at the integers 1 .. m - 1
+        near = np.clip(np.round(t), 1, m - 1)
+        return np.abs(t - near) * 2.0 / a
+    return np.minimum(comp(z.real), comp(-z.imag))
+
+
+def near_decisions(bits_per_sc, xhat, y0, tol=NEAR_TOL):
+    """[S-1, N] bool: decisions that single-precision rounding may tip -- a component of the fp64 ``xhat`` [S-1, N] lies
+    within tol * max(1, |xhat|) * max_n |y0| / |y0[n]| of a slicer threshold (y0 [N]: the received pilot; 0 = unloaded)."""
+    xhat = np.asarray(xhat, dtype=np.complex128)
+    a0 = np.abs(np.asarray(y0))
+    with np.errstate(divide="ignore"):
+        bound = tol * np.maximum(1.0, np.abs(xhat)) * (a0.max() / a0)[None, :]
+    return (threshold_distance(bits_per_sc, xhat) <= bound) & (a0 > 0)[None, :]
+
+
+def ber_per_bin(prof, bits_per_sc):
+    """Bit error rate per subcarrier [pairs, n_snr, n_ch, N]; NaN on unloaded bins."""
+    d = prof.decisions.astype(np.float64) * int(bits_per_sc)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(d > 0, prof.bit_err / np.where(d > 0, d, 1.0), np.nan)
+
+
+def evm_db(prof):
+    """Error-vector magnitude per subcarrier in dB relative to the constellation's unit average power:
+    10 log10(err_power / decisions); NaN on unloaded bins."""
+    d = prof.decisions.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(d > 0, 10.0 * np.log10(prof.err_power / np.where(d > 0, d, 1.0)), np.nan)
+
+
+# ---- fp64 host mirror ----
+
+def frame_profile(st, grids, unit_noise, w_tx, w_rx, h, snr_db, bits_per_sc, active=None, mask=None,
+                  noise_before_truncate=1):
+    """fp64 host mirror of one frame of ``wofdm_rx_profile`` (main_BER_calculation.m:253-272,
+    277-355).  grids [S, N]: the transmitted constellation points (zeros on unloaded bins);
+    unit_noise [noise_len] complex; w_tx [P], w_rx [N + delta], h [taps].  Returns (bit_err [N], sym_err [N], err_power
+    [N], xhat [S-1, N], y0 [N]); unloaded bins are 0 everywhere."""
+    from . import timefreq as T
+    X = np.asarray(grids, dtype=np.complex128)
+    n, delta, gam, k = st.n_fft, st.tail_rx, st.prefix_rm, int(bits_per_sc)
+    S, B = X.shape[0], st.sym_len - st.tail_tx
+    if X.shape != (S, n) or B != n + delta + gam:
+        raise ValueError("grids must be [S, %d] and the structure consistent" % n)
+    on = np.ones(n, dtype=bool) if active is None else np.asarray(active).reshape(-1) != 0
+    tx = T.tx_waveform(st, X.T, np.asarray(w_tx, np.float64), st.tail_tx, mask, guard_band=None)
+    conv = np.convolve(np.asarray(h, dtype=np.complex128).reshape(-1), tx)           # m:260
+    noise = np.asarray(unit_noise, dtype=np.complex128).reshape(-1)
+    nl = conv.size if noise_before_truncate else S * B
+    if noise.size < nl:
+        raise ValueError("unit_noise holds %d samples, %d needed" % (noise.size, nl))
+    ps, pn = np.mean(np.abs(conv[:nl]) ** 2), np.mean(np.abs(noise[:nl]) ** 2)       # add_wgn, m:277-294
+    g = np.sqrt(ps * 10.0 ** (-0.1 * float(snr_db)) / pn)
+    r = (conv[:S * B] + g * noise[:S * B]).reshape(S, B)                             # truncate, m:261-263
+    blocks = r[:, gam:gam + n + delta] * np.asarray(w_rx, np.float64)[None, :]       # wofdm_rx, m:297-355
+    z = blocks[:, :n].copy()
+    z[:, :delta] += blocks[:, n:]
+    Y = np.fft.fft(np.roll(z, -(st.circ_shift + delta // 2), axis=1), axis=1)
+    xhat = np.zeros((S - 1, n), dtype=np.complex128)
+    xhat[:, on] = Y[1:, on] / (Y[0, on] / X[0, on])[None, :]                         # m:266-268
+    d = np.where(on[None, :], slice_labels(k, X[1:]) ^ slice_labels(k, xhat), 0)
+    bits = sum((d >> b) & 1 for b in range(k))
+    err = np.where(on[None, :], np.abs(xhat - X[1:]) ** 2, 0.0)
+    return (bits.sum(axis=0).astype(np.uint64), (d != 0).sum(axis=0).astype(np.uint64), err.sum(axis=0), xhat,
+            np.where(on, Y[0], 0.0))
+
+
+# ---- the random streams of csrc/philox.h on the host ----
+
+def _philox(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on uint64 arrays that hold 32-bit words"""
+    lo = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & lo for c in np.broadcast_arrays(c0, c1, c2, c3))
+    k0, k1 = np.uint64(k0), np.uint64(k1)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & lo, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & lo
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & lo, (k1 + np.uint64(0xBB67AE85)) & lo
+    return np.stack([c0, c1, c2, c3], axis=-1)
+
+
+def _stream(seed, stream, cell, frame, n_blocks):
+    seed, frame = int(seed) & (2 ** 64 - 1), int(frame) & (2 ** 64 - 1)
+    return _philox(np.arange(n_blocks, dtype=np.uint64), frame & 0xFFFFFFFF, frame >> 32,
+                   (stream << 28) | (int(cell) & 0x0FFFFFFF), seed & 0xFFFFFFFF, seed >> 32)
+
+
+def gen_labels(n_fft, bits_per_sc, syms, seed, cell, frame):
+    """[S, N] uint8 labels of stream 0 of (seed, cell, frame): csrc/philox.h, what a plan draws."""
+    k = int(bits_per_sc)
+    ks = 8 if k == 6 else k
+    bps = n_fft * ks // 128
+    w = _stream(seed, 0, cell, frame, syms * bps).reshape(syms, bps * 4)
+    bit = np.arange(n_fft, dtype=np.int64) * ks
+    return ((w[:, bit >> 5] >> (bit & 31).astype(np.uint64)[None, :]) & np.uint64((1 << k) - 1)).astype(np.uint8)
+
+
+def gen_noise(noise_len, seed, cell, frame):
+    """[noise_len] complex unit normals of stream 1 of (seed, cell, frame): the uniforms in single precision as the kernels
+    form them, Box-Muller in double."""
+    w = _stream(seed, 1, cell, frame, (noise_len + 1) // 2).reshape(-1, 2)[:noise_len]
+    u1 = (w[:, 0].astype(np.float32).astype(np.float64) * 2.0 ** -32 + 2.0 ** -33).astype(np.float32).astype(np.float64)
+    u2 = (w[:, 1] >> np.uint64(9)).astype(np.float64) * 2.0 ** -23
+    return np.sqrt(-2.0 * np.log(u1)) * np.exp(2j * np.pi * u2)
+
+
+def _noise_len(st, syms, n_taps, noise_before_truncate):
+    B = st.sym_len - st.tail_tx
+    return st.tail_tx + syms * B + n_taps - 1 if noise_before_truncate else syms * B
+
+
+def _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask):
+    from . import _lib
+    w_tx = _lib.f32(np.atleast_2d(w_tx_pairs))
+    w_rx = _lib.f32(np.atleast_2d(w_rx_pairs))
+    if w_tx.shape[1] != st.sym_len or w_rx.shape != (w_tx.shape[0], st.n_fft + st.tail_rx):
+        raise ValueError("windows must be [pairs, %d] and [pairs, %d]" % (st.sym_len, st.n_fft + st.tail_rx))
+    hc = np.ascontiguousarray(np.atleast_2d(h), dtype=np.complex64)
+    snr = _lib.f32(np.atleast_1d(snr_db))
+    act = None if active is None else np.ascontiguousarray(np.asarray(active).reshape(-1) != 0, dtype=np.uint8)
+    if act is not None and act.shape != (st.n_fft,):
+        raise ValueError("active must hold %d flags" % st.n_fft)
+    m = None if mask is None else _lib.f32(np.asarray(mask).reshape(-1), (2 * st.sym_len - 1,))
+    return w_tx, w_rx, hc, snr, act, m
+
+
+def _decisions(st, syms, frames, act):
+    on = np.ones(st.n_fft, dtype=bool) if act is None else act != 0
+    return np.where(on, int(frames) * (int(syms) - 1), 0).astype(np.uint64)
+
+
+def rx_profile_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, active=None,
+                    mask=None, noise_before_truncate=1, with_near=False):
+    """The host route of ``rx_profile_gpu``: the same frames from the same Philox streams, each through
+    ``frame_profile`` (single-precision inputs as the GPU receives them, fp64 arithmetic).  with_near=True: also the
+    number of ``near_decisions`` per cell [pairs, n_snr, n_ch]."""
+    from . import timefreq as T
+    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, hc.shape[0], st.n_fft
+    k, S = int(bits_per_sc), int(syms)
+    tab = T.qam_table(k)
+    nl = _noise_len(st, S, hc.shape[1], noise_before_truncate)
+    on = np.ones(n, dtype=bool) if act is None else act != 0
+    bit = np.zeros((pairs, n_snr, n_ch, n), dtype=np.uint64)
+    sym = np.zeros_like(bit)
+    pw = np.zeros(bit.shape, dtype=np.float64)
+    near = np.zeros((pairs, n_snr, n_ch), dtype=np.int64)
+    for cell in range(pairs * n_snr * n_ch):
+        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
+        for f in range(int(frames)):
+            fr = int(frame_offset) + f
+            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
+            b, se, e, xhat, y0 = frame_profile(st, grid, gen_noise(nl, seed, cell, fr), w_tx[p], w_rx[p], hc[c],
+                                               snr[s], k, act, m, noise_before_truncate)
+            bit[p, s, c] += b
+            sym[p, s, c] += se
+            pw[p, s, c] += e
+            if with_near:
+                near[p, s, c] += int(near_decisions(k, xhat, y0).sum())
+    prof = RxProfile(bit, sym, pw, _decisions(st, S, frames, act))
+    return (prof, near) if with_near else prof
+
+
+# ---- GPU ----
+
+def rx_profile_chunk_frames(st, syms, masked):
+    """Frames one chunk of ``wofdm_rx_profile`` holds (include/wofdm.h: WOFDM_RX_PROFILE_CHUNK_BYTES over the bytes of a
+    frame's symbol grid, waveform, -- masked -- filtered symbols and per-bin partial sums; at most 65535)."""
+    from . import _lib
+    P = st.sym_len
+    T = st.tail_tx + syms * (P - st.tail_tx)
+    per_frame = 8 * (syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0) + st.n_fft)
+    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+
+
+def rx_profile_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, active=None,
+                   mask=None, noise_before_truncate=1, device=0, out=None):
+    """``wofdm_rx_profile``: per-subcarrier bit errors, symbol errors and error power of the frames [frame_offset,
+    frame_offset + frames) of every cell of the sweep w_tx_pairs [pairs, P] x w_rx_pairs [pairs, N + delta] x snr_db
+    [n_snr] x h [n_ch, taps] -- drawn as a ``Plan`` of the same cfg and seed draws them, with the allocation ``active`` [N]
+    and the Tx mask ``mask`` [2P-1].  Returns ``RxProfile``; ``out`` (an earlier result of the same shape) is accumulated
+    into, its ``decisions`` added up.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    from .simulation import make_cfg
+    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0]
+    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[1], n_ch, n_snr, pairs, bool(noise_before_truncate),
+                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
+    shape = (pairs, n_snr, n_ch, st.n_fft)
+    errs = np.zeros(shape + (2,), dtype=np.uint64)
+    pw = np.zeros(shape, dtype=np.float64)
+    hf = _lib.c64_as_f32(hc)
+    _lib.check(_lib.load().wofdm_rx_profile(
+        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
+        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, errs.ctypes.data, pw.ctypes.data))
+    prof = RxProfile(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
+                     _decisions(st, syms, frames, act))
+    if out is not None:
+        if out.bit_err.shape != shape:
+            raise ValueError("out has another shape")
+        prof = RxProfile(out.bit_err + prof.bit_err, out.sym_err + prof.sym_err, out.err_power + prof.err_power,
+                         out.decisions + prof.decisions)
+    return prof
+
+
+def rx_profile_kernel_ms():
+    """Milliseconds the kernels of this thread's last ``rx_profile_gpu`` call took (``wofdm_rx_profile_kernel_ms``)."""
+    import ctypes as C
+    from . import _lib
+    ms = C.c_float()
+    _lib.check(_lib.load().wofdm_rx_profile_kernel_ms(C.byref(ms)))
+    return float(ms.value)
