@@ -108,6 +108,11 @@ struct wofdm_plan {
     float2 *d_tspec = nullptr;         // [WOFDM_TXFFT_LEN] its fast-convolution spectrum (FFT form)
     float *d_tspec4 = nullptr;         // the same x 2^4 in layout 15's order: [kc][re | im][lane][j] <-> bin lane + 64 j + 256 kc
     unsigned *d_status = nullptr;      // kernel status word (wofdm_kparams::status)
+    unsigned long long *d_work = nullptr;   // work counter of the launch in flight (wofdm_kparams::work)
+    // wofdm_work_split's share of the static heads and the chunk of the tail (developer override: WOFDM_SPLIT_ALPHA, a fraction
+    // in [0, 1), and WOFDM_SPLIT_CHUNK, read when the plan is created; tools/README.md)
+    uint32_t split_alpha_256 = WOFDM_SPLIT_ALPHA_256, split_chunk = WOFDM_SPLIT_CHUNK;
+    bool split_forced = false;         // either of them given: every launch with more items than workgroups has a tail
     uint4 *d_fira = nullptr;           // [n_ch][4][64] Toeplitz operands of the matrix-pipe FIR (MFMA A layout)
     float firm_sx = 1.f, firm_sh = 1.f; // powers of two carried by the f16 samples / f16 taps there
     uint4 *d_dftc = nullptr;           // [10][64] operands of the matrix-pipe 256-point transforms (build_dftc)
@@ -289,8 +294,12 @@ int launch(wofdm_plan *pl, int mode, wofdm_kparams &kp, uint64_t total_items, in
     kp.status = pl->d_status;
     kp.dftc = pl->d_dftc;
     kp.rx_scale = pl->d_rxs;
-    kp.items_q = total_items / grid;
-    kp.items_r = total_items % grid;
+    const bool dynamic = (mode == WOFDM_MODE_GEN || mode == WOFDM_MODE_INJECT) && wofdm_layout_dynamic(pl->layout, pl->g.N)
+                         && (pl->split_forced || (pl->occ >= 2 && total_items / grid >= WOFDM_SPLIT_MIN_ITEMS));
+    const wofdm_split sp = wofdm_work_split(total_items, grid, dynamic, pl->split_alpha_256, pl->split_chunk);
+    kp.head_q = sp.head_q; kp.head_r = sp.head_r; kp.tail0 = sp.tail0; kp.total = total_items;
+    kp.chunk = sp.chunk;
+    kp.work = pl->d_work;
     kp.lds_bytes = pl->base.lds_bytes;
     float2 *tm = pl->var == WOFDM_VAR_TXFFT ? (pl->layout == 15 ? reinterpret_cast<float2 *>(pl->d_tspec4) : pl->d_tspec) : pl->d_tmask;
     kp.tx_scale = pl->base.tx_scale;
@@ -325,6 +334,8 @@ int launch(wofdm_plan *pl, int mode, wofdm_kparams &kp, uint64_t total_items, in
         const int dev = pl->device & 63;
         if (last[dev]) HIP_TRY(hipStreamWaitEvent(stream, last[dev], 0));
         else HIP_TRY(hipEventCreateWithFlags(&last[dev], hipEventDisableTiming));
+        // (the work counter is the plan's: zeroed behind the previous launch, whichever stream that ran on)
+        if (kp.tail0 < kp.total) HIP_TRY(hipMemsetAsync(pl->d_work, 0, sizeof(unsigned long long), stream));
         HIP_TRY(hipLaunchKernel(reinterpret_cast<const void *>(fn), dim3((unsigned)grid),
                                 dim3(64u * (unsigned)wofdm_waves(pl->layout, pl->g.N, pl->g.S, pl->g.B)), args, kp.lds_bytes, stream));
         HIP_TRY(hipEventRecord(last[dev], stream));
@@ -591,6 +602,26 @@ int wofdm_plan_create(wofdm_plan **out, const wofdm_cfg *cfg, int device, const 
     pl->cus = prop.multiProcessorCount;
     PLAN_TRY(hipMalloc(&pl->d_status, sizeof(unsigned)));
     PLAN_TRY(hipMemset(pl->d_status, 0, sizeof(unsigned)));
+    PLAN_TRY(hipMalloc(&pl->d_work, sizeof(unsigned long long)));
+    PLAN_TRY(hipMemset(pl->d_work, 0, sizeof(unsigned long long)));
+    if (const char *e = std::getenv("WOFDM_SPLIT_ALPHA")) {
+        const double a = std::strtod(e, nullptr);
+        if (!(a >= 0.0 && a < 1.0)) {
+            wofdm_plan_destroy(pl);
+            return fail(WOFDM_E_INVALID, "WOFDM_SPLIT_ALPHA=%s: a fraction in [0, 1)", e);
+        }
+        pl->split_alpha_256 = (uint32_t)(a * 256.0);
+        pl->split_forced = true;
+    }
+    if (const char *e = std::getenv("WOFDM_SPLIT_CHUNK")) {
+        const unsigned long c = std::strtoul(e, nullptr, 0);
+        if (c < 1 || c > (1ul << 20)) {
+            wofdm_plan_destroy(pl);
+            return fail(WOFDM_E_INVALID, "WOFDM_SPLIT_CHUNK=%s: 1 ... 2^20 items", e);
+        }
+        pl->split_chunk = (uint32_t)c;
+        pl->split_forced = true;
+    }
     if ((rc = configure(pl)) != WOFDM_OK) {
         wofdm_plan_destroy(pl);
         return rc;
@@ -622,6 +653,7 @@ int wofdm_plan_destroy(wofdm_plan *pl)
     if (pl->d_tspec) (void)hipFree(pl->d_tspec);
     if (pl->d_tspec4) (void)hipFree(pl->d_tspec4);
     if (pl->d_status) (void)hipFree(pl->d_status);
+    if (pl->d_work) (void)hipFree(pl->d_work);
     if (pl->d_fira) (void)hipFree(pl->d_fira);
     if (pl->d_dftc) (void)hipFree(pl->d_dftc);
     if (pl->d_rxs) (void)hipFree(pl->d_rxs);

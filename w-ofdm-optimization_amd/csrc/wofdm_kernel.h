@@ -22,6 +22,7 @@ struct wofdm_kdump {          // device pointers, all may be null
 //   sums  float [2][32]      per-wave signal / noise power partials, double-buffered by frame parity
 //   flags int   [64]         [w] = last loop iteration whose phase A wave w has finished,
 //                            [16] = last iteration whose pilot equaliser G is published, [20] = a wave gave up waiting,
+//                            [17 .. 19], [21 .. 23], [28 .. 31] = the hand-out of the launch's items (WS_* in wofdm_kernel.hip),
 //                            [32 + w] = (Tx-mask variants) last iteration whose masked symbol wave w has written to its row,
 //                            [48 + w] = (Tx-mask variants on the matrix pipe, layouts 9 / 15) last iteration whose row wave w has
 //                            turned into its two f16 planes (the successor's first tile reads the row's last samples)
@@ -60,7 +61,11 @@ struct wofdm_kparams {
     uint32_t inject_base_cell;   // injected arrays AND the counter array are indexed from this cell
     unsigned lds_bytes;
     uint64_t frames_per_cell, frame_offset;
-    uint64_t items_q, items_r;     // (cell, frame) items per workgroup: q, and one more for the first r
+    // (cell, frame) items of the launch, cell-major (wofdm_work_split): workgroup b starts with a run of head_q items, one more
+    // for the first head_r workgroups; the items [tail0, total) go out in chunks of `chunk` through the work counter
+    uint64_t head_q, head_r, tail0, total;
+    uint32_t chunk;               // 0: no tail
+    unsigned long long *work;     // the plan's work counter: items of the tail handed out so far (zero at the launch)
     uint32_t seed_lo, seed_hi;
     unsigned long long *counts;   // [cells][4], entry 0 = cell inject_base_cell
     // layouts 10 / 11 / 12 (both transforms on the matrix pipe): operand table [10 + 2 (N/256 - 1)][64] x 16 bytes
@@ -89,6 +94,37 @@ struct wofdm_kparams {
     uint32_t audit_items;
 #endif
 };
+
+// How a launch's (cell, frame) items are shared out among its workgroups (wofdm_work_split).
+//   equal split:  workgroup b runs head_q consecutive items, one more if b < head_r (total / grid and total % grid): all there is
+//                 to a launch that is not `dynamic`, or has no more items than workgroups;
+//   dynamic:      a static head of head_q = alpha_256 / 256 of total / grid items per workgroup, and behind the heads a tail,
+//                 [tail0, total), that the workgroups take in chunks of `chunk` items, first come first served
+//                 (wofdm_frames_kernel: take_chunk).
+// launch() makes a launch dynamic where that pays: more than one workgroup per CU -- those do not run at one rate, DESIGN.md
+// section 4; one workgroup per CU has nothing to even out and N = 512 lost 5 % to the chunks' barriers -- and at least
+// WOFDM_SPLIT_MIN_ITEMS items per workgroup: a grab costs a workgroup about as much as a fifth of a frame, and a tail of a few
+// chunks evens out nothing (launches of 80 ... 125 items per workgroup lost 3 ... 8 %, those of 977 and 1 953 gained 7 % and
+// 5 %; nothing in between has been measured: profiles/work_split.txt).
+// The instantiations that hold the hand-out's code, and so can be given a tail: the layouts of the plain and allocation variants
+// that run with several workgroups per CU (10, 11: N = 256; 13, 14, 16: N = 64, 128), and layout 12 at N = 512 (one workgroup per
+// CU: a tail only under the developer override).  Every other kernel is compiled as it was with equal shares.
+static constexpr bool wofdm_layout_dynamic(int layout, int n_fft)
+{
+    return layout == 10 || layout == 11 || layout == 13 || layout == 14 || layout == 16 || (layout == 12 && n_fft == 512);
+}
+#define WOFDM_SPLIT_ALPHA_256 192     // 3/4 static; the chunked quarter absorbs the spread of the workgroups' rates
+#define WOFDM_SPLIT_CHUNK 8           // (both: interleaved A/Bs at C2, profiles/work_split.txt)
+#define WOFDM_SPLIT_MIN_ITEMS 512
+struct wofdm_split { uint64_t head_q, head_r, tail0; uint32_t chunk; };    // chunk 0: no tail
+static inline wofdm_split wofdm_work_split(uint64_t total, uint64_t grid, bool dynamic, uint32_t alpha_256, uint32_t chunk)
+{
+    const uint64_t q = total / grid;
+    if (!dynamic || total <= grid) return {q, total % grid, total, 0u};
+    // (q * alpha in two parts: q may take all 64 bits' worth of frames_per_cell * cells / grid)
+    const uint64_t head = (q >> 8) * alpha_256 + (((q & 255u) * alpha_256) >> 8);
+    return {head, 0u, head * grid, chunk};
+}
 
 // DFT lengths from which the generated unit noise is parked in HBM scratch between the FIR and
 // the noise-scaling phase instead of registers

@@ -783,6 +783,24 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
     DELAY_AT(11);
     for (int i = tid; i < gm[WOFDM_G_FBUF]; i += blockDim.x) fbuf[i] = mk(0.f, 0.f);
     if (tid < 64) flags[tid] = 0;
+    // the idle words 17 ... 19, 21 ... 23, 28 ... 31: what handing out the tail of the launch's items needs (take_chunk below)
+    enum { WS_OFF_LO = 17, WS_OFF_HI = 18,         // what the work counter gave last: items of the tail handed out before
+           WS_CHUNK = 19,                          // items per chunk; 0: the launch has no tail
+           WS_LEFT_LO = 21, WS_LEFT_HI = 22,       // items of the tail
+           WS_TAIL0_LO = 23, WS_TAIL0_HI = 28,     // its first item
+           WS_WORK_LO = 29, WS_WORK_HI = 30,       // the work counter's address
+           WS_CELL0 = 31 };                        // first cell of the launch
+    // (compiled into the kernels that can be given a tail, wofdm_layout_dynamic: the others keep the loop control they had with
+    // equal shares -- the build table's SET of kernels with scratch is left as it was; registers moved a little in a sixth of them)
+    constexpr bool DYN = !DUMP && wofdm_layout_dynamic(LAY, N);
+    if (DYN && tid == 0) {
+        const uint64_t left = p.total - p.tail0, wp = (uint64_t)(uintptr_t)p.work;
+        flags[WS_CHUNK] = (int)p.chunk;
+        flags[WS_LEFT_LO] = (int)(uint32_t)left; flags[WS_LEFT_HI] = (int)(uint32_t)(left >> 32);
+        flags[WS_TAIL0_LO] = (int)(uint32_t)p.tail0; flags[WS_TAIL0_HI] = (int)(uint32_t)(p.tail0 >> 32);
+        flags[WS_WORK_LO] = (int)(uint32_t)wp; flags[WS_WORK_HI] = (int)(uint32_t)(wp >> 32);
+        flags[WS_CELL0] = (int)p.first_cell;
+    }
     if (tid < 64) sums[tid] = 0.f;                 // (waves a short frame does not have leave their partial sums at zero)
     int iter = 0;                                  // frames this workgroup has started
     if constexpr (MDS) {
@@ -851,31 +869,67 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
     constexpr int bps = N * ks / 128;             // Philox blocks of data bits per symbol
     static_assert(SPW * bps <= 64, "data-bit blocks of a wave must fit one pass");
 
-    // Work items (cell, frame), cell-major: every workgroup takes one CONTIGUOUS run of them
-    // (items_q or items_q + 1 items), so that it stays on a cell for as many frames as possible --
-    // with the reference's 100 frames per cell a grid-strided walk would change cell (counter
-    // flush, channel taps, noise level) on every single frame.  One 64-bit divide per workgroup
-    // here; the loop itself steps with scalar adds and compares only.
+    // Work items (cell, frame), cell-major.  Every workgroup starts with one CONTIGUOUS run of them (head_q items, one more
+    // for the first head_r workgroups: wofdm_work_split), so that it stays on a cell for as many frames as possible -- with the reference's
+    // 100 frames per cell a grid-strided walk would change cell (counter flush, channel taps, noise level) on every single
+    // frame.  The items behind these runs, [tail0, total) -- none in a short launch --, are handed out in chunks of `chunk` consecutive items by one
+    // atomicAdd on the plan's work counter each, which evens out the end of the launch: the workgroups of a CU do not run at one
+    // rate (the SIMD arbiter favours the oldest), and with equal shares the first to finish left its wave slots empty until the
+    // last was through (profiles/work_split.txt).  One 64-bit divide per run or chunk (seek); the loop
+    // itself steps with scalar adds and compares only.
+    // What the hand-out needs lives in the LDS words WS_* (written once, above), not in registers: held across the frame loop
+    // the launch parameters alone cost the C2 kernel 16 more spilled SGPRs and 12 VGPRs.
     const uint64_t F = p.frames_per_cell;
-    const uint64_t bq = blockIdx.x;
-    const uint64_t item0 = bq * p.items_q + (bq < p.items_r ? bq : p.items_r);
-    uint64_t n_items = p.items_q + (bq < p.items_r ? 1u : 0u);
-    const uint32_t cell_rel = (uint32_t)(item0 / F);
-    uint32_t cell = __builtin_amdgcn_readfirstlane(p.first_cell + cell_rel);
-    uint64_t fidx = item0 - (uint64_t)cell_rel * F;
-    {
+    const int n_ch = gm[WOFDM_G_NCH], n_snr = gm[WOFDM_G_NSNR];
+    uint64_t n_items = p.head_q + (blockIdx.x < p.head_r ? 1u : 0u), fidx = 0;
+    uint32_t cell = 0;
+    int ch = 0, sn = 0, pair = 0;
+    auto ws_get = [&](int i) { return __builtin_amdgcn_readfirstlane((uint32_t)flags[i]); };
+    auto ws_get64 = [&](int lo, int hi) { return ((uint64_t)ws_get(hi) << 32) | ws_get(lo); };
+    auto seek = [&](uint64_t item, uint32_t first_cell) {
+        // (opaque copies of the divisors: what a division prepares from its divisor alone would otherwise be computed in
+        // front of the frame loop and held in registers across it)
+        uint32_t f_lo = (uint32_t)F, f_hi = (uint32_t)(F >> 32);
+        uint32_t nc = (uint32_t)n_ch, ns = (uint32_t)n_snr;
+        if constexpr (DYN) asm volatile("" : "+s"(f_lo), "+s"(f_hi), "+s"(nc), "+s"(ns));
+        const uint64_t Fd = ((uint64_t)f_hi << 32) | f_lo;
+        const uint32_t cell_rel = (uint32_t)(item / Fd);
+        cell = __builtin_amdgcn_readfirstlane(first_cell + cell_rel);
+        fidx = item - (uint64_t)cell_rel * Fd;
         const uint32_t flo = __builtin_amdgcn_readfirstlane((uint32_t)fidx);
         const uint32_t fhi = __builtin_amdgcn_readfirstlane((uint32_t)(fidx >> 32));
         fidx = ((uint64_t)fhi << 32) | flo;
-    }
-    const int n_ch = gm[WOFDM_G_NCH], n_snr = gm[WOFDM_G_NSNR];
-    // cell = (pair*n_snr + sn)*n_ch + ch
-    int ch = __builtin_amdgcn_readfirstlane((int)(cell % (uint32_t)n_ch));
-    int sn = __builtin_amdgcn_readfirstlane((int)((cell / (uint32_t)n_ch) % (uint32_t)n_snr));
-    int pair = __builtin_amdgcn_readfirstlane((int)(cell / ((uint32_t)n_ch * (uint32_t)n_snr)));
+        // cell = (pair*n_snr + sn)*n_ch + ch
+        ch = __builtin_amdgcn_readfirstlane((int)(cell % nc));
+        sn = __builtin_amdgcn_readfirstlane((int)((cell / nc) % ns));
+        pair = __builtin_amdgcn_readfirstlane((int)(cell / (nc * ns)));
+    };
+    uint64_t item = (uint64_t)blockIdx.x * p.head_q + (blockIdx.x < p.head_r ? blockIdx.x : p.head_r);   // first of the run
     auto next_cell = [&]() {
         ++cell;
         if (++ch == n_ch) { ch = 0; if (++sn == n_snr) { sn = 0; ++pair; } }
+    };
+    // The next chunk, when the run is used up (a scalar condition: every wave gets here): thread 0 asks the work counter and
+    // all waves read the answer from LDS between two barriers.  Nothing here waits for another workgroup: an answer at or
+    // beyond the end of the tail ends the loop.  (Asking one frame ahead, from inside the frame loop, would take the atomic's
+    // round trip -- about a microsecond per chunk of eight frames -- off the workgroup's path; the frame loop with that
+    // branch in it put 12 more production kernels into scratch, so the frame loop is left as it was.)
+    auto take_chunk = [&](uint32_t chunk) {        // false: nothing left
+        if (tid == 0) {
+            typedef __attribute__((address_space(1))) unsigned long long gu64;
+            gu64 *work = (gu64 *)(((uint64_t)(uint32_t)flags[WS_WORK_HI] << 32) | (uint32_t)flags[WS_WORK_LO]);
+            const unsigned long long off = __hip_atomic_fetch_add(work, (unsigned long long)chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            flags[WS_OFF_LO] = (int)(uint32_t)off;
+            flags[WS_OFF_HI] = (int)(uint32_t)(off >> 32);
+        }
+        __syncthreads();
+        const uint64_t off = ws_get64(WS_OFF_LO, WS_OFF_HI);
+        __syncthreads();
+        const uint64_t left = ws_get64(WS_LEFT_LO, WS_LEFT_HI);
+        if (off >= left) return false;
+        n_items = left - off < (uint64_t)chunk ? left - off : (uint64_t)chunk;
+        item = ws_get64(WS_TAIL0_LO, WS_TAIL0_HI) + off;
+        return true;
     };
 
     const uint32_t seed_lo = __builtin_amdgcn_readfirstlane(p.seed_lo);
@@ -909,6 +963,8 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
     unsigned long long stamp_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long stamp_t = __builtin_amdgcn_s_memtime();
 #endif
+    for (;;) {                                      // the workgroup's runs: the static one, then chunk by chunk (not indented)
+    if constexpr (DYN) seek(item, ws_get(WS_CELL0)); else seek(item, p.first_cell);
     for (; n_items != 0; --n_items) {
         STAMP(7);                                   // loop control, cell changes
         WAVE_PRIO(PRIO_LATENCY);
@@ -3451,6 +3507,14 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         }
         STAMP(6);
         if (++fidx == F) { fidx = 0; next_cell(); }
+    }
+#ifdef WOFDM_STAMP
+    STAMP(7);                                       // (the hand-out counts as loop control)
+#endif
+    if constexpr (DYN) {
+        const uint32_t chunk = ws_get(WS_CHUNK);    // the run is used up
+        if (chunk == 0 || !take_chunk(chunk)) break;
+    } else break;
     }
     if (cur_cell != 0xFFFFFFFFu) flush(cur_cell);
     if constexpr (RELAXF) {
