@@ -187,6 +187,16 @@ int wofdm_plan_info(wofdm_plan *plan, int32_t info[5]);
  * convolution form.  (Test and profiling aid; the results do not depend on it beyond fp32 rounding.) */
 int wofdm_plan_kernel_id(wofdm_plan *plan, int32_t id[2]);
 
+/* Built geometries.  For the seven structures at n_fft = 256, cp = 32 with the reference's tails, 16 symbols per frame, 21 taps and
+ * noise_before_truncate = 1 (ids 1 ... 7: wtx, wrx, WOLA, CPW, CPwtx, CPwrx, CP) the library holds a second build of the plain
+ * generate-mode kernel with the structure lengths as compile-time constants; a plain plan of such a geometry launches it (layouts
+ * 10 and 11; the counters are the same, bit for bit).  wofdm_plan_kernel_geo: *id = the id of the built geometry of the kernel that
+ * wofdm_plan_launch runs, 0 = geometry at run time (any other geometry, allocation and Tx-mask plans, the injected and instrumented
+ * entry points, WOFDM_OPT_GENERIC_GEOMETRY); wofdm_plan_kernel_id does not depend on it.  wofdm_cfg_geo_id: the id of cfg's
+ * geometry (every length equal to a built one's), 0 if none, a negative error for an invalid cfg; host only, no device needed. */
+int wofdm_plan_kernel_geo(wofdm_plan *plan, int32_t *id);
+int wofdm_cfg_geo_id(const wofdm_cfg *cfg);
+
 /* Diagnostic choice among the kernels of the family (A/B measurements and the tests; the results do not depend
  * on it beyond fp32 rounding, the defaults are the fastest kernels).  Takes effect for the launches that follow;
  * returns WOFDM_E_UNSUPPORTED -- and leaves the plan as it was -- when no kernel fits the geometry under the option.
@@ -198,11 +208,14 @@ int wofdm_plan_kernel_id(wofdm_plan *plan, int32_t id[2]);
  *   WOFDM_OPT_DFT_VALU       1 = the 256-point IDFT / DFT (dftmtx, main_BER_calculation.m:306, 370) as in-register radix-16
  *                            stages on the VALU (layouts 6, 7) instead of split-f16 products on the matrix pipe (layouts
  *                            10, 11); likewise n_fft = 512, 1024 (8 instead of 12), 64, 128 (2 instead of 13, 14, 16) and the Tx-mask
- *                            kernel at n_fft = 256 (9 instead of 15); 0 = default */
+ *                            kernel at n_fft = 256 (9 instead of 15); 0 = default
+ *   WOFDM_OPT_GENERIC_GEOMETRY 1 = the kernel that reads the structure lengths at run time also where the geometry is a built one
+ *                            (wofdm_plan_kernel_geo then reports 0; identical results); 0 = default */
 #define WOFDM_OPT_FIR_VALU       0
 #define WOFDM_OPT_MAX_SPW        1
 #define WOFDM_OPT_TXMASK_DIRECT  2
 #define WOFDM_OPT_DFT_VALU       3
+#define WOFDM_OPT_GENERIC_GEOMETRY 4
 int wofdm_plan_set_option(wofdm_plan *plan, int32_t option, int32_t value);
 
 /* One-shot, host pointers in / host counters out (synchronous):

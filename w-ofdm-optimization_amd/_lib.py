@@ -19,7 +19,7 @@ WOFDM_OK = 0
 ERRORS = {-1: "WOFDM_E_INVALID", -2: "WOFDM_E_UNSUPPORTED", -3: "WOFDM_E_HIP", -4: "WOFDM_E_NOMEM"}
 MAX_TAPS = 21
 #: wofdm_plan_set_option: diagnostic kernel choice (include/wofdm.h)
-OPTIONS = {"fir_valu": 0, "max_spw": 1, "txmask_direct": 2, "dft_valu": 3}
+OPTIONS = {"fir_valu": 0, "max_spw": 1, "txmask_direct": 2, "dft_valu": 3, "generic_geometry": 4}
 MAX_SYMS = 16
 #: wofdm_tx_papr (include/wofdm.h): device-memory budget of a chunk of frames, most periods the `periods` output takes
 TX_PAPR_CHUNK_BYTES = 256 << 20
@@ -36,7 +36,7 @@ EXPORTS = (
     "wofdm_plan_set_tx_mask", "wofdm_plan_status", "wofdm_plan_kernel_id", "wofdm_plan_set_option",
     "wofdm_interference", "wofdm_tx_psd", "wofdm_tx_psd_batch", "wofdm_tx_psd_batch_masked",
     "wofdm_interference_masked", "wofdm_tx_papr", "wofdm_tx_papr_kernel_ms",
-    "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms",
+    "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms", "wofdm_plan_kernel_geo", "wofdm_cfg_geo_id",
 )
 
 
@@ -130,6 +130,8 @@ def load():
     L.wofdm_plan_dump_frame.argtypes = [vp, C.c_uint32, u64, vp, vp, vp, C.POINTER(Dump)]
     L.wofdm_plan_info.argtypes = [vp, vp]
     L.wofdm_plan_kernel_id.argtypes = [vp, vp]
+    L.wofdm_plan_kernel_geo.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.wofdm_cfg_geo_id.argtypes = [C.POINTER(Cfg)]
     L.wofdm_plan_set_allocation.argtypes = [vp, vp]
     L.wofdm_plan_set_tx_mask.argtypes = [vp, vp]
     L.wofdm_plan_status.argtypes = [vp]

@@ -21,7 +21,9 @@ gfx950 code object of the library:
  6. no kernel of the library contains a flat_* instruction (LDS words are ds_read / ds_write).
 
 The layouts are described in wofdm_kernel.h (wofdm_layout_info); MDFT_LAYOUTS below are those whose transforms run on the
-matrix pipe.  tests/test_code_layout.py runs the same scan.
+matrix pipe.  The kernels with a built geometry (wofdm_geo_table, last template argument > 0) are checked as every other; the
+summary counts them on their own ("geo_kernels"), so that "kernels" and "mdft_kernels" stay the generic family's.
+tests/test_code_layout.py runs the same scan.
 """
 import os
 import re
@@ -151,9 +153,16 @@ def is_mdft(fn):
     return bool(m) and int(m.group(1)) in MDFT_LAYOUTS
 
 
+def geo_id(fn):
+    """id of the built geometry of a frame kernel (seventh template argument of wofdm_frames_kernel); 0: geometry at run time"""
+    m = re.search(r"wofdm_frames_kernelILi\d+ELi\dELi\d+ELb\dELb\dELi\dELi(\d+)E", fn)
+    return int(m.group(1)) if m else 0
+
+
 def verify(lib):
     """-> (list of violation strings, summary dict)"""
-    bad, summ = [], {"kernels": 0, "chains": 0, "mdft_kernels": 0, "kernels_with_swizzles": 0, "write_to_mfma_states": {}}
+    bad, summ = [], {"kernels": 0, "chains": 0, "mdft_kernels": 0, "kernels_with_swizzles": 0, "write_to_mfma_states": {},
+                      "geo_kernels": 0}
     with tempfile.TemporaryDirectory() as tmp:
         for co in code_objects(lib, tmp):
             r = scan(co)
@@ -175,12 +184,13 @@ def verify(lib):
                 elif a // 64 != (b - 1) // 64:
                     bad.append("MFMA chain at %#x crosses a 64-byte line in %s" % (a, fn[:90]))
             for fn, n in r["flat"].items():
-                summ["kernels"] += "wofdm_frames_kernel" in fn
+                summ["kernels"] += "wofdm_frames_kernel" in fn and not geo_id(fn)
+                summ["geo_kernels"] += geo_id(fn) > 0
                 if n:
                     bad.append("%d flat_* instruction(s) in %s" % (n, fn[:90]))
             for fn, n in r["swz"].items():
                 if is_mdft(fn):
-                    summ["mdft_kernels"] += 1
+                    summ["mdft_kernels"] += not geo_id(fn)
                     if n:
                         bad.append("%d op_sel-swizzled v_pk_* instruction(s) in the matrix-pipe kernel %s" % (n, fn[:90]))
                 elif "wofdm_frames_kernel" in fn and n:
@@ -204,7 +214,8 @@ def main(argv):
         print("verify_code_layout: %d violation(s) in %s -- the library must not be used" % (len(bad), argv[1]), file=sys.stderr)
         return 1
     print("verify_code_layout: %d kernels, %d six-MFMA chains in one cache line each, %d matrix-pipe kernels without swizzled "
-          "packed arithmetic: ok" % (summ["kernels"], summ["chains"], summ["mdft_kernels"]))
+          "packed arithmetic, %d kernels with a built geometry: ok"
+          % (summ["kernels"], summ["chains"], summ["mdft_kernels"], summ["geo_kernels"]))
     return 0
 
 

@@ -103,6 +103,8 @@ struct wofdm_plan {
     bool fir_valu = false;             // WOFDM_OPT_FIR_VALU: FIR on the VALU in every layout
     bool dft_valu = false;             // WOFDM_OPT_DFT_VALU: N = 256 transforms on the VALU (layouts 6, 7 instead of 10, 11)
     int max_spw = 0;                   // WOFDM_OPT_MAX_SPW: 0 = no cap
+    bool generic_geo = false;          // WOFDM_OPT_GENERIC_GEOMETRY: never a kernel with the geometry built in
+    int geo = 0;                       // id of the built geometry of fn[WOFDM_MODE_GEN] (wofdm_geo_table); 0: geometry at run time
     uint32_t *d_amask = nullptr;       // [N/4] words, byte r bit 7: subcarrier j + r N/4 not loaded
     float2 *d_tmask = nullptr;         // [2P-1] circular impulse response of the Tx mask
     float2 *d_tspec = nullptr;         // [WOFDM_TXFFT_LEN] its fast-convolution spectrum (FFT form)
@@ -132,6 +134,12 @@ size_t wofdm_amask_words(int N)
 {
     const size_t NQ = (size_t)N / 4;
     return N == 256 ? 2 * NQ + 256 : NQ + (NQ > 256 ? NQ : 256);
+}
+
+// id of the geometry in wofdm_geo_table (every field equal), else 0
+int geo_id_of(const geom &g)
+{
+    return wofdm_geo_id(wofdm_geo_row{g.N, g.S, g.mu, g.rho, g.beta, g.delta, g.gamma, g.kappa, g.L, g.P, g.B, g.T, g.NL});
 }
 
 // Select the kernel variant from the plan's options and size everything that depends on it
@@ -178,18 +186,34 @@ int configure(wofdm_plan *pl)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn[m]),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
+    // Generate mode of a plain plan whose geometry is a row of wofdm_geo_table: the kernel with that row's lengths built in (the
+    // same statements on the same operands, so the same counters; WOFDM_OPT_GENERIC_GEOMETRY keeps the generic kernel).  Injected,
+    // instrumented, allocation and masked plans keep the generic kernels.
+    int geo = 0;
+    if (var == WOFDM_VAR_PLAIN && (layout == 10 || layout == 11) && !pl->generic_geo) {
+        geo = geo_id_of(g);
+        if (geo && wofdm_geo_layout(geo) != layout) geo = 0;
+        if (geo && !wofdm_geo_unit_matches(g.N, g.k)) geo = 0;      // (the generic unit is another build of the source: its kernels run)
+    }
+    if (geo) {
+        fn[WOFDM_MODE_GEN] = wofdm_select_kernel_geo(g.N, g.k, geo);
+        if (!fn[WOFDM_MODE_GEN])
+            return fail(WOFDM_E_UNSUPPORTED, "no kernel for the built geometry %d at n_fft=%d bits_per_sc=%d", geo, g.N, g.k);
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn[WOFDM_MODE_GEN]),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
     int occ = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
         &occ, reinterpret_cast<const void *>(fn[WOFDM_MODE_GEN]), 64 * wofdm_waves(layout, g.N, g.S, g.B), lds));
     if (occ < 1) return fail(WOFDM_E_UNSUPPORTED, "kernel does not fit a CU (LDS %u bytes)", lds);
-    // (the LDS goes in units of 5 120 bytes, which the occupancy API does not know: wofdm_lds_workgroups_per_cu)
+    // (the LDS goes in units of 1 280 bytes (WOFDM_LDS_GRANULE), which the occupancy API does not know: wofdm_lds_workgroups_per_cu)
     if (occ > wofdm_lds_workgroups_per_cu(lds)) occ = wofdm_lds_workgroups_per_cu(lds);
     const int fbuf = wofdm_fbuf_len(g.N, g.T, layout, g.S, g.B);
     HIP_TRY(hipMemcpy(pl->d_geo + WOFDM_G_FBUF, &fbuf, sizeof(int), hipMemcpyHostToDevice));
     const int spwr = wofdm_spwr(layout, g.N, g.S, g.B);
     HIP_TRY(hipMemcpy(pl->d_geo + WOFDM_G_SPWR, &spwr, sizeof(int), hipMemcpyHostToDevice));
     for (int m = 0; m < 4; ++m) pl->fn[m] = fn[m];
-    pl->var = var; pl->layout = layout; pl->occ = occ; pl->base.lds_bytes = lds;
+    pl->var = var; pl->layout = layout; pl->geo = geo; pl->occ = occ; pl->base.lds_bytes = lds;
     // scale of the on-air samples inside the kernel (wofdm_kparams): 1/N of the IDFT, times the
     // f16 centring of the matrix-pipe layouts
     const bool fm = wofdm_layout_info(layout, g.N).fir != WOFDM_FIR_VALU;
@@ -798,7 +822,7 @@ int wofdm_plan_set_option(wofdm_plan *pl, int32_t option, int32_t value)
     if (!pl) return fail(WOFDM_E_INVALID, "plan is NULL");
     HIP_TRY(hipSetDevice(pl->device));
     HIP_TRY(hipDeviceSynchronize());           // no launch of this plan may still be running on the old choice
-    const bool direct = pl->force_direct_mask, valu = pl->fir_valu, dvalu = pl->dft_valu;
+    const bool direct = pl->force_direct_mask, valu = pl->fir_valu, dvalu = pl->dft_valu, ggeo = pl->generic_geo;
     const int cap = pl->max_spw;
     switch (option) {
     case WOFDM_OPT_FIR_VALU: pl->fir_valu = value != 0; break;
@@ -809,10 +833,11 @@ int wofdm_plan_set_option(wofdm_plan *pl, int32_t option, int32_t value)
         break;
     case WOFDM_OPT_TXMASK_DIRECT: pl->force_direct_mask = value != 0; break;
     case WOFDM_OPT_DFT_VALU: pl->dft_valu = value != 0; break;
+    case WOFDM_OPT_GENERIC_GEOMETRY: pl->generic_geo = value != 0; break;
     default: return fail(WOFDM_E_INVALID, "unknown option %d", (int)option);
     }
     const int rc = configure(pl);
-    if (rc != WOFDM_OK) { pl->force_direct_mask = direct; pl->fir_valu = valu; pl->max_spw = cap; pl->dft_valu = dvalu; }
+    if (rc != WOFDM_OK) { pl->force_direct_mask = direct; pl->fir_valu = valu; pl->max_spw = cap; pl->dft_valu = dvalu; pl->generic_geo = ggeo; }
     // (the noise scratch rows are sized per layout: a forced grid in launch() regrows them, a new layout here)
     if (rc == WOFDM_OK) {
         const size_t row = wofdm_noise_scratch_len(pl->g.N, pl->layout);
@@ -861,6 +886,20 @@ int wofdm_plan_kernel_id(wofdm_plan *pl, int32_t id[2])
     id[0] = pl->layout;
     id[1] = pl->var;
     return WOFDM_OK;
+}
+
+int wofdm_plan_kernel_geo(wofdm_plan *pl, int32_t *id)
+{
+    if (!pl || !id) return fail(WOFDM_E_INVALID, "NULL argument");
+    *id = pl->geo;
+    return WOFDM_OK;
+}
+
+int wofdm_cfg_geo_id(const wofdm_cfg *cfg)
+{
+    geom g;
+    const int rc = check_cfg(cfg, &g);
+    return rc != WOFDM_OK ? rc : geo_id_of(g);
 }
 
 int wofdm_plan_launch(wofdm_plan *pl, uint64_t frame_offset, uint64_t frames_per_cell,

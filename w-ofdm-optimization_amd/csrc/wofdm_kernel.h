@@ -197,11 +197,11 @@ static constexpr wofdm_layout wofdm_layout_info(int id, int n_fft)
 }
 #define WOFDM_FIR8_VT 48      // words per plane of layout 8's virtual row behind the last symbol
 #define WOFDM_FIRM_PRE 24     // zero samples in front of the frame in the f16 planes (taps - 1 <= 24, 16-byte rows)
-static inline int wofdm_rb(int n_fft, int layout = 1) { return wofdm_layout_info(layout, n_fft).rb; }
+static constexpr int wofdm_rb(int n_fft, int layout = 1) { return wofdm_layout_info(layout, n_fft).rb; }
 // Layout 16: the symbols a wave takes -- the frame spread evenly over the fewest waves (at most four) whose share, rounded up to
 // an even count (a wave's rows are split between the two f16 planes), fits the 1024 / N symbol slots and the ten tiles of a
 // wave; 0: none fits.  The last wave takes what is left (S - (W - 1) spwr symbols, any count >= 1).
-static inline int wofdm_small_spwr(int n_fft, int S, int B)
+static constexpr int wofdm_small_spwr(int n_fft, int S, int B)
 {
     const int slots = 1024 / n_fft;
     for (int W = 1; W <= 4; ++W) {
@@ -211,12 +211,12 @@ static inline int wofdm_small_spwr(int n_fft, int S, int B)
     return 0;
 }
 // symbols per wave as the kernel of `layout` runs this geometry, and the waves of its workgroup
-static inline int wofdm_spwr(int layout, int n_fft, int S, int B)
+static constexpr int wofdm_spwr(int layout, int n_fft, int S, int B)
 {
     const wofdm_layout li = wofdm_layout_info(layout, n_fft);
     return li.partial ? wofdm_small_spwr(n_fft, S, B) : li.spw;
 }
-static inline int wofdm_waves(int layout, int n_fft, int S, int B)
+static constexpr int wofdm_waves(int layout, int n_fft, int S, int B)
 {
     const int r = wofdm_spwr(layout, n_fft, S, B);
     return r > 0 ? (S + r - 1) / r : 0;
@@ -224,7 +224,7 @@ static inline int wofdm_waves(int layout, int n_fft, int S, int B)
 // Layout of the plain and allocation variants: four symbols per wave at N = 256 (quarter-wave layouts, S a multiple of 4,
 // four symbols within the FIR outputs of a wave), the matrix-pipe layouts 13 / 14 / 16 at N = 64, 128 and 12 / 8 at N >= 512
 // where they fit, else two symbols per wave where the register budget allows it (N <= 256) and S is even, else one.
-static inline int wofdm_pick_layout(int n_fft, int S, int B, bool plain = false, bool firm = true, bool mdft = true)
+static constexpr int wofdm_pick_layout(int n_fft, int S, int B, bool plain = false, bool firm = true, bool mdft = true)
 {
     // (the matrix-pipe kernels take a stride of at least n_fft for granted: their tiles below SPW n_fft
     // samples carry no validity tests)
@@ -264,7 +264,7 @@ static inline size_t wofdm_noise_scratch_len(int n_fft, int layout)
 // float2 elements of the frame buffer.  Matrix-pipe layouts: the same bytes hold two planes of
 // packed-f16 words (hi and lo halves of every sample), each `len` words long: 24 zeros, the frame,
 // and zeros up to the end of the tile that covers the trailing samples behind the last wave.
-static inline int wofdm_fbuf_len(int N, int T, int layout, int S = 0, int B = 0)
+static constexpr int wofdm_fbuf_len(int N, int T, int layout, int S = 0, int B = 0)
 {
     const wofdm_layout li = wofdm_layout_info(layout, N);
     // (behind the last wave's first sample: its tiles and one more of zeros; layout 16: the last wave starts at (W - 1) spwr B)
@@ -300,6 +300,46 @@ static inline unsigned wofdm_lds_bytes(int N, int T, int layout, int S, int B)
     // (layout 15, behind the fall tails: 16 bytes of alignment, a row of 344 samples per wave for the mask stage's spill, and 64 spare
     // bytes at the very end -- the target of the mask stage's stores that have no output)
     return (unsigned)(fixed + 8 * wofdm_fbuf_len(N, T, layout, S, B) + 8 * S * beta + (layout == 15 ? 16 + S * 344 * 8 + 64 : 0));
+}
+
+// ---- Built geometries ----
+// The frame kernel reads its structure lengths from a device array, again in every phase (GEO_PHASE in wofdm_kernel.hip): they are
+// run-time values to it.  For the geometries of this table the generate-mode, production, plain kernels of N = 256 are built a
+// second time with the row's lengths as compile-time constants (template parameter GEO of wofdm_frames_kernel = the row's id =
+// its index + 1; id 0 = geometry at run time, every other kernel).  n_snr, n_channels and everything per cell stay run-time values.
+// Rows: the seven structures (variants.py: wtx, wrx, WOLA, CPW, CPwtx, CPwrx, CP) at N = 256, CP 32, the reference's tails, 16
+// symbols per frame, 21 taps, noise_before_truncate = 1.  A row whose kernel fails the build's static checks, spills to scratch, takes
+// more than 168 VGPRs or loses the third workgroup per CU is taken out of the table and runs generic (profiles/kernel_table_geo.json).
+// (The "// <id> <name>" comment of each row is read as data: tools/kernel_table.py and the tests take the rows' structure names from it.
+// Taking a row out renumbers the rows below it: renumber their comments and regenerate profiles/kernel_table_geo.json.)
+struct wofdm_geo_row { int n_fft, S, mu, rho, beta, delta, gamma, kappa, L, P, B, T, NL; };
+#define WOFDM_GEO_COUNT 7
+static constexpr wofdm_geo_row wofdm_geo_table[WOFDM_GEO_COUNT] = {
+    //N   S   mu  rho beta delta gamma kappa L   P    B    T     NL
+    {256, 16, 32, 8,  8,   0,    32,   0,    21, 296, 288, 4616, 4636},   // 1 wtx
+    {256, 16, 32, 5,  0,   10,   27,   0,    21, 293, 293, 4688, 4708},   // 2 wrx
+    {256, 16, 32, 8,  8,   10,   22,   5,    21, 296, 288, 4616, 4636},   // 3 WOLA
+    {256, 16, 32, 13, 8,   10,   27,   0,    21, 301, 293, 4696, 4716},   // 4 CPW
+    {256, 16, 32, 0,  8,   0,    24,   8,    21, 288, 280, 4488, 4508},   // 5 CPwtx
+    {256, 16, 32, 0,  0,   10,   22,   5,    21, 288, 288, 4608, 4628},   // 6 CPwrx
+    {256, 16, 32, 0,  0,   0,    32,   0,    21, 288, 288, 4608, 4628},   // 7 CP
+};
+static constexpr wofdm_geo_row wofdm_geo_row_of(int id) { return id >= 1 && id <= WOFDM_GEO_COUNT ? wofdm_geo_table[id - 1] : wofdm_geo_row{}; }
+// the layout a row's kernel is built as (what wofdm_pick_layout gives the geometry under the default options)
+static constexpr int wofdm_geo_layout(int id)
+{
+    return id >= 1 && id <= WOFDM_GEO_COUNT ? wofdm_pick_layout(wofdm_geo_table[id - 1].n_fft, wofdm_geo_table[id - 1].S, wofdm_geo_table[id - 1].B, true) : 0;
+}
+// id of a geometry: every field equal to a row's, else 0
+static constexpr int wofdm_geo_id(const wofdm_geo_row &g)
+{
+    for (int i = 0; i < WOFDM_GEO_COUNT; ++i) {
+        const wofdm_geo_row &r = wofdm_geo_table[i];
+        if (r.n_fft == g.n_fft && r.S == g.S && r.mu == g.mu && r.rho == g.rho && r.beta == g.beta && r.delta == g.delta
+            && r.gamma == g.gamma && r.kappa == g.kappa && r.L == g.L && r.P == g.P && r.B == g.B && r.T == g.T && r.NL == g.NL)
+            return i + 1;
+    }
+    return 0;
 }
 
 // kernel registry (wofdm_kernel.hip)
@@ -374,6 +414,37 @@ static inline wofdm_kernel_fn wofdm_select_kernel(int n_fft, int bits_per_sc, in
     if (n_fft == 1024 && bits_per_sc == 4) return wofdm_select_kernel_n1024_k4(layout, mode, var);
     if (n_fft == 1024 && bits_per_sc == 6) return wofdm_select_kernel_n1024_k6(layout, mode, var);
     return nullptr;
+}
+// the kernels of the built geometries (wofdm_geo_table): wofdm_frames_kernel<256, k, wofdm_geo_layout(geo), false, false, 0, geo>,
+// in translation units of their own (wofdm_kernel.hip with -DWOFDM_TU_GEO -DWOFDM_TU_N=256 -DWOFDM_TU_K=<k>: a kernel's register
+// allocation answers to what is compiled beside it, and the generic kernels are to come out as they are); nullptr: none built
+wofdm_kernel_fn wofdm_select_kernel_geo_n256_k2(int geo);
+wofdm_kernel_fn wofdm_select_kernel_geo_n256_k4(int geo);
+wofdm_kernel_fn wofdm_select_kernel_geo_n256_k6(int geo);
+static inline wofdm_kernel_fn wofdm_select_kernel_geo(int n_fft, int bits_per_sc, int geo)
+{
+    if (n_fft == 256 && bits_per_sc == 2) return wofdm_select_kernel_geo_n256_k2(geo);
+    if (n_fft == 256 && bits_per_sc == 4) return wofdm_select_kernel_geo_n256_k4(geo);
+    if (n_fft == 256 && bits_per_sc == 6) return wofdm_select_kernel_geo_n256_k6(geo);
+    return nullptr;
+}
+// which build of wofdm_kernel.hip a unit is (WOFDM_UNIT_BUILD there; 0 = the product's): the generic unit of (N, k) and the unit of
+// its built geometries.  configure() takes a built geometry's kernel only where the two agree -- a library with one generic unit
+// swapped for another build (tests/native: the fault-injected one) then runs that unit's kernels, as it means to.
+// (Why here and not in that library's Makefile: it links the product's wofdm_kernel_n*_k*.o by wildcard, the *_geo.o units with them,
+// and the rule must hold for any such library -- a developer variant too -- without each of them knowing which units to swap in pairs.)
+int wofdm_kernel_unit_build_n256_k2(void);
+int wofdm_kernel_unit_build_n256_k4(void);
+int wofdm_kernel_unit_build_n256_k6(void);
+int wofdm_kernel_geo_unit_build_n256_k2(void);
+int wofdm_kernel_geo_unit_build_n256_k4(void);
+int wofdm_kernel_geo_unit_build_n256_k6(void);
+static inline bool wofdm_geo_unit_matches(int n_fft, int bits_per_sc)
+{
+    if (n_fft == 256 && bits_per_sc == 2) return wofdm_kernel_unit_build_n256_k2() == wofdm_kernel_geo_unit_build_n256_k2();
+    if (n_fft == 256 && bits_per_sc == 4) return wofdm_kernel_unit_build_n256_k4() == wofdm_kernel_geo_unit_build_n256_k4();
+    if (n_fft == 256 && bits_per_sc == 6) return wofdm_kernel_unit_build_n256_k6() == wofdm_kernel_geo_unit_build_n256_k6();
+    return false;
 }
 hipError_t wofdm_philox_kat_launch(const uint32_t *ctr_key_dev, uint32_t *out_dev, hipStream_t s);
 

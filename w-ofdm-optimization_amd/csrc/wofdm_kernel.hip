@@ -48,6 +48,11 @@
 #ifndef WOFDM_FAULT_SKIP_FLAG
 #define WOFDM_FAULT_SKIP_FLAG 0
 #endif
+// What a unit reports as its build (wofdm_kernel_unit_build_n<N>_k<k>, at the end of this file): 0 = the product's statements, anything
+// else = a build that computes something else on purpose.  A unit of built geometries is used only beside a generic unit of the
+// same build, so a library that swaps in one unit of another build (libwofdm_hip_fault.so does) runs that unit's kernels and not
+// the product's specialised ones in their place.
+#define WOFDM_UNIT_BUILD (WOFDM_FAULT_SKIP_FLAG ? 1 : 0)
 
 // N = 1024: the unit noise of every tile stays in registers instead of being parked in the HBM scratch row (see phase B), since
 // the end of round 4: with the transforms on the matrix pipe the kernel holds FIR outputs and noise of all nine tiles at 128 registers
@@ -652,18 +657,49 @@ template <int N, int LAY> struct fir_geo {
     static constexpr int CH = RB <= 6 ? RB : (RB % 5 == 0 ? 5 : 6);
 };
 
+// The structure lengths as the kernel sees them (gm, gq, gqc below).  GEO = 0: the device array behind the kernel's argument,
+// read by scalar loads.  GEO > 0 (a row of wofdm_geo_table): the row's lengths as constants -- nothing is loaded, the row
+// addresses, the "last symbol" tests and the tile bounds fold, and of every pair of instantiations a phase chooses between
+// (body_tail, all_full, rx_part, the prefix bound, the folded Rx pass) one is left; the per-launch entries (n_snr, n_channels)
+// and the entries of the other variants come from memory as before.
+template <int GEO, int LAY> struct geo_vals {
+    const int *__restrict__ p;
+    __device__ __forceinline__ int operator[](int i) const
+    {
+        if constexpr (GEO > 0) {
+            constexpr wofdm_geo_row R = wofdm_geo_row_of(GEO);
+            switch (i) {
+            case WOFDM_G_S: return R.S; case WOFDM_G_MU: return R.mu; case WOFDM_G_RHO: return R.rho; case WOFDM_G_BETA: return R.beta;
+            case WOFDM_G_DELTA: return R.delta; case WOFDM_G_GAMMA: return R.gamma; case WOFDM_G_KAPPA: return R.kappa;
+            case WOFDM_G_L: return R.L; case WOFDM_G_P: return R.P; case WOFDM_G_B: return R.B; case WOFDM_G_T: return R.T;
+            case WOFDM_G_NL: return R.NL; case WOFDM_G_FBUF: return wofdm_fbuf_len(R.n_fft, R.T, LAY, R.S, R.B);
+            case WOFDM_G_SPWR: return wofdm_spwr(LAY, R.n_fft, R.S, R.B);
+            default: return p[i];
+            }
+        } else return p[i];
+    }
+    __device__ __forceinline__ geo_vals operator+(int o) const { return geo_vals{p + o}; }
+};
+
 // VAR: 0 = every subcarrier loaded (main_BER_calculation.m); 1 = subcarrier allocation: only the
 // bins flagged in g_amask carry data, the others transmit zero and are not counted
 // (main_channel_mask.m:387-390, 367-371); 2 = allocation + the per-symbol spectral Tx mask
 // dft_rc_filt (main_channel_mask.m:398-417), g_tmask = its length-(2P-1) circular impulse response
-template <int N, int K, int LAY, bool INJECT, bool DUMP, int VAR>
+
+// GEO: 0 = the structure lengths at run time; > 0 = those of row GEO of wofdm_geo_table as constants (geo_vals above)
+template <int N, int K, int LAY, bool INJECT, bool DUMP, int VAR, int GEO = 0>
 __global__ void __launch_bounds__(wofdm_layout_info(LAY, N).wg, wofdm_layout_info(LAY, N).min_waves)
 wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                     const float *__restrict__ g_wrx, const float2 *__restrict__ g_h_,
-                    const float *__restrict__ g_nlin, const int *__restrict__ gm,
+                    const float *__restrict__ g_nlin, const int *__restrict__ gm_,
                     const uint32_t *__restrict__ g_amask, const float2 *__restrict__ g_tmask,
                     const uint4 *__restrict__ g_fira)
 {
+    // the built geometries (wofdm_geo_table): generate mode, production, plain, in the layout the geometry gets
+    static_assert(GEO == 0 || (!INJECT && !DUMP && VAR == WOFDM_VAR_PLAIN), "geometries are built into the plain production kernels");
+    static_assert(GEO == 0 || wofdm_geo_row_of(GEO).n_fft == N, "the row's DFT length is not this kernel's");
+    static_assert(GEO == 0 || wofdm_geo_layout(GEO) == LAY, "the row's layout (wofdm_pick_layout) is not this kernel's");
+    const geo_vals<GEO, LAY> gm{gm_};
     // The layout (wofdm_kernel.h, wofdm_layout_info) decides the shape of the kernel:
     constexpr wofdm_layout LI = wofdm_layout_info(LAY, N);
     static_assert(wofdm_layout_built(LAY, N, VAR), "not a (layout, N, variant) the library is built for");
@@ -749,8 +785,8 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
     // the whole frame loop they overflow the SGPR file and come back as v_readlane traffic.
 #define GEO_PHASE()                                                                            \
     int goff_ = 0;                    /* opaque OFFSET: the pointer keeps its noalias provenance, */ \
-    asm volatile("" : "+s"(goff_));   /* so the reads stay scalar loads (a laundered pointer      */ \
-    const int *__restrict__ gq = gm + goff_   /* turns them into flat vector loads)               */
+    if constexpr (GEO == 0) asm volatile("" : "+s"(goff_));   /* so the reads stay scalar loads (a laundered pointer */ \
+    const auto gq = gm + goff_        /* turns them into flat vector loads); GEO > 0: constants, nothing is emitted */
 
     // LDS carve with compile-time offsets (wofdm_lds<N>): only the frame buffer, last, has a
     // run-time length.  Fewer live scalars = fewer SGPR spills in the frame loop.
@@ -2718,8 +2754,8 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         // start of phase C -- these loads, then a loop of dependent LDS reads over the waves' partial sums -- taking
         // 8.6 % of a wave's time for two dozen instructions).
         int goffc_ = 0;
-        asm volatile("" : "+s"(goffc_));
-        const int *__restrict__ gqc = gm + goffc_;
+        if constexpr (GEO == 0) asm volatile("" : "+s"(goffc_));
+        const auto gqc = gm + goffc_;                  // (a built geometry: constants, no request)
         const int cS = gqc[WOFDM_G_S], cB = gqc[WOFDM_G_B], cDelta = gqc[WOFDM_G_DELTA], cGam = gqc[WOFDM_G_GAMMA];
         const int cPlen = FIRQ ? gqc[WOFDM_G_FBUF] : 0;
         STAMP(2);
@@ -3576,13 +3612,35 @@ template <int N> wofdm_kernel_fn pick(int k, int layout, int mode, int var)
 // -DWOFDM_TU_K=<k>, see the Makefile) so that the kernel family builds in parallel;
 // wofdm_kernel.h dispatches on n_fft and bits_per_sc.  Nothing but the frame kernel is compiled here (its register allocation
 // answers to what else is compiled beside it): the auxiliary kernels have units of their own, wofdm_aux.hip.
+// With -DWOFDM_TU_GEO the unit holds the kernels of the built geometries of that (N, k) instead (wofdm_geo_table), and nothing else.
 #if !defined(WOFDM_TU_N) || !defined(WOFDM_TU_K)
 #error "compile with -DWOFDM_TU_N=<64|128|256|512|1024> -DWOFDM_TU_K=<2|4|6>"
 #endif
 #define WOFDM_CAT2(a, b) a##b
 #define WOFDM_CAT(a, b) WOFDM_CAT2(a, b)
 
+#ifdef WOFDM_TU_GEO
+namespace {
+template <int N, int K, int... I> wofdm_kernel_fn pick_geo(int geo, std::integer_sequence<int, I...>)
+{
+    wofdm_kernel_fn fn = nullptr;
+    ((geo == I + 1 && wofdm_geo_row_of(I + 1).n_fft == N
+          ? (void)(fn = wofdm_frames_kernel<N, K, wofdm_geo_layout(I + 1), false, false, WOFDM_VAR_PLAIN, I + 1>) : (void)0), ...);
+    return fn;
+}
+}  // namespace
+
+wofdm_kernel_fn WOFDM_CAT(WOFDM_CAT(WOFDM_CAT(wofdm_select_kernel_geo_n, WOFDM_TU_N), _k), WOFDM_TU_K)(int geo)
+{
+    return pick_geo<WOFDM_TU_N, WOFDM_TU_K>(geo, std::make_integer_sequence<int, WOFDM_GEO_COUNT>{});
+}
+// (which build of this source the unit is -- WOFDM_UNIT_BUILD above: a built geometry's kernel stands in only for a generic unit
+// of the same build, configure() in wofdm_abi.hip)
+int WOFDM_CAT(WOFDM_CAT(WOFDM_CAT(wofdm_kernel_geo_unit_build_n, WOFDM_TU_N), _k), WOFDM_TU_K)(void) { return WOFDM_UNIT_BUILD; }
+#else
 wofdm_kernel_fn WOFDM_CAT(WOFDM_CAT(WOFDM_CAT(wofdm_select_kernel_n, WOFDM_TU_N), _k), WOFDM_TU_K)(int layout, int mode, int var)
 {
     return pick<WOFDM_TU_N>(WOFDM_TU_K, layout, mode, var);
 }
+int WOFDM_CAT(WOFDM_CAT(WOFDM_CAT(wofdm_kernel_unit_build_n, WOFDM_TU_N), _k), WOFDM_TU_K)(void) { return WOFDM_UNIT_BUILD; }
+#endif

@@ -95,6 +95,13 @@ class Plan:
         _lib.check(self.lib.wofdm_plan_kernel_id(self._h_plan, a))
         return int(a[0]), int(a[1])
 
+    def kernel_geo(self):
+        """Id of the built geometry of the kernel ``launch`` runs (``wofdm_plan_kernel_geo``): 1 ... 7 = the structure lengths
+        are compile-time constants of that kernel, 0 = it reads them at run time."""
+        a = C.c_int32()
+        _lib.check(self.lib.wofdm_plan_kernel_geo(self._h_plan, C.byref(a)))
+        return int(a.value)
+
     def set_allocation(self, active):
         """Subcarrier allocation (``wofdm_plan_set_allocation``): ``active`` [N] truthy = bin
         carries data; None = every bin (main_channel_mask.m:387-390, 367-369)."""
@@ -119,7 +126,8 @@ class Plan:
 
     def set_option(self, name, value):
         """Kernel choice (``wofdm_plan_set_option``): ``fir_valu`` 0/1, ``dft_valu`` 0/1 (the transforms on the vector pipe:
-        the kernels for a GPU that is shared with other work, include/wofdm.h), ``max_spw`` 0/1/2/4, ``txmask_direct`` 0/1.
+        the kernels for a GPU that is shared with other work, include/wofdm.h), ``max_spw`` 0/1/2/4, ``txmask_direct`` 0/1, ``generic_geometry`` 0/1
+        (the kernel that reads the structure lengths at run time also where the geometry is a built one).
         Same results, other kernels of the family (A/B measurements, tests)."""
         _lib.check(self.lib.wofdm_plan_set_option(self._h_plan, _lib.OPTIONS[name], int(value)))
 
