@@ -393,8 +393,46 @@ int wofdm_rx_profile(const wofdm_cfg *cfg, int device,
                      uint64_t *errs,         /* [cells][n_fft][2] = {bit errors, symbol errors}, ACCUMULATED into */
                      double *err_power);     /* [cells][n_fft] = sum |Xhat - X|^2, ACCUMULATED into; or NULL */
 
-/* *ms = milliseconds (HIP events) the kernels of the calling thread's last successful wofdm_rx_profile call took, first chunk
- * to last; 0 before any.  Measurement aid (tools/bench_rx_profile.py). */
+/* wofdm_rx_profile beside an asynchronous adjacent-band neighbour: what the victim of wofdm_rx_profile loses, bin by bin, to a
+ * second transmitter that is not symbol-aligned with it -- the interference the Rx window is there to reject.  The reference
+ * has no such experiment (matlab/main_channel_mask.m frees half the band for a neighbour and stops at the transmitter).
+ *   Victim: exactly wofdm_rx_profile -- frames, cells, streams 0 and 1, allocation, mask, both noise_before_truncate orders,
+ * outputs, ordered sums, the gate.
+ *   Neighbour: the victim's numerology and Tx chain (cfg, k, the Tx window of the cell's pair, the same tx_mask or none) on the
+ * allocation aci_active[n_fft] (any set; usually the complement of active), with labels of its own: stream 2 of philox.h
+ * (WOFDM_STREAM_ACI), counter (u bps + blk, frame lo, frame hi, 2 << 28 | cell), key and slot layout of stream 0.  It sends S + 1
+ * symbols u = 0 ... S, a waveform xi of tail_tx + (S + 1) B samples, placed so that its symbol u begins at victim time
+ * (u - 1) B + aci_delay, 0 <= aci_delay < B: the on-air sample t of the victim's frame carries a xi[t + B - aci_delay] with a
+ * = 10^(aci_level_db / 20), an index inside xi for every t of the frame, so the frame has a neighbour from its first sample
+ * (pilot included) to its last; what the neighbour sent before t = 0 passes its channel like the rest.  Its channel is
+ * aci_h[channel of the cell] ([n_channels][n_taps][2]), or the victim's h[channel] if aci_h is NULL.
+ *   Received: r = conv(h, x) + conv(aci_h, a xi shifted) + g n.  Ps, Pn and so g are measured on the victim's conv alone, over
+ * the samples wofdm_rx_profile uses: snr_db stays the victim's SNR and the neighbour comes on top.  Outputs: errs and err_power
+ * on the victim's loaded bins, ACCUMULATED into, as in wofdm_rx_profile.
+ *   An aci_active that loads no bin is valid and means no neighbour: the call then IS wofdm_rx_profile (same kernels, same
+ * chunks, same bits).  WOFDM_E_INVALID: a NULL aci_active, a non-finite aci_level_db (or one whose amplitude overflows single
+ * precision), non-finite aci_h taps, a negative aci_delay; WOFDM_E_UNSUPPORTED: aci_delay >= B = P - tail_tx; and every limit
+ * and check of wofdm_rx_profile.  Every argument is checked before the device is touched; a failed call leaves errs and
+ * err_power as they were.  Repeated calls give identical bits, a split frame range the integer counters of one call.
+ *   Chunks: min(65535, WOFDM_RX_PROFILE_CHUNK_BYTES / (8 (S n_fft + (S + 1) n_fft + T + (T + B) + [mask] (2 S + 1) (2P-1) +
+ * n_fft)))  frames -- both symbol grids, both waveforms, (masked) both sets of filtered symbols, the per-bin partials. */
+int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device,
+                         const float *w_tx,           /* [pairs][P] */
+                         const float *w_rx,           /* [pairs][N+tail_rx] */
+                         const float *h,              /* [n_channels][n_taps][2] */
+                         const float *snr_db,         /* [n_snr] */
+                         const uint8_t *active,       /* [n_fft] or NULL */
+                         const float *tx_mask,        /* [2P-1] or NULL */
+                         const uint8_t *aci_active,   /* [n_fft] bins the neighbour loads */
+                         const float *aci_h,          /* [n_channels][n_taps][2]; NULL = the victim's h */
+                         int32_t aci_delay,           /* samples, 0 <= aci_delay < B */
+                         float aci_level_db,          /* dB; neighbour amplitude 10^(level/20), finite */
+                         uint64_t *errs,              /* [cells][n_fft][2], ACCUMULATED into */
+                         double *err_power);          /* [cells][n_fft], ACCUMULATED into; or NULL */
+
+/* *ms = milliseconds (HIP events) the kernels of the calling thread's last successful wofdm_rx_profile or
+ * wofdm_rx_profile_aci call took (whichever came last), first chunk to last; 0 before any.  Measurement aid
+ * (tools/bench_rx_profile.py, tools/bench_rx_profile_aci.py). */
 int wofdm_rx_profile_kernel_ms(float *ms);
 
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */

@@ -37,6 +37,7 @@ EXPORTS = (
     "wofdm_interference", "wofdm_tx_psd", "wofdm_tx_psd_batch", "wofdm_tx_psd_batch_masked",
     "wofdm_interference_masked", "wofdm_tx_papr", "wofdm_tx_papr_kernel_ms",
     "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms", "wofdm_plan_kernel_geo", "wofdm_cfg_geo_id",
+    "wofdm_rx_profile_aci",
 )
 
 
@@ -148,6 +149,7 @@ def load():
     L.wofdm_tx_papr.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, C.c_float, C.c_float, i32, vp, vp, vp]
     L.wofdm_tx_papr_kernel_ms.argtypes = [C.POINTER(C.c_float)]
     L.wofdm_rx_profile.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.wofdm_rx_profile_aci.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp]
     L.wofdm_rx_profile_kernel_ms.argtypes = [C.POINTER(C.c_float)]
     _LIB = L
     return L

@@ -283,6 +283,52 @@ def profile_for_window_file(type_ofdm, cp, windows, channels, snr_db, num_subcar
     return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
 
 
+def aci_for_window_file(type_ofdm, cp, windows, channels, snr_db, delays, level_db=0.0, aci_channels=None, num_subcar=256,
+                        bits_per_subcar=4, symbols_per_tx=16, ensemble=100, roll_off=ROLL_OFF, seed=0, frame_range=None,
+                        gpu=True, device=0, tail_tx=8, tail_rx=10):
+    """The neighbour's side of the mask experiment: ``profile_for_window_file`` with a second transmitter of the same
+    numerology on the COMPLEMENTARY half band, not symbol-aligned with the victim -- what the free half band and the
+    confined spectrum are for, and what the Rx window is there to reject.  Every window pair of the file + the RC pair, the
+    victim on ``half_band_allocation``, the neighbour on the other bins with the pair's Tx window (and the mask, in the masked
+    run), ``level_db`` dB against the victim, through ``aci_channels`` [n_channels][taps] (None: the victim's), its symbols
+    beginning ``delay`` samples after the victim's for every delay of ``delays`` (0 <= delay < stride).  ``snr_db`` is the
+    victim's SNR; the neighbour comes on top.  On the GPU two ``wofdm_rx_profile_aci`` calls per delay (gpu=False: the fp64
+    host route ``rx_profile.rx_profile_aci_host``, for small ensembles); the frames are those of ``profile_for_window_file``
+    with the same arguments, so the two results differ by the neighbour alone.
+    Returns {name: {delay: {"profile", "profile_masked"}}} with the names of ``V.matlab_pair_plan``; each an
+    ``rx_profile.RxProfile`` of that pair, arrays [n_snr, n_channels, N]."""
+    from . import rx_profile as R
+    n = num_subcar
+    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
+                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
+    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
+    plan = V.matlab_pair_plan(type_ofdm)
+
+    def pick(key, side):
+        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
+
+    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
+    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
+    h = np.atleast_2d(np.asarray(channels))
+    alloc = half_band_allocation(n)
+    mask = tx_mask(st.sym_len, roll_off)
+    first, count = (0, ensemble) if frame_range is None else frame_range
+    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, h, snr_db, seed, first, count, ~alloc)
+    kw = dict(aci_level_db=level_db, aci_h=aci_channels, active=alloc)
+    run = R.rx_profile_aci_gpu if gpu else R.rx_profile_aci_host
+    if gpu:
+        kw["device"] = device
+    out = {name: {} for name, _ in plan}
+    for d in delays:
+        plain = run(*args, int(d), **kw)
+        masked = run(*args, int(d), mask=mask, **kw)
+        for i, (name, _) in enumerate(plan):
+            out[name][int(d)] = {"profile": R.RxProfile(plain.bit_err[i], plain.sym_err[i], plain.err_power[i], plain.decisions),
+                                 "profile_masked": R.RxProfile(masked.bit_err[i], masked.sym_err[i], masked.err_power[i],
+                                                               masked.decisions)}
+    return out
+
+
 def results_from_counts(names, masked, plain):
     def ber(c):      # mean over channels of per-channel BER (lines 84-117)
         return (c[..., 0] / np.maximum(c[..., 1], 1)).mean(axis=-1)

@@ -5,6 +5,9 @@
 //   counter = (block, frame lo, frame hi, stream << 28 | cell)
 //   stream 0: data bits   -- replaces randi([0 1], ...)   matlab/main_BER_calculation.m:246
 //   stream 1: unit noise  -- replaces randn + 1j*randn    matlab/main_BER_calculation.m:290
+//   stream 2: data bits of the adjacent-band neighbour of wofdm_rx_profile_aci (no counterpart in the reference): block and
+//             slot layout of stream 0, for the neighbour's S + 1 symbols u = 0 ... S: counter (u bps + blk, frame lo, frame
+//             hi, 2 << 28 | cell), bps = N kslot / 128 blocks per symbol.  The frame kernels never draw it.
 //
 // Bits: subcarrier n of symbol s owns a kslot-bit field (kslot = 2, 4, 8 for k = 2, 4, 6) at
 // bit offset n*kslot of the symbol's bit stream, i.e. block s*(N*kslot/128) + (n*kslot >> 7),
@@ -18,6 +21,7 @@
 
 #define WOFDM_STREAM_BITS  0u
 #define WOFDM_STREAM_NOISE 1u
+#define WOFDM_STREAM_ACI   2u
 
 struct philox_out { uint32_t w[4]; };
 

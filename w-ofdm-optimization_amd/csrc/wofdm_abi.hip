@@ -2,6 +2,7 @@
 // Plans own the constants in HBM; launches are asynchronous on the caller's stream.
 #include "../../include/wofdm.h"
 #include "wofdm_kernel.h"
+#include "philox.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1477,11 +1478,26 @@ int wofdm_tx_papr_kernel_ms(float *ms)
     return WOFDM_OK;
 }
 
-// Every argument is checked before the first HIP call; the caller's arrays are written only after everything has succeeded.
-int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
-                     const float *snr_db, const uint8_t *active, const float *tx_mask, uint64_t *errs, double *err_power)
+}  // extern "C"
+
+namespace {
+
+// the neighbour of wofdm_rx_profile_aci; a null pointer to it is wofdm_rx_profile
+struct aci_args {
+    const uint8_t *active;
+    const float *h;
+    int32_t delay;
+    float level_db;
+};
+
+// wofdm_rx_profile and wofdm_rx_profile_aci.  Every argument is checked before the first HIP call; the caller's arrays are
+// written only after everything has succeeded.
+int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
+                    const float *snr_db, const uint8_t *active, const float *tx_mask, const aci_args *aci, uint64_t *errs,
+                    double *err_power)
 {
     if (!cfg || !w_tx || !w_rx || !h || !snr_db || !errs) return fail(WOFDM_E_INVALID, "NULL argument");
+    if (aci && !aci->active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active)");
     const int N = cfg->n_fft, k = cfg->bits_per_sc, S = cfg->syms_per_frame, L = cfg->n_taps;
     if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
         return fail(WOFDM_E_UNSUPPORTED, "n_fft=%d not in {64,128,256,512,1024}", N);
@@ -1524,13 +1540,29 @@ int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const 
         for (int n = 0; n < N; ++n) n_act += (hact[(size_t)n] = active[n] ? 1 : 0);
         if (n_act == 0) return fail(WOFDM_E_INVALID, "the allocation loads no subcarrier");
     }
+    // the neighbour: an allocation that loads no bin is "no neighbour" and takes the plain route (nb stays false)
+    std::vector<uint8_t> hiact;
+    bool nb = false;
+    if (aci) {
+        if (!std::isfinite(aci->level_db) || !std::isfinite((float)std::pow(10.0, 0.05 * (double)aci->level_db)))
+            return fail(WOFDM_E_INVALID, "aci_level_db must be finite, and so the amplitude 10^(level / 20) in single precision");
+        if (aci->delay < 0) return fail(WOFDM_E_INVALID, "aci_delay=%d is negative", aci->delay);
+        if (aci->delay >= B)
+            return fail(WOFDM_E_UNSUPPORTED, "aci_delay=%d must be below the symbol stride B = %d", aci->delay, B);
+        if (aci->h && !finite(aci->h, (size_t)cfg->n_channels * L * 2)) return fail(WOFDM_E_INVALID, "aci_h taps must be finite");
+        hiact.resize((size_t)N);
+        for (int n = 0; n < N; ++n) nb |= (hiact[(size_t)n] = aci->active[n] ? 1 : 0) != 0;
+    }
     int rc = use_device(device);
     if (rc != WOFDM_OK) return rc;
     g_rxprof_ms = 0.f;
     const uint64_t items = cells * frames;
     if (items == 0) return WOFDM_OK;
-    // frames per chunk: what the budget holds (symbol grid + waveform + filtered symbols + partials of a frame), as the header documents it
-    const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) + (uint64_t)N);
+    // frames per chunk: what the budget holds (symbol grid + waveform + filtered symbols + partials of a frame; with a neighbour
+    // its S + 1 symbols beside them), as the header documents it
+    const int Ti = T + B;
+    const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) + (uint64_t)N +
+                                       (nb ? (uint64_t)(S + 1) * N + (uint64_t)Ti + (tx_mask ? (uint64_t)(S + 1) * Lm : 0ull) : 0ull));
     const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
                                                                        std::max<uint64_t>(1, WOFDM_RX_PROFILE_CHUNK_BYTES / job_bytes)));
     std::vector<float2> hspec;
@@ -1563,6 +1595,20 @@ int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const 
         (tx_mask && !d_spec.upload(hspec.data(), hspec.size())) || hipMemset(d_errs, 0, 2 * n_out * 8) != hipSuccess ||
         hipMemset(d_pow, 0, n_out * 8) != hipSuccess)
         return fail(WOFDM_E_HIP, "upload failed");
+    // the neighbour's side of the chunk: allocation, channels, and grids, waveforms, tables of its S + 1 symbols
+    dev_buf<uint8_t> d_iact;
+    dev_buf<float2> d_hi, d_Xi, d_xi, d_Yi;
+    dev_buf<wofdm_bjob> d_ijobs;
+    dev_buf<wofdm_mjob> d_imjobs;
+    if (nb) {
+        const std::vector<float2> hpi = pack_taps(cfg, g, aci->h ? aci->h : h);
+        if (!d_iact.alloc(hiact.size()) || !d_hi.alloc(hpi.size()) || !d_Xi.alloc((size_t)chunk * (S + 1) * N) ||
+            !d_xi.alloc((size_t)chunk * Ti) || !d_ijobs.alloc((size_t)chunk) ||
+            (tx_mask && (!d_Yi.alloc((size_t)chunk * (S + 1) * Lm) || !d_imjobs.alloc((size_t)chunk))))
+            return fail(WOFDM_E_NOMEM, "device allocation failed (neighbour)");
+        if (!d_iact.upload(hiact.data(), hiact.size()) || !d_hi.upload(hpi.data(), hpi.size()))
+            return fail(WOFDM_E_HIP, "upload failed");
+    }
     hipEvent_t ev[2] = {nullptr, nullptr};
     if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) {
         if (ev[0]) (void)hipEventDestroy(ev[0]);
@@ -1580,6 +1626,14 @@ int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const 
     rp.seed_lo = pp.seed_lo; rp.seed_hi = pp.seed_hi; rp.frames = frames; rp.frame_offset = cfg->frame_offset;
     rp.X = d_X; rp.x = d_x; rp.wrx = d_wr; rp.h = d_h; rp.nlin = d_nlin; rp.amask = d_act;
     rp.part_pow = d_ppow; rp.part_cnt = d_pcnt; rp.errs = d_errs; rp.pow = d_pow;
+    wofdm_pparams pa = pp;
+    wofdm_aparams apar{};
+    if (nb) {
+        pa.S = S + 1; pa.stream = WOFDM_STREAM_ACI; pa.amask = d_iact; pa.jobs = d_ijobs; pa.mjobs = d_imjobs;
+        pa.X = d_Xi; pa.x = d_xi; pa.Y = d_Yi;
+        apar.xi = d_xi; apar.hi = d_hi; apar.Ti = Ti; apar.ioff = B - aci->delay;
+        apar.a_lvl = (float)std::pow(10.0, 0.05 * (double)aci->level_db);
+    }
     std::vector<unsigned long long> herr(2 * n_out);
     std::vector<double> hpow(n_out);
     float ms = 0.f;
@@ -1593,7 +1647,9 @@ int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const 
         for (uint64_t i0 = 0; e == hipSuccess && i0 < items; i0 += chunk) {
             pp.item0 = rp.item0 = i0;
             pp.n_jobs = rp.n_jobs = (int32_t)std::min<uint64_t>(chunk, items - i0);
-            e = ax->rx_profile(&pp, &rp, nullptr);
+            pa.item0 = pp.item0;
+            pa.n_jobs = pp.n_jobs;
+            e = nb ? ax->rx_profile_aci(&pp, &pa, &rp, &apar, nullptr) : ax->rx_profile(&pp, &rp, nullptr);
         }
         if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -1610,6 +1666,24 @@ int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const 
         for (size_t i = 0; i < n_out; ++i) err_power[i] += hpow[i];
     g_rxprof_ms = ms;
     return WOFDM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
+                     const float *snr_db, const uint8_t *active, const float *tx_mask, uint64_t *errs, double *err_power)
+{
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, errs, err_power);
+}
+
+int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
+                         const float *snr_db, const uint8_t *active, const float *tx_mask, const uint8_t *aci_active,
+                         const float *aci_h, int32_t aci_delay, float aci_level_db, uint64_t *errs, double *err_power)
+{
+    const aci_args aci = {aci_active, aci_h, aci_delay, aci_level_db};
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, errs, err_power);
 }
 
 int wofdm_rx_profile_kernel_ms(float *ms)

@@ -1,6 +1,6 @@
 // wofdm_aux.hip -- the auxiliary kernels beside the frame kernel: closed-form ICI/ISI power (wofdm_interference,
 // wofdm_interference_masked) and Tx waveform + averaged periodogram (wofdm_tx_psd, wofdm_tx_psd_batch,
-// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
+// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile; beside an adjacent-band neighbour: wofdm_rx_profile_aci).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
 // on n_fft through the unit's table of launchers (wofdm_aux_fns).
 #include "wofdm_kernel.h"
 #include "wofdm_device.h"
@@ -856,8 +856,8 @@ wofdm_interf_masked_kernel(const wofdm_mparams p, const float *__restrict__ g_wr
 // of the frame kernel feeds its IDFT --, their waveforms by the waveform kernels above with one job per frame, and {peak,
 // energy} of every symbol period of those waveforms with its histogram bin.
 //
-// Generation: thread = one Philox block of the label stream (stream 0 of philox.h: counter (s bps + blk, frame lo, frame hi,
-// pair), key = seed), 256 blocks per workgroup into LDS; they are 256 * 128 / kslot consecutive subcarriers of X, which the
+// Generation: thread = one Philox block of the label stream (stream p.stream of philox.h, 0 unless the caller asks for the
+// neighbour's stream 2: counter (s bps + blk, frame lo, frame hi, stream << 28 | pair), key = seed), 256 blocks per workgroup into LDS; they are 256 * 128 / kslot consecutive subcarriers of X, which the
 // workgroup then maps (qam_point, zero on unloaded bins) and stores side by side.  The first n_jobs threads of the grid also
 // write the chunk's job tables: job j = frame (item0 + j) % frames of pair (item0 + j) / frames.
 template <int N>
@@ -868,7 +868,7 @@ __global__ void __launch_bounds__(256) wofdm_papr_gen_kernel(const wofdm_pparams
     const int tid = threadIdx.x, S = p.S;
     const int ks = p.k == 6 ? 8 : p.k, bps = N * ks / 128, per = 128 / ks;      // (wofdm_kslot)
     if (tid < (1 << p.k)) lut[tid] = qam_point(p.k, (uint32_t)tid);
-    const uint32_t gid = blockIdx.x * 256u + (uint32_t)tid;           // (n_jobs S bps <= 65535 * 16 * 64)
+    const uint32_t gid = blockIdx.x * 256u + (uint32_t)tid;           // (n_jobs S bps <= 65535 * 17 * 64 < 2^27)
     if (gid < (uint32_t)p.n_jobs) {
         const uint64_t pair = (p.item0 + gid) / p.frames;
         const int T = p.beta + S * (p.P - p.beta);
@@ -888,7 +888,7 @@ __global__ void __launch_bounds__(256) wofdm_papr_gen_kernel(const wofdm_pparams
         const uint32_t j = sym / (uint32_t)S, s = sym - j * (uint32_t)S;
         const uint64_t item = p.item0 + j, pair = item / p.frames, frame = p.frame_offset + (item - pair * p.frames);
         const philox_out o = philox4x32_10(s * (uint32_t)bps + blk, (uint32_t)frame, (uint32_t)(frame >> 32),
-                                           (WOFDM_STREAM_BITS << 28) | (uint32_t)pair, p.seed_lo, p.seed_hi);
+                                           (p.stream << 28) | (uint32_t)pair, p.seed_lo, p.seed_hi);
 #pragma unroll
         for (int i = 0; i < 4; ++i) words[4 * tid + i] = o.w[i];
     }
@@ -1042,7 +1042,9 @@ template <int N> struct rxp_geo {
     static constexpr int LOG2 = N == 64 ? 6 : (N == 128 ? 7 : (N == 256 ? 8 : (N == 512 ? 9 : 10)));
     static constexpr int XROW = N + 64 + 24;                          // tail_rx <= 64, WOFDM_LT - 1 <= 24 samples of history
     static constexpr int LDS = 8 * (N / 2) + 8 * N + 4 * (N + 64) + 4 * 64 + WAVES * 8 * (N + XROW);
+    static constexpr int LDS_ACI = LDS + WAVES * 8 * XROW;            // the ACI arm: a second x row per wave (the neighbour's)
     static_assert(LDS <= 160 * 1024 && WAVES * 8 * N <= WAVES * 8 * (N + XROW) && (1 << LOG2) == N, "LDS");
+    static_assert(LDS_ACI <= 160 * 1024, "LDS (ACI arm)");
 };
 
 // the complex unit normal of sample a of (seed, cell, frame): philox.h, block a / 2, words 2 (a % 2) and 2 (a % 2) + 1
@@ -1068,10 +1070,16 @@ __device__ __forceinline__ uint32_t rxp_slice(int k, float re, float im)
     return ((uint32_t)(ii ^ (ii >> 1)) << hb) | (uint32_t)(qi ^ (qi >> 1));
 }
 
-template <int N>
-__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(const wofdm_rparams p)
+// The body of both receive kernels.  ACI = false is wofdm_rx_profile's kernel as it was.  ACI = true (wofdm_rx_profile_aci)
+// adds an adjacent-band neighbour to pass 2: the wave stages a second row with the neighbour's samples under the same window
+// -- the victim's on-air sample t carries a_lvl xi[t + ioff], zero outside xi --, and rxs() adds their 21-tap sum with the
+// neighbour's channel hi[ch], scaled by a_lvl, to the received sample.  Pass 1 does not see the neighbour: Ps, Pn and the
+// noise gain are the victim's.
+template <int N, bool ACI>
+__device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_aparams &ap)
 {
     using RG = rxp_geo<N>;
+    constexpr int ROWLEN = N + (ACI ? 2 : 1) * RG::XROW;
     constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2 *tw = reinterpret_cast<float2 *>(smem);                    // e^{-2 pi i k / N}, k < N / 2
@@ -1090,6 +1098,8 @@ __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(co
     const float2 *__restrict__ x = p.x + (size_t)job * T;
     const float2 *__restrict__ Xg = p.X + (size_t)job * S * N;
     const float2 *__restrict__ taps = p.h + (size_t)ch * LT;
+    const float2 *__restrict__ xi = ACI ? ap.xi + (size_t)job * ap.Ti : nullptr;
+    const float2 *__restrict__ itaps = ACI ? ap.hi + (size_t)ch * LT : nullptr;
     for (int i = tid; i < N / 2; i += NT) {
         float sv, cv;
         sincospif(-2.0f * (float)i / (float)N, &sv, &cv);
@@ -1130,8 +1140,9 @@ __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(co
     }
     const float g = sqrtf(Ps * p.nlin[sn] / Pn);
     // pass 2
-    float2 *buf = rows + (size_t)wv * (N + RG::XROW);
+    float2 *buf = rows + (size_t)wv * ROWLEN;
     float2 *xr = buf + N;
+    [[maybe_unused]] float2 *xir = xr + RG::XROW;                     // (ACI)
     float pw[BINS];
     uint32_t cnt[BINS];
 #pragma unroll
@@ -1148,6 +1159,10 @@ __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(co
             for (int i = lane; i < N + delta + LT - 1; i += 64) {
                 const int t = a0 - (LT - 1) + i;
                 xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
+                if constexpr (ACI) {
+                    const int ti = t + ap.ioff;
+                    xir[i] = (ti >= 0 && ti < ap.Ti) ? xi[ti] : make_float2(0.f, 0.f);
+                }
             }
             wave_sync();
             // r[a] = conv[a] + g n[a] (m:260-261, 290-293) of the sample m under the window
@@ -1158,6 +1173,17 @@ __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(co
                     const float2 xv = xr[m + (LT - 1) - l], hv = taps[l];
                     cr += hv.x * xv.x - hv.y * xv.y;
                     ci += hv.x * xv.y + hv.y * xv.x;
+                }
+                if constexpr (ACI) {
+                    float ar = 0.f, ai = 0.f;
+#pragma unroll
+                    for (int l = 0; l < LT; ++l) {
+                        const float2 xv = xir[m + (LT - 1) - l], hv = itaps[l];
+                        ar += hv.x * xv.x - hv.y * xv.y;
+                        ai += hv.x * xv.y + hv.y * xv.x;
+                    }
+                    cr += ap.a_lvl * ar;
+                    ci += ap.a_lvl * ai;
                 }
                 const uint32_t a = (uint32_t)(a0 + m);
                 const v2f nz = rxp_noise(a >> 1, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, (int)(a & 1u));
@@ -1236,6 +1262,17 @@ __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(co
         p.part_pow[(size_t)job * N + n] = t;
         p.part_cnt[(size_t)job * N + n] = c;
     }
+}
+
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(const wofdm_rparams p)
+{
+    rxprof_body<N, false>(p, wofdm_aparams{});
+}
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_aci_kernel(const wofdm_rparams p, const wofdm_aparams ap)
+{
+    rxprof_body<N, true>(p, ap);
 }
 
 // totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
@@ -1455,16 +1492,44 @@ hipError_t rx_profile_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, h
     return hipGetLastError();
 }
 
+// wofdm_rx_profile_aci, one chunk: the victim's Tx chain, the neighbour's (S + 1 symbols, its own stream, allocation, tables
+// and buffers), the receive kernel's ACI arm, and the ordered sums
+hipError_t rx_profile_aci_launch(const wofdm_pparams *pp, const wofdm_pparams *pa, const wofdm_rparams *rp,
+                                 const wofdm_aparams *app, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N;
+    const wofdm_rparams &r = *rp;
+    const wofdm_aparams &a = *app;
+    if (r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
+        r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 || r.n_snr < 1)
+        return hipErrorInvalidValue;
+    if (pa->n_jobs != pp->n_jobs || pa->item0 != pp->item0 || pa->frames != pp->frames || pa->frame_offset != pp->frame_offset ||
+        pa->S != r.S + 1 || pa->P != pp->P || pa->beta != pp->beta || pa->cp != pp->cp || pa->cs != pp->cs || pa->wdiv != pp->wdiv ||
+        a.Ti != r.T + r.B || a.ioff < 1 || a.ioff > r.B || a.xi != pa->x || a.hi == nullptr || pa->X == pp->X || pa->x == pp->x ||
+        pa->jobs == pp->jobs)
+        return hipErrorInvalidValue;
+    hipError_t e = tx_chain_launch(*pp, s);
+    if (e == hipSuccess) e = tx_chain_launch(*pa, s);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_aci_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                rxp_geo<N>::LDS_ACI);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_rxprof_aci_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_ACI, s, r, a);
+    const uint64_t cell0 = r.item0 / r.frames, cell1 = (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames;
+    hipLaunchKernelGGL(wofdm_rxprof_reduce_kernel<N>, dim3(N / 64, (unsigned)(cell1 - cell0 + 1)), dim3(64), 0, s, r, cell0);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 const wofdm_aux_fns *WOFDM_CAT(wofdm_aux_n, WOFDM_TU_N)(void)
 {
 #if WOFDM_TU_N <= 256
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, psd_launch, psd_batch_launch, psd_batch_masked_launch,
-                                      papr_launch, rx_profile_launch};
+                                      papr_launch, rx_profile_launch, rx_profile_aci_launch};
 #else
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, nullptr, psd_batch_launch, psd_batch_masked_launch,
-                                      papr_launch, rx_profile_launch};
+                                      papr_launch, rx_profile_launch, rx_profile_aci_launch};
 #endif
     return &fns;
 }

@@ -488,6 +488,8 @@ struct wofdm_pparams {
     uint64_t item0, frames, frame_offset;
     uint32_t wdiv;                    // cells per window pair: the item's "pair" is its CELL of the label stream, its window that
                                       // of pair / wdiv (wofdm_tx_papr: 1; wofdm_rx_profile: n_snr n_channels)
+    uint32_t stream;                  // label stream of philox.h the grids are drawn from: 0 = WOFDM_STREAM_BITS (the frames of
+                                      // a plan), WOFDM_STREAM_ACI for the neighbour of wofdm_rx_profile_aci (with its own amask)
     const float *wtx;                 // [pairs][P]
     const uint8_t *amask;             // [n_fft] 0 / 1, or null = every bin loaded
     const float2 *spec;               // [8 n_fft] fast-convolution spectrum of the Tx mask, or null = no mask
@@ -514,6 +516,15 @@ struct wofdm_rparams {
     uint32_t *part_cnt;               // [n_jobs][n_fft] bit errors | symbol errors << 16 of the item
     unsigned long long *errs;         // [cells][n_fft][2], accumulated into
     double *pow;                      // [cells][n_fft], accumulated into
+};
+// The adjacent-band neighbour of wofdm_rx_profile_aci, a second argument of the receive kernel's ACI arm (the plain kernel and
+// its parameters stay as they are): its waveforms xi[job][Ti], Ti = T + B (S + 1 symbols), its channels, its amplitude; the
+// victim's on-air sample t carries a_lvl xi[t + ioff], ioff = B - aci_delay in [1, B].
+struct wofdm_aparams {
+    const float2 *xi;
+    const float2 *hi;                 // [n_ch][WOFDM_LT], zero padded
+    int32_t Ti, ioff;
+    float a_lvl;
 };
 
 // the launchers of one DFT length
@@ -545,6 +556,11 @@ struct wofdm_aux_fns {
     // Receive profile of one chunk of (cell, frame) items: the Tx chain of papr (p->wdiv = cells per window pair), one
     // workgroup per item for its per-bin error counts and error power, and the sums of the chunk in frame order.
     hipError_t (*rx_profile)(const wofdm_pparams *p, const wofdm_rparams *r, hipStream_t s);
+    // The same beside an adjacent-band neighbour (wofdm_rx_profile_aci): a second pass through the Tx chain with pa (S + 1
+    // symbols of the label stream pa->stream on the allocation pa->amask, tables and buffers of its own), and the ACI arm of the
+    // receive kernel, which adds the neighbour's waveform a->xi through a->hi to every received sample of pass 2.
+    hipError_t (*rx_profile_aci)(const wofdm_pparams *p, const wofdm_pparams *pa, const wofdm_rparams *r, const wofdm_aparams *a,
+                                 hipStream_t s);
 };
 const wofdm_aux_fns *wofdm_aux_n64(void);
 const wofdm_aux_fns *wofdm_aux_n128(void);

@@ -9,6 +9,9 @@ matlab/main_channel_mask.m the per-bin picture is the interesting one.
 ``rx_profile_gpu`` runs on the GPU (no CPU fallback); ``frame_profile`` is the fp64 numpy mirror of ONE frame with the
 randomness given, ``rx_profile_host`` draws the same Philox streams on the host (csrc/philox.h) and runs it frame by frame
 -- for small ensembles, the check of the GPU route.
+
+``rx_profile_aci_gpu`` (``wofdm_rx_profile_aci``) is the same profile with an asynchronous adjacent-band neighbour on the
+air -- the interference the Rx window is there to reject; ``frame_profile_aci`` and ``rx_profile_aci_host`` mirror it.
 """
 import collections
 
@@ -84,6 +87,12 @@ def frame_profile(st, grids, unit_noise, w_tx, w_rx, h, snr_db, bits_per_sc, act
     277-355).  grids [S, N]: the transmitted constellation points (zeros on unloaded bins);
     unit_noise [noise_len] complex; w_tx [P], w_rx [N + delta], h [taps].  Returns (bit_err [N], sym_err [N], err_power
     [N], xhat [S-1, N], y0 [N]); unloaded bins are 0 everywhere."""
+    return _frame_steps(st, grids, unit_noise, w_tx, w_rx, h, snr_db, bits_per_sc, active, mask, noise_before_truncate)[:5]
+
+
+def _frame_steps(st, grids, unit_noise, w_tx, w_rx, h, snr_db, bits_per_sc, active, mask, noise_before_truncate, beside=None):
+    """The steps of ``frame_profile``; beside(S, B) -> [S B] complex or None: what another transmitter adds to the truncated
+    received samples (after the noise, whose gain never sees it).  Returns frame_profile's five outputs and Y [S, N]."""
     from . import timefreq as T
     X = np.asarray(grids, dtype=np.complex128)
     n, delta, gam, k = st.n_fft, st.tail_rx, st.prefix_rm, int(bits_per_sc)
@@ -99,7 +108,9 @@ def frame_profile(st, grids, unit_noise, w_tx, w_rx, h, snr_db, bits_per_sc, act
         raise ValueError("unit_noise holds %d samples, %d needed" % (noise.size, nl))
     ps, pn = np.mean(np.abs(conv[:nl]) ** 2), np.mean(np.abs(noise[:nl]) ** 2)       # add_wgn, m:277-294
     g = np.sqrt(ps * 10.0 ** (-0.1 * float(snr_db)) / pn)
-    r = (conv[:S * B] + g * noise[:S * B]).reshape(S, B)                             # truncate, m:261-263
+    r = conv[:S * B] + g * noise[:S * B]                                             # truncate, m:261-263
+    other = None if beside is None else beside(S, B)
+    r = (r if other is None else r + other).reshape(S, B)
     blocks = r[:, gam:gam + n + delta] * np.asarray(w_rx, np.float64)[None, :]       # wofdm_rx, m:297-355
     z = blocks[:, :n].copy()
     z[:, :delta] += blocks[:, n:]
@@ -110,7 +121,33 @@ def frame_profile(st, grids, unit_noise, w_tx, w_rx, h, snr_db, bits_per_sc, act
     bits = sum((d >> b) & 1 for b in range(k))
     err = np.where(on[None, :], np.abs(xhat - X[1:]) ** 2, 0.0)
     return (bits.sum(axis=0).astype(np.uint64), (d != 0).sum(axis=0).astype(np.uint64), err.sum(axis=0), xhat,
-            np.where(on, Y[0], 0.0))
+            np.where(on, Y[0], 0.0), Y)
+
+
+def frame_profile_aci(st, grids, aci_grids, unit_noise, w_tx, w_rx, h, aci_h, delay, level_db, snr_db, bits_per_sc,
+                      active=None, mask=None, noise_before_truncate=1, with_y=False):
+    """fp64 host mirror of one frame of ``wofdm_rx_profile_aci``: ``frame_profile`` (its own steps) with an adjacent-band
+    neighbour beside the victim.  aci_grids [S + 1, N]: the neighbour's constellation points (zeros on the bins it leaves
+    free), sent through the victim's Tx chain (w_tx, mask) as a waveform xi of tail_tx + (S + 1) B samples; its symbol u
+    begins at victim time (u - 1) B + delay, 0 <= delay < B, so the victim's on-air sample t carries a xi[t + B - delay], a
+    = 10^(level_db / 20); it passes aci_h [taps] (None: h) -- what it sent before t = 0 included --, and is added to the
+    received samples after the noise: Ps, Pn and the noise gain are the victim's alone.  Returns what ``frame_profile``
+    returns (with an all-zero aci_grids the same arrays); with_y=True: Y [S, N] as a sixth output."""
+    from . import timefreq as T
+    Xi = np.asarray(aci_grids, dtype=np.complex128)
+    S = np.asarray(grids).shape[0]
+    B, d = st.sym_len - st.tail_tx, int(delay)
+    if Xi.shape != (S + 1, st.n_fft):
+        raise ValueError("aci_grids must be [S + 1, %d]" % st.n_fft)
+    if not 0 <= d < B:
+        raise ValueError("delay must lie in [0, %d)" % B)
+    hi = np.asarray(h if aci_h is None else aci_h, dtype=np.complex128).reshape(-1)
+
+    def beside(S_, B_):
+        xi = T.tx_waveform(st, Xi.T, np.asarray(w_tx, np.float64), st.tail_tx, mask, guard_band=None)
+        return 10.0 ** (0.05 * float(level_db)) * np.convolve(hi, xi)[B_ - d:B_ - d + S_ * B_]
+    out = _frame_steps(st, grids, unit_noise, w_tx, w_rx, h, snr_db, bits_per_sc, active, mask, noise_before_truncate, beside)
+    return out if with_y else out[:5]
 
 
 # ---- the random streams of csrc/philox.h on the host ----
@@ -133,12 +170,16 @@ def _stream(seed, stream, cell, frame, n_blocks):
                    (stream << 28) | (int(cell) & 0x0FFFFFFF), seed & 0xFFFFFFFF, seed >> 32)
 
 
-def gen_labels(n_fft, bits_per_sc, syms, seed, cell, frame):
-    """[S, N] uint8 labels of stream 0 of (seed, cell, frame): csrc/philox.h, what a plan draws."""
+STREAM_BITS, STREAM_NOISE, STREAM_ACI = 0, 1, 2           # csrc/philox.h
+
+
+def gen_labels(n_fft, bits_per_sc, syms, seed, cell, frame, stream=0):
+    """[S, N] uint8 labels of stream 0 of (seed, cell, frame): csrc/philox.h, what a plan draws.  stream=2
+    (``STREAM_ACI``): the labels of the neighbour of ``wofdm_rx_profile_aci``, the same layout on its own stream."""
     k = int(bits_per_sc)
     ks = 8 if k == 6 else k
     bps = n_fft * ks // 128
-    w = _stream(seed, 0, cell, frame, syms * bps).reshape(syms, bps * 4)
+    w = _stream(seed, int(stream), cell, frame, syms * bps).reshape(syms, bps * 4)
     bit = np.arange(n_fft, dtype=np.int64) * ks
     return ((w[:, bit >> 5] >> (bit & 31).astype(np.uint64)[None, :]) & np.uint64((1 << k) - 1)).astype(np.uint8)
 
@@ -252,8 +293,108 @@ def rx_profile_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, see
     return prof
 
 
+# ---- beside an adjacent-band neighbour (wofdm_rx_profile_aci) ----
+
+def _prepare_aci(st, hc, aci_active, aci_h, aci_delay, aci_level_db):
+    iact = np.ascontiguousarray(np.asarray(aci_active).reshape(-1) != 0, dtype=np.uint8)
+    if iact.shape != (st.n_fft,):
+        raise ValueError("aci_active must hold %d flags" % st.n_fft)
+    hi = None if aci_h is None else np.ascontiguousarray(np.atleast_2d(aci_h), dtype=np.complex64)
+    if hi is not None and hi.shape != hc.shape:
+        raise ValueError("aci_h must have the shape of h, %s" % (hc.shape,))
+    return iact, hi, int(aci_delay), float(np.float32(aci_level_db))
+
+
+def rx_profile_aci_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, aci_active,
+                        aci_delay, aci_level_db=0.0, aci_h=None, active=None, mask=None, noise_before_truncate=1,
+                        with_near=False):
+    """The host route of ``rx_profile_aci_gpu``: the frames of ``rx_profile_host`` with the neighbour's S + 1 symbols of
+    stream 2 on ``aci_active`` beside each, through ``frame_profile_aci``.  An ``aci_active`` without a loaded bin is
+    ``rx_profile_host``.  with_near=True: also the number of ``near_decisions`` per cell [pairs, n_snr, n_ch]."""
+    from . import timefreq as T
+    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    iact, hi, d, lvl = _prepare_aci(st, hc, aci_active, aci_h, aci_delay, aci_level_db)
+    if not iact.any():
+        return rx_profile_host(st, bits_per_sc, syms, w_tx, w_rx, hc, snr, seed, frame_offset, frames, act, m,
+                               noise_before_truncate, with_near)
+    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, hc.shape[0], st.n_fft
+    k, S = int(bits_per_sc), int(syms)
+    tab = T.qam_table(k)
+    nl = _noise_len(st, S, hc.shape[1], noise_before_truncate)
+    on = np.ones(n, dtype=bool) if act is None else act != 0
+    bit = np.zeros((pairs, n_snr, n_ch, n), dtype=np.uint64)
+    sym = np.zeros_like(bit)
+    pw = np.zeros(bit.shape, dtype=np.float64)
+    near = np.zeros((pairs, n_snr, n_ch), dtype=np.int64)
+    for cell in range(pairs * n_snr * n_ch):
+        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
+        for f in range(int(frames)):
+            fr = int(frame_offset) + f
+            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
+            igrid = tab[gen_labels(n, k, S + 1, seed, cell, fr, STREAM_ACI)] * (iact != 0)[None, :]
+            b, se, e, xhat, y0 = frame_profile_aci(st, grid, igrid, gen_noise(nl, seed, cell, fr), w_tx[p], w_rx[p], hc[c],
+                                                   None if hi is None else hi[c], d, lvl, snr[s], k, act, m,
+                                                   noise_before_truncate)
+            bit[p, s, c] += b
+            sym[p, s, c] += se
+            pw[p, s, c] += e
+            if with_near:
+                near[p, s, c] += int(near_decisions(k, xhat, y0).sum())
+    prof = RxProfile(bit, sym, pw, _decisions(st, S, frames, act))
+    return (prof, near) if with_near else prof
+
+
+def rx_profile_aci_chunk_frames(st, syms, masked):
+    """Frames one chunk of ``wofdm_rx_profile_aci`` holds with a neighbour (include/wofdm.h: both symbol grids, S and S + 1
+    symbols, both waveforms, T and T + B samples, -- masked -- both sets of filtered symbols, the per-bin partials; at most
+    65535).  Without one (an empty ``aci_active``) the call chunks as ``rx_profile_chunk_frames``."""
+    from . import _lib
+    P = st.sym_len
+    B = P - st.tail_tx
+    T = st.tail_tx + syms * B
+    per_frame = 8 * (syms * st.n_fft + (syms + 1) * st.n_fft + T + (T + B) + ((2 * syms + 1) * (2 * P - 1) if masked else 0)
+                     + st.n_fft)
+    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+
+
+def rx_profile_aci_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, aci_active,
+                       aci_delay, aci_level_db=0.0, aci_h=None, active=None, mask=None, noise_before_truncate=1, device=0,
+                       out=None):
+    """``wofdm_rx_profile_aci``: ``rx_profile_gpu`` of the same arguments with an asynchronous adjacent-band neighbour on the
+    air -- the victim's numerology, Tx window and mask on the bins ``aci_active`` [N], S + 1 symbols of label stream 2, its
+    symbol u beginning at victim time (u - 1) B + ``aci_delay`` (0 <= aci_delay < B), amplitude 10^(aci_level_db / 20),
+    through ``aci_h`` [n_ch, taps] (None: h).  The SNR stays the victim's.  Returns ``RxProfile`` on the victim's loaded
+    bins; ``out`` is accumulated into.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    from .simulation import make_cfg
+    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    iact, hi, d, lvl = _prepare_aci(st, hc, aci_active, aci_h, aci_delay, aci_level_db)
+    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0]
+    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[1], n_ch, n_snr, pairs, bool(noise_before_truncate),
+                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
+    shape = (pairs, n_snr, n_ch, st.n_fft)
+    errs = np.zeros(shape + (2,), dtype=np.uint64)
+    pw = np.zeros(shape, dtype=np.float64)
+    hf = _lib.c64_as_f32(hc)
+    hif = None if hi is None else _lib.c64_as_f32(hi)
+    _lib.check(_lib.load().wofdm_rx_profile_aci(
+        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
+        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, iact.ctypes.data,
+        None if hif is None else hif.ctypes.data, d, lvl, errs.ctypes.data, pw.ctypes.data))
+    prof = RxProfile(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
+                     _decisions(st, syms, frames, act))
+    if out is not None:
+        if out.bit_err.shape != shape:
+            raise ValueError("out has another shape")
+        prof = RxProfile(out.bit_err + prof.bit_err, out.sym_err + prof.sym_err, out.err_power + prof.err_power,
+                         out.decisions + prof.decisions)
+    return prof
+
+
 def rx_profile_kernel_ms():
-    """Milliseconds the kernels of this thread's last ``rx_profile_gpu`` call took (``wofdm_rx_profile_kernel_ms``)."""
+    """Milliseconds the kernels of this thread's last ``rx_profile_gpu`` or ``rx_profile_aci_gpu`` call took
+    (``wofdm_rx_profile_kernel_ms``)."""
     import ctypes as C
     from . import _lib
     ms = C.c_float()
