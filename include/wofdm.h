@@ -432,8 +432,63 @@ int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device,
 
 /* *ms = milliseconds (HIP events) the kernels of the calling thread's last successful wofdm_rx_profile or
  * wofdm_rx_profile_aci call took (whichever came last), first chunk to last; 0 before any.  Measurement aid
- * (tools/bench_rx_profile.py, tools/bench_rx_profile_aci.py). */
+ * (tools/bench_rx_profile.py, tools/bench_rx_profile_aci.py).  A successful wofdm_rx_profile_sync call (below) counts as
+ * such a call too: the figure is then that of its whole sweep (tools/bench_rx_profile_sync.py). */
 int wofdm_rx_profile_kernel_ms(float *ms);
+
+/* wofdm_rx_profile under receiver timing and carrier-frequency offset: what the victim of wofdm_rx_profile loses, bin by bin
+ * and symbol by symbol, when the receiver's windows begin early or late and its oscillator is off -- the tolerance the cyclic
+ * suffix, the prefix removal and the Rx window trade.  The reference has no such experiment: its receiver is synchronised.  A
+ * call takes a LIST of points and runs the Tx chain and the power pass once per frame, whatever n_points is.
+ *   Victim: exactly wofdm_rx_profile -- frames, cells, streams 0 and 1, allocation, mask, both noise_before_truncate orders, Ps,
+ * Pn and the noise gain g (which never sees the offsets), the gate.
+ *   Received signal, for every integer on-air index a: r[a] = conv[a] + g n[a], conv = conv(h, x), zero outside [0, T + L - 1);
+ * n[a] the unit normal of stream 1 at sample index a mod 2^32 (block (uint32) a >> 1, word pair a & 1), so negative indices
+ * land on counter words no frame uses.  Nothing precedes the frame and nothing follows it: it is alone on the air.
+ *   Per point: sample m, 0 <= m < n_fft + tail_rx, of symbol s sits at a = s B + prefix_rm + timing + m and is multiplied, signal
+ * and noise, by e^{+2 pi i cfo a / n_fft} (cfo_tracked = 0, a free-running oscillator) or by e^{+2 pi i cfo m / n_fft}
+ * (cfo_tracked = 1: the common phase of every symbol removed); then Rx window, fold, shift, DFT, the pilot LS estimate from
+ * symbol 0 -- the pilot sees the offsets the data sees --, equaliser and slicer as in wofdm_rx_profile.  With the + sign a
+ * positive cfo moves what was sent on bin n - 1 onto bin n.  The phase at the window's start, exp(2 pi i frac(cfo (s B +
+ * prefix_rm + timing) / n_fft)), is prepared per (point, symbol) on the host in double precision from cfo as stored and kept
+ * in single; the kernel forms only the in-window factor in single precision -- with |cfo| <= 4 its argument stays at a few
+ * turns and its rounding near 3e-6 rad, below the 2e-5 stage tolerance: hence the limit on cfo.
+ *   Outputs (host), ACCUMULATED into: errs[n_points][cells][n_fft][2] and err_power[n_points][cells][n_fft] (or NULL) per point
+ * as in wofdm_rx_profile; sym_errs[n_points][cells][S-1][2] = {bit errors, symbol errors} and sym_power[n_points][cells][S-1] =
+ * sum |Xhat - X|^2 (either may be NULL) over the loaded bins per data symbol s = 1 ... S-1 -- the error against the distance
+ * from the pilot, the figure a free-running offset needs.  Integer counters are exact; float sums are formed in a fixed order
+ * -- per symbol a lane's bins ascending, then the ordered wave sum; per frame in fp32 as in wofdm_rx_profile; over the frames
+ * of a cell in frame order, fp64, one addition per frame onto the running total --, so repeated calls give identical bits, a
+ * split frame range gives the integer counters of one call, and a point's results do not depend on which other points share
+ * its call.  A point with timing = 0 and cfo = 0, under either flag, gives the bits of wofdm_rx_profile, err_power bytes
+ * included (as long as no cell's frames are split over two chunks of that call).
+ *   Every limit and check of wofdm_rx_profile applies.  WOFDM_E_INVALID: NULL points or errs, n_points < 1, a non-finite cfo,
+ * reserved != 0, cfo_tracked other than 0 or 1; WOFDM_E_UNSUPPORTED: n_points > WOFDM_SYNC_MAX_POINTS, |timing| >= B = P -
+ * tail_tx, |cfo| > 4.  Every argument is checked before the device is touched; a failed call leaves all four outputs as they were.
+ *   Chunks: min(65535, WOFDM_RX_PROFILE_CHUNK_BYTES / (8 (S n_fft + T + [mask] S (2P-1)) + 8 n_points (n_fft + S)))  frames --
+ * symbol grid, waveform, (masked) filtered symbols, and per point the per-bin and per-symbol partials.
+ *   Measured on an MI355X (tools/bench_rx_profile_sync.py, profiles/rx_profile_sync.txt): 9 timing points on 64 cells x 2000
+ * frames x 16 symbols at n_fft = 256 take 98 ms of kernels (134 ms masked), 2.7 (2.0) times one wofdm_rx_profile call on the
+ * same cells and frames in the same run -- 0.30 (0.22) of a call per point. */
+#define WOFDM_SYNC_MAX_POINTS 64
+typedef struct wofdm_sync_point {
+    int32_t timing;       /* theta, samples: the receiver's windows begin theta samples late (> 0) or early (< 0) */
+    float   cfo;          /* epsilon, in subcarrier spacings */
+    int32_t cfo_tracked;  /* 0: free-running oscillator; 1: the common phase of every symbol removed */
+    int32_t reserved;     /* 0 */
+} wofdm_sync_point;
+int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device,
+                          const float *w_tx,                /* [pairs][P] */
+                          const float *w_rx,                /* [pairs][N+tail_rx] */
+                          const float *h,                   /* [n_channels][n_taps][2] */
+                          const float *snr_db,              /* [n_snr] */
+                          const uint8_t *active,            /* [n_fft] or NULL */
+                          const float *tx_mask,             /* [2P-1] or NULL */
+                          int32_t n_points, const wofdm_sync_point *points,
+                          uint64_t *errs,                   /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                          double *err_power,                /* [n_points][cells][n_fft], or NULL */
+                          uint64_t *sym_errs,               /* [n_points][cells][S-1][2], or NULL */
+                          double *sym_power);               /* [n_points][cells][S-1], or NULL */
 
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

@@ -13,7 +13,8 @@ as ``wofdm_amd`` through the shim module at the repository root.
   timefreq     Tx-side PSD / out-of-band-radiation estimate (timefreq_simulation.py)
   channel_mask main_channel_mask.m: half-band loading + spectral Tx mask (GPU: allocation / tx_mask)
   rx_profile   per-subcarrier BER / EVM of the frames the BER loop runs (GPU: wofdm_rx_profile; fp64 host mirror), alone or
-               beside an asynchronous adjacent-band neighbour (GPU: wofdm_rx_profile_aci)
+               beside an asynchronous adjacent-band neighbour (GPU: wofdm_rx_profile_aci), or under receiver timing and
+               carrier-frequency offset (GPU: wofdm_rx_profile_sync)
   _lib         ctypes binding of libwofdm_hip.so (include/wofdm.h)
 """
 from . import variants  # noqa: F401
@@ -33,9 +34,11 @@ from ._lib import kernel_source_hash  # noqa: F401
 from .timefreq import (frame_papr, papr_ccdf, papr_hist, run_timefreq, tx_papr_gpu,  # noqa: F401
                        tx_psd_batch_gpu, tx_waveform)
 from .channel_mask import (aci_for_window_file, interference_for_window_file, papr_for_window_file,  # noqa: F401
-                           profile_for_window_file, spectrum_for_window_file)
-from .rx_profile import (RxProfile, ber_per_bin, evm_db, frame_profile, frame_profile_aci,  # noqa: F401
-                         rx_profile_aci_gpu, rx_profile_aci_host, rx_profile_gpu, rx_profile_host)
+                           profile_for_window_file, spectrum_for_window_file, sync_for_window_file)
+from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_db, frame_profile,  # noqa: F401
+                         frame_profile_aci, frame_profile_sync, gen_noise_at, rx_profile_aci_gpu, rx_profile_aci_host,
+                         rx_profile_gpu, rx_profile_host, rx_profile_sync_chunk_frames, rx_profile_sync_gpu,
+                         rx_profile_sync_host)
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

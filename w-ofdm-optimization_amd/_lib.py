@@ -26,6 +26,8 @@ TX_PAPR_CHUNK_BYTES = 256 << 20
 TX_PAPR_MAX_PERIODS = 1 << 20
 #: wofdm_rx_profile (include/wofdm.h): device-memory budget of a chunk of frames
 RX_PROFILE_CHUNK_BYTES = 256 << 20
+#: wofdm_rx_profile_sync (include/wofdm.h): most points one call takes
+SYNC_MAX_POINTS = 64
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -37,7 +39,7 @@ EXPORTS = (
     "wofdm_interference", "wofdm_tx_psd", "wofdm_tx_psd_batch", "wofdm_tx_psd_batch_masked",
     "wofdm_interference_masked", "wofdm_tx_papr", "wofdm_tx_papr_kernel_ms",
     "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms", "wofdm_plan_kernel_geo", "wofdm_cfg_geo_id",
-    "wofdm_rx_profile_aci",
+    "wofdm_rx_profile_aci", "wofdm_rx_profile_sync",
 )
 
 
@@ -75,6 +77,11 @@ class Cfg(C.Structure):
 class PsdJob(C.Structure):
     """Mirror of ``wofdm_psd_job``."""
     _fields_ = [(n, C.c_int32) for n in ("block", "cp", "cs", "overlap")]
+
+
+class SyncPoint(C.Structure):
+    """Mirror of ``wofdm_sync_point`` (16 bytes)."""
+    _fields_ = [("timing", C.c_int32), ("cfo", C.c_float), ("cfo_tracked", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Dump(C.Structure):
@@ -151,6 +158,7 @@ def load():
     L.wofdm_rx_profile.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_rx_profile_aci.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp]
     L.wofdm_rx_profile_kernel_ms.argtypes = [C.POINTER(C.c_float)]
+    L.wofdm_rx_profile_sync.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, i32, C.POINTER(SyncPoint), vp, vp, vp, vp]
     _LIB = L
     return L
 

@@ -1489,15 +1489,24 @@ struct aci_args {
     int32_t delay;
     float level_db;
 };
+// the receiver offsets of wofdm_rx_profile_sync and its per-symbol outputs; a null pointer to it is a synchronised receiver
+struct sync_args {
+    int32_t n_points;
+    const wofdm_sync_point *points;
+    uint64_t *sym_errs;
+    double *sym_power;
+};
 
-// wofdm_rx_profile and wofdm_rx_profile_aci.  Every argument is checked before the first HIP call; the caller's arrays are
-// written only after everything has succeeded.
+// wofdm_rx_profile, wofdm_rx_profile_aci and wofdm_rx_profile_sync.  Every argument is checked before the first HIP call; the
+// caller's arrays are written only after everything has succeeded.
 int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
-                    const float *snr_db, const uint8_t *active, const float *tx_mask, const aci_args *aci, uint64_t *errs,
-                    double *err_power)
+                    const float *snr_db, const uint8_t *active, const float *tx_mask, const aci_args *aci, const sync_args *sync,
+                    uint64_t *errs, double *err_power)
 {
     if (!cfg || !w_tx || !w_rx || !h || !snr_db || !errs) return fail(WOFDM_E_INVALID, "NULL argument");
     if (aci && !aci->active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active)");
+    if (sync && !sync->points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
+    if (sync && sync->n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", sync->n_points);
     const int N = cfg->n_fft, k = cfg->bits_per_sc, S = cfg->syms_per_frame, L = cfg->n_taps;
     if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
         return fail(WOFDM_E_UNSUPPORTED, "n_fft=%d not in {64,128,256,512,1024}", N);
@@ -1553,6 +1562,38 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         hiact.resize((size_t)N);
         for (int n = 0; n < N; ++n) nb |= (hiact[(size_t)n] = aci->active[n] ? 1 : 0) != 0;
     }
+    // the receiver offsets: the base phasor of every (point, symbol) in double precision, from cfo as stored
+    const int NP = sync ? sync->n_points : 1;
+    std::vector<wofdm_spoint> hpts;
+    std::vector<float2> hbase;
+    if (sync) {
+        if (NP > WOFDM_SYNC_MAX_POINTS) return fail(WOFDM_E_UNSUPPORTED, "n_points=%d exceeds %d", NP, WOFDM_SYNC_MAX_POINTS);
+        for (int i = 0; i < NP; ++i) {
+            const wofdm_sync_point &q = sync->points[i];
+            if (!std::isfinite(q.cfo)) return fail(WOFDM_E_INVALID, "points[%d].cfo must be finite", i);
+            if (q.reserved != 0) return fail(WOFDM_E_INVALID, "points[%d].reserved=%d must be 0", i, q.reserved);
+            if (q.cfo_tracked != 0 && q.cfo_tracked != 1)
+                return fail(WOFDM_E_INVALID, "points[%d].cfo_tracked=%d must be 0 or 1", i, q.cfo_tracked);
+        }
+        hpts.resize((size_t)NP);
+        hbase.resize((size_t)NP * S);
+        for (int i = 0; i < NP; ++i) {
+            const wofdm_sync_point &q = sync->points[i];
+            if ((int64_t)q.timing >= (int64_t)B || (int64_t)q.timing <= -(int64_t)B)
+                return fail(WOFDM_E_UNSUPPORTED, "points[%d].timing=%d must lie inside (-B, B), B = %d", i, q.timing, B);
+            if (std::fabs(q.cfo) > 4.0f)
+                return fail(WOFDM_E_UNSUPPORTED, "points[%d].cfo=%g exceeds 4 subcarrier spacings", i, (double)q.cfo);
+            hpts[(size_t)i].theta = q.timing;
+            hpts[(size_t)i].eps = q.cfo;
+            for (int s = 0; s < S; ++s) {
+                // eps (s B + gam + theta) / N is exact in double: 24 bits times less than 2^16, over a power of two
+                const double turns = (double)q.cfo * (double)(s * B + gam + q.timing) / (double)N;
+                const double ph = 2.0 * 3.14159265358979323846 * (turns - std::nearbyint(turns));
+                hbase[(size_t)i * S + s] =
+                    q.cfo_tracked ? make_float2(1.f, 0.f) : make_float2((float)std::cos(ph), (float)std::sin(ph));
+            }
+        }
+    }
     int rc = use_device(device);
     if (rc != WOFDM_OK) return rc;
     g_rxprof_ms = 0.f;
@@ -1561,7 +1602,9 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     // frames per chunk: what the budget holds (symbol grid + waveform + filtered symbols + partials of a frame; with a neighbour
     // its S + 1 symbols beside them), as the header documents it
     const int Ti = T + B;
-    const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) + (uint64_t)N +
+    // (under receiver offsets the partials are per point, per bin and per symbol)
+    const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) +
+                                       (sync ? (uint64_t)NP * (uint64_t)(N + S) : (uint64_t)N) +
                                        (nb ? (uint64_t)(S + 1) * N + (uint64_t)Ti + (tx_mask ? (uint64_t)(S + 1) * Lm : 0ull) : 0ull));
     const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
                                                                        std::max<uint64_t>(1, WOFDM_RX_PROFILE_CHUNK_BYTES / job_bytes)));
@@ -1575,7 +1618,8 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     const std::vector<float2> hp = pack_taps(cfg, g, h);
     std::vector<float> nlin((size_t)cfg->n_snr);
     for (int i = 0; i < cfg->n_snr; ++i) nlin[(size_t)i] = (float)std::pow(10.0, -0.1 * (double)snr_db[i]);
-    const size_t n_w = (size_t)pairs * P, n_wr = (size_t)pairs * NW, n_out = (size_t)cells * N;
+    const size_t n_w = (size_t)pairs * P, n_wr = (size_t)pairs * NW, n_out = (size_t)NP * cells * N;
+    const size_t n_sym = sync ? (size_t)NP * cells * (S - 1) : 0;
     dev_buf<float> d_w, d_wr, d_nlin, d_ppow;
     dev_buf<uint8_t> d_act;
     dev_buf<float2> d_h, d_spec, d_X, d_x, d_Y;
@@ -1586,7 +1630,8 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     dev_buf<double> d_pow;
     if (!d_w.alloc(n_w) || !d_wr.alloc(n_wr) || !d_nlin.alloc(nlin.size()) || !d_h.alloc(hp.size()) ||
         !d_X.alloc((size_t)chunk * S * N) || !d_x.alloc((size_t)chunk * T) || !d_jobs.alloc((size_t)chunk) ||
-        !d_ppow.alloc((size_t)chunk * N) || !d_pcnt.alloc((size_t)chunk * N) || !d_errs.alloc(2 * n_out) || !d_pow.alloc(n_out) ||
+        !d_ppow.alloc((size_t)chunk * NP * N) || !d_pcnt.alloc((size_t)chunk * NP * N) || !d_errs.alloc(2 * n_out) ||
+        !d_pow.alloc(n_out) ||
         (active && !d_act.alloc(hact.size())) ||
         (tx_mask && (!d_spec.alloc(hspec.size()) || !d_Y.alloc((size_t)chunk * S * Lm) || !d_mjobs.alloc((size_t)chunk))))
         return fail(WOFDM_E_NOMEM, "device allocation failed");
@@ -1595,6 +1640,21 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         (tx_mask && !d_spec.upload(hspec.data(), hspec.size())) || hipMemset(d_errs, 0, 2 * n_out * 8) != hipSuccess ||
         hipMemset(d_pow, 0, n_out * 8) != hipSuccess)
         return fail(WOFDM_E_HIP, "upload failed");
+    // the receiver offsets' side: the points, their base phasors, and the per-symbol partials and totals
+    dev_buf<wofdm_spoint> d_pts;
+    dev_buf<float2> d_base;
+    dev_buf<float> d_spow;
+    dev_buf<uint32_t> d_scnt;
+    dev_buf<unsigned long long> d_serrs;
+    dev_buf<double> d_stot;
+    if (sync) {
+        if (!d_pts.alloc(hpts.size()) || !d_base.alloc(hbase.size()) || !d_spow.alloc((size_t)chunk * NP * S) ||
+            !d_scnt.alloc((size_t)chunk * NP * S) || !d_serrs.alloc(2 * n_sym) || !d_stot.alloc(n_sym))
+            return fail(WOFDM_E_NOMEM, "device allocation failed (receiver offsets)");
+        if (!d_pts.upload(hpts.data(), hpts.size()) || !d_base.upload(hbase.data(), hbase.size()) ||
+            hipMemset(d_serrs, 0, 2 * n_sym * 8) != hipSuccess || hipMemset(d_stot, 0, n_sym * 8) != hipSuccess)
+            return fail(WOFDM_E_HIP, "upload failed");
+    }
     // the neighbour's side of the chunk: allocation, channels, and grids, waveforms, tables of its S + 1 symbols
     dev_buf<uint8_t> d_iact;
     dev_buf<float2> d_hi, d_Xi, d_xi, d_Yi;
@@ -1620,6 +1680,9 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     pp.frames = frames; pp.frame_offset = cfg->frame_offset; pp.wdiv = (uint32_t)cpp;
     pp.wtx = d_w; pp.amask = d_act; pp.spec = d_spec; pp.jobs = d_jobs; pp.mjobs = d_mjobs;
     pp.X = d_X; pp.x = d_x; pp.Y = d_Y;
+    wofdm_sparams spar{};
+    spar.n_points = NP; spar.cells = cells; spar.pts = d_pts; spar.base = d_base; spar.sym_pow = d_spow; spar.sym_cnt = d_scnt;
+    spar.sym_errs = d_serrs; spar.sym_tot = d_stot;
     wofdm_rparams rp{};
     rp.S = S; rp.k = k; rp.B = B; rp.T = T; rp.NL = cfg->noise_before_truncate ? T + L - 1 : S * B;
     rp.delta = delta; rp.gam = gam; rp.kap = cfg->circ_shift; rp.n_ch = cfg->n_channels; rp.n_snr = cfg->n_snr;
@@ -1634,8 +1697,8 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         apar.xi = d_xi; apar.hi = d_hi; apar.Ti = Ti; apar.ioff = B - aci->delay;
         apar.a_lvl = (float)std::pow(10.0, 0.05 * (double)aci->level_db);
     }
-    std::vector<unsigned long long> herr(2 * n_out);
-    std::vector<double> hpow(n_out);
+    std::vector<unsigned long long> herr(2 * n_out), hserr(2 * n_sym);
+    std::vector<double> hpow(n_out), hspow(n_sym);
     float ms = 0.f;
     hipError_t e = hipSuccess;
     {
@@ -1649,7 +1712,8 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
             pp.n_jobs = rp.n_jobs = (int32_t)std::min<uint64_t>(chunk, items - i0);
             pa.item0 = pp.item0;
             pa.n_jobs = pp.n_jobs;
-            e = nb ? ax->rx_profile_aci(&pp, &pa, &rp, &apar, nullptr) : ax->rx_profile(&pp, &rp, nullptr);
+            e = sync ? ax->rx_profile_sync(&pp, &rp, &spar, nullptr)
+                     : (nb ? ax->rx_profile_aci(&pp, &pa, &rp, &apar, nullptr) : ax->rx_profile(&pp, &rp, nullptr));
         }
         if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -1658,12 +1722,18 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     (void)hipEventDestroy(ev[0]);
     (void)hipEventDestroy(ev[1]);
     if (e != hipSuccess || hipMemcpy(herr.data(), d_errs, 2 * n_out * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(hpow.data(), d_pow, n_out * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(hpow.data(), d_pow, n_out * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        (n_sym && (hipMemcpy(hserr.data(), d_serrs, 2 * n_sym * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                   hipMemcpy(hspow.data(), d_stot, n_sym * 8, hipMemcpyDeviceToHost) != hipSuccess)))
         return fail(WOFDM_E_HIP, "receive-profile kernels or copy-back failed: %s",
                     hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
     for (size_t i = 0; i < 2 * n_out; ++i) errs[i] += herr[i];
     if (err_power)
         for (size_t i = 0; i < n_out; ++i) err_power[i] += hpow[i];
+    if (sync && sync->sym_errs)
+        for (size_t i = 0; i < 2 * n_sym; ++i) sync->sym_errs[i] += hserr[i];
+    if (sync && sync->sym_power)
+        for (size_t i = 0; i < n_sym; ++i) sync->sym_power[i] += hspow[i];
     g_rxprof_ms = ms;
     return WOFDM_OK;
 }
@@ -1675,7 +1745,7 @@ extern "C" {
 int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                      const float *snr_db, const uint8_t *active, const float *tx_mask, uint64_t *errs, double *err_power)
 {
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -1683,7 +1753,15 @@ int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, co
                          const float *aci_h, int32_t aci_delay, float aci_level_db, uint64_t *errs, double *err_power)
 {
     const aci_args aci = {aci_active, aci_h, aci_delay, aci_level_db};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, errs, err_power);
+}
+
+int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
+                          const float *snr_db, const uint8_t *active, const float *tx_mask, int32_t n_points,
+                          const wofdm_sync_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
+{
+    const sync_args sync = {n_points, points, sym_errs, sym_power};
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, errs, err_power);
 }
 
 int wofdm_rx_profile_kernel_ms(float *ms)

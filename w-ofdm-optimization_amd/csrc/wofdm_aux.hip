@@ -1,6 +1,6 @@
 // wofdm_aux.hip -- the auxiliary kernels beside the frame kernel: closed-form ICI/ISI power (wofdm_interference,
 // wofdm_interference_masked) and Tx waveform + averaged periodogram (wofdm_tx_psd, wofdm_tx_psd_batch,
-// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile; beside an adjacent-band neighbour: wofdm_rx_profile_aci).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
+// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile; beside an adjacent-band neighbour: wofdm_rx_profile_aci; under receiver timing and carrier offsets: wofdm_rx_profile_sync).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
 // on n_fft through the unit's table of launchers (wofdm_aux_fns).
 #include "wofdm_kernel.h"
 #include "wofdm_device.h"
@@ -1299,6 +1299,253 @@ __global__ void __launch_bounds__(64) wofdm_rxprof_reduce_kernel(const wofdm_rpa
     }
 }
 
+// The receive profile under receiver timing and carrier-frequency offsets (wofdm_rx_profile_sync): the item, the LDS image,
+// pass 1 and every expression of pass 2 are rxprof_body<N, false>'s -- a body of its own, so that the two kernels above compile
+// as they did --, with pass 2 run once per point of sp: the windows begin at s B + gam + theta (reads outside [0, T) of x are
+// zero, the noise of sample a is that of counter word (uint32) a: a negative a lands on words no frame uses), and the
+// received sample m under the window, signal and noise, is multiplied by base[point][s] e^{2 pi i eps m / N} before the Rx
+// window -- the host's base phasor carries the phase at the window's start (1 when the common phase is tracked), the kernel
+// forms the in-window factor from the fraction of eps m / N.  At theta = 0, eps = 0 both factors are exactly 1 and the
+// point gives the bits of wofdm_rxprof_kernel.  Beside the per-bin partials part_pow, part_cnt [job][point][N] the wave of
+// symbol s >= 1 leaves the symbol's sums over the loaded bins -- a lane's bins ascending, then papr_wave_reduce -- in sym_pow,
+// sym_cnt [job][point][S].  The pilot of a point sees the point's offsets.  LDS: rxp_geo<N>::LDS, whatever theta and n_points.
+template <int N>
+__device__ __forceinline__ void rxprof_sync_body(const wofdm_rparams &p, const wofdm_sparams &sp)
+{
+    using RG = rxp_geo<N>;
+    constexpr int ROWLEN = N + RG::XROW;
+    constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float2 *tw = reinterpret_cast<float2 *>(smem);                    // e^{-2 pi i k / N}, k < N / 2
+    float2 *G = tw + N / 2;                                           // pilot equaliser X0 / Y0 of the point
+    float *wrx = reinterpret_cast<float *>(G + N);
+    float *red = wrx + N + 64;                                        // [2][W] power partials
+    float2 *rows = reinterpret_cast<float2 *>(red + 64);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int S = p.S, B = p.B, T = p.T, NL = p.NL, delta = p.delta, NP = sp.n_points;
+    const uint32_t job = blockIdx.x;
+    const uint64_t item = p.item0 + job, cell64 = item / p.frames, frame = p.frame_offset + (item - cell64 * p.frames);
+    const uint32_t cell = (uint32_t)cell64, f_lo = (uint32_t)frame, f_hi = (uint32_t)(frame >> 32);
+    const int ch = (int)(cell % (uint32_t)p.n_ch), sn = (int)((cell / (uint32_t)p.n_ch) % (uint32_t)p.n_snr);
+    const int pair = (int)(cell / ((uint32_t)p.n_ch * (uint32_t)p.n_snr));
+    const float2 *__restrict__ x = p.x + (size_t)job * T;
+    const float2 *__restrict__ Xg = p.X + (size_t)job * S * N;
+    const float2 *__restrict__ taps = p.h + (size_t)ch * LT;
+    for (int i = tid; i < N / 2; i += NT) {
+        float sv, cv;
+        sincospif(-2.0f * (float)i / (float)N, &sv, &cv);
+        tw[i] = make_float2(cv, sv);
+    }
+    for (int i = tid; i < N + delta; i += NT) wrx[i] = p.wrx[(size_t)pair * (N + delta) + i];
+    // pass 1, once per item: signal and noise power over the same NL samples; the gain never sees the offsets
+    float ps = 0.f, pn = 0.f;
+    for (int q = tid; 2 * q < NL; q += NT) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int jj = 2 * q + e;
+            if (jj >= NL) break;
+            float cr = 0.f, ci = 0.f;
+            for (int l = 0; l < LT; ++l) {
+                const int t = jj - l;
+                if (t < 0 || t >= T) continue;
+                const float2 xv = x[t], hv = taps[l];
+                cr += hv.x * xv.x - hv.y * xv.y;
+                ci += hv.x * xv.y + hv.y * xv.x;
+            }
+            const v2f nz = rxp_noise((uint32_t)q, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, e);
+            ps += cr * cr + ci * ci;
+            pn += nz.x * nz.x + nz.y * nz.y;
+        }
+    }
+    ps = papr_wave_reduce<false>(ps);
+    pn = papr_wave_reduce<false>(pn);
+    if (lane == 0) {
+        red[wv] = ps;
+        red[W + wv] = pn;
+    }
+    __syncthreads();
+    float Ps = 0.f, Pn = 0.f;
+    for (int w = 0; w < W; ++w) {
+        Ps += red[w];
+        Pn += red[W + w];
+    }
+    const float g = sqrtf(Ps * p.nlin[sn] / Pn);
+    // pass 2, once per point
+    float2 *buf = rows + (size_t)wv * ROWLEN;
+    float2 *xr = buf + N;
+    const int h2 = delta >> 1;
+#pragma unroll 1
+    for (int pt = 0; pt < NP; ++pt) {
+        const int theta = sp.pts[pt].theta;
+        const float turn = sp.pts[pt].eps * (1.0f / (float)N);        // (exact: N is a power of two)
+        const size_t slot = (size_t)job * NP + pt;
+        float pw[BINS];
+        uint32_t cnt[BINS];
+#pragma unroll
+        for (int j = 0; j < BINS; ++j) {
+            pw[j] = 0.f;
+            cnt[j] = 0u;
+        }
+        for (int s0 = 0; s0 < S; s0 += W) {
+            const int s = s0 + wv;
+            const bool live = s < S;                                  // (wave-uniform)
+            if (live) {
+                const int a0 = s * B + p.gam + theta;                 // first sample under the moved Rx window
+                const float2 bs = sp.base[(size_t)pt * S + s];
+                for (int i = lane; i < N + delta + LT - 1; i += 64) {
+                    const int t = a0 - (LT - 1) + i;
+                    xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
+                }
+                wave_sync();
+                // r[a] = conv[a] + g n[a] of the sample m under the window, a = a0 + m, rotated by the oscillator's phase there
+                auto rxs = [&](int m) {
+                    float cr = 0.f, ci = 0.f;
+#pragma unroll
+                    for (int l = 0; l < LT; ++l) {
+                        const float2 xv = xr[m + (LT - 1) - l], hv = taps[l];
+                        cr += hv.x * xv.x - hv.y * xv.y;
+                        ci += hv.x * xv.y + hv.y * xv.x;
+                    }
+                    const uint32_t a = (uint32_t)(a0 + m);
+                    const v2f nz = rxp_noise(a >> 1, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, (int)(a & 1u));
+                    const float2 r = make_float2(cr + g * nz.x, ci + g * nz.y);
+                    float tn = turn * (float)m, sv, cv;
+                    tn -= rintf(tn);
+                    sincospif(2.0f * tn, &sv, &cv);
+                    const float qr = bs.x * cv - bs.y * sv, qi = bs.x * sv + bs.y * cv;
+                    return make_float2(r.x * qr - r.y * qi, r.x * qi + r.y * qr);
+                };
+#pragma unroll 1
+                for (int j = 0; j < BINS; ++j) {
+                    const int t = lane + 64 * j, m0 = (t + p.kap + h2) & (N - 1);
+                    float2 z = rxs(m0);
+                    z.x *= wrx[m0];
+                    z.y *= wrx[m0];
+                    if (m0 < delta) {
+                        const float2 z2 = rxs(m0 + N);
+                        z.x += wrx[m0 + N] * z2.x;
+                        z.y += wrx[m0 + N] * z2.y;
+                    }
+                    buf[__brev((uint32_t)t) >> (32 - LOG2)] = z;
+                }
+                wave_sync();
+                for (int len = 2, sh = LOG2 - 1; len <= N; len <<= 1, --sh) {
+                    const int half = len >> 1;
+                    for (int b = lane; b < N / 2; b += 64) {
+                        const int kk = b & (half - 1), i = ((b - kk) << 1) | kk;
+                        const float2 w = tw[kk << sh], a = buf[i], c = buf[i + half];
+                        const float tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
+                        buf[i] = make_float2(a.x + tr, a.y + ti);
+                        buf[i + half] = make_float2(a.x - tr, a.y - ti);
+                    }
+                    wave_sync();
+                }
+            }
+            if (s0 == 0) {
+                // pilot LS estimate of the point: the pilot sees the offsets the data sees
+                if (wv == 0)
+                    for (int n = lane; n < N; n += 64) {
+                        const float2 y = buf[n], x0 = Xg[n];
+                        const float d = y.x * y.x + y.y * y.y;
+                        const bool on = p.amask == nullptr || p.amask[n] != 0;
+                        G[n] = on ? make_float2((x0.x * y.x + x0.y * y.y) / d, (x0.y * y.x - x0.x * y.y) / d) : make_float2(0.f, 0.f);
+                    }
+                __syncthreads();
+            }
+            if (live) {
+                float spw = 0.f;
+                uint32_t scn = 0u;
+                if (s >= 1) {
+#pragma unroll
+                    for (int j = 0; j < BINS; ++j) {
+                        const int n = lane + 64 * j;
+                        if (p.amask != nullptr && p.amask[n] == 0) continue;
+                        const float2 y = buf[n], gq = G[n], xs = Xg[(size_t)s * N + n];
+                        const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;
+                        const uint32_t d = rxp_slice(p.k, xs.x, xs.y) ^ rxp_slice(p.k, er, ei);
+                        const uint32_t c = (uint32_t)__popc(d) + (d != 0u ? 0x10000u : 0u);
+                        const float e2 = (er - xs.x) * (er - xs.x) + (ei - xs.y) * (ei - xs.y);
+                        cnt[j] += c;
+                        pw[j] += e2;
+                        scn += c;
+                        spw += e2;
+                    }
+                }
+                // the symbol's sums over the bins: at most N k < 2^16 bit errors and N symbol errors, so the halves do not meet
+                spw = papr_wave_reduce<false>(spw);
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) scn += (uint32_t)__shfl_xor((int)scn, o, 64);
+                if (lane == 0) {
+                    sp.sym_pow[slot * S + s] = spw;
+                    sp.sym_cnt[slot * S + s] = scn;
+                }
+            }
+            wave_sync();
+        }
+        // the waves' sums in wave order (their rows are free now): float [W][N], then uint32 [W][N]
+        __syncthreads();
+        float *redp = reinterpret_cast<float *>(rows);
+        uint32_t *redc = reinterpret_cast<uint32_t *>(redp + W * N);
+#pragma unroll
+        for (int j = 0; j < BINS; ++j) {
+            redp[wv * N + lane + 64 * j] = pw[j];
+            redc[wv * N + lane + 64 * j] = cnt[j];
+        }
+        __syncthreads();
+        for (int n = tid; n < N; n += NT) {
+            float t = 0.f;
+            uint32_t c = 0u;
+            for (int w = 0; w < W; ++w) {
+                t += redp[w * N + n];
+                c += redc[w * N + n];
+            }
+            p.part_pow[slot * N + n] = t;
+            p.part_cnt[slot * N + n] = c;
+        }
+        __syncthreads();                                              // the rows and G belong to the next point
+    }
+}
+
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_sync_kernel(const wofdm_rparams p, const wofdm_sparams sp)
+{
+    rxprof_sync_body<N>(p, sp);
+}
+
+// wofdm_rxprof_reduce_kernel per point: totals[point][cell][n] += the chunk's items of the cell, in frame order, one addition
+// per frame onto the running total (so the sums do not depend on where a chunk ends); grid (N / 64 + 1, cells the chunk
+// touches, points) -- the last block of x takes the data symbols s = 1 ... S - 1 in the bins' place
+template <int N>
+__global__ void __launch_bounds__(64) wofdm_rxprof_sync_reduce_kernel(const wofdm_rparams p, const wofdm_sparams sp, uint64_t cell0)
+{
+    const bool syms = blockIdx.x == N / 64;
+    const int n = syms ? (int)threadIdx.x + 1 : (int)(blockIdx.x * 64 + threadIdx.x), len = syms ? p.S : N;
+    if (syms && n >= p.S) return;
+    const uint64_t cell = cell0 + blockIdx.y, end = p.item0 + (uint64_t)p.n_jobs;
+    const uint64_t lo = cell * p.frames > p.item0 ? cell * p.frames : p.item0;
+    const uint64_t hi = (cell + 1) * p.frames < end ? (cell + 1) * p.frames : end;
+    if (lo >= hi) return;
+    const uint32_t pt = blockIdx.z;
+    const float *ppow = syms ? sp.sym_pow : p.part_pow;
+    const uint32_t *pcnt = syms ? sp.sym_cnt : p.part_cnt;
+    const size_t out = syms ? ((size_t)pt * sp.cells + cell) * (size_t)(p.S - 1) + (size_t)(n - 1) : ((size_t)pt * sp.cells + cell) * N + n;
+    double *tot = syms ? sp.sym_tot : p.pow;
+    unsigned long long *terr = syms ? sp.sym_errs : p.errs;
+    double acc = tot[out];
+    unsigned long long be = 0ull, se = 0ull;
+    for (uint64_t i = lo; i < hi; ++i) {
+        const size_t idx = ((size_t)(i - p.item0) * sp.n_points + pt) * (size_t)len + n;
+        const uint32_t c = pcnt[idx];
+        acc += (double)ppow[idx];
+        be += c & 0xFFFFu;
+        se += c >> 16;
+    }
+    terr[2 * out] += be;
+    terr[2 * out + 1] += se;
+    tot[out] = acc;
+}
+
 #if WOFDM_TU_N == 64
 // Philox known-answer kernel (wofdm_philox_kat): in one unit only
 __global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
@@ -1520,16 +1767,41 @@ hipError_t rx_profile_aci_launch(const wofdm_pparams *pp, const wofdm_pparams *p
     return hipGetLastError();
 }
 
+// wofdm_rx_profile_sync, one chunk: the Tx chain once, the receive kernel over the points, and the ordered sums per point
+hipError_t rx_profile_sync_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, const wofdm_sparams *spp, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N;
+    const wofdm_rparams &r = *rp;
+    const wofdm_sparams &sp = *spp;
+    if (r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
+        r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 || r.n_snr < 1)
+        return hipErrorInvalidValue;
+    if (sp.n_points < 1 || sp.n_points > WOFDM_SYNC_POINTS || sp.pts == nullptr || sp.base == nullptr || sp.sym_pow == nullptr ||
+        sp.sym_cnt == nullptr || sp.sym_errs == nullptr || sp.sym_tot == nullptr || r.S < 2 || r.S > 64 ||
+        (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames >= sp.cells)
+        return hipErrorInvalidValue;
+    hipError_t e = tx_chain_launch(*pp, s);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_sync_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                rxp_geo<N>::LDS);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_rxprof_sync_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r, sp);
+    const uint64_t cell0 = r.item0 / r.frames, cell1 = (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames;
+    hipLaunchKernelGGL(wofdm_rxprof_sync_reduce_kernel<N>, dim3(N / 64 + 1, (unsigned)(cell1 - cell0 + 1), (unsigned)sp.n_points),
+                       dim3(64), 0, s, r, sp, cell0);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 const wofdm_aux_fns *WOFDM_CAT(wofdm_aux_n, WOFDM_TU_N)(void)
 {
 #if WOFDM_TU_N <= 256
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, psd_launch, psd_batch_launch, psd_batch_masked_launch,
-                                      papr_launch, rx_profile_launch, rx_profile_aci_launch};
+                                      papr_launch, rx_profile_launch, rx_profile_aci_launch, rx_profile_sync_launch};
 #else
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, nullptr, psd_batch_launch, psd_batch_masked_launch,
-                                      papr_launch, rx_profile_launch, rx_profile_aci_launch};
+                                      papr_launch, rx_profile_launch, rx_profile_aci_launch, rx_profile_sync_launch};
 #endif
     return &fns;
 }

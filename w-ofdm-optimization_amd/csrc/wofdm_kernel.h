@@ -526,6 +526,27 @@ struct wofdm_aparams {
     int32_t Ti, ioff;
     float a_lvl;
 };
+// The receiver offsets of wofdm_rx_profile_sync, a second argument of wofdm_rxprof_sync_kernel: the Tx chain and pass 1 of an
+// item run once, pass 2 once per point with the receive windows moved by theta samples and every sample under them rotated by
+// base[point][s] e^{2 pi i eps m / n_fft} (m: index under the window).  base is prepared on the host in double precision:
+// exp(2 pi i frac(eps (s B + gam + theta) / n_fft)) for a free-running oscillator, 1 for a tracked one.  With it the partials
+// and totals of wofdm_rparams carry a leading point axis: part_pow, part_cnt [n_jobs][n_points][n_fft]; errs, pow
+// [n_points][cells][n_fft].
+#define WOFDM_SYNC_POINTS 64               // WOFDM_SYNC_MAX_POINTS of include/wofdm.h
+struct wofdm_spoint {
+    int32_t theta;                    // |theta| < B
+    float eps;                        // subcarrier spacings
+};
+struct wofdm_sparams {
+    int32_t n_points;
+    uint64_t cells;
+    const wofdm_spoint *pts;          // [n_points]
+    const float2 *base;               // [n_points][S]
+    float *sym_pow;                   // [n_jobs][n_points][S] sum over the loaded bins of |Xhat - X|^2 of symbol s (s = 0: 0)
+    uint32_t *sym_cnt;                // [n_jobs][n_points][S] bit errors | symbol errors << 16 of symbol s
+    unsigned long long *sym_errs;     // [n_points][cells][S - 1][2], accumulated into
+    double *sym_tot;                  // [n_points][cells][S - 1], accumulated into
+};
 
 // the launchers of one DFT length
 struct wofdm_aux_fns {
@@ -561,6 +582,9 @@ struct wofdm_aux_fns {
     // receive kernel, which adds the neighbour's waveform a->xi through a->hi to every received sample of pass 2.
     hipError_t (*rx_profile_aci)(const wofdm_pparams *p, const wofdm_pparams *pa, const wofdm_rparams *r, const wofdm_aparams *a,
                                  hipStream_t s);
+    // The same under receiver timing and carrier offsets (wofdm_rx_profile_sync): the Tx chain once, wofdm_rxprof_sync_kernel
+    // (pass 1 once per item, pass 2 once per point of sp), and the ordered sums per point, per bin and per data symbol.
+    hipError_t (*rx_profile_sync)(const wofdm_pparams *p, const wofdm_rparams *r, const wofdm_sparams *sp, hipStream_t s);
 };
 const wofdm_aux_fns *wofdm_aux_n64(void);
 const wofdm_aux_fns *wofdm_aux_n128(void);

@@ -12,6 +12,10 @@ randomness given, ``rx_profile_host`` draws the same Philox streams on the host 
 
 ``rx_profile_aci_gpu`` (``wofdm_rx_profile_aci``) is the same profile with an asynchronous adjacent-band neighbour on the
 air -- the interference the Rx window is there to reject; ``frame_profile_aci`` and ``rx_profile_aci_host`` mirror it.
+
+``rx_profile_sync_gpu`` (``wofdm_rx_profile_sync``) is the profile under receiver timing and carrier-frequency offset, a
+list of ``SyncPoint`` per call, per subcarrier and per data symbol; ``frame_profile_sync`` and ``rx_profile_sync_host``
+mirror it.
 """
 import collections
 
@@ -20,6 +24,17 @@ import numpy as np
 RxProfile = collections.namedtuple("RxProfile", "bit_err sym_err err_power decisions")
 RxProfile.__doc__ = """bit_err, sym_err (uint64), err_power (float64): [pairs, n_snr, n_ch, N]; decisions [N]: hard decisions a
 bin took per cell = frames * (S - 1) on the loaded bins, 0 on the others."""
+
+RxProfileSync = collections.namedtuple("RxProfileSync", "bit_err sym_err err_power bit_err_sym sym_err_sym err_power_sym decisions")
+RxProfileSync.__doc__ = """bit_err, sym_err (uint64), err_power (float64): [points, pairs, n_snr, n_ch, N] as ``RxProfile``'s per
+point; bit_err_sym, sym_err_sym (uint64), err_power_sym (float64): [points, pairs, n_snr, n_ch, S - 1], the same three sums
+over the loaded bins per data symbol s = 1 ... S - 1; decisions [N] as ``RxProfile``'s (per point)."""
+
+SyncPoint = collections.namedtuple("SyncPoint", "timing cfo cfo_tracked", defaults=(0.0, 1))
+SyncPoint.__doc__ = """One receiver offset of ``wofdm_rx_profile_sync``: timing (theta, samples: the receive windows begin theta
+samples late (> 0) or early (< 0), |theta| < B), cfo (epsilon, in subcarrier spacings, |epsilon| <= 4, used as stored in
+single precision), cfo_tracked (0: free-running oscillator, every sample rotated by e^{2 pi i epsilon a / N} at its on-air
+index a; 1: the common phase of every symbol removed, e^{2 pi i epsilon m / N} at index m under the window)."""
 
 NEAR_TOL = 1e-4
 
@@ -190,6 +205,21 @@ def gen_noise(noise_len, seed, cell, frame):
     w = _stream(seed, 1, cell, frame, (noise_len + 1) // 2).reshape(-1, 2)[:noise_len]
     u1 = (w[:, 0].astype(np.float32).astype(np.float64) * 2.0 ** -32 + 2.0 ** -33).astype(np.float32).astype(np.float64)
     u2 = (w[:, 1] >> np.uint64(9)).astype(np.float64) * 2.0 ** -23
+    return np.sqrt(-2.0 * np.log(u1)) * np.exp(2j * np.pi * u2)
+
+
+def gen_noise_at(idx, seed, cell, frame):
+    """Complex unit normals of stream 1 of (seed, cell, frame) at the sample indices ``idx`` (any integers, any shape): sample a
+    is that of counter word a mod 2^32 -- block (a mod 2^32) >> 1, word pair a & 1 --, so on [0, noise_len) this is
+    ``gen_noise`` and a negative index lands on words no frame uses."""
+    a = np.asarray(idx, dtype=np.int64) & np.int64(0xFFFFFFFF)
+    seed, frame = int(seed) & (2 ** 64 - 1), int(frame) & (2 ** 64 - 1)
+    w = _philox((a >> 1).astype(np.uint64), frame & 0xFFFFFFFF, frame >> 32, (1 << 28) | (int(cell) & 0x0FFFFFFF),
+                seed & 0xFFFFFFFF, seed >> 32)
+    odd = (a & 1) != 0
+    w0, w1 = np.where(odd, w[..., 2], w[..., 0]), np.where(odd, w[..., 3], w[..., 1])
+    u1 = (w0.astype(np.float32).astype(np.float64) * 2.0 ** -32 + 2.0 ** -33).astype(np.float32).astype(np.float64)
+    u2 = (w1 >> np.uint64(9)).astype(np.float64) * 2.0 ** -23
     return np.sqrt(-2.0 * np.log(u1)) * np.exp(2j * np.pi * u2)
 
 
@@ -393,10 +423,174 @@ def rx_profile_aci_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db,
 
 
 def rx_profile_kernel_ms():
-    """Milliseconds the kernels of this thread's last ``rx_profile_gpu`` or ``rx_profile_aci_gpu`` call took
-    (``wofdm_rx_profile_kernel_ms``)."""
+    """Milliseconds the kernels of this thread's last ``rx_profile_gpu``, ``rx_profile_aci_gpu`` or ``rx_profile_sync_gpu``
+    call took (``wofdm_rx_profile_kernel_ms``)."""
     import ctypes as C
     from . import _lib
     ms = C.c_float()
     _lib.check(_lib.load().wofdm_rx_profile_kernel_ms(C.byref(ms)))
     return float(ms.value)
+
+
+# ---- under receiver timing and carrier-frequency offset (wofdm_rx_profile_sync) ----
+
+def _sync_front(st, grids, noise_at, w_tx, h, snr_db, active, mask, noise_before_truncate):
+    """What the points of a frame share: X [S, N], conv(h, x) [T + taps - 1], the noise gain g (``frame_profile``'s: the
+    offsets never touch it) and the loaded bins."""
+    from . import timefreq as T
+    X = np.asarray(grids, dtype=np.complex128)
+    n = st.n_fft
+    S, B = X.shape[0], st.sym_len - st.tail_tx
+    if X.shape != (S, n) or B != n + st.tail_rx + st.prefix_rm:
+        raise ValueError("grids must be [S, %d] and the structure consistent" % n)
+    on = np.ones(n, dtype=bool) if active is None else np.asarray(active).reshape(-1) != 0
+    tx = T.tx_waveform(st, X.T, np.asarray(w_tx, np.float64), st.tail_tx, mask, guard_band=None)
+    conv = np.convolve(np.asarray(h, dtype=np.complex128).reshape(-1), tx)
+    nl = conv.size if noise_before_truncate else S * B
+    noise = np.asarray(noise_at(np.arange(nl, dtype=np.int64)), dtype=np.complex128)
+    ps, pn = np.mean(np.abs(conv[:nl]) ** 2), np.mean(np.abs(noise) ** 2)
+    return X, conv, np.sqrt(ps * 10.0 ** (-0.1 * float(snr_db)) / pn), on
+
+
+def _sync_point(st, front, noise_at, w_rx, point, bits_per_sc):
+    """One point on a frame's shared part: ``frame_profile_sync``'s outputs and Y [S, N]"""
+    X, conv, g, on = front
+    n, delta, gam, k = st.n_fft, st.tail_rx, st.prefix_rm, int(bits_per_sc)
+    S, B = X.shape[0], st.sym_len - st.tail_tx
+    theta, eps = int(point.timing), float(np.float32(point.cfo))
+    if abs(theta) >= B or not abs(eps) <= 4.0 or point.cfo_tracked not in (0, 1):
+        raise ValueError("a point needs |timing| < %d, |cfo| <= 4 and cfo_tracked in (0, 1)" % B)
+    m = np.arange(n + delta, dtype=np.int64)
+    a = (np.arange(S, dtype=np.int64) * B + gam + theta)[:, None] + m[None, :]          # on-air index of every sample used
+    inside = (a >= 0) & (a < conv.size)
+    r = np.where(inside, conv[np.clip(a, 0, conv.size - 1)], 0.0) + g * np.asarray(noise_at(a), dtype=np.complex128)
+    turns = eps * (m[None, :] if point.cfo_tracked else a).astype(np.float64) / n      # (exact: 24 bits times an integer)
+    blocks = r * np.exp(2j * np.pi * (turns - np.round(turns))) * np.asarray(w_rx, np.float64)[None, :]
+    z = blocks[:, :n].copy()
+    z[:, :delta] += blocks[:, n:]
+    Y = np.fft.fft(np.roll(z, -(st.circ_shift + delta // 2), axis=1), axis=1)
+    xhat = np.zeros((S - 1, n), dtype=np.complex128)
+    xhat[:, on] = Y[1:, on] / (Y[0, on] / X[0, on])[None, :]
+    d = np.where(on[None, :], slice_labels(k, X[1:]) ^ slice_labels(k, xhat), 0)
+    bits = sum((d >> b) & 1 for b in range(k))
+    err = np.where(on[None, :], np.abs(xhat - X[1:]) ** 2, 0.0)
+    return (bits.sum(axis=0).astype(np.uint64), (d != 0).sum(axis=0).astype(np.uint64), err.sum(axis=0), xhat,
+            np.where(on, Y[0], 0.0), bits.sum(axis=1).astype(np.uint64), (d != 0).sum(axis=1).astype(np.uint64),
+            err.sum(axis=1), Y)
+
+
+def frame_profile_sync(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, active=None, mask=None,
+                       noise_before_truncate=1, with_y=False):
+    """fp64 host mirror of one frame and one point of ``wofdm_rx_profile_sync``: ``frame_profile`` with the receive windows
+    moved by ``point.timing`` samples and the oscillator off by ``point.cfo`` subcarrier spacings.  noise_at(idx) -> the
+    complex unit normals at the integer sample indices idx (``gen_noise_at`` of the frame): the received signal is r[a] =
+    conv(h, x)[a] + g n[a] for every integer a, conv zero outside [0, T + taps - 1), g from Ps and Pn over [0, noise_len) as
+    in ``frame_profile``; sample m of symbol s sits at a = s B + prefix_rm + timing + m and is multiplied by e^{2 pi i cfo a /
+    N} (free-running) or e^{2 pi i cfo m / N} (tracked) before the Rx window; the pilot sees the same offsets.  Returns
+    (bit_err [N], sym_err [N], err_power [N], xhat [S-1, N], y0 [N], bit_err_sym [S-1], sym_err_sym [S-1], err_power_sym
+    [S-1]) -- the first five are ``frame_profile``'s, exactly, at timing = 0, cfo = 0 --; with_y=True: Y [S, N] as a ninth."""
+    front = _sync_front(st, grids, noise_at, w_tx, h, snr_db, active, mask, noise_before_truncate)
+    out = _sync_point(st, front, noise_at, w_rx, point, bits_per_sc)
+    return out if with_y else out[:8]
+
+
+def _prepare_sync(points):
+    pts = [SyncPoint(*q) for q in points]
+    pts = [SyncPoint(int(q.timing), float(np.float32(q.cfo)), int(q.cfo_tracked)) for q in pts]
+    if not pts:
+        raise ValueError("at least one point is needed")
+    return pts
+
+
+def rx_profile_sync_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points,
+                         active=None, mask=None, noise_before_truncate=1, with_near=False):
+    """The host route of ``rx_profile_sync_gpu``: the frames of ``rx_profile_host`` from the same Philox streams, each through
+    ``frame_profile_sync`` for every point of ``points`` (``SyncPoint`` or (timing, cfo, cfo_tracked) tuples); the Tx chain,
+    the channel and the noise gain of a frame are shared by its points.  Returns ``RxProfileSync``; with_near=True: also the
+    number of ``near_decisions`` per point and cell [points, pairs, n_snr, n_ch]."""
+    from . import timefreq as T
+    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts = _prepare_sync(points)
+    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, hc.shape[0], st.n_fft
+    k, S, B = int(bits_per_sc), int(syms), st.sym_len - st.tail_tx
+    tab = T.qam_table(k)
+    nl = _noise_len(st, S, hc.shape[1], noise_before_truncate)
+    on = np.ones(n, dtype=bool) if act is None else act != 0
+    # the sample indices a frame's points read, as one range
+    lo = min(0, st.prefix_rm + min(q.timing for q in pts))
+    hi = max(nl, (S - 1) * B + st.prefix_rm + max(q.timing for q in pts) + n + st.tail_rx)
+    shape = (len(pts), pairs, n_snr, n_ch)
+    bit = np.zeros(shape + (n,), dtype=np.uint64)
+    sym = np.zeros_like(bit)
+    pw = np.zeros(bit.shape, dtype=np.float64)
+    sbit = np.zeros(shape + (S - 1,), dtype=np.uint64)
+    ssym = np.zeros_like(sbit)
+    spw = np.zeros(sbit.shape, dtype=np.float64)
+    near = np.zeros(shape, dtype=np.int64)
+    for cell in range(pairs * n_snr * n_ch):
+        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
+        for f in range(int(frames)):
+            fr = int(frame_offset) + f
+            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
+            noise = gen_noise_at(np.arange(lo, hi, dtype=np.int64), seed, cell, fr)
+
+            def noise_at(idx, noise=noise):
+                return noise[np.asarray(idx, dtype=np.int64) - lo]
+            front = _sync_front(st, grid, noise_at, w_tx[p], hc[c], snr[s], act, m, noise_before_truncate)
+            for i, q in enumerate(pts):
+                b, se, e, xhat, y0, sb, ss, sp = _sync_point(st, front, noise_at, w_rx[p], q, k)[:8]
+                bit[i, p, s, c] += b
+                sym[i, p, s, c] += se
+                pw[i, p, s, c] += e
+                sbit[i, p, s, c] += sb
+                ssym[i, p, s, c] += ss
+                spw[i, p, s, c] += sp
+                if with_near:
+                    near[i, p, s, c] += int(near_decisions(k, xhat, y0).sum())
+    prof = RxProfileSync(bit, sym, pw, sbit, ssym, spw, _decisions(st, S, frames, act))
+    return (prof, near) if with_near else prof
+
+
+def rx_profile_sync_chunk_frames(st, syms, masked, n_points):
+    """Frames one chunk of ``wofdm_rx_profile_sync`` holds (include/wofdm.h: the symbol grid, the waveform and -- masked -- the
+    filtered symbols of a frame, and per point its per-bin and per-symbol partials; at most 65535)."""
+    from . import _lib
+    P = st.sym_len
+    T = st.tail_tx + syms * (P - st.tail_tx)
+    per_frame = 8 * (syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0)) + 8 * int(n_points) * (st.n_fft + syms)
+    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+
+
+def rx_profile_sync_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points,
+                        active=None, mask=None, noise_before_truncate=1, device=0, out=None):
+    """``wofdm_rx_profile_sync``: ``rx_profile_gpu`` of the same arguments for every receiver offset of ``points``
+    (``SyncPoint`` or (timing, cfo, cfo_tracked) tuples, at most ``_lib.SYNC_MAX_POINTS``) in ONE call -- the Tx chain and the
+    power pass run once per frame --, per subcarrier and per data symbol.  Returns ``RxProfileSync``; ``out`` (an earlier
+    result of the same shape) is accumulated into.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    from .simulation import make_cfg
+    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts = _prepare_sync(points)
+    cpts = (_lib.SyncPoint * len(pts))(*[_lib.SyncPoint(q.timing, q.cfo, q.cfo_tracked, 0) for q in pts])
+    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0]
+    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[1], n_ch, n_snr, pairs, bool(noise_before_truncate),
+                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
+    shape = (len(pts), pairs, n_snr, n_ch)
+    errs = np.zeros(shape + (st.n_fft, 2), dtype=np.uint64)
+    pw = np.zeros(shape + (st.n_fft,), dtype=np.float64)
+    serrs = np.zeros(shape + (int(syms) - 1, 2), dtype=np.uint64)
+    spw = np.zeros(shape + (int(syms) - 1,), dtype=np.float64)
+    hf = _lib.c64_as_f32(hc)
+    _lib.check(_lib.load().wofdm_rx_profile_sync(
+        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
+        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, len(pts), cpts, errs.ctypes.data,
+        pw.ctypes.data, serrs.ctypes.data, spw.ctypes.data))
+    prof = RxProfileSync(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
+                         np.ascontiguousarray(serrs[..., 0]), np.ascontiguousarray(serrs[..., 1]), spw,
+                         _decisions(st, syms, frames, act))
+    if out is not None:
+        if out.bit_err.shape != prof.bit_err.shape:
+            raise ValueError("out has another shape")
+        prof = RxProfileSync(*(a + b for a, b in zip(out, prof)))
+    return prof
