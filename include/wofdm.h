@@ -433,7 +433,8 @@ int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device,
 /* *ms = milliseconds (HIP events) the kernels of the calling thread's last successful wofdm_rx_profile or
  * wofdm_rx_profile_aci call took (whichever came last), first chunk to last; 0 before any.  Measurement aid
  * (tools/bench_rx_profile.py, tools/bench_rx_profile_aci.py).  A successful wofdm_rx_profile_sync call (below) counts as
- * such a call too: the figure is then that of its whole sweep (tools/bench_rx_profile_sync.py). */
+ * such a call too: the figure is then that of its whole sweep (tools/bench_rx_profile_sync.py); so does a successful
+ * wofdm_rx_profile_doppler call, with all its tracks (tools/bench_rx_profile_doppler.py). */
 int wofdm_rx_profile_kernel_ms(float *ms);
 
 /* wofdm_rx_profile under receiver timing and carrier-frequency offset: what the victim of wofdm_rx_profile loses, bin by bin
@@ -489,6 +490,52 @@ int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device,
                           double *err_power,                /* [n_points][cells][n_fft], or NULL */
                           uint64_t *sym_errs,               /* [n_points][cells][S-1][2], or NULL */
                           double *sym_power);               /* [n_points][cells][S-1], or NULL */
+
+/* wofdm_rx_profile over channels that MOVE within the frame: what the victim of wofdm_rx_profile loses, bin by bin and symbol
+ * by symbol, when the taps drift under a receiver that equalises with the pilot of symbol 0 alone -- the mobility the channel
+ * generator names (channels.gen_chan_track: Veh-A, 2 GHz, 100 km/h, f_D = 185 Hz), where both the Rx window (ICI rejection)
+ * and the distance from the pilot matter.  Every other call here holds one snapshot of the channel for the whole frame.  A call
+ * takes a LIST of tracks, typically the same realisations at several speeds, and runs the Tx chain once per frame, whatever
+ * n_tracks is; every track sees the same labels and the same noise, so a comparison across tracks is paired.
+ *   Victim: exactly wofdm_rx_profile -- frames, cells, streams 0 and 1, allocation, mask, both noise_before_truncate orders, the
+ * gate; the noise of on-air sample a is the unit normal the plain kernel uses for it.
+ *   Channel: h_track[track][channel][q] is the tap vector at on-air index q knot_step (knot q).  For the receive index a, q =
+ * min(a div knot_step, n_knots - 2), f = (a - q knot_step) / knot_step and h_l[a] = K[q][l] + f (K[q+1][l] - K[q][l]) -- in this
+ * form, so that equal knots give the knot back exactly --, and conv[a] = sum_l h_l[a] x[a - l], 0 <= a < T + n_taps - 1: the tap
+ * is taken at the OUTPUT sample's time.  Ps, Pn and the noise gain g are measured as in wofdm_rx_profile, on this conv, per
+ * track.  Rx window, fold, shift, DFT, the pilot LS estimate from symbol 0, equaliser, slicer and counters are unchanged.
+ *   Outputs (host), ACCUMULATED into, with the shapes and the ordered sums of wofdm_rx_profile_sync, "track" for "point":
+ * errs[n_tracks][cells][n_fft][2], err_power[n_tracks][cells][n_fft] (or NULL), sym_errs[n_tracks][cells][S-1][2] and
+ * sym_power[n_tracks][cells][S-1] (either may be NULL).  Integer counters are exact; float sums per frame in fp32 in the sync
+ * kernel's order, over the frames of a cell in fp64, one addition per frame --, so repeated calls give identical bits, a split
+ * frame range gives the integer counters of one call, and a track's results do not depend on which other tracks share its
+ * call.  A track whose knots all equal h[channel] gives the bits of wofdm_rx_profile, err_power bytes included (as long as no
+ * cell's frames are split over two chunks of that call).
+ *   Every limit and check of wofdm_rx_profile applies.  WOFDM_E_INVALID: NULL h_track or errs, n_tracks < 1, n_knots < 2,
+ * knot_step < 1, a non-finite knot, a track that does not cover the frame: (n_knots - 1) knot_step < tail_tx + S B + n_taps - 2;
+ * WOFDM_E_UNSUPPORTED: n_tracks > WOFDM_DOPPLER_MAX_TRACKS, n_knots > WOFDM_DOPPLER_MAX_KNOTS.  Every argument is checked
+ * before the device is touched; a failed call leaves all four outputs as they were.
+ *   Chunks: min(65535, WOFDM_RX_PROFILE_CHUNK_BYTES / (8 (S n_fft + T + [mask] S (2P-1)) + 8 n_tracks (n_fft + S)))  frames --
+ * wofdm_rx_profile_sync's formula with the tracks for its points.
+ *   A successful call counts for wofdm_rx_profile_kernel_ms.
+ *   Measured on an MI355X (tools/bench_rx_profile_doppler.py, profiles/rx_profile_doppler.txt): on 64 cells x 2000 frames x
+ * 16 symbols at n_fft = 256 one track takes 41.7 ms of kernels (72.3 ms masked), 1.17 (1.09) times one wofdm_rx_profile call on
+ * the same cells and frames in the same run; four tracks take 94.3 (122.1) ms, 2.65 (1.84) times -- 0.49 (0.25) of a plain call
+ * per additional track. */
+#define WOFDM_DOPPLER_MAX_TRACKS 16
+#define WOFDM_DOPPLER_MAX_KNOTS  64
+int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device,
+                             const float *w_tx,             /* [pairs][P] */
+                             const float *w_rx,             /* [pairs][N+tail_rx] */
+                             const float *h_track,          /* [n_tracks][n_channels][n_knots][n_taps][2] */
+                             int32_t n_tracks, int32_t n_knots, int32_t knot_step,
+                             const float *snr_db,           /* [n_snr] */
+                             const uint8_t *active,         /* [n_fft] or NULL */
+                             const float *tx_mask,          /* [2P-1] or NULL */
+                             uint64_t *errs,                /* [n_tracks][cells][n_fft][2], ACCUMULATED into */
+                             double *err_power,             /* [n_tracks][cells][n_fft], or NULL */
+                             uint64_t *sym_errs,            /* [n_tracks][cells][S-1][2], or NULL */
+                             double *sym_power);            /* [n_tracks][cells][S-1], or NULL */
 
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

@@ -14,7 +14,8 @@ as ``wofdm_amd`` through the shim module at the repository root.
   channel_mask main_channel_mask.m: half-band loading + spectral Tx mask (GPU: allocation / tx_mask)
   rx_profile   per-subcarrier BER / EVM of the frames the BER loop runs (GPU: wofdm_rx_profile; fp64 host mirror), alone or
                beside an asynchronous adjacent-band neighbour (GPU: wofdm_rx_profile_aci), or under receiver timing and
-               carrier-frequency offset (GPU: wofdm_rx_profile_sync)
+               carrier-frequency offset (GPU: wofdm_rx_profile_sync), or over channels that move within the frame
+               (GPU: wofdm_rx_profile_doppler)
   _lib         ctypes binding of libwofdm_hip.so (include/wofdm.h)
 """
 from . import variants  # noqa: F401
@@ -33,12 +34,13 @@ from .simulation import (Plan, ber_for_window_file, error_rates, make_cfg,  # no
 from ._lib import kernel_source_hash  # noqa: F401
 from .timefreq import (frame_papr, papr_ccdf, papr_hist, run_timefreq, tx_papr_gpu,  # noqa: F401
                        tx_psd_batch_gpu, tx_waveform)
-from .channel_mask import (aci_for_window_file, interference_for_window_file, papr_for_window_file,  # noqa: F401
-                           profile_for_window_file, spectrum_for_window_file, sync_for_window_file)
+from .channel_mask import (aci_for_window_file, doppler_for_window_file, interference_for_window_file,  # noqa: F401
+                           papr_for_window_file, profile_for_window_file, spectrum_for_window_file, sync_for_window_file)
 from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_db, frame_profile,  # noqa: F401
                          frame_profile_aci, frame_profile_sync, gen_noise_at, rx_profile_aci_gpu, rx_profile_aci_host,
                          rx_profile_gpu, rx_profile_host, rx_profile_sync_chunk_frames, rx_profile_sync_gpu,
-                         rx_profile_sync_host)
+                         rx_profile_sync_host, frame_profile_doppler, rx_profile_doppler_chunk_frames,
+                         rx_profile_doppler_gpu, rx_profile_doppler_host, tv_conv)
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

@@ -28,6 +28,9 @@ TX_PAPR_MAX_PERIODS = 1 << 20
 RX_PROFILE_CHUNK_BYTES = 256 << 20
 #: wofdm_rx_profile_sync (include/wofdm.h): most points one call takes
 SYNC_MAX_POINTS = 64
+#: wofdm_rx_profile_doppler (include/wofdm.h): most tracks one call takes, most knots a track has
+DOPPLER_MAX_TRACKS = 16
+DOPPLER_MAX_KNOTS = 64
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -39,7 +42,7 @@ EXPORTS = (
     "wofdm_interference", "wofdm_tx_psd", "wofdm_tx_psd_batch", "wofdm_tx_psd_batch_masked",
     "wofdm_interference_masked", "wofdm_tx_papr", "wofdm_tx_papr_kernel_ms",
     "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms", "wofdm_plan_kernel_geo", "wofdm_cfg_geo_id",
-    "wofdm_rx_profile_aci", "wofdm_rx_profile_sync",
+    "wofdm_rx_profile_aci", "wofdm_rx_profile_sync", "wofdm_rx_profile_doppler",
 )
 
 
@@ -159,6 +162,7 @@ def load():
     L.wofdm_rx_profile_aci.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.c_float, vp, vp]
     L.wofdm_rx_profile_kernel_ms.argtypes = [C.POINTER(C.c_float)]
     L.wofdm_rx_profile_sync.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, i32, C.POINTER(SyncPoint), vp, vp, vp, vp]
+    L.wofdm_rx_profile_doppler.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     _LIB = L
     return L
 

@@ -368,6 +368,45 @@ def sync_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_s
     return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
 
 
+def doppler_for_window_file(type_ofdm, cp, windows, tracks, knot_step, snr_db, num_subcar=256, bits_per_subcar=4,
+                            symbols_per_tx=16, ensemble=100, roll_off=ROLL_OFF, seed=0, frame_range=None, gpu=True, device=0,
+                            tail_tx=8, tail_rx=10):
+    """The mobility side of the mask experiment: ``profile_for_window_file`` over channels that move within the frame, under
+    a receiver that equalises with the pilot of symbol 0 alone -- where both the Rx window (ICI rejection) and the distance
+    from the pilot matter.  Every window pair of the file + the RC pair under half-band loading, for every SNR point, channel
+    and track of ``tracks`` [n_tracks, n_channels, n_knots, taps] (``channels.gen_channel_tracks``: the same realisations at
+    several speeds; knot q at on-air index q * knot_step), plain and masked (``tx_mask(P)``) -- on the GPU two
+    ``wofdm_rx_profile_doppler`` calls whatever the number of tracks: the Tx chain of a frame runs once for all of them
+    (gpu=False: the fp64 host route ``rx_profile.rx_profile_doppler_host``, for small ensembles).  The frames are those of
+    ``profile_for_window_file`` with the same arguments, so a track whose knots all equal its channel is that result.
+    Returns {name: {"profile", "profile_masked"}} with the names of ``V.matlab_pair_plan``; each an
+    ``rx_profile.RxProfileSync`` of that pair, arrays [tracks, n_snr, n_channels, N] and [tracks, n_snr, n_channels, S - 1]."""
+    from . import rx_profile as R
+    n = num_subcar
+    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
+                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
+    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
+    plan = V.matlab_pair_plan(type_ofdm)
+
+    def pick(key, side):
+        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
+
+    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
+    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
+    alloc = half_band_allocation(n)
+    mask = tx_mask(st.sym_len, roll_off)
+    first, count = (0, ensemble) if frame_range is None else frame_range
+    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.asarray(tracks), knot_step, snr_db, seed, first, count)
+    run = R.rx_profile_doppler_gpu if gpu else R.rx_profile_doppler_host
+    kw = dict(active=alloc, device=device) if gpu else dict(active=alloc)
+    plain = run(*args, **kw)
+    masked = run(*args, mask=mask, **kw)
+
+    def of_pair(prof, i):
+        return R.RxProfileSync(*(a[:, i] for a in prof[:6]), prof.decisions)
+    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
+
+
 def results_from_counts(names, masked, plain):
     def ber(c):      # mean over channels of per-channel BER (lines 84-117)
         return (c[..., 0] / np.maximum(c[..., 1], 1)).mean(axis=-1)

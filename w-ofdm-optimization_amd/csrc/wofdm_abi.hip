@@ -1496,17 +1496,28 @@ struct sync_args {
     uint64_t *sym_errs;
     double *sym_power;
 };
+// the moving channels of wofdm_rx_profile_doppler (they take the place of h) and its per-symbol outputs; a null pointer to it
+// is a channel that holds still over the frame
+struct doppler_args {
+    const float *h_track;
+    int32_t n_tracks, n_knots, knot_step;
+    uint64_t *sym_errs;
+    double *sym_power;
+};
 
-// wofdm_rx_profile, wofdm_rx_profile_aci and wofdm_rx_profile_sync.  Every argument is checked before the first HIP call; the
+// wofdm_rx_profile, wofdm_rx_profile_aci, wofdm_rx_profile_sync and wofdm_rx_profile_doppler.  Every argument is checked before the first HIP call; the
 // caller's arrays are written only after everything has succeeded.
 int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                     const float *snr_db, const uint8_t *active, const float *tx_mask, const aci_args *aci, const sync_args *sync,
-                    uint64_t *errs, double *err_power)
+                    const doppler_args *dop, uint64_t *errs, double *err_power)
 {
-    if (!cfg || !w_tx || !w_rx || !h || !snr_db || !errs) return fail(WOFDM_E_INVALID, "NULL argument");
+    if (!cfg || !w_tx || !w_rx || !(dop ? dop->h_track : h) || !snr_db || !errs) return fail(WOFDM_E_INVALID, "NULL argument");
     if (aci && !aci->active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active)");
     if (sync && !sync->points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
     if (sync && sync->n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", sync->n_points);
+    if (dop && (dop->n_tracks < 1 || dop->n_knots < 2 || dop->knot_step < 1))
+        return fail(WOFDM_E_INVALID, "n_tracks=%d must be >= 1, n_knots=%d >= 2, knot_step=%d >= 1", dop->n_tracks, dop->n_knots,
+                    dop->knot_step);
     const int N = cfg->n_fft, k = cfg->bits_per_sc, S = cfg->syms_per_frame, L = cfg->n_taps;
     if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
         return fail(WOFDM_E_UNSUPPORTED, "n_fft=%d not in {64,128,256,512,1024}", N);
@@ -1539,7 +1550,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         return true;
     };
     if (!finite(w_tx, (size_t)pairs * P) || !finite(w_rx, (size_t)pairs * NW)) return fail(WOFDM_E_INVALID, "windows must be finite");
-    if (!finite(h, (size_t)cfg->n_channels * L * 2)) return fail(WOFDM_E_INVALID, "channel taps must be finite");
+    if (!dop && !finite(h, (size_t)cfg->n_channels * L * 2)) return fail(WOFDM_E_INVALID, "channel taps must be finite");
     if (!finite(snr_db, (size_t)cfg->n_snr)) return fail(WOFDM_E_INVALID, "SNR points must be finite");
     if (tx_mask && !finite(tx_mask, (size_t)Lm)) return fail(WOFDM_E_INVALID, "mask gains must be finite");
     std::vector<uint8_t> hact;
@@ -1563,7 +1574,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         for (int n = 0; n < N; ++n) nb |= (hiact[(size_t)n] = aci->active[n] ? 1 : 0) != 0;
     }
     // the receiver offsets: the base phasor of every (point, symbol) in double precision, from cfo as stored
-    const int NP = sync ? sync->n_points : 1;
+    const int NP = sync ? sync->n_points : (dop ? dop->n_tracks : 1);
     std::vector<wofdm_spoint> hpts;
     std::vector<float2> hbase;
     if (sync) {
@@ -1594,6 +1605,17 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
             }
         }
     }
+    // the moving channels: every knot finite, and the knots reach the last sample of conv, index T + L - 2
+    if (dop) {
+        if (NP > WOFDM_DOPPLER_MAX_TRACKS) return fail(WOFDM_E_UNSUPPORTED, "n_tracks=%d exceeds %d", NP, WOFDM_DOPPLER_MAX_TRACKS);
+        if (dop->n_knots > WOFDM_DOPPLER_MAX_KNOTS)
+            return fail(WOFDM_E_UNSUPPORTED, "n_knots=%d exceeds %d", dop->n_knots, WOFDM_DOPPLER_MAX_KNOTS);
+        if (!finite(dop->h_track, (size_t)NP * cfg->n_channels * dop->n_knots * L * 2))
+            return fail(WOFDM_E_INVALID, "channel knots must be finite");
+        if ((int64_t)(dop->n_knots - 1) * (int64_t)dop->knot_step < (int64_t)T + L - 2)
+            return fail(WOFDM_E_INVALID, "the knots end at sample %lld, the frame's last at %d: (n_knots - 1) knot_step >= "
+                        "tail_tx + S B + n_taps - 2 required", (long long)(dop->n_knots - 1) * dop->knot_step, T + L - 2);
+    }
     int rc = use_device(device);
     if (rc != WOFDM_OK) return rc;
     g_rxprof_ms = 0.f;
@@ -1602,9 +1624,9 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     // frames per chunk: what the budget holds (symbol grid + waveform + filtered symbols + partials of a frame; with a neighbour
     // its S + 1 symbols beside them), as the header documents it
     const int Ti = T + B;
-    // (under receiver offsets the partials are per point, per bin and per symbol)
+    // (under receiver offsets or moving channels the partials are per point or track, per bin and per symbol)
     const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) +
-                                       (sync ? (uint64_t)NP * (uint64_t)(N + S) : (uint64_t)N) +
+                                       (sync || dop ? (uint64_t)NP * (uint64_t)(N + S) : (uint64_t)N) +
                                        (nb ? (uint64_t)(S + 1) * N + (uint64_t)Ti + (tx_mask ? (uint64_t)(S + 1) * Lm : 0ull) : 0ull));
     const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
                                                                        std::max<uint64_t>(1, WOFDM_RX_PROFILE_CHUNK_BYTES / job_bytes)));
@@ -1615,11 +1637,21 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     }
     geom g{};
     g.L = L;
-    const std::vector<float2> hp = pack_taps(cfg, g, h);
+    // the taps as the kernels read them; of moving channels the knots, [n_tracks][n_channels][n_knots][WOFDM_LT], zero padded
+    std::vector<float2> hp;
+    if (dop) {
+        const size_t rows = (size_t)NP * cfg->n_channels * dop->n_knots;
+        hp.assign(rows * WOFDM_LT, make_float2(0.f, 0.f));
+        for (size_t r = 0; r < rows; ++r)
+            for (int l = 0; l < L; ++l)
+                hp[r * WOFDM_LT + l] = make_float2(dop->h_track[2 * (r * L + l)], dop->h_track[2 * (r * L + l) + 1]);
+    } else {
+        hp = pack_taps(cfg, g, h);
+    }
     std::vector<float> nlin((size_t)cfg->n_snr);
     for (int i = 0; i < cfg->n_snr; ++i) nlin[(size_t)i] = (float)std::pow(10.0, -0.1 * (double)snr_db[i]);
     const size_t n_w = (size_t)pairs * P, n_wr = (size_t)pairs * NW, n_out = (size_t)NP * cells * N;
-    const size_t n_sym = sync ? (size_t)NP * cells * (S - 1) : 0;
+    const size_t n_sym = sync || dop ? (size_t)NP * cells * (S - 1) : 0;
     dev_buf<float> d_w, d_wr, d_nlin, d_ppow;
     dev_buf<uint8_t> d_act;
     dev_buf<float2> d_h, d_spec, d_X, d_x, d_Y;
@@ -1647,11 +1679,11 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     dev_buf<uint32_t> d_scnt;
     dev_buf<unsigned long long> d_serrs;
     dev_buf<double> d_stot;
-    if (sync) {
-        if (!d_pts.alloc(hpts.size()) || !d_base.alloc(hbase.size()) || !d_spow.alloc((size_t)chunk * NP * S) ||
+    if (sync || dop) {
+        if ((sync && (!d_pts.alloc(hpts.size()) || !d_base.alloc(hbase.size()))) || !d_spow.alloc((size_t)chunk * NP * S) ||
             !d_scnt.alloc((size_t)chunk * NP * S) || !d_serrs.alloc(2 * n_sym) || !d_stot.alloc(n_sym))
-            return fail(WOFDM_E_NOMEM, "device allocation failed (receiver offsets)");
-        if (!d_pts.upload(hpts.data(), hpts.size()) || !d_base.upload(hbase.data(), hbase.size()) ||
+            return fail(WOFDM_E_NOMEM, "device allocation failed (receiver offsets or tracks)");
+        if ((sync && (!d_pts.upload(hpts.data(), hpts.size()) || !d_base.upload(hbase.data(), hbase.size()))) ||
             hipMemset(d_serrs, 0, 2 * n_sym * 8) != hipSuccess || hipMemset(d_stot, 0, n_sym * 8) != hipSuccess)
             return fail(WOFDM_E_HIP, "upload failed");
     }
@@ -1683,6 +1715,10 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     wofdm_sparams spar{};
     spar.n_points = NP; spar.cells = cells; spar.pts = d_pts; spar.base = d_base; spar.sym_pow = d_spow; spar.sym_cnt = d_scnt;
     spar.sym_errs = d_serrs; spar.sym_tot = d_stot;
+    wofdm_dparams dpar{};
+    if (dop) {
+        dpar.knots = d_h; dpar.n_knots = dop->n_knots; dpar.knot_step = dop->knot_step;
+    }
     wofdm_rparams rp{};
     rp.S = S; rp.k = k; rp.B = B; rp.T = T; rp.NL = cfg->noise_before_truncate ? T + L - 1 : S * B;
     rp.delta = delta; rp.gam = gam; rp.kap = cfg->circ_shift; rp.n_ch = cfg->n_channels; rp.n_snr = cfg->n_snr;
@@ -1712,7 +1748,8 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
             pp.n_jobs = rp.n_jobs = (int32_t)std::min<uint64_t>(chunk, items - i0);
             pa.item0 = pp.item0;
             pa.n_jobs = pp.n_jobs;
-            e = sync ? ax->rx_profile_sync(&pp, &rp, &spar, nullptr)
+            e = dop ? ax->rx_profile_doppler(&pp, &rp, &spar, &dpar, nullptr)
+                : sync ? ax->rx_profile_sync(&pp, &rp, &spar, nullptr)
                      : (nb ? ax->rx_profile_aci(&pp, &pa, &rp, &apar, nullptr) : ax->rx_profile(&pp, &rp, nullptr));
         }
         if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
@@ -1730,10 +1767,12 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     for (size_t i = 0; i < 2 * n_out; ++i) errs[i] += herr[i];
     if (err_power)
         for (size_t i = 0; i < n_out; ++i) err_power[i] += hpow[i];
-    if (sync && sync->sym_errs)
-        for (size_t i = 0; i < 2 * n_sym; ++i) sync->sym_errs[i] += hserr[i];
-    if (sync && sync->sym_power)
-        for (size_t i = 0; i < n_sym; ++i) sync->sym_power[i] += hspow[i];
+    uint64_t *sym_errs = sync ? sync->sym_errs : (dop ? dop->sym_errs : nullptr);
+    double *sym_power = sync ? sync->sym_power : (dop ? dop->sym_power : nullptr);
+    if (sym_errs)
+        for (size_t i = 0; i < 2 * n_sym; ++i) sym_errs[i] += hserr[i];
+    if (sym_power)
+        for (size_t i = 0; i < n_sym; ++i) sym_power[i] += hspow[i];
     g_rxprof_ms = ms;
     return WOFDM_OK;
 }
@@ -1745,7 +1784,7 @@ extern "C" {
 int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                      const float *snr_db, const uint8_t *active, const float *tx_mask, uint64_t *errs, double *err_power)
 {
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -1753,7 +1792,7 @@ int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, co
                          const float *aci_h, int32_t aci_delay, float aci_level_db, uint64_t *errs, double *err_power)
 {
     const aci_args aci = {aci_active, aci_h, aci_delay, aci_level_db};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -1761,7 +1800,15 @@ int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, c
                           const wofdm_sync_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const sync_args sync = {n_points, points, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, nullptr, errs, err_power);
+}
+
+int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h_track,
+                             int32_t n_tracks, int32_t n_knots, int32_t knot_step, const float *snr_db, const uint8_t *active,
+                             const float *tx_mask, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
+{
+    const doppler_args dop = {h_track, n_tracks, n_knots, knot_step, sym_errs, sym_power};
+    return rx_profile_impl(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask, nullptr, nullptr, &dop, errs, err_power);
 }
 
 int wofdm_rx_profile_kernel_ms(float *ms)

@@ -1,10 +1,11 @@
 // wofdm_aux.hip -- the auxiliary kernels beside the frame kernel: closed-form ICI/ISI power (wofdm_interference,
 // wofdm_interference_masked) and Tx waveform + averaged periodogram (wofdm_tx_psd, wofdm_tx_psd_batch,
-// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile; beside an adjacent-band neighbour: wofdm_rx_profile_aci; under receiver timing and carrier offsets: wofdm_rx_profile_sync).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
+// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile; beside an adjacent-band neighbour: wofdm_rx_profile_aci; under receiver timing and carrier offsets: wofdm_rx_profile_sync; over channels that move within the frame: wofdm_rx_profile_doppler).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
 // on n_fft through the unit's table of launchers (wofdm_aux_fns).
 #include "wofdm_kernel.h"
 #include "wofdm_device.h"
 #include "philox.h"
+#include <type_traits>
 
 #if !defined(WOFDM_TU_N)
 #error "compile with -DWOFDM_TU_N=<64|128|256|512|1024>"
@@ -1045,6 +1046,8 @@ template <int N> struct rxp_geo {
     static constexpr int LDS_ACI = LDS + WAVES * 8 * XROW;            // the ACI arm: a second x row per wave (the neighbour's)
     static_assert(LDS <= 160 * 1024 && WAVES * 8 * N <= WAVES * 8 * (N + XROW) && (1 << LOG2) == N, "LDS");
     static_assert(LDS_ACI <= 160 * 1024, "LDS (ACI arm)");
+    static constexpr int LDS_DOP = LDS + 8 * WOFDM_DOPPLER_KNOTS * WOFDM_LT;   // the moving channel: a track's knots [64][21] float2
+    static_assert(LDS_DOP <= 160 * 1024 && LDS % 8 == 0, "LDS (moving channel)");
 };
 
 // the complex unit normal of sample a of (seed, cell, frame): philox.h, block a / 2, words 2 (a % 2) and 2 (a % 2) + 1
@@ -1546,6 +1549,269 @@ __global__ void __launch_bounds__(64) wofdm_rxprof_sync_reduce_kernel(const wofd
     tot[out] = acc;
 }
 
+// The knot interval of the on-air index a (wofdm_dparams): q = min(a / step, last), last = n_knots - 2, and the fraction
+// f = (a - q step) / step.  The quotient comes from the single-precision reciprocal rstep = 1 / step and two corrections, not
+// from a 32-bit division per sample: a < 2^22 is exact in single precision and the product carries under 3 2^-24 of a / step
+// < 2^22, so its integer part is off by one at most.  The knots cover the frame, so only a = (last + 1) step meets the
+// clamp, with f = 1.
+__device__ __forceinline__ void dop_interval(uint32_t a, uint32_t step, float rstep, uint32_t last, uint32_t &q, float &f)
+{
+    uint32_t qq = (uint32_t)((float)a * rstep);
+    int32_t r = (int32_t)(a - qq * step);
+    if (r < 0) {
+        --qq;
+        r += (int32_t)step;
+    }
+    if (r >= (int32_t)step) {
+        ++qq;
+        r -= (int32_t)step;
+    }
+    if (qq > last) {
+        r += (int32_t)((qq - last) * step);
+        qq = last;
+    }
+    q = qq;
+    f = (float)r * rstep;
+}
+
+// One tap of the 21-tap sum, cr += hv.x xv.x - hv.y xv.y and ci += hv.x xv.y + hv.y xv.x, in the operations the compiler forms
+// for these statements in wofdm_rxprof_kernel, where the taps are wave-uniform: the first product of each line fused onto the
+// rounded second, then the addition -- but in the copy of rxs() for the folded sample m0 + N (FOLD) the imaginary part has
+// the second product fused onto the rounded first (read in the generated assembly).  With the taps per lane the compiler
+// chooses yet other fusions from one inlined copy to the next, and a static track would miss the plain call's bits by an
+// ulp here and there; so the choice is written down.
+template <bool FOLD>
+__device__ __forceinline__ void dop_tap(const float2 hv, const float2 xv, float &cr, float &ci)
+{
+#pragma clang fp contract(off)
+    const float re = __builtin_fmaf(hv.x, xv.x, -(hv.y * xv.y));
+    const float im = FOLD ? __builtin_fmaf(hv.y, xv.x, hv.x * xv.y) : __builtin_fmaf(hv.x, xv.y, hv.y * xv.x);
+    cr = cr + re;
+    ci = ci + im;
+}
+
+// The receive profile over channels that move within the frame (wofdm_rx_profile_doppler): the item, the LDS image, the DFT,
+// the pilot step, the per-bin and per-symbol partials and their order are rxprof_sync_body's -- a body of its own again, so
+// that the three kernels above compile as they did --, with BOTH passes run once per track of dp (sp.n_points tracks; theta
+// and eps do not exist here): the workgroup stages the knots of (track, the item's channel) in LDS, [n_knots][WOFDM_LT]
+// float2 behind the waves' rows, and every sample of pass 1 and of pass 2's rxs() forms its 21 taps from the two knots
+// around its own on-air index, hv = K[q] + f (K[q + 1] - K[q]) -- the tap at the OUTPUT sample's time; with equal knots hv
+// is the knot, bit for bit, and every expression after it is the plain kernel's, so a static track gives its bits.  Ps is
+// measured per track on the track's conv; Pn does not depend on the channel and is measured with the first track.  Lanes
+// of a wave sit on neighbouring samples, so their knot reads are broadcasts but for the lanes astride a knot.
+// LDS: rxp_geo<N>::LDS_DOP.
+template <int N>
+__device__ __forceinline__ void rxprof_doppler_body(const wofdm_rparams &p, const wofdm_sparams &sp, const wofdm_dparams &dp)
+{
+    using RG = rxp_geo<N>;
+    constexpr int ROWLEN = N + RG::XROW;
+    constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float2 *tw = reinterpret_cast<float2 *>(smem);                    // e^{-2 pi i k / N}, k < N / 2
+    float2 *G = tw + N / 2;                                           // pilot equaliser X0 / Y0 of the track
+    float *wrx = reinterpret_cast<float *>(G + N);
+    float *red = wrx + N + 64;                                        // [2][W] power partials
+    float2 *rows = reinterpret_cast<float2 *>(red + 64);
+    float2 *kn = rows + (size_t)W * ROWLEN;                           // [n_knots][LT] knots of the track, the item's channel
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int S = p.S, B = p.B, T = p.T, NL = p.NL, delta = p.delta, NTR = sp.n_points, NK = dp.n_knots;
+    const uint32_t step = (uint32_t)dp.knot_step, last = (uint32_t)(NK - 2);
+    const float rstep = 1.0f / (float)step;
+    const uint32_t job = blockIdx.x;
+    const uint64_t item = p.item0 + job, cell64 = item / p.frames, frame = p.frame_offset + (item - cell64 * p.frames);
+    const uint32_t cell = (uint32_t)cell64, f_lo = (uint32_t)frame, f_hi = (uint32_t)(frame >> 32);
+    const int ch = (int)(cell % (uint32_t)p.n_ch), sn = (int)((cell / (uint32_t)p.n_ch) % (uint32_t)p.n_snr);
+    const int pair = (int)(cell / ((uint32_t)p.n_ch * (uint32_t)p.n_snr));
+    const float2 *__restrict__ x = p.x + (size_t)job * T;
+    const float2 *__restrict__ Xg = p.X + (size_t)job * S * N;
+    for (int i = tid; i < N / 2; i += NT) {
+        float sv, cv;
+        sincospif(-2.0f * (float)i / (float)N, &sv, &cv);
+        tw[i] = make_float2(cv, sv);
+    }
+    for (int i = tid; i < N + delta; i += NT) wrx[i] = p.wrx[(size_t)pair * (N + delta) + i];
+    float2 *buf = rows + (size_t)wv * ROWLEN;
+    float2 *xr = buf + N;
+    const int h2 = delta >> 1;
+#pragma unroll 1
+    for (int tk = 0; tk < NTR; ++tk) {
+        const float2 *__restrict__ knots = dp.knots + ((size_t)tk * p.n_ch + ch) * (size_t)NK * LT;
+        for (int i = tid; i < NK * LT; i += NT) kn[i] = knots[i];
+        __syncthreads();
+        // pass 1, once per track: the signal power over the NL samples of the track's conv; the noise power with the first
+        float ps = 0.f, pn = 0.f;
+        for (int q = tid; 2 * q < NL; q += NT) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int jj = 2 * q + e;
+                if (jj >= NL) break;
+                uint32_t kq;
+                float kf;
+                dop_interval((uint32_t)jj, step, rstep, last, kq, kf);
+                const float2 *k0 = kn + kq * LT;
+                float cr = 0.f, ci = 0.f;
+                for (int l = 0; l < LT; ++l) {
+                    const int t = jj - l;
+                    if (t < 0 || t >= T) continue;
+                    const float2 ka = k0[l], kb = k0[LT + l];
+                    const float2 xv = x[t], hv = make_float2(ka.x + kf * (kb.x - ka.x), ka.y + kf * (kb.y - ka.y));
+                    dop_tap<false>(hv, xv, cr, ci);
+                }
+                ps += cr * cr + ci * ci;
+                if (tk == 0) {
+                    const v2f nz = rxp_noise((uint32_t)q, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, e);
+                    pn += nz.x * nz.x + nz.y * nz.y;
+                }
+            }
+        }
+        ps = papr_wave_reduce<false>(ps);
+        if (lane == 0) red[wv] = ps;
+        if (tk == 0) {
+            pn = papr_wave_reduce<false>(pn);
+            if (lane == 0) red[W + wv] = pn;
+        }
+        __syncthreads();
+        float Ps = 0.f, Pn = 0.f;
+        for (int w = 0; w < W; ++w) {
+            Ps += red[w];
+            Pn += red[W + w];
+        }
+        const float g = sqrtf(Ps * p.nlin[sn] / Pn);
+        // pass 2 of the track
+        const size_t slot = (size_t)job * NTR + tk;
+        float pw[BINS];
+        uint32_t cnt[BINS];
+#pragma unroll
+        for (int j = 0; j < BINS; ++j) {
+            pw[j] = 0.f;
+            cnt[j] = 0u;
+        }
+        for (int s0 = 0; s0 < S; s0 += W) {
+            const int s = s0 + wv;
+            const bool live = s < S;                                  // (wave-uniform)
+            if (live) {
+                const int a0 = s * B + p.gam;                         // first sample under the Rx window
+                for (int i = lane; i < N + delta + LT - 1; i += 64) {
+                    const int t = a0 - (LT - 1) + i;
+                    xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
+                }
+                wave_sync();
+                // r[a] = conv[a] + g n[a] of the sample m under the window, a = a0 + m, with the taps at a
+                auto rxs = [&](int m, auto fold) {
+                    const uint32_t a = (uint32_t)(a0 + m);
+                    uint32_t kq;
+                    float kf;
+                    dop_interval(a, step, rstep, last, kq, kf);
+                    const float2 *k0 = kn + kq * LT;
+                    float cr = 0.f, ci = 0.f;
+#pragma unroll
+                    for (int l = 0; l < LT; ++l) {
+                        const float2 ka = k0[l], kb = k0[LT + l];
+                        const float2 xv = xr[m + (LT - 1) - l], hv = make_float2(ka.x + kf * (kb.x - ka.x), ka.y + kf * (kb.y - ka.y));
+                        dop_tap<decltype(fold)::value>(hv, xv, cr, ci);
+                    }
+                    const v2f nz = rxp_noise(a >> 1, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, (int)(a & 1u));
+                    return make_float2(cr + g * nz.x, ci + g * nz.y);
+                };
+#pragma unroll 1
+                for (int j = 0; j < BINS; ++j) {
+                    const int t = lane + 64 * j, m0 = (t + p.kap + h2) & (N - 1);
+                    float2 z = rxs(m0, std::false_type{});
+                    z.x *= wrx[m0];
+                    z.y *= wrx[m0];
+                    if (m0 < delta) {
+                        const float2 z2 = rxs(m0 + N, std::true_type{});
+                        z.x += wrx[m0 + N] * z2.x;
+                        z.y += wrx[m0 + N] * z2.y;
+                    }
+                    buf[__brev((uint32_t)t) >> (32 - LOG2)] = z;
+                }
+                wave_sync();
+                for (int len = 2, sh = LOG2 - 1; len <= N; len <<= 1, --sh) {
+                    const int half = len >> 1;
+                    for (int b = lane; b < N / 2; b += 64) {
+                        const int kk = b & (half - 1), i = ((b - kk) << 1) | kk;
+                        const float2 w = tw[kk << sh], a = buf[i], c = buf[i + half];
+                        const float tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
+                        buf[i] = make_float2(a.x + tr, a.y + ti);
+                        buf[i + half] = make_float2(a.x - tr, a.y - ti);
+                    }
+                    wave_sync();
+                }
+            }
+            if (s0 == 0) {
+                // pilot LS estimate of the track, from symbol 0 alone
+                if (wv == 0)
+                    for (int n = lane; n < N; n += 64) {
+                        const float2 y = buf[n], x0 = Xg[n];
+                        const float d = y.x * y.x + y.y * y.y;
+                        const bool on = p.amask == nullptr || p.amask[n] != 0;
+                        G[n] = on ? make_float2((x0.x * y.x + x0.y * y.y) / d, (x0.y * y.x - x0.x * y.y) / d) : make_float2(0.f, 0.f);
+                    }
+                __syncthreads();
+            }
+            if (live) {
+                float spw = 0.f;
+                uint32_t scn = 0u;
+                if (s >= 1) {
+#pragma unroll
+                    for (int j = 0; j < BINS; ++j) {
+                        const int n = lane + 64 * j;
+                        if (p.amask != nullptr && p.amask[n] == 0) continue;
+                        const float2 y = buf[n], gq = G[n], xs = Xg[(size_t)s * N + n];
+                        const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;
+                        const uint32_t d = rxp_slice(p.k, xs.x, xs.y) ^ rxp_slice(p.k, er, ei);
+                        const uint32_t c = (uint32_t)__popc(d) + (d != 0u ? 0x10000u : 0u);
+                        const float e2 = (er - xs.x) * (er - xs.x) + (ei - xs.y) * (ei - xs.y);
+                        cnt[j] += c;
+                        pw[j] += e2;
+                        scn += c;
+                        spw += e2;
+                    }
+                }
+                // the symbol's sums over the bins: at most N k < 2^16 bit errors and N symbol errors, so the halves do not meet
+                spw = papr_wave_reduce<false>(spw);
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) scn += (uint32_t)__shfl_xor((int)scn, o, 64);
+                if (lane == 0) {
+                    sp.sym_pow[slot * S + s] = spw;
+                    sp.sym_cnt[slot * S + s] = scn;
+                }
+            }
+            wave_sync();
+        }
+        // the waves' sums in wave order (their rows are free now): float [W][N], then uint32 [W][N]
+        __syncthreads();
+        float *redp = reinterpret_cast<float *>(rows);
+        uint32_t *redc = reinterpret_cast<uint32_t *>(redp + W * N);
+#pragma unroll
+        for (int j = 0; j < BINS; ++j) {
+            redp[wv * N + lane + 64 * j] = pw[j];
+            redc[wv * N + lane + 64 * j] = cnt[j];
+        }
+        __syncthreads();
+        for (int n = tid; n < N; n += NT) {
+            float t = 0.f;
+            uint32_t c = 0u;
+            for (int w = 0; w < W; ++w) {
+                t += redp[w * N + n];
+                c += redc[w * N + n];
+            }
+            p.part_pow[slot * N + n] = t;
+            p.part_cnt[slot * N + n] = c;
+        }
+        __syncthreads();                                              // the rows, G and the knots belong to the next track
+    }
+}
+
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_doppler_kernel(const wofdm_rparams p, const wofdm_sparams sp,
+                                                                                     const wofdm_dparams dp)
+{
+    rxprof_doppler_body<N>(p, sp, dp);
+}
+
 #if WOFDM_TU_N == 64
 // Philox known-answer kernel (wofdm_philox_kat): in one unit only
 __global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
@@ -1792,16 +2058,51 @@ hipError_t rx_profile_sync_launch(const wofdm_pparams *pp, const wofdm_rparams *
     return hipGetLastError();
 }
 
+// wofdm_rx_profile_doppler, one chunk: the Tx chain once, the receive kernel over the tracks, and rx_profile_sync's ordered sums
+// with the tracks as its points
+hipError_t rx_profile_doppler_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, const wofdm_sparams *spp,
+                                     const wofdm_dparams *dpp, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N;
+    const wofdm_rparams &r = *rp;
+    const wofdm_sparams &sp = *spp;
+    const wofdm_dparams &dp = *dpp;
+    if (r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
+        r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 || r.n_snr < 1)
+        return hipErrorInvalidValue;
+    if (sp.n_points < 1 || sp.n_points > WOFDM_DOPPLER_TRACKS || sp.sym_pow == nullptr || sp.sym_cnt == nullptr ||
+        sp.sym_errs == nullptr || sp.sym_tot == nullptr || r.S < 2 || r.S > 64 ||
+        (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames >= sp.cells)
+        return hipErrorInvalidValue;
+    // the knots fit the LDS image and cover every sample either pass takes a tap at; the indices stay exact in single precision
+    if (dp.knots == nullptr || dp.n_knots < 2 || dp.n_knots > WOFDM_DOPPLER_KNOTS || dp.knot_step < 1 || r.T + WOFDM_LT >= (1 << 22) ||
+        (int64_t)(dp.n_knots - 1) * dp.knot_step < (int64_t)(r.NL > r.T ? r.NL : r.T) - 1)
+        return hipErrorInvalidValue;
+    hipError_t e = tx_chain_launch(*pp, s);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_doppler_kernel<N>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, rxp_geo<N>::LDS_DOP);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_rxprof_doppler_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_DOP, s, r,
+                       sp, dp);
+    const uint64_t cell0 = r.item0 / r.frames, cell1 = (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames;
+    hipLaunchKernelGGL(wofdm_rxprof_sync_reduce_kernel<N>, dim3(N / 64 + 1, (unsigned)(cell1 - cell0 + 1), (unsigned)sp.n_points),
+                       dim3(64), 0, s, r, sp, cell0);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 const wofdm_aux_fns *WOFDM_CAT(wofdm_aux_n, WOFDM_TU_N)(void)
 {
 #if WOFDM_TU_N <= 256
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, psd_launch, psd_batch_launch, psd_batch_masked_launch,
-                                      papr_launch, rx_profile_launch, rx_profile_aci_launch, rx_profile_sync_launch};
+                                      papr_launch, rx_profile_launch, rx_profile_aci_launch, rx_profile_sync_launch,
+                                      rx_profile_doppler_launch};
 #else
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, nullptr, psd_batch_launch, psd_batch_masked_launch,
-                                      papr_launch, rx_profile_launch, rx_profile_aci_launch, rx_profile_sync_launch};
+                                      papr_launch, rx_profile_launch, rx_profile_aci_launch, rx_profile_sync_launch,
+                                      rx_profile_doppler_launch};
 #endif
     return &fns;
 }

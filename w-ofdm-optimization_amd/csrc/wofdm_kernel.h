@@ -547,6 +547,17 @@ struct wofdm_sparams {
     unsigned long long *sym_errs;     // [n_points][cells][S - 1][2], accumulated into
     double *sym_tot;                  // [n_points][cells][S - 1], accumulated into
 };
+// The moving channel of wofdm_rx_profile_doppler, a third argument of wofdm_rxprof_doppler_kernel: per track and channel the
+// tap vectors at the on-air indices 0, knot_step, 2 knot_step, ... (the knots); the tap l at on-air index a is
+// K[q][l] + f (K[q + 1][l] - K[q][l]), q = min(a / knot_step, n_knots - 2), f = (a - q knot_step) / knot_step, taken at the
+// OUTPUT sample of the convolution.  The tracks take the place of wofdm_sparams' points (n_points = n_tracks; pts and base
+// are not read): partials and totals carry a leading track axis, and wofdm_rxprof_sync_reduce_kernel adds them up.
+#define WOFDM_DOPPLER_TRACKS 16            // WOFDM_DOPPLER_MAX_TRACKS of include/wofdm.h
+#define WOFDM_DOPPLER_KNOTS 64             // WOFDM_DOPPLER_MAX_KNOTS of include/wofdm.h
+struct wofdm_dparams {
+    const float2 *knots;              // [n_tracks][n_ch][n_knots][WOFDM_LT], zero padded
+    int32_t n_knots, knot_step;       // (n_knots - 1) knot_step >= T + n_taps - 2: the knots cover the frame
+};
 
 // the launchers of one DFT length
 struct wofdm_aux_fns {
@@ -585,6 +596,10 @@ struct wofdm_aux_fns {
     // The same under receiver timing and carrier offsets (wofdm_rx_profile_sync): the Tx chain once, wofdm_rxprof_sync_kernel
     // (pass 1 once per item, pass 2 once per point of sp), and the ordered sums per point, per bin and per data symbol.
     hipError_t (*rx_profile_sync)(const wofdm_pparams *p, const wofdm_rparams *r, const wofdm_sparams *sp, hipStream_t s);
+    // The same over channels that move within the frame (wofdm_rx_profile_doppler): the Tx chain once,
+    // wofdm_rxprof_doppler_kernel (pass 1 and pass 2 once per track of dp, sp->n_points tracks), and rx_profile_sync's sums.
+    hipError_t (*rx_profile_doppler)(const wofdm_pparams *p, const wofdm_rparams *r, const wofdm_sparams *sp,
+                                     const wofdm_dparams *dp, hipStream_t s);
 };
 const wofdm_aux_fns *wofdm_aux_n64(void);
 const wofdm_aux_fns *wofdm_aux_n128(void);

@@ -16,6 +16,10 @@ air -- the interference the Rx window is there to reject; ``frame_profile_aci`` 
 ``rx_profile_sync_gpu`` (``wofdm_rx_profile_sync``) is the profile under receiver timing and carrier-frequency offset, a
 list of ``SyncPoint`` per call, per subcarrier and per data symbol; ``frame_profile_sync`` and ``rx_profile_sync_host``
 mirror it.
+
+``rx_profile_doppler_gpu`` (``wofdm_rx_profile_doppler``) is the profile over channels that move within the frame, a list of
+tracks (knots of the tap vector, linear in between) per call; ``tv_conv``, ``frame_profile_doppler`` and
+``rx_profile_doppler_host`` mirror it.
 """
 import collections
 
@@ -434,9 +438,10 @@ def rx_profile_kernel_ms():
 
 # ---- under receiver timing and carrier-frequency offset (wofdm_rx_profile_sync) ----
 
-def _sync_front(st, grids, noise_at, w_tx, h, snr_db, active, mask, noise_before_truncate):
+def _sync_front(st, grids, noise_at, w_tx, h, snr_db, active, mask, noise_before_truncate, channel=None):
     """What the points of a frame share: X [S, N], conv(h, x) [T + taps - 1], the noise gain g (``frame_profile``'s: the
-    offsets never touch it) and the loaded bins."""
+    offsets never touch it) and the loaded bins.  channel(x) -> what is received of the waveform x in conv(h, x)'s place (a
+    channel that moves within the frame: ``frame_profile_doppler``); h is not read then."""
     from . import timefreq as T
     X = np.asarray(grids, dtype=np.complex128)
     n = st.n_fft
@@ -445,7 +450,7 @@ def _sync_front(st, grids, noise_at, w_tx, h, snr_db, active, mask, noise_before
         raise ValueError("grids must be [S, %d] and the structure consistent" % n)
     on = np.ones(n, dtype=bool) if active is None else np.asarray(active).reshape(-1) != 0
     tx = T.tx_waveform(st, X.T, np.asarray(w_tx, np.float64), st.tail_tx, mask, guard_band=None)
-    conv = np.convolve(np.asarray(h, dtype=np.complex128).reshape(-1), tx)
+    conv = np.convolve(np.asarray(h, dtype=np.complex128).reshape(-1), tx) if channel is None else channel(tx)
     nl = conv.size if noise_before_truncate else S * B
     noise = np.asarray(noise_at(np.arange(nl, dtype=np.int64)), dtype=np.complex128)
     ps, pn = np.mean(np.abs(conv[:nl]) ** 2), np.mean(np.abs(noise) ** 2)
@@ -585,6 +590,147 @@ def rx_profile_sync_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db
     _lib.check(_lib.load().wofdm_rx_profile_sync(
         C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
         None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, len(pts), cpts, errs.ctypes.data,
+        pw.ctypes.data, serrs.ctypes.data, spw.ctypes.data))
+    prof = RxProfileSync(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
+                         np.ascontiguousarray(serrs[..., 0]), np.ascontiguousarray(serrs[..., 1]), spw,
+                         _decisions(st, syms, frames, act))
+    if out is not None:
+        if out.bit_err.shape != prof.bit_err.shape:
+            raise ValueError("out has another shape")
+        prof = RxProfileSync(*(a + b for a, b in zip(out, prof)))
+    return prof
+
+
+# ---- over a channel that moves within the frame (wofdm_rx_profile_doppler) ----
+
+def tv_conv(track, knot_step, x):
+    """The time-varying convolution of ``wofdm_rx_profile_doppler`` in double precision.  track [n_knots, taps]: knot q is the
+    tap vector at on-air index q * knot_step; for the output index a, 0 <= a < len(x) + taps - 1, with q = min(a // knot_step,
+    n_knots - 2) and f = (a - q * knot_step) / knot_step the taps are h_l[a] = K[q][l] + f (K[q+1][l] - K[q][l]) -- taken at the
+    OUTPUT sample's time -- and the result is sum_l h_l[a] x[a - l].  It is formed as c_q[a] + f (c_{q+1}[a] - c_q[a]) from the
+    knots' own convolutions c_q = np.convolve(K[q], x), the same sum by linearity: so a track of equal knots gives
+    np.convolve(K[0], x), exactly.  The knots must reach the last output: (n_knots - 1) knot_step >= len(x) + taps - 2."""
+    K = np.asarray(track, dtype=np.complex128)
+    x = np.asarray(x, dtype=np.complex128).reshape(-1)
+    ks = int(knot_step)
+    if K.ndim != 2 or K.shape[0] < 2 or ks < 1:
+        raise ValueError("track must be [n_knots >= 2, taps] and knot_step >= 1")
+    a = np.arange(x.size + K.shape[1] - 1, dtype=np.int64)
+    if (K.shape[0] - 1) * ks < a[-1]:
+        raise ValueError("the knots end at sample %d, the convolution at %d" % ((K.shape[0] - 1) * ks, a[-1]))
+    q = np.minimum(a // ks, K.shape[0] - 2)
+    f = (a - q * ks).astype(np.float64) / ks
+    c = np.zeros((K.shape[0], a.size), dtype=np.complex128)
+    for i in np.union1d(q, q + 1):
+        c[i] = np.convolve(K[i], x)
+    return c[q, a] + f * (c[q + 1, a] - c[q, a])
+
+
+def frame_profile_doppler(st, grids, unit_noise, w_tx, w_rx, track, knot_step, snr_db, bits_per_sc, active=None, mask=None,
+                          noise_before_truncate=1, with_y=False):
+    """fp64 host mirror of one frame and one track of ``wofdm_rx_profile_doppler``: ``frame_profile`` with ``tv_conv(track,
+    knot_step, x)`` in the place of conv(h, x) -- Ps, the noise gain and every received sample are those of the moving channel;
+    the receiver, its pilot estimate from symbol 0 included, is unchanged.  unit_noise [noise_len] as ``frame_profile``'s.
+    Returns what ``frame_profile_sync`` returns: (bit_err [N], sym_err [N], err_power [N], xhat [S-1, N], y0 [N], bit_err_sym
+    [S-1], sym_err_sym [S-1], err_power_sym [S-1]) -- the first five are ``frame_profile``'s, exactly, on a track whose knots
+    all equal h --; with_y=True: Y [S, N] as a ninth."""
+    noise = np.asarray(unit_noise, dtype=np.complex128).reshape(-1)
+    S, B = np.asarray(grids).shape[0], st.sym_len - st.tail_tx
+    nl = _noise_len(st, S, np.asarray(track).shape[-1], noise_before_truncate)
+    if noise.size < nl:
+        raise ValueError("unit_noise holds %d samples, %d needed" % (noise.size, nl))
+
+    def noise_at(idx):
+        return noise[np.asarray(idx, dtype=np.int64)]
+    front = _sync_front(st, grids, noise_at, w_tx, None, snr_db, active, mask, noise_before_truncate,
+                        channel=lambda x: tv_conv(track, knot_step, x))
+    out = _sync_point(st, front, noise_at, w_rx, SyncPoint(0, 0.0, 1), bits_per_sc)
+    return out if with_y else out[:8]
+
+
+def _prepare_tracks(tracks):
+    """[n_tracks, n_ch, n_knots, taps] complex64, as the GPU receives them"""
+    tr = np.ascontiguousarray(tracks, dtype=np.complex64)
+    if tr.ndim != 4 or tr.shape[0] < 1 or tr.shape[2] < 2:
+        raise ValueError("tracks must be [n_tracks >= 1, n_ch, n_knots >= 2, taps]")
+    return tr
+
+
+def rx_profile_doppler_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, tracks, knot_step, snr_db, seed, frame_offset,
+                            frames, active=None, mask=None, noise_before_truncate=1, with_near=False):
+    """The host route of ``rx_profile_doppler_gpu``: the frames of ``rx_profile_host`` from the same Philox streams, each
+    through ``frame_profile_doppler`` for every track of ``tracks`` [n_tracks, n_ch, n_knots, taps] (the cell's channel picks
+    the track's row); the labels, the Tx waveform and the noise of a frame are shared by its tracks.  Returns
+    ``RxProfileSync`` with a leading track axis; with_near=True: also the number of ``near_decisions`` per track and cell
+    [n_tracks, pairs, n_snr, n_ch]."""
+    from . import timefreq as T
+    tr = _prepare_tracks(tracks)
+    w_tx, w_rx, _, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, tr[0, :, 0], snr_db, active, mask)
+    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, tr.shape[1], st.n_fft
+    k, S = int(bits_per_sc), int(syms)
+    tab = T.qam_table(k)
+    nl = _noise_len(st, S, tr.shape[3], noise_before_truncate)
+    on = np.ones(n, dtype=bool) if act is None else act != 0
+    shape = (tr.shape[0], pairs, n_snr, n_ch)
+    bit = np.zeros(shape + (n,), dtype=np.uint64)
+    sym = np.zeros_like(bit)
+    pw = np.zeros(bit.shape, dtype=np.float64)
+    sbit = np.zeros(shape + (S - 1,), dtype=np.uint64)
+    ssym = np.zeros_like(sbit)
+    spw = np.zeros(sbit.shape, dtype=np.float64)
+    near = np.zeros(shape, dtype=np.int64)
+    for cell in range(pairs * n_snr * n_ch):
+        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
+        for f in range(int(frames)):
+            fr = int(frame_offset) + f
+            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
+            noise = gen_noise(nl, seed, cell, fr)
+            for i in range(tr.shape[0]):
+                b, se, e, xhat, y0, sb, ss, sp = frame_profile_doppler(st, grid, noise, w_tx[p], w_rx[p], tr[i, c], knot_step,
+                                                                       snr[s], k, act, m, noise_before_truncate)
+                bit[i, p, s, c] += b
+                sym[i, p, s, c] += se
+                pw[i, p, s, c] += e
+                sbit[i, p, s, c] += sb
+                ssym[i, p, s, c] += ss
+                spw[i, p, s, c] += sp
+                if with_near:
+                    near[i, p, s, c] += int(near_decisions(k, xhat, y0).sum())
+    prof = RxProfileSync(bit, sym, pw, sbit, ssym, spw, _decisions(st, S, frames, act))
+    return (prof, near) if with_near else prof
+
+
+def rx_profile_doppler_chunk_frames(st, syms, masked, n_tracks):
+    """Frames one chunk of ``wofdm_rx_profile_doppler`` holds (include/wofdm.h): ``rx_profile_sync_chunk_frames`` with the
+    tracks for its points."""
+    return rx_profile_sync_chunk_frames(st, syms, masked, n_tracks)
+
+
+def rx_profile_doppler_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, tracks, knot_step, snr_db, seed, frame_offset,
+                           frames, active=None, mask=None, noise_before_truncate=1, device=0, out=None):
+    """``wofdm_rx_profile_doppler``: ``rx_profile_gpu`` of the same arguments over channels that move within the frame, for
+    every track of ``tracks`` [n_tracks, n_ch, n_knots, taps] (at most ``_lib.DOPPLER_MAX_TRACKS`` tracks of
+    ``_lib.DOPPLER_MAX_KNOTS`` knots, knot q the taps at on-air index q * knot_step, linear in between: ``tv_conv``) in ONE
+    call -- the Tx chain runs once per frame, every track sees the same labels and noise --, per subcarrier and per data
+    symbol.  Returns the ``RxProfileSync`` tuple with a leading track axis; ``out`` (an earlier result of the same shape) is
+    accumulated into.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    from .simulation import make_cfg
+    tr = _prepare_tracks(tracks)
+    w_tx, w_rx, _, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, tr[0, :, 0], snr_db, active, mask)
+    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, tr.shape[1]
+    cfg = make_cfg(st, int(bits_per_sc), int(syms), tr.shape[3], n_ch, n_snr, pairs, bool(noise_before_truncate),
+                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
+    shape = (tr.shape[0], pairs, n_snr, n_ch)
+    errs = np.zeros(shape + (st.n_fft, 2), dtype=np.uint64)
+    pw = np.zeros(shape + (st.n_fft,), dtype=np.float64)
+    serrs = np.zeros(shape + (int(syms) - 1, 2), dtype=np.uint64)
+    spw = np.zeros(shape + (int(syms) - 1,), dtype=np.float64)
+    hf = _lib.c64_as_f32(tr)
+    _lib.check(_lib.load().wofdm_rx_profile_doppler(
+        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, tr.shape[0], tr.shape[2], int(knot_step),
+        snr.ctypes.data, None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, errs.ctypes.data,
         pw.ctypes.data, serrs.ctypes.data, spw.ctypes.data))
     prof = RxProfileSync(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
                          np.ascontiguousarray(serrs[..., 0]), np.ascontiguousarray(serrs[..., 1]), spw,
