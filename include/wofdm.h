@@ -305,6 +305,50 @@ int wofdm_tx_psd_batch_masked(int32_t n_fft, int device, int32_t n_jobs, const w
                               const float *mask_gain, const int32_t *job_mask,
                               int32_t n_blocks, int32_t no_symbols, const float *X, float *psd);
 
+/* The transmitter's last stage, a memoryless power amplifier (wofdm_rx_profile_pa, wofdm_tx_psd_batch_pa).  It compresses the
+ * peaks wofdm_tx_papr counts: that raises the error vector on every loaded bin and puts back, as spectral regrowth, the
+ * out-of-band radiation the Tx window and the mask removed.  With r = |x| and rho = r / a_sat the output is y = g x; the phase
+ * is untouched (AM/AM only, no AM/PM).
+ *   WOFDM_PA_LINEAR  y = x, no arithmetic at all
+ *   WOFDM_PA_RAPP    AM/AM of a solid-state amplifier, smoothness p = smooth: g = (1 + rho^(2p))^(-1/(2p)), evaluated above rho =
+ *                    1 as (1 / rho) (1 + rho^(-2p))^(-1/(2p)), so that no finite input overflows; g = 1 at r = 0
+ *   WOFDM_PA_CLIP    the soft limiter, the p -> infinity limit: g = 1 for rho <= 1, else 1 / rho
+ * a_sat^2 = ref_power 10^(ibo_db / 10): the input back-off counts from a reference power, which the two routes take a little
+ * differently -- wofdm_rx_profile_pa gets it from the caller per window pair (rx_profile.pa_ref_power: the mean over the symbol
+ * periods, the mean the PAPR histogram's axis counts from), wofdm_tx_psd_batch_pa measures it on the device over a job's whole
+ * waveform, the last ramp-down included.  The kernels evaluate g in single precision (hardware log2 / exp2), one device
+ * function for both routes; rx_profile.pa_gain is the double-precision mirror.
+ *   Limits, both routes.  WOFDM_E_UNSUPPORTED: smooth outside [0.5, 16] for the Rapp model (the other two ignore it), ibo_db
+ * outside [-40, 60], a model other than the three, more than WOFDM_PA_MAX_POINTS points; WOFDM_E_INVALID: a non-finite
+ * ibo_db or smooth, reserved != 0. */
+#define WOFDM_PA_LINEAR 0
+#define WOFDM_PA_RAPP   1
+#define WOFDM_PA_CLIP   2
+#define WOFDM_PA_MAX_POINTS 16
+typedef struct wofdm_pa_point {
+    int32_t model;
+    float   ibo_db;    /* input back-off: a_sat^2 = ref_power 10^(ibo_db / 10) */
+    float   smooth;    /* p of the Rapp model; ignored by the other two */
+    int32_t reserved;  /* 0 */
+} wofdm_pa_point;
+
+/* wofdm_tx_psd_batch_masked behind the amplifier: spectral regrowth.  pa[n_pa] is a table of amplifiers, job_pa[n_jobs] the
+ * index of a job's, or -1 = none (NULL = none anywhere).  A job's reference power is the mean of |x|^2 over all len = overlap +
+ * no_symbols (P - overlap) samples of its own finished waveform -- window, mask and overlap-add done, the last ramp-down
+ * included --, summed on the device in a fixed order; a_sat is formed from it in double precision and stored in single.  One
+ * elementwise kernel, and the reduction in front of it, run between the waveform kernels and the periodogram.  job_power
+ * [n_jobs][2] (or NULL): the mean power of a job's waveform before and behind its amplifier (equal without one).  A job
+ * without power passes through unchanged.  A job with job_pa = -1, or with a WOFDM_PA_LINEAR point, gives the bits
+ * wofdm_tx_psd_batch_masked gives for it; repeated calls give identical bits.  Every check of wofdm_tx_psd_batch_masked
+ * applies, and the amplifier's limits above; WOFDM_E_INVALID: n_pa < 0, NULL pa with n_pa > 0, a job_pa entry outside
+ * [-1, n_pa).  Every argument is checked before the device is touched. */
+int wofdm_tx_psd_batch_pa(int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs,
+                          const float *w_tx, int32_t n_masks, const int32_t *mask_len,
+                          const float *mask_gain, const int32_t *job_mask,
+                          int32_t n_pa, const wofdm_pa_point *pa, const int32_t *job_pa,
+                          int32_t n_blocks, int32_t no_symbols, const float *X, float *psd,
+                          float *job_power);                 /* [n_jobs][2] = {mean |x|^2, mean |y|^2}, or NULL */
+
 /* Peak-to-average power ratio (PAPR) of the on-air frames, per symbol period, as a histogram -- for exactly the frames the
  * BER loop transmits.  The reference has no PAPR figure: this entry point replaces no line of it; it completes the
  * window / Tx-mask study beside the BER, interference and spectrum entry points above.
@@ -434,7 +478,8 @@ int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device,
  * wofdm_rx_profile_aci call took (whichever came last), first chunk to last; 0 before any.  Measurement aid
  * (tools/bench_rx_profile.py, tools/bench_rx_profile_aci.py).  A successful wofdm_rx_profile_sync call (below) counts as
  * such a call too: the figure is then that of its whole sweep (tools/bench_rx_profile_sync.py); so does a successful
- * wofdm_rx_profile_doppler call, with all its tracks (tools/bench_rx_profile_doppler.py). */
+ * wofdm_rx_profile_doppler call, with all its tracks (tools/bench_rx_profile_doppler.py), and a successful
+ * wofdm_rx_profile_pa call, with all its points (tools/bench_rx_profile_pa.py). */
 int wofdm_rx_profile_kernel_ms(float *ms);
 
 /* wofdm_rx_profile under receiver timing and carrier-frequency offset: what the victim of wofdm_rx_profile loses, bin by bin
@@ -536,6 +581,53 @@ int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device,
                              double *err_power,             /* [n_tracks][cells][n_fft], or NULL */
                              uint64_t *sym_errs,            /* [n_tracks][cells][S-1][2], or NULL */
                              double *sym_power);            /* [n_tracks][cells][S-1], or NULL */
+
+/* wofdm_rx_profile behind the power amplifier (wofdm_pa_point above): what the victim of wofdm_rx_profile loses, bin by bin and
+ * symbol by symbol, when the transmitter's last stage compresses the peaks of the waveform -- "which window pair is best at 3 dB
+ * back-off".  A call takes a LIST of points (model, back-off, smoothness) and runs the Tx chain once per frame, whatever
+ * n_points is; every point sees the same labels and the same noise, so back-offs compare pairwise.
+ *   Victim: exactly wofdm_rx_profile -- frames, cells, streams 0 and 1, allocation, mask, both noise_before_truncate orders, the
+ * gate; the noise of on-air sample a is the unit normal the plain kernel uses for it.
+ *   Amplifier: it acts on the finished on-air waveform x[tail_tx + S B] -- after the window, the mask and the overlap-add, the
+ * last ramp-down included, before the channel.  Point i of a cell uses a_sat^2 = ref_power[pair of the cell] 10^(ibo_db_i / 10),
+ * formed on the host in double precision and stored in single.  The amplified waveforms are materialised per point by a small
+ * kernel, which also forms the two power sums of pa_power; a WOFDM_PA_LINEAR point reads the unamplified waveform itself.
+ *   Powers: Ps is measured per point on conv(h, y), as wofdm_rx_profile_doppler measures it per track -- snr_db stays the SNR
+ * at the receiver, the power the back-off gives away is not charged to the link --, Pn with the first point.  Rx window, fold,
+ * shift, DFT, the pilot LS estimate from symbol 0 (the pilot went through the amplifier too), equaliser, slicer and counters
+ * are unchanged.
+ *   Outputs (host), ACCUMULATED into, with the shapes and the ordered sums of wofdm_rx_profile_sync, "point" on the leading
+ * axis: errs[n_points][cells][n_fft][2], err_power[n_points][cells][n_fft] (or NULL), sym_errs[n_points][cells][S-1][2] and
+ * sym_power[n_points][cells][S-1] (either may be NULL), and pa_power[n_points][cells][2] = {sum |x|^2, sum |y|^2} over the T =
+ * tail_tx + S B samples of the cell's frames (or NULL): per frame in fp32 in a fixed order, over the frames in fp64 in frame
+ * order.  Integer counters are exact; float sums per frame in fp32 in the sync kernel's order, over the frames of a cell in
+ * fp64, one addition per frame --, so repeated calls give identical bits, a split frame range gives the integer counters of one
+ * call, and a point's results do not depend on which other points share its call.  A WOFDM_PA_LINEAR point gives the bits of
+ * wofdm_rx_profile, err_power bytes included (as long as no cell's frames are split over two chunks of that call).
+ *   Every limit and check of wofdm_rx_profile applies, and the amplifier's limits above.  WOFDM_E_INVALID: NULL points, errs or
+ * ref_power, n_points < 1, a ref_power that is not finite and positive.  Every
+ * argument is checked before the device is touched; a failed call leaves all five outputs as they were.
+ *   Chunks: min(65535, WOFDM_RX_PROFILE_CHUNK_BYTES / (8 (S n_fft + T + [mask] S (2P-1)) + 8 n_points (n_fft + S + T)))  frames --
+ * wofdm_rx_profile_sync's formula plus one waveform per point.
+ *   A successful call counts for wofdm_rx_profile_kernel_ms.
+ *   Measured on an MI355X (tools/bench_rx_profile_pa.py, profiles/rx_profile_pa.txt): on 64 cells x 2000 frames x 16 symbols at
+ * n_fft = 256 one point takes 56.5 ms of kernels (88.8 ms masked), 1.44 (1.25) times one wofdm_rx_profile call on the same cells
+ * and frames in the same run; four points take 133.6 (152.8) ms, 3.41 (2.15) times -- 0.66 (0.30) of a plain call per
+ * additional point. */
+int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device,
+                        const float *w_tx,                  /* [pairs][P] */
+                        const float *w_rx,                  /* [pairs][N+tail_rx] */
+                        const float *h,                     /* [n_channels][n_taps][2] */
+                        const float *snr_db,                /* [n_snr] */
+                        const uint8_t *active,              /* [n_fft] or NULL */
+                        const float *tx_mask,               /* [2P-1] or NULL */
+                        int32_t n_points, const wofdm_pa_point *points,
+                        const float *ref_power,             /* [pairs]: mean on-air power the back-off counts from */
+                        uint64_t *errs,                     /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                        double *err_power,                  /* [n_points][cells][n_fft], or NULL */
+                        uint64_t *sym_errs,                 /* [n_points][cells][S-1][2], or NULL */
+                        double *sym_power,                  /* [n_points][cells][S-1], or NULL */
+                        double *pa_power);                  /* [n_points][cells][2], or NULL */
 
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

@@ -15,7 +15,8 @@ as ``wofdm_amd`` through the shim module at the repository root.
   rx_profile   per-subcarrier BER / EVM of the frames the BER loop runs (GPU: wofdm_rx_profile; fp64 host mirror), alone or
                beside an asynchronous adjacent-band neighbour (GPU: wofdm_rx_profile_aci), or under receiver timing and
                carrier-frequency offset (GPU: wofdm_rx_profile_sync), or over channels that move within the frame
-               (GPU: wofdm_rx_profile_doppler)
+               (GPU: wofdm_rx_profile_doppler), or behind a nonlinear power amplifier (GPU: wofdm_rx_profile_pa; the
+               spectral regrowth: timefreq / wofdm_tx_psd_batch_pa)
   _lib         ctypes binding of libwofdm_hip.so (include/wofdm.h)
 """
 from . import variants  # noqa: F401
@@ -32,15 +33,17 @@ from .simulation import (Plan, ber_for_window_file, error_rates, make_cfg,  # no
                          results_from_counts, run_counts, run_counts_injected, run_simulation,
                          save_ber_results, simulation_fun, wOFDMSystem)
 from ._lib import kernel_source_hash  # noqa: F401
-from .timefreq import (frame_papr, papr_ccdf, papr_hist, run_timefreq, tx_papr_gpu,  # noqa: F401
+from .timefreq import (estimate_obr, frame_papr, papr_ccdf, papr_hist, run_timefreq, tx_papr_gpu,  # noqa: F401
                        tx_psd_batch_gpu, tx_waveform)
 from .channel_mask import (aci_for_window_file, doppler_for_window_file, interference_for_window_file,  # noqa: F401
-                           papr_for_window_file, profile_for_window_file, spectrum_for_window_file, sync_for_window_file)
+                           pa_for_window_file, papr_for_window_file, profile_for_window_file, spectrum_for_window_file, sync_for_window_file)
 from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_db, frame_profile,  # noqa: F401
                          frame_profile_aci, frame_profile_sync, gen_noise_at, rx_profile_aci_gpu, rx_profile_aci_host,
                          rx_profile_gpu, rx_profile_host, rx_profile_sync_chunk_frames, rx_profile_sync_gpu,
                          rx_profile_sync_host, frame_profile_doppler, rx_profile_doppler_chunk_frames,
-                         rx_profile_doppler_gpu, rx_profile_doppler_host, tv_conv)
+                         rx_profile_doppler_gpu, rx_profile_doppler_host, tv_conv,
+                         PA_CLIP, PA_LINEAR, PA_RAPP, PaPoint, RxProfilePa, frame_profile_pa, pa_apply, pa_gain, pa_ref_power,
+                         rx_profile_pa_chunk_frames, rx_profile_pa_gpu, rx_profile_pa_host)
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

@@ -31,6 +31,9 @@ SYNC_MAX_POINTS = 64
 #: wofdm_rx_profile_doppler (include/wofdm.h): most tracks one call takes, most knots a track has
 DOPPLER_MAX_TRACKS = 16
 DOPPLER_MAX_KNOTS = 64
+#: wofdm_rx_profile_pa, wofdm_tx_psd_batch_pa (include/wofdm.h): the amplifier models, most points one call takes
+PA_LINEAR, PA_RAPP, PA_CLIP = 0, 1, 2
+PA_MAX_POINTS = 16
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -43,6 +46,7 @@ EXPORTS = (
     "wofdm_interference_masked", "wofdm_tx_papr", "wofdm_tx_papr_kernel_ms",
     "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms", "wofdm_plan_kernel_geo", "wofdm_cfg_geo_id",
     "wofdm_rx_profile_aci", "wofdm_rx_profile_sync", "wofdm_rx_profile_doppler",
+    "wofdm_rx_profile_pa", "wofdm_tx_psd_batch_pa",
 )
 
 
@@ -85,6 +89,11 @@ class PsdJob(C.Structure):
 class SyncPoint(C.Structure):
     """Mirror of ``wofdm_sync_point`` (16 bytes)."""
     _fields_ = [("timing", C.c_int32), ("cfo", C.c_float), ("cfo_tracked", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PaPoint(C.Structure):
+    """Mirror of ``wofdm_pa_point`` (16 bytes)."""
+    _fields_ = [("model", C.c_int32), ("ibo_db", C.c_float), ("smooth", C.c_float), ("reserved", C.c_int32)]
 
 
 class Dump(C.Structure):
@@ -163,6 +172,8 @@ def load():
     L.wofdm_rx_profile_kernel_ms.argtypes = [C.POINTER(C.c_float)]
     L.wofdm_rx_profile_sync.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, i32, C.POINTER(SyncPoint), vp, vp, vp, vp]
     L.wofdm_rx_profile_doppler.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.wofdm_rx_profile_pa.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, i32, C.POINTER(PaPoint), vp, vp, vp, vp, vp, vp]
+    L.wofdm_tx_psd_batch_pa.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, C.POINTER(PaPoint), vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L
 

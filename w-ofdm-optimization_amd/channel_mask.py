@@ -10,7 +10,9 @@ experiment: the periodogram and out-of-band radiation of the plain and of the ma
 ISI power of the same two systems (``wofdm_interference_masked``): what the mask costs next to what it buys.
 ``papr_for_window_file`` is the envelope side: the PAPR histogram and CCDF of the plain and of the masked frames
 (``wofdm_tx_papr``).  ``profile_for_window_file`` shows where in the band the errors of the two systems sit: bit errors,
-symbol errors and error-vector power per subcarrier (``wofdm_rx_profile``).
+symbol errors and error-vector power per subcarrier (``wofdm_rx_profile``).  ``pa_for_window_file`` puts both systems behind
+a nonlinear power amplifier: the profile and the spectral regrowth per back-off (``wofdm_rx_profile_pa``,
+``wofdm_tx_psd_batch_pa``).
 
 BER is accumulated over the whole ensemble here as there (lines 341-359).  The reference sends
 the same data bits through both runs with independent noise (two ``add_wgn`` calls); here the
@@ -405,6 +407,74 @@ def doppler_for_window_file(type_ofdm, cp, windows, tracks, knot_step, snr_db, n
     def of_pair(prof, i):
         return R.RxProfileSync(*(a[:, i] for a in prof[:6]), prof.decisions)
     return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
+
+
+def pa_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_subcar=256, bits_per_subcar=4, symbols_per_tx=16,
+                       ensemble=100, roll_off=ROLL_OFF, seed=0, frame_range=None, symbols=None, rng=None, gpu=True, device=0,
+                       tail_tx=8, tail_rx=10):
+    """The amplifier's side of the mask experiment: what the PAPR of ``papr_for_window_file`` costs behind the transmitter's
+    last stage -- "which window pair is best at 3 dB back-off".  Every window pair of the file + the RC pair under half-band
+    loading, plain and masked (``tx_mask(P)``), for every point of ``points`` (``rx_profile.PaPoint`` or (model, ibo_db, smooth)
+    tuples: linear, Rapp, soft limiter): the receive profile of ``profile_for_window_file`` behind the amplifier, per SNR point
+    and channel, and the periodogram and out-of-band radiation of ``spectrum_for_window_file`` behind it (``symbols`` / ``rng``
+    as there) -- compression raises the error vector on the loaded bins and puts back, as regrowth, the radiation window and
+    mask removed.  On the GPU two ``wofdm_rx_profile_pa`` calls and one ``wofdm_tx_psd_batch_pa`` call whatever len(points) is
+    (and the two ``wofdm_tx_papr`` runs of ``rx_profile.pa_ref_power``, which measure the mean power per pair the receive
+    route's back-off counts from; the spectrum route measures each waveform's own); gpu=False: the fp64 host routes
+    ``rx_profile.rx_profile_pa_host`` and ``timefreq.tx_waveform(..., pa=)``, for small ensembles.  The frames are those of
+    ``profile_for_window_file`` with the same arguments, so a ``PA_LINEAR`` point is its result.
+    Returns {name: {"profile", "profile_masked", "psd", "psd_masked", "obr", "obr_masked", "ref_power", "ref_power_masked",
+    "f_axis"}} with the names of ``V.matlab_pair_plan``: the profiles ``rx_profile.RxProfilePa`` of that pair, arrays [points,
+    n_snr, n_channels, ...]; psd [points, 8 N], obr [points]."""
+    from . import rx_profile as R
+    from . import timefreq as T
+    n = num_subcar
+    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
+                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
+    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
+    plan = V.matlab_pair_plan(type_ofdm)
+
+    def pick(key, side):
+        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
+
+    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
+    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
+    h = np.atleast_2d(np.asarray(channels))
+    pts = [R._pa_point(q) for q in points]
+    alloc = half_band_allocation(n)
+    mask = tx_mask(st.sym_len, roll_off)
+    first, count = (0, ensemble) if frame_range is None else frame_range
+    # the receive route: the mean power per pair, then one call per system
+    ref = [R.pa_ref_power(st, bits_per_subcar, symbols_per_tx, w_tx, seed, first, count, active=alloc, mask=m, gpu=gpu,
+                          **(dict(device=device) if gpu else {})) for m in (None, mask)]
+    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, h, snr_db, seed, first, count, pts)
+    run = R.rx_profile_pa_gpu if gpu else R.rx_profile_pa_host
+    kw = dict(active=alloc, device=device) if gpu else dict(active=alloc)
+    plain = run(*args, ref[0], **kw)
+    masked = run(*args, ref[1], mask=mask, **kw)
+    # the spectrum route: every (pair, system, point) as one job
+    if symbols is None:
+        rng = np.random.RandomState() if rng is None else rng
+        symbols = rng.choice(T.SYMBOLS_16QAM, size=(int(alloc.sum()), T.NO_SYMBOLS), replace=True)
+    grid = np.zeros((n, np.asarray(symbols).shape[1]), dtype=np.complex128)
+    grid[alloc] = np.asarray(symbols)
+    fft_len = 8 * n
+    combos = [(w, m, q) for w in w_tx for m in (None, mask) for q in pts]
+    if gpu:
+        ests = T.tx_psd_batch_gpu(n, grid.T.astype(np.complex64)[None], [(0, st.cp, st.cs, st.tail_tx, w, m, q) for w, m, q in combos],
+                                  device)
+    else:
+        ests = [T.psd_estimate(T.tx_waveform(st, grid, w, st.tail_tx, m, guard_band=None, pa=q), fft_len) for w, m, q in combos]
+    ests = np.asarray(ests).reshape(len(plan), 2, len(pts), fft_len)
+    unloaded = np.fft.fftshift(np.repeat(~alloc, fft_len // n))
+    f_axis = np.linspace(-.5, .5 - 1 / fft_len, fft_len) / 200e-9
+
+    def of_pair(prof, i):
+        return R.RxProfilePa(*(a[:, i] for a in prof[:7]), prof.decisions)
+    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i), "psd": ests[i, 0], "psd_masked": ests[i, 1],
+                   "obr": ests[i, 0][:, unloaded].mean(axis=1), "obr_masked": ests[i, 1][:, unloaded].mean(axis=1),
+                   "ref_power": ref[0][i], "ref_power_masked": ref[1][i], "f_axis": f_axis}
+            for i, (name, _) in enumerate(plan)}
 
 
 def results_from_counts(names, masked, plain):

@@ -2,6 +2,7 @@
 // Plans own the constants in HBM; launches are asynchronous on the caller's stream.
 #include "../../include/wofdm.h"
 #include "wofdm_kernel.h"
+#include "wofdm_pa.h"
 #include "philox.h"
 
 #include <algorithm>
@@ -411,6 +412,28 @@ int use_device(int device)
 }
 
 // the channels' taps as the kernels read them: [n_channels][WOFDM_LT] float2, zero padded
+// The checks of a table of amplifier points (include/wofdm.h, both routes), and the points as the kernels read them
+int check_pa_points(int32_t n, const wofdm_pa_point *pts, std::vector<wofdm_papoint> *out)
+{
+    if (n > WOFDM_PA_MAX_POINTS) return fail(WOFDM_E_UNSUPPORTED, "%d amplifier points exceed %d", n, WOFDM_PA_MAX_POINTS);
+    out->resize((size_t)(n > 0 ? n : 0));
+    for (int i = 0; i < n; ++i) {
+        const wofdm_pa_point &q = pts[i];
+        if (!std::isfinite(q.ibo_db) || !std::isfinite(q.smooth))
+            return fail(WOFDM_E_INVALID, "amplifier point %d: ibo_db and smooth must be finite", i);
+        if (q.reserved != 0) return fail(WOFDM_E_INVALID, "amplifier point %d: reserved=%d must be 0", i, q.reserved);
+        if (q.model != WOFDM_PA_LINEAR && q.model != WOFDM_PA_RAPP && q.model != WOFDM_PA_CLIP)
+            return fail(WOFDM_E_UNSUPPORTED, "amplifier point %d: model %d is not known", i, q.model);
+        if (q.ibo_db < -40.f || q.ibo_db > 60.f)
+            return fail(WOFDM_E_UNSUPPORTED, "amplifier point %d: ibo_db=%g outside [-40, 60]", i, (double)q.ibo_db);
+        if (q.model == WOFDM_PA_RAPP && (q.smooth < 0.5f || q.smooth > 16.f))
+            return fail(WOFDM_E_UNSUPPORTED, "amplifier point %d: smooth=%g outside [0.5, 16]", i, (double)q.smooth);
+        const double p2 = q.model == WOFDM_PA_RAPP ? 2.0 * (double)q.smooth : 2.0;
+        (*out)[(size_t)i] = {q.model, (float)p2, (float)(1.0 / p2), 0};
+    }
+    return WOFDM_OK;
+}
+
 std::vector<float2> pack_taps(const wofdm_cfg *cfg, const geom &g, const float *h)
 {
     std::vector<float2> hp((size_t)cfg->n_channels * WOFDM_LT, make_float2(0.f, 0.f));
@@ -1226,14 +1249,24 @@ int wofdm_tx_psd(const wofdm_cfg *cfg, int device, const float *w_tx, const floa
     return WOFDM_OK;
 }
 
-// wofdm_tx_psd_batch (n_masks = 0, job_mask = NULL) and wofdm_tx_psd_batch_masked.  Every argument is checked before
-// the first HIP call.
+// the amplifier table of wofdm_tx_psd_batch_pa and its output; a null pointer to it is wofdm_tx_psd_batch(_masked)
+struct psd_pa_args {
+    int32_t n_pa;
+    const wofdm_pa_point *pa;
+    const int32_t *job_pa;
+    float *job_power;
+};
+
+// wofdm_tx_psd_batch (n_masks = 0, job_mask = NULL), wofdm_tx_psd_batch_masked and wofdm_tx_psd_batch_pa.  Every argument is
+// checked before the first HIP call.
 static int psd_batch(const char *who, int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs, const float *w_tx,
                      int32_t n_masks, const int32_t *mask_len, const float *mask_gain, const int32_t *job_mask,
-                     int32_t n_blocks, int32_t no_symbols, const float *X, float *psd)
+                     int32_t n_blocks, int32_t no_symbols, const float *X, float *psd, const psd_pa_args *amp = nullptr)
 {
     if (!jobs || !w_tx || !X || !psd || (n_masks > 0 && (!mask_len || !mask_gain)))
         return fail(WOFDM_E_INVALID, "NULL argument");
+    if (amp && amp->n_pa < 0) return fail(WOFDM_E_INVALID, "bad n_pa");
+    if (amp && amp->n_pa > 0 && !amp->pa) return fail(WOFDM_E_INVALID, "NULL argument (pa)");
     const int N = n_fft;
     if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
         return fail(WOFDM_E_UNSUPPORTED, "%s is built for n_fft in {64,128,256,512,1024}", who);
@@ -1292,6 +1325,22 @@ static int psd_batch(const char *who, int32_t n_fft, int device, int32_t n_jobs,
     }
     for (int j = 0; j < n_jobs; ++j)
         if (!(job_mask && job_mask[j] >= 0)) hplain.push_back(hj[(size_t)j]);
+    // the amplifier of every job: the table's checks, then model, 2 p, 1 / (2 p) and 10^(ibo / 10) per job (model -1: none)
+    std::vector<wofdm_pajob> hpa;
+    if (amp) {
+        std::vector<wofdm_papoint> pts;
+        const int prc = check_pa_points(amp->n_pa, amp->pa, &pts);
+        if (prc != WOFDM_OK) return prc;
+        hpa.assign((size_t)n_jobs, wofdm_pajob{-1, 2.f, 0.5f, 0, 1.0});
+        for (int j = 0; j < n_jobs; ++j) {
+            const int a = amp->job_pa ? amp->job_pa[j] : -1;
+            if (a < -1 || a >= amp->n_pa)
+                return fail(WOFDM_E_INVALID, "job %d: amplifier index %d outside [-1, %d)", j, a, amp->n_pa);
+            if (a >= 0)
+                hpa[(size_t)j] = {pts[(size_t)a].model, pts[(size_t)a].two_p, pts[(size_t)a].inv_two_p, 0,
+                                  std::pow(10.0, 0.1 * (double)amp->pa[a].ibo_db)};
+        }
+    }
     const int rc = use_device(device);
     if (rc != WOFDM_OK) return rc;
     // one fast-convolution spectrum per mask in use (host, fp64, O(M log M)), whatever the number of jobs that share it
@@ -1319,19 +1368,39 @@ static int psd_batch(const char *who, int32_t n_fft, int device, int32_t n_jobs,
     if (masked && (!d_spec.upload(hspec.data(), hspec.size()) || !d_mjobs.upload(hm.data(), hm.size()) ||
                    (!hplain.empty() && !d_plain.upload(hplain.data(), hplain.size()))))
         return fail(WOFDM_E_HIP, "upload failed");
+    dev_buf<wofdm_pajob> d_pa;
+    dev_buf<float> d_jpow;
+    if (amp) {
+        if (!d_pa.alloc(hpa.size()) || !d_jpow.alloc(2 * (size_t)n_jobs)) return fail(WOFDM_E_NOMEM, "device allocation failed (amplifier)");
+        if (!d_pa.upload(hpa.data(), hpa.size())) return fail(WOFDM_E_HIP, "upload failed");
+    }
     // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
     std::lock_guard<std::mutex> gate(g_gate_mu);
     (void)hipDeviceSynchronize();
     const wofdm_aux_fns *ax = wofdm_aux(N);
     const int ni = (int)n_items, np = (int)hplain.size(), nm = (int)hm.size();
     hipError_t e = hipErrorInvalidValue;
-    if (ax && !masked) e = ax->psd_batch(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
-    if (ax && masked)
+    std::vector<float> hjpow(amp ? 2 * (size_t)n_jobs : 0);
+    const wofdm_pa_fns *axp = wofdm_aux_pa(N);
+    if (amp) {
+        // (without a masked job every job is a plain one: the job table itself)
+        if (axp)
+            e = axp->psd_batch_pa(n_jobs, no_symbols, ni, d_jobs, d_items, masked ? np : n_jobs, masked ? d_plain : d_jobs, nm,
+                                  d_mjobs, max_len, d_spec, d_Y, d_w, d_X, d_x, d_part, d_psd, d_pa, d_jpow, nullptr);
+    } else if (ax && !masked) {
+        e = ax->psd_batch(n_jobs, no_symbols, ni, d_jobs, d_items, d_w, d_X, d_x, d_part, d_psd, nullptr);
+    } else if (ax)
         e = ax->psd_batch_masked(n_jobs, no_symbols, ni, d_jobs, d_items, np, d_plain, nm, d_mjobs, max_len, d_spec, d_Y, d_w, d_X,
                                  d_x, d_part, d_psd, nullptr);
     if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        (amp && hipMemcpy(hjpow.data(), d_jpow, hjpow.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
         hipMemcpy(psd, d_psd, (size_t)n_jobs * FL * 4, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(WOFDM_E_HIP, "PSD kernels or copy-back failed: %s", hipGetErrorString(hipGetLastError()));
+    // the sums over a job's len samples -> mean powers
+    if (amp && amp->job_power)
+        for (int j = 0; j < n_jobs; ++j)
+            for (int w = 0; w < 2; ++w)
+                amp->job_power[2 * j + w] = (float)((double)hjpow[(size_t)(2 * j + w)] / (double)hj[(size_t)j].len);
     return WOFDM_OK;
 }
 
@@ -1348,6 +1417,16 @@ int wofdm_tx_psd_batch_masked(int32_t n_fft, int device, int32_t n_jobs, const w
 {
     return psd_batch("wofdm_tx_psd_batch_masked", n_fft, device, n_jobs, jobs, w_tx, n_masks, mask_len, mask_gain, job_mask,
                      n_blocks, no_symbols, X, psd);
+}
+
+int wofdm_tx_psd_batch_pa(int32_t n_fft, int device, int32_t n_jobs, const wofdm_psd_job *jobs, const float *w_tx,
+                          int32_t n_masks, const int32_t *mask_len, const float *mask_gain, const int32_t *job_mask,
+                          int32_t n_pa, const wofdm_pa_point *pa, const int32_t *job_pa, int32_t n_blocks, int32_t no_symbols,
+                          const float *X, float *psd, float *job_power)
+{
+    const psd_pa_args amp = {n_pa, pa, job_pa, job_power};
+    return psd_batch("wofdm_tx_psd_batch_pa", n_fft, device, n_jobs, jobs, w_tx, n_masks, mask_len, mask_gain, job_mask, n_blocks,
+                     no_symbols, X, psd, &amp);
 }
 
 // Every argument is checked before the first HIP call; the caller's arrays are written only after everything has succeeded.
@@ -1505,13 +1584,25 @@ struct doppler_args {
     double *sym_power;
 };
 
-// wofdm_rx_profile, wofdm_rx_profile_aci, wofdm_rx_profile_sync and wofdm_rx_profile_doppler.  Every argument is checked before the first HIP call; the
+// the power amplifier of wofdm_rx_profile_pa and its outputs; a null pointer to it is a linear transmitter
+struct pa_args {
+    int32_t n_points;
+    const wofdm_pa_point *points;
+    const float *ref_power;
+    uint64_t *sym_errs;
+    double *sym_power;
+    double *pa_power;
+};
+
+// wofdm_rx_profile, wofdm_rx_profile_aci, wofdm_rx_profile_sync, wofdm_rx_profile_doppler and wofdm_rx_profile_pa.  Every argument is checked before the first HIP call; the
 // caller's arrays are written only after everything has succeeded.
 int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                     const float *snr_db, const uint8_t *active, const float *tx_mask, const aci_args *aci, const sync_args *sync,
-                    const doppler_args *dop, uint64_t *errs, double *err_power)
+                    const doppler_args *dop, const pa_args *amp, uint64_t *errs, double *err_power)
 {
     if (!cfg || !w_tx || !w_rx || !(dop ? dop->h_track : h) || !snr_db || !errs) return fail(WOFDM_E_INVALID, "NULL argument");
+    if (amp && (!amp->points || !amp->ref_power)) return fail(WOFDM_E_INVALID, "NULL argument (points or ref_power)");
+    if (amp && amp->n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", amp->n_points);
     if (aci && !aci->active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active)");
     if (sync && !sync->points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
     if (sync && sync->n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", sync->n_points);
@@ -1574,7 +1665,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         for (int n = 0; n < N; ++n) nb |= (hiact[(size_t)n] = aci->active[n] ? 1 : 0) != 0;
     }
     // the receiver offsets: the base phasor of every (point, symbol) in double precision, from cfo as stored
-    const int NP = sync ? sync->n_points : (dop ? dop->n_tracks : 1);
+    const int NP = sync ? sync->n_points : (dop ? dop->n_tracks : (amp ? amp->n_points : 1));
     std::vector<wofdm_spoint> hpts;
     std::vector<float2> hbase;
     if (sync) {
@@ -1616,6 +1707,23 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
             return fail(WOFDM_E_INVALID, "the knots end at sample %lld, the frame's last at %d: (n_knots - 1) knot_step >= "
                         "tail_tx + S B + n_taps - 2 required", (long long)(dop->n_knots - 1) * dop->knot_step, T + L - 2);
     }
+    // the amplifier: the points, and the saturation amplitude of every (point, pair) in double precision, stored in single
+    std::vector<wofdm_papoint> hpa;
+    std::vector<float> hasat;
+    if (amp) {
+        const int prc = check_pa_points(NP, amp->points, &hpa);
+        if (prc != WOFDM_OK) return prc;
+        hasat.resize((size_t)NP * pairs);
+        for (uint64_t p = 0; p < pairs; ++p)
+            if (!std::isfinite(amp->ref_power[p]) || !(amp->ref_power[p] > 0.f))
+                return fail(WOFDM_E_INVALID, "ref_power[%llu] must be finite and positive", (unsigned long long)p);
+        for (int i = 0; i < NP; ++i)
+            for (uint64_t p = 0; p < pairs; ++p) {
+                // (the root of a positive single-precision number times 10^-4 ... 10^6 is a normal single-precision number)
+                hasat[(size_t)i * pairs + p] =
+                    (float)std::sqrt((double)amp->ref_power[p] * std::pow(10.0, 0.1 * (double)amp->points[i].ibo_db));
+            }
+    }
     int rc = use_device(device);
     if (rc != WOFDM_OK) return rc;
     g_rxprof_ms = 0.f;
@@ -1624,9 +1732,10 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     // frames per chunk: what the budget holds (symbol grid + waveform + filtered symbols + partials of a frame; with a neighbour
     // its S + 1 symbols beside them), as the header documents it
     const int Ti = T + B;
-    // (under receiver offsets or moving channels the partials are per point or track, per bin and per symbol)
+    // (under receiver offsets or moving channels the partials are per point or track, per bin and per symbol; behind the
+    // amplifier every point has a waveform of its own beside them)
     const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) +
-                                       (sync || dop ? (uint64_t)NP * (uint64_t)(N + S) : (uint64_t)N) +
+                                       (sync || dop ? (uint64_t)NP * (uint64_t)(N + S) : (amp ? (uint64_t)NP * (uint64_t)(N + S + T) : (uint64_t)N)) +
                                        (nb ? (uint64_t)(S + 1) * N + (uint64_t)Ti + (tx_mask ? (uint64_t)(S + 1) * Lm : 0ull) : 0ull));
     const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
                                                                        std::max<uint64_t>(1, WOFDM_RX_PROFILE_CHUNK_BYTES / job_bytes)));
@@ -1651,7 +1760,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     std::vector<float> nlin((size_t)cfg->n_snr);
     for (int i = 0; i < cfg->n_snr; ++i) nlin[(size_t)i] = (float)std::pow(10.0, -0.1 * (double)snr_db[i]);
     const size_t n_w = (size_t)pairs * P, n_wr = (size_t)pairs * NW, n_out = (size_t)NP * cells * N;
-    const size_t n_sym = sync || dop ? (size_t)NP * cells * (S - 1) : 0;
+    const size_t n_sym = sync || dop || amp ? (size_t)NP * cells * (S - 1) : 0;
     dev_buf<float> d_w, d_wr, d_nlin, d_ppow;
     dev_buf<uint8_t> d_act;
     dev_buf<float2> d_h, d_spec, d_X, d_x, d_Y;
@@ -1679,12 +1788,26 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     dev_buf<uint32_t> d_scnt;
     dev_buf<unsigned long long> d_serrs;
     dev_buf<double> d_stot;
-    if (sync || dop) {
+    if (sync || dop || amp) {
         if ((sync && (!d_pts.alloc(hpts.size()) || !d_base.alloc(hbase.size()))) || !d_spow.alloc((size_t)chunk * NP * S) ||
             !d_scnt.alloc((size_t)chunk * NP * S) || !d_serrs.alloc(2 * n_sym) || !d_stot.alloc(n_sym))
             return fail(WOFDM_E_NOMEM, "device allocation failed (receiver offsets or tracks)");
         if ((sync && (!d_pts.upload(hpts.data(), hpts.size()) || !d_base.upload(hbase.data(), hbase.size()))) ||
             hipMemset(d_serrs, 0, 2 * n_sym * 8) != hipSuccess || hipMemset(d_stot, 0, n_sym * 8) != hipSuccess)
+            return fail(WOFDM_E_HIP, "upload failed");
+    }
+    // the amplifier's side: points, saturation amplitudes, the points' waveforms and power sums of the chunk, the power totals
+    dev_buf<wofdm_papoint> d_papts;
+    dev_buf<float> d_asat, d_pwr;
+    dev_buf<float2> d_y;
+    dev_buf<double> d_ptot;
+    const size_t n_ptot = amp ? (size_t)NP * cells * 2 : 0;
+    if (amp) {
+        if (!d_papts.alloc(hpa.size()) || !d_asat.alloc(hasat.size()) || !d_y.alloc((size_t)chunk * NP * T) ||
+            !d_pwr.alloc((size_t)chunk * NP * 2) || !d_ptot.alloc(n_ptot))
+            return fail(WOFDM_E_NOMEM, "device allocation failed (amplifier)");
+        if (!d_papts.upload(hpa.data(), hpa.size()) || !d_asat.upload(hasat.data(), hasat.size()) ||
+            hipMemset(d_ptot, 0, n_ptot * 8) != hipSuccess)
             return fail(WOFDM_E_HIP, "upload failed");
     }
     // the neighbour's side of the chunk: allocation, channels, and grids, waveforms, tables of its S + 1 symbols
@@ -1719,6 +1842,11 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     if (dop) {
         dpar.knots = d_h; dpar.n_knots = dop->n_knots; dpar.knot_step = dop->knot_step;
     }
+    wofdm_paparams papar{};
+    if (amp) {
+        papar.n_points = NP; papar.pairs = (int32_t)pairs; papar.pts = d_papts; papar.asat = d_asat; papar.y = d_y;
+        papar.pwr = d_pwr; papar.pwr_tot = d_ptot;
+    }
     wofdm_rparams rp{};
     rp.S = S; rp.k = k; rp.B = B; rp.T = T; rp.NL = cfg->noise_before_truncate ? T + L - 1 : S * B;
     rp.delta = delta; rp.gam = gam; rp.kap = cfg->circ_shift; rp.n_ch = cfg->n_channels; rp.n_snr = cfg->n_snr;
@@ -1734,7 +1862,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         apar.a_lvl = (float)std::pow(10.0, 0.05 * (double)aci->level_db);
     }
     std::vector<unsigned long long> herr(2 * n_out), hserr(2 * n_sym);
-    std::vector<double> hpow(n_out), hspow(n_sym);
+    std::vector<double> hpow(n_out), hspow(n_sym), hptot(n_ptot);
     float ms = 0.f;
     hipError_t e = hipSuccess;
     {
@@ -1742,13 +1870,15 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         std::lock_guard<std::mutex> gate(g_gate_mu);
         (void)hipDeviceSynchronize();
         const wofdm_aux_fns *ax = wofdm_aux(N);
-        e = ax ? hipEventRecord(ev[0], nullptr) : hipErrorInvalidValue;
+        const wofdm_pa_fns *axp = wofdm_aux_pa(N);
+        e = ax && axp ? hipEventRecord(ev[0], nullptr) : hipErrorInvalidValue;
         for (uint64_t i0 = 0; e == hipSuccess && i0 < items; i0 += chunk) {
             pp.item0 = rp.item0 = i0;
             pp.n_jobs = rp.n_jobs = (int32_t)std::min<uint64_t>(chunk, items - i0);
             pa.item0 = pp.item0;
             pa.n_jobs = pp.n_jobs;
-            e = dop ? ax->rx_profile_doppler(&pp, &rp, &spar, &dpar, nullptr)
+            e = amp ? axp->rx_profile_pa(&pp, &rp, &spar, &papar, nullptr)
+                : dop ? ax->rx_profile_doppler(&pp, &rp, &spar, &dpar, nullptr)
                 : sync ? ax->rx_profile_sync(&pp, &rp, &spar, nullptr)
                      : (nb ? ax->rx_profile_aci(&pp, &pa, &rp, &apar, nullptr) : ax->rx_profile(&pp, &rp, nullptr));
         }
@@ -1761,18 +1891,21 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     if (e != hipSuccess || hipMemcpy(herr.data(), d_errs, 2 * n_out * 8, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(hpow.data(), d_pow, n_out * 8, hipMemcpyDeviceToHost) != hipSuccess ||
         (n_sym && (hipMemcpy(hserr.data(), d_serrs, 2 * n_sym * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                   hipMemcpy(hspow.data(), d_stot, n_sym * 8, hipMemcpyDeviceToHost) != hipSuccess)))
+                   hipMemcpy(hspow.data(), d_stot, n_sym * 8, hipMemcpyDeviceToHost) != hipSuccess)) ||
+        (n_ptot && hipMemcpy(hptot.data(), d_ptot, n_ptot * 8, hipMemcpyDeviceToHost) != hipSuccess))
         return fail(WOFDM_E_HIP, "receive-profile kernels or copy-back failed: %s",
                     hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
     for (size_t i = 0; i < 2 * n_out; ++i) errs[i] += herr[i];
     if (err_power)
         for (size_t i = 0; i < n_out; ++i) err_power[i] += hpow[i];
-    uint64_t *sym_errs = sync ? sync->sym_errs : (dop ? dop->sym_errs : nullptr);
-    double *sym_power = sync ? sync->sym_power : (dop ? dop->sym_power : nullptr);
+    uint64_t *sym_errs = sync ? sync->sym_errs : (dop ? dop->sym_errs : (amp ? amp->sym_errs : nullptr));
+    double *sym_power = sync ? sync->sym_power : (dop ? dop->sym_power : (amp ? amp->sym_power : nullptr));
     if (sym_errs)
         for (size_t i = 0; i < 2 * n_sym; ++i) sym_errs[i] += hserr[i];
     if (sym_power)
         for (size_t i = 0; i < n_sym; ++i) sym_power[i] += hspow[i];
+    if (amp && amp->pa_power)
+        for (size_t i = 0; i < n_ptot; ++i) amp->pa_power[i] += hptot[i];
     g_rxprof_ms = ms;
     return WOFDM_OK;
 }
@@ -1784,7 +1917,7 @@ extern "C" {
 int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                      const float *snr_db, const uint8_t *active, const float *tx_mask, uint64_t *errs, double *err_power)
 {
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -1792,7 +1925,7 @@ int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, co
                          const float *aci_h, int32_t aci_delay, float aci_level_db, uint64_t *errs, double *err_power)
 {
     const aci_args aci = {aci_active, aci_h, aci_delay, aci_level_db};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -1800,7 +1933,7 @@ int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, c
                           const wofdm_sync_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const sync_args sync = {n_points, points, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h_track,
@@ -1808,7 +1941,16 @@ int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device, const float *w_tx
                              const float *tx_mask, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const doppler_args dop = {h_track, n_tracks, n_knots, knot_step, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask, nullptr, nullptr, &dop, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask, nullptr, nullptr, &dop, nullptr, errs, err_power);
+}
+
+int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                        const uint8_t *active, const float *tx_mask, int32_t n_points, const wofdm_pa_point *points,
+                        const float *ref_power, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power,
+                        double *pa_power)
+{
+    const pa_args amp = {n_points, points, ref_power, sym_errs, sym_power, pa_power};
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, &amp, errs, err_power);
 }
 
 int wofdm_rx_profile_kernel_ms(float *ms)

@@ -1,8 +1,9 @@
 // wofdm_aux.hip -- the auxiliary kernels beside the frame kernel: closed-form ICI/ISI power (wofdm_interference,
 // wofdm_interference_masked) and Tx waveform + averaged periodogram (wofdm_tx_psd, wofdm_tx_psd_batch,
-// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile; beside an adjacent-band neighbour: wofdm_rx_profile_aci; under receiver timing and carrier offsets: wofdm_rx_profile_sync; over channels that move within the frame: wofdm_rx_profile_doppler).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
+// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile; beside an adjacent-band neighbour: wofdm_rx_profile_aci; under receiver timing and carrier offsets: wofdm_rx_profile_sync; over channels that move within the frame: wofdm_rx_profile_doppler; behind a nonlinear power amplifier: wofdm_rx_profile_pa, wofdm_tx_psd_batch_pa).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
 // on n_fft through the unit's table of launchers (wofdm_aux_fns).
 #include "wofdm_kernel.h"
+#include "wofdm_pa.h"
 #include "wofdm_device.h"
 #include "philox.h"
 #include <type_traits>
@@ -1812,6 +1813,355 @@ __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_doppler_k
     rxprof_doppler_body<N>(p, sp, dp);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The memoryless power amplifier behind the Tx chain (wofdm_rx_profile_pa, wofdm_tx_psd_batch_pa; wofdm_pa.h): y = g x with
+// r = |x|, rho = r / a_sat; the phase is untouched (no AM/PM).
+//   WOFDM_PA_M_LINEAR  y = x, no arithmetic at all
+//   WOFDM_PA_M_RAPP    g = (1 + rho^(2p))^(-1/(2p)); above rho = 1 in the form (1 / rho) (1 + rho^(-2p))^(-1/(2p)), so that no
+//                      finite input overflows: with u = 2^(-2p |log2 rho|) <= 1 both forms are 2^(-log2(1 + u) / (2p)), times
+//                      1 / rho above 1.  log2 / exp2 are the hardware forms (v_log_f32, v_exp_f32): their absolute error of an ulp or so of the
+//                      argument's logarithm reaches g as some 1e-7, the rounding of the fp32 chain around it.
+//   WOFDM_PA_M_CLIP    the soft limiter, the p -> infinity limit: g = 1 up to rho = 1, 1 / rho above
+// g = 1 at r = 0.  The ONE definition both routes' kernels call; rx_profile.pa_gain is its fp64 mirror.
+__device__ __forceinline__ float2 pa_amplify(const float2 v, int model, float asat, float two_p, float inv_two_p)
+{
+    if (model == WOFDM_PA_M_LINEAR) return v;
+    const float r = sqrtf(v.x * v.x + v.y * v.y);
+    if (!(r > 0.f)) return v;
+    const float rho = r / asat;
+    float g;
+    if (model == WOFDM_PA_M_CLIP) {
+        g = rho > 1.f ? 1.0f / rho : 1.f;
+    } else {
+        const float u = __builtin_amdgcn_exp2f(-two_p * fabsf(__builtin_amdgcn_logf(rho)));
+        g = __builtin_amdgcn_exp2f(-inv_two_p * __builtin_amdgcn_logf(1.f + u));
+        if (rho > 1.f) g = g / rho;
+    }
+    return make_float2(g * v.x, g * v.y);
+}
+
+// The amplified waveforms of wofdm_rx_profile_pa: grid (jobs of the chunk, points), 256 threads.  y[job][point][t] =
+// pa_amplify(x[job][t]) with a_sat of (point, the pair of the job's cell); a linear point writes nothing -- the receive kernel
+// reads x itself.  pwr[job][point] = {sum |x|^2, sum |y|^2} over the T samples: thread-strided partials, the wave sum of
+// papr_wave_reduce, the four waves in order.
+__global__ void __launch_bounds__(256) wofdm_pa_wave_kernel(const wofdm_paparams pa, const float2 *__restrict__ x, int T, uint64_t item0,
+                                                            uint64_t frames, uint32_t cpp)
+{
+    __shared__ float red[2][4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t job = blockIdx.x, pt = blockIdx.y;
+    const uint64_t cell = (item0 + job) / frames;
+    const uint32_t pair = (uint32_t)(cell / cpp);
+    const wofdm_papoint q = pa.pts[pt];
+    const float asat = pa.asat[(size_t)pt * pa.pairs + pair];
+    const float2 *__restrict__ src = x + (size_t)job * T;
+    float2 *__restrict__ dst = pa.y + ((size_t)job * pa.n_points + pt) * (size_t)T;
+    float si = 0.f, so = 0.f;
+    if (q.model == WOFDM_PA_M_LINEAR) {
+        for (int t = tid; t < T; t += 256) {
+            const float2 v = src[t];
+            si += v.x * v.x + v.y * v.y;
+        }
+        so = si;
+    } else {
+        for (int t = tid; t < T; t += 256) {
+            const float2 v = src[t], w = pa_amplify(v, q.model, asat, q.two_p, q.inv_two_p);
+            dst[t] = w;
+            si += v.x * v.x + v.y * v.y;
+            so += w.x * w.x + w.y * w.y;
+        }
+    }
+    si = papr_wave_reduce<false>(si);
+    so = papr_wave_reduce<false>(so);
+    if (lane == 0) {
+        red[0][wv] = si;
+        red[1][wv] = so;
+    }
+    __syncthreads();
+    if (tid < 2) {
+        float t = 0.f;
+        for (int w = 0; w < 4; ++w) t += red[tid][w];
+        pa.pwr[((size_t)job * pa.n_points + pt) * 2 + tid] = t;
+    }
+}
+
+// pwr_tot[point][cell][2] += the chunk's items of the cell, in frame order, one addition per frame onto the running fp64 total;
+// grid (cells the chunk touches), a thread per (point, which)
+__global__ void __launch_bounds__(64) wofdm_pa_power_reduce_kernel(const wofdm_paparams pa, uint64_t item0, int n_jobs, uint64_t frames,
+                                                                   uint64_t cells, uint64_t cell0)
+{
+    const uint32_t pt = threadIdx.x >> 1, which = threadIdx.x & 1;
+    if (pt >= (uint32_t)pa.n_points) return;
+    const uint64_t cell = cell0 + blockIdx.x, end = item0 + (uint64_t)n_jobs;
+    const uint64_t lo = cell * frames > item0 ? cell * frames : item0;
+    const uint64_t hi = (cell + 1) * frames < end ? (cell + 1) * frames : end;
+    if (lo >= hi) return;
+    const size_t out = ((size_t)pt * cells + cell) * 2 + which;
+    double acc = pa.pwr_tot[out];
+    for (uint64_t i = lo; i < hi; ++i) acc += (double)pa.pwr[((size_t)(i - item0) * pa.n_points + pt) * 2 + which];
+    pa.pwr_tot[out] = acc;
+}
+
+// The receive profile behind the amplifier (wofdm_rx_profile_pa): the item, the LDS image, the DFT, the pilot step, the
+// per-bin and per-symbol partials and their order are rxprof_sync_body's -- a body of its own again, so that the four kernels
+// above compile as they did --, with BOTH passes run once per point of pa (sp.n_points points; theta and eps do not exist
+// here) on the point's waveform: y[job][point] of wofdm_pa_wave_kernel, or x itself for a linear point.  Ps is measured per
+// point on conv(h, y); Pn does not depend on the waveform and is measured with the first point; the noise of on-air sample a
+// is the plain kernel's.  The taps are wave-uniform as in wofdm_rxprof_kernel, but two inlined copies of one expression need
+// not round alike (the note above dop_tap): the tap sums are written with dop_tap, the operations the plain kernel's
+// assembly shows, so a linear point gives its bits.  LDS: rxp_geo<N>::LDS.
+template <int N>
+__device__ __forceinline__ void rxprof_pa_body(const wofdm_rparams &p, const wofdm_sparams &sp, const wofdm_paparams &pa)
+{
+    using RG = rxp_geo<N>;
+    constexpr int ROWLEN = N + RG::XROW;
+    constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float2 *tw = reinterpret_cast<float2 *>(smem);                    // e^{-2 pi i k / N}, k < N / 2
+    float2 *G = tw + N / 2;                                           // pilot equaliser X0 / Y0 of the point
+    float *wrx = reinterpret_cast<float *>(G + N);
+    float *red = wrx + N + 64;                                        // [2][W] power partials
+    float2 *rows = reinterpret_cast<float2 *>(red + 64);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int S = p.S, B = p.B, T = p.T, NL = p.NL, delta = p.delta, NP = sp.n_points;
+    const uint32_t job = blockIdx.x;
+    const uint64_t item = p.item0 + job, cell64 = item / p.frames, frame = p.frame_offset + (item - cell64 * p.frames);
+    const uint32_t cell = (uint32_t)cell64, f_lo = (uint32_t)frame, f_hi = (uint32_t)(frame >> 32);
+    const int ch = (int)(cell % (uint32_t)p.n_ch), sn = (int)((cell / (uint32_t)p.n_ch) % (uint32_t)p.n_snr);
+    const int pair = (int)(cell / ((uint32_t)p.n_ch * (uint32_t)p.n_snr));
+    const float2 *__restrict__ Xg = p.X + (size_t)job * S * N;
+    const float2 *__restrict__ taps = p.h + (size_t)ch * LT;
+    for (int i = tid; i < N / 2; i += NT) {
+        float sv, cv;
+        sincospif(-2.0f * (float)i / (float)N, &sv, &cv);
+        tw[i] = make_float2(cv, sv);
+    }
+    for (int i = tid; i < N + delta; i += NT) wrx[i] = p.wrx[(size_t)pair * (N + delta) + i];
+    float2 *buf = rows + (size_t)wv * ROWLEN;
+    float2 *xr = buf + N;
+    const int h2 = delta >> 1;
+#pragma unroll 1
+    for (int pt = 0; pt < NP; ++pt) {
+        // the point's on-air waveform
+        const float2 *__restrict__ x = pa.pts[pt].model == WOFDM_PA_M_LINEAR ? p.x + (size_t)job * T
+                                                                             : pa.y + ((size_t)job * NP + pt) * (size_t)T;
+        // pass 1, once per point: the signal power over the NL samples of conv(h, y); the noise power with the first
+        float ps = 0.f, pn = 0.f;
+        for (int q = tid; 2 * q < NL; q += NT) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int jj = 2 * q + e;
+                if (jj >= NL) break;
+                float cr = 0.f, ci = 0.f;
+                for (int l = 0; l < LT; ++l) {
+                    const int t = jj - l;
+                    if (t < 0 || t >= T) continue;
+                    dop_tap<false>(taps[l], x[t], cr, ci);
+                }
+                ps += cr * cr + ci * ci;
+                if (pt == 0) {
+                    const v2f nz = rxp_noise((uint32_t)q, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, e);
+                    pn += nz.x * nz.x + nz.y * nz.y;
+                }
+            }
+        }
+        ps = papr_wave_reduce<false>(ps);
+        if (lane == 0) red[wv] = ps;
+        if (pt == 0) {
+            pn = papr_wave_reduce<false>(pn);
+            if (lane == 0) red[W + wv] = pn;
+        }
+        __syncthreads();
+        float Ps = 0.f, Pn = 0.f;
+        for (int w = 0; w < W; ++w) {
+            Ps += red[w];
+            Pn += red[W + w];
+        }
+        const float g = sqrtf(Ps * p.nlin[sn] / Pn);
+        // pass 2 of the point
+        const size_t slot = (size_t)job * NP + pt;
+        float pw[BINS];
+        uint32_t cnt[BINS];
+#pragma unroll
+        for (int j = 0; j < BINS; ++j) {
+            pw[j] = 0.f;
+            cnt[j] = 0u;
+        }
+        for (int s0 = 0; s0 < S; s0 += W) {
+            const int s = s0 + wv;
+            const bool live = s < S;                                  // (wave-uniform)
+            if (live) {
+                const int a0 = s * B + p.gam;                         // first sample under the Rx window
+                for (int i = lane; i < N + delta + LT - 1; i += 64) {
+                    const int t = a0 - (LT - 1) + i;
+                    xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
+                }
+                wave_sync();
+                // r[a] = conv[a] + g n[a] of the sample m under the window, a = a0 + m
+                auto rxs = [&](int m, auto fold) {
+                    float cr = 0.f, ci = 0.f;
+#pragma unroll
+                    for (int l = 0; l < LT; ++l) dop_tap<decltype(fold)::value>(taps[l], xr[m + (LT - 1) - l], cr, ci);
+                    const uint32_t a = (uint32_t)(a0 + m);
+                    const v2f nz = rxp_noise(a >> 1, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, (int)(a & 1u));
+                    return make_float2(cr + g * nz.x, ci + g * nz.y);
+                };
+#pragma unroll 1
+                for (int j = 0; j < BINS; ++j) {
+                    const int t = lane + 64 * j, m0 = (t + p.kap + h2) & (N - 1);
+                    float2 z = rxs(m0, std::false_type{});
+                    z.x *= wrx[m0];
+                    z.y *= wrx[m0];
+                    if (m0 < delta) {
+                        const float2 z2 = rxs(m0 + N, std::true_type{});
+                        z.x += wrx[m0 + N] * z2.x;
+                        z.y += wrx[m0 + N] * z2.y;
+                    }
+                    buf[__brev((uint32_t)t) >> (32 - LOG2)] = z;
+                }
+                wave_sync();
+                for (int len = 2, sh = LOG2 - 1; len <= N; len <<= 1, --sh) {
+                    const int half = len >> 1;
+                    for (int b = lane; b < N / 2; b += 64) {
+                        const int kk = b & (half - 1), i = ((b - kk) << 1) | kk;
+                        const float2 w = tw[kk << sh], a = buf[i], c = buf[i + half];
+                        const float tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
+                        buf[i] = make_float2(a.x + tr, a.y + ti);
+                        buf[i + half] = make_float2(a.x - tr, a.y - ti);
+                    }
+                    wave_sync();
+                }
+            }
+            if (s0 == 0) {
+                // pilot LS estimate of the point: the pilot went through the amplifier as the data did
+                if (wv == 0)
+                    for (int n = lane; n < N; n += 64) {
+                        const float2 y = buf[n], x0 = Xg[n];
+                        const float d = y.x * y.x + y.y * y.y;
+                        const bool on = p.amask == nullptr || p.amask[n] != 0;
+                        G[n] = on ? make_float2((x0.x * y.x + x0.y * y.y) / d, (x0.y * y.x - x0.x * y.y) / d) : make_float2(0.f, 0.f);
+                    }
+                __syncthreads();
+            }
+            if (live) {
+                float spw = 0.f;
+                uint32_t scn = 0u;
+                if (s >= 1) {
+#pragma unroll
+                    for (int j = 0; j < BINS; ++j) {
+                        const int n = lane + 64 * j;
+                        if (p.amask != nullptr && p.amask[n] == 0) continue;
+                        const float2 y = buf[n], gq = G[n], xs = Xg[(size_t)s * N + n];
+                        const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;
+                        const uint32_t d = rxp_slice(p.k, xs.x, xs.y) ^ rxp_slice(p.k, er, ei);
+                        const uint32_t c = (uint32_t)__popc(d) + (d != 0u ? 0x10000u : 0u);
+                        const float e2 = (er - xs.x) * (er - xs.x) + (ei - xs.y) * (ei - xs.y);
+                        cnt[j] += c;
+                        pw[j] += e2;
+                        scn += c;
+                        spw += e2;
+                    }
+                }
+                // the symbol's sums over the bins: at most N k < 2^16 bit errors and N symbol errors, so the halves do not meet
+                spw = papr_wave_reduce<false>(spw);
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) scn += (uint32_t)__shfl_xor((int)scn, o, 64);
+                if (lane == 0) {
+                    sp.sym_pow[slot * S + s] = spw;
+                    sp.sym_cnt[slot * S + s] = scn;
+                }
+            }
+            wave_sync();
+        }
+        // the waves' sums in wave order (their rows are free now): float [W][N], then uint32 [W][N]
+        __syncthreads();
+        float *redp = reinterpret_cast<float *>(rows);
+        uint32_t *redc = reinterpret_cast<uint32_t *>(redp + W * N);
+#pragma unroll
+        for (int j = 0; j < BINS; ++j) {
+            redp[wv * N + lane + 64 * j] = pw[j];
+            redc[wv * N + lane + 64 * j] = cnt[j];
+        }
+        __syncthreads();
+        for (int n = tid; n < N; n += NT) {
+            float t = 0.f;
+            uint32_t c = 0u;
+            for (int w = 0; w < W; ++w) {
+                t += redp[w * N + n];
+                c += redc[w * N + n];
+            }
+            p.part_pow[slot * N + n] = t;
+            p.part_cnt[slot * N + n] = c;
+        }
+        __syncthreads();                                              // the rows and G belong to the next point
+    }
+}
+
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_pa_kernel(const wofdm_rparams p, const wofdm_sparams sp,
+                                                                                const wofdm_paparams pa)
+{
+    rxprof_pa_body<N>(p, sp, pa);
+}
+
+// The amplifier of wofdm_tx_psd_batch_pa, two kernels between the waveform kernels and the periodogram; grid (jobs), 1024
+// threads each.  The first leaves power[job][0] = sum |x|^2 over the job's len samples (thread-strided partials,
+// papr_wave_reduce, the 16 waves in order: a fixed order); the second forms a_sat^2 = (sum / len) 10^(ibo / 10) in double,
+// stores a_sat in single precision, amplifies the job's waveform in place and leaves power[job][1] = sum |y|^2, in the same
+// order.  A job without an amplifier, with a linear one or without power keeps its waveform, bit for bit, and gets
+// power[job][1] = power[job][0].
+__global__ void __launch_bounds__(1024) wofdm_pa_job_power_kernel(const wofdm_bjob *__restrict__ jobs, const float2 *__restrict__ x,
+                                                                  float *__restrict__ power)
+{
+    __shared__ float red[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const wofdm_bjob jb = jobs[blockIdx.x];
+    const float2 *__restrict__ src = x + jb.x_off;
+    float si = 0.f;
+    for (int t = tid; t < jb.len; t += 1024) {
+        const float2 v = src[t];
+        si += v.x * v.x + v.y * v.y;
+    }
+    si = papr_wave_reduce<false>(si);
+    if (lane == 0) red[wv] = si;
+    __syncthreads();
+    if (tid == 0) {
+        float t = 0.f;
+        for (int w = 0; w < 16; ++w) t += red[w];
+        power[2 * blockIdx.x] = t;
+    }
+}
+__global__ void __launch_bounds__(1024) wofdm_pa_job_apply_kernel(const wofdm_bjob *__restrict__ jobs, const wofdm_pajob *__restrict__ pa,
+                                                                  float2 *__restrict__ x, float *__restrict__ power)
+{
+    __shared__ float red[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const wofdm_bjob jb = jobs[blockIdx.x];
+    const wofdm_pajob q = pa[blockIdx.x];
+    const float sum_in = power[2 * blockIdx.x];
+    if (q.model < 0 || q.model == WOFDM_PA_M_LINEAR || !(sum_in > 0.f)) {         // (uniform over the workgroup)
+        if (tid == 0) power[2 * blockIdx.x + 1] = sum_in;
+        return;
+    }
+    const float asat = (float)sqrt((double)sum_in / (double)jb.len * q.scale);
+    float2 *__restrict__ xj = x + jb.x_off;
+    float so = 0.f;
+    for (int t = tid; t < jb.len; t += 1024) {
+        const float2 w = pa_amplify(xj[t], q.model, asat, q.two_p, q.inv_two_p);
+        xj[t] = w;
+        so += w.x * w.x + w.y * w.y;
+    }
+    so = papr_wave_reduce<false>(so);
+    if (lane == 0) red[wv] = so;
+    __syncthreads();
+    if (tid == 0) {
+        float t = 0.f;
+        for (int w = 0; w < 16; ++w) t += red[w];
+        power[2 * blockIdx.x + 1] = t;
+    }
+}
+
 #if WOFDM_TU_N == 64
 // Philox known-answer kernel (wofdm_philox_kat): in one unit only
 __global__ void philox_kat_kernel(const uint32_t *ck, uint32_t *out)
@@ -1882,10 +2232,11 @@ hipError_t psd_batch_launch(int n_jobs, int no_symbols, int n_items, const wofdm
 
 // wofdm_tx_psd_batch_masked: the unmasked jobs' waveforms by wofdm_txwave_batch_kernel, the masked ones by the fast-convolution
 // kernel and its gather, then periodogram and reduction of all jobs as in psd_batch_launch
-hipError_t psd_batch_masked_launch(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs, const wofdm_bitem *items,
-                                   int n_plain, const wofdm_bjob *plain_jobs, int n_masked, const wofdm_mjob *mjobs, int max_len,
-                                   const float2 *spec, float2 *Y, const float *wtx, const float2 *X, float2 *x, float *partial,
-                                   float *psd, hipStream_t s)
+// (pa, power: the amplifier of wofdm_tx_psd_batch_pa between the waveforms and the periodogram, or null)
+hipError_t psd_batch_masked_impl(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs, const wofdm_bitem *items,
+                                 int n_plain, const wofdm_bjob *plain_jobs, int n_masked, const wofdm_mjob *mjobs, int max_len,
+                                 const float2 *spec, float2 *Y, const float *wtx, const float2 *X, float2 *x, float *partial,
+                                 float *psd, const wofdm_pajob *pa, float *power, hipStream_t s)
 {
     constexpr int N = WOFDM_TU_N, FL = 8 * N, M = FL / wofdm_psd_batch_r(N), WW = bwave_geo<N>::WAVES, G = bmask_geo<N>::G;
     const size_t lds_a = 8 * (size_t)N * (1 + WW), lds_b = 8 * (size_t)M * 9, lds_m = bmask_geo<N>::LDS;
@@ -1907,10 +2258,32 @@ hipError_t psd_batch_masked_launch(int n_jobs, int no_symbols, int n_items, cons
         hipLaunchKernelGGL(wofdm_txmask_ola_kernel<N>, dim3((max_len + 255) / 256, n_masked), dim3(256), 0, s, jobs, mjobs,
                            no_symbols, (const float2 *)Y, x);
     }
+    if (pa != nullptr) {
+        hipLaunchKernelGGL(wofdm_pa_job_power_kernel, dim3(n_jobs), dim3(1024), 0, s, jobs, (const float2 *)x, power);
+        hipLaunchKernelGGL(wofdm_pa_job_apply_kernel, dim3(n_jobs), dim3(1024), 0, s, jobs, pa, x, power);
+    }
     hipLaunchKernelGGL(wofdm_psd_batch_kernel<FL>, dim3(n_items), dim3(512), lds_b, s, jobs, items, (const float2 *)x, partial);
     hipLaunchKernelGGL(wofdm_psd_reduce_kernel<FL>, dim3((FL + 255) / 256, n_jobs), dim3(256), 0, s, jobs,
                        (const float *)partial, psd);
     return hipGetLastError();
+}
+hipError_t psd_batch_masked_launch(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs, const wofdm_bitem *items,
+                                   int n_plain, const wofdm_bjob *plain_jobs, int n_masked, const wofdm_mjob *mjobs, int max_len,
+                                   const float2 *spec, float2 *Y, const float *wtx, const float2 *X, float2 *x, float *partial,
+                                   float *psd, hipStream_t s)
+{
+    return psd_batch_masked_impl(n_jobs, no_symbols, n_items, jobs, items, n_plain, plain_jobs, n_masked, mjobs, max_len, spec, Y,
+                                 wtx, X, x, partial, psd, nullptr, nullptr, s);
+}
+// wofdm_tx_psd_batch_pa (wofdm_pa_fns)
+hipError_t psd_batch_pa_launch(int n_jobs, int no_symbols, int n_items, const wofdm_bjob *jobs, const wofdm_bitem *items,
+                               int n_plain, const wofdm_bjob *plain_jobs, int n_masked, const wofdm_mjob *mjobs, int max_len,
+                               const float2 *spec, float2 *Y, const float *wtx, const float2 *X, float2 *x, float *partial,
+                               float *psd, const wofdm_pajob *pa, float *power, hipStream_t s)
+{
+    if (pa == nullptr || power == nullptr) return hipErrorInvalidValue;
+    return psd_batch_masked_impl(n_jobs, no_symbols, n_items, jobs, items, n_plain, plain_jobs, n_masked, mjobs, max_len, spec, Y,
+                                 wtx, X, x, partial, psd, pa, power, s);
 }
 
 // wofdm_interference_masked: the pulses of every pair, then the (pair, channel) jobs
@@ -2091,7 +2464,49 @@ hipError_t rx_profile_doppler_launch(const wofdm_pparams *pp, const wofdm_rparam
     return hipGetLastError();
 }
 
+// wofdm_rx_profile_pa, one chunk: the Tx chain once, the points' amplified waveforms and power sums, the receive kernel over
+// the points, rx_profile_sync's ordered sums with the points as its points, and the power sums in frame order
+hipError_t rx_profile_pa_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, const wofdm_sparams *spp, const wofdm_paparams *pap,
+                                hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N;
+    const wofdm_rparams &r = *rp;
+    const wofdm_sparams &sp = *spp;
+    const wofdm_paparams &pa = *pap;
+    if (r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
+        r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 || r.n_snr < 1)
+        return hipErrorInvalidValue;
+    if (sp.n_points < 1 || sp.n_points > WOFDM_PA_POINTS || sp.sym_pow == nullptr || sp.sym_cnt == nullptr ||
+        sp.sym_errs == nullptr || sp.sym_tot == nullptr || r.S < 2 || r.S > 64 ||
+        (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames >= sp.cells)
+        return hipErrorInvalidValue;
+    const uint64_t cell0 = r.item0 / r.frames, cell1 = (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames;
+    // the saturation table covers the pair of every cell of the chunk
+    if (pa.n_points != sp.n_points || pa.pairs < 1 || pa.pts == nullptr || pa.asat == nullptr || pa.y == nullptr || pa.pwr == nullptr ||
+        pa.pwr_tot == nullptr || r.x != pp->x || cell1 / pp->wdiv >= (uint64_t)pa.pairs)
+        return hipErrorInvalidValue;
+    hipError_t e = tx_chain_launch(*pp, s);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_pa_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                rxp_geo<N>::LDS);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_pa_wave_kernel, dim3((unsigned)r.n_jobs, (unsigned)pa.n_points), dim3(256), 0, s, pa, r.x, r.T, r.item0,
+                       r.frames, pp->wdiv);
+    hipLaunchKernelGGL(wofdm_rxprof_pa_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r, sp, pa);
+    hipLaunchKernelGGL(wofdm_rxprof_sync_reduce_kernel<N>, dim3(N / 64 + 1, (unsigned)(cell1 - cell0 + 1), (unsigned)sp.n_points),
+                       dim3(64), 0, s, r, sp, cell0);
+    hipLaunchKernelGGL(wofdm_pa_power_reduce_kernel, dim3((unsigned)(cell1 - cell0 + 1)), dim3(64), 0, s, pa, r.item0, r.n_jobs,
+                       r.frames, sp.cells, cell0);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
+{
+    static const wofdm_pa_fns fns = {rx_profile_pa_launch, psd_batch_pa_launch};
+    return &fns;
+}
 
 const wofdm_aux_fns *WOFDM_CAT(wofdm_aux_n, WOFDM_TU_N)(void)
 {

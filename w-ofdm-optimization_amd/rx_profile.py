@@ -20,6 +20,10 @@ mirror it.
 ``rx_profile_doppler_gpu`` (``wofdm_rx_profile_doppler``) is the profile over channels that move within the frame, a list of
 tracks (knots of the tap vector, linear in between) per call; ``tv_conv``, ``frame_profile_doppler`` and
 ``rx_profile_doppler_host`` mirror it.
+
+``rx_profile_pa_gpu`` (``wofdm_rx_profile_pa``) is the profile behind a memoryless power amplifier (linear, Rapp, soft
+limiter), a list of ``PaPoint`` per call, with the power before and behind the amplifier; ``pa_gain``, ``pa_apply``,
+``frame_profile_pa`` and ``rx_profile_pa_host`` mirror it, ``pa_ref_power`` measures the mean power the back-off counts from.
 """
 import collections
 
@@ -427,8 +431,8 @@ def rx_profile_aci_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db,
 
 
 def rx_profile_kernel_ms():
-    """Milliseconds the kernels of this thread's last ``rx_profile_gpu``, ``rx_profile_aci_gpu`` or ``rx_profile_sync_gpu``
-    call took (``wofdm_rx_profile_kernel_ms``)."""
+    """Milliseconds the kernels of this thread's last ``rx_profile_gpu``, ``rx_profile_aci_gpu``, ``rx_profile_sync_gpu``,
+    ``rx_profile_doppler_gpu`` or ``rx_profile_pa_gpu`` call took (``wofdm_rx_profile_kernel_ms``)."""
     import ctypes as C
     from . import _lib
     ms = C.c_float()
@@ -740,3 +744,221 @@ def rx_profile_doppler_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, tracks
             raise ValueError("out has another shape")
         prof = RxProfileSync(*(a + b for a, b in zip(out, prof)))
     return prof
+
+
+# ---- behind a nonlinear power amplifier (wofdm_rx_profile_pa) ----
+
+PA_LINEAR, PA_RAPP, PA_CLIP = 0, 1, 2                      # include/wofdm.h
+
+PaPoint = collections.namedtuple("PaPoint", "model ibo_db smooth", defaults=(2.0,))
+PaPoint.__doc__ = """One amplifier of ``wofdm_rx_profile_pa`` / ``wofdm_tx_psd_batch_pa``: model (``PA_LINEAR``: y = x; ``PA_RAPP``:
+AM/AM of a solid-state amplifier with smoothness ``smooth`` = p in [0.5, 16]; ``PA_CLIP``: the soft limiter, its p -> infinity
+limit), ibo_db (input back-off in [-40, 60]: a_sat^2 = reference power * 10^(ibo_db / 10)); ibo_db and smooth are used as
+stored in single precision."""
+
+RxProfilePa = collections.namedtuple("RxProfilePa",
+                                     "bit_err sym_err err_power bit_err_sym sym_err_sym err_power_sym pa_power decisions")
+RxProfilePa.__doc__ = """``RxProfileSync``'s fields with the amplifier's points on the leading axis, and pa_power (float64)
+[points, pairs, n_snr, n_ch, 2] = {sum |x|^2, sum |y|^2} over the T on-air samples of the cell's frames, before and behind the
+amplifier."""
+
+
+def _pa_point(point):
+    q = PaPoint(*point)
+    q = PaPoint(int(q.model), float(np.float32(q.ibo_db)), float(np.float32(q.smooth)))
+    if q.model not in (PA_LINEAR, PA_RAPP, PA_CLIP) or not -40.0 <= q.ibo_db <= 60.0 or \
+            (q.model == PA_RAPP and not 0.5 <= q.smooth <= 16.0):
+        raise ValueError("a point needs a known model, ibo_db in [-40, 60] and, for the Rapp model, smooth in [0.5, 16]: %r" % (q,))
+    return q
+
+
+def pa_gain(model, rho, smooth=2.0):
+    """The amplifier's gain g(rho) in double precision, rho = |x| / a_sat (any shape, >= 0): 1 for ``PA_LINEAR``; (1 +
+    rho^(2p))^(-1/(2p)) for ``PA_RAPP`` with p = smooth, evaluated above rho = 1 as (1 / rho) (1 + rho^(-2p))^(-1/(2p)) so that no
+    finite rho overflows; 1 up to rho = 1 and 1 / rho above for ``PA_CLIP``.  g = 1 at rho = 0."""
+    rho = np.asarray(rho, dtype=np.float64)
+    if model == PA_LINEAR:
+        return np.ones_like(rho)
+    lo, hi = np.minimum(rho, 1.0), np.maximum(rho, 1.0)               # each form on its own side only
+    if model == PA_CLIP:
+        return np.where(rho > 1.0, 1.0 / hi, 1.0)
+    if model != PA_RAPP:
+        raise ValueError("unknown amplifier model %r" % (model,))
+    p2 = 2.0 * float(smooth)
+    return np.where(rho > 1.0, (1.0 / hi) * (1.0 + hi ** -p2) ** (-1.0 / p2), (1.0 + lo ** p2) ** (-1.0 / p2))
+
+
+def pa_saturation(point, ref_power):
+    """a_sat of a point: sqrt(ref_power 10^(ibo_db / 10)) in double precision, stored in single (as the library stores it)"""
+    q = _pa_point(point)
+    return float(np.float32(np.sqrt(float(ref_power) * 10.0 ** (0.1 * q.ibo_db))))
+
+
+def pa_apply(x, point, ref_power):
+    """y = g(|x| / a_sat) x in double precision: the waveform x behind the amplifier ``point`` (``PaPoint`` or (model, ibo_db,
+    smooth)) whose back-off counts from ``ref_power``; the phase is untouched.  A ``PA_LINEAR`` point returns x itself."""
+    q = _pa_point(point)
+    x = np.asarray(x, dtype=np.complex128)
+    if q.model == PA_LINEAR:
+        return x
+    return pa_gain(q.model, np.abs(x) / pa_saturation(q, ref_power), q.smooth) * x
+
+
+def frame_profile_pa(st, grids, unit_noise, w_tx, w_rx, h, point, ref_power, snr_db, bits_per_sc, active=None, mask=None,
+                     noise_before_truncate=1, with_y=False):
+    """fp64 host mirror of one frame and one point of ``wofdm_rx_profile_pa``: ``frame_profile`` with the finished on-air
+    waveform x (window, mask, overlap-add, the last ramp-down included) passed through ``pa_apply(x, point, ref_power)`` before
+    the channel -- Ps, the noise gain and every received sample are those of the amplified waveform; the receiver, its pilot
+    estimate from symbol 0 included, is unchanged.  Returns what ``frame_profile_sync`` returns and the two power sums:
+    (bit_err [N], sym_err [N], err_power [N], xhat [S-1, N], y0 [N], bit_err_sym [S-1], sym_err_sym [S-1], err_power_sym [S-1],
+    pa_power [2] = {sum |x|^2, sum |y|^2}) -- the first five are ``frame_profile``'s, exactly, on a ``PA_LINEAR`` point --;
+    with_y=True: Y [S, N] as a tenth."""
+    noise = np.asarray(unit_noise, dtype=np.complex128).reshape(-1)
+    hc = np.asarray(h, dtype=np.complex128).reshape(-1)
+    S = np.asarray(grids).shape[0]
+    nl = _noise_len(st, S, hc.size, noise_before_truncate)
+    if noise.size < nl:
+        raise ValueError("unit_noise holds %d samples, %d needed" % (noise.size, nl))
+    power = np.zeros(2)
+
+    def noise_at(idx):
+        return noise[np.asarray(idx, dtype=np.int64)]
+
+    def channel(x):
+        y = pa_apply(x, point, ref_power)
+        power[:] = (np.abs(x) ** 2).sum(), (np.abs(y) ** 2).sum()
+        return np.convolve(hc, y)
+    front = _sync_front(st, grids, noise_at, w_tx, None, snr_db, active, mask, noise_before_truncate, channel=channel)
+    out = _sync_point(st, front, noise_at, w_rx, SyncPoint(0, 0.0, 1), bits_per_sc)
+    return out[:8] + (power,) + ((out[8],) if with_y else ())
+
+
+def _prepare_pa(points, ref_power, pairs):
+    pts = [_pa_point(q) for q in points]
+    if not pts:
+        raise ValueError("at least one point is needed")
+    ref = np.ascontiguousarray(np.atleast_1d(ref_power), dtype=np.float32)
+    if ref.shape != (pairs,) or not (np.isfinite(ref) & (ref > 0)).all():
+        raise ValueError("ref_power must hold %d finite positive powers" % pairs)
+    return pts, ref
+
+
+def rx_profile_pa_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, ref_power,
+                       active=None, mask=None, noise_before_truncate=1, with_near=False):
+    """The host route of ``rx_profile_pa_gpu``: the frames of ``rx_profile_host`` from the same Philox streams, each through
+    ``frame_profile_pa`` for every point of ``points`` with the reference power ``ref_power`` [pairs] of the cell's window pair
+    (single precision, as the GPU receives it); the labels and the noise of a frame are shared by its points.  Returns
+    ``RxProfilePa``; with_near=True: also the number of ``near_decisions`` per point and cell [points, pairs, n_snr, n_ch]."""
+    from . import timefreq as T
+    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, hc.shape[0], st.n_fft
+    pts, ref = _prepare_pa(points, ref_power, pairs)
+    k, S = int(bits_per_sc), int(syms)
+    tab = T.qam_table(k)
+    nl = _noise_len(st, S, hc.shape[1], noise_before_truncate)
+    on = np.ones(n, dtype=bool) if act is None else act != 0
+    shape = (len(pts), pairs, n_snr, n_ch)
+    bit = np.zeros(shape + (n,), dtype=np.uint64)
+    sym = np.zeros_like(bit)
+    pw = np.zeros(bit.shape, dtype=np.float64)
+    sbit = np.zeros(shape + (S - 1,), dtype=np.uint64)
+    ssym = np.zeros_like(sbit)
+    spw = np.zeros(sbit.shape, dtype=np.float64)
+    ppw = np.zeros(shape + (2,), dtype=np.float64)
+    near = np.zeros(shape, dtype=np.int64)
+    for cell in range(pairs * n_snr * n_ch):
+        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
+        for f in range(int(frames)):
+            fr = int(frame_offset) + f
+            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
+            noise = gen_noise(nl, seed, cell, fr)
+            for i, q in enumerate(pts):
+                b, se, e, xhat, y0, sb, ss, sp, pp = frame_profile_pa(st, grid, noise, w_tx[p], w_rx[p], hc[c], q, ref[p],
+                                                                      snr[s], k, act, m, noise_before_truncate)
+                bit[i, p, s, c] += b
+                sym[i, p, s, c] += se
+                pw[i, p, s, c] += e
+                sbit[i, p, s, c] += sb
+                ssym[i, p, s, c] += ss
+                spw[i, p, s, c] += sp
+                ppw[i, p, s, c] += pp
+                if with_near:
+                    near[i, p, s, c] += int(near_decisions(k, xhat, y0).sum())
+    prof = RxProfilePa(bit, sym, pw, sbit, ssym, spw, ppw, _decisions(st, S, frames, act))
+    return (prof, near) if with_near else prof
+
+
+def rx_profile_pa_chunk_frames(st, syms, masked, n_points):
+    """Frames one chunk of ``wofdm_rx_profile_pa`` holds (include/wofdm.h): ``rx_profile_sync_chunk_frames``' bytes plus one
+    waveform per point; at most 65535."""
+    from . import _lib
+    P = st.sym_len
+    T = st.tail_tx + syms * (P - st.tail_tx)
+    per_frame = 8 * (syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0)) + 8 * int(n_points) * (st.n_fft + syms + T)
+    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+
+
+def rx_profile_pa_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, ref_power,
+                      active=None, mask=None, noise_before_truncate=1, device=0, out=None):
+    """``wofdm_rx_profile_pa``: ``rx_profile_gpu`` of the same arguments behind a memoryless power amplifier, for every point of
+    ``points`` (``PaPoint`` or (model, ibo_db, smooth) tuples, at most ``_lib.PA_MAX_POINTS``) in ONE call -- the Tx chain runs
+    once per frame, every point sees the same labels and noise --, per subcarrier and per data symbol.  ``ref_power`` [pairs]:
+    the mean on-air power of a window pair's waveform the back-off counts from (``pa_ref_power``).  Returns ``RxProfilePa``;
+    ``out`` (an earlier result of the same shape) is accumulated into.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    from .simulation import make_cfg
+    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0]
+    pts, ref = _prepare_pa(points, ref_power, pairs)
+    cpts = (_lib.PaPoint * len(pts))(*[_lib.PaPoint(q.model, q.ibo_db, q.smooth, 0) for q in pts])
+    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[1], n_ch, n_snr, pairs, bool(noise_before_truncate),
+                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
+    shape = (len(pts), pairs, n_snr, n_ch)
+    errs = np.zeros(shape + (st.n_fft, 2), dtype=np.uint64)
+    pw = np.zeros(shape + (st.n_fft,), dtype=np.float64)
+    serrs = np.zeros(shape + (int(syms) - 1, 2), dtype=np.uint64)
+    spw = np.zeros(shape + (int(syms) - 1,), dtype=np.float64)
+    ppw = np.zeros(shape + (2,), dtype=np.float64)
+    hf = _lib.c64_as_f32(hc)
+    _lib.check(_lib.load().wofdm_rx_profile_pa(
+        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
+        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, len(pts), cpts, ref.ctypes.data,
+        errs.ctypes.data, pw.ctypes.data, serrs.ctypes.data, spw.ctypes.data, ppw.ctypes.data))
+    prof = RxProfilePa(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
+                       np.ascontiguousarray(serrs[..., 0]), np.ascontiguousarray(serrs[..., 1]), spw, ppw,
+                       _decisions(st, syms, frames, act))
+    if out is not None:
+        if out.bit_err.shape != prof.bit_err.shape:
+            raise ValueError("out has another shape")
+        prof = RxProfilePa(*(a + b for a, b in zip(out, prof)))
+    return prof
+
+
+def pa_ref_power(st, bits_per_sc, syms, w_tx_pairs, seed, frame_offset, frames, active=None, mask=None, gpu=True, device=0):
+    """The reference power of ``rx_profile_pa_gpu``: the mean on-air power per window pair [pairs] (float64) over the symbol
+    periods of the frames [frame_offset, frame_offset + frames) that pair p transmits as cell p of ``tx_papr_gpu`` -- the sum of
+    the periods' energies over frames * S * B samples, so the back-off counts from the same mean the PAPR histogram's axis
+    counts from (the trailing tail_tx samples belong to no period).  gpu=True: from the {peak, energy} periods of
+    ``tx_papr_gpu`` (as many calls as its ``periods`` output needs); gpu=False: from the host mirror ``timefreq.frame_papr`` on
+    the same labels."""
+    from . import _lib
+    from . import timefreq as T
+    w = _lib.f32(np.atleast_2d(w_tx_pairs))
+    pairs, S, B = w.shape[0], int(syms), st.sym_len - st.tail_tx
+    total = np.zeros(pairs, dtype=np.float64)
+    if gpu:
+        step = max(1, _lib.TX_PAPR_MAX_PERIODS // (pairs * S))
+        for f0 in range(0, int(frames), step):
+            per = T.tx_papr_gpu(st, bits_per_sc, S, w, seed, int(frame_offset) + f0, min(step, int(frames) - f0), active=active,
+                                mask=mask, periods=True, device=device)[2]
+            total += per[..., 1].astype(np.float64).sum(axis=(1, 2))
+    else:
+        tab = T.qam_table(bits_per_sc)
+        on = np.ones(st.n_fft, dtype=bool) if active is None else np.asarray(active).reshape(-1) != 0
+        m = None if mask is None else _lib.f32(np.asarray(mask).reshape(-1), (2 * st.sym_len - 1,))
+        for p in range(pairs):
+            grids = np.stack([tab[gen_labels(st.n_fft, bits_per_sc, S, seed, p, int(frame_offset) + f)] * on[None, :]
+                              for f in range(int(frames))])
+            total[p] = T.frame_papr(st, grids, w[p], m)[..., 1].sum()
+    return total / (int(frames) * S * B)

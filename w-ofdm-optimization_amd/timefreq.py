@@ -72,10 +72,13 @@ def mask_rows(rows, mask):
     return out
 
 
-def tx_waveform(st, X, w_tx, overlap, mask=None, guard_band=GUARD_BAND):
+def tx_waveform(st, X, w_tx, overlap, mask=None, guard_band=GUARD_BAND, pa=None):
     """fp64 host mirror of the waveform the spectrum kernels transmit: ``overlap_and_add`` of the
     ``tx_symbols``, each passed through ``mask_rows`` first when ``mask`` [2P-1] is given.  X as
-    ``draw_symbols`` gives it, or [N, S] on every bin with guard_band=None."""
+    ``draw_symbols`` gives it, or [N, S] on every bin with guard_band=None.  pa: an amplifier
+    (``rx_profile.PaPoint`` or (model, ibo_db, smooth)) behind the finished waveform, as ``wofdm_tx_psd_batch_pa``
+    places it: its back-off counts from the mean of |x|^2 over the WHOLE waveform, the last ramp-down included
+    (``rx_profile.pa_apply``); a waveform without power passes unchanged."""
     if guard_band is None:
         t = np.fft.ifft(np.asarray(X, dtype=np.complex128), axis=0)
         rows = (np.asarray(w_tx)[:, None] * t[(np.arange(st.sym_len) - st.cp) % st.n_fft]).T
@@ -83,7 +86,13 @@ def tx_waveform(st, X, w_tx, overlap, mask=None, guard_band=GUARD_BAND):
         rows = tx_symbols(st, X, w_tx, guard_band)
     if mask is not None:
         rows = mask_rows(rows, mask)
-    return overlap_and_add(rows, overlap)
+    x = overlap_and_add(rows, overlap)
+    if pa is not None:
+        from . import rx_profile as R
+        ref = float(np.mean(np.abs(x) ** 2))
+        if ref > 0:
+            x = R.pa_apply(x, pa, ref)
+    return x
 
 
 def psd_estimate(x, fft_len):
@@ -130,7 +139,7 @@ def psd_estimate_gpu(st, X, w_tx, overlap, guard_band=GUARD_BAND, device=0, mask
     return out.astype(np.float64) / (length // (8 * n) + 1)
 
 
-def tx_psd_batch_gpu(n_fft, grids, jobs, device=0, divide=True):
+def tx_psd_batch_gpu(n_fft, grids, jobs, device=0, divide=True, power=False):
     """Averaged periodograms of many Tx waveforms in one ``wofdm_tx_psd_batch`` call, any N in
     {64, ..., 1024}.  grids: [n_blocks, no_symbols, N] complex symbols on every bin (as given);
     jobs: sequence of (block, cp, cs, overlap, w_tx) or (block, cp, cs, overlap, w_tx, mask), w_tx of
@@ -139,7 +148,13 @@ def tx_psd_batch_gpu(n_fft, grids, jobs, device=0, divide=True):
     share one table entry; masked jobs need 3P-2 <= 8N), the others through ``wofdm_tx_psd_batch``.
     Returns [n_jobs, 8 N] float64: ``psd_estimate(tx_waveform(...), 8 N)`` of each job's waveform, i.e.
     the kernel's slice sums divided by the reference's slice count (length // 8 N + 1); with
-    divide=False the undivided float32 sums.  No CPU fallback."""
+    divide=False the undivided float32 sums.  A job may carry a seventh field, pa: None or the amplifier
+    behind its finished waveform (``rx_profile.PaPoint`` or (model, ibo_db, smooth); its back-off counts from the
+    mean power of the job's whole waveform, measured on the device).  A call with any such field, or with
+    power=True, goes through ``wofdm_tx_psd_batch_pa`` (equal points share one table entry, at most
+    ``_lib.PA_MAX_POINTS`` of them); calls without go exactly where they went.  power=True: returns (periodograms,
+    job_power [n_jobs, 2] float32 = the mean power of every job's waveform before and behind its amplifier).
+    No CPU fallback."""
     import ctypes as C
     from . import _lib
     n = int(n_fft)
@@ -147,11 +162,14 @@ def tx_psd_batch_gpu(n_fft, grids, jobs, device=0, divide=True):
     if grids.ndim != 3 or grids.shape[2] != n:
         raise ValueError("grids must be [n_blocks, no_symbols, %d], got %s" % (n, grids.shape))
     n_blocks, no_symbols = grids.shape[:2]
-    jobs = [tuple(j) + (None,) * (6 - len(j)) for j in jobs]
+    jobs = [tuple(j) + (None,) * (7 - len(j)) for j in jobs]
+    use_pa = bool(power) or any(j[6] is not None for j in jobs)
+    pa_tab, pa_of = [], {}
+    job_pa = np.full(max(1, len(jobs)), -1, dtype=np.int32)
     cj = (_lib.PsdJob * max(1, len(jobs)))()
     wins, lengths, tables, table_of = [], [], [], {}
     job_mask = np.full(max(1, len(jobs)), -1, dtype=np.int32)
-    for j, (block, cp, cs, overlap, w, mask) in enumerate(jobs):
+    for j, (block, cp, cs, overlap, w, mask, pa) in enumerate(jobs):
         cj[j].block, cj[j].cp, cj[j].cs, cj[j].overlap = int(block), int(cp), int(cs), int(overlap)
         wins.append(_lib.f32(np.asarray(w).reshape(-1), (n + cp + cs,)))
         lengths.append(overlap + no_symbols * (n + cp + cs - overlap))
@@ -160,10 +178,25 @@ def tx_psd_batch_gpu(n_fft, grids, jobs, device=0, divide=True):
             job_mask[j] = table_of.setdefault(m.tobytes(), len(tables))
             if job_mask[j] == len(tables):
                 tables.append(m)
+        if pa is not None:
+            from . import rx_profile as R
+            q = R._pa_point(pa)
+            job_pa[j] = pa_of.setdefault(q, len(pa_tab))
+            if job_pa[j] == len(pa_tab):
+                pa_tab.append(q)
     w_all = _lib.f32(np.concatenate(wins) if wins else np.zeros(1))
     gf = _lib.c64_as_f32(grids)
     out = np.zeros((max(1, len(jobs)), 8 * n), dtype=np.float32)
-    if tables:
+    jpow = np.zeros((max(1, len(jobs)), 2), dtype=np.float32)
+    if use_pa:
+        mask_len = np.array([t.size for t in tables] or [0], dtype=np.int32)
+        gains = _lib.f32(np.concatenate(tables) if tables else np.zeros(1))
+        cpa = (_lib.PaPoint * max(1, len(pa_tab)))(*[_lib.PaPoint(q.model, q.ibo_db, q.smooth, 0) for q in pa_tab])
+        _lib.check(_lib.load().wofdm_tx_psd_batch_pa(
+            n, int(device), len(jobs), C.addressof(cj), w_all.ctypes.data, len(tables), mask_len.ctypes.data,
+            gains.ctypes.data, job_mask.ctypes.data, len(pa_tab), cpa, job_pa.ctypes.data, int(n_blocks), int(no_symbols),
+            gf.ctypes.data, out.ctypes.data, jpow.ctypes.data))
+    elif tables:
         mask_len = np.array([t.size for t in tables], dtype=np.int32)
         gains = _lib.f32(np.concatenate(tables))
         _lib.check(_lib.load().wofdm_tx_psd_batch_masked(
@@ -172,9 +205,9 @@ def tx_psd_batch_gpu(n_fft, grids, jobs, device=0, divide=True):
     else:
         _lib.check(_lib.load().wofdm_tx_psd_batch(n, int(device), len(jobs), C.addressof(cj), w_all.ctypes.data,
                                                   int(n_blocks), int(no_symbols), gf.ctypes.data, out.ctypes.data))
-    if not divide:
-        return out
-    return out.astype(np.float64) / (np.array(lengths, dtype=np.int64) // (8 * n) + 1)[:, None]
+    if divide:
+        out = out.astype(np.float64) / (np.array(lengths, dtype=np.int64) // (8 * n) + 1)[:, None]
+    return (out, jpow) if power else out
 
 
 def analytical_psd(st, w_tx, sampling_period, guard_band=GUARD_BAND, fft_len=None):
@@ -227,18 +260,22 @@ def _obr_dicts(st, w_tx, samp_period, ests):
     return tuple(out)
 
 
-def estimate_obr(st, w_tx, samp_period=200e-9, X=None, rng=None, gpu=False, mask=None):
+def estimate_obr(st, w_tx, samp_period=200e-9, X=None, rng=None, gpu=False, mask=None, pa=None):
     """``wOFDMSystem.estimate_obr`` (lines 216-296): three dicts (optimised window, RC window,
     plain CP-OFDM) with the reference's keys.  gpu=True: waveform and periodogram on the GPU,
     ``wofdm_tx_psd`` per window at N <= 256, one ``wofdm_tx_psd_batch`` call for the three at
     N = 512 / 1024.  mask: [2P-1] gains of a spectral Tx mask (``mask_rows``) applied to all three
-    waveforms; the host route is ``tx_waveform``, the GPU route one ``wofdm_tx_psd_batch_masked`` call."""
+    waveforms; the host route is ``tx_waveform``, the GPU route one ``wofdm_tx_psd_batch_masked`` call.  pa: an
+    amplifier (``rx_profile.PaPoint``) behind all three waveforms, each backed off from its own mean power: the
+    spectral regrowth; the host route is ``tx_waveform(..., pa=pa)``, the GPU route one ``wofdm_tx_psd_batch_pa`` call."""
     n = st.n_fft
     fft_len = 8 * n
     X = draw_symbols(n, rng) if X is None else np.asarray(X)
     wins = _obr_windows(st, w_tx)
     if not gpu:
-        ests = [psd_estimate(tx_waveform(st, X, w, ov, mask), fft_len) for w, ov in wins]
+        ests = [psd_estimate(tx_waveform(st, X, w, ov, mask, pa=pa), fft_len) for w, ov in wins]
+    elif pa is not None:
+        ests = list(tx_psd_batch_gpu(n, _full_grid(n, X)[None], [(0, st.cp, st.cs, ov, w, mask, pa) for w, ov in wins]))
     elif mask is not None:
         ests = list(tx_psd_batch_gpu(n, _full_grid(n, X)[None], [(0, st.cp, st.cs, ov, w, mask) for w, ov in wins]))
     elif n <= 256:
