@@ -1019,7 +1019,8 @@ __global__ void __launch_bounds__(WOFDM_PAPR_WAVES * 64) wofdm_papr_period_kerne
 }
 
 // ---------------------------------------------------------------------------------------------
-// Per-subcarrier BER and EVM of the frames the BER loop runs (wofdm_rx_profile): a second, unfused implementation of the
+// Per-subcarrier BER and EVM of the frames the BER loop runs (wofdm_rx_profile and its four arms _aci, _sync, _doppler, _pa:
+// one body, rxprof_body<N, ARM> below, whose comment says what each arm adds): a second, unfused implementation of the
 // whole frame pipeline behind the Tx chain above,
 //   conv, add_wgn, truncate        matlab/main_BER_calculation.m:260-261, 277-294
 //   wofdm_rx                       main_BER_calculation.m:297-355 (Rx window, fold, circular shift, DFT)
@@ -1074,32 +1075,98 @@ __device__ __forceinline__ uint32_t rxp_slice(int k, float re, float im)
     return ((uint32_t)(ii ^ (ii >> 1)) << hb) | (uint32_t)(qi ^ (qi >> 1));
 }
 
-// The body of both receive kernels.  ACI = false is wofdm_rx_profile's kernel as it was.  ACI = true (wofdm_rx_profile_aci)
-// adds an adjacent-band neighbour to pass 2: the wave stages a second row with the neighbour's samples under the same window
-// -- the victim's on-air sample t carries a_lvl xi[t + ioff], zero outside xi --, and rxs() adds their 21-tap sum with the
-// neighbour's channel hi[ch], scaled by a_lvl, to the received sample.  Pass 1 does not see the neighbour: Ps, Pn and the
-// noise gain are the victim's.
-template <int N, bool ACI>
-__device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_aparams &ap)
+// The knot interval of the on-air index a (wofdm_dparams): q = min(a / step, last), last = n_knots - 2, and the fraction
+// f = (a - q step) / step.  The quotient comes from the single-precision reciprocal rstep = 1 / step and two corrections, not
+// from a 32-bit division per sample: a < 2^22 is exact in single precision and the product carries under 3 2^-24 of a / step
+// < 2^22, so its integer part is off by one at most.  The knots cover the frame, so only a = (last + 1) step meets the
+// clamp, with f = 1.
+__device__ __forceinline__ void dop_interval(uint32_t a, uint32_t step, float rstep, uint32_t last, uint32_t &q, float &f)
+{
+    uint32_t qq = (uint32_t)((float)a * rstep);
+    int32_t r = (int32_t)(a - qq * step);
+    if (r < 0) {
+        --qq;
+        r += (int32_t)step;
+    }
+    if (r >= (int32_t)step) {
+        ++qq;
+        r -= (int32_t)step;
+    }
+    if (qq > last) {
+        r += (int32_t)((qq - last) * step);
+        qq = last;
+    }
+    q = qq;
+    f = (float)r * rstep;
+}
+
+// One tap of the 21-tap sum, cr += hv.x xv.x - hv.y xv.y and ci += hv.x xv.y + hv.y xv.x, for every arm and both passes.  The
+// operations are written down: they are the ones the compiler once formed for these statements in the plain kernel, the first
+// product of each line fused onto the rounded second, then the addition -- but in the copy of rxs() for the folded sample
+// m0 + N (FOLD) the imaginary part has the second product fused onto the rounded first.  Left to itself the compiler chooses
+// its fusions anew in every inlined copy (other ones still where the taps are per lane), and the arms' identities with the
+// plain call -- an offset-free point, a static track, a linear amplifier -- would hang on its mood.  The real part is formed
+// as cr - fma(-hv.x, xv.x, hv.y xv.y): the same value, rounding being symmetric, and the instructions the plain kernel had
+// (a plain multiply and an fma with a negated source; with the negation on the product the plain call ran 0.3 % longer).
+template <bool FOLD>
+__device__ __forceinline__ void fir_tap(const float2 hv, const float2 xv, float &cr, float &ci)
+{
+#pragma clang fp contract(off)
+    const float nre = __builtin_fmaf(-hv.x, xv.x, hv.y * xv.y);
+    const float im = FOLD ? __builtin_fmaf(hv.y, xv.x, hv.x * xv.y) : __builtin_fmaf(hv.x, xv.y, hv.y * xv.x);
+    cr = cr - nre;
+    ci = ci + im;
+}
+
+// The one body of the five receive kernels; ARM selects at compile time what an arm adds to the pipeline above, and the
+// parameters of the other arms are not read.
+//   RXP_PLAIN    wofdm_rx_profile: nothing.
+//   RXP_ACI      wofdm_rx_profile_aci: the wave stages a second row with the neighbour's samples under the same window -- the
+//                victim's on-air sample t carries a_lvl xi[t + ioff], zero outside xi --, and rxs() adds their 21-tap sum with
+//                the neighbour's channel hi[ch], scaled by a_lvl.  Pass 1 does not see the neighbour.  LDS: LDS_ACI.
+//   RXP_SYNC     wofdm_rx_profile_sync: pass 2 once per point of sp.  The windows begin at s B + gam + theta (reads outside
+//                [0, T) of x are zero, the noise of sample a is that of counter word (uint32) a: a negative a lands on words
+//                no frame uses), and the received sample m under the window, signal and noise, is multiplied by
+//                base[point][s] e^{2 pi i eps m / N} -- the host's base phasor carries the phase at the window's start (1 when
+//                the common phase is tracked), the kernel forms the in-window factor from the fraction of eps m / N.  At
+//                theta = 0, eps = 0 both factors are exactly 1: the point gives the plain kernel's bits.
+//   RXP_DOPPLER  wofdm_rx_profile_doppler: both passes once per track of dp (sp.n_points tracks).  The workgroup stages the
+//                knots of (track, the item's channel) behind the waves' rows, [n_knots][WOFDM_LT] float2, and every sample of
+//                either pass forms its 21 taps from the two knots around its own on-air index, hv = K[q] + f (K[q + 1] - K[q])
+//                -- the tap at the OUTPUT sample's time; with equal knots hv is the knot, bit for bit, so a static track gives
+//                the plain kernel's bits.  Lanes of a wave sit on neighbouring samples, so their knot reads are broadcasts but
+//                for the lanes astride a knot.  LDS: LDS_DOP.
+//   RXP_PA       wofdm_rx_profile_pa: both passes once per point of pa (sp.n_points points) on the point's waveform,
+//                y[job][point] of wofdm_pa_wave_kernel, or x itself for a linear point, which so gives the plain kernel's bits.
+// The arms with a point loop (points, tracks) write the partials part_pow, part_cnt [job][point][N], and the wave of symbol
+// s >= 1 leaves beside them the symbol's sums over the loaded bins -- a lane's bins ascending, then papr_wave_reduce -- in
+// sym_pow, sym_cnt [job][point][S].  The pilot of a point sees what the point's data sees.  Where pass 1 runs per point, Ps
+// is the point's; Pn depends on neither channel nor waveform and is measured with the first.
+enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA };
+template <int N, int ARM>
+__device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_aparams &ap, const wofdm_sparams &sp,
+                                            const wofdm_dparams &dp, const wofdm_paparams &pa)
 {
     using RG = rxp_geo<N>;
+    constexpr bool ACI = ARM == RXP_ACI, SYNC = ARM == RXP_SYNC, DOP = ARM == RXP_DOPPLER, PA = ARM == RXP_PA;
+    constexpr bool POINTS = SYNC || DOP || PA, PASS1_PER_POINT = DOP || PA;
     constexpr int ROWLEN = N + (ACI ? 2 : 1) * RG::XROW;
     constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2 *tw = reinterpret_cast<float2 *>(smem);                    // e^{-2 pi i k / N}, k < N / 2
-    float2 *G = tw + N / 2;                                           // pilot equaliser X0 / Y0
+    float2 *G = tw + N / 2;                                           // pilot equaliser X0 / Y0 (of the point)
     float *wrx = reinterpret_cast<float *>(G + N);
     float *red = wrx + N + 64;                                        // [2][W] power partials
     float2 *rows = reinterpret_cast<float2 *>(red + 64);
+    [[maybe_unused]] float2 *kn = rows + (size_t)W * ROWLEN;          // (DOP) [n_knots][LT] knots of the track, the item's channel
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int S = p.S, B = p.B, T = p.T, NL = p.NL, delta = p.delta;
+    const int S = p.S, B = p.B, T = p.T, NL = p.NL, delta = p.delta, NP = POINTS ? sp.n_points : 1;
     const uint32_t job = blockIdx.x;
     const uint64_t item = p.item0 + job, cell64 = item / p.frames, frame = p.frame_offset + (item - cell64 * p.frames);
     const uint32_t cell = (uint32_t)cell64, f_lo = (uint32_t)frame, f_hi = (uint32_t)(frame >> 32);
     const int ch = (int)(cell % (uint32_t)p.n_ch), sn = (int)((cell / (uint32_t)p.n_ch) % (uint32_t)p.n_snr);
     const int pair = (int)(cell / ((uint32_t)p.n_ch * (uint32_t)p.n_snr));
-    const float2 *__restrict__ x = p.x + (size_t)job * T;
     const float2 *__restrict__ Xg = p.X + (size_t)job * S * N;
     const float2 *__restrict__ taps = p.h + (size_t)ch * LT;
     const float2 *__restrict__ xi = ACI ? ap.xi + (size_t)job * ap.Ti : nullptr;
@@ -1110,279 +1177,80 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
         tw[i] = make_float2(cv, sv);
     }
     for (int i = tid; i < N + delta; i += NT) wrx[i] = p.wrx[(size_t)pair * (N + delta) + i];
-    // pass 1: signal and noise power over the same NL samples (add_wgn, m:277-294); a thread takes whole Philox blocks
-    float ps = 0.f, pn = 0.f;
-    for (int q = tid; 2 * q < NL; q += NT) {
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int jj = 2 * q + e;
-            if (jj >= NL) break;
-            float cr = 0.f, ci = 0.f;
-            for (int l = 0; l < LT; ++l) {
-                const int t = jj - l;
-                if (t < 0 || t >= T) continue;
-                const float2 xv = x[t], hv = taps[l];
-                cr += hv.x * xv.x - hv.y * xv.y;
-                ci += hv.x * xv.y + hv.y * xv.x;
-            }
-            const v2f nz = rxp_noise((uint32_t)q, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, e);
-            ps += cr * cr + ci * ci;
-            pn += nz.x * nz.x + nz.y * nz.y;
+    // the 21 taps at the on-air index a: the channel's own, wave-uniform, or (DOP) a lane's, between the knots around a
+    const uint32_t kstep = (uint32_t)dp.knot_step, klast = (uint32_t)(dp.n_knots - 2);
+    const float rstep = 1.0f / (float)kstep;
+    auto taps_at = [&]([[maybe_unused]] uint32_t a) {
+        if constexpr (DOP) {
+            uint32_t kq;
+            float kf;
+            dop_interval(a, kstep, rstep, klast, kq, kf);
+            const float2 *k0 = kn + kq * LT;
+            return [=](int l) {
+                const float2 ka = k0[l], kb = k0[LT + l];
+                return make_float2(ka.x + kf * (kb.x - ka.x), ka.y + kf * (kb.y - ka.y));
+            };
+        } else {
+            return [=](int l) { return taps[l]; };
         }
-    }
-    ps = papr_wave_reduce<false>(ps);
-    pn = papr_wave_reduce<false>(pn);
-    if (lane == 0) {
-        red[wv] = ps;
-        red[W + wv] = pn;
-    }
-    __syncthreads();
-    float Ps = 0.f, Pn = 0.f;
-    for (int w = 0; w < W; ++w) {
-        Ps += red[w];
-        Pn += red[W + w];
-    }
-    const float g = sqrtf(Ps * p.nlin[sn] / Pn);
-    // pass 2
+    };
+    // pass 1: signal and noise power over the same NL samples (add_wgn, m:277-294), the noise power only where `first`; a
+    // thread takes whole Philox blocks.  Gives the noise gain g.
+    auto pass1 = [&](const float2 *__restrict__ x, bool first) {
+        float ps = 0.f, pn = 0.f;
+        for (int q = tid; 2 * q < NL; q += NT) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int jj = 2 * q + e;
+                if (jj >= NL) break;
+                const auto tap = taps_at((uint32_t)jj);
+                float cr = 0.f, ci = 0.f;
+                for (int l = 0; l < LT; ++l) {
+                    const int t = jj - l;
+                    if (t < 0 || t >= T) continue;
+                    fir_tap<false>(tap(l), x[t], cr, ci);
+                }
+                ps += __builtin_fmaf(ci, ci, cr * cr);                // (written down: which square is fused moved with the code around it)
+                if (first) {
+                    const v2f nz = rxp_noise((uint32_t)q, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, e);
+                    pn += nz.x * nz.x + nz.y * nz.y;
+                }
+            }
+        }
+        ps = papr_wave_reduce<false>(ps);
+        if (lane == 0) red[wv] = ps;
+        if (first) {
+            pn = papr_wave_reduce<false>(pn);
+            if (lane == 0) red[W + wv] = pn;
+        }
+        __syncthreads();
+        float Ps = 0.f, Pn = 0.f;
+        for (int w = 0; w < W; ++w) {
+            Ps += red[w];
+            Pn += red[W + w];
+        }
+        return sqrtf(Ps * p.nlin[sn] / Pn);
+    };
+    float g = 0.f;
+    if constexpr (!PASS1_PER_POINT) g = pass1(p.x + (size_t)job * T, true);   // (the gain never sees a point's offsets)
     float2 *buf = rows + (size_t)wv * ROWLEN;
     float2 *xr = buf + N;
     [[maybe_unused]] float2 *xir = xr + RG::XROW;                     // (ACI)
-    float pw[BINS];
-    uint32_t cnt[BINS];
-#pragma unroll
-    for (int j = 0; j < BINS; ++j) {
-        pw[j] = 0.f;
-        cnt[j] = 0u;
-    }
-    const int h2 = delta >> 1;
-    for (int s0 = 0; s0 < S; s0 += W) {
-        const int s = s0 + wv;
-        const bool live = s < S;                                      // (wave-uniform)
-        if (live) {
-            const int a0 = s * B + p.gam;                             // first sample under the Rx window (m:442-454)
-            for (int i = lane; i < N + delta + LT - 1; i += 64) {
-                const int t = a0 - (LT - 1) + i;
-                xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
-                if constexpr (ACI) {
-                    const int ti = t + ap.ioff;
-                    xir[i] = (ti >= 0 && ti < ap.Ti) ? xi[ti] : make_float2(0.f, 0.f);
-                }
-            }
-            wave_sync();
-            // r[a] = conv[a] + g n[a] (m:260-261, 290-293) of the sample m under the window
-            auto rxs = [&](int m) {
-                float cr = 0.f, ci = 0.f;
-#pragma unroll
-                for (int l = 0; l < LT; ++l) {
-                    const float2 xv = xr[m + (LT - 1) - l], hv = taps[l];
-                    cr += hv.x * xv.x - hv.y * xv.y;
-                    ci += hv.x * xv.y + hv.y * xv.x;
-                }
-                if constexpr (ACI) {
-                    float ar = 0.f, ai = 0.f;
-#pragma unroll
-                    for (int l = 0; l < LT; ++l) {
-                        const float2 xv = xir[m + (LT - 1) - l], hv = itaps[l];
-                        ar += hv.x * xv.x - hv.y * xv.y;
-                        ai += hv.x * xv.y + hv.y * xv.x;
-                    }
-                    cr += ap.a_lvl * ar;
-                    ci += ap.a_lvl * ai;
-                }
-                const uint32_t a = (uint32_t)(a0 + m);
-                const v2f nz = rxp_noise(a >> 1, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, (int)(a & 1u));
-                return make_float2(cr + g * nz.x, ci + g * nz.y);
-            };
-#pragma unroll 1
-            for (int j = 0; j < BINS; ++j) {
-                // Rx window, fold, circular shift (m:297-355): z[t] = sum_{m = t + kappa + delta/2 (mod N)} w[m] r[gamma + m]
-                const int t = lane + 64 * j, m0 = (t + p.kap + h2) & (N - 1);
-                float2 z = rxs(m0);
-                z.x *= wrx[m0];
-                z.y *= wrx[m0];
-                if (m0 < delta) {
-                    const float2 z2 = rxs(m0 + N);
-                    z.x += wrx[m0 + N] * z2.x;
-                    z.y += wrx[m0 + N] * z2.y;
-                }
-                buf[__brev((uint32_t)t) >> (32 - LOG2)] = z;
-            }
-            wave_sync();
-            // DFT (dftmtx(N), m:306): radix-2 stages in place
-            for (int len = 2, sh = LOG2 - 1; len <= N; len <<= 1, --sh) {
-                const int half = len >> 1;
-                for (int b = lane; b < N / 2; b += 64) {
-                    const int kk = b & (half - 1), i = ((b - kk) << 1) | kk;
-                    const float2 w = tw[kk << sh], a = buf[i], c = buf[i + half];
-                    const float tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
-                    buf[i] = make_float2(a.x + tr, a.y + ti);
-                    buf[i + half] = make_float2(a.x - tr, a.y - ti);
-                }
-                wave_sync();
-            }
-        }
-        if (s0 == 0) {
-            // pilot LS estimate (m:266-267): G = X0 / Y0 on the loaded bins
-            if (wv == 0)
-                for (int n = lane; n < N; n += 64) {
-                    const float2 y = buf[n], x0 = Xg[n];
-                    const float d = y.x * y.x + y.y * y.y;
-                    const bool on = p.amask == nullptr || p.amask[n] != 0;
-                    G[n] = on ? make_float2((x0.x * y.x + x0.y * y.y) / d, (x0.y * y.x - x0.x * y.y) / d) : make_float2(0.f, 0.f);
-                }
-            __syncthreads();
-        }
-        if (live && s >= 1) {
-#pragma unroll
-            for (int j = 0; j < BINS; ++j) {
-                const int n = lane + 64 * j;
-                if (p.amask != nullptr && p.amask[n] == 0) continue;
-                const float2 y = buf[n], gq = G[n], xs = Xg[(size_t)s * N + n];
-                const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;       // equaliser (m:268)
-                const uint32_t d = rxp_slice(p.k, xs.x, xs.y) ^ rxp_slice(p.k, er, ei);        // (X is the point of its own label)
-                cnt[j] += (uint32_t)__popc(d) + (d != 0u ? 0x10000u : 0u);
-                pw[j] += (er - xs.x) * (er - xs.x) + (ei - xs.y) * (ei - xs.y);
-            }
-        }
-        wave_sync();
-    }
-    // the waves' sums in wave order (their rows are free now): float [W][N], then uint32 [W][N]
-    __syncthreads();
-    float *redp = reinterpret_cast<float *>(rows);
-    uint32_t *redc = reinterpret_cast<uint32_t *>(redp + W * N);
-#pragma unroll
-    for (int j = 0; j < BINS; ++j) {
-        redp[wv * N + lane + 64 * j] = pw[j];
-        redc[wv * N + lane + 64 * j] = cnt[j];
-    }
-    __syncthreads();
-    for (int n = tid; n < N; n += NT) {
-        float t = 0.f;
-        uint32_t c = 0u;
-        for (int w = 0; w < W; ++w) {
-            t += redp[w * N + n];
-            c += redc[w * N + n];
-        }
-        p.part_pow[(size_t)job * N + n] = t;
-        p.part_cnt[(size_t)job * N + n] = c;
-    }
-}
-
-template <int N>
-__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(const wofdm_rparams p)
-{
-    rxprof_body<N, false>(p, wofdm_aparams{});
-}
-template <int N>
-__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_aci_kernel(const wofdm_rparams p, const wofdm_aparams ap)
-{
-    rxprof_body<N, true>(p, ap);
-}
-
-// totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
-template <int N>
-__global__ void __launch_bounds__(64) wofdm_rxprof_reduce_kernel(const wofdm_rparams p, uint64_t cell0)
-{
-    const int n = blockIdx.x * 64 + threadIdx.x;
-    const uint64_t cell = cell0 + blockIdx.y, end = p.item0 + (uint64_t)p.n_jobs;
-    const uint64_t lo = cell * p.frames > p.item0 ? cell * p.frames : p.item0;
-    const uint64_t hi = (cell + 1) * p.frames < end ? (cell + 1) * p.frames : end;
-    double acc = 0.0;
-    unsigned long long be = 0ull, se = 0ull;
-    for (uint64_t i = lo; i < hi; ++i) {
-        const size_t idx = (size_t)(i - p.item0) * N + n;
-        const uint32_t c = p.part_cnt[idx];
-        acc += (double)p.part_pow[idx];
-        be += c & 0xFFFFu;
-        se += c >> 16;
-    }
-    if (lo < hi) {
-        p.errs[2 * (cell * N + n)] += be;
-        p.errs[2 * (cell * N + n) + 1] += se;
-        p.pow[cell * N + n] += acc;
-    }
-}
-
-// The receive profile under receiver timing and carrier-frequency offsets (wofdm_rx_profile_sync): the item, the LDS image,
-// pass 1 and every expression of pass 2 are rxprof_body<N, false>'s -- a body of its own, so that the two kernels above compile
-// as they did --, with pass 2 run once per point of sp: the windows begin at s B + gam + theta (reads outside [0, T) of x are
-// zero, the noise of sample a is that of counter word (uint32) a: a negative a lands on words no frame uses), and the
-// received sample m under the window, signal and noise, is multiplied by base[point][s] e^{2 pi i eps m / N} before the Rx
-// window -- the host's base phasor carries the phase at the window's start (1 when the common phase is tracked), the kernel
-// forms the in-window factor from the fraction of eps m / N.  At theta = 0, eps = 0 both factors are exactly 1 and the
-// point gives the bits of wofdm_rxprof_kernel.  Beside the per-bin partials part_pow, part_cnt [job][point][N] the wave of
-// symbol s >= 1 leaves the symbol's sums over the loaded bins -- a lane's bins ascending, then papr_wave_reduce -- in sym_pow,
-// sym_cnt [job][point][S].  The pilot of a point sees the point's offsets.  LDS: rxp_geo<N>::LDS, whatever theta and n_points.
-template <int N>
-__device__ __forceinline__ void rxprof_sync_body(const wofdm_rparams &p, const wofdm_sparams &sp)
-{
-    using RG = rxp_geo<N>;
-    constexpr int ROWLEN = N + RG::XROW;
-    constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float2 *tw = reinterpret_cast<float2 *>(smem);                    // e^{-2 pi i k / N}, k < N / 2
-    float2 *G = tw + N / 2;                                           // pilot equaliser X0 / Y0 of the point
-    float *wrx = reinterpret_cast<float *>(G + N);
-    float *red = wrx + N + 64;                                        // [2][W] power partials
-    float2 *rows = reinterpret_cast<float2 *>(red + 64);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int S = p.S, B = p.B, T = p.T, NL = p.NL, delta = p.delta, NP = sp.n_points;
-    const uint32_t job = blockIdx.x;
-    const uint64_t item = p.item0 + job, cell64 = item / p.frames, frame = p.frame_offset + (item - cell64 * p.frames);
-    const uint32_t cell = (uint32_t)cell64, f_lo = (uint32_t)frame, f_hi = (uint32_t)(frame >> 32);
-    const int ch = (int)(cell % (uint32_t)p.n_ch), sn = (int)((cell / (uint32_t)p.n_ch) % (uint32_t)p.n_snr);
-    const int pair = (int)(cell / ((uint32_t)p.n_ch * (uint32_t)p.n_snr));
-    const float2 *__restrict__ x = p.x + (size_t)job * T;
-    const float2 *__restrict__ Xg = p.X + (size_t)job * S * N;
-    const float2 *__restrict__ taps = p.h + (size_t)ch * LT;
-    for (int i = tid; i < N / 2; i += NT) {
-        float sv, cv;
-        sincospif(-2.0f * (float)i / (float)N, &sv, &cv);
-        tw[i] = make_float2(cv, sv);
-    }
-    for (int i = tid; i < N + delta; i += NT) wrx[i] = p.wrx[(size_t)pair * (N + delta) + i];
-    // pass 1, once per item: signal and noise power over the same NL samples; the gain never sees the offsets
-    float ps = 0.f, pn = 0.f;
-    for (int q = tid; 2 * q < NL; q += NT) {
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int jj = 2 * q + e;
-            if (jj >= NL) break;
-            float cr = 0.f, ci = 0.f;
-            for (int l = 0; l < LT; ++l) {
-                const int t = jj - l;
-                if (t < 0 || t >= T) continue;
-                const float2 xv = x[t], hv = taps[l];
-                cr += hv.x * xv.x - hv.y * xv.y;
-                ci += hv.x * xv.y + hv.y * xv.x;
-            }
-            const v2f nz = rxp_noise((uint32_t)q, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, e);
-            ps += cr * cr + ci * ci;
-            pn += nz.x * nz.x + nz.y * nz.y;
-        }
-    }
-    ps = papr_wave_reduce<false>(ps);
-    pn = papr_wave_reduce<false>(pn);
-    if (lane == 0) {
-        red[wv] = ps;
-        red[W + wv] = pn;
-    }
-    __syncthreads();
-    float Ps = 0.f, Pn = 0.f;
-    for (int w = 0; w < W; ++w) {
-        Ps += red[w];
-        Pn += red[W + w];
-    }
-    const float g = sqrtf(Ps * p.nlin[sn] / Pn);
-    // pass 2, once per point
-    float2 *buf = rows + (size_t)wv * ROWLEN;
-    float2 *xr = buf + N;
     const int h2 = delta >> 1;
 #pragma unroll 1
     for (int pt = 0; pt < NP; ++pt) {
-        const int theta = sp.pts[pt].theta;
-        const float turn = sp.pts[pt].eps * (1.0f / (float)N);        // (exact: N is a power of two)
+        // the point's on-air waveform
+        const float2 *__restrict__ x = (!PA || pa.pts[pt].model == WOFDM_PA_M_LINEAR) ? p.x + (size_t)job * T
+                                                                                      : pa.y + ((size_t)job * NP + pt) * (size_t)T;
+        if constexpr (DOP) {
+            const float2 *__restrict__ knots = dp.knots + ((size_t)pt * p.n_ch + ch) * (size_t)dp.n_knots * LT;
+            for (int i = tid; i < dp.n_knots * LT; i += NT) kn[i] = knots[i];
+            __syncthreads();
+        }
+        if constexpr (PASS1_PER_POINT) g = pass1(x, pt == 0);
+        // pass 2
+        const int theta = SYNC ? sp.pts[pt].theta : 0;
+        [[maybe_unused]] const float turn = SYNC ? sp.pts[pt].eps * (1.0f / (float)N) : 0.f;   // (exact: N is a power of two)
         const size_t slot = (size_t)job * NP + pt;
         float pw[BINS];
         uint32_t cnt[BINS];
@@ -1395,45 +1263,63 @@ __device__ __forceinline__ void rxprof_sync_body(const wofdm_rparams &p, const w
             const int s = s0 + wv;
             const bool live = s < S;                                  // (wave-uniform)
             if (live) {
-                const int a0 = s * B + p.gam + theta;                 // first sample under the moved Rx window
-                const float2 bs = sp.base[(size_t)pt * S + s];
+                const int a0 = s * B + p.gam + theta;                 // first sample under the Rx window (m:442-454)
+                [[maybe_unused]] const float2 bs = SYNC ? sp.base[(size_t)pt * S + s] : make_float2(1.f, 0.f);
                 for (int i = lane; i < N + delta + LT - 1; i += 64) {
                     const int t = a0 - (LT - 1) + i;
                     xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
+                    if constexpr (ACI) {
+                        const int ti = t + ap.ioff;
+                        xir[i] = (ti >= 0 && ti < ap.Ti) ? xi[ti] : make_float2(0.f, 0.f);
+                    }
                 }
                 wave_sync();
-                // r[a] = conv[a] + g n[a] of the sample m under the window, a = a0 + m, rotated by the oscillator's phase there
-                auto rxs = [&](int m) {
+                // r[a] = conv[a] + g n[a] (m:260-261, 290-293) of the sample m under the window, a = a0 + m
+                auto rxs = [&](int m, auto fold) {
+                    const uint32_t a = (uint32_t)(a0 + m);
+                    const auto tap = taps_at(a);
                     float cr = 0.f, ci = 0.f;
 #pragma unroll
-                    for (int l = 0; l < LT; ++l) {
-                        const float2 xv = xr[m + (LT - 1) - l], hv = taps[l];
-                        cr += hv.x * xv.x - hv.y * xv.y;
-                        ci += hv.x * xv.y + hv.y * xv.x;
+                    for (int l = 0; l < LT; ++l) fir_tap<decltype(fold)::value>(tap(l), xr[m + (LT - 1) - l], cr, ci);
+                    if constexpr (ACI) {
+                        float ar = 0.f, ai = 0.f;
+#pragma unroll
+                        for (int l = 0; l < LT; ++l) {
+                            const float2 xv = xir[m + (LT - 1) - l], hv = itaps[l];
+                            ar += hv.x * xv.x - hv.y * xv.y;
+                            ai += hv.x * xv.y + hv.y * xv.x;
+                        }
+                        cr += ap.a_lvl * ar;
+                        ci += ap.a_lvl * ai;
                     }
-                    const uint32_t a = (uint32_t)(a0 + m);
                     const v2f nz = rxp_noise(a >> 1, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, (int)(a & 1u));
                     const float2 r = make_float2(cr + g * nz.x, ci + g * nz.y);
-                    float tn = turn * (float)m, sv, cv;
-                    tn -= rintf(tn);
-                    sincospif(2.0f * tn, &sv, &cv);
-                    const float qr = bs.x * cv - bs.y * sv, qi = bs.x * sv + bs.y * cv;
-                    return make_float2(r.x * qr - r.y * qi, r.x * qi + r.y * qr);
+                    if constexpr (SYNC) {                             // rotated by the oscillator's phase at m
+                        float tn = turn * (float)m, sv, cv;
+                        tn -= rintf(tn);
+                        sincospif(2.0f * tn, &sv, &cv);
+                        const float qr = bs.x * cv - bs.y * sv, qi = bs.x * sv + bs.y * cv;
+                        return make_float2(r.x * qr - r.y * qi, __builtin_fmaf(r.x, qi, r.y * qr));   // (r.x qi + r.y qr, written down likewise)
+                    } else {
+                        return r;
+                    }
                 };
 #pragma unroll 1
                 for (int j = 0; j < BINS; ++j) {
+                    // Rx window, fold, circular shift (m:297-355): z[t] = sum_{m = t + kappa + delta/2 (mod N)} w[m] r[gamma + m]
                     const int t = lane + 64 * j, m0 = (t + p.kap + h2) & (N - 1);
-                    float2 z = rxs(m0);
+                    float2 z = rxs(m0, std::false_type{});
                     z.x *= wrx[m0];
                     z.y *= wrx[m0];
                     if (m0 < delta) {
-                        const float2 z2 = rxs(m0 + N);
+                        const float2 z2 = rxs(m0 + N, std::true_type{});
                         z.x += wrx[m0 + N] * z2.x;
                         z.y += wrx[m0 + N] * z2.y;
                     }
                     buf[__brev((uint32_t)t) >> (32 - LOG2)] = z;
                 }
                 wave_sync();
+                // DFT (dftmtx(N), m:306): radix-2 stages in place
                 for (int len = 2, sh = LOG2 - 1; len <= N; len <<= 1, --sh) {
                     const int half = len >> 1;
                     for (int b = lane; b < N / 2; b += 64) {
@@ -1447,7 +1333,7 @@ __device__ __forceinline__ void rxprof_sync_body(const wofdm_rparams &p, const w
                 }
             }
             if (s0 == 0) {
-                // pilot LS estimate of the point: the pilot sees the offsets the data sees
+                // pilot LS estimate (m:266-267): G = X0 / Y0 on the loaded bins
                 if (wv == 0)
                     for (int n = lane; n < N; n += 64) {
                         const float2 y = buf[n], x0 = Xg[n];
@@ -1458,31 +1344,35 @@ __device__ __forceinline__ void rxprof_sync_body(const wofdm_rparams &p, const w
                 __syncthreads();
             }
             if (live) {
-                float spw = 0.f;
-                uint32_t scn = 0u;
+                [[maybe_unused]] float spw = 0.f;
+                [[maybe_unused]] uint32_t scn = 0u;
                 if (s >= 1) {
 #pragma unroll
                     for (int j = 0; j < BINS; ++j) {
                         const int n = lane + 64 * j;
                         if (p.amask != nullptr && p.amask[n] == 0) continue;
                         const float2 y = buf[n], gq = G[n], xs = Xg[(size_t)s * N + n];
-                        const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;
-                        const uint32_t d = rxp_slice(p.k, xs.x, xs.y) ^ rxp_slice(p.k, er, ei);
+                        const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;   // equaliser (m:268)
+                        const uint32_t d = rxp_slice(p.k, xs.x, xs.y) ^ rxp_slice(p.k, er, ei);    // (X is the point of its own label)
                         const uint32_t c = (uint32_t)__popc(d) + (d != 0u ? 0x10000u : 0u);
                         const float e2 = (er - xs.x) * (er - xs.x) + (ei - xs.y) * (ei - xs.y);
                         cnt[j] += c;
                         pw[j] += e2;
-                        scn += c;
-                        spw += e2;
+                        if constexpr (POINTS) {
+                            scn += c;
+                            spw += e2;
+                        }
                     }
                 }
-                // the symbol's sums over the bins: at most N k < 2^16 bit errors and N symbol errors, so the halves do not meet
-                spw = papr_wave_reduce<false>(spw);
+                if constexpr (POINTS) {
+                    // the symbol's sums over the bins: at most N k < 2^16 bit errors and N symbol errors, so the halves do not meet
+                    spw = papr_wave_reduce<false>(spw);
 #pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) scn += (uint32_t)__shfl_xor((int)scn, o, 64);
-                if (lane == 0) {
-                    sp.sym_pow[slot * S + s] = spw;
-                    sp.sym_cnt[slot * S + s] = scn;
+                    for (int o = 32; o >= 1; o >>= 1) scn += (uint32_t)__shfl_xor((int)scn, o, 64);
+                    if (lane == 0) {
+                        sp.sym_pow[slot * S + s] = spw;
+                        sp.sym_cnt[slot * S + s] = scn;
+                    }
                 }
             }
             wave_sync();
@@ -1507,14 +1397,60 @@ __device__ __forceinline__ void rxprof_sync_body(const wofdm_rparams &p, const w
             p.part_pow[slot * N + n] = t;
             p.part_cnt[slot * N + n] = c;
         }
-        __syncthreads();                                              // the rows and G belong to the next point
+        if constexpr (POINTS) __syncthreads();                        // the rows, G and the knots belong to the next point
     }
 }
 
 template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(const wofdm_rparams p)
+{
+    rxprof_body<N, RXP_PLAIN>(p, wofdm_aparams{}, wofdm_sparams{}, wofdm_dparams{}, wofdm_paparams{});
+}
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_aci_kernel(const wofdm_rparams p, const wofdm_aparams ap)
+{
+    rxprof_body<N, RXP_ACI>(p, ap, wofdm_sparams{}, wofdm_dparams{}, wofdm_paparams{});
+}
+template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_sync_kernel(const wofdm_rparams p, const wofdm_sparams sp)
 {
-    rxprof_sync_body<N>(p, sp);
+    rxprof_body<N, RXP_SYNC>(p, wofdm_aparams{}, sp, wofdm_dparams{}, wofdm_paparams{});
+}
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_doppler_kernel(const wofdm_rparams p, const wofdm_sparams sp,
+                                                                                     const wofdm_dparams dp)
+{
+    rxprof_body<N, RXP_DOPPLER>(p, wofdm_aparams{}, sp, dp, wofdm_paparams{});
+}
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_pa_kernel(const wofdm_rparams p, const wofdm_sparams sp,
+                                                                                const wofdm_paparams pa)
+{
+    rxprof_body<N, RXP_PA>(p, wofdm_aparams{}, sp, wofdm_dparams{}, pa);
+}
+
+// totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
+template <int N>
+__global__ void __launch_bounds__(64) wofdm_rxprof_reduce_kernel(const wofdm_rparams p, uint64_t cell0)
+{
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    const uint64_t cell = cell0 + blockIdx.y, end = p.item0 + (uint64_t)p.n_jobs;
+    const uint64_t lo = cell * p.frames > p.item0 ? cell * p.frames : p.item0;
+    const uint64_t hi = (cell + 1) * p.frames < end ? (cell + 1) * p.frames : end;
+    double acc = 0.0;
+    unsigned long long be = 0ull, se = 0ull;
+    for (uint64_t i = lo; i < hi; ++i) {
+        const size_t idx = (size_t)(i - p.item0) * N + n;
+        const uint32_t c = p.part_cnt[idx];
+        acc += (double)p.part_pow[idx];
+        be += c & 0xFFFFu;
+        se += c >> 16;
+    }
+    if (lo < hi) {
+        p.errs[2 * (cell * N + n)] += be;
+        p.errs[2 * (cell * N + n) + 1] += se;
+        p.pow[cell * N + n] += acc;
+    }
 }
 
 // wofdm_rxprof_reduce_kernel per point: totals[point][cell][n] += the chunk's items of the cell, in frame order, one addition
@@ -1548,269 +1484,6 @@ __global__ void __launch_bounds__(64) wofdm_rxprof_sync_reduce_kernel(const wofd
     terr[2 * out] += be;
     terr[2 * out + 1] += se;
     tot[out] = acc;
-}
-
-// The knot interval of the on-air index a (wofdm_dparams): q = min(a / step, last), last = n_knots - 2, and the fraction
-// f = (a - q step) / step.  The quotient comes from the single-precision reciprocal rstep = 1 / step and two corrections, not
-// from a 32-bit division per sample: a < 2^22 is exact in single precision and the product carries under 3 2^-24 of a / step
-// < 2^22, so its integer part is off by one at most.  The knots cover the frame, so only a = (last + 1) step meets the
-// clamp, with f = 1.
-__device__ __forceinline__ void dop_interval(uint32_t a, uint32_t step, float rstep, uint32_t last, uint32_t &q, float &f)
-{
-    uint32_t qq = (uint32_t)((float)a * rstep);
-    int32_t r = (int32_t)(a - qq * step);
-    if (r < 0) {
-        --qq;
-        r += (int32_t)step;
-    }
-    if (r >= (int32_t)step) {
-        ++qq;
-        r -= (int32_t)step;
-    }
-    if (qq > last) {
-        r += (int32_t)((qq - last) * step);
-        qq = last;
-    }
-    q = qq;
-    f = (float)r * rstep;
-}
-
-// One tap of the 21-tap sum, cr += hv.x xv.x - hv.y xv.y and ci += hv.x xv.y + hv.y xv.x, in the operations the compiler forms
-// for these statements in wofdm_rxprof_kernel, where the taps are wave-uniform: the first product of each line fused onto the
-// rounded second, then the addition -- but in the copy of rxs() for the folded sample m0 + N (FOLD) the imaginary part has
-// the second product fused onto the rounded first (read in the generated assembly).  With the taps per lane the compiler
-// chooses yet other fusions from one inlined copy to the next, and a static track would miss the plain call's bits by an
-// ulp here and there; so the choice is written down.
-template <bool FOLD>
-__device__ __forceinline__ void dop_tap(const float2 hv, const float2 xv, float &cr, float &ci)
-{
-#pragma clang fp contract(off)
-    const float re = __builtin_fmaf(hv.x, xv.x, -(hv.y * xv.y));
-    const float im = FOLD ? __builtin_fmaf(hv.y, xv.x, hv.x * xv.y) : __builtin_fmaf(hv.x, xv.y, hv.y * xv.x);
-    cr = cr + re;
-    ci = ci + im;
-}
-
-// The receive profile over channels that move within the frame (wofdm_rx_profile_doppler): the item, the LDS image, the DFT,
-// the pilot step, the per-bin and per-symbol partials and their order are rxprof_sync_body's -- a body of its own again, so
-// that the three kernels above compile as they did --, with BOTH passes run once per track of dp (sp.n_points tracks; theta
-// and eps do not exist here): the workgroup stages the knots of (track, the item's channel) in LDS, [n_knots][WOFDM_LT]
-// float2 behind the waves' rows, and every sample of pass 1 and of pass 2's rxs() forms its 21 taps from the two knots
-// around its own on-air index, hv = K[q] + f (K[q + 1] - K[q]) -- the tap at the OUTPUT sample's time; with equal knots hv
-// is the knot, bit for bit, and every expression after it is the plain kernel's, so a static track gives its bits.  Ps is
-// measured per track on the track's conv; Pn does not depend on the channel and is measured with the first track.  Lanes
-// of a wave sit on neighbouring samples, so their knot reads are broadcasts but for the lanes astride a knot.
-// LDS: rxp_geo<N>::LDS_DOP.
-template <int N>
-__device__ __forceinline__ void rxprof_doppler_body(const wofdm_rparams &p, const wofdm_sparams &sp, const wofdm_dparams &dp)
-{
-    using RG = rxp_geo<N>;
-    constexpr int ROWLEN = N + RG::XROW;
-    constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float2 *tw = reinterpret_cast<float2 *>(smem);                    // e^{-2 pi i k / N}, k < N / 2
-    float2 *G = tw + N / 2;                                           // pilot equaliser X0 / Y0 of the track
-    float *wrx = reinterpret_cast<float *>(G + N);
-    float *red = wrx + N + 64;                                        // [2][W] power partials
-    float2 *rows = reinterpret_cast<float2 *>(red + 64);
-    float2 *kn = rows + (size_t)W * ROWLEN;                           // [n_knots][LT] knots of the track, the item's channel
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int S = p.S, B = p.B, T = p.T, NL = p.NL, delta = p.delta, NTR = sp.n_points, NK = dp.n_knots;
-    const uint32_t step = (uint32_t)dp.knot_step, last = (uint32_t)(NK - 2);
-    const float rstep = 1.0f / (float)step;
-    const uint32_t job = blockIdx.x;
-    const uint64_t item = p.item0 + job, cell64 = item / p.frames, frame = p.frame_offset + (item - cell64 * p.frames);
-    const uint32_t cell = (uint32_t)cell64, f_lo = (uint32_t)frame, f_hi = (uint32_t)(frame >> 32);
-    const int ch = (int)(cell % (uint32_t)p.n_ch), sn = (int)((cell / (uint32_t)p.n_ch) % (uint32_t)p.n_snr);
-    const int pair = (int)(cell / ((uint32_t)p.n_ch * (uint32_t)p.n_snr));
-    const float2 *__restrict__ x = p.x + (size_t)job * T;
-    const float2 *__restrict__ Xg = p.X + (size_t)job * S * N;
-    for (int i = tid; i < N / 2; i += NT) {
-        float sv, cv;
-        sincospif(-2.0f * (float)i / (float)N, &sv, &cv);
-        tw[i] = make_float2(cv, sv);
-    }
-    for (int i = tid; i < N + delta; i += NT) wrx[i] = p.wrx[(size_t)pair * (N + delta) + i];
-    float2 *buf = rows + (size_t)wv * ROWLEN;
-    float2 *xr = buf + N;
-    const int h2 = delta >> 1;
-#pragma unroll 1
-    for (int tk = 0; tk < NTR; ++tk) {
-        const float2 *__restrict__ knots = dp.knots + ((size_t)tk * p.n_ch + ch) * (size_t)NK * LT;
-        for (int i = tid; i < NK * LT; i += NT) kn[i] = knots[i];
-        __syncthreads();
-        // pass 1, once per track: the signal power over the NL samples of the track's conv; the noise power with the first
-        float ps = 0.f, pn = 0.f;
-        for (int q = tid; 2 * q < NL; q += NT) {
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int jj = 2 * q + e;
-                if (jj >= NL) break;
-                uint32_t kq;
-                float kf;
-                dop_interval((uint32_t)jj, step, rstep, last, kq, kf);
-                const float2 *k0 = kn + kq * LT;
-                float cr = 0.f, ci = 0.f;
-                for (int l = 0; l < LT; ++l) {
-                    const int t = jj - l;
-                    if (t < 0 || t >= T) continue;
-                    const float2 ka = k0[l], kb = k0[LT + l];
-                    const float2 xv = x[t], hv = make_float2(ka.x + kf * (kb.x - ka.x), ka.y + kf * (kb.y - ka.y));
-                    dop_tap<false>(hv, xv, cr, ci);
-                }
-                ps += cr * cr + ci * ci;
-                if (tk == 0) {
-                    const v2f nz = rxp_noise((uint32_t)q, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, e);
-                    pn += nz.x * nz.x + nz.y * nz.y;
-                }
-            }
-        }
-        ps = papr_wave_reduce<false>(ps);
-        if (lane == 0) red[wv] = ps;
-        if (tk == 0) {
-            pn = papr_wave_reduce<false>(pn);
-            if (lane == 0) red[W + wv] = pn;
-        }
-        __syncthreads();
-        float Ps = 0.f, Pn = 0.f;
-        for (int w = 0; w < W; ++w) {
-            Ps += red[w];
-            Pn += red[W + w];
-        }
-        const float g = sqrtf(Ps * p.nlin[sn] / Pn);
-        // pass 2 of the track
-        const size_t slot = (size_t)job * NTR + tk;
-        float pw[BINS];
-        uint32_t cnt[BINS];
-#pragma unroll
-        for (int j = 0; j < BINS; ++j) {
-            pw[j] = 0.f;
-            cnt[j] = 0u;
-        }
-        for (int s0 = 0; s0 < S; s0 += W) {
-            const int s = s0 + wv;
-            const bool live = s < S;                                  // (wave-uniform)
-            if (live) {
-                const int a0 = s * B + p.gam;                         // first sample under the Rx window
-                for (int i = lane; i < N + delta + LT - 1; i += 64) {
-                    const int t = a0 - (LT - 1) + i;
-                    xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
-                }
-                wave_sync();
-                // r[a] = conv[a] + g n[a] of the sample m under the window, a = a0 + m, with the taps at a
-                auto rxs = [&](int m, auto fold) {
-                    const uint32_t a = (uint32_t)(a0 + m);
-                    uint32_t kq;
-                    float kf;
-                    dop_interval(a, step, rstep, last, kq, kf);
-                    const float2 *k0 = kn + kq * LT;
-                    float cr = 0.f, ci = 0.f;
-#pragma unroll
-                    for (int l = 0; l < LT; ++l) {
-                        const float2 ka = k0[l], kb = k0[LT + l];
-                        const float2 xv = xr[m + (LT - 1) - l], hv = make_float2(ka.x + kf * (kb.x - ka.x), ka.y + kf * (kb.y - ka.y));
-                        dop_tap<decltype(fold)::value>(hv, xv, cr, ci);
-                    }
-                    const v2f nz = rxp_noise(a >> 1, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, (int)(a & 1u));
-                    return make_float2(cr + g * nz.x, ci + g * nz.y);
-                };
-#pragma unroll 1
-                for (int j = 0; j < BINS; ++j) {
-                    const int t = lane + 64 * j, m0 = (t + p.kap + h2) & (N - 1);
-                    float2 z = rxs(m0, std::false_type{});
-                    z.x *= wrx[m0];
-                    z.y *= wrx[m0];
-                    if (m0 < delta) {
-                        const float2 z2 = rxs(m0 + N, std::true_type{});
-                        z.x += wrx[m0 + N] * z2.x;
-                        z.y += wrx[m0 + N] * z2.y;
-                    }
-                    buf[__brev((uint32_t)t) >> (32 - LOG2)] = z;
-                }
-                wave_sync();
-                for (int len = 2, sh = LOG2 - 1; len <= N; len <<= 1, --sh) {
-                    const int half = len >> 1;
-                    for (int b = lane; b < N / 2; b += 64) {
-                        const int kk = b & (half - 1), i = ((b - kk) << 1) | kk;
-                        const float2 w = tw[kk << sh], a = buf[i], c = buf[i + half];
-                        const float tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
-                        buf[i] = make_float2(a.x + tr, a.y + ti);
-                        buf[i + half] = make_float2(a.x - tr, a.y - ti);
-                    }
-                    wave_sync();
-                }
-            }
-            if (s0 == 0) {
-                // pilot LS estimate of the track, from symbol 0 alone
-                if (wv == 0)
-                    for (int n = lane; n < N; n += 64) {
-                        const float2 y = buf[n], x0 = Xg[n];
-                        const float d = y.x * y.x + y.y * y.y;
-                        const bool on = p.amask == nullptr || p.amask[n] != 0;
-                        G[n] = on ? make_float2((x0.x * y.x + x0.y * y.y) / d, (x0.y * y.x - x0.x * y.y) / d) : make_float2(0.f, 0.f);
-                    }
-                __syncthreads();
-            }
-            if (live) {
-                float spw = 0.f;
-                uint32_t scn = 0u;
-                if (s >= 1) {
-#pragma unroll
-                    for (int j = 0; j < BINS; ++j) {
-                        const int n = lane + 64 * j;
-                        if (p.amask != nullptr && p.amask[n] == 0) continue;
-                        const float2 y = buf[n], gq = G[n], xs = Xg[(size_t)s * N + n];
-                        const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;
-                        const uint32_t d = rxp_slice(p.k, xs.x, xs.y) ^ rxp_slice(p.k, er, ei);
-                        const uint32_t c = (uint32_t)__popc(d) + (d != 0u ? 0x10000u : 0u);
-                        const float e2 = (er - xs.x) * (er - xs.x) + (ei - xs.y) * (ei - xs.y);
-                        cnt[j] += c;
-                        pw[j] += e2;
-                        scn += c;
-                        spw += e2;
-                    }
-                }
-                // the symbol's sums over the bins: at most N k < 2^16 bit errors and N symbol errors, so the halves do not meet
-                spw = papr_wave_reduce<false>(spw);
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) scn += (uint32_t)__shfl_xor((int)scn, o, 64);
-                if (lane == 0) {
-                    sp.sym_pow[slot * S + s] = spw;
-                    sp.sym_cnt[slot * S + s] = scn;
-                }
-            }
-            wave_sync();
-        }
-        // the waves' sums in wave order (their rows are free now): float [W][N], then uint32 [W][N]
-        __syncthreads();
-        float *redp = reinterpret_cast<float *>(rows);
-        uint32_t *redc = reinterpret_cast<uint32_t *>(redp + W * N);
-#pragma unroll
-        for (int j = 0; j < BINS; ++j) {
-            redp[wv * N + lane + 64 * j] = pw[j];
-            redc[wv * N + lane + 64 * j] = cnt[j];
-        }
-        __syncthreads();
-        for (int n = tid; n < N; n += NT) {
-            float t = 0.f;
-            uint32_t c = 0u;
-            for (int w = 0; w < W; ++w) {
-                t += redp[w * N + n];
-                c += redc[w * N + n];
-            }
-            p.part_pow[slot * N + n] = t;
-            p.part_cnt[slot * N + n] = c;
-        }
-        __syncthreads();                                              // the rows, G and the knots belong to the next track
-    }
-}
-
-template <int N>
-__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_doppler_kernel(const wofdm_rparams p, const wofdm_sparams sp,
-                                                                                     const wofdm_dparams dp)
-{
-    rxprof_doppler_body<N>(p, sp, dp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1900,209 +1573,6 @@ __global__ void __launch_bounds__(64) wofdm_pa_power_reduce_kernel(const wofdm_p
     double acc = pa.pwr_tot[out];
     for (uint64_t i = lo; i < hi; ++i) acc += (double)pa.pwr[((size_t)(i - item0) * pa.n_points + pt) * 2 + which];
     pa.pwr_tot[out] = acc;
-}
-
-// The receive profile behind the amplifier (wofdm_rx_profile_pa): the item, the LDS image, the DFT, the pilot step, the
-// per-bin and per-symbol partials and their order are rxprof_sync_body's -- a body of its own again, so that the four kernels
-// above compile as they did --, with BOTH passes run once per point of pa (sp.n_points points; theta and eps do not exist
-// here) on the point's waveform: y[job][point] of wofdm_pa_wave_kernel, or x itself for a linear point.  Ps is measured per
-// point on conv(h, y); Pn does not depend on the waveform and is measured with the first point; the noise of on-air sample a
-// is the plain kernel's.  The taps are wave-uniform as in wofdm_rxprof_kernel, but two inlined copies of one expression need
-// not round alike (the note above dop_tap): the tap sums are written with dop_tap, the operations the plain kernel's
-// assembly shows, so a linear point gives its bits.  LDS: rxp_geo<N>::LDS.
-template <int N>
-__device__ __forceinline__ void rxprof_pa_body(const wofdm_rparams &p, const wofdm_sparams &sp, const wofdm_paparams &pa)
-{
-    using RG = rxp_geo<N>;
-    constexpr int ROWLEN = N + RG::XROW;
-    constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float2 *tw = reinterpret_cast<float2 *>(smem);                    // e^{-2 pi i k / N}, k < N / 2
-    float2 *G = tw + N / 2;                                           // pilot equaliser X0 / Y0 of the point
-    float *wrx = reinterpret_cast<float *>(G + N);
-    float *red = wrx + N + 64;                                        // [2][W] power partials
-    float2 *rows = reinterpret_cast<float2 *>(red + 64);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int S = p.S, B = p.B, T = p.T, NL = p.NL, delta = p.delta, NP = sp.n_points;
-    const uint32_t job = blockIdx.x;
-    const uint64_t item = p.item0 + job, cell64 = item / p.frames, frame = p.frame_offset + (item - cell64 * p.frames);
-    const uint32_t cell = (uint32_t)cell64, f_lo = (uint32_t)frame, f_hi = (uint32_t)(frame >> 32);
-    const int ch = (int)(cell % (uint32_t)p.n_ch), sn = (int)((cell / (uint32_t)p.n_ch) % (uint32_t)p.n_snr);
-    const int pair = (int)(cell / ((uint32_t)p.n_ch * (uint32_t)p.n_snr));
-    const float2 *__restrict__ Xg = p.X + (size_t)job * S * N;
-    const float2 *__restrict__ taps = p.h + (size_t)ch * LT;
-    for (int i = tid; i < N / 2; i += NT) {
-        float sv, cv;
-        sincospif(-2.0f * (float)i / (float)N, &sv, &cv);
-        tw[i] = make_float2(cv, sv);
-    }
-    for (int i = tid; i < N + delta; i += NT) wrx[i] = p.wrx[(size_t)pair * (N + delta) + i];
-    float2 *buf = rows + (size_t)wv * ROWLEN;
-    float2 *xr = buf + N;
-    const int h2 = delta >> 1;
-#pragma unroll 1
-    for (int pt = 0; pt < NP; ++pt) {
-        // the point's on-air waveform
-        const float2 *__restrict__ x = pa.pts[pt].model == WOFDM_PA_M_LINEAR ? p.x + (size_t)job * T
-                                                                             : pa.y + ((size_t)job * NP + pt) * (size_t)T;
-        // pass 1, once per point: the signal power over the NL samples of conv(h, y); the noise power with the first
-        float ps = 0.f, pn = 0.f;
-        for (int q = tid; 2 * q < NL; q += NT) {
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int jj = 2 * q + e;
-                if (jj >= NL) break;
-                float cr = 0.f, ci = 0.f;
-                for (int l = 0; l < LT; ++l) {
-                    const int t = jj - l;
-                    if (t < 0 || t >= T) continue;
-                    dop_tap<false>(taps[l], x[t], cr, ci);
-                }
-                ps += cr * cr + ci * ci;
-                if (pt == 0) {
-                    const v2f nz = rxp_noise((uint32_t)q, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, e);
-                    pn += nz.x * nz.x + nz.y * nz.y;
-                }
-            }
-        }
-        ps = papr_wave_reduce<false>(ps);
-        if (lane == 0) red[wv] = ps;
-        if (pt == 0) {
-            pn = papr_wave_reduce<false>(pn);
-            if (lane == 0) red[W + wv] = pn;
-        }
-        __syncthreads();
-        float Ps = 0.f, Pn = 0.f;
-        for (int w = 0; w < W; ++w) {
-            Ps += red[w];
-            Pn += red[W + w];
-        }
-        const float g = sqrtf(Ps * p.nlin[sn] / Pn);
-        // pass 2 of the point
-        const size_t slot = (size_t)job * NP + pt;
-        float pw[BINS];
-        uint32_t cnt[BINS];
-#pragma unroll
-        for (int j = 0; j < BINS; ++j) {
-            pw[j] = 0.f;
-            cnt[j] = 0u;
-        }
-        for (int s0 = 0; s0 < S; s0 += W) {
-            const int s = s0 + wv;
-            const bool live = s < S;                                  // (wave-uniform)
-            if (live) {
-                const int a0 = s * B + p.gam;                         // first sample under the Rx window
-                for (int i = lane; i < N + delta + LT - 1; i += 64) {
-                    const int t = a0 - (LT - 1) + i;
-                    xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
-                }
-                wave_sync();
-                // r[a] = conv[a] + g n[a] of the sample m under the window, a = a0 + m
-                auto rxs = [&](int m, auto fold) {
-                    float cr = 0.f, ci = 0.f;
-#pragma unroll
-                    for (int l = 0; l < LT; ++l) dop_tap<decltype(fold)::value>(taps[l], xr[m + (LT - 1) - l], cr, ci);
-                    const uint32_t a = (uint32_t)(a0 + m);
-                    const v2f nz = rxp_noise(a >> 1, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, (int)(a & 1u));
-                    return make_float2(cr + g * nz.x, ci + g * nz.y);
-                };
-#pragma unroll 1
-                for (int j = 0; j < BINS; ++j) {
-                    const int t = lane + 64 * j, m0 = (t + p.kap + h2) & (N - 1);
-                    float2 z = rxs(m0, std::false_type{});
-                    z.x *= wrx[m0];
-                    z.y *= wrx[m0];
-                    if (m0 < delta) {
-                        const float2 z2 = rxs(m0 + N, std::true_type{});
-                        z.x += wrx[m0 + N] * z2.x;
-                        z.y += wrx[m0 + N] * z2.y;
-                    }
-                    buf[__brev((uint32_t)t) >> (32 - LOG2)] = z;
-                }
-                wave_sync();
-                for (int len = 2, sh = LOG2 - 1; len <= N; len <<= 1, --sh) {
-                    const int half = len >> 1;
-                    for (int b = lane; b < N / 2; b += 64) {
-                        const int kk = b & (half - 1), i = ((b - kk) << 1) | kk;
-                        const float2 w = tw[kk << sh], a = buf[i], c = buf[i + half];
-                        const float tr = c.x * w.x - c.y * w.y, ti = c.x * w.y + c.y * w.x;
-                        buf[i] = make_float2(a.x + tr, a.y + ti);
-                        buf[i + half] = make_float2(a.x - tr, a.y - ti);
-                    }
-                    wave_sync();
-                }
-            }
-            if (s0 == 0) {
-                // pilot LS estimate of the point: the pilot went through the amplifier as the data did
-                if (wv == 0)
-                    for (int n = lane; n < N; n += 64) {
-                        const float2 y = buf[n], x0 = Xg[n];
-                        const float d = y.x * y.x + y.y * y.y;
-                        const bool on = p.amask == nullptr || p.amask[n] != 0;
-                        G[n] = on ? make_float2((x0.x * y.x + x0.y * y.y) / d, (x0.y * y.x - x0.x * y.y) / d) : make_float2(0.f, 0.f);
-                    }
-                __syncthreads();
-            }
-            if (live) {
-                float spw = 0.f;
-                uint32_t scn = 0u;
-                if (s >= 1) {
-#pragma unroll
-                    for (int j = 0; j < BINS; ++j) {
-                        const int n = lane + 64 * j;
-                        if (p.amask != nullptr && p.amask[n] == 0) continue;
-                        const float2 y = buf[n], gq = G[n], xs = Xg[(size_t)s * N + n];
-                        const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;
-                        const uint32_t d = rxp_slice(p.k, xs.x, xs.y) ^ rxp_slice(p.k, er, ei);
-                        const uint32_t c = (uint32_t)__popc(d) + (d != 0u ? 0x10000u : 0u);
-                        const float e2 = (er - xs.x) * (er - xs.x) + (ei - xs.y) * (ei - xs.y);
-                        cnt[j] += c;
-                        pw[j] += e2;
-                        scn += c;
-                        spw += e2;
-                    }
-                }
-                // the symbol's sums over the bins: at most N k < 2^16 bit errors and N symbol errors, so the halves do not meet
-                spw = papr_wave_reduce<false>(spw);
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) scn += (uint32_t)__shfl_xor((int)scn, o, 64);
-                if (lane == 0) {
-                    sp.sym_pow[slot * S + s] = spw;
-                    sp.sym_cnt[slot * S + s] = scn;
-                }
-            }
-            wave_sync();
-        }
-        // the waves' sums in wave order (their rows are free now): float [W][N], then uint32 [W][N]
-        __syncthreads();
-        float *redp = reinterpret_cast<float *>(rows);
-        uint32_t *redc = reinterpret_cast<uint32_t *>(redp + W * N);
-#pragma unroll
-        for (int j = 0; j < BINS; ++j) {
-            redp[wv * N + lane + 64 * j] = pw[j];
-            redc[wv * N + lane + 64 * j] = cnt[j];
-        }
-        __syncthreads();
-        for (int n = tid; n < N; n += NT) {
-            float t = 0.f;
-            uint32_t c = 0u;
-            for (int w = 0; w < W; ++w) {
-                t += redp[w * N + n];
-                c += redc[w * N + n];
-            }
-            p.part_pow[slot * N + n] = t;
-            p.part_cnt[slot * N + n] = c;
-        }
-        __syncthreads();                                              // the rows and G belong to the next point
-    }
-}
-
-template <int N>
-__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_pa_kernel(const wofdm_rparams p, const wofdm_sparams sp,
-                                                                                const wofdm_paparams pa)
-{
-    rxprof_pa_body<N>(p, sp, pa);
 }
 
 // The amplifier of wofdm_tx_psd_batch_pa, two kernels between the waveform kernels and the periodogram; grid (jobs), 1024
@@ -2359,22 +1829,52 @@ hipError_t papr_launch(const wofdm_pparams *pp, hipStream_t s)
     return hipGetLastError();
 }
 
+// What the five receive-profile launchers share.  The chunk of r is the chunk of pp's Tx chain, within the receive kernel's geometry:
+bool rxprof_args_ok(const wofdm_pparams *pp, const wofdm_rparams &r)
+{
+    constexpr int N = WOFDM_TU_N;
+    return !(r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
+             r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 ||
+             r.n_snr < 1);
+}
+// the arms with a point loop: the points, the per-symbol partials and totals, and the chunk's cells within the totals
+bool rxprof_points_ok(const wofdm_sparams &sp, const wofdm_rparams &r, int max_points)
+{
+    return !(sp.n_points < 1 || sp.n_points > max_points || sp.sym_pow == nullptr || sp.sym_cnt == nullptr || sp.sym_errs == nullptr ||
+             sp.sym_tot == nullptr || r.S < 2 || r.S > 64 || (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames >= sp.cells);
+}
+// the cells the chunk's items touch: the first, and how many
+unsigned rxprof_cells(const wofdm_rparams &r, uint64_t &cell0)
+{
+    cell0 = r.item0 / r.frames;
+    return (unsigned)((r.item0 + (uint64_t)r.n_jobs - 1) / r.frames - cell0 + 1);
+}
+// the ordered sums of the chunk onto the totals: per point of sp, or (null) the plain ones
+void rxprof_reduce_launch(const wofdm_rparams &r, const wofdm_sparams *sp, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N;
+    uint64_t cell0;
+    const unsigned n_cells = rxprof_cells(r, cell0);
+    if (sp == nullptr)
+        hipLaunchKernelGGL(wofdm_rxprof_reduce_kernel<N>, dim3(N / 64, n_cells), dim3(64), 0, s, r, cell0);
+    else
+        hipLaunchKernelGGL(wofdm_rxprof_sync_reduce_kernel<N>, dim3(N / 64 + 1, n_cells, (unsigned)sp->n_points), dim3(64), 0, s, r,
+                           *sp, cell0);
+}
+
 // wofdm_rx_profile, one chunk: the Tx chain of the chunk's (cell, frame) items, their receive profiles, and the ordered sums
 hipError_t rx_profile_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, hipStream_t s)
 {
     constexpr int N = WOFDM_TU_N;
     const wofdm_rparams &r = *rp;
-    if (r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
-        r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 || r.n_snr < 1)
-        return hipErrorInvalidValue;
+    if (!rxprof_args_ok(pp, r)) return hipErrorInvalidValue;
     hipError_t e = tx_chain_launch(*pp, s);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 rxp_geo<N>::LDS);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(wofdm_rxprof_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r);
-    const uint64_t cell0 = r.item0 / r.frames, cell1 = (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames;
-    hipLaunchKernelGGL(wofdm_rxprof_reduce_kernel<N>, dim3(N / 64, (unsigned)(cell1 - cell0 + 1)), dim3(64), 0, s, r, cell0);
+    rxprof_reduce_launch(r, nullptr, s);
     return hipGetLastError();
 }
 
@@ -2386,9 +1886,7 @@ hipError_t rx_profile_aci_launch(const wofdm_pparams *pp, const wofdm_pparams *p
     constexpr int N = WOFDM_TU_N;
     const wofdm_rparams &r = *rp;
     const wofdm_aparams &a = *app;
-    if (r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
-        r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 || r.n_snr < 1)
-        return hipErrorInvalidValue;
+    if (!rxprof_args_ok(pp, r)) return hipErrorInvalidValue;
     if (pa->n_jobs != pp->n_jobs || pa->item0 != pp->item0 || pa->frames != pp->frames || pa->frame_offset != pp->frame_offset ||
         pa->S != r.S + 1 || pa->P != pp->P || pa->beta != pp->beta || pa->cp != pp->cp || pa->cs != pp->cs || pa->wdiv != pp->wdiv ||
         a.Ti != r.T + r.B || a.ioff < 1 || a.ioff > r.B || a.xi != pa->x || a.hi == nullptr || pa->X == pp->X || pa->x == pp->x ||
@@ -2401,8 +1899,7 @@ hipError_t rx_profile_aci_launch(const wofdm_pparams *pp, const wofdm_pparams *p
                                 rxp_geo<N>::LDS_ACI);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(wofdm_rxprof_aci_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_ACI, s, r, a);
-    const uint64_t cell0 = r.item0 / r.frames, cell1 = (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames;
-    hipLaunchKernelGGL(wofdm_rxprof_reduce_kernel<N>, dim3(N / 64, (unsigned)(cell1 - cell0 + 1)), dim3(64), 0, s, r, cell0);
+    rxprof_reduce_launch(r, nullptr, s);
     return hipGetLastError();
 }
 
@@ -2412,12 +1909,7 @@ hipError_t rx_profile_sync_launch(const wofdm_pparams *pp, const wofdm_rparams *
     constexpr int N = WOFDM_TU_N;
     const wofdm_rparams &r = *rp;
     const wofdm_sparams &sp = *spp;
-    if (r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
-        r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 || r.n_snr < 1)
-        return hipErrorInvalidValue;
-    if (sp.n_points < 1 || sp.n_points > WOFDM_SYNC_POINTS || sp.pts == nullptr || sp.base == nullptr || sp.sym_pow == nullptr ||
-        sp.sym_cnt == nullptr || sp.sym_errs == nullptr || sp.sym_tot == nullptr || r.S < 2 || r.S > 64 ||
-        (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames >= sp.cells)
+    if (!rxprof_args_ok(pp, r) || !rxprof_points_ok(sp, r, WOFDM_SYNC_POINTS) || sp.pts == nullptr || sp.base == nullptr)
         return hipErrorInvalidValue;
     hipError_t e = tx_chain_launch(*pp, s);
     if (e == hipSuccess)
@@ -2425,9 +1917,7 @@ hipError_t rx_profile_sync_launch(const wofdm_pparams *pp, const wofdm_rparams *
                                 rxp_geo<N>::LDS);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(wofdm_rxprof_sync_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r, sp);
-    const uint64_t cell0 = r.item0 / r.frames, cell1 = (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames;
-    hipLaunchKernelGGL(wofdm_rxprof_sync_reduce_kernel<N>, dim3(N / 64 + 1, (unsigned)(cell1 - cell0 + 1), (unsigned)sp.n_points),
-                       dim3(64), 0, s, r, sp, cell0);
+    rxprof_reduce_launch(r, &sp, s);
     return hipGetLastError();
 }
 
@@ -2440,13 +1930,7 @@ hipError_t rx_profile_doppler_launch(const wofdm_pparams *pp, const wofdm_rparam
     const wofdm_rparams &r = *rp;
     const wofdm_sparams &sp = *spp;
     const wofdm_dparams &dp = *dpp;
-    if (r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
-        r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 || r.n_snr < 1)
-        return hipErrorInvalidValue;
-    if (sp.n_points < 1 || sp.n_points > WOFDM_DOPPLER_TRACKS || sp.sym_pow == nullptr || sp.sym_cnt == nullptr ||
-        sp.sym_errs == nullptr || sp.sym_tot == nullptr || r.S < 2 || r.S > 64 ||
-        (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames >= sp.cells)
-        return hipErrorInvalidValue;
+    if (!rxprof_args_ok(pp, r) || !rxprof_points_ok(sp, r, WOFDM_DOPPLER_TRACKS)) return hipErrorInvalidValue;
     // the knots fit the LDS image and cover every sample either pass takes a tap at; the indices stay exact in single precision
     if (dp.knots == nullptr || dp.n_knots < 2 || dp.n_knots > WOFDM_DOPPLER_KNOTS || dp.knot_step < 1 || r.T + WOFDM_LT >= (1 << 22) ||
         (int64_t)(dp.n_knots - 1) * dp.knot_step < (int64_t)(r.NL > r.T ? r.NL : r.T) - 1)
@@ -2458,9 +1942,7 @@ hipError_t rx_profile_doppler_launch(const wofdm_pparams *pp, const wofdm_rparam
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(wofdm_rxprof_doppler_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_DOP, s, r,
                        sp, dp);
-    const uint64_t cell0 = r.item0 / r.frames, cell1 = (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames;
-    hipLaunchKernelGGL(wofdm_rxprof_sync_reduce_kernel<N>, dim3(N / 64 + 1, (unsigned)(cell1 - cell0 + 1), (unsigned)sp.n_points),
-                       dim3(64), 0, s, r, sp, cell0);
+    rxprof_reduce_launch(r, &sp, s);
     return hipGetLastError();
 }
 
@@ -2473,17 +1955,12 @@ hipError_t rx_profile_pa_launch(const wofdm_pparams *pp, const wofdm_rparams *rp
     const wofdm_rparams &r = *rp;
     const wofdm_sparams &sp = *spp;
     const wofdm_paparams &pa = *pap;
-    if (r.n_jobs != pp->n_jobs || r.item0 != pp->item0 || r.frames != pp->frames || r.delta < 0 || r.delta > 64 || (r.delta & 1) ||
-        r.gam < 0 || r.B != N + r.delta + r.gam || r.T != pp->beta + r.S * r.B || r.NL > r.T + WOFDM_LT - 1 || r.n_ch < 1 || r.n_snr < 1)
-        return hipErrorInvalidValue;
-    if (sp.n_points < 1 || sp.n_points > WOFDM_PA_POINTS || sp.sym_pow == nullptr || sp.sym_cnt == nullptr ||
-        sp.sym_errs == nullptr || sp.sym_tot == nullptr || r.S < 2 || r.S > 64 ||
-        (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames >= sp.cells)
-        return hipErrorInvalidValue;
-    const uint64_t cell0 = r.item0 / r.frames, cell1 = (r.item0 + (uint64_t)r.n_jobs - 1) / r.frames;
+    if (!rxprof_args_ok(pp, r) || !rxprof_points_ok(sp, r, WOFDM_PA_POINTS)) return hipErrorInvalidValue;
+    uint64_t cell0;
+    const unsigned n_cells = rxprof_cells(r, cell0);
     // the saturation table covers the pair of every cell of the chunk
     if (pa.n_points != sp.n_points || pa.pairs < 1 || pa.pts == nullptr || pa.asat == nullptr || pa.y == nullptr || pa.pwr == nullptr ||
-        pa.pwr_tot == nullptr || r.x != pp->x || cell1 / pp->wdiv >= (uint64_t)pa.pairs)
+        pa.pwr_tot == nullptr || r.x != pp->x || (cell0 + n_cells - 1) / pp->wdiv >= (uint64_t)pa.pairs)
         return hipErrorInvalidValue;
     hipError_t e = tx_chain_launch(*pp, s);
     if (e == hipSuccess)
@@ -2493,10 +1970,8 @@ hipError_t rx_profile_pa_launch(const wofdm_pparams *pp, const wofdm_rparams *rp
     hipLaunchKernelGGL(wofdm_pa_wave_kernel, dim3((unsigned)r.n_jobs, (unsigned)pa.n_points), dim3(256), 0, s, pa, r.x, r.T, r.item0,
                        r.frames, pp->wdiv);
     hipLaunchKernelGGL(wofdm_rxprof_pa_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r, sp, pa);
-    hipLaunchKernelGGL(wofdm_rxprof_sync_reduce_kernel<N>, dim3(N / 64 + 1, (unsigned)(cell1 - cell0 + 1), (unsigned)sp.n_points),
-                       dim3(64), 0, s, r, sp, cell0);
-    hipLaunchKernelGGL(wofdm_pa_power_reduce_kernel, dim3((unsigned)(cell1 - cell0 + 1)), dim3(64), 0, s, pa, r.item0, r.n_jobs,
-                       r.frames, sp.cells, cell0);
+    rxprof_reduce_launch(r, &sp, s);
+    hipLaunchKernelGGL(wofdm_pa_power_reduce_kernel, dim3(n_cells), dim3(64), 0, s, pa, r.item0, r.n_jobs, r.frames, sp.cells, cell0);
     return hipGetLastError();
 }
 
