@@ -479,7 +479,8 @@ int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device,
  * (tools/bench_rx_profile.py, tools/bench_rx_profile_aci.py).  A successful wofdm_rx_profile_sync call (below) counts as
  * such a call too: the figure is then that of its whole sweep (tools/bench_rx_profile_sync.py); so does a successful
  * wofdm_rx_profile_doppler call, with all its tracks (tools/bench_rx_profile_doppler.py), and a successful
- * wofdm_rx_profile_pa call, with all its points (tools/bench_rx_profile_pa.py). */
+ * wofdm_rx_profile_pa call, with all its points (tools/bench_rx_profile_pa.py), and a successful wofdm_rx_profile_pn call,
+ * with its walk and all its points (tools/bench_rx_profile_pn.py). */
 int wofdm_rx_profile_kernel_ms(float *ms);
 
 /* wofdm_rx_profile under receiver timing and carrier-frequency offset: what the victim of wofdm_rx_profile loses, bin by bin
@@ -628,6 +629,70 @@ int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device,
                         uint64_t *sym_errs,                 /* [n_points][cells][S-1][2], or NULL */
                         double *sym_power,                  /* [n_points][cells][S-1], or NULL */
                         double *pa_power);                  /* [n_points][cells][2], or NULL */
+
+/* wofdm_rx_profile under oscillator PHASE NOISE: what the victim of wofdm_rx_profile loses, bin by bin and symbol by symbol,
+ * when the receiver's oscillator phase is a random walk (a Lorentzian line) -- the carrier-frequency offset of
+ * wofdm_rx_profile_sync is a deterministic ramp, every other call holds the phase still.  The walk does two things: it turns a
+ * whole symbol by a common phase error (CPE), which under the pilot-of-symbol-0 receiver grows with the distance from the
+ * pilot -- hence the per-symbol outputs --, and it smears every subcarrier onto its neighbours (ICI), the quantity the Rx
+ * window is there to reject.  The reference has no such experiment.  A call takes a LIST of points (linewidth, tracked or
+ * not) and runs the Tx chain, the power pass and the walk once per frame, whatever n_points is; every point sees the same
+ * labels, the same noise and the same unit walk, so linewidths compare pairwise.
+ *   Victim: exactly wofdm_rx_profile -- frames, cells, streams 0 and 1, allocation, mask, both noise_before_truncate orders, Ps,
+ * Pn and the noise gain g (which never sees the phase), the gate; the noise of on-air sample a is the unit normal the plain
+ * kernel uses for it.
+ *   Walk: the increment xi[j] of on-air index j >= 0 of (seed, cell, frame) is one component of a complex unit normal of
+ * stream 3 of philox.h: complex index c = j >> 1 from block c >> 1, word pair c & 1 (the layout of the noise of stream 1),
+ * counter (c >> 1, frame lo, frame hi, 3 << 28 | cell), key = seed; the real part for even j, the imaginary part for odd j.
+ * The two uniforms are formed in single precision as the noise forms them (their values are exact), the Box-Muller step
+ * sqrt(-2 ln u1) (cos, sin) 2 pi u2 in double precision.  The unit walk u[a] = xi[0] + ... + xi[a], 0 <= a < S B, is
+ * accumulated and kept in double precision on the device, once per frame (a workgroup-wide prefix sum in a fixed order).
+ *   Per point: linewidth is beta, the two-sided 3 dB width of the Lorentzian line in subcarrier spacings, 0 <= beta <= 1; the
+ * walk's variance per sample is sigma^2 = 2 pi beta / n_fft, and sigma / (2 pi) is formed on the host in double precision from
+ * beta as stored.  Sample m, 0 <= m < n_fft + tail_rx, of symbol s sits at a = s B + prefix_rm + m -- the windows of a
+ * receiver at timing 0 read exactly the on-air indices [0, S B) -- and is multiplied, signal and noise, before the Rx window
+ * by e^{i sigma u[a]} (cpe_tracked = 0, a free-running oscillator) or by e^{i sigma (u[a] - ubar_s)} (cpe_tracked = 1: a
+ * genie removes the common phase error), ubar_s the unweighted mean of u over the n_fft + tail_rx samples under the symbol's
+ * window, formed in double precision in a fixed order; then Rx window, fold, shift, DFT, the pilot LS estimate from symbol 0
+ * -- the pilot sees what the data sees --, equaliser and slicer as in wofdm_rx_profile.  The phase is reduced in double
+ * precision, t = (sigma / 2 pi) u less its nearest integer, and only then rounded to single for the sine and cosine: the
+ * rotation is good to about 2e-7 rad for every beta and n_fft, an order below the in-window factor of wofdm_rx_profile_sync,
+ * so there is no limit of the |cfo| <= 4 kind.
+ *   Outputs (host), ACCUMULATED into, with the shapes and the ordered sums of wofdm_rx_profile_sync, "point" on the leading
+ * axis: errs[n_points][cells][n_fft][2], err_power[n_points][cells][n_fft] (or NULL), sym_errs[n_points][cells][S-1][2] and
+ * sym_power[n_points][cells][S-1] (either may be NULL).  Integer counters are exact; float sums per frame in fp32 in the sync
+ * kernel's order, over the frames of a cell in fp64, one addition per frame --, so repeated calls give identical bits, a split
+ * frame range gives the integer counters of one call, and a point's results do not depend on which other points share its
+ * call.  A point with linewidth = 0, under either flag, gives the bits of wofdm_rx_profile, err_power bytes included (as long
+ * as no cell's frames are split over two chunks of that call).
+ *   Every limit and check of wofdm_rx_profile applies.  WOFDM_E_INVALID: NULL points or errs, n_points < 1, a non-finite or
+ * negative linewidth, cpe_tracked other than 0 or 1, reserved != 0; WOFDM_E_UNSUPPORTED: n_points > WOFDM_PN_MAX_POINTS,
+ * linewidth > 1.  Every argument is checked before the device is touched; a failed call leaves all four outputs as they were.
+ *   Chunks: min(65535, WOFDM_RX_PROFILE_CHUNK_BYTES / (8 (S n_fft + T + [mask] S (2P-1)) + 8 S B + 8 n_points (n_fft + S)))
+ * frames -- wofdm_rx_profile_sync's formula plus the walk, S B doubles.
+ *   A successful call counts for wofdm_rx_profile_kernel_ms.
+ *   Measured on an MI355X (tools/bench_rx_profile_pn.py, profiles/rx_profile_pn.txt): on 64 cells x 2000 frames x 16 symbols at
+ * n_fft = 256 one point takes 55.9 ms of kernels (83.1 ms masked), 1.43 (1.17) times one wofdm_rx_profile call on the same cells
+ * and frames in the same run; four points take 79.1 (106.9) ms, 2.02 (1.51) times -- 0.20 (0.11) of a plain call per
+ * additional point, beside wofdm_rx_profile_sync's 0.30 (0.22) per point measured the same way. */
+#define WOFDM_PN_MAX_POINTS 16
+typedef struct wofdm_pn_point {
+    float   linewidth;    /* beta: two-sided 3 dB Lorentzian linewidth in subcarrier spacings, 0 <= beta <= 1 */
+    int32_t cpe_tracked;  /* 0: free-running oscillator; 1: the common phase error of every symbol removed (a genie) */
+    int32_t reserved[2];  /* 0 */
+} wofdm_pn_point;
+int wofdm_rx_profile_pn(const wofdm_cfg *cfg, int device,
+                        const float *w_tx,                  /* [pairs][P] */
+                        const float *w_rx,                  /* [pairs][N+tail_rx] */
+                        const float *h,                     /* [n_channels][n_taps][2] */
+                        const float *snr_db,                /* [n_snr] */
+                        const uint8_t *active,              /* [n_fft] or NULL */
+                        const float *tx_mask,               /* [2P-1] or NULL */
+                        int32_t n_points, const wofdm_pn_point *points,
+                        uint64_t *errs,                     /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                        double *err_power,                  /* [n_points][cells][n_fft], or NULL */
+                        uint64_t *sym_errs,                 /* [n_points][cells][S-1][2], or NULL */
+                        double *sym_power);                 /* [n_points][cells][S-1], or NULL */
 
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

@@ -34,6 +34,8 @@ DOPPLER_MAX_KNOTS = 64
 #: wofdm_rx_profile_pa, wofdm_tx_psd_batch_pa (include/wofdm.h): the amplifier models, most points one call takes
 PA_LINEAR, PA_RAPP, PA_CLIP = 0, 1, 2
 PA_MAX_POINTS = 16
+#: wofdm_rx_profile_pn (include/wofdm.h): most points one call takes
+PN_MAX_POINTS = 16
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -46,7 +48,7 @@ EXPORTS = (
     "wofdm_interference_masked", "wofdm_tx_papr", "wofdm_tx_papr_kernel_ms",
     "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms", "wofdm_plan_kernel_geo", "wofdm_cfg_geo_id",
     "wofdm_rx_profile_aci", "wofdm_rx_profile_sync", "wofdm_rx_profile_doppler",
-    "wofdm_rx_profile_pa", "wofdm_tx_psd_batch_pa",
+    "wofdm_rx_profile_pa", "wofdm_tx_psd_batch_pa", "wofdm_rx_profile_pn",
 )
 
 
@@ -94,6 +96,11 @@ class SyncPoint(C.Structure):
 class PaPoint(C.Structure):
     """Mirror of ``wofdm_pa_point`` (16 bytes)."""
     _fields_ = [("model", C.c_int32), ("ibo_db", C.c_float), ("smooth", C.c_float), ("reserved", C.c_int32)]
+
+
+class PnPoint(C.Structure):
+    """Mirror of ``wofdm_pn_point`` (16 bytes)."""
+    _fields_ = [("linewidth", C.c_float), ("cpe_tracked", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class Dump(C.Structure):
@@ -173,6 +180,7 @@ def load():
     L.wofdm_rx_profile_sync.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, i32, C.POINTER(SyncPoint), vp, vp, vp, vp]
     L.wofdm_rx_profile_doppler.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_rx_profile_pa.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, i32, C.POINTER(PaPoint), vp, vp, vp, vp, vp, vp]
+    L.wofdm_rx_profile_pn.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, i32, C.POINTER(PnPoint), vp, vp, vp, vp]
     L.wofdm_tx_psd_batch_pa.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, C.POINTER(PaPoint), vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L

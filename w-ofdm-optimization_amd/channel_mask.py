@@ -370,6 +370,45 @@ def sync_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_s
     return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
 
 
+def pn_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_subcar=256, bits_per_subcar=4, symbols_per_tx=16,
+                       ensemble=100, roll_off=ROLL_OFF, seed=0, frame_range=None, gpu=True, device=0, tail_tx=8, tail_rx=10):
+    """The oscillator side of the mask experiment: ``profile_for_window_file`` with a receiver whose oscillator phase is a
+    random walk -- a common phase error that grows with the distance from the pilot, and ICI, which the Rx window is there to
+    reject and in which the window pairs differ.  Every window pair of the file + the RC pair under half-band loading, for
+    every SNR point, channel and point of ``points`` (``rx_profile.PnPoint`` or (linewidth, cpe_tracked) tuples: subcarrier
+    spacings, 0 / 1), plain and masked (``tx_mask(P)``) -- on the GPU two ``wofdm_rx_profile_pn`` calls whatever len(points)
+    is: the Tx chain, the power pass and the phase walk of a frame run once for all its points (gpu=False: the fp64 host
+    route ``rx_profile.rx_profile_pn_host``, for small ensembles).  The frames are those of ``profile_for_window_file`` with
+    the same arguments, so a point of linewidth 0 is its result.
+    Returns {name: {"profile", "profile_masked"}} with the names of ``V.matlab_pair_plan``; each an
+    ``rx_profile.RxProfileSync`` of that pair, arrays [points, n_snr, n_channels, N] and [points, n_snr, n_channels, S - 1]."""
+    from . import rx_profile as R
+    n = num_subcar
+    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
+                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
+    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
+    plan = V.matlab_pair_plan(type_ofdm)
+
+    def pick(key, side):
+        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
+
+    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
+    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
+    h = np.atleast_2d(np.asarray(channels))
+    alloc = half_band_allocation(n)
+    mask = tx_mask(st.sym_len, roll_off)
+    first, count = (0, ensemble) if frame_range is None else frame_range
+    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, h, snr_db, seed, first, count, list(points))
+    run = R.rx_profile_pn_gpu if gpu else R.rx_profile_pn_host
+    kw = dict(active=alloc, device=device) if gpu else dict(active=alloc)
+    plain = run(*args, **kw)
+    masked = run(*args, mask=mask, **kw)
+
+    def of_pair(prof, i):
+        return R.RxProfileSync(*(a[:, i] for a in prof[:6]), prof.decisions)
+    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
+
+
 def doppler_for_window_file(type_ofdm, cp, windows, tracks, knot_step, snr_db, num_subcar=256, bits_per_subcar=4,
                             symbols_per_tx=16, ensemble=100, roll_off=ROLL_OFF, seed=0, frame_range=None, gpu=True, device=0,
                             tail_tx=8, tail_rx=10):

@@ -8,6 +8,12 @@
 //   stream 2: data bits of the adjacent-band neighbour of wofdm_rx_profile_aci (no counterpart in the reference): block and
 //             slot layout of stream 0, for the neighbour's S + 1 symbols u = 0 ... S: counter (u bps + blk, frame lo, frame
 //             hi, 2 << 28 | cell), bps = N kslot / 128 blocks per symbol.  The frame kernels never draw it.
+//   stream 3: increments of the oscillator's phase walk of wofdm_rx_profile_pn (no counterpart in the reference): the noise
+//             layout of stream 1 with one REAL unit normal per on-air sample -- complex normal c = j >> 1 comes from block
+//             c >> 1, words 2 (c & 1) and 2 (c & 1) + 1, and the increment of on-air index j is its real part for even j,
+//             its imaginary part for odd j; counter (c >> 1, frame lo, frame hi, 3 << 28 | cell).  u1 and u2 are formed in
+//             single precision as below (so their values are exact), the Box-Muller step is done in double precision.  The
+//             frame kernels never draw it.
 //
 // Bits: subcarrier n of symbol s owns a kslot-bit field (kslot = 2, 4, 8 for k = 2, 4, 6) at
 // bit offset n*kslot of the symbol's bit stream, i.e. block s*(N*kslot/128) + (n*kslot >> 7),
@@ -22,6 +28,7 @@
 #define WOFDM_STREAM_BITS  0u
 #define WOFDM_STREAM_NOISE 1u
 #define WOFDM_STREAM_ACI   2u
+#define WOFDM_STREAM_PN    3u
 
 struct philox_out { uint32_t w[4]; };
 

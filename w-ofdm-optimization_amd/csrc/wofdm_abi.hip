@@ -1594,11 +1594,21 @@ struct pa_args {
     double *pa_power;
 };
 
-// wofdm_rx_profile, wofdm_rx_profile_aci, wofdm_rx_profile_sync, wofdm_rx_profile_doppler and wofdm_rx_profile_pa.  Every argument is checked before the first HIP call; the
+// the oscillator phase noise of wofdm_rx_profile_pn and its per-symbol outputs; a null pointer to it is an oscillator that holds
+// its phase
+struct pn_args {
+    int32_t n_points;
+    const wofdm_pn_point *points;
+    uint64_t *sym_errs;
+    double *sym_power;
+};
+
+// wofdm_rx_profile, wofdm_rx_profile_aci, wofdm_rx_profile_sync, wofdm_rx_profile_doppler, wofdm_rx_profile_pa and
+// wofdm_rx_profile_pn.  Every argument is checked before the first HIP call; the
 // caller's arrays are written only after everything has succeeded.
 int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                     const float *snr_db, const uint8_t *active, const float *tx_mask, const aci_args *aci, const sync_args *sync,
-                    const doppler_args *dop, const pa_args *amp, uint64_t *errs, double *err_power)
+                    const doppler_args *dop, const pa_args *amp, const pn_args *pn, uint64_t *errs, double *err_power)
 {
     if (!cfg || !w_tx || !w_rx || !(dop ? dop->h_track : h) || !snr_db || !errs) return fail(WOFDM_E_INVALID, "NULL argument");
     if (amp && (!amp->points || !amp->ref_power)) return fail(WOFDM_E_INVALID, "NULL argument (points or ref_power)");
@@ -1606,6 +1616,8 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     if (aci && !aci->active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active)");
     if (sync && !sync->points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
     if (sync && sync->n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", sync->n_points);
+    if (pn && !pn->points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
+    if (pn && pn->n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", pn->n_points);
     if (dop && (dop->n_tracks < 1 || dop->n_knots < 2 || dop->knot_step < 1))
         return fail(WOFDM_E_INVALID, "n_tracks=%d must be >= 1, n_knots=%d >= 2, knot_step=%d >= 1", dop->n_tracks, dop->n_knots,
                     dop->knot_step);
@@ -1665,7 +1677,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         for (int n = 0; n < N; ++n) nb |= (hiact[(size_t)n] = aci->active[n] ? 1 : 0) != 0;
     }
     // the receiver offsets: the base phasor of every (point, symbol) in double precision, from cfo as stored
-    const int NP = sync ? sync->n_points : (dop ? dop->n_tracks : (amp ? amp->n_points : 1));
+    const int NP = sync ? sync->n_points : (dop ? dop->n_tracks : (amp ? amp->n_points : (pn ? pn->n_points : 1)));
     std::vector<wofdm_spoint> hpts;
     std::vector<float2> hbase;
     if (sync) {
@@ -1694,6 +1706,28 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
                 hbase[(size_t)i * S + s] =
                     q.cfo_tracked ? make_float2(1.f, 0.f) : make_float2((float)std::cos(ph), (float)std::sin(ph));
             }
+        }
+    }
+    // the phase noise: sigma / (2 pi) = sqrt(beta / (2 pi n_fft)) of every point in double precision, from beta as stored
+    std::vector<wofdm_pnpoint> hpn;
+    if (pn) {
+        if (NP > WOFDM_PN_MAX_POINTS) return fail(WOFDM_E_UNSUPPORTED, "n_points=%d exceeds %d", NP, WOFDM_PN_MAX_POINTS);
+        for (int i = 0; i < NP; ++i) {
+            const wofdm_pn_point &q = pn->points[i];
+            if (!std::isfinite(q.linewidth) || q.linewidth < 0.f)
+                return fail(WOFDM_E_INVALID, "points[%d].linewidth must be finite and >= 0", i);
+            if (q.cpe_tracked != 0 && q.cpe_tracked != 1)
+                return fail(WOFDM_E_INVALID, "points[%d].cpe_tracked=%d must be 0 or 1", i, q.cpe_tracked);
+            if (q.reserved[0] != 0 || q.reserved[1] != 0) return fail(WOFDM_E_INVALID, "points[%d].reserved must be 0", i);
+        }
+        hpn.resize((size_t)NP);
+        for (int i = 0; i < NP; ++i) {
+            const wofdm_pn_point &q = pn->points[i];
+            if (q.linewidth > 1.0f)
+                return fail(WOFDM_E_UNSUPPORTED, "points[%d].linewidth=%g exceeds 1 subcarrier spacing", i, (double)q.linewidth);
+            hpn[(size_t)i].turn = std::sqrt((double)q.linewidth / (2.0 * 3.14159265358979323846 * (double)N));
+            hpn[(size_t)i].tracked = q.cpe_tracked;
+            hpn[(size_t)i].pad = 0;
         }
     }
     // the moving channels: every knot finite, and the knots reach the last sample of conv, index T + L - 2
@@ -1732,10 +1766,11 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     // frames per chunk: what the budget holds (symbol grid + waveform + filtered symbols + partials of a frame; with a neighbour
     // its S + 1 symbols beside them), as the header documents it
     const int Ti = T + B;
-    // (under receiver offsets or moving channels the partials are per point or track, per bin and per symbol; behind the
-    // amplifier every point has a waveform of its own beside them)
+    // (under receiver offsets, moving channels or phase noise the partials are per point or track, per bin and per symbol;
+    // behind the amplifier every point has a waveform of its own beside them; the phase walk is S B doubles)
     const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) +
-                                       (sync || dop ? (uint64_t)NP * (uint64_t)(N + S) : (amp ? (uint64_t)NP * (uint64_t)(N + S + T) : (uint64_t)N)) +
+                                       (sync || dop || pn ? (uint64_t)NP * (uint64_t)(N + S) : (amp ? (uint64_t)NP * (uint64_t)(N + S + T) : (uint64_t)N)) +
+                                       (pn ? (uint64_t)S * B : 0ull) +
                                        (nb ? (uint64_t)(S + 1) * N + (uint64_t)Ti + (tx_mask ? (uint64_t)(S + 1) * Lm : 0ull) : 0ull));
     const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
                                                                        std::max<uint64_t>(1, WOFDM_RX_PROFILE_CHUNK_BYTES / job_bytes)));
@@ -1760,7 +1795,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     std::vector<float> nlin((size_t)cfg->n_snr);
     for (int i = 0; i < cfg->n_snr; ++i) nlin[(size_t)i] = (float)std::pow(10.0, -0.1 * (double)snr_db[i]);
     const size_t n_w = (size_t)pairs * P, n_wr = (size_t)pairs * NW, n_out = (size_t)NP * cells * N;
-    const size_t n_sym = sync || dop || amp ? (size_t)NP * cells * (S - 1) : 0;
+    const size_t n_sym = sync || dop || amp || pn ? (size_t)NP * cells * (S - 1) : 0;
     dev_buf<float> d_w, d_wr, d_nlin, d_ppow;
     dev_buf<uint8_t> d_act;
     dev_buf<float2> d_h, d_spec, d_X, d_x, d_Y;
@@ -1788,7 +1823,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     dev_buf<uint32_t> d_scnt;
     dev_buf<unsigned long long> d_serrs;
     dev_buf<double> d_stot;
-    if (sync || dop || amp) {
+    if (sync || dop || amp || pn) {
         if ((sync && (!d_pts.alloc(hpts.size()) || !d_base.alloc(hbase.size()))) || !d_spow.alloc((size_t)chunk * NP * S) ||
             !d_scnt.alloc((size_t)chunk * NP * S) || !d_serrs.alloc(2 * n_sym) || !d_stot.alloc(n_sym))
             return fail(WOFDM_E_NOMEM, "device allocation failed (receiver offsets or tracks)");
@@ -1809,6 +1844,14 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         if (!d_papts.upload(hpa.data(), hpa.size()) || !d_asat.upload(hasat.data(), hasat.size()) ||
             hipMemset(d_ptot, 0, n_ptot * 8) != hipSuccess)
             return fail(WOFDM_E_HIP, "upload failed");
+    }
+    // the phase noise's side: the points and the unit walks of the chunk's items
+    dev_buf<wofdm_pnpoint> d_pnpts;
+    dev_buf<double> d_walk;
+    if (pn) {
+        if (!d_pnpts.alloc(hpn.size()) || !d_walk.alloc((size_t)chunk * S * B))
+            return fail(WOFDM_E_NOMEM, "device allocation failed (phase noise)");
+        if (!d_pnpts.upload(hpn.data(), hpn.size())) return fail(WOFDM_E_HIP, "upload failed");
     }
     // the neighbour's side of the chunk: allocation, channels, and grids, waveforms, tables of its S + 1 symbols
     dev_buf<uint8_t> d_iact;
@@ -1847,6 +1890,8 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         papar.n_points = NP; papar.pairs = (int32_t)pairs; papar.pts = d_papts; papar.asat = d_asat; papar.y = d_y;
         papar.pwr = d_pwr; papar.pwr_tot = d_ptot;
     }
+    wofdm_pnparams pnpar{};
+    pnpar.pts = d_pnpts; pnpar.walk = d_walk;
     wofdm_rparams rp{};
     rp.S = S; rp.k = k; rp.B = B; rp.T = T; rp.NL = cfg->noise_before_truncate ? T + L - 1 : S * B;
     rp.delta = delta; rp.gam = gam; rp.kap = cfg->circ_shift; rp.n_ch = cfg->n_channels; rp.n_snr = cfg->n_snr;
@@ -1880,6 +1925,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
             e = amp ? axp->rx_profile_pa(&pp, &rp, &spar, &papar, nullptr)
                 : dop ? ax->rx_profile_doppler(&pp, &rp, &spar, &dpar, nullptr)
                 : sync ? ax->rx_profile_sync(&pp, &rp, &spar, nullptr)
+                : pn ? ax->rx_profile_pn(&pp, &rp, &spar, &pnpar, nullptr)
                      : (nb ? ax->rx_profile_aci(&pp, &pa, &rp, &apar, nullptr) : ax->rx_profile(&pp, &rp, nullptr));
         }
         if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
@@ -1898,8 +1944,8 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     for (size_t i = 0; i < 2 * n_out; ++i) errs[i] += herr[i];
     if (err_power)
         for (size_t i = 0; i < n_out; ++i) err_power[i] += hpow[i];
-    uint64_t *sym_errs = sync ? sync->sym_errs : (dop ? dop->sym_errs : (amp ? amp->sym_errs : nullptr));
-    double *sym_power = sync ? sync->sym_power : (dop ? dop->sym_power : (amp ? amp->sym_power : nullptr));
+    uint64_t *sym_errs = sync ? sync->sym_errs : (dop ? dop->sym_errs : (amp ? amp->sym_errs : (pn ? pn->sym_errs : nullptr)));
+    double *sym_power = sync ? sync->sym_power : (dop ? dop->sym_power : (amp ? amp->sym_power : (pn ? pn->sym_power : nullptr)));
     if (sym_errs)
         for (size_t i = 0; i < 2 * n_sym; ++i) sym_errs[i] += hserr[i];
     if (sym_power)
@@ -1917,7 +1963,7 @@ extern "C" {
 int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                      const float *snr_db, const uint8_t *active, const float *tx_mask, uint64_t *errs, double *err_power)
 {
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -1925,7 +1971,7 @@ int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, co
                          const float *aci_h, int32_t aci_delay, float aci_level_db, uint64_t *errs, double *err_power)
 {
     const aci_args aci = {aci_active, aci_h, aci_delay, aci_level_db};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -1933,7 +1979,7 @@ int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, c
                           const wofdm_sync_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const sync_args sync = {n_points, points, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h_track,
@@ -1941,7 +1987,7 @@ int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device, const float *w_tx
                              const float *tx_mask, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const doppler_args dop = {h_track, n_tracks, n_knots, knot_step, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask, nullptr, nullptr, &dop, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask, nullptr, nullptr, &dop, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
@@ -1950,7 +1996,15 @@ int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device, const float *w_tx, con
                         double *pa_power)
 {
     const pa_args amp = {n_points, points, ref_power, sym_errs, sym_power, pa_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, &amp, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, &amp, nullptr, errs, err_power);
+}
+
+int wofdm_rx_profile_pn(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                        const uint8_t *active, const float *tx_mask, int32_t n_points, const wofdm_pn_point *points, uint64_t *errs,
+                        double *err_power, uint64_t *sym_errs, double *sym_power)
+{
+    const pn_args pn = {n_points, points, sym_errs, sym_power};
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, &pn, errs, err_power);
 }
 
 int wofdm_rx_profile_kernel_ms(float *ms)

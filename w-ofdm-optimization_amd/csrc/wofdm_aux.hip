@@ -1,6 +1,6 @@
 // wofdm_aux.hip -- the auxiliary kernels beside the frame kernel: closed-form ICI/ISI power (wofdm_interference,
 // wofdm_interference_masked) and Tx waveform + averaged periodogram (wofdm_tx_psd, wofdm_tx_psd_batch,
-// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile; beside an adjacent-band neighbour: wofdm_rx_profile_aci; under receiver timing and carrier offsets: wofdm_rx_profile_sync; over channels that move within the frame: wofdm_rx_profile_doppler; behind a nonlinear power amplifier: wofdm_rx_profile_pa, wofdm_tx_psd_batch_pa).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
+// wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile; beside an adjacent-band neighbour: wofdm_rx_profile_aci; under receiver timing and carrier offsets: wofdm_rx_profile_sync; over channels that move within the frame: wofdm_rx_profile_doppler; behind a nonlinear power amplifier: wofdm_rx_profile_pa, wofdm_tx_psd_batch_pa; under oscillator phase noise: wofdm_rx_profile_pn).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
 // on n_fft through the unit's table of launchers (wofdm_aux_fns).
 #include "wofdm_kernel.h"
 #include "wofdm_pa.h"
@@ -1019,7 +1019,7 @@ __global__ void __launch_bounds__(WOFDM_PAPR_WAVES * 64) wofdm_papr_period_kerne
 }
 
 // ---------------------------------------------------------------------------------------------
-// Per-subcarrier BER and EVM of the frames the BER loop runs (wofdm_rx_profile and its four arms _aci, _sync, _doppler, _pa:
+// Per-subcarrier BER and EVM of the frames the BER loop runs (wofdm_rx_profile and its five arms _aci, _sync, _doppler, _pa, _pn:
 // one body, rxprof_body<N, ARM> below, whose comment says what each arm adds): a second, unfused implementation of the
 // whole frame pipeline behind the Tx chain above,
 //   conv, add_wgn, truncate        matlab/main_BER_calculation.m:260-261, 277-294
@@ -1064,6 +1064,83 @@ __device__ __forceinline__ v2f rxp_noise(uint32_t a, uint32_t f_lo, uint32_t f_h
     sincospif(2.0f * u2, &sv, &cv);
     return mk(rad * cv, rad * sv);
 }
+// The four phase-walk increments of Philox block b of (seed, cell, frame): philox.h, stream 3 -- the complex unit normals
+// 2 b (words 0, 1) and 2 b + 1 (words 2, 3), real then imaginary part, are the increments of the on-air indices 4 b ... 4 b + 3.
+// u1 and u2 are rxp_noise's, formed in single precision (exact values: a 32-bit word times 2^-32 plus 2^-33 rounded once,
+// 23 bits times 2^-23); the Box-Muller step is in double precision.
+__device__ __forceinline__ void pn_increments(uint32_t b, uint32_t f_lo, uint32_t f_hi, uint32_t cell, uint32_t k0, uint32_t k1, double xi[4])
+{
+    const philox_out o = philox4x32_10(b, f_lo, f_hi, (WOFDM_STREAM_PN << 28) | cell, k0, k1);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const float u1 = fmaf((float)o.w[2 * e], 2.3283064365386963e-10f, 1.1641532182693481e-10f);
+        const float u2 = (float)(o.w[2 * e + 1] >> 9) * 1.1920928955078125e-07f;
+        const double rad = sqrt(-2.0 * log((double)u1));
+        double sv, cv;
+        sincospi(2.0 * (double)u2, &sv, &cv);
+        xi[2 * e] = rad * cv;
+        xi[2 * e + 1] = rad * sv;
+    }
+}
+// sum over the 64 lanes of a wave in double precision, in a fixed order: the butterfly over lane distances 1, 2, 4, ... 32
+// (both partners form the same sum, addition being commutative, so the result is wave-uniform to the bit)
+__device__ __forceinline__ double pn_wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The unit phase walks of wofdm_rx_profile_pn (wofdm_pnparams): one workgroup of 1024 threads per (cell, frame) item of the
+// chunk, walk[job][a] = xi[0] + ... + xi[a] for a < len = S B, in double precision.  Thread t owns the run
+// [t R, (t + 1) R) of on-air indices, R = 4 ceil(len / 4096): whole Philox blocks, each drawn once.  The order of additions is
+// fixed:
+//   1. the thread writes its increments to walk[] and adds them up, ascending from 0.0: its total;
+//   2. the exclusive prefix of the totals: inside a wave the inclusive scan over lane distances 1, 2, 4, ... 32 (a lane adds
+//      the partial sum of the lane that distance below it, where there is one); "lanes before" is the scan of the lane
+//      below, 0.0 for lane 0; "waves before" is the sum of the earlier waves' totals (lane 63's scan, through LDS), added
+//      in wave order from 0.0; prefix = (waves before) + (lanes before);
+//   3. the thread reads its increments back and adds them one by one onto its prefix, ascending; every partial sum is u[a].
+// rx_profile.pn_walk (a numpy cumsum in double) differs from it by the order of the additions only.
+__global__ void __launch_bounds__(1024) wofdm_pn_walk_kernel(double *__restrict__ walk, int len, uint32_t seed_lo, uint32_t seed_hi,
+                                                             uint64_t item0, uint64_t frames, uint64_t frame_offset)
+{
+    __shared__ double wtot[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t item = item0 + blockIdx.x, cell64 = item / frames, frame = frame_offset + (item - cell64 * frames);
+    const uint32_t cell = (uint32_t)cell64, f_lo = (uint32_t)frame, f_hi = (uint32_t)(frame >> 32);
+    double *__restrict__ u = walk + (size_t)blockIdx.x * (size_t)len;
+    const int R = 4 * ((len + 4095) / 4096), lo = tid * R, hi = lo + R < len ? lo + R : len;
+    double tot = 0.0;
+    for (int j = lo; j < hi; j += 4) {
+        double xi[4];
+        pn_increments((uint32_t)(j >> 2), f_lo, f_hi, cell, seed_lo, seed_hi, xi);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (j + e < hi) {
+                u[j + e] = xi[e];
+                tot += xi[e];
+            }
+    }
+    double inc = tot;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double below = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += below;
+    }
+    if (lane == 63) wtot[wv] = inc;
+    double lanes_before = __shfl_up(inc, 1, 64);
+    if (lane == 0) lanes_before = 0.0;
+    __syncthreads();
+    double waves_before = 0.0;
+    for (int w = 0; w < wv; ++w) waves_before += wtot[w];
+    double acc = waves_before + lanes_before;
+    for (int j = lo; j < hi; ++j) {
+        acc += u[j];
+        u[j] = acc;
+    }
+}
+
 // qamdemod, hard decision (main_BER_calculation.m:269-270): MATLAB Gray label of the nearest point
 __device__ __forceinline__ uint32_t rxp_slice(int k, float re, float im)
 {
@@ -1118,7 +1195,7 @@ __device__ __forceinline__ void fir_tap(const float2 hv, const float2 xv, float 
     ci = ci + im;
 }
 
-// The one body of the five receive kernels; ARM selects at compile time what an arm adds to the pipeline above, and the
+// The one body of the six receive kernels; ARM selects at compile time what an arm adds to the pipeline above, and the
 // parameters of the other arms are not read.
 //   RXP_PLAIN    wofdm_rx_profile: nothing.
 //   RXP_ACI      wofdm_rx_profile_aci: the wave stages a second row with the neighbour's samples under the same window -- the
@@ -1138,18 +1215,29 @@ __device__ __forceinline__ void fir_tap(const float2 hv, const float2 xv, float 
 //                for the lanes astride a knot.  LDS: LDS_DOP.
 //   RXP_PA       wofdm_rx_profile_pa: both passes once per point of pa (sp.n_points points) on the point's waveform,
 //                y[job][point] of wofdm_pa_wave_kernel, or x itself for a linear point, which so gives the plain kernel's bits.
+//   RXP_PN       wofdm_rx_profile_pn: pass 2 once per point of pn (sp.n_points points).  The received sample m of symbol s,
+//                signal and noise, is multiplied by e^{2 pi i t}, t the fraction of turn (u[a0 + m] - c) in double precision
+//                (t -= rint(t)), rounded to single for sincospif(2 t): u the item's unit walk (wofdm_pn_walk_kernel, read
+//                from global memory: LDS does not grow), turn = sigma / (2 pi) the point's, c = 0 for a free-running
+//                oscillator and, where the common phase error is tracked, the mean of u over the N + delta samples under
+//                the symbol's window, formed in double as u[a0] + (sum of u[a0 + m] - u[a0]) / (N + delta) -- a lane's
+//                samples m = lane, lane + 64, ... ascending, then pn_wave_sum.  |t| <= 1/2, so the rounding to single
+//                costs at most 2^-26 of a turn, 1e-7 rad, and sincospif some 1e-7 more: the rotation is good to about
+//                2e-7 rad for every beta and N, where the sync arm's in-window factor carries the rounding of eps m / N
+//                in single precision (which is what limits |cfo| there; no such limit here).  At beta = 0 turn = 0, t = 0
+//                exactly and the factor is exactly 1 under either flag: the point gives the plain kernel's bits.
 // The arms with a point loop (points, tracks) write the partials part_pow, part_cnt [job][point][N], and the wave of symbol
 // s >= 1 leaves beside them the symbol's sums over the loaded bins -- a lane's bins ascending, then papr_wave_reduce -- in
 // sym_pow, sym_cnt [job][point][S].  The pilot of a point sees what the point's data sees.  Where pass 1 runs per point, Ps
 // is the point's; Pn depends on neither channel nor waveform and is measured with the first.
-enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA };
+enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN };
 template <int N, int ARM>
 __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_aparams &ap, const wofdm_sparams &sp,
-                                            const wofdm_dparams &dp, const wofdm_paparams &pa)
+                                            const wofdm_dparams &dp, const wofdm_paparams &pa, const wofdm_pnparams &pn)
 {
     using RG = rxp_geo<N>;
-    constexpr bool ACI = ARM == RXP_ACI, SYNC = ARM == RXP_SYNC, DOP = ARM == RXP_DOPPLER, PA = ARM == RXP_PA;
-    constexpr bool POINTS = SYNC || DOP || PA, PASS1_PER_POINT = DOP || PA;
+    constexpr bool ACI = ARM == RXP_ACI, SYNC = ARM == RXP_SYNC, DOP = ARM == RXP_DOPPLER, PA = ARM == RXP_PA, PN = ARM == RXP_PN;
+    constexpr bool POINTS = SYNC || DOP || PA || PN, PASS1_PER_POINT = DOP || PA;
     constexpr int ROWLEN = N + (ACI ? 2 : 1) * RG::XROW;
     constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1171,6 +1259,7 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
     const float2 *__restrict__ taps = p.h + (size_t)ch * LT;
     const float2 *__restrict__ xi = ACI ? ap.xi + (size_t)job * ap.Ti : nullptr;
     const float2 *__restrict__ itaps = ACI ? ap.hi + (size_t)ch * LT : nullptr;
+    [[maybe_unused]] const double *__restrict__ walk = PN ? pn.walk + (size_t)job * (size_t)(S * B) : nullptr;
     for (int i = tid; i < N / 2; i += NT) {
         float sv, cv;
         sincospif(-2.0f * (float)i / (float)N, &sv, &cv);
@@ -1251,6 +1340,8 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
         // pass 2
         const int theta = SYNC ? sp.pts[pt].theta : 0;
         [[maybe_unused]] const float turn = SYNC ? sp.pts[pt].eps * (1.0f / (float)N) : 0.f;   // (exact: N is a power of two)
+        [[maybe_unused]] const double pn_turn = PN ? pn.pts[pt].turn : 0.0;
+        [[maybe_unused]] const bool pn_tracked = PN ? pn.pts[pt].tracked != 0 : false;
         const size_t slot = (size_t)job * NP + pt;
         float pw[BINS];
         uint32_t cnt[BINS];
@@ -1265,6 +1356,17 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
             if (live) {
                 const int a0 = s * B + p.gam + theta;                 // first sample under the Rx window (m:442-454)
                 [[maybe_unused]] const float2 bs = SYNC ? sp.base[(size_t)pt * S + s] : make_float2(1.f, 0.f);
+                // (PN) the walk under the window, a0 + m < S B, and the common phase the point takes off it
+                [[maybe_unused]] const double *__restrict__ uw = PN ? walk + a0 : nullptr;
+                [[maybe_unused]] double pn_c = 0.0;
+                if constexpr (PN) {
+                    if (pn_tracked) {
+                        const double u0 = uw[0];
+                        double acc = 0.0;
+                        for (int m = lane; m < N + delta; m += 64) acc += uw[m] - u0;
+                        pn_c = u0 + pn_wave_sum(acc) / (double)(N + delta);
+                    }
+                }
                 for (int i = lane; i < N + delta + LT - 1; i += 64) {
                     const int t = a0 - (LT - 1) + i;
                     xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
@@ -1300,6 +1402,12 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
                         sincospif(2.0f * tn, &sv, &cv);
                         const float qr = bs.x * cv - bs.y * sv, qi = bs.x * sv + bs.y * cv;
                         return make_float2(r.x * qr - r.y * qi, __builtin_fmaf(r.x, qi, r.y * qr));   // (r.x qi + r.y qr, written down likewise)
+                    } else if constexpr (PN) {                        // rotated by the oscillator's phase at a0 + m
+                        double td = (uw[m] - pn_c) * pn_turn;
+                        td -= rint(td);
+                        float sv, cv;
+                        sincospif(2.0f * (float)td, &sv, &cv);
+                        return make_float2(r.x * cv - r.y * sv, __builtin_fmaf(r.x, sv, r.y * cv));   // (the sync arm's forms)
                     } else {
                         return r;
                     }
@@ -1404,29 +1512,35 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(const wofdm_rparams p)
 {
-    rxprof_body<N, RXP_PLAIN>(p, wofdm_aparams{}, wofdm_sparams{}, wofdm_dparams{}, wofdm_paparams{});
+    rxprof_body<N, RXP_PLAIN>(p, wofdm_aparams{}, wofdm_sparams{}, wofdm_dparams{}, wofdm_paparams{}, wofdm_pnparams{});
 }
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_aci_kernel(const wofdm_rparams p, const wofdm_aparams ap)
 {
-    rxprof_body<N, RXP_ACI>(p, ap, wofdm_sparams{}, wofdm_dparams{}, wofdm_paparams{});
+    rxprof_body<N, RXP_ACI>(p, ap, wofdm_sparams{}, wofdm_dparams{}, wofdm_paparams{}, wofdm_pnparams{});
 }
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_sync_kernel(const wofdm_rparams p, const wofdm_sparams sp)
 {
-    rxprof_body<N, RXP_SYNC>(p, wofdm_aparams{}, sp, wofdm_dparams{}, wofdm_paparams{});
+    rxprof_body<N, RXP_SYNC>(p, wofdm_aparams{}, sp, wofdm_dparams{}, wofdm_paparams{}, wofdm_pnparams{});
 }
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_doppler_kernel(const wofdm_rparams p, const wofdm_sparams sp,
                                                                                      const wofdm_dparams dp)
 {
-    rxprof_body<N, RXP_DOPPLER>(p, wofdm_aparams{}, sp, dp, wofdm_paparams{});
+    rxprof_body<N, RXP_DOPPLER>(p, wofdm_aparams{}, sp, dp, wofdm_paparams{}, wofdm_pnparams{});
 }
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_pa_kernel(const wofdm_rparams p, const wofdm_sparams sp,
                                                                                 const wofdm_paparams pa)
 {
-    rxprof_body<N, RXP_PA>(p, wofdm_aparams{}, sp, wofdm_dparams{}, pa);
+    rxprof_body<N, RXP_PA>(p, wofdm_aparams{}, sp, wofdm_dparams{}, pa, wofdm_pnparams{});
+}
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_pn_kernel(const wofdm_rparams p, const wofdm_sparams sp,
+                                                                                const wofdm_pnparams pn)
+{
+    rxprof_body<N, RXP_PN>(p, wofdm_aparams{}, sp, wofdm_dparams{}, wofdm_paparams{}, pn);
 }
 
 // totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
@@ -1829,7 +1943,7 @@ hipError_t papr_launch(const wofdm_pparams *pp, hipStream_t s)
     return hipGetLastError();
 }
 
-// What the five receive-profile launchers share.  The chunk of r is the chunk of pp's Tx chain, within the receive kernel's geometry:
+// What the six receive-profile launchers share.  The chunk of r is the chunk of pp's Tx chain, within the receive kernel's geometry:
 bool rxprof_args_ok(const wofdm_pparams *pp, const wofdm_rparams &r)
 {
     constexpr int N = WOFDM_TU_N;
@@ -1975,6 +2089,30 @@ hipError_t rx_profile_pa_launch(const wofdm_pparams *pp, const wofdm_rparams *rp
     return hipGetLastError();
 }
 
+// wofdm_rx_profile_pn, one chunk: the Tx chain once, the items' unit phase walks, the receive kernel over the points, and
+// rx_profile_sync's ordered sums with the points as its points
+hipError_t rx_profile_pn_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, const wofdm_sparams *spp, const wofdm_pnparams *pnp,
+                                hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N;
+    const wofdm_rparams &r = *rp;
+    const wofdm_sparams &sp = *spp;
+    const wofdm_pnparams &pn = *pnp;
+    // (rxprof_args_ok: B = N + delta + gam, so the last sample under the last window is the walk's last, index S B - 1)
+    if (!rxprof_args_ok(pp, r) || !rxprof_points_ok(sp, r, WOFDM_PN_POINTS) || pn.pts == nullptr || pn.walk == nullptr)
+        return hipErrorInvalidValue;
+    hipError_t e = tx_chain_launch(*pp, s);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_pn_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                rxp_geo<N>::LDS);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_pn_walk_kernel, dim3((unsigned)r.n_jobs), dim3(1024), 0, s, pn.walk, r.S * r.B, r.seed_lo, r.seed_hi, r.item0,
+                       r.frames, r.frame_offset);
+    hipLaunchKernelGGL(wofdm_rxprof_pn_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r, sp, pn);
+    rxprof_reduce_launch(r, &sp, s);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
@@ -1988,11 +2126,11 @@ const wofdm_aux_fns *WOFDM_CAT(wofdm_aux_n, WOFDM_TU_N)(void)
 #if WOFDM_TU_N <= 256
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, psd_launch, psd_batch_launch, psd_batch_masked_launch,
                                       papr_launch, rx_profile_launch, rx_profile_aci_launch, rx_profile_sync_launch,
-                                      rx_profile_doppler_launch};
+                                      rx_profile_doppler_launch, rx_profile_pn_launch};
 #else
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, nullptr, psd_batch_launch, psd_batch_masked_launch,
                                       papr_launch, rx_profile_launch, rx_profile_aci_launch, rx_profile_sync_launch,
-                                      rx_profile_doppler_launch};
+                                      rx_profile_doppler_launch, rx_profile_pn_launch};
 #endif
     return &fns;
 }

@@ -558,6 +558,20 @@ struct wofdm_dparams {
     const float2 *knots;              // [n_tracks][n_ch][n_knots][WOFDM_LT], zero padded
     int32_t n_knots, knot_step;       // (n_knots - 1) knot_step >= T + n_taps - 2: the knots cover the frame
 };
+// The oscillator phase noise of wofdm_rx_profile_pn, a third argument of wofdm_rxprof_pn_kernel.  wofdm_pn_walk_kernel leaves
+// the unit walk of every item of the chunk in walk, u[a] = xi[0] + ... + xi[a] over the on-air indices a < S B a receiver at
+// timing 0 reads (xi: stream 3 of philox.h), once per frame whatever the number of points; the point scales it: the sample
+// at a is rotated by e^{i sigma u[a]}, or by e^{i sigma (u[a] - mean of u under the symbol's window)} where the common
+// phase error is tracked.  The points take the place of wofdm_sparams' points (pts and base of it are not read).
+#define WOFDM_PN_POINTS 16                 // WOFDM_PN_MAX_POINTS of include/wofdm.h
+struct wofdm_pnpoint {
+    double turn;                      // sigma / (2 pi) = sqrt(beta / (2 pi n_fft)) (host, double, from beta as stored)
+    int32_t tracked, pad;
+};
+struct wofdm_pnparams {
+    const wofdm_pnpoint *pts;         // [n_points]
+    double *walk;                     // [n_jobs][S B]
+};
 
 // the launchers of one DFT length
 struct wofdm_aux_fns {
@@ -600,6 +614,10 @@ struct wofdm_aux_fns {
     // wofdm_rxprof_doppler_kernel (pass 1 and pass 2 once per track of dp, sp->n_points tracks), and rx_profile_sync's sums.
     hipError_t (*rx_profile_doppler)(const wofdm_pparams *p, const wofdm_rparams *r, const wofdm_sparams *sp,
                                      const wofdm_dparams *dp, hipStream_t s);
+    // The same under oscillator phase noise (wofdm_rx_profile_pn): the Tx chain once, wofdm_pn_walk_kernel (the items' unit
+    // walks, once), wofdm_rxprof_pn_kernel (pass 1 once per item, pass 2 once per point of pn), and rx_profile_sync's sums.
+    hipError_t (*rx_profile_pn)(const wofdm_pparams *p, const wofdm_rparams *r, const wofdm_sparams *sp, const wofdm_pnparams *pn,
+                                hipStream_t s);
 };
 const wofdm_aux_fns *wofdm_aux_n64(void);
 const wofdm_aux_fns *wofdm_aux_n128(void);

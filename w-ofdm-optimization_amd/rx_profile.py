@@ -24,6 +24,10 @@ tracks (knots of the tap vector, linear in between) per call; ``tv_conv``, ``fra
 ``rx_profile_pa_gpu`` (``wofdm_rx_profile_pa``) is the profile behind a memoryless power amplifier (linear, Rapp, soft
 limiter), a list of ``PaPoint`` per call, with the power before and behind the amplifier; ``pa_gain``, ``pa_apply``,
 ``frame_profile_pa`` and ``rx_profile_pa_host`` mirror it, ``pa_ref_power`` measures the mean power the back-off counts from.
+
+``rx_profile_pn_gpu`` (``wofdm_rx_profile_pn``) is the profile under oscillator phase noise, the receiver's phase a random walk
+drawn from Philox stream 3, a list of ``PnPoint`` (linewidth, free-running or common phase error tracked) per call;
+``gen_pn_increments``, ``pn_walk``, ``frame_profile_pn`` and ``rx_profile_pn_host`` mirror it.
 """
 import collections
 
@@ -193,7 +197,7 @@ def _stream(seed, stream, cell, frame, n_blocks):
                    (stream << 28) | (int(cell) & 0x0FFFFFFF), seed & 0xFFFFFFFF, seed >> 32)
 
 
-STREAM_BITS, STREAM_NOISE, STREAM_ACI = 0, 1, 2           # csrc/philox.h
+STREAM_BITS, STREAM_NOISE, STREAM_ACI, STREAM_PN = 0, 1, 2, 3   # csrc/philox.h
 
 
 def gen_labels(n_fft, bits_per_sc, syms, seed, cell, frame, stream=0):
@@ -432,7 +436,7 @@ def rx_profile_aci_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db,
 
 def rx_profile_kernel_ms():
     """Milliseconds the kernels of this thread's last ``rx_profile_gpu``, ``rx_profile_aci_gpu``, ``rx_profile_sync_gpu``,
-    ``rx_profile_doppler_gpu`` or ``rx_profile_pa_gpu`` call took (``wofdm_rx_profile_kernel_ms``)."""
+    ``rx_profile_doppler_gpu``, ``rx_profile_pa_gpu`` or ``rx_profile_pn_gpu`` call took (``wofdm_rx_profile_kernel_ms``)."""
     import ctypes as C
     from . import _lib
     ms = C.c_float()
@@ -474,7 +478,14 @@ def _sync_point(st, front, noise_at, w_rx, point, bits_per_sc):
     inside = (a >= 0) & (a < conv.size)
     r = np.where(inside, conv[np.clip(a, 0, conv.size - 1)], 0.0) + g * np.asarray(noise_at(a), dtype=np.complex128)
     turns = eps * (m[None, :] if point.cfo_tracked else a).astype(np.float64) / n      # (exact: 24 bits times an integer)
-    blocks = r * np.exp(2j * np.pi * (turns - np.round(turns))) * np.asarray(w_rx, np.float64)[None, :]
+    return _point_outputs(st, X, on, r * np.exp(2j * np.pi * (turns - np.round(turns))), w_rx, k)
+
+
+def _point_outputs(st, X, on, r, w_rx, k):
+    """The receiver behind the oscillator, for the arms with a point loop: r [S, N + delta], the received samples under the
+    symbols' windows, rotated -> ``_sync_point``'s outputs"""
+    n, delta, S = st.n_fft, st.tail_rx, X.shape[0]
+    blocks = r * np.asarray(w_rx, np.float64)[None, :]
     z = blocks[:, :n].copy()
     z[:, :delta] += blocks[:, n:]
     Y = np.fft.fft(np.roll(z, -(st.circ_shift + delta // 2), axis=1), axis=1)
@@ -962,3 +973,180 @@ def pa_ref_power(st, bits_per_sc, syms, w_tx_pairs, seed, frame_offset, frames, 
                               for f in range(int(frames))])
             total[p] = T.frame_papr(st, grids, w[p], m)[..., 1].sum()
     return total / (int(frames) * S * B)
+
+
+# ---- under oscillator phase noise (wofdm_rx_profile_pn) ----
+
+PnPoint = collections.namedtuple("PnPoint", "linewidth cpe_tracked", defaults=(0,))
+PnPoint.__doc__ = """One oscillator of ``wofdm_rx_profile_pn``: linewidth (beta, the two-sided 3 dB width of its Lorentzian line
+in subcarrier spacings, 0 <= beta <= 1, used as stored in single precision: the phase walks with variance 2 pi beta / n_fft per
+sample), cpe_tracked (0: free-running; 1: a genie removes every symbol's common phase error)."""
+
+
+def _pn_prepare(points):
+    pts = [PnPoint(*q) for q in points]
+    pts = [PnPoint(float(np.float32(q.linewidth)), int(q.cpe_tracked)) for q in pts]
+    if not pts:
+        raise ValueError("at least one point is needed")
+    for q in pts:
+        if not 0.0 <= q.linewidth <= 1.0 or q.cpe_tracked not in (0, 1):
+            raise ValueError("a point needs 0 <= linewidth <= 1 and cpe_tracked in (0, 1): %r" % (q,))
+    return pts
+
+
+def gen_pn_increments(n, seed, cell, frame):
+    """[n] float64: the phase-walk increments xi[0 ... n) of stream 3 of (seed, cell, frame), csrc/philox.h -- real unit
+    normals, two per complex unit normal of the stream: complex index c = j >> 1 from block c >> 1, word pair c & 1 (the
+    layout of ``gen_noise`` on stream 1), the real part for even j, the imaginary part for odd j; the uniforms in single
+    precision as the kernels form them, Box-Muller in double."""
+    n = int(n)
+    nc = (n + 1) // 2
+    w = _stream(seed, STREAM_PN, cell, frame, (nc + 1) // 2).reshape(-1, 2)[:nc]
+    u1 = (w[:, 0].astype(np.float32).astype(np.float64) * 2.0 ** -32 + 2.0 ** -33).astype(np.float32).astype(np.float64)
+    u2 = (w[:, 1] >> np.uint64(9)).astype(np.float64) * 2.0 ** -23
+    rad = np.sqrt(-2.0 * np.log(u1))
+    return np.stack([rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)], axis=1).reshape(-1)[:n]
+
+
+def pn_walk(n, seed, cell, frame):
+    """[n] float64: the unit phase walk u[a] = xi[0] + ... + xi[a] of (seed, cell, frame), a < n -- what
+    ``wofdm_pn_walk_kernel`` leaves for the n = S B on-air indices a receiver at timing 0 reads, up to the order of the fp64
+    additions.  A point scales it by sigma = sqrt(2 pi linewidth / n_fft)."""
+    return np.cumsum(gen_pn_increments(n, seed, cell, frame))
+
+
+def _pn_point(st, front, noise_at, w_rx, walk, point, bits_per_sc, with_cpe=False):
+    """One point on a frame's shared part and its unit walk [S B]: ``_sync_point``'s outputs; with_cpe=True: also sigma and
+    the windows' mean walk ubar [S]"""
+    X, conv, g, on = front
+    n, delta, gam = st.n_fft, st.tail_rx, st.prefix_rm
+    S, B = X.shape[0], st.sym_len - st.tail_tx
+    q = _pn_prepare([point])[0]
+    u = np.asarray(walk, dtype=np.float64).reshape(-1)
+    if u.size < S * B:
+        raise ValueError("the walk holds %d samples, %d needed" % (u.size, S * B))
+    a = (np.arange(S, dtype=np.int64) * B + gam)[:, None] + np.arange(n + delta, dtype=np.int64)[None, :]   # all in [0, S B)
+    r = conv[a] + g * np.asarray(noise_at(a), dtype=np.complex128)
+    turn = np.sqrt(q.linewidth / (2.0 * np.pi * n))                   # sigma / (2 pi), from beta as stored
+    ubar = u[a[:, 0]] + np.mean(u[a] - u[a[:, :1]], axis=1)
+    t = (u[a] - ubar[:, None] if q.cpe_tracked else u[a]) * turn
+    out = _point_outputs(st, X, on, r * np.exp(2j * np.pi * (t - np.round(t))), w_rx, int(bits_per_sc))
+    return out + (2.0 * np.pi * turn, ubar) if with_cpe else out
+
+
+def frame_profile_pn(st, grids, unit_noise, w_tx, w_rx, h, walk, point, snr_db, bits_per_sc, active=None, mask=None,
+                     noise_before_truncate=1, with_y=False):
+    """fp64 host mirror of one frame and one point of ``wofdm_rx_profile_pn``: ``frame_profile`` with the receiver's oscillator
+    phase a random walk.  walk [>= S B]: the frame's unit walk (``pn_walk``); sample m of symbol s sits at a = s B + prefix_rm
+    + m and is multiplied, signal and noise, by e^{i sigma u[a]} (free-running) or e^{i sigma (u[a] - ubar_s)} (cpe_tracked),
+    sigma^2 = 2 pi linewidth / n_fft, ubar_s the mean of u over the N + tail_rx samples under the symbol's window, before the Rx
+    window; the noise gain never sees the phase and the pilot sees what the data sees.  unit_noise [noise_len] as
+    ``frame_profile``'s.  Returns what ``frame_profile_sync`` returns: (bit_err [N], sym_err [N], err_power [N], xhat [S-1, N],
+    y0 [N], bit_err_sym [S-1], sym_err_sym [S-1], err_power_sym [S-1]) -- the first five are ``frame_profile``'s, exactly, at
+    linewidth = 0 under either flag --; with_y=True: Y [S, N], sigma and ubar [S] as a ninth to eleventh."""
+    noise = np.asarray(unit_noise, dtype=np.complex128).reshape(-1)
+    hc = np.asarray(h, dtype=np.complex128).reshape(-1)
+    nl = _noise_len(st, np.asarray(grids).shape[0], hc.size, noise_before_truncate)
+    if noise.size < nl:
+        raise ValueError("unit_noise holds %d samples, %d needed" % (noise.size, nl))
+
+    def noise_at(idx):
+        return noise[np.asarray(idx, dtype=np.int64)]
+    front = _sync_front(st, grids, noise_at, w_tx, hc, snr_db, active, mask, noise_before_truncate)
+    out = _pn_point(st, front, noise_at, w_rx, walk, point, bits_per_sc, with_cpe=True)
+    return out if with_y else out[:8]
+
+
+def rx_profile_pn_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points,
+                       active=None, mask=None, noise_before_truncate=1, with_near=False):
+    """The host route of ``rx_profile_pn_gpu``: the frames of ``rx_profile_host`` from the same Philox streams, each through
+    ``frame_profile_pn`` for every point of ``points`` (``PnPoint`` or (linewidth, cpe_tracked) tuples); the Tx chain, the
+    channel, the noise gain and the unit walk (stream 3) of a frame are shared by its points.  Returns ``RxProfileSync``;
+    with_near=True: also the number of ``near_decisions`` per point and cell [points, pairs, n_snr, n_ch]."""
+    from . import timefreq as T
+    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts = _pn_prepare(points)
+    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, hc.shape[0], st.n_fft
+    k, S, B = int(bits_per_sc), int(syms), st.sym_len - st.tail_tx
+    tab = T.qam_table(k)
+    nl = max(_noise_len(st, S, hc.shape[1], noise_before_truncate), S * B)
+    on = np.ones(n, dtype=bool) if act is None else act != 0
+    shape = (len(pts), pairs, n_snr, n_ch)
+    bit = np.zeros(shape + (n,), dtype=np.uint64)
+    sym = np.zeros_like(bit)
+    pw = np.zeros(bit.shape, dtype=np.float64)
+    sbit = np.zeros(shape + (S - 1,), dtype=np.uint64)
+    ssym = np.zeros_like(sbit)
+    spw = np.zeros(sbit.shape, dtype=np.float64)
+    near = np.zeros(shape, dtype=np.int64)
+    for cell in range(pairs * n_snr * n_ch):
+        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
+        for f in range(int(frames)):
+            fr = int(frame_offset) + f
+            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
+            noise = gen_noise(nl, seed, cell, fr)
+            walk = pn_walk(S * B, seed, cell, fr)
+
+            def noise_at(idx, noise=noise):
+                return noise[np.asarray(idx, dtype=np.int64)]
+            front = _sync_front(st, grid, noise_at, w_tx[p], hc[c], snr[s], act, m, noise_before_truncate)
+            for i, q in enumerate(pts):
+                b, se, e, xhat, y0, sb, ss, sp = _pn_point(st, front, noise_at, w_rx[p], walk, q, k)[:8]
+                bit[i, p, s, c] += b
+                sym[i, p, s, c] += se
+                pw[i, p, s, c] += e
+                sbit[i, p, s, c] += sb
+                ssym[i, p, s, c] += ss
+                spw[i, p, s, c] += sp
+                if with_near:
+                    near[i, p, s, c] += int(near_decisions(k, xhat, y0).sum())
+    prof = RxProfileSync(bit, sym, pw, sbit, ssym, spw, _decisions(st, S, frames, act))
+    return (prof, near) if with_near else prof
+
+
+def rx_profile_pn_chunk_frames(st, syms, masked, n_points):
+    """Frames one chunk of ``wofdm_rx_profile_pn`` holds (include/wofdm.h): ``rx_profile_sync_chunk_frames``' bytes plus the
+    frame's unit walk, S B doubles; at most 65535."""
+    from . import _lib
+    P = st.sym_len
+    B = P - st.tail_tx
+    T = st.tail_tx + syms * B
+    per_frame = 8 * (syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0)) + 8 * syms * B + \
+        8 * int(n_points) * (st.n_fft + syms)
+    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+
+
+def rx_profile_pn_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points,
+                      active=None, mask=None, noise_before_truncate=1, device=0, out=None):
+    """``wofdm_rx_profile_pn``: ``rx_profile_gpu`` of the same arguments under oscillator phase noise, for every point of
+    ``points`` (``PnPoint`` or (linewidth, cpe_tracked) tuples, at most ``_lib.PN_MAX_POINTS``) in ONE call -- the Tx chain, the
+    power pass and the phase walk run once per frame, every point sees the same labels, noise and unit walk --, per subcarrier
+    and per data symbol.  Returns ``RxProfileSync``; ``out`` (an earlier result of the same shape) is accumulated into.  No
+    CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    from .simulation import make_cfg
+    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts = _pn_prepare(points)
+    cpts = (_lib.PnPoint * len(pts))(*[_lib.PnPoint(q.linewidth, q.cpe_tracked, (C.c_int32 * 2)(0, 0)) for q in pts])
+    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0]
+    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[1], n_ch, n_snr, pairs, bool(noise_before_truncate),
+                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
+    shape = (len(pts), pairs, n_snr, n_ch)
+    errs = np.zeros(shape + (st.n_fft, 2), dtype=np.uint64)
+    pw = np.zeros(shape + (st.n_fft,), dtype=np.float64)
+    serrs = np.zeros(shape + (int(syms) - 1, 2), dtype=np.uint64)
+    spw = np.zeros(shape + (int(syms) - 1,), dtype=np.float64)
+    hf = _lib.c64_as_f32(hc)
+    _lib.check(_lib.load().wofdm_rx_profile_pn(
+        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
+        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, len(pts), cpts, errs.ctypes.data,
+        pw.ctypes.data, serrs.ctypes.data, spw.ctypes.data))
+    prof = RxProfileSync(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
+                         np.ascontiguousarray(serrs[..., 0]), np.ascontiguousarray(serrs[..., 1]), spw,
+                         _decisions(st, syms, frames, act))
+    if out is not None:
+        if out.bit_err.shape != prof.bit_err.shape:
+            raise ValueError("out has another shape")
+        prof = RxProfileSync(*(a + b for a, b in zip(out, prof)))
+    return prof
