@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Developer tool (GPU box): the bytes of the five receive-profile entry points, as SHA-256 digests -- for comparing two
-builds of the library (WOFDM_LIB=... selects one; run the tool once per build and diff the outputs line for line).
+"""Developer tool: the bytes of the six receive-profile entry points, as SHA-256 digests -- for comparing two builds of the
+library (WOFDM_LIB=... selects one) or two versions of the Python layer above it: run the tool once per build or tree and diff
+the outputs line for line.  It uses the package's public names only, so the same file runs against either tree.
 
 It runs the tests' own cases with the tests' own frame counts, so the shapes are the smallest that reach S < W, S no multiple
 of W, W = 4 at N = 1024, the fold with and without an Rx tail and both noise orders:
@@ -9,19 +10,26 @@ of W, W = 4 at N = 1024, the fold with and without an Rx tail and both noise ord
   rx_profile_sync     CASES and points of tests/test_gpu_rx_profile_sync.py
   rx_profile_doppler  tests/doppler_cases.py CASES, and the extra steps and knot counts of its EXTRA case
   rx_profile_pa       tests/pa_cases.py
+  rx_profile_pn       CASES and POINTS of tests/test_gpu_rx_profile_pn.py
 and for each entry point the chunk-straddling shape of its test file (N = 1024, S = 16, cp + cs = 64, four chunks and a bit).
 The seeds are the cases' base seeds: the tests pick theirs with the oracle or the mirrors, which no digest needs.
 
-One JSON line per (entry point, case): {"entry", "case", "sha256": {field: digest of the array's bytes}}.  The bytes depend on
-the compiler, so a recorded output is a comparison of two builds, never a golden for the suite.
+--route gpu (the default, GPU box): the ``rx_profile_*_gpu`` functions.  --route host (any machine, no library, no GPU): the
+fp64 mirrors ``rx_profile_*_host`` with with_near=True on the same small cases, the near counts hashed as a field of their
+own, the pa arm's reference power from ``pa_ref_power(..., gpu=False)``; the chunk shapes are left out (chunking is a GPU
+notion, and they are too large for the mirror).  The seconds per case go to stderr, the slowest case last.
 
-    WOFDM_LIB=/path/to/libwofdm_hip.so python tools/rx_profile_digest.py [--out FILE]
+One JSON line per (entry point, case): {"entry", "case", "sha256": {field: digest of the array's bytes}}.  The bytes depend on
+the compiler, so a recorded output is a comparison of two runs, never a golden for the suite.
+
+    WOFDM_LIB=/path/to/libwofdm_hip.so python tools/rx_profile_digest.py [--route gpu|host] [--out FILE]
 """
 import argparse
 import hashlib
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -38,33 +46,64 @@ import rx_profile_cases as RC  # noqa: E402
 import test_gpu_rx_profile_aci as TA  # noqa: E402
 import test_gpu_rx_profile_doppler as TD  # noqa: E402
 import test_gpu_rx_profile_pa as TP  # noqa: E402
+import test_gpu_rx_profile_pn as TN  # noqa: E402
 import test_gpu_rx_profile_sync as TS  # noqa: E402
 
 
-def digests(prof):
-    return {f: hashlib.sha256(np.ascontiguousarray(getattr(prof, f)).tobytes()).hexdigest() for f in prof._fields}
+def host_plain(c, seed, frame_offset, frames):
+    return R.rx_profile_host(c["st"], c["k"], c["S"], c["w_tx"], c["w_rx"], c["h"], c["snr"], seed, frame_offset, frames,
+                             active=c["active"], mask=c["mask"], noise_before_truncate=c["nbt"], with_near=True)
 
 
-def runs():
-    """(entry, case, callable that returns the profile)"""
+def host_aci(c, seed, frame_offset, frames):
+    return R.rx_profile_aci_host(c["st"], c["k"], c["S"], c["w_tx"], c["w_rx"], c["h"], c["snr"], seed, frame_offset, frames,
+                                 c["aci_active"], c["delay"], c["level"], c["aci_h"], active=c["active"], mask=c["mask"],
+                                 noise_before_truncate=c["nbt"], with_near=True)
+
+
+#: entry -> (gpu route -> profile, host route -> (profile, near)), both (case, seed, frame_offset, frames, **kw)
+ROUTES = {
+    "rx_profile": (RC.run_gpu, host_plain),
+    "rx_profile_aci": (TA.run_gpu, host_aci),
+    "rx_profile_sync": (TS.run_gpu, TS.host),
+    "rx_profile_doppler": (TD.run_gpu, DC.host),
+    "rx_profile_pa": (TP.run_gpu, PC.host),
+    "rx_profile_pn": (TN.run_gpu, TN.host),
+}
+
+
+def digests(prof, near=None):
+    d = {f: hashlib.sha256(np.ascontiguousarray(getattr(prof, f)).tobytes()).hexdigest() for f in prof._fields}
+    if near is not None:
+        d["near"] = hashlib.sha256(np.ascontiguousarray(near).tobytes()).hexdigest()
+    return d
+
+
+def small_cases():
+    """(entry, case name, case, seed, extra keywords): RC.FRAMES frames each"""
     for i, n in enumerate(RC.NS):
         for variant in ("plain", "half_masked"):
             system = RC.SYSTEMS[(i + (variant != "plain")) % len(RC.SYSTEMS)]
             cp, S, k = RC.shape_of(n, system, variant)
             c = RC.make_case(W.make_structure(system, n, cp), k, S, variant, 2000 + n + RC.SYSTEMS.index(system))
-            yield "rx_profile", "n%d_%s_%s" % (n, system, variant), lambda c=c, n=n: RC.run_gpu(c, 10 * n, 0, RC.FRAMES)
+            yield "rx_profile", "n%d_%s_%s" % (n, system, variant), c, 10 * n, {}
     for j, name in enumerate(TA.CASES):
-        yield "rx_profile_aci", name, lambda name=name, j=j: TA.run_gpu(TA.case(name), 100 * (1 + j), 0, RC.FRAMES)
+        yield "rx_profile_aci", name, TA.case(name), 100 * (1 + j), {}
     for j, name in enumerate(TS.CASES):
-        yield "rx_profile_sync", name, lambda name=name, j=j: TS.run_gpu(TS.case(name), 100 * (1 + j), 0, RC.FRAMES)
+        yield "rx_profile_sync", name, TS.case(name), 100 * (1 + j), {}
     for j, name in enumerate(DC.CASES):
-        yield "rx_profile_doppler", name, lambda name=name, j=j: TD.run_gpu(DC.case(name), 100 * (1 + j), 0, RC.FRAMES)
-    for i, (tracks, step) in enumerate(DC.extra_tracks(DC.case(DC.EXTRA))):
-        yield ("rx_profile_doppler", "%s_step%d_knots%d" % (DC.EXTRA, step, tracks.shape[2]),
-               lambda tracks=tracks, step=step: TD.run_gpu(DC.case(DC.EXTRA), 100, 0, RC.FRAMES, tracks=tracks, knot_step=step))
+        yield "rx_profile_doppler", name, DC.case(name), 100 * (1 + j), {}
+    for tracks, step in DC.extra_tracks(DC.case(DC.EXTRA)):
+        yield ("rx_profile_doppler", "%s_step%d_knots%d" % (DC.EXTRA, step, tracks.shape[2]), DC.case(DC.EXTRA), 100,
+               dict(tracks=tracks, knot_step=step))
     for j, name in enumerate(PC.CASES):
-        yield "rx_profile_pa", name, lambda name=name, j=j: TP.run_gpu(PC.case(name), 100 * (1 + j), 0, RC.FRAMES)
-    # the chunk-straddling shape of the five test files: N = 1024, S = 16, cp + cs = 64, seed 7000
+        yield "rx_profile_pa", name, PC.case(name), 100 * (1 + j), {}
+    for j, name in enumerate(TN.CASES):
+        yield "rx_profile_pn", name, TN.case(name), 100 * (1 + j), {}
+
+
+def chunk_cases():
+    """(entry, case, frames, extra keywords): the chunk-straddling shape of the six test files, N = 1024, S = 16, cp + cs = 64"""
     st, S = W.make_structure("wtx", 1024, 56), 16
     big = RC.make_case(st, 4, S, "plain", 3001)
     half = CM.half_band_allocation(1024)
@@ -72,30 +111,53 @@ def runs():
     def frames_of(per_chunk):
         return per_chunk // 2 + 19
 
-    yield "rx_profile", "chunks", lambda: RC.run_gpu(big, 7000, 0, frames_of(R.rx_profile_chunk_frames(st, S, False)))
+    yield "rx_profile", big, frames_of(R.rx_profile_chunk_frames(st, S, False)), {}
     ca = dict(big, active=half, aci_active=~half, delay=501, level=0.0, aci_h=None)
-    yield "rx_profile_aci", "chunks", lambda: TA.run_gpu(ca, 7000, 0, frames_of(R.rx_profile_aci_chunk_frames(st, S, False)))
+    yield "rx_profile_aci", ca, frames_of(R.rx_profile_aci_chunk_frames(st, S, False)), {}
     cs = dict(big, active=half, points=[R.SyncPoint(0, 0.0, 1), R.SyncPoint(-40, 0.03, 0)])
-    yield "rx_profile_sync", "chunks", lambda: TS.run_gpu(cs, 7000, 0, frames_of(R.rx_profile_sync_chunk_frames(st, S, False, 2)))
+    yield "rx_profile_sync", cs, frames_of(R.rx_profile_sync_chunk_frames(st, S, False, 2)), {}
     cd = dict(big, active=half, knot_step=st.stride)
     cd["tracks"] = DC.tracks_of(cd, (0.0, 0.002), st.stride, S + 2)
-    yield "rx_profile_doppler", "chunks", lambda: TD.run_gpu(cd, 7000, 0, frames_of(R.rx_profile_doppler_chunk_frames(st, S, False, 2)))
+    yield "rx_profile_doppler", cd, frames_of(R.rx_profile_doppler_chunk_frames(st, S, False, 2)), {}
     cq = dict(big, active=half, name="over_the_frame_limit")
     pts, ref = (R.PaPoint(R.PA_LINEAR, 0.0), R.PaPoint(R.PA_RAPP, 3.0, 2.0)), np.full(RC.PAIRS, 1.0 / 1024, np.float32)
-    yield "rx_profile_pa", "chunks", lambda: TP.run_gpu(cq, 7000, 0, frames_of(R.rx_profile_pa_chunk_frames(st, S, False, 2)),
-                                                        points=pts, ref=ref)
+    yield "rx_profile_pa", cq, frames_of(R.rx_profile_pa_chunk_frames(st, S, False, 2)), dict(points=pts, ref=ref)
+    cn = dict(big, active=half, points=[R.PnPoint(0.0, 1), R.PnPoint(0.01, 0)])
+    yield "rx_profile_pn", cn, frames_of(R.rx_profile_pn_chunk_frames(st, S, False, 2)), {}
+
+
+def runs(route):
+    """(entry, case, callable that returns the digests)"""
+    for entry, name, c, seed, kw in small_cases():
+        if route == "host":
+            yield entry, name, lambda e=entry, c=c, s=seed, kw=kw: digests(*ROUTES[e][1](c, s, 0, RC.FRAMES, **kw))
+        else:
+            yield entry, name, lambda e=entry, c=c, s=seed, kw=kw: digests(ROUTES[e][0](c, s, 0, RC.FRAMES, **kw))
+    if route == "gpu":
+        # by entry point, the chunk shape behind its small cases (seed 7000)
+        for entry, c, frames, kw in chunk_cases():
+            yield entry, "chunks", lambda e=entry, c=c, f=frames, kw=kw: digests(ROUTES[e][0](c, 7000, 0, f, **kw))
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--route", choices=("gpu", "host"), default="gpu")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    for entry, case, call in runs():
-        line = json.dumps({"entry": entry, "case": case, "sha256": digests(call())}, sort_keys=True)
+    slowest = (0.0, None)
+    for entry, case, call in runs(args.route):
+        t0 = time.perf_counter()
+        line = json.dumps({"entry": entry, "case": case, "sha256": call()}, sort_keys=True)
+        dt = time.perf_counter() - t0
+        slowest = max(slowest, (dt, "%s %s" % (entry, case)))
         print(line, flush=True)
+        if args.route == "host":
+            print("%s %s: %.1f s" % (entry, case, dt), file=sys.stderr, flush=True)
         if args.out:
             with open(args.out, "a") as f:
                 f.write(line + "\n")
+    if args.route == "host":
+        print("slowest case: %s, %.1f s" % (slowest[1], slowest[0]), file=sys.stderr)
 
 
 if __name__ == "__main__":

@@ -67,6 +67,44 @@ def dft_rc_filt(rows, roll_off=ROLL_OFF):
     return out
 
 
+def _frames(ensemble, frame_range):
+    """(first frame, count): the whole ensemble, or ``frame_range`` as given"""
+    return (0, ensemble) if frame_range is None else frame_range
+
+
+def _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off=ROLL_OFF, rx=True):
+    """What every ``*_for_window_file`` function begins with: the structure (a tail only on the side the system windows), the
+    pair plan, the windows of every pair of the file + the RC pair, w_tx [pairs, P] and w_rx [pairs, N + delta], the half-band
+    allocation and the Tx mask.  rx=False (the Tx-side functions, whose window files need not hold the Rx windows): w_rx is
+    None."""
+    st = V.make_structure(type_ofdm, num_subcar, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
+                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
+    rc = (V.tx_rc_window(st), V.rx_rc_window(st))
+    plan = V.matlab_pair_plan(type_ofdm)
+
+    def stack(side):
+        return np.stack([rc[side] if k[side] == "rc" else np.asarray(windows[k[side]], dtype=np.float64) for _, k in plan])
+    return st, plan, stack(0), stack(1) if rx else None, half_band_allocation(num_subcar), tx_mask(st.sym_len, roll_off)
+
+
+def _profiles_per_pair(arm, plan, alloc, mask, head, ensemble, frame_range, gpu, device, tail=(), tail_masked=None, **kw):
+    """What the receive-profile functions end with: ``rx_profile.rx_profile<arm>_gpu`` (gpu=False: ``..._host``, which takes
+    no device) on the frames of ``_frames``, plain and masked, and the result per pair of the plan -- {name: {"profile",
+    "profile_masked"}}, each the route's namedtuple without the pair axis.  head: the arguments before (first, count); tail:
+    the arm's own behind them (tail_masked: those of the masked call, where they differ); kw: its keywords."""
+    from . import rx_profile as R
+    first, count = _frames(ensemble, frame_range)
+    run = getattr(R, "rx_profile%s_%s" % (arm, "gpu" if gpu else "host"))
+    kw = dict(kw, active=alloc, **(dict(device=device) if gpu else {}))
+    plain = run(*head, first, count, *tail, **kw)
+    masked = run(*head, first, count, *(tail if tail_masked is None else tail_masked), mask=mask, **kw)
+
+    def of_pair(prof, i):
+        # (RxProfile's arrays begin with the pair axis, the others' with the point or track axis)
+        return type(prof)(*(a[i] if type(prof) is R.RxProfile else a[:, i] for a in prof[:-1]), prof.decisions)
+    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
+
+
 def run_sim_mc(system, n_fft, cp, w_tx, w_rx, channels, snr_db, ensemble, bits_per_subcar=4,
                symbols_per_tx=16, tail_tx=None, tail_rx=None, roll_off=ROLL_OFF, seed=0, device=0,
                frame_range=None):
@@ -80,7 +118,7 @@ def run_sim_mc(system, n_fft, cp, w_tx, w_rx, channels, snr_db, ensemble, bits_p
     snr = np.atleast_1d(np.asarray(snr_db, dtype=np.float64))
     cfg = S.make_cfg(st, bits_per_subcar, symbols_per_tx, h.shape[1], h.shape[0], snr.size,
                      w_tx.shape[0], noise_before_truncate=True, seed=seed)
-    lo, n = (0, ensemble) if frame_range is None else frame_range
+    lo, n = _frames(ensemble, frame_range)
     with S.Plan(cfg, w_tx, w_rx, h.astype(np.complex64), snr.astype(np.float32), device=device) as plan:
         plan.set_allocation(half_band_allocation(n_fft))
         plain = plan.run(lo, n)
@@ -97,17 +135,8 @@ def ber_for_window_file(type_ofdm, cp, windows, channels, snr_db, num_subcar=256
     pair, plain and masked.  Returns ({variable name: BER vs SNR}, (counts_masked, counts_plain))
     with the saved variable names of lines 287-330 (``berSNR``, ``berMaskedSNR``, ``berRCSNR``,
     ``berMaskedRCSNR``, ``ber[Masked]SNRStep{1,2,3}{A,B}``)."""
-    st = V.make_structure(type_ofdm, num_subcar, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
-                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
-    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
-    plan = V.matlab_pair_plan(type_ofdm)
-
-    def pick(key, side):
-        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
-
+    st, plan, w_tx, w_rx, _, _ = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx)
     names = [n for n, _ in plan]
-    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
-    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
     masked, plain = run_sim_mc(type_ofdm, num_subcar, cp, w_tx, w_rx, channels, snr_db, ensemble,
                                bits_per_subcar, symbols_per_tx, st.tail_tx, st.tail_rx, seed=seed,
                                device=device, frame_range=frame_range)
@@ -126,19 +155,13 @@ def spectrum_for_window_file(type_ofdm, cp, windows, num_subcar=256, symbols=Non
     "f_axis"}} with the names of ``V.matlab_pair_plan``."""
     from . import timefreq as T
     n = num_subcar
-    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
-                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
-    alloc = half_band_allocation(n)
+    st, plan, wins, _, alloc, mask = _window_file_setup(type_ofdm, cp, windows, n, tail_tx, tail_rx, roll_off, rx=False)
     if symbols is None:
         rng = np.random.RandomState() if rng is None else rng
         symbols = rng.choice(T.SYMBOLS_16QAM, size=(int(alloc.sum()), T.NO_SYMBOLS), replace=True)
     symbols = np.asarray(symbols)
     grid = np.zeros((n, symbols.shape[1]), dtype=np.complex128)
     grid[alloc] = symbols
-    rc_tx = V.tx_rc_window(st)
-    plan = V.matlab_pair_plan(type_ofdm)
-    wins = [rc_tx if k[0] == "rc" else np.asarray(windows[k[0]], dtype=np.float64) for _, k in plan]
-    mask = tx_mask(st.sym_len, roll_off)
     overlap = st.tail_tx
     fft_len = 8 * n
     if gpu:
@@ -169,20 +192,8 @@ def interference_for_window_file(type_ofdm, cp, windows, channels, num_subcar=25
     {"power", "power_masked", "wanted", "wanted_masked"}}, each [n_channels][N], with the names of
     ``V.matlab_pair_plan``; SIR per subcarrier = wanted / power on the loaded bins (both are 0 on the others)."""
     from . import interference as I
-    n = num_subcar
-    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
-                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
-    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
-    plan = V.matlab_pair_plan(type_ofdm)
-
-    def pick(key, side):
-        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
-
-    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
-    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off)
     h = np.atleast_2d(np.asarray(channels))
-    alloc = half_band_allocation(n)
-    mask = tx_mask(st.sym_len, roll_off)
     if gpu:
         plain = I.interf_power_masked_gpu(st, w_tx, w_rx, h, active=alloc, device=device)
         masked = I.interf_power_masked_gpu(st, w_tx, w_rx, h, active=alloc, mask=mask, device=device)
@@ -209,14 +220,8 @@ def papr_for_window_file(type_ofdm, cp, windows, num_subcar=256, bits_per_subcar
     "max_db", "max_db_masked", "edges_db"}} with the names of ``V.matlab_pair_plan``; ccdf[i] = Pr(PAPR >= edges_db[i])."""
     from . import timefreq as T
     n = num_subcar
-    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
-                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
-    rc_tx = V.tx_rc_window(st)
-    plan = V.matlab_pair_plan(type_ofdm)
-    w_tx = np.stack([rc_tx if k[0] == "rc" else np.asarray(windows[k[0]], dtype=np.float64) for _, k in plan])
-    alloc = half_band_allocation(n)
-    mask = tx_mask(st.sym_len, roll_off)
-    first, count = (0, ensemble) if frame_range is None else frame_range
+    st, plan, w_tx, _, alloc, mask = _window_file_setup(type_ofdm, cp, windows, n, tail_tx, tail_rx, roll_off, rx=False)
+    first, count = _frames(ensemble, frame_range)
     if gpu:
         plain = T.tx_papr_gpu(st, bits_per_subcar, symbols_per_tx, w_tx, seed, first, count, active=alloc, lo_db=lo_db,
                               step_db=step_db, n_bins=n_bins, device=device)
@@ -256,33 +261,9 @@ def profile_for_window_file(type_ofdm, cp, windows, channels, snr_db, num_subcar
     cover the SAME frame range: bits and noise are those of the cell, so the two profiles differ by the mask alone.
     Returns {name: {"profile", "profile_masked"}} with the names of ``V.matlab_pair_plan``; each is an
     ``rx_profile.RxProfile`` of that pair, arrays [n_snr, n_channels, N] (``rx_profile.ber_per_bin``, ``evm_db``)."""
-    from . import rx_profile as R
-    n = num_subcar
-    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
-                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
-    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
-    plan = V.matlab_pair_plan(type_ofdm)
-
-    def pick(key, side):
-        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
-
-    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
-    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
-    h = np.atleast_2d(np.asarray(channels))
-    alloc = half_band_allocation(n)
-    mask = tx_mask(st.sym_len, roll_off)
-    first, count = (0, ensemble) if frame_range is None else frame_range
-    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, h, snr_db, seed, first, count)
-    if gpu:
-        plain = R.rx_profile_gpu(*args, active=alloc, device=device)
-        masked = R.rx_profile_gpu(*args, active=alloc, mask=mask, device=device)
-    else:
-        plain = R.rx_profile_host(*args, active=alloc)
-        masked = R.rx_profile_host(*args, active=alloc, mask=mask)
-
-    def of_pair(prof, i):
-        return R.RxProfile(prof.bit_err[i], prof.sym_err[i], prof.err_power[i], prof.decisions)
-    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off)
+    head = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.atleast_2d(np.asarray(channels)), snr_db, seed)
+    return _profiles_per_pair("", plan, alloc, mask, head, ensemble, frame_range, gpu, device)
 
 
 def aci_for_window_file(type_ofdm, cp, windows, channels, snr_db, delays, level_db=0.0, aci_channels=None, num_subcar=256,
@@ -299,35 +280,14 @@ def aci_for_window_file(type_ofdm, cp, windows, channels, snr_db, delays, level_
     with the same arguments, so the two results differ by the neighbour alone.
     Returns {name: {delay: {"profile", "profile_masked"}}} with the names of ``V.matlab_pair_plan``; each an
     ``rx_profile.RxProfile`` of that pair, arrays [n_snr, n_channels, N]."""
-    from . import rx_profile as R
-    n = num_subcar
-    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
-                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
-    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
-    plan = V.matlab_pair_plan(type_ofdm)
-
-    def pick(key, side):
-        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
-
-    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
-    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
-    h = np.atleast_2d(np.asarray(channels))
-    alloc = half_band_allocation(n)
-    mask = tx_mask(st.sym_len, roll_off)
-    first, count = (0, ensemble) if frame_range is None else frame_range
-    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, h, snr_db, seed, first, count, ~alloc)
-    kw = dict(aci_level_db=level_db, aci_h=aci_channels, active=alloc)
-    run = R.rx_profile_aci_gpu if gpu else R.rx_profile_aci_host
-    if gpu:
-        kw["device"] = device
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off)
+    head = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.atleast_2d(np.asarray(channels)), snr_db, seed)
     out = {name: {} for name, _ in plan}
     for d in delays:
-        plain = run(*args, int(d), **kw)
-        masked = run(*args, int(d), mask=mask, **kw)
-        for i, (name, _) in enumerate(plan):
-            out[name][int(d)] = {"profile": R.RxProfile(plain.bit_err[i], plain.sym_err[i], plain.err_power[i], plain.decisions),
-                                 "profile_masked": R.RxProfile(masked.bit_err[i], masked.sym_err[i], masked.err_power[i],
-                                                               masked.decisions)}
+        per_pair = _profiles_per_pair("_aci", plan, alloc, mask, head, ensemble, frame_range, gpu, device, tail=(~alloc, int(d)),
+                                      aci_level_db=level_db, aci_h=aci_channels)
+        for name, _ in plan:
+            out[name][int(d)] = per_pair[name]
     return out
 
 
@@ -343,31 +303,9 @@ def sync_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_s
     same arguments, so the point (0, 0) is its result.
     Returns {name: {"profile", "profile_masked"}} with the names of ``V.matlab_pair_plan``; each an
     ``rx_profile.RxProfileSync`` of that pair, arrays [points, n_snr, n_channels, N] and [points, n_snr, n_channels, S - 1]."""
-    from . import rx_profile as R
-    n = num_subcar
-    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
-                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
-    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
-    plan = V.matlab_pair_plan(type_ofdm)
-
-    def pick(key, side):
-        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
-
-    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
-    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
-    h = np.atleast_2d(np.asarray(channels))
-    alloc = half_band_allocation(n)
-    mask = tx_mask(st.sym_len, roll_off)
-    first, count = (0, ensemble) if frame_range is None else frame_range
-    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, h, snr_db, seed, first, count, list(points))
-    run = R.rx_profile_sync_gpu if gpu else R.rx_profile_sync_host
-    kw = dict(active=alloc, device=device) if gpu else dict(active=alloc)
-    plain = run(*args, **kw)
-    masked = run(*args, mask=mask, **kw)
-
-    def of_pair(prof, i):
-        return R.RxProfileSync(*(a[:, i] for a in prof[:6]), prof.decisions)
-    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off)
+    head = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.atleast_2d(np.asarray(channels)), snr_db, seed)
+    return _profiles_per_pair("_sync", plan, alloc, mask, head, ensemble, frame_range, gpu, device, tail=(list(points),))
 
 
 def pn_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_subcar=256, bits_per_subcar=4, symbols_per_tx=16,
@@ -382,31 +320,9 @@ def pn_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_sub
     the same arguments, so a point of linewidth 0 is its result.
     Returns {name: {"profile", "profile_masked"}} with the names of ``V.matlab_pair_plan``; each an
     ``rx_profile.RxProfileSync`` of that pair, arrays [points, n_snr, n_channels, N] and [points, n_snr, n_channels, S - 1]."""
-    from . import rx_profile as R
-    n = num_subcar
-    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
-                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
-    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
-    plan = V.matlab_pair_plan(type_ofdm)
-
-    def pick(key, side):
-        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
-
-    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
-    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
-    h = np.atleast_2d(np.asarray(channels))
-    alloc = half_band_allocation(n)
-    mask = tx_mask(st.sym_len, roll_off)
-    first, count = (0, ensemble) if frame_range is None else frame_range
-    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, h, snr_db, seed, first, count, list(points))
-    run = R.rx_profile_pn_gpu if gpu else R.rx_profile_pn_host
-    kw = dict(active=alloc, device=device) if gpu else dict(active=alloc)
-    plain = run(*args, **kw)
-    masked = run(*args, mask=mask, **kw)
-
-    def of_pair(prof, i):
-        return R.RxProfileSync(*(a[:, i] for a in prof[:6]), prof.decisions)
-    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off)
+    head = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.atleast_2d(np.asarray(channels)), snr_db, seed)
+    return _profiles_per_pair("_pn", plan, alloc, mask, head, ensemble, frame_range, gpu, device, tail=(list(points),))
 
 
 def doppler_for_window_file(type_ofdm, cp, windows, tracks, knot_step, snr_db, num_subcar=256, bits_per_subcar=4,
@@ -422,30 +338,9 @@ def doppler_for_window_file(type_ofdm, cp, windows, tracks, knot_step, snr_db, n
     ``profile_for_window_file`` with the same arguments, so a track whose knots all equal its channel is that result.
     Returns {name: {"profile", "profile_masked"}} with the names of ``V.matlab_pair_plan``; each an
     ``rx_profile.RxProfileSync`` of that pair, arrays [tracks, n_snr, n_channels, N] and [tracks, n_snr, n_channels, S - 1]."""
-    from . import rx_profile as R
-    n = num_subcar
-    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
-                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
-    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
-    plan = V.matlab_pair_plan(type_ofdm)
-
-    def pick(key, side):
-        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
-
-    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
-    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
-    alloc = half_band_allocation(n)
-    mask = tx_mask(st.sym_len, roll_off)
-    first, count = (0, ensemble) if frame_range is None else frame_range
-    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.asarray(tracks), knot_step, snr_db, seed, first, count)
-    run = R.rx_profile_doppler_gpu if gpu else R.rx_profile_doppler_host
-    kw = dict(active=alloc, device=device) if gpu else dict(active=alloc)
-    plain = run(*args, **kw)
-    masked = run(*args, mask=mask, **kw)
-
-    def of_pair(prof, i):
-        return R.RxProfileSync(*(a[:, i] for a in prof[:6]), prof.decisions)
-    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off)
+    head = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.asarray(tracks), knot_step, snr_db, seed)
+    return _profiles_per_pair("_doppler", plan, alloc, mask, head, ensemble, frame_range, gpu, device)
 
 
 def pa_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_subcar=256, bits_per_subcar=4, symbols_per_tx=16,
@@ -468,29 +363,15 @@ def pa_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_sub
     from . import rx_profile as R
     from . import timefreq as T
     n = num_subcar
-    st = V.make_structure(type_ofdm, n, cp, tail_tx if type_ofdm in V.TX_WINDOWED else 0,
-                          tail_rx if type_ofdm in V.RX_WINDOWED else 0)
-    rc = {"tx": V.tx_rc_window(st), "rx": V.rx_rc_window(st)}
-    plan = V.matlab_pair_plan(type_ofdm)
-
-    def pick(key, side):
-        return rc[side] if key == "rc" else np.asarray(windows[key], dtype=np.float64)
-
-    w_tx = np.stack([pick(k[0], "tx") for _, k in plan])
-    w_rx = np.stack([pick(k[1], "rx") for _, k in plan])
-    h = np.atleast_2d(np.asarray(channels))
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, n, tail_tx, tail_rx, roll_off)
     pts = [R._pa_point(q) for q in points]
-    alloc = half_band_allocation(n)
-    mask = tx_mask(st.sym_len, roll_off)
-    first, count = (0, ensemble) if frame_range is None else frame_range
+    first, count = _frames(ensemble, frame_range)
     # the receive route: the mean power per pair, then one call per system
     ref = [R.pa_ref_power(st, bits_per_subcar, symbols_per_tx, w_tx, seed, first, count, active=alloc, mask=m, gpu=gpu,
                           **(dict(device=device) if gpu else {})) for m in (None, mask)]
-    args = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, h, snr_db, seed, first, count, pts)
-    run = R.rx_profile_pa_gpu if gpu else R.rx_profile_pa_host
-    kw = dict(active=alloc, device=device) if gpu else dict(active=alloc)
-    plain = run(*args, ref[0], **kw)
-    masked = run(*args, ref[1], mask=mask, **kw)
+    head = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.atleast_2d(np.asarray(channels)), snr_db, seed)
+    out = _profiles_per_pair("_pa", plan, alloc, mask, head, ensemble, frame_range, gpu, device, tail=(pts, ref[0]),
+                             tail_masked=(pts, ref[1]))
     # the spectrum route: every (pair, system, point) as one job
     if symbols is None:
         rng = np.random.RandomState() if rng is None else rng
@@ -507,13 +388,11 @@ def pa_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_sub
     ests = np.asarray(ests).reshape(len(plan), 2, len(pts), fft_len)
     unloaded = np.fft.fftshift(np.repeat(~alloc, fft_len // n))
     f_axis = np.linspace(-.5, .5 - 1 / fft_len, fft_len) / 200e-9
-
-    def of_pair(prof, i):
-        return R.RxProfilePa(*(a[:, i] for a in prof[:7]), prof.decisions)
-    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i), "psd": ests[i, 0], "psd_masked": ests[i, 1],
-                   "obr": ests[i, 0][:, unloaded].mean(axis=1), "obr_masked": ests[i, 1][:, unloaded].mean(axis=1),
-                   "ref_power": ref[0][i], "ref_power_masked": ref[1][i], "f_axis": f_axis}
-            for i, (name, _) in enumerate(plan)}
+    for i, (name, _) in enumerate(plan):
+        out[name].update({"psd": ests[i, 0], "psd_masked": ests[i, 1], "obr": ests[i, 0][:, unloaded].mean(axis=1),
+                          "obr_masked": ests[i, 1][:, unloaded].mean(axis=1), "ref_power": ref[0][i],
+                          "ref_power_masked": ref[1][i], "f_axis": f_axis})
+    return out
 
 
 def results_from_counts(names, masked, plain):

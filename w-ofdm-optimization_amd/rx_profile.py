@@ -260,36 +260,134 @@ def _decisions(st, syms, frames, act):
     return np.where(on, int(frames) * (int(syms) - 1), 0).astype(np.uint64)
 
 
-def rx_profile_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, active=None,
-                    mask=None, noise_before_truncate=1, with_near=False):
-    """The host route of ``rx_profile_gpu``: the same frames from the same Philox streams, each through
-    ``frame_profile`` (single-precision inputs as the GPU receives them, fp64 arithmetic).  with_near=True: also the
-    number of ``near_decisions`` per cell [pairs, n_snr, n_ch]."""
+# ---- the host sweep and the GPU call every arm goes through ----
+
+#: what ``_host_sweep`` hands an arm: the prepared arguments (single precision, as the GPU receives them), k, S, the noise
+#: samples a frame needs (``_noise_len``) and the seed
+_Sweep = collections.namedtuple("_Sweep", "st k S w_tx w_rx hc snr act m nbt noise_len seed")
+
+
+def _host_sweep(result, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, active, mask,
+                noise_before_truncate, with_near):
+    """The host route of every arm: the cells (pair, SNR point, channel) of the sweep and their frames [frame_offset,
+    frame_offset + frames), the labels of stream 0 drawn per frame, the sums kept per field of ``result`` (a namedtuple type
+    whose last field is ``decisions``: per bin [N], ``*_sym`` per data symbol [S - 1], ``pa_power`` [2]; the counters uint64,
+    the powers float64, added up frame by frame).  arm(q: ``_Sweep``) does the arm's own argument preparation and returns
+    (lead, frame): lead = () or (n_points,), the leading axis of every sum, and frame(p, s, c, cell, fr, grid) -> per point
+    one tuple (bit_err, sym_err, err_power, xhat, y0, then the further fields of ``result`` in its order; anything behind is
+    ignored), for which the arm draws what the frame needs beyond the labels.  Returns ``result``, and with_near=True also the
+    number of ``near_decisions`` per point and cell."""
     from . import timefreq as T
     w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
     pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, hc.shape[0], st.n_fft
     k, S = int(bits_per_sc), int(syms)
+    lead, frame = arm(_Sweep(st, k, S, w_tx, w_rx, hc, snr, act, m, noise_before_truncate,
+                             _noise_len(st, S, hc.shape[1], noise_before_truncate), seed))
     tab = T.qam_table(k)
-    nl = _noise_len(st, S, hc.shape[1], noise_before_truncate)
     on = np.ones(n, dtype=bool) if act is None else act != 0
-    bit = np.zeros((pairs, n_snr, n_ch, n), dtype=np.uint64)
-    sym = np.zeros_like(bit)
-    pw = np.zeros(bit.shape, dtype=np.float64)
-    near = np.zeros((pairs, n_snr, n_ch), dtype=np.int64)
+    shape = lead + (pairs, n_snr, n_ch)
+    sums = [np.zeros(shape + ((2,) if f == "pa_power" else (S - 1,) if f.endswith("_sym") else (n,)),
+                     dtype=np.float64 if "power" in f else np.uint64) for f in result._fields[:-1]]
+    near = np.zeros(shape, dtype=np.int64)
     for cell in range(pairs * n_snr * n_ch):
         p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
         for f in range(int(frames)):
             fr = int(frame_offset) + f
             grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
-            b, se, e, xhat, y0 = frame_profile(st, grid, gen_noise(nl, seed, cell, fr), w_tx[p], w_rx[p], hc[c],
-                                               snr[s], k, act, m, noise_before_truncate)
-            bit[p, s, c] += b
-            sym[p, s, c] += se
-            pw[p, s, c] += e
-            if with_near:
-                near[p, s, c] += int(near_decisions(k, xhat, y0).sum())
-    prof = RxProfile(bit, sym, pw, _decisions(st, S, frames, act))
+            for i, o in enumerate(frame(p, s, c, cell, fr, grid)):
+                at = (i, p, s, c) if lead else (p, s, c)
+                for a, v in zip(sums, o[:3] + o[5:]):
+                    a[at] += v
+                if with_near:
+                    near[at] += int(near_decisions(k, o[3], o[4]).sum())
+    prof = result(*sums, _decisions(st, S, frames, act))
     return (prof, near) if with_near else prof
+
+
+def _plain_arm(q):
+    """``rx_profile_host``'s arm: the frame's unit noise, ``frame_profile``"""
+    def frame(p, s, c, cell, fr, grid):
+        return [frame_profile(q.st, grid, gen_noise(q.noise_len, q.seed, cell, fr), q.w_tx[p], q.w_rx[p], q.hc[c], q.snr[s],
+                              q.k, q.act, q.m, q.nbt)]
+    return (), frame
+
+
+def rx_profile_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, active=None,
+                    mask=None, noise_before_truncate=1, with_near=False):
+    """The host route of ``rx_profile_gpu``: the same frames from the same Philox streams, each through
+    ``frame_profile`` (single-precision inputs as the GPU receives them, fp64 arithmetic).  with_near=True: also the
+    number of ``near_decisions`` per cell [pairs, n_snr, n_ch]."""
+    return _host_sweep(RxProfile, _plain_arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames,
+                       active, mask, noise_before_truncate, with_near)
+
+
+def _noise_lookup(noise, lo=0):
+    """noise_at(idx) of ``_sync_front`` and the point functions on a frame's samples [lo, lo + len(noise))"""
+    def noise_at(idx):
+        return noise[np.asarray(idx, dtype=np.int64) - lo]
+    return noise_at
+
+
+def _unit_noise_lookup(st, grids, unit_noise, n_taps, noise_before_truncate):
+    """The same on the ``unit_noise`` argument of a frame mirror, which must hold the frame's ``_noise_len`` samples"""
+    noise = np.asarray(unit_noise, dtype=np.complex128).reshape(-1)
+    nl = _noise_len(st, np.asarray(grids).shape[0], n_taps, noise_before_truncate)
+    if noise.size < nl:
+        raise ValueError("unit_noise holds %d samples, %d needed" % (noise.size, nl))
+    return _noise_lookup(noise)
+
+
+def _chunk_frames(st, syms, masked, per_point=0, n_points=0, per_frame_extra=0, neighbour=False):
+    """Frames one chunk holds: the byte budget of include/wofdm.h (``job_bytes`` of rx_profile_impl) over the bytes of a frame
+    -- 8 per element: the symbol grid [S, N], the waveform [T], masked the filtered symbols [S, 2P - 1]; with a neighbour
+    its grid [S + 1, N], waveform [T + B] and filtered symbols; ``per_frame_extra`` elements of the arm's own; ``per_point``
+    elements (the partial sums, a waveform) for each of ``n_points`` --, at least 1, at most 65535."""
+    from . import _lib
+    P, B = st.sym_len, st.sym_len - st.tail_tx
+    T = st.tail_tx + syms * B
+    words = syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0)
+    if neighbour:
+        words += (syms + 1) * st.n_fft + T + B + ((syms + 1) * (2 * P - 1) if masked else 0)
+    per_frame = 8 * (words + per_frame_extra + int(n_points) * per_point)
+    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+
+
+def _gpu_call(entry, result, st, bits_per_sc, syms, prepared, seed, frame_offset, frames, noise_before_truncate, device, out,
+              lead=(), after_h=(), after_mask=(), n_ch=None):
+    """One call of the library's receive-profile entry point ``entry``: prepared = ``_prepare``'s six (the fifth argument of
+    the entry point is prepared[2], of any rank, taps last; n_ch: its channels where they are not its first axis); after_h,
+    after_mask: the arm's own ctypes arguments, behind h and behind the mask; lead = () or (n_points,).  The outputs are
+    those ``result`` has fields for -- the {bit, symbol} counters and the power per bin; with ``*_sym`` fields the same per
+    data symbol; with ``pa_power`` the power sums --, each behind the leading axes lead + (pairs, n_snr, n_ch).  Returns
+    ``result``, added to ``out`` (an earlier result of the same shape) where given."""
+    import ctypes as C
+    from . import _lib
+    from .simulation import make_cfg
+    w_tx, w_rx, hc, snr, act, m = prepared
+    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0] if n_ch is None else n_ch
+    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[-1], n_ch, n_snr, pairs, bool(noise_before_truncate),
+                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
+    shape = tuple(lead) + (pairs, n_snr, n_ch)
+    tails = [(st.n_fft,)] + [(int(syms) - 1,)] * ("bit_err_sym" in result._fields)
+    outs = []
+    for tail in tails:
+        outs += [np.zeros(shape + tail + (2,), dtype=np.uint64), np.zeros(shape + tail, dtype=np.float64)]
+    if "pa_power" in result._fields:
+        outs.append(np.zeros(shape + (2,), dtype=np.float64))
+    hf = _lib.c64_as_f32(hc)
+    _lib.check(getattr(_lib.load(), entry)(
+        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, *after_h, snr.ctypes.data,
+        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, *after_mask,
+        *(a.ctypes.data for a in outs)))
+    fields = []
+    for a in outs:
+        fields += [np.ascontiguousarray(a[..., 0]), np.ascontiguousarray(a[..., 1])] if a.dtype == np.uint64 else [a]
+    prof = result(*fields, _decisions(st, syms, frames, act))
+    if out is not None:
+        if out.bit_err.shape != prof.bit_err.shape:
+            raise ValueError("out has another shape")
+        prof = result(*(a + b for a, b in zip(out, prof)))
+    return prof
 
 
 # ---- GPU ----
@@ -297,11 +395,7 @@ def rx_profile_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, se
 def rx_profile_chunk_frames(st, syms, masked):
     """Frames one chunk of ``wofdm_rx_profile`` holds (include/wofdm.h: WOFDM_RX_PROFILE_CHUNK_BYTES over the bytes of a
     frame's symbol grid, waveform, -- masked -- filtered symbols and per-bin partial sums; at most 65535)."""
-    from . import _lib
-    P = st.sym_len
-    T = st.tail_tx + syms * (P - st.tail_tx)
-    per_frame = 8 * (syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0) + st.n_fft)
-    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+    return _chunk_frames(st, syms, masked, per_point=st.n_fft, n_points=1)
 
 
 def rx_profile_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, active=None,
@@ -311,28 +405,9 @@ def rx_profile_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, see
     [n_snr] x h [n_ch, taps] -- drawn as a ``Plan`` of the same cfg and seed draws them, with the allocation ``active`` [N]
     and the Tx mask ``mask`` [2P-1].  Returns ``RxProfile``; ``out`` (an earlier result of the same shape) is accumulated
     into, its ``decisions`` added up.  No CPU fallback."""
-    import ctypes as C
-    from . import _lib
-    from .simulation import make_cfg
-    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
-    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0]
-    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[1], n_ch, n_snr, pairs, bool(noise_before_truncate),
-                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
-    shape = (pairs, n_snr, n_ch, st.n_fft)
-    errs = np.zeros(shape + (2,), dtype=np.uint64)
-    pw = np.zeros(shape, dtype=np.float64)
-    hf = _lib.c64_as_f32(hc)
-    _lib.check(_lib.load().wofdm_rx_profile(
-        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
-        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, errs.ctypes.data, pw.ctypes.data))
-    prof = RxProfile(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
-                     _decisions(st, syms, frames, act))
-    if out is not None:
-        if out.bit_err.shape != shape:
-            raise ValueError("out has another shape")
-        prof = RxProfile(out.bit_err + prof.bit_err, out.sym_err + prof.sym_err, out.err_power + prof.err_power,
-                         out.decisions + prof.decisions)
-    return prof
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    return _gpu_call("wofdm_rx_profile", RxProfile, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                     noise_before_truncate, device, out)
 
 
 # ---- beside an adjacent-band neighbour (wofdm_rx_profile_aci) ----
@@ -354,49 +429,27 @@ def rx_profile_aci_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db
     stream 2 on ``aci_active`` beside each, through ``frame_profile_aci``.  An ``aci_active`` without a loaded bin is
     ``rx_profile_host``.  with_near=True: also the number of ``near_decisions`` per cell [pairs, n_snr, n_ch]."""
     from . import timefreq as T
-    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
-    iact, hi, d, lvl = _prepare_aci(st, hc, aci_active, aci_h, aci_delay, aci_level_db)
-    if not iact.any():
-        return rx_profile_host(st, bits_per_sc, syms, w_tx, w_rx, hc, snr, seed, frame_offset, frames, act, m,
-                               noise_before_truncate, with_near)
-    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, hc.shape[0], st.n_fft
-    k, S = int(bits_per_sc), int(syms)
-    tab = T.qam_table(k)
-    nl = _noise_len(st, S, hc.shape[1], noise_before_truncate)
-    on = np.ones(n, dtype=bool) if act is None else act != 0
-    bit = np.zeros((pairs, n_snr, n_ch, n), dtype=np.uint64)
-    sym = np.zeros_like(bit)
-    pw = np.zeros(bit.shape, dtype=np.float64)
-    near = np.zeros((pairs, n_snr, n_ch), dtype=np.int64)
-    for cell in range(pairs * n_snr * n_ch):
-        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
-        for f in range(int(frames)):
-            fr = int(frame_offset) + f
-            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
-            igrid = tab[gen_labels(n, k, S + 1, seed, cell, fr, STREAM_ACI)] * (iact != 0)[None, :]
-            b, se, e, xhat, y0 = frame_profile_aci(st, grid, igrid, gen_noise(nl, seed, cell, fr), w_tx[p], w_rx[p], hc[c],
-                                                   None if hi is None else hi[c], d, lvl, snr[s], k, act, m,
-                                                   noise_before_truncate)
-            bit[p, s, c] += b
-            sym[p, s, c] += se
-            pw[p, s, c] += e
-            if with_near:
-                near[p, s, c] += int(near_decisions(k, xhat, y0).sum())
-    prof = RxProfile(bit, sym, pw, _decisions(st, S, frames, act))
-    return (prof, near) if with_near else prof
+
+    def arm(q):
+        iact, hi, d, lvl = _prepare_aci(st, q.hc, aci_active, aci_h, aci_delay, aci_level_db)
+        if not iact.any():
+            return _plain_arm(q)
+        tab = T.qam_table(q.k)
+
+        def frame(p, s, c, cell, fr, grid):
+            igrid = tab[gen_labels(st.n_fft, q.k, q.S + 1, seed, cell, fr, STREAM_ACI)] * (iact != 0)[None, :]
+            return [frame_profile_aci(st, grid, igrid, gen_noise(q.noise_len, seed, cell, fr), q.w_tx[p], q.w_rx[p], q.hc[c],
+                                      None if hi is None else hi[c], d, lvl, q.snr[s], q.k, q.act, q.m, q.nbt)]
+        return (), frame
+    return _host_sweep(RxProfile, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames,
+                       active, mask, noise_before_truncate, with_near)
 
 
 def rx_profile_aci_chunk_frames(st, syms, masked):
     """Frames one chunk of ``wofdm_rx_profile_aci`` holds with a neighbour (include/wofdm.h: both symbol grids, S and S + 1
     symbols, both waveforms, T and T + B samples, -- masked -- both sets of filtered symbols, the per-bin partials; at most
     65535).  Without one (an empty ``aci_active``) the call chunks as ``rx_profile_chunk_frames``."""
-    from . import _lib
-    P = st.sym_len
-    B = P - st.tail_tx
-    T = st.tail_tx + syms * B
-    per_frame = 8 * (syms * st.n_fft + (syms + 1) * st.n_fft + T + (T + B) + ((2 * syms + 1) * (2 * P - 1) if masked else 0)
-                     + st.n_fft)
-    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+    return _chunk_frames(st, syms, masked, per_point=st.n_fft, n_points=1, neighbour=True)
 
 
 def rx_profile_aci_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, aci_active,
@@ -407,31 +460,13 @@ def rx_profile_aci_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db,
     symbol u beginning at victim time (u - 1) B + ``aci_delay`` (0 <= aci_delay < B), amplitude 10^(aci_level_db / 20),
     through ``aci_h`` [n_ch, taps] (None: h).  The SNR stays the victim's.  Returns ``RxProfile`` on the victim's loaded
     bins; ``out`` is accumulated into.  No CPU fallback."""
-    import ctypes as C
     from . import _lib
-    from .simulation import make_cfg
-    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
-    iact, hi, d, lvl = _prepare_aci(st, hc, aci_active, aci_h, aci_delay, aci_level_db)
-    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0]
-    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[1], n_ch, n_snr, pairs, bool(noise_before_truncate),
-                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
-    shape = (pairs, n_snr, n_ch, st.n_fft)
-    errs = np.zeros(shape + (2,), dtype=np.uint64)
-    pw = np.zeros(shape, dtype=np.float64)
-    hf = _lib.c64_as_f32(hc)
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    iact, hi, d, lvl = _prepare_aci(st, prepared[2], aci_active, aci_h, aci_delay, aci_level_db)
     hif = None if hi is None else _lib.c64_as_f32(hi)
-    _lib.check(_lib.load().wofdm_rx_profile_aci(
-        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
-        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, iact.ctypes.data,
-        None if hif is None else hif.ctypes.data, d, lvl, errs.ctypes.data, pw.ctypes.data))
-    prof = RxProfile(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
-                     _decisions(st, syms, frames, act))
-    if out is not None:
-        if out.bit_err.shape != shape:
-            raise ValueError("out has another shape")
-        prof = RxProfile(out.bit_err + prof.bit_err, out.sym_err + prof.sym_err, out.err_power + prof.err_power,
-                         out.decisions + prof.decisions)
-    return prof
+    return _gpu_call("wofdm_rx_profile_aci", RxProfile, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                     noise_before_truncate, device, out,
+                     after_mask=(iact.ctypes.data, None if hif is None else hif.ctypes.data, d, lvl))
 
 
 def rx_profile_kernel_ms():
@@ -528,57 +563,26 @@ def rx_profile_sync_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_d
     ``frame_profile_sync`` for every point of ``points`` (``SyncPoint`` or (timing, cfo, cfo_tracked) tuples); the Tx chain,
     the channel and the noise gain of a frame are shared by its points.  Returns ``RxProfileSync``; with_near=True: also the
     number of ``near_decisions`` per point and cell [points, pairs, n_snr, n_ch]."""
-    from . import timefreq as T
-    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
-    pts = _prepare_sync(points)
-    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, hc.shape[0], st.n_fft
-    k, S, B = int(bits_per_sc), int(syms), st.sym_len - st.tail_tx
-    tab = T.qam_table(k)
-    nl = _noise_len(st, S, hc.shape[1], noise_before_truncate)
-    on = np.ones(n, dtype=bool) if act is None else act != 0
-    # the sample indices a frame's points read, as one range
-    lo = min(0, st.prefix_rm + min(q.timing for q in pts))
-    hi = max(nl, (S - 1) * B + st.prefix_rm + max(q.timing for q in pts) + n + st.tail_rx)
-    shape = (len(pts), pairs, n_snr, n_ch)
-    bit = np.zeros(shape + (n,), dtype=np.uint64)
-    sym = np.zeros_like(bit)
-    pw = np.zeros(bit.shape, dtype=np.float64)
-    sbit = np.zeros(shape + (S - 1,), dtype=np.uint64)
-    ssym = np.zeros_like(sbit)
-    spw = np.zeros(sbit.shape, dtype=np.float64)
-    near = np.zeros(shape, dtype=np.int64)
-    for cell in range(pairs * n_snr * n_ch):
-        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
-        for f in range(int(frames)):
-            fr = int(frame_offset) + f
-            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
-            noise = gen_noise_at(np.arange(lo, hi, dtype=np.int64), seed, cell, fr)
+    def arm(q):
+        pts = _prepare_sync(points)
+        # the sample indices a frame's points read, as one range
+        lo = min(0, st.prefix_rm + min(pt.timing for pt in pts))
+        hi = max(q.noise_len, (q.S - 1) * (st.sym_len - st.tail_tx) + st.prefix_rm + max(pt.timing for pt in pts) + st.n_fft
+                 + st.tail_rx)
 
-            def noise_at(idx, noise=noise):
-                return noise[np.asarray(idx, dtype=np.int64) - lo]
-            front = _sync_front(st, grid, noise_at, w_tx[p], hc[c], snr[s], act, m, noise_before_truncate)
-            for i, q in enumerate(pts):
-                b, se, e, xhat, y0, sb, ss, sp = _sync_point(st, front, noise_at, w_rx[p], q, k)[:8]
-                bit[i, p, s, c] += b
-                sym[i, p, s, c] += se
-                pw[i, p, s, c] += e
-                sbit[i, p, s, c] += sb
-                ssym[i, p, s, c] += ss
-                spw[i, p, s, c] += sp
-                if with_near:
-                    near[i, p, s, c] += int(near_decisions(k, xhat, y0).sum())
-    prof = RxProfileSync(bit, sym, pw, sbit, ssym, spw, _decisions(st, S, frames, act))
-    return (prof, near) if with_near else prof
+        def frame(p, s, c, cell, fr, grid):
+            noise_at = _noise_lookup(gen_noise_at(np.arange(lo, hi, dtype=np.int64), seed, cell, fr), lo)
+            front = _sync_front(st, grid, noise_at, q.w_tx[p], q.hc[c], q.snr[s], q.act, q.m, q.nbt)
+            return (_sync_point(st, front, noise_at, q.w_rx[p], pt, q.k)[:8] for pt in pts)
+        return (len(pts),), frame
+    return _host_sweep(RxProfileSync, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames,
+                       active, mask, noise_before_truncate, with_near)
 
 
 def rx_profile_sync_chunk_frames(st, syms, masked, n_points):
     """Frames one chunk of ``wofdm_rx_profile_sync`` holds (include/wofdm.h: the symbol grid, the waveform and -- masked -- the
     filtered symbols of a frame, and per point its per-bin and per-symbol partials; at most 65535)."""
-    from . import _lib
-    P = st.sym_len
-    T = st.tail_tx + syms * (P - st.tail_tx)
-    per_frame = 8 * (syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0)) + 8 * int(n_points) * (st.n_fft + syms)
-    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+    return _chunk_frames(st, syms, masked, per_point=st.n_fft + syms, n_points=n_points)
 
 
 def rx_profile_sync_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points,
@@ -587,33 +591,12 @@ def rx_profile_sync_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db
     (``SyncPoint`` or (timing, cfo, cfo_tracked) tuples, at most ``_lib.SYNC_MAX_POINTS``) in ONE call -- the Tx chain and the
     power pass run once per frame --, per subcarrier and per data symbol.  Returns ``RxProfileSync``; ``out`` (an earlier
     result of the same shape) is accumulated into.  No CPU fallback."""
-    import ctypes as C
     from . import _lib
-    from .simulation import make_cfg
-    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
     pts = _prepare_sync(points)
     cpts = (_lib.SyncPoint * len(pts))(*[_lib.SyncPoint(q.timing, q.cfo, q.cfo_tracked, 0) for q in pts])
-    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0]
-    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[1], n_ch, n_snr, pairs, bool(noise_before_truncate),
-                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
-    shape = (len(pts), pairs, n_snr, n_ch)
-    errs = np.zeros(shape + (st.n_fft, 2), dtype=np.uint64)
-    pw = np.zeros(shape + (st.n_fft,), dtype=np.float64)
-    serrs = np.zeros(shape + (int(syms) - 1, 2), dtype=np.uint64)
-    spw = np.zeros(shape + (int(syms) - 1,), dtype=np.float64)
-    hf = _lib.c64_as_f32(hc)
-    _lib.check(_lib.load().wofdm_rx_profile_sync(
-        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
-        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, len(pts), cpts, errs.ctypes.data,
-        pw.ctypes.data, serrs.ctypes.data, spw.ctypes.data))
-    prof = RxProfileSync(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
-                         np.ascontiguousarray(serrs[..., 0]), np.ascontiguousarray(serrs[..., 1]), spw,
-                         _decisions(st, syms, frames, act))
-    if out is not None:
-        if out.bit_err.shape != prof.bit_err.shape:
-            raise ValueError("out has another shape")
-        prof = RxProfileSync(*(a + b for a, b in zip(out, prof)))
-    return prof
+    return _gpu_call("wofdm_rx_profile_sync", RxProfileSync, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                     noise_before_truncate, device, out, lead=(len(pts),), after_mask=(len(pts), cpts))
 
 
 # ---- over a channel that moves within the frame (wofdm_rx_profile_doppler) ----
@@ -649,14 +632,7 @@ def frame_profile_doppler(st, grids, unit_noise, w_tx, w_rx, track, knot_step, s
     Returns what ``frame_profile_sync`` returns: (bit_err [N], sym_err [N], err_power [N], xhat [S-1, N], y0 [N], bit_err_sym
     [S-1], sym_err_sym [S-1], err_power_sym [S-1]) -- the first five are ``frame_profile``'s, exactly, on a track whose knots
     all equal h --; with_y=True: Y [S, N] as a ninth."""
-    noise = np.asarray(unit_noise, dtype=np.complex128).reshape(-1)
-    S, B = np.asarray(grids).shape[0], st.sym_len - st.tail_tx
-    nl = _noise_len(st, S, np.asarray(track).shape[-1], noise_before_truncate)
-    if noise.size < nl:
-        raise ValueError("unit_noise holds %d samples, %d needed" % (noise.size, nl))
-
-    def noise_at(idx):
-        return noise[np.asarray(idx, dtype=np.int64)]
+    noise_at = _unit_noise_lookup(st, grids, unit_noise, np.asarray(track).shape[-1], noise_before_truncate)
     front = _sync_front(st, grids, noise_at, w_tx, None, snr_db, active, mask, noise_before_truncate,
                         channel=lambda x: tv_conv(track, knot_step, x))
     out = _sync_point(st, front, noise_at, w_rx, SyncPoint(0, 0.0, 1), bits_per_sc)
@@ -678,41 +654,16 @@ def rx_profile_doppler_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, track
     the track's row); the labels, the Tx waveform and the noise of a frame are shared by its tracks.  Returns
     ``RxProfileSync`` with a leading track axis; with_near=True: also the number of ``near_decisions`` per track and cell
     [n_tracks, pairs, n_snr, n_ch]."""
-    from . import timefreq as T
     tr = _prepare_tracks(tracks)
-    w_tx, w_rx, _, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, tr[0, :, 0], snr_db, active, mask)
-    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, tr.shape[1], st.n_fft
-    k, S = int(bits_per_sc), int(syms)
-    tab = T.qam_table(k)
-    nl = _noise_len(st, S, tr.shape[3], noise_before_truncate)
-    on = np.ones(n, dtype=bool) if act is None else act != 0
-    shape = (tr.shape[0], pairs, n_snr, n_ch)
-    bit = np.zeros(shape + (n,), dtype=np.uint64)
-    sym = np.zeros_like(bit)
-    pw = np.zeros(bit.shape, dtype=np.float64)
-    sbit = np.zeros(shape + (S - 1,), dtype=np.uint64)
-    ssym = np.zeros_like(sbit)
-    spw = np.zeros(sbit.shape, dtype=np.float64)
-    near = np.zeros(shape, dtype=np.int64)
-    for cell in range(pairs * n_snr * n_ch):
-        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
-        for f in range(int(frames)):
-            fr = int(frame_offset) + f
-            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
-            noise = gen_noise(nl, seed, cell, fr)
-            for i in range(tr.shape[0]):
-                b, se, e, xhat, y0, sb, ss, sp = frame_profile_doppler(st, grid, noise, w_tx[p], w_rx[p], tr[i, c], knot_step,
-                                                                       snr[s], k, act, m, noise_before_truncate)
-                bit[i, p, s, c] += b
-                sym[i, p, s, c] += se
-                pw[i, p, s, c] += e
-                sbit[i, p, s, c] += sb
-                ssym[i, p, s, c] += ss
-                spw[i, p, s, c] += sp
-                if with_near:
-                    near[i, p, s, c] += int(near_decisions(k, xhat, y0).sum())
-    prof = RxProfileSync(bit, sym, pw, sbit, ssym, spw, _decisions(st, S, frames, act))
-    return (prof, near) if with_near else prof
+
+    def arm(q):
+        def frame(p, s, c, cell, fr, grid):
+            noise = gen_noise(q.noise_len, seed, cell, fr)
+            return (frame_profile_doppler(st, grid, noise, q.w_tx[p], q.w_rx[p], tr[i, c], knot_step, q.snr[s], q.k, q.act, q.m,
+                                          q.nbt) for i in range(tr.shape[0]))
+        return (tr.shape[0],), frame
+    return _host_sweep(RxProfileSync, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, tr[0, :, 0], snr_db, seed, frame_offset,
+                       frames, active, mask, noise_before_truncate, with_near)
 
 
 def rx_profile_doppler_chunk_frames(st, syms, masked, n_tracks):
@@ -729,32 +680,11 @@ def rx_profile_doppler_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, tracks
     call -- the Tx chain runs once per frame, every track sees the same labels and noise --, per subcarrier and per data
     symbol.  Returns the ``RxProfileSync`` tuple with a leading track axis; ``out`` (an earlier result of the same shape) is
     accumulated into.  No CPU fallback."""
-    import ctypes as C
-    from . import _lib
-    from .simulation import make_cfg
     tr = _prepare_tracks(tracks)
     w_tx, w_rx, _, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, tr[0, :, 0], snr_db, active, mask)
-    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, tr.shape[1]
-    cfg = make_cfg(st, int(bits_per_sc), int(syms), tr.shape[3], n_ch, n_snr, pairs, bool(noise_before_truncate),
-                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
-    shape = (tr.shape[0], pairs, n_snr, n_ch)
-    errs = np.zeros(shape + (st.n_fft, 2), dtype=np.uint64)
-    pw = np.zeros(shape + (st.n_fft,), dtype=np.float64)
-    serrs = np.zeros(shape + (int(syms) - 1, 2), dtype=np.uint64)
-    spw = np.zeros(shape + (int(syms) - 1,), dtype=np.float64)
-    hf = _lib.c64_as_f32(tr)
-    _lib.check(_lib.load().wofdm_rx_profile_doppler(
-        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, tr.shape[0], tr.shape[2], int(knot_step),
-        snr.ctypes.data, None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, errs.ctypes.data,
-        pw.ctypes.data, serrs.ctypes.data, spw.ctypes.data))
-    prof = RxProfileSync(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
-                         np.ascontiguousarray(serrs[..., 0]), np.ascontiguousarray(serrs[..., 1]), spw,
-                         _decisions(st, syms, frames, act))
-    if out is not None:
-        if out.bit_err.shape != prof.bit_err.shape:
-            raise ValueError("out has another shape")
-        prof = RxProfileSync(*(a + b for a, b in zip(out, prof)))
-    return prof
+    return _gpu_call("wofdm_rx_profile_doppler", RxProfileSync, st, bits_per_sc, syms, (w_tx, w_rx, tr, snr, act, m), seed,
+                     frame_offset, frames, noise_before_truncate, device, out, lead=(tr.shape[0],),
+                     after_h=(tr.shape[0], tr.shape[2], int(knot_step)), n_ch=tr.shape[1])
 
 
 # ---- behind a nonlinear power amplifier (wofdm_rx_profile_pa) ----
@@ -824,16 +754,9 @@ def frame_profile_pa(st, grids, unit_noise, w_tx, w_rx, h, point, ref_power, snr
     (bit_err [N], sym_err [N], err_power [N], xhat [S-1, N], y0 [N], bit_err_sym [S-1], sym_err_sym [S-1], err_power_sym [S-1],
     pa_power [2] = {sum |x|^2, sum |y|^2}) -- the first five are ``frame_profile``'s, exactly, on a ``PA_LINEAR`` point --;
     with_y=True: Y [S, N] as a tenth."""
-    noise = np.asarray(unit_noise, dtype=np.complex128).reshape(-1)
     hc = np.asarray(h, dtype=np.complex128).reshape(-1)
-    S = np.asarray(grids).shape[0]
-    nl = _noise_len(st, S, hc.size, noise_before_truncate)
-    if noise.size < nl:
-        raise ValueError("unit_noise holds %d samples, %d needed" % (noise.size, nl))
+    noise_at = _unit_noise_lookup(st, grids, unit_noise, hc.size, noise_before_truncate)
     power = np.zeros(2)
-
-    def noise_at(idx):
-        return noise[np.asarray(idx, dtype=np.int64)]
 
     def channel(x):
         y = pa_apply(x, point, ref_power)
@@ -860,53 +783,23 @@ def rx_profile_pa_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db,
     ``frame_profile_pa`` for every point of ``points`` with the reference power ``ref_power`` [pairs] of the cell's window pair
     (single precision, as the GPU receives it); the labels and the noise of a frame are shared by its points.  Returns
     ``RxProfilePa``; with_near=True: also the number of ``near_decisions`` per point and cell [points, pairs, n_snr, n_ch]."""
-    from . import timefreq as T
-    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
-    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, hc.shape[0], st.n_fft
-    pts, ref = _prepare_pa(points, ref_power, pairs)
-    k, S = int(bits_per_sc), int(syms)
-    tab = T.qam_table(k)
-    nl = _noise_len(st, S, hc.shape[1], noise_before_truncate)
-    on = np.ones(n, dtype=bool) if act is None else act != 0
-    shape = (len(pts), pairs, n_snr, n_ch)
-    bit = np.zeros(shape + (n,), dtype=np.uint64)
-    sym = np.zeros_like(bit)
-    pw = np.zeros(bit.shape, dtype=np.float64)
-    sbit = np.zeros(shape + (S - 1,), dtype=np.uint64)
-    ssym = np.zeros_like(sbit)
-    spw = np.zeros(sbit.shape, dtype=np.float64)
-    ppw = np.zeros(shape + (2,), dtype=np.float64)
-    near = np.zeros(shape, dtype=np.int64)
-    for cell in range(pairs * n_snr * n_ch):
-        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
-        for f in range(int(frames)):
-            fr = int(frame_offset) + f
-            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
-            noise = gen_noise(nl, seed, cell, fr)
-            for i, q in enumerate(pts):
-                b, se, e, xhat, y0, sb, ss, sp, pp = frame_profile_pa(st, grid, noise, w_tx[p], w_rx[p], hc[c], q, ref[p],
-                                                                      snr[s], k, act, m, noise_before_truncate)
-                bit[i, p, s, c] += b
-                sym[i, p, s, c] += se
-                pw[i, p, s, c] += e
-                sbit[i, p, s, c] += sb
-                ssym[i, p, s, c] += ss
-                spw[i, p, s, c] += sp
-                ppw[i, p, s, c] += pp
-                if with_near:
-                    near[i, p, s, c] += int(near_decisions(k, xhat, y0).sum())
-    prof = RxProfilePa(bit, sym, pw, sbit, ssym, spw, ppw, _decisions(st, S, frames, act))
-    return (prof, near) if with_near else prof
+    def arm(q):
+        pts, ref = _prepare_pa(points, ref_power, q.w_tx.shape[0])
+
+        def frame(p, s, c, cell, fr, grid):
+            noise = gen_noise(q.noise_len, seed, cell, fr)
+            return (frame_profile_pa(st, grid, noise, q.w_tx[p], q.w_rx[p], q.hc[c], pt, ref[p], q.snr[s], q.k, q.act, q.m, q.nbt)
+                    for pt in pts)
+        return (len(pts),), frame
+    return _host_sweep(RxProfilePa, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames,
+                       active, mask, noise_before_truncate, with_near)
 
 
 def rx_profile_pa_chunk_frames(st, syms, masked, n_points):
     """Frames one chunk of ``wofdm_rx_profile_pa`` holds (include/wofdm.h): ``rx_profile_sync_chunk_frames``' bytes plus one
     waveform per point; at most 65535."""
-    from . import _lib
-    P = st.sym_len
-    T = st.tail_tx + syms * (P - st.tail_tx)
-    per_frame = 8 * (syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0)) + 8 * int(n_points) * (st.n_fft + syms + T)
-    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+    return _chunk_frames(st, syms, masked, per_point=st.n_fft + syms + st.tail_tx + syms * (st.sym_len - st.tail_tx),
+                         n_points=n_points)
 
 
 def rx_profile_pa_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, ref_power,
@@ -916,34 +809,12 @@ def rx_profile_pa_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, 
     once per frame, every point sees the same labels and noise --, per subcarrier and per data symbol.  ``ref_power`` [pairs]:
     the mean on-air power of a window pair's waveform the back-off counts from (``pa_ref_power``).  Returns ``RxProfilePa``;
     ``out`` (an earlier result of the same shape) is accumulated into.  No CPU fallback."""
-    import ctypes as C
     from . import _lib
-    from .simulation import make_cfg
-    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
-    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0]
-    pts, ref = _prepare_pa(points, ref_power, pairs)
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts, ref = _prepare_pa(points, ref_power, prepared[0].shape[0])
     cpts = (_lib.PaPoint * len(pts))(*[_lib.PaPoint(q.model, q.ibo_db, q.smooth, 0) for q in pts])
-    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[1], n_ch, n_snr, pairs, bool(noise_before_truncate),
-                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
-    shape = (len(pts), pairs, n_snr, n_ch)
-    errs = np.zeros(shape + (st.n_fft, 2), dtype=np.uint64)
-    pw = np.zeros(shape + (st.n_fft,), dtype=np.float64)
-    serrs = np.zeros(shape + (int(syms) - 1, 2), dtype=np.uint64)
-    spw = np.zeros(shape + (int(syms) - 1,), dtype=np.float64)
-    ppw = np.zeros(shape + (2,), dtype=np.float64)
-    hf = _lib.c64_as_f32(hc)
-    _lib.check(_lib.load().wofdm_rx_profile_pa(
-        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
-        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, len(pts), cpts, ref.ctypes.data,
-        errs.ctypes.data, pw.ctypes.data, serrs.ctypes.data, spw.ctypes.data, ppw.ctypes.data))
-    prof = RxProfilePa(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
-                       np.ascontiguousarray(serrs[..., 0]), np.ascontiguousarray(serrs[..., 1]), spw, ppw,
-                       _decisions(st, syms, frames, act))
-    if out is not None:
-        if out.bit_err.shape != prof.bit_err.shape:
-            raise ValueError("out has another shape")
-        prof = RxProfilePa(*(a + b for a, b in zip(out, prof)))
-    return prof
+    return _gpu_call("wofdm_rx_profile_pa", RxProfilePa, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                     noise_before_truncate, device, out, lead=(len(pts),), after_mask=(len(pts), cpts, ref.ctypes.data))
 
 
 def pa_ref_power(st, bits_per_sc, syms, w_tx_pairs, seed, frame_offset, frames, active=None, mask=None, gpu=True, device=0):
@@ -1044,14 +915,8 @@ def frame_profile_pn(st, grids, unit_noise, w_tx, w_rx, h, walk, point, snr_db, 
     ``frame_profile``'s.  Returns what ``frame_profile_sync`` returns: (bit_err [N], sym_err [N], err_power [N], xhat [S-1, N],
     y0 [N], bit_err_sym [S-1], sym_err_sym [S-1], err_power_sym [S-1]) -- the first five are ``frame_profile``'s, exactly, at
     linewidth = 0 under either flag --; with_y=True: Y [S, N], sigma and ubar [S] as a ninth to eleventh."""
-    noise = np.asarray(unit_noise, dtype=np.complex128).reshape(-1)
     hc = np.asarray(h, dtype=np.complex128).reshape(-1)
-    nl = _noise_len(st, np.asarray(grids).shape[0], hc.size, noise_before_truncate)
-    if noise.size < nl:
-        raise ValueError("unit_noise holds %d samples, %d needed" % (noise.size, nl))
-
-    def noise_at(idx):
-        return noise[np.asarray(idx, dtype=np.int64)]
+    noise_at = _unit_noise_lookup(st, grids, unit_noise, hc.size, noise_before_truncate)
     front = _sync_front(st, grids, noise_at, w_tx, hc, snr_db, active, mask, noise_before_truncate)
     out = _pn_point(st, front, noise_at, w_rx, walk, point, bits_per_sc, with_cpe=True)
     return out if with_y else out[:8]
@@ -1063,57 +928,25 @@ def rx_profile_pn_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db,
     ``frame_profile_pn`` for every point of ``points`` (``PnPoint`` or (linewidth, cpe_tracked) tuples); the Tx chain, the
     channel, the noise gain and the unit walk (stream 3) of a frame are shared by its points.  Returns ``RxProfileSync``;
     with_near=True: also the number of ``near_decisions`` per point and cell [points, pairs, n_snr, n_ch]."""
-    from . import timefreq as T
-    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
-    pts = _pn_prepare(points)
-    pairs, n_snr, n_ch, n = w_tx.shape[0], snr.size, hc.shape[0], st.n_fft
-    k, S, B = int(bits_per_sc), int(syms), st.sym_len - st.tail_tx
-    tab = T.qam_table(k)
-    nl = max(_noise_len(st, S, hc.shape[1], noise_before_truncate), S * B)
-    on = np.ones(n, dtype=bool) if act is None else act != 0
-    shape = (len(pts), pairs, n_snr, n_ch)
-    bit = np.zeros(shape + (n,), dtype=np.uint64)
-    sym = np.zeros_like(bit)
-    pw = np.zeros(bit.shape, dtype=np.float64)
-    sbit = np.zeros(shape + (S - 1,), dtype=np.uint64)
-    ssym = np.zeros_like(sbit)
-    spw = np.zeros(sbit.shape, dtype=np.float64)
-    near = np.zeros(shape, dtype=np.int64)
-    for cell in range(pairs * n_snr * n_ch):
-        p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
-        for f in range(int(frames)):
-            fr = int(frame_offset) + f
-            grid = tab[gen_labels(n, k, S, seed, cell, fr)] * on[None, :]
-            noise = gen_noise(nl, seed, cell, fr)
-            walk = pn_walk(S * B, seed, cell, fr)
+    def arm(q):
+        pts = _pn_prepare(points)
+        SB = q.S * (st.sym_len - st.tail_tx)
 
-            def noise_at(idx, noise=noise):
-                return noise[np.asarray(idx, dtype=np.int64)]
-            front = _sync_front(st, grid, noise_at, w_tx[p], hc[c], snr[s], act, m, noise_before_truncate)
-            for i, q in enumerate(pts):
-                b, se, e, xhat, y0, sb, ss, sp = _pn_point(st, front, noise_at, w_rx[p], walk, q, k)[:8]
-                bit[i, p, s, c] += b
-                sym[i, p, s, c] += se
-                pw[i, p, s, c] += e
-                sbit[i, p, s, c] += sb
-                ssym[i, p, s, c] += ss
-                spw[i, p, s, c] += sp
-                if with_near:
-                    near[i, p, s, c] += int(near_decisions(k, xhat, y0).sum())
-    prof = RxProfileSync(bit, sym, pw, sbit, ssym, spw, _decisions(st, S, frames, act))
-    return (prof, near) if with_near else prof
+        def frame(p, s, c, cell, fr, grid):
+            noise_at = _noise_lookup(gen_noise(max(q.noise_len, SB), seed, cell, fr))
+            walk = pn_walk(SB, seed, cell, fr)
+            front = _sync_front(st, grid, noise_at, q.w_tx[p], q.hc[c], q.snr[s], q.act, q.m, q.nbt)
+            return (_pn_point(st, front, noise_at, q.w_rx[p], walk, pt, q.k)[:8] for pt in pts)
+        return (len(pts),), frame
+    return _host_sweep(RxProfileSync, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames,
+                       active, mask, noise_before_truncate, with_near)
 
 
 def rx_profile_pn_chunk_frames(st, syms, masked, n_points):
     """Frames one chunk of ``wofdm_rx_profile_pn`` holds (include/wofdm.h): ``rx_profile_sync_chunk_frames``' bytes plus the
     frame's unit walk, S B doubles; at most 65535."""
-    from . import _lib
-    P = st.sym_len
-    B = P - st.tail_tx
-    T = st.tail_tx + syms * B
-    per_frame = 8 * (syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0)) + 8 * syms * B + \
-        8 * int(n_points) * (st.n_fft + syms)
-    return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
+    return _chunk_frames(st, syms, masked, per_point=st.n_fft + syms, n_points=n_points,
+                         per_frame_extra=syms * (st.sym_len - st.tail_tx))
 
 
 def rx_profile_pn_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points,
@@ -1125,28 +958,8 @@ def rx_profile_pn_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, 
     CPU fallback."""
     import ctypes as C
     from . import _lib
-    from .simulation import make_cfg
-    w_tx, w_rx, hc, snr, act, m = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
     pts = _pn_prepare(points)
     cpts = (_lib.PnPoint * len(pts))(*[_lib.PnPoint(q.linewidth, q.cpe_tracked, (C.c_int32 * 2)(0, 0)) for q in pts])
-    pairs, n_snr, n_ch = w_tx.shape[0], snr.size, hc.shape[0]
-    cfg = make_cfg(st, int(bits_per_sc), int(syms), hc.shape[1], n_ch, n_snr, pairs, bool(noise_before_truncate),
-                   seed=int(seed), frames_per_cell=int(frames), frame_offset=int(frame_offset))
-    shape = (len(pts), pairs, n_snr, n_ch)
-    errs = np.zeros(shape + (st.n_fft, 2), dtype=np.uint64)
-    pw = np.zeros(shape + (st.n_fft,), dtype=np.float64)
-    serrs = np.zeros(shape + (int(syms) - 1, 2), dtype=np.uint64)
-    spw = np.zeros(shape + (int(syms) - 1,), dtype=np.float64)
-    hf = _lib.c64_as_f32(hc)
-    _lib.check(_lib.load().wofdm_rx_profile_pn(
-        C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, snr.ctypes.data,
-        None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, len(pts), cpts, errs.ctypes.data,
-        pw.ctypes.data, serrs.ctypes.data, spw.ctypes.data))
-    prof = RxProfileSync(np.ascontiguousarray(errs[..., 0]), np.ascontiguousarray(errs[..., 1]), pw,
-                         np.ascontiguousarray(serrs[..., 0]), np.ascontiguousarray(serrs[..., 1]), spw,
-                         _decisions(st, syms, frames, act))
-    if out is not None:
-        if out.bit_err.shape != prof.bit_err.shape:
-            raise ValueError("out has another shape")
-        prof = RxProfileSync(*(a + b for a, b in zip(out, prof)))
-    return prof
+    return _gpu_call("wofdm_rx_profile_pn", RxProfileSync, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                     noise_before_truncate, device, out, lead=(len(pts),), after_mask=(len(pts), cpts))
