@@ -694,6 +694,88 @@ int wofdm_rx_profile_pn(const wofdm_cfg *cfg, int device,
                         uint64_t *sym_errs,                 /* [n_points][cells][S-1][2], or NULL */
                         double *sym_power);                 /* [n_points][cells][S-1], or NULL */
 
+/* wofdm_rx_profile with the five impairments COMBINED: the amplifier of wofdm_rx_profile_pa, the moving channel of
+ * wofdm_rx_profile_doppler, the neighbour of wofdm_rx_profile_aci, the receiver offsets of wofdm_rx_profile_sync and the phase
+ * noise of wofdm_rx_profile_pn in one chain -- "which window pair is best at 3 dB back-off, 100 km/h, a 1e-3 linewidth and a
+ * neighbour 10 dB up".  The effects do not add: the amplifier's regrowth and the neighbour's leakage both land on what the Rx
+ * window rejects, and carrier offset and phase noise share the rotation.  A call takes a LIST of points, each switching on any
+ * subset of the five; the Tx chain, the walk and (where a point wants it) the neighbour run once per frame, and every point
+ * sees the same labels, noise, walk and neighbour.
+ *   Model, one chain in the order of the physics, each stage exactly the one its own call documents:
+ *   1. the Tx chain of wofdm_rx_profile, once per frame;
+ *   2. the point's amplifier on the finished waveform (wofdm_rx_profile_pa's materialising kernel; pa_model = WOFDM_PA_LINEAR
+ *      reads x itself);
+ *   3. the channel: track >= 0 picks h_track[track], with the taps taken at the OUTPUT sample's time as in
+ *      wofdm_rx_profile_doppler; track = -1 the static h;
+ *   4. where aci_on, the neighbour of wofdm_rx_profile_aci -- S + 1 symbols of stream 2 on aci_active, generated once per
+ *      frame if any point wants it, linear, through the static aci_h (NULL: h) -- at the point's amplitude
+ *      10^(aci_level_db / 20) and offset B - aci_delay; an aci_active that loads no bin is no neighbour;
+ *   5. g n: Ps is measured per point on the point's waveform and channel (as _pa and _doppler do), Pn with the first point;
+ *      neither sees the neighbour, the offsets or the phase;
+ *   6. the windows begin at s B + prefix_rm + timing;
+ *   7. the received sample -- signal, neighbour and noise -- is multiplied by wofdm_rx_profile_sync's factor and then by
+ *      wofdm_rx_profile_pn's: two multiplies, each in the form its own call has, each exactly (1, 0) when neutral;
+ *   8. Rx window, fold, shift, DFT, pilot of symbol 0, equaliser, slicer and counters, unchanged.
+ *   Three interactions have a rule of their own.
+ *   The walk under a timing offset: the unit walk stays wofdm_rx_profile_pn's, u[a] for 0 <= a < S B, in its order of
+ *   additions.  A sample at on-air index a outside [0, S B) reads u[clamp(a, 0, S B - 1)]: the oscillator holds its phase
+ *   outside the frame.  At timing = 0 the clamp is never met (the largest index read is exactly S B - 1).  The tracked mean
+ *   is taken over the same clamped values.
+ *   The tap time under a timing offset: the knots must cover tail_tx + S B + n_taps - 2 + max(0, the largest timing of the
+ *   call), else WOFDM_E_INVALID.  For a < 0 every product is zero; the tap time used there is 0, so no tap is ever formed from
+ *   a wrapped index.
+ *   The static channel beside tracks: the library stages h as one more track, h at every knot -- with equal knots the
+ *   interpolated tap is the knot, bit for bit --, so there is one tap path and track = -1 gives the bits of h.
+ *   Identities: a call whose point has one impairment on returns, for that point, the BYTES of that impairment's own entry
+ *   point with the same cfg and seed (all five outputs of wofdm_rx_profile_pa; the per-bin outputs of wofdm_rx_profile_aci), and
+ *   an all-off point those of wofdm_rx_profile (as long as no cell's frames are split over two chunks of either call).
+ *   Arguments: h is always needed; h_track [n_tracks][n_channels][n_knots][n_taps][2] with n_tracks <=
+ * WOFDM_DOPPLER_MAX_TRACKS, n_knots, knot_step as in wofdm_rx_profile_doppler, NULL (and the three integers ignored) when no
+ * point names a track; aci_active and aci_h as in wofdm_rx_profile_aci, both may be NULL when no point has aci_on; ref_power
+ * [pairs] as in wofdm_rx_profile_pa, may be NULL when every point is linear.
+ *   Outputs: the five of wofdm_rx_profile_pa, "point" on the leading axis, ACCUMULATED into, with its NULL rules and its
+ * ordered sums; pa_power of a linear point is {sum |x|^2, sum |x|^2}.
+ *   Limits, the union of the five calls': |timing| < B, |cfo| <= 4, 0 <= linewidth <= 1, 0 <= aci_delay < B, a finite level
+ * whose amplitude is finite in single precision, the amplifier's limits, the knots' limits, -1 <= track < n_tracks, flags 0 or
+ * 1, reserved 0, n_points in [1, WOFDM_LINK_MAX_POINTS], and no needed argument NULL.  Every argument is checked before the
+ * device is touched; a failed call leaves all five outputs as they were.
+ *   Chunks: min(65535, WOFDM_RX_PROFILE_CHUNK_BYTES / (8 (S n_fft + T + [mask] S (2P-1)) + 8 n_points (n_fft + S + T) + 8 S B +
+ * [a point has aci_on] 8 ((S + 1) n_fft + T + B + [mask] (S + 1) (2P-1))))  frames -- wofdm_rx_profile_pa's formula plus the
+ * walk plus the neighbour's buffers.
+ *   A successful call holds the launch gate and counts for wofdm_rx_profile_kernel_ms.
+ *   Measured on an MI355X (tools/bench_rx_profile_link.py, profiles/rx_profile_link.txt): on 64 cells x 2000 frames x 16 symbols at
+ * n_fft = 256 a point costs 73 ms of kernels (98 ms masked) whatever single impairment it switches on, 1.88 (1.39) times one
+ * wofdm_rx_profile call on the same cells and frames in the same run and 1.2 to 1.7 times that impairment's own entry point --
+ * every point pays the power pass and per-lane taps; one point with everything on takes 94.2 (143.0) ms, four such points 201.4
+ * (275.4) ms, 5.17 (3.90) times -- 0.92 (0.62) of a plain call per additional point. */
+#define WOFDM_LINK_MAX_POINTS 16
+typedef struct wofdm_link_point {
+    int32_t pa_model; float pa_ibo_db; float pa_smooth;    /* wofdm_pa_point's; WOFDM_PA_LINEAR = no amplifier      */
+    int32_t track;                                         /* index into h_track, or -1 = the static channel h      */
+    int32_t timing; float cfo; int32_t cfo_tracked;        /* wofdm_sync_point's                                    */
+    float   linewidth; int32_t cpe_tracked;                /* wofdm_pn_point's                                      */
+    int32_t aci_on; int32_t aci_delay; float aci_level_db; /* neighbour on the air for this point; delay, level     */
+    int32_t reserved[4];                                   /* 0                                                     */
+} wofdm_link_point;
+int wofdm_rx_profile_link(const wofdm_cfg *cfg, int device,
+                          const float *w_tx,                /* [pairs][P] */
+                          const float *w_rx,                /* [pairs][N+tail_rx] */
+                          const float *h,                   /* [n_channels][n_taps][2] */
+                          const float *snr_db,              /* [n_snr] */
+                          const uint8_t *active,            /* [n_fft] or NULL */
+                          const float *tx_mask,             /* [2P-1] or NULL */
+                          const float *h_track,             /* [n_tracks][n_channels][n_knots][n_taps][2], or NULL */
+                          int32_t n_tracks, int32_t n_knots, int32_t knot_step,
+                          const uint8_t *aci_active,        /* [n_fft], or NULL */
+                          const float *aci_h,               /* [n_channels][n_taps][2], or NULL = h */
+                          const float *ref_power,           /* [pairs], or NULL */
+                          int32_t n_points, const wofdm_link_point *points,
+                          uint64_t *errs,                   /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                          double *err_power,                /* [n_points][cells][n_fft], or NULL */
+                          uint64_t *sym_errs,               /* [n_points][cells][S-1][2], or NULL */
+                          double *sym_power,                /* [n_points][cells][S-1], or NULL */
+                          double *pa_power);                /* [n_points][cells][2], or NULL */
+
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: the bytes of the six receive-profile entry points, as SHA-256 digests -- for comparing two builds of the
+"""Developer tool: the bytes of the seven receive-profile entry points, as SHA-256 digests -- for comparing two builds of the
 library (WOFDM_LIB=... selects one) or two versions of the Python layer above it: run the tool once per build or tree and diff
 the outputs line for line.  It uses the package's public names only, so the same file runs against either tree.
 
@@ -11,6 +11,7 @@ of W, W = 4 at N = 1024, the fold with and without an Rx tail and both noise ord
   rx_profile_doppler  tests/doppler_cases.py CASES, and the extra steps and knot counts of its EXTRA case
   rx_profile_pa       tests/pa_cases.py
   rx_profile_pn       CASES and POINTS of tests/test_gpu_rx_profile_pn.py
+  rx_profile_link     the cases of tests/test_gpu_rx_profile_link.py, composed points and their single-impairment points
 and for each entry point the chunk-straddling shape of its test file (N = 1024, S = 16, cp + cs = 64, four chunks and a bit).
 The seeds are the cases' base seeds: the tests pick theirs with the oracle or the mirrors, which no digest needs.
 
@@ -45,6 +46,7 @@ import pa_cases as PC  # noqa: E402
 import rx_profile_cases as RC  # noqa: E402
 import test_gpu_rx_profile_aci as TA  # noqa: E402
 import test_gpu_rx_profile_doppler as TD  # noqa: E402
+import test_gpu_rx_profile_link as TL  # noqa: E402
 import test_gpu_rx_profile_pa as TP  # noqa: E402
 import test_gpu_rx_profile_pn as TN  # noqa: E402
 import test_gpu_rx_profile_sync as TS  # noqa: E402
@@ -61,6 +63,13 @@ def host_aci(c, seed, frame_offset, frames):
                                  noise_before_truncate=c["nbt"], with_near=True)
 
 
+def gpu_link(c, seed, frame_offset, frames, **kw):
+    if "ref_power" in kw:                                              # (the chunk shape: its own sides, no case name)
+        return W.rx_profile_link_gpu(c["st"], c["k"], c["S"], c["w_tx"], c["w_rx"], c["h"], c["snr"], seed, frame_offset, frames,
+                                     c["points"], active=c["active"], mask=c["mask"], noise_before_truncate=c["nbt"], **kw)
+    return TL.run_gpu(c, seed, frame_offset, frames)
+
+
 #: entry -> (gpu route -> profile, host route -> (profile, near)), both (case, seed, frame_offset, frames, **kw)
 ROUTES = {
     "rx_profile": (RC.run_gpu, host_plain),
@@ -69,6 +78,7 @@ ROUTES = {
     "rx_profile_doppler": (TD.run_gpu, DC.host),
     "rx_profile_pa": (TP.run_gpu, PC.host),
     "rx_profile_pn": (TN.run_gpu, TN.host),
+    "rx_profile_link": (gpu_link, TL.host),
 }
 
 
@@ -100,10 +110,13 @@ def small_cases():
         yield "rx_profile_pa", name, PC.case(name), 100 * (1 + j), {}
     for j, name in enumerate(TN.CASES):
         yield "rx_profile_pn", name, TN.case(name), 100 * (1 + j), {}
+    for j, name in enumerate(TL.CASES):
+        c = TL.case(name)
+        yield "rx_profile_link", name, dict(c, points=c["composed"] + c["singles"]), 100 * (1 + j), {}
 
 
 def chunk_cases():
-    """(entry, case, frames, extra keywords): the chunk-straddling shape of the six test files, N = 1024, S = 16, cp + cs = 64"""
+    """(entry, case, frames, extra keywords): the chunk-straddling shape of the seven test files, N = 1024, S = 16, cp + cs = 64"""
     st, S = W.make_structure("wtx", 1024, 56), 16
     big = RC.make_case(st, 4, S, "plain", 3001)
     half = CM.half_band_allocation(1024)
@@ -124,6 +137,9 @@ def chunk_cases():
     yield "rx_profile_pa", cq, frames_of(R.rx_profile_pa_chunk_frames(st, S, False, 2)), dict(points=pts, ref=ref)
     cn = dict(big, active=half, points=[R.PnPoint(0.0, 1), R.PnPoint(0.01, 0)])
     yield "rx_profile_pn", cn, frames_of(R.rx_profile_pn_chunk_frames(st, S, False, 2)), {}
+    cl = dict(cd, points=[R.LinkPoint(), R.LinkPoint(pts[1], 1, 2, 0.02, 1, 0.01, 0, (501, 0.0))])
+    yield ("rx_profile_link", cl, frames_of(R.rx_profile_link_chunk_frames(st, S, False, 2, True)),
+           dict(tracks=cd["tracks"], knot_step=st.stride, aci_active=~half, ref_power=ref))
 
 
 def runs(route):

@@ -17,7 +17,7 @@ as ``wofdm_amd`` through the shim module at the repository root.
                carrier-frequency offset (GPU: wofdm_rx_profile_sync), or over channels that move within the frame
                (GPU: wofdm_rx_profile_doppler), or behind a nonlinear power amplifier (GPU: wofdm_rx_profile_pa; the
                spectral regrowth: timefreq / wofdm_tx_psd_batch_pa), or under oscillator phase noise (GPU:
-               wofdm_rx_profile_pn)
+               wofdm_rx_profile_pn), or with all five combined (GPU: wofdm_rx_profile_link)
   _lib         ctypes binding of libwofdm_hip.so (include/wofdm.h)
 """
 from . import variants  # noqa: F401
@@ -37,7 +37,7 @@ from ._lib import kernel_source_hash  # noqa: F401
 from .timefreq import (estimate_obr, frame_papr, papr_ccdf, papr_hist, run_timefreq, tx_papr_gpu,  # noqa: F401
                        tx_psd_batch_gpu, tx_waveform)
 from .channel_mask import (aci_for_window_file, doppler_for_window_file, interference_for_window_file,  # noqa: F401
-                           pa_for_window_file, papr_for_window_file, pn_for_window_file, profile_for_window_file,
+                           link_for_window_file, pa_for_window_file, papr_for_window_file, pn_for_window_file, profile_for_window_file,
                            spectrum_for_window_file, sync_for_window_file)
 from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_db, frame_profile,  # noqa: F401
                          frame_profile_aci, frame_profile_sync, gen_noise_at, rx_profile_aci_gpu, rx_profile_aci_host,
@@ -47,7 +47,9 @@ from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_d
                          PA_CLIP, PA_LINEAR, PA_RAPP, PaPoint, RxProfilePa, frame_profile_pa, pa_apply, pa_gain, pa_ref_power,
                          rx_profile_pa_chunk_frames, rx_profile_pa_gpu, rx_profile_pa_host,
                          PnPoint, frame_profile_pn, gen_pn_increments, pn_walk, rx_profile_pn_chunk_frames, rx_profile_pn_gpu,
-                         rx_profile_pn_host)
+                         rx_profile_pn_host,
+                         LinkPoint, RxProfileLink, frame_profile_link, rx_profile_link_chunk_frames, rx_profile_link_gpu,
+                         rx_profile_link_host)
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

@@ -36,6 +36,8 @@ PA_LINEAR, PA_RAPP, PA_CLIP = 0, 1, 2
 PA_MAX_POINTS = 16
 #: wofdm_rx_profile_pn (include/wofdm.h): most points one call takes
 PN_MAX_POINTS = 16
+#: wofdm_rx_profile_link (include/wofdm.h): most points one call takes
+LINK_MAX_POINTS = 16
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -49,6 +51,7 @@ EXPORTS = (
     "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms", "wofdm_plan_kernel_geo", "wofdm_cfg_geo_id",
     "wofdm_rx_profile_aci", "wofdm_rx_profile_sync", "wofdm_rx_profile_doppler",
     "wofdm_rx_profile_pa", "wofdm_tx_psd_batch_pa", "wofdm_rx_profile_pn",
+    "wofdm_rx_profile_link",
 )
 
 
@@ -101,6 +104,14 @@ class PaPoint(C.Structure):
 class PnPoint(C.Structure):
     """Mirror of ``wofdm_pn_point`` (16 bytes)."""
     _fields_ = [("linewidth", C.c_float), ("cpe_tracked", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class LinkPoint(C.Structure):
+    """Mirror of ``wofdm_link_point`` (64 bytes)."""
+    _fields_ = [("pa_model", C.c_int32), ("pa_ibo_db", C.c_float), ("pa_smooth", C.c_float), ("track", C.c_int32),
+                ("timing", C.c_int32), ("cfo", C.c_float), ("cfo_tracked", C.c_int32), ("linewidth", C.c_float),
+                ("cpe_tracked", C.c_int32), ("aci_on", C.c_int32), ("aci_delay", C.c_int32), ("aci_level_db", C.c_float),
+                ("reserved", C.c_int32 * 4)]
 
 
 class Dump(C.Structure):
@@ -181,6 +192,8 @@ def load():
     L.wofdm_rx_profile_doppler.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_rx_profile_pa.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, i32, C.POINTER(PaPoint), vp, vp, vp, vp, vp, vp]
     L.wofdm_rx_profile_pn.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, i32, C.POINTER(PnPoint), vp, vp, vp, vp]
+    L.wofdm_rx_profile_link.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
+                                        C.POINTER(LinkPoint), vp, vp, vp, vp, vp]
     L.wofdm_tx_psd_batch_pa.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, C.POINTER(PaPoint), vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L

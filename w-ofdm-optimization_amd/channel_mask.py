@@ -395,6 +395,36 @@ def pa_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, num_sub
     return out
 
 
+def link_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, tracks=None, knot_step=None, aci_channels=None,
+                         num_subcar=256, bits_per_subcar=4, symbols_per_tx=16, ensemble=100, roll_off=ROLL_OFF, seed=0,
+                         frame_range=None, gpu=True, device=0, tail_tx=8, tail_rx=10):
+    """The whole link of the mask experiment: ``profile_for_window_file`` with the impairments of ``pa_for_window_file``,
+    ``doppler_for_window_file``, ``aci_for_window_file``, ``sync_for_window_file`` and ``pn_for_window_file`` in ONE chain -- "which
+    window pair is best at 3 dB back-off, 100 km/h, a 1e-3 linewidth and a neighbour 10 dB up"; the effects do not add.  Every
+    window pair of the file + the RC pair under half-band loading, for every SNR point, channel and point of ``points``
+    (``rx_profile.LinkPoint`` or tuples in its order, each switching on any subset), plain and masked (``tx_mask(P)``): the
+    amplifier's back-off counts from ``rx_profile.pa_ref_power`` of the pair (measured only where a point has an amplifier),
+    ``tracks`` [n_tracks, n_channels, n_knots, taps] and ``knot_step`` as in ``doppler_for_window_file``, the neighbour on the
+    complementary half band through ``aci_channels`` (None: the victim's) as in ``aci_for_window_file``.  On the GPU two
+    ``wofdm_rx_profile_link`` calls whatever len(points) is (gpu=False: the fp64 host route
+    ``rx_profile.rx_profile_link_host``, for small ensembles).  The frames are those of ``profile_for_window_file`` with the
+    same arguments, so an all-off point is its result.
+    Returns {name: {"profile", "profile_masked"}} with the names of ``V.matlab_pair_plan``; each an
+    ``rx_profile.RxProfileLink`` of that pair, arrays [points, n_snr, n_channels, ...]."""
+    from . import rx_profile as R
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off)
+    pts = [R.LinkPoint(*q) for q in points]
+    first, count = _frames(ensemble, frame_range)
+    ref = [None, None]
+    if any(q.pa is not None for q in pts):
+        ref = [R.pa_ref_power(st, bits_per_subcar, symbols_per_tx, w_tx, seed, first, count, active=alloc, mask=m, gpu=gpu,
+                              **(dict(device=device) if gpu else {})) for m in (None, mask)]
+    head = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.atleast_2d(np.asarray(channels)), snr_db, seed)
+    side = (tracks, knot_step, ~alloc if any(q.aci is not None for q in pts) else None, aci_channels)
+    return _profiles_per_pair("_link", plan, alloc, mask, head, ensemble, frame_range, gpu, device, tail=(pts, *side, ref[0]),
+                              tail_masked=(pts, *side, ref[1]))
+
+
 def results_from_counts(names, masked, plain):
     def ber(c):      # mean over channels of per-channel BER (lines 84-117)
         return (c[..., 0] / np.maximum(c[..., 1], 1)).mean(axis=-1)

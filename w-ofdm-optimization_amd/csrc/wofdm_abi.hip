@@ -2,7 +2,7 @@
 // Plans own the constants in HBM; launches are asynchronous on the caller's stream.
 #include "../../include/wofdm.h"
 #include "wofdm_kernel.h"
-#include "wofdm_pa.h"
+#include "wofdm_link.h"
 #include "philox.h"
 
 #include <algorithm>
@@ -1603,15 +1603,29 @@ struct pn_args {
     double *sym_power;
 };
 
-// wofdm_rx_profile, wofdm_rx_profile_aci, wofdm_rx_profile_sync, wofdm_rx_profile_doppler, wofdm_rx_profile_pa and
-// wofdm_rx_profile_pn.  Every argument is checked before the first HIP call; the
+// the five impairments combined (wofdm_rx_profile_link): its points beside the arguments of the arms it switches on -- sync, amp
+// and pn carry its points' receiver offsets, amplifiers and oscillators (n_points each, the outputs in sync and amp), dop the
+// tracks if a point names one, aci the neighbour's allocation and channels if a point has aci_on --, so every stage is checked
+// and prepared by the code of its own arm
+struct link_args {
+    int32_t n_points;
+    const wofdm_link_point *points;
+};
+
+// wofdm_rx_profile, wofdm_rx_profile_aci, wofdm_rx_profile_sync, wofdm_rx_profile_doppler, wofdm_rx_profile_pa,
+// wofdm_rx_profile_pn and wofdm_rx_profile_link.  Every argument is checked before the first HIP call; the
 // caller's arrays are written only after everything has succeeded.
 int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                     const float *snr_db, const uint8_t *active, const float *tx_mask, const aci_args *aci, const sync_args *sync,
-                    const doppler_args *dop, const pa_args *amp, const pn_args *pn, uint64_t *errs, double *err_power)
+                    const doppler_args *dop, const pa_args *amp, const pn_args *pn, const link_args *link, uint64_t *errs,
+                    double *err_power)
 {
-    if (!cfg || !w_tx || !w_rx || !(dop ? dop->h_track : h) || !snr_db || !errs) return fail(WOFDM_E_INVALID, "NULL argument");
-    if (amp && (!amp->points || !amp->ref_power)) return fail(WOFDM_E_INVALID, "NULL argument (points or ref_power)");
+    // (the link call has the static channel beside its tracks, and needs no reference power where every point is linear)
+    if (!cfg || !w_tx || !w_rx || !(dop && !link ? dop->h_track : h) || (dop && !dop->h_track) || !snr_db || !errs)
+        return fail(WOFDM_E_INVALID, "NULL argument");
+    bool link_pa = false;
+    for (int i = 0; link && amp && amp->points && i < amp->n_points; ++i) link_pa |= amp->points[i].model != WOFDM_PA_LINEAR;
+    if (amp && (!amp->points || (!amp->ref_power && (!link || link_pa)))) return fail(WOFDM_E_INVALID, "NULL argument (points or ref_power)");
     if (amp && amp->n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", amp->n_points);
     if (aci && !aci->active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active)");
     if (sync && !sync->points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
@@ -1653,7 +1667,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         return true;
     };
     if (!finite(w_tx, (size_t)pairs * P) || !finite(w_rx, (size_t)pairs * NW)) return fail(WOFDM_E_INVALID, "windows must be finite");
-    if (!dop && !finite(h, (size_t)cfg->n_channels * L * 2)) return fail(WOFDM_E_INVALID, "channel taps must be finite");
+    if ((!dop || link) && !finite(h, (size_t)cfg->n_channels * L * 2)) return fail(WOFDM_E_INVALID, "channel taps must be finite");
     if (!finite(snr_db, (size_t)cfg->n_snr)) return fail(WOFDM_E_INVALID, "SNR points must be finite");
     if (tx_mask && !finite(tx_mask, (size_t)Lm)) return fail(WOFDM_E_INVALID, "mask gains must be finite");
     std::vector<uint8_t> hact;
@@ -1677,7 +1691,9 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         for (int n = 0; n < N; ++n) nb |= (hiact[(size_t)n] = aci->active[n] ? 1 : 0) != 0;
     }
     // the receiver offsets: the base phasor of every (point, symbol) in double precision, from cfo as stored
-    const int NP = sync ? sync->n_points : (dop ? dop->n_tracks : (amp ? amp->n_points : (pn ? pn->n_points : 1)));
+    const int NP = link ? link->n_points : sync ? sync->n_points : (dop ? dop->n_tracks : (amp ? amp->n_points : (pn ? pn->n_points : 1)));
+    const int NTR = dop ? dop->n_tracks : 0;
+    int max_theta = 0;                                                // (link) the largest timing offset, or 0
     std::vector<wofdm_spoint> hpts;
     std::vector<float2> hbase;
     if (sync) {
@@ -1698,6 +1714,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
             if (std::fabs(q.cfo) > 4.0f)
                 return fail(WOFDM_E_UNSUPPORTED, "points[%d].cfo=%g exceeds 4 subcarrier spacings", i, (double)q.cfo);
             hpts[(size_t)i].theta = q.timing;
+            max_theta = std::max(max_theta, (int)q.timing);
             hpts[(size_t)i].eps = q.cfo;
             for (int s = 0; s < S; ++s) {
                 // eps (s B + gam + theta) / N is exact in double: 24 bits times less than 2^16, over a power of two
@@ -1732,14 +1749,42 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     }
     // the moving channels: every knot finite, and the knots reach the last sample of conv, index T + L - 2
     if (dop) {
-        if (NP > WOFDM_DOPPLER_MAX_TRACKS) return fail(WOFDM_E_UNSUPPORTED, "n_tracks=%d exceeds %d", NP, WOFDM_DOPPLER_MAX_TRACKS);
+        if (NTR > WOFDM_DOPPLER_MAX_TRACKS) return fail(WOFDM_E_UNSUPPORTED, "n_tracks=%d exceeds %d", NTR, WOFDM_DOPPLER_MAX_TRACKS);
         if (dop->n_knots > WOFDM_DOPPLER_MAX_KNOTS)
             return fail(WOFDM_E_UNSUPPORTED, "n_knots=%d exceeds %d", dop->n_knots, WOFDM_DOPPLER_MAX_KNOTS);
-        if (!finite(dop->h_track, (size_t)NP * cfg->n_channels * dop->n_knots * L * 2))
+        if (!finite(dop->h_track, (size_t)NTR * cfg->n_channels * dop->n_knots * L * 2))
             return fail(WOFDM_E_INVALID, "channel knots must be finite");
-        if ((int64_t)(dop->n_knots - 1) * (int64_t)dop->knot_step < (int64_t)T + L - 2)
+        // (link: a late window takes taps max_theta samples further on; 0 otherwise)
+        if ((int64_t)(dop->n_knots - 1) * (int64_t)dop->knot_step < (int64_t)T + L - 2 + max_theta)
             return fail(WOFDM_E_INVALID, "the knots end at sample %lld, the frame's last at %d: (n_knots - 1) knot_step >= "
-                        "tail_tx + S B + n_taps - 2 required", (long long)(dop->n_knots - 1) * dop->knot_step, T + L - 2);
+                        "tail_tx + S B + n_taps - 2%s required", (long long)(dop->n_knots - 1) * dop->knot_step, T + L - 2 + max_theta,
+                        link ? " + the largest positive timing" : "");
+    }
+    // the link points' own part: the track and the neighbour of every point
+    std::vector<wofdm_lpoint> hlk;
+    bool link_nb = false;
+    if (link) {
+        hlk.resize((size_t)NP);
+        for (int i = 0; i < NP; ++i) {
+            const wofdm_link_point &q = link->points[i];
+            if (q.track < -1 || q.track >= NTR) return fail(WOFDM_E_INVALID, "points[%d].track=%d must be -1 or below n_tracks=%d", i, q.track, NTR);
+            if (q.aci_on != 0 && q.aci_on != 1) return fail(WOFDM_E_INVALID, "points[%d].aci_on=%d must be 0 or 1", i, q.aci_on);
+            if (q.reserved[0] != 0 || q.reserved[1] != 0 || q.reserved[2] != 0 || q.reserved[3] != 0)
+                return fail(WOFDM_E_INVALID, "points[%d].reserved must be 0", i);
+            if (!std::isfinite(q.aci_level_db) || !std::isfinite((float)std::pow(10.0, 0.05 * (double)q.aci_level_db)))
+                return fail(WOFDM_E_INVALID, "points[%d].aci_level_db must be finite, and so the amplitude 10^(level / 20)", i);
+            if (q.aci_delay < 0) return fail(WOFDM_E_INVALID, "points[%d].aci_delay=%d is negative", i, q.aci_delay);
+        }
+        for (int i = 0; i < NP; ++i) {
+            const wofdm_link_point &q = link->points[i];
+            if (q.aci_delay >= B)
+                return fail(WOFDM_E_UNSUPPORTED, "points[%d].aci_delay=%d must be below the symbol stride B = %d", i, q.aci_delay, B);
+            // (an allocation that loads no bin is "no neighbour", as in wofdm_rx_profile_aci)
+            hlk[(size_t)i] = {q.track < 0 ? NTR : q.track, q.aci_on && nb ? 1 : 0, B - q.aci_delay,
+                              (float)std::pow(10.0, 0.05 * (double)q.aci_level_db)};
+            link_nb |= hlk[(size_t)i].aci_on != 0;
+        }
+        nb = link_nb;
     }
     // the amplifier: the points, and the saturation amplitude of every (point, pair) in double precision, stored in single
     std::vector<wofdm_papoint> hpa;
@@ -1747,11 +1792,11 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     if (amp) {
         const int prc = check_pa_points(NP, amp->points, &hpa);
         if (prc != WOFDM_OK) return prc;
-        hasat.resize((size_t)NP * pairs);
-        for (uint64_t p = 0; p < pairs; ++p)
+        hasat.assign((size_t)NP * pairs, 1.f);                        // (link, every point linear, no ref_power: never read)
+        for (uint64_t p = 0; amp->ref_power && p < pairs; ++p)
             if (!std::isfinite(amp->ref_power[p]) || !(amp->ref_power[p] > 0.f))
                 return fail(WOFDM_E_INVALID, "ref_power[%llu] must be finite and positive", (unsigned long long)p);
-        for (int i = 0; i < NP; ++i)
+        for (int i = 0; amp->ref_power && i < NP; ++i)
             for (uint64_t p = 0; p < pairs; ++p) {
                 // (the root of a positive single-precision number times 10^-4 ... 10^6 is a normal single-precision number)
                 hasat[(size_t)i * pairs + p] =
@@ -1768,8 +1813,9 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     const int Ti = T + B;
     // (under receiver offsets, moving channels or phase noise the partials are per point or track, per bin and per symbol;
     // behind the amplifier every point has a waveform of its own beside them; the phase walk is S B doubles)
+    // (the link call: the amplifier's per-point term, the walk, and the neighbour's buffers where a point has aci_on)
     const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) +
-                                       (sync || dop || pn ? (uint64_t)NP * (uint64_t)(N + S) : (amp ? (uint64_t)NP * (uint64_t)(N + S + T) : (uint64_t)N)) +
+                                       (link ? (uint64_t)NP * (uint64_t)(N + S + T) : sync || dop || pn ? (uint64_t)NP * (uint64_t)(N + S) : (amp ? (uint64_t)NP * (uint64_t)(N + S + T) : (uint64_t)N)) +
                                        (pn ? (uint64_t)S * B : 0ull) +
                                        (nb ? (uint64_t)(S + 1) * N + (uint64_t)Ti + (tx_mask ? (uint64_t)(S + 1) * Lm : 0ull) : 0ull));
     const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
@@ -1783,13 +1829,21 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     g.L = L;
     // the taps as the kernels read them; of moving channels the knots, [n_tracks][n_channels][n_knots][WOFDM_LT], zero padded
     std::vector<float2> hp;
+    // (link: the knots of its tracks and behind them the static track, h at every knot -- two knots that cover every sample
+    // where no point names a track)
+    const int link_knots = dop ? dop->n_knots : 2, link_step = dop ? dop->knot_step : T + L + B;
     if (dop) {
-        const size_t rows = (size_t)NP * cfg->n_channels * dop->n_knots;
+        const size_t rows = (size_t)NTR * cfg->n_channels * dop->n_knots;
         hp.assign(rows * WOFDM_LT, make_float2(0.f, 0.f));
         for (size_t r = 0; r < rows; ++r)
             for (int l = 0; l < L; ++l)
                 hp[r * WOFDM_LT + l] = make_float2(dop->h_track[2 * (r * L + l)], dop->h_track[2 * (r * L + l) + 1]);
-    } else {
+    }
+    if (link) {
+        const std::vector<float2> hs = pack_taps(cfg, g, h);
+        for (int c = 0; c < cfg->n_channels; ++c)
+            for (int q = 0; q < link_knots; ++q) hp.insert(hp.end(), hs.begin() + (size_t)c * WOFDM_LT, hs.begin() + (size_t)(c + 1) * WOFDM_LT);
+    } else if (!dop) {
         hp = pack_taps(cfg, g, h);
     }
     std::vector<float> nlin((size_t)cfg->n_snr);
@@ -1853,6 +1907,11 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
             return fail(WOFDM_E_NOMEM, "device allocation failed (phase noise)");
         if (!d_pnpts.upload(hpn.data(), hpn.size())) return fail(WOFDM_E_HIP, "upload failed");
     }
+    dev_buf<wofdm_lpoint> d_lkpts;
+    if (link) {
+        if (!d_lkpts.alloc(hlk.size())) return fail(WOFDM_E_NOMEM, "device allocation failed (link points)");
+        if (!d_lkpts.upload(hlk.data(), hlk.size())) return fail(WOFDM_E_HIP, "upload failed");
+    }
     // the neighbour's side of the chunk: allocation, channels, and grids, waveforms, tables of its S + 1 symbols
     dev_buf<uint8_t> d_iact;
     dev_buf<float2> d_hi, d_Xi, d_xi, d_Yi;
@@ -1882,9 +1941,11 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     spar.n_points = NP; spar.cells = cells; spar.pts = d_pts; spar.base = d_base; spar.sym_pow = d_spow; spar.sym_cnt = d_scnt;
     spar.sym_errs = d_serrs; spar.sym_tot = d_stot;
     wofdm_dparams dpar{};
-    if (dop) {
-        dpar.knots = d_h; dpar.n_knots = dop->n_knots; dpar.knot_step = dop->knot_step;
+    if (dop || link) {
+        dpar.knots = d_h; dpar.n_knots = link_knots; dpar.knot_step = link_step;
     }
+    wofdm_lparams lkpar{};
+    lkpar.pts = d_lkpts;
     wofdm_paparams papar{};
     if (amp) {
         papar.n_points = NP; papar.pairs = (int32_t)pairs; papar.pts = d_papts; papar.asat = d_asat; papar.y = d_y;
@@ -1916,13 +1977,15 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         (void)hipDeviceSynchronize();
         const wofdm_aux_fns *ax = wofdm_aux(N);
         const wofdm_pa_fns *axp = wofdm_aux_pa(N);
-        e = ax && axp ? hipEventRecord(ev[0], nullptr) : hipErrorInvalidValue;
+        const wofdm_link_fns *axl = wofdm_aux_link(N);
+        e = ax && axp && axl ? hipEventRecord(ev[0], nullptr) : hipErrorInvalidValue;
         for (uint64_t i0 = 0; e == hipSuccess && i0 < items; i0 += chunk) {
             pp.item0 = rp.item0 = i0;
             pp.n_jobs = rp.n_jobs = (int32_t)std::min<uint64_t>(chunk, items - i0);
             pa.item0 = pp.item0;
             pa.n_jobs = pp.n_jobs;
-            e = amp ? axp->rx_profile_pa(&pp, &rp, &spar, &papar, nullptr)
+            e = link ? axl->rx_profile_link(&pp, nb ? &pa : nullptr, &rp, &apar, &spar, &dpar, &papar, &pnpar, &lkpar, NTR + 1, max_theta, nullptr)
+                : amp ? axp->rx_profile_pa(&pp, &rp, &spar, &papar, nullptr)
                 : dop ? ax->rx_profile_doppler(&pp, &rp, &spar, &dpar, nullptr)
                 : sync ? ax->rx_profile_sync(&pp, &rp, &spar, nullptr)
                 : pn ? ax->rx_profile_pn(&pp, &rp, &spar, &pnpar, nullptr)
@@ -1963,7 +2026,7 @@ extern "C" {
 int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                      const float *snr_db, const uint8_t *active, const float *tx_mask, uint64_t *errs, double *err_power)
 {
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -1971,7 +2034,7 @@ int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, co
                          const float *aci_h, int32_t aci_delay, float aci_level_db, uint64_t *errs, double *err_power)
 {
     const aci_args aci = {aci_active, aci_h, aci_delay, aci_level_db};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, nullptr, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -1979,7 +2042,7 @@ int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, c
                           const wofdm_sync_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const sync_args sync = {n_points, points, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, nullptr, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, nullptr, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h_track,
@@ -1987,7 +2050,7 @@ int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device, const float *w_tx
                              const float *tx_mask, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const doppler_args dop = {h_track, n_tracks, n_knots, knot_step, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask, nullptr, nullptr, &dop, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask, nullptr, nullptr, &dop, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
@@ -1996,7 +2059,7 @@ int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device, const float *w_tx, con
                         double *pa_power)
 {
     const pa_args amp = {n_points, points, ref_power, sym_errs, sym_power, pa_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, &amp, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, &amp, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_pn(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
@@ -2004,7 +2067,41 @@ int wofdm_rx_profile_pn(const wofdm_cfg *cfg, int device, const float *w_tx, con
                         double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const pn_args pn = {n_points, points, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, &pn, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, &pn, nullptr, errs, err_power);
+}
+
+int wofdm_rx_profile_link(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                          const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                          int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
+                          const wofdm_link_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power,
+                          double *pa_power)
+{
+    if (!points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
+    if (n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", n_points);
+    if (n_points > WOFDM_LINK_MAX_POINTS) return fail(WOFDM_E_UNSUPPORTED, "n_points=%d exceeds %d", n_points, WOFDM_LINK_MAX_POINTS);
+    // every stage's points in the form its own arm takes them, so that its own arm's code checks and prepares them
+    std::vector<wofdm_sync_point> spts((size_t)n_points);
+    std::vector<wofdm_pn_point> npts((size_t)n_points);
+    std::vector<wofdm_pa_point> apts((size_t)n_points);
+    bool any_track = false, any_nb = false;
+    for (int i = 0; i < n_points; ++i) {
+        const wofdm_link_point &q = points[i];
+        spts[(size_t)i] = {q.timing, q.cfo, q.cfo_tracked, 0};
+        npts[(size_t)i] = {q.linewidth, q.cpe_tracked, {0, 0}};
+        apts[(size_t)i] = {q.pa_model, q.pa_ibo_db, q.pa_smooth, 0};
+        any_track |= q.track >= 0;
+        any_nb |= q.aci_on != 0;
+    }
+    if (any_track && !h_track) return fail(WOFDM_E_INVALID, "NULL argument (h_track, and a point names a track)");
+    if (any_nb && !aci_active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active, and a point has aci_on)");
+    const aci_args aci = {aci_active, aci_h, 0, 0.f};
+    const sync_args sync = {n_points, spts.data(), sym_errs, sym_power};
+    const doppler_args dop = {h_track, n_tracks, n_knots, knot_step, nullptr, nullptr};
+    const pa_args amp = {n_points, apts.data(), ref_power, nullptr, nullptr, pa_power};
+    const pn_args pn = {n_points, npts.data(), nullptr, nullptr};
+    const link_args link = {n_points, points};
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, any_nb ? &aci : nullptr, &sync, any_track ? &dop : nullptr,
+                           &amp, &pn, &link, errs, err_power);
 }
 
 int wofdm_rx_profile_kernel_ms(float *ms)

@@ -3,7 +3,7 @@
 // wofdm_tx_psd_batch_masked), the Tx PAPR (wofdm_tx_papr) and the per-subcarrier receive profile (wofdm_rx_profile; beside an adjacent-band neighbour: wofdm_rx_profile_aci; under receiver timing and carrier offsets: wofdm_rx_profile_sync; over channels that move within the frame: wofdm_rx_profile_doppler; behind a nonlinear power amplifier: wofdm_rx_profile_pa, wofdm_tx_psd_batch_pa; under oscillator phase noise: wofdm_rx_profile_pn).  Compiled once per DFT length (-DWOFDM_TU_N=<N>, see the Makefile); wofdm_kernel.h dispatches
 // on n_fft through the unit's table of launchers (wofdm_aux_fns).
 #include "wofdm_kernel.h"
-#include "wofdm_pa.h"
+#include "wofdm_link.h"
 #include "wofdm_device.h"
 #include "philox.h"
 #include <type_traits>
@@ -1019,8 +1019,8 @@ __global__ void __launch_bounds__(WOFDM_PAPR_WAVES * 64) wofdm_papr_period_kerne
 }
 
 // ---------------------------------------------------------------------------------------------
-// Per-subcarrier BER and EVM of the frames the BER loop runs (wofdm_rx_profile and its five arms _aci, _sync, _doppler, _pa, _pn:
-// one body, rxprof_body<N, ARM> below, whose comment says what each arm adds): a second, unfused implementation of the
+// Per-subcarrier BER and EVM of the frames the BER loop runs (wofdm_rx_profile and its six arms _aci, _sync, _doppler, _pa, _pn,
+// _link: one body, rxprof_body<N, ARM> below, whose comment says what each arm adds): a second, unfused implementation of the
 // whole frame pipeline behind the Tx chain above,
 //   conv, add_wgn, truncate        matlab/main_BER_calculation.m:260-261, 277-294
 //   wofdm_rx                       main_BER_calculation.m:297-355 (Rx window, fold, circular shift, DFT)
@@ -1050,6 +1050,9 @@ template <int N> struct rxp_geo {
     static_assert(LDS_ACI <= 160 * 1024, "LDS (ACI arm)");
     static constexpr int LDS_DOP = LDS + 8 * WOFDM_DOPPLER_KNOTS * WOFDM_LT;   // the moving channel: a track's knots [64][21] float2
     static_assert(LDS_DOP <= 160 * 1024 && LDS % 8 == 0, "LDS (moving channel)");
+    // the link arm: the neighbour's row and the knots (75 776 B at N = 256, 129 024 B at N = 512, 131 584 B at N = 1024)
+    static constexpr int LDS_LINK = LDS + WAVES * 8 * XROW + 8 * WOFDM_DOPPLER_KNOTS * WOFDM_LT;
+    static_assert(LDS_LINK <= 160 * 1024, "LDS (link arm)");
 };
 
 // the complex unit normal of sample a of (seed, cell, frame): philox.h, block a / 2, words 2 (a % 2) and 2 (a % 2) + 1
@@ -1195,7 +1198,25 @@ __device__ __forceinline__ void fir_tap(const float2 hv, const float2 xv, float 
     ci = ci + im;
 }
 
-// The one body of the six receive kernels; ARM selects at compile time what an arm adds to the pipeline above, and the
+// One tap of the neighbour's 21-tap sum in the link arm, ar += hv.x xv.x - hv.y xv.y and ai += hv.x xv.y + hv.y xv.x, written
+// down like fir_tap and for the same reason: these are the operations the compiler forms today for the ACI arm's statements in
+// wofdm_rxprof_aci_kernel, at every N (read from its assembly) -- the first product of the real part fused onto the rounded
+// second; of the imaginary part the first product fused in the copy of rxs() for m0, the second in the copy for the folded
+// sample m0 + N --, whereas in the link arm's copy for m0 + N it fused the first: wofdm_rx_profile_link's neighbour-only point
+// then missed wofdm_rx_profile_aci's bytes wherever the Rx window has a tail.  The ACI arm keeps its statements: written down
+// like this its kernel computes the same values but is scheduled differently (the negation moves from the fma's addend into
+// the product), and the six earlier kernels are to come out instruction for instruction.
+template <bool FOLD>
+__device__ __forceinline__ void aci_tap(const float2 hv, const float2 xv, float &ar, float &ai)
+{
+#pragma clang fp contract(off)
+    const float re = __builtin_fmaf(hv.x, xv.x, -(hv.y * xv.y));
+    const float im = FOLD ? __builtin_fmaf(hv.y, xv.x, hv.x * xv.y) : __builtin_fmaf(hv.x, xv.y, hv.y * xv.x);
+    ar = ar + re;
+    ai = ai + im;
+}
+
+// The one body of the seven receive kernels; ARM selects at compile time what an arm adds to the pipeline above, and the
 // parameters of the other arms are not read.
 //   RXP_PLAIN    wofdm_rx_profile: nothing.
 //   RXP_ACI      wofdm_rx_profile_aci: the wave stages a second row with the neighbour's samples under the same window -- the
@@ -1226,17 +1247,29 @@ __device__ __forceinline__ void fir_tap(const float2 hv, const float2 xv, float 
 //                2e-7 rad for every beta and N, where the sync arm's in-window factor carries the rounding of eps m / N
 //                in single precision (which is what limits |cfo| there; no such limit here).  At beta = 0 turn = 0, t = 0
 //                exactly and the factor is exactly 1 under either flag: the point gives the plain kernel's bits.
+//   RXP_LINK     wofdm_rx_profile_link: every stage above at once, per point of lk (sp.n_points points; wofdm_link.h) -- each
+//                compile-time flag is "its arm or RXP_LINK".  Both passes run once per point on the point's waveform (pa) with
+//                the taps of the point's track (dp: the static channel is one more track, h at every knot, so there is one tap
+//                path); where the point's neighbour is on the air (wave-uniform) its row is staged with the point's offset and
+//                added with the point's amplitude; the windows begin at s B + gam + theta; the received sample is multiplied by
+//                the sync arm's factor (sp) and then by the phase noise's (pn), two multiplies, each exactly (1, 0) when neutral.
+//                Under a timing offset the walk is read at clamp(a, 0, S B - 1) -- the oscillator holds its phase outside the
+//                frame; at theta = 0 the clamp is never met --, the tracked mean over the same clamped values, and a sample
+//                before the frame (a < 0: every product is zero) takes its taps at time 0.  LDS: LDS_LINK.
 // The arms with a point loop (points, tracks) write the partials part_pow, part_cnt [job][point][N], and the wave of symbol
 // s >= 1 leaves beside them the symbol's sums over the loaded bins -- a lane's bins ascending, then papr_wave_reduce -- in
 // sym_pow, sym_cnt [job][point][S].  The pilot of a point sees what the point's data sees.  Where pass 1 runs per point, Ps
 // is the point's; Pn depends on neither channel nor waveform and is measured with the first.
-enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN };
+enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
 template <int N, int ARM>
 __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_aparams &ap, const wofdm_sparams &sp,
-                                            const wofdm_dparams &dp, const wofdm_paparams &pa, const wofdm_pnparams &pn)
+                                            const wofdm_dparams &dp, const wofdm_paparams &pa, const wofdm_pnparams &pn,
+                                            const wofdm_lparams &lk)
 {
     using RG = rxp_geo<N>;
-    constexpr bool ACI = ARM == RXP_ACI, SYNC = ARM == RXP_SYNC, DOP = ARM == RXP_DOPPLER, PA = ARM == RXP_PA, PN = ARM == RXP_PN;
+    constexpr bool LINK = ARM == RXP_LINK;
+    constexpr bool ACI = ARM == RXP_ACI || LINK, SYNC = ARM == RXP_SYNC || LINK, DOP = ARM == RXP_DOPPLER || LINK;
+    constexpr bool PA = ARM == RXP_PA || LINK, PN = ARM == RXP_PN || LINK;
     constexpr bool POINTS = SYNC || DOP || PA || PN, PASS1_PER_POINT = DOP || PA;
     constexpr int ROWLEN = N + (ACI ? 2 : 1) * RG::XROW;
     constexpr int W = RG::WAVES, NT = W * 64, LT = WOFDM_LT, BINS = RG::BINS, LOG2 = RG::LOG2;
@@ -1260,6 +1293,7 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
     const float2 *__restrict__ xi = ACI ? ap.xi + (size_t)job * ap.Ti : nullptr;
     const float2 *__restrict__ itaps = ACI ? ap.hi + (size_t)ch * LT : nullptr;
     [[maybe_unused]] const double *__restrict__ walk = PN ? pn.walk + (size_t)job * (size_t)(S * B) : nullptr;
+    [[maybe_unused]] const int walk_last = S * B - 1;                 // (LINK) the oscillator holds its phase outside the frame
     for (int i = tid; i < N / 2; i += NT) {
         float sv, cv;
         sincospif(-2.0f * (float)i / (float)N, &sv, &cv);
@@ -1332,7 +1366,8 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
         const float2 *__restrict__ x = (!PA || pa.pts[pt].model == WOFDM_PA_M_LINEAR) ? p.x + (size_t)job * T
                                                                                       : pa.y + ((size_t)job * NP + pt) * (size_t)T;
         if constexpr (DOP) {
-            const float2 *__restrict__ knots = dp.knots + ((size_t)pt * p.n_ch + ch) * (size_t)dp.n_knots * LT;
+            const int trk = LINK ? lk.pts[pt].track : pt;
+            const float2 *__restrict__ knots = dp.knots + ((size_t)trk * p.n_ch + ch) * (size_t)dp.n_knots * LT;
             for (int i = tid; i < dp.n_knots * LT; i += NT) kn[i] = knots[i];
             __syncthreads();
         }
@@ -1342,6 +1377,10 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
         [[maybe_unused]] const float turn = SYNC ? sp.pts[pt].eps * (1.0f / (float)N) : 0.f;   // (exact: N is a power of two)
         [[maybe_unused]] const double pn_turn = PN ? pn.pts[pt].turn : 0.0;
         [[maybe_unused]] const bool pn_tracked = PN ? pn.pts[pt].tracked != 0 : false;
+        // (LINK) the neighbour of the point: on the air or not (wave-uniform), its offset and amplitude
+        [[maybe_unused]] const bool nb_on = LINK ? lk.pts[pt].aci_on != 0 : ACI;
+        [[maybe_unused]] const int ioff = LINK ? lk.pts[pt].ioff : ap.ioff;
+        [[maybe_unused]] const float a_lvl = LINK ? lk.pts[pt].a_lvl : ap.a_lvl;
         const size_t slot = (size_t)job * NP + pt;
         float pw[BINS];
         uint32_t cnt[BINS];
@@ -1357,13 +1396,22 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
                 const int a0 = s * B + p.gam + theta;                 // first sample under the Rx window (m:442-454)
                 [[maybe_unused]] const float2 bs = SYNC ? sp.base[(size_t)pt * S + s] : make_float2(1.f, 0.f);
                 // (PN) the walk under the window, a0 + m < S B, and the common phase the point takes off it
+                // (LINK: a timing offset moves the window off [0, S B), and the index is clamped onto it)
                 [[maybe_unused]] const double *__restrict__ uw = PN ? walk + a0 : nullptr;
+                [[maybe_unused]] auto u_at = [&](int m) {
+                    if constexpr (LINK) {
+                        const int a = a0 + m;
+                        return walk[a < 0 ? 0 : (a > walk_last ? walk_last : a)];
+                    } else {
+                        return uw[m];
+                    }
+                };
                 [[maybe_unused]] double pn_c = 0.0;
                 if constexpr (PN) {
                     if (pn_tracked) {
-                        const double u0 = uw[0];
+                        const double u0 = u_at(0);
                         double acc = 0.0;
-                        for (int m = lane; m < N + delta; m += 64) acc += uw[m] - u0;
+                        for (int m = lane; m < N + delta; m += 64) acc += u_at(m) - u0;
                         pn_c = u0 + pn_wave_sum(acc) / (double)(N + delta);
                     }
                 }
@@ -1371,46 +1419,61 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
                     const int t = a0 - (LT - 1) + i;
                     xr[i] = (t >= 0 && t < T) ? x[t] : make_float2(0.f, 0.f);
                     if constexpr (ACI) {
-                        const int ti = t + ap.ioff;
-                        xir[i] = (ti >= 0 && ti < ap.Ti) ? xi[ti] : make_float2(0.f, 0.f);
+                        if (!LINK || nb_on) {
+                            const int ti = t + ioff;
+                            xir[i] = (ti >= 0 && ti < ap.Ti) ? xi[ti] : make_float2(0.f, 0.f);
+                        }
                     }
                 }
                 wave_sync();
                 // r[a] = conv[a] + g n[a] (m:260-261, 290-293) of the sample m under the window, a = a0 + m
                 auto rxs = [&](int m, auto fold) {
                     const uint32_t a = (uint32_t)(a0 + m);
-                    const auto tap = taps_at(a);
+                    // (LINK: before the frame every product is zero, and the tap time is 0, never a wrapped index)
+                    const auto tap = taps_at(LINK && a0 + m < 0 ? 0u : a);
                     float cr = 0.f, ci = 0.f;
 #pragma unroll
                     for (int l = 0; l < LT; ++l) fir_tap<decltype(fold)::value>(tap(l), xr[m + (LT - 1) - l], cr, ci);
                     if constexpr (ACI) {
-                        float ar = 0.f, ai = 0.f;
+                        if (!LINK || nb_on) {
+                            float ar = 0.f, ai = 0.f;
 #pragma unroll
-                        for (int l = 0; l < LT; ++l) {
-                            const float2 xv = xir[m + (LT - 1) - l], hv = itaps[l];
-                            ar += hv.x * xv.x - hv.y * xv.y;
-                            ai += hv.x * xv.y + hv.y * xv.x;
+                            for (int l = 0; l < LT; ++l) {
+                                const float2 xv = xir[m + (LT - 1) - l], hv = itaps[l];
+                                if constexpr (LINK) {
+                                    aci_tap<decltype(fold)::value>(hv, xv, ar, ai);
+                                } else {
+                                    ar += hv.x * xv.x - hv.y * xv.y;
+                                    ai += hv.x * xv.y + hv.y * xv.x;
+                                }
+                            }
+                            if constexpr (LINK) {
+                                cr = __builtin_fmaf(a_lvl, ar, cr);   // (cr += a_lvl ar as the aci kernel has it)
+                                ci = __builtin_fmaf(a_lvl, ai, ci);
+                            } else {
+                                cr += a_lvl * ar;
+                                ci += a_lvl * ai;
+                            }
                         }
-                        cr += ap.a_lvl * ar;
-                        ci += ap.a_lvl * ai;
                     }
                     const v2f nz = rxp_noise(a >> 1, f_lo, f_hi, cell, p.seed_lo, p.seed_hi, (int)(a & 1u));
-                    const float2 r = make_float2(cr + g * nz.x, ci + g * nz.y);
+                    float2 r = make_float2(cr + g * nz.x, ci + g * nz.y);
+                    // (LINK: the carrier offset's rotation, then the phase noise's; each is exactly (1, 0) when neutral)
                     if constexpr (SYNC) {                             // rotated by the oscillator's phase at m
                         float tn = turn * (float)m, sv, cv;
                         tn -= rintf(tn);
                         sincospif(2.0f * tn, &sv, &cv);
                         const float qr = bs.x * cv - bs.y * sv, qi = bs.x * sv + bs.y * cv;
-                        return make_float2(r.x * qr - r.y * qi, __builtin_fmaf(r.x, qi, r.y * qr));   // (r.x qi + r.y qr, written down likewise)
-                    } else if constexpr (PN) {                        // rotated by the oscillator's phase at a0 + m
-                        double td = (uw[m] - pn_c) * pn_turn;
+                        r = make_float2(r.x * qr - r.y * qi, __builtin_fmaf(r.x, qi, r.y * qr));   // (r.x qi + r.y qr, written down likewise)
+                    }
+                    if constexpr (PN) {                               // rotated by the oscillator's phase at a0 + m
+                        double td = (u_at(m) - pn_c) * pn_turn;
                         td -= rint(td);
                         float sv, cv;
                         sincospif(2.0f * (float)td, &sv, &cv);
-                        return make_float2(r.x * cv - r.y * sv, __builtin_fmaf(r.x, sv, r.y * cv));   // (the sync arm's forms)
-                    } else {
-                        return r;
+                        r = make_float2(r.x * cv - r.y * sv, __builtin_fmaf(r.x, sv, r.y * cv));   // (the sync arm's forms)
                     }
+                    return r;
                 };
 #pragma unroll 1
                 for (int j = 0; j < BINS; ++j) {
@@ -1512,35 +1575,43 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_kernel(const wofdm_rparams p)
 {
-    rxprof_body<N, RXP_PLAIN>(p, wofdm_aparams{}, wofdm_sparams{}, wofdm_dparams{}, wofdm_paparams{}, wofdm_pnparams{});
+    rxprof_body<N, RXP_PLAIN>(p, wofdm_aparams{}, wofdm_sparams{}, wofdm_dparams{}, wofdm_paparams{}, wofdm_pnparams{}, wofdm_lparams{});
 }
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_aci_kernel(const wofdm_rparams p, const wofdm_aparams ap)
 {
-    rxprof_body<N, RXP_ACI>(p, ap, wofdm_sparams{}, wofdm_dparams{}, wofdm_paparams{}, wofdm_pnparams{});
+    rxprof_body<N, RXP_ACI>(p, ap, wofdm_sparams{}, wofdm_dparams{}, wofdm_paparams{}, wofdm_pnparams{}, wofdm_lparams{});
 }
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_sync_kernel(const wofdm_rparams p, const wofdm_sparams sp)
 {
-    rxprof_body<N, RXP_SYNC>(p, wofdm_aparams{}, sp, wofdm_dparams{}, wofdm_paparams{}, wofdm_pnparams{});
+    rxprof_body<N, RXP_SYNC>(p, wofdm_aparams{}, sp, wofdm_dparams{}, wofdm_paparams{}, wofdm_pnparams{}, wofdm_lparams{});
 }
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_doppler_kernel(const wofdm_rparams p, const wofdm_sparams sp,
                                                                                      const wofdm_dparams dp)
 {
-    rxprof_body<N, RXP_DOPPLER>(p, wofdm_aparams{}, sp, dp, wofdm_paparams{}, wofdm_pnparams{});
+    rxprof_body<N, RXP_DOPPLER>(p, wofdm_aparams{}, sp, dp, wofdm_paparams{}, wofdm_pnparams{}, wofdm_lparams{});
 }
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_pa_kernel(const wofdm_rparams p, const wofdm_sparams sp,
                                                                                 const wofdm_paparams pa)
 {
-    rxprof_body<N, RXP_PA>(p, wofdm_aparams{}, sp, wofdm_dparams{}, pa, wofdm_pnparams{});
+    rxprof_body<N, RXP_PA>(p, wofdm_aparams{}, sp, wofdm_dparams{}, pa, wofdm_pnparams{}, wofdm_lparams{});
 }
 template <int N>
 __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_pn_kernel(const wofdm_rparams p, const wofdm_sparams sp,
                                                                                 const wofdm_pnparams pn)
 {
-    rxprof_body<N, RXP_PN>(p, wofdm_aparams{}, sp, wofdm_dparams{}, wofdm_paparams{}, pn);
+    rxprof_body<N, RXP_PN>(p, wofdm_aparams{}, sp, wofdm_dparams{}, wofdm_paparams{}, pn, wofdm_lparams{});
+}
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_link_kernel(const wofdm_rparams p, const wofdm_aparams ap,
+                                                                                  const wofdm_sparams sp, const wofdm_dparams dp,
+                                                                                  const wofdm_paparams pa, const wofdm_pnparams pn,
+                                                                                  const wofdm_lparams lk)
+{
+    rxprof_body<N, RXP_LINK>(p, ap, sp, dp, pa, pn, lk);
 }
 
 // totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
@@ -1943,7 +2014,7 @@ hipError_t papr_launch(const wofdm_pparams *pp, hipStream_t s)
     return hipGetLastError();
 }
 
-// What the six receive-profile launchers share.  The chunk of r is the chunk of pp's Tx chain, within the receive kernel's geometry:
+// What the seven receive-profile launchers share.  The chunk of r is the chunk of pp's Tx chain, within the receive kernel's geometry:
 bool rxprof_args_ok(const wofdm_pparams *pp, const wofdm_rparams &r)
 {
     constexpr int N = WOFDM_TU_N;
@@ -2113,11 +2184,70 @@ hipError_t rx_profile_pn_launch(const wofdm_pparams *pp, const wofdm_rparams *rp
     return hipGetLastError();
 }
 
+// wofdm_rx_profile_link, one chunk: the launchers above put together -- the Tx chain once, the neighbour's where a point wants it
+// (nbp), the points' waveforms and power sums, the items' unit walks, the receive body's link arm over the points,
+// rx_profile_sync's ordered sums and the amplifier's power sums
+hipError_t rx_profile_link_launch(const wofdm_pparams *pp, const wofdm_pparams *nbp, const wofdm_rparams *rp, const wofdm_aparams *app,
+                                  const wofdm_sparams *spp, const wofdm_dparams *dpp, const wofdm_paparams *pap,
+                                  const wofdm_pnparams *pnp, const wofdm_lparams *lkp, int n_tracks, int max_theta, hipStream_t s)
+{
+    constexpr int N = WOFDM_TU_N;
+    const wofdm_rparams &r = *rp;
+    const wofdm_aparams &a = *app;
+    const wofdm_sparams &sp = *spp;
+    const wofdm_dparams &dp = *dpp;
+    const wofdm_paparams &pa = *pap;
+    const wofdm_pnparams &pn = *pnp;
+    const wofdm_lparams &lk = *lkp;
+    if (!rxprof_args_ok(pp, r) || !rxprof_points_ok(sp, r, WOFDM_LINK_POINTS) || sp.pts == nullptr || sp.base == nullptr ||
+        pn.pts == nullptr || pn.walk == nullptr || lk.pts == nullptr || n_tracks < 1 || max_theta < 0 || max_theta >= r.B)
+        return hipErrorInvalidValue;
+    // the knots: rx_profile_doppler's conditions, and the samples a late window reaches
+    if (dp.knots == nullptr || dp.n_knots < 2 || dp.n_knots > WOFDM_DOPPLER_KNOTS || dp.knot_step < 1 ||
+        r.T + r.B + WOFDM_LT >= (1 << 22) ||
+        (int64_t)(dp.n_knots - 1) * dp.knot_step < (int64_t)(r.NL > r.T ? r.NL : r.T) - 1 + max_theta)
+        return hipErrorInvalidValue;
+    uint64_t cell0;
+    const unsigned n_cells = rxprof_cells(r, cell0);
+    // the amplifier: rx_profile_pa's conditions
+    if (pa.n_points != sp.n_points || pa.pairs < 1 || pa.pts == nullptr || pa.asat == nullptr || pa.y == nullptr || pa.pwr == nullptr ||
+        pa.pwr_tot == nullptr || r.x != pp->x || (cell0 + n_cells - 1) / pp->wdiv >= (uint64_t)pa.pairs)
+        return hipErrorInvalidValue;
+    // the neighbour: rx_profile_aci's conditions but for the offset, which is the points'
+    if (nbp != nullptr &&
+        (nbp->n_jobs != pp->n_jobs || nbp->item0 != pp->item0 || nbp->frames != pp->frames || nbp->frame_offset != pp->frame_offset ||
+         nbp->S != r.S + 1 || nbp->P != pp->P || nbp->beta != pp->beta || nbp->cp != pp->cp || nbp->cs != pp->cs ||
+         nbp->wdiv != pp->wdiv || a.Ti != r.T + r.B || a.xi != nbp->x || a.hi == nullptr || nbp->X == pp->X || nbp->x == pp->x ||
+         nbp->jobs == pp->jobs))
+        return hipErrorInvalidValue;
+    hipError_t e = tx_chain_launch(*pp, s);
+    if (e == hipSuccess && nbp != nullptr) e = tx_chain_launch(*nbp, s);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_link_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                rxp_geo<N>::LDS_LINK);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wofdm_pa_wave_kernel, dim3((unsigned)r.n_jobs, (unsigned)pa.n_points), dim3(256), 0, s, pa, r.x, r.T, r.item0,
+                       r.frames, pp->wdiv);
+    hipLaunchKernelGGL(wofdm_pn_walk_kernel, dim3((unsigned)r.n_jobs), dim3(1024), 0, s, pn.walk, r.S * r.B, r.seed_lo, r.seed_hi, r.item0,
+                       r.frames, r.frame_offset);
+    hipLaunchKernelGGL(wofdm_rxprof_link_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_LINK, s, r, a,
+                       sp, dp, pa, pn, lk);
+    rxprof_reduce_launch(r, &sp, s);
+    hipLaunchKernelGGL(wofdm_pa_power_reduce_kernel, dim3(n_cells), dim3(64), 0, s, pa, r.item0, r.n_jobs, r.frames, sp.cells, cell0);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
 {
     static const wofdm_pa_fns fns = {rx_profile_pa_launch, psd_batch_pa_launch};
+    return &fns;
+}
+
+const wofdm_link_fns *WOFDM_CAT(wofdm_aux_link_n, WOFDM_TU_N)(void)
+{
+    static const wofdm_link_fns fns = {rx_profile_link_launch};
     return &fns;
 }
 

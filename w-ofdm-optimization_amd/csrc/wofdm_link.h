@@ -1,0 +1,50 @@
+// wofdm_link.h -- the five impairments combined (wofdm_rx_profile_link): the parameters of the receive body's seventh arm
+// (wofdm_aux.hip) and its launcher, one table per DFT length beside wofdm_aux_fns and wofdm_pa_fns.  A header of its own:
+// wofdm_kernel.h is part of the frame kernels' source hash (profiles/hbm_traffic.json), and nothing here touches them
+// (GNUmakefile tells make which objects depend on this file, for the same reason).
+#pragma once
+#include "wofdm_pa.h"
+
+#define WOFDM_LINK_POINTS 16               // WOFDM_LINK_MAX_POINTS of include/wofdm.h
+
+// What a point of wofdm_rx_profile_link adds to the points of the arms it switches on: those stay where their arms read them --
+// the receiver offsets in wofdm_sparams (pts, base), the oscillator in wofdm_pnparams (pts), the amplifier in wofdm_paparams (pts,
+// y: the point's waveform) --, all with the link call's n_points points.
+struct wofdm_lpoint {
+    int32_t track;                    // row of wofdm_dparams' knots: a track of the call, or the static one behind them
+    int32_t aci_on;                   // the neighbour is on the air for this point
+    int32_t ioff;                     // B - aci_delay in [1, B]
+    float a_lvl;                      // 10^(aci_level_db / 20)
+};
+// A seventh argument of wofdm_rxprof_link_kernel.  wofdm_dparams' knots hold n_tracks + 1 tracks: behind the call's own the
+// static channel h at every knot, which is what a point without a track reads (with equal knots the tap is the knot, bit for
+// bit); wofdm_aparams' ioff and a_lvl are not read, its xi only where a point has aci_on.
+struct wofdm_lparams {
+    const wofdm_lpoint *pts;          // [n_points]
+};
+
+struct wofdm_link_fns {
+    // wofdm_rx_profile_link, one chunk: the Tx chain once, the neighbour's (nb != null: a point has aci_on) once, the points'
+    // amplified waveforms and power sums, the items' unit walks, wofdm_rxprof_link_kernel (both passes once per point),
+    // rx_profile_sync's ordered sums and the power sums in frame order.  n_tracks: the tracks of dp's knots, the static one
+    // included; max_theta: the largest timing offset of the points, or 0 (the knots cover the samples it reaches).
+    hipError_t (*rx_profile_link)(const wofdm_pparams *p, const wofdm_pparams *nb, const wofdm_rparams *r, const wofdm_aparams *a,
+                                  const wofdm_sparams *sp, const wofdm_dparams *dp, const wofdm_paparams *pa,
+                                  const wofdm_pnparams *pn, const wofdm_lparams *lk, int n_tracks, int max_theta, hipStream_t s);
+};
+const wofdm_link_fns *wofdm_aux_link_n64(void);
+const wofdm_link_fns *wofdm_aux_link_n128(void);
+const wofdm_link_fns *wofdm_aux_link_n256(void);
+const wofdm_link_fns *wofdm_aux_link_n512(void);
+const wofdm_link_fns *wofdm_aux_link_n1024(void);
+static inline const wofdm_link_fns *wofdm_aux_link(int n_fft)
+{
+    switch (n_fft) {
+    case 64: return wofdm_aux_link_n64();
+    case 128: return wofdm_aux_link_n128();
+    case 256: return wofdm_aux_link_n256();
+    case 512: return wofdm_aux_link_n512();
+    case 1024: return wofdm_aux_link_n1024();
+    }
+    return nullptr;
+}

@@ -28,6 +28,10 @@ limiter), a list of ``PaPoint`` per call, with the power before and behind the a
 ``rx_profile_pn_gpu`` (``wofdm_rx_profile_pn``) is the profile under oscillator phase noise, the receiver's phase a random walk
 drawn from Philox stream 3, a list of ``PnPoint`` (linewidth, free-running or common phase error tracked) per call;
 ``gen_pn_increments``, ``pn_walk``, ``frame_profile_pn`` and ``rx_profile_pn_host`` mirror it.
+
+``rx_profile_link_gpu`` (``wofdm_rx_profile_link``) is the profile with all five combined in one chain, a list of ``LinkPoint``
+per call, each switching on any subset; ``frame_profile_link`` and ``rx_profile_link_host`` mirror it, composed of the mirrors
+above.
 """
 import collections
 
@@ -160,7 +164,6 @@ def frame_profile_aci(st, grids, aci_grids, unit_noise, w_tx, w_rx, h, aci_h, de
     = 10^(level_db / 20); it passes aci_h [taps] (None: h) -- what it sent before t = 0 included --, and is added to the
     received samples after the noise: Ps, Pn and the noise gain are the victim's alone.  Returns what ``frame_profile``
     returns (with an all-zero aci_grids the same arrays); with_y=True: Y [S, N] as a sixth output."""
-    from . import timefreq as T
     Xi = np.asarray(aci_grids, dtype=np.complex128)
     S = np.asarray(grids).shape[0]
     B, d = st.sym_len - st.tail_tx, int(delay)
@@ -168,13 +171,18 @@ def frame_profile_aci(st, grids, aci_grids, unit_noise, w_tx, w_rx, h, aci_h, de
         raise ValueError("aci_grids must be [S + 1, %d]" % st.n_fft)
     if not 0 <= d < B:
         raise ValueError("delay must lie in [0, %d)" % B)
-    hi = np.asarray(h if aci_h is None else aci_h, dtype=np.complex128).reshape(-1)
-
     def beside(S_, B_):
-        xi = T.tx_waveform(st, Xi.T, np.asarray(w_tx, np.float64), st.tail_tx, mask, guard_band=None)
-        return 10.0 ** (0.05 * float(level_db)) * np.convolve(hi, xi)[B_ - d:B_ - d + S_ * B_]
+        return _aci_on_air(st, Xi, w_tx, h if aci_h is None else aci_h, level_db, mask)[B_ - d:B_ - d + S_ * B_]
     out = _frame_steps(st, grids, unit_noise, w_tx, w_rx, h, snr_db, bits_per_sc, active, mask, noise_before_truncate, beside)
     return out if with_y else out[:5]
+
+
+def _aci_on_air(st, Xi, w_tx, hi, level_db, mask):
+    """The neighbour of ``frame_profile_aci`` as received: 10^(level_db / 20) conv(hi, xi), xi the waveform of its grids Xi [S +
+    1, N] through the victim's Tx chain; the victim's on-air sample t carries element t + B - delay of it."""
+    from . import timefreq as T
+    xi = T.tx_waveform(st, np.asarray(Xi).T, np.asarray(w_tx, np.float64), st.tail_tx, mask, guard_band=None)
+    return 10.0 ** (0.05 * float(level_db)) * np.convolve(np.asarray(hi, dtype=np.complex128).reshape(-1), xi)
 
 
 # ---- the random streams of csrc/philox.h on the host ----
@@ -471,7 +479,7 @@ def rx_profile_aci_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db,
 
 def rx_profile_kernel_ms():
     """Milliseconds the kernels of this thread's last ``rx_profile_gpu``, ``rx_profile_aci_gpu``, ``rx_profile_sync_gpu``,
-    ``rx_profile_doppler_gpu``, ``rx_profile_pa_gpu`` or ``rx_profile_pn_gpu`` call took (``wofdm_rx_profile_kernel_ms``)."""
+    ``rx_profile_doppler_gpu``, ``rx_profile_pa_gpu``, ``rx_profile_pn_gpu`` or ``rx_profile_link_gpu`` call took (``wofdm_rx_profile_kernel_ms``)."""
     import ctypes as C
     from . import _lib
     ms = C.c_float()
@@ -500,8 +508,10 @@ def _sync_front(st, grids, noise_at, w_tx, h, snr_db, active, mask, noise_before
     return X, conv, np.sqrt(ps * 10.0 ** (-0.1 * float(snr_db)) / pn), on
 
 
-def _sync_point(st, front, noise_at, w_rx, point, bits_per_sc):
-    """One point on a frame's shared part: ``frame_profile_sync``'s outputs and Y [S, N]"""
+def _sync_point(st, front, noise_at, w_rx, point, bits_per_sc, beside=None, phase=None):
+    """One point on a frame's shared part: ``frame_profile_sync``'s outputs and Y [S, N].  ``frame_profile_link``'s further
+    stages, on the on-air indices a [S, N + delta] of the samples under the windows: beside(a) -> what another transmitter adds
+    to them (after the noise); phase(a) -> a second rotation behind the carrier offset's."""
     X, conv, g, on = front
     n, delta, gam, k = st.n_fft, st.tail_rx, st.prefix_rm, int(bits_per_sc)
     S, B = X.shape[0], st.sym_len - st.tail_tx
@@ -512,8 +522,11 @@ def _sync_point(st, front, noise_at, w_rx, point, bits_per_sc):
     a = (np.arange(S, dtype=np.int64) * B + gam + theta)[:, None] + m[None, :]          # on-air index of every sample used
     inside = (a >= 0) & (a < conv.size)
     r = np.where(inside, conv[np.clip(a, 0, conv.size - 1)], 0.0) + g * np.asarray(noise_at(a), dtype=np.complex128)
+    if beside is not None:
+        r = r + beside(a)
     turns = eps * (m[None, :] if point.cfo_tracked else a).astype(np.float64) / n      # (exact: 24 bits times an integer)
-    return _point_outputs(st, X, on, r * np.exp(2j * np.pi * (turns - np.round(turns))), w_rx, k)
+    r = r * np.exp(2j * np.pi * (turns - np.round(turns)))
+    return _point_outputs(st, X, on, r if phase is None else r * phase(a), w_rx, k)
 
 
 def _point_outputs(st, X, on, r, w_rx, k):
@@ -886,6 +899,15 @@ def pn_walk(n, seed, cell, frame):
     return np.cumsum(gen_pn_increments(n, seed, cell, frame))
 
 
+def _pn_turns(n_fft, u, a, q):
+    """The phase of the prepared point q in turns, t [S, N + delta], where the walk u is read at the indices a [S, N + delta]
+    (inside u), sigma / (2 pi), and the windows' mean walk ubar [S]"""
+    turn = np.sqrt(q.linewidth / (2.0 * np.pi * n_fft))               # sigma / (2 pi), from beta as stored
+    ubar = u[a[:, 0]] + np.mean(u[a] - u[a[:, :1]], axis=1)
+    t = (u[a] - ubar[:, None] if q.cpe_tracked else u[a]) * turn
+    return t, turn, ubar
+
+
 def _pn_point(st, front, noise_at, w_rx, walk, point, bits_per_sc, with_cpe=False):
     """One point on a frame's shared part and its unit walk [S B]: ``_sync_point``'s outputs; with_cpe=True: also sigma and
     the windows' mean walk ubar [S]"""
@@ -898,9 +920,7 @@ def _pn_point(st, front, noise_at, w_rx, walk, point, bits_per_sc, with_cpe=Fals
         raise ValueError("the walk holds %d samples, %d needed" % (u.size, S * B))
     a = (np.arange(S, dtype=np.int64) * B + gam)[:, None] + np.arange(n + delta, dtype=np.int64)[None, :]   # all in [0, S B)
     r = conv[a] + g * np.asarray(noise_at(a), dtype=np.complex128)
-    turn = np.sqrt(q.linewidth / (2.0 * np.pi * n))                   # sigma / (2 pi), from beta as stored
-    ubar = u[a[:, 0]] + np.mean(u[a] - u[a[:, :1]], axis=1)
-    t = (u[a] - ubar[:, None] if q.cpe_tracked else u[a]) * turn
+    t, turn, ubar = _pn_turns(n, u, a, q)
     out = _point_outputs(st, X, on, r * np.exp(2j * np.pi * (t - np.round(t))), w_rx, int(bits_per_sc))
     return out + (2.0 * np.pi * turn, ubar) if with_cpe else out
 
@@ -963,3 +983,197 @@ def rx_profile_pn_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, 
     cpts = (_lib.PnPoint * len(pts))(*[_lib.PnPoint(q.linewidth, q.cpe_tracked, (C.c_int32 * 2)(0, 0)) for q in pts])
     return _gpu_call("wofdm_rx_profile_pn", RxProfileSync, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
                      noise_before_truncate, device, out, lead=(len(pts),), after_mask=(len(pts), cpts))
+
+
+# ---- the five impairments combined (wofdm_rx_profile_link) ----
+
+LinkPoint = collections.namedtuple("LinkPoint", "pa track timing cfo cfo_tracked linewidth cpe_tracked aci",
+                                   defaults=(None, None, 0, 0.0, 1, 0.0, 0, None))
+LinkPoint.__doc__ = """One point of ``wofdm_rx_profile_link``, every field "off" by default: pa (a ``PaPoint`` or None: no amplifier),
+track (index into the call's tracks, or None: the static channel h), timing, cfo, cfo_tracked (``SyncPoint``'s), linewidth,
+cpe_tracked (``PnPoint``'s), aci ((delay, level_db) of the neighbour, or None: none on the air)."""
+
+RxProfileLink = collections.namedtuple("RxProfileLink", RxProfilePa._fields)
+RxProfileLink.__doc__ = """``RxProfilePa``'s fields with the points of ``wofdm_rx_profile_link`` on the leading axis; pa_power of a
+point without an amplifier is {sum |x|^2, sum |x|^2}."""
+
+
+def _link_prepare(st, points, n_tracks):
+    """The points as the library reads them (single-precision values, None for what is off), checked against its limits"""
+    B = st.sym_len - st.tail_tx
+    pts = []
+    for q in points:
+        q = LinkPoint(*q)
+        pa = None if q.pa is None else _pa_point(q.pa)
+        track = None if q.track is None or int(q.track) == -1 else int(q.track)
+        sync = _prepare_sync([(q.timing, q.cfo, q.cfo_tracked)])[0]
+        pn = _pn_prepare([(q.linewidth, q.cpe_tracked)])[0]
+        aci = None if q.aci is None else (int(q.aci[0]), float(np.float32(q.aci[1])))
+        if track is not None and not 0 <= track < n_tracks:
+            raise ValueError("a point's track must be None or in [0, %d): %r" % (n_tracks, q))
+        if abs(sync.timing) >= B or not abs(sync.cfo) <= 4.0 or sync.cfo_tracked not in (0, 1):
+            raise ValueError("a point needs |timing| < %d, |cfo| <= 4 and cfo_tracked in (0, 1): %r" % (B, q))
+        if aci is not None and (not 0 <= aci[0] < B or not np.isfinite(aci[1])):
+            raise ValueError("a point's neighbour needs 0 <= delay < %d and a finite level: %r" % (B, q))
+        pts.append(LinkPoint(pa, track, sync.timing, sync.cfo, sync.cfo_tracked, pn.linewidth, pn.cpe_tracked, aci))
+    if not pts:
+        raise ValueError("at least one point is needed")
+    return pts
+
+
+def _link_front(st, grids, noise_at, w_tx, h, track, knot_step, pa, ref_power, snr_db, active, mask, noise_before_truncate):
+    """``_sync_front`` of a point's waveform and channel -- ``pa_apply`` (pa None: x itself), then ``tv_conv`` with the track
+    [n_knots, taps] or (None) conv with h --, and the two power sums of ``frame_profile_pa``"""
+    power = np.zeros(2)
+
+    def channel(x):
+        y = x if pa is None else pa_apply(x, pa, ref_power)
+        power[:] = (np.abs(x) ** 2).sum(), (np.abs(y) ** 2).sum()
+        return np.convolve(np.asarray(h, dtype=np.complex128).reshape(-1), y) if track is None else tv_conv(track, knot_step, y)
+    return _sync_front(st, grids, noise_at, w_tx, None, snr_db, active, mask, noise_before_truncate, channel=channel), power
+
+
+def _link_walk_index(a, n):
+    """The walk's index of the on-air index a: clamped onto [0, n), n = S B -- the oscillator holds its phase outside the frame"""
+    return np.clip(np.asarray(a, dtype=np.int64), 0, n - 1)
+
+
+def _link_point(st, front, power, noise_at, w_rx, walk, on_air, point, bits_per_sc):
+    """One prepared point on its front: ``_sync_point`` with the neighbour ``on_air`` (``_aci_on_air`` at amplitude 1, or None)
+    at the point's level and offset beside the received samples, and ``_pn_turns`` of the clamped walk behind the carrier
+    offset's rotation.  Returns ``frame_profile_pa``'s nine outputs and Y."""
+    S, B = front[0].shape[0], st.sym_len - st.tail_tx
+    u = np.asarray(walk, dtype=np.float64).reshape(-1)
+    if u.size < S * B:
+        raise ValueError("the walk holds %d samples, %d needed" % (u.size, S * B))
+    beside = None
+    if point.aci is not None and on_air is not None:
+        d, lvl = point.aci
+
+        def beside(a):
+            i = a + (B - d)
+            return 10.0 ** (0.05 * lvl) * np.where((i >= 0) & (i < on_air.size), on_air[np.clip(i, 0, on_air.size - 1)], 0.0)
+
+    def phase(a):
+        t = _pn_turns(st.n_fft, u, _link_walk_index(a, S * B), PnPoint(point.linewidth, point.cpe_tracked))[0]
+        return np.exp(2j * np.pi * (t - np.round(t)))
+    out = _sync_point(st, front, noise_at, w_rx, SyncPoint(point.timing, point.cfo, point.cfo_tracked), bits_per_sc, beside, phase)
+    return out[:8] + (power, out[8])
+
+
+def frame_profile_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, walk, track=None, knot_step=None,
+                       ref_power=None, aci_grids=None, aci_h=None, active=None, mask=None, noise_before_truncate=1, with_y=False):
+    """fp64 host mirror of one frame and one point of ``wofdm_rx_profile_link``, composed of the arms' own mirrors: the Tx chain
+    of ``frame_profile``; ``pa_apply`` (point.pa, ``ref_power``); ``tv_conv`` with ``track`` [n_knots, taps] -- the row of the
+    call's tracks the point names, for the cell's channel -- or conv with h; the neighbour of ``frame_profile_aci`` (aci_grids [S
+    + 1, N] through aci_h, None: h) at point.aci = (delay, level_db); Ps, Pn and g of the point's waveform and channel alone;
+    the windows of ``frame_profile_sync`` at point.timing, its rotation, and then ``frame_profile_pn``'s with the unit walk
+    ``walk`` [>= S B] read at clamp(a, 0, S B - 1), the tracked mean over the same clamped values.  noise_at(idx) as
+    ``frame_profile_sync``'s.  Returns what ``frame_profile_pa`` returns: (bit_err [N], sym_err [N], err_power [N], xhat [S-1, N],
+    y0 [N], bit_err_sym [S-1], sym_err_sym [S-1], err_power_sym [S-1], pa_power [2]); with_y=True: Y [S, N] as a tenth."""
+    q = _link_prepare(st, [LinkPoint(*point)._replace(track=None)], 0)[0]
+    if track is not None:
+        q = q._replace(track=0)
+    front, power = _link_front(st, grids, noise_at, w_tx, h, track, knot_step, q.pa, ref_power, snr_db, active, mask,
+                               noise_before_truncate)
+    on_air = None
+    if q.aci is not None:
+        if np.asarray(aci_grids).shape != (np.asarray(grids).shape[0] + 1, st.n_fft):
+            raise ValueError("aci_grids must be [S + 1, %d]" % st.n_fft)
+        on_air = _aci_on_air(st, aci_grids, w_tx, h if aci_h is None else aci_h, 0.0, mask)
+    out = _link_point(st, front, power, noise_at, w_rx, walk, on_air, q, bits_per_sc)
+    return out if with_y else out[:9]
+
+
+def _link_sides(st, hc, points, tracks, aci_active, aci_h, ref_power, pairs):
+    """The prepared side arguments of a link call: points, tracks [n_tracks, n_ch, n_knots, taps] or None, the neighbour's
+    allocation and channels or None, the reference powers [pairs] or None"""
+    tr = None if tracks is None else _prepare_tracks(tracks)
+    if tr is not None and (tr.shape[1] != hc.shape[0] or tr.shape[3] != hc.shape[1]):
+        raise ValueError("tracks must have the channels and taps of h, %s" % (hc.shape,))
+    pts = _link_prepare(st, points, 0 if tr is None else tr.shape[0])
+    iact = hi = ref = None
+    if any(q.aci is not None for q in pts):
+        if aci_active is None:
+            raise ValueError("a point has a neighbour: aci_active is needed")
+        iact, hi = _prepare_aci(st, hc, aci_active, aci_h, 0, 0.0)[:2]
+    if any(q.pa is not None and q.pa.model != PA_LINEAR for q in pts):
+        if ref_power is None:
+            raise ValueError("a point has an amplifier: ref_power is needed")
+    if ref_power is not None:
+        ref = _prepare_pa([PaPoint(PA_LINEAR, 0.0)], ref_power, pairs)[1]
+    return pts, tr, iact, hi, ref
+
+
+def rx_profile_link_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points,
+                         tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None, mask=None,
+                         noise_before_truncate=1, with_near=False):
+    """The host route of ``rx_profile_link_gpu``: the frames of ``rx_profile_host`` from the same Philox streams, each through
+    ``frame_profile_link``'s steps for every point of ``points`` (``LinkPoint`` or tuples in its order); the labels, the noise,
+    the unit walk and the neighbour of a frame are shared by its points, the waveform and the channel by the points with the
+    same amplifier and track.  Returns ``RxProfileLink``; with_near=True: also the number of ``near_decisions`` per point and cell
+    [points, pairs, n_snr, n_ch]."""
+    from . import timefreq as T
+
+    def arm(q):
+        pts, tr, iact, hi, ref = _link_sides(st, q.hc, points, tracks, aci_active, aci_h, ref_power, q.w_tx.shape[0])
+        B = st.sym_len - st.tail_tx
+        nb = iact is not None and iact.any()
+        # the sample indices a frame's points read, as one range (``rx_profile_sync_host``'s)
+        lo = min(0, st.prefix_rm + min(pt.timing for pt in pts))
+        hi_ = max(q.noise_len, (q.S - 1) * B + st.prefix_rm + max(pt.timing for pt in pts) + st.n_fft + st.tail_rx)
+        tab = T.qam_table(q.k)
+
+        def frame(p, s, c, cell, fr, grid):
+            noise_at = _noise_lookup(gen_noise_at(np.arange(lo, hi_, dtype=np.int64), seed, cell, fr), lo)
+            walk = pn_walk(q.S * B, seed, cell, fr)
+            on_air = None
+            if nb:
+                igrid = tab[gen_labels(st.n_fft, q.k, q.S + 1, seed, cell, fr, STREAM_ACI)] * (iact != 0)[None, :]
+                on_air = _aci_on_air(st, igrid, q.w_tx[p], q.hc[c] if hi is None else hi[c], 0.0, q.m)
+            fronts = {}
+            for pt in pts:
+                key = (pt.pa, pt.track)
+                if key not in fronts:
+                    fronts[key] = _link_front(st, grid, noise_at, q.w_tx[p], q.hc[c], None if pt.track is None else tr[pt.track, c],
+                                              knot_step, pt.pa, None if ref is None else ref[p], q.snr[s], q.act, q.m, q.nbt)
+                yield _link_point(st, *fronts[key], noise_at, q.w_rx[p], walk, on_air, pt, q.k)[:9]
+        return (len(pts),), frame
+    return _host_sweep(RxProfileLink, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames,
+                       active, mask, noise_before_truncate, with_near)
+
+
+def rx_profile_link_chunk_frames(st, syms, masked, n_points, neighbour):
+    """Frames one chunk of ``wofdm_rx_profile_link`` holds (include/wofdm.h): ``rx_profile_pa_chunk_frames``' bytes plus the
+    frame's unit walk, S B doubles, plus -- neighbour: a point has one on the air -- ``rx_profile_aci_chunk_frames``' buffers of
+    the neighbour; at most 65535."""
+    B = st.sym_len - st.tail_tx
+    return _chunk_frames(st, syms, masked, per_point=st.n_fft + syms + st.tail_tx + syms * B, n_points=n_points,
+                         per_frame_extra=syms * B, neighbour=bool(neighbour))
+
+
+def rx_profile_link_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, tracks=None,
+                        knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None, mask=None,
+                        noise_before_truncate=1, device=0, out=None):
+    """``wofdm_rx_profile_link``: ``rx_profile_gpu`` of the same arguments with the five impairments combined, for every point of
+    ``points`` (``LinkPoint`` or tuples in its order, at most ``_lib.LINK_MAX_POINTS``) in ONE call -- amplifier, moving channel
+    (``tracks`` [n_tracks, n_ch, n_knots, taps] and ``knot_step`` as ``rx_profile_doppler_gpu``'s), neighbour (``aci_active``,
+    ``aci_h`` as ``rx_profile_aci_gpu``'s), receiver offsets and phase noise, each as its own call has it.  ``tracks``,
+    ``aci_active`` and ``ref_power`` are needed only where a point uses them.  A point with one impairment on returns the bytes
+    of that impairment's own call.  Returns ``RxProfileLink``; ``out`` (an earlier result of the same shape) is accumulated
+    into.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts, tr, iact, hi, ref = _link_sides(st, prepared[2], points, tracks, aci_active, aci_h, ref_power, prepared[0].shape[0])
+    trf = None if tr is None else _lib.c64_as_f32(tr)
+    hif = None if hi is None else _lib.c64_as_f32(hi)
+    lin = PaPoint(PA_LINEAR, 0.0)
+    cpts = (_lib.LinkPoint * len(pts))(*[
+        _lib.LinkPoint(*(q.pa or lin), -1 if q.track is None else q.track, q.timing, q.cfo, q.cfo_tracked, q.linewidth, q.cpe_tracked,
+                       int(q.aci is not None), *(q.aci or (0, 0.0)), (C.c_int32 * 4)(0, 0, 0, 0)) for q in pts])
+    knots = (0, 0, 0) if tr is None else (tr.shape[0], tr.shape[2], int(knot_step))
+    return _gpu_call("wofdm_rx_profile_link", RxProfileLink, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                     noise_before_truncate, device, out, lead=(len(pts),),
+                     after_mask=(None if trf is None else trf.ctypes.data, *knots, None if iact is None else iact.ctypes.data,
+                                 None if hif is None else hif.ctypes.data, None if ref is None else ref.ctypes.data, len(pts), cpts))
