@@ -776,6 +776,77 @@ int wofdm_rx_profile_link(const wofdm_cfg *cfg, int device,
                           double *sym_power,                /* [n_points][cells][S-1], or NULL */
                           double *pa_power);                /* [n_points][cells][2], or NULL */
 
+/* wofdm_rx_profile_link with SOFT decisions: beside the hard counters of every point, what a coded receiver could carry -- the
+ * bit-interleaved coded modulation (BICM) rate, the generalized mutual information (GMI) of the max-log bit metrics the
+ * demapper would hand a decoder, per bin and per data symbol.  At the error rates the combined impairments give, uncoded BER is
+ * set by the few bins in a null and ranks window pairs otherwise than the rate does; EVM cannot stand in for it, the
+ * disturbance (regrowth, ICI, phase noise) not being Gaussian.
+ *   Definition.  For a point, a loaded bin n and a data symbol s >= 1 of a frame, with the quantities of the link chain:
+ *     e      = G[n] Y_s[n], the equalised value the slicer sees, G[n] = X_0[n] / Y_0[n] the point's pilot equaliser;
+ *     v      = g^2 Pn / NL, the per-sample noise variance add_wgn put on the air for this frame and point -- g, Pn, NL exactly
+ *              what pass 1 measures (v = Ps / NL 10^(-snr / 10)); where pass 1 runs per point, the point's;
+ *     W2     = sum_{m < n_fft + tail_rx} w_rx[m]^2 of the pair, formed on the host in double precision, passed in single;
+ *     nu[n]  = |G[n]|^2 v W2, the noise variance the receiver would ASSUME on the bin: it never sees the neighbour, the
+ *              offsets, the phase or the amplifier's distortion -- hence the scales below;
+ *     L_i    = ( min_{x: bit_i(x) = 1} |e - x|^2 - min_{x: bit_i(x) = 0} |e - x|^2 ) / nu[n], the max-log metric of bit i of the
+ *              label, i = 0 the top bit, over the unit-power constellation with the slicer's MATLAB Gray labelling; L_i > 0
+ *              decides for bit 0, and its sign is the slicer's decision.  The kernel forms the difference per axis (the other
+ *              axis' distance is common to both minima), at most 8 levels per axis;
+ *     pen_j  = sum_{i < k} log2(1 + exp(-(1 - 2 b_i) c_j L_i)), b_i the transmitted bit, for every scale c_j of the call,
+ *              evaluated as max(-z, 0) + log1p(exp(-|z|)) in base 2 with the hardware exp2 / log2 (below 2^-6 the log1p is
+ *              its series, so the small penalties keep their relative accuracy).
+ *   The call accumulates bit_penalty[point][cell][scale][n], the sum of pen_j over the frames and data symbols, and
+ * sym_penalty[point][cell][scale][s - 1], the sum over the frames and loaded bins.  k - penalty / decisions is an achievable
+ * rate for EVERY scale, so the caller takes the maximum over the scales -- per bin, per symbol or per cell.  The matched scale
+ * is not 1: the pilot's own noise alone pushes it to about 0.5, interference the receiver does not model far lower (0.01 where
+ * ISI dominates), and an octave grid gives up as much as 10 % of the rate against a fine one -- so a list, 1 <= n_scales <=
+ * WOFDM_SOFT_MAX_SCALES, each finite and positive.
+ *   Order of additions: a wave writes the penalties of its symbol's bins, fp32, to a scratch [frame][point][S-1][scale][n_fft]
+ * and leaves their sum over the loaded bins -- a lane's bins n = lane + 64 j ascending, then the wave sum of the per-symbol
+ * error power -- beside it; a second kernel adds, per (point, scale, bin), the data symbols of a frame ascending in single
+ * precision; a third makes ONE addition per frame onto the running fp64 total of the cell, frames ascending (the same for the
+ * symbols' sums).
+ * No float atomics; repeated calls give identical bytes, the totals do not depend on where a chunk ends, a scale's results do
+ * not depend on which other scales share its call, nor a point's on the other points.  Unloaded bins are exactly 0; a loaded bin
+ * with Y_0 = 0 behaves as err_power does.
+ *   The five outputs of wofdm_rx_profile_link are, for the same cfg, seed and points, the BYTES of wofdm_rx_profile_link (as
+ * long as no cell's frames are split over two chunks of either call): the hard counters and powers are produced by the same
+ * statements.
+ *   Every argument, limit and check of wofdm_rx_profile_link applies.  WOFDM_E_INVALID: NULL scales or bit_penalty, n_scales <
+ * 1, a scale that is not finite or not positive; WOFDM_E_UNSUPPORTED: n_scales > WOFDM_SOFT_MAX_SCALES.  Every argument is
+ * checked before the device is touched; a failed call leaves all seven outputs as they were.
+ *   Chunks: min(65535, WOFDM_RX_PROFILE_CHUNK_BYTES / (wofdm_rx_profile_link's bytes of a frame + 4 n_points n_scales ((S - 1)
+ * n_fft + S)))  frames -- the link call's formula plus the fp32 penalties of every (point, scale): per data symbol the bins, and
+ * the symbols' sums.
+ *   A successful call holds the launch gate and counts for wofdm_rx_profile_kernel_ms.
+ *   Measured on an MI355X (tools/bench_rx_profile_soft.py, profiles/rx_profile_soft.txt): on 64 cells x 2000 frames x 16 symbols
+ * at n_fft = 256 an all-off point takes 96.2 ms of kernels with one scale and 136.7 ms with sixteen (masked 123.0 and 166.1 ms),
+ * 1.40 and 1.98 (1.33 and 1.80) times wofdm_rx_profile_link with the same point in the same run; the everything-on point 122.4
+ * and 175.7 (176.3 and 211.9) ms, 1.37 and 1.97 (1.23 and 1.48) times -- about 30 ms that do not depend on the scales and 0.02 to
+ * 0.04 of a link call per further scale.  Other n_fft: not measured. */
+#define WOFDM_SOFT_MAX_SCALES 16
+int wofdm_rx_profile_soft(const wofdm_cfg *cfg, int device,
+                          const float *w_tx,                /* [pairs][P] */
+                          const float *w_rx,                /* [pairs][N+tail_rx] */
+                          const float *h,                   /* [n_channels][n_taps][2] */
+                          const float *snr_db,              /* [n_snr] */
+                          const uint8_t *active,            /* [n_fft] or NULL */
+                          const float *tx_mask,             /* [2P-1] or NULL */
+                          const float *h_track,             /* [n_tracks][n_channels][n_knots][n_taps][2], or NULL */
+                          int32_t n_tracks, int32_t n_knots, int32_t knot_step,
+                          const uint8_t *aci_active,        /* [n_fft], or NULL */
+                          const float *aci_h,               /* [n_channels][n_taps][2], or NULL = h */
+                          const float *ref_power,           /* [pairs], or NULL */
+                          int32_t n_points, const wofdm_link_point *points,
+                          int32_t n_scales, const float *scales,
+                          uint64_t *errs,                   /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                          double *err_power,                /* [n_points][cells][n_fft], or NULL */
+                          uint64_t *sym_errs,               /* [n_points][cells][S-1][2], or NULL */
+                          double *sym_power,                /* [n_points][cells][S-1], or NULL */
+                          double *pa_power,                 /* [n_points][cells][2], or NULL */
+                          double *bit_penalty,              /* [n_points][cells][n_scales][n_fft], ACCUMULATED into */
+                          double *sym_penalty);             /* [n_points][cells][n_scales][S-1], or NULL */
+
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

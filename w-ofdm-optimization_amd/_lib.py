@@ -38,6 +38,8 @@ PA_MAX_POINTS = 16
 PN_MAX_POINTS = 16
 #: wofdm_rx_profile_link (include/wofdm.h): most points one call takes
 LINK_MAX_POINTS = 16
+#: wofdm_rx_profile_soft (include/wofdm.h): most scales one call takes
+SOFT_MAX_SCALES = 16
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -51,7 +53,7 @@ EXPORTS = (
     "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms", "wofdm_plan_kernel_geo", "wofdm_cfg_geo_id",
     "wofdm_rx_profile_aci", "wofdm_rx_profile_sync", "wofdm_rx_profile_doppler",
     "wofdm_rx_profile_pa", "wofdm_tx_psd_batch_pa", "wofdm_rx_profile_pn",
-    "wofdm_rx_profile_link",
+    "wofdm_rx_profile_link", "wofdm_rx_profile_soft",
 )
 
 
@@ -194,6 +196,8 @@ def load():
     L.wofdm_rx_profile_pn.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, i32, C.POINTER(PnPoint), vp, vp, vp, vp]
     L.wofdm_rx_profile_link.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
                                         C.POINTER(LinkPoint), vp, vp, vp, vp, vp]
+    L.wofdm_rx_profile_soft.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
+                                        C.POINTER(LinkPoint), i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_tx_psd_batch_pa.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, C.POINTER(PaPoint), vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L

@@ -101,7 +101,8 @@ def _profiles_per_pair(arm, plan, alloc, mask, head, ensemble, frame_range, gpu,
 
     def of_pair(prof, i):
         # (RxProfile's arrays begin with the pair axis, the others' with the point or track axis)
-        return type(prof)(*(a[i] if type(prof) is R.RxProfile else a[:, i] for a in prof[:-1]), prof.decisions)
+        # (a one-dimensional field -- the scales of RxProfileSoft -- belongs to every pair)
+        return type(prof)(*(a[i] if type(prof) is R.RxProfile else a if a.ndim == 1 else a[:, i] for a in prof[:-1]), prof.decisions)
     return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
 
 
@@ -423,6 +424,30 @@ def link_for_window_file(type_ofdm, cp, windows, channels, snr_db, points, track
     side = (tracks, knot_step, ~alloc if any(q.aci is not None for q in pts) else None, aci_channels)
     return _profiles_per_pair("_link", plan, alloc, mask, head, ensemble, frame_range, gpu, device, tail=(pts, *side, ref[0]),
                               tail_masked=(pts, *side, ref[1]))
+
+
+def soft_for_window_file(type_ofdm, cp, windows, channels, snr_db, points=None, scales=None, tracks=None, knot_step=None,
+                         aci_channels=None, num_subcar=256, bits_per_subcar=4, symbols_per_tx=16, ensemble=100, roll_off=ROLL_OFF,
+                         seed=0, frame_range=None, gpu=True, device=0, tail_tx=8, tail_rx=10):
+    """``link_for_window_file`` with soft decisions: the same pairs, frames, points (None: one all-off point) and side arguments,
+    and for the scales ``scales`` (None: ``rx_profile.SOFT_SCALES``) the penalties from which ``rx_profile.gmi_per_bin``,
+    ``gmi_per_symbol`` and ``gmi`` form the rate a coded receiver could carry -- what ranks window pairs where the uncoded error
+    rates are far above anything a link runs at.  On the GPU two ``wofdm_rx_profile_soft`` calls whatever the number of points
+    and scales (gpu=False: ``rx_profile.rx_profile_soft_host``).  Returns {name: {"profile", "profile_masked"}}, each an
+    ``rx_profile.RxProfileSoft`` of that pair, arrays [points, n_snr, n_channels, ...]; its hard fields are
+    ``link_for_window_file``'s."""
+    from . import rx_profile as R
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off)
+    pts = [R.LinkPoint()] if points is None else [R.LinkPoint(*q) for q in points]
+    first, count = _frames(ensemble, frame_range)
+    ref = [None, None]
+    if any(q.pa is not None for q in pts):
+        ref = [R.pa_ref_power(st, bits_per_subcar, symbols_per_tx, w_tx, seed, first, count, active=alloc, mask=m, gpu=gpu,
+                              **(dict(device=device) if gpu else {})) for m in (None, mask)]
+    head = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.atleast_2d(np.asarray(channels)), snr_db, seed)
+    side = (tracks, knot_step, ~alloc if any(q.aci is not None for q in pts) else None, aci_channels)
+    return _profiles_per_pair("_soft", plan, alloc, mask, head, ensemble, frame_range, gpu, device, tail=(pts, scales, *side, ref[0]),
+                              tail_masked=(pts, scales, *side, ref[1]))
 
 
 def results_from_counts(names, masked, plain):

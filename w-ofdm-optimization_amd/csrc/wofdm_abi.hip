@@ -1611,14 +1611,22 @@ struct link_args {
     int32_t n_points;
     const wofdm_link_point *points;
 };
+// the soft outputs of wofdm_rx_profile_soft beside a link call's arguments (checked by its entry point); a null pointer to it is
+// wofdm_rx_profile_link
+struct soft_args {
+    int32_t n_scales;
+    const float *scales;
+    double *bit_penalty;
+    double *sym_penalty;
+};
 
 // wofdm_rx_profile, wofdm_rx_profile_aci, wofdm_rx_profile_sync, wofdm_rx_profile_doppler, wofdm_rx_profile_pa,
 // wofdm_rx_profile_pn and wofdm_rx_profile_link.  Every argument is checked before the first HIP call; the
 // caller's arrays are written only after everything has succeeded.
 int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                     const float *snr_db, const uint8_t *active, const float *tx_mask, const aci_args *aci, const sync_args *sync,
-                    const doppler_args *dop, const pa_args *amp, const pn_args *pn, const link_args *link, uint64_t *errs,
-                    double *err_power)
+                    const doppler_args *dop, const pa_args *amp, const pn_args *pn, const link_args *link, const soft_args *soft,
+                    uint64_t *errs, double *err_power)
 {
     // (the link call has the static channel beside its tracks, and needs no reference power where every point is linear)
     if (!cfg || !w_tx || !w_rx || !(dop && !link ? dop->h_track : h) || (dop && !dop->h_track) || !snr_db || !errs)
@@ -1817,7 +1825,9 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
     const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) +
                                        (link ? (uint64_t)NP * (uint64_t)(N + S + T) : sync || dop || pn ? (uint64_t)NP * (uint64_t)(N + S) : (amp ? (uint64_t)NP * (uint64_t)(N + S + T) : (uint64_t)N)) +
                                        (pn ? (uint64_t)S * B : 0ull) +
-                                       (nb ? (uint64_t)(S + 1) * N + (uint64_t)Ti + (tx_mask ? (uint64_t)(S + 1) * Lm : 0ull) : 0ull));
+                                       (nb ? (uint64_t)(S + 1) * N + (uint64_t)Ti + (tx_mask ? (uint64_t)(S + 1) * Lm : 0ull) : 0ull)) +
+                               // (the soft call: per point and scale the penalties of every data symbol's bins and the symbols' sums, fp32)
+                               (soft ? 4ull * (uint64_t)NP * (uint64_t)soft->n_scales * ((uint64_t)(S - 1) * N + (uint64_t)S) : 0ull);
     const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
                                                                        std::max<uint64_t>(1, WOFDM_RX_PROFILE_CHUNK_BYTES / job_bytes)));
     std::vector<float2> hspec;
@@ -1912,6 +1922,28 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         if (!d_lkpts.alloc(hlk.size())) return fail(WOFDM_E_NOMEM, "device allocation failed (link points)");
         if (!d_lkpts.upload(hlk.data(), hlk.size())) return fail(WOFDM_E_HIP, "upload failed");
     }
+    // the demapper's side: the pairs' W2 = sum w_rx^2 (double, stored in single), the chunk's penalties, the totals
+    dev_buf<float> d_w2, d_bpart, d_spart;
+    dev_buf<double> d_btot, d_sptot;
+    const size_t NSC = soft ? (size_t)soft->n_scales : 0, n_bpen = (size_t)NP * cells * NSC * N, n_spen = (size_t)NP * cells * NSC * (S - 1);
+    wofdm_softparams sopar{};
+    if (soft) {
+        std::vector<float> hw2((size_t)pairs);
+        for (uint64_t p = 0; p < pairs; ++p) {
+            double acc = 0.0;
+            for (int m = 0; m < NW; ++m) acc += (double)w_rx[p * NW + m] * (double)w_rx[p * NW + m];
+            hw2[(size_t)p] = (float)acc;
+        }
+        if (!d_w2.alloc(hw2.size()) || !d_bpart.alloc((size_t)chunk * NP * (S - 1) * NSC * N) ||
+            !d_spart.alloc((size_t)chunk * NP * NSC * S) || !d_btot.alloc(n_bpen) || !d_sptot.alloc(n_spen))
+            return fail(WOFDM_E_NOMEM, "device allocation failed (soft outputs)");
+        if (!d_w2.upload(hw2.data(), hw2.size()) || hipMemset(d_btot, 0, n_bpen * 8) != hipSuccess ||
+            hipMemset(d_sptot, 0, n_spen * 8) != hipSuccess)
+            return fail(WOFDM_E_HIP, "upload failed");
+        sopar.n_scales = soft->n_scales;
+        for (int j = 0; j < soft->n_scales; ++j) sopar.cs[j] = (float)((double)soft->scales[j] * 1.4426950408889634074);
+        sopar.w2 = d_w2; sopar.bit_part = d_bpart; sopar.sym_part = d_spart; sopar.bit_tot = d_btot; sopar.sym_tot = d_sptot;
+    }
     // the neighbour's side of the chunk: allocation, channels, and grids, waveforms, tables of its S + 1 symbols
     dev_buf<uint8_t> d_iact;
     dev_buf<float2> d_hi, d_Xi, d_xi, d_Yi;
@@ -1968,7 +2000,7 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         apar.a_lvl = (float)std::pow(10.0, 0.05 * (double)aci->level_db);
     }
     std::vector<unsigned long long> herr(2 * n_out), hserr(2 * n_sym);
-    std::vector<double> hpow(n_out), hspow(n_sym), hptot(n_ptot);
+    std::vector<double> hpow(n_out), hspow(n_sym), hptot(n_ptot), hbpen(n_bpen), hspen(n_spen);
     float ms = 0.f;
     hipError_t e = hipSuccess;
     {
@@ -1984,7 +2016,8 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
             pp.n_jobs = rp.n_jobs = (int32_t)std::min<uint64_t>(chunk, items - i0);
             pa.item0 = pp.item0;
             pa.n_jobs = pp.n_jobs;
-            e = link ? axl->rx_profile_link(&pp, nb ? &pa : nullptr, &rp, &apar, &spar, &dpar, &papar, &pnpar, &lkpar, NTR + 1, max_theta, nullptr)
+            e = soft ? axl->rx_profile_soft(&pp, nb ? &pa : nullptr, &rp, &apar, &spar, &dpar, &papar, &pnpar, &lkpar, &sopar, NTR + 1, max_theta, nullptr)
+                : link ? axl->rx_profile_link(&pp, nb ? &pa : nullptr, &rp, &apar, &spar, &dpar, &papar, &pnpar, &lkpar, NTR + 1, max_theta, nullptr)
                 : amp ? axp->rx_profile_pa(&pp, &rp, &spar, &papar, nullptr)
                 : dop ? ax->rx_profile_doppler(&pp, &rp, &spar, &dpar, nullptr)
                 : sync ? ax->rx_profile_sync(&pp, &rp, &spar, nullptr)
@@ -2001,7 +2034,9 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         hipMemcpy(hpow.data(), d_pow, n_out * 8, hipMemcpyDeviceToHost) != hipSuccess ||
         (n_sym && (hipMemcpy(hserr.data(), d_serrs, 2 * n_sym * 8, hipMemcpyDeviceToHost) != hipSuccess ||
                    hipMemcpy(hspow.data(), d_stot, n_sym * 8, hipMemcpyDeviceToHost) != hipSuccess)) ||
-        (n_ptot && hipMemcpy(hptot.data(), d_ptot, n_ptot * 8, hipMemcpyDeviceToHost) != hipSuccess))
+        (n_ptot && hipMemcpy(hptot.data(), d_ptot, n_ptot * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (n_bpen && (hipMemcpy(hbpen.data(), d_btot, n_bpen * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                    hipMemcpy(hspen.data(), d_sptot, n_spen * 8, hipMemcpyDeviceToHost) != hipSuccess)))
         return fail(WOFDM_E_HIP, "receive-profile kernels or copy-back failed: %s",
                     hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
     for (size_t i = 0; i < 2 * n_out; ++i) errs[i] += herr[i];
@@ -2015,6 +2050,11 @@ int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const f
         for (size_t i = 0; i < n_sym; ++i) sym_power[i] += hspow[i];
     if (amp && amp->pa_power)
         for (size_t i = 0; i < n_ptot; ++i) amp->pa_power[i] += hptot[i];
+    if (soft) {
+        for (size_t i = 0; i < n_bpen; ++i) soft->bit_penalty[i] += hbpen[i];
+        if (soft->sym_penalty)
+            for (size_t i = 0; i < n_spen; ++i) soft->sym_penalty[i] += hspen[i];
+    }
     g_rxprof_ms = ms;
     return WOFDM_OK;
 }
@@ -2026,7 +2066,7 @@ extern "C" {
 int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                      const float *snr_db, const uint8_t *active, const float *tx_mask, uint64_t *errs, double *err_power)
 {
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -2034,7 +2074,7 @@ int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, co
                          const float *aci_h, int32_t aci_delay, float aci_level_db, uint64_t *errs, double *err_power)
 {
     const aci_args aci = {aci_active, aci_h, aci_delay, aci_level_db};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
@@ -2042,7 +2082,7 @@ int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, c
                           const wofdm_sync_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const sync_args sync = {n_points, points, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, nullptr, nullptr, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h_track,
@@ -2050,7 +2090,7 @@ int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device, const float *w_tx
                              const float *tx_mask, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const doppler_args dop = {h_track, n_tracks, n_knots, knot_step, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask, nullptr, nullptr, &dop, nullptr, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask, nullptr, nullptr, &dop, nullptr, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
@@ -2059,7 +2099,7 @@ int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device, const float *w_tx, con
                         double *pa_power)
 {
     const pa_args amp = {n_points, points, ref_power, sym_errs, sym_power, pa_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, &amp, nullptr, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, &amp, nullptr, nullptr, nullptr, errs, err_power);
 }
 
 int wofdm_rx_profile_pn(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
@@ -2067,14 +2107,15 @@ int wofdm_rx_profile_pn(const wofdm_cfg *cfg, int device, const float *w_tx, con
                         double *err_power, uint64_t *sym_errs, double *sym_power)
 {
     const pn_args pn = {n_points, points, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, &pn, nullptr, errs, err_power);
+    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, &pn, nullptr, nullptr, errs, err_power);
 }
 
-int wofdm_rx_profile_link(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
-                          const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
-                          int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
-                          const wofdm_link_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power,
-                          double *pa_power)
+// wofdm_rx_profile_link and (soft) wofdm_rx_profile_soft
+static int rx_profile_link_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                                const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                                int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power,
+                                int32_t n_points, const wofdm_link_point *points, const soft_args *soft, uint64_t *errs,
+                                double *err_power, uint64_t *sym_errs, double *sym_power, double *pa_power)
 {
     if (!points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
     if (n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", n_points);
@@ -2101,7 +2142,34 @@ int wofdm_rx_profile_link(const wofdm_cfg *cfg, int device, const float *w_tx, c
     const pn_args pn = {n_points, npts.data(), nullptr, nullptr};
     const link_args link = {n_points, points};
     return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, any_nb ? &aci : nullptr, &sync, any_track ? &dop : nullptr,
-                           &amp, &pn, &link, errs, err_power);
+                           &amp, &pn, &link, soft, errs, err_power);
+}
+
+int wofdm_rx_profile_link(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                          const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                          int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
+                          const wofdm_link_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power,
+                          double *pa_power)
+{
+    return rx_profile_link_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active,
+                                aci_h, ref_power, n_points, points, nullptr, errs, err_power, sym_errs, sym_power, pa_power);
+}
+
+int wofdm_rx_profile_soft(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                          const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                          int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
+                          const wofdm_link_point *points, int32_t n_scales, const float *scales, uint64_t *errs, double *err_power,
+                          uint64_t *sym_errs, double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty)
+{
+    if (!scales || !bit_penalty) return fail(WOFDM_E_INVALID, "NULL argument (scales or bit_penalty)");
+    if (n_scales < 1) return fail(WOFDM_E_INVALID, "n_scales=%d must be >= 1", n_scales);
+    if (n_scales > WOFDM_SOFT_MAX_SCALES) return fail(WOFDM_E_UNSUPPORTED, "n_scales=%d exceeds %d", n_scales, WOFDM_SOFT_MAX_SCALES);
+    for (int j = 0; j < n_scales; ++j)
+        if (!std::isfinite(scales[j]) || !(scales[j] > 0.f))
+            return fail(WOFDM_E_INVALID, "scales[%d] must be finite and positive", j);
+    const soft_args soft = {n_scales, scales, bit_penalty, sym_penalty};
+    return rx_profile_link_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active,
+                                aci_h, ref_power, n_points, points, &soft, errs, err_power, sym_errs, sym_power, pa_power);
 }
 
 int wofdm_rx_profile_kernel_ms(float *ms)

@@ -1216,6 +1216,109 @@ __device__ __forceinline__ void aci_tap(const float2 hv, const float2 xv, float 
     ai = ai + im;
 }
 
+// log2(1 + x) for 0 <= x <= 1 with the hardware logarithm: below 2^-6 the rounding of 1 + x would cost 2^-24 / x of the
+// result, and the series x log2(e) (1 - x / 2 + x^2 / 3) is good to x^3 / 4 <= 2^-20 there; above, 1 + x carries 2^-18 at most.
+__device__ __forceinline__ float soft_log2_1p(float x)
+{
+    const float ser = x * 1.4426950408889634f * __builtin_fmaf(x, __builtin_fmaf(x, 0.33333333f, -0.5f), 1.0f);
+    return x < 0.015625f ? ser : __builtin_amdgcn_logf(1.0f + x);
+}
+
+// The demapper of wofdm_rxprof_soft_kernel (wofdm_softparams, wofdm_link.h) for the wave's data symbol s >= 1: row = the symbol's
+// DFT outputs, G the point's pilot equaliser, Xs the transmitted points, vw = v W2.  Per loaded bin n = lane + 64 j, j ascending:
+//   e = G[n] row[n], rn = 1 / (a^2 |G[n]|^2 vw), a the constellation's scale (levels 2 l - (m - 1) over a per axis, m = 2^(k/2));
+//   per axis and bit position of the axis' Gray index the smallest squared distance, in level units, to a level whose bit is 1
+//   and to one whose bit is 0 -- the other axis' distance is common to both minima and cancels in their difference --, so
+//   z_i = (1 - 2 b_i) Lambda_i = (1 - 2 b_i) (min1 - min0) rn, i = 0 the top bit of the label (the I axis' top bit), b_i the
+//   transmitted bit (the label of Xs as rxp_slice reads it);
+//   per scale j: pen_j = sum_i [max(-t, 0) + log2(1 + 2^-|t|)], t = cs[j] z_i, i ascending, with v_exp_f32 / v_log_f32.
+// pen_j goes to bit_part[slot][s - 1][j][n] (0 on an unloaded bin: every element of the symbol's rows is written), the lane's
+// sum over its bins, then the wave's (papr_wave_reduce), to sym_part[slot][j][s].  The bins' loop is not unrolled -- 16 scales
+// times 6 bits of exp2 / log2 pairs are code enough once -- and the scales' loop is, so that the lane's sums stay in registers.
+template <int N>
+__device__ __forceinline__ void soft_symbol(const wofdm_rparams &p, const wofdm_softparams &so, const float2 *row, const float2 *G,
+                                            const float2 *__restrict__ Xs, float vw, size_t slot, int s, int lane)
+{
+    constexpr int BINS = N / 64, SC = WOFDM_SOFT_SCALES;
+    const int k = p.k, hb = k >> 1, mm = (1 << hb) - 1, nsc = so.n_scales, S = p.S;
+    const float a = k == 2 ? 1.4142135623730951f : (k == 4 ? 3.1622776601683795f : 6.4807406984078604f);
+    float *__restrict__ bp = so.bit_part + (slot * (size_t)(S - 1) + (size_t)(s - 1)) * (size_t)nsc * N;
+    float ssum[SC];
+#pragma unroll
+    for (int j = 0; j < SC; ++j) ssum[j] = 0.f;
+#pragma unroll 1
+    for (int j = 0; j < BINS; ++j) {
+        const int n = lane + 64 * j;
+        const bool on = p.amask == nullptr || p.amask[n] != 0;
+        const float2 y = row[n], gq = G[n], xs = Xs[n];
+        const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;
+        const float rn = 1.0f / (a * a * (gq.x * gq.x + gq.y * gq.y) * vw);
+        const uint32_t lab = rxp_slice(k, xs.x, xs.y);
+        // z[i], i = 0 ... k - 1: the I axis' bits from its top one, then the Q axis'
+        float z[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ax = 0; ax < 2; ++ax) {
+            const float u = ax == 0 ? er * a : -ei * a;               // level units: the levels are 2 l - mm, l = 0 ... mm
+            float m0[3], m1[3];
+#pragma unroll
+            for (int b = 0; b < 3; ++b) m0[b] = m1[b] = 3.0e38f;
+#pragma unroll
+            for (int l = 0; l < 8; ++l) {
+                if (l <= mm) {
+                    const float t = u - (float)(2 * l - mm), d = t * t;
+                    const int gry = l ^ (l >> 1);
+#pragma unroll
+                    for (int b = 0; b < 3; ++b) {
+                        if ((gry >> b) & 1)
+                            m1[b] = fminf(m1[b], d);
+                        else
+                            m0[b] = fminf(m0[b], d);
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                // bit i of the axis from the top: position hb - 1 - i of the Gray index, hb - 1 - i + (I axis: hb) of the label
+                float lam = 0.f;
+                uint32_t bit = 0u;
+#pragma unroll
+                for (int b = 0; b < 3; ++b)
+                    if (b == hb - 1 - i) {
+                        lam = (m1[b] - m0[b]) * rn;
+                        bit = (lab >> (ax == 0 ? b + hb : b)) & 1u;
+                    }
+                const float zz = bit ? -lam : lam;
+#pragma unroll
+                for (int q = 0; q < 6; ++q)
+                    if (q == ax * hb + i && i < hb) z[q] = zz;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < SC; ++c) {
+            if (c < nsc) {
+                const float cs = so.cs[c];
+                float pen = 0.f;
+#pragma unroll
+                for (int i = 0; i < 6; ++i)
+                    if (i < k) {
+                        const float t = cs * z[i];
+                        pen += fmaxf(-t, 0.f) + soft_log2_1p(__builtin_amdgcn_exp2f(-fabsf(t)));
+                    }
+                pen = on ? pen : 0.f;
+                bp[(size_t)c * N + n] = pen;
+                ssum[c] += pen;
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < SC; ++c) {
+        if (c < nsc) {
+            const float t = papr_wave_reduce<false>(ssum[c]);
+            if (lane == 0) so.sym_part[(slot * (size_t)nsc + (size_t)c) * (size_t)S + (size_t)s] = t;
+        }
+    }
+}
+
 // The one body of the seven receive kernels; ARM selects at compile time what an arm adds to the pipeline above, and the
 // parameters of the other arms are not read.
 //   RXP_PLAIN    wofdm_rx_profile: nothing.
@@ -1256,16 +1359,19 @@ __device__ __forceinline__ void aci_tap(const float2 hv, const float2 xv, float 
 //                Under a timing offset the walk is read at clamp(a, 0, S B - 1) -- the oscillator holds its phase outside the
 //                frame; at theta = 0 the clamp is never met --, the tracked mean over the same clamped values, and a sample
 //                before the frame (a < 0: every product is zero) takes its taps at time 0.  LDS: LDS_LINK.
+//   SOFT         (RXP_LINK only: wofdm_rx_profile_soft) behind pass 1 the point's v W2, and behind the hard decisions of every data
+//                symbol the demapper soft_symbol above; with the flag false no statement of the body changes.
 // The arms with a point loop (points, tracks) write the partials part_pow, part_cnt [job][point][N], and the wave of symbol
 // s >= 1 leaves beside them the symbol's sums over the loaded bins -- a lane's bins ascending, then papr_wave_reduce -- in
 // sym_pow, sym_cnt [job][point][S].  The pilot of a point sees what the point's data sees.  Where pass 1 runs per point, Ps
 // is the point's; Pn depends on neither channel nor waveform and is measured with the first.
 enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
-template <int N, int ARM>
+template <int N, int ARM, bool SOFT = false>
 __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_aparams &ap, const wofdm_sparams &sp,
                                             const wofdm_dparams &dp, const wofdm_paparams &pa, const wofdm_pnparams &pn,
-                                            const wofdm_lparams &lk)
+                                            const wofdm_lparams &lk, [[maybe_unused]] const wofdm_softparams &so = wofdm_softparams{})
 {
+    static_assert(!SOFT || ARM == RXP_LINK, "the demapper is instantiated for the link arm only");
     using RG = rxp_geo<N>;
     constexpr bool LINK = ARM == RXP_LINK;
     constexpr bool ACI = ARM == RXP_ACI || LINK, SYNC = ARM == RXP_SYNC || LINK, DOP = ARM == RXP_DOPPLER || LINK;
@@ -1372,6 +1478,13 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
             __syncthreads();
         }
         if constexpr (PASS1_PER_POINT) g = pass1(x, pt == 0);
+        // (SOFT) v W2 of the point: v = g^2 Pn / NL, Pn the sum pass 1 formed (its partials stay in red), W2 the pair's
+        [[maybe_unused]] float soft_vw = 0.f;
+        if constexpr (SOFT) {
+            float Pn = 0.f;
+            for (int w = 0; w < W; ++w) Pn += red[W + w];
+            soft_vw = g * g * Pn / (float)NL * so.w2[pair];
+        }
         // pass 2
         const int theta = SYNC ? sp.pts[pt].theta : 0;
         [[maybe_unused]] const float turn = SYNC ? sp.pts[pt].eps * (1.0f / (float)N) : 0.f;   // (exact: N is a power of two)
@@ -1545,6 +1658,9 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
                         sp.sym_cnt[slot * S + s] = scn;
                     }
                 }
+                if constexpr (SOFT) {
+                    if (s >= 1) soft_symbol<N>(p, so, buf, G, Xg + (size_t)s * N, soft_vw, slot, s, lane);
+                }
             }
             wave_sync();
         }
@@ -1613,6 +1729,15 @@ __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_link_kern
 {
     rxprof_body<N, RXP_LINK>(p, ap, sp, dp, pa, pn, lk);
 }
+// wofdm_rx_profile_soft: the link arm with the demapper (soft_symbol) behind the hard decisions of every data symbol
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_soft_kernel(const wofdm_rparams p, const wofdm_aparams ap,
+                                                                                  const wofdm_sparams sp, const wofdm_dparams dp,
+                                                                                  const wofdm_paparams pa, const wofdm_pnparams pn,
+                                                                                  const wofdm_lparams lk, const wofdm_softparams so)
+{
+    rxprof_body<N, RXP_LINK, true>(p, ap, sp, dp, pa, pn, lk, so);
+}
 
 // totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
 template <int N>
@@ -1669,6 +1794,59 @@ __global__ void __launch_bounds__(64) wofdm_rxprof_sync_reduce_kernel(const wofd
     terr[2 * out] += be;
     terr[2 * out + 1] += se;
     tot[out] = acc;
+}
+
+// The ordered sums of wofdm_rx_profile_soft, first step: the penalties of a frame's data symbols s = 1 ... S - 1, ascending in
+// single precision from the first, per (item, point, scale, bin); the sum takes the place of the first symbol's element of
+// bit_part.  One thread per element, every element of the chunk at once -- the second step's loop over the frames is serial,
+// and S - 1 loads per frame inside it made the call six times the link call's length.
+template <int N>
+__global__ void __launch_bounds__(256) wofdm_rxprof_soft_frame_kernel(const wofdm_softparams so, int S, size_t n_elems)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;          // (slot, scale, n)
+    if (e >= n_elems) return;
+    const size_t row = (size_t)so.n_scales * N, slot = e / row;
+    float *q = so.bit_part + slot * (size_t)(S - 1) * row + (e - slot * row);
+    float f = q[0];
+    for (int s = 2; s < S; ++s) f += q[(size_t)(s - 1) * row];
+    q[0] = f;
+}
+
+// Second step: bit_tot[point][cell][scale][n] += the frames' sums of the chunk's items of the cell, one addition per frame
+// onto the running fp64 total, frames ascending, so the totals do not depend on where a chunk ends; grid (N / 64 + 1, cells the
+// chunk touches, points x scales) -- the last block of x adds the symbols' sums sym_part onto
+// sym_tot[point][cell][scale][s - 1] the same way.  Eight frames' loads are in flight at a time; the additions stay in order.
+template <int N>
+__global__ void __launch_bounds__(64) wofdm_rxprof_soft_reduce_kernel(const wofdm_rparams p, const wofdm_sparams sp,
+                                                                      const wofdm_softparams so, uint64_t cell0)
+{
+    const bool syms = blockIdx.x == N / 64;
+    const int S = p.S, nsc = so.n_scales;
+    const int n = syms ? (int)threadIdx.x + 1 : (int)(blockIdx.x * 64 + threadIdx.x);
+    if (syms && n >= S) return;
+    const uint64_t cell = cell0 + blockIdx.y, end = p.item0 + (uint64_t)p.n_jobs;
+    const uint64_t lo = cell * p.frames > p.item0 ? cell * p.frames : p.item0;
+    const uint64_t hi = (cell + 1) * p.frames < end ? (cell + 1) * p.frames : end;
+    if (lo >= hi) return;
+    const uint32_t pt = blockIdx.z / (uint32_t)nsc, sc = blockIdx.z - pt * (uint32_t)nsc;
+    const size_t cellrow = ((size_t)pt * sp.cells + cell) * (size_t)nsc + sc;
+    double *tot = syms ? so.sym_tot + cellrow * (size_t)(S - 1) + (size_t)(n - 1) : so.bit_tot + cellrow * N + n;
+    // the element of item 0 of the chunk, and the distance from an item to the next
+    const size_t per_item = (size_t)sp.n_points * (size_t)nsc * (syms ? (size_t)S : (size_t)(S - 1) * N);
+    const float *src = syms ? so.sym_part + ((size_t)pt * nsc + sc) * (size_t)S + (size_t)n
+                            : so.bit_part + ((size_t)pt * (size_t)(S - 1) * nsc + sc) * N + n;
+    double acc = *tot;
+    uint64_t i = lo - p.item0;
+    const uint64_t stop = hi - p.item0;
+    for (; i + 8 <= stop; i += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = src[(size_t)(i + u) * per_item];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += (double)v[u];
+    }
+    for (; i < stop; ++i) acc += (double)src[(size_t)i * per_item];
+    *tot = acc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2187,9 +2365,10 @@ hipError_t rx_profile_pn_launch(const wofdm_pparams *pp, const wofdm_rparams *rp
 // wofdm_rx_profile_link, one chunk: the launchers above put together -- the Tx chain once, the neighbour's where a point wants it
 // (nbp), the points' waveforms and power sums, the items' unit walks, the receive body's link arm over the points,
 // rx_profile_sync's ordered sums and the amplifier's power sums
-hipError_t rx_profile_link_launch(const wofdm_pparams *pp, const wofdm_pparams *nbp, const wofdm_rparams *rp, const wofdm_aparams *app,
-                                  const wofdm_sparams *spp, const wofdm_dparams *dpp, const wofdm_paparams *pap,
-                                  const wofdm_pnparams *pnp, const wofdm_lparams *lkp, int n_tracks, int max_theta, hipStream_t s)
+// (sop: wofdm_rx_profile_soft -- the same chunk through wofdm_rxprof_soft_kernel, and its own ordered sums behind the others)
+hipError_t link_chunk_launch(const wofdm_pparams *pp, const wofdm_pparams *nbp, const wofdm_rparams *rp, const wofdm_aparams *app,
+                             const wofdm_sparams *spp, const wofdm_dparams *dpp, const wofdm_paparams *pap, const wofdm_pnparams *pnp,
+                             const wofdm_lparams *lkp, const wofdm_softparams *sop, int n_tracks, int max_theta, hipStream_t s)
 {
     constexpr int N = WOFDM_TU_N;
     const wofdm_rparams &r = *rp;
@@ -2220,21 +2399,53 @@ hipError_t rx_profile_link_launch(const wofdm_pparams *pp, const wofdm_pparams *
          nbp->wdiv != pp->wdiv || a.Ti != r.T + r.B || a.xi != nbp->x || a.hi == nullptr || nbp->X == pp->X || nbp->x == pp->x ||
          nbp->jobs == pp->jobs))
         return hipErrorInvalidValue;
+    // the demapper: its scales and scratch
+    if (sop != nullptr && (sop->n_scales < 1 || sop->n_scales > WOFDM_SOFT_SCALES || sop->w2 == nullptr || sop->bit_part == nullptr ||
+                           sop->sym_part == nullptr || sop->bit_tot == nullptr || sop->sym_tot == nullptr))
+        return hipErrorInvalidValue;
     hipError_t e = tx_chain_launch(*pp, s);
     if (e == hipSuccess && nbp != nullptr) e = tx_chain_launch(*nbp, s);
     if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_link_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                rxp_geo<N>::LDS_LINK);
+        e = hipFuncSetAttribute(sop != nullptr ? reinterpret_cast<const void *>(wofdm_rxprof_soft_kernel<N>)
+                                               : reinterpret_cast<const void *>(wofdm_rxprof_link_kernel<N>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, rxp_geo<N>::LDS_LINK);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(wofdm_pa_wave_kernel, dim3((unsigned)r.n_jobs, (unsigned)pa.n_points), dim3(256), 0, s, pa, r.x, r.T, r.item0,
                        r.frames, pp->wdiv);
     hipLaunchKernelGGL(wofdm_pn_walk_kernel, dim3((unsigned)r.n_jobs), dim3(1024), 0, s, pn.walk, r.S * r.B, r.seed_lo, r.seed_hi, r.item0,
                        r.frames, r.frame_offset);
-    hipLaunchKernelGGL(wofdm_rxprof_link_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_LINK, s, r, a,
-                       sp, dp, pa, pn, lk);
+    if (sop != nullptr)
+        hipLaunchKernelGGL(wofdm_rxprof_soft_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_LINK, s, r,
+                           a, sp, dp, pa, pn, lk, *sop);
+    else
+        hipLaunchKernelGGL(wofdm_rxprof_link_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_LINK, s, r,
+                           a, sp, dp, pa, pn, lk);
     rxprof_reduce_launch(r, &sp, s);
     hipLaunchKernelGGL(wofdm_pa_power_reduce_kernel, dim3(n_cells), dim3(64), 0, s, pa, r.item0, r.n_jobs, r.frames, sp.cells, cell0);
+    if (sop != nullptr) {
+        const size_t n_elems = (size_t)r.n_jobs * (size_t)sp.n_points * (size_t)sop->n_scales * N;
+        hipLaunchKernelGGL(wofdm_rxprof_soft_frame_kernel<N>, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, s, *sop, r.S, n_elems);
+        hipLaunchKernelGGL(wofdm_rxprof_soft_reduce_kernel<N>, dim3(N / 64 + 1, n_cells, (unsigned)(sp.n_points * sop->n_scales)),
+                           dim3(64), 0, s, r, sp, *sop, cell0);
+    }
     return hipGetLastError();
+}
+
+hipError_t rx_profile_link_launch(const wofdm_pparams *pp, const wofdm_pparams *nbp, const wofdm_rparams *rp, const wofdm_aparams *app,
+                                  const wofdm_sparams *spp, const wofdm_dparams *dpp, const wofdm_paparams *pap,
+                                  const wofdm_pnparams *pnp, const wofdm_lparams *lkp, int n_tracks, int max_theta, hipStream_t s)
+{
+    return link_chunk_launch(pp, nbp, rp, app, spp, dpp, pap, pnp, lkp, nullptr, n_tracks, max_theta, s);
+}
+
+// wofdm_rx_profile_soft, one chunk
+hipError_t rx_profile_soft_launch(const wofdm_pparams *pp, const wofdm_pparams *nbp, const wofdm_rparams *rp, const wofdm_aparams *app,
+                                  const wofdm_sparams *spp, const wofdm_dparams *dpp, const wofdm_paparams *pap,
+                                  const wofdm_pnparams *pnp, const wofdm_lparams *lkp, const wofdm_softparams *sop, int n_tracks,
+                                  int max_theta, hipStream_t s)
+{
+    if (sop == nullptr) return hipErrorInvalidValue;
+    return link_chunk_launch(pp, nbp, rp, app, spp, dpp, pap, pnp, lkp, sop, n_tracks, max_theta, s);
 }
 
 }  // namespace
@@ -2247,7 +2458,7 @@ const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
 
 const wofdm_link_fns *WOFDM_CAT(wofdm_aux_link_n, WOFDM_TU_N)(void)
 {
-    static const wofdm_link_fns fns = {rx_profile_link_launch};
+    static const wofdm_link_fns fns = {rx_profile_link_launch, rx_profile_soft_launch};
     return &fns;
 }
 

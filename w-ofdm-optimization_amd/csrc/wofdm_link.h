@@ -1,5 +1,6 @@
 // wofdm_link.h -- the five impairments combined (wofdm_rx_profile_link): the parameters of the receive body's seventh arm
-// (wofdm_aux.hip) and its launcher, one table per DFT length beside wofdm_aux_fns and wofdm_pa_fns.  A header of its own:
+// (wofdm_aux.hip) and its launcher, one table per DFT length beside wofdm_aux_fns and wofdm_pa_fns; and the same arm with soft
+// decisions (wofdm_rx_profile_soft).  A header of its own:
 // wofdm_kernel.h is part of the frame kernels' source hash (profiles/hbm_traffic.json), and nothing here touches them
 // (GNUmakefile tells make which objects depend on this file, for the same reason).
 #pragma once
@@ -23,6 +24,24 @@ struct wofdm_lparams {
     const wofdm_lpoint *pts;          // [n_points]
 };
 
+// The soft outputs of wofdm_rx_profile_soft, an eighth argument of wofdm_rxprof_soft_kernel (the link arm with the demapper
+// switched on).  For the decision of loaded bin n, data symbol s >= 1: nu = |G[n]|^2 v W2, v = g^2 Pn / NL the per-sample noise
+// variance pass 1 put on the air for the point, W2 = w2[pair]; Lambda_i the max-log bit metrics over nu; and per scale j
+// pen_j = sum_i log2(1 + 2^(-(1 - 2 b_i) cs[j] Lambda_i)), cs[j] = c_j log2(e) formed on the host.  The wave of symbol s writes
+// pen_j of its bins to bit_part (0 on unloaded bins), coalesced, and leaves their sum over the loaded bins -- a lane's bins
+// ascending, then papr_wave_reduce -- in sym_part; wofdm_rxprof_soft_frame_kernel adds a frame's symbols, ascending in single
+// precision, into the first symbol's element, and wofdm_rxprof_soft_reduce_kernel the frames onto the fp64 totals, ascending.
+#define WOFDM_SOFT_SCALES 16               // WOFDM_SOFT_MAX_SCALES of include/wofdm.h
+struct wofdm_softparams {
+    int32_t n_scales;
+    float cs[WOFDM_SOFT_SCALES];      // c_j log2(e)
+    const float *w2;                  // [pairs] sum of the Rx window's squares (host, double, stored in single)
+    float *bit_part;                  // [n_jobs][n_points][S - 1][n_scales][n_fft]; [..][0][..][..] becomes the frame's sum
+    float *sym_part;                  // [n_jobs][n_points][n_scales][S] (s = 0 is not written and not read)
+    double *bit_tot;                  // [n_points][cells][n_scales][n_fft], accumulated into
+    double *sym_tot;                  // [n_points][cells][n_scales][S - 1], accumulated into
+};
+
 struct wofdm_link_fns {
     // wofdm_rx_profile_link, one chunk: the Tx chain once, the neighbour's (nb != null: a point has aci_on) once, the points'
     // amplified waveforms and power sums, the items' unit walks, wofdm_rxprof_link_kernel (both passes once per point),
@@ -31,6 +50,12 @@ struct wofdm_link_fns {
     hipError_t (*rx_profile_link)(const wofdm_pparams *p, const wofdm_pparams *nb, const wofdm_rparams *r, const wofdm_aparams *a,
                                   const wofdm_sparams *sp, const wofdm_dparams *dp, const wofdm_paparams *pa,
                                   const wofdm_pnparams *pn, const wofdm_lparams *lk, int n_tracks, int max_theta, hipStream_t s);
+    // wofdm_rx_profile_soft, one chunk: rx_profile_link with wofdm_rxprof_soft_kernel in the link kernel's place, and behind the
+    // ordered sums wofdm_rxprof_soft_reduce_kernel's
+    hipError_t (*rx_profile_soft)(const wofdm_pparams *p, const wofdm_pparams *nb, const wofdm_rparams *r, const wofdm_aparams *a,
+                                  const wofdm_sparams *sp, const wofdm_dparams *dp, const wofdm_paparams *pa,
+                                  const wofdm_pnparams *pn, const wofdm_lparams *lk, const wofdm_softparams *so, int n_tracks,
+                                  int max_theta, hipStream_t s);
 };
 const wofdm_link_fns *wofdm_aux_link_n64(void);
 const wofdm_link_fns *wofdm_aux_link_n128(void);

@@ -32,6 +32,11 @@ drawn from Philox stream 3, a list of ``PnPoint`` (linewidth, free-running or co
 ``rx_profile_link_gpu`` (``wofdm_rx_profile_link``) is the profile with all five combined in one chain, a list of ``LinkPoint``
 per call, each switching on any subset; ``frame_profile_link`` and ``rx_profile_link_host`` mirror it, composed of the mirrors
 above.
+
+``rx_profile_soft_gpu`` (``wofdm_rx_profile_soft``) is the link call with soft decisions: beside the hard counters the max-log
+bit metrics' penalties per bin and per data symbol for a list of scales, from which ``gmi_per_bin``, ``gmi_per_symbol`` and
+``gmi`` form the achievable (BICM) rate; ``bit_llrs``, ``soft_penalties``, ``frame_profile_soft`` and ``rx_profile_soft_host``
+mirror it.
 """
 import collections
 
@@ -276,11 +281,11 @@ _Sweep = collections.namedtuple("_Sweep", "st k S w_tx w_rx hc snr act m nbt noi
 
 
 def _host_sweep(result, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, active, mask,
-                noise_before_truncate, with_near):
+                noise_before_truncate, with_near, n_scales=None):
     """The host route of every arm: the cells (pair, SNR point, channel) of the sweep and their frames [frame_offset,
     frame_offset + frames), the labels of stream 0 drawn per frame, the sums kept per field of ``result`` (a namedtuple type
-    whose last field is ``decisions``: per bin [N], ``*_sym`` per data symbol [S - 1], ``pa_power`` [2]; the counters uint64,
-    the powers float64, added up frame by frame).  arm(q: ``_Sweep``) does the arm's own argument preparation and returns
+    whose last field is ``decisions``: per bin [N], ``*_sym`` per data symbol [S - 1], ``pa_power`` [2], ``bit_penalty*`` with
+    the ``n_scales`` scales before that axis; the counters uint64, the powers and penalties float64, added up frame by frame).  arm(q: ``_Sweep``) does the arm's own argument preparation and returns
     (lead, frame): lead = () or (n_points,), the leading axis of every sum, and frame(p, s, c, cell, fr, grid) -> per point
     one tuple (bit_err, sym_err, err_power, xhat, y0, then the further fields of ``result`` in its order; anything behind is
     ignored), for which the arm draws what the frame needs beyond the labels.  Returns ``result``, and with_near=True also the
@@ -294,8 +299,9 @@ def _host_sweep(result, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, s
     tab = T.qam_table(k)
     on = np.ones(n, dtype=bool) if act is None else act != 0
     shape = lead + (pairs, n_snr, n_ch)
-    sums = [np.zeros(shape + ((2,) if f == "pa_power" else (S - 1,) if f.endswith("_sym") else (n,)),
-                     dtype=np.float64 if "power" in f else np.uint64) for f in result._fields[:-1]]
+    sums = [np.zeros(shape + ((int(n_scales),) if f.startswith("bit_penalty") else ()) +
+                     ((2,) if f == "pa_power" else (S - 1,) if f.endswith("_sym") else (n,)),
+                     dtype=np.float64 if "power" in f or "penalty" in f else np.uint64) for f in result._fields[:-1]]
     near = np.zeros(shape, dtype=np.int64)
     for cell in range(pairs * n_snr * n_ch):
         p, s, c = cell // (n_snr * n_ch), (cell // n_ch) % n_snr, cell % n_ch
@@ -345,28 +351,30 @@ def _unit_noise_lookup(st, grids, unit_noise, n_taps, noise_before_truncate):
     return _noise_lookup(noise)
 
 
-def _chunk_frames(st, syms, masked, per_point=0, n_points=0, per_frame_extra=0, neighbour=False):
+def _chunk_frames(st, syms, masked, per_point=0, n_points=0, per_frame_extra=0, neighbour=False, extra_bytes=0):
     """Frames one chunk holds: the byte budget of include/wofdm.h (``job_bytes`` of rx_profile_impl) over the bytes of a frame
     -- 8 per element: the symbol grid [S, N], the waveform [T], masked the filtered symbols [S, 2P - 1]; with a neighbour
     its grid [S + 1, N], waveform [T + B] and filtered symbols; ``per_frame_extra`` elements of the arm's own; ``per_point``
-    elements (the partial sums, a waveform) for each of ``n_points`` --, at least 1, at most 65535."""
+    elements (the partial sums, a waveform) for each of ``n_points``; ``extra_bytes`` bytes that are no 8-byte elements --, at
+    least 1, at most 65535."""
     from . import _lib
     P, B = st.sym_len, st.sym_len - st.tail_tx
     T = st.tail_tx + syms * B
     words = syms * st.n_fft + T + (syms * (2 * P - 1) if masked else 0)
     if neighbour:
         words += (syms + 1) * st.n_fft + T + B + ((syms + 1) * (2 * P - 1) if masked else 0)
-    per_frame = 8 * (words + per_frame_extra + int(n_points) * per_point)
+    per_frame = 8 * (words + per_frame_extra + int(n_points) * per_point) + int(extra_bytes)
     return min(65535, max(1, _lib.RX_PROFILE_CHUNK_BYTES // per_frame))
 
 
 def _gpu_call(entry, result, st, bits_per_sc, syms, prepared, seed, frame_offset, frames, noise_before_truncate, device, out,
-              lead=(), after_h=(), after_mask=(), n_ch=None):
+              lead=(), after_h=(), after_mask=(), n_ch=None, n_scales=None):
     """One call of the library's receive-profile entry point ``entry``: prepared = ``_prepare``'s six (the fifth argument of
     the entry point is prepared[2], of any rank, taps last; n_ch: its channels where they are not its first axis); after_h,
     after_mask: the arm's own ctypes arguments, behind h and behind the mask; lead = () or (n_points,).  The outputs are
     those ``result`` has fields for -- the {bit, symbol} counters and the power per bin; with ``*_sym`` fields the same per
-    data symbol; with ``pa_power`` the power sums --, each behind the leading axes lead + (pairs, n_snr, n_ch).  Returns
+    data symbol; with ``pa_power`` the power sums; with ``bit_penalty`` the penalties of the ``n_scales`` scales per bin and per
+    data symbol --, each behind the leading axes lead + (pairs, n_snr, n_ch).  Returns
     ``result``, added to ``out`` (an earlier result of the same shape) where given."""
     import ctypes as C
     from . import _lib
@@ -382,6 +390,8 @@ def _gpu_call(entry, result, st, bits_per_sc, syms, prepared, seed, frame_offset
         outs += [np.zeros(shape + tail + (2,), dtype=np.uint64), np.zeros(shape + tail, dtype=np.float64)]
     if "pa_power" in result._fields:
         outs.append(np.zeros(shape + (2,), dtype=np.float64))
+    if "bit_penalty" in result._fields:
+        outs += [np.zeros(shape + (int(n_scales),) + tail, dtype=np.float64) for tail in tails]
     hf = _lib.c64_as_f32(hc)
     _lib.check(getattr(_lib.load(), entry)(
         C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, *after_h, snr.ctypes.data,
@@ -1071,6 +1081,14 @@ def frame_profile_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_p
     ``walk`` [>= S B] read at clamp(a, 0, S B - 1), the tracked mean over the same clamped values.  noise_at(idx) as
     ``frame_profile_sync``'s.  Returns what ``frame_profile_pa`` returns: (bit_err [N], sym_err [N], err_power [N], xhat [S-1, N],
     y0 [N], bit_err_sym [S-1], sym_err_sym [S-1], err_power_sym [S-1], pa_power [2]); with_y=True: Y [S, N] as a tenth."""
+    out = _frame_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, walk, track, knot_step, ref_power, aci_grids,
+                      aci_h, active, mask, noise_before_truncate)[1]
+    return out if with_y else out[:9]
+
+
+def _frame_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, walk, track, knot_step, ref_power, aci_grids, aci_h,
+                active, mask, noise_before_truncate):
+    """The steps of ``frame_profile_link``: (the point's front (X, conv, g, on), ``_link_point``'s ten outputs)"""
     q = _link_prepare(st, [LinkPoint(*point)._replace(track=None)], 0)[0]
     if track is not None:
         q = q._replace(track=0)
@@ -1081,8 +1099,7 @@ def frame_profile_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_p
         if np.asarray(aci_grids).shape != (np.asarray(grids).shape[0] + 1, st.n_fft):
             raise ValueError("aci_grids must be [S + 1, %d]" % st.n_fft)
         on_air = _aci_on_air(st, aci_grids, w_tx, h if aci_h is None else aci_h, 0.0, mask)
-    out = _link_point(st, front, power, noise_at, w_rx, walk, on_air, q, bits_per_sc)
-    return out if with_y else out[:9]
+    return front, _link_point(st, front, power, noise_at, w_rx, walk, on_air, q, bits_per_sc)
 
 
 def _link_sides(st, hc, points, tracks, aci_active, aci_h, ref_power, pairs):
@@ -1177,3 +1194,216 @@ def rx_profile_link_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db
                      noise_before_truncate, device, out, lead=(len(pts),),
                      after_mask=(None if trf is None else trf.ctypes.data, *knots, None if iact is None else iact.ctypes.data,
                                  None if hif is None else hif.ctypes.data, None if ref is None else ref.ctypes.data, len(pts), cpts))
+
+
+# ---- soft decisions: bit LLRs and the achievable rate (wofdm_rx_profile_soft) ----
+
+#: the default scales of ``rx_profile_soft_gpu``: the half-octave list 2^(1 - j / 2), j = 0 ... 15 (2 down to 0.011) -- the matched
+#: scale runs from about 0.5 (the pilot's own noise) to 0.01 (where ISI dominates), and an octave grid gives up as much as 10 %
+#: of the rate against a fine one
+SOFT_SCALES = tuple(float(np.float32(2.0 ** (1.0 - 0.5 * j))) for j in range(16))
+
+_SOFT_SUMS = RxProfilePa._fields[:-1] + ("bit_penalty", "bit_penalty_sym", "decisions")
+#: the fields ``_host_sweep`` and ``_gpu_call`` add up for the soft call: ``RxProfileSoft`` without the scales
+_RxSoftSums = collections.namedtuple("_RxSoftSums", _SOFT_SUMS)
+RxProfileSoft = collections.namedtuple("RxProfileSoft", _SOFT_SUMS[:-1] + ("scales", "decisions"))
+RxProfileSoft.__doc__ = """``RxProfileLink``'s fields, and bit_penalty (float64) [points, pairs, n_snr, n_ch, n_scales, N]: the sum
+over a bin's decisions of sum_i log2(1 + exp(-(1 - 2 b_i) c_j Lambda_i)) for every scale c_j; bit_penalty_sym [points, pairs, n_snr,
+n_ch, n_scales, S - 1]: the same sums over the loaded bins per data symbol; scales [n_scales] (float32, as the library received
+them).  ``gmi_per_bin``, ``gmi_per_symbol`` and ``gmi`` turn them into rates."""
+
+
+def _soft_scales(scales):
+    from . import _lib
+    sc = _lib.f32(np.asarray(SOFT_SCALES if scales is None else scales).reshape(-1))
+    if not 1 <= sc.size <= _lib.SOFT_MAX_SCALES or not (np.isfinite(sc) & (sc > 0)).all():
+        raise ValueError("1 to %d finite positive scales are needed" % _lib.SOFT_MAX_SCALES)
+    return sc
+
+
+def bit_llrs(bits_per_sc, xhat, nu=1.0):
+    """The max-log bit metrics of the equalised values ``xhat`` (any shape), [..., k]: Lambda_i = (min over the constellation
+    points whose bit i is 1 of |xhat - x|^2, less the same minimum over the points whose bit i is 0) / nu, i = 0 the top bit of
+    the label -- positive for a 0.  Brute force over every point of ``timefreq.qam_table`` (the kernel forms the difference per
+    axis); nu broadcasts against xhat."""
+    from . import timefreq as T
+    k = int(bits_per_sc)
+    tab = T.qam_table(k)
+    e = np.asarray(xhat, dtype=np.complex128)
+    d = np.abs(e[..., None] - tab) ** 2                                # [..., 2^k]
+    lab = np.arange(1 << k)
+    out = np.empty(e.shape + (k,), dtype=np.float64)
+    for i in range(k):
+        one = ((lab >> (k - 1 - i)) & 1) != 0
+        out[..., i] = d[..., one].min(axis=-1) - d[..., ~one].min(axis=-1)
+    return out / np.asarray(nu, dtype=np.float64)[..., None]
+
+
+def soft_penalties(bits_per_sc, X, xhat, nu, scales, on=None):
+    """The penalties of ``wofdm_rx_profile_soft`` on a mirror's outputs: X [S - 1, N] the transmitted points of the data symbols,
+    xhat [S - 1, N] the equalised values, nu [N] the noise variance the receiver assumes per bin, scales [n_scales]; on [N]: the
+    loaded bins (None: all).  Returns pen [n_scales, S - 1, N] = sum_i log2(1 + exp(-(1 - 2 b_i) c_j Lambda_i)), evaluated as
+    max(-z, 0) + log1p(exp(-|z|)) over ln 2, b_i the bits of X's label (``slice_labels``); 0 on unloaded bins."""
+    k = int(bits_per_sc)
+    X = np.asarray(X, dtype=np.complex128)
+    on = np.ones(X.shape[-1], dtype=bool) if on is None else np.asarray(on).reshape(-1) != 0
+    nu = np.where(on, np.asarray(nu, dtype=np.float64), 1.0)
+    lab = slice_labels(k, X)
+    sign = np.stack([1.0 - 2.0 * ((lab >> (k - 1 - i)) & 1) for i in range(k)], axis=-1)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        z0 = sign * bit_llrs(k, np.where(on[None, :], xhat, 0.0), nu[None, :])          # [S - 1, N, k]
+        z = np.asarray(scales, dtype=np.float64).reshape(-1)[:, None, None, None] * z0[None]
+        pen = ((np.maximum(-z, 0.0) + np.log1p(np.exp(-np.abs(z)))) / np.log(2.0)).sum(axis=-1)
+    return np.where(on[None, None, :], pen, 0.0)
+
+
+def _soft_outputs(st, front, out, w_rx, snr_db, bits_per_sc, scales, noise_before_truncate):
+    """nu [N], bit penalties [n_scales, N] and symbol penalties [n_scales, S - 1] of a point of a frame: front = the point's (X,
+    conv, g, on), out = ``_link_point``'s outputs (xhat fourth, Y last).  v = mean |conv|^2 10^(-snr / 10) over the samples the
+    power pass reads -- which is g^2 Pn / NL --, W2 the sum of the window's squares, G = X_0 / Y_0."""
+    X, conv, _, on = front
+    S, B = X.shape[0], st.sym_len - st.tail_tx
+    nl = conv.size if noise_before_truncate else S * B
+    v = np.mean(np.abs(conv[:nl]) ** 2) * 10.0 ** (-0.1 * float(snr_db))
+    w2 = float((np.asarray(w_rx, np.float64) ** 2).sum())
+    Y0 = out[-1][0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        nu = np.where(on, np.abs(X[0] / np.where(on, Y0, 1.0)) ** 2 * v * w2, 0.0)
+    pen = soft_penalties(bits_per_sc, X[1:], out[3], nu, scales, on)
+    return nu, pen.sum(axis=1), pen.sum(axis=2)
+
+
+def frame_profile_soft(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, walk, scales=None, track=None,
+                       knot_step=None, ref_power=None, aci_grids=None, aci_h=None, active=None, mask=None, noise_before_truncate=1,
+                       with_y=False):
+    """fp64 host mirror of one frame and one point of ``wofdm_rx_profile_soft``: ``frame_profile_link`` of the same arguments, and
+    for the scales ``scales`` (None: ``SOFT_SCALES``) the penalties of include/wofdm.h's definition -- e = xhat, G = X_0 / Y_0,
+    nu[n] = |G[n]|^2 v W2 with v = Ps / NL 10^(-snr / 10) of the point's waveform and channel and W2 = sum w_rx^2, the metrics of
+    ``bit_llrs``, the sums of ``soft_penalties``.  Returns ``frame_profile_link``'s nine outputs, then nu [N], bit_penalty
+    [n_scales, N] and bit_penalty_sym [n_scales, S - 1]; with_y=True: Y [S, N] as a thirteenth."""
+    sc = _soft_scales(scales)
+    front, out = _frame_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, walk, track, knot_step, ref_power,
+                             aci_grids, aci_h, active, mask, noise_before_truncate)
+    soft = _soft_outputs(st, front, out, w_rx, snr_db, bits_per_sc, sc, noise_before_truncate)
+    return out[:9] + soft + ((out[9],) if with_y else ())
+
+
+def _soft_result(sums, scales):
+    return RxProfileSoft(*sums[:-1], scales, sums.decisions)
+
+
+def rx_profile_soft_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                         scales=None, tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None,
+                         mask=None, noise_before_truncate=1, with_near=False):
+    """The host route of ``rx_profile_soft_gpu``: ``rx_profile_link_host``'s frames and points (None: one all-off ``LinkPoint``),
+    each also through ``frame_profile_soft``'s steps for the scales ``scales`` (None: ``SOFT_SCALES``).  Returns
+    ``RxProfileSoft``; with_near=True: also the number of ``near_decisions`` per point and cell."""
+    from . import timefreq as T
+    sc = _soft_scales(scales)
+    points = [LinkPoint()] if points is None else points
+
+    def arm(q):
+        pts, tr, iact, hi, ref = _link_sides(st, q.hc, points, tracks, aci_active, aci_h, ref_power, q.w_tx.shape[0])
+        B = st.sym_len - st.tail_tx
+        nb = iact is not None and iact.any()
+        lo = min(0, st.prefix_rm + min(pt.timing for pt in pts))
+        hi_ = max(q.noise_len, (q.S - 1) * B + st.prefix_rm + max(pt.timing for pt in pts) + st.n_fft + st.tail_rx)
+        tab = T.qam_table(q.k)
+
+        def frame(p, s, c, cell, fr, grid):
+            noise_at = _noise_lookup(gen_noise_at(np.arange(lo, hi_, dtype=np.int64), seed, cell, fr), lo)
+            walk = pn_walk(q.S * B, seed, cell, fr)
+            on_air = None
+            if nb:
+                igrid = tab[gen_labels(st.n_fft, q.k, q.S + 1, seed, cell, fr, STREAM_ACI)] * (iact != 0)[None, :]
+                on_air = _aci_on_air(st, igrid, q.w_tx[p], q.hc[c] if hi is None else hi[c], 0.0, q.m)
+            fronts = {}
+            for pt in pts:
+                key = (pt.pa, pt.track)
+                if key not in fronts:
+                    fronts[key] = _link_front(st, grid, noise_at, q.w_tx[p], q.hc[c], None if pt.track is None else tr[pt.track, c],
+                                              knot_step, pt.pa, None if ref is None else ref[p], q.snr[s], q.act, q.m, q.nbt)
+                out = _link_point(st, *fronts[key], noise_at, q.w_rx[p], walk, on_air, pt, q.k)
+                yield out[:9] + _soft_outputs(st, fronts[key][0], out, q.w_rx[p], q.snr[s], q.k, sc, q.nbt)[1:]
+        return (len(pts),), frame
+    res = _host_sweep(_RxSoftSums, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames,
+                      active, mask, noise_before_truncate, with_near, n_scales=sc.size)
+    return (_soft_result(res[0], sc), res[1]) if with_near else _soft_result(res, sc)
+
+
+def rx_profile_soft_chunk_frames(st, syms, masked, n_points, neighbour, n_scales):
+    """Frames one chunk of ``wofdm_rx_profile_soft`` holds (include/wofdm.h): ``rx_profile_link_chunk_frames``' bytes plus, per
+    point and scale, the fp32 penalties of every data symbol's bins and the symbols' sums, 4 ((S - 1) N + S) bytes; at most 65535."""
+    B = st.sym_len - st.tail_tx
+    return _chunk_frames(st, syms, masked, per_point=st.n_fft + syms + st.tail_tx + syms * B, n_points=n_points,
+                         per_frame_extra=syms * B, neighbour=bool(neighbour),
+                         extra_bytes=4 * int(n_points) * int(n_scales) * ((syms - 1) * st.n_fft + syms))
+
+
+def rx_profile_soft_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                        scales=None, tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None,
+                        mask=None, noise_before_truncate=1, device=0, out=None):
+    """``wofdm_rx_profile_soft``: ``rx_profile_link_gpu`` of the same arguments -- its five outputs are that call's bytes -- and
+    beside them the penalties of the max-log bit metrics for every scale of ``scales`` (None: ``SOFT_SCALES``; at most
+    ``_lib.SOFT_MAX_SCALES``), per bin and per data symbol.  points=None is one all-off ``LinkPoint``.  Returns
+    ``RxProfileSoft``; ``out`` (an earlier result of the same shape and scales) is accumulated into.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    sc = _soft_scales(scales)
+    points = [LinkPoint()] if points is None else points
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts, tr, iact, hi, ref = _link_sides(st, prepared[2], points, tracks, aci_active, aci_h, ref_power, prepared[0].shape[0])
+    trf = None if tr is None else _lib.c64_as_f32(tr)
+    hif = None if hi is None else _lib.c64_as_f32(hi)
+    lin = PaPoint(PA_LINEAR, 0.0)
+    cpts = (_lib.LinkPoint * len(pts))(*[
+        _lib.LinkPoint(*(q.pa or lin), -1 if q.track is None else q.track, q.timing, q.cfo, q.cfo_tracked, q.linewidth, q.cpe_tracked,
+                       int(q.aci is not None), *(q.aci or (0, 0.0)), (C.c_int32 * 4)(0, 0, 0, 0)) for q in pts])
+    knots = (0, 0, 0) if tr is None else (tr.shape[0], tr.shape[2], int(knot_step))
+    prev = None
+    if out is not None:
+        if not np.array_equal(out.scales, sc):
+            raise ValueError("out has other scales")
+        prev = _RxSoftSums(*out[:-2], out.decisions)
+    res = _gpu_call("wofdm_rx_profile_soft", _RxSoftSums, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                    noise_before_truncate, device, prev, lead=(len(pts),), n_scales=sc.size,
+                    after_mask=(None if trf is None else trf.ctypes.data, *knots, None if iact is None else iact.ctypes.data,
+                                None if hif is None else hif.ctypes.data, None if ref is None else ref.ctypes.data, len(pts), cpts,
+                                int(sc.size), sc.ctypes.data))
+    return _soft_result(res, sc)
+
+
+def _soft_rates(pen, dec, k):
+    """k - pen / dec along the scale axis (-2 of pen) and its maximum: (rate, index of the scale), NaN / 0 where dec is 0"""
+    dec = np.asarray(dec, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(dec > 0, int(k) - pen / np.where(dec > 0, dec, 1.0)[..., None, :], np.nan)
+    bad = np.isnan(r).all(axis=-2)
+    idx = np.where(bad, 0, np.argmax(np.where(np.isnan(r), -np.inf, r), axis=-2))
+    return np.where(bad, np.nan, np.take_along_axis(r, idx[..., None, :], axis=-2)[..., 0, :]), idx
+
+
+def gmi_per_bin(prof, bits_per_sc):
+    """The achievable rate per subcarrier in bit per decision, k - bit_penalty / decisions at the scale that maximises it (every
+    scale gives an achievable rate): (rate, scale index) [points, pairs, n_snr, n_ch, N]; NaN (index 0) on unloaded bins."""
+    return _soft_rates(prof.bit_penalty, prof.decisions, bits_per_sc)
+
+
+def gmi_per_symbol(prof, bits_per_sc):
+    """The same per data symbol over the loaded bins: (rate, scale index) [points, pairs, n_snr, n_ch, S - 1]"""
+    n_sym = prof.bit_penalty_sym.shape[-1]
+    dec = np.full(n_sym, float(prof.decisions.astype(np.float64).sum()) / n_sym)
+    return _soft_rates(prof.bit_penalty_sym, dec, bits_per_sc)
+
+
+def gmi(prof, bits_per_sc, per_bin_scale=True):
+    """The achievable rate of a cell in bit per decision, the mean over its loaded bins: per_bin_scale=True with every bin at its
+    own best scale -- (rate [points, pairs, n_snr, n_ch], scale index [..., N], as ``gmi_per_bin``'s) --, False with one scale for
+    the cell, the best for its total penalty -- (rate [...], scale index [...])."""
+    on = prof.decisions > 0
+    if per_bin_scale:
+        r, idx = gmi_per_bin(prof, bits_per_sc)
+        return r[..., on].mean(axis=-1), idx
+    total = float(prof.decisions.astype(np.float64).sum())
+    r, idx = _soft_rates(prof.bit_penalty.sum(axis=-1, keepdims=True), np.array([total]), bits_per_sc)
+    return r[..., 0], idx[..., 0]
