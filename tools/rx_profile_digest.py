@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: the bytes of the seven receive-profile entry points, as SHA-256 digests -- for comparing two builds of the
+"""Developer tool: the bytes of the eight receive-profile entry points and of wofdm_tx_papr, as SHA-256 digests -- for comparing two builds of the
 library (WOFDM_LIB=... selects one) or two versions of the Python layer above it: run the tool once per build or tree and diff
 the outputs line for line.  It uses the package's public names only, so the same file runs against either tree.
 
@@ -12,7 +12,12 @@ of W, W = 4 at N = 1024, the fold with and without an Rx tail and both noise ord
   rx_profile_pa       tests/pa_cases.py
   rx_profile_pn       CASES and POINTS of tests/test_gpu_rx_profile_pn.py
   rx_profile_link     the cases of tests/test_gpu_rx_profile_link.py, composed points and their single-impairment points
-and for each entry point the chunk-straddling shape of its test file (N = 1024, S = 16, cp + cs = 64, four chunks and a bit).
+  rx_profile_soft     the same cases with the points and default scales of tests/test_gpu_rx_profile_soft.py: the link fields and
+                      beside them bit_penalty and bit_penalty_sym (the ABI's sym_penalty)
+  tx_papr             tests/papr_cases.py: every N, system and variant; hist, max_papr and periods (--route gpu only: the
+                      oracle is its only mirror, and the tests hold it against that)
+and for each entry point the chunk-straddling shape of its test file (N = 1024, S = 16, cp + cs = 64, four chunks and a bit;
+tx_papr: one pair, a full chunk and 37 frames, periods from the 39 frames around the boundary).
 The seeds are the cases' base seeds: the tests pick theirs with the oracle or the mirrors, which no digest needs.
 
 --route gpu (the default, GPU box): the ``rx_profile_*_gpu`` functions.  --route host (any machine, no library, no GPU): the
@@ -40,15 +45,18 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import wofdm_amd as W  # noqa: E402
 from wofdm_amd import channel_mask as CM  # noqa: E402
 from wofdm_amd import rx_profile as R  # noqa: E402
+from wofdm_amd import timefreq as TF  # noqa: E402
 
 import doppler_cases as DC  # noqa: E402
 import pa_cases as PC  # noqa: E402
+import papr_cases as XC  # noqa: E402
 import rx_profile_cases as RC  # noqa: E402
 import test_gpu_rx_profile_aci as TA  # noqa: E402
 import test_gpu_rx_profile_doppler as TD  # noqa: E402
 import test_gpu_rx_profile_link as TL  # noqa: E402
 import test_gpu_rx_profile_pa as TP  # noqa: E402
 import test_gpu_rx_profile_pn as TN  # noqa: E402
+import test_gpu_rx_profile_soft as TQ  # noqa: E402
 import test_gpu_rx_profile_sync as TS  # noqa: E402
 
 
@@ -70,6 +78,23 @@ def gpu_link(c, seed, frame_offset, frames, **kw):
     return TL.run_gpu(c, seed, frame_offset, frames)
 
 
+def gpu_soft(c, seed, frame_offset, frames, **kw):
+    if "scales" in kw:                                                 # (the chunk shape: its own points and scales)
+        return W.rx_profile_soft_gpu(c["st"], c["k"], c["S"], c["w_tx"], c["w_rx"], c["h"], c["snr"], seed, frame_offset, frames,
+                                     c["points"], kw["scales"], active=c["active"])
+    return TQ.run_soft(c, seed, frame_offset, frames)
+
+
+def papr_digests(c, seed, frame_offset, frames, periods_at=None):
+    """hist, max_papr and periods of one wofdm_tx_papr call; periods_at: (frame_offset, frames) of a second call the periods
+    come from, where the first has too many to ask for"""
+    kw = dict(active=c["active"], mask=c["mask"], lo_db=XC.LO_DB, step_db=XC.STEP_DB, n_bins=XC.N_BINS)
+    out = TF.tx_papr_gpu(c["st"], c["k"], c["S"], c["w"], seed, frame_offset, frames, periods=periods_at is None, **kw)
+    per = out[2] if periods_at is None else TF.tx_papr_gpu(c["st"], c["k"], c["S"], c["w"], seed, *periods_at, periods=True, **kw)[2]
+    return {f: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+            for f, a in (("hist", out[0]), ("max_papr", out[1]), ("periods", per))}
+
+
 #: entry -> (gpu route -> profile, host route -> (profile, near)), both (case, seed, frame_offset, frames, **kw)
 ROUTES = {
     "rx_profile": (RC.run_gpu, host_plain),
@@ -79,6 +104,7 @@ ROUTES = {
     "rx_profile_pa": (TP.run_gpu, PC.host),
     "rx_profile_pn": (TN.run_gpu, TN.host),
     "rx_profile_link": (gpu_link, TL.host),
+    "rx_profile_soft": (gpu_soft, lambda *a, **kw: (TQ.host_soft(*a, **kw), None)),   # (the link entry has the near counts)
 }
 
 
@@ -113,10 +139,24 @@ def small_cases():
     for j, name in enumerate(TL.CASES):
         c = TL.case(name)
         yield "rx_profile_link", name, dict(c, points=c["composed"] + c["singles"]), 100 * (1 + j), {}
+    for j, name in enumerate(TQ.CASES):
+        yield "rx_profile_soft", name, TL.case(name), 100 * (1 + j), {}
+
+
+def papr_cases():
+    """(case name, case, seed): tests/papr_cases.py without its oracle, XC.FRAMES frames each"""
+    for n in XC.NS:
+        for system in XC.SYSTEMS:
+            for variant in XC.VARIANTS:
+                _, S, k = XC.shape_of(n, system, variant)
+                st = XC.structure(n, system)
+                c = dict(st=st, k=k, S=S, w=XC.random_windows(st, XC.PAIRS, 1000 + n + XC.SYSTEMS.index(system)),
+                         active=XC.allocation(n, variant), mask=XC.mask_of(st, variant))
+                yield "n%d_%s_%s" % (n, system, variant), c, 10 * (n + 7 * XC.SYSTEMS.index(system) + XC.VARIANTS.index(variant))
 
 
 def chunk_cases():
-    """(entry, case, frames, extra keywords): the chunk-straddling shape of the seven test files, N = 1024, S = 16, cp + cs = 64"""
+    """(entry, case, frames, extra keywords): the chunk-straddling shape of the eight test files, N = 1024, S = 16, cp + cs = 64"""
     st, S = W.make_structure("wtx", 1024, 56), 16
     big = RC.make_case(st, 4, S, "plain", 3001)
     half = CM.half_band_allocation(1024)
@@ -140,6 +180,8 @@ def chunk_cases():
     cl = dict(cd, points=[R.LinkPoint(), R.LinkPoint(pts[1], 1, 2, 0.02, 1, 0.01, 0, (501, 0.0))])
     yield ("rx_profile_link", cl, frames_of(R.rx_profile_link_chunk_frames(st, S, False, 2, True)),
            dict(tracks=cd["tracks"], knot_step=st.stride, aci_active=~half, ref_power=ref))
+    cq = dict(big, active=half, points=[R.LinkPoint(), R.LinkPoint(linewidth=0.01)])
+    yield "rx_profile_soft", cq, frames_of(R.rx_profile_soft_chunk_frames(st, S, False, 2, False, 2)), dict(scales=(0.5, 0.1))
 
 
 def runs(route):
@@ -153,6 +195,12 @@ def runs(route):
         # by entry point, the chunk shape behind its small cases (seed 7000)
         for entry, c, frames, kw in chunk_cases():
             yield entry, "chunks", lambda e=entry, c=c, f=frames, kw=kw: digests(ROUTES[e][0](c, 7000, 0, f, **kw))
+        for name, c, seed in papr_cases():
+            yield "tx_papr", name, lambda c=c, s=seed: papr_digests(c, s, 0, XC.FRAMES)
+        st = XC.structure(1024, "wtx")
+        c = dict(st=st, k=4, S=16, w=XC.random_windows(st, 1, 9), active=None, mask=None)
+        per_chunk = TF.tx_papr_chunk_frames(st, 16, False)
+        yield "tx_papr", "chunks", lambda c=c, n=per_chunk: papr_digests(c, 40, 0, n + 37, periods_at=(n - 2, 39))
 
 
 def main():

@@ -387,7 +387,7 @@ int check_launch_args(wofdm_plan *pl, uint64_t frames_per_cell)
     return WOFDM_OK;
 }
 
-// ---- the auxiliary entry points (wofdm_interference*, wofdm_tx_psd*) ----
+// ---- the auxiliary entry points (wofdm_interference*, wofdm_tx_psd*, wofdm_tx_papr, wofdm_rx_profile*) ----
 
 // Owner of a device allocation: whichever way its entry point returns, everything is freed.
 template <typename T> struct dev_buf {
@@ -411,7 +411,6 @@ int use_device(int device)
     return WOFDM_OK;
 }
 
-// the channels' taps as the kernels read them: [n_channels][WOFDM_LT] float2, zero padded
 // The checks of a table of amplifier points (include/wofdm.h, both routes), and the points as the kernels read them
 int check_pa_points(int32_t n, const wofdm_pa_point *pts, std::vector<wofdm_papoint> *out)
 {
@@ -434,6 +433,7 @@ int check_pa_points(int32_t n, const wofdm_pa_point *pts, std::vector<wofdm_papo
     return WOFDM_OK;
 }
 
+// the channels' taps as the kernels read them: [n_channels][WOFDM_LT] float2, zero padded
 std::vector<float2> pack_taps(const wofdm_cfg *cfg, const geom &g, const float *h)
 {
     std::vector<float2> hp((size_t)cfg->n_channels * WOFDM_LT, make_float2(0.f, 0.f));
@@ -441,6 +441,133 @@ std::vector<float2> pack_taps(const wofdm_cfg *cfg, const geom &g, const float *
         for (int l = 0; l < g.L; ++l)
             hp[(size_t)c * WOFDM_LT + l] = make_float2(h[2 * ((size_t)c * g.L + l)], h[2 * ((size_t)c * g.L + l) + 1]);
     return hp;
+}
+
+// ---- what wofdm_tx_papr and the receive profiles share: the Tx chain of a chunk of frames, and the loop over a call's chunks ----
+
+// The frames of a Tx chain: P samples a symbol, B = P - tail_tx from one symbol to the next, T samples a frame; Lm taps of the
+// mask's circular impulse response, FL points of its fast convolution
+struct tx_geom {
+    int N, k, S, P, beta, B, T, Lm, FL;
+};
+tx_geom tx_geom_of(const wofdm_cfg *cfg)
+{
+    tx_geom g{};
+    g.N = cfg->n_fft; g.k = cfg->bits_per_sc; g.S = cfg->syms_per_frame;
+    g.P = g.N + cfg->cp + cfg->cs; g.beta = cfg->tail_tx; g.B = g.P - g.beta; g.T = g.beta + g.S * g.B;
+    g.Lm = 2 * g.P - 1; g.FL = 8 * g.N;
+    return g;
+}
+
+// The Tx chain's checks, each refusal in its one wording; a caller makes them in the order its header documents.
+int check_tx_grid(const wofdm_cfg *cfg)
+{
+    const int N = cfg->n_fft, k = cfg->bits_per_sc, S = cfg->syms_per_frame;
+    if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
+        return fail(WOFDM_E_UNSUPPORTED, "n_fft=%d not in {64,128,256,512,1024}", N);
+    if (k != 2 && k != 4 && k != 6) return fail(WOFDM_E_UNSUPPORTED, "bits_per_sc=%d not in {2,4,6}", k);
+    if (S < 2 || S > WOFDM_MAX_SYMS) return fail(WOFDM_E_UNSUPPORTED, "syms_per_frame=%d not in [2,%d]", S, WOFDM_MAX_SYMS);
+    return WOFDM_OK;
+}
+// (the two callers refuse a symbol that does not fit in words of their own)
+bool tx_symbol_fits(const wofdm_cfg *cfg, const tx_geom &g) { return cfg->cp <= g.N && cfg->cs <= g.N && 2 * g.beta <= g.P; }
+int check_mask_length(const float *tx_mask, const tx_geom &g)
+{
+    if (tx_mask && g.P > wofdm_txmask_batch_pmax(g.N))
+        return fail(WOFDM_E_UNSUPPORTED, "the Tx mask needs 3 P - 2 <= 8 n_fft, i.e. P = n_fft + cp + cs <= %d at n_fft = %d (P = %d)",
+                    wofdm_txmask_batch_pmax(g.N), g.N, g.P);
+    return WOFDM_OK;
+}
+int check_mask_gains(const float *tx_mask, const tx_geom &g)
+{
+    for (int i = 0; tx_mask && i < g.Lm; ++i)
+        if (!std::isfinite(tx_mask[i])) return fail(WOFDM_E_INVALID, "mask gains must be finite");
+    return WOFDM_OK;
+}
+// the allocation as the kernels read it, 0 / 1 per bin (no allocation: hact stays empty, every bin is loaded)
+int check_allocation(const uint8_t *active, int N, std::vector<uint8_t> *hact)
+{
+    if (!active) return WOFDM_OK;
+    hact->resize((size_t)N);
+    int n_act = 0;
+    for (int n = 0; n < N; ++n) n_act += ((*hact)[(size_t)n] = active[n] ? 1 : 0);
+    return n_act ? WOFDM_OK : fail(WOFDM_E_INVALID, "the allocation loads no subcarrier");
+}
+
+// What the Tx chains of a call share on the device: the Tx windows, and the spectrum of the mask's fast convolution
+struct tx_shared {
+    dev_buf<float> w;
+    dev_buf<float2> spec;
+    int stage(const float *w_tx, size_t n_w, const float *tx_mask, const tx_geom &g)
+    {
+        std::vector<float2> hspec;
+        if (tx_mask) {
+            hspec.resize((size_t)g.FL);
+            mask_fastconv_spectrum(tx_mask, g.Lm, g.FL, hspec.data());
+        }
+        if (!w.alloc(n_w) || (tx_mask && !spec.alloc(hspec.size()))) return fail(WOFDM_E_NOMEM, "device allocation failed");
+        if (!w.upload(w_tx, n_w) || (tx_mask && !spec.upload(hspec.data(), hspec.size()))) return fail(WOFDM_E_HIP, "upload failed");
+        return WOFDM_OK;
+    }
+};
+// One Tx chain's device side: its allocation, and of a chunk's frames the symbol grids, the waveforms, under a mask the filtered
+// symbols, and the job tables
+struct tx_chain {
+    dev_buf<uint8_t> act;
+    dev_buf<float2> X, x, Y;
+    dev_buf<wofdm_bjob> jobs;
+    dev_buf<wofdm_mjob> mjobs;
+    // syms: the symbols of a frame (the neighbour has one more than g.S); whose: what the refusal adds to "allocation failed"
+    int stage(const tx_geom &g, int syms, size_t chunk, const std::vector<uint8_t> &hact, bool masked, const char *whose)
+    {
+        if (!X.alloc(chunk * syms * g.N) || !x.alloc(chunk * (g.beta + (size_t)syms * g.B)) || !jobs.alloc(chunk) ||
+            (!hact.empty() && !act.alloc(hact.size())) || (masked && (!Y.alloc(chunk * syms * g.Lm) || !mjobs.alloc(chunk))))
+            return fail(WOFDM_E_NOMEM, "device allocation failed%s", whose);
+        if (!hact.empty() && !act.upload(hact.data(), hact.size())) return fail(WOFDM_E_HIP, "upload failed");
+        return WOFDM_OK;
+    }
+    // the chain's parameters but for the chunk itself (item0, n_jobs); wdiv: cells per window pair
+    wofdm_pparams params(const wofdm_cfg *cfg, const tx_geom &g, int syms, uint32_t wdiv, const tx_shared &sh) const
+    {
+        wofdm_pparams pp{};
+        pp.S = syms; pp.k = g.k; pp.P = g.P; pp.cp = cfg->cp; pp.cs = cfg->cs; pp.beta = g.beta; pp.n_bins = 1;
+        pp.seed_lo = (uint32_t)cfg->seed; pp.seed_hi = (uint32_t)(cfg->seed >> 32);
+        pp.frames = cfg->frames_per_cell; pp.frame_offset = cfg->frame_offset; pp.wdiv = wdiv;
+        pp.wtx = sh.w; pp.amask = act; pp.spec = sh.spec; pp.jobs = jobs; pp.mjobs = mjobs;
+        pp.X = X; pp.x = x; pp.Y = Y;
+        return pp;
+    }
+};
+
+// frames per chunk: what the budget holds, at most a grid's y dimension, at least one
+uint64_t chunk_frames(uint64_t items, uint64_t budget, uint64_t job_bytes)
+{
+    return std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS, std::max<uint64_t>(1, budget / job_bytes)));
+}
+
+// The chunk loop of a call: launch(item0, n_jobs) enqueues one chunk on the null stream.  *err is what the loop ended with, *ms
+// the time between the first chunk's enqueue and the last one's end.
+template <typename F> int run_chunks(uint64_t items, uint64_t chunk, F launch, hipError_t *err, float *ms)
+{
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) {
+        if (ev[0]) (void)hipEventDestroy(ev[0]);
+        return fail(WOFDM_E_HIP, "event creation failed");
+    }
+    {
+        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        (void)hipDeviceSynchronize();
+        hipError_t e = hipEventRecord(ev[0], nullptr);
+        for (uint64_t i0 = 0; e == hipSuccess && i0 < items; i0 += chunk) e = launch(i0, (int32_t)std::min<uint64_t>(chunk, items - i0));
+        if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipEventElapsedTime(ms, ev[0], ev[1]);
+        *err = e;
+    }
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    return WOFDM_OK;
 }
 
 }  // namespace
@@ -1434,14 +1561,11 @@ int wofdm_tx_papr(const wofdm_cfg *cfg, int device, const float *w_tx, const uin
                   float lo_db, float step_db, int32_t n_bins, uint64_t *hist, float *max_papr, float *periods)
 {
     if (!cfg || !w_tx || !hist) return fail(WOFDM_E_INVALID, "NULL argument");
-    const int N = cfg->n_fft, k = cfg->bits_per_sc, S = cfg->syms_per_frame;
-    if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
-        return fail(WOFDM_E_UNSUPPORTED, "n_fft=%d not in {64,128,256,512,1024}", N);
-    if (k != 2 && k != 4 && k != 6) return fail(WOFDM_E_UNSUPPORTED, "bits_per_sc=%d not in {2,4,6}", k);
-    if (S < 2 || S > WOFDM_MAX_SYMS) return fail(WOFDM_E_UNSUPPORTED, "syms_per_frame=%d not in [2,%d]", S, WOFDM_MAX_SYMS);
-    const int P = N + cfg->cp + cfg->cs, beta = cfg->tail_tx;
-    if (cfg->cp < 0 || cfg->cs < 0 || cfg->cp > N || cfg->cs > N || beta < 0 || 2 * beta > P)
-        return fail(WOFDM_E_INVALID, "bad cp / cs / tail_tx");
+    int rc = check_tx_grid(cfg);
+    if (rc != WOFDM_OK) return rc;
+    const tx_geom g = tx_geom_of(cfg);
+    const int N = g.N, S = g.S, P = g.P;
+    if (cfg->cp < 0 || cfg->cs < 0 || g.beta < 0 || !tx_symbol_fits(cfg, g)) return fail(WOFDM_E_INVALID, "bad cp / cs / tail_tx");
     if (cfg->n_window_pairs < 1) return fail(WOFDM_E_INVALID, "n_window_pairs must be >= 1");
     if (n_bins < 1) return fail(WOFDM_E_INVALID, "n_bins=%d", n_bins);
     if (!(step_db > 0.f) || !std::isfinite(step_db) || !std::isfinite(lo_db))
@@ -1452,88 +1576,48 @@ int wofdm_tx_papr(const wofdm_cfg *cfg, int device, const float *w_tx, const uin
         return fail(WOFDM_E_UNSUPPORTED, "too many window pairs (2^28 cells, 2^31 window samples)");
     if (n_bins > WOFDM_PAPR_MAX_BINS) return fail(WOFDM_E_UNSUPPORTED, "n_bins=%d exceeds %d", n_bins, WOFDM_PAPR_MAX_BINS);
     if (frames > (UINT64_MAX >> 6) / pairs) return fail(WOFDM_E_UNSUPPORTED, "pairs * frames_per_cell * syms_per_frame overflows");
-    if (tx_mask && P > wofdm_txmask_batch_pmax(N))
-        return fail(WOFDM_E_UNSUPPORTED, "the Tx mask needs 3 P - 2 <= 8 n_fft, i.e. P = n_fft + cp + cs <= %d at n_fft = %d (P = %d)",
-                    wofdm_txmask_batch_pmax(N), N, P);
+    if ((rc = check_mask_length(tx_mask, g)) != WOFDM_OK) return rc;
     const uint64_t items = pairs * frames, n_periods = items * (uint64_t)S;
     if (periods && n_periods > WOFDM_TX_PAPR_MAX_PERIODS)
         return fail(WOFDM_E_UNSUPPORTED, "periods is a diagnostic output: at most %d periods (%llu asked for)",
                     WOFDM_TX_PAPR_MAX_PERIODS, (unsigned long long)n_periods);
-    const int Lm = 2 * P - 1, FL = 8 * N, B = P - beta, T = beta + S * B;
     std::vector<uint8_t> hact;
-    if (active) {
-        hact.resize((size_t)N);
-        int n_act = 0;
-        for (int n = 0; n < N; ++n) n_act += (hact[(size_t)n] = active[n] ? 1 : 0);
-        if (n_act == 0) return fail(WOFDM_E_INVALID, "the allocation loads no subcarrier");
-    }
-    if (tx_mask)
-        for (int i = 0; i < Lm; ++i)
-            if (!std::isfinite(tx_mask[i])) return fail(WOFDM_E_INVALID, "mask gains must be finite");
-    int rc = use_device(device);
+    if ((rc = check_allocation(active, N, &hact)) != WOFDM_OK || (rc = check_mask_gains(tx_mask, g)) != WOFDM_OK) return rc;
+    rc = use_device(device);
     if (rc != WOFDM_OK) return rc;
     g_papr_ms = 0.f;
     if (items == 0) return WOFDM_OK;
     // frames per chunk: what the budget holds (symbol grid + waveform + filtered symbols of a frame), as the header documents it
-    const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull));
-    const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
-                                                                       std::max<uint64_t>(1, WOFDM_TX_PAPR_CHUNK_BYTES / job_bytes)));
-    std::vector<float2> hspec;
-    if (tx_mask) {
-        hspec.resize((size_t)FL);
-        mask_fastconv_spectrum(tx_mask, Lm, FL, hspec.data());
-    }
-    const size_t n_w = (size_t)pairs * P, n_hist = (size_t)pairs * n_bins;
-    dev_buf<float> d_w;
-    dev_buf<uint8_t> d_act;
-    dev_buf<float2> d_spec, d_X, d_x, d_Y, d_per;
-    dev_buf<wofdm_bjob> d_jobs;
-    dev_buf<wofdm_mjob> d_mjobs;
+    const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)g.T + (tx_mask ? (uint64_t)S * g.Lm : 0ull));
+    const uint64_t chunk = chunk_frames(items, WOFDM_TX_PAPR_CHUNK_BYTES, job_bytes);
+    const size_t n_hist = (size_t)pairs * n_bins;
+    tx_shared sh;
+    tx_chain tx;
+    dev_buf<float2> d_per;
     dev_buf<unsigned long long> d_hist;
     dev_buf<uint32_t> d_max;
-    if (!d_w.alloc(n_w) || !d_X.alloc((size_t)chunk * S * N) || !d_x.alloc((size_t)chunk * T) || !d_jobs.alloc((size_t)chunk) ||
-        !d_hist.alloc(n_hist) || !d_max.alloc((size_t)pairs) || (active && !d_act.alloc(hact.size())) ||
-        (tx_mask && (!d_spec.alloc(hspec.size()) || !d_Y.alloc((size_t)chunk * S * Lm) || !d_mjobs.alloc((size_t)chunk))) ||
-        (periods && !d_per.alloc((size_t)n_periods)))
+    if ((rc = sh.stage(w_tx, (size_t)pairs * P, tx_mask, g)) != WOFDM_OK ||
+        (rc = tx.stage(g, S, (size_t)chunk, hact, tx_mask != nullptr, "")) != WOFDM_OK)
+        return rc;
+    if (!d_hist.alloc(n_hist) || !d_max.alloc((size_t)pairs) || (periods && !d_per.alloc((size_t)n_periods)))
         return fail(WOFDM_E_NOMEM, "device allocation failed");
-    if (!d_w.upload(w_tx, n_w) || (active && !d_act.upload(hact.data(), hact.size())) ||
-        (tx_mask && !d_spec.upload(hspec.data(), hspec.size())) || hipMemset(d_hist, 0, n_hist * 8) != hipSuccess ||
-        hipMemset(d_max, 0, (size_t)pairs * 4) != hipSuccess)
+    if (hipMemset(d_hist, 0, n_hist * 8) != hipSuccess || hipMemset(d_max, 0, (size_t)pairs * 4) != hipSuccess)
         return fail(WOFDM_E_HIP, "upload failed");
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) {
-        if (ev[0]) (void)hipEventDestroy(ev[0]);
-        return fail(WOFDM_E_HIP, "event creation failed");
-    }
-    wofdm_pparams pp{};
-    pp.S = S; pp.k = k; pp.P = P; pp.cp = cfg->cp; pp.cs = cfg->cs; pp.beta = beta; pp.n_bins = n_bins;
-    pp.lo_db = lo_db; pp.step_db = step_db;
-    pp.seed_lo = (uint32_t)cfg->seed; pp.seed_hi = (uint32_t)(cfg->seed >> 32);
-    pp.frames = frames; pp.frame_offset = cfg->frame_offset; pp.wdiv = 1;
-    pp.wtx = d_w; pp.amask = d_act; pp.spec = d_spec; pp.jobs = d_jobs; pp.mjobs = d_mjobs;
-    pp.X = d_X; pp.x = d_x; pp.Y = d_Y; pp.hist = d_hist; pp.max_bits = d_max; pp.periods = d_per;
+    wofdm_pparams pp = tx.params(cfg, g, S, 1, sh);
+    pp.n_bins = n_bins; pp.lo_db = lo_db; pp.step_db = step_db;
+    pp.hist = d_hist; pp.max_bits = d_max; pp.periods = d_per;
     std::vector<unsigned long long> hh(n_hist);
     std::vector<uint32_t> hmax((size_t)pairs);
     std::vector<float> hper(periods ? (size_t)n_periods * 2 : 0);
     float ms = 0.f;
     hipError_t e = hipSuccess;
-    {
-        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
-        std::lock_guard<std::mutex> gate(g_gate_mu);
-        (void)hipDeviceSynchronize();
-        const wofdm_aux_fns *ax = wofdm_aux(N);
-        e = ax ? hipEventRecord(ev[0], nullptr) : hipErrorInvalidValue;
-        for (uint64_t i0 = 0; e == hipSuccess && i0 < items; i0 += chunk) {
-            pp.item0 = i0;
-            pp.n_jobs = (int32_t)std::min<uint64_t>(chunk, items - i0);
-            e = ax->papr(&pp, nullptr);
-        }
-        if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    }
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
+    const wofdm_aux_fns *ax = wofdm_aux(N);
+    rc = run_chunks(items, chunk, [&](uint64_t item0, int32_t n_jobs) {
+        pp.item0 = item0;
+        pp.n_jobs = n_jobs;
+        return ax ? ax->papr(&pp, nullptr) : hipErrorInvalidValue;
+    }, &e, &ms);
+    if (rc != WOFDM_OK) return rc;
     if (e != hipSuccess || hipMemcpy(hh.data(), d_hist, n_hist * 8, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(hmax.data(), d_max, (size_t)pairs * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         (periods && hipMemcpy(hper.data(), d_per, (size_t)n_periods * 8, hipMemcpyDeviceToHost) != hipSuccess))
@@ -1561,501 +1645,585 @@ int wofdm_tx_papr_kernel_ms(float *ms)
 
 namespace {
 
-// the neighbour of wofdm_rx_profile_aci; a null pointer to it is wofdm_rx_profile
-struct aci_args {
+// A receive-profile call, whichever of the eight entry points made it: what every call has, and the stages that are on, each
+// with its own inputs and outputs.  The entry points fill it; rx_profile_run checks it, prepares the stages, runs the chunks
+// and copies back.
+struct rx_call {
+    const wofdm_cfg *cfg;
+    int device;
+    const float *w_tx, *w_rx, *h, *snr_db;
     const uint8_t *active;
-    const float *h;
-    int32_t delay;
-    float level_db;
-};
-// the receiver offsets of wofdm_rx_profile_sync and its per-symbol outputs; a null pointer to it is a synchronised receiver
-struct sync_args {
-    int32_t n_points;
-    const wofdm_sync_point *points;
-    uint64_t *sym_errs;
+    const float *tx_mask;
+    uint64_t *errs;
+    double *err_power;
+    int32_t arm;                      // RXP_* of wofdm_link.h: the receive kernel the chunks run
+    int32_t n_points;                 // the points (tracks) of the arm's point loop; 1 where it has none
+    bool per_symbol;                  // the arm has a point loop, and with it the per-symbol sums behind sym_errs, sym_power
+    uint64_t *sym_errs;               // (either may be null)
     double *sym_power;
-};
-// the moving channels of wofdm_rx_profile_doppler (they take the place of h) and its per-symbol outputs; a null pointer to it
-// is a channel that holds still over the frame
-struct doppler_args {
-    const float *h_track;
-    int32_t n_tracks, n_knots, knot_step;
-    uint64_t *sym_errs;
-    double *sym_power;
+    // the adjacent-band neighbour; a link call's offset and level are its points'
+    struct { bool on; const uint8_t *active; const float *h; int32_t delay; float level_db; } nb;
+    // the receiver's timing and carrier offsets
+    struct { bool on; const wofdm_sync_point *points; } sync;
+    // the channels that move within the frame; static_track: the static channel h stands behind them as one more track (it is
+    // then needed, and is the only track where on is false)
+    struct { bool on, static_track; const float *h_track; int32_t n_tracks, n_knots, knot_step; } dop;
+    // the power amplifier; ref_optional: no reference power is needed where every point is linear
+    struct { bool on, ref_optional; const wofdm_pa_point *points; const float *ref_power; double *pa_power; } amp;
+    // the oscillator's phase noise
+    struct { bool on; const wofdm_pn_point *points; } pn;
+    // the points of wofdm_rx_profile_link, which switch the five stages above per point; as_sync, as_pn, as_pa: what a point
+    // says to each of them, in the form the stage takes (its points point here)
+    struct {
+        bool on;
+        const wofdm_link_point *points;
+        std::vector<wofdm_sync_point> as_sync;
+        std::vector<wofdm_pn_point> as_pn;
+        std::vector<wofdm_pa_point> as_pa;
+    } link;
+    // the soft demapper of wofdm_rx_profile_soft
+    struct { bool on; int32_t n_scales; const float *scales; double *bit_penalty, *sym_penalty; } soft;
 };
 
-// the power amplifier of wofdm_rx_profile_pa and its outputs; a null pointer to it is a linear transmitter
-struct pa_args {
-    int32_t n_points;
-    const wofdm_pa_point *points;
-    const float *ref_power;
-    uint64_t *sym_errs;
-    double *sym_power;
-    double *pa_power;
+// the receive side's geometry beside the Tx chain's, and the cells of the call
+struct rx_geom : tx_geom {
+    int L, delta, gam, NW;
+    uint64_t pairs, cpp, cells, frames;   // cpp: cells per window pair
 };
 
-// the oscillator phase noise of wofdm_rx_profile_pn and its per-symbol outputs; a null pointer to it is an oscillator that holds
-// its phase
-struct pn_args {
-    int32_t n_points;
-    const wofdm_pn_point *points;
-    uint64_t *sym_errs;
-    double *sym_power;
+// A call on its way: the geometry, what the stages prepared on the host, their device side, and the chunk the launcher takes
+struct rx_run {
+    const rx_call &c;
+    rx_geom g;
+    // host: the allocations, whether a neighbour is on the air at all, the points as the kernels read them
+    std::vector<uint8_t> act, nb_act;
+    bool nb;
+    int max_theta;                    // the largest timing offset, or 0
+    std::vector<wofdm_spoint> pts;
+    std::vector<float2> base, taps;
+    std::vector<wofdm_pnpoint> pn;
+    std::vector<wofdm_lpoint> lk;
+    std::vector<wofdm_papoint> pa;
+    std::vector<float> asat;
+    int n_knots, knot_step;
+    // device
+    size_t chunk, n_out, n_sym, n_ptot, n_bpen, n_spen;
+    tx_shared sh;
+    tx_chain tx, nbtx;
+    dev_buf<float> d_wr, d_nlin, d_ppow, d_spow, d_asat, d_pwr, d_w2, d_bpart, d_spart;
+    dev_buf<float2> d_h, d_hi, d_base, d_y;
+    dev_buf<uint32_t> d_pcnt, d_scnt;
+    dev_buf<unsigned long long> d_errs, d_serrs;
+    dev_buf<double> d_pow, d_stot, d_ptot, d_walk, d_btot, d_sptot;
+    dev_buf<wofdm_spoint> d_pts;
+    dev_buf<wofdm_papoint> d_papts;
+    dev_buf<wofdm_pnpoint> d_pnpts;
+    dev_buf<wofdm_lpoint> d_lkpts;
+    wofdm_rxchunk ck;
+    int n_tracks() const { return c.dop.on ? c.dop.n_tracks : 0; }
 };
 
-// the five impairments combined (wofdm_rx_profile_link): its points beside the arguments of the arms it switches on -- sync, amp
-// and pn carry its points' receiver offsets, amplifiers and oscillators (n_points each, the outputs in sync and amp), dop the
-// tracks if a point names one, aci the neighbour's allocation and channels if a point has aci_on --, so every stage is checked
-// and prepared by the code of its own arm
-struct link_args {
-    int32_t n_points;
-    const wofdm_link_point *points;
-};
-// the soft outputs of wofdm_rx_profile_soft beside a link call's arguments (checked by its entry point); a null pointer to it is
-// wofdm_rx_profile_link
-struct soft_args {
-    int32_t n_scales;
-    const float *scales;
-    double *bit_penalty;
-    double *sym_penalty;
-};
-
-// wofdm_rx_profile, wofdm_rx_profile_aci, wofdm_rx_profile_sync, wofdm_rx_profile_doppler, wofdm_rx_profile_pa,
-// wofdm_rx_profile_pn and wofdm_rx_profile_link.  Every argument is checked before the first HIP call; the
-// caller's arrays are written only after everything has succeeded.
-int rx_profile_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
-                    const float *snr_db, const uint8_t *active, const float *tx_mask, const aci_args *aci, const sync_args *sync,
-                    const doppler_args *dop, const pa_args *amp, const pn_args *pn, const link_args *link, const soft_args *soft,
-                    uint64_t *errs, double *err_power)
+bool all_finite(const float *a, size_t n)
 {
-    // (the link call has the static channel beside its tracks, and needs no reference power where every point is linear)
-    if (!cfg || !w_tx || !w_rx || !(dop && !link ? dop->h_track : h) || (dop && !dop->h_track) || !snr_db || !errs)
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(a[i])) return false;
+    return true;
+}
+
+// ---- the checks, in the order a caller meets them: the NULL arguments and the stages' counts, the geometry, the finiteness ----
+
+int check_rx_args(const rx_call &c)
+{
+    if (!c.cfg || !c.w_tx || !c.w_rx || ((!c.dop.on || c.dop.static_track) && !c.h) || (c.dop.on && !c.dop.h_track) || !c.snr_db ||
+        !c.errs)
         return fail(WOFDM_E_INVALID, "NULL argument");
-    bool link_pa = false;
-    for (int i = 0; link && amp && amp->points && i < amp->n_points; ++i) link_pa |= amp->points[i].model != WOFDM_PA_LINEAR;
-    if (amp && (!amp->points || (!amp->ref_power && (!link || link_pa)))) return fail(WOFDM_E_INVALID, "NULL argument (points or ref_power)");
-    if (amp && amp->n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", amp->n_points);
-    if (aci && !aci->active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active)");
-    if (sync && !sync->points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
-    if (sync && sync->n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", sync->n_points);
-    if (pn && !pn->points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
-    if (pn && pn->n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", pn->n_points);
-    if (dop && (dop->n_tracks < 1 || dop->n_knots < 2 || dop->knot_step < 1))
-        return fail(WOFDM_E_INVALID, "n_tracks=%d must be >= 1, n_knots=%d >= 2, knot_step=%d >= 1", dop->n_tracks, dop->n_knots,
-                    dop->knot_step);
-    const int N = cfg->n_fft, k = cfg->bits_per_sc, S = cfg->syms_per_frame, L = cfg->n_taps;
-    if (N != 64 && N != 128 && N != 256 && N != 512 && N != 1024)
-        return fail(WOFDM_E_UNSUPPORTED, "n_fft=%d not in {64,128,256,512,1024}", N);
-    if (k != 2 && k != 4 && k != 6) return fail(WOFDM_E_UNSUPPORTED, "bits_per_sc=%d not in {2,4,6}", k);
-    if (S < 2 || S > WOFDM_MAX_SYMS) return fail(WOFDM_E_UNSUPPORTED, "syms_per_frame=%d not in [2,%d]", S, WOFDM_MAX_SYMS);
+    if (c.amp.on) {
+        bool needs_ref = !c.amp.ref_optional;
+        for (int i = 0; c.amp.ref_optional && c.amp.points && i < c.n_points; ++i)
+            needs_ref |= c.amp.points[i].model != WOFDM_PA_LINEAR;
+        if (!c.amp.points || (!c.amp.ref_power && needs_ref)) return fail(WOFDM_E_INVALID, "NULL argument (points or ref_power)");
+        if (c.n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", c.n_points);
+    }
+    if (c.nb.on && !c.nb.active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active)");
+    // (where both stages are on their points are the link call's, which has checked them)
+    if ((c.sync.on && !c.sync.points) || (c.pn.on && !c.pn.points)) return fail(WOFDM_E_INVALID, "NULL argument (points)");
+    if ((c.sync.on || c.pn.on) && c.n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", c.n_points);
+    if (c.dop.on && (c.dop.n_tracks < 1 || c.dop.n_knots < 2 || c.dop.knot_step < 1))
+        return fail(WOFDM_E_INVALID, "n_tracks=%d must be >= 1, n_knots=%d >= 2, knot_step=%d >= 1", c.dop.n_tracks, c.dop.n_knots,
+                    c.dop.knot_step);
+    return WOFDM_OK;
+}
+
+int check_rx_geometry(const rx_call &c, rx_geom *out)
+{
+    const wofdm_cfg *cfg = c.cfg;
+    int rc = check_tx_grid(cfg);
+    if (rc != WOFDM_OK) return rc;
+    const int N = cfg->n_fft, L = cfg->n_taps;
     if (cfg->n_channels < 1 || cfg->n_snr < 1 || cfg->n_window_pairs < 1)
         return fail(WOFDM_E_INVALID, "n_channels, n_snr, n_window_pairs must be >= 1");
     if (cfg->cp < 0 || cfg->cs < 0 || cfg->tail_tx < 0 || cfg->tail_rx < 0 || cfg->prefix_rm < 0 || cfg->circ_shift < 0 ||
         cfg->circ_shift >= N || L < 1)
         return fail(WOFDM_E_INVALID, "negative length, n_taps < 1 or circ_shift >= n_fft");
     if (L > WOFDM_MAX_TAPS) return fail(WOFDM_E_UNSUPPORTED, "n_taps=%d exceeds %d", L, WOFDM_MAX_TAPS);
-    const int P = N + cfg->cp + cfg->cs, beta = cfg->tail_tx, delta = cfg->tail_rx, gam = cfg->prefix_rm;
-    if ((delta & 1) || delta > 64) return fail(WOFDM_E_UNSUPPORTED, "tail_rx=%d must be even and <= 64", delta);
-    if (cfg->cp > N || cfg->cs > N || 2 * beta > P) return fail(WOFDM_E_UNSUPPORTED, "cp, cs <= n_fft and 2 tail_tx <= P required");
-    if (N + delta + gam != P - beta)
-        return fail(WOFDM_E_UNSUPPORTED, "n_fft+tail_rx+prefix_rm (%d) != n_fft+cp+cs-tail_tx (%d)", N + delta + gam, P - beta);
-    if (tx_mask && P > wofdm_txmask_batch_pmax(N))
-        return fail(WOFDM_E_UNSUPPORTED, "the Tx mask needs 3 P - 2 <= 8 n_fft, i.e. P = n_fft + cp + cs <= %d at n_fft = %d (P = %d)",
-                    wofdm_txmask_batch_pmax(N), N, P);
-    const uint64_t pairs = (uint64_t)cfg->n_window_pairs, cpp = (uint64_t)cfg->n_snr * (uint64_t)cfg->n_channels;
-    const uint64_t cells = pairs * cpp, frames = cfg->frames_per_cell;
+    rx_geom &g = *out;
+    static_cast<tx_geom &>(g) = tx_geom_of(cfg);
+    g.L = L; g.delta = cfg->tail_rx; g.gam = cfg->prefix_rm; g.NW = N + g.delta;
+    if ((g.delta & 1) || g.delta > 64) return fail(WOFDM_E_UNSUPPORTED, "tail_rx=%d must be even and <= 64", g.delta);
+    if (!tx_symbol_fits(cfg, g)) return fail(WOFDM_E_UNSUPPORTED, "cp, cs <= n_fft and 2 tail_tx <= P required");
+    if (N + g.delta + g.gam != g.B)
+        return fail(WOFDM_E_UNSUPPORTED, "n_fft+tail_rx+prefix_rm (%d) != n_fft+cp+cs-tail_tx (%d)", N + g.delta + g.gam, g.B);
+    if ((rc = check_mask_length(c.tx_mask, g)) != WOFDM_OK) return rc;
+    g.pairs = (uint64_t)cfg->n_window_pairs; g.cpp = (uint64_t)cfg->n_snr * (uint64_t)cfg->n_channels;
+    g.cells = g.pairs * g.cpp; g.frames = cfg->frames_per_cell;
     // (the cell shares its counter word with the stream id; w_off of the job tables is 32-bit)
-    if (cells >= (1u << 28) || pairs * (uint64_t)P > (uint64_t)INT32_MAX)
+    if (g.cells >= (1u << 28) || g.pairs * (uint64_t)g.P > (uint64_t)INT32_MAX)
         return fail(WOFDM_E_UNSUPPORTED, "too many cells (2^28) or window samples (2^31)");
-    if (frames > (UINT64_MAX >> 6) / cells) return fail(WOFDM_E_UNSUPPORTED, "cells * frames_per_cell * syms_per_frame overflows");
-    const int Lm = 2 * P - 1, FL = 8 * N, B = P - beta, T = beta + S * B, NW = N + delta;
-    const auto finite = [](const float *a, size_t n) {
-        for (size_t i = 0; i < n; ++i)
-            if (!std::isfinite(a[i])) return false;
-        return true;
-    };
-    if (!finite(w_tx, (size_t)pairs * P) || !finite(w_rx, (size_t)pairs * NW)) return fail(WOFDM_E_INVALID, "windows must be finite");
-    if ((!dop || link) && !finite(h, (size_t)cfg->n_channels * L * 2)) return fail(WOFDM_E_INVALID, "channel taps must be finite");
-    if (!finite(snr_db, (size_t)cfg->n_snr)) return fail(WOFDM_E_INVALID, "SNR points must be finite");
-    if (tx_mask && !finite(tx_mask, (size_t)Lm)) return fail(WOFDM_E_INVALID, "mask gains must be finite");
-    std::vector<uint8_t> hact;
-    if (active) {
-        hact.resize((size_t)N);
-        int n_act = 0;
-        for (int n = 0; n < N; ++n) n_act += (hact[(size_t)n] = active[n] ? 1 : 0);
-        if (n_act == 0) return fail(WOFDM_E_INVALID, "the allocation loads no subcarrier");
+    if (g.frames > (UINT64_MAX >> 6) / g.cells) return fail(WOFDM_E_UNSUPPORTED, "cells * frames_per_cell * syms_per_frame overflows");
+    return WOFDM_OK;
+}
+
+int check_rx_finite(const rx_call &c, const rx_geom &g)
+{
+    if (!all_finite(c.w_tx, (size_t)g.pairs * g.P) || !all_finite(c.w_rx, (size_t)g.pairs * g.NW))
+        return fail(WOFDM_E_INVALID, "windows must be finite");
+    if ((!c.dop.on || c.dop.static_track) && !all_finite(c.h, (size_t)c.cfg->n_channels * g.L * 2))
+        return fail(WOFDM_E_INVALID, "channel taps must be finite");
+    if (!all_finite(c.snr_db, (size_t)c.cfg->n_snr)) return fail(WOFDM_E_INVALID, "SNR points must be finite");
+    return check_mask_gains(c.tx_mask, g);
+}
+
+// ---- the stages' host side: a stage's points checked, and turned into what the kernels read ----
+
+// the neighbour: an allocation that loads no bin is "no neighbour" (nb stays false), and the call takes the route without one
+int prep_nb(rx_run &r)
+{
+    const auto &nb = r.c.nb;
+    if (!nb.on) return WOFDM_OK;
+    if (!std::isfinite(nb.level_db) || !std::isfinite((float)std::pow(10.0, 0.05 * (double)nb.level_db)))
+        return fail(WOFDM_E_INVALID, "aci_level_db must be finite, and so the amplitude 10^(level / 20) in single precision");
+    if (nb.delay < 0) return fail(WOFDM_E_INVALID, "aci_delay=%d is negative", nb.delay);
+    if (nb.delay >= r.g.B)
+        return fail(WOFDM_E_UNSUPPORTED, "aci_delay=%d must be below the symbol stride B = %d", nb.delay, r.g.B);
+    if (nb.h && !all_finite(nb.h, (size_t)r.c.cfg->n_channels * r.g.L * 2)) return fail(WOFDM_E_INVALID, "aci_h taps must be finite");
+    r.nb_act.resize((size_t)r.g.N);
+    for (int n = 0; n < r.g.N; ++n) r.nb |= (r.nb_act[(size_t)n] = nb.active[n] ? 1 : 0) != 0;
+    return WOFDM_OK;
+}
+
+// the receiver offsets: the base phasor of every (point, symbol) in double precision, from cfo as stored
+int prep_sync(rx_run &r)
+{
+    if (!r.c.sync.on) return WOFDM_OK;
+    const int NP = r.c.n_points, S = r.g.S, B = r.g.B;
+    if (NP > WOFDM_SYNC_MAX_POINTS) return fail(WOFDM_E_UNSUPPORTED, "n_points=%d exceeds %d", NP, WOFDM_SYNC_MAX_POINTS);
+    for (int i = 0; i < NP; ++i) {
+        const wofdm_sync_point &q = r.c.sync.points[i];
+        if (!std::isfinite(q.cfo)) return fail(WOFDM_E_INVALID, "points[%d].cfo must be finite", i);
+        if (q.reserved != 0) return fail(WOFDM_E_INVALID, "points[%d].reserved=%d must be 0", i, q.reserved);
+        if (q.cfo_tracked != 0 && q.cfo_tracked != 1)
+            return fail(WOFDM_E_INVALID, "points[%d].cfo_tracked=%d must be 0 or 1", i, q.cfo_tracked);
     }
-    // the neighbour: an allocation that loads no bin is "no neighbour" and takes the plain route (nb stays false)
-    std::vector<uint8_t> hiact;
-    bool nb = false;
-    if (aci) {
-        if (!std::isfinite(aci->level_db) || !std::isfinite((float)std::pow(10.0, 0.05 * (double)aci->level_db)))
-            return fail(WOFDM_E_INVALID, "aci_level_db must be finite, and so the amplitude 10^(level / 20) in single precision");
-        if (aci->delay < 0) return fail(WOFDM_E_INVALID, "aci_delay=%d is negative", aci->delay);
-        if (aci->delay >= B)
-            return fail(WOFDM_E_UNSUPPORTED, "aci_delay=%d must be below the symbol stride B = %d", aci->delay, B);
-        if (aci->h && !finite(aci->h, (size_t)cfg->n_channels * L * 2)) return fail(WOFDM_E_INVALID, "aci_h taps must be finite");
-        hiact.resize((size_t)N);
-        for (int n = 0; n < N; ++n) nb |= (hiact[(size_t)n] = aci->active[n] ? 1 : 0) != 0;
-    }
-    // the receiver offsets: the base phasor of every (point, symbol) in double precision, from cfo as stored
-    const int NP = link ? link->n_points : sync ? sync->n_points : (dop ? dop->n_tracks : (amp ? amp->n_points : (pn ? pn->n_points : 1)));
-    const int NTR = dop ? dop->n_tracks : 0;
-    int max_theta = 0;                                                // (link) the largest timing offset, or 0
-    std::vector<wofdm_spoint> hpts;
-    std::vector<float2> hbase;
-    if (sync) {
-        if (NP > WOFDM_SYNC_MAX_POINTS) return fail(WOFDM_E_UNSUPPORTED, "n_points=%d exceeds %d", NP, WOFDM_SYNC_MAX_POINTS);
-        for (int i = 0; i < NP; ++i) {
-            const wofdm_sync_point &q = sync->points[i];
-            if (!std::isfinite(q.cfo)) return fail(WOFDM_E_INVALID, "points[%d].cfo must be finite", i);
-            if (q.reserved != 0) return fail(WOFDM_E_INVALID, "points[%d].reserved=%d must be 0", i, q.reserved);
-            if (q.cfo_tracked != 0 && q.cfo_tracked != 1)
-                return fail(WOFDM_E_INVALID, "points[%d].cfo_tracked=%d must be 0 or 1", i, q.cfo_tracked);
-        }
-        hpts.resize((size_t)NP);
-        hbase.resize((size_t)NP * S);
-        for (int i = 0; i < NP; ++i) {
-            const wofdm_sync_point &q = sync->points[i];
-            if ((int64_t)q.timing >= (int64_t)B || (int64_t)q.timing <= -(int64_t)B)
-                return fail(WOFDM_E_UNSUPPORTED, "points[%d].timing=%d must lie inside (-B, B), B = %d", i, q.timing, B);
-            if (std::fabs(q.cfo) > 4.0f)
-                return fail(WOFDM_E_UNSUPPORTED, "points[%d].cfo=%g exceeds 4 subcarrier spacings", i, (double)q.cfo);
-            hpts[(size_t)i].theta = q.timing;
-            max_theta = std::max(max_theta, (int)q.timing);
-            hpts[(size_t)i].eps = q.cfo;
-            for (int s = 0; s < S; ++s) {
-                // eps (s B + gam + theta) / N is exact in double: 24 bits times less than 2^16, over a power of two
-                const double turns = (double)q.cfo * (double)(s * B + gam + q.timing) / (double)N;
-                const double ph = 2.0 * 3.14159265358979323846 * (turns - std::nearbyint(turns));
-                hbase[(size_t)i * S + s] =
-                    q.cfo_tracked ? make_float2(1.f, 0.f) : make_float2((float)std::cos(ph), (float)std::sin(ph));
-            }
+    r.pts.resize((size_t)NP);
+    r.base.resize((size_t)NP * S);
+    for (int i = 0; i < NP; ++i) {
+        const wofdm_sync_point &q = r.c.sync.points[i];
+        if ((int64_t)q.timing >= (int64_t)B || (int64_t)q.timing <= -(int64_t)B)
+            return fail(WOFDM_E_UNSUPPORTED, "points[%d].timing=%d must lie inside (-B, B), B = %d", i, q.timing, B);
+        if (std::fabs(q.cfo) > 4.0f)
+            return fail(WOFDM_E_UNSUPPORTED, "points[%d].cfo=%g exceeds 4 subcarrier spacings", i, (double)q.cfo);
+        r.pts[(size_t)i].theta = q.timing;
+        r.max_theta = std::max(r.max_theta, (int)q.timing);
+        r.pts[(size_t)i].eps = q.cfo;
+        for (int s = 0; s < S; ++s) {
+            // eps (s B + gam + theta) / N is exact in double: 24 bits times less than 2^16, over a power of two
+            const double turns = (double)q.cfo * (double)(s * B + r.g.gam + q.timing) / (double)r.g.N;
+            const double ph = 2.0 * 3.14159265358979323846 * (turns - std::nearbyint(turns));
+            r.base[(size_t)i * S + s] = q.cfo_tracked ? make_float2(1.f, 0.f) : make_float2((float)std::cos(ph), (float)std::sin(ph));
         }
     }
-    // the phase noise: sigma / (2 pi) = sqrt(beta / (2 pi n_fft)) of every point in double precision, from beta as stored
-    std::vector<wofdm_pnpoint> hpn;
-    if (pn) {
-        if (NP > WOFDM_PN_MAX_POINTS) return fail(WOFDM_E_UNSUPPORTED, "n_points=%d exceeds %d", NP, WOFDM_PN_MAX_POINTS);
-        for (int i = 0; i < NP; ++i) {
-            const wofdm_pn_point &q = pn->points[i];
-            if (!std::isfinite(q.linewidth) || q.linewidth < 0.f)
-                return fail(WOFDM_E_INVALID, "points[%d].linewidth must be finite and >= 0", i);
-            if (q.cpe_tracked != 0 && q.cpe_tracked != 1)
-                return fail(WOFDM_E_INVALID, "points[%d].cpe_tracked=%d must be 0 or 1", i, q.cpe_tracked);
-            if (q.reserved[0] != 0 || q.reserved[1] != 0) return fail(WOFDM_E_INVALID, "points[%d].reserved must be 0", i);
-        }
-        hpn.resize((size_t)NP);
-        for (int i = 0; i < NP; ++i) {
-            const wofdm_pn_point &q = pn->points[i];
-            if (q.linewidth > 1.0f)
-                return fail(WOFDM_E_UNSUPPORTED, "points[%d].linewidth=%g exceeds 1 subcarrier spacing", i, (double)q.linewidth);
-            hpn[(size_t)i].turn = std::sqrt((double)q.linewidth / (2.0 * 3.14159265358979323846 * (double)N));
-            hpn[(size_t)i].tracked = q.cpe_tracked;
-            hpn[(size_t)i].pad = 0;
-        }
+    return WOFDM_OK;
+}
+
+// the phase noise: sigma / (2 pi) = sqrt(beta / (2 pi n_fft)) of every point in double precision, from beta as stored
+int prep_pn(rx_run &r)
+{
+    if (!r.c.pn.on) return WOFDM_OK;
+    const int NP = r.c.n_points;
+    if (NP > WOFDM_PN_MAX_POINTS) return fail(WOFDM_E_UNSUPPORTED, "n_points=%d exceeds %d", NP, WOFDM_PN_MAX_POINTS);
+    for (int i = 0; i < NP; ++i) {
+        const wofdm_pn_point &q = r.c.pn.points[i];
+        if (!std::isfinite(q.linewidth) || q.linewidth < 0.f)
+            return fail(WOFDM_E_INVALID, "points[%d].linewidth must be finite and >= 0", i);
+        if (q.cpe_tracked != 0 && q.cpe_tracked != 1)
+            return fail(WOFDM_E_INVALID, "points[%d].cpe_tracked=%d must be 0 or 1", i, q.cpe_tracked);
+        if (q.reserved[0] != 0 || q.reserved[1] != 0) return fail(WOFDM_E_INVALID, "points[%d].reserved must be 0", i);
     }
-    // the moving channels: every knot finite, and the knots reach the last sample of conv, index T + L - 2
-    if (dop) {
-        if (NTR > WOFDM_DOPPLER_MAX_TRACKS) return fail(WOFDM_E_UNSUPPORTED, "n_tracks=%d exceeds %d", NTR, WOFDM_DOPPLER_MAX_TRACKS);
-        if (dop->n_knots > WOFDM_DOPPLER_MAX_KNOTS)
-            return fail(WOFDM_E_UNSUPPORTED, "n_knots=%d exceeds %d", dop->n_knots, WOFDM_DOPPLER_MAX_KNOTS);
-        if (!finite(dop->h_track, (size_t)NTR * cfg->n_channels * dop->n_knots * L * 2))
-            return fail(WOFDM_E_INVALID, "channel knots must be finite");
-        // (link: a late window takes taps max_theta samples further on; 0 otherwise)
-        if ((int64_t)(dop->n_knots - 1) * (int64_t)dop->knot_step < (int64_t)T + L - 2 + max_theta)
-            return fail(WOFDM_E_INVALID, "the knots end at sample %lld, the frame's last at %d: (n_knots - 1) knot_step >= "
-                        "tail_tx + S B + n_taps - 2%s required", (long long)(dop->n_knots - 1) * dop->knot_step, T + L - 2 + max_theta,
-                        link ? " + the largest positive timing" : "");
+    r.pn.resize((size_t)NP);
+    for (int i = 0; i < NP; ++i) {
+        const wofdm_pn_point &q = r.c.pn.points[i];
+        if (q.linewidth > 1.0f)
+            return fail(WOFDM_E_UNSUPPORTED, "points[%d].linewidth=%g exceeds 1 subcarrier spacing", i, (double)q.linewidth);
+        r.pn[(size_t)i].turn = std::sqrt((double)q.linewidth / (2.0 * 3.14159265358979323846 * (double)r.g.N));
+        r.pn[(size_t)i].tracked = q.cpe_tracked;
+        r.pn[(size_t)i].pad = 0;
     }
-    // the link points' own part: the track and the neighbour of every point
-    std::vector<wofdm_lpoint> hlk;
-    bool link_nb = false;
-    if (link) {
-        hlk.resize((size_t)NP);
-        for (int i = 0; i < NP; ++i) {
-            const wofdm_link_point &q = link->points[i];
-            if (q.track < -1 || q.track >= NTR) return fail(WOFDM_E_INVALID, "points[%d].track=%d must be -1 or below n_tracks=%d", i, q.track, NTR);
-            if (q.aci_on != 0 && q.aci_on != 1) return fail(WOFDM_E_INVALID, "points[%d].aci_on=%d must be 0 or 1", i, q.aci_on);
-            if (q.reserved[0] != 0 || q.reserved[1] != 0 || q.reserved[2] != 0 || q.reserved[3] != 0)
-                return fail(WOFDM_E_INVALID, "points[%d].reserved must be 0", i);
-            if (!std::isfinite(q.aci_level_db) || !std::isfinite((float)std::pow(10.0, 0.05 * (double)q.aci_level_db)))
-                return fail(WOFDM_E_INVALID, "points[%d].aci_level_db must be finite, and so the amplitude 10^(level / 20)", i);
-            if (q.aci_delay < 0) return fail(WOFDM_E_INVALID, "points[%d].aci_delay=%d is negative", i, q.aci_delay);
-        }
-        for (int i = 0; i < NP; ++i) {
-            const wofdm_link_point &q = link->points[i];
-            if (q.aci_delay >= B)
-                return fail(WOFDM_E_UNSUPPORTED, "points[%d].aci_delay=%d must be below the symbol stride B = %d", i, q.aci_delay, B);
-            // (an allocation that loads no bin is "no neighbour", as in wofdm_rx_profile_aci)
-            hlk[(size_t)i] = {q.track < 0 ? NTR : q.track, q.aci_on && nb ? 1 : 0, B - q.aci_delay,
-                              (float)std::pow(10.0, 0.05 * (double)q.aci_level_db)};
-            link_nb |= hlk[(size_t)i].aci_on != 0;
-        }
-        nb = link_nb;
+    return WOFDM_OK;
+}
+
+// the moving channels: every knot finite, and the knots reach the last sample of conv, index T + L - 2 -- under receiver
+// offsets a late window takes taps max_theta samples further on
+int check_knots(const rx_run &r)
+{
+    const auto &dop = r.c.dop;
+    if (!dop.on) return WOFDM_OK;
+    if (dop.n_tracks > WOFDM_DOPPLER_MAX_TRACKS)
+        return fail(WOFDM_E_UNSUPPORTED, "n_tracks=%d exceeds %d", dop.n_tracks, WOFDM_DOPPLER_MAX_TRACKS);
+    if (dop.n_knots > WOFDM_DOPPLER_MAX_KNOTS) return fail(WOFDM_E_UNSUPPORTED, "n_knots=%d exceeds %d", dop.n_knots, WOFDM_DOPPLER_MAX_KNOTS);
+    if (!all_finite(dop.h_track, (size_t)dop.n_tracks * r.c.cfg->n_channels * dop.n_knots * r.g.L * 2))
+        return fail(WOFDM_E_INVALID, "channel knots must be finite");
+    const int last = r.g.T + r.g.L - 2 + r.max_theta;
+    if ((int64_t)(dop.n_knots - 1) * (int64_t)dop.knot_step < (int64_t)last)
+        return fail(WOFDM_E_INVALID, "the knots end at sample %lld, the frame's last at %d: (n_knots - 1) knot_step >= "
+                    "tail_tx + S B + n_taps - 2%s required", (long long)(dop.n_knots - 1) * dop.knot_step, last,
+                    r.c.sync.on ? " + the largest positive timing" : "");
+    return WOFDM_OK;
+}
+
+// the link points' own part: the track and the neighbour of every point; a neighbour no point switches on is no neighbour
+int prep_link(rx_run &r)
+{
+    if (!r.c.link.on) return WOFDM_OK;
+    const int NP = r.c.n_points, NTR = r.n_tracks(), B = r.g.B;
+    for (int i = 0; i < NP; ++i) {
+        const wofdm_link_point &q = r.c.link.points[i];
+        if (q.track < -1 || q.track >= NTR) return fail(WOFDM_E_INVALID, "points[%d].track=%d must be -1 or below n_tracks=%d", i, q.track, NTR);
+        if (q.aci_on != 0 && q.aci_on != 1) return fail(WOFDM_E_INVALID, "points[%d].aci_on=%d must be 0 or 1", i, q.aci_on);
+        if (q.reserved[0] != 0 || q.reserved[1] != 0 || q.reserved[2] != 0 || q.reserved[3] != 0)
+            return fail(WOFDM_E_INVALID, "points[%d].reserved must be 0", i);
+        if (!std::isfinite(q.aci_level_db) || !std::isfinite((float)std::pow(10.0, 0.05 * (double)q.aci_level_db)))
+            return fail(WOFDM_E_INVALID, "points[%d].aci_level_db must be finite, and so the amplitude 10^(level / 20)", i);
+        if (q.aci_delay < 0) return fail(WOFDM_E_INVALID, "points[%d].aci_delay=%d is negative", i, q.aci_delay);
     }
-    // the amplifier: the points, and the saturation amplitude of every (point, pair) in double precision, stored in single
-    std::vector<wofdm_papoint> hpa;
-    std::vector<float> hasat;
-    if (amp) {
-        const int prc = check_pa_points(NP, amp->points, &hpa);
-        if (prc != WOFDM_OK) return prc;
-        hasat.assign((size_t)NP * pairs, 1.f);                        // (link, every point linear, no ref_power: never read)
-        for (uint64_t p = 0; amp->ref_power && p < pairs; ++p)
-            if (!std::isfinite(amp->ref_power[p]) || !(amp->ref_power[p] > 0.f))
-                return fail(WOFDM_E_INVALID, "ref_power[%llu] must be finite and positive", (unsigned long long)p);
-        for (int i = 0; amp->ref_power && i < NP; ++i)
-            for (uint64_t p = 0; p < pairs; ++p) {
-                // (the root of a positive single-precision number times 10^-4 ... 10^6 is a normal single-precision number)
-                hasat[(size_t)i * pairs + p] =
-                    (float)std::sqrt((double)amp->ref_power[p] * std::pow(10.0, 0.1 * (double)amp->points[i].ibo_db));
-            }
+    r.lk.resize((size_t)NP);
+    bool any_nb = false;
+    for (int i = 0; i < NP; ++i) {
+        const wofdm_link_point &q = r.c.link.points[i];
+        if (q.aci_delay >= B)
+            return fail(WOFDM_E_UNSUPPORTED, "points[%d].aci_delay=%d must be below the symbol stride B = %d", i, q.aci_delay, B);
+        // (an allocation that loads no bin is "no neighbour", as in wofdm_rx_profile_aci; the static track is the last)
+        r.lk[(size_t)i] = {q.track < 0 ? NTR : q.track, q.aci_on && r.nb ? 1 : 0, B - q.aci_delay,
+                           (float)std::pow(10.0, 0.05 * (double)q.aci_level_db)};
+        any_nb |= r.lk[(size_t)i].aci_on != 0;
     }
-    int rc = use_device(device);
-    if (rc != WOFDM_OK) return rc;
-    g_rxprof_ms = 0.f;
-    const uint64_t items = cells * frames;
-    if (items == 0) return WOFDM_OK;
-    // frames per chunk: what the budget holds (symbol grid + waveform + filtered symbols + partials of a frame; with a neighbour
-    // its S + 1 symbols beside them), as the header documents it
-    const int Ti = T + B;
-    // (under receiver offsets, moving channels or phase noise the partials are per point or track, per bin and per symbol;
-    // behind the amplifier every point has a waveform of its own beside them; the phase walk is S B doubles)
-    // (the link call: the amplifier's per-point term, the walk, and the neighbour's buffers where a point has aci_on)
-    const uint64_t job_bytes = 8ull * ((uint64_t)S * N + (uint64_t)T + (tx_mask ? (uint64_t)S * Lm : 0ull) +
-                                       (link ? (uint64_t)NP * (uint64_t)(N + S + T) : sync || dop || pn ? (uint64_t)NP * (uint64_t)(N + S) : (amp ? (uint64_t)NP * (uint64_t)(N + S + T) : (uint64_t)N)) +
-                                       (pn ? (uint64_t)S * B : 0ull) +
-                                       (nb ? (uint64_t)(S + 1) * N + (uint64_t)Ti + (tx_mask ? (uint64_t)(S + 1) * Lm : 0ull) : 0ull)) +
-                               // (the soft call: per point and scale the penalties of every data symbol's bins and the symbols' sums, fp32)
-                               (soft ? 4ull * (uint64_t)NP * (uint64_t)soft->n_scales * ((uint64_t)(S - 1) * N + (uint64_t)S) : 0ull);
-    const uint64_t chunk = std::min<uint64_t>(items, std::min<uint64_t>(WOFDM_PAPR_MAX_JOBS,
-                                                                       std::max<uint64_t>(1, WOFDM_RX_PROFILE_CHUNK_BYTES / job_bytes)));
-    std::vector<float2> hspec;
-    if (tx_mask) {
-        hspec.resize((size_t)FL);
-        mask_fastconv_spectrum(tx_mask, Lm, FL, hspec.data());
-    }
-    geom g{};
-    g.L = L;
-    // the taps as the kernels read them; of moving channels the knots, [n_tracks][n_channels][n_knots][WOFDM_LT], zero padded
-    std::vector<float2> hp;
-    // (link: the knots of its tracks and behind them the static track, h at every knot -- two knots that cover every sample
-    // where no point names a track)
-    const int link_knots = dop ? dop->n_knots : 2, link_step = dop ? dop->knot_step : T + L + B;
-    if (dop) {
-        const size_t rows = (size_t)NTR * cfg->n_channels * dop->n_knots;
-        hp.assign(rows * WOFDM_LT, make_float2(0.f, 0.f));
-        for (size_t r = 0; r < rows; ++r)
-            for (int l = 0; l < L; ++l)
-                hp[r * WOFDM_LT + l] = make_float2(dop->h_track[2 * (r * L + l)], dop->h_track[2 * (r * L + l) + 1]);
-    }
-    if (link) {
-        const std::vector<float2> hs = pack_taps(cfg, g, h);
-        for (int c = 0; c < cfg->n_channels; ++c)
-            for (int q = 0; q < link_knots; ++q) hp.insert(hp.end(), hs.begin() + (size_t)c * WOFDM_LT, hs.begin() + (size_t)(c + 1) * WOFDM_LT);
-    } else if (!dop) {
-        hp = pack_taps(cfg, g, h);
-    }
-    std::vector<float> nlin((size_t)cfg->n_snr);
-    for (int i = 0; i < cfg->n_snr; ++i) nlin[(size_t)i] = (float)std::pow(10.0, -0.1 * (double)snr_db[i]);
-    const size_t n_w = (size_t)pairs * P, n_wr = (size_t)pairs * NW, n_out = (size_t)NP * cells * N;
-    const size_t n_sym = sync || dop || amp || pn ? (size_t)NP * cells * (S - 1) : 0;
-    dev_buf<float> d_w, d_wr, d_nlin, d_ppow;
-    dev_buf<uint8_t> d_act;
-    dev_buf<float2> d_h, d_spec, d_X, d_x, d_Y;
-    dev_buf<wofdm_bjob> d_jobs;
-    dev_buf<wofdm_mjob> d_mjobs;
-    dev_buf<uint32_t> d_pcnt;
-    dev_buf<unsigned long long> d_errs;
-    dev_buf<double> d_pow;
-    if (!d_w.alloc(n_w) || !d_wr.alloc(n_wr) || !d_nlin.alloc(nlin.size()) || !d_h.alloc(hp.size()) ||
-        !d_X.alloc((size_t)chunk * S * N) || !d_x.alloc((size_t)chunk * T) || !d_jobs.alloc((size_t)chunk) ||
-        !d_ppow.alloc((size_t)chunk * NP * N) || !d_pcnt.alloc((size_t)chunk * NP * N) || !d_errs.alloc(2 * n_out) ||
-        !d_pow.alloc(n_out) ||
-        (active && !d_act.alloc(hact.size())) ||
-        (tx_mask && (!d_spec.alloc(hspec.size()) || !d_Y.alloc((size_t)chunk * S * Lm) || !d_mjobs.alloc((size_t)chunk))))
-        return fail(WOFDM_E_NOMEM, "device allocation failed");
-    if (!d_w.upload(w_tx, n_w) || !d_wr.upload(w_rx, n_wr) || !d_nlin.upload(nlin.data(), nlin.size()) ||
-        !d_h.upload(hp.data(), hp.size()) || (active && !d_act.upload(hact.data(), hact.size())) ||
-        (tx_mask && !d_spec.upload(hspec.data(), hspec.size())) || hipMemset(d_errs, 0, 2 * n_out * 8) != hipSuccess ||
-        hipMemset(d_pow, 0, n_out * 8) != hipSuccess)
-        return fail(WOFDM_E_HIP, "upload failed");
-    // the receiver offsets' side: the points, their base phasors, and the per-symbol partials and totals
-    dev_buf<wofdm_spoint> d_pts;
-    dev_buf<float2> d_base;
-    dev_buf<float> d_spow;
-    dev_buf<uint32_t> d_scnt;
-    dev_buf<unsigned long long> d_serrs;
-    dev_buf<double> d_stot;
-    if (sync || dop || amp || pn) {
-        if ((sync && (!d_pts.alloc(hpts.size()) || !d_base.alloc(hbase.size()))) || !d_spow.alloc((size_t)chunk * NP * S) ||
-            !d_scnt.alloc((size_t)chunk * NP * S) || !d_serrs.alloc(2 * n_sym) || !d_stot.alloc(n_sym))
-            return fail(WOFDM_E_NOMEM, "device allocation failed (receiver offsets or tracks)");
-        if ((sync && (!d_pts.upload(hpts.data(), hpts.size()) || !d_base.upload(hbase.data(), hbase.size()))) ||
-            hipMemset(d_serrs, 0, 2 * n_sym * 8) != hipSuccess || hipMemset(d_stot, 0, n_sym * 8) != hipSuccess)
-            return fail(WOFDM_E_HIP, "upload failed");
-    }
-    // the amplifier's side: points, saturation amplitudes, the points' waveforms and power sums of the chunk, the power totals
-    dev_buf<wofdm_papoint> d_papts;
-    dev_buf<float> d_asat, d_pwr;
-    dev_buf<float2> d_y;
-    dev_buf<double> d_ptot;
-    const size_t n_ptot = amp ? (size_t)NP * cells * 2 : 0;
-    if (amp) {
-        if (!d_papts.alloc(hpa.size()) || !d_asat.alloc(hasat.size()) || !d_y.alloc((size_t)chunk * NP * T) ||
-            !d_pwr.alloc((size_t)chunk * NP * 2) || !d_ptot.alloc(n_ptot))
-            return fail(WOFDM_E_NOMEM, "device allocation failed (amplifier)");
-        if (!d_papts.upload(hpa.data(), hpa.size()) || !d_asat.upload(hasat.data(), hasat.size()) ||
-            hipMemset(d_ptot, 0, n_ptot * 8) != hipSuccess)
-            return fail(WOFDM_E_HIP, "upload failed");
-    }
-    // the phase noise's side: the points and the unit walks of the chunk's items
-    dev_buf<wofdm_pnpoint> d_pnpts;
-    dev_buf<double> d_walk;
-    if (pn) {
-        if (!d_pnpts.alloc(hpn.size()) || !d_walk.alloc((size_t)chunk * S * B))
-            return fail(WOFDM_E_NOMEM, "device allocation failed (phase noise)");
-        if (!d_pnpts.upload(hpn.data(), hpn.size())) return fail(WOFDM_E_HIP, "upload failed");
-    }
-    dev_buf<wofdm_lpoint> d_lkpts;
-    if (link) {
-        if (!d_lkpts.alloc(hlk.size())) return fail(WOFDM_E_NOMEM, "device allocation failed (link points)");
-        if (!d_lkpts.upload(hlk.data(), hlk.size())) return fail(WOFDM_E_HIP, "upload failed");
-    }
-    // the demapper's side: the pairs' W2 = sum w_rx^2 (double, stored in single), the chunk's penalties, the totals
-    dev_buf<float> d_w2, d_bpart, d_spart;
-    dev_buf<double> d_btot, d_sptot;
-    const size_t NSC = soft ? (size_t)soft->n_scales : 0, n_bpen = (size_t)NP * cells * NSC * N, n_spen = (size_t)NP * cells * NSC * (S - 1);
-    wofdm_softparams sopar{};
-    if (soft) {
-        std::vector<float> hw2((size_t)pairs);
+    r.nb = any_nb;
+    return WOFDM_OK;
+}
+
+// the amplifier: the points, and the saturation amplitude of every (point, pair) in double precision, stored in single
+int prep_amp(rx_run &r)
+{
+    const auto &amp = r.c.amp;
+    if (!amp.on) return WOFDM_OK;
+    const int NP = r.c.n_points;
+    const uint64_t pairs = r.g.pairs;
+    const int prc = check_pa_points(NP, amp.points, &r.pa);
+    if (prc != WOFDM_OK) return prc;
+    r.asat.assign((size_t)NP * pairs, 1.f);                           // (every point linear and no ref_power: never read)
+    for (uint64_t p = 0; amp.ref_power && p < pairs; ++p)
+        if (!std::isfinite(amp.ref_power[p]) || !(amp.ref_power[p] > 0.f))
+            return fail(WOFDM_E_INVALID, "ref_power[%llu] must be finite and positive", (unsigned long long)p);
+    for (int i = 0; amp.ref_power && i < NP; ++i)
         for (uint64_t p = 0; p < pairs; ++p) {
-            double acc = 0.0;
-            for (int m = 0; m < NW; ++m) acc += (double)w_rx[p * NW + m] * (double)w_rx[p * NW + m];
-            hw2[(size_t)p] = (float)acc;
+            // (the root of a positive single-precision number times 10^-4 ... 10^6 is a normal single-precision number)
+            r.asat[(size_t)i * pairs + p] = (float)std::sqrt((double)amp.ref_power[p] * std::pow(10.0, 0.1 * (double)amp.points[i].ibo_db));
         }
-        if (!d_w2.alloc(hw2.size()) || !d_bpart.alloc((size_t)chunk * NP * (S - 1) * NSC * N) ||
-            !d_spart.alloc((size_t)chunk * NP * NSC * S) || !d_btot.alloc(n_bpen) || !d_sptot.alloc(n_spen))
-            return fail(WOFDM_E_NOMEM, "device allocation failed (soft outputs)");
-        if (!d_w2.upload(hw2.data(), hw2.size()) || hipMemset(d_btot, 0, n_bpen * 8) != hipSuccess ||
-            hipMemset(d_sptot, 0, n_spen * 8) != hipSuccess)
-            return fail(WOFDM_E_HIP, "upload failed");
-        sopar.n_scales = soft->n_scales;
-        for (int j = 0; j < soft->n_scales; ++j) sopar.cs[j] = (float)((double)soft->scales[j] * 1.4426950408889634074);
-        sopar.w2 = d_w2; sopar.bit_part = d_bpart; sopar.sym_part = d_spart; sopar.bit_tot = d_btot; sopar.sym_tot = d_sptot;
+    return WOFDM_OK;
+}
+
+// The taps as the kernels read them.  Of moving channels the knots, [n_tracks][n_channels][n_knots][WOFDM_LT], zero padded, and
+// behind them the static track where the call has one: h at every knot (without a track of the caller's, two knots that cover
+// every sample).  Without either, h as it is -- the static track of one knot.
+void pack_channel(rx_run &r)
+{
+    const rx_call &c = r.c;
+    const int L = r.g.L;
+    r.n_knots = c.dop.on ? c.dop.n_knots : 2;
+    r.knot_step = c.dop.on ? c.dop.knot_step : r.g.T + L + r.g.B;
+    const size_t rows = c.dop.on ? (size_t)c.dop.n_tracks * c.cfg->n_channels * c.dop.n_knots : 0;
+    r.taps.assign(rows * WOFDM_LT, make_float2(0.f, 0.f));
+    for (size_t row = 0; row < rows; ++row)
+        for (int l = 0; l < L; ++l)
+            r.taps[row * WOFDM_LT + l] = make_float2(c.dop.h_track[2 * (row * L + l)], c.dop.h_track[2 * (row * L + l) + 1]);
+    if (c.dop.on && !c.dop.static_track) return;
+    geom gl{};
+    gl.L = L;
+    const std::vector<float2> hs = pack_taps(c.cfg, gl, c.h);
+    for (int ch = 0; ch < c.cfg->n_channels; ++ch)
+        for (int q = 0; q < (c.dop.static_track ? r.n_knots : 1); ++q)
+            r.taps.insert(r.taps.end(), hs.begin() + (size_t)ch * WOFDM_LT, hs.begin() + (size_t)(ch + 1) * WOFDM_LT);
+}
+
+// Bytes of scratch per frame, the sum of the stages' terms as the header documents them: 8-byte words but for the demapper's
+uint64_t rx_job_bytes(const rx_run &r)
+{
+    const rx_call &c = r.c;
+    const uint64_t S = (uint64_t)r.g.S, N = (uint64_t)r.g.N, T = (uint64_t)r.g.T, B = (uint64_t)r.g.B, NP = (uint64_t)c.n_points;
+    const uint64_t Lm = c.tx_mask ? (uint64_t)r.g.Lm : 0;                  // filtered symbols only under a mask
+    uint64_t words = S * N + T + S * Lm;                                  // symbol grid, waveform, filtered symbols
+    words += NP * N;                                                      // the partials per bin, of every point
+    if (c.per_symbol) words += NP * S;                                    // the partials per symbol
+    if (c.amp.on) words += NP * T;                                        // every point's amplified waveform
+    if (c.pn.on) words += S * B;                                          // the unit phase walk
+    if (r.nb) words += (S + 1) * N + (T + B) + (S + 1) * Lm;              // the neighbour's chain of S + 1 symbols
+    // the demapper: per point and scale the penalties of every data symbol's bins and the symbols' sums, fp32
+    return 8 * words + (c.soft.on ? 4 * NP * (uint64_t)c.soft.n_scales * ((S - 1) * N + S) : 0);
+}
+
+// ---- the stages' device side: allocation, upload, and the stage's parameters in the chunk ----
+
+// the Tx chain, the receive kernel's constants, the partials per bin and the totals
+int stage_base(rx_run &r)
+{
+    const rx_call &c = r.c;
+    const rx_geom &g = r.g;
+    const size_t NP = (size_t)c.n_points, n_wr = (size_t)g.pairs * g.NW, n_part = r.chunk * NP * g.N;
+    std::vector<float> nlin((size_t)c.cfg->n_snr);
+    for (int i = 0; i < c.cfg->n_snr; ++i) nlin[(size_t)i] = (float)std::pow(10.0, -0.1 * (double)c.snr_db[i]);
+    int rc = r.sh.stage(c.w_tx, (size_t)g.pairs * g.P, c.tx_mask, g);
+    if (rc == WOFDM_OK) rc = r.tx.stage(g, g.S, r.chunk, r.act, c.tx_mask != nullptr, "");
+    if (rc != WOFDM_OK) return rc;
+    if (!r.d_wr.alloc(n_wr) || !r.d_nlin.alloc(nlin.size()) || !r.d_h.alloc(r.taps.size()) || !r.d_ppow.alloc(n_part) ||
+        !r.d_pcnt.alloc(n_part) || !r.d_errs.alloc(2 * r.n_out) || !r.d_pow.alloc(r.n_out))
+        return fail(WOFDM_E_NOMEM, "device allocation failed");
+    if (!r.d_wr.upload(c.w_rx, n_wr) || !r.d_nlin.upload(nlin.data(), nlin.size()) || !r.d_h.upload(r.taps.data(), r.taps.size()) ||
+        hipMemset(r.d_errs, 0, 2 * r.n_out * 8) != hipSuccess || hipMemset(r.d_pow, 0, r.n_out * 8) != hipSuccess)
+        return fail(WOFDM_E_HIP, "upload failed");
+    r.ck.tx = r.tx.params(c.cfg, g, g.S, (uint32_t)g.cpp, r.sh);
+    wofdm_rparams &rp = r.ck.r;
+    rp.S = g.S; rp.k = g.k; rp.B = g.B; rp.T = g.T; rp.NL = c.cfg->noise_before_truncate ? g.T + g.L - 1 : g.S * g.B;
+    rp.delta = g.delta; rp.gam = g.gam; rp.kap = c.cfg->circ_shift; rp.n_ch = c.cfg->n_channels; rp.n_snr = c.cfg->n_snr;
+    rp.seed_lo = r.ck.tx.seed_lo; rp.seed_hi = r.ck.tx.seed_hi; rp.frames = g.frames; rp.frame_offset = c.cfg->frame_offset;
+    rp.X = r.tx.X; rp.x = r.tx.x; rp.wrx = r.d_wr; rp.h = r.d_h; rp.nlin = r.d_nlin; rp.amask = r.tx.act;
+    rp.part_pow = r.d_ppow; rp.part_cnt = r.d_pcnt; rp.errs = r.d_errs; rp.pow = r.d_pow;
+    if (c.dop.on || c.dop.static_track) {
+        r.ck.dp.knots = r.d_h; r.ck.dp.n_knots = r.n_knots; r.ck.dp.knot_step = r.knot_step;
     }
-    // the neighbour's side of the chunk: allocation, channels, and grids, waveforms, tables of its S + 1 symbols
-    dev_buf<uint8_t> d_iact;
-    dev_buf<float2> d_hi, d_Xi, d_xi, d_Yi;
-    dev_buf<wofdm_bjob> d_ijobs;
-    dev_buf<wofdm_mjob> d_imjobs;
-    if (nb) {
-        const std::vector<float2> hpi = pack_taps(cfg, g, aci->h ? aci->h : h);
-        if (!d_iact.alloc(hiact.size()) || !d_hi.alloc(hpi.size()) || !d_Xi.alloc((size_t)chunk * (S + 1) * N) ||
-            !d_xi.alloc((size_t)chunk * Ti) || !d_ijobs.alloc((size_t)chunk) ||
-            (tx_mask && (!d_Yi.alloc((size_t)chunk * (S + 1) * Lm) || !d_imjobs.alloc((size_t)chunk))))
-            return fail(WOFDM_E_NOMEM, "device allocation failed (neighbour)");
-        if (!d_iact.upload(hiact.data(), hiact.size()) || !d_hi.upload(hpi.data(), hpi.size()))
-            return fail(WOFDM_E_HIP, "upload failed");
+    r.ck.n_tracks = r.n_tracks() + 1; r.ck.max_theta = r.max_theta;
+    return WOFDM_OK;
+}
+
+// the point loop's side: the receiver offsets' points and base phasors, and the per-symbol partials and totals
+int stage_points(rx_run &r)
+{
+    wofdm_sparams &sp = r.ck.sp;
+    sp.n_points = r.c.n_points; sp.cells = r.g.cells;
+    if (!r.c.per_symbol) return WOFDM_OK;
+    const size_t n_part = r.chunk * (size_t)r.c.n_points * r.g.S;
+    const bool sync = r.c.sync.on;
+    if ((sync && (!r.d_pts.alloc(r.pts.size()) || !r.d_base.alloc(r.base.size()))) || !r.d_spow.alloc(n_part) || !r.d_scnt.alloc(n_part) ||
+        !r.d_serrs.alloc(2 * r.n_sym) || !r.d_stot.alloc(r.n_sym))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (receiver offsets or tracks)");
+    if ((sync && (!r.d_pts.upload(r.pts.data(), r.pts.size()) || !r.d_base.upload(r.base.data(), r.base.size()))) ||
+        hipMemset(r.d_serrs, 0, 2 * r.n_sym * 8) != hipSuccess || hipMemset(r.d_stot, 0, r.n_sym * 8) != hipSuccess)
+        return fail(WOFDM_E_HIP, "upload failed");
+    sp.pts = r.d_pts; sp.base = r.d_base; sp.sym_pow = r.d_spow; sp.sym_cnt = r.d_scnt; sp.sym_errs = r.d_serrs; sp.sym_tot = r.d_stot;
+    return WOFDM_OK;
+}
+
+// the amplifier's side: points, saturation amplitudes, the points' waveforms and power sums of the chunk, the power totals
+int stage_amp(rx_run &r)
+{
+    if (!r.c.amp.on) return WOFDM_OK;
+    const size_t NP = (size_t)r.c.n_points;
+    if (!r.d_papts.alloc(r.pa.size()) || !r.d_asat.alloc(r.asat.size()) || !r.d_y.alloc(r.chunk * NP * r.g.T) ||
+        !r.d_pwr.alloc(r.chunk * NP * 2) || !r.d_ptot.alloc(r.n_ptot))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (amplifier)");
+    if (!r.d_papts.upload(r.pa.data(), r.pa.size()) || !r.d_asat.upload(r.asat.data(), r.asat.size()) ||
+        hipMemset(r.d_ptot, 0, r.n_ptot * 8) != hipSuccess)
+        return fail(WOFDM_E_HIP, "upload failed");
+    wofdm_paparams &pa = r.ck.pa;
+    pa.n_points = (int32_t)NP; pa.pairs = (int32_t)r.g.pairs; pa.pts = r.d_papts; pa.asat = r.d_asat; pa.y = r.d_y;
+    pa.pwr = r.d_pwr; pa.pwr_tot = r.d_ptot;
+    return WOFDM_OK;
+}
+
+// the phase noise's side: the points and the unit walks of the chunk's items
+int stage_pn(rx_run &r)
+{
+    if (!r.c.pn.on) return WOFDM_OK;
+    if (!r.d_pnpts.alloc(r.pn.size()) || !r.d_walk.alloc(r.chunk * r.g.S * r.g.B)) return fail(WOFDM_E_NOMEM, "device allocation failed (phase noise)");
+    if (!r.d_pnpts.upload(r.pn.data(), r.pn.size())) return fail(WOFDM_E_HIP, "upload failed");
+    r.ck.pn.pts = r.d_pnpts; r.ck.pn.walk = r.d_walk;
+    return WOFDM_OK;
+}
+
+int stage_link(rx_run &r)
+{
+    if (!r.c.link.on) return WOFDM_OK;
+    if (!r.d_lkpts.alloc(r.lk.size())) return fail(WOFDM_E_NOMEM, "device allocation failed (link points)");
+    if (!r.d_lkpts.upload(r.lk.data(), r.lk.size())) return fail(WOFDM_E_HIP, "upload failed");
+    r.ck.lk.pts = r.d_lkpts;
+    return WOFDM_OK;
+}
+
+// the demapper's side: the pairs' W2 = sum w_rx^2 (double, stored in single), the scales as c_j log2(e), the chunk's penalties,
+// the totals
+int stage_soft(rx_run &r)
+{
+    const auto &soft = r.c.soft;
+    if (!soft.on) return WOFDM_OK;
+    const rx_geom &g = r.g;
+    const size_t NP = (size_t)r.c.n_points, NSC = (size_t)soft.n_scales;
+    std::vector<float> hw2((size_t)g.pairs);
+    for (uint64_t p = 0; p < g.pairs; ++p) {
+        double acc = 0.0;
+        for (int m = 0; m < g.NW; ++m) acc += (double)r.c.w_rx[p * g.NW + m] * (double)r.c.w_rx[p * g.NW + m];
+        hw2[(size_t)p] = (float)acc;
     }
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) {
-        if (ev[0]) (void)hipEventDestroy(ev[0]);
-        return fail(WOFDM_E_HIP, "event creation failed");
-    }
-    wofdm_pparams pp{};
-    pp.S = S; pp.k = k; pp.P = P; pp.cp = cfg->cp; pp.cs = cfg->cs; pp.beta = beta; pp.n_bins = 1;
-    pp.seed_lo = (uint32_t)cfg->seed; pp.seed_hi = (uint32_t)(cfg->seed >> 32);
-    pp.frames = frames; pp.frame_offset = cfg->frame_offset; pp.wdiv = (uint32_t)cpp;
-    pp.wtx = d_w; pp.amask = d_act; pp.spec = d_spec; pp.jobs = d_jobs; pp.mjobs = d_mjobs;
-    pp.X = d_X; pp.x = d_x; pp.Y = d_Y;
-    wofdm_sparams spar{};
-    spar.n_points = NP; spar.cells = cells; spar.pts = d_pts; spar.base = d_base; spar.sym_pow = d_spow; spar.sym_cnt = d_scnt;
-    spar.sym_errs = d_serrs; spar.sym_tot = d_stot;
-    wofdm_dparams dpar{};
-    if (dop || link) {
-        dpar.knots = d_h; dpar.n_knots = link_knots; dpar.knot_step = link_step;
-    }
-    wofdm_lparams lkpar{};
-    lkpar.pts = d_lkpts;
-    wofdm_paparams papar{};
-    if (amp) {
-        papar.n_points = NP; papar.pairs = (int32_t)pairs; papar.pts = d_papts; papar.asat = d_asat; papar.y = d_y;
-        papar.pwr = d_pwr; papar.pwr_tot = d_ptot;
-    }
-    wofdm_pnparams pnpar{};
-    pnpar.pts = d_pnpts; pnpar.walk = d_walk;
-    wofdm_rparams rp{};
-    rp.S = S; rp.k = k; rp.B = B; rp.T = T; rp.NL = cfg->noise_before_truncate ? T + L - 1 : S * B;
-    rp.delta = delta; rp.gam = gam; rp.kap = cfg->circ_shift; rp.n_ch = cfg->n_channels; rp.n_snr = cfg->n_snr;
-    rp.seed_lo = pp.seed_lo; rp.seed_hi = pp.seed_hi; rp.frames = frames; rp.frame_offset = cfg->frame_offset;
-    rp.X = d_X; rp.x = d_x; rp.wrx = d_wr; rp.h = d_h; rp.nlin = d_nlin; rp.amask = d_act;
-    rp.part_pow = d_ppow; rp.part_cnt = d_pcnt; rp.errs = d_errs; rp.pow = d_pow;
-    wofdm_pparams pa = pp;
-    wofdm_aparams apar{};
-    if (nb) {
-        pa.S = S + 1; pa.stream = WOFDM_STREAM_ACI; pa.amask = d_iact; pa.jobs = d_ijobs; pa.mjobs = d_imjobs;
-        pa.X = d_Xi; pa.x = d_xi; pa.Y = d_Yi;
-        apar.xi = d_xi; apar.hi = d_hi; apar.Ti = Ti; apar.ioff = B - aci->delay;
-        apar.a_lvl = (float)std::pow(10.0, 0.05 * (double)aci->level_db);
-    }
-    std::vector<unsigned long long> herr(2 * n_out), hserr(2 * n_sym);
-    std::vector<double> hpow(n_out), hspow(n_sym), hptot(n_ptot), hbpen(n_bpen), hspen(n_spen);
+    if (!r.d_w2.alloc(hw2.size()) || !r.d_bpart.alloc(r.chunk * NP * (g.S - 1) * NSC * g.N) || !r.d_spart.alloc(r.chunk * NP * NSC * g.S) ||
+        !r.d_btot.alloc(r.n_bpen) || !r.d_sptot.alloc(r.n_spen))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (soft outputs)");
+    if (!r.d_w2.upload(hw2.data(), hw2.size()) || hipMemset(r.d_btot, 0, r.n_bpen * 8) != hipSuccess ||
+        hipMemset(r.d_sptot, 0, r.n_spen * 8) != hipSuccess)
+        return fail(WOFDM_E_HIP, "upload failed");
+    wofdm_softparams &so = r.ck.soft;
+    so.n_scales = soft.n_scales;
+    for (int j = 0; j < soft.n_scales; ++j) so.cs[j] = (float)((double)soft.scales[j] * 1.4426950408889634074);
+    so.w2 = r.d_w2; so.bit_part = r.d_bpart; so.sym_part = r.d_spart; so.bit_tot = r.d_btot; so.sym_tot = r.d_sptot;
+    r.ck.soft_on = true;
+    return WOFDM_OK;
+}
+
+// the neighbour's side of the chunk: allocation, channels, and the Tx chain of its S + 1 symbols on the victim's windows and mask
+int stage_nb(rx_run &r)
+{
+    if (!r.nb) return WOFDM_OK;
+    const rx_call &c = r.c;
+    const rx_geom &g = r.g;
+    geom gl{};
+    gl.L = g.L;
+    const std::vector<float2> hpi = pack_taps(c.cfg, gl, c.nb.h ? c.nb.h : c.h);
+    const int rc = r.nbtx.stage(g, g.S + 1, r.chunk, r.nb_act, c.tx_mask != nullptr, " (neighbour)");
+    if (rc != WOFDM_OK) return rc;
+    if (!r.d_hi.alloc(hpi.size())) return fail(WOFDM_E_NOMEM, "device allocation failed (neighbour)");
+    if (!r.d_hi.upload(hpi.data(), hpi.size())) return fail(WOFDM_E_HIP, "upload failed");
+    r.ck.nb = r.nbtx.params(c.cfg, g, g.S + 1, (uint32_t)g.cpp, r.sh);
+    r.ck.nb.stream = WOFDM_STREAM_ACI;
+    wofdm_aparams &a = r.ck.a;
+    a.xi = r.nbtx.x; a.hi = r.d_hi; a.Ti = g.T + g.B; a.ioff = g.B - c.nb.delay;
+    a.a_lvl = (float)std::pow(10.0, 0.05 * (double)c.nb.level_db);
+    r.ck.nb_on = true;
+    return WOFDM_OK;
+}
+
+template <typename T> bool fetch(std::vector<T> &host, const T *dev)
+{
+    return host.empty() || hipMemcpy(host.data(), dev, host.size() * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
+}
+template <typename T, typename U> void add_to(T *out, const std::vector<U> &host)
+{
+    for (size_t i = 0; out && i < host.size(); ++i) out[i] += host[i];
+}
+
+// The eight receive profiles.  Every argument is checked before the first HIP call -- the NULL arguments and the stages' counts,
+// the geometry, the finiteness, then the stages' points: sync, pn, doppler, link, amplifier --; the caller's arrays are written
+// only after everything has succeeded.
+int rx_profile_run(const rx_call &c)
+{
+    int rc = check_rx_args(c);
+    if (rc != WOFDM_OK) return rc;
+    rx_run r{c};
+    if ((rc = check_rx_geometry(c, &r.g)) != WOFDM_OK || (rc = check_rx_finite(c, r.g)) != WOFDM_OK ||
+        (rc = check_allocation(c.active, r.g.N, &r.act)) != WOFDM_OK || (rc = prep_nb(r)) != WOFDM_OK ||
+        (rc = prep_sync(r)) != WOFDM_OK || (rc = prep_pn(r)) != WOFDM_OK || (rc = check_knots(r)) != WOFDM_OK ||
+        (rc = prep_link(r)) != WOFDM_OK || (rc = prep_amp(r)) != WOFDM_OK || (rc = use_device(c.device)) != WOFDM_OK)
+        return rc;
+    g_rxprof_ms = 0.f;
+    const rx_geom &g = r.g;
+    const uint64_t items = g.cells * g.frames;
+    if (items == 0) return WOFDM_OK;
+    r.chunk = (size_t)chunk_frames(items, WOFDM_RX_PROFILE_CHUNK_BYTES, rx_job_bytes(r));
+    pack_channel(r);
+    const size_t NP = (size_t)c.n_points, NSC = c.soft.on ? (size_t)c.soft.n_scales : 0;
+    r.n_out = NP * g.cells * g.N;
+    r.n_sym = c.per_symbol ? NP * g.cells * (g.S - 1) : 0;
+    r.n_ptot = c.amp.on ? NP * g.cells * 2 : 0;
+    r.n_bpen = NP * g.cells * NSC * g.N;
+    r.n_spen = NP * g.cells * NSC * (g.S - 1);
+    if ((rc = stage_base(r)) != WOFDM_OK || (rc = stage_points(r)) != WOFDM_OK || (rc = stage_amp(r)) != WOFDM_OK ||
+        (rc = stage_pn(r)) != WOFDM_OK || (rc = stage_link(r)) != WOFDM_OK || (rc = stage_soft(r)) != WOFDM_OK ||
+        (rc = stage_nb(r)) != WOFDM_OK)
+        return rc;
+    // (a neighbour that loads no bin: the plain kernel)
+    r.ck.arm = c.arm == RXP_ACI && !r.nb ? RXP_PLAIN : c.arm;
+    std::vector<unsigned long long> herr(2 * r.n_out), hserr(2 * r.n_sym);
+    std::vector<double> hpow(r.n_out), hspow(r.n_sym), hptot(r.n_ptot), hbpen(r.n_bpen), hspen(r.n_spen);
     float ms = 0.f;
     hipError_t e = hipSuccess;
-    {
-        // (no frame kernel of this process beside these kernels: the gate of launch() is held until they have finished)
-        std::lock_guard<std::mutex> gate(g_gate_mu);
-        (void)hipDeviceSynchronize();
-        const wofdm_aux_fns *ax = wofdm_aux(N);
-        const wofdm_pa_fns *axp = wofdm_aux_pa(N);
-        const wofdm_link_fns *axl = wofdm_aux_link(N);
-        e = ax && axp && axl ? hipEventRecord(ev[0], nullptr) : hipErrorInvalidValue;
-        for (uint64_t i0 = 0; e == hipSuccess && i0 < items; i0 += chunk) {
-            pp.item0 = rp.item0 = i0;
-            pp.n_jobs = rp.n_jobs = (int32_t)std::min<uint64_t>(chunk, items - i0);
-            pa.item0 = pp.item0;
-            pa.n_jobs = pp.n_jobs;
-            e = soft ? axl->rx_profile_soft(&pp, nb ? &pa : nullptr, &rp, &apar, &spar, &dpar, &papar, &pnpar, &lkpar, &sopar, NTR + 1, max_theta, nullptr)
-                : link ? axl->rx_profile_link(&pp, nb ? &pa : nullptr, &rp, &apar, &spar, &dpar, &papar, &pnpar, &lkpar, NTR + 1, max_theta, nullptr)
-                : amp ? axp->rx_profile_pa(&pp, &rp, &spar, &papar, nullptr)
-                : dop ? ax->rx_profile_doppler(&pp, &rp, &spar, &dpar, nullptr)
-                : sync ? ax->rx_profile_sync(&pp, &rp, &spar, nullptr)
-                : pn ? ax->rx_profile_pn(&pp, &rp, &spar, &pnpar, nullptr)
-                     : (nb ? ax->rx_profile_aci(&pp, &pa, &rp, &apar, nullptr) : ax->rx_profile(&pp, &rp, nullptr));
-        }
-        if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    }
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
-    if (e != hipSuccess || hipMemcpy(herr.data(), d_errs, 2 * n_out * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(hpow.data(), d_pow, n_out * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-        (n_sym && (hipMemcpy(hserr.data(), d_serrs, 2 * n_sym * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                   hipMemcpy(hspow.data(), d_stot, n_sym * 8, hipMemcpyDeviceToHost) != hipSuccess)) ||
-        (n_ptot && hipMemcpy(hptot.data(), d_ptot, n_ptot * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (n_bpen && (hipMemcpy(hbpen.data(), d_btot, n_bpen * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                    hipMemcpy(hspen.data(), d_sptot, n_spen * 8, hipMemcpyDeviceToHost) != hipSuccess)))
+    const wofdm_link_fns *ax = wofdm_aux_link(g.N);
+    rc = run_chunks(items, r.chunk, [&](uint64_t item0, int32_t n_jobs) {
+        r.ck.tx.item0 = r.ck.nb.item0 = r.ck.r.item0 = item0;
+        r.ck.tx.n_jobs = r.ck.nb.n_jobs = r.ck.r.n_jobs = n_jobs;
+        return ax ? ax->rx_profile_chunk(&r.ck, nullptr) : hipErrorInvalidValue;
+    }, &e, &ms);
+    if (rc != WOFDM_OK) return rc;
+    if (e != hipSuccess || !fetch(herr, r.d_errs.p) || !fetch(hpow, r.d_pow.p) || !fetch(hserr, r.d_serrs.p) || !fetch(hspow, r.d_stot.p) ||
+        !fetch(hptot, r.d_ptot.p) || !fetch(hbpen, r.d_btot.p) || !fetch(hspen, r.d_sptot.p))
         return fail(WOFDM_E_HIP, "receive-profile kernels or copy-back failed: %s",
                     hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
-    for (size_t i = 0; i < 2 * n_out; ++i) errs[i] += herr[i];
-    if (err_power)
-        for (size_t i = 0; i < n_out; ++i) err_power[i] += hpow[i];
-    uint64_t *sym_errs = sync ? sync->sym_errs : (dop ? dop->sym_errs : (amp ? amp->sym_errs : (pn ? pn->sym_errs : nullptr)));
-    double *sym_power = sync ? sync->sym_power : (dop ? dop->sym_power : (amp ? amp->sym_power : (pn ? pn->sym_power : nullptr)));
-    if (sym_errs)
-        for (size_t i = 0; i < 2 * n_sym; ++i) sym_errs[i] += hserr[i];
-    if (sym_power)
-        for (size_t i = 0; i < n_sym; ++i) sym_power[i] += hspow[i];
-    if (amp && amp->pa_power)
-        for (size_t i = 0; i < n_ptot; ++i) amp->pa_power[i] += hptot[i];
-    if (soft) {
-        for (size_t i = 0; i < n_bpen; ++i) soft->bit_penalty[i] += hbpen[i];
-        if (soft->sym_penalty)
-            for (size_t i = 0; i < n_spen; ++i) soft->sym_penalty[i] += hspen[i];
-    }
+    add_to(c.errs, herr);
+    add_to(c.err_power, hpow);
+    add_to(c.sym_errs, hserr);
+    add_to(c.sym_power, hspow);
+    add_to(c.amp.pa_power, hptot);
+    add_to(c.soft.bit_penalty, hbpen);
+    add_to(c.soft.sym_penalty, hspen);
     g_rxprof_ms = ms;
+    return WOFDM_OK;
+}
+
+// what every call has; the arm and the stages are the entry point's to add
+rx_call rx_base(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                const uint8_t *active, const float *tx_mask)
+{
+    rx_call c{};
+    c.cfg = cfg; c.device = device; c.w_tx = w_tx; c.w_rx = w_rx; c.h = h; c.snr_db = snr_db; c.active = active; c.tx_mask = tx_mask;
+    c.arm = RXP_PLAIN; c.n_points = 1;
+    return c;
+}
+// an arm with a point loop: its points, and the outputs every call and every such arm has
+void rx_outputs(rx_call &c, int32_t arm, int32_t n_points, uint64_t *errs, double *err_power, uint64_t *sym_errs = nullptr,
+                double *sym_power = nullptr)
+{
+    c.arm = arm; c.n_points = n_points; c.per_symbol = arm != RXP_PLAIN && arm != RXP_ACI;
+    c.errs = errs; c.err_power = err_power; c.sym_errs = sym_errs; c.sym_power = sym_power;
+}
+
+// wofdm_rx_profile_link and wofdm_rx_profile_soft: the points switch the five stages, each of which takes what a point says to
+// it in its own arm's form, so that its own arm's code checks and prepares it
+int rx_link_stages(rx_call &c, int32_t n_points, const wofdm_link_point *points)
+{
+    if (!points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
+    if (n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", n_points);
+    if (n_points > WOFDM_LINK_MAX_POINTS) return fail(WOFDM_E_UNSUPPORTED, "n_points=%d exceeds %d", n_points, WOFDM_LINK_MAX_POINTS);
+    bool any_track = false, any_nb = false;
+    for (int i = 0; i < n_points; ++i) {
+        const wofdm_link_point &q = points[i];
+        c.link.as_sync.push_back({q.timing, q.cfo, q.cfo_tracked, 0});
+        c.link.as_pn.push_back({q.linewidth, q.cpe_tracked, {0, 0}});
+        c.link.as_pa.push_back({q.pa_model, q.pa_ibo_db, q.pa_smooth, 0});
+        any_track |= q.track >= 0;
+        any_nb |= q.aci_on != 0;
+    }
+    if (any_track && !c.dop.h_track) return fail(WOFDM_E_INVALID, "NULL argument (h_track, and a point names a track)");
+    if (any_nb && !c.nb.active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active, and a point has aci_on)");
+    c.link.on = true; c.link.points = points;
+    c.sync.on = c.amp.on = c.pn.on = true;
+    c.sync.points = c.link.as_sync.data(); c.pn.points = c.link.as_pn.data(); c.amp.points = c.link.as_pa.data();
+    // (the tracks and the neighbour are on where a point wants them; the static channel is behind the tracks either way, and
+    // a linear point needs no reference power)
+    c.dop.on = any_track; c.dop.static_track = true; c.nb.on = any_nb; c.amp.ref_optional = true;
     return WOFDM_OK;
 }
 
@@ -2066,31 +2234,39 @@ extern "C" {
 int wofdm_rx_profile(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                      const float *snr_db, const uint8_t *active, const float *tx_mask, uint64_t *errs, double *err_power)
 {
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
+    rx_call c = rx_base(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask);
+    rx_outputs(c, RXP_PLAIN, 1, errs, err_power);
+    return rx_profile_run(c);
 }
 
 int wofdm_rx_profile_aci(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                          const float *snr_db, const uint8_t *active, const float *tx_mask, const uint8_t *aci_active,
                          const float *aci_h, int32_t aci_delay, float aci_level_db, uint64_t *errs, double *err_power)
 {
-    const aci_args aci = {aci_active, aci_h, aci_delay, aci_level_db};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, &aci, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
+    rx_call c = rx_base(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask);
+    rx_outputs(c, RXP_ACI, 1, errs, err_power);
+    c.nb = {true, aci_active, aci_h, aci_delay, aci_level_db};
+    return rx_profile_run(c);
 }
 
 int wofdm_rx_profile_sync(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
                           const float *snr_db, const uint8_t *active, const float *tx_mask, int32_t n_points,
                           const wofdm_sync_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
-    const sync_args sync = {n_points, points, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, &sync, nullptr, nullptr, nullptr, nullptr, nullptr, errs, err_power);
+    rx_call c = rx_base(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask);
+    rx_outputs(c, RXP_SYNC, n_points, errs, err_power, sym_errs, sym_power);
+    c.sync = {true, points};
+    return rx_profile_run(c);
 }
 
 int wofdm_rx_profile_doppler(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h_track,
                              int32_t n_tracks, int32_t n_knots, int32_t knot_step, const float *snr_db, const uint8_t *active,
                              const float *tx_mask, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power)
 {
-    const doppler_args dop = {h_track, n_tracks, n_knots, knot_step, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask, nullptr, nullptr, &dop, nullptr, nullptr, nullptr, nullptr, errs, err_power);
+    rx_call c = rx_base(cfg, device, w_tx, w_rx, nullptr, snr_db, active, tx_mask);
+    rx_outputs(c, RXP_DOPPLER, n_tracks, errs, err_power, sym_errs, sym_power);
+    c.dop = {true, false, h_track, n_tracks, n_knots, knot_step};
+    return rx_profile_run(c);
 }
 
 int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
@@ -2098,51 +2274,20 @@ int wofdm_rx_profile_pa(const wofdm_cfg *cfg, int device, const float *w_tx, con
                         const float *ref_power, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power,
                         double *pa_power)
 {
-    const pa_args amp = {n_points, points, ref_power, sym_errs, sym_power, pa_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, &amp, nullptr, nullptr, nullptr, errs, err_power);
+    rx_call c = rx_base(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask);
+    rx_outputs(c, RXP_PA, n_points, errs, err_power, sym_errs, sym_power);
+    c.amp = {true, false, points, ref_power, pa_power};
+    return rx_profile_run(c);
 }
 
 int wofdm_rx_profile_pn(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
                         const uint8_t *active, const float *tx_mask, int32_t n_points, const wofdm_pn_point *points, uint64_t *errs,
                         double *err_power, uint64_t *sym_errs, double *sym_power)
 {
-    const pn_args pn = {n_points, points, sym_errs, sym_power};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, nullptr, nullptr, nullptr, nullptr, &pn, nullptr, nullptr, errs, err_power);
-}
-
-// wofdm_rx_profile_link and (soft) wofdm_rx_profile_soft
-static int rx_profile_link_impl(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
-                                const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
-                                int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power,
-                                int32_t n_points, const wofdm_link_point *points, const soft_args *soft, uint64_t *errs,
-                                double *err_power, uint64_t *sym_errs, double *sym_power, double *pa_power)
-{
-    if (!points) return fail(WOFDM_E_INVALID, "NULL argument (points)");
-    if (n_points < 1) return fail(WOFDM_E_INVALID, "n_points=%d must be >= 1", n_points);
-    if (n_points > WOFDM_LINK_MAX_POINTS) return fail(WOFDM_E_UNSUPPORTED, "n_points=%d exceeds %d", n_points, WOFDM_LINK_MAX_POINTS);
-    // every stage's points in the form its own arm takes them, so that its own arm's code checks and prepares them
-    std::vector<wofdm_sync_point> spts((size_t)n_points);
-    std::vector<wofdm_pn_point> npts((size_t)n_points);
-    std::vector<wofdm_pa_point> apts((size_t)n_points);
-    bool any_track = false, any_nb = false;
-    for (int i = 0; i < n_points; ++i) {
-        const wofdm_link_point &q = points[i];
-        spts[(size_t)i] = {q.timing, q.cfo, q.cfo_tracked, 0};
-        npts[(size_t)i] = {q.linewidth, q.cpe_tracked, {0, 0}};
-        apts[(size_t)i] = {q.pa_model, q.pa_ibo_db, q.pa_smooth, 0};
-        any_track |= q.track >= 0;
-        any_nb |= q.aci_on != 0;
-    }
-    if (any_track && !h_track) return fail(WOFDM_E_INVALID, "NULL argument (h_track, and a point names a track)");
-    if (any_nb && !aci_active) return fail(WOFDM_E_INVALID, "NULL argument (aci_active, and a point has aci_on)");
-    const aci_args aci = {aci_active, aci_h, 0, 0.f};
-    const sync_args sync = {n_points, spts.data(), sym_errs, sym_power};
-    const doppler_args dop = {h_track, n_tracks, n_knots, knot_step, nullptr, nullptr};
-    const pa_args amp = {n_points, apts.data(), ref_power, nullptr, nullptr, pa_power};
-    const pn_args pn = {n_points, npts.data(), nullptr, nullptr};
-    const link_args link = {n_points, points};
-    return rx_profile_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, any_nb ? &aci : nullptr, &sync, any_track ? &dop : nullptr,
-                           &amp, &pn, &link, soft, errs, err_power);
+    rx_call c = rx_base(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask);
+    rx_outputs(c, RXP_PN, n_points, errs, err_power, sym_errs, sym_power);
+    c.pn = {true, points};
+    return rx_profile_run(c);
 }
 
 int wofdm_rx_profile_link(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
@@ -2151,8 +2296,13 @@ int wofdm_rx_profile_link(const wofdm_cfg *cfg, int device, const float *w_tx, c
                           const wofdm_link_point *points, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power,
                           double *pa_power)
 {
-    return rx_profile_link_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active,
-                                aci_h, ref_power, n_points, points, nullptr, errs, err_power, sym_errs, sym_power, pa_power);
+    rx_call c = rx_base(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask);
+    rx_outputs(c, RXP_LINK, n_points, errs, err_power, sym_errs, sym_power);
+    c.dop = {false, false, h_track, n_tracks, n_knots, knot_step};
+    c.nb = {false, aci_active, aci_h, 0, 0.f};
+    c.amp = {false, false, nullptr, ref_power, pa_power};
+    const int rc = rx_link_stages(c, n_points, points);
+    return rc != WOFDM_OK ? rc : rx_profile_run(c);
 }
 
 int wofdm_rx_profile_soft(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
@@ -2167,9 +2317,14 @@ int wofdm_rx_profile_soft(const wofdm_cfg *cfg, int device, const float *w_tx, c
     for (int j = 0; j < n_scales; ++j)
         if (!std::isfinite(scales[j]) || !(scales[j] > 0.f))
             return fail(WOFDM_E_INVALID, "scales[%d] must be finite and positive", j);
-    const soft_args soft = {n_scales, scales, bit_penalty, sym_penalty};
-    return rx_profile_link_impl(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active,
-                                aci_h, ref_power, n_points, points, &soft, errs, err_power, sym_errs, sym_power, pa_power);
+    rx_call c = rx_base(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask);
+    rx_outputs(c, RXP_LINK, n_points, errs, err_power, sym_errs, sym_power);
+    c.dop = {false, false, h_track, n_tracks, n_knots, knot_step};
+    c.nb = {false, aci_active, aci_h, 0, 0.f};
+    c.amp = {false, false, nullptr, ref_power, pa_power};
+    c.soft = {true, n_scales, scales, bit_penalty, sym_penalty};
+    const int rc = rx_link_stages(c, n_points, points);
+    return rc != WOFDM_OK ? rc : rx_profile_run(c);
 }
 
 int wofdm_rx_profile_kernel_ms(float *ms)

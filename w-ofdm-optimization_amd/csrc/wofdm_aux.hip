@@ -1365,7 +1365,6 @@ __device__ __forceinline__ void soft_symbol(const wofdm_rparams &p, const wofdm_
 // s >= 1 leaves beside them the symbol's sums over the loaded bins -- a lane's bins ascending, then papr_wave_reduce -- in
 // sym_pow, sym_cnt [job][point][S].  The pilot of a point sees what the point's data sees.  Where pass 1 runs per point, Ps
 // is the point's; Pn depends on neither channel nor waveform and is measured with the first.
-enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
 template <int N, int ARM, bool SOFT = false>
 __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_aparams &ap, const wofdm_sparams &sp,
                                             const wofdm_dparams &dp, const wofdm_paparams &pa, const wofdm_pnparams &pn,
@@ -2192,7 +2191,8 @@ hipError_t papr_launch(const wofdm_pparams *pp, hipStream_t s)
     return hipGetLastError();
 }
 
-// What the seven receive-profile launchers share.  The chunk of r is the chunk of pp's Tx chain, within the receive kernel's geometry:
+// What the chunk of a receive profile (wofdm_rxchunk) has to satisfy, stage by stage.  The chunk of r is the chunk of pp's Tx
+// chain, within the receive kernel's geometry:
 bool rxprof_args_ok(const wofdm_pparams *pp, const wofdm_rparams &r)
 {
     constexpr int N = WOFDM_TU_N;
@@ -2212,6 +2212,41 @@ unsigned rxprof_cells(const wofdm_rparams &r, uint64_t &cell0)
     cell0 = r.item0 / r.frames;
     return (unsigned)((r.item0 + (uint64_t)r.n_jobs - 1) / r.frames - cell0 + 1);
 }
+// the neighbour: the victim's chunk and frame geometry with S + 1 symbols, tables and buffers of its own; own_offset: the offset
+// is the call's (wofdm_rx_profile_aci), not the points'
+bool rxprof_nb_ok(const wofdm_rxchunk &c, bool own_offset)
+{
+    const wofdm_pparams &p = c.tx, &nb = c.nb;
+    const wofdm_rparams &r = c.r;
+    const wofdm_aparams &a = c.a;
+    return !(nb.n_jobs != p.n_jobs || nb.item0 != p.item0 || nb.frames != p.frames || nb.frame_offset != p.frame_offset ||
+             nb.S != r.S + 1 || nb.P != p.P || nb.beta != p.beta || nb.cp != p.cp || nb.cs != p.cs || nb.wdiv != p.wdiv ||
+             a.Ti != r.T + r.B || (own_offset && (a.ioff < 1 || a.ioff > r.B)) || a.xi != nb.x || a.hi == nullptr || nb.X == p.X ||
+             nb.x == p.x || nb.jobs == p.jobs);
+}
+// the knots fit the LDS image and cover every sample either pass takes a tap at -- late: a window max_theta samples late reaches
+// further, by less than a stride --; the indices stay exact in single precision
+bool rxprof_knots_ok(const wofdm_dparams &dp, const wofdm_rparams &r, bool late, int max_theta)
+{
+    return !(dp.knots == nullptr || dp.n_knots < 2 || dp.n_knots > WOFDM_DOPPLER_KNOTS || dp.knot_step < 1 ||
+             r.T + (late ? r.B : 0) + WOFDM_LT >= (1 << 22) ||
+             (int64_t)(dp.n_knots - 1) * dp.knot_step < (int64_t)(r.NL > r.T ? r.NL : r.T) - 1 + max_theta);
+}
+// the amplifier: a point of its own per point of sp, and a saturation table that covers the pair of every cell of the chunk
+bool rxprof_pa_ok(const wofdm_rxchunk &c)
+{
+    const wofdm_paparams &pa = c.pa;
+    uint64_t cell0;
+    const unsigned n_cells = rxprof_cells(c.r, cell0);
+    return !(pa.n_points != c.sp.n_points || pa.pairs < 1 || pa.pts == nullptr || pa.asat == nullptr || pa.y == nullptr ||
+             pa.pwr == nullptr || pa.pwr_tot == nullptr || c.r.x != c.tx.x || (cell0 + n_cells - 1) / c.tx.wdiv >= (uint64_t)pa.pairs);
+}
+// the demapper: its scales and scratch
+bool rxprof_soft_ok(const wofdm_softparams &so)
+{
+    return !(so.n_scales < 1 || so.n_scales > WOFDM_SOFT_SCALES || so.w2 == nullptr || so.bit_part == nullptr ||
+             so.sym_part == nullptr || so.bit_tot == nullptr || so.sym_tot == nullptr);
+}
 // the ordered sums of the chunk onto the totals: per point of sp, or (null) the plain ones
 void rxprof_reduce_launch(const wofdm_rparams &r, const wofdm_sparams *sp, hipStream_t s)
 {
@@ -2225,253 +2260,98 @@ void rxprof_reduce_launch(const wofdm_rparams &r, const wofdm_sparams *sp, hipSt
                            *sp, cell0);
 }
 
-// wofdm_rx_profile, one chunk: the Tx chain of the chunk's (cell, frame) items, their receive profiles, and the ordered sums
-hipError_t rx_profile_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, hipStream_t s)
+// One chunk of a receive profile, whichever of the eight entry points it belongs to (wofdm_link.h): the stages the arm switches
+// on are checked, then enqueued in the one order there is -- the Tx chain of the chunk's (cell, frame) items; the neighbour's;
+// the points' amplified waveforms and power sums; the items' unit phase walks; the arm's receive kernel; the ordered sums
+// (per point where the arm has points); the amplifier's power sums in frame order; the demapper's ordered sums behind the others.
+hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
 {
     constexpr int N = WOFDM_TU_N;
-    const wofdm_rparams &r = *rp;
-    if (!rxprof_args_ok(pp, r)) return hipErrorInvalidValue;
-    hipError_t e = tx_chain_launch(*pp, s);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                rxp_geo<N>::LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_rxprof_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r);
-    rxprof_reduce_launch(r, nullptr, s);
-    return hipGetLastError();
-}
-
-// wofdm_rx_profile_aci, one chunk: the victim's Tx chain, the neighbour's (S + 1 symbols, its own stream, allocation, tables
-// and buffers), the receive kernel's ACI arm, and the ordered sums
-hipError_t rx_profile_aci_launch(const wofdm_pparams *pp, const wofdm_pparams *pa, const wofdm_rparams *rp,
-                                 const wofdm_aparams *app, hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N;
-    const wofdm_rparams &r = *rp;
-    const wofdm_aparams &a = *app;
-    if (!rxprof_args_ok(pp, r)) return hipErrorInvalidValue;
-    if (pa->n_jobs != pp->n_jobs || pa->item0 != pp->item0 || pa->frames != pp->frames || pa->frame_offset != pp->frame_offset ||
-        pa->S != r.S + 1 || pa->P != pp->P || pa->beta != pp->beta || pa->cp != pp->cp || pa->cs != pp->cs || pa->wdiv != pp->wdiv ||
-        a.Ti != r.T + r.B || a.ioff < 1 || a.ioff > r.B || a.xi != pa->x || a.hi == nullptr || pa->X == pp->X || pa->x == pp->x ||
-        pa->jobs == pp->jobs)
-        return hipErrorInvalidValue;
-    hipError_t e = tx_chain_launch(*pp, s);
-    if (e == hipSuccess) e = tx_chain_launch(*pa, s);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_aci_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                rxp_geo<N>::LDS_ACI);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_rxprof_aci_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_ACI, s, r, a);
-    rxprof_reduce_launch(r, nullptr, s);
-    return hipGetLastError();
-}
-
-// wofdm_rx_profile_sync, one chunk: the Tx chain once, the receive kernel over the points, and the ordered sums per point
-hipError_t rx_profile_sync_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, const wofdm_sparams *spp, hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N;
-    const wofdm_rparams &r = *rp;
-    const wofdm_sparams &sp = *spp;
-    if (!rxprof_args_ok(pp, r) || !rxprof_points_ok(sp, r, WOFDM_SYNC_POINTS) || sp.pts == nullptr || sp.base == nullptr)
-        return hipErrorInvalidValue;
-    hipError_t e = tx_chain_launch(*pp, s);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_sync_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                rxp_geo<N>::LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_rxprof_sync_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r, sp);
-    rxprof_reduce_launch(r, &sp, s);
-    return hipGetLastError();
-}
-
-// wofdm_rx_profile_doppler, one chunk: the Tx chain once, the receive kernel over the tracks, and rx_profile_sync's ordered sums
-// with the tracks as its points
-hipError_t rx_profile_doppler_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, const wofdm_sparams *spp,
-                                     const wofdm_dparams *dpp, hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N;
-    const wofdm_rparams &r = *rp;
-    const wofdm_sparams &sp = *spp;
-    const wofdm_dparams &dp = *dpp;
-    if (!rxprof_args_ok(pp, r) || !rxprof_points_ok(sp, r, WOFDM_DOPPLER_TRACKS)) return hipErrorInvalidValue;
-    // the knots fit the LDS image and cover every sample either pass takes a tap at; the indices stay exact in single precision
-    if (dp.knots == nullptr || dp.n_knots < 2 || dp.n_knots > WOFDM_DOPPLER_KNOTS || dp.knot_step < 1 || r.T + WOFDM_LT >= (1 << 22) ||
-        (int64_t)(dp.n_knots - 1) * dp.knot_step < (int64_t)(r.NL > r.T ? r.NL : r.T) - 1)
-        return hipErrorInvalidValue;
-    hipError_t e = tx_chain_launch(*pp, s);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_doppler_kernel<N>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, rxp_geo<N>::LDS_DOP);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_rxprof_doppler_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_DOP, s, r,
-                       sp, dp);
-    rxprof_reduce_launch(r, &sp, s);
-    return hipGetLastError();
-}
-
-// wofdm_rx_profile_pa, one chunk: the Tx chain once, the points' amplified waveforms and power sums, the receive kernel over
-// the points, rx_profile_sync's ordered sums with the points as its points, and the power sums in frame order
-hipError_t rx_profile_pa_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, const wofdm_sparams *spp, const wofdm_paparams *pap,
-                                hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N;
-    const wofdm_rparams &r = *rp;
-    const wofdm_sparams &sp = *spp;
-    const wofdm_paparams &pa = *pap;
-    if (!rxprof_args_ok(pp, r) || !rxprof_points_ok(sp, r, WOFDM_PA_POINTS)) return hipErrorInvalidValue;
-    uint64_t cell0;
-    const unsigned n_cells = rxprof_cells(r, cell0);
-    // the saturation table covers the pair of every cell of the chunk
-    if (pa.n_points != sp.n_points || pa.pairs < 1 || pa.pts == nullptr || pa.asat == nullptr || pa.y == nullptr || pa.pwr == nullptr ||
-        pa.pwr_tot == nullptr || r.x != pp->x || (cell0 + n_cells - 1) / pp->wdiv >= (uint64_t)pa.pairs)
-        return hipErrorInvalidValue;
-    hipError_t e = tx_chain_launch(*pp, s);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_pa_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                rxp_geo<N>::LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_pa_wave_kernel, dim3((unsigned)r.n_jobs, (unsigned)pa.n_points), dim3(256), 0, s, pa, r.x, r.T, r.item0,
-                       r.frames, pp->wdiv);
-    hipLaunchKernelGGL(wofdm_rxprof_pa_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r, sp, pa);
-    rxprof_reduce_launch(r, &sp, s);
-    hipLaunchKernelGGL(wofdm_pa_power_reduce_kernel, dim3(n_cells), dim3(64), 0, s, pa, r.item0, r.n_jobs, r.frames, sp.cells, cell0);
-    return hipGetLastError();
-}
-
-// wofdm_rx_profile_pn, one chunk: the Tx chain once, the items' unit phase walks, the receive kernel over the points, and
-// rx_profile_sync's ordered sums with the points as its points
-hipError_t rx_profile_pn_launch(const wofdm_pparams *pp, const wofdm_rparams *rp, const wofdm_sparams *spp, const wofdm_pnparams *pnp,
-                                hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N;
-    const wofdm_rparams &r = *rp;
-    const wofdm_sparams &sp = *spp;
-    const wofdm_pnparams &pn = *pnp;
-    // (rxprof_args_ok: B = N + delta + gam, so the last sample under the last window is the walk's last, index S B - 1)
-    if (!rxprof_args_ok(pp, r) || !rxprof_points_ok(sp, r, WOFDM_PN_POINTS) || pn.pts == nullptr || pn.walk == nullptr)
-        return hipErrorInvalidValue;
-    hipError_t e = tx_chain_launch(*pp, s);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_rxprof_pn_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                rxp_geo<N>::LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_pn_walk_kernel, dim3((unsigned)r.n_jobs), dim3(1024), 0, s, pn.walk, r.S * r.B, r.seed_lo, r.seed_hi, r.item0,
-                       r.frames, r.frame_offset);
-    hipLaunchKernelGGL(wofdm_rxprof_pn_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS, s, r, sp, pn);
-    rxprof_reduce_launch(r, &sp, s);
-    return hipGetLastError();
-}
-
-// wofdm_rx_profile_link, one chunk: the launchers above put together -- the Tx chain once, the neighbour's where a point wants it
-// (nbp), the points' waveforms and power sums, the items' unit walks, the receive body's link arm over the points,
-// rx_profile_sync's ordered sums and the amplifier's power sums
-// (sop: wofdm_rx_profile_soft -- the same chunk through wofdm_rxprof_soft_kernel, and its own ordered sums behind the others)
-hipError_t link_chunk_launch(const wofdm_pparams *pp, const wofdm_pparams *nbp, const wofdm_rparams *rp, const wofdm_aparams *app,
-                             const wofdm_sparams *spp, const wofdm_dparams *dpp, const wofdm_paparams *pap, const wofdm_pnparams *pnp,
-                             const wofdm_lparams *lkp, const wofdm_softparams *sop, int n_tracks, int max_theta, hipStream_t s)
-{
-    constexpr int N = WOFDM_TU_N;
-    const wofdm_rparams &r = *rp;
-    const wofdm_aparams &a = *app;
-    const wofdm_sparams &sp = *spp;
-    const wofdm_dparams &dp = *dpp;
-    const wofdm_paparams &pa = *pap;
-    const wofdm_pnparams &pn = *pnp;
-    const wofdm_lparams &lk = *lkp;
-    if (!rxprof_args_ok(pp, r) || !rxprof_points_ok(sp, r, WOFDM_LINK_POINTS) || sp.pts == nullptr || sp.base == nullptr ||
-        pn.pts == nullptr || pn.walk == nullptr || lk.pts == nullptr || n_tracks < 1 || max_theta < 0 || max_theta >= r.B)
-        return hipErrorInvalidValue;
-    // the knots: rx_profile_doppler's conditions, and the samples a late window reaches
-    if (dp.knots == nullptr || dp.n_knots < 2 || dp.n_knots > WOFDM_DOPPLER_KNOTS || dp.knot_step < 1 ||
-        r.T + r.B + WOFDM_LT >= (1 << 22) ||
-        (int64_t)(dp.n_knots - 1) * dp.knot_step < (int64_t)(r.NL > r.T ? r.NL : r.T) - 1 + max_theta)
+    // the most points an arm's kernel takes (the arms without a point loop: none)
+    constexpr int MAX_POINTS[] = {0, 0, WOFDM_SYNC_POINTS, WOFDM_DOPPLER_TRACKS, WOFDM_PA_POINTS, WOFDM_PN_POINTS, WOFDM_LINK_POINTS};
+    const wofdm_rxchunk &c = *cp;
+    const wofdm_rparams &r = c.r;
+    if (c.arm < RXP_PLAIN || c.arm > RXP_LINK) return hipErrorInvalidValue;
+    const bool link = c.arm == RXP_LINK, points = MAX_POINTS[c.arm] > 0;
+    const bool nb = c.arm == RXP_ACI || (link && c.nb_on), sync = c.arm == RXP_SYNC || link, knots = c.arm == RXP_DOPPLER || link;
+    const bool amp = c.arm == RXP_PA || link, walk = c.arm == RXP_PN || link, soft = link && c.soft_on;
+    if (nb != c.nb_on || soft != c.soft_on || !rxprof_args_ok(&c.tx, r) || (points && !rxprof_points_ok(c.sp, r, MAX_POINTS[c.arm])) ||
+        (nb && !rxprof_nb_ok(c, !link)) || (sync && (c.sp.pts == nullptr || c.sp.base == nullptr)) ||
+        (knots && !rxprof_knots_ok(c.dp, r, link, link ? c.max_theta : 0)) || (amp && !rxprof_pa_ok(c)) ||
+        // (rxprof_args_ok: B = N + delta + gam, so the last sample under the last window is the walk's last, index S B - 1)
+        (walk && (c.pn.pts == nullptr || c.pn.walk == nullptr)) ||
+        (link && (c.lk.pts == nullptr || c.n_tracks < 1 || c.max_theta < 0 || c.max_theta >= r.B)) || (soft && !rxprof_soft_ok(c.soft)))
         return hipErrorInvalidValue;
     uint64_t cell0;
     const unsigned n_cells = rxprof_cells(r, cell0);
-    // the amplifier: rx_profile_pa's conditions
-    if (pa.n_points != sp.n_points || pa.pairs < 1 || pa.pts == nullptr || pa.asat == nullptr || pa.y == nullptr || pa.pwr == nullptr ||
-        pa.pwr_tot == nullptr || r.x != pp->x || (cell0 + n_cells - 1) / pp->wdiv >= (uint64_t)pa.pairs)
-        return hipErrorInvalidValue;
-    // the neighbour: rx_profile_aci's conditions but for the offset, which is the points'
-    if (nbp != nullptr &&
-        (nbp->n_jobs != pp->n_jobs || nbp->item0 != pp->item0 || nbp->frames != pp->frames || nbp->frame_offset != pp->frame_offset ||
-         nbp->S != r.S + 1 || nbp->P != pp->P || nbp->beta != pp->beta || nbp->cp != pp->cp || nbp->cs != pp->cs ||
-         nbp->wdiv != pp->wdiv || a.Ti != r.T + r.B || a.xi != nbp->x || a.hi == nullptr || nbp->X == pp->X || nbp->x == pp->x ||
-         nbp->jobs == pp->jobs))
-        return hipErrorInvalidValue;
-    // the demapper: its scales and scratch
-    if (sop != nullptr && (sop->n_scales < 1 || sop->n_scales > WOFDM_SOFT_SCALES || sop->w2 == nullptr || sop->bit_part == nullptr ||
-                           sop->sym_part == nullptr || sop->bit_tot == nullptr || sop->sym_tot == nullptr))
-        return hipErrorInvalidValue;
-    hipError_t e = tx_chain_launch(*pp, s);
-    if (e == hipSuccess && nbp != nullptr) e = tx_chain_launch(*nbp, s);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(sop != nullptr ? reinterpret_cast<const void *>(wofdm_rxprof_soft_kernel<N>)
-                                               : reinterpret_cast<const void *>(wofdm_rxprof_link_kernel<N>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, rxp_geo<N>::LDS_LINK);
+    hipError_t e = tx_chain_launch(c.tx, s);
+    if (e == hipSuccess && nb) e = tx_chain_launch(c.nb, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wofdm_pa_wave_kernel, dim3((unsigned)r.n_jobs, (unsigned)pa.n_points), dim3(256), 0, s, pa, r.x, r.T, r.item0,
-                       r.frames, pp->wdiv);
-    hipLaunchKernelGGL(wofdm_pn_walk_kernel, dim3((unsigned)r.n_jobs), dim3(1024), 0, s, pn.walk, r.S * r.B, r.seed_lo, r.seed_hi, r.item0,
-                       r.frames, r.frame_offset);
-    if (sop != nullptr)
-        hipLaunchKernelGGL(wofdm_rxprof_soft_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_LINK, s, r,
-                           a, sp, dp, pa, pn, lk, *sop);
-    else
-        hipLaunchKernelGGL(wofdm_rxprof_link_kernel<N>, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), rxp_geo<N>::LDS_LINK, s, r,
-                           a, sp, dp, pa, pn, lk);
-    rxprof_reduce_launch(r, &sp, s);
-    hipLaunchKernelGGL(wofdm_pa_power_reduce_kernel, dim3(n_cells), dim3(64), 0, s, pa, r.item0, r.n_jobs, r.frames, sp.cells, cell0);
-    if (sop != nullptr) {
-        const size_t n_elems = (size_t)r.n_jobs * (size_t)sp.n_points * (size_t)sop->n_scales * N;
-        hipLaunchKernelGGL(wofdm_rxprof_soft_frame_kernel<N>, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, s, *sop, r.S, n_elems);
-        hipLaunchKernelGGL(wofdm_rxprof_soft_reduce_kernel<N>, dim3(N / 64 + 1, n_cells, (unsigned)(sp.n_points * sop->n_scales)),
-                           dim3(64), 0, s, r, sp, *sop, cell0);
+    // the arm's kernel with its LDS, behind what it reads: the points' waveforms, the walks
+    const auto receive = [&](auto kernel, int lds, const auto &...args) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return;
+        if (amp)
+            hipLaunchKernelGGL(wofdm_pa_wave_kernel, dim3((unsigned)r.n_jobs, (unsigned)c.pa.n_points), dim3(256), 0, s, c.pa, r.x, r.T,
+                               r.item0, r.frames, c.tx.wdiv);
+        if (walk)
+            hipLaunchKernelGGL(wofdm_pn_walk_kernel, dim3((unsigned)r.n_jobs), dim3(1024), 0, s, c.pn.walk, r.S * r.B, r.seed_lo, r.seed_hi,
+                               r.item0, r.frames, r.frame_offset);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)r.n_jobs), dim3(rxp_geo<N>::WAVES * 64), lds, s, r, args...);
+    };
+    switch (c.arm) {
+    case RXP_PLAIN: receive(wofdm_rxprof_kernel<N>, rxp_geo<N>::LDS); break;
+    case RXP_ACI: receive(wofdm_rxprof_aci_kernel<N>, rxp_geo<N>::LDS_ACI, c.a); break;
+    case RXP_SYNC: receive(wofdm_rxprof_sync_kernel<N>, rxp_geo<N>::LDS, c.sp); break;
+    case RXP_DOPPLER: receive(wofdm_rxprof_doppler_kernel<N>, rxp_geo<N>::LDS_DOP, c.sp, c.dp); break;
+    case RXP_PA: receive(wofdm_rxprof_pa_kernel<N>, rxp_geo<N>::LDS, c.sp, c.pa); break;
+    case RXP_PN: receive(wofdm_rxprof_pn_kernel<N>, rxp_geo<N>::LDS, c.sp, c.pn); break;
+    default:
+        if (soft)
+            receive(wofdm_rxprof_soft_kernel<N>, rxp_geo<N>::LDS_LINK, c.a, c.sp, c.dp, c.pa, c.pn, c.lk, c.soft);
+        else
+            receive(wofdm_rxprof_link_kernel<N>, rxp_geo<N>::LDS_LINK, c.a, c.sp, c.dp, c.pa, c.pn, c.lk);
+    }
+    if (e != hipSuccess) return e;
+    rxprof_reduce_launch(r, points ? &c.sp : nullptr, s);
+    if (amp)
+        hipLaunchKernelGGL(wofdm_pa_power_reduce_kernel, dim3(n_cells), dim3(64), 0, s, c.pa, r.item0, r.n_jobs, r.frames, c.sp.cells,
+                           cell0);
+    if (soft) {
+        const size_t n_elems = (size_t)r.n_jobs * (size_t)c.sp.n_points * (size_t)c.soft.n_scales * N;
+        hipLaunchKernelGGL(wofdm_rxprof_soft_frame_kernel<N>, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, s, c.soft, r.S,
+                           n_elems);
+        hipLaunchKernelGGL(wofdm_rxprof_soft_reduce_kernel<N>, dim3(N / 64 + 1, n_cells, (unsigned)(c.sp.n_points * c.soft.n_scales)),
+                           dim3(64), 0, s, r, c.sp, c.soft, cell0);
     }
     return hipGetLastError();
-}
-
-hipError_t rx_profile_link_launch(const wofdm_pparams *pp, const wofdm_pparams *nbp, const wofdm_rparams *rp, const wofdm_aparams *app,
-                                  const wofdm_sparams *spp, const wofdm_dparams *dpp, const wofdm_paparams *pap,
-                                  const wofdm_pnparams *pnp, const wofdm_lparams *lkp, int n_tracks, int max_theta, hipStream_t s)
-{
-    return link_chunk_launch(pp, nbp, rp, app, spp, dpp, pap, pnp, lkp, nullptr, n_tracks, max_theta, s);
-}
-
-// wofdm_rx_profile_soft, one chunk
-hipError_t rx_profile_soft_launch(const wofdm_pparams *pp, const wofdm_pparams *nbp, const wofdm_rparams *rp, const wofdm_aparams *app,
-                                  const wofdm_sparams *spp, const wofdm_dparams *dpp, const wofdm_paparams *pap,
-                                  const wofdm_pnparams *pnp, const wofdm_lparams *lkp, const wofdm_softparams *sop, int n_tracks,
-                                  int max_theta, hipStream_t s)
-{
-    if (sop == nullptr) return hipErrorInvalidValue;
-    return link_chunk_launch(pp, nbp, rp, app, spp, dpp, pap, pnp, lkp, sop, n_tracks, max_theta, s);
 }
 
 }  // namespace
 
 const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
 {
-    static const wofdm_pa_fns fns = {rx_profile_pa_launch, psd_batch_pa_launch};
+    static const wofdm_pa_fns fns = {psd_batch_pa_launch};
     return &fns;
 }
 
 const wofdm_link_fns *WOFDM_CAT(wofdm_aux_link_n, WOFDM_TU_N)(void)
 {
-    static const wofdm_link_fns fns = {rx_profile_link_launch, rx_profile_soft_launch};
+    static const wofdm_link_fns fns = {rx_profile_chunk};
     return &fns;
 }
 
+// The five rx_profile* members behind papr stay null and nothing reads them: every receive profile goes through
+// wofdm_link_fns::rx_profile_chunk.  Their declarations are in wofdm_kernel.h, a file of the frame kernels' source hash, and
+// leave with the next change that re-stamps profiles/hbm_traffic.json anyway.
 const wofdm_aux_fns *WOFDM_CAT(wofdm_aux_n, WOFDM_TU_N)(void)
 {
 #if WOFDM_TU_N <= 256
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, psd_launch, psd_batch_launch, psd_batch_masked_launch,
-                                      papr_launch, rx_profile_launch, rx_profile_aci_launch, rx_profile_sync_launch,
-                                      rx_profile_doppler_launch, rx_profile_pn_launch};
+                                      papr_launch};
 #else
     static const wofdm_aux_fns fns = {interf_launch, interf_masked_launch, nullptr, psd_batch_launch, psd_batch_masked_launch,
-                                      papr_launch, rx_profile_launch, rx_profile_aci_launch, rx_profile_sync_launch,
-                                      rx_profile_doppler_launch, rx_profile_pn_launch};
+                                      papr_launch};
 #endif
     return &fns;
 }

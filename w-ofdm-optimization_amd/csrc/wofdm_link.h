@@ -1,6 +1,6 @@
 // wofdm_link.h -- the five impairments combined (wofdm_rx_profile_link): the parameters of the receive body's seventh arm
-// (wofdm_aux.hip) and its launcher, one table per DFT length beside wofdm_aux_fns and wofdm_pa_fns; and the same arm with soft
-// decisions (wofdm_rx_profile_soft).  A header of its own:
+// (wofdm_aux.hip), and the same arm with soft decisions (wofdm_rx_profile_soft); the chunk of a receive-profile call and its
+// launcher, one table per DFT length beside wofdm_aux_fns and wofdm_pa_fns.  A header of its own:
 // wofdm_kernel.h is part of the frame kernels' source hash (profiles/hbm_traffic.json), and nothing here touches them
 // (GNUmakefile tells make which objects depend on this file, for the same reason).
 #pragma once
@@ -42,20 +42,34 @@ struct wofdm_softparams {
     double *sym_tot;                  // [n_points][cells][n_scales][S - 1], accumulated into
 };
 
+// The arms of the receive body (rxprof_body of wofdm_aux.hip, which says what each adds)
+enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
+
+// One chunk of a receive-profile call, whichever of the eight: the victim's Tx chain, the receive kernel's parameters, and the
+// stages' parameter structs as the kernels take them.  The arm says which stages the chunk runs -- a stage's struct is read
+// only where its arm or RXP_LINK is on --; the link arm runs every stage, its points switch them, and only its neighbour
+// (no point has aci_on: nb_on = false) and its demapper (wofdm_rx_profile_soft: soft_on) are the call's to leave out.
+struct wofdm_rxchunk {
+    int32_t arm;                      // RXP_*
+    bool nb_on, soft_on;              // RXP_ACI: nb_on is true
+    wofdm_pparams tx, nb;             // the victim's Tx chain; the neighbour's (S + 1 symbols, its own stream, allocation, buffers)
+    wofdm_rparams r;
+    wofdm_aparams a;                  // RXP_LINK: ioff and a_lvl are the points'
+    wofdm_sparams sp;
+    wofdm_dparams dp;
+    wofdm_paparams pa;
+    wofdm_pnparams pn;
+    wofdm_lparams lk;
+    wofdm_softparams soft;
+    int32_t n_tracks;                 // RXP_LINK: the tracks of dp's knots, the static one included
+    int32_t max_theta;                // RXP_LINK: the largest timing offset of the points, or 0 (the knots cover the samples it reaches)
+};
+
 struct wofdm_link_fns {
-    // wofdm_rx_profile_link, one chunk: the Tx chain once, the neighbour's (nb != null: a point has aci_on) once, the points'
-    // amplified waveforms and power sums, the items' unit walks, wofdm_rxprof_link_kernel (both passes once per point),
-    // rx_profile_sync's ordered sums and the power sums in frame order.  n_tracks: the tracks of dp's knots, the static one
-    // included; max_theta: the largest timing offset of the points, or 0 (the knots cover the samples it reaches).
-    hipError_t (*rx_profile_link)(const wofdm_pparams *p, const wofdm_pparams *nb, const wofdm_rparams *r, const wofdm_aparams *a,
-                                  const wofdm_sparams *sp, const wofdm_dparams *dp, const wofdm_paparams *pa,
-                                  const wofdm_pnparams *pn, const wofdm_lparams *lk, int n_tracks, int max_theta, hipStream_t s);
-    // wofdm_rx_profile_soft, one chunk: rx_profile_link with wofdm_rxprof_soft_kernel in the link kernel's place, and behind the
-    // ordered sums wofdm_rxprof_soft_reduce_kernel's
-    hipError_t (*rx_profile_soft)(const wofdm_pparams *p, const wofdm_pparams *nb, const wofdm_rparams *r, const wofdm_aparams *a,
-                                  const wofdm_sparams *sp, const wofdm_dparams *dp, const wofdm_paparams *pa,
-                                  const wofdm_pnparams *pn, const wofdm_lparams *lk, const wofdm_softparams *so, int n_tracks,
-                                  int max_theta, hipStream_t s);
+    // One chunk of any receive profile, on stream s: the Tx chain, the neighbour's, the amplifier's waveforms and power sums,
+    // the items' unit walks, the arm's receive kernel, the ordered sums (per point where the arm has points), the power sums in
+    // frame order, the demapper's ordered sums -- each where its stage is on, in this order.
+    hipError_t (*rx_profile_chunk)(const wofdm_rxchunk *c, hipStream_t s);
 };
 const wofdm_link_fns *wofdm_aux_link_n64(void);
 const wofdm_link_fns *wofdm_aux_link_n128(void);

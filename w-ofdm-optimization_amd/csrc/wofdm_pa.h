@@ -1,7 +1,8 @@
 // wofdm_pa.h -- the memoryless power amplifier behind the Tx chain (wofdm_rx_profile_pa, wofdm_tx_psd_batch_pa): the
-// parameters of its kernels (wofdm_aux.hip) and their launchers, one table per DFT length beside wofdm_aux_fns.  A header of
-// its own: wofdm_kernel.h is part of the frame kernels' source hash (profiles/hbm_traffic.json), and nothing here touches them
-// (GNUmakefile tells make which objects depend on this file, for the same reason).
+// parameters of its kernels (wofdm_aux.hip) and the PSD's launcher, one table per DFT length beside wofdm_aux_fns (the receive
+// profile's chunk is launched through wofdm_link.h).  A header of its own: wofdm_kernel.h is part of the frame kernels' source
+// hash (profiles/hbm_traffic.json), and nothing here touches them (GNUmakefile tells make which objects depend on this file,
+// for the same reason).
 #pragma once
 #include "wofdm_kernel.h"
 
@@ -39,10 +40,6 @@ struct wofdm_pajob {
 };
 
 struct wofdm_pa_fns {
-    // wofdm_rx_profile_pa, one chunk: the Tx chain once, the points' waveforms and power sums, wofdm_rxprof_pa_kernel (pass 1
-    // and pass 2 once per point), rx_profile_sync's ordered sums and the power sums' in frame order.
-    hipError_t (*rx_profile_pa)(const wofdm_pparams *p, const wofdm_rparams *r, const wofdm_sparams *sp, const wofdm_paparams *pa,
-                                hipStream_t s);
     // wofdm_tx_psd_batch_pa: psd_batch_masked of wofdm_aux_fns (n_masked = 0: every job in plain_jobs) with, between the
     // waveform kernels and the periodogram, the jobs' mean powers (power[n_jobs][2] = {sum |x|^2, sum |y|^2}, device) and the
     // amplifier on the jobs that have one.

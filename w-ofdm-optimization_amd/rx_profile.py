@@ -352,7 +352,7 @@ def _unit_noise_lookup(st, grids, unit_noise, n_taps, noise_before_truncate):
 
 
 def _chunk_frames(st, syms, masked, per_point=0, n_points=0, per_frame_extra=0, neighbour=False, extra_bytes=0):
-    """Frames one chunk holds: the byte budget of include/wofdm.h (``job_bytes`` of rx_profile_impl) over the bytes of a frame
+    """Frames one chunk holds: the byte budget of include/wofdm.h (``rx_job_bytes`` of wofdm_abi.hip) over the bytes of a frame
     -- 8 per element: the symbol grid [S, N], the waveform [T], masked the filtered symbols [S, 2P - 1]; with a neighbour
     its grid [S + 1, N], waveform [T + B] and filtered symbols; ``per_frame_extra`` elements of the arm's own; ``per_point``
     elements (the partial sums, a waveform) for each of ``n_points``; ``extra_bytes`` bytes that are no 8-byte elements --, at
