@@ -847,6 +847,80 @@ int wofdm_rx_profile_soft(const wofdm_cfg *cfg, int device,
                           double *bit_penalty,              /* [n_points][cells][n_scales][n_fft], ACCUMULATED into */
                           double *sym_penalty);             /* [n_points][cells][n_scales][S-1], or NULL */
 
+/* wofdm_rx_profile_soft behind a TRACKING receiver.  Every other receive profile equalises with the one least-squares estimate of
+ * symbol 0 and holds it for the frame, and the only relief on offer is a genie (cfo_tracked, cpe_tracked) no receiver has.
+ * This call gives the receiver two mechanisms of a real one: a comb of pilot subcarriers in every data symbol, from which it
+ * estimates the symbol's common phase, and a postamble, a second known symbol at the frame's end, between which and the pilot it
+ * interpolates the channel estimate.  Which window pair is best on a link that drifts is a question for this receiver: a window
+ * that rejects ICI and one that merely rotates less rank differently once the common rotation is estimated and removed.
+ *   Per call: pilots [n_fft], or NULL for no comb; a non-zero entry makes the bin a pilot bin.  Per link point one
+ * wofdm_tracking_point {cpe, post}: cpe = 1 switches on the comb's phase estimate, post = 1 makes symbol S - 1 a postamble.  The
+ * Tx side is untouched: a pilot bin carries the label the stream gives it, and the receiver knows it, as it already knows symbol
+ * 0; with post it also knows symbol S - 1.
+ *   Definition.  For a point, a frame and a data symbol s -- 1 <= s <= S - 1, with post 1 <= s <= S - 2 --, Y_s the link chain's
+ * DFT outputs, X_s the transmitted points and t = s / (S - 1):
+ *     H0[n]  = Y_0[n] / X_0[n] on the loaded bins; with post HL[n] = Y_{S-1}[n] / X_{S-1}[n];
+ *     Hh_s   = H0 without post.  With post cL = sum_{n loaded} HL[n] conj(H0[n]), rho = cL / |cL| (1 if cL = 0), and
+ *              Hh_s = H0 + t (HL conj(rho) - H0): the SHAPE is interpolated with the postamble's common rotation taken off, so a
+ *              free-running oscillator does not wreck the interpolation;
+ *     q_s    = with cpe: c_s / |c_s| (1 if c_s = 0), c_s = sum_{p in pilots} Y_s[p] conj(Hh_s[p] X_s[p]) -- the channel-weighted
+ *              estimate: a plain phase average over equalised pilots lets faded bins dominate --; with post and no cpe:
+ *              e^{i t arg rho}, arg the principal value, which is right while the drift over the frame stays under half a turn;
+ *              with neither: 1;
+ *     e      = Y_s[n] conj(q_s) / Hh_s[n], and nu_s[n] = v W2 / |Hh_s[n]|^2, v and W2 wofdm_rx_profile_soft's.
+ *   The slicer, the error vector and the demapper all see this one e, and everything behind it is wofdm_rx_profile_soft's.
+ *   Pilot bins count no decision, no error, no power and no penalty on ANY point of the call: they are exact zeros, as unloaded
+ * bins are; symbol S - 1 of a point with post likewise, per symbol and in the bins' sums.  A bin of point i so takes
+ * frames (S - 1 - post_i) decisions.
+ *   Order of additions: cL and c_s are formed by one wave, a lane's bins n = lane + 64 j ascending, then the wave sum of the
+ * per-symbol error power, on either component; everything else as wofdm_rx_profile_soft.  For a point with post the waves visit
+ * the symbols in the order 0, S - 1, 1, ... S - 2; for every other point in the soft call's order.
+ *   Identities, by bytes: with pilots NULL and every point {0, 0} all seven outputs are wofdm_rx_profile_soft's; with a comb a
+ * {0, 0} point has its bytes on every data bin of errs, err_power and bit_penalty.  A point's results do not depend on the
+ * other points of the call, a scale's not on the other scales; repeated calls give identical bytes; the totals do not depend on
+ * where a chunk ends.
+ *   Every argument, limit and check of wofdm_rx_profile_soft applies, then, in this order, WOFDM_E_INVALID for: a pilot on a bin
+ * that is not loaded; a comb that leaves no loaded bin for data; and point by point cpe or post outside {0, 1}; reserved not 0;
+ * post with syms_per_frame < 3; cpe without a pilot bin.  NULL tracking is WOFDM_E_INVALID.  Every argument is checked before
+ * the device is touched; a failed call leaves all seven outputs as they were.
+ *   Chunks: wofdm_rx_profile_soft's formula -- the receiver has no per-frame buffers of its own.
+ *   A successful call holds the launch gate and counts for wofdm_rx_profile_kernel_ms.
+ *   Measured on an MI355X (tools/bench_rx_profile_tracking.py, profiles/rx_profile_tracking.txt): on 64 cells x 2000 frames x 16
+ * symbols at n_fft = 256, one point with a free-running carrier offset and linewidth, a comb on every eighth loaded bin, against
+ * wofdm_rx_profile_soft with the same point in the same run (96.4 ms of kernels with one scale, 139.1 ms with sixteen; masked 123.2
+ * and 167.1 ms; spread over the rounds 0.3 ms): the {0, 0} receiver 1.012 and 0.999 (masked 1.011 and 1.010) times, {1, 0} 1.038 and
+ * 1.005 (1.031 and 1.023), {0, 1} 1.032 and 1.002 (1.027 and 1.032), {1, 1} 1.043 and 1.009 (1.036 and 1.027) -- at most 4.6 ms, more
+ * than the spread: the comb correlation and one pass over the bins per data symbol, the second estimate and one more barrier per
+ * frame; how the 4 ms split between them was not measured.  Other n_fft: not measured. */
+typedef struct wofdm_tracking_point {
+    int32_t cpe;                                           /* 1: the comb's common-phase estimate per data symbol        */
+    int32_t post;                                          /* 1: symbol S - 1 is a postamble                             */
+    int32_t reserved[2];                                   /* 0                                                          */
+} wofdm_tracking_point;
+int wofdm_rx_profile_tracking(const wofdm_cfg *cfg, int device,
+                              const float *w_tx,            /* [pairs][P] */
+                              const float *w_rx,            /* [pairs][N+tail_rx] */
+                              const float *h,               /* [n_channels][n_taps][2] */
+                              const float *snr_db,          /* [n_snr] */
+                              const uint8_t *active,        /* [n_fft] or NULL */
+                              const float *tx_mask,         /* [2P-1] or NULL */
+                              const float *h_track,         /* [n_tracks][n_channels][n_knots][n_taps][2], or NULL */
+                              int32_t n_tracks, int32_t n_knots, int32_t knot_step,
+                              const uint8_t *aci_active,    /* [n_fft], or NULL */
+                              const float *aci_h,           /* [n_channels][n_taps][2], or NULL = h */
+                              const float *ref_power,       /* [pairs], or NULL */
+                              int32_t n_points, const wofdm_link_point *points,
+                              int32_t n_scales, const float *scales,
+                              const uint8_t *pilots,        /* [n_fft], or NULL */
+                              const wofdm_tracking_point *tracking, /* [n_points] */
+                              uint64_t *errs,               /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                              double *err_power,            /* [n_points][cells][n_fft], or NULL */
+                              uint64_t *sym_errs,           /* [n_points][cells][S-1][2], or NULL */
+                              double *sym_power,            /* [n_points][cells][S-1], or NULL */
+                              double *pa_power,             /* [n_points][cells][2], or NULL */
+                              double *bit_penalty,          /* [n_points][cells][n_scales][n_fft], ACCUMULATED into */
+                              double *sym_penalty);         /* [n_points][cells][n_scales][S-1], or NULL */
+
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

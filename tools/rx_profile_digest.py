@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: the bytes of the eight receive-profile entry points and of wofdm_tx_papr, as SHA-256 digests -- for comparing two builds of the
+"""Developer tool: the bytes of the nine receive-profile entry points and of wofdm_tx_papr, as SHA-256 digests -- for comparing two builds of the
 library (WOFDM_LIB=... selects one) or two versions of the Python layer above it: run the tool once per build or tree and diff
 the outputs line for line.  It uses the package's public names only, so the same file runs against either tree.
 
@@ -14,6 +14,8 @@ of W, W = 4 at N = 1024, the fold with and without an Rx tail and both noise ord
   rx_profile_link     the cases of tests/test_gpu_rx_profile_link.py, composed points and their single-impairment points
   rx_profile_soft     the same cases with the points and default scales of tests/test_gpu_rx_profile_soft.py: the link fields and
                       beside them bit_penalty and bit_penalty_sym (the ABI's sym_penalty)
+  rx_profile_tracking the cases of tests/test_gpu_rx_profile_tracking.py with its comb, points, receivers and scales, and the
+                      decisions per point and per symbol
   tx_papr             tests/papr_cases.py: every N, system and variant; hist, max_papr and periods (--route gpu only: the
                       oracle is its only mirror, and the tests hold it against that)
 and for each entry point the chunk-straddling shape of its test file (N = 1024, S = 16, cp + cs = 64, four chunks and a bit;
@@ -58,6 +60,7 @@ import test_gpu_rx_profile_pa as TP  # noqa: E402
 import test_gpu_rx_profile_pn as TN  # noqa: E402
 import test_gpu_rx_profile_soft as TQ  # noqa: E402
 import test_gpu_rx_profile_sync as TS  # noqa: E402
+import test_gpu_rx_profile_tracking as TT  # noqa: E402
 
 
 def host_plain(c, seed, frame_offset, frames):
@@ -85,6 +88,13 @@ def gpu_soft(c, seed, frame_offset, frames, **kw):
     return TQ.run_soft(c, seed, frame_offset, frames)
 
 
+def gpu_tracking(c, seed, frame_offset, frames, **kw):
+    if "scales" in kw:                                                 # (the chunk shape: its own comb, points and scales)
+        return W.rx_profile_tracking_gpu(c["st"], c["k"], c["S"], c["w_tx"], c["w_rx"], c["h"], c["snr"], seed, frame_offset, frames,
+                                         c["points"], c["tracking"], c["pilots"], kw["scales"], active=c["active"])
+    return TT.run_gpu(c, seed, frame_offset, frames)
+
+
 def papr_digests(c, seed, frame_offset, frames, periods_at=None):
     """hist, max_papr and periods of one wofdm_tx_papr call; periods_at: (frame_offset, frames) of a second call the periods
     come from, where the first has too many to ask for"""
@@ -105,6 +115,7 @@ ROUTES = {
     "rx_profile_pn": (TN.run_gpu, TN.host),
     "rx_profile_link": (gpu_link, TL.host),
     "rx_profile_soft": (gpu_soft, lambda *a, **kw: (TQ.host_soft(*a, **kw), None)),   # (the link entry has the near counts)
+    "rx_profile_tracking": (gpu_tracking, TT.host),
 }
 
 
@@ -141,6 +152,8 @@ def small_cases():
         yield "rx_profile_link", name, dict(c, points=c["composed"] + c["singles"]), 100 * (1 + j), {}
     for j, name in enumerate(TQ.CASES):
         yield "rx_profile_soft", name, TL.case(name), 100 * (1 + j), {}
+    for name in TT.CASES:
+        yield "rx_profile_tracking", name, TT.case(name), TT.base_seed(name), {}
 
 
 def papr_cases():
@@ -156,7 +169,7 @@ def papr_cases():
 
 
 def chunk_cases():
-    """(entry, case, frames, extra keywords): the chunk-straddling shape of the eight test files, N = 1024, S = 16, cp + cs = 64"""
+    """(entry, case, frames, extra keywords): the chunk-straddling shape of the nine test files, N = 1024, S = 16, cp + cs = 64"""
     st, S = W.make_structure("wtx", 1024, 56), 16
     big = RC.make_case(st, 4, S, "plain", 3001)
     half = CM.half_band_allocation(1024)
@@ -182,6 +195,9 @@ def chunk_cases():
            dict(tracks=cd["tracks"], knot_step=st.stride, aci_active=~half, ref_power=ref))
     cq = dict(big, active=half, points=[R.LinkPoint(), R.LinkPoint(linewidth=0.01)])
     yield "rx_profile_soft", cq, frames_of(R.rx_profile_soft_chunk_frames(st, S, False, 2, False, 2)), dict(scales=(0.5, 0.1))
+    ct = dict(big, active=half, pilots=R.pilot_comb(half, 8), points=[R.LinkPoint(linewidth=0.01), R.LinkPoint(cfo=0.01, cfo_tracked=0)],
+              tracking=[R.TrackingPoint(1, 1), R.TrackingPoint(0, 1)])
+    yield "rx_profile_tracking", ct, frames_of(R.rx_profile_tracking_chunk_frames(st, S, False, 2, False, 2)), dict(scales=(0.5, 0.1))
 
 
 def runs(route):

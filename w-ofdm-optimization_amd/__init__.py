@@ -18,7 +18,8 @@ as ``wofdm_amd`` through the shim module at the repository root.
                (GPU: wofdm_rx_profile_doppler), or behind a nonlinear power amplifier (GPU: wofdm_rx_profile_pa; the
                spectral regrowth: timefreq / wofdm_tx_psd_batch_pa), or under oscillator phase noise (GPU:
                wofdm_rx_profile_pn), or with all five combined (GPU: wofdm_rx_profile_link), with soft decisions and the
-               achievable rate beside the hard counters (GPU: wofdm_rx_profile_soft)
+               achievable rate beside the hard counters (GPU: wofdm_rx_profile_soft), behind a receiver that tracks with comb
+               pilots and a postamble (GPU: wofdm_rx_profile_tracking)
   _lib         ctypes binding of libwofdm_hip.so (include/wofdm.h)
 """
 from . import variants  # noqa: F401
@@ -39,7 +40,7 @@ from .timefreq import (estimate_obr, frame_papr, papr_ccdf, papr_hist, run_timef
                        tx_psd_batch_gpu, tx_waveform)
 from .channel_mask import (aci_for_window_file, doppler_for_window_file, interference_for_window_file,  # noqa: F401
                            link_for_window_file, soft_for_window_file, pa_for_window_file, papr_for_window_file, pn_for_window_file, profile_for_window_file,
-                           spectrum_for_window_file, sync_for_window_file)
+                           spectrum_for_window_file, sync_for_window_file, tracking_for_window_file)
 from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_db, frame_profile,  # noqa: F401
                          frame_profile_aci, frame_profile_sync, gen_noise_at, rx_profile_aci_gpu, rx_profile_aci_host,
                          rx_profile_gpu, rx_profile_host, rx_profile_sync_chunk_frames, rx_profile_sync_gpu,
@@ -52,7 +53,9 @@ from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_d
                          LinkPoint, RxProfileLink, frame_profile_link, rx_profile_link_chunk_frames, rx_profile_link_gpu,
                          rx_profile_link_host,
                          RxProfileSoft, SOFT_SCALES, bit_llrs, frame_profile_soft, gmi, gmi_per_bin, gmi_per_symbol,
-                         rx_profile_soft_chunk_frames, rx_profile_soft_gpu, rx_profile_soft_host, soft_penalties)
+                         rx_profile_soft_chunk_frames, rx_profile_soft_gpu, rx_profile_soft_host, soft_penalties,
+                         RxProfileTracking, TrackingPoint, frame_profile_tracking, pilot_comb, rx_profile_tracking_chunk_frames,
+                         rx_profile_tracking_gpu, rx_profile_tracking_host, tracking_equalise)
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

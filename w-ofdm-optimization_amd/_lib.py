@@ -53,7 +53,7 @@ EXPORTS = (
     "wofdm_rx_profile", "wofdm_rx_profile_kernel_ms", "wofdm_plan_kernel_geo", "wofdm_cfg_geo_id",
     "wofdm_rx_profile_aci", "wofdm_rx_profile_sync", "wofdm_rx_profile_doppler",
     "wofdm_rx_profile_pa", "wofdm_tx_psd_batch_pa", "wofdm_rx_profile_pn",
-    "wofdm_rx_profile_link", "wofdm_rx_profile_soft",
+    "wofdm_rx_profile_link", "wofdm_rx_profile_soft", "wofdm_rx_profile_tracking",
 )
 
 
@@ -114,6 +114,11 @@ class LinkPoint(C.Structure):
                 ("timing", C.c_int32), ("cfo", C.c_float), ("cfo_tracked", C.c_int32), ("linewidth", C.c_float),
                 ("cpe_tracked", C.c_int32), ("aci_on", C.c_int32), ("aci_delay", C.c_int32), ("aci_level_db", C.c_float),
                 ("reserved", C.c_int32 * 4)]
+
+
+class TrackingPoint(C.Structure):
+    """Mirror of ``wofdm_tracking_point`` (16 bytes)."""
+    _fields_ = [("cpe", C.c_int32), ("post", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class Dump(C.Structure):
@@ -198,6 +203,8 @@ def load():
                                         C.POINTER(LinkPoint), vp, vp, vp, vp, vp]
     L.wofdm_rx_profile_soft.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
                                         C.POINTER(LinkPoint), i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.wofdm_rx_profile_tracking.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
+                                            C.POINTER(LinkPoint), i32, vp, vp, C.POINTER(TrackingPoint), vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_tx_psd_batch_pa.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, C.POINTER(PaPoint), vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L

@@ -450,6 +450,38 @@ def soft_for_window_file(type_ofdm, cp, windows, channels, snr_db, points=None, 
                               tail_masked=(pts, scales, *side, ref[1]))
 
 
+def tracking_for_window_file(type_ofdm, cp, windows, channels, snr_db, points=None, tracking=None, pilot_spacing=8, scales=None,
+                             tracks=None, knot_step=None, aci_channels=None, num_subcar=256, bits_per_subcar=4, symbols_per_tx=16,
+                             ensemble=100, roll_off=ROLL_OFF, seed=0, frame_range=None, gpu=True, device=0, tail_tx=8, tail_rx=10):
+    """``soft_for_window_file`` behind a receiver that tracks -- which window pair is best once the common rotation is estimated
+    and removed and the channel estimate follows the frame: the same pairs, frames, points and side arguments, a comb of pilots
+    on every ``pilot_spacing``-th loaded bin (``rx_profile.pilot_comb``; None: no comb) and one ``rx_profile.TrackingPoint`` (or
+    (cpe, post)) per point in ``tracking`` (None: all (0, 0)).  On the GPU two ``wofdm_rx_profile_tracking`` calls whatever the
+    number of points and scales (gpu=False: ``rx_profile.rx_profile_tracking_host``).  Returns {name: {"profile",
+    "profile_masked"}}, each an ``rx_profile.RxProfileTracking`` of that pair, arrays [points, n_snr, n_channels, ...]; with no
+    comb and every point (0, 0) its fields are ``soft_for_window_file``'s."""
+    from . import rx_profile as R
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off)
+    pts = [R.LinkPoint()] if points is None else [R.LinkPoint(*q) for q in points]
+    first, count = _frames(ensemble, frame_range)
+    ref = [None, None]
+    if any(q.pa is not None for q in pts):
+        ref = [R.pa_ref_power(st, bits_per_subcar, symbols_per_tx, w_tx, seed, first, count, active=alloc, mask=m, gpu=gpu,
+                              **(dict(device=device) if gpu else {})) for m in (None, mask)]
+    pil = None if pilot_spacing is None else R.pilot_comb(alloc, pilot_spacing)
+    run = R.rx_profile_tracking_gpu if gpu else R.rx_profile_tracking_host
+    side = dict(tracks=tracks, knot_step=knot_step, aci_active=~alloc if any(q.aci is not None for q in pts) else None,
+                aci_h=aci_channels, active=alloc, **(dict(device=device) if gpu else {}))
+    head = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.atleast_2d(np.asarray(channels)), snr_db, seed, first, count, pts,
+            tracking, pil, scales)
+    plain, masked = run(*head, ref_power=ref[0], **side), run(*head, ref_power=ref[1], mask=mask, **side)
+
+    def of_pair(prof, i):
+        # (the sums begin with the point axis, then the pair's; the scales and the decisions belong to every pair)
+        return type(prof)(*(a[:, i] for a in prof[:-3]), *prof[-3:])
+    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
+
+
 def results_from_counts(names, masked, plain):
     def ber(c):      # mean over channels of per-channel BER (lines 84-117)
         return (c[..., 0] / np.maximum(c[..., 1], 1)).mean(axis=-1)

@@ -1645,7 +1645,7 @@ int wofdm_tx_papr_kernel_ms(float *ms)
 
 namespace {
 
-// A receive-profile call, whichever of the eight entry points made it: what every call has, and the stages that are on, each
+// A receive-profile call, whichever of the entry points made it: what every call has, and the stages that are on, each
 // with its own inputs and outputs.  The entry points fill it; rx_profile_run checks it, prepares the stages, runs the chunks
 // and copies back.
 struct rx_call {
@@ -1683,6 +1683,8 @@ struct rx_call {
     } link;
     // the soft demapper of wofdm_rx_profile_soft
     struct { bool on; int32_t n_scales; const float *scales; double *bit_penalty, *sym_penalty; } soft;
+    // the tracking receiver of wofdm_rx_profile_tracking: the comb (may be null) and a tracking point per link point
+    struct { bool on; const uint8_t *pilots; const wofdm_tracking_point *points; } trk;
 };
 
 // the receive side's geometry beside the Tx chain's, and the cells of the call
@@ -1705,6 +1707,8 @@ struct rx_run {
     std::vector<wofdm_lpoint> lk;
     std::vector<wofdm_papoint> pa;
     std::vector<float> asat;
+    std::vector<uint8_t> pil;         // the comb as 0 / 1, empty without one
+    std::vector<wofdm_tpoint> tp;
     int n_knots, knot_step;
     // device
     size_t chunk, n_out, n_sym, n_ptot, n_bpen, n_spen;
@@ -1719,6 +1723,8 @@ struct rx_run {
     dev_buf<wofdm_papoint> d_papts;
     dev_buf<wofdm_pnpoint> d_pnpts;
     dev_buf<wofdm_lpoint> d_lkpts;
+    dev_buf<uint8_t> d_pil;
+    dev_buf<wofdm_tpoint> d_tp;
     wofdm_rxchunk ck;
     int n_tracks() const { return c.dop.on ? c.dop.n_tracks : 0; }
 };
@@ -1941,6 +1947,38 @@ int prep_amp(rx_run &r)
     return WOFDM_OK;
 }
 
+// the tracking receiver, in the order include/wofdm.h documents: the comb -- every pilot on a loaded bin, a data bin left --, then
+// point by point the flags, reserved, post against S, cpe against the comb
+int prep_track(rx_run &r)
+{
+    const auto &trk = r.c.trk;
+    if (!trk.on) return WOFDM_OK;
+    const int N = r.g.N, NP = r.c.n_points;
+    int n_pil = 0, n_data = 0;
+    const auto loaded = [&](int n) { return r.act.empty() || r.act[(size_t)n] != 0; };   // (no allocation: every bin)
+    if (trk.pilots) {
+        r.pil.resize((size_t)N);
+        for (int n = 0; n < N; ++n) {
+            r.pil[(size_t)n] = trk.pilots[n] ? 1 : 0;
+            if (trk.pilots[n] && !loaded(n)) return fail(WOFDM_E_INVALID, "pilots[%d] is set on a bin that is not loaded", n);
+            n_pil += trk.pilots[n] ? 1 : 0;
+        }
+    }
+    for (int n = 0; n < N; ++n) n_data += loaded(n) && !(trk.pilots && trk.pilots[n]) ? 1 : 0;
+    if (n_data < 1) return fail(WOFDM_E_INVALID, "the comb leaves no data bin");
+    r.tp.resize((size_t)NP);
+    for (int i = 0; i < NP; ++i) {
+        const wofdm_tracking_point &q = trk.points[i];
+        if ((q.cpe != 0 && q.cpe != 1) || (q.post != 0 && q.post != 1))
+            return fail(WOFDM_E_INVALID, "tracking[%d]: cpe=%d and post=%d must be 0 or 1", i, q.cpe, q.post);
+        if (q.reserved[0] != 0 || q.reserved[1] != 0) return fail(WOFDM_E_INVALID, "tracking[%d].reserved must be 0", i);
+        if (q.post && r.g.S < 3) return fail(WOFDM_E_INVALID, "tracking[%d].post needs syms_per_frame >= 3, not %d", i, r.g.S);
+        if (q.cpe && n_pil < 1) return fail(WOFDM_E_INVALID, "tracking[%d].cpe needs at least one pilot bin", i);
+        r.tp[(size_t)i] = {q.cpe, q.post};
+    }
+    return WOFDM_OK;
+}
+
 // The taps as the kernels read them.  Of moving channels the knots, [n_tracks][n_channels][n_knots][WOFDM_LT], zero padded, and
 // behind them the static track where the call has one: h at every knot (without a track of the caller's, two knots that cover
 // every sample).  Without either, h as it is -- the static track of one knot.
@@ -2095,6 +2133,20 @@ int stage_soft(rx_run &r)
     return WOFDM_OK;
 }
 
+// the tracking receiver's side: the comb and the points
+int stage_track(rx_run &r)
+{
+    if (!r.c.trk.on) return WOFDM_OK;
+    if ((!r.pil.empty() && !r.d_pil.alloc(r.pil.size())) || !r.d_tp.alloc(r.tp.size()))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (tracking receiver)");
+    if ((!r.pil.empty() && !r.d_pil.upload(r.pil.data(), r.pil.size())) || !r.d_tp.upload(r.tp.data(), r.tp.size()))
+        return fail(WOFDM_E_HIP, "upload failed");
+    r.ck.tk.pilots = r.pil.empty() ? nullptr : (const uint8_t *)r.d_pil;
+    r.ck.tk.pts = r.d_tp;
+    r.ck.track_on = true;
+    return WOFDM_OK;
+}
+
 // the neighbour's side of the chunk: allocation, channels, and the Tx chain of its S + 1 symbols on the victim's windows and mask
 int stage_nb(rx_run &r)
 {
@@ -2126,9 +2178,9 @@ template <typename T, typename U> void add_to(T *out, const std::vector<U> &host
     for (size_t i = 0; out && i < host.size(); ++i) out[i] += host[i];
 }
 
-// The eight receive profiles.  Every argument is checked before the first HIP call -- the NULL arguments and the stages' counts,
-// the geometry, the finiteness, then the stages' points: sync, pn, doppler, link, amplifier --; the caller's arrays are written
-// only after everything has succeeded.
+// The receive profiles.  Every argument is checked before the first HIP call -- the NULL arguments and the stages' counts,
+// the geometry, the finiteness, then the stages' points: sync, pn, doppler, link, amplifier, tracking --; the caller's arrays are
+// written only after everything has succeeded.
 int rx_profile_run(const rx_call &c)
 {
     int rc = check_rx_args(c);
@@ -2137,7 +2189,8 @@ int rx_profile_run(const rx_call &c)
     if ((rc = check_rx_geometry(c, &r.g)) != WOFDM_OK || (rc = check_rx_finite(c, r.g)) != WOFDM_OK ||
         (rc = check_allocation(c.active, r.g.N, &r.act)) != WOFDM_OK || (rc = prep_nb(r)) != WOFDM_OK ||
         (rc = prep_sync(r)) != WOFDM_OK || (rc = prep_pn(r)) != WOFDM_OK || (rc = check_knots(r)) != WOFDM_OK ||
-        (rc = prep_link(r)) != WOFDM_OK || (rc = prep_amp(r)) != WOFDM_OK || (rc = use_device(c.device)) != WOFDM_OK)
+        (rc = prep_link(r)) != WOFDM_OK || (rc = prep_amp(r)) != WOFDM_OK || (rc = prep_track(r)) != WOFDM_OK ||
+        (rc = use_device(c.device)) != WOFDM_OK)
         return rc;
     g_rxprof_ms = 0.f;
     const rx_geom &g = r.g;
@@ -2153,7 +2206,7 @@ int rx_profile_run(const rx_call &c)
     r.n_spen = NP * g.cells * NSC * (g.S - 1);
     if ((rc = stage_base(r)) != WOFDM_OK || (rc = stage_points(r)) != WOFDM_OK || (rc = stage_amp(r)) != WOFDM_OK ||
         (rc = stage_pn(r)) != WOFDM_OK || (rc = stage_link(r)) != WOFDM_OK || (rc = stage_soft(r)) != WOFDM_OK ||
-        (rc = stage_nb(r)) != WOFDM_OK)
+        (rc = stage_track(r)) != WOFDM_OK || (rc = stage_nb(r)) != WOFDM_OK)
         return rc;
     // (a neighbour that loads no bin: the plain kernel)
     r.ck.arm = c.arm == RXP_ACI && !r.nb ? RXP_PLAIN : c.arm;
@@ -2323,6 +2376,30 @@ int wofdm_rx_profile_soft(const wofdm_cfg *cfg, int device, const float *w_tx, c
     c.nb = {false, aci_active, aci_h, 0, 0.f};
     c.amp = {false, false, nullptr, ref_power, pa_power};
     c.soft = {true, n_scales, scales, bit_penalty, sym_penalty};
+    const int rc = rx_link_stages(c, n_points, points);
+    return rc != WOFDM_OK ? rc : rx_profile_run(c);
+}
+
+int wofdm_rx_profile_tracking(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                              const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                              int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
+                              const wofdm_link_point *points, int32_t n_scales, const float *scales, const uint8_t *pilots,
+                              const wofdm_tracking_point *tracking, uint64_t *errs, double *err_power, uint64_t *sym_errs,
+                              double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty)
+{
+    if (!scales || !bit_penalty || !tracking) return fail(WOFDM_E_INVALID, "NULL argument (scales, bit_penalty or tracking)");
+    if (n_scales < 1) return fail(WOFDM_E_INVALID, "n_scales=%d must be >= 1", n_scales);
+    if (n_scales > WOFDM_SOFT_MAX_SCALES) return fail(WOFDM_E_UNSUPPORTED, "n_scales=%d exceeds %d", n_scales, WOFDM_SOFT_MAX_SCALES);
+    for (int j = 0; j < n_scales; ++j)
+        if (!std::isfinite(scales[j]) || !(scales[j] > 0.f))
+            return fail(WOFDM_E_INVALID, "scales[%d] must be finite and positive", j);
+    rx_call c = rx_base(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask);
+    rx_outputs(c, RXP_LINK, n_points, errs, err_power, sym_errs, sym_power);
+    c.dop = {false, false, h_track, n_tracks, n_knots, knot_step};
+    c.nb = {false, aci_active, aci_h, 0, 0.f};
+    c.amp = {false, false, nullptr, ref_power, pa_power};
+    c.soft = {true, n_scales, scales, bit_penalty, sym_penalty};
+    c.trk = {true, pilots, tracking};
     const int rc = rx_link_stages(c, n_points, points);
     return rc != WOFDM_OK ? rc : rx_profile_run(c);
 }

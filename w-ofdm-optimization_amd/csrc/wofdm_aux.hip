@@ -1053,6 +1053,9 @@ template <int N> struct rxp_geo {
     // the link arm: the neighbour's row and the knots (75 776 B at N = 256, 129 024 B at N = 512, 131 584 B at N = 1024)
     static constexpr int LDS_LINK = LDS + WAVES * 8 * XROW + 8 * WOFDM_DOPPLER_KNOTS * WOFDM_LT;
     static_assert(LDS_LINK <= 160 * 1024, "LDS (link arm)");
+    // the tracking receiver: one more float2 [N], HL (139 776 B at N = 1024)
+    static constexpr int LDS_TRACK = LDS_LINK + 8 * N;
+    static_assert(LDS_TRACK <= 160 * 1024, "LDS (tracking receiver)");
 };
 
 // the complex unit normal of sample a of (seed, cell, frame): philox.h, block a / 2, words 2 (a % 2) and 2 (a % 2) + 1
@@ -1235,9 +1238,12 @@ __device__ __forceinline__ float soft_log2_1p(float x)
 // pen_j goes to bit_part[slot][s - 1][j][n] (0 on an unloaded bin: every element of the symbol's rows is written), the lane's
 // sum over its bins, then the wave's (papr_wave_reduce), to sym_part[slot][j][s].  The bins' loop is not unrolled -- 16 scales
 // times 6 bits of exp2 / log2 pairs are code enough once -- and the scales' loop is, so that the lane's sums stay in registers.
-template <int N>
+// TRACK (wofdm_rxprof_tracking_kernel): pil, the comb, or null -- a pilot bin is written as an unloaded one is, 0 --, and G is
+// whatever equaliser the point's receiver formed for this symbol, e = G row and nu = |G|^2 vw as above.
+template <int N, bool TRACK = false>
 __device__ __forceinline__ void soft_symbol(const wofdm_rparams &p, const wofdm_softparams &so, const float2 *row, const float2 *G,
-                                            const float2 *__restrict__ Xs, float vw, size_t slot, int s, int lane)
+                                            const float2 *__restrict__ Xs, float vw, size_t slot, int s, int lane,
+                                            [[maybe_unused]] const uint8_t *__restrict__ pil = nullptr)
 {
     constexpr int BINS = N / 64, SC = WOFDM_SOFT_SCALES;
     const int k = p.k, hb = k >> 1, mm = (1 << hb) - 1, nsc = so.n_scales, S = p.S;
@@ -1249,7 +1255,8 @@ __device__ __forceinline__ void soft_symbol(const wofdm_rparams &p, const wofdm_
 #pragma unroll 1
     for (int j = 0; j < BINS; ++j) {
         const int n = lane + 64 * j;
-        const bool on = p.amask == nullptr || p.amask[n] != 0;
+        bool on = p.amask == nullptr || p.amask[n] != 0;
+        if constexpr (TRACK) on = on && (pil == nullptr || pil[n] == 0);
         const float2 y = row[n], gq = G[n], xs = Xs[n];
         const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;
         const float rn = 1.0f / (a * a * (gq.x * gq.x + gq.y * gq.y) * vw);
@@ -1319,6 +1326,17 @@ __device__ __forceinline__ void soft_symbol(const wofdm_rparams &p, const wofdm_
     }
 }
 
+// The scratch of a symbol that counts nothing (the postamble of a tracking point): the zeros soft_symbol would write on a
+// symbol without a loaded bin, for wofdm_rxprof_soft_frame_kernel and the symbols' sums to add
+template <int N>
+__device__ __forceinline__ void soft_symbol_zero(const wofdm_softparams &so, int S, size_t slot, int s, int lane)
+{
+    const int nsc = so.n_scales;
+    float *__restrict__ bp = so.bit_part + (slot * (size_t)(S - 1) + (size_t)(s - 1)) * (size_t)nsc * N;
+    for (int i = lane; i < nsc * N; i += 64) bp[i] = 0.f;
+    if (lane < nsc) so.sym_part[(slot * (size_t)nsc + (size_t)lane) * (size_t)S + (size_t)s] = 0.f;
+}
+
 // The one body of the seven receive kernels; ARM selects at compile time what an arm adds to the pipeline above, and the
 // parameters of the other arms are not read.
 //   RXP_PLAIN    wofdm_rx_profile: nothing.
@@ -1361,16 +1379,31 @@ __device__ __forceinline__ void soft_symbol(const wofdm_rparams &p, const wofdm_
 //                before the frame (a < 0: every product is zero) takes its taps at time 0.  LDS: LDS_LINK.
 //   SOFT         (RXP_LINK only: wofdm_rx_profile_soft) behind pass 1 the point's v W2, and behind the hard decisions of every data
 //                symbol the demapper soft_symbol above; with the flag false no statement of the body changes.
+//   TRACK        (SOFT only: wofdm_rx_profile_tracking) per point the flags cpe and post of tk (wave-uniform).  A point with neither
+//                runs the statements above, G = X0 / Y0 and the soft kernel's symbol-to-wave assignment; pilot bins of the comb
+//                count nothing.  A point with either keeps H0 = Y0 / X0 in G's place.  With post the waves visit the symbols in
+//                the order 0, S - 1, 1, 2, ... S - 2 over the same rounds, so that behind the first round's barrier wave 0
+//                publishes H0 and wave 1 HL = Y_{S-1} / X_{S-1} (hl, one more float2 [N] behind the knots: LDS_TRACK); wave 0
+//                then forms cL = sum_n HL[n] conj(H0[n]) -- a lane's bins ascending (an unloaded bin adds an exact zero), then
+//                papr_wave_reduce on either component --, rho = cL / |cL| (1 where cL = 0), leaves rho in red[2 W], turns hl into
+//                HL conj(rho) - H0, and one more barrier follows.  The wave of a data symbol s forms, with t = s / (S - 1),
+//                Hh[n] = H0[n] + t hl[n] (post) or H0[n]; the phase q -- cpe: c = sum over the comb of Y_s[p] conj(Hh[p] X_s[p]), a
+//                lane's pilot bins ascending, then papr_wave_reduce, q = c / |c| (1 where c = 0); post alone: e^{i t arg rho} --;
+//                and the symbol's equaliser conj(q) conj(Hh) / |Hh|^2 per bin in its own x row, free behind the transform, which
+//                the slicer's loop and the demapper then read in G's place: one e for both.  The postamble's wave counts
+//                nothing and writes the zeros of its symbol.  With the flag false no statement of the body changes.
 // The arms with a point loop (points, tracks) write the partials part_pow, part_cnt [job][point][N], and the wave of symbol
 // s >= 1 leaves beside them the symbol's sums over the loaded bins -- a lane's bins ascending, then papr_wave_reduce -- in
 // sym_pow, sym_cnt [job][point][S].  The pilot of a point sees what the point's data sees.  Where pass 1 runs per point, Ps
 // is the point's; Pn depends on neither channel nor waveform and is measured with the first.
-template <int N, int ARM, bool SOFT = false>
+template <int N, int ARM, bool SOFT = false, bool TRACK = false>
 __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_aparams &ap, const wofdm_sparams &sp,
                                             const wofdm_dparams &dp, const wofdm_paparams &pa, const wofdm_pnparams &pn,
-                                            const wofdm_lparams &lk, [[maybe_unused]] const wofdm_softparams &so = wofdm_softparams{})
+                                            const wofdm_lparams &lk, [[maybe_unused]] const wofdm_softparams &so = wofdm_softparams{},
+                                            [[maybe_unused]] const wofdm_trackparams &tk = wofdm_trackparams{})
 {
     static_assert(!SOFT || ARM == RXP_LINK, "the demapper is instantiated for the link arm only");
+    static_assert(!TRACK || SOFT, "the tracking receiver is instantiated with the demapper only");
     using RG = rxp_geo<N>;
     constexpr bool LINK = ARM == RXP_LINK;
     constexpr bool ACI = ARM == RXP_ACI || LINK, SYNC = ARM == RXP_SYNC || LINK, DOP = ARM == RXP_DOPPLER || LINK;
@@ -1385,6 +1418,7 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
     float *red = wrx + N + 64;                                        // [2][W] power partials
     float2 *rows = reinterpret_cast<float2 *>(red + 64);
     [[maybe_unused]] float2 *kn = rows + (size_t)W * ROWLEN;          // (DOP) [n_knots][LT] knots of the track, the item's channel
+    [[maybe_unused]] float2 *hl = kn + WOFDM_DOPPLER_KNOTS * LT;      // (TRACK) [N] HL, then HL conj(rho) - H0
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int S = p.S, B = p.B, T = p.T, NL = p.NL, delta = p.delta, NP = POINTS ? sp.n_points : 1;
@@ -1494,6 +1528,13 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
         [[maybe_unused]] const int ioff = LINK ? lk.pts[pt].ioff : ap.ioff;
         [[maybe_unused]] const float a_lvl = LINK ? lk.pts[pt].a_lvl : ap.a_lvl;
         const size_t slot = (size_t)job * NP + pt;
+        // (TRACK) the point's receiver (wave-uniform): tracked = either mechanism is on
+        [[maybe_unused]] bool tcpe = false, tpost = false;
+        if constexpr (TRACK) {
+            tcpe = __builtin_amdgcn_readfirstlane(tk.pts[pt].cpe) != 0;
+            tpost = __builtin_amdgcn_readfirstlane(tk.pts[pt].post) != 0;
+        }
+        [[maybe_unused]] const bool tracked = tcpe || tpost;
         float pw[BINS];
         uint32_t cnt[BINS];
 #pragma unroll
@@ -1502,8 +1543,11 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
             cnt[j] = 0u;
         }
         for (int s0 = 0; s0 < S; s0 += W) {
-            const int s = s0 + wv;
+            int s = s0 + wv;
             const bool live = s < S;                                  // (wave-uniform)
+            if constexpr (TRACK) {
+                if (tpost && live) s = s == 0 ? 0 : (s == 1 ? S - 1 : s - 1);   // the postamble in the first round
+            }
             if (live) {
                 const int a0 = s * B + p.gam + theta;                 // first sample under the Rx window (m:442-454)
                 [[maybe_unused]] const float2 bs = SYNC ? sp.base[(size_t)pt * S + s] : make_float2(1.f, 0.f);
@@ -1616,25 +1660,110 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
                 }
             }
             if (s0 == 0) {
-                // pilot LS estimate (m:266-267): G = X0 / Y0 on the loaded bins
-                if (wv == 0)
-                    for (int n = lane; n < N; n += 64) {
-                        const float2 y = buf[n], x0 = Xg[n];
-                        const float d = y.x * y.x + y.y * y.y;
-                        const bool on = p.amask == nullptr || p.amask[n] != 0;
-                        G[n] = on ? make_float2((x0.x * y.x + x0.y * y.y) / d, (x0.y * y.x - x0.x * y.y) / d) : make_float2(0.f, 0.f);
+                if constexpr (TRACK) {
+                    if (tracked) {
+                        // the channel estimates of the known symbols on the loaded bins: wave 0 H0 = Y0 / X0, wave 1 HL
+                        if (wv == 0 || (tpost && wv == 1)) {
+                            float2 *dst = wv == 0 ? G : hl;
+                            const float2 *__restrict__ Xk = Xg + (size_t)s * N;
+                            for (int n = lane; n < N; n += 64) {
+                                const float2 y = buf[n], xk = Xk[n];
+                                const float d = xk.x * xk.x + xk.y * xk.y;
+                                const bool on = p.amask == nullptr || p.amask[n] != 0;
+                                dst[n] = on ? make_float2((y.x * xk.x + y.y * xk.y) / d, (y.y * xk.x - y.x * xk.y) / d) : make_float2(0.f, 0.f);
+                            }
+                        }
+                        __syncthreads();
+                        if (tpost) {
+                            if (wv == 0) {
+                                float cx = 0.f, cy = 0.f;
+                                for (int n = lane; n < N; n += 64) {
+                                    const float2 a = hl[n], b = G[n];
+                                    cx += a.x * b.x + a.y * b.y;
+                                    cy += a.y * b.x - a.x * b.y;
+                                }
+                                cx = papr_wave_reduce<false>(cx);
+                                cy = papr_wave_reduce<false>(cy);
+                                const float m = sqrtf(cx * cx + cy * cy);
+                                const float2 rho = m > 0.f ? make_float2(cx / m, cy / m) : make_float2(1.f, 0.f);
+                                for (int n = lane; n < N; n += 64) {
+                                    const float2 a = hl[n], b = G[n];
+                                    hl[n] = make_float2(a.x * rho.x + a.y * rho.y - b.x, a.y * rho.x - a.x * rho.y - b.y);
+                                }
+                                if (lane == 0) {
+                                    red[2 * W] = rho.x;
+                                    red[2 * W + 1] = rho.y;
+                                }
+                            }
+                            __syncthreads();
+                        }
                     }
-                __syncthreads();
+                }
+                if (!tracked) {
+                    // pilot LS estimate (m:266-267): G = X0 / Y0 on the loaded bins
+                    if (wv == 0)
+                        for (int n = lane; n < N; n += 64) {
+                            const float2 y = buf[n], x0 = Xg[n];
+                            const float d = y.x * y.x + y.y * y.y;
+                            const bool on = p.amask == nullptr || p.amask[n] != 0;
+                            G[n] = on ? make_float2((x0.x * y.x + x0.y * y.y) / d, (x0.y * y.x - x0.x * y.y) / d) : make_float2(0.f, 0.f);
+                        }
+                    __syncthreads();
+                }
             }
             if (live) {
                 [[maybe_unused]] float spw = 0.f;
                 [[maybe_unused]] uint32_t scn = 0u;
-                if (s >= 1) {
+                // (TRACK) a symbol that counts: not the pilot, and not the postamble of a point with post
+                [[maybe_unused]] const bool counted = s >= 1 && !(tpost && s == S - 1);
+                [[maybe_unused]] const float2 *Gs = G;                // the equaliser the symbol's decisions see
+                if constexpr (TRACK) {
+                    if (tracked && counted) {
+                        const float2 *__restrict__ Xs = Xg + (size_t)s * N;
+                        const float t = (float)s / (float)(S - 1);
+                        float2 q = make_float2(1.f, 0.f);
+                        if (tcpe) {
+                            float cx = 0.f, cy = 0.f;
+                            for (int n = lane; n < N; n += 64) {
+                                if (tk.pilots[n] == 0) continue;
+                                float2 hh = G[n];
+                                if (tpost) hh = make_float2(hh.x + t * hl[n].x, hh.y + t * hl[n].y);
+                                const float2 y = buf[n], xs = Xs[n];
+                                const float zr = hh.x * xs.x - hh.y * xs.y, zi = hh.x * xs.y + hh.y * xs.x;
+                                cx += y.x * zr + y.y * zi;
+                                cy += y.y * zr - y.x * zi;
+                            }
+                            cx = papr_wave_reduce<false>(cx);
+                            cy = papr_wave_reduce<false>(cy);
+                            const float m = sqrtf(cx * cx + cy * cy);
+                            if (m > 0.f) q = make_float2(cx / m, cy / m);
+                        } else {
+                            // e^{i t arg rho}, the principal value, in turns: atan2 / pi <= 1 in magnitude, so sincospif needs no reduction
+                            float sv, cv;
+                            sincospif(t * (atan2f(red[2 * W + 1], red[2 * W]) * 0.31830988618379067f), &sv, &cv);
+                            q = make_float2(cv, sv);
+                        }
+                        // conj(q) conj(Hh) / |Hh|^2 per bin, 0 on an unloaded one as G is
+                        for (int n = lane; n < N; n += 64) {
+                            float2 hh = G[n];
+                            if (tpost) hh = make_float2(hh.x + t * hl[n].x, hh.y + t * hl[n].y);
+                            const float d = hh.x * hh.x + hh.y * hh.y;
+                            const bool on = p.amask == nullptr || p.amask[n] != 0;
+                            xr[n] = on ? make_float2((q.x * hh.x - q.y * hh.y) / d, -(q.x * hh.y + q.y * hh.x) / d) : make_float2(0.f, 0.f);
+                        }
+                        wave_sync();
+                        Gs = xr;
+                    }
+                }
+                if (TRACK ? counted : s >= 1) {
 #pragma unroll
                     for (int j = 0; j < BINS; ++j) {
                         const int n = lane + 64 * j;
                         if (p.amask != nullptr && p.amask[n] == 0) continue;
-                        const float2 y = buf[n], gq = G[n], xs = Xg[(size_t)s * N + n];
+                        if constexpr (TRACK) {
+                            if (tk.pilots != nullptr && tk.pilots[n] != 0) continue;
+                        }
+                        const float2 y = buf[n], gq = (TRACK ? Gs : G)[n], xs = Xg[(size_t)s * N + n];
                         const float er = y.x * gq.x - y.y * gq.y, ei = y.x * gq.y + y.y * gq.x;   // equaliser (m:268)
                         const uint32_t d = rxp_slice(p.k, xs.x, xs.y) ^ rxp_slice(p.k, er, ei);    // (X is the point of its own label)
                         const uint32_t c = (uint32_t)__popc(d) + (d != 0u ? 0x10000u : 0u);
@@ -1657,7 +1786,12 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
                         sp.sym_cnt[slot * S + s] = scn;
                     }
                 }
-                if constexpr (SOFT) {
+                if constexpr (TRACK) {
+                    if (counted)
+                        soft_symbol<N, true>(p, so, buf, Gs, Xg + (size_t)s * N, soft_vw, slot, s, lane, tk.pilots);
+                    else if (s >= 1)
+                        soft_symbol_zero<N>(so, S, slot, s, lane);
+                } else if constexpr (SOFT) {
                     if (s >= 1) soft_symbol<N>(p, so, buf, G, Xg + (size_t)s * N, soft_vw, slot, s, lane);
                 }
             }
@@ -1736,6 +1870,16 @@ __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_soft_kern
                                                                                   const wofdm_lparams lk, const wofdm_softparams so)
 {
     rxprof_body<N, RXP_LINK, true>(p, ap, sp, dp, pa, pn, lk, so);
+}
+// wofdm_rx_profile_tracking: the soft kernel with the tracking receiver (TRACK) in the one-shot receiver's place, per point
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_tracking_kernel(const wofdm_rparams p, const wofdm_aparams ap,
+                                                                                      const wofdm_sparams sp, const wofdm_dparams dp,
+                                                                                      const wofdm_paparams pa, const wofdm_pnparams pn,
+                                                                                      const wofdm_lparams lk, const wofdm_softparams so,
+                                                                                      const wofdm_trackparams tk)
+{
+    rxprof_body<N, RXP_LINK, true, true>(p, ap, sp, dp, pa, pn, lk, so, tk);
 }
 
 // totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
@@ -2260,7 +2404,7 @@ void rxprof_reduce_launch(const wofdm_rparams &r, const wofdm_sparams *sp, hipSt
                            *sp, cell0);
 }
 
-// One chunk of a receive profile, whichever of the eight entry points it belongs to (wofdm_link.h): the stages the arm switches
+// One chunk of a receive profile, whichever of the entry points it belongs to (wofdm_link.h): the stages the arm switches
 // on are checked, then enqueued in the one order there is -- the Tx chain of the chunk's (cell, frame) items; the neighbour's;
 // the points' amplified waveforms and power sums; the items' unit phase walks; the arm's receive kernel; the ordered sums
 // (per point where the arm has points); the amplifier's power sums in frame order; the demapper's ordered sums behind the others.
@@ -2274,8 +2418,8 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
     if (c.arm < RXP_PLAIN || c.arm > RXP_LINK) return hipErrorInvalidValue;
     const bool link = c.arm == RXP_LINK, points = MAX_POINTS[c.arm] > 0;
     const bool nb = c.arm == RXP_ACI || (link && c.nb_on), sync = c.arm == RXP_SYNC || link, knots = c.arm == RXP_DOPPLER || link;
-    const bool amp = c.arm == RXP_PA || link, walk = c.arm == RXP_PN || link, soft = link && c.soft_on;
-    if (nb != c.nb_on || soft != c.soft_on || !rxprof_args_ok(&c.tx, r) || (points && !rxprof_points_ok(c.sp, r, MAX_POINTS[c.arm])) ||
+    const bool amp = c.arm == RXP_PA || link, walk = c.arm == RXP_PN || link, soft = link && c.soft_on, track = soft && c.track_on;
+    if (nb != c.nb_on || soft != c.soft_on || track != c.track_on || (track && (c.tk.pts == nullptr || r.S > 64)) || !rxprof_args_ok(&c.tx, r) || (points && !rxprof_points_ok(c.sp, r, MAX_POINTS[c.arm])) ||
         (nb && !rxprof_nb_ok(c, !link)) || (sync && (c.sp.pts == nullptr || c.sp.base == nullptr)) ||
         (knots && !rxprof_knots_ok(c.dp, r, link, link ? c.max_theta : 0)) || (amp && !rxprof_pa_ok(c)) ||
         // (rxprof_args_ok: B = N + delta + gam, so the last sample under the last window is the walk's last, index S B - 1)
@@ -2307,7 +2451,9 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
     case RXP_PA: receive(wofdm_rxprof_pa_kernel<N>, rxp_geo<N>::LDS, c.sp, c.pa); break;
     case RXP_PN: receive(wofdm_rxprof_pn_kernel<N>, rxp_geo<N>::LDS, c.sp, c.pn); break;
     default:
-        if (soft)
+        if (track)
+            receive(wofdm_rxprof_tracking_kernel<N>, rxp_geo<N>::LDS_TRACK, c.a, c.sp, c.dp, c.pa, c.pn, c.lk, c.soft, c.tk);
+        else if (soft)
             receive(wofdm_rxprof_soft_kernel<N>, rxp_geo<N>::LDS_LINK, c.a, c.sp, c.dp, c.pa, c.pn, c.lk, c.soft);
         else
             receive(wofdm_rxprof_link_kernel<N>, rxp_geo<N>::LDS_LINK, c.a, c.sp, c.dp, c.pa, c.pn, c.lk);

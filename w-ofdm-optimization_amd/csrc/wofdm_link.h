@@ -42,16 +42,30 @@ struct wofdm_softparams {
     double *sym_tot;                  // [n_points][cells][n_scales][S - 1], accumulated into
 };
 
+// The tracking receiver of wofdm_rx_profile_tracking, a ninth argument of wofdm_rxprof_tracking_kernel (the link arm with the
+// demapper and the TRACK flag): the comb of pilot bins and per point the two mechanisms.  A point with neither runs the soft
+// kernel's statements; one with either equalises with Hhat_s = H0 + t (HL conj(rho) - H0), t = s / (S - 1), and the phase q_s
+// (include/wofdm.h has the definition).  Pilot bins, and the last symbol of a point with post, count nothing.
+struct wofdm_tpoint {
+    int32_t cpe;                      // the per-symbol common phase from the comb
+    int32_t post;                     // symbol S - 1 is a second known symbol
+};
+struct wofdm_trackparams {
+    const uint8_t *pilots;            // [n_fft], or null: no comb
+    const wofdm_tpoint *pts;          // [n_points]
+};
+
 // The arms of the receive body (rxprof_body of wofdm_aux.hip, which says what each adds)
 enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
 
-// One chunk of a receive-profile call, whichever of the eight: the victim's Tx chain, the receive kernel's parameters, and the
+// One chunk of a receive-profile call, whichever of the ten: the victim's Tx chain, the receive kernel's parameters, and the
 // stages' parameter structs as the kernels take them.  The arm says which stages the chunk runs -- a stage's struct is read
 // only where its arm or RXP_LINK is on --; the link arm runs every stage, its points switch them, and only its neighbour
-// (no point has aci_on: nb_on = false) and its demapper (wofdm_rx_profile_soft: soft_on) are the call's to leave out.
+// (no point has aci_on: nb_on = false), its demapper (wofdm_rx_profile_soft: soft_on) and, with the demapper, its tracking receiver
+// (wofdm_rx_profile_tracking: track_on) are the call's to leave out.
 struct wofdm_rxchunk {
     int32_t arm;                      // RXP_*
-    bool nb_on, soft_on;              // RXP_ACI: nb_on is true
+    bool nb_on, soft_on, track_on;    // RXP_ACI: nb_on is true; track_on needs soft_on
     wofdm_pparams tx, nb;             // the victim's Tx chain; the neighbour's (S + 1 symbols, its own stream, allocation, buffers)
     wofdm_rparams r;
     wofdm_aparams a;                  // RXP_LINK: ioff and a_lvl are the points'
@@ -61,6 +75,7 @@ struct wofdm_rxchunk {
     wofdm_pnparams pn;
     wofdm_lparams lk;
     wofdm_softparams soft;
+    wofdm_trackparams tk;
     int32_t n_tracks;                 // RXP_LINK: the tracks of dp's knots, the static one included
     int32_t max_theta;                // RXP_LINK: the largest timing offset of the points, or 0 (the knots cover the samples it reaches)
 };

@@ -37,6 +37,11 @@ above.
 bit metrics' penalties per bin and per data symbol for a list of scales, from which ``gmi_per_bin``, ``gmi_per_symbol`` and
 ``gmi`` form the achievable (BICM) rate; ``bit_llrs``, ``soft_penalties``, ``frame_profile_soft`` and ``rx_profile_soft_host``
 mirror it.
+
+``rx_profile_tracking_gpu`` (``wofdm_rx_profile_tracking``) is the soft call behind a receiver that tracks: a comb of pilot bins
+(``pilot_comb``) gives a common-phase estimate per data symbol, a postamble lets the channel estimate be interpolated over the
+frame, a ``TrackingPoint`` per link point switches either on; ``tracking_equalise`` states the definition in fp64,
+``frame_profile_tracking`` and ``rx_profile_tracking_host`` mirror the call.
 """
 import collections
 
@@ -92,17 +97,18 @@ def threshold_distance(bits_per_sc, z):
 
 def near_decisions(bits_per_sc, xhat, y0, tol=NEAR_TOL):
     """[S-1, N] bool: decisions that single-precision rounding may tip -- a component of the fp64 ``xhat`` [S-1, N] lies
-    within tol * max(1, |xhat|) * max_n |y0| / |y0[n]| of a slicer threshold (y0 [N]: the received pilot; 0 = unloaded)."""
+    within tol * max(1, |xhat|) * max_n |y0| / |y0[n]| of a slicer threshold (y0 [N]: the received pilot; 0 = unloaded).  y0
+    [S-1, N]: the estimate every symbol is equalised with (a tracking receiver's), the maximum taken per symbol; 0 = no decision."""
     xhat = np.asarray(xhat, dtype=np.complex128)
-    a0 = np.abs(np.asarray(y0))
-    with np.errstate(divide="ignore"):
-        bound = tol * np.maximum(1.0, np.abs(xhat)) * (a0.max() / a0)[None, :]
-    return (threshold_distance(bits_per_sc, xhat) <= bound) & (a0 > 0)[None, :]
+    a0 = np.atleast_2d(np.abs(np.asarray(y0)))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        bound = tol * np.maximum(1.0, np.abs(xhat)) * (a0.max(axis=-1, keepdims=True) / a0)
+    return (threshold_distance(bits_per_sc, xhat) <= bound) & (a0 > 0)
 
 
 def ber_per_bin(prof, bits_per_sc):
     """Bit error rate per subcarrier [pairs, n_snr, n_ch, N]; NaN on unloaded bins."""
-    d = prof.decisions.astype(np.float64) * int(bits_per_sc)
+    d = _decisions_like(prof.decisions, prof.bit_err) * int(bits_per_sc)
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(d > 0, prof.bit_err / np.where(d > 0, d, 1.0), np.nan)
 
@@ -110,9 +116,16 @@ def ber_per_bin(prof, bits_per_sc):
 def evm_db(prof):
     """Error-vector magnitude per subcarrier in dB relative to the constellation's unit average power:
     10 log10(err_power / decisions); NaN on unloaded bins."""
-    d = prof.decisions.astype(np.float64)
+    d = _decisions_like(prof.decisions, prof.err_power)
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(d > 0, 10.0 * np.log10(prof.err_power / np.where(d > 0, d, 1.0)), np.nan)
+
+
+def _decisions_like(dec, arr):
+    """The decisions as float64, broadcastable against ``arr`` [..., n]: [n] as they are; per point [points, n] (a tracking
+    receiver's) with the axes between the point's and the last of ``arr`` [points, ..., n] as ones"""
+    dec = np.asarray(dec).astype(np.float64)
+    return dec if dec.ndim == 1 else dec.reshape((dec.shape[0],) + (1,) * (np.ndim(arr) - 2) + (dec.shape[1],))
 
 
 # ---- fp64 host mirror ----
@@ -1242,19 +1255,19 @@ def bit_llrs(bits_per_sc, xhat, nu=1.0):
 def soft_penalties(bits_per_sc, X, xhat, nu, scales, on=None):
     """The penalties of ``wofdm_rx_profile_soft`` on a mirror's outputs: X [S - 1, N] the transmitted points of the data symbols,
     xhat [S - 1, N] the equalised values, nu [N] the noise variance the receiver assumes per bin, scales [n_scales]; on [N]: the
-    loaded bins (None: all).  Returns pen [n_scales, S - 1, N] = sum_i log2(1 + exp(-(1 - 2 b_i) c_j Lambda_i)), evaluated as
+    loaded bins (None: all) -- nu and on may also be [S - 1, N], per symbol.  Returns pen [n_scales, S - 1, N] = sum_i log2(1 + exp(-(1 - 2 b_i) c_j Lambda_i)), evaluated as
     max(-z, 0) + log1p(exp(-|z|)) over ln 2, b_i the bits of X's label (``slice_labels``); 0 on unloaded bins."""
     k = int(bits_per_sc)
     X = np.asarray(X, dtype=np.complex128)
-    on = np.ones(X.shape[-1], dtype=bool) if on is None else np.asarray(on).reshape(-1) != 0
-    nu = np.where(on, np.asarray(nu, dtype=np.float64), 1.0)
+    on = np.ones((1, X.shape[-1]), dtype=bool) if on is None else np.atleast_2d(np.asarray(on) != 0)
+    nu = np.where(on, np.atleast_2d(np.asarray(nu, dtype=np.float64)), 1.0)
     lab = slice_labels(k, X)
     sign = np.stack([1.0 - 2.0 * ((lab >> (k - 1 - i)) & 1) for i in range(k)], axis=-1)
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        z0 = sign * bit_llrs(k, np.where(on[None, :], xhat, 0.0), nu[None, :])          # [S - 1, N, k]
+        z0 = sign * bit_llrs(k, np.where(on, xhat, 0.0), nu)                            # [S - 1, N, k]
         z = np.asarray(scales, dtype=np.float64).reshape(-1)[:, None, None, None] * z0[None]
         pen = ((np.maximum(-z, 0.0) + np.log1p(np.exp(-np.abs(z)))) / np.log(2.0)).sum(axis=-1)
-    return np.where(on[None, None, :], pen, 0.0)
+    return np.where(on[None], pen, 0.0)
 
 
 def _soft_outputs(st, front, out, w_rx, snr_db, bits_per_sc, scales, noise_before_truncate):
@@ -1298,12 +1311,21 @@ def rx_profile_soft_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_d
     """The host route of ``rx_profile_soft_gpu``: ``rx_profile_link_host``'s frames and points (None: one all-off ``LinkPoint``),
     each also through ``frame_profile_soft``'s steps for the scales ``scales`` (None: ``SOFT_SCALES``).  Returns
     ``RxProfileSoft``; with_near=True: also the number of ``near_decisions`` per point and cell."""
+    return _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, scales, tracks,
+                       knot_step, aci_active, aci_h, ref_power, active, mask, noise_before_truncate, with_near)
+
+
+def _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, scales, tracks,
+                knot_step, aci_active, aci_h, ref_power, active, mask, noise_before_truncate, with_near, receiver=None):
+    """``rx_profile_soft_host``'s sweep; receiver(q: ``_Sweep``) -> per point a function (front, out, p, s) -> the frame's tuple
+    behind ``_link_point``'s outputs ``out`` in the place of the one-shot receiver's (``rx_profile_tracking_host``)"""
     from . import timefreq as T
     sc = _soft_scales(scales)
     points = [LinkPoint()] if points is None else points
 
     def arm(q):
         pts, tr, iact, hi, ref = _link_sides(st, q.hc, points, tracks, aci_active, aci_h, ref_power, q.w_tx.shape[0])
+        rec = None if receiver is None else receiver(q, len(pts), sc)
         B = st.sym_len - st.tail_tx
         nb = iact is not None and iact.any()
         lo = min(0, st.prefix_rm + min(pt.timing for pt in pts))
@@ -1318,13 +1340,16 @@ def rx_profile_soft_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_d
                 igrid = tab[gen_labels(st.n_fft, q.k, q.S + 1, seed, cell, fr, STREAM_ACI)] * (iact != 0)[None, :]
                 on_air = _aci_on_air(st, igrid, q.w_tx[p], q.hc[c] if hi is None else hi[c], 0.0, q.m)
             fronts = {}
-            for pt in pts:
+            for i, pt in enumerate(pts):
                 key = (pt.pa, pt.track)
                 if key not in fronts:
                     fronts[key] = _link_front(st, grid, noise_at, q.w_tx[p], q.hc[c], None if pt.track is None else tr[pt.track, c],
                                               knot_step, pt.pa, None if ref is None else ref[p], q.snr[s], q.act, q.m, q.nbt)
                 out = _link_point(st, *fronts[key], noise_at, q.w_rx[p], walk, on_air, pt, q.k)
-                yield out[:9] + _soft_outputs(st, fronts[key][0], out, q.w_rx[p], q.snr[s], q.k, sc, q.nbt)[1:]
+                if rec is None:
+                    yield out[:9] + _soft_outputs(st, fronts[key][0], out, q.w_rx[p], q.snr[s], q.k, sc, q.nbt)[1:]
+                else:
+                    yield rec[i](fronts[key][0], out, p, s)
         return (len(pts),), frame
     res = _host_sweep(_RxSoftSums, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames,
                       active, mask, noise_before_truncate, with_near, n_scales=sc.size)
@@ -1376,8 +1401,9 @@ def rx_profile_soft_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db
 def _soft_rates(pen, dec, k):
     """k - pen / dec along the scale axis (-2 of pen) and its maximum: (rate, index of the scale), NaN / 0 where dec is 0"""
     dec = np.asarray(dec, dtype=np.float64)
+    ok = dec > 0 if dec.ndim == 1 else (dec > 0)[..., None, :]         # (per point: the scale axis beside the others)
     with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(dec > 0, int(k) - pen / np.where(dec > 0, dec, 1.0)[..., None, :], np.nan)
+        r = np.where(ok, int(k) - pen / np.where(dec > 0, dec, 1.0)[..., None, :], np.nan)
     bad = np.isnan(r).all(axis=-2)
     idx = np.where(bad, 0, np.argmax(np.where(np.isnan(r), -np.inf, r), axis=-2))
     return np.where(bad, np.nan, np.take_along_axis(r, idx[..., None, :], axis=-2)[..., 0, :]), idx
@@ -1386,12 +1412,14 @@ def _soft_rates(pen, dec, k):
 def gmi_per_bin(prof, bits_per_sc):
     """The achievable rate per subcarrier in bit per decision, k - bit_penalty / decisions at the scale that maximises it (every
     scale gives an achievable rate): (rate, scale index) [points, pairs, n_snr, n_ch, N]; NaN (index 0) on unloaded bins."""
-    return _soft_rates(prof.bit_penalty, prof.decisions, bits_per_sc)
+    return _soft_rates(prof.bit_penalty, _decisions_like(prof.decisions, prof.bit_err), bits_per_sc)
 
 
 def gmi_per_symbol(prof, bits_per_sc):
     """The same per data symbol over the loaded bins: (rate, scale index) [points, pairs, n_snr, n_ch, S - 1]"""
     n_sym = prof.bit_penalty_sym.shape[-1]
+    if hasattr(prof, "decisions_sym"):
+        return _soft_rates(prof.bit_penalty_sym, _decisions_like(prof.decisions_sym, prof.bit_err_sym), bits_per_sc)
     dec = np.full(n_sym, float(prof.decisions.astype(np.float64).sum()) / n_sym)
     return _soft_rates(prof.bit_penalty_sym, dec, bits_per_sc)
 
@@ -1400,10 +1428,226 @@ def gmi(prof, bits_per_sc, per_bin_scale=True):
     """The achievable rate of a cell in bit per decision, the mean over its loaded bins: per_bin_scale=True with every bin at its
     own best scale -- (rate [points, pairs, n_snr, n_ch], scale index [..., N], as ``gmi_per_bin``'s) --, False with one scale for
     the cell, the best for its total penalty -- (rate [...], scale index [...])."""
-    on = prof.decisions > 0
+    per_point = prof.decisions.ndim == 2                               # (a tracking receiver's: the data bins are the call's)
+    on = (prof.decisions > 0).any(axis=0) if per_point else prof.decisions > 0
     if per_bin_scale:
         r, idx = gmi_per_bin(prof, bits_per_sc)
         return r[..., on].mean(axis=-1), idx
-    total = float(prof.decisions.astype(np.float64).sum())
-    r, idx = _soft_rates(prof.bit_penalty.sum(axis=-1, keepdims=True), np.array([total]), bits_per_sc)
+    total = prof.decisions.astype(np.float64).sum(axis=-1)
+    dec = _decisions_like(total[:, None], prof.bit_err) if per_point else np.array([float(total)])
+    r, idx = _soft_rates(prof.bit_penalty.sum(axis=-1, keepdims=True), dec, bits_per_sc)
     return r[..., 0], idx[..., 0]
+
+
+# ---- a receiver that tracks: comb pilots and a postamble (wofdm_rx_profile_tracking) ----
+
+TrackingPoint = collections.namedtuple("TrackingPoint", "cpe post", defaults=(0, 0))
+TrackingPoint.__doc__ = """The receiver of one point of ``wofdm_rx_profile_tracking``: cpe (1: the common phase of every data symbol
+is estimated from the comb of pilot bins and removed), post (1: symbol S - 1 is a postamble, a second known symbol, and the
+channel estimate is interpolated between the pilot and it; needs S >= 3).  (0, 0) is the one-shot receiver of every other call."""
+
+RxProfileTracking = collections.namedtuple("RxProfileTracking", _SOFT_SUMS[:-1] + ("scales", "decisions_sym", "decisions"))
+RxProfileTracking.__doc__ = """``RxProfileSoft``'s fields, with the decisions per point: decisions [points, N] = frames * (S - 1 -
+post) on the data bins -- loaded and no pilot --, 0 on the others; decisions_sym [points, S - 1]: the decisions a data symbol
+took per cell, frames * data bins, 0 for the postamble of a point with post."""
+
+
+def pilot_comb(active, spacing, first=0):
+    """[N] bool: every ``spacing``-th loaded bin of ``active`` [N] from the ``first`` loaded one on -- the comb of
+    ``wofdm_rx_profile_tracking``"""
+    act = np.asarray(active).reshape(-1) != 0
+    if int(spacing) < 1 or int(first) < 0:
+        raise ValueError("spacing must be >= 1 and first >= 0")
+    out = np.zeros(act.size, dtype=bool)
+    out[np.flatnonzero(act)[int(first)::int(spacing)]] = True
+    return out
+
+
+def tracking_equalise(X, Y, on, pilots, cpe, post):
+    """The definition of include/wofdm.h (``wofdm_rx_profile_tracking``) in double precision.  X, Y [S, N]: the transmitted points
+    and the DFT outputs of a frame; on [N]: the loaded bins; pilots [N] or None: the comb; cpe, post: the point's flags.  With t =
+    s / (S - 1) for the symbols s = 1 ... S - 1:
+      H0 = Y_0 / X_0 on the loaded bins; post: HL = Y_{S-1} / X_{S-1}, cL = sum_{n loaded} HL conj(H0), rho = cL / |cL| (1 if cL =
+      0), Hh_s = H0 + t (HL conj(rho) - H0); else Hh_s = H0;
+      cpe: c_s = sum_{p in pilots} Y_s[p] conj(Hh_s[p] X_s[p]), q_s = c_s / |c_s| (1 if c_s = 0); post alone: q_s = e^{i t arg rho};
+      neither: q_s = 1;
+      e = Y_s conj(q_s) / Hh_s.
+    Returns (e [S - 1, N], Hh [S - 1, N], q [S - 1]): e is 0 where no decision is taken -- unloaded bins, pilot bins, and with
+    post the row of symbol S - 1 --, Hh is 0 on the unloaded bins."""
+    X, Y = np.asarray(X, dtype=np.complex128), np.asarray(Y, dtype=np.complex128)
+    S, n = X.shape
+    on = np.asarray(on).reshape(-1) != 0
+    pil = np.zeros(n, dtype=bool) if pilots is None else np.asarray(pilots).reshape(-1) != 0
+    if Y.shape != (S, n) or on.shape != (n,) or pil.shape != (n,) or (pil & ~on).any():
+        raise ValueError("X, Y must be [S, N], on and pilots [N], and every pilot on a loaded bin")
+    if cpe not in (0, 1) or post not in (0, 1) or (post and S < 3) or (cpe and not pil.any()):
+        raise ValueError("flags must be 0 or 1, post needs S >= 3 and cpe a pilot bin")
+    t = np.arange(1, S, dtype=np.float64) / (S - 1)
+    H0 = np.zeros(n, dtype=np.complex128)
+    H0[on] = Y[0, on] / X[0, on]
+    Hh = np.tile(H0, (S - 1, 1))
+    rho = 1.0 + 0.0j
+    if post:
+        HL = np.zeros(n, dtype=np.complex128)
+        HL[on] = Y[S - 1, on] / X[S - 1, on]
+        cL = (HL[on] * np.conj(H0[on])).sum()
+        rho = cL / abs(cL) if cL != 0 else 1.0 + 0.0j
+        Hh = H0[None, :] + t[:, None] * (HL * np.conj(rho) - H0)[None, :]
+    q = np.ones(S - 1, dtype=np.complex128)
+    if cpe:
+        c = (Y[1:, pil] * np.conj(Hh[:, pil] * X[1:, pil])).sum(axis=1)
+        q = np.where(c != 0, c / np.where(c != 0, np.abs(c), 1.0), 1.0)
+    elif post:
+        q = np.exp(1j * t * np.angle(rho))
+    data = np.tile(on & ~pil, (S - 1, 1))
+    if post:
+        data[S - 2] = False
+    e = np.zeros((S - 1, n), dtype=np.complex128)
+    e[data] = (Y[1:] * np.conj(q)[:, None])[data] / Hh[data]
+    return e, Hh, q
+
+
+def _tracking_outputs(st, front, out, w_rx, snr_db, bits_per_sc, scales, noise_before_truncate, pilots, tp):
+    """The frame's tuple of a point behind ``_link_point``'s outputs ``out`` (Y last), with ``tracking_equalise`` in the one-shot
+    receiver's place: ``frame_profile_tracking``'s outputs.  The counters and the penalties are ``_point_outputs``' and
+    ``_soft_outputs``' statements on e, with nu_s[n] = v W2 / |Hh_s[n]|^2."""
+    X, conv, _, on = front
+    k, S, B = int(bits_per_sc), X.shape[0], st.sym_len - st.tail_tx
+    e, Hh, _ = tracking_equalise(X, out[-1], on, pilots, tp.cpe, tp.post)
+    pil = np.zeros(on.size, dtype=bool) if pilots is None else np.asarray(pilots).reshape(-1) != 0
+    data = np.tile(on & ~pil, (S - 1, 1))
+    if tp.post:
+        data[S - 2] = False
+    d = np.where(data, slice_labels(k, X[1:]) ^ slice_labels(k, e), 0)
+    bits = sum((d >> b) & 1 for b in range(k))
+    err = np.where(data, np.abs(e - X[1:]) ** 2, 0.0)
+    nl = conv.size if noise_before_truncate else S * B
+    v = np.mean(np.abs(conv[:nl]) ** 2) * 10.0 ** (-0.1 * float(snr_db))
+    w2 = float((np.asarray(w_rx, np.float64) ** 2).sum())
+    Hd = np.where(data, Hh, 0.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        nu = np.where(data, v * w2 / np.where(data, np.abs(Hh), 1.0) ** 2, 0.0)
+    pen = soft_penalties(k, X[1:], e, nu, scales, data)
+    return (bits.sum(axis=0).astype(np.uint64), (d != 0).sum(axis=0).astype(np.uint64), err.sum(axis=0), e, Hd,
+            bits.sum(axis=1).astype(np.uint64), (d != 0).sum(axis=1).astype(np.uint64), err.sum(axis=1), out[8], pen.sum(axis=1),
+            pen.sum(axis=2))
+
+
+def _tracking_prepare(st, syms, n_points, tracking, pilots, act):
+    """The tracking points (None: all (0, 0)), one per link point, and the comb [N] bool or None, checked as the library does"""
+    tps = [TrackingPoint()] * n_points if tracking is None else [TrackingPoint(*(int(v) for v in TrackingPoint(*q))) for q in tracking]
+    on = np.ones(st.n_fft, dtype=bool) if act is None else np.asarray(act).reshape(-1) != 0
+    pil = None if pilots is None else np.ascontiguousarray(np.asarray(pilots).reshape(-1) != 0)
+    if len(tps) != n_points:
+        raise ValueError("%d tracking points for %d link points" % (len(tps), n_points))
+    if pil is not None and (pil.shape != (st.n_fft,) or (pil & ~on).any()):
+        raise ValueError("pilots must hold %d flags, each on a loaded bin" % st.n_fft)
+    if not (on if pil is None else on & ~pil).any():
+        raise ValueError("the comb leaves no data bin")
+    for q in tps:
+        if q.cpe not in (0, 1) or q.post not in (0, 1) or (q.post and int(syms) < 3) or (q.cpe and (pil is None or not pil.any())):
+            raise ValueError("a tracking point needs flags 0 or 1, post S >= 3 and cpe a pilot bin: %r" % (q,))
+    return tps, pil
+
+
+def _tracking_decisions(st, syms, frames, act, pil, tps):
+    """decisions [points, N] and decisions_sym [points, S - 1] of ``RxProfileTracking``"""
+    on = np.ones(st.n_fft, dtype=bool) if act is None else np.asarray(act).reshape(-1) != 0
+    data = on & ~pil if pil is not None else on
+    S = int(syms)
+    dec = np.stack([np.where(data, int(frames) * (S - 1 - q.post), 0) for q in tps]).astype(np.uint64)
+    sym = np.full((len(tps), S - 1), int(frames) * int(data.sum()), dtype=np.uint64)
+    for i, q in enumerate(tps):
+        if q.post:
+            sym[i, S - 2] = 0
+    return dec, sym
+
+
+def _tracking_result(sums, scales, dec, sym):
+    return RxProfileTracking(*sums[:-1], scales, sym, dec)
+
+
+def frame_profile_tracking(st, grids, noise_at, w_tx, w_rx, h, point, tracking, snr_db, bits_per_sc, walk, pilots=None, scales=None,
+                           track=None, knot_step=None, ref_power=None, aci_grids=None, aci_h=None, active=None, mask=None,
+                           noise_before_truncate=1, with_y=False):
+    """fp64 host mirror of one frame and one point of ``wofdm_rx_profile_tracking``: ``frame_profile_soft``'s chain up to the DFT
+    outputs, then ``tracking_equalise`` with the comb ``pilots`` and the point's ``tracking`` = (cpe, post), then the slicer, the
+    error vector and the demapper on its e with nu_s[n] = v W2 / |Hh_s[n]|^2.  Returns (bit_err [N], sym_err [N], err_power [N], e
+    [S-1, N], Hh [S-1, N] -- 0 where no decision is taken --, bit_err_sym [S-1], sym_err_sym [S-1], err_power_sym [S-1], pa_power
+    [2], bit_penalty [n_scales, N], bit_penalty_sym [n_scales, S-1]); with_y=True: Y [S, N] as a twelfth."""
+    sc = _soft_scales(scales)
+    tps, pil = _tracking_prepare(st, np.asarray(grids).shape[0], 1, [tracking], pilots, active)
+    front, out = _frame_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, walk, track, knot_step, ref_power,
+                             aci_grids, aci_h, active, mask, noise_before_truncate)
+    res = _tracking_outputs(st, front, out, w_rx, snr_db, bits_per_sc, sc, noise_before_truncate, pil, tps[0])
+    return res + ((out[9],) if with_y else ())
+
+
+def rx_profile_tracking_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                             tracking=None, pilots=None, scales=None, tracks=None, knot_step=None, aci_active=None, aci_h=None,
+                             ref_power=None, active=None, mask=None, noise_before_truncate=1, with_near=False):
+    """The host route of ``rx_profile_tracking_gpu``: ``rx_profile_soft_host``'s frames and points, each through
+    ``frame_profile_tracking``'s steps with the comb ``pilots`` [N] (None: none) and the point's ``TrackingPoint`` of ``tracking``
+    (None: all (0, 0)).  Returns ``RxProfileTracking``; with_near=True: also the number of ``near_decisions`` per point and cell,
+    the rule's weight being max_n |Hh_s| / |Hh_s[n]| per symbol."""
+    held = {}
+
+    def receiver(q, n_points, sc):
+        tps, pil = _tracking_prepare(st, q.S, n_points, tracking, pilots, q.act)
+        held.update(tps=tps, pil=pil, act=q.act)
+        return [lambda front, out, p, s, tp=tp: _tracking_outputs(st, front, out, q.w_rx[p], q.snr[s], q.k, sc, q.nbt, pil, tp)
+                for tp in tps]
+    res = _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, scales, tracks,
+                      knot_step, aci_active, aci_h, ref_power, active, mask, noise_before_truncate, with_near, receiver)
+    soft = res[0] if with_near else res
+    dec, sym = _tracking_decisions(st, syms, frames, held["act"], held["pil"], held["tps"])
+    prof = RxProfileTracking(*soft[:-1], sym, dec)
+    return (prof, res[1]) if with_near else prof
+
+
+def rx_profile_tracking_chunk_frames(st, syms, masked, n_points, neighbour, n_scales):
+    """Frames one chunk of ``wofdm_rx_profile_tracking`` holds: ``rx_profile_soft_chunk_frames``' -- the receiver has no per-frame
+    buffers of its own"""
+    return rx_profile_soft_chunk_frames(st, syms, masked, n_points, neighbour, n_scales)
+
+
+def rx_profile_tracking_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                            tracking=None, pilots=None, scales=None, tracks=None, knot_step=None, aci_active=None, aci_h=None,
+                            ref_power=None, active=None, mask=None, noise_before_truncate=1, device=0, out=None):
+    """``wofdm_rx_profile_tracking``: ``rx_profile_soft_gpu`` of the same arguments behind a receiver that tracks -- ``pilots`` [N]
+    (None: no comb; ``pilot_comb``) and one ``TrackingPoint`` (or (cpe, post)) per point in ``tracking`` (None: all (0, 0), and
+    then without a comb the soft call's bytes).  Pilot bins count nothing on any point, the postamble of a point with post
+    nothing on that point.  Returns ``RxProfileTracking``; ``out`` (an earlier result of the same shape and scales) is
+    accumulated into.  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    sc = _soft_scales(scales)
+    points = [LinkPoint()] if points is None else points
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts, tr, iact, hi, ref = _link_sides(st, prepared[2], points, tracks, aci_active, aci_h, ref_power, prepared[0].shape[0])
+    tps, pil = _tracking_prepare(st, syms, len(pts), tracking, pilots, prepared[4])
+    trf = None if tr is None else _lib.c64_as_f32(tr)
+    hif = None if hi is None else _lib.c64_as_f32(hi)
+    lin = PaPoint(PA_LINEAR, 0.0)
+    cpts = (_lib.LinkPoint * len(pts))(*[
+        _lib.LinkPoint(*(q.pa or lin), -1 if q.track is None else q.track, q.timing, q.cfo, q.cfo_tracked, q.linewidth, q.cpe_tracked,
+                       int(q.aci is not None), *(q.aci or (0, 0.0)), (C.c_int32 * 4)(0, 0, 0, 0)) for q in pts])
+    ctps = (_lib.TrackingPoint * len(tps))(*[_lib.TrackingPoint(q.cpe, q.post, (C.c_int32 * 2)(0, 0)) for q in tps])
+    pil8 = None if pil is None else np.ascontiguousarray(pil, dtype=np.uint8)
+    knots = (0, 0, 0) if tr is None else (tr.shape[0], tr.shape[2], int(knot_step))
+    prev = None
+    if out is not None:
+        if not np.array_equal(out.scales, sc):
+            raise ValueError("out has other scales")
+        prev = _RxSoftSums(*out[:-3], np.zeros(st.n_fft, dtype=np.uint64))
+    res = _gpu_call("wofdm_rx_profile_tracking", _RxSoftSums, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                    noise_before_truncate, device, prev, lead=(len(pts),), n_scales=sc.size,
+                    after_mask=(None if trf is None else trf.ctypes.data, *knots, None if iact is None else iact.ctypes.data,
+                                None if hif is None else hif.ctypes.data, None if ref is None else ref.ctypes.data, len(pts), cpts,
+                                int(sc.size), sc.ctypes.data, None if pil8 is None else pil8.ctypes.data, ctps))
+    dec, sym = _tracking_decisions(st, syms, frames, prepared[4], pil, tps)
+    if out is not None:
+        if out.decisions.shape != dec.shape:
+            raise ValueError("out has another shape")
+        dec, sym = out.decisions + dec, out.decisions_sym + sym
+    return _tracking_result(res, sc, dec, sym)
