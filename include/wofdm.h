@@ -921,6 +921,99 @@ int wofdm_rx_profile_tracking(const wofdm_cfg *cfg, int device,
                               double *bit_penalty,          /* [n_points][cells][n_scales][n_fft], ACCUMULATED into */
                               double *sym_penalty);         /* [n_points][cells][n_scales][S-1], or NULL */
 
+/* The CODED link: wofdm_rx_profile_tracking with an 8-bit soft-bit interface behind the demapper and a K = 7 Viterbi decoder behind
+ * that.  The GMI of the calls above is a bound for an ideal code at the best metric scale; a receiver with a fixed-point demapper
+ * and a real decoder falls short of it by an amount that depends on where in the band and in the frame the bad soft bits sit.
+ *   Soft bit.  For a point, a frame, a data symbol s, a data bin n (loaded, no pilot bin) and label bit i (0 = the top bit), z_i
+ * = (1 - 2 b_i) Lambda_i is what the demapper forms in single precision -- e and nu the tracking receiver's; the scales do not
+ * enter --, and d = clamp(rint(llr_scale z_i), -127, 127), round half even, an int8; NaN gives 0.  d > 0: the demapper agrees
+ * with the transmitted bit.  This is the random-coset view: the Philox labels are the scrambler, the transmitted codeword is all
+ * zero, and the frames are those of every other entry point.  Unloaded bins, pilot bins and the postamble of a point with post
+ * hold 0.
+ *   Order.  A symbol's position j = r k + i, r the rank of bin n among the data bins ascending; n_c = k D, D the data bins.  The
+ * interleaver perm [n_c] is a permutation of 0 ... n_c - 1: coded-stream index c reads position perm[c]; NULL is the identity.
+ *   Code.  K = 7, generators 133 / 171 octal: register r_t = (u_t << 6) | s_{t-1}, state s_{t-1} = (u_{t-1} ... u_{t-6}) with
+ * u_{t-1} in bit 5; A_t = parity(r_t & 0133), B_t = parity(r_t & 0171); s_t = (u_t << 5) | (s_{t-1} >> 1).  The predecessors of
+ * state s are p0 = (s << 1) & 63 and p1 = p0 | 1, its input bit s >> 5.  Free distance 10.
+ *   Rates, by the pattern index t mod period:   rate 0 = 1/2: A and B always;   rate 1 = 2/3: A 1 1, B 1 0;   rate 2 = 3/4: A 1 1 0,
+ * B 1 0 1.  The kept outputs of step t, A before B, t ascending, consume c = 0, 1, 2, ...; T = wofdm_code_steps(rate, n_c) is the
+ * largest T whose kept outputs number at most n_c (n_c = 56: 28 / 37 / 42; 57: 28 / 38 / 42; 64: 32 / 42 / 48; 6144: 3072 / 4096 /
+ * 4608), left-over positions are ignored.  One zero-terminated codeword per point, frame and data symbol: the last 6 steps are the
+ * tail, and T >= 7.
+ *   Decoder.  Pure integer arithmetic: the metric to minimise is the sum of d over the kept outputs whose hypothesised coded bit
+ * is 1, int32 throughout.  Only paths from state 0 are considered (2^30 on the other states at t = 0, which is equivalent for
+ * every T here); the survivor into a state is p0 unless p1's metric is strictly smaller; the traceback starts from state 0 at
+ * step T.  A decoded u_t != 0 for t < T - 6 is an info-bit error, any u_t != 0 a codeword error.  One wave per codeword, one
+ * state per lane; the survivors stay in LDS.
+ *   The call takes every argument of wofdm_rx_profile_tracking through `tracking`, then llr_scale, perm, and 1 <= n_codes <=
+ * WOFDM_CODE_MAX codes, all decoded from the same soft bits; then the seven outputs, which are wofdm_rx_profile_tracking's bytes;
+ * then code_errs[point][cell][code][s - 1] = {info-bit errors, codeword errors}, ACCUMULATED into; then soft_bits[cell][frame]
+ * [point][s - 1][n][8] (bytes k ... 7 are 0), or NULL -- overwritten, not accumulated, chunk by chunk as the call goes.  A point
+ * with post adds nothing for symbol S - 1.
+ *   Identities, by bytes: the counters are integers added by integer atomics, so code_errs depends neither on where a chunk ends,
+ * nor on the other points or codes of the call, nor on whether soft_bits is requested; repeated calls are identical.
+ *   Checks: wofdm_rx_profile_tracking's, then in this order WOFDM_E_INVALID for NULL codes or code_errs; llr_scale not finite or
+ * not positive; n_codes < 1 (WOFDM_E_UNSUPPORTED for n_codes > WOFDM_CODE_MAX); code by code a rate outside {0, 1, 2}, reserved not
+ * 0, T < 7; perm not a permutation; and WOFDM_E_UNSUPPORTED for soft_bits of more than 2^30 bytes.  Every argument is checked
+ * before the device is touched; a failed check leaves all outputs as they were.  (A device failure in a later chunk leaves
+ * soft_bits holding the earlier chunks' blocks: it is copied as the call goes; every other output is written at the end.)
+ *   Chunks: wofdm_rx_profile_tracking's formula plus 8 n_points (S - 1) n_fft bytes per frame, the soft bits.
+ *   A successful call holds the launch gate and counts for wofdm_rx_profile_kernel_ms (with soft_bits, the copies included).
+ *   Measured on an MI355X (tools/bench_rx_profile_coded.py, profiles/rx_profile_coded.txt): on 64 cells x 2000 frames x 16 symbols
+ * at n_fft = 256, 16-QAM, one point behind the (1, 1) receiver and a comb on every eighth loaded bin (n_c = 448), the tracking
+ * call takes 104.9 ms of kernels, this call 130.5 ms with one code and 182.2 ms with three (masked 133.5, 148.4 and 200.2 ms):
+ * 25.9 ms per code, 0.25 (masked 0.19) of a tracking call; the soft-bit stores cost nothing measurable.  Other n_fft: not measured. */
+#define WOFDM_CODE_MAX 4
+#define WOFDM_CODE_MAX_STEPS 4608                          /* wofdm_viterbi_decode: the most steps of a codeword         */
+typedef struct wofdm_code {
+    int32_t rate;                                          /* 0: 1/2, 1: 2/3, 2: 3/4                                     */
+    int32_t reserved[3];                                   /* 0                                                          */
+} wofdm_code;
+int wofdm_rx_profile_coded(const wofdm_cfg *cfg, int device,
+                           const float *w_tx,               /* [pairs][P] */
+                           const float *w_rx,               /* [pairs][N+tail_rx] */
+                           const float *h,                  /* [n_channels][n_taps][2] */
+                           const float *snr_db,             /* [n_snr] */
+                           const uint8_t *active,           /* [n_fft] or NULL */
+                           const float *tx_mask,            /* [2P-1] or NULL */
+                           const float *h_track,            /* [n_tracks][n_channels][n_knots][n_taps][2], or NULL */
+                           int32_t n_tracks, int32_t n_knots, int32_t knot_step,
+                           const uint8_t *aci_active,       /* [n_fft], or NULL */
+                           const float *aci_h,              /* [n_channels][n_taps][2], or NULL = h */
+                           const float *ref_power,          /* [pairs], or NULL */
+                           int32_t n_points, const wofdm_link_point *points,
+                           int32_t n_scales, const float *scales,
+                           const uint8_t *pilots,           /* [n_fft], or NULL */
+                           const wofdm_tracking_point *tracking, /* [n_points] */
+                           float llr_scale,
+                           const int32_t *perm,             /* [n_c], or NULL */
+                           int32_t n_codes, const wofdm_code *codes,
+                           uint64_t *errs,                  /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                           double *err_power,               /* [n_points][cells][n_fft], or NULL */
+                           uint64_t *sym_errs,              /* [n_points][cells][S-1][2], or NULL */
+                           double *sym_power,               /* [n_points][cells][S-1], or NULL */
+                           double *pa_power,                /* [n_points][cells][2], or NULL */
+                           double *bit_penalty,             /* [n_points][cells][n_scales][n_fft], ACCUMULATED into */
+                           double *sym_penalty,             /* [n_points][cells][n_scales][S-1], or NULL */
+                           uint64_t *code_errs,             /* [n_points][cells][n_codes][S-1][2], ACCUMULATED into */
+                           int8_t *soft_bits);              /* [cells][frames][n_points][S-1][n_fft][8], or NULL */
+
+/* Host only: the steps T of a codeword of rate 0, 1 or 2 over n_c coded-stream positions (above); WOFDM_E_INVALID otherwise. */
+int wofdm_code_steps(int32_t rate, int32_t n_c);
+
+/* The decoder alone, on soft bits of the caller's: n_cw codewords of n_c soft bits each, d > 0 for a coded bit 0, any int8
+ * (-128 included); coded-stream index c of a codeword reads soft[cw][perm[c]] (NULL: c).  bits[cw][t], t < T =
+ * wofdm_code_steps(rate, n_c), are the decoded u_t, the tail included; metric[cw] the survivor's metric at state 0.  It decodes
+ * any codeword, not only the all-zero one.  WOFDM_E_INVALID: NULL soft or bits, a rate outside {0, 1, 2}, n_c or n_cw < 1, T < 7,
+ * perm not a permutation; WOFDM_E_UNSUPPORTED: T > WOFDM_CODE_MAX_STEPS.  Checked before the device is touched.  The call
+ * holds the launch gate while its kernel runs; it neither counts for nor resets wofdm_rx_profile_kernel_ms. */
+int wofdm_viterbi_decode(int device, int32_t rate, int32_t n_c,
+                         const int32_t *perm,               /* [n_c], or NULL */
+                         int32_t n_cw,
+                         const int8_t *soft,                /* [n_cw][n_c] */
+                         uint8_t *bits,                     /* [n_cw][T] */
+                         int32_t *metric);                  /* [n_cw], or NULL */
+
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

@@ -40,6 +40,9 @@ PN_MAX_POINTS = 16
 LINK_MAX_POINTS = 16
 #: wofdm_rx_profile_soft (include/wofdm.h): most scales one call takes
 SOFT_MAX_SCALES = 16
+#: wofdm_rx_profile_coded, wofdm_viterbi_decode (include/wofdm.h): most codes one call takes, most steps of a codeword
+CODE_MAX = 4
+CODE_MAX_STEPS = 4608
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -54,6 +57,7 @@ EXPORTS = (
     "wofdm_rx_profile_aci", "wofdm_rx_profile_sync", "wofdm_rx_profile_doppler",
     "wofdm_rx_profile_pa", "wofdm_tx_psd_batch_pa", "wofdm_rx_profile_pn",
     "wofdm_rx_profile_link", "wofdm_rx_profile_soft", "wofdm_rx_profile_tracking",
+    "wofdm_rx_profile_coded", "wofdm_code_steps", "wofdm_viterbi_decode",
 )
 
 
@@ -119,6 +123,11 @@ class LinkPoint(C.Structure):
 class TrackingPoint(C.Structure):
     """Mirror of ``wofdm_tracking_point`` (16 bytes)."""
     _fields_ = [("cpe", C.c_int32), ("post", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class Code(C.Structure):
+    """Mirror of ``wofdm_code`` (16 bytes)."""
+    _fields_ = [("rate", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class Dump(C.Structure):
@@ -205,6 +214,12 @@ def load():
                                         C.POINTER(LinkPoint), i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_rx_profile_tracking.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
                                             C.POINTER(LinkPoint), i32, vp, vp, C.POINTER(TrackingPoint), vp, vp, vp, vp, vp, vp, vp]
+    L.wofdm_rx_profile_coded.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
+                                         C.POINTER(LinkPoint), i32, vp, vp, C.POINTER(TrackingPoint), C.c_float, vp, i32,
+                                         C.POINTER(Code), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.wofdm_code_steps.argtypes = [i32, i32]
+    L.wofdm_code_steps.restype = C.c_int
+    L.wofdm_viterbi_decode.argtypes = [C.c_int, i32, i32, vp, i32, vp, vp, vp]
     L.wofdm_tx_psd_batch_pa.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, C.POINTER(PaPoint), vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L

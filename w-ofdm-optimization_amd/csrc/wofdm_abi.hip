@@ -1685,6 +1685,11 @@ struct rx_call {
     struct { bool on; int32_t n_scales; const float *scales; double *bit_penalty, *sym_penalty; } soft;
     // the tracking receiver of wofdm_rx_profile_tracking: the comb (may be null) and a tracking point per link point
     struct { bool on; const uint8_t *pilots; const wofdm_tracking_point *points; } trk;
+    // the coded link of wofdm_rx_profile_coded: the quantiser's scale, the interleaver (may be null), the codes, the counters
+    // and (may be null) the soft bits themselves
+    struct {
+        bool on; float llr_scale; const int32_t *perm; int32_t n_codes; const wofdm_code *codes; uint64_t *code_errs; int8_t *soft_bits;
+    } code;
 };
 
 // the receive side's geometry beside the Tx chain's, and the cells of the call
@@ -1709,9 +1714,14 @@ struct rx_run {
     std::vector<float> asat;
     std::vector<uint8_t> pil;         // the comb as 0 / 1, empty without one
     std::vector<wofdm_tpoint> tp;
+    std::vector<int32_t> gather;      // the coded link: byte 8 n + i of coded-stream index c in a symbol's soft bits
+    int32_t csteps[WOFDM_CODE_CODES];
     int n_knots, knot_step;
     // device
-    size_t chunk, n_out, n_sym, n_ptot, n_bpen, n_spen;
+    size_t chunk, n_out, n_sym, n_ptot, n_bpen, n_spen, n_cerr;
+    dev_buf<int8_t> d_sbits;
+    dev_buf<int32_t> d_gather;
+    dev_buf<unsigned long long> d_cerrs;
     tx_shared sh;
     tx_chain tx, nbtx;
     dev_buf<float> d_wr, d_nlin, d_ppow, d_spow, d_asat, d_pwr, d_w2, d_bpart, d_spart;
@@ -1979,6 +1989,61 @@ int prep_track(rx_run &r)
     return WOFDM_OK;
 }
 
+// the largest T whose kept outputs number at most n_c (include/wofdm.h): rate 1/2 keeps 2 per step; 2/3 (A 1 1, B 1 0) 3 per
+// period of 2, 2 in its first step; 3/4 (A 1 1 0, B 1 0 1) 4 per period of 3, 2 in its first step and 1 in its second
+int32_t code_steps(int32_t rate, int64_t n_c)
+{
+    if (rate == 0) return (int32_t)(n_c / 2);
+    if (rate == 1) return (int32_t)(2 * (n_c / 3) + (n_c % 3 == 2 ? 1 : 0));
+    const int64_t rem = n_c % 4;
+    return (int32_t)(3 * (n_c / 4) + (rem >= 3 ? 2 : (rem == 2 ? 1 : 0)));
+}
+
+bool is_permutation(const int32_t *perm, int64_t n)
+{
+    std::vector<uint8_t> seen((size_t)n, 0);
+    for (int64_t c = 0; c < n; ++c) {
+        if (perm[c] < 0 || perm[c] >= n || seen[(size_t)perm[c]]) return false;
+        seen[(size_t)perm[c]] = 1;
+    }
+    return true;
+}
+
+// the coded link, in the order include/wofdm.h documents; leaves the gather table of a symbol's soft bits: coded-stream index c
+// reads position j = perm[c] = r k + i, bit i of the r-th data bin n, at byte 8 n + i
+int prep_code(rx_run &r)
+{
+    const auto &cd = r.c.code;
+    if (!cd.on) return WOFDM_OK;
+    if (!cd.codes || !cd.code_errs) return fail(WOFDM_E_INVALID, "NULL argument (codes or code_errs)");
+    if (!std::isfinite(cd.llr_scale) || !(cd.llr_scale > 0.f)) return fail(WOFDM_E_INVALID, "llr_scale must be finite and positive");
+    if (cd.n_codes < 1) return fail(WOFDM_E_INVALID, "n_codes=%d must be >= 1", cd.n_codes);
+    if (cd.n_codes > WOFDM_CODE_MAX) return fail(WOFDM_E_UNSUPPORTED, "n_codes=%d exceeds %d", cd.n_codes, WOFDM_CODE_MAX);
+    const int N = r.g.N, k = r.g.k;
+    std::vector<int32_t> bins;
+    for (int n = 0; n < N; ++n)
+        if ((r.act.empty() || r.act[(size_t)n] != 0) && (r.pil.empty() || r.pil[(size_t)n] == 0)) bins.push_back(n);
+    const int32_t n_c = k * (int32_t)bins.size();
+    for (int i = 0; i < cd.n_codes; ++i) {
+        const wofdm_code &q = cd.codes[i];
+        if (q.rate < 0 || q.rate > 2) return fail(WOFDM_E_INVALID, "codes[%d].rate=%d must be 0, 1 or 2", i, q.rate);
+        if (q.reserved[0] != 0 || q.reserved[1] != 0 || q.reserved[2] != 0) return fail(WOFDM_E_INVALID, "codes[%d].reserved must be 0", i);
+        r.csteps[i] = code_steps(q.rate, n_c);
+        if (r.csteps[i] < 7)
+            return fail(WOFDM_E_INVALID, "codes[%d]: %d coded bits per symbol give %d steps, at least 7 are needed", i, n_c, r.csteps[i]);
+    }
+    if (cd.perm && !is_permutation(cd.perm, n_c)) return fail(WOFDM_E_INVALID, "perm is not a permutation of 0 ... %d", n_c - 1);
+    const uint64_t bytes = r.g.cells * r.g.frames * (uint64_t)r.c.n_points * (uint64_t)(r.g.S - 1) * (uint64_t)N * 8;
+    if (cd.soft_bits && bytes > (1ull << 30))
+        return fail(WOFDM_E_UNSUPPORTED, "soft_bits of %llu bytes exceed 2^30", (unsigned long long)bytes);
+    r.gather.resize((size_t)n_c);
+    for (int32_t c = 0; c < n_c; ++c) {
+        const int32_t j = cd.perm ? cd.perm[c] : c;
+        r.gather[(size_t)c] = 8 * bins[(size_t)(j / k)] + j % k;
+    }
+    return WOFDM_OK;
+}
+
 // The taps as the kernels read them.  Of moving channels the knots, [n_tracks][n_channels][n_knots][WOFDM_LT], zero padded, and
 // behind them the static track where the call has one: h at every knot (without a track of the caller's, two knots that cover
 // every sample).  Without either, h as it is -- the static track of one knot.
@@ -2015,7 +2080,8 @@ uint64_t rx_job_bytes(const rx_run &r)
     if (c.pn.on) words += S * B;                                          // the unit phase walk
     if (r.nb) words += (S + 1) * N + (T + B) + (S + 1) * Lm;              // the neighbour's chain of S + 1 symbols
     // the demapper: per point and scale the penalties of every data symbol's bins and the symbols' sums, fp32
-    return 8 * words + (c.soft.on ? 4 * NP * (uint64_t)c.soft.n_scales * ((S - 1) * N + S) : 0);
+    // the coded link: 8 bytes of soft bits per point, data symbol and bin (the decoder's survivors are in LDS)
+    return 8 * words + (c.soft.on ? 4 * NP * (uint64_t)c.soft.n_scales * ((S - 1) * N + S) : 0) + (c.code.on ? 8 * NP * (S - 1) * N : 0);
 }
 
 // ---- the stages' device side: allocation, upload, and the stage's parameters in the chunk ----
@@ -2147,6 +2213,28 @@ int stage_track(rx_run &r)
     return WOFDM_OK;
 }
 
+// the coded link's side: the chunk's soft bits, the gather table, the counters
+int stage_code(rx_run &r)
+{
+    const auto &cd = r.c.code;
+    if (!cd.on) return WOFDM_OK;
+    const rx_geom &g = r.g;
+    if (!r.d_sbits.alloc(r.chunk * (size_t)r.c.n_points * (g.S - 1) * g.N * 8) || !r.d_gather.alloc(r.gather.size()) ||
+        !r.d_cerrs.alloc(r.n_cerr))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (coded link)");
+    if (!r.d_gather.upload(r.gather.data(), r.gather.size()) || hipMemset(r.d_cerrs, 0, r.n_cerr * 8) != hipSuccess)
+        return fail(WOFDM_E_HIP, "upload failed");
+    wofdm_codeparams &k = r.ck.cd;
+    k.llr_scale = cd.llr_scale; k.soft = r.d_sbits; k.gather = r.d_gather; k.n_c = (int32_t)r.gather.size(); k.n_codes = cd.n_codes;
+    for (int i = 0; i < cd.n_codes; ++i) {
+        k.rate[i] = cd.codes[i].rate;
+        k.steps[i] = r.csteps[i];
+    }
+    k.errs = r.d_cerrs;
+    r.ck.code_on = true;
+    return WOFDM_OK;
+}
+
 // the neighbour's side of the chunk: allocation, channels, and the Tx chain of its S + 1 symbols on the victim's windows and mask
 int stage_nb(rx_run &r)
 {
@@ -2190,7 +2278,7 @@ int rx_profile_run(const rx_call &c)
         (rc = check_allocation(c.active, r.g.N, &r.act)) != WOFDM_OK || (rc = prep_nb(r)) != WOFDM_OK ||
         (rc = prep_sync(r)) != WOFDM_OK || (rc = prep_pn(r)) != WOFDM_OK || (rc = check_knots(r)) != WOFDM_OK ||
         (rc = prep_link(r)) != WOFDM_OK || (rc = prep_amp(r)) != WOFDM_OK || (rc = prep_track(r)) != WOFDM_OK ||
-        (rc = use_device(c.device)) != WOFDM_OK)
+        (rc = prep_code(r)) != WOFDM_OK || (rc = use_device(c.device)) != WOFDM_OK)
         return rc;
     g_rxprof_ms = 0.f;
     const rx_geom &g = r.g;
@@ -2204,25 +2292,33 @@ int rx_profile_run(const rx_call &c)
     r.n_ptot = c.amp.on ? NP * g.cells * 2 : 0;
     r.n_bpen = NP * g.cells * NSC * g.N;
     r.n_spen = NP * g.cells * NSC * (g.S - 1);
+    r.n_cerr = c.code.on ? NP * g.cells * (size_t)c.code.n_codes * (g.S - 1) * 2 : 0;
     if ((rc = stage_base(r)) != WOFDM_OK || (rc = stage_points(r)) != WOFDM_OK || (rc = stage_amp(r)) != WOFDM_OK ||
         (rc = stage_pn(r)) != WOFDM_OK || (rc = stage_link(r)) != WOFDM_OK || (rc = stage_soft(r)) != WOFDM_OK ||
-        (rc = stage_track(r)) != WOFDM_OK || (rc = stage_nb(r)) != WOFDM_OK)
+        (rc = stage_track(r)) != WOFDM_OK || (rc = stage_code(r)) != WOFDM_OK || (rc = stage_nb(r)) != WOFDM_OK)
         return rc;
     // (a neighbour that loads no bin: the plain kernel)
     r.ck.arm = c.arm == RXP_ACI && !r.nb ? RXP_PLAIN : c.arm;
     std::vector<unsigned long long> herr(2 * r.n_out), hserr(2 * r.n_sym);
+    std::vector<unsigned long long> hcerr(r.n_cerr);
     std::vector<double> hpow(r.n_out), hspow(r.n_sym), hptot(r.n_ptot), hbpen(r.n_bpen), hspen(r.n_spen);
     float ms = 0.f;
     hipError_t e = hipSuccess;
     const wofdm_link_fns *ax = wofdm_aux_link(g.N);
+    // (the coded link's soft bits, where the caller wants them: the items are [cell][frame], so a chunk's block is contiguous
+    // in the caller's array, and its copy waits for the chunk)
+    const size_t item_bytes = c.code.on ? NP * (size_t)(g.S - 1) * g.N * 8 : 0;
     rc = run_chunks(items, r.chunk, [&](uint64_t item0, int32_t n_jobs) {
         r.ck.tx.item0 = r.ck.nb.item0 = r.ck.r.item0 = item0;
         r.ck.tx.n_jobs = r.ck.nb.n_jobs = r.ck.r.n_jobs = n_jobs;
-        return ax ? ax->rx_profile_chunk(&r.ck, nullptr) : hipErrorInvalidValue;
+        hipError_t le = ax ? ax->rx_profile_chunk(&r.ck, nullptr) : hipErrorInvalidValue;
+        if (le == hipSuccess && c.code.on && c.code.soft_bits)
+            le = hipMemcpy(c.code.soft_bits + item0 * item_bytes, r.d_sbits.p, (size_t)n_jobs * item_bytes, hipMemcpyDeviceToHost);
+        return le;
     }, &e, &ms);
     if (rc != WOFDM_OK) return rc;
     if (e != hipSuccess || !fetch(herr, r.d_errs.p) || !fetch(hpow, r.d_pow.p) || !fetch(hserr, r.d_serrs.p) || !fetch(hspow, r.d_stot.p) ||
-        !fetch(hptot, r.d_ptot.p) || !fetch(hbpen, r.d_btot.p) || !fetch(hspen, r.d_sptot.p))
+        !fetch(hptot, r.d_ptot.p) || !fetch(hbpen, r.d_btot.p) || !fetch(hspen, r.d_sptot.p) || !fetch(hcerr, r.d_cerrs.p))
         return fail(WOFDM_E_HIP, "receive-profile kernels or copy-back failed: %s",
                     hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
     add_to(c.errs, herr);
@@ -2232,6 +2328,7 @@ int rx_profile_run(const rx_call &c)
     add_to(c.amp.pa_power, hptot);
     add_to(c.soft.bit_penalty, hbpen);
     add_to(c.soft.sym_penalty, hspen);
+    add_to(c.code.code_errs, hcerr);
     g_rxprof_ms = ms;
     return WOFDM_OK;
 }
@@ -2380,12 +2477,14 @@ int wofdm_rx_profile_soft(const wofdm_cfg *cfg, int device, const float *w_tx, c
     return rc != WOFDM_OK ? rc : rx_profile_run(c);
 }
 
-int wofdm_rx_profile_tracking(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
-                              const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
-                              int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
-                              const wofdm_link_point *points, int32_t n_scales, const float *scales, const uint8_t *pilots,
-                              const wofdm_tracking_point *tracking, uint64_t *errs, double *err_power, uint64_t *sym_errs,
-                              double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty)
+// wofdm_rx_profile_tracking and, with the coded link behind it (code, or null), wofdm_rx_profile_coded: one call, filled once
+static int rx_tracking_call(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                            const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                            int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
+                            const wofdm_link_point *points, int32_t n_scales, const float *scales, const uint8_t *pilots,
+                            const wofdm_tracking_point *tracking, uint64_t *errs, double *err_power, uint64_t *sym_errs,
+                            double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty,
+                            const decltype(rx_call::code) *code)
 {
     if (!scales || !bit_penalty || !tracking) return fail(WOFDM_E_INVALID, "NULL argument (scales, bit_penalty or tracking)");
     if (n_scales < 1) return fail(WOFDM_E_INVALID, "n_scales=%d must be >= 1", n_scales);
@@ -2400,8 +2499,81 @@ int wofdm_rx_profile_tracking(const wofdm_cfg *cfg, int device, const float *w_t
     c.amp = {false, false, nullptr, ref_power, pa_power};
     c.soft = {true, n_scales, scales, bit_penalty, sym_penalty};
     c.trk = {true, pilots, tracking};
+    if (code) c.code = *code;
     const int rc = rx_link_stages(c, n_points, points);
     return rc != WOFDM_OK ? rc : rx_profile_run(c);
+}
+
+int wofdm_rx_profile_tracking(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                              const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                              int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
+                              const wofdm_link_point *points, int32_t n_scales, const float *scales, const uint8_t *pilots,
+                              const wofdm_tracking_point *tracking, uint64_t *errs, double *err_power, uint64_t *sym_errs,
+                              double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty)
+{
+    return rx_tracking_call(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active, aci_h,
+                            ref_power, n_points, points, n_scales, scales, pilots, tracking, errs, err_power, sym_errs, sym_power,
+                            pa_power, bit_penalty, sym_penalty, nullptr);
+}
+
+int wofdm_rx_profile_coded(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                           const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                           int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
+                           const wofdm_link_point *points, int32_t n_scales, const float *scales, const uint8_t *pilots,
+                           const wofdm_tracking_point *tracking, float llr_scale, const int32_t *perm, int32_t n_codes,
+                           const wofdm_code *codes, uint64_t *errs, double *err_power, uint64_t *sym_errs, double *sym_power,
+                           double *pa_power, double *bit_penalty, double *sym_penalty, uint64_t *code_errs, int8_t *soft_bits)
+{
+    const decltype(rx_call::code) code = {true, llr_scale, perm, n_codes, codes, code_errs, soft_bits};
+    return rx_tracking_call(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active, aci_h,
+                            ref_power, n_points, points, n_scales, scales, pilots, tracking, errs, err_power, sym_errs, sym_power,
+                            pa_power, bit_penalty, sym_penalty, &code);
+}
+
+int wofdm_code_steps(int32_t rate, int32_t n_c)
+{
+    if (rate < 0 || rate > 2 || n_c < 0) return fail(WOFDM_E_INVALID, "rate=%d must be 0, 1 or 2 and n_c=%d >= 0", rate, n_c);
+    return code_steps(rate, n_c);
+}
+
+int wofdm_viterbi_decode(int device, int32_t rate, int32_t n_c, const int32_t *perm, int32_t n_cw, const int8_t *soft, uint8_t *bits,
+                         int32_t *metric)
+{
+    if (!soft || !bits) return fail(WOFDM_E_INVALID, "NULL argument (soft or bits)");
+    if (rate < 0 || rate > 2) return fail(WOFDM_E_INVALID, "rate=%d must be 0, 1 or 2", rate);
+    if (n_c < 1 || n_cw < 1) return fail(WOFDM_E_INVALID, "n_c=%d and n_cw=%d must be >= 1", n_c, n_cw);
+    const int32_t T = code_steps(rate, n_c);
+    if (T < 7) return fail(WOFDM_E_INVALID, "n_c=%d gives %d steps, at least 7 are needed", n_c, T);
+    if (T > WOFDM_CODE_MAX_STEPS) return fail(WOFDM_E_UNSUPPORTED, "n_c=%d gives %d steps, more than %d", n_c, T, WOFDM_CODE_MAX_STEPS);
+    if (perm && !is_permutation(perm, n_c)) return fail(WOFDM_E_INVALID, "perm is not a permutation of 0 ... %d", n_c - 1);
+    int rc = use_device(device);
+    if (rc != WOFDM_OK) return rc;
+    std::vector<int32_t> gather((size_t)n_c);
+    for (int32_t c = 0; c < n_c; ++c) gather[(size_t)c] = perm ? perm[c] : c;
+    const size_t n_soft = (size_t)n_cw * (size_t)n_c, n_bits = (size_t)n_cw * (size_t)T;
+    dev_buf<int8_t> d_soft;
+    dev_buf<int32_t> d_gather, d_metric;
+    dev_buf<uint8_t> d_bits;
+    if (!d_soft.alloc(n_soft) || !d_gather.alloc(gather.size()) || !d_bits.alloc(n_bits) || !d_metric.alloc((size_t)n_cw))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (decoder)");
+    if (!d_soft.upload(soft, n_soft) || !d_gather.upload(gather.data(), gather.size())) return fail(WOFDM_E_HIP, "upload failed");
+    wofdm_codeparams cd{};
+    cd.soft = d_soft; cd.gather = d_gather; cd.n_c = n_c; cd.n_codes = 1; cd.rate[0] = rate; cd.steps[0] = T; cd.cw_stride = n_c;
+    cd.bits = d_bits; cd.metric = d_metric; cd.n_cw = (uint32_t)n_cw;
+    std::vector<uint8_t> hbits(n_bits);
+    std::vector<int32_t> hmetric((size_t)n_cw);
+    hipError_t e;
+    {
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the decoder is in every auxiliary unit)
+        e = ax && ax->viterbi ? ax->viterbi(&cd, nullptr) : hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess || !fetch(hbits, d_bits.p) || !fetch(hmetric, d_metric.p))
+        return fail(WOFDM_E_HIP, "decoder kernel or copy-back failed: %s", hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
+    std::memcpy(bits, hbits.data(), n_bits);
+    if (metric) std::memcpy(metric, hmetric.data(), hmetric.size() * sizeof(int32_t));
+    return WOFDM_OK;
 }
 
 int wofdm_rx_profile_kernel_ms(float *ms)

@@ -1240,10 +1240,13 @@ __device__ __forceinline__ float soft_log2_1p(float x)
 // times 6 bits of exp2 / log2 pairs are code enough once -- and the scales' loop is, so that the lane's sums stay in registers.
 // TRACK (wofdm_rxprof_tracking_kernel): pil, the comb, or null -- a pilot bin is written as an unloaded one is, 0 --, and G is
 // whatever equaliser the point's receiver formed for this symbol, e = G row and nu = |G|^2 vw as above.
-template <int N, bool TRACK = false>
+// CODED (wofdm_rxprof_coded_kernel): beside the penalties the bin's soft bits d_i = clamp(rint(llr z_i), -127, 127), round half
+// even, NaN -> 0, 0 where the bin takes no decision, as ONE 8-byte store to sb[slot][s - 1][n][8] (bytes k ... 7 are 0).
+template <int N, bool TRACK = false, bool CODED = false>
 __device__ __forceinline__ void soft_symbol(const wofdm_rparams &p, const wofdm_softparams &so, const float2 *row, const float2 *G,
                                             const float2 *__restrict__ Xs, float vw, size_t slot, int s, int lane,
-                                            [[maybe_unused]] const uint8_t *__restrict__ pil = nullptr)
+                                            [[maybe_unused]] const uint8_t *__restrict__ pil = nullptr,
+                                            [[maybe_unused]] float llr = 0.f, [[maybe_unused]] int8_t *__restrict__ sb = nullptr)
 {
     constexpr int BINS = N / 64, SC = WOFDM_SOFT_SCALES;
     const int k = p.k, hb = k >> 1, mm = (1 << hb) - 1, nsc = so.n_scales, S = p.S;
@@ -1300,6 +1303,17 @@ __device__ __forceinline__ void soft_symbol(const wofdm_rparams &p, const wofdm_
                     if (q == ax * hb + i && i < hb) z[q] = zz;
             }
         }
+        if constexpr (CODED) {
+            uint32_t w[2] = {0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                const float t = llr * z[i];                           // (z[i] = 0 for i >= k)
+                const int d = t != t ? 0 : (int)__builtin_rintf(fminf(fmaxf(t, -127.f), 127.f));
+                w[i >> 2] |= ((uint32_t)d & 0xFFu) << (8 * (i & 3));
+            }
+            uint2 *dst = reinterpret_cast<uint2 *>(sb + ((slot * (size_t)(S - 1) + (size_t)(s - 1)) * N + (size_t)n) * 8);
+            *dst = on ? make_uint2(w[0], w[1]) : make_uint2(0u, 0u);
+        }
 #pragma unroll
         for (int c = 0; c < SC; ++c) {
             if (c < nsc) {
@@ -1335,6 +1349,13 @@ __device__ __forceinline__ void soft_symbol_zero(const wofdm_softparams &so, int
     float *__restrict__ bp = so.bit_part + (slot * (size_t)(S - 1) + (size_t)(s - 1)) * (size_t)nsc * N;
     for (int i = lane; i < nsc * N; i += 64) bp[i] = 0.f;
     if (lane < nsc) so.sym_part[(slot * (size_t)nsc + (size_t)lane) * (size_t)S + (size_t)s] = 0.f;
+}
+// (CODED) and its soft bits: the zeros of a symbol that holds no codeword
+template <int N>
+__device__ __forceinline__ void coded_symbol_zero(int8_t *__restrict__ sb, int S, size_t slot, int s, int lane)
+{
+    uint2 *dst = reinterpret_cast<uint2 *>(sb + (slot * (size_t)(S - 1) + (size_t)(s - 1)) * (size_t)N * 8);
+    for (int n = lane; n < N; n += 64) dst[n] = make_uint2(0u, 0u);
 }
 
 // The one body of the seven receive kernels; ARM selects at compile time what an arm adds to the pipeline above, and the
@@ -1396,14 +1417,16 @@ __device__ __forceinline__ void soft_symbol_zero(const wofdm_softparams &so, int
 // s >= 1 leaves beside them the symbol's sums over the loaded bins -- a lane's bins ascending, then papr_wave_reduce -- in
 // sym_pow, sym_cnt [job][point][S].  The pilot of a point sees what the point's data sees.  Where pass 1 runs per point, Ps
 // is the point's; Pn depends on neither channel nor waveform and is measured with the first.
-template <int N, int ARM, bool SOFT = false, bool TRACK = false>
+template <int N, int ARM, bool SOFT = false, bool TRACK = false, bool CODED = false>
 __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_aparams &ap, const wofdm_sparams &sp,
                                             const wofdm_dparams &dp, const wofdm_paparams &pa, const wofdm_pnparams &pn,
                                             const wofdm_lparams &lk, [[maybe_unused]] const wofdm_softparams &so = wofdm_softparams{},
-                                            [[maybe_unused]] const wofdm_trackparams &tk = wofdm_trackparams{})
+                                            [[maybe_unused]] const wofdm_trackparams &tk = wofdm_trackparams{},
+                                            [[maybe_unused]] const wofdm_codeparams &cd = wofdm_codeparams{})
 {
     static_assert(!SOFT || ARM == RXP_LINK, "the demapper is instantiated for the link arm only");
     static_assert(!TRACK || SOFT, "the tracking receiver is instantiated with the demapper only");
+    static_assert(!CODED || TRACK, "the soft-bit stores are instantiated with the tracking receiver only");
     using RG = rxp_geo<N>;
     constexpr bool LINK = ARM == RXP_LINK;
     constexpr bool ACI = ARM == RXP_ACI || LINK, SYNC = ARM == RXP_SYNC || LINK, DOP = ARM == RXP_DOPPLER || LINK;
@@ -1787,10 +1810,13 @@ __device__ __forceinline__ void rxprof_body(const wofdm_rparams &p, const wofdm_
                     }
                 }
                 if constexpr (TRACK) {
-                    if (counted)
-                        soft_symbol<N, true>(p, so, buf, Gs, Xg + (size_t)s * N, soft_vw, slot, s, lane, tk.pilots);
-                    else if (s >= 1)
+                    if (counted) {
+                        soft_symbol<N, true, CODED>(p, so, buf, Gs, Xg + (size_t)s * N, soft_vw, slot, s, lane, tk.pilots, cd.llr_scale,
+                                                    cd.soft);
+                    } else if (s >= 1) {
                         soft_symbol_zero<N>(so, S, slot, s, lane);
+                        if constexpr (CODED) coded_symbol_zero<N>(cd.soft, S, slot, s, lane);
+                    }
                 } else if constexpr (SOFT) {
                     if (s >= 1) soft_symbol<N>(p, so, buf, G, Xg + (size_t)s * N, soft_vw, slot, s, lane);
                 }
@@ -1880,6 +1906,113 @@ __global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_tracking_
                                                                                       const wofdm_trackparams tk)
 {
     rxprof_body<N, RXP_LINK, true, true>(p, ap, sp, dp, pa, pn, lk, so, tk);
+}
+// wofdm_rx_profile_coded: the tracking kernel plus the soft-bit stores (CODED) wofdm_viterbi_kernel decodes
+template <int N>
+__global__ void __launch_bounds__(rxp_geo<N>::WAVES * 64) wofdm_rxprof_coded_kernel(const wofdm_rparams p, const wofdm_aparams ap,
+                                                                                   const wofdm_sparams sp, const wofdm_dparams dp,
+                                                                                   const wofdm_paparams pa, const wofdm_pnparams pn,
+                                                                                   const wofdm_lparams lk, const wofdm_softparams so,
+                                                                                   const wofdm_trackparams tk, const wofdm_codeparams cd)
+{
+    rxprof_body<N, RXP_LINK, true, true, true>(p, ap, sp, dp, pa, pn, lk, so, tk, cd);
+}
+
+// The K = 7 decoder of include/wofdm.h, generators 133 / 171 octal: one wave per (codeword, code), lane = state s.  The wave
+// first gathers its codeword through cd.gather and depunctures it into LDS -- step t's pair (dA, dB) as two int8, 0 where the
+// pattern keeps nothing: a lane takes the steps t = lane, lane + 64, ... --, then walks the trellis: the metrics of the
+// predecessors p0 = (s << 1) & 63 and p1 = p0 | 1 come by two cross-lane reads, the branch into s with input bit u = s >> 5 has
+// the coded bits A = parity(r & 0133), B = parity(r & 0171) of r = (u << 6) | p -- bit 0 of r is in both generators, so p1's pair
+// is the complement of p0's --, the metric is the sum of d over the hypothesised ones, int32, and the survivor is p0 unless p1's
+// metric is strictly smaller.  The 64 decisions of a step are one __ballot word, which lane 0 leaves in LDS; the traceback from
+// state 0 at step T reads them back (wave-uniform) and leaves u_t as bytes, which the lanes then count (the profile: integer
+// atomics on errs) or copy out (wofdm_viterbi_decode).  LDS: 11 bytes per step (8 decisions, 2 branch metrics, 1 decoded bit),
+// at most 50 688 B at T = 4608; every loop has a wave-uniform trip count.
+__global__ void __launch_bounds__(64) wofdm_viterbi_kernel(const wofdm_codeparams cd)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char vsm[];
+    const int lane = threadIdx.x;
+    const int code = blockIdx.y, rate = cd.rate[code], T = cd.steps[code], n_c = cd.n_c;
+    const uint64_t w = blockIdx.x;
+    // the profile: codeword w = (job, point, data symbol); the postamble of a point with post holds no codeword, and its wave
+    // leaves before it does anything (wave-uniform; the workgroup is this one wave)
+    int sym = 0, pt = 0;
+    if (cd.errs != nullptr) {
+        sym = (int)(w % (uint64_t)cd.S1);
+        pt = (int)((w / (uint64_t)cd.S1) % (uint64_t)cd.n_points);
+        if (cd.pts[pt].post != 0 && sym == cd.S1 - 1) return;
+    }
+    unsigned long long *hist = reinterpret_cast<unsigned long long *>(vsm);        // [T]
+    uint16_t *bm = reinterpret_cast<uint16_t *>(hist + T);                          // [T] dA | dB << 8
+    uint8_t *ub = reinterpret_cast<uint8_t *>(bm + T);                              // [T]
+    const int8_t *__restrict__ soft = cd.soft + (int64_t)w * cd.cw_stride;
+    // the coded-stream indices of step t's kept outputs, A before B: rate 1/2 (2 t, 2 t + 1); rate 2/3, period 2, A 1 1, B 1 0;
+    // rate 3/4, period 3, A 1 1 0, B 1 0 1
+    for (int t = lane; t < T; t += 64) {
+        int ca, cb;
+        if (rate == 0) {
+            ca = 2 * t;
+            cb = 2 * t + 1;
+        } else if (rate == 1) {
+            const int q = t >> 1, ph = t & 1;
+            ca = 3 * q + 2 * ph;
+            cb = ph == 0 ? 3 * q + 1 : -1;
+        } else {
+            const int q = t / 3, ph = t - 3 * q;
+            ca = ph == 2 ? -1 : 4 * q + 2 * ph;
+            cb = ph == 1 ? -1 : 4 * q + (ph == 0 ? 1 : 3);
+        }
+        const int da = ca >= 0 && ca < n_c ? soft[cd.gather[ca]] : 0;
+        const int db = cb >= 0 && cb < n_c ? soft[cd.gather[cb]] : 0;
+        bm[t] = (uint16_t)(((uint32_t)da & 0xFFu) | (((uint32_t)db & 0xFFu) << 8));
+    }
+    __syncthreads();
+    const int p0 = (lane << 1) & 63, u = lane >> 5, r0 = (u << 6) | p0;
+    const bool a0 = (__popc(r0 & 0133) & 1) != 0, b0 = (__popc(r0 & 0171) & 1) != 0;
+    int m = lane == 0 ? 0 : (1 << 30);
+    for (int t = 0; t < T; ++t) {
+        const uint32_t pr = bm[t];
+        const int da = (int)(int8_t)(pr & 0xFFu), db = (int)(int8_t)(pr >> 8);
+        const int c0 = __shfl(m, p0, 64) + (a0 ? da : 0) + (b0 ? db : 0);
+        const int c1 = __shfl(m, p0 | 1, 64) + (a0 ? 0 : da) + (b0 ? 0 : db);
+        const bool dec = c1 < c0;
+        m = dec ? c1 : c0;
+        const unsigned long long word = __ballot(dec);
+        if (lane == 0) hist[t] = word;
+    }
+    __syncthreads();
+    // traceback from state 0 at step T (every lane walks the same path: the reads are broadcasts)
+    int st = 0;
+    for (int t = T - 1; t >= 0; --t) {
+        const unsigned long long word = hist[t];
+        if (lane == 0) ub[t] = (uint8_t)(st >> 5);
+        st = ((st << 1) & 63) | (int)((word >> st) & 1ull);
+    }
+    __syncthreads();
+    if (cd.errs != nullptr) {
+        // info-bit errors over t < T - 6, a codeword error for any u_t != 0
+        const uint64_t job = w / ((uint64_t)cd.S1 * (uint64_t)cd.n_points), cell = (cd.item0 + job) / cd.frames;
+        int info = 0, any = 0;
+        for (int t = lane; t < T; t += 64) {
+            const int b = ub[t];
+            info += t < T - 6 ? b : 0;
+            any |= b;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            info += __shfl_xor(info, o, 64);
+            any |= __shfl_xor(any, o, 64);
+        }
+        if (lane == 0 && any != 0) {
+            unsigned long long *e = cd.errs + ((((uint64_t)pt * cd.cells + cell) * (uint64_t)cd.n_codes + (uint64_t)code) * (uint64_t)cd.S1 + (uint64_t)sym) * 2;
+            if (info != 0) atomicAdd(e, (unsigned long long)info);
+            atomicAdd(e + 1, 1ull);
+        }
+    } else {
+        uint8_t *__restrict__ out = cd.bits + w * (uint64_t)T;
+        for (int t = lane; t < T; t += 64) out[t] = ub[t];
+        if (lane == 0 && cd.metric != nullptr) cd.metric[w] = m;
+    }
 }
 
 // totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
@@ -2391,6 +2524,22 @@ bool rxprof_soft_ok(const wofdm_softparams &so)
     return !(so.n_scales < 1 || so.n_scales > WOFDM_SOFT_SCALES || so.w2 == nullptr || so.bit_part == nullptr ||
              so.sym_part == nullptr || so.bit_tot == nullptr || so.sym_tot == nullptr);
 }
+// the coded link: the codes, their steps (7 ... 4608: the decoder's LDS is 11 bytes per step) and the buffers
+bool viterbi_ok(const wofdm_codeparams &cd, bool profile)
+{
+    if (cd.n_codes < 1 || cd.n_codes > WOFDM_CODE_CODES || cd.n_c < 1 || cd.soft == nullptr || cd.gather == nullptr ||
+        (profile && (cd.errs == nullptr || !(cd.llr_scale > 0.f))))
+        return false;
+    for (int i = 0; i < cd.n_codes; ++i)
+        if (cd.rate[i] < 0 || cd.rate[i] > 2 || cd.steps[i] < 7 || cd.steps[i] > 4608) return false;
+    return true;
+}
+unsigned viterbi_lds(const wofdm_codeparams &cd)
+{
+    int T = 0;
+    for (int i = 0; i < cd.n_codes; ++i) T = cd.steps[i] > T ? cd.steps[i] : T;
+    return 11u * (unsigned)T;
+}
 // the ordered sums of the chunk onto the totals: per point of sp, or (null) the plain ones
 void rxprof_reduce_launch(const wofdm_rparams &r, const wofdm_sparams *sp, hipStream_t s)
 {
@@ -2419,7 +2568,9 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
     const bool link = c.arm == RXP_LINK, points = MAX_POINTS[c.arm] > 0;
     const bool nb = c.arm == RXP_ACI || (link && c.nb_on), sync = c.arm == RXP_SYNC || link, knots = c.arm == RXP_DOPPLER || link;
     const bool amp = c.arm == RXP_PA || link, walk = c.arm == RXP_PN || link, soft = link && c.soft_on, track = soft && c.track_on;
-    if (nb != c.nb_on || soft != c.soft_on || track != c.track_on || (track && (c.tk.pts == nullptr || r.S > 64)) || !rxprof_args_ok(&c.tx, r) || (points && !rxprof_points_ok(c.sp, r, MAX_POINTS[c.arm])) ||
+    const bool code = track && c.code_on;
+    if (nb != c.nb_on || soft != c.soft_on || track != c.track_on || code != c.code_on || (code && !viterbi_ok(c.cd, true)) ||
+        (track && (c.tk.pts == nullptr || r.S > 64)) || !rxprof_args_ok(&c.tx, r) || (points && !rxprof_points_ok(c.sp, r, MAX_POINTS[c.arm])) ||
         (nb && !rxprof_nb_ok(c, !link)) || (sync && (c.sp.pts == nullptr || c.sp.base == nullptr)) ||
         (knots && !rxprof_knots_ok(c.dp, r, link, link ? c.max_theta : 0)) || (amp && !rxprof_pa_ok(c)) ||
         // (rxprof_args_ok: B = N + delta + gam, so the last sample under the last window is the walk's last, index S B - 1)
@@ -2451,7 +2602,9 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
     case RXP_PA: receive(wofdm_rxprof_pa_kernel<N>, rxp_geo<N>::LDS, c.sp, c.pa); break;
     case RXP_PN: receive(wofdm_rxprof_pn_kernel<N>, rxp_geo<N>::LDS, c.sp, c.pn); break;
     default:
-        if (track)
+        if (code)
+            receive(wofdm_rxprof_coded_kernel<N>, rxp_geo<N>::LDS_TRACK, c.a, c.sp, c.dp, c.pa, c.pn, c.lk, c.soft, c.tk, c.cd);
+        else if (track)
             receive(wofdm_rxprof_tracking_kernel<N>, rxp_geo<N>::LDS_TRACK, c.a, c.sp, c.dp, c.pa, c.pn, c.lk, c.soft, c.tk);
         else if (soft)
             receive(wofdm_rxprof_soft_kernel<N>, rxp_geo<N>::LDS_LINK, c.a, c.sp, c.dp, c.pa, c.pn, c.lk, c.soft);
@@ -2470,6 +2623,25 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
         hipLaunchKernelGGL(wofdm_rxprof_soft_reduce_kernel<N>, dim3(N / 64 + 1, n_cells, (unsigned)(c.sp.n_points * c.soft.n_scales)),
                            dim3(64), 0, s, r, c.sp, c.soft, cell0);
     }
+    if (code) {
+        // the decoder behind the soft bits: one wave per (frame, point, data symbol) and code
+        wofdm_codeparams cd = c.cd;
+        cd.cw_stride = (int64_t)N * 8;
+        cd.pts = c.tk.pts; cd.n_points = c.sp.n_points; cd.S1 = r.S - 1;
+        cd.item0 = r.item0; cd.frames = r.frames; cd.cells = c.sp.cells;
+        cd.bits = nullptr; cd.metric = nullptr;
+        cd.n_cw = (uint32_t)r.n_jobs * (uint32_t)cd.n_points * (uint32_t)cd.S1;
+        hipLaunchKernelGGL(wofdm_viterbi_kernel, dim3(cd.n_cw, (unsigned)cd.n_codes), dim3(64), viterbi_lds(cd), s, cd);
+    }
+    return hipGetLastError();
+}
+
+// wofdm_viterbi_decode: the decoder on soft bits of the caller's
+hipError_t viterbi_launch(const wofdm_codeparams *cd, hipStream_t s)
+{
+    if (!viterbi_ok(*cd, false) || cd->n_codes != 1 || cd->bits == nullptr || cd->errs != nullptr || cd->n_cw < 1)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wofdm_viterbi_kernel, dim3(cd->n_cw, 1), dim3(64), viterbi_lds(*cd), s, *cd);
     return hipGetLastError();
 }
 
@@ -2483,7 +2655,7 @@ const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
 
 const wofdm_link_fns *WOFDM_CAT(wofdm_aux_link_n, WOFDM_TU_N)(void)
 {
-    static const wofdm_link_fns fns = {rx_profile_chunk};
+    static const wofdm_link_fns fns = {rx_profile_chunk, viterbi_launch};
     return &fns;
 }
 

@@ -55,6 +55,30 @@ struct wofdm_trackparams {
     const wofdm_tpoint *pts;          // [n_points]
 };
 
+// The coded link of wofdm_rx_profile_coded, a tenth argument of wofdm_rxprof_coded_kernel (the tracking kernel with the CODED
+// flag) and the argument of wofdm_viterbi_kernel.  The receive kernel leaves, per bin of every data symbol, the k soft bits d =
+// clamp(rint(llr_scale z_i), -127, 127) (include/wofdm.h) as one 8-byte store, padded with zeros; 0 where no decision is taken.
+// The decoder reads a codeword's coded-stream index c at byte gather[c] of the codeword's block (cw_stride bytes apart): for the
+// profile gather[c] = 8 n + i of position perm[c] = r k + i (n the r-th data bin), for wofdm_viterbi_decode perm[c] itself.
+#define WOFDM_CODE_CODES 4                 // WOFDM_CODE_MAX of include/wofdm.h
+struct wofdm_codeparams {
+    float llr_scale;
+    int8_t *soft;                     // [n_jobs][n_points][S - 1][n_fft][8]; the decoder alone: [n_cw][cw_stride]
+    const int32_t *gather;            // [n_c]
+    int32_t n_c, n_codes;
+    int32_t rate[WOFDM_CODE_CODES], steps[WOFDM_CODE_CODES];   // steps: wofdm_code_steps(rate, n_c) >= 7
+    int64_t cw_stride;                // bytes between the blocks of two codewords
+    // the profile (bits null): codeword w is (job, point, data symbol), counted into errs unless pts[point].post and the last symbol
+    unsigned long long *errs;         // [n_points][cells][n_codes][S - 1][2] {info-bit errors, codeword errors}, integer atomics
+    const wofdm_tpoint *pts;          // [n_points]
+    int32_t n_points, S1;             // S1 = S - 1
+    uint64_t item0, frames, cells;
+    // wofdm_viterbi_decode (errs null): the decoded bits and the final metrics of code 0
+    uint8_t *bits;                    // [n_cw][steps[0]]
+    int32_t *metric;                  // [n_cw], or null
+    uint32_t n_cw;
+};
+
 // The arms of the receive body (rxprof_body of wofdm_aux.hip, which says what each adds)
 enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
 
@@ -66,6 +90,7 @@ enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
 struct wofdm_rxchunk {
     int32_t arm;                      // RXP_*
     bool nb_on, soft_on, track_on;    // RXP_ACI: nb_on is true; track_on needs soft_on
+    bool code_on;                     // (wofdm_rx_profile_coded) needs track_on: the soft-bit stores and the decoder behind them
     wofdm_pparams tx, nb;             // the victim's Tx chain; the neighbour's (S + 1 symbols, its own stream, allocation, buffers)
     wofdm_rparams r;
     wofdm_aparams a;                  // RXP_LINK: ioff and a_lvl are the points'
@@ -76,6 +101,7 @@ struct wofdm_rxchunk {
     wofdm_lparams lk;
     wofdm_softparams soft;
     wofdm_trackparams tk;
+    wofdm_codeparams cd;
     int32_t n_tracks;                 // RXP_LINK: the tracks of dp's knots, the static one included
     int32_t max_theta;                // RXP_LINK: the largest timing offset of the points, or 0 (the knots cover the samples it reaches)
 };
@@ -85,6 +111,8 @@ struct wofdm_link_fns {
     // the items' unit walks, the arm's receive kernel, the ordered sums (per point where the arm has points), the power sums in
     // frame order, the demapper's ordered sums -- each where its stage is on, in this order.
     hipError_t (*rx_profile_chunk)(const wofdm_rxchunk *c, hipStream_t s);
+    // wofdm_viterbi_kernel on soft bits of the caller's (cd.errs null, cd.bits set): one wave per codeword of code 0
+    hipError_t (*viterbi)(const wofdm_codeparams *cd, hipStream_t s);
 };
 const wofdm_link_fns *wofdm_aux_link_n64(void);
 const wofdm_link_fns *wofdm_aux_link_n128(void);

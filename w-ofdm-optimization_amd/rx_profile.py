@@ -381,7 +381,7 @@ def _chunk_frames(st, syms, masked, per_point=0, n_points=0, per_frame_extra=0, 
 
 
 def _gpu_call(entry, result, st, bits_per_sc, syms, prepared, seed, frame_offset, frames, noise_before_truncate, device, out,
-              lead=(), after_h=(), after_mask=(), n_ch=None, n_scales=None):
+              lead=(), after_h=(), after_mask=(), n_ch=None, n_scales=None, behind=()):
     """One call of the library's receive-profile entry point ``entry``: prepared = ``_prepare``'s six (the fifth argument of
     the entry point is prepared[2], of any rank, taps last; n_ch: its channels where they are not its first axis); after_h,
     after_mask: the arm's own ctypes arguments, behind h and behind the mask; lead = () or (n_points,).  The outputs are
@@ -409,7 +409,7 @@ def _gpu_call(entry, result, st, bits_per_sc, syms, prepared, seed, frame_offset
     _lib.check(getattr(_lib.load(), entry)(
         C.byref(cfg), int(device), w_tx.ctypes.data, w_rx.ctypes.data, hf.ctypes.data, *after_h, snr.ctypes.data,
         None if act is None else act.ctypes.data, None if m is None else m.ctypes.data, *after_mask,
-        *(a.ctypes.data for a in outs)))
+        *(a.ctypes.data for a in outs), *behind))                      # (behind: the entry point's arguments after the outputs)
     fields = []
     for a in outs:
         fields += [np.ascontiguousarray(a[..., 0]), np.ascontiguousarray(a[..., 1])] if a.dtype == np.uint64 else [a]
@@ -1317,8 +1317,9 @@ def rx_profile_soft_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_d
 
 def _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, scales, tracks,
                 knot_step, aci_active, aci_h, ref_power, active, mask, noise_before_truncate, with_near, receiver=None):
-    """``rx_profile_soft_host``'s sweep; receiver(q: ``_Sweep``) -> per point a function (front, out, p, s) -> the frame's tuple
-    behind ``_link_point``'s outputs ``out`` in the place of the one-shot receiver's (``rx_profile_tracking_host``)"""
+    """``rx_profile_soft_host``'s sweep; receiver(q: ``_Sweep``, n_points, scales) -> per point a function (front, out, p, s, c, f)
+    -> the frame's tuple behind ``_link_point``'s outputs ``out`` in the place of the one-shot receiver's, (p, s, c) the cell's
+    pair, SNR point and channel and f the frame's index in the call (``rx_profile_tracking_host``, ``rx_profile_coded_host``)"""
     from . import timefreq as T
     sc = _soft_scales(scales)
     points = [LinkPoint()] if points is None else points
@@ -1349,7 +1350,7 @@ def _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, 
                 if rec is None:
                     yield out[:9] + _soft_outputs(st, fronts[key][0], out, q.w_rx[p], q.snr[s], q.k, sc, q.nbt)[1:]
                 else:
-                    yield rec[i](fronts[key][0], out, p, s)
+                    yield rec[i](fronts[key][0], out, p, s, c, fr - int(frame_offset))
         return (len(pts),), frame
     res = _host_sweep(_RxSoftSums, arm, st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames,
                       active, mask, noise_before_truncate, with_near, n_scales=sc.size)
@@ -1595,7 +1596,7 @@ def rx_profile_tracking_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, s
     def receiver(q, n_points, sc):
         tps, pil = _tracking_prepare(st, q.S, n_points, tracking, pilots, q.act)
         held.update(tps=tps, pil=pil, act=q.act)
-        return [lambda front, out, p, s, tp=tp: _tracking_outputs(st, front, out, q.w_rx[p], q.snr[s], q.k, sc, q.nbt, pil, tp)
+        return [lambda front, out, p, s, c, f, tp=tp: _tracking_outputs(st, front, out, q.w_rx[p], q.snr[s], q.k, sc, q.nbt, pil, tp)
                 for tp in tps]
     res = _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, scales, tracks,
                       knot_step, aci_active, aci_h, ref_power, active, mask, noise_before_truncate, with_near, receiver)
@@ -1651,3 +1652,361 @@ def rx_profile_tracking_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, sn
             raise ValueError("out has another shape")
         dec, sym = out.decisions + dec, out.decisions_sym + sym
     return _tracking_result(res, sc, dec, sym)
+
+
+# ---- the coded link: 8-bit soft bits and a K = 7 Viterbi decoder (wofdm_rx_profile_coded, wofdm_viterbi_decode) ----
+
+#: the rates of include/wofdm.h by index, and their puncturing patterns (A keeps, B keeps) by t mod period
+CODE_RATES = ("1/2", "2/3", "3/4")
+_PUNCTURE = (((1,), (1,)), ((1, 1), (1, 0)), ((1, 1, 0), (1, 0, 1)))
+#: the default quantiser scale: it clamps 4-5 % of the soft bits on the mirror's 16-22 dB cells
+LLR_SCALE = 0.25
+
+RxProfileCoded = collections.namedtuple(
+    "RxProfileCoded", RxProfileTracking._fields + ("info_err", "cw_err", "info_bits", "codewords", "rates", "llr_scale", "soft_bits"))
+RxProfileCoded.__doc__ = """``RxProfileTracking``'s fields, and info_err, cw_err (uint64) [points, pairs, n_snr, n_ch, codes, S - 1]:
+the decoded info-bit errors and codeword errors per data symbol; info_bits [codes]: T - 6 of each code; codewords [points, S - 1]:
+the codewords a data symbol carried per cell (frames; 0 for the postamble of a point with post); rates [codes]; llr_scale;
+soft_bits (int8) [pairs, n_snr, n_ch, frames, points, S - 1, N, 8] or None."""
+
+
+def code_steps(rate, n_c):
+    """T = wofdm_code_steps(rate, n_c) of include/wofdm.h: the largest T whose kept outputs number at most n_c"""
+    rate, n_c = int(rate), int(n_c)
+    if rate not in (0, 1, 2) or n_c < 0:
+        raise ValueError("rate must be 0, 1 or 2 and n_c >= 0")
+    if rate == 0:
+        return n_c // 2
+    if rate == 1:
+        return 2 * (n_c // 3) + int(n_c % 3 == 2)
+    return 3 * (n_c // 4) + (0, 0, 1, 2)[n_c % 4]
+
+
+def _kept_index(rate, steps):
+    """(ca, cb) [T]: the coded-stream index of A_t and of B_t, -1 where the pattern punctures it; and the kept outputs' number"""
+    pa, pb = _PUNCTURE[int(rate)]
+    ca, cb = np.full(steps, -1, dtype=np.int64), np.full(steps, -1, dtype=np.int64)
+    c = 0
+    for t in range(steps):
+        if pa[t % len(pa)]:
+            ca[t], c = c, c + 1
+        if pb[t % len(pb)]:
+            cb[t], c = c, c + 1
+    return ca, cb, c
+
+
+def _parity(v):
+    v = np.asarray(v)
+    return sum((v >> b) & 1 for b in range(7)) & 1
+
+
+def default_interleaver(n_c):
+    """perm [n_c]: the positions written row-wise into 17 columns and read column-wise -- 17 is coprime to k = 2, 4, 6, so
+    neighbours of the coded stream land bins apart and on rotating bit significance"""
+    return np.array([j for col in range(17) for j in range(col, int(n_c), 17)], dtype=np.int32)
+
+
+def _check_perm(perm, n_c):
+    if perm is None:
+        return None
+    p = np.ascontiguousarray(np.asarray(perm).reshape(-1), dtype=np.int32)
+    if p.size != n_c or not np.array_equal(np.sort(p), np.arange(n_c)):
+        raise ValueError("perm must be a permutation of 0 ... %d" % (n_c - 1))
+    return p
+
+
+def conv_encode(info, rate):
+    """The K = 7, 133 / 171 code of include/wofdm.h: info [..., T - 6] bits -> the kept coded bits [..., n_kept] (uint8), A before
+    B, t ascending, six zero tail bits appended"""
+    info = np.asarray(info).astype(np.int64) & 1
+    u = np.concatenate([info, np.zeros(info.shape[:-1] + (6,), dtype=np.int64)], axis=-1)
+    steps = u.shape[-1]
+    ca, cb, kept = _kept_index(rate, steps)
+    out = np.zeros(u.shape[:-1] + (kept,), dtype=np.uint8)
+    state = np.zeros(u.shape[:-1], dtype=np.int64)
+    for t in range(steps):
+        r = (u[..., t] << 6) | state
+        if ca[t] >= 0:
+            out[..., ca[t]] = _parity(r & 0o133)
+        if cb[t] >= 0:
+            out[..., cb[t]] = _parity(r & 0o171)
+        state = (u[..., t] << 5) | (state >> 1)
+    return out
+
+
+def viterbi_decode(soft, rate, perm=None):
+    """The integer mirror of ``wofdm_viterbi_decode``, vectorised over the codewords: soft [n_cw, n_c] int8 (d > 0: a coded bit
+    0), coded-stream index c reading soft[:, perm[c]] (None: c).  The metric is the sum of d over the kept outputs whose
+    hypothesised bit is 1, int32; paths start in state 0 (2^30 on the others); the survivor is p0 = (s << 1) & 63 unless p1 = p0 | 1
+    is strictly smaller; the traceback starts from state 0 at step T.  Returns (bits [n_cw, T] uint8, metric [n_cw] int32)."""
+    soft = np.atleast_2d(np.asarray(soft)).astype(np.int32)
+    n_cw, n_c = soft.shape
+    steps = code_steps(rate, n_c)
+    if steps < 7:
+        raise ValueError("n_c=%d gives %d steps, at least 7 are needed" % (n_c, steps))
+    p = _check_perm(perm, n_c)
+    if p is not None:
+        soft = soft[:, p]
+    ca, cb, _ = _kept_index(rate, steps)
+    ext = np.concatenate([soft, np.zeros((n_cw, 1), dtype=np.int32)], axis=1)        # (index -1: a punctured output, 0)
+    d_a, d_b = ext[:, ca], ext[:, cb]
+    s = np.arange(64)
+    p0 = (s << 1) & 63
+    p1, r0 = p0 | 1, ((s >> 5) << 6) | p0
+    a0, b0 = _parity(r0 & 0o133).astype(np.int32), _parity(r0 & 0o171).astype(np.int32)   # (p1's pair is the complement)
+    m = np.full((n_cw, 64), 1 << 30, dtype=np.int32)
+    m[:, 0] = 0
+    dec = np.empty((steps, n_cw, 64), dtype=bool)
+    for t in range(steps):
+        da, db = d_a[:, t:t + 1], d_b[:, t:t + 1]
+        c0 = m[:, p0] + a0 * da + b0 * db
+        c1 = m[:, p1] + (1 - a0) * da + (1 - b0) * db
+        dec[t] = c1 < c0
+        m = np.where(dec[t], c1, c0)
+    state, rows = np.zeros(n_cw, dtype=np.int64), np.arange(n_cw)
+    bits = np.empty((n_cw, steps), dtype=np.uint8)
+    for t in range(steps - 1, -1, -1):
+        bits[:, t] = state >> 5
+        state = ((state << 1) & 63) | dec[t, rows, state]
+    return bits, m[:, 0].astype(np.int32)
+
+
+def viterbi_decode_gpu(soft, rate, perm=None, device=0):
+    """``wofdm_viterbi_decode``: soft [n_cw, n_c] int8 -> (bits [n_cw, T] uint8, metric [n_cw] int32).  No CPU fallback."""
+    from . import _lib
+    soft = np.ascontiguousarray(np.atleast_2d(np.asarray(soft)), dtype=np.int8)
+    n_cw, n_c = soft.shape
+    steps = code_steps(rate, n_c)
+    p = _check_perm(perm, n_c)
+    bits = np.zeros((n_cw, max(steps, 1)), dtype=np.uint8)
+    metric = np.zeros(n_cw, dtype=np.int32)
+    _lib.check(_lib.load().wofdm_viterbi_decode(int(device), int(rate), n_c, None if p is None else p.ctypes.data, n_cw,
+                                                soft.ctypes.data, bits.ctypes.data, metric.ctypes.data))
+    return bits[:, :steps], metric
+
+
+def soft_bits(z, llr_scale=LLR_SCALE):
+    """The quantiser of include/wofdm.h on z = (1 - 2 b) Lambda (any shape): d = clip(rint(llr_scale z), -127, 127), round half
+    even, int8, NaN -> 0.  Returns (d, llr_scale z unrounded)."""
+    t = float(llr_scale) * np.asarray(z, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        d = np.where(np.isnan(t), 0.0, np.clip(np.rint(t), -127.0, 127.0))
+    return d.astype(np.int8), t
+
+
+def _code_list(codes):
+    rates = [int(r) for r in np.asarray((0,) if codes is None else codes).reshape(-1)]
+    from . import _lib
+    if not 1 <= len(rates) <= _lib.CODE_MAX or any(r not in (0, 1, 2) for r in rates):
+        raise ValueError("1 to %d codes of rate 0, 1 or 2 are needed" % _lib.CODE_MAX)
+    return rates
+
+
+def _code_prepare(st, bits_per_sc, act, pil, codes, perm, llr_scale):
+    """(rates, perm or None, pos [n_c]: the index 8 n + i of position j = r k + i in a symbol's soft bits [N, 8], T per code)"""
+    rates = _code_list(codes)
+    on = np.ones(st.n_fft, dtype=bool) if act is None else np.asarray(act).reshape(-1) != 0
+    data = on & ~pil if pil is not None else on
+    k = int(bits_per_sc)
+    pos = (8 * np.flatnonzero(data)[:, None] + np.arange(k)[None, :]).reshape(-1)
+    steps = [code_steps(r, pos.size) for r in rates]
+    if min(steps) < 7:
+        raise ValueError("%d coded bits per symbol give fewer than 7 steps" % pos.size)
+    if not (np.isfinite(llr_scale) and llr_scale > 0):
+        raise ValueError("llr_scale must be finite and positive")
+    return rates, _check_perm(perm, pos.size), pos, steps
+
+
+def _coded_z(st, front, res, w_rx, snr_db, bits_per_sc, noise_before_truncate, pil, tp):
+    """z [S - 1, N, k] = (1 - 2 b_i) Lambda_i of the tracking mirror's outputs ``res`` (e fourth, Hh fifth) with nu_s[n] = v W2 /
+    |Hh_s[n]|^2, 0 where no decision is taken; and the weight max_m |Hh_s[m]| / |Hh_s[n]| [S - 1, N] of the near rule"""
+    X, conv, _, on = front
+    k, S, B = int(bits_per_sc), X.shape[0], st.sym_len - st.tail_tx
+    data = np.tile(on & ~pil if pil is not None else on, (S - 1, 1))
+    if tp.post:
+        data[S - 2] = False
+    nl = conv.size if noise_before_truncate else S * B
+    v = np.mean(np.abs(conv[:nl]) ** 2) * 10.0 ** (-0.1 * float(snr_db))
+    w2 = float((np.asarray(w_rx, np.float64) ** 2).sum())
+    mag = np.abs(res[4])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        nu = np.where(data, v * w2 / np.where(data, mag, 1.0) ** 2, 1.0)
+        weight = np.where(data, mag.max(axis=1, keepdims=True) / np.where(data, mag, 1.0), 0.0)
+        lab = slice_labels(k, X[1:])
+        sign = np.stack([1.0 - 2.0 * ((lab >> (k - 1 - i)) & 1) for i in range(k)], axis=-1)
+        z = sign * bit_llrs(k, np.where(data, res[3], 0.0), nu)
+    return np.where(data[..., None], z, 0.0), weight
+
+
+def _decode_frame(d, tp, pos, perm, rates):
+    """(info errors, codeword errors) [codes, S - 1] of a frame's soft bits d [S - 1, N, 8]: one codeword per data symbol, none
+    on the postamble of a point with post"""
+    S1 = d.shape[0]
+    use = S1 - 1 if tp.post else S1
+    info, cw = np.zeros((len(rates), S1), dtype=np.uint64), np.zeros((len(rates), S1), dtype=np.uint64)
+    stream = d.reshape(S1, -1)[:use, pos]
+    for j, r in enumerate(rates):
+        bits, _ = viterbi_decode(stream, r, perm)
+        info[j, :use] = bits[:, :bits.shape[1] - 6].sum(axis=1)
+        cw[j, :use] = bits.any(axis=1)
+    return info, cw
+
+
+def frame_profile_coded(st, grids, noise_at, w_tx, w_rx, h, point, tracking, snr_db, bits_per_sc, walk, pilots=None, scales=None,
+                        llr_scale=LLR_SCALE, perm=None, codes=None, track=None, knot_step=None, ref_power=None, aci_grids=None,
+                        aci_h=None, active=None, mask=None, noise_before_truncate=1):
+    """fp64 host mirror of one frame and one point of ``wofdm_rx_profile_coded``: ``frame_profile_tracking``'s outputs, then the
+    soft bits d [S - 1, N, 8] (int8), llr_scale z unrounded [S - 1, N, k], the near rule's weight [S - 1, N], and the decoded
+    info-bit and codeword errors [codes, S - 1] of ``viterbi_decode``."""
+    sc = _soft_scales(scales)
+    tps, pil = _tracking_prepare(st, np.asarray(grids).shape[0], 1, [tracking], pilots, active)
+    rates, p, pos, _ = _code_prepare(st, bits_per_sc, active, pil, codes, perm, llr_scale)
+    front, out = _frame_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, walk, track, knot_step, ref_power,
+                             aci_grids, aci_h, active, mask, noise_before_truncate)
+    res = _tracking_outputs(st, front, out, w_rx, snr_db, bits_per_sc, sc, noise_before_truncate, pil, tps[0])
+    z, weight = _coded_z(st, front, res, w_rx, snr_db, bits_per_sc, noise_before_truncate, pil, tps[0])
+    d8 = np.zeros(z.shape[:2] + (8,), dtype=np.int8)
+    d8[..., :z.shape[-1]], t = soft_bits(z, llr_scale)
+    return res + (d8, t, weight) + _decode_frame(d8, tps[0], pos, p, rates)
+
+
+def _coded_result(trk, info, cw, steps, tps, frames, rates, llr_scale, soft):
+    S1 = trk.decisions_sym.shape[-1]
+    words = np.full((len(tps), S1), int(frames), dtype=np.uint64)
+    for i, q in enumerate(tps):
+        if q.post:
+            words[i, S1 - 1] = 0
+    return RxProfileCoded(*trk, info, cw, np.array([t - 6 for t in steps], dtype=np.int64), words, tuple(rates), float(llr_scale), soft)
+
+
+def rx_profile_coded_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                          tracking=None, pilots=None, scales=None, llr_scale=LLR_SCALE, perm=None, codes=None, tracks=None,
+                          knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None, mask=None,
+                          noise_before_truncate=1, with_near=False, with_soft=False):
+    """The host route of ``rx_profile_coded_gpu``: ``rx_profile_tracking_host``'s frames, points and arrays, each frame's z
+    through ``soft_bits`` and every data symbol's codeword through ``viterbi_decode`` for the rates ``codes`` (None: rate 1/2).
+    Returns ``RxProfileCoded`` (with_near: and the near decisions); with_soft=True keeps soft_bits, and the result carries two
+    more arrays behind it in a tuple: llr_scale z unrounded [..., k] and the near rule's weight [..., S - 1, N]."""
+    held = {}
+
+    def receiver(q, n_points, sc):
+        tps, pil = _tracking_prepare(st, q.S, n_points, tracking, pilots, q.act)
+        rates, p, pos, steps = _code_prepare(st, q.k, q.act, pil, codes, perm, llr_scale)
+        shape = (n_points, q.w_tx.shape[0], q.snr.size, q.hc.shape[0], len(rates), q.S - 1)
+        held.update(tps=tps, pil=pil, act=q.act, rates=rates, steps=steps, info=np.zeros(shape, np.uint64), cw=np.zeros(shape, np.uint64))
+        if with_soft:
+            # [pairs, n_snr, n_ch, frames, points, S - 1, N, .]: the library's soft_bits, and beside it llr z and the weight
+            lead = shape[1:4] + (int(frames), n_points, q.S - 1, st.n_fft)
+            held.update(d=np.zeros(lead + (8,), np.int8), t=np.zeros(lead + (q.k,), np.float64), w=np.zeros(lead, np.float64))
+
+        def one(i, tp):
+            def run(front, out, p_, s_, c_, f_):
+                res = _tracking_outputs(st, front, out, q.w_rx[p_], q.snr[s_], q.k, sc, q.nbt, pil, tp)
+                z, weight = _coded_z(st, front, res, q.w_rx[p_], q.snr[s_], q.k, q.nbt, pil, tp)
+                d8 = np.zeros(z.shape[:2] + (8,), dtype=np.int8)
+                d8[..., :q.k], t = soft_bits(z, llr_scale)
+                info, cw = _decode_frame(d8, tp, pos, p, rates)
+                held["info"][i, p_, s_, c_] += info
+                held["cw"][i, p_, s_, c_] += cw
+                if with_soft:
+                    held["d"][p_, s_, c_, f_, i], held["t"][p_, s_, c_, f_, i], held["w"][p_, s_, c_, f_, i] = d8, t, weight
+                return res
+            return run
+        return [one(i, tp) for i, tp in enumerate(tps)]
+    res = _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, scales, tracks,
+                      knot_step, aci_active, aci_h, ref_power, active, mask, noise_before_truncate, with_near, receiver)
+    soft = res[0] if with_near else res
+    dec, sym = _tracking_decisions(st, syms, frames, held["act"], held["pil"], held["tps"])
+    trk = RxProfileTracking(*soft[:-1], sym, dec)
+    prof = _coded_result(trk, held["info"], held["cw"], held["steps"], held["tps"], frames, held["rates"], llr_scale, held.get("d"))
+    if with_soft:
+        prof = (prof, held["t"], held["w"])
+    return (prof, res[1]) if with_near else prof
+
+
+def rx_profile_coded_chunk_frames(st, syms, masked, n_points, neighbour, n_scales):
+    """Frames one chunk of ``wofdm_rx_profile_coded`` holds: ``rx_profile_tracking_chunk_frames``' bytes plus the soft bits, 8 (S -
+    1) N bytes per point; at most 65535"""
+    B = st.sym_len - st.tail_tx
+    return _chunk_frames(st, syms, masked, per_point=st.n_fft + syms + st.tail_tx + syms * B, n_points=n_points,
+                         per_frame_extra=syms * B, neighbour=bool(neighbour),
+                         extra_bytes=4 * int(n_points) * int(n_scales) * ((syms - 1) * st.n_fft + syms)
+                         + 8 * int(n_points) * (syms - 1) * st.n_fft)
+
+
+def rx_profile_coded_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                         tracking=None, pilots=None, scales=None, llr_scale=LLR_SCALE, perm=None, codes=None, tracks=None,
+                         knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None, mask=None,
+                         noise_before_truncate=1, device=0, out=None, export=False):
+    """``wofdm_rx_profile_coded``: ``rx_profile_tracking_gpu`` of the same arguments -- its fields are that call's bytes --, the
+    demapper's z quantised to int8 with ``llr_scale``, and every data symbol's codeword decoded on the GPU for each rate of
+    ``codes`` (None: rate 1/2) behind the interleaver ``perm`` (None: identity; ``default_interleaver``).  export=True also
+    returns the soft bits.  Returns ``RxProfileCoded``; ``out`` (an earlier result of the same shape, scales and codes) is
+    accumulated into (its soft bits are dropped).  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    sc = _soft_scales(scales)
+    points = [LinkPoint()] if points is None else points
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts, tr, iact, hi, ref = _link_sides(st, prepared[2], points, tracks, aci_active, aci_h, ref_power, prepared[0].shape[0])
+    tps, pil = _tracking_prepare(st, syms, len(pts), tracking, pilots, prepared[4])
+    rates, p, _, steps = _code_prepare(st, bits_per_sc, prepared[4], pil, codes, perm, llr_scale)
+    trf = None if tr is None else _lib.c64_as_f32(tr)
+    hif = None if hi is None else _lib.c64_as_f32(hi)
+    lin = PaPoint(PA_LINEAR, 0.0)
+    cpts = (_lib.LinkPoint * len(pts))(*[
+        _lib.LinkPoint(*(q.pa or lin), -1 if q.track is None else q.track, q.timing, q.cfo, q.cfo_tracked, q.linewidth, q.cpe_tracked,
+                       int(q.aci is not None), *(q.aci or (0, 0.0)), (C.c_int32 * 4)(0, 0, 0, 0)) for q in pts])
+    ctps = (_lib.TrackingPoint * len(tps))(*[_lib.TrackingPoint(q.cpe, q.post, (C.c_int32 * 2)(0, 0)) for q in tps])
+    ccodes = (_lib.Code * len(rates))(*[_lib.Code(r, (C.c_int32 * 3)(0, 0, 0)) for r in rates])
+    pil8 = None if pil is None else np.ascontiguousarray(pil, dtype=np.uint8)
+    knots = (0, 0, 0) if tr is None else (tr.shape[0], tr.shape[2], int(knot_step))
+    prev = None
+    if out is not None:
+        if not np.array_equal(out.scales, sc) or tuple(out.rates) != tuple(rates):
+            raise ValueError("out has other scales or codes")
+        prev = _RxSoftSums(*out[:9], np.zeros(st.n_fft, dtype=np.uint64))
+    cells = (prepared[0].shape[0], prepared[3].size, prepared[2].shape[0])
+    cerr = np.zeros((len(pts),) + cells + (len(rates), int(syms) - 1, 2), dtype=np.uint64)
+    sb = np.zeros(cells + (int(frames), len(pts), int(syms) - 1, st.n_fft, 8), dtype=np.int8) if export else None
+    res = _gpu_call("wofdm_rx_profile_coded", _RxSoftSums, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                    noise_before_truncate, device, prev, lead=(len(pts),), n_scales=sc.size,
+                    after_mask=(None if trf is None else trf.ctypes.data, *knots, None if iact is None else iact.ctypes.data,
+                                None if hif is None else hif.ctypes.data, None if ref is None else ref.ctypes.data, len(pts), cpts,
+                                int(sc.size), sc.ctypes.data, None if pil8 is None else pil8.ctypes.data, ctps,
+                                C.c_float(float(llr_scale)), None if p is None else p.ctypes.data, len(rates), ccodes),
+                    behind=(cerr.ctypes.data, None if sb is None else sb.ctypes.data))
+    dec, sym = _tracking_decisions(st, syms, frames, prepared[4], pil, tps)
+    if out is not None:
+        if out.decisions.shape != dec.shape:
+            raise ValueError("out has another shape")
+        dec, sym = out.decisions + dec, out.decisions_sym + sym
+    prof = _coded_result(_tracking_result(res, sc, dec, sym), np.ascontiguousarray(cerr[..., 0]), np.ascontiguousarray(cerr[..., 1]),
+                         steps, tps, frames, rates, llr_scale, sb)
+    if out is not None:
+        prof = prof._replace(info_err=out.info_err + prof.info_err, cw_err=out.cw_err + prof.cw_err,
+                             codewords=out.codewords + prof.codewords)
+    return prof
+
+
+def _coded_rates(prof, err, per_word):
+    err = err.astype(np.float64)                                       # [points, (pairs,) n_snr, n_ch, codes, S - 1]
+    mid = (1,) * (err.ndim - 3)
+    words = (prof.codewords.astype(np.float64).reshape((err.shape[0],) + mid + (1, err.shape[-1]))
+             * np.asarray(per_word, np.float64).reshape((1,) + mid + (-1, 1)))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per_sym = np.where(words > 0, err / np.where(words > 0, words, 1.0), np.nan)
+        total = words.sum(axis=-1)
+        per_cell = np.where(total > 0, err.sum(axis=-1) / np.where(total > 0, total, 1.0), np.nan)
+    return per_sym, per_cell
+
+
+def coded_ber(prof):
+    """The decoded info-bit error rate: (per data symbol [points, pairs, n_snr, n_ch, codes, S - 1], per cell [..., codes]); NaN
+    where a symbol carried no codeword"""
+    return _coded_rates(prof, prof.info_err, prof.info_bits)
+
+
+def coded_cwer(prof):
+    """The codeword error rate, shaped as ``coded_ber``'s"""
+    return _coded_rates(prof, prof.cw_err, np.ones(len(prof.rates)))
