@@ -1014,6 +1014,76 @@ int wofdm_viterbi_decode(int device, int32_t rate, int32_t n_c,
                          uint8_t *bits,                     /* [n_cw][T] */
                          int32_t *metric);                  /* [n_cw], or NULL */
 
+/* The same decoder for codewords of any length up to WOFDM_CODE_LONG_MAX_STEPS steps: arguments, checks, code, metric, start and
+ * tie rule are wofdm_viterbi_decode's, and on every word that call takes, bits and metric are that call's -- exact maximum-
+ * likelihood decoding, no truncated window.  WOFDM_E_UNSUPPORTED only for T > WOFDM_CODE_LONG_MAX_STEPS.  One wave per codeword,
+ * one state per lane; the survivor history streams to device memory in blocks of 64 steps, 512 bytes each, so the scratch is
+ * 512 ceil(T / 64) bytes per codeword (8 MiB at the largest T), and the call walks the codewords in groups whose scratch stays
+ * within WOFDM_RX_PROFILE_CHUNK_BYTES.  int32 suffices for the metric: |d| <= 128 and two outputs per step, so |metric| <= 256 T
+ * <= 2^28 beside the 2^30 of the start.  The call holds the launch gate while its kernels run; it neither counts for nor resets
+ * wofdm_rx_profile_kernel_ms. */
+#define WOFDM_CODE_LONG_MAX_STEPS 1048576
+int wofdm_viterbi_decode_long(int device, int32_t rate, int32_t n_c,
+                              const int32_t *perm,          /* [n_c], or NULL */
+                              int32_t n_cw,
+                              const int8_t *soft,           /* [n_cw][n_c] */
+                              uint8_t *bits,                /* [n_cw][T] */
+                              int32_t *metric);             /* [n_cw], or NULL */
+
+/* The coded link with FRAME-SPANNING codewords: wofdm_rx_profile_coded's soft bits -- the same frames, quantiser, order within a
+ * symbol, n_c = k D and random-coset view --, but ONE zero-terminated codeword per point and frame over the point's data symbols,
+ * interleaved in time as well as in frequency, decoded by the streaming decoder of wofdm_viterbi_decode_long.
+ *   Codeword.  A point has S_d = S - 1 data symbols, S - 2 with post; its codeword has n_f = n_c S_d coded-stream positions and T =
+ * wofdm_code_steps(rate, n_f) steps per code.  (A point with S_d = 0 would carry no codeword and count nothing; the tracking
+ * receiver's own checks ask for S >= 3 with post, so S_d >= 1 in every call that passes them.)
+ *   Frame interleaver.  Coded-stream index c sits in data symbol 1 + j, j = c mod S_d, and with q = c div S_d at the symbol's
+ * position perm[(q + j sym_rot) mod n_c] (NULL perm: the identity).  For each j this is a bijection of the symbol's positions;
+ * consecutive coded bits go to consecutive symbols and, for sym_rot != 0, to different places of the band.  With S_d = 1 and sym_rot
+ * = 0 it is perm itself: the per-symbol call's codeword.
+ *   Arguments: every argument of wofdm_rx_profile_coded through codes, then sym_rot; the seven outputs of
+ * wofdm_rx_profile_tracking, which are that call's bytes; frame_errs[point][cell][code] = {info-bit errors (decoded u_t != 0, t < T
+ * - 6), codeword errors}, ACCUMULATED into; soft_bits as in wofdm_rx_profile_coded, the same bytes.
+ *   Identities, by bytes: frame_errs depends neither on where a chunk ends, nor on the other points or codes of the call, nor on
+ * whether soft_bits is requested; repeated calls are identical; it equals wofdm_viterbi_decode_long on the exported soft bits
+ * gathered through the frame interleaver; with S = 2, no post and sym_rot = 0 it is code_errs[...][0] of wofdm_rx_profile_coded.
+ *   Checks: wofdm_rx_profile_coded's -- without code_errs, and without its T < 7 per symbol: a symbol holds no codeword here --,
+ * then in this order WOFDM_E_INVALID for sym_rot outside [0, n_c); for NULL frame_errs; for a code whose T < 7 at an S_d in use;
+ * and WOFDM_E_UNSUPPORTED for a T > WOFDM_CODE_LONG_MAX_STEPS (which n_fft <= 1024, k <= 6 and S <= 64 never reach).  Every argument
+ * is checked before the device is touched; a failed check leaves all outputs as they were.
+ *   Chunks: wofdm_rx_profile_coded's formula plus 512 n_points ceil(T_max / 64) bytes per frame, the survivor history, T_max the
+ * longest codeword of the call; the codes of a chunk are decoded by one launch each and share the history.
+ *   A successful call holds the launch gate and counts for wofdm_rx_profile_kernel_ms.
+ *   Measured: tools/bench_rx_profile_coded_frame.py, profiles/rx_profile_coded_frame.txt. */
+int wofdm_rx_profile_coded_frame(const wofdm_cfg *cfg, int device,
+                                 const float *w_tx,             /* [pairs][P] */
+                                 const float *w_rx,             /* [pairs][N+tail_rx] */
+                                 const float *h,                /* [n_channels][n_taps][2] */
+                                 const float *snr_db,           /* [n_snr] */
+                                 const uint8_t *active,         /* [n_fft] or NULL */
+                                 const float *tx_mask,          /* [2P-1] or NULL */
+                                 const float *h_track,          /* [n_tracks][n_channels][n_knots][n_taps][2], or NULL */
+                                 int32_t n_tracks, int32_t n_knots, int32_t knot_step,
+                                 const uint8_t *aci_active,     /* [n_fft], or NULL */
+                                 const float *aci_h,            /* [n_channels][n_taps][2], or NULL = h */
+                                 const float *ref_power,        /* [pairs], or NULL */
+                                 int32_t n_points, const wofdm_link_point *points,
+                                 int32_t n_scales, const float *scales,
+                                 const uint8_t *pilots,         /* [n_fft], or NULL */
+                                 const wofdm_tracking_point *tracking, /* [n_points] */
+                                 float llr_scale,
+                                 const int32_t *perm,           /* [n_c], or NULL */
+                                 int32_t n_codes, const wofdm_code *codes,
+                                 int32_t sym_rot,               /* in [0, n_c) */
+                                 uint64_t *errs,                /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                                 double *err_power,             /* [n_points][cells][n_fft], or NULL */
+                                 uint64_t *sym_errs,            /* [n_points][cells][S-1][2], or NULL */
+                                 double *sym_power,             /* [n_points][cells][S-1], or NULL */
+                                 double *pa_power,              /* [n_points][cells][2], or NULL */
+                                 double *bit_penalty,           /* [n_points][cells][n_scales][n_fft], ACCUMULATED into */
+                                 double *sym_penalty,           /* [n_points][cells][n_scales][S-1], or NULL */
+                                 uint64_t *frame_errs,          /* [n_points][cells][n_codes][2], ACCUMULATED into */
+                                 int8_t *soft_bits);            /* [cells][frames][n_points][S-1][n_fft][8], or NULL */
+
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

@@ -20,7 +20,8 @@ as ``wofdm_amd`` through the shim module at the repository root.
                wofdm_rx_profile_pn), or with all five combined (GPU: wofdm_rx_profile_link), with soft decisions and the
                achievable rate beside the hard counters (GPU: wofdm_rx_profile_soft), behind a receiver that tracks with comb
                pilots and a postamble (GPU: wofdm_rx_profile_tracking), with 8-bit soft bits and a K = 7 Viterbi decoder behind
-               it (GPU: wofdm_rx_profile_coded, wofdm_viterbi_decode)
+               it (GPU: wofdm_rx_profile_coded, wofdm_viterbi_decode), per data symbol or with one codeword over the frame (GPU:
+               wofdm_rx_profile_coded_frame, wofdm_viterbi_decode_long)
   _lib         ctypes binding of libwofdm_hip.so (include/wofdm.h)
 """
 from . import variants  # noqa: F401
@@ -39,7 +40,7 @@ from .simulation import (Plan, ber_for_window_file, error_rates, make_cfg,  # no
 from ._lib import kernel_source_hash  # noqa: F401
 from .timefreq import (estimate_obr, frame_papr, papr_ccdf, papr_hist, run_timefreq, tx_papr_gpu,  # noqa: F401
                        tx_psd_batch_gpu, tx_waveform)
-from .channel_mask import (aci_for_window_file, coded_for_window_file, doppler_for_window_file, interference_for_window_file,  # noqa: F401
+from .channel_mask import (aci_for_window_file, coded_for_window_file, coded_frame_for_window_file, doppler_for_window_file, interference_for_window_file,  # noqa: F401
                            link_for_window_file, soft_for_window_file, pa_for_window_file, papr_for_window_file, pn_for_window_file, profile_for_window_file,
                            spectrum_for_window_file, sync_for_window_file, tracking_for_window_file)
 from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_db, frame_profile,  # noqa: F401
@@ -59,7 +60,10 @@ from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_d
                          rx_profile_tracking_gpu, rx_profile_tracking_host, tracking_equalise,
                          CODE_RATES, LLR_SCALE, RxProfileCoded, code_steps, coded_ber, coded_cwer, conv_encode, default_interleaver,
                          frame_profile_coded, rx_profile_coded_chunk_frames, rx_profile_coded_gpu, rx_profile_coded_host, soft_bits,
-                         viterbi_decode, viterbi_decode_gpu)
+                         viterbi_decode, viterbi_decode_gpu,
+                         RxProfileCodedFrame, coded_fer, coded_frame_ber, default_sym_rot, frame_codewords, frame_interleaver,
+                         frame_profile_coded_frame, rx_profile_coded_frame_chunk_frames, rx_profile_coded_frame_gpu,
+                         rx_profile_coded_frame_host, viterbi_decode_long_gpu)
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

@@ -43,6 +43,8 @@ SOFT_MAX_SCALES = 16
 #: wofdm_rx_profile_coded, wofdm_viterbi_decode (include/wofdm.h): most codes one call takes, most steps of a codeword
 CODE_MAX = 4
 CODE_MAX_STEPS = 4608
+#: wofdm_viterbi_decode_long, wofdm_rx_profile_coded_frame (include/wofdm.h): most steps of a codeword
+CODE_LONG_MAX_STEPS = 1048576
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -58,6 +60,7 @@ EXPORTS = (
     "wofdm_rx_profile_pa", "wofdm_tx_psd_batch_pa", "wofdm_rx_profile_pn",
     "wofdm_rx_profile_link", "wofdm_rx_profile_soft", "wofdm_rx_profile_tracking",
     "wofdm_rx_profile_coded", "wofdm_code_steps", "wofdm_viterbi_decode",
+    "wofdm_viterbi_decode_long", "wofdm_rx_profile_coded_frame",
 )
 
 
@@ -220,6 +223,10 @@ def load():
     L.wofdm_code_steps.argtypes = [i32, i32]
     L.wofdm_code_steps.restype = C.c_int
     L.wofdm_viterbi_decode.argtypes = [C.c_int, i32, i32, vp, i32, vp, vp, vp]
+    L.wofdm_viterbi_decode_long.argtypes = [C.c_int, i32, i32, vp, i32, vp, vp, vp]
+    L.wofdm_rx_profile_coded_frame.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
+                                               C.POINTER(LinkPoint), i32, vp, vp, C.POINTER(TrackingPoint), C.c_float, vp, i32,
+                                               C.POINTER(Code), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_tx_psd_batch_pa.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, C.POINTER(PaPoint), vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L

@@ -1690,6 +1690,9 @@ struct rx_call {
     struct {
         bool on; float llr_scale; const int32_t *perm; int32_t n_codes; const wofdm_code *codes; uint64_t *code_errs; int8_t *soft_bits;
     } code;
+    // the frame-spanning code of wofdm_rx_profile_coded_frame: code is on with it (code_errs null) and gives the soft bits, the
+    // interleaver within a symbol and the codes; the rotation from symbol to symbol and the counters
+    struct { bool on; int32_t sym_rot; uint64_t *frame_errs; } frm;
 };
 
 // the receive side's geometry beside the Tx chain's, and the cells of the call
@@ -1716,9 +1719,16 @@ struct rx_run {
     std::vector<wofdm_tpoint> tp;
     std::vector<int32_t> gather;      // the coded link: byte 8 n + i of coded-stream index c in a symbol's soft bits
     int32_t csteps[WOFDM_CODE_CODES];
+    // the frame-spanning code: per variant (0: the points without post, S_d = S - 1; 1: those with, S_d = S - 2; wofdm_link.h)
+    // whether a point uses it, the codeword's positions, the gather table, per code the steps (0: unused), and the history's blocks
+    bool fuse[2];
+    int32_t fnc[2], fsteps[WOFDM_CODE_CODES][2], hist_blocks;
+    std::vector<int32_t> fgather[2];
     int n_knots, knot_step;
     // device
-    size_t chunk, n_out, n_sym, n_ptot, n_bpen, n_spen, n_cerr;
+    size_t chunk, n_out, n_sym, n_ptot, n_bpen, n_spen, n_cerr, n_ferr;
+    dev_buf<int32_t> d_fgather[2];
+    dev_buf<unsigned long long> d_hist, d_ferrs;
     dev_buf<int8_t> d_sbits;
     dev_buf<int32_t> d_gather;
     dev_buf<unsigned long long> d_cerrs;
@@ -2015,7 +2025,8 @@ int prep_code(rx_run &r)
 {
     const auto &cd = r.c.code;
     if (!cd.on) return WOFDM_OK;
-    if (!cd.codes || !cd.code_errs) return fail(WOFDM_E_INVALID, "NULL argument (codes or code_errs)");
+    const bool frame = r.c.frm.on;                                     // (its counters and lengths: prep_frame)
+    if (!cd.codes || (!frame && !cd.code_errs)) return fail(WOFDM_E_INVALID, "NULL argument (codes or code_errs)");
     if (!std::isfinite(cd.llr_scale) || !(cd.llr_scale > 0.f)) return fail(WOFDM_E_INVALID, "llr_scale must be finite and positive");
     if (cd.n_codes < 1) return fail(WOFDM_E_INVALID, "n_codes=%d must be >= 1", cd.n_codes);
     if (cd.n_codes > WOFDM_CODE_MAX) return fail(WOFDM_E_UNSUPPORTED, "n_codes=%d exceeds %d", cd.n_codes, WOFDM_CODE_MAX);
@@ -2029,7 +2040,7 @@ int prep_code(rx_run &r)
         if (q.rate < 0 || q.rate > 2) return fail(WOFDM_E_INVALID, "codes[%d].rate=%d must be 0, 1 or 2", i, q.rate);
         if (q.reserved[0] != 0 || q.reserved[1] != 0 || q.reserved[2] != 0) return fail(WOFDM_E_INVALID, "codes[%d].reserved must be 0", i);
         r.csteps[i] = code_steps(q.rate, n_c);
-        if (r.csteps[i] < 7)
+        if (!frame && r.csteps[i] < 7)
             return fail(WOFDM_E_INVALID, "codes[%d]: %d coded bits per symbol give %d steps, at least 7 are needed", i, n_c, r.csteps[i]);
     }
     if (cd.perm && !is_permutation(cd.perm, n_c)) return fail(WOFDM_E_INVALID, "perm is not a permutation of 0 ... %d", n_c - 1);
@@ -2040,6 +2051,50 @@ int prep_code(rx_run &r)
     for (int32_t c = 0; c < n_c; ++c) {
         const int32_t j = cd.perm ? cd.perm[c] : c;
         r.gather[(size_t)c] = 8 * bins[(size_t)(j / k)] + j % k;
+    }
+    return WOFDM_OK;
+}
+
+// wofdm_viterbi_decode_long and the frame-spanning code: the history is 512 bytes per block of 64 steps
+int32_t hist_blocks_of(int32_t steps) { return (steps + 63) / 64; }
+
+// the frame-spanning code, in the order include/wofdm.h documents, behind prep_code (which leaves the gather table of one symbol);
+// leaves per variant the gather table of the frame: coded-stream index c sits in data symbol 1 + j, j = c mod S_d, at the
+// symbol's position perm[(c div S_d + j sym_rot) mod n_c], which is byte 8 N j + gather[(c div S_d + j sym_rot) mod n_c] of the
+// (frame, point)'s soft bits [S - 1][N][8]
+int prep_frame(rx_run &r)
+{
+    const auto &fm = r.c.frm;
+    if (!fm.on) return WOFDM_OK;
+    const int32_t n_c = (int32_t)r.gather.size(), S = r.g.S, N = r.g.N;
+    if (fm.sym_rot < 0 || fm.sym_rot >= n_c) return fail(WOFDM_E_INVALID, "sym_rot=%d outside [0, %d)", fm.sym_rot, n_c);
+    if (!fm.frame_errs) return fail(WOFDM_E_INVALID, "NULL argument (frame_errs)");
+    r.fuse[0] = r.fuse[1] = false;
+    for (int i = 0; i < r.c.n_points; ++i) r.fuse[r.tp[(size_t)i].post ? 1 : 0] = true;
+    r.hist_blocks = 1;
+    for (int v = 0; v < 2; ++v) {
+        const int64_t s_d = S - 1 - v;
+        r.fnc[v] = r.fuse[v] && s_d >= 1 ? (int32_t)((int64_t)n_c * s_d) : 0;       // (n_c <= 6 * 1024, S <= 64)
+    }
+    for (int pass = 0; pass < 2; ++pass)                                 // (every T < 7 before any T beyond the limit)
+        for (int i = 0; i < r.c.code.n_codes; ++i)
+            for (int v = 0; v < 2; ++v) {
+                const int32_t T = r.fnc[v] > 0 ? code_steps(r.c.code.codes[i].rate, r.fnc[v]) : 0;
+                r.fsteps[i][v] = T;
+                if (r.fnc[v] == 0) continue;
+                if (pass == 0 && T < 7)
+                    return fail(WOFDM_E_INVALID, "codes[%d]: %d coded bits per frame give %d steps, at least 7 are needed", i, r.fnc[v], T);
+                if (pass == 1 && T > WOFDM_CODE_LONG_MAX_STEPS)
+                    return fail(WOFDM_E_UNSUPPORTED, "codes[%d]: %d steps, more than %d", i, T, WOFDM_CODE_LONG_MAX_STEPS);
+                r.hist_blocks = std::max(r.hist_blocks, hist_blocks_of(T));
+            }
+    for (int v = 0; v < 2; ++v) {
+        const int32_t s_d = S - 1 - v;
+        r.fgather[v].resize((size_t)r.fnc[v]);
+        for (int32_t c = 0; c < r.fnc[v]; ++c) {
+            const int32_t j = c % s_d, q = c / s_d;
+            r.fgather[v][(size_t)c] = 8 * N * j + r.gather[(size_t)(((int64_t)q + (int64_t)j * fm.sym_rot) % n_c)];
+        }
     }
     return WOFDM_OK;
 }
@@ -2081,7 +2136,10 @@ uint64_t rx_job_bytes(const rx_run &r)
     if (r.nb) words += (S + 1) * N + (T + B) + (S + 1) * Lm;              // the neighbour's chain of S + 1 symbols
     // the demapper: per point and scale the penalties of every data symbol's bins and the symbols' sums, fp32
     // the coded link: 8 bytes of soft bits per point, data symbol and bin (the decoder's survivors are in LDS)
-    return 8 * words + (c.soft.on ? 4 * NP * (uint64_t)c.soft.n_scales * ((S - 1) * N + S) : 0) + (c.code.on ? 8 * NP * (S - 1) * N : 0);
+    // the frame-spanning code: 512 bytes of survivor history per point and block of 64 steps of the longest codeword, which the
+    // codes' launches share
+    return 8 * words + (c.soft.on ? 4 * NP * (uint64_t)c.soft.n_scales * ((S - 1) * N + S) : 0) + (c.code.on ? 8 * NP * (S - 1) * N : 0) +
+           (c.frm.on ? 512 * NP * (uint64_t)r.hist_blocks : 0);
 }
 
 // ---- the stages' device side: allocation, upload, and the stage's parameters in the chunk ----
@@ -2219,10 +2277,12 @@ int stage_code(rx_run &r)
     const auto &cd = r.c.code;
     if (!cd.on) return WOFDM_OK;
     const rx_geom &g = r.g;
+    // (the frame-spanning code has counters and gather tables of its own: stage_frame)
+    const bool sym = !r.c.frm.on;
     if (!r.d_sbits.alloc(r.chunk * (size_t)r.c.n_points * (g.S - 1) * g.N * 8) || !r.d_gather.alloc(r.gather.size()) ||
-        !r.d_cerrs.alloc(r.n_cerr))
+        (sym && !r.d_cerrs.alloc(r.n_cerr)))
         return fail(WOFDM_E_NOMEM, "device allocation failed (coded link)");
-    if (!r.d_gather.upload(r.gather.data(), r.gather.size()) || hipMemset(r.d_cerrs, 0, r.n_cerr * 8) != hipSuccess)
+    if (!r.d_gather.upload(r.gather.data(), r.gather.size()) || (sym && hipMemset(r.d_cerrs, 0, r.n_cerr * 8) != hipSuccess))
         return fail(WOFDM_E_HIP, "upload failed");
     wofdm_codeparams &k = r.ck.cd;
     k.llr_scale = cd.llr_scale; k.soft = r.d_sbits; k.gather = r.d_gather; k.n_c = (int32_t)r.gather.size(); k.n_codes = cd.n_codes;
@@ -2232,6 +2292,29 @@ int stage_code(rx_run &r)
     }
     k.errs = r.d_cerrs;
     r.ck.code_on = true;
+    return WOFDM_OK;
+}
+
+// the frame-spanning code's side (behind stage_code): the gather tables in use, the chunk's history, the counters
+int stage_frame(rx_run &r)
+{
+    if (!r.c.frm.on) return WOFDM_OK;
+    wofdm_longparams &k = r.ck.fr;
+    k = wofdm_longparams{};
+    for (int v = 0; v < 2; ++v) {
+        if (r.fnc[v] == 0) continue;
+        if (!r.d_fgather[v].alloc(r.fgather[v].size())) return fail(WOFDM_E_NOMEM, "device allocation failed (frame code)");
+        if (!r.d_fgather[v].upload(r.fgather[v].data(), r.fgather[v].size())) return fail(WOFDM_E_HIP, "upload failed");
+        k.gather[v] = r.d_fgather[v];
+        k.n_c[v] = r.fnc[v];
+    }
+    if (!r.d_hist.alloc(r.chunk * (size_t)r.c.n_points * (size_t)r.hist_blocks * 64) || !r.d_ferrs.alloc(r.n_ferr))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (frame code)");
+    if (hipMemset(r.d_ferrs, 0, r.n_ferr * 8) != hipSuccess) return fail(WOFDM_E_HIP, "upload failed");
+    k.hist = r.d_hist; k.hist_blocks = r.hist_blocks; k.errs = r.d_ferrs;
+    for (int i = 0; i < r.c.code.n_codes; ++i)
+        for (int v = 0; v < 2; ++v) r.ck.fr_steps[i][v] = r.fsteps[i][v];
+    r.ck.frame_on = true;
     return WOFDM_OK;
 }
 
@@ -2278,7 +2361,7 @@ int rx_profile_run(const rx_call &c)
         (rc = check_allocation(c.active, r.g.N, &r.act)) != WOFDM_OK || (rc = prep_nb(r)) != WOFDM_OK ||
         (rc = prep_sync(r)) != WOFDM_OK || (rc = prep_pn(r)) != WOFDM_OK || (rc = check_knots(r)) != WOFDM_OK ||
         (rc = prep_link(r)) != WOFDM_OK || (rc = prep_amp(r)) != WOFDM_OK || (rc = prep_track(r)) != WOFDM_OK ||
-        (rc = prep_code(r)) != WOFDM_OK || (rc = use_device(c.device)) != WOFDM_OK)
+        (rc = prep_code(r)) != WOFDM_OK || (rc = prep_frame(r)) != WOFDM_OK || (rc = use_device(c.device)) != WOFDM_OK)
         return rc;
     g_rxprof_ms = 0.f;
     const rx_geom &g = r.g;
@@ -2293,14 +2376,17 @@ int rx_profile_run(const rx_call &c)
     r.n_bpen = NP * g.cells * NSC * g.N;
     r.n_spen = NP * g.cells * NSC * (g.S - 1);
     r.n_cerr = c.code.on ? NP * g.cells * (size_t)c.code.n_codes * (g.S - 1) * 2 : 0;
+    r.n_ferr = c.frm.on ? NP * g.cells * (size_t)c.code.n_codes * 2 : 0;
+    if (c.frm.on) r.n_cerr = 0;
     if ((rc = stage_base(r)) != WOFDM_OK || (rc = stage_points(r)) != WOFDM_OK || (rc = stage_amp(r)) != WOFDM_OK ||
         (rc = stage_pn(r)) != WOFDM_OK || (rc = stage_link(r)) != WOFDM_OK || (rc = stage_soft(r)) != WOFDM_OK ||
-        (rc = stage_track(r)) != WOFDM_OK || (rc = stage_code(r)) != WOFDM_OK || (rc = stage_nb(r)) != WOFDM_OK)
+        (rc = stage_track(r)) != WOFDM_OK || (rc = stage_code(r)) != WOFDM_OK || (rc = stage_frame(r)) != WOFDM_OK ||
+        (rc = stage_nb(r)) != WOFDM_OK)
         return rc;
     // (a neighbour that loads no bin: the plain kernel)
     r.ck.arm = c.arm == RXP_ACI && !r.nb ? RXP_PLAIN : c.arm;
     std::vector<unsigned long long> herr(2 * r.n_out), hserr(2 * r.n_sym);
-    std::vector<unsigned long long> hcerr(r.n_cerr);
+    std::vector<unsigned long long> hcerr(r.n_cerr), hferr(r.n_ferr);
     std::vector<double> hpow(r.n_out), hspow(r.n_sym), hptot(r.n_ptot), hbpen(r.n_bpen), hspen(r.n_spen);
     float ms = 0.f;
     hipError_t e = hipSuccess;
@@ -2318,7 +2404,7 @@ int rx_profile_run(const rx_call &c)
     }, &e, &ms);
     if (rc != WOFDM_OK) return rc;
     if (e != hipSuccess || !fetch(herr, r.d_errs.p) || !fetch(hpow, r.d_pow.p) || !fetch(hserr, r.d_serrs.p) || !fetch(hspow, r.d_stot.p) ||
-        !fetch(hptot, r.d_ptot.p) || !fetch(hbpen, r.d_btot.p) || !fetch(hspen, r.d_sptot.p) || !fetch(hcerr, r.d_cerrs.p))
+        !fetch(hptot, r.d_ptot.p) || !fetch(hbpen, r.d_btot.p) || !fetch(hspen, r.d_sptot.p) || !fetch(hcerr, r.d_cerrs.p) || !fetch(hferr, r.d_ferrs.p))
         return fail(WOFDM_E_HIP, "receive-profile kernels or copy-back failed: %s",
                     hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
     add_to(c.errs, herr);
@@ -2329,6 +2415,7 @@ int rx_profile_run(const rx_call &c)
     add_to(c.soft.bit_penalty, hbpen);
     add_to(c.soft.sym_penalty, hspen);
     add_to(c.code.code_errs, hcerr);
+    add_to(c.frm.frame_errs, hferr);
     g_rxprof_ms = ms;
     return WOFDM_OK;
 }
@@ -2484,7 +2571,7 @@ static int rx_tracking_call(const wofdm_cfg *cfg, int device, const float *w_tx,
                             const wofdm_link_point *points, int32_t n_scales, const float *scales, const uint8_t *pilots,
                             const wofdm_tracking_point *tracking, uint64_t *errs, double *err_power, uint64_t *sym_errs,
                             double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty,
-                            const decltype(rx_call::code) *code)
+                            const decltype(rx_call::code) *code, const decltype(rx_call::frm) *frm = nullptr)
 {
     if (!scales || !bit_penalty || !tracking) return fail(WOFDM_E_INVALID, "NULL argument (scales, bit_penalty or tracking)");
     if (n_scales < 1) return fail(WOFDM_E_INVALID, "n_scales=%d must be >= 1", n_scales);
@@ -2500,6 +2587,7 @@ static int rx_tracking_call(const wofdm_cfg *cfg, int device, const float *w_tx,
     c.soft = {true, n_scales, scales, bit_penalty, sym_penalty};
     c.trk = {true, pilots, tracking};
     if (code) c.code = *code;
+    if (frm) c.frm = *frm;
     const int rc = rx_link_stages(c, n_points, points);
     return rc != WOFDM_OK ? rc : rx_profile_run(c);
 }
@@ -2528,6 +2616,22 @@ int wofdm_rx_profile_coded(const wofdm_cfg *cfg, int device, const float *w_tx, 
     return rx_tracking_call(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active, aci_h,
                             ref_power, n_points, points, n_scales, scales, pilots, tracking, errs, err_power, sym_errs, sym_power,
                             pa_power, bit_penalty, sym_penalty, &code);
+}
+
+int wofdm_rx_profile_coded_frame(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h,
+                                 const float *snr_db, const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks,
+                                 int32_t n_knots, int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power,
+                                 int32_t n_points, const wofdm_link_point *points, int32_t n_scales, const float *scales,
+                                 const uint8_t *pilots, const wofdm_tracking_point *tracking, float llr_scale, const int32_t *perm,
+                                 int32_t n_codes, const wofdm_code *codes, int32_t sym_rot, uint64_t *errs, double *err_power,
+                                 uint64_t *sym_errs, double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty,
+                                 uint64_t *frame_errs, int8_t *soft_bits)
+{
+    const decltype(rx_call::code) code = {true, llr_scale, perm, n_codes, codes, nullptr, soft_bits};
+    const decltype(rx_call::frm) frm = {true, sym_rot, frame_errs};
+    return rx_tracking_call(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active, aci_h,
+                            ref_power, n_points, points, n_scales, scales, pilots, tracking, errs, err_power, sym_errs, sym_power,
+                            pa_power, bit_penalty, sym_penalty, &code, &frm);
 }
 
 int wofdm_code_steps(int32_t rate, int32_t n_c)
@@ -2567,6 +2671,56 @@ int wofdm_viterbi_decode(int device, int32_t rate, int32_t n_c, const int32_t *p
         std::lock_guard<std::mutex> gate(g_gate_mu);
         const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the decoder is in every auxiliary unit)
         e = ax && ax->viterbi ? ax->viterbi(&cd, nullptr) : hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess || !fetch(hbits, d_bits.p) || !fetch(hmetric, d_metric.p))
+        return fail(WOFDM_E_HIP, "decoder kernel or copy-back failed: %s", hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
+    std::memcpy(bits, hbits.data(), n_bits);
+    if (metric) std::memcpy(metric, hmetric.data(), hmetric.size() * sizeof(int32_t));
+    return WOFDM_OK;
+}
+
+int wofdm_viterbi_decode_long(int device, int32_t rate, int32_t n_c, const int32_t *perm, int32_t n_cw, const int8_t *soft, uint8_t *bits,
+                              int32_t *metric)
+{
+    if (!soft || !bits) return fail(WOFDM_E_INVALID, "NULL argument (soft or bits)");
+    if (rate < 0 || rate > 2) return fail(WOFDM_E_INVALID, "rate=%d must be 0, 1 or 2", rate);
+    if (n_c < 1 || n_cw < 1) return fail(WOFDM_E_INVALID, "n_c=%d and n_cw=%d must be >= 1", n_c, n_cw);
+    const int32_t T = code_steps(rate, n_c);
+    if (T < 7) return fail(WOFDM_E_INVALID, "n_c=%d gives %d steps, at least 7 are needed", n_c, T);
+    if (T > WOFDM_CODE_LONG_MAX_STEPS)
+        return fail(WOFDM_E_UNSUPPORTED, "n_c=%d gives %d steps, more than %d", n_c, T, WOFDM_CODE_LONG_MAX_STEPS);
+    if (perm && !is_permutation(perm, n_c)) return fail(WOFDM_E_INVALID, "perm is not a permutation of 0 ... %d", n_c - 1);
+    int rc = use_device(device);
+    if (rc != WOFDM_OK) return rc;
+    std::vector<int32_t> gather((size_t)n_c);
+    for (int32_t c = 0; c < n_c; ++c) gather[(size_t)c] = perm ? perm[c] : c;
+    // the codewords in groups whose history stays within the receive profiles' chunk budget (one codeword: at most 8 MiB)
+    const int32_t blocks = hist_blocks_of(T);
+    const size_t group = (size_t)std::min<uint64_t>((uint64_t)n_cw, std::max<uint64_t>(1, WOFDM_RX_PROFILE_CHUNK_BYTES / (512ull * (uint64_t)blocks)));
+    const size_t n_soft = (size_t)n_cw * (size_t)n_c, n_bits = (size_t)n_cw * (size_t)T;
+    dev_buf<int8_t> d_soft;
+    dev_buf<int32_t> d_gather, d_metric;
+    dev_buf<uint8_t> d_bits;
+    dev_buf<unsigned long long> d_hist;
+    if (!d_soft.alloc(n_soft) || !d_gather.alloc(gather.size()) || !d_bits.alloc(n_bits) || !d_metric.alloc((size_t)n_cw) ||
+        !d_hist.alloc(group * (size_t)blocks * 64))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (decoder)");
+    if (!d_soft.upload(soft, n_soft) || !d_gather.upload(gather.data(), gather.size())) return fail(WOFDM_E_HIP, "upload failed");
+    wofdm_longparams lp{};
+    lp.hist = d_hist; lp.gather[0] = d_gather; lp.n_c[0] = n_c; lp.steps[0] = T; lp.rate = rate; lp.hist_blocks = blocks;
+    lp.cw_stride = n_c;
+    std::vector<uint8_t> hbits(n_bits);
+    std::vector<int32_t> hmetric((size_t)n_cw);
+    hipError_t e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the decoder is in every auxiliary unit)
+        for (size_t w0 = 0; e == hipSuccess && w0 < (size_t)n_cw; w0 += group) {
+            lp.soft = d_soft.p + w0 * (size_t)n_c; lp.bits = d_bits.p + w0 * (size_t)T; lp.metric = d_metric.p + w0;
+            lp.n_cw = (uint32_t)std::min(group, (size_t)n_cw - w0);
+            e = ax && ax->viterbi_long ? ax->viterbi_long(&lp, nullptr) : hipErrorInvalidValue;
+        }
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     if (e != hipSuccess || !fetch(hbits, d_bits.p) || !fetch(hmetric, d_metric.p))

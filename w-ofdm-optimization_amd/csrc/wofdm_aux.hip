@@ -2015,6 +2015,148 @@ __global__ void __launch_bounds__(64) wofdm_viterbi_kernel(const wofdm_codeparam
     }
 }
 
+// The pair (dA, dB) of step t as wofdm_viterbi_kernel forms it, in two stages so that both loads of a block can be in flight
+// while an earlier block is walked: the byte offsets of the two kept outputs through the gather table (-1: the pattern keeps
+// nothing, c >= n_c, or t >= T), then the soft bits behind them.
+__device__ __forceinline__ void vlong_offsets(const int32_t *__restrict__ gather, int rate, int n_c, int T, int t, int &oa, int &ob)
+{
+    int ca, cb;
+    if (rate == 0) {
+        ca = 2 * t;
+        cb = 2 * t + 1;
+    } else if (rate == 1) {
+        const int q = t >> 1, ph = t & 1;
+        ca = 3 * q + 2 * ph;
+        cb = ph == 0 ? 3 * q + 1 : -1;
+    } else {
+        const int q = t / 3, ph = t - 3 * q;
+        ca = ph == 2 ? -1 : 4 * q + 2 * ph;
+        cb = ph == 1 ? -1 : 4 * q + (ph == 0 ? 1 : 3);
+    }
+    // (the loads themselves are unconditional, on an index clamped into the table, so that nothing waits for them here)
+    const int ga = gather[min(max(ca, 0), n_c - 1)], gb = gather[min(max(cb, 0), n_c - 1)];
+    oa = t < T && ca >= 0 && ca < n_c ? ga : -1;
+    ob = t < T && cb >= 0 && cb < n_c ? gb : -1;
+}
+typedef short vlong_i16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int vlong_pair(const int8_t *__restrict__ soft, int oa, int ob)
+{
+    const int sa = soft[max(oa, 0)], sb = soft[max(ob, 0)];             // (unconditional as well: byte 0 is the block's)
+    const int da = oa >= 0 ? sa : 0, db = ob >= 0 ? sb : 0;
+    return (int)(((uint32_t)da & 0xFFFFu) | ((uint32_t)db << 16));       // two int16
+}
+
+// The decoder of wofdm_viterbi_kernel for codewords of any length up to WOFDM_CODE_LONG_STEPS (wofdm_longparams): the same code,
+// metric, start and tie rules -- the decoded bits and the metric are that kernel's wherever it takes the word --, one wave per
+// codeword, lane = state, and no LDS: the survivor history goes to device memory in blocks of 64 steps.
+//   Forward.  Lane l holds the pair of step 64 b + l of the current block; the pairs of block b + 1 and the gather offsets of
+// block b + 2 are loaded before block b is walked.  Step i of a block reads its pair from lane i (v_readlane: a constant lane in
+// the unrolled full block, a wave-uniform one in the last, partial block), and every lane keeps its own decision as bit i of a
+// 64-bit word: the block's history is the 64 x 64 bit matrix [state][step], one word per lane, and leaves as one 512-byte
+// store.  (The transpose of wofdm_viterbi_kernel's ballot words: a lane ORs a bit into its own register, so the step needs
+// neither a ballot nor a write into another lane.)
+//   Traceback.  Blocks descending: one 512-byte load, one word per lane, then the steps descending -- the decision of the path's
+// state st at step i is bit i of lane st's word, a lane read with a wave-uniform index; the state and the block's 64 decoded
+// bits are wave-uniform.  The profile counts the masks' bits -- t < T - 6: info bits -- and ends with integer atomics where the
+// codeword has an error; the decoder alone stores bit l of a block's mask from lane l, one byte each.
+//   Every trip count is wave-uniform; the workgroup is the one wave, and no wave waits for another.  int32 suffices: |d| <= 128,
+// two outputs per step, so |metric| <= 2^28 at T = 2^20 beside the 2^30 of the start.
+__global__ void __launch_bounds__(64) wofdm_viterbi_long_kernel(const wofdm_longparams lp)
+{
+    const int lane = threadIdx.x;
+    const uint64_t w = blockIdx.x;
+    int v = 0, pt = 0;
+    if (lp.errs != nullptr) {
+        pt = (int)(w % (uint64_t)lp.n_points);
+        v = lp.pts[pt].post != 0 ? 1 : 0;
+    }
+    const int rate = lp.rate, T = lp.steps[v], n_c = lp.n_c[v];
+    if (T < 7) return;                                                  // (a point without a data symbol: wave-uniform)
+    const int n_blocks = (T + 63) >> 6;
+    const int32_t *__restrict__ gather = lp.gather[v];
+    const int8_t *__restrict__ soft = lp.soft + (int64_t)w * lp.cw_stride;
+    unsigned long long *__restrict__ hist = lp.hist + (size_t)w * (size_t)lp.hist_blocks * 64;
+
+    const int p0 = (lane << 1) & 63, u = lane >> 5, r0 = (u << 6) | p0;
+    const bool a0 = (__popc(r0 & 0133) & 1) != 0, b0 = (__popc(r0 & 0171) & 1) != 0;
+    int m = lane == 0 ? 0 : (1 << 30);
+    // one step: the survivor into this lane's state; its decision is bit i of the lane's history word of the block
+    uint32_t hlo, hhi;
+    // (the branch metric is a dot product of the step's pair, two int16, with the lane's 0 / 1 pair: v_dot2c_i32_i16, exact)
+    const vlong_i16x2 sel0 = {(short)(a0 ? 1 : 0), (short)(b0 ? 1 : 0)}, sel1 = {(short)(a0 ? 0 : 1), (short)(b0 ? 0 : 1)};
+    const auto step = [&](int i, int pair) {
+        const vlong_i16x2 d = __builtin_bit_cast(vlong_i16x2, pair);
+        const int c0 = __builtin_amdgcn_sdot2(sel0, d, __shfl(m, p0, 64), false);
+        const int c1 = __builtin_amdgcn_sdot2(sel1, d, __shfl(m, p0 | 1, 64), false);
+        const bool dec = c1 < c0;
+        m = dec ? c1 : c0;
+        if (i < 32)
+            hlo |= dec ? 1u << i : 0u;
+        else
+            hhi |= dec ? 1u << (i - 32) : 0u;
+    };
+    int dp, oa, ob;
+    vlong_offsets(gather, rate, n_c, T, lane, oa, ob);
+    dp = vlong_pair(soft, oa, ob);
+    vlong_offsets(gather, rate, n_c, T, 64 + lane, oa, ob);
+    for (int b = 0; b < n_blocks; ++b) {
+        int noa, nob;
+        const int ndp = vlong_pair(soft, oa, ob);                        // block b + 1 (zeros behind the codeword's end)
+        vlong_offsets(gather, rate, n_c, T, 64 * (b + 2) + lane, noa, nob);
+        hlo = hhi = 0u;
+        const int n = T - 64 * b;
+        if (n >= 64) {
+#pragma unroll
+            for (int i = 0; i < 64; ++i) step(i, __builtin_amdgcn_readlane(dp, i));
+        } else {
+            for (int i = 0; i < n; ++i) step(i, __builtin_amdgcn_readlane(dp, i));
+        }
+        hist[(size_t)b * 64 + (size_t)lane] = ((unsigned long long)hhi << 32) | (unsigned long long)hlo;
+        dp = ndp; oa = noa; ob = nob;
+    }
+    // (a lane reads back what it stored itself: program order, no fence is needed)
+    int st = 0, info = 0;
+    bool any = false;
+    uint8_t *__restrict__ out = lp.errs == nullptr ? lp.bits + w * (uint64_t)T : nullptr;
+    for (int b = n_blocks - 1; b >= 0; --b) {
+        const unsigned long long hw = hist[(size_t)b * 64 + (size_t)lane];
+        const int wlo = (int)(uint32_t)hw, whi = (int)(uint32_t)(hw >> 32);
+        const int n = T - 64 * b;
+        unsigned long long mask = 0ull;
+        // step i of the block: the decision of the path's state st is bit i of lane st's word
+        const auto back = [&](int i) {
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane(i < 32 ? wlo : whi, st);
+            mask |= (unsigned long long)(st >> 5) << i;
+            st = ((st << 1) & 63) | (int)((word >> (i & 31)) & 1u);
+        };
+        if (n >= 64) {
+#pragma unroll
+            for (int i = 63; i >= 0; --i) back(i);
+        } else {
+            for (int i = n - 1; i >= 0; --i) back(i);
+        }
+        if (out != nullptr) {
+            if (lane < n) out[(size_t)b * 64 + (size_t)lane] = (uint8_t)((mask >> lane) & 1ull);
+        } else {
+            // info bits: t < T - 6, the first lim = T - 6 - 64 b of the block
+            const int lim = T - 6 - 64 * b;
+            const unsigned long long im = lim >= 64 ? ~0ull : (lim <= 0 ? 0ull : (1ull << lim) - 1ull);
+            info += __popcll(mask & im);
+            any = any || mask != 0ull;
+        }
+    }
+    if (lp.errs != nullptr) {
+        if (lane == 0 && any) {
+            const uint64_t job = w / (uint64_t)lp.n_points, cell = (lp.item0 + job) / lp.frames;
+            unsigned long long *e = lp.errs + (((uint64_t)pt * lp.cells + cell) * (uint64_t)lp.n_codes + (uint64_t)lp.code) * 2;
+            if (info != 0) atomicAdd(e, (unsigned long long)info);
+            atomicAdd(e + 1, 1ull);
+        }
+    } else if (lane == 0 && lp.metric != nullptr) {
+        lp.metric[w] = m;
+    }
+}
+
 // totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
 template <int N>
 __global__ void __launch_bounds__(64) wofdm_rxprof_reduce_kernel(const wofdm_rparams p, uint64_t cell0)
@@ -2540,6 +2682,20 @@ unsigned viterbi_lds(const wofdm_codeparams &cd)
     for (int i = 0; i < cd.n_codes; ++i) T = cd.steps[i] > T ? cd.steps[i] : T;
     return 11u * (unsigned)T;
 }
+// the streaming decoder: the variants in use (profile: both may be, and one without a codeword has steps 0), the history's room
+bool viterbi_long_ok(const wofdm_longparams &lp, bool profile)
+{
+    if (lp.rate < 0 || lp.rate > 2 || lp.soft == nullptr || lp.hist == nullptr || lp.n_cw < 1 || lp.hist_blocks < 1) return false;
+    for (int v = 0; v < (profile ? 2 : 1); ++v) {
+        if (profile && lp.steps[v] == 0) continue;
+        if (lp.steps[v] < 7 || lp.steps[v] > WOFDM_CODE_LONG_STEPS || lp.n_c[v] < 1 || lp.gather[v] == nullptr ||
+            (lp.steps[v] + 63) / 64 > lp.hist_blocks)
+            return false;
+    }
+    return profile ? lp.errs != nullptr && lp.pts != nullptr && lp.n_points >= 1 && lp.code >= 0 && lp.code < lp.n_codes &&
+                         lp.bits == nullptr && lp.frames >= 1
+                   : lp.errs == nullptr && lp.bits != nullptr;
+}
 // the ordered sums of the chunk onto the totals: per point of sp, or (null) the plain ones
 void rxprof_reduce_launch(const wofdm_rparams &r, const wofdm_sparams *sp, hipStream_t s)
 {
@@ -2568,8 +2724,10 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
     const bool link = c.arm == RXP_LINK, points = MAX_POINTS[c.arm] > 0;
     const bool nb = c.arm == RXP_ACI || (link && c.nb_on), sync = c.arm == RXP_SYNC || link, knots = c.arm == RXP_DOPPLER || link;
     const bool amp = c.arm == RXP_PA || link, walk = c.arm == RXP_PN || link, soft = link && c.soft_on, track = soft && c.track_on;
-    const bool code = track && c.code_on;
-    if (nb != c.nb_on || soft != c.soft_on || track != c.track_on || code != c.code_on || (code && !viterbi_ok(c.cd, true)) ||
+    const bool code = track && c.code_on, frame = code && c.frame_on;
+    if (nb != c.nb_on || soft != c.soft_on || track != c.track_on || code != c.code_on || frame != c.frame_on ||
+        (code && !frame && !viterbi_ok(c.cd, true)) ||
+        (frame && (c.cd.soft == nullptr || !(c.cd.llr_scale > 0.f) || c.cd.n_codes < 1 || c.cd.n_codes > WOFDM_CODE_CODES)) ||
         (track && (c.tk.pts == nullptr || r.S > 64)) || !rxprof_args_ok(&c.tx, r) || (points && !rxprof_points_ok(c.sp, r, MAX_POINTS[c.arm])) ||
         (nb && !rxprof_nb_ok(c, !link)) || (sync && (c.sp.pts == nullptr || c.sp.base == nullptr)) ||
         (knots && !rxprof_knots_ok(c.dp, r, link, link ? c.max_theta : 0)) || (amp && !rxprof_pa_ok(c)) ||
@@ -2623,7 +2781,22 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
         hipLaunchKernelGGL(wofdm_rxprof_soft_reduce_kernel<N>, dim3(N / 64 + 1, n_cells, (unsigned)(c.sp.n_points * c.soft.n_scales)),
                            dim3(64), 0, s, r, c.sp, c.soft, cell0);
     }
-    if (code) {
+    if (frame) {
+        // the decoder behind the soft bits: one wave per (frame, point), one launch per code -- they share the history
+        wofdm_longparams lp = c.fr;
+        lp.soft = c.cd.soft;
+        lp.cw_stride = (int64_t)(r.S - 1) * N * 8;
+        lp.pts = c.tk.pts; lp.n_points = c.sp.n_points; lp.n_codes = c.cd.n_codes;
+        lp.item0 = r.item0; lp.frames = r.frames; lp.cells = c.sp.cells;
+        lp.bits = nullptr; lp.metric = nullptr;
+        lp.n_cw = (uint32_t)r.n_jobs * (uint32_t)lp.n_points;
+        for (int i = 0; i < lp.n_codes; ++i) {
+            lp.rate = c.cd.rate[i]; lp.code = i;
+            lp.steps[0] = c.fr_steps[i][0]; lp.steps[1] = c.fr_steps[i][1];
+            if (!viterbi_long_ok(lp, true)) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(wofdm_viterbi_long_kernel, dim3(lp.n_cw), dim3(64), 0, s, lp);
+        }
+    } else if (code) {
         // the decoder behind the soft bits: one wave per (frame, point, data symbol) and code
         wofdm_codeparams cd = c.cd;
         cd.cw_stride = (int64_t)N * 8;
@@ -2645,6 +2818,14 @@ hipError_t viterbi_launch(const wofdm_codeparams *cd, hipStream_t s)
     return hipGetLastError();
 }
 
+// wofdm_viterbi_decode_long: the streaming decoder on soft bits of the caller's
+hipError_t viterbi_long_launch(const wofdm_longparams *lp, hipStream_t s)
+{
+    if (!viterbi_long_ok(*lp, false)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wofdm_viterbi_long_kernel, dim3(lp->n_cw), dim3(64), 0, s, *lp);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
@@ -2655,7 +2836,7 @@ const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
 
 const wofdm_link_fns *WOFDM_CAT(wofdm_aux_link_n, WOFDM_TU_N)(void)
 {
-    static const wofdm_link_fns fns = {rx_profile_chunk, viterbi_launch};
+    static const wofdm_link_fns fns = {rx_profile_chunk, viterbi_launch, viterbi_long_launch};
     return &fns;
 }
 

@@ -79,10 +79,35 @@ struct wofdm_codeparams {
     uint32_t n_cw;
 };
 
+// The streaming decoder wofdm_viterbi_long_kernel (wofdm_rx_profile_coded_frame, wofdm_viterbi_decode_long): the code, metric and
+// rules of wofdm_viterbi_kernel, the survivor history in device memory instead of LDS -- hist holds the decisions in blocks of
+// 64 steps: bit i of word [wave][block][s] is the decision into state s at step 64 block + i of the launch's wave-th codeword,
+// 512 bytes per block, ceil(steps / 64) blocks per codeword.  One launch decodes ONE code; codeword w reads coded-stream index c at byte
+// gather[c] of its block soft + w cw_stride.  A variant v is a codeword length: the profile has one per number of data symbols
+// S_d in use -- variant 1 belongs to the points with post, variant 0 to the others --, the decoder alone only variant 0.
+#define WOFDM_CODE_LONG_STEPS 1048576      // WOFDM_CODE_LONG_MAX_STEPS of include/wofdm.h
+struct wofdm_longparams {
+    const int8_t *soft;               // the profile: [n_jobs][n_points][S - 1][n_fft][8]; the decoder alone: [n_cw][n_c]
+    unsigned long long *hist;         // [n_cw][hist_blocks][64]
+    const int32_t *gather[2];         // [n_c[v]]; the profile: (S_d, perm, sym_rot and the data bins folded) 8 (N j + n) + i
+    int32_t n_c[2], steps[2];         // steps[v] = wofdm_code_steps(rate, n_c[v]) in 7 ... WOFDM_CODE_LONG_STEPS, or 0: no codeword
+    int32_t rate, hist_blocks;        // hist_blocks >= ceil(steps[v] / 64)
+    int64_t cw_stride;
+    uint32_t n_cw;                    // the launch's codewords; the profile: n_jobs n_points, codeword w = (job, point)
+    // the profile (bits null): counted into errs[point][cell][n_codes][2] at code
+    unsigned long long *errs;         // {info-bit errors, codeword errors}, integer atomics
+    const wofdm_tpoint *pts;          // [n_points]
+    int32_t n_points, code, n_codes;
+    uint64_t item0, frames, cells;
+    // wofdm_viterbi_decode_long (errs null)
+    uint8_t *bits;                    // [n_cw][steps[0]]
+    int32_t *metric;                  // [n_cw], or null
+};
+
 // The arms of the receive body (rxprof_body of wofdm_aux.hip, which says what each adds)
 enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
 
-// One chunk of a receive-profile call, whichever of the ten: the victim's Tx chain, the receive kernel's parameters, and the
+// One chunk of a receive-profile call, whichever of the eleven: the victim's Tx chain, the receive kernel's parameters, and the
 // stages' parameter structs as the kernels take them.  The arm says which stages the chunk runs -- a stage's struct is read
 // only where its arm or RXP_LINK is on --; the link arm runs every stage, its points switch them, and only its neighbour
 // (no point has aci_on: nb_on = false), its demapper (wofdm_rx_profile_soft: soft_on) and, with the demapper, its tracking receiver
@@ -91,6 +116,8 @@ struct wofdm_rxchunk {
     int32_t arm;                      // RXP_*
     bool nb_on, soft_on, track_on;    // RXP_ACI: nb_on is true; track_on needs soft_on
     bool code_on;                     // (wofdm_rx_profile_coded) needs track_on: the soft-bit stores and the decoder behind them
+    bool frame_on;                    // (wofdm_rx_profile_coded_frame) needs code_on: wofdm_viterbi_long_kernel over the frame's
+                                      // data symbols, one launch per code of cd, in the place of the per-symbol decoder
     wofdm_pparams tx, nb;             // the victim's Tx chain; the neighbour's (S + 1 symbols, its own stream, allocation, buffers)
     wofdm_rparams r;
     wofdm_aparams a;                  // RXP_LINK: ioff and a_lvl are the points'
@@ -101,7 +128,9 @@ struct wofdm_rxchunk {
     wofdm_lparams lk;
     wofdm_softparams soft;
     wofdm_trackparams tk;
-    wofdm_codeparams cd;
+    wofdm_codeparams cd;              // frame_on: llr_scale, soft, n_codes and rate; errs and steps are not read
+    wofdm_longparams fr;              // frame_on: hist, gather, n_c, hist_blocks, errs; the launcher fills in the rest
+    int32_t fr_steps[WOFDM_CODE_CODES][2];   // frame_on: steps per code and variant
     int32_t n_tracks;                 // RXP_LINK: the tracks of dp's knots, the static one included
     int32_t max_theta;                // RXP_LINK: the largest timing offset of the points, or 0 (the knots cover the samples it reaches)
 };
@@ -113,6 +142,8 @@ struct wofdm_link_fns {
     hipError_t (*rx_profile_chunk)(const wofdm_rxchunk *c, hipStream_t s);
     // wofdm_viterbi_kernel on soft bits of the caller's (cd.errs null, cd.bits set): one wave per codeword of code 0
     hipError_t (*viterbi)(const wofdm_codeparams *cd, hipStream_t s);
+    // wofdm_viterbi_long_kernel on soft bits of the caller's (lp.errs null, lp.bits set): one wave per codeword, variant 0
+    hipError_t (*viterbi_long)(const wofdm_longparams *lp, hipStream_t s);
 };
 const wofdm_link_fns *wofdm_aux_link_n64(void);
 const wofdm_link_fns *wofdm_aux_link_n128(void);

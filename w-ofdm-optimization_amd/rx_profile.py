@@ -2010,3 +2010,245 @@ def coded_ber(prof):
 def coded_cwer(prof):
     """The codeword error rate, shaped as ``coded_ber``'s"""
     return _coded_rates(prof, prof.cw_err, np.ones(len(prof.rates)))
+
+
+# ---- the coded link with frame-spanning codewords (wofdm_rx_profile_coded_frame, wofdm_viterbi_decode_long) ----
+
+RxProfileCodedFrame = collections.namedtuple(
+    "RxProfileCodedFrame", RxProfileTracking._fields + ("info_err", "cw_err", "info_bits", "codewords", "rates", "llr_scale", "sym_rot",
+                                                        "soft_bits"))
+RxProfileCodedFrame.__doc__ = """``RxProfileTracking``'s fields, and info_err, cw_err (uint64) [points, pairs, n_snr, n_ch, codes]: the
+decoded info-bit errors and codeword errors of the frames' codewords; info_bits [points, codes]: T - 6 of each code over the point's
+data symbols; codewords [points]: the codewords per cell (frames); rates [codes]; llr_scale; sym_rot; soft_bits (int8) [pairs,
+n_snr, n_ch, frames, points, S - 1, N, 8] or None."""
+
+
+def default_sym_rot(n_c, s_d):
+    """The rotation that spreads a frame's symbols evenly over the interleaver's span: n_c // s_d"""
+    return int(n_c) // int(s_d)
+
+
+def frame_interleaver(n_c, s_d, sym_rot, perm=None):
+    """The frame interleaver of include/wofdm.h: (j, position) [n_c s_d] -- coded-stream index c sits in data symbol 1 + j, j = c
+    mod s_d, at the symbol's position perm[(c div s_d + j sym_rot) mod n_c] (perm None: the identity).  sym_rot >= 0 counts
+    modulo n_c (``default_sym_rot`` of one symbol is n_c, which is 0); the library takes [0, n_c) only."""
+    n_c, s_d, sym_rot = int(n_c), int(s_d), int(sym_rot)
+    if n_c < 1 or s_d < 1 or sym_rot < 0:
+        raise ValueError("n_c and s_d must be >= 1 and sym_rot >= 0")
+    p = _check_perm(perm, n_c)
+    c = np.arange(n_c * s_d, dtype=np.int64)
+    j, q = c % s_d, c // s_d
+    at = (q + j * sym_rot) % n_c
+    return j, (at if p is None else p[at].astype(np.int64))
+
+
+def viterbi_decode_long_gpu(soft, rate, perm=None, device=0):
+    """``wofdm_viterbi_decode_long``: ``viterbi_decode_gpu`` for codewords of up to 2^20 steps, the same bits and metric.  No CPU
+    fallback."""
+    from . import _lib
+    soft = np.ascontiguousarray(np.atleast_2d(np.asarray(soft)), dtype=np.int8)
+    n_cw, n_c = soft.shape
+    steps = code_steps(rate, n_c)
+    p = _check_perm(perm, n_c)
+    bits = np.zeros((n_cw, max(steps, 1)), dtype=np.uint8)
+    metric = np.zeros(n_cw, dtype=np.int32)
+    _lib.check(_lib.load().wofdm_viterbi_decode_long(int(device), int(rate), n_c, None if p is None else p.ctypes.data, n_cw,
+                                                     soft.ctypes.data, bits.ctypes.data, metric.ctypes.data))
+    return bits[:, :steps], metric
+
+
+def _frame_code_prepare(st, bits_per_sc, syms, act, pil, tps, codes, perm, llr_scale, sym_rot):
+    """(rates, perm or None, pos [n_c] as ``_code_prepare``'s, sym_rot, T [points, codes] over each point's data symbols)"""
+    from . import _lib
+    rates = _code_list(codes)
+    on = np.ones(st.n_fft, dtype=bool) if act is None else np.asarray(act).reshape(-1) != 0
+    data = on & ~pil if pil is not None else on
+    pos = (8 * np.flatnonzero(data)[:, None] + np.arange(int(bits_per_sc))[None, :]).reshape(-1)
+    if not (np.isfinite(llr_scale) and llr_scale > 0):
+        raise ValueError("llr_scale must be finite and positive")
+    rot = default_sym_rot(pos.size, max(int(syms) - 1, 1)) % pos.size if sym_rot is None else int(sym_rot)
+    if not 0 <= rot < pos.size:
+        raise ValueError("sym_rot must be in [0, %d)" % pos.size)
+    steps = np.array([[code_steps(r, pos.size * (int(syms) - 1 - int(q.post))) if int(syms) - 1 - int(q.post) >= 1 else 0
+                       for r in rates] for q in tps], dtype=np.int64).reshape(len(tps), len(rates))
+    used = steps[steps > 0]
+    if used.size and used.min() < 7:
+        raise ValueError("%d coded bits per symbol give a codeword of fewer than 7 steps" % pos.size)
+    if used.size and used.max() > _lib.CODE_LONG_MAX_STEPS:
+        raise ValueError("a codeword of more than %d steps" % _lib.CODE_LONG_MAX_STEPS)
+    return rates, _check_perm(perm, pos.size), pos, rot, steps
+
+
+def frame_codewords(d, post, pos, perm, sym_rot):
+    """The frames' codewords of soft bits d [..., S - 1, N, 8] (int8) as the decoder reads them: [..., n_c S_d], S_d = S - 1 - post,
+    gathered through ``frame_interleaver``; pos: the index 8 n + i of a symbol's position (``_code_prepare``)"""
+    d = np.asarray(d)
+    S1 = d.shape[-3]
+    s_d = S1 - int(bool(post))
+    j, at = frame_interleaver(pos.size, s_d, sym_rot, perm)
+    return d.reshape(d.shape[:-3] + (S1, -1))[..., j, np.asarray(pos)[at]]
+
+
+def _decode_frame_long(d, tp, pos, perm, rates, sym_rot):
+    """(info errors, codeword errors) [codes] of a frame's soft bits d [S - 1, N, 8]: one codeword over the point's data symbols"""
+    info, cw = np.zeros(len(rates), dtype=np.uint64), np.zeros(len(rates), dtype=np.uint64)
+    if d.shape[0] - int(bool(tp.post)) < 1:
+        return info, cw
+    word = frame_codewords(d, tp.post, pos, perm, sym_rot)[None]
+    for i, r in enumerate(rates):
+        bits, _ = viterbi_decode(word, r)
+        info[i], cw[i] = bits[0, :bits.shape[1] - 6].sum(), bits[0].any()
+    return info, cw
+
+
+def frame_profile_coded_frame(st, grids, noise_at, w_tx, w_rx, h, point, tracking, snr_db, bits_per_sc, walk, pilots=None, scales=None,
+                              llr_scale=LLR_SCALE, perm=None, codes=None, sym_rot=None, track=None, knot_step=None, ref_power=None,
+                              aci_grids=None, aci_h=None, active=None, mask=None, noise_before_truncate=1):
+    """fp64 host mirror of one frame and one point of ``wofdm_rx_profile_coded_frame``: ``frame_profile_coded``'s outputs through the
+    near rule's weight, then the decoded info-bit and codeword errors [codes] of the frame's one codeword (``viterbi_decode``)."""
+    sc = _soft_scales(scales)
+    syms = np.asarray(grids).shape[0]
+    tps, pil = _tracking_prepare(st, syms, 1, [tracking], pilots, active)
+    rates, p, pos, rot, _ = _frame_code_prepare(st, bits_per_sc, syms, active, pil, tps, codes, perm, llr_scale, sym_rot)
+    front, out = _frame_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, walk, track, knot_step, ref_power,
+                             aci_grids, aci_h, active, mask, noise_before_truncate)
+    res = _tracking_outputs(st, front, out, w_rx, snr_db, bits_per_sc, sc, noise_before_truncate, pil, tps[0])
+    z, weight = _coded_z(st, front, res, w_rx, snr_db, bits_per_sc, noise_before_truncate, pil, tps[0])
+    d8 = np.zeros(z.shape[:2] + (8,), dtype=np.int8)
+    d8[..., :z.shape[-1]], t = soft_bits(z, llr_scale)
+    return res + (d8, t, weight) + _decode_frame_long(d8, tps[0], pos, p, rates, rot)
+
+
+def _coded_frame_result(trk, info, cw, steps, frames, rates, llr_scale, sym_rot, soft):
+    return RxProfileCodedFrame(*trk, info, cw, np.maximum(steps - 6, 0), np.full(steps.shape[0], int(frames), dtype=np.uint64),
+                               tuple(rates), float(llr_scale), int(sym_rot), soft)
+
+
+def rx_profile_coded_frame_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                                tracking=None, pilots=None, scales=None, llr_scale=LLR_SCALE, perm=None, codes=None, sym_rot=None,
+                                tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None, mask=None,
+                                noise_before_truncate=1, with_near=False, with_soft=False):
+    """The host route of ``rx_profile_coded_frame_gpu``: ``rx_profile_coded_host``'s frames, points, arrays and soft bits, each
+    (frame, point)'s one codeword through ``frame_interleaver`` and ``viterbi_decode`` for the rates ``codes`` (None: rate 1/2);
+    sym_rot None: ``default_sym_rot`` over S - 1 symbols.  Returns ``RxProfileCodedFrame`` (with_near: and the near decisions);
+    with_soft as in ``rx_profile_coded_host``."""
+    held = {}
+
+    def receiver(q, n_points, sc):
+        tps, pil = _tracking_prepare(st, q.S, n_points, tracking, pilots, q.act)
+        rates, p, pos, rot, steps = _frame_code_prepare(st, q.k, q.S, q.act, pil, tps, codes, perm, llr_scale, sym_rot)
+        shape = (n_points, q.w_tx.shape[0], q.snr.size, q.hc.shape[0], len(rates))
+        held.update(tps=tps, pil=pil, act=q.act, rates=rates, steps=steps, rot=rot, info=np.zeros(shape, np.uint64),
+                    cw=np.zeros(shape, np.uint64))
+        if with_soft:
+            lead = shape[1:4] + (int(frames), n_points, q.S - 1, st.n_fft)
+            held.update(d=np.zeros(lead + (8,), np.int8), t=np.zeros(lead + (q.k,), np.float64), w=np.zeros(lead, np.float64))
+
+        def one(i, tp):
+            def run(front, out, p_, s_, c_, f_):
+                res = _tracking_outputs(st, front, out, q.w_rx[p_], q.snr[s_], q.k, sc, q.nbt, pil, tp)
+                z, weight = _coded_z(st, front, res, q.w_rx[p_], q.snr[s_], q.k, q.nbt, pil, tp)
+                d8 = np.zeros(z.shape[:2] + (8,), dtype=np.int8)
+                d8[..., :q.k], t = soft_bits(z, llr_scale)
+                info, cw = _decode_frame_long(d8, tp, pos, p, rates, rot)
+                held["info"][i, p_, s_, c_] += info
+                held["cw"][i, p_, s_, c_] += cw
+                if with_soft:
+                    held["d"][p_, s_, c_, f_, i], held["t"][p_, s_, c_, f_, i], held["w"][p_, s_, c_, f_, i] = d8, t, weight
+                return res
+            return run
+        return [one(i, tp) for i, tp in enumerate(tps)]
+    res = _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, scales, tracks,
+                      knot_step, aci_active, aci_h, ref_power, active, mask, noise_before_truncate, with_near, receiver)
+    soft = res[0] if with_near else res
+    dec, sym = _tracking_decisions(st, syms, frames, held["act"], held["pil"], held["tps"])
+    trk = RxProfileTracking(*soft[:-1], sym, dec)
+    prof = _coded_frame_result(trk, held["info"], held["cw"], held["steps"], frames, held["rates"], llr_scale, held["rot"], held.get("d"))
+    if with_soft:
+        prof = (prof, held["t"], held["w"])
+    return (prof, res[1]) if with_near else prof
+
+
+def rx_profile_coded_frame_chunk_frames(st, bits_per_sc, syms, masked, n_points, neighbour, n_scales, n_data_bins, codes=(0,), post=False):
+    """Frames one chunk of ``wofdm_rx_profile_coded_frame`` holds: ``rx_profile_coded_chunk_frames``' bytes plus the survivor
+    history, 512 ceil(T_max / 64) bytes per point, T_max the longest codeword: the largest rate of ``codes`` over S - 1 data symbols
+    (post=True: every point has a postamble, S - 2) of n_data_bins bins; at most 65535"""
+    B = st.sym_len - st.tail_tx
+    n_f = int(bits_per_sc) * int(n_data_bins) * (int(syms) - 1 - int(bool(post)))
+    t_max = max(code_steps(r, n_f) for r in _code_list(codes))
+    return _chunk_frames(st, syms, masked, per_point=st.n_fft + syms + st.tail_tx + syms * B, n_points=n_points,
+                         per_frame_extra=syms * B, neighbour=bool(neighbour),
+                         extra_bytes=4 * int(n_points) * int(n_scales) * ((syms - 1) * st.n_fft + syms)
+                         + 8 * int(n_points) * (syms - 1) * st.n_fft + 512 * int(n_points) * ((t_max + 63) // 64))
+
+
+def rx_profile_coded_frame_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                               tracking=None, pilots=None, scales=None, llr_scale=LLR_SCALE, perm=None, codes=None, sym_rot=None,
+                               tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None, mask=None,
+                               noise_before_truncate=1, device=0, out=None, export=False):
+    """``wofdm_rx_profile_coded_frame``: ``rx_profile_coded_gpu``'s frames, tracking fields and soft bits -- that call's bytes --,
+    and per point and frame ONE codeword over the point's data symbols, interleaved by ``frame_interleaver`` with ``perm`` and
+    ``sym_rot`` (None: ``default_sym_rot`` over S - 1 symbols) and decoded on the GPU for each rate of ``codes`` (None: rate 1/2).
+    export=True also returns the soft bits.  Returns ``RxProfileCodedFrame``; ``out`` (an earlier result of the same shape, scales,
+    codes and sym_rot) is accumulated into (its soft bits are dropped).  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    sc = _soft_scales(scales)
+    points = [LinkPoint()] if points is None else points
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts, tr, iact, hi, ref = _link_sides(st, prepared[2], points, tracks, aci_active, aci_h, ref_power, prepared[0].shape[0])
+    tps, pil = _tracking_prepare(st, syms, len(pts), tracking, pilots, prepared[4])
+    rates, p, _, rot, steps = _frame_code_prepare(st, bits_per_sc, syms, prepared[4], pil, tps, codes, perm, llr_scale, sym_rot)
+    trf = None if tr is None else _lib.c64_as_f32(tr)
+    hif = None if hi is None else _lib.c64_as_f32(hi)
+    lin = PaPoint(PA_LINEAR, 0.0)
+    cpts = (_lib.LinkPoint * len(pts))(*[
+        _lib.LinkPoint(*(q.pa or lin), -1 if q.track is None else q.track, q.timing, q.cfo, q.cfo_tracked, q.linewidth, q.cpe_tracked,
+                       int(q.aci is not None), *(q.aci or (0, 0.0)), (C.c_int32 * 4)(0, 0, 0, 0)) for q in pts])
+    ctps = (_lib.TrackingPoint * len(tps))(*[_lib.TrackingPoint(q.cpe, q.post, (C.c_int32 * 2)(0, 0)) for q in tps])
+    ccodes = (_lib.Code * len(rates))(*[_lib.Code(r, (C.c_int32 * 3)(0, 0, 0)) for r in rates])
+    pil8 = None if pil is None else np.ascontiguousarray(pil, dtype=np.uint8)
+    knots = (0, 0, 0) if tr is None else (tr.shape[0], tr.shape[2], int(knot_step))
+    prev = None
+    if out is not None:
+        if not np.array_equal(out.scales, sc) or tuple(out.rates) != tuple(rates) or out.sym_rot != rot:
+            raise ValueError("out has other scales, codes or sym_rot")
+        prev = _RxSoftSums(*out[:9], np.zeros(st.n_fft, dtype=np.uint64))
+    cells = (prepared[0].shape[0], prepared[3].size, prepared[2].shape[0])
+    ferr = np.zeros((len(pts),) + cells + (len(rates), 2), dtype=np.uint64)
+    sb = np.zeros(cells + (int(frames), len(pts), int(syms) - 1, st.n_fft, 8), dtype=np.int8) if export else None
+    res = _gpu_call("wofdm_rx_profile_coded_frame", _RxSoftSums, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                    noise_before_truncate, device, prev, lead=(len(pts),), n_scales=sc.size,
+                    after_mask=(None if trf is None else trf.ctypes.data, *knots, None if iact is None else iact.ctypes.data,
+                                None if hif is None else hif.ctypes.data, None if ref is None else ref.ctypes.data, len(pts), cpts,
+                                int(sc.size), sc.ctypes.data, None if pil8 is None else pil8.ctypes.data, ctps,
+                                C.c_float(float(llr_scale)), None if p is None else p.ctypes.data, len(rates), ccodes, int(rot)),
+                    behind=(ferr.ctypes.data, None if sb is None else sb.ctypes.data))
+    dec, sym = _tracking_decisions(st, syms, frames, prepared[4], pil, tps)
+    if out is not None:
+        if out.decisions.shape != dec.shape:
+            raise ValueError("out has another shape")
+        dec, sym = out.decisions + dec, out.decisions_sym + sym
+    prof = _coded_frame_result(_tracking_result(res, sc, dec, sym), np.ascontiguousarray(ferr[..., 0]),
+                               np.ascontiguousarray(ferr[..., 1]), steps, frames, rates, llr_scale, rot, sb)
+    if out is not None:
+        prof = prof._replace(info_err=out.info_err + prof.info_err, cw_err=out.cw_err + prof.cw_err,
+                             codewords=out.codewords + prof.codewords)
+    return prof
+
+
+def coded_frame_ber(prof):
+    """The decoded info-bit error rate of the frames' codewords [points, pairs, n_snr, n_ch, codes]; NaN where a point carried no
+    codeword"""
+    bits = (prof.codewords.astype(np.float64)[:, None] * prof.info_bits.astype(np.float64)).reshape(
+        (prof.info_err.shape[0],) + (1,) * (prof.info_err.ndim - 2) + (-1,))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(bits > 0, prof.info_err.astype(np.float64) / np.where(bits > 0, bits, 1.0), np.nan)
+
+
+def coded_fer(prof):
+    """The frame (codeword) error rate, shaped as ``coded_frame_ber``'s"""
+    words = (prof.codewords.astype(np.float64)[:, None] * (prof.info_bits > 0)).reshape(
+        (prof.cw_err.shape[0],) + (1,) * (prof.cw_err.ndim - 2) + (-1,))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(words > 0, prof.cw_err.astype(np.float64) / np.where(words > 0, words, 1.0), np.nan)
