@@ -1084,6 +1084,107 @@ int wofdm_rx_profile_coded_frame(const wofdm_cfg *cfg, int device,
                                  uint64_t *frame_errs,          /* [n_points][cells][n_codes][2], ACCUMULATED into */
                                  int8_t *soft_bits);            /* [cells][frames][n_points][S-1][n_fft][8], or NULL */
 
+/* The coded link with a quasi-cyclic LDPC code and a layered min-sum decoder.
+ *   The code is (J, L), 3 <= J <= 6, J < L <= 24, over a word of n transmitted positions.
+ *   Lift.  Z = wofdm_ldpc_lift(J, L, n) is the smallest prime Z >= max(L, ceil(n / L)) whose multiplicative order of 2 is at least L.
+ * The check matrix has J x L blocks of Z x Z.
+ *   Blocks.  Block (i, j) is zero for j < i; otherwise it is the circulant that joins check i Z + r to variable j Z + ((r + s(i, j))
+ * mod Z), s(i, j) = (i 2^j) mod Z.  Row i has degree L - i.  The structure has no 4-cycle: Z is prime and the 2^j, j < L, are
+ * distinct mod Z.
+ *   Parity and information.  Block columns 0 ... J - 1 are the parity part, block upper triangular with permutations on the
+ * diagonal; the full length is n0 = L Z >= n.  The code is shortened by s = n0 - n: variables n ... n0 - 1 are known zeros and are
+ * not transmitted.  The information bits are variables J Z ... n - 1, K = (L - J) Z - s of them; K >= 1, or the code is invalid.
+ *   Encoder (the Python mirror only: the profile's codeword is all zero in the random-coset view).  Back-substitution from block
+ * row J - 1 up to 0: a row's parity block is the XOR of the row's other blocks through the diagonal block's permutation.
+ *   Decoder: pure integer, layered, normalised min-sum.  Start: Q[v] = d[v] (int8, any value, -128 included) for v < n and 127
+ * for the shortened positions -- ordinary variables from there on --; R[e] = 0 on every edge.  One iteration is the layers i = 0 ...
+ * J - 1 in order; a layer touches each variable at most once, so its checks are independent.  For a check and each of its edges j:
+ * t_j = Q[v_j] - R_j, a_j = min(|t_j|, 127); m1 <= m2 the two smallest a over the edges; the new magnitude is (3 m) >> 2 with m =
+ * m2 on an edge whose a_j = m1 and m1 elsewhere (ties need no rule: m2 = m1 then); the new sign is negative where the number of
+ * negative t on the OTHER edges is odd, t = 0 counting as positive; Q[v_j] = t_j + R_j(new).  |Q| <= 128 + 6 * 95, so int16 holds
+ * it and there is no saturation rule.  After each full iteration the hard decision is x[v] = (Q[v] < 0) over all n0 variables; if
+ * every check's parity is even the word has converged and decoding stops, otherwise it goes on, up to max_iter, 1 <= max_iter <=
+ * 64.  Outputs: x[0 ... n - 1], the iterations run, the converged flag.
+ *   wofdm_ldpc_kernel: one workgroup per (codeword, code), Q as int16 and R as int8 in LDS, 304 + 2 L Z + Z (J L - J (J - 1) / 2)
+ * bytes (each array rounded up to four): 33 KiB at (4, 8, 6272), at most 131 KiB at n = WOFDM_LDPC_MAX_BITS and J = 6, within the
+ * 160 KiB of a workgroup (a code beyond that would be WOFDM_E_UNSUPPORTED; none in the ranges above is). */
+#define WOFDM_LDPC_MAX_BITS 16384
+typedef struct wofdm_ldpc_code {
+    int32_t J, L;              /* 3 <= J <= 6, J < L <= 24 */
+    int32_t max_iter;          /* 1 ... 64 */
+    int32_t reserved;          /* 0 */
+} wofdm_ldpc_code;
+
+/* Host only: the lift Z (>= 5) of the (J, L) code over n positions, or WOFDM_E_INVALID (negative) outside the ranges above, for n
+ * outside 1 ... 2^24, or where K < 1. */
+int wofdm_ldpc_lift(int32_t J, int32_t L, int32_t n);
+
+/* The decoder alone, on n_cw words of n soft bits each: coded-stream index c (variable c of the code) is read at soft[w][perm[c]]
+ * (NULL perm: the identity), as in wofdm_viterbi_decode_long.  bits[w][v] = x[v], iters[w] the iterations run, converged[w] 0 / 1.
+ *   Checks, all before the device is touched, in this order: WOFDM_E_INVALID for NULL soft or bits; J, L; max_iter; n or n_cw < 1;
+ * WOFDM_E_UNSUPPORTED for n > WOFDM_LDPC_MAX_BITS; WOFDM_E_INVALID for K < 1; WOFDM_E_UNSUPPORTED for a decoder state beyond a
+ * workgroup's LDS (a guard: no code of the ranges above reaches it); WOFDM_E_INVALID for a perm that is no permutation.  A failed
+ * check leaves the outputs as they were.  The call holds the launch gate while its kernel runs; it neither counts for nor resets
+ * wofdm_rx_profile_kernel_ms. */
+int wofdm_ldpc_decode(int device, int32_t J, int32_t L, int32_t max_iter, int32_t n,
+                      const int32_t *perm,                  /* [n], or NULL */
+                      int32_t n_cw,
+                      const int8_t *soft,                   /* [n_cw][n] */
+                      uint8_t *bits,                        /* [n_cw][n] */
+                      int32_t *iters,                       /* [n_cw], or NULL */
+                      uint8_t *converged);                  /* [n_cw], or NULL */
+
+/* The coded link with LDPC codewords over the frame: wofdm_rx_profile_coded_frame's soft bits, frame interleaver (perm, sym_rot)
+ * and random-coset view -- the transmitted codeword is all zero --, decoded by wofdm_ldpc_kernel.
+ *   Codewords.  A point's frame has n_f = n_c S_d coded-stream positions behind the frame interleaver (S_d = S - 1, S - 2 with
+ * post).  It carries W = ceil(n_f / WOFDM_LDPC_MAX_BITS) codewords of n = floor(n_f / W) positions each; codeword w holds the
+ * coded-stream indices w n ... w n + n - 1 -- contiguous ranges, so every codeword sees every data symbol --, and the left-over
+ * positions are ignored.  Every code of the call is lifted for this n.
+ *   Arguments: every argument of wofdm_rx_profile_coded_frame through perm; n_codes (1 ... WOFDM_CODE_MAX) codes; sym_rot; the seven
+ * outputs of wofdm_rx_profile_tracking, that call's bytes; ldpc_errs[point][cell][code] = {info-bit errors (x[v] != 0, J Z <= v <
+ * n), codeword errors (any info bit wrong), unconverged codewords, iterations run}, ACCUMULATED into; soft_bits as in the coded
+ * calls, the same bytes.
+ *   Identities, by bytes: ldpc_errs depends neither on where a chunk ends, nor on the other points or codes of the call, nor on
+ * whether soft_bits is requested; repeated calls are identical; it equals wofdm_ldpc_decode on the exported soft bits gathered
+ * through the frame interleaver.
+ *   Checks: wofdm_rx_profile_coded_frame's through perm and the size of soft_bits (codes NULL and n_codes in their places, no
+ * rates), then in this order WOFDM_E_INVALID for sym_rot outside [0, n_c); for NULL ldpc_errs; then code by code for J, L,
+ * max_iter outside their ranges, reserved != 0, K < 1 at an S_d in use, and (WOFDM_E_UNSUPPORTED, the same guard as the decoder's)
+ * a decoder state beyond a workgroup's LDS.  Every argument is checked before the device is touched; a failed check leaves all
+ * outputs as they were.
+ *   Chunks: wofdm_rx_profile_coded's formula -- the decoder's state is in LDS.  One launch per code.
+ *   A successful call holds the launch gate and counts for wofdm_rx_profile_kernel_ms.
+ *   Measured: tools/bench_rx_profile_ldpc.py, profiles/rx_profile_ldpc.txt. */
+int wofdm_rx_profile_ldpc(const wofdm_cfg *cfg, int device,
+                          const float *w_tx,             /* [pairs][P] */
+                          const float *w_rx,             /* [pairs][N+tail_rx] */
+                          const float *h,                /* [n_channels][n_taps][2] */
+                          const float *snr_db,           /* [n_snr] */
+                          const uint8_t *active,         /* [n_fft] or NULL */
+                          const float *tx_mask,          /* [2P-1] or NULL */
+                          const float *h_track,          /* [n_tracks][n_channels][n_knots][n_taps][2], or NULL */
+                          int32_t n_tracks, int32_t n_knots, int32_t knot_step,
+                          const uint8_t *aci_active,     /* [n_fft], or NULL */
+                          const float *aci_h,            /* [n_channels][n_taps][2], or NULL = h */
+                          const float *ref_power,        /* [pairs], or NULL */
+                          int32_t n_points, const wofdm_link_point *points,
+                          int32_t n_scales, const float *scales,
+                          const uint8_t *pilots,         /* [n_fft], or NULL */
+                          const wofdm_tracking_point *tracking, /* [n_points] */
+                          float llr_scale,
+                          const int32_t *perm,           /* [n_c], or NULL */
+                          int32_t n_codes, const wofdm_ldpc_code *codes,
+                          int32_t sym_rot,               /* in [0, n_c) */
+                          uint64_t *errs,                /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                          double *err_power,             /* [n_points][cells][n_fft], or NULL */
+                          uint64_t *sym_errs,            /* [n_points][cells][S-1][2], or NULL */
+                          double *sym_power,             /* [n_points][cells][S-1], or NULL */
+                          double *pa_power,              /* [n_points][cells][2], or NULL */
+                          double *bit_penalty,           /* [n_points][cells][n_scales][n_fft], ACCUMULATED into */
+                          double *sym_penalty,           /* [n_points][cells][n_scales][S-1], or NULL */
+                          uint64_t *ldpc_errs,           /* [n_points][cells][n_codes][4], ACCUMULATED into */
+                          int8_t *soft_bits);            /* [cells][frames][n_points][S-1][n_fft][8], or NULL */
+
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

@@ -21,7 +21,8 @@ as ``wofdm_amd`` through the shim module at the repository root.
                achievable rate beside the hard counters (GPU: wofdm_rx_profile_soft), behind a receiver that tracks with comb
                pilots and a postamble (GPU: wofdm_rx_profile_tracking), with 8-bit soft bits and a K = 7 Viterbi decoder behind
                it (GPU: wofdm_rx_profile_coded, wofdm_viterbi_decode), per data symbol or with one codeword over the frame (GPU:
-               wofdm_rx_profile_coded_frame, wofdm_viterbi_decode_long)
+               wofdm_rx_profile_coded_frame, wofdm_viterbi_decode_long), or with a quasi-cyclic LDPC code and a layered min-sum
+               decoder over the frame (GPU: wofdm_rx_profile_ldpc, wofdm_ldpc_decode)
   _lib         ctypes binding of libwofdm_hip.so (include/wofdm.h)
 """
 from . import variants  # noqa: F401
@@ -41,6 +42,7 @@ from ._lib import kernel_source_hash  # noqa: F401
 from .timefreq import (estimate_obr, frame_papr, papr_ccdf, papr_hist, run_timefreq, tx_papr_gpu,  # noqa: F401
                        tx_psd_batch_gpu, tx_waveform)
 from .channel_mask import (aci_for_window_file, coded_for_window_file, coded_frame_for_window_file, doppler_for_window_file, interference_for_window_file,  # noqa: F401
+                           ldpc_for_window_file,
                            link_for_window_file, soft_for_window_file, pa_for_window_file, papr_for_window_file, pn_for_window_file, profile_for_window_file,
                            spectrum_for_window_file, sync_for_window_file, tracking_for_window_file)
 from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_db, frame_profile,  # noqa: F401
@@ -63,7 +65,10 @@ from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_d
                          viterbi_decode, viterbi_decode_gpu,
                          RxProfileCodedFrame, coded_fer, coded_frame_ber, default_sym_rot, frame_codewords, frame_interleaver,
                          frame_profile_coded_frame, rx_profile_coded_frame_chunk_frames, rx_profile_coded_frame_gpu,
-                         rx_profile_coded_frame_host, viterbi_decode_long_gpu)
+                         rx_profile_coded_frame_host, viterbi_decode_long_gpu,
+                         LDPC_MAX_ITER, RxProfileLdpc, frame_profile_ldpc, ldpc_ber, ldpc_decode, ldpc_decode_at, ldpc_decode_gpu,
+                         ldpc_edges, ldpc_encode, ldpc_fer, ldpc_frame_words, ldpc_lift, ldpc_mean_iterations,
+                         rx_profile_ldpc_chunk_frames, rx_profile_ldpc_gpu, rx_profile_ldpc_host)
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

@@ -45,6 +45,8 @@ CODE_MAX = 4
 CODE_MAX_STEPS = 4608
 #: wofdm_viterbi_decode_long, wofdm_rx_profile_coded_frame (include/wofdm.h): most steps of a codeword
 CODE_LONG_MAX_STEPS = 1048576
+#: wofdm_ldpc_decode, wofdm_rx_profile_ldpc (include/wofdm.h): most positions of a codeword
+LDPC_MAX_BITS = 16384
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -61,6 +63,7 @@ EXPORTS = (
     "wofdm_rx_profile_link", "wofdm_rx_profile_soft", "wofdm_rx_profile_tracking",
     "wofdm_rx_profile_coded", "wofdm_code_steps", "wofdm_viterbi_decode",
     "wofdm_viterbi_decode_long", "wofdm_rx_profile_coded_frame",
+    "wofdm_ldpc_lift", "wofdm_ldpc_decode", "wofdm_rx_profile_ldpc",
 )
 
 
@@ -131,6 +134,11 @@ class TrackingPoint(C.Structure):
 class Code(C.Structure):
     """Mirror of ``wofdm_code`` (16 bytes)."""
     _fields_ = [("rate", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class LdpcCode(C.Structure):
+    """Mirror of ``wofdm_ldpc_code`` (16 bytes)."""
+    _fields_ = [("J", C.c_int32), ("L", C.c_int32), ("max_iter", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Dump(C.Structure):
@@ -227,6 +235,12 @@ def load():
     L.wofdm_rx_profile_coded_frame.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
                                                C.POINTER(LinkPoint), i32, vp, vp, C.POINTER(TrackingPoint), C.c_float, vp, i32,
                                                C.POINTER(Code), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.wofdm_ldpc_lift.argtypes = [i32, i32, i32]
+    L.wofdm_ldpc_lift.restype = C.c_int
+    L.wofdm_ldpc_decode.argtypes = [C.c_int, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
+    L.wofdm_rx_profile_ldpc.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
+                                        C.POINTER(LinkPoint), i32, vp, vp, C.POINTER(TrackingPoint), C.c_float, vp, i32,
+                                        C.POINTER(LdpcCode), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_tx_psd_batch_pa.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, C.POINTER(PaPoint), vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L

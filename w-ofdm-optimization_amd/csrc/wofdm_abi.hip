@@ -1693,6 +1693,9 @@ struct rx_call {
     // the frame-spanning code of wofdm_rx_profile_coded_frame: code is on with it (code_errs null) and gives the soft bits, the
     // interleaver within a symbol and the codes; the rotation from symbol to symbol and the counters
     struct { bool on; int32_t sym_rot; uint64_t *frame_errs; } frm;
+    // the LDPC code of wofdm_rx_profile_ldpc: code and frm are on with it (codes, code_errs and frame_errs null) and give the soft
+    // bits, the frame interleaver and n_codes; the codes and the counters
+    struct { bool on; const wofdm_ldpc_code *codes; uint64_t *ldpc_errs; } ldpc;
 };
 
 // the receive side's geometry beside the Tx chain's, and the cells of the call
@@ -1724,6 +1727,10 @@ struct rx_run {
     bool fuse[2];
     int32_t fnc[2], fsteps[WOFDM_CODE_CODES][2], hist_blocks;
     std::vector<int32_t> fgather[2];
+    // the LDPC code: per variant the words of a frame and their positions (0: unused), per code and variant the lift
+    int32_t lW[2], ln[2], lZ[WOFDM_CODE_CODES][2];
+    size_t n_lerr;
+    dev_buf<unsigned long long> d_lerrs;
     int n_knots, knot_step;
     // device
     size_t chunk, n_out, n_sym, n_ptot, n_bpen, n_spen, n_cerr, n_ferr;
@@ -2026,7 +2033,9 @@ int prep_code(rx_run &r)
     const auto &cd = r.c.code;
     if (!cd.on) return WOFDM_OK;
     const bool frame = r.c.frm.on;                                     // (its counters and lengths: prep_frame)
-    if (!cd.codes || (!frame && !cd.code_errs)) return fail(WOFDM_E_INVALID, "NULL argument (codes or code_errs)");
+    const bool ldpc = r.c.ldpc.on;                                     // (its codes are checked behind the frame's: prep_frame)
+    if (ldpc ? !r.c.ldpc.codes : (!cd.codes || (!frame && !cd.code_errs)))
+        return fail(WOFDM_E_INVALID, "NULL argument (codes or code_errs)");
     if (!std::isfinite(cd.llr_scale) || !(cd.llr_scale > 0.f)) return fail(WOFDM_E_INVALID, "llr_scale must be finite and positive");
     if (cd.n_codes < 1) return fail(WOFDM_E_INVALID, "n_codes=%d must be >= 1", cd.n_codes);
     if (cd.n_codes > WOFDM_CODE_MAX) return fail(WOFDM_E_UNSUPPORTED, "n_codes=%d exceeds %d", cd.n_codes, WOFDM_CODE_MAX);
@@ -2035,7 +2044,7 @@ int prep_code(rx_run &r)
     for (int n = 0; n < N; ++n)
         if ((r.act.empty() || r.act[(size_t)n] != 0) && (r.pil.empty() || r.pil[(size_t)n] == 0)) bins.push_back(n);
     const int32_t n_c = k * (int32_t)bins.size();
-    for (int i = 0; i < cd.n_codes; ++i) {
+    for (int i = 0; !ldpc && i < cd.n_codes; ++i) {
         const wofdm_code &q = cd.codes[i];
         if (q.rate < 0 || q.rate > 2) return fail(WOFDM_E_INVALID, "codes[%d].rate=%d must be 0, 1 or 2", i, q.rate);
         if (q.reserved[0] != 0 || q.reserved[1] != 0 || q.reserved[2] != 0) return fail(WOFDM_E_INVALID, "codes[%d].reserved must be 0", i);
@@ -2055,6 +2064,49 @@ int prep_code(rx_run &r)
     return WOFDM_OK;
 }
 
+// The lift of the (J, L) code over n positions (include/wofdm.h): the smallest prime Z >= max(L, ceil(n / L)) whose
+// multiplicative order of 2 is at least L; the caller has checked the ranges
+int32_t ldpc_lift(int32_t J, int32_t L, int32_t n)
+{
+    (void)J;
+    for (int32_t Z = std::max(L, (n + L - 1) / L);; ++Z) {
+        bool ok = Z >= 3;
+        for (int32_t d = 2; ok && d * d <= Z; ++d) ok = Z % d != 0;
+        int32_t p = 2 % Z;
+        for (int32_t k = 1; ok && k < L; ++k) {                          // 2^k != 1 for 0 < k < L
+            ok = p != 1;
+            p = (2 * p) % Z;
+        }
+        if (ok) return Z;
+    }
+}
+bool ldpc_ranges_ok(int32_t J, int32_t L) { return J >= 3 && J <= 6 && L > J && L <= 24; }
+
+// the LDPC codes of wofdm_rx_profile_ldpc, behind prep_frame's sym_rot and ldpc_errs, code by code in the order include/wofdm.h
+// documents: a frame of n_f positions carries W = ceil(n_f / WOFDM_LDPC_MAX_BITS) words of n = floor(n_f / W) positions
+int prep_ldpc(rx_run &r)
+{
+    for (int v = 0; v < 2; ++v) {
+        r.lW[v] = r.fnc[v] > 0 ? (r.fnc[v] + WOFDM_LDPC_MAX_BITS - 1) / WOFDM_LDPC_MAX_BITS : 0;
+        r.ln[v] = r.lW[v] > 0 ? r.fnc[v] / r.lW[v] : 0;
+    }
+    for (int i = 0; i < r.c.code.n_codes; ++i) {
+        const wofdm_ldpc_code &q = r.c.ldpc.codes[i];
+        if (q.J < 3 || q.J > 6) return fail(WOFDM_E_INVALID, "codes[%d].J=%d must be 3 ... 6", i, q.J);
+        if (q.L <= q.J || q.L > 24) return fail(WOFDM_E_INVALID, "codes[%d].L=%d must be J + 1 ... 24", i, q.L);
+        if (q.max_iter < 1 || q.max_iter > 64) return fail(WOFDM_E_INVALID, "codes[%d].max_iter=%d must be 1 ... 64", i, q.max_iter);
+        if (q.reserved != 0) return fail(WOFDM_E_INVALID, "codes[%d].reserved must be 0", i);
+        for (int v = 0; v < 2; ++v) {
+            r.lZ[i][v] = r.lW[v] > 0 ? ldpc_lift(q.J, q.L, r.ln[v]) : 0;
+            if (r.lW[v] > 0 && (int64_t)(q.L - q.J) * r.lZ[i][v] - ((int64_t)q.L * r.lZ[i][v] - r.ln[v]) < 1)
+                return fail(WOFDM_E_INVALID, "codes[%d]: (%d, %d) over %d positions has no information bit", i, q.J, q.L, r.ln[v]);
+            if (r.lW[v] > 0 && wofdm_ldpc_lds(q.J, q.L, r.lZ[i][v]) > WOFDM_LDPC_LDS_MAX)
+                return fail(WOFDM_E_UNSUPPORTED, "codes[%d]: the decoder's LDS exceeds %d bytes", i, WOFDM_LDPC_LDS_MAX);
+        }
+    }
+    return WOFDM_OK;
+}
+
 // wofdm_viterbi_decode_long and the frame-spanning code: the history is 512 bytes per block of 64 steps
 int32_t hist_blocks_of(int32_t steps) { return (steps + 63) / 64; }
 
@@ -2068,7 +2120,8 @@ int prep_frame(rx_run &r)
     if (!fm.on) return WOFDM_OK;
     const int32_t n_c = (int32_t)r.gather.size(), S = r.g.S, N = r.g.N;
     if (fm.sym_rot < 0 || fm.sym_rot >= n_c) return fail(WOFDM_E_INVALID, "sym_rot=%d outside [0, %d)", fm.sym_rot, n_c);
-    if (!fm.frame_errs) return fail(WOFDM_E_INVALID, "NULL argument (frame_errs)");
+    const bool ldpc = r.c.ldpc.on;
+    if (ldpc ? !r.c.ldpc.ldpc_errs : !fm.frame_errs) return fail(WOFDM_E_INVALID, "NULL argument (%s)", ldpc ? "ldpc_errs" : "frame_errs");
     r.fuse[0] = r.fuse[1] = false;
     for (int i = 0; i < r.c.n_points; ++i) r.fuse[r.tp[(size_t)i].post ? 1 : 0] = true;
     r.hist_blocks = 1;
@@ -2076,7 +2129,7 @@ int prep_frame(rx_run &r)
         const int64_t s_d = S - 1 - v;
         r.fnc[v] = r.fuse[v] && s_d >= 1 ? (int32_t)((int64_t)n_c * s_d) : 0;       // (n_c <= 6 * 1024, S <= 64)
     }
-    for (int pass = 0; pass < 2; ++pass)                                 // (every T < 7 before any T beyond the limit)
+    for (int pass = 0; !ldpc && pass < 2; ++pass)                        // (every T < 7 before any T beyond the limit)
         for (int i = 0; i < r.c.code.n_codes; ++i)
             for (int v = 0; v < 2; ++v) {
                 const int32_t T = r.fnc[v] > 0 ? code_steps(r.c.code.codes[i].rate, r.fnc[v]) : 0;
@@ -2096,7 +2149,7 @@ int prep_frame(rx_run &r)
             r.fgather[v][(size_t)c] = 8 * N * j + r.gather[(size_t)(((int64_t)q + (int64_t)j * fm.sym_rot) % n_c)];
         }
     }
-    return WOFDM_OK;
+    return ldpc ? prep_ldpc(r) : WOFDM_OK;
 }
 
 // The taps as the kernels read them.  Of moving channels the knots, [n_tracks][n_channels][n_knots][WOFDM_LT], zero padded, and
@@ -2139,7 +2192,7 @@ uint64_t rx_job_bytes(const rx_run &r)
     // the frame-spanning code: 512 bytes of survivor history per point and block of 64 steps of the longest codeword, which the
     // codes' launches share
     return 8 * words + (c.soft.on ? 4 * NP * (uint64_t)c.soft.n_scales * ((S - 1) * N + S) : 0) + (c.code.on ? 8 * NP * (S - 1) * N : 0) +
-           (c.frm.on ? 512 * NP * (uint64_t)r.hist_blocks : 0);
+           (c.frm.on && !c.ldpc.on ? 512 * NP * (uint64_t)r.hist_blocks : 0);
 }
 
 // ---- the stages' device side: allocation, upload, and the stage's parameters in the chunk ----
@@ -2286,7 +2339,7 @@ int stage_code(rx_run &r)
         return fail(WOFDM_E_HIP, "upload failed");
     wofdm_codeparams &k = r.ck.cd;
     k.llr_scale = cd.llr_scale; k.soft = r.d_sbits; k.gather = r.d_gather; k.n_c = (int32_t)r.gather.size(); k.n_codes = cd.n_codes;
-    for (int i = 0; i < cd.n_codes; ++i) {
+    for (int i = 0; !r.c.ldpc.on && i < cd.n_codes; ++i) {
         k.rate[i] = cd.codes[i].rate;
         k.steps[i] = r.csteps[i];
     }
@@ -2295,10 +2348,36 @@ int stage_code(rx_run &r)
     return WOFDM_OK;
 }
 
+// the LDPC code's side (behind stage_code, in stage_frame's place): the frame's gather tables in use, the counters
+int stage_ldpc(rx_run &r)
+{
+    wofdm_ldpcparams &k = r.ck.ld;
+    k = wofdm_ldpcparams{};
+    for (int v = 0; v < 2; ++v) {
+        if (r.fnc[v] == 0) continue;
+        if (!r.d_fgather[v].alloc(r.fgather[v].size())) return fail(WOFDM_E_NOMEM, "device allocation failed (LDPC code)");
+        if (!r.d_fgather[v].upload(r.fgather[v].data(), r.fgather[v].size())) return fail(WOFDM_E_HIP, "upload failed");
+        k.gather[v] = r.d_fgather[v];
+        k.n[v] = r.ln[v];
+        k.W[v] = r.lW[v];
+    }
+    if (!r.d_lerrs.alloc(r.n_lerr)) return fail(WOFDM_E_NOMEM, "device allocation failed (LDPC code)");
+    if (hipMemset(r.d_lerrs, 0, r.n_lerr * 8) != hipSuccess) return fail(WOFDM_E_HIP, "upload failed");
+    k.errs = r.d_lerrs;
+    for (int i = 0; i < r.c.code.n_codes; ++i) {
+        const wofdm_ldpc_code &q = r.c.ldpc.codes[i];
+        r.ck.ld_code[i][0] = q.J; r.ck.ld_code[i][1] = q.L; r.ck.ld_code[i][2] = q.max_iter;
+        r.ck.ld_Z[i][0] = r.lZ[i][0]; r.ck.ld_Z[i][1] = r.lZ[i][1];
+    }
+    r.ck.ldpc_on = true;
+    return WOFDM_OK;
+}
+
 // the frame-spanning code's side (behind stage_code): the gather tables in use, the chunk's history, the counters
 int stage_frame(rx_run &r)
 {
     if (!r.c.frm.on) return WOFDM_OK;
+    if (r.c.ldpc.on) return stage_ldpc(r);
     wofdm_longparams &k = r.ck.fr;
     k = wofdm_longparams{};
     for (int v = 0; v < 2; ++v) {
@@ -2376,7 +2455,8 @@ int rx_profile_run(const rx_call &c)
     r.n_bpen = NP * g.cells * NSC * g.N;
     r.n_spen = NP * g.cells * NSC * (g.S - 1);
     r.n_cerr = c.code.on ? NP * g.cells * (size_t)c.code.n_codes * (g.S - 1) * 2 : 0;
-    r.n_ferr = c.frm.on ? NP * g.cells * (size_t)c.code.n_codes * 2 : 0;
+    r.n_ferr = c.frm.on && !c.ldpc.on ? NP * g.cells * (size_t)c.code.n_codes * 2 : 0;
+    r.n_lerr = c.ldpc.on ? NP * g.cells * (size_t)c.code.n_codes * 4 : 0;
     if (c.frm.on) r.n_cerr = 0;
     if ((rc = stage_base(r)) != WOFDM_OK || (rc = stage_points(r)) != WOFDM_OK || (rc = stage_amp(r)) != WOFDM_OK ||
         (rc = stage_pn(r)) != WOFDM_OK || (rc = stage_link(r)) != WOFDM_OK || (rc = stage_soft(r)) != WOFDM_OK ||
@@ -2386,7 +2466,7 @@ int rx_profile_run(const rx_call &c)
     // (a neighbour that loads no bin: the plain kernel)
     r.ck.arm = c.arm == RXP_ACI && !r.nb ? RXP_PLAIN : c.arm;
     std::vector<unsigned long long> herr(2 * r.n_out), hserr(2 * r.n_sym);
-    std::vector<unsigned long long> hcerr(r.n_cerr), hferr(r.n_ferr);
+    std::vector<unsigned long long> hcerr(r.n_cerr), hferr(r.n_ferr), hlerr(r.n_lerr);
     std::vector<double> hpow(r.n_out), hspow(r.n_sym), hptot(r.n_ptot), hbpen(r.n_bpen), hspen(r.n_spen);
     float ms = 0.f;
     hipError_t e = hipSuccess;
@@ -2404,7 +2484,8 @@ int rx_profile_run(const rx_call &c)
     }, &e, &ms);
     if (rc != WOFDM_OK) return rc;
     if (e != hipSuccess || !fetch(herr, r.d_errs.p) || !fetch(hpow, r.d_pow.p) || !fetch(hserr, r.d_serrs.p) || !fetch(hspow, r.d_stot.p) ||
-        !fetch(hptot, r.d_ptot.p) || !fetch(hbpen, r.d_btot.p) || !fetch(hspen, r.d_sptot.p) || !fetch(hcerr, r.d_cerrs.p) || !fetch(hferr, r.d_ferrs.p))
+        !fetch(hptot, r.d_ptot.p) || !fetch(hbpen, r.d_btot.p) || !fetch(hspen, r.d_sptot.p) || !fetch(hcerr, r.d_cerrs.p) || !fetch(hferr, r.d_ferrs.p) ||
+        !fetch(hlerr, r.d_lerrs.p))
         return fail(WOFDM_E_HIP, "receive-profile kernels or copy-back failed: %s",
                     hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
     add_to(c.errs, herr);
@@ -2416,6 +2497,7 @@ int rx_profile_run(const rx_call &c)
     add_to(c.soft.sym_penalty, hspen);
     add_to(c.code.code_errs, hcerr);
     add_to(c.frm.frame_errs, hferr);
+    add_to(c.ldpc.ldpc_errs, hlerr);
     g_rxprof_ms = ms;
     return WOFDM_OK;
 }
@@ -2571,7 +2653,8 @@ static int rx_tracking_call(const wofdm_cfg *cfg, int device, const float *w_tx,
                             const wofdm_link_point *points, int32_t n_scales, const float *scales, const uint8_t *pilots,
                             const wofdm_tracking_point *tracking, uint64_t *errs, double *err_power, uint64_t *sym_errs,
                             double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty,
-                            const decltype(rx_call::code) *code, const decltype(rx_call::frm) *frm = nullptr)
+                            const decltype(rx_call::code) *code, const decltype(rx_call::frm) *frm = nullptr,
+                            const decltype(rx_call::ldpc) *ldpc = nullptr)
 {
     if (!scales || !bit_penalty || !tracking) return fail(WOFDM_E_INVALID, "NULL argument (scales, bit_penalty or tracking)");
     if (n_scales < 1) return fail(WOFDM_E_INVALID, "n_scales=%d must be >= 1", n_scales);
@@ -2588,6 +2671,7 @@ static int rx_tracking_call(const wofdm_cfg *cfg, int device, const float *w_tx,
     c.trk = {true, pilots, tracking};
     if (code) c.code = *code;
     if (frm) c.frm = *frm;
+    if (ldpc) c.ldpc = *ldpc;
     const int rc = rx_link_stages(c, n_points, points);
     return rc != WOFDM_OK ? rc : rx_profile_run(c);
 }
@@ -2632,6 +2716,33 @@ int wofdm_rx_profile_coded_frame(const wofdm_cfg *cfg, int device, const float *
     return rx_tracking_call(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active, aci_h,
                             ref_power, n_points, points, n_scales, scales, pilots, tracking, errs, err_power, sym_errs, sym_power,
                             pa_power, bit_penalty, sym_penalty, &code, &frm);
+}
+
+int wofdm_rx_profile_ldpc(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                          const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                          int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
+                          const wofdm_link_point *points, int32_t n_scales, const float *scales, const uint8_t *pilots,
+                          const wofdm_tracking_point *tracking, float llr_scale, const int32_t *perm, int32_t n_codes,
+                          const wofdm_ldpc_code *codes, int32_t sym_rot, uint64_t *errs, double *err_power, uint64_t *sym_errs,
+                          double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty, uint64_t *ldpc_errs,
+                          int8_t *soft_bits)
+{
+    const decltype(rx_call::code) code = {true, llr_scale, perm, n_codes, nullptr, nullptr, soft_bits};
+    const decltype(rx_call::frm) frm = {true, sym_rot, nullptr};
+    const decltype(rx_call::ldpc) ldpc = {true, codes, ldpc_errs};
+    return rx_tracking_call(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active, aci_h,
+                            ref_power, n_points, points, n_scales, scales, pilots, tracking, errs, err_power, sym_errs, sym_power,
+                            pa_power, bit_penalty, sym_penalty, &code, &frm, &ldpc);
+}
+
+int wofdm_ldpc_lift(int32_t J, int32_t L, int32_t n)
+{
+    if (!ldpc_ranges_ok(J, L)) return fail(WOFDM_E_INVALID, "J=%d must be 3 ... 6 and L=%d in J + 1 ... 24", J, L);
+    if (n < 1 || n > (1 << 24)) return fail(WOFDM_E_INVALID, "n=%d must be 1 ... 2^24", n);
+    const int32_t Z = ldpc_lift(J, L, n);
+    if ((int64_t)(L - J) * Z - ((int64_t)L * Z - n) < 1)
+        return fail(WOFDM_E_INVALID, "(%d, %d) over %d positions has no information bit", J, L, n);
+    return Z;
 }
 
 int wofdm_code_steps(int32_t rate, int32_t n_c)
@@ -2727,6 +2838,51 @@ int wofdm_viterbi_decode_long(int device, int32_t rate, int32_t n_c, const int32
         return fail(WOFDM_E_HIP, "decoder kernel or copy-back failed: %s", hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
     std::memcpy(bits, hbits.data(), n_bits);
     if (metric) std::memcpy(metric, hmetric.data(), hmetric.size() * sizeof(int32_t));
+    return WOFDM_OK;
+}
+
+int wofdm_ldpc_decode(int device, int32_t J, int32_t L, int32_t max_iter, int32_t n, const int32_t *perm, int32_t n_cw, const int8_t *soft,
+                      uint8_t *bits, int32_t *iters, uint8_t *converged)
+{
+    if (!soft || !bits) return fail(WOFDM_E_INVALID, "NULL argument (soft or bits)");
+    if (!ldpc_ranges_ok(J, L)) return fail(WOFDM_E_INVALID, "J=%d must be 3 ... 6 and L=%d in J + 1 ... 24", J, L);
+    if (max_iter < 1 || max_iter > 64) return fail(WOFDM_E_INVALID, "max_iter=%d must be 1 ... 64", max_iter);
+    if (n < 1 || n_cw < 1) return fail(WOFDM_E_INVALID, "n=%d and n_cw=%d must be >= 1", n, n_cw);
+    if (n > WOFDM_LDPC_MAX_BITS) return fail(WOFDM_E_UNSUPPORTED, "n=%d exceeds %d", n, WOFDM_LDPC_MAX_BITS);
+    const int32_t Z = ldpc_lift(J, L, n);
+    if ((int64_t)(L - J) * Z - ((int64_t)L * Z - n) < 1)
+        return fail(WOFDM_E_INVALID, "(%d, %d) over %d positions has no information bit", J, L, n);
+    if (wofdm_ldpc_lds(J, L, Z) > WOFDM_LDPC_LDS_MAX) return fail(WOFDM_E_UNSUPPORTED, "the decoder's LDS exceeds %d bytes", WOFDM_LDPC_LDS_MAX);
+    if (perm && !is_permutation(perm, n)) return fail(WOFDM_E_INVALID, "perm is not a permutation of 0 ... %d", n - 1);
+    int rc = use_device(device);
+    if (rc != WOFDM_OK) return rc;
+    std::vector<int32_t> gather((size_t)n);
+    for (int32_t c = 0; c < n; ++c) gather[(size_t)c] = perm ? perm[c] : c;
+    const size_t n_soft = (size_t)n_cw * (size_t)n;
+    dev_buf<int8_t> d_soft;
+    dev_buf<int32_t> d_gather, d_iters;
+    dev_buf<uint8_t> d_bits, d_conv;
+    if (!d_soft.alloc(n_soft) || !d_gather.alloc(gather.size()) || !d_bits.alloc(n_soft) || !d_iters.alloc((size_t)n_cw) ||
+        !d_conv.alloc((size_t)n_cw))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (decoder)");
+    if (!d_soft.upload(soft, n_soft) || !d_gather.upload(gather.data(), gather.size())) return fail(WOFDM_E_HIP, "upload failed");
+    wofdm_ldpcparams lp{};
+    lp.soft = d_soft; lp.gather[0] = d_gather; lp.n[0] = n; lp.W[0] = 1; lp.Z[0] = Z; lp.J = J; lp.L = L; lp.max_iter = max_iter;
+    lp.cw_stride = n; lp.n_cw = (uint32_t)n_cw; lp.bits = d_bits; lp.iters = d_iters; lp.conv = d_conv;
+    std::vector<uint8_t> hbits(n_soft), hconv((size_t)n_cw);
+    std::vector<int32_t> hiters((size_t)n_cw);
+    hipError_t e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the decoder is in every auxiliary unit)
+        e = ax && ax->ldpc ? ax->ldpc(&lp, nullptr) : hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess || !fetch(hbits, d_bits.p) || !fetch(hiters, d_iters.p) || !fetch(hconv, d_conv.p))
+        return fail(WOFDM_E_HIP, "decoder kernel or copy-back failed: %s", hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
+    std::memcpy(bits, hbits.data(), n_soft);
+    if (iters) std::memcpy(iters, hiters.data(), hiters.size() * sizeof(int32_t));
+    if (converged) std::memcpy(converged, hconv.data(), hconv.size());
     return WOFDM_OK;
 }
 

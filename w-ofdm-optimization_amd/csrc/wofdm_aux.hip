@@ -2157,6 +2157,144 @@ __global__ void __launch_bounds__(64) wofdm_viterbi_long_kernel(const wofdm_long
     }
 }
 
+// The layered, normalised min-sum decoder of the quasi-cyclic (J, L) code of include/wofdm.h (wofdm_ldpcparams): pure integer,
+// held bit for bit to the numpy mirror.  One workgroup per codeword of blockDim.x = 64 ... 256 threads (the launcher: Z rounded up
+// to waves); Q (int16) and R (int8) live in LDS for the whole decode, the soft bits are gathered straight into Q.
+//   A layer i touches every variable at most once -- block column j holds one circulant of the block row --, so its Z checks
+// are independent and are strided over the threads; check r of layer i reads variable j Z + (r + s(i, j)) mod Z and R at
+// [edge][r]: consecutive threads, consecutive LDS words (R) or a rotation of them (Q).  Two passes over a check's edges: the
+// first finds the two smallest magnitudes of t = Q - R and the parity of the signs, the second forms t again and stores the new
+// R and Q; t is not kept in registers (the degree is up to 24 and not a compile-time number).  A barrier ends every layer.
+//   After the J layers the syndrome: every thread ORs the parities of its checks, the workgroup's OR (__syncthreads_or) is the
+// stop decision of ALL threads -- the barriers and the iteration loop's trip count are workgroup-uniform; the strided loops
+// between two barriers hold none.  |Q| <= 128 + 6 * 95: int16 never saturates.
+__global__ void __launch_bounds__(256) wofdm_ldpc_kernel(const wofdm_ldpcparams lp)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const uint64_t w = blockIdx.x;
+    const int wi = blockIdx.y;
+    int v = 0, pt = 0;
+    if (lp.errs != nullptr) {
+        pt = (int)(w % (uint64_t)lp.n_points);
+        v = lp.pts[pt].post != 0 ? 1 : 0;
+    }
+    if (wi >= lp.W[v]) return;                                          // (workgroup-uniform, before the first barrier)
+    const int J = lp.J, L = lp.L, n = lp.n[v], Z = lp.Z[v], n0 = L * Z, E = J * L - J * (J - 1) / 2;
+    int *__restrict__ cnt = reinterpret_cast<int *>(lsm);
+    int16_t *__restrict__ sh = reinterpret_cast<int16_t *>(lsm + 16);
+    int16_t *__restrict__ Q = reinterpret_cast<int16_t *>(lsm + WOFDM_LDPC_LDS_HEAD);
+    int8_t *__restrict__ R = reinterpret_cast<int8_t *>(lsm + WOFDM_LDPC_LDS_HEAD + ((2 * n0 + 3) & ~3));
+    const int8_t *__restrict__ soft = lp.soft + (int64_t)w * lp.cw_stride;
+    const int32_t *__restrict__ gather = lp.gather[v] + (size_t)wi * (size_t)n;
+
+    if (tid < 4) cnt[tid] = 0;
+    // s(i, j) = (i 2^j) mod Z
+    for (int x = tid; x < J * L; x += nt) {
+        const int i = x / L, j = x - i * L;
+        int p = 1 % Z;
+        for (int q = 0; q < j; ++q) {
+            p += p;
+            p = p >= Z ? p - Z : p;
+        }
+        sh[x] = (int16_t)((i * p) % Z);
+    }
+    for (int x = tid; x < n0; x += nt) Q[x] = x < n ? (int16_t)soft[gather[x]] : (int16_t)127;
+    {
+        uint32_t *__restrict__ R4 = reinterpret_cast<uint32_t *>(R);
+        const int words = (E * Z + 3) >> 2;
+        for (int x = tid; x < words; x += nt) R4[x] = 0u;
+    }
+    __syncthreads();
+
+    int it = 0;
+    bool conv = false;
+    while (it < lp.max_iter) {
+        int eb = 0;
+        for (int i = 0; i < J; ++i) {
+            const int deg = L - i;
+            const int16_t *__restrict__ si = sh + i * L + i;
+            for (int r = tid; r < Z; r += nt) {
+                int m1 = 255, m2 = 255, par = 0;
+                for (int e = 0; e < deg; ++e) {
+                    int c = r + si[e];
+                    c = c >= Z ? c - Z : c;
+                    const int t = (int)Q[(i + e) * Z + c] - (int)R[(eb + e) * Z + r];
+                    const int a = min(abs(t), 127);
+                    par ^= t < 0 ? 1 : 0;
+                    if (a < m1) {
+                        m2 = m1;
+                        m1 = a;
+                    } else if (a < m2) {
+                        m2 = a;
+                    }
+                }
+                const int g1 = (3 * m1) >> 2, g2 = (3 * m2) >> 2;
+                for (int e = 0; e < deg; ++e) {
+                    int c = r + si[e];
+                    c = c >= Z ? c - Z : c;
+                    const int qi = (i + e) * Z + c, ri = (eb + e) * Z + r;
+                    const int t = (int)Q[qi] - (int)R[ri];
+                    const int a = min(abs(t), 127);
+                    const int mag = a == m1 ? g2 : g1;
+                    const int rn = (par ^ (t < 0 ? 1 : 0)) != 0 ? -mag : mag;
+                    R[ri] = (int8_t)rn;
+                    Q[qi] = (int16_t)(t + rn);
+                }
+            }
+            eb += deg;
+            __syncthreads();
+        }
+        ++it;
+        // the syndrome of the hard decisions
+        int bad = 0;
+        for (int i = 0; i < J; ++i) {
+            const int deg = L - i;
+            const int16_t *__restrict__ si = sh + i * L + i;
+            for (int r = tid; r < Z; r += nt) {
+                int par = 0;
+                for (int e = 0; e < deg; ++e) {
+                    int c = r + si[e];
+                    c = c >= Z ? c - Z : c;
+                    par ^= (int)Q[(i + e) * Z + c] < 0 ? 1 : 0;
+                }
+                bad |= par;
+            }
+        }
+        // (a barrier as well: nobody writes Q for the next layer before everybody has read it)
+        if (__syncthreads_or(bad) == 0) {
+            conv = true;
+            break;
+        }
+    }
+
+    if (lp.errs == nullptr) {
+        uint8_t *__restrict__ out = lp.bits + w * (uint64_t)n;
+        for (int x = tid; x < n; x += nt) out[x] = Q[x] < 0 ? 1 : 0;
+        if (tid == 0) {
+            if (lp.iters != nullptr) lp.iters[w] = it;
+            if (lp.conv != nullptr) lp.conv[w] = conv ? 1 : 0;
+        }
+    } else {
+        // the information bits are variables J Z ... n - 1
+        int wrong = 0;
+        for (int x = J * Z + tid; x < n; x += nt) wrong += Q[x] < 0 ? 1 : 0;
+        if (wrong != 0) atomicAdd(&cnt[0], wrong);
+        __syncthreads();
+        if (tid == 0) {
+            const uint64_t job = w / (uint64_t)lp.n_points, cell = (lp.item0 + job) / lp.frames;
+            unsigned long long *e = lp.errs + (((uint64_t)pt * lp.cells + cell) * (uint64_t)lp.n_codes + (uint64_t)lp.code) * 4;
+            const int info = cnt[0];
+            if (info != 0) {
+                atomicAdd(e, (unsigned long long)info);
+                atomicAdd(e + 1, 1ull);
+            }
+            if (!conv) atomicAdd(e + 2, 1ull);
+            atomicAdd(e + 3, (unsigned long long)it);
+        }
+    }
+}
+
 // totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
 template <int N>
 __global__ void __launch_bounds__(64) wofdm_rxprof_reduce_kernel(const wofdm_rparams p, uint64_t cell0)
@@ -2696,6 +2834,40 @@ bool viterbi_long_ok(const wofdm_longparams &lp, bool profile)
                          lp.bits == nullptr && lp.frames >= 1
                    : lp.errs == nullptr && lp.bits != nullptr;
 }
+// the LDPC decoder: the code, the variants in use (profile: both may be, one with W = 0 is unused), the LDS
+bool ldpc_ok(const wofdm_ldpcparams &lp, bool profile)
+{
+    if (lp.J < 3 || lp.J > 6 || lp.L <= lp.J || lp.L > 24 || lp.max_iter < 1 || lp.max_iter > 64 || lp.soft == nullptr || lp.n_cw < 1)
+        return false;
+    for (int v = 0; v < (profile ? 2 : 1); ++v) {
+        if (profile && lp.W[v] == 0) continue;
+        if (lp.W[v] < 1 || lp.n[v] < 1 || lp.n[v] > WOFDM_LDPC_BITS || lp.gather[v] == nullptr || lp.Z[v] < lp.L ||
+            (int64_t)lp.L * lp.Z[v] < lp.n[v] || lp.J * lp.Z[v] >= lp.n[v] || lp.Z[v] > 32767 ||
+            wofdm_ldpc_lds(lp.J, lp.L, lp.Z[v]) > WOFDM_LDPC_LDS_MAX)
+            return false;
+    }
+    return profile ? lp.errs != nullptr && lp.pts != nullptr && lp.n_points >= 1 && lp.code >= 0 && lp.code < lp.n_codes &&
+                         lp.bits == nullptr && lp.frames >= 1
+                   : lp.errs == nullptr && lp.bits != nullptr && lp.W[0] == 1;
+}
+// one launch of the decoder: grid (n_cw, the most words per frame), Z rounded up to waves as the workgroup, at most 256 threads
+hipError_t ldpc_enqueue(const wofdm_ldpcparams &lp, bool profile, hipStream_t s)
+{
+    int Z = 0, W = 0;
+    for (int v = 0; v < (profile ? 2 : 1); ++v) {
+        if (lp.W[v] == 0) continue;
+        Z = lp.Z[v] > Z ? lp.Z[v] : Z;
+        W = lp.W[v] > W ? lp.W[v] : W;
+    }
+    if (W == 0) return hipSuccess;                                      // (no point carries a codeword)
+    const int lds = (int)wofdm_ldpc_lds(lp.J, lp.L, Z);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_ldpc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             lds);
+    if (e != hipSuccess) return e;
+    const unsigned threads = (unsigned)(Z >= 256 ? 256 : ((Z + 63) / 64) * 64);
+    hipLaunchKernelGGL(wofdm_ldpc_kernel, dim3(lp.n_cw, (unsigned)W), dim3(threads), (unsigned)lds, s, lp);
+    return hipSuccess;
+}
 // the ordered sums of the chunk onto the totals: per point of sp, or (null) the plain ones
 void rxprof_reduce_launch(const wofdm_rparams &r, const wofdm_sparams *sp, hipStream_t s)
 {
@@ -2724,10 +2896,10 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
     const bool link = c.arm == RXP_LINK, points = MAX_POINTS[c.arm] > 0;
     const bool nb = c.arm == RXP_ACI || (link && c.nb_on), sync = c.arm == RXP_SYNC || link, knots = c.arm == RXP_DOPPLER || link;
     const bool amp = c.arm == RXP_PA || link, walk = c.arm == RXP_PN || link, soft = link && c.soft_on, track = soft && c.track_on;
-    const bool code = track && c.code_on, frame = code && c.frame_on;
-    if (nb != c.nb_on || soft != c.soft_on || track != c.track_on || code != c.code_on || frame != c.frame_on ||
-        (code && !frame && !viterbi_ok(c.cd, true)) ||
-        (frame && (c.cd.soft == nullptr || !(c.cd.llr_scale > 0.f) || c.cd.n_codes < 1 || c.cd.n_codes > WOFDM_CODE_CODES)) ||
+    const bool code = track && c.code_on, frame = code && c.frame_on, ldpc = code && !frame && c.ldpc_on;
+    if (nb != c.nb_on || soft != c.soft_on || track != c.track_on || code != c.code_on || frame != c.frame_on || ldpc != c.ldpc_on ||
+        (code && !frame && !ldpc && !viterbi_ok(c.cd, true)) ||
+        ((frame || ldpc) && (c.cd.soft == nullptr || !(c.cd.llr_scale > 0.f) || c.cd.n_codes < 1 || c.cd.n_codes > WOFDM_CODE_CODES)) ||
         (track && (c.tk.pts == nullptr || r.S > 64)) || !rxprof_args_ok(&c.tx, r) || (points && !rxprof_points_ok(c.sp, r, MAX_POINTS[c.arm])) ||
         (nb && !rxprof_nb_ok(c, !link)) || (sync && (c.sp.pts == nullptr || c.sp.base == nullptr)) ||
         (knots && !rxprof_knots_ok(c.dp, r, link, link ? c.max_theta : 0)) || (amp && !rxprof_pa_ok(c)) ||
@@ -2796,6 +2968,22 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
             if (!viterbi_long_ok(lp, true)) return hipErrorInvalidValue;
             hipLaunchKernelGGL(wofdm_viterbi_long_kernel, dim3(lp.n_cw), dim3(64), 0, s, lp);
         }
+    } else if (ldpc) {
+        // the decoder behind the soft bits: one workgroup per (frame, point, word of the frame), one launch per code
+        wofdm_ldpcparams lp = c.ld;
+        lp.soft = c.cd.soft;
+        lp.cw_stride = (int64_t)(r.S - 1) * N * 8;
+        lp.pts = c.tk.pts; lp.n_points = c.sp.n_points; lp.n_codes = c.cd.n_codes;
+        lp.item0 = r.item0; lp.frames = r.frames; lp.cells = c.sp.cells;
+        lp.bits = nullptr; lp.iters = nullptr; lp.conv = nullptr;
+        lp.n_cw = (uint32_t)r.n_jobs * (uint32_t)lp.n_points;
+        for (int i = 0; i < lp.n_codes; ++i) {
+            lp.J = c.ld_code[i][0]; lp.L = c.ld_code[i][1]; lp.max_iter = c.ld_code[i][2]; lp.code = i;
+            lp.Z[0] = c.ld_Z[i][0]; lp.Z[1] = c.ld_Z[i][1];
+            if (!ldpc_ok(lp, true)) return hipErrorInvalidValue;
+            const hipError_t le = ldpc_enqueue(lp, true, s);
+            if (le != hipSuccess) return le;
+        }
     } else if (code) {
         // the decoder behind the soft bits: one wave per (frame, point, data symbol) and code
         wofdm_codeparams cd = c.cd;
@@ -2826,6 +3014,14 @@ hipError_t viterbi_long_launch(const wofdm_longparams *lp, hipStream_t s)
     return hipGetLastError();
 }
 
+// wofdm_ldpc_decode: the LDPC decoder on soft bits of the caller's
+hipError_t ldpc_launch(const wofdm_ldpcparams *lp, hipStream_t s)
+{
+    if (!ldpc_ok(*lp, false)) return hipErrorInvalidValue;
+    const hipError_t e = ldpc_enqueue(*lp, false, s);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
 }  // namespace
 
 const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
@@ -2836,7 +3032,7 @@ const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
 
 const wofdm_link_fns *WOFDM_CAT(wofdm_aux_link_n, WOFDM_TU_N)(void)
 {
-    static const wofdm_link_fns fns = {rx_profile_chunk, viterbi_launch, viterbi_long_launch};
+    static const wofdm_link_fns fns = {rx_profile_chunk, viterbi_launch, viterbi_long_launch, ldpc_launch};
     return &fns;
 }
 

@@ -104,10 +104,43 @@ struct wofdm_longparams {
     int32_t *metric;                  // [n_cw], or null
 };
 
+// The layered min-sum decoder wofdm_ldpc_kernel (wofdm_rx_profile_ldpc, wofdm_ldpc_decode) of the quasi-cyclic (J, L) code of
+// include/wofdm.h.  One launch decodes ONE code, one workgroup per codeword; a codeword reads variable x < n at byte
+// gather[v][wi n + x] of its block soft + w cw_stride, wi its index within the frame (the decoder alone: 0).  A variant v is a
+// word length as in wofdm_longparams; the profile's grid is (n_jobs n_points, the largest W in use), and a workgroup whose wi is not
+// below its variant's W leaves at once.  LDS: a header of WOFDM_LDPC_LDS_HEAD bytes (the counters, the J L shifts), Q as int16
+// [L Z] rounded up to four bytes, R as int8 [edge][Z], edge = the layer's edges in column order, the layers one behind the other.
+#define WOFDM_LDPC_BITS 16384              // WOFDM_LDPC_MAX_BITS of include/wofdm.h
+#define WOFDM_LDPC_LDS_HEAD 304            // 4 int32 counters, 6 x 24 int16 shifts
+#define WOFDM_LDPC_LDS_MAX 163584          // the 160 KiB of a gfx950 workgroup less the kernel's 256 static bytes (the OR's)
+struct wofdm_ldpcparams {
+    const int8_t *soft;               // the profile: [n_jobs][n_points][S - 1][n_fft][8]; the decoder alone: [n_cw][n]
+    const int32_t *gather[2];         // [W[v] n[v]] at least
+    int32_t n[2], W[2], Z[2];         // the word's positions, the words per frame (0: the variant is unused), the lift
+    int32_t J, L, max_iter;
+    int64_t cw_stride;
+    uint32_t n_cw;                    // grid x; the profile: n_jobs n_points, block w = (job, point)
+    // the profile (bits null): counted into errs[point][cell][n_codes][4] at code
+    unsigned long long *errs;         // {info-bit errors, codeword errors, unconverged codewords, iterations}, integer atomics
+    const wofdm_tpoint *pts;          // [n_points]
+    int32_t n_points, code, n_codes;
+    uint64_t item0, frames, cells;
+    // wofdm_ldpc_decode (errs null)
+    uint8_t *bits;                    // [n_cw][n[0]]
+    int32_t *iters;                   // [n_cw]
+    uint8_t *conv;                    // [n_cw]
+};
+// the decoder's LDS in bytes (host and launcher alike)
+static inline uint64_t wofdm_ldpc_lds(int32_t J, int32_t L, int32_t Z)
+{
+    const uint64_t q = (2ull * (uint64_t)L * (uint64_t)Z + 3ull) & ~3ull;
+    return WOFDM_LDPC_LDS_HEAD + q + (((uint64_t)Z * (uint64_t)(J * L - J * (J - 1) / 2) + 3ull) & ~3ull);
+}
+
 // The arms of the receive body (rxprof_body of wofdm_aux.hip, which says what each adds)
 enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
 
-// One chunk of a receive-profile call, whichever of the eleven: the victim's Tx chain, the receive kernel's parameters, and the
+// One chunk of a receive-profile call, whichever of the twelve: the victim's Tx chain, the receive kernel's parameters, and the
 // stages' parameter structs as the kernels take them.  The arm says which stages the chunk runs -- a stage's struct is read
 // only where its arm or RXP_LINK is on --; the link arm runs every stage, its points switch them, and only its neighbour
 // (no point has aci_on: nb_on = false), its demapper (wofdm_rx_profile_soft: soft_on) and, with the demapper, its tracking receiver
@@ -133,6 +166,11 @@ struct wofdm_rxchunk {
     int32_t fr_steps[WOFDM_CODE_CODES][2];   // frame_on: steps per code and variant
     int32_t n_tracks;                 // RXP_LINK: the tracks of dp's knots, the static one included
     int32_t max_theta;                // RXP_LINK: the largest timing offset of the points, or 0 (the knots cover the samples it reaches)
+    bool ldpc_on;                     // (wofdm_rx_profile_ldpc) needs code_on, never with frame_on: wofdm_ldpc_kernel over the frame's
+                                      // data symbols, one launch per code, in the place of the per-symbol decoder; of cd as frame_on
+    wofdm_ldpcparams ld;              // ldpc_on: gather, n, W, errs; the launcher fills in the rest
+    int32_t ld_code[WOFDM_CODE_CODES][3];    // ldpc_on: J, L, max_iter per code
+    int32_t ld_Z[WOFDM_CODE_CODES][2];       // ldpc_on: the lift per code and variant
 };
 
 struct wofdm_link_fns {
@@ -144,6 +182,8 @@ struct wofdm_link_fns {
     hipError_t (*viterbi)(const wofdm_codeparams *cd, hipStream_t s);
     // wofdm_viterbi_long_kernel on soft bits of the caller's (lp.errs null, lp.bits set): one wave per codeword, variant 0
     hipError_t (*viterbi_long)(const wofdm_longparams *lp, hipStream_t s);
+    // wofdm_ldpc_kernel on soft bits of the caller's (lp.errs null, lp.bits set): one workgroup per codeword, variant 0
+    hipError_t (*ldpc)(const wofdm_ldpcparams *lp, hipStream_t s);
 };
 const wofdm_link_fns *wofdm_aux_link_n64(void);
 const wofdm_link_fns *wofdm_aux_link_n128(void);

@@ -2252,3 +2252,326 @@ def coded_fer(prof):
         (prof.cw_err.shape[0],) + (1,) * (prof.cw_err.ndim - 2) + (-1,))
     with np.errstate(divide="ignore", invalid="ignore"):
         return np.where(words > 0, prof.cw_err.astype(np.float64) / np.where(words > 0, words, 1.0), np.nan)
+
+
+# ---- the coded link with a quasi-cyclic LDPC code (wofdm_rx_profile_ldpc, wofdm_ldpc_decode) ----
+
+#: the iterations a code runs at most where none are given
+LDPC_MAX_ITER = 30
+
+RxProfileLdpc = collections.namedtuple(
+    "RxProfileLdpc", RxProfileTracking._fields + ("info_err", "cw_err", "unconverged", "iterations", "info_bits", "codewords", "codes",
+                                                  "llr_scale", "sym_rot", "soft_bits"))
+RxProfileLdpc.__doc__ = """``RxProfileTracking``'s fields, and info_err, cw_err, unconverged, iterations (uint64) [points, pairs, n_snr,
+n_ch, codes]: the decoded info-bit errors, the codewords with one, the codewords whose syndrome never vanished and the iterations
+run, summed over the frames' codewords; info_bits [points, codes]: K of each code at the point's word length; codewords [points]:
+the codewords per cell (frames times W); codes [codes]: (J, L, max_iter); llr_scale; sym_rot; soft_bits (int8) [pairs, n_snr, n_ch,
+frames, points, S - 1, N, 8] or None."""
+
+
+def ldpc_lift(J, L, n):
+    """The lift of include/wofdm.h: the smallest prime Z >= max(L, ceil(n / L)) whose multiplicative order of 2 is at least L.
+    ValueError outside 3 <= J <= 6, J < L <= 24, n >= 1, or where K = (L - J) Z - (L Z - n) < 1."""
+    J, L, n = int(J), int(L), int(n)
+    if not (3 <= J <= 6 and J < L <= 24 and n >= 1):
+        raise ValueError("a code needs 3 <= J <= 6, J < L <= 24 and n >= 1")
+    Z = max(L, -(-n // L))
+    while True:
+        if Z >= 3 and all(Z % d for d in range(2, int(Z ** 0.5) + 1)) and all(pow(2, k, Z) != 1 for k in range(1, L)):
+            break
+        Z += 1
+    if (L - J) * Z - (L * Z - n) < 1:
+        raise ValueError("(%d, %d) over %d positions has no information bit" % (J, L, n))
+    return Z
+
+
+def ldpc_edges(J, L, n):
+    """(Z, [layer i: int64 [L - i, Z]]): the variable that edge e of check i Z + r joins, (i + e) Z + (r + s(i, i + e)) mod Z with
+    s(i, j) = (i 2^j) mod Z -- the check matrix of include/wofdm.h, layer by layer, edges in column order"""
+    Z = ldpc_lift(J, L, n)
+    r = np.arange(Z, dtype=np.int64)
+    return Z, [np.stack([j * Z + (r + (i * pow(2, j, Z)) % Z) % Z for j in range(i, int(L))]) for i in range(int(J))]
+
+
+def ldpc_encode(info, J, L, n):
+    """The encoder of include/wofdm.h: info [..., K] bits -> the codeword's n transmitted bits [..., n] (uint8), the information
+    bits at J Z ... n - 1 and the shortened positions zero; back-substitution from block row J - 1 up to 0"""
+    Z, idx = ldpc_edges(J, L, n)
+    info = np.asarray(info).astype(np.uint8) & 1
+    if info.shape[-1] != n - J * Z:
+        raise ValueError("the code has K = %d information bits" % (n - J * Z))
+    x = np.zeros(info.shape[:-1] + (int(L) * Z,), dtype=np.uint8)
+    x[..., J * Z:n] = info
+    for i in range(int(J) - 1, -1, -1):
+        x[..., idx[i][0]] = x[..., idx[i][1:]].sum(axis=-2, dtype=np.int64) & 1
+    return x[..., :n]
+
+
+def ldpc_decode_at(soft, J, L, stops, perm=None):
+    """``ldpc_decode`` at several max_iter in one run: {max_iter: (bits, iters, converged)} for every max_iter of ``stops`` -- a
+    decoder stopped at M is the longer run's state after M iterations, the words that converged earlier frozen"""
+    soft = np.atleast_2d(np.asarray(soft)).astype(np.int16)
+    n_cw, n = soft.shape
+    J, L = int(J), int(L)
+    Z, idx = ldpc_edges(J, L, n)
+    stops = sorted({int(m) for m in stops})
+    if not stops or stops[0] < 1 or stops[-1] > 64:
+        raise ValueError("max_iter must be 1 ... 64")
+    p = _check_perm(perm, n)
+    if p is not None:
+        soft = soft[:, p]
+    Q = np.full((n_cw, L * Z), 127, dtype=np.int16)
+    Q[:, :n] = soft
+    R = [np.zeros((n_cw, L - i, Z), dtype=np.int16) for i in range(J)]
+    iters, conv, live, res = np.zeros(n_cw, dtype=np.int32), np.zeros(n_cw, dtype=bool), np.arange(n_cw), {}
+    for it in range(1, stops[-1] + 1):
+        if live.size:
+            q = Q[live]
+            for i in range(J):
+                t = q[:, idx[i]] - R[i][live]
+                a = np.minimum(np.abs(t), 127)
+                m1 = a.min(axis=1, keepdims=True)
+                rest = a.copy()
+                np.put_along_axis(rest, a.argmin(axis=1)[:, None, :], 255, axis=1)
+                m2 = rest.min(axis=1, keepdims=True)
+                neg = t < 0
+                odd = np.logical_xor.reduce(neg, axis=1, keepdims=True) ^ neg      # (the other edges' negative signs)
+                mag = (3 * np.where(a == m1, m2, m1)) >> 2
+                new = np.where(odd, -mag, mag).astype(np.int16)
+                q[:, idx[i]] = t + new
+                R[i][live] = new
+            Q[live] = q
+            iters[live] = it
+            bad = np.zeros(live.size, dtype=bool)
+            for i in range(J):
+                bad |= np.logical_xor.reduce(q[:, idx[i]] < 0, axis=1).any(axis=1)
+            conv[live[~bad]] = True
+            live = live[bad]
+        if it in stops:
+            res[it] = ((Q[:, :n] < 0).astype(np.uint8), iters.copy(), conv.copy())
+    return res
+
+
+def ldpc_decode(soft, J, L, max_iter=LDPC_MAX_ITER, perm=None):
+    """The integer mirror of ``wofdm_ldpc_decode``, vectorised over the codewords and over the checks of a layer: soft [n_cw, n]
+    int8 (d > 0: a coded bit 0), variable c reading soft[:, perm[c]] (None: c); the layered, normalised min-sum decoder of
+    include/wofdm.h.  Returns (bits [n_cw, n] uint8, iters [n_cw] int32, converged [n_cw] bool)."""
+    return ldpc_decode_at(soft, J, L, (int(max_iter),), perm)[int(max_iter)]
+
+
+def ldpc_decode_gpu(soft, J, L, max_iter=LDPC_MAX_ITER, perm=None, device=0):
+    """``wofdm_ldpc_decode``: soft [n_cw, n] int8 -> (bits [n_cw, n] uint8, iters [n_cw] int32, converged [n_cw] bool).  No CPU
+    fallback."""
+    from . import _lib
+    soft = np.ascontiguousarray(np.atleast_2d(np.asarray(soft)), dtype=np.int8)
+    n_cw, n = soft.shape
+    p = _check_perm(perm, n)
+    bits = np.zeros((n_cw, n), dtype=np.uint8)
+    iters, conv = np.zeros(n_cw, dtype=np.int32), np.zeros(n_cw, dtype=np.uint8)
+    _lib.check(_lib.load().wofdm_ldpc_decode(int(device), int(J), int(L), int(max_iter), n, None if p is None else p.ctypes.data, n_cw,
+                                             soft.ctypes.data, bits.ctypes.data, iters.ctypes.data, conv.ctypes.data))
+    return bits, iters, conv != 0
+
+
+def _ldpc_code_list(codes):
+    from . import _lib
+    out = []
+    for c in ((4, 8),) if codes is None else codes:
+        c = tuple(int(x) for x in c)
+        if len(c) not in (2, 3):
+            raise ValueError("a code is (J, L) or (J, L, max_iter)")
+        c = c if len(c) == 3 else c + (LDPC_MAX_ITER,)
+        if not (3 <= c[0] <= 6 and c[0] < c[1] <= 24 and 1 <= c[2] <= 64):
+            raise ValueError("a code needs 3 <= J <= 6, J < L <= 24 and 1 <= max_iter <= 64")
+        out.append(c)
+    if not 1 <= len(out) <= _lib.CODE_MAX:
+        raise ValueError("1 to %d codes are needed" % _lib.CODE_MAX)
+    return out
+
+
+def ldpc_frame_words(n_f):
+    """(W, n): the codewords a frame of n_f coded-stream positions carries and their length, W = ceil(n_f / 16384), n = n_f // W"""
+    from . import _lib
+    W = -(-int(n_f) // _lib.LDPC_MAX_BITS)
+    return W, (int(n_f) // W if W else 0)
+
+
+def _ldpc_prepare(st, bits_per_sc, syms, act, pil, tps, codes, perm, llr_scale, sym_rot):
+    """(codes, perm or None, pos [n_c] as ``_code_prepare``'s, sym_rot, W [points], n [points], K [points, codes])"""
+    cl = _ldpc_code_list(codes)
+    on = np.ones(st.n_fft, dtype=bool) if act is None else np.asarray(act).reshape(-1) != 0
+    data = on & ~pil if pil is not None else on
+    pos = (8 * np.flatnonzero(data)[:, None] + np.arange(int(bits_per_sc))[None, :]).reshape(-1)
+    if not (np.isfinite(llr_scale) and llr_scale > 0):
+        raise ValueError("llr_scale must be finite and positive")
+    rot = default_sym_rot(pos.size, max(int(syms) - 1, 1)) % pos.size if sym_rot is None else int(sym_rot)
+    if not 0 <= rot < pos.size:
+        raise ValueError("sym_rot must be in [0, %d)" % pos.size)
+    words = [ldpc_frame_words(pos.size * max(int(syms) - 1 - int(q.post), 0)) for q in tps]
+    K = np.array([[n - J * ldpc_lift(J, L, n) if W else 0 for J, L, _ in cl] for W, n in words], dtype=np.int64).reshape(len(tps), len(cl))
+    return (cl, _check_perm(perm, pos.size), pos, rot, np.array([w[0] for w in words], dtype=np.int64),
+            np.array([w[1] for w in words], dtype=np.int64), K)
+
+
+def _decode_frame_ldpc(d, tp, pos, perm, codes, sym_rot):
+    """{info errors, codeword errors, unconverged, iterations} [codes, 4] of a frame's soft bits d [S - 1, N, 8]: its W codewords"""
+    out = np.zeros((len(codes), 4), dtype=np.uint64)
+    if d.shape[0] - int(bool(tp.post)) < 1:
+        return out
+    stream = frame_codewords(d, tp.post, pos, perm, sym_rot)
+    W, n = ldpc_frame_words(stream.size)
+    words = stream[:W * n].reshape(W, n)
+    for i, (J, L, max_iter) in enumerate(codes):
+        bits, iters, conv = ldpc_decode(words, J, L, max_iter)
+        info = bits[:, J * ldpc_lift(J, L, n):]
+        out[i] = info.sum(), info.any(axis=1).sum(), (~conv).sum(), iters.sum()
+    return out
+
+
+def frame_profile_ldpc(st, grids, noise_at, w_tx, w_rx, h, point, tracking, snr_db, bits_per_sc, walk, pilots=None, scales=None,
+                       llr_scale=LLR_SCALE, perm=None, codes=None, sym_rot=None, track=None, knot_step=None, ref_power=None,
+                       aci_grids=None, aci_h=None, active=None, mask=None, noise_before_truncate=1):
+    """fp64 host mirror of one frame and one point of ``wofdm_rx_profile_ldpc``: ``frame_profile_coded``'s outputs through the
+    near rule's weight, then {info errors, codeword errors, unconverged, iterations} [codes, 4] of the frame's codewords
+    (``ldpc_decode``)."""
+    sc = _soft_scales(scales)
+    syms = np.asarray(grids).shape[0]
+    tps, pil = _tracking_prepare(st, syms, 1, [tracking], pilots, active)
+    cl, p, pos, rot = _ldpc_prepare(st, bits_per_sc, syms, active, pil, tps, codes, perm, llr_scale, sym_rot)[:4]
+    front, out = _frame_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, walk, track, knot_step, ref_power,
+                             aci_grids, aci_h, active, mask, noise_before_truncate)
+    res = _tracking_outputs(st, front, out, w_rx, snr_db, bits_per_sc, sc, noise_before_truncate, pil, tps[0])
+    z, weight = _coded_z(st, front, res, w_rx, snr_db, bits_per_sc, noise_before_truncate, pil, tps[0])
+    d8 = np.zeros(z.shape[:2] + (8,), dtype=np.int8)
+    d8[..., :z.shape[-1]], t = soft_bits(z, llr_scale)
+    return res + (d8, t, weight, _decode_frame_ldpc(d8, tps[0], pos, p, cl, rot))
+
+
+def _ldpc_result(trk, lerr, K, W, frames, codes, llr_scale, sym_rot, soft):
+    return RxProfileLdpc(*trk, *(np.ascontiguousarray(lerr[..., i]) for i in range(4)), K, (W * int(frames)).astype(np.uint64),
+                         tuple(codes), float(llr_scale), int(sym_rot), soft)
+
+
+def rx_profile_ldpc_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                         tracking=None, pilots=None, scales=None, llr_scale=LLR_SCALE, perm=None, codes=None, sym_rot=None,
+                         tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None, mask=None,
+                         noise_before_truncate=1, with_near=False, with_soft=False):
+    """The host route of ``rx_profile_ldpc_gpu``: ``rx_profile_coded_frame_host``'s frames, points, arrays and soft bits, each
+    (frame, point)'s codewords through ``frame_interleaver`` and ``ldpc_decode`` for the codes ``codes`` -- (J, L) or (J, L,
+    max_iter) each, None: (4, 8) --; sym_rot None: ``default_sym_rot`` over S - 1 symbols.  Returns ``RxProfileLdpc`` (with_near:
+    and the near decisions); with_soft as in ``rx_profile_coded_host``."""
+    held = {}
+
+    def receiver(q, n_points, sc):
+        tps, pil = _tracking_prepare(st, q.S, n_points, tracking, pilots, q.act)
+        cl, p, pos, rot, W, _, K = _ldpc_prepare(st, q.k, q.S, q.act, pil, tps, codes, perm, llr_scale, sym_rot)
+        shape = (n_points, q.w_tx.shape[0], q.snr.size, q.hc.shape[0], len(cl), 4)
+        held.update(tps=tps, pil=pil, act=q.act, codes=cl, K=K, W=W, rot=rot, lerr=np.zeros(shape, np.uint64))
+        if with_soft:
+            lead = shape[1:4] + (int(frames), n_points, q.S - 1, st.n_fft)
+            held.update(d=np.zeros(lead + (8,), np.int8), t=np.zeros(lead + (q.k,), np.float64), w=np.zeros(lead, np.float64))
+
+        def one(i, tp):
+            def run(front, out, p_, s_, c_, f_):
+                res = _tracking_outputs(st, front, out, q.w_rx[p_], q.snr[s_], q.k, sc, q.nbt, pil, tp)
+                z, weight = _coded_z(st, front, res, q.w_rx[p_], q.snr[s_], q.k, q.nbt, pil, tp)
+                d8 = np.zeros(z.shape[:2] + (8,), dtype=np.int8)
+                d8[..., :q.k], t = soft_bits(z, llr_scale)
+                held["lerr"][i, p_, s_, c_] += _decode_frame_ldpc(d8, tp, pos, p, cl, rot)
+                if with_soft:
+                    held["d"][p_, s_, c_, f_, i], held["t"][p_, s_, c_, f_, i], held["w"][p_, s_, c_, f_, i] = d8, t, weight
+                return res
+            return run
+        return [one(i, tp) for i, tp in enumerate(tps)]
+    res = _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, scales, tracks,
+                      knot_step, aci_active, aci_h, ref_power, active, mask, noise_before_truncate, with_near, receiver)
+    soft = res[0] if with_near else res
+    dec, sym = _tracking_decisions(st, syms, frames, held["act"], held["pil"], held["tps"])
+    trk = RxProfileTracking(*soft[:-1], sym, dec)
+    prof = _ldpc_result(trk, held["lerr"], held["K"], held["W"], frames, held["codes"], llr_scale, held["rot"], held.get("d"))
+    if with_soft:
+        prof = (prof, held["t"], held["w"])
+    return (prof, res[1]) if with_near else prof
+
+
+def rx_profile_ldpc_chunk_frames(st, syms, masked, n_points, neighbour, n_scales):
+    """Frames one chunk of ``wofdm_rx_profile_ldpc`` holds: ``rx_profile_coded_chunk_frames``' -- the decoder's state is in LDS"""
+    return rx_profile_coded_chunk_frames(st, syms, masked, n_points, neighbour, n_scales)
+
+
+def rx_profile_ldpc_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                        tracking=None, pilots=None, scales=None, llr_scale=LLR_SCALE, perm=None, codes=None, sym_rot=None,
+                        tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None, mask=None,
+                        noise_before_truncate=1, device=0, out=None, export=False):
+    """``wofdm_rx_profile_ldpc``: ``rx_profile_coded_frame_gpu``'s frames, tracking fields, soft bits and frame interleaver -- those
+    calls' bytes --, and per point and frame W codewords of the quasi-cyclic LDPC codes ``codes`` ((J, L) or (J, L, max_iter)
+    each, None: (4, 8)), decoded on the GPU by the layered min-sum decoder.  export=True also returns the soft bits.  Returns
+    ``RxProfileLdpc``; ``out`` (an earlier result of the same shape, scales, codes and sym_rot) is accumulated into (its soft bits
+    are dropped).  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    sc = _soft_scales(scales)
+    points = [LinkPoint()] if points is None else points
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts, tr, iact, hi, ref = _link_sides(st, prepared[2], points, tracks, aci_active, aci_h, ref_power, prepared[0].shape[0])
+    tps, pil = _tracking_prepare(st, syms, len(pts), tracking, pilots, prepared[4])
+    cl, p, _, rot, W, _, K = _ldpc_prepare(st, bits_per_sc, syms, prepared[4], pil, tps, codes, perm, llr_scale, sym_rot)
+    trf = None if tr is None else _lib.c64_as_f32(tr)
+    hif = None if hi is None else _lib.c64_as_f32(hi)
+    lin = PaPoint(PA_LINEAR, 0.0)
+    cpts = (_lib.LinkPoint * len(pts))(*[
+        _lib.LinkPoint(*(q.pa or lin), -1 if q.track is None else q.track, q.timing, q.cfo, q.cfo_tracked, q.linewidth, q.cpe_tracked,
+                       int(q.aci is not None), *(q.aci or (0, 0.0)), (C.c_int32 * 4)(0, 0, 0, 0)) for q in pts])
+    ctps = (_lib.TrackingPoint * len(tps))(*[_lib.TrackingPoint(q.cpe, q.post, (C.c_int32 * 2)(0, 0)) for q in tps])
+    ccodes = (_lib.LdpcCode * len(cl))(*[_lib.LdpcCode(J, L, m, 0) for J, L, m in cl])
+    pil8 = None if pil is None else np.ascontiguousarray(pil, dtype=np.uint8)
+    knots = (0, 0, 0) if tr is None else (tr.shape[0], tr.shape[2], int(knot_step))
+    prev = None
+    if out is not None:
+        if not np.array_equal(out.scales, sc) or tuple(out.codes) != tuple(cl) or out.sym_rot != rot:
+            raise ValueError("out has other scales, codes or sym_rot")
+        prev = _RxSoftSums(*out[:9], np.zeros(st.n_fft, dtype=np.uint64))
+    cells = (prepared[0].shape[0], prepared[3].size, prepared[2].shape[0])
+    lerr = np.zeros((len(pts),) + cells + (len(cl), 4), dtype=np.uint64)
+    sb = np.zeros(cells + (int(frames), len(pts), int(syms) - 1, st.n_fft, 8), dtype=np.int8) if export else None
+    res = _gpu_call("wofdm_rx_profile_ldpc", _RxSoftSums, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                    noise_before_truncate, device, prev, lead=(len(pts),), n_scales=sc.size,
+                    after_mask=(None if trf is None else trf.ctypes.data, *knots, None if iact is None else iact.ctypes.data,
+                                None if hif is None else hif.ctypes.data, None if ref is None else ref.ctypes.data, len(pts), cpts,
+                                int(sc.size), sc.ctypes.data, None if pil8 is None else pil8.ctypes.data, ctps,
+                                C.c_float(float(llr_scale)), None if p is None else p.ctypes.data, len(cl), ccodes, int(rot)),
+                    behind=(lerr.ctypes.data, None if sb is None else sb.ctypes.data))
+    dec, sym = _tracking_decisions(st, syms, frames, prepared[4], pil, tps)
+    if out is not None:
+        if out.decisions.shape != dec.shape:
+            raise ValueError("out has another shape")
+        dec, sym = out.decisions + dec, out.decisions_sym + sym
+    prof = _ldpc_result(_tracking_result(res, sc, dec, sym), lerr, K, W, frames, cl, llr_scale, rot, sb)
+    if out is not None:
+        prof = prof._replace(info_err=out.info_err + prof.info_err, cw_err=out.cw_err + prof.cw_err,
+                             unconverged=out.unconverged + prof.unconverged, iterations=out.iterations + prof.iterations,
+                             codewords=out.codewords + prof.codewords)
+    return prof
+
+
+def _ldpc_per_word(prof, counts, per_word):
+    words = (prof.codewords.astype(np.float64)[:, None] * per_word).reshape(
+        (counts.shape[0],) + (1,) * (counts.ndim - 2) + (-1,))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(words > 0, counts.astype(np.float64) / np.where(words > 0, words, 1.0), np.nan)
+
+
+def ldpc_ber(prof):
+    """The decoded info-bit error rate of the frames' codewords [points, pairs, n_snr, n_ch, codes]; NaN where a point carried no
+    codeword"""
+    return _ldpc_per_word(prof, prof.info_err, prof.info_bits.astype(np.float64))
+
+
+def ldpc_fer(prof):
+    """The codeword error rate (any info bit wrong), shaped as ``ldpc_ber``'s"""
+    return _ldpc_per_word(prof, prof.cw_err, (prof.info_bits > 0).astype(np.float64))
+
+
+def ldpc_mean_iterations(prof):
+    """The iterations run per codeword, shaped as ``ldpc_ber``'s"""
+    return _ldpc_per_word(prof, prof.iterations, (prof.info_bits > 0).astype(np.float64))
