@@ -9,9 +9,18 @@ namespace {
 // ~4 cycles per SIMD whether it is v_fma_f32 or v_pk_fma_f32 (tools/ubench/valu_rate.hip:
 // 4.5 vs 5.1 cycles), so the fp32 peak is only reachable with packed math, and complex
 // arithmetic packs naturally as (re, im).
+// That price holds with the matrix pipe idle.  Beside MFMAs a packed fp32 instruction waits for the pipe where a plain one issues
+// under it (tools/ubench/valu_beside_mfma.hip, profiles/packed_beside_mfma.txt: 13 v_pk_fma_f32 behind each MFMA of a wave cost
+// 57 cycles per MFMA more than alone, 13 v_fma_f32 24), so the matrix-pipe FIR's kernels write the arithmetic that sits between and
+// right behind their tile's MFMAs per component (fma2 / mul2 below) -- the sites an A/B of correct builds confirmed, no others.
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ v2f mk(float x, float y) { return (v2f){x, y}; }
+
+// a b + c and a w per component: the two IEEE operations of v_pk_fma_f32 / v_pk_mul_f32 as plain instructions (-fno-slp-vectorize:
+// nothing packs them again)
+__device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return mk(__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)); }
+__device__ __forceinline__ v2f mul2(v2f a, float w) { return mk(a.x * w, a.y * w); }
 
 __device__ __forceinline__ v2f ldg2(const float2 *p) { const float2 t = *p; return mk(t.x, t.y); }
 

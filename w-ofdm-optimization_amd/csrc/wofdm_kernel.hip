@@ -519,14 +519,18 @@ __device__ __forceinline__ void radix8_elems(f4 &r0, f4 &i0, f4 &r1, f4 &i1)
 // convert + scale is needed.  UNIT = false leaves out the factor sqrt(2 ln 2) of the radius
 // (-2 ln u1 = 2 ln2 * -log2 u1): where the noise only meets its own measured power (g = sqrt(Ps nlin / Pn),
 // r = c + g n) a common factor cancels exactly; WOFDM_NOISE_UNSCALE restores it for stage dumps.
+// PLAIN: (cos, sin) x radius as two v_mul_f32 instead of one v_pk_mul_f32 -- for the callers that draw their noise between and behind
+// the MFMAs of the FIR's tile (the kernels of the matrix-pipe FIR: the only users of UNIT = false), where the packed multiply waits
+// for the matrix pipe (wofdm_device.h; C2 -0.8 % in an interleaved A/B, profiles/packed_beside_mfma.txt).  The same two products.
 #define WOFDM_NOISE_UNSCALE 1.1774100225154747f
-template <bool UNIT = true> __device__ __forceinline__ v2f box_muller(uint32_t a, uint32_t b)
+template <bool UNIT = true, bool PLAIN = !UNIT> __device__ __forceinline__ v2f box_muller(uint32_t a, uint32_t b)
 {
     const float u1 = fmaf((float)a, 2.3283064365386963e-10f, 1.1641532182693481e-10f);
     const float u2 = __builtin_bit_cast(float, __builtin_amdgcn_alignbit(0x7Fu, b, 9));   // 1 + (b >> 9) 2^-23
     const float l2 = __builtin_amdgcn_logf(u1);
     const float rad = UNIT ? __builtin_amdgcn_sqrtf(-1.3862943611198906f * l2) : __builtin_amdgcn_sqrtf(-l2);
-    return mk(__builtin_amdgcn_cosf(u2), __builtin_amdgcn_sinf(u2)) * rad;
+    if constexpr (PLAIN) return mul2(mk(__builtin_amdgcn_cosf(u2), __builtin_amdgcn_sinf(u2)), rad);
+    else return mk(__builtin_amdgcn_cosf(u2), __builtin_amdgcn_sinf(u2)) * rad;
 }
 
 // One block of stream `stream` of (seed, cell, frame), Philox4x32-10 as in philox.h with the
@@ -2447,7 +2451,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                 // next tile's rows requested ten instructions ahead of their use -- 499 cycles per tile for a wave on its own,
                 // 274 of them vector issue (profiles/r04_stamp_occ.txt).  Here the Philox rounds of the tile's noise pair sit
                 // BETWEEN the MFMAs (two rounds = eight instructions = 34 cycles per gap: the chain never waits), the Box-Muller
-                // transform (18 instructions) behind the last one takes the place of the wait states, the guard behind it keeps
+                // transform (20 instructions, its radius multiplies per component) behind the last one takes the place of the wait states, the guard behind it keeps
                 // the operands allocated up to there without spending a cycle, and the next tile's rows are requested a whole
                 // tile ahead.  tests/test_code_layout.py checks the distances in the built code.
                 bops o = bq;
@@ -2494,7 +2498,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
 #undef WOFDM_TIE
                 n0 = box_muller<false>(c0, c1);
                 n1 = box_muller<false>(c2, c3);
-                // ... and ends in front of the guard: 18 vector instructions (two of them per 16 cycles at best) between the last
+                // ... and ends in front of the guard: 20 vector instructions (two of them per 16 cycles at best) between the last
                 // MFMA and the first instruction that may read its result or write one of its operand registers
                 asm volatile("" : "+v"(d), "+v"(n0), "+v"(n1) : "v"(o.h0), "v"(o.h1), "v"(o.l0), "v"(o.l1), "v"(A[0]), "v"(A[1]), "v"(A[2]), "v"(A[3]));
             } else {
@@ -2526,10 +2530,12 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
             // (selects, not branches: columns behind the wave's samples may hold anything)
             const v2f a0 = valid ? c0 : zero2, a1 = valid1 ? c1 : zero2;
             const v2f m0 = valid ? n0 : zero2, m1 = valid1 ? n1 : zero2;
-            ps2 = __builtin_elementwise_fma(a0, a0, ps2);
-            ps2 = __builtin_elementwise_fma(a1, a1, ps2);
-            pn2 = __builtin_elementwise_fma(m0, m0, pn2);
-            pn2 = __builtin_elementwise_fma(m1, m1, pn2);
+            // (the power sums per component, two accumulators per lane as before: the four v_pk_fma_f32 of a tile sat right behind
+            // its chain and waited for the matrix pipe -- wofdm_device.h)
+            ps2 = fma2(a0, a0, ps2);
+            ps2 = fma2(a1, a1, ps2);
+            pn2 = fma2(m0, m0, pn2);
+            pn2 = fma2(m1, m1, pn2);
             if (DUMP) {
                 const v2f e0 = c0 * p.dump_unscale_rx, e1 = c1 * p.dump_unscale_rx;
                 if (p.dump.conv) {
@@ -2576,10 +2582,10 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
             const v2f c0 = mk(d.x, d.y), c1 = mk(d.z, d.w);
             const v2f a0 = v0 ? c0 : zero2, a1 = v1 ? c1 : zero2;
             const v2f m0 = v0 ? n0 : zero2, m1 = v1 ? n1 : zero2;
-            ps2 = __builtin_elementwise_fma(a0, a0, ps2);
-            ps2 = __builtin_elementwise_fma(a1, a1, ps2);
-            pn2 = __builtin_elementwise_fma(m0, m0, pn2);
-            pn2 = __builtin_elementwise_fma(m1, m1, pn2);
+            ps2 = fma2(a0, a0, ps2);
+            ps2 = fma2(a1, a1, ps2);
+            pn2 = fma2(m0, m0, pn2);
+            pn2 = fma2(m1, m1, pn2);
             if (DUMP) {
                 const v2f e0 = c0 * p.dump_unscale_rx, e1 = c1 * p.dump_unscale_rx;
                 if (p.dump.conv) {
@@ -2861,8 +2867,8 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                 // (odd strides, one symbol per wave: the row's last pair holds one sample of the row; the 16 bytes would reach
                 // into the next wave's row)
                 const bool half = ODDB && jr == LW - 1;
-                const v2f r0 = __builtin_elementwise_fma(mk(g, g), nz[2 * G], acc[2 * G]);
-                const v2f r1 = __builtin_elementwise_fma(mk(g, g), nz[2 * G + 1], acc[2 * G + 1]);
+                const v2f r0 = fma2(mk(g, g), nz[2 * G], acc[2 * G]);              // (per component: wofdm_device.h)
+                const v2f r1 = fma2(mk(g, g), nz[2 * G + 1], acc[2 * G + 1]);
                 v2f *dst = (FIR8 || jl < SPWR2 * B - 128 * G ? rxb : rxb1) + 128 * G;
                 if constexpr (PARTG) {
                     const bool idn = FIR8 ? jr >= rx_xb : ((jr >= rx_xb && jr < rx_len) || jr >= rx_len + rx_xb);
