@@ -1094,8 +1094,9 @@ int wofdm_rx_profile_coded_frame(const wofdm_cfg *cfg, int device,
  *   Parity and information.  Block columns 0 ... J - 1 are the parity part, block upper triangular with permutations on the
  * diagonal; the full length is n0 = L Z >= n.  The code is shortened by s = n0 - n: variables n ... n0 - 1 are known zeros and are
  * not transmitted.  The information bits are variables J Z ... n - 1, K = (L - J) Z - s of them; K >= 1, or the code is invalid.
- *   Encoder (the Python mirror only: the profile's codeword is all zero in the random-coset view).  Back-substitution from block
- * row J - 1 up to 0: a row's parity block is the XOR of the row's other blocks through the diagonal block's permutation.
+ *   Encoder (wofdm_ldpc_encode below; wofdm_rx_profile_ldpc needs none, its codeword is all zero in the random-coset view).
+ * Back-substitution from block row J - 1 up to 0: a row's parity block is the XOR of the row's other blocks through the diagonal
+ * block's permutation.
  *   Decoder: pure integer, layered, normalised min-sum.  Start: Q[v] = d[v] (int8, any value, -128 included) for v < n and 127
  * for the shortened positions -- ordinary variables from there on --; R[e] = 0 on every edge.  One iteration is the layers i = 0 ...
  * J - 1 in order; a layer touches each variable at most once, so its checks are independent.  For a check and each of its edges j:
@@ -1184,6 +1185,104 @@ int wofdm_rx_profile_ldpc(const wofdm_cfg *cfg, int device,
                           double *sym_penalty,           /* [n_points][cells][n_scales][S-1], or NULL */
                           uint64_t *ldpc_errs,           /* [n_points][cells][n_codes][4], ACCUMULATED into */
                           int8_t *soft_bits);            /* [cells][frames][n_points][S-1][n_fft][8], or NULL */
+
+/* Random information words: the coded link without the all-zero view.
+ *   The three coded calls above count a decoded 1 as an error: the Philox labels are the scrambler and the transmitted codeword
+ * is all zero.  That is exact for a decoder that treats 0 and 1 alike, and neither of these does -- the Viterbi survivor is p0
+ * unless p1 is STRICTLY smaller, the min-sum decoder counts t = 0 as positive and decides x = (Q < 0) --, so every tie and every
+ * soft bit that is exactly 0 falls towards the transmitted word.  Here the transmitted word is random.
+ *   Information stream.  A fifth Philox stream, 4 (WOFDM_STREAM_INFO of csrc/wofdm_link.h), beside the four of csrc/philox.h: block b of (seed, cell, frame) is
+ * philox4x32_10 of counter (b, frame lo, frame hi, 4 << 28 | cell) under key (seed lo, seed hi), frame the global frame index as
+ * in the other streams; bit i of the frame's stream is bit i mod 32 of word (i mod 128) div 32 of block i div 128.  The stream
+ * depends neither on the point nor on the code: every point and every code of a call carries the same information, so they
+ * compare pairwise, as labels and noise already do.  wofdm_coset_info (host only) writes bits 0 ... n_bits - 1 as bytes;
+ * WOFDM_E_INVALID for NULL bits, n_bits < 0 or cell >= 2^28. */
+int wofdm_coset_info(uint64_t seed, uint32_t cell, uint64_t frame, int32_t n_bits,
+                     uint8_t *bits);                        /* [n_bits] */
+
+/* The K = 7 encoder of wofdm_rx_profile_coded's code on the GPU: n_cw information words of T - 6 bits each (bytes; bit 0 counts), T
+ * = wofdm_code_steps(rate, n_c); six zero tail steps are appended; coded[w][c] is the kept output with coded-stream index c, A
+ * before B, punctured as defined there, and the left-over positions c >= the kept outputs' number are 0.  Every output is a parity
+ * of seven information bits, so a lane takes one step and stores at the closed-form positions of its outputs; it equals the
+ * Python mirror conv_encode bit for bit.  Checks, those of wofdm_viterbi_decode_long and before the device is touched:
+ * WOFDM_E_INVALID for NULL info or coded, a rate outside {0, 1, 2}, n_c or n_cw < 1, T < 7; WOFDM_E_UNSUPPORTED for T >
+ * WOFDM_CODE_LONG_MAX_STEPS.  The call holds the launch gate while its kernel runs; it neither counts for nor resets
+ * wofdm_rx_profile_kernel_ms. */
+int wofdm_conv_encode(int device, int32_t rate, int32_t n_c, int32_t n_cw,
+                      const uint8_t *info,                  /* [n_cw][T - 6] */
+                      uint8_t *coded);                      /* [n_cw][n_c] */
+
+/* The encoder of the (J, L) code over n positions on the GPU: n_cw information words of K bits each (bytes; bit 0 counts) on
+ * variables J Z ... n - 1, word[w][v] = x[v] for v < n.  Back-substitution from block row J - 1 up to 0: check r of row i XORs
+ * x[j Z + (r + s(i, j)) mod Z] over j > i, and the result is variable i Z + (r + s(i, i)) mod Z.  One workgroup per word, the
+ * word as bits in LDS, a row's Z checks strided over the threads, one barrier per row; it equals the Python mirror ldpc_encode bit
+ * for bit.  Checks: wofdm_ldpc_decode's without max_iter and perm, in that order, before the device is touched.  The call holds
+ * the launch gate while its kernel runs; it neither counts for nor resets wofdm_rx_profile_kernel_ms. */
+int wofdm_ldpc_encode(int device, int32_t J, int32_t L, int32_t n, int32_t n_cw,
+                      const uint8_t *info,                  /* [n_cw][K] */
+                      uint8_t *word);                       /* [n_cw][n] */
+
+/* Both decoders on random transmitted words, on the same frames: wofdm_rx_profile_coded_frame's and wofdm_rx_profile_ldpc's
+ * frames, soft bits d, frame interleaver (perm, sym_rot), n_f, T, W, n and Z, with 0 ... WOFDM_CODE_MAX Viterbi codes and 0 ...
+ * WOFDM_CODE_MAX LDPC codes, at least one in all.  The receive chain runs once for both families.
+ *   Transmitted words.  A Viterbi code's word is the encoder's (wofdm_conv_encode) of the frame's stream bits 0 ... T - 7; LDPC word w
+ * of a code carries stream bits w n ... w n + K - 1 on variables J Z ... n - 1 (wofdm_ldpc_encode).  The decoder for coded-stream
+ * index c sees d' = x_c ? -d : d, x_c the transmitted coded bit (|d| <= 127: the negation is exact; left-over and shortened
+ * positions have x = 0): the implied scrambler is label XOR x, and not a single frame changes.
+ *   Counting.  Viterbi: an info-bit error is a decoded u_t != stream bit t, t < T - 6; a codeword error is any u_t wrong, the
+ * tail checked against 0.  LDPC: info-bit errors are x[v] != the transmitted x[v] on J Z <= v < n, a codeword error any of them;
+ * unconverged words and iterations as in wofdm_rx_profile_ldpc.
+ *   Arguments: every argument of wofdm_rx_profile_coded_frame through perm; n_codes, codes; n_ldpc, ldpc_codes; sym_rot; the seven
+ * outputs of wofdm_rx_profile_tracking, that call's bytes; frame_errs[point][cell][code] as wofdm_rx_profile_coded_frame's and
+ * ldpc_errs[point][cell][code] as wofdm_rx_profile_ldpc's, ACCUMULATED into, each NULL exactly where its count is 0; soft_bits as
+ * in the coded calls, the same bytes (d, not d').
+ *   Fused: no codeword is ever in device memory.  The streaming Viterbi instantiation draws one Philox block per 128 steps, forms a
+ * step's A and B from seven stream bits and XORs the traceback's 64-bit decision masks with the stream; the LDPC instantiation
+ * draws its word's information bits, encodes them in LDS -- 4 ceil(L Z / 32) bytes beside the decoder's --, flips the signs
+ * while it gathers and compares with the kept word at the end.  One launch per code.
+ *   Identities, by bytes: the counters depend neither on where a chunk ends, nor on the other points or codes (of either family)
+ * of the call, nor on whether soft_bits is requested; repeated calls are identical; they equal wofdm_viterbi_decode_long and
+ * wofdm_ldpc_decode on the exported soft bits gathered through the frame interleaver and flipped by the transmitted words.
+ *   Checks, in this order: wofdm_rx_profile_coded_frame's through perm and the size of soft_bits (llr_scale; perm; soft_bits), then
+ * WOFDM_E_INVALID for n_codes or n_ldpc < 0; WOFDM_E_UNSUPPORTED for either above WOFDM_CODE_MAX; WOFDM_E_INVALID for both 0; for
+ * NULL codes or ldpc_codes where the count is > 0; for sym_rot outside [0, n_c); for NULL frame_errs or ldpc_errs where the count
+ * is > 0; then the Viterbi codes as wofdm_rx_profile_coded_frame checks them (rate, reserved; T < 7; T beyond the limit) and the
+ * LDPC codes as wofdm_rx_profile_ldpc does, the LDS guard with the word's bits included.  Every argument is checked before the
+ * device is touched; a failed check leaves all outputs as they were.
+ *   Chunks: wofdm_rx_profile_coded_frame's formula, its history term only where n_codes > 0.
+ *   A successful call holds the launch gate and counts for wofdm_rx_profile_kernel_ms.
+ *   Measured: tools/bench_rx_profile_coset.py, profiles/rx_profile_coset.txt. */
+int wofdm_rx_profile_coset(const wofdm_cfg *cfg, int device,
+                           const float *w_tx,             /* [pairs][P] */
+                           const float *w_rx,             /* [pairs][N+tail_rx] */
+                           const float *h,                /* [n_channels][n_taps][2] */
+                           const float *snr_db,           /* [n_snr] */
+                           const uint8_t *active,         /* [n_fft] or NULL */
+                           const float *tx_mask,          /* [2P-1] or NULL */
+                           const float *h_track,          /* [n_tracks][n_channels][n_knots][n_taps][2], or NULL */
+                           int32_t n_tracks, int32_t n_knots, int32_t knot_step,
+                           const uint8_t *aci_active,     /* [n_fft], or NULL */
+                           const float *aci_h,            /* [n_channels][n_taps][2], or NULL = h */
+                           const float *ref_power,        /* [pairs], or NULL */
+                           int32_t n_points, const wofdm_link_point *points,
+                           int32_t n_scales, const float *scales,
+                           const uint8_t *pilots,         /* [n_fft], or NULL */
+                           const wofdm_tracking_point *tracking, /* [n_points] */
+                           float llr_scale,
+                           const int32_t *perm,           /* [n_c], or NULL */
+                           int32_t n_codes, const wofdm_code *codes,
+                           int32_t n_ldpc, const wofdm_ldpc_code *ldpc_codes,
+                           int32_t sym_rot,               /* in [0, n_c) */
+                           uint64_t *errs,                /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                           double *err_power,             /* [n_points][cells][n_fft], or NULL */
+                           uint64_t *sym_errs,            /* [n_points][cells][S-1][2], or NULL */
+                           double *sym_power,             /* [n_points][cells][S-1], or NULL */
+                           double *pa_power,              /* [n_points][cells][2], or NULL */
+                           double *bit_penalty,           /* [n_points][cells][n_scales][n_fft], ACCUMULATED into */
+                           double *sym_penalty,           /* [n_points][cells][n_scales][S-1], or NULL */
+                           uint64_t *frame_errs,          /* [n_points][cells][n_codes][2], ACCUMULATED into; NULL where n_codes = 0 */
+                           uint64_t *ldpc_errs,           /* [n_points][cells][n_ldpc][4], ACCUMULATED into; NULL where n_ldpc = 0 */
+                           int8_t *soft_bits);            /* [cells][frames][n_points][S-1][n_fft][8], or NULL */
 
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

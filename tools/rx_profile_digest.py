@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: the bytes of the twelve receive-profile entry points and of wofdm_tx_papr, as SHA-256 digests -- for comparing two builds of the
+"""Developer tool: the bytes of the thirteen receive-profile entry points and of wofdm_tx_papr, as SHA-256 digests -- for comparing two builds of the
 library (WOFDM_LIB=... selects one) or two versions of the Python layer above it: run the tool once per build or tree and diff
 the outputs line for line.  It uses the package's public names and the case modules of tests/, so against a tree or a library
 that lacks the youngest entry point run THAT tree's own copy of this tool: the earlier entries' lines are made the same way by both
@@ -27,6 +27,9 @@ of W, W = 4 at N = 1024, the fold with and without an Rx tail and both noise ord
   rx_profile_ldpc     the same cases, points, receivers and interleaver with the three LDPC codes of tests/
                       test_gpu_rx_profile_ldpc.py: the tracking fields, info_err, cw_err, unconverged, iterations, info_bits,
                       codewords, sym_rot and the exported soft bits (the chunk shape without them)
+  rx_profile_coset    the same cases, points, receivers and interleaver with the three Viterbi rates and the three LDPC codes of tests/
+                      test_gpu_rx_profile_coset.py: the tracking fields, both families' counters, info bits and codewords, sym_rot
+                      and the exported soft bits (the chunk shape without them)
   tx_papr             tests/papr_cases.py: every N, system and variant; hist, max_papr and periods (--route gpu only: the
                       oracle is its only mirror, and the tests hold it against that)
 and for each entry point the chunk-straddling shape of its test file (N = 1024, S = 16, cp + cs = 64, four chunks and a bit;
@@ -67,6 +70,7 @@ import rx_profile_cases as RC  # noqa: E402
 import test_gpu_rx_profile_aci as TA  # noqa: E402
 import test_gpu_rx_profile_coded as TC  # noqa: E402
 import test_gpu_rx_profile_coded_frame as TCF  # noqa: E402
+import test_gpu_rx_profile_coset as TCS  # noqa: E402
 import test_gpu_rx_profile_doppler as TD  # noqa: E402
 import test_gpu_rx_profile_ldpc as TLD  # noqa: E402
 import test_gpu_rx_profile_link as TL  # noqa: E402
@@ -148,6 +152,19 @@ def host_ldpc(c, seed, frame_offset, frames):
                                   R.LLR_SCALE, c["perm"], TLD.CODES, with_near=True, **TT.sides(c, seed, frame_offset, frames))
 
 
+def gpu_coset(c, seed, frame_offset, frames, **kw):
+    if "scales" in kw:                                                 # (the chunk shape: its own comb, points, scales and codes)
+        return W.rx_profile_coset_gpu(c["st"], c["k"], c["S"], c["w_tx"], c["w_rx"], c["h"], c["snr"], seed, frame_offset, frames,
+                                      c["points"], c["tracking"], c["pilots"], kw["scales"], R.LLR_SCALE, c["perm"], kw["codes"],
+                                      kw["ldpc_codes"], active=c["active"])
+    return TCS.run_gpu(c, seed, frame_offset, frames, export=True)
+
+
+def host_coset(c, seed, frame_offset, frames):
+    return R.rx_profile_coset_host(*TT.head(c, seed, frame_offset, frames), c["points"], c["tracking"], c["pilots"], TC.SCALES,
+                                   R.LLR_SCALE, c["perm"], TCS.RATES, TCS.CODES, with_near=True, **TT.sides(c, seed, frame_offset, frames))
+
+
 def papr_digests(c, seed, frame_offset, frames, periods_at=None):
     """hist, max_papr and periods of one wofdm_tx_papr call; periods_at: (frame_offset, frames) of a second call the periods
     come from, where the first has too many to ask for"""
@@ -172,6 +189,7 @@ ROUTES = {
     "rx_profile_coded": (gpu_coded, host_coded),
     "rx_profile_coded_frame": (gpu_coded_frame, host_coded_frame),
     "rx_profile_ldpc": (gpu_ldpc, host_ldpc),
+    "rx_profile_coset": (gpu_coset, host_coset),
 }
 
 
@@ -217,6 +235,8 @@ def small_cases():
         yield "rx_profile_coded_frame", name, TC.case(name), TC.seed_of(name), {}
     for name in TT.CASES:
         yield "rx_profile_ldpc", name, TC.case(name), TC.seed_of(name), {}
+    for name in TT.CASES:
+        yield "rx_profile_coset", name, TC.case(name), TC.seed_of(name), {}
 
 
 def papr_cases():
@@ -232,7 +252,7 @@ def papr_cases():
 
 
 def chunk_cases():
-    """(entry, case, frames, extra keywords): the chunk-straddling shape of the twelve test files, N = 1024, S = 16, cp + cs = 64"""
+    """(entry, case, frames, extra keywords): the chunk-straddling shape of the thirteen test files, N = 1024, S = 16, cp + cs = 64"""
     st, S = W.make_structure("wtx", 1024, 56), 16
     big = RC.make_case(st, 4, S, "plain", 3001)
     half = CM.half_band_allocation(1024)
@@ -269,6 +289,9 @@ def chunk_cases():
            dict(scales=(0.5,), codes=(0, 2)))
     yield ("rx_profile_ldpc", cc, frames_of(R.rx_profile_ldpc_chunk_frames(st, S, False, 2, False, 1)),
            dict(scales=(0.5,), codes=((4, 8, 6), (4, 16, 10))))
+    yield ("rx_profile_coset", cc,
+           frames_of(R.rx_profile_coset_chunk_frames(st, 4, S, False, 2, False, 1, int((half & ~ct["pilots"]).sum()), (0, 2), True)),
+           dict(scales=(0.5,), codes=(0, 2), ldpc_codes=((4, 8, 6), (4, 16, 10))))
 
 
 def runs(route):

@@ -47,6 +47,8 @@ CODE_MAX_STEPS = 4608
 CODE_LONG_MAX_STEPS = 1048576
 #: wofdm_ldpc_decode, wofdm_rx_profile_ldpc (include/wofdm.h): most positions of a codeword
 LDPC_MAX_BITS = 16384
+#: wofdm_coset_info, wofdm_rx_profile_coset (csrc/wofdm_link.h): the Philox stream of the information words
+STREAM_INFO = 4
 
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
@@ -64,6 +66,7 @@ EXPORTS = (
     "wofdm_rx_profile_coded", "wofdm_code_steps", "wofdm_viterbi_decode",
     "wofdm_viterbi_decode_long", "wofdm_rx_profile_coded_frame",
     "wofdm_ldpc_lift", "wofdm_ldpc_decode", "wofdm_rx_profile_ldpc",
+    "wofdm_coset_info", "wofdm_conv_encode", "wofdm_ldpc_encode", "wofdm_rx_profile_coset",
 )
 
 
@@ -241,6 +244,12 @@ def load():
     L.wofdm_rx_profile_ldpc.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
                                         C.POINTER(LinkPoint), i32, vp, vp, C.POINTER(TrackingPoint), C.c_float, vp, i32,
                                         C.POINTER(LdpcCode), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.wofdm_coset_info.argtypes = [u64, C.c_uint32, u64, i32, vp]
+    L.wofdm_conv_encode.argtypes = [C.c_int, i32, i32, i32, vp, vp]
+    L.wofdm_ldpc_encode.argtypes = [C.c_int, i32, i32, i32, i32, vp, vp]
+    L.wofdm_rx_profile_coset.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
+                                         C.POINTER(LinkPoint), i32, vp, vp, C.POINTER(TrackingPoint), C.c_float, vp, i32,
+                                         C.POINTER(Code), i32, C.POINTER(LdpcCode), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_tx_psd_batch_pa.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, C.POINTER(PaPoint), vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L

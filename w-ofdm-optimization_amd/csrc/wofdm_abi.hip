@@ -1696,6 +1696,12 @@ struct rx_call {
     // the LDPC code of wofdm_rx_profile_ldpc: code and frm are on with it (codes, code_errs and frame_errs null) and give the soft
     // bits, the frame interleaver and n_codes; the codes and the counters
     struct { bool on; const wofdm_ldpc_code *codes; uint64_t *ldpc_errs; } ldpc;
+    // the coset view of wofdm_rx_profile_coset: code is on with it (codes, code_errs null, n_codes 0) and gives the soft bits and the
+    // interleaver within a symbol; frm and ldpc stay off -- both families' codes, the rotation and the counters are here
+    struct {
+        bool on; int32_t n_codes; const wofdm_code *codes; int32_t n_ldpc; const wofdm_ldpc_code *ldpc_codes; int32_t sym_rot;
+        uint64_t *frame_errs, *ldpc_errs;
+    } coset;
 };
 
 // the receive side's geometry beside the Tx chain's, and the cells of the call
@@ -2034,11 +2040,12 @@ int prep_code(rx_run &r)
     if (!cd.on) return WOFDM_OK;
     const bool frame = r.c.frm.on;                                     // (its counters and lengths: prep_frame)
     const bool ldpc = r.c.ldpc.on;                                     // (its codes are checked behind the frame's: prep_frame)
-    if (ldpc ? !r.c.ldpc.codes : (!cd.codes || (!frame && !cd.code_errs)))
+    const bool coset = r.c.coset.on;                                   // (its counts and codes come behind perm: prep_coset)
+    if (!coset && (ldpc ? !r.c.ldpc.codes : (!cd.codes || (!frame && !cd.code_errs))))
         return fail(WOFDM_E_INVALID, "NULL argument (codes or code_errs)");
     if (!std::isfinite(cd.llr_scale) || !(cd.llr_scale > 0.f)) return fail(WOFDM_E_INVALID, "llr_scale must be finite and positive");
-    if (cd.n_codes < 1) return fail(WOFDM_E_INVALID, "n_codes=%d must be >= 1", cd.n_codes);
-    if (cd.n_codes > WOFDM_CODE_MAX) return fail(WOFDM_E_UNSUPPORTED, "n_codes=%d exceeds %d", cd.n_codes, WOFDM_CODE_MAX);
+    if (!coset && cd.n_codes < 1) return fail(WOFDM_E_INVALID, "n_codes=%d must be >= 1", cd.n_codes);
+    if (!coset && cd.n_codes > WOFDM_CODE_MAX) return fail(WOFDM_E_UNSUPPORTED, "n_codes=%d exceeds %d", cd.n_codes, WOFDM_CODE_MAX);
     const int N = r.g.N, k = r.g.k;
     std::vector<int32_t> bins;
     for (int n = 0; n < N; ++n)
@@ -2084,24 +2091,27 @@ bool ldpc_ranges_ok(int32_t J, int32_t L) { return J >= 3 && J <= 6 && L > J && 
 
 // the LDPC codes of wofdm_rx_profile_ldpc, behind prep_frame's sym_rot and ldpc_errs, code by code in the order include/wofdm.h
 // documents: a frame of n_f positions carries W = ceil(n_f / WOFDM_LDPC_MAX_BITS) words of n = floor(n_f / W) positions
-int prep_ldpc(rx_run &r)
+// (the coset view's codes likewise, behind prep_coset's; its decoder keeps the transmitted word in LDS as well)
+int prep_ldpc(rx_run &r, const wofdm_ldpc_code *codes, int32_t n_codes, bool coset)
 {
     for (int v = 0; v < 2; ++v) {
         r.lW[v] = r.fnc[v] > 0 ? (r.fnc[v] + WOFDM_LDPC_MAX_BITS - 1) / WOFDM_LDPC_MAX_BITS : 0;
         r.ln[v] = r.lW[v] > 0 ? r.fnc[v] / r.lW[v] : 0;
     }
-    for (int i = 0; i < r.c.code.n_codes; ++i) {
-        const wofdm_ldpc_code &q = r.c.ldpc.codes[i];
-        if (q.J < 3 || q.J > 6) return fail(WOFDM_E_INVALID, "codes[%d].J=%d must be 3 ... 6", i, q.J);
-        if (q.L <= q.J || q.L > 24) return fail(WOFDM_E_INVALID, "codes[%d].L=%d must be J + 1 ... 24", i, q.L);
-        if (q.max_iter < 1 || q.max_iter > 64) return fail(WOFDM_E_INVALID, "codes[%d].max_iter=%d must be 1 ... 64", i, q.max_iter);
-        if (q.reserved != 0) return fail(WOFDM_E_INVALID, "codes[%d].reserved must be 0", i);
+    for (int i = 0; i < n_codes; ++i) {
+        const wofdm_ldpc_code &q = codes[i];
+        const char *name = coset ? "ldpc_codes" : "codes";
+        if (q.J < 3 || q.J > 6) return fail(WOFDM_E_INVALID, "%s[%d].J=%d must be 3 ... 6", name, i, q.J);
+        if (q.L <= q.J || q.L > 24) return fail(WOFDM_E_INVALID, "%s[%d].L=%d must be J + 1 ... 24", name, i, q.L);
+        if (q.max_iter < 1 || q.max_iter > 64) return fail(WOFDM_E_INVALID, "%s[%d].max_iter=%d must be 1 ... 64", name, i, q.max_iter);
+        if (q.reserved != 0) return fail(WOFDM_E_INVALID, "%s[%d].reserved must be 0", name, i);
         for (int v = 0; v < 2; ++v) {
             r.lZ[i][v] = r.lW[v] > 0 ? ldpc_lift(q.J, q.L, r.ln[v]) : 0;
             if (r.lW[v] > 0 && (int64_t)(q.L - q.J) * r.lZ[i][v] - ((int64_t)q.L * r.lZ[i][v] - r.ln[v]) < 1)
-                return fail(WOFDM_E_INVALID, "codes[%d]: (%d, %d) over %d positions has no information bit", i, q.J, q.L, r.ln[v]);
-            if (r.lW[v] > 0 && wofdm_ldpc_lds(q.J, q.L, r.lZ[i][v]) > WOFDM_LDPC_LDS_MAX)
-                return fail(WOFDM_E_UNSUPPORTED, "codes[%d]: the decoder's LDS exceeds %d bytes", i, WOFDM_LDPC_LDS_MAX);
+                return fail(WOFDM_E_INVALID, "%s[%d]: (%d, %d) over %d positions has no information bit", name, i, q.J, q.L, r.ln[v]);
+            if (r.lW[v] > 0 &&
+                (coset ? wofdm_ldpc_coset_lds(q.J, q.L, r.lZ[i][v]) : wofdm_ldpc_lds(q.J, q.L, r.lZ[i][v])) > WOFDM_LDPC_LDS_MAX)
+                return fail(WOFDM_E_UNSUPPORTED, "%s[%d]: the decoder's LDS exceeds %d bytes", name, i, WOFDM_LDPC_LDS_MAX);
         }
     }
     return WOFDM_OK;
@@ -2109,6 +2119,49 @@ int prep_ldpc(rx_run &r)
 
 // wofdm_viterbi_decode_long and the frame-spanning code: the history is 512 bytes per block of 64 steps
 int32_t hist_blocks_of(int32_t steps) { return (steps + 63) / 64; }
+
+// the variants a call's points use and their coded-stream lengths
+void frame_lengths(rx_run &r)
+{
+    const int32_t n_c = (int32_t)r.gather.size(), S = r.g.S;
+    r.fuse[0] = r.fuse[1] = false;
+    for (int i = 0; i < r.c.n_points; ++i) r.fuse[r.tp[(size_t)i].post ? 1 : 0] = true;
+    r.hist_blocks = 1;
+    for (int v = 0; v < 2; ++v) {
+        const int64_t s_d = S - 1 - v;
+        r.fnc[v] = r.fuse[v] && s_d >= 1 ? (int32_t)((int64_t)n_c * s_d) : 0;       // (n_c <= 6 * 1024, S <= 64)
+    }
+}
+// the Viterbi codes' steps per variant, and the history's blocks
+int frame_steps(rx_run &r, const wofdm_code *codes, int32_t n_codes)
+{
+    for (int pass = 0; pass < 2; ++pass)                                 // (every T < 7 before any T beyond the limit)
+        for (int i = 0; i < n_codes; ++i)
+            for (int v = 0; v < 2; ++v) {
+                const int32_t T = r.fnc[v] > 0 ? code_steps(codes[i].rate, r.fnc[v]) : 0;
+                r.fsteps[i][v] = T;
+                if (r.fnc[v] == 0) continue;
+                if (pass == 0 && T < 7)
+                    return fail(WOFDM_E_INVALID, "codes[%d]: %d coded bits per frame give %d steps, at least 7 are needed", i, r.fnc[v], T);
+                if (pass == 1 && T > WOFDM_CODE_LONG_MAX_STEPS)
+                    return fail(WOFDM_E_UNSUPPORTED, "codes[%d]: %d steps, more than %d", i, T, WOFDM_CODE_LONG_MAX_STEPS);
+                r.hist_blocks = std::max(r.hist_blocks, hist_blocks_of(T));
+            }
+    return WOFDM_OK;
+}
+// the frame's gather tables per variant
+void frame_gathers(rx_run &r, int32_t sym_rot)
+{
+    const int32_t n_c = (int32_t)r.gather.size(), S = r.g.S, N = r.g.N;
+    for (int v = 0; v < 2; ++v) {
+        const int32_t s_d = S - 1 - v;
+        r.fgather[v].resize((size_t)r.fnc[v]);
+        for (int32_t c = 0; c < r.fnc[v]; ++c) {
+            const int32_t j = c % s_d, q = c / s_d;
+            r.fgather[v][(size_t)c] = 8 * N * j + r.gather[(size_t)(((int64_t)q + (int64_t)j * sym_rot) % n_c)];
+        }
+    }
+}
 
 // the frame-spanning code, in the order include/wofdm.h documents, behind prep_code (which leaves the gather table of one symbol);
 // leaves per variant the gather table of the frame: coded-stream index c sits in data symbol 1 + j, j = c mod S_d, at the
@@ -2118,38 +2171,43 @@ int prep_frame(rx_run &r)
 {
     const auto &fm = r.c.frm;
     if (!fm.on) return WOFDM_OK;
-    const int32_t n_c = (int32_t)r.gather.size(), S = r.g.S, N = r.g.N;
+    const int32_t n_c = (int32_t)r.gather.size();
     if (fm.sym_rot < 0 || fm.sym_rot >= n_c) return fail(WOFDM_E_INVALID, "sym_rot=%d outside [0, %d)", fm.sym_rot, n_c);
     const bool ldpc = r.c.ldpc.on;
     if (ldpc ? !r.c.ldpc.ldpc_errs : !fm.frame_errs) return fail(WOFDM_E_INVALID, "NULL argument (%s)", ldpc ? "ldpc_errs" : "frame_errs");
-    r.fuse[0] = r.fuse[1] = false;
-    for (int i = 0; i < r.c.n_points; ++i) r.fuse[r.tp[(size_t)i].post ? 1 : 0] = true;
-    r.hist_blocks = 1;
-    for (int v = 0; v < 2; ++v) {
-        const int64_t s_d = S - 1 - v;
-        r.fnc[v] = r.fuse[v] && s_d >= 1 ? (int32_t)((int64_t)n_c * s_d) : 0;       // (n_c <= 6 * 1024, S <= 64)
+    frame_lengths(r);
+    const int rc = ldpc ? WOFDM_OK : frame_steps(r, r.c.code.codes, r.c.code.n_codes);
+    if (rc != WOFDM_OK) return rc;
+    frame_gathers(r, fm.sym_rot);
+    return ldpc ? prep_ldpc(r, r.c.ldpc.codes, r.c.code.n_codes, false) : WOFDM_OK;
+}
+
+// the coset view (wofdm_rx_profile_coset), behind prep_code's llr_scale, perm and soft_bits, in the order include/wofdm.h
+// documents: the counts, the code arrays, sym_rot, the counters, the Viterbi codes as wofdm_rx_profile_coded_frame checks them,
+// the LDPC codes as wofdm_rx_profile_ldpc does
+int prep_coset(rx_run &r)
+{
+    const auto &cs = r.c.coset;
+    if (!cs.on) return WOFDM_OK;
+    if (cs.n_codes < 0 || cs.n_ldpc < 0) return fail(WOFDM_E_INVALID, "n_codes=%d and n_ldpc=%d must be >= 0", cs.n_codes, cs.n_ldpc);
+    if (cs.n_codes > WOFDM_CODE_MAX || cs.n_ldpc > WOFDM_CODE_MAX)
+        return fail(WOFDM_E_UNSUPPORTED, "n_codes=%d or n_ldpc=%d exceeds %d", cs.n_codes, cs.n_ldpc, WOFDM_CODE_MAX);
+    if (cs.n_codes + cs.n_ldpc < 1) return fail(WOFDM_E_INVALID, "n_codes + n_ldpc must be >= 1");
+    if ((cs.n_codes > 0 && !cs.codes) || (cs.n_ldpc > 0 && !cs.ldpc_codes)) return fail(WOFDM_E_INVALID, "NULL argument (codes or ldpc_codes)");
+    const int32_t n_c = (int32_t)r.gather.size();
+    if (cs.sym_rot < 0 || cs.sym_rot >= n_c) return fail(WOFDM_E_INVALID, "sym_rot=%d outside [0, %d)", cs.sym_rot, n_c);
+    if ((cs.n_codes > 0 && !cs.frame_errs) || (cs.n_ldpc > 0 && !cs.ldpc_errs))
+        return fail(WOFDM_E_INVALID, "NULL argument (frame_errs or ldpc_errs)");
+    for (int i = 0; i < cs.n_codes; ++i) {
+        const wofdm_code &q = cs.codes[i];
+        if (q.rate < 0 || q.rate > 2) return fail(WOFDM_E_INVALID, "codes[%d].rate=%d must be 0, 1 or 2", i, q.rate);
+        if (q.reserved[0] != 0 || q.reserved[1] != 0 || q.reserved[2] != 0) return fail(WOFDM_E_INVALID, "codes[%d].reserved must be 0", i);
     }
-    for (int pass = 0; !ldpc && pass < 2; ++pass)                        // (every T < 7 before any T beyond the limit)
-        for (int i = 0; i < r.c.code.n_codes; ++i)
-            for (int v = 0; v < 2; ++v) {
-                const int32_t T = r.fnc[v] > 0 ? code_steps(r.c.code.codes[i].rate, r.fnc[v]) : 0;
-                r.fsteps[i][v] = T;
-                if (r.fnc[v] == 0) continue;
-                if (pass == 0 && T < 7)
-                    return fail(WOFDM_E_INVALID, "codes[%d]: %d coded bits per frame give %d steps, at least 7 are needed", i, r.fnc[v], T);
-                if (pass == 1 && T > WOFDM_CODE_LONG_MAX_STEPS)
-                    return fail(WOFDM_E_UNSUPPORTED, "codes[%d]: %d steps, more than %d", i, T, WOFDM_CODE_LONG_MAX_STEPS);
-                r.hist_blocks = std::max(r.hist_blocks, hist_blocks_of(T));
-            }
-    for (int v = 0; v < 2; ++v) {
-        const int32_t s_d = S - 1 - v;
-        r.fgather[v].resize((size_t)r.fnc[v]);
-        for (int32_t c = 0; c < r.fnc[v]; ++c) {
-            const int32_t j = c % s_d, q = c / s_d;
-            r.fgather[v][(size_t)c] = 8 * N * j + r.gather[(size_t)(((int64_t)q + (int64_t)j * fm.sym_rot) % n_c)];
-        }
-    }
-    return ldpc ? prep_ldpc(r) : WOFDM_OK;
+    frame_lengths(r);
+    const int rc = frame_steps(r, cs.codes, cs.n_codes);
+    if (rc != WOFDM_OK) return rc;
+    frame_gathers(r, cs.sym_rot);
+    return prep_ldpc(r, cs.ldpc_codes, cs.n_ldpc, true);
 }
 
 // The taps as the kernels read them.  Of moving channels the knots, [n_tracks][n_channels][n_knots][WOFDM_LT], zero padded, and
@@ -2192,7 +2250,7 @@ uint64_t rx_job_bytes(const rx_run &r)
     // the frame-spanning code: 512 bytes of survivor history per point and block of 64 steps of the longest codeword, which the
     // codes' launches share
     return 8 * words + (c.soft.on ? 4 * NP * (uint64_t)c.soft.n_scales * ((S - 1) * N + S) : 0) + (c.code.on ? 8 * NP * (S - 1) * N : 0) +
-           (c.frm.on && !c.ldpc.on ? 512 * NP * (uint64_t)r.hist_blocks : 0);
+           ((c.frm.on && !c.ldpc.on) || (c.coset.on && c.coset.n_codes > 0) ? 512 * NP * (uint64_t)r.hist_blocks : 0);
 }
 
 // ---- the stages' device side: allocation, upload, and the stage's parameters in the chunk ----
@@ -2331,7 +2389,7 @@ int stage_code(rx_run &r)
     if (!cd.on) return WOFDM_OK;
     const rx_geom &g = r.g;
     // (the frame-spanning code has counters and gather tables of its own: stage_frame)
-    const bool sym = !r.c.frm.on;
+    const bool sym = !r.c.frm.on && !r.c.coset.on;
     if (!r.d_sbits.alloc(r.chunk * (size_t)r.c.n_points * (g.S - 1) * g.N * 8) || !r.d_gather.alloc(r.gather.size()) ||
         (sym && !r.d_cerrs.alloc(r.n_cerr)))
         return fail(WOFDM_E_NOMEM, "device allocation failed (coded link)");
@@ -2348,15 +2406,24 @@ int stage_code(rx_run &r)
     return WOFDM_OK;
 }
 
-// the LDPC code's side (behind stage_code, in stage_frame's place): the frame's gather tables in use, the counters
-int stage_ldpc(rx_run &r)
+// the frame's gather tables in use, on the device
+int stage_fgather(rx_run &r, const char *what)
+{
+    for (int v = 0; v < 2; ++v) {
+        if (r.fnc[v] == 0) continue;
+        if (!r.d_fgather[v].alloc(r.fgather[v].size())) return fail(WOFDM_E_NOMEM, "device allocation failed (%s)", what);
+        if (!r.d_fgather[v].upload(r.fgather[v].data(), r.fgather[v].size())) return fail(WOFDM_E_HIP, "upload failed");
+    }
+    return WOFDM_OK;
+}
+
+// the LDPC codes' side: the words per variant, the counters, the codes and their lifts
+int stage_ldpc_codes(rx_run &r, const wofdm_ldpc_code *codes, int32_t n_codes)
 {
     wofdm_ldpcparams &k = r.ck.ld;
     k = wofdm_ldpcparams{};
     for (int v = 0; v < 2; ++v) {
         if (r.fnc[v] == 0) continue;
-        if (!r.d_fgather[v].alloc(r.fgather[v].size())) return fail(WOFDM_E_NOMEM, "device allocation failed (LDPC code)");
-        if (!r.d_fgather[v].upload(r.fgather[v].data(), r.fgather[v].size())) return fail(WOFDM_E_HIP, "upload failed");
         k.gather[v] = r.d_fgather[v];
         k.n[v] = r.ln[v];
         k.W[v] = r.lW[v];
@@ -2364,26 +2431,21 @@ int stage_ldpc(rx_run &r)
     if (!r.d_lerrs.alloc(r.n_lerr)) return fail(WOFDM_E_NOMEM, "device allocation failed (LDPC code)");
     if (hipMemset(r.d_lerrs, 0, r.n_lerr * 8) != hipSuccess) return fail(WOFDM_E_HIP, "upload failed");
     k.errs = r.d_lerrs;
-    for (int i = 0; i < r.c.code.n_codes; ++i) {
-        const wofdm_ldpc_code &q = r.c.ldpc.codes[i];
+    for (int i = 0; i < n_codes; ++i) {
+        const wofdm_ldpc_code &q = codes[i];
         r.ck.ld_code[i][0] = q.J; r.ck.ld_code[i][1] = q.L; r.ck.ld_code[i][2] = q.max_iter;
         r.ck.ld_Z[i][0] = r.lZ[i][0]; r.ck.ld_Z[i][1] = r.lZ[i][1];
     }
-    r.ck.ldpc_on = true;
     return WOFDM_OK;
 }
 
-// the frame-spanning code's side (behind stage_code): the gather tables in use, the chunk's history, the counters
-int stage_frame(rx_run &r)
+// the Viterbi codes' side: the codeword lengths per variant, the chunk's history, the counters, the codes' steps
+int stage_frame_codes(rx_run &r, int32_t n_codes)
 {
-    if (!r.c.frm.on) return WOFDM_OK;
-    if (r.c.ldpc.on) return stage_ldpc(r);
     wofdm_longparams &k = r.ck.fr;
     k = wofdm_longparams{};
     for (int v = 0; v < 2; ++v) {
         if (r.fnc[v] == 0) continue;
-        if (!r.d_fgather[v].alloc(r.fgather[v].size())) return fail(WOFDM_E_NOMEM, "device allocation failed (frame code)");
-        if (!r.d_fgather[v].upload(r.fgather[v].data(), r.fgather[v].size())) return fail(WOFDM_E_HIP, "upload failed");
         k.gather[v] = r.d_fgather[v];
         k.n_c[v] = r.fnc[v];
     }
@@ -2391,9 +2453,36 @@ int stage_frame(rx_run &r)
         return fail(WOFDM_E_NOMEM, "device allocation failed (frame code)");
     if (hipMemset(r.d_ferrs, 0, r.n_ferr * 8) != hipSuccess) return fail(WOFDM_E_HIP, "upload failed");
     k.hist = r.d_hist; k.hist_blocks = r.hist_blocks; k.errs = r.d_ferrs;
-    for (int i = 0; i < r.c.code.n_codes; ++i)
+    for (int i = 0; i < n_codes; ++i)
         for (int v = 0; v < 2; ++v) r.ck.fr_steps[i][v] = r.fsteps[i][v];
-    r.ck.frame_on = true;
+    return WOFDM_OK;
+}
+
+// the frame-spanning code's side (behind stage_code), or in its place the LDPC code's
+int stage_frame(rx_run &r)
+{
+    if (!r.c.frm.on) return WOFDM_OK;
+    const bool ldpc = r.c.ldpc.on;
+    int rc = stage_fgather(r, ldpc ? "LDPC code" : "frame code");
+    if (rc == WOFDM_OK) rc = ldpc ? stage_ldpc_codes(r, r.c.ldpc.codes, r.c.code.n_codes) : stage_frame_codes(r, r.c.code.n_codes);
+    if (rc != WOFDM_OK) return rc;
+    (ldpc ? r.ck.ldpc_on : r.ck.frame_on) = true;
+    return WOFDM_OK;
+}
+
+// the coset view's side (behind stage_code): both families over the same gather tables, the rates, the stream's key
+int stage_coset(rx_run &r)
+{
+    const auto &cs = r.c.coset;
+    if (!cs.on) return WOFDM_OK;
+    int rc = stage_fgather(r, "coset view");
+    if (rc == WOFDM_OK && cs.n_codes > 0) rc = stage_frame_codes(r, cs.n_codes);
+    if (rc == WOFDM_OK && cs.n_ldpc > 0) rc = stage_ldpc_codes(r, cs.ldpc_codes, cs.n_ldpc);
+    if (rc != WOFDM_OK) return rc;
+    for (int i = 0; i < cs.n_codes; ++i) r.ck.cd.rate[i] = cs.codes[i].rate;
+    r.ck.cs_nv = cs.n_codes; r.ck.cs_nl = cs.n_ldpc;
+    r.ck.cs = {(uint32_t)r.c.cfg->seed, (uint32_t)(r.c.cfg->seed >> 32), r.c.cfg->frame_offset};
+    r.ck.coset_on = true;
     return WOFDM_OK;
 }
 
@@ -2440,7 +2529,8 @@ int rx_profile_run(const rx_call &c)
         (rc = check_allocation(c.active, r.g.N, &r.act)) != WOFDM_OK || (rc = prep_nb(r)) != WOFDM_OK ||
         (rc = prep_sync(r)) != WOFDM_OK || (rc = prep_pn(r)) != WOFDM_OK || (rc = check_knots(r)) != WOFDM_OK ||
         (rc = prep_link(r)) != WOFDM_OK || (rc = prep_amp(r)) != WOFDM_OK || (rc = prep_track(r)) != WOFDM_OK ||
-        (rc = prep_code(r)) != WOFDM_OK || (rc = prep_frame(r)) != WOFDM_OK || (rc = use_device(c.device)) != WOFDM_OK)
+        (rc = prep_code(r)) != WOFDM_OK || (rc = prep_frame(r)) != WOFDM_OK || (rc = prep_coset(r)) != WOFDM_OK ||
+        (rc = use_device(c.device)) != WOFDM_OK)
         return rc;
     g_rxprof_ms = 0.f;
     const rx_geom &g = r.g;
@@ -2458,10 +2548,14 @@ int rx_profile_run(const rx_call &c)
     r.n_ferr = c.frm.on && !c.ldpc.on ? NP * g.cells * (size_t)c.code.n_codes * 2 : 0;
     r.n_lerr = c.ldpc.on ? NP * g.cells * (size_t)c.code.n_codes * 4 : 0;
     if (c.frm.on) r.n_cerr = 0;
+    if (c.coset.on) {
+        r.n_ferr = NP * g.cells * (size_t)c.coset.n_codes * 2;
+        r.n_lerr = NP * g.cells * (size_t)c.coset.n_ldpc * 4;
+    }
     if ((rc = stage_base(r)) != WOFDM_OK || (rc = stage_points(r)) != WOFDM_OK || (rc = stage_amp(r)) != WOFDM_OK ||
         (rc = stage_pn(r)) != WOFDM_OK || (rc = stage_link(r)) != WOFDM_OK || (rc = stage_soft(r)) != WOFDM_OK ||
         (rc = stage_track(r)) != WOFDM_OK || (rc = stage_code(r)) != WOFDM_OK || (rc = stage_frame(r)) != WOFDM_OK ||
-        (rc = stage_nb(r)) != WOFDM_OK)
+        (rc = stage_coset(r)) != WOFDM_OK || (rc = stage_nb(r)) != WOFDM_OK)
         return rc;
     // (a neighbour that loads no bin: the plain kernel)
     r.ck.arm = c.arm == RXP_ACI && !r.nb ? RXP_PLAIN : c.arm;
@@ -2498,6 +2592,10 @@ int rx_profile_run(const rx_call &c)
     add_to(c.code.code_errs, hcerr);
     add_to(c.frm.frame_errs, hferr);
     add_to(c.ldpc.ldpc_errs, hlerr);
+    if (c.coset.on) {
+        add_to(c.coset.frame_errs, hferr);
+        add_to(c.coset.ldpc_errs, hlerr);
+    }
     g_rxprof_ms = ms;
     return WOFDM_OK;
 }
@@ -2654,7 +2752,7 @@ static int rx_tracking_call(const wofdm_cfg *cfg, int device, const float *w_tx,
                             const wofdm_tracking_point *tracking, uint64_t *errs, double *err_power, uint64_t *sym_errs,
                             double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty,
                             const decltype(rx_call::code) *code, const decltype(rx_call::frm) *frm = nullptr,
-                            const decltype(rx_call::ldpc) *ldpc = nullptr)
+                            const decltype(rx_call::ldpc) *ldpc = nullptr, const decltype(rx_call::coset) *coset = nullptr)
 {
     if (!scales || !bit_penalty || !tracking) return fail(WOFDM_E_INVALID, "NULL argument (scales, bit_penalty or tracking)");
     if (n_scales < 1) return fail(WOFDM_E_INVALID, "n_scales=%d must be >= 1", n_scales);
@@ -2672,6 +2770,7 @@ static int rx_tracking_call(const wofdm_cfg *cfg, int device, const float *w_tx,
     if (code) c.code = *code;
     if (frm) c.frm = *frm;
     if (ldpc) c.ldpc = *ldpc;
+    if (coset) c.coset = *coset;
     const int rc = rx_link_stages(c, n_points, points);
     return rc != WOFDM_OK ? rc : rx_profile_run(c);
 }
@@ -2733,6 +2832,22 @@ int wofdm_rx_profile_ldpc(const wofdm_cfg *cfg, int device, const float *w_tx, c
     return rx_tracking_call(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active, aci_h,
                             ref_power, n_points, points, n_scales, scales, pilots, tracking, errs, err_power, sym_errs, sym_power,
                             pa_power, bit_penalty, sym_penalty, &code, &frm, &ldpc);
+}
+
+int wofdm_rx_profile_coset(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                           const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                           int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
+                           const wofdm_link_point *points, int32_t n_scales, const float *scales, const uint8_t *pilots,
+                           const wofdm_tracking_point *tracking, float llr_scale, const int32_t *perm, int32_t n_codes,
+                           const wofdm_code *codes, int32_t n_ldpc, const wofdm_ldpc_code *ldpc_codes, int32_t sym_rot, uint64_t *errs,
+                           double *err_power, uint64_t *sym_errs, double *sym_power, double *pa_power, double *bit_penalty,
+                           double *sym_penalty, uint64_t *frame_errs, uint64_t *ldpc_errs, int8_t *soft_bits)
+{
+    const decltype(rx_call::code) code = {true, llr_scale, perm, 0, nullptr, nullptr, soft_bits};
+    const decltype(rx_call::coset) coset = {true, n_codes, codes, n_ldpc, ldpc_codes, sym_rot, frame_errs, ldpc_errs};
+    return rx_tracking_call(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active, aci_h,
+                            ref_power, n_points, points, n_scales, scales, pilots, tracking, errs, err_power, sym_errs, sym_power,
+                            pa_power, bit_penalty, sym_penalty, &code, nullptr, nullptr, &coset);
 }
 
 int wofdm_ldpc_lift(int32_t J, int32_t L, int32_t n)
@@ -2883,6 +2998,83 @@ int wofdm_ldpc_decode(int device, int32_t J, int32_t L, int32_t max_iter, int32_
     std::memcpy(bits, hbits.data(), n_soft);
     if (iters) std::memcpy(iters, hiters.data(), hiters.size() * sizeof(int32_t));
     if (converged) std::memcpy(converged, hconv.data(), hconv.size());
+    return WOFDM_OK;
+}
+
+int wofdm_coset_info(uint64_t seed, uint32_t cell, uint64_t frame, int32_t n_bits, uint8_t *bits)
+{
+    if (!bits) return fail(WOFDM_E_INVALID, "NULL argument (bits)");
+    if (n_bits < 0) return fail(WOFDM_E_INVALID, "n_bits=%d must be >= 0", n_bits);
+    if (cell >= (1u << 28)) return fail(WOFDM_E_INVALID, "cell=%u must be below 2^28", cell);
+    uint32_t word = 0;
+    for (int32_t i = 0; i < n_bits; ++i) {
+        if ((i & 31) == 0) word = wofdm_info_word((uint32_t)seed, (uint32_t)(seed >> 32), cell, frame, (uint32_t)i >> 5);
+        bits[i] = (uint8_t)((word >> (i & 31)) & 1u);
+    }
+    return WOFDM_OK;
+}
+
+int wofdm_conv_encode(int device, int32_t rate, int32_t n_c, int32_t n_cw, const uint8_t *info, uint8_t *coded)
+{
+    if (!info || !coded) return fail(WOFDM_E_INVALID, "NULL argument (info or coded)");
+    if (rate < 0 || rate > 2) return fail(WOFDM_E_INVALID, "rate=%d must be 0, 1 or 2", rate);
+    if (n_c < 1 || n_cw < 1) return fail(WOFDM_E_INVALID, "n_c=%d and n_cw=%d must be >= 1", n_c, n_cw);
+    const int32_t T = code_steps(rate, n_c);
+    if (T < 7) return fail(WOFDM_E_INVALID, "n_c=%d gives %d steps, at least 7 are needed", n_c, T);
+    if (T > WOFDM_CODE_LONG_MAX_STEPS)
+        return fail(WOFDM_E_UNSUPPORTED, "n_c=%d gives %d steps, more than %d", n_c, T, WOFDM_CODE_LONG_MAX_STEPS);
+    int rc = use_device(device);
+    if (rc != WOFDM_OK) return rc;
+    const size_t n_info = (size_t)n_cw * (size_t)(T - 6), n_coded = (size_t)n_cw * (size_t)n_c;
+    dev_buf<uint8_t> d_info, d_coded;
+    // (T = 7 at one codeword: one information bit; the buffers are never empty)
+    if (!d_info.alloc(n_info) || !d_coded.alloc(n_coded)) return fail(WOFDM_E_NOMEM, "device allocation failed (encoder)");
+    if (!d_info.upload(info, n_info)) return fail(WOFDM_E_HIP, "upload failed");
+    wofdm_convencparams ep{};
+    ep.info = d_info; ep.coded = d_coded; ep.rate = rate; ep.n_c = n_c; ep.steps = T; ep.n_cw = (uint32_t)n_cw;
+    std::vector<uint8_t> hcoded(n_coded);
+    hipError_t e;
+    {
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the encoder is in every auxiliary unit)
+        e = ax && ax->conv_encode ? ax->conv_encode(&ep, nullptr) : hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess || !fetch(hcoded, d_coded.p))
+        return fail(WOFDM_E_HIP, "encoder kernel or copy-back failed: %s", hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
+    std::memcpy(coded, hcoded.data(), n_coded);
+    return WOFDM_OK;
+}
+
+int wofdm_ldpc_encode(int device, int32_t J, int32_t L, int32_t n, int32_t n_cw, const uint8_t *info, uint8_t *word)
+{
+    if (!info || !word) return fail(WOFDM_E_INVALID, "NULL argument (info or word)");
+    if (!ldpc_ranges_ok(J, L)) return fail(WOFDM_E_INVALID, "J=%d must be 3 ... 6 and L=%d in J + 1 ... 24", J, L);
+    if (n < 1 || n_cw < 1) return fail(WOFDM_E_INVALID, "n=%d and n_cw=%d must be >= 1", n, n_cw);
+    if (n > WOFDM_LDPC_MAX_BITS) return fail(WOFDM_E_UNSUPPORTED, "n=%d exceeds %d", n, WOFDM_LDPC_MAX_BITS);
+    const int32_t Z = ldpc_lift(J, L, n);
+    if ((int64_t)(L - J) * Z - ((int64_t)L * Z - n) < 1)
+        return fail(WOFDM_E_INVALID, "(%d, %d) over %d positions has no information bit", J, L, n);
+    if (wofdm_ldpc_lds(J, L, Z) > WOFDM_LDPC_LDS_MAX) return fail(WOFDM_E_UNSUPPORTED, "the decoder's LDS exceeds %d bytes", WOFDM_LDPC_LDS_MAX);
+    int rc = use_device(device);
+    if (rc != WOFDM_OK) return rc;
+    const size_t n_info = (size_t)n_cw * (size_t)(n - J * Z), n_word = (size_t)n_cw * (size_t)n;
+    dev_buf<uint8_t> d_info, d_word;
+    if (!d_info.alloc(n_info) || !d_word.alloc(n_word)) return fail(WOFDM_E_NOMEM, "device allocation failed (encoder)");
+    if (!d_info.upload(info, n_info)) return fail(WOFDM_E_HIP, "upload failed");
+    wofdm_ldpcencparams ep{};
+    ep.info = d_info; ep.word = d_word; ep.J = J; ep.L = L; ep.n = n; ep.Z = Z; ep.n_cw = (uint32_t)n_cw;
+    std::vector<uint8_t> hword(n_word);
+    hipError_t e;
+    {
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the encoder is in every auxiliary unit)
+        e = ax && ax->ldpc_encode ? ax->ldpc_encode(&ep, nullptr) : hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess || !fetch(hword, d_word.p))
+        return fail(WOFDM_E_HIP, "encoder kernel or copy-back failed: %s", hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
+    std::memcpy(word, hword.data(), n_word);
     return WOFDM_OK;
 }
 

@@ -2295,6 +2295,366 @@ __global__ void __launch_bounds__(256) wofdm_ldpc_kernel(const wofdm_ldpcparams 
     }
 }
 
+// ---- the encoders, alone (wofdm_conv_encode, wofdm_ldpc_encode) and inside the coset instantiations of the two decoders ----
+
+// The coded-stream indices of step t's kept outputs, A before B, -1 where the pattern keeps nothing (vlong_offsets' closed form)
+__device__ __forceinline__ void conv_kept(int rate, int t, int &ca, int &cb)
+{
+    if (rate == 0) {
+        ca = 2 * t;
+        cb = 2 * t + 1;
+    } else if (rate == 1) {
+        const int q = t >> 1, ph = t & 1;
+        ca = 3 * q + 2 * ph;
+        cb = ph == 0 ? 3 * q + 1 : -1;
+    } else {
+        const int q = t / 3, ph = t - 3 * q;
+        ca = ph == 2 ? -1 : 4 * q + 2 * ph;
+        cb = ph == 1 ? -1 : 4 * q + (ph == 0 ? 1 : 3);
+    }
+}
+// A | B << 1 of step t from r = (u_t << 6) | state, whose bit j is u_(t - 6 + j): each a parity of seven information bits
+__device__ __forceinline__ uint32_t conv_ab(uint32_t r)
+{
+    return (uint32_t)(__popc(r & 0133u) & 1) | ((uint32_t)(__popc(r & 0171u) & 1) << 1);
+}
+
+// The K = 7 encoder of include/wofdm.h (wofdm_convencparams): one step per lane, grid (n_cw, ceil(T / 256)).  Lane t gathers u_(t
+// - 6) ... u_t -- zero before the word and on the six tail steps --, forms A and B and stores them at their closed-form
+// positions; the last step's lane also clears the positions behind the kept outputs.
+__global__ void __launch_bounds__(256) wofdm_conv_encode_kernel(const wofdm_convencparams ep)
+{
+    const int t = (int)(blockIdx.y * 256u + threadIdx.x), T = ep.steps, K = T - 6, n_c = ep.n_c;
+    if (t >= T) return;
+    const uint8_t *__restrict__ info = ep.info + (uint64_t)blockIdx.x * (uint64_t)K;
+    uint8_t *__restrict__ out = ep.coded + (uint64_t)blockIdx.x * (uint64_t)n_c;
+    uint32_t r = 0u;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const int i = t - 6 + j;
+        r |= (i >= 0 && i < K ? (uint32_t)info[i] & 1u : 0u) << j;
+    }
+    int ca, cb;
+    conv_kept(ep.rate, t, ca, cb);
+    const uint32_t ab = conv_ab(r);
+    if (ca >= 0 && ca < n_c) out[ca] = (uint8_t)(ab & 1u);
+    if (cb >= 0 && cb < n_c) out[cb] = (uint8_t)(ab >> 1);
+    if (t == T - 1)
+        for (int c = max(ca, cb) + 1; c < n_c; ++c) out[c] = 0;
+}
+
+// s(i, j) = (i 2^j) mod Z into sh [J L], as wofdm_ldpc_kernel forms them
+__device__ __forceinline__ void ldpc_shifts(int16_t *__restrict__ sh, int J, int L, int Z, int tid, int nt)
+{
+    for (int x = tid; x < J * L; x += nt) {
+        const int i = x / L, j = x - i * L;
+        int p = 1 % Z;
+        for (int q = 0; q < j; ++q) {
+            p += p;
+            p = p >= Z ? p - Z : p;
+        }
+        sh[x] = (int16_t)((i * p) % Z);
+    }
+}
+// a codeword as bits in LDS: variable v is bit v mod 32 of word v div 32
+__device__ __forceinline__ uint32_t ldpc_bit(const uint32_t *xb, int v) { return (xb[v >> 5] >> (v & 31)) & 1u; }
+
+// The encoder of include/wofdm.h on a word held as bits in LDS: back-substitution from block row J - 1 up to 0 -- check r of row
+// i XORs x[j Z + (r + s(i, j)) mod Z] over j > i into variable i Z + (r + s(i, i)) mod Z.  A row reads block columns above its
+// own and writes its own: its Z checks are independent, strided over the threads, and an LDS atomic OR sets the bit (neighbours
+// share a word).  Entered behind a barrier that left sh, the information bits and zeros everywhere else; one barrier per row.
+__device__ __forceinline__ void ldpc_encode_lds(uint32_t *xb, const int16_t *__restrict__ sh, int J, int L, int Z, int tid, int nt)
+{
+    for (int i = J - 1; i >= 0; --i) {
+        const int16_t *__restrict__ si = sh + i * L;
+        for (int r = tid; r < Z; r += nt) {
+            uint32_t par = 0u;
+            for (int j = i + 1; j < L; ++j) {
+                int c = r + si[j];
+                c = c >= Z ? c - Z : c;
+                par ^= ldpc_bit(xb, j * Z + c);
+            }
+            int c = r + si[i];
+            c = c >= Z ? c - Z : c;
+            const int v = i * Z + c;
+            if (par != 0u) atomicOr(&xb[v >> 5], 1u << (v & 31));
+        }
+        __syncthreads();
+    }
+}
+
+// wofdm_ldpc_encode (wofdm_ldpcencparams): one workgroup per codeword, the word as bits in LDS behind the shifts (288 bytes)
+#define WOFDM_LDPC_ENC_HEAD 288            // 6 x 24 int16 shifts
+__global__ void __launch_bounds__(256) wofdm_ldpc_encode_kernel(const wofdm_ldpcencparams ep)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char esm[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int J = ep.J, L = ep.L, n = ep.n, Z = ep.Z, k0 = J * Z, words = (L * Z + 31) >> 5;
+    int16_t *__restrict__ sh = reinterpret_cast<int16_t *>(esm);
+    uint32_t *xb = reinterpret_cast<uint32_t *>(esm + WOFDM_LDPC_ENC_HEAD);
+    const uint8_t *__restrict__ info = ep.info + (uint64_t)blockIdx.x * (uint64_t)(n - k0);
+    ldpc_shifts(sh, J, L, Z, tid, nt);
+    for (int x = tid; x < words; x += nt) {
+        uint32_t wv = 0u;
+        for (int b = 0; b < 32; ++b) {
+            const int v = 32 * x + b;
+            wv |= (v >= k0 && v < n ? (uint32_t)info[v - k0] & 1u : 0u) << b;
+        }
+        xb[x] = wv;
+    }
+    __syncthreads();
+    ldpc_encode_lds(xb, sh, J, L, Z, tid, nt);
+    uint8_t *__restrict__ out = ep.word + (uint64_t)blockIdx.x * (uint64_t)n;
+    for (int x = tid; x < n; x += nt) out[x] = (uint8_t)ldpc_bit(xb, x);
+}
+
+// 32 bits of the information stream of (cell, frame) from bit `start` > -32 on; a bit below 0 reads 0
+__device__ __forceinline__ uint32_t coset_bits32(const wofdm_cosetparams &cs, uint32_t cell, uint64_t frame, int start)
+{
+    if (start < 0) return wofdm_info_word(cs.seed_lo, cs.seed_hi, cell, frame, 0u) << (-start);
+    const uint32_t q = (uint32_t)start >> 5, sft = (uint32_t)start & 31u;
+    const uint32_t lo = wofdm_info_word(cs.seed_lo, cs.seed_hi, cell, frame, q);
+    return sft == 0u ? lo : (lo >> sft) | (wofdm_info_word(cs.seed_lo, cs.seed_hi, cell, frame, q + 1u) << (32u - sft));
+}
+
+// wofdm_viterbi_long_kernel in the coset view (wofdm_rx_profile_coset): the transmitted word is conv_encode of the frame's
+// information stream, bits 0 ... T - 7, and the decoder sees d' = x_c ? -d : d.  The stream comes as one Philox block per 128
+// steps, kept as two 64-bit words (wave-uniform); lane l forms the register of step 64 b + l from the block's word and the six
+// bits before it, its A and B by conv_ab, and flips its pair before the block is walked.  The traceback draws the blocks again,
+// descending, and XORs a block's 64 decoded bits with the stream's (the tail's are zero): what is left are the errors, counted
+// as wofdm_viterbi_long_kernel counts the ones.  Everything else is that kernel, statement for statement.
+__global__ void __launch_bounds__(64) wofdm_viterbi_coset_kernel(const wofdm_longparams lp, const wofdm_cosetparams cs)
+{
+    const int lane = threadIdx.x;
+    const uint64_t w = blockIdx.x;
+    const int pt = (int)(w % (uint64_t)lp.n_points);
+    const int v = lp.pts[pt].post != 0 ? 1 : 0;
+    const int rate = lp.rate, T = lp.steps[v], n_c = lp.n_c[v];
+    if (T < 7) return;                                                  // (a point without a data symbol: wave-uniform)
+    const int n_blocks = (T + 63) >> 6;
+    const int32_t *__restrict__ gather = lp.gather[v];
+    const int8_t *__restrict__ soft = lp.soft + (int64_t)w * lp.cw_stride;
+    unsigned long long *__restrict__ hist = lp.hist + (size_t)w * (size_t)lp.hist_blocks * 64;
+    const uint64_t item = lp.item0 + w / (uint64_t)lp.n_points, cell = item / lp.frames;
+    const uint64_t frame = cs.frame_offset + (item - cell * lp.frames);
+
+    // the stream's bits 64 b ... 64 b + 63, those of the tail (t >= T - 6) zero
+    int drawn = -1;
+    unsigned long long even = 0ull, odd = 0ull;
+    const auto stream64 = [&](int b) {
+        if ((b >> 1) != drawn) {
+            drawn = b >> 1;
+            const philox_out o = philox4x32_10((uint32_t)drawn, (uint32_t)frame, (uint32_t)(frame >> 32),
+                                               (WOFDM_STREAM_INFO << 28) | (uint32_t)cell, cs.seed_lo, cs.seed_hi);
+            even = ((unsigned long long)o.w[1] << 32) | o.w[0];
+            odd = ((unsigned long long)o.w[3] << 32) | o.w[2];
+        }
+        const int lim = T - 6 - 64 * b;
+        const unsigned long long im = lim >= 64 ? ~0ull : (lim <= 0 ? 0ull : (1ull << lim) - 1ull);
+        return ((b & 1) != 0 ? odd : even) & im;
+    };
+
+    const int p0 = (lane << 1) & 63, u = lane >> 5, r0 = (u << 6) | p0;
+    const bool a0 = (__popc(r0 & 0133) & 1) != 0, b0 = (__popc(r0 & 0171) & 1) != 0;
+    int m = lane == 0 ? 0 : (1 << 30);
+    uint32_t hlo, hhi;
+    const vlong_i16x2 sel0 = {(short)(a0 ? 1 : 0), (short)(b0 ? 1 : 0)}, sel1 = {(short)(a0 ? 0 : 1), (short)(b0 ? 0 : 1)};
+    const auto step = [&](int i, int pair) {
+        const vlong_i16x2 d = __builtin_bit_cast(vlong_i16x2, pair);
+        const int c0 = __builtin_amdgcn_sdot2(sel0, d, __shfl(m, p0, 64), false);
+        const int c1 = __builtin_amdgcn_sdot2(sel1, d, __shfl(m, p0 | 1, 64), false);
+        const bool dec = c1 < c0;
+        m = dec ? c1 : c0;
+        if (i < 32)
+            hlo |= dec ? 1u << i : 0u;
+        else
+            hhi |= dec ? 1u << (i - 32) : 0u;
+    };
+    int dp, oa, ob;
+    vlong_offsets(gather, rate, n_c, T, lane, oa, ob);
+    dp = vlong_pair(soft, oa, ob);
+    vlong_offsets(gather, rate, n_c, T, 64 + lane, oa, ob);
+    unsigned long long before = 0ull;                                    // the stream's word of block b - 1
+    for (int b = 0; b < n_blocks; ++b) {
+        int noa, nob;
+        const int ndp = vlong_pair(soft, oa, ob);                        // block b + 1 (zeros behind the codeword's end)
+        vlong_offsets(gather, rate, n_c, T, 64 * (b + 2) + lane, noa, nob);
+        // the transmitted pair of step 64 b + lane, and d' for both of its outputs (|d| <= 127: the negation is exact)
+        const unsigned long long cur = stream64(b);
+        const uint32_t ab = conv_ab((uint32_t)((lane >= 6 ? cur >> (lane - 6) : (cur << (6 - lane)) | (before >> (58 + lane))) & 0x7Full));
+        const int da = (int)(short)(dp & 0xFFFF), db = dp >> 16;
+        const int fp = (int)(((uint32_t)((ab & 1u) != 0u ? -da : da) & 0xFFFFu) | ((uint32_t)((ab & 2u) != 0u ? -db : db) << 16));
+        hlo = hhi = 0u;
+        const int n = T - 64 * b;
+        if (n >= 64) {
+#pragma unroll
+            for (int i = 0; i < 64; ++i) step(i, __builtin_amdgcn_readlane(fp, i));
+        } else {
+            for (int i = 0; i < n; ++i) step(i, __builtin_amdgcn_readlane(fp, i));
+        }
+        hist[(size_t)b * 64 + (size_t)lane] = ((unsigned long long)hhi << 32) | (unsigned long long)hlo;
+        dp = ndp; oa = noa; ob = nob;
+        before = cur;
+    }
+    // (a lane reads back what it stored itself: program order, no fence is needed)
+    int st = 0, info = 0;
+    bool any = false;
+    for (int b = n_blocks - 1; b >= 0; --b) {
+        const unsigned long long hw = hist[(size_t)b * 64 + (size_t)lane];
+        const int wlo = (int)(uint32_t)hw, whi = (int)(uint32_t)(hw >> 32);
+        const int n = T - 64 * b;
+        unsigned long long mask = 0ull;
+        const auto back = [&](int i) {
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane(i < 32 ? wlo : whi, st);
+            mask |= (unsigned long long)(st >> 5) << i;
+            st = ((st << 1) & 63) | (int)((word >> (i & 31)) & 1u);
+        };
+        if (n >= 64) {
+#pragma unroll
+            for (int i = 63; i >= 0; --i) back(i);
+        } else {
+            for (int i = n - 1; i >= 0; --i) back(i);
+        }
+        mask ^= stream64(b);
+        const int lim = T - 6 - 64 * b;
+        const unsigned long long im = lim >= 64 ? ~0ull : (lim <= 0 ? 0ull : (1ull << lim) - 1ull);
+        info += __popcll(mask & im);
+        any = any || mask != 0ull;
+    }
+    if (lane == 0 && any) {
+        unsigned long long *e = lp.errs + (((uint64_t)pt * lp.cells + cell) * (uint64_t)lp.n_codes + (uint64_t)lp.code) * 2;
+        if (info != 0) atomicAdd(e, (unsigned long long)info);
+        atomicAdd(e + 1, 1ull);
+    }
+}
+
+// wofdm_ldpc_kernel in the coset view (wofdm_rx_profile_coset): word wi of the frame carries the information stream's bits wi n
+// ... wi n + K - 1 on variables J Z ... n - 1.  The workgroup draws them into LDS as bits (behind R: wofdm_ldpc_coset_lds),
+// encodes them there (ldpc_encode_lds), flips the signs while it gathers into Q -- d' = x ? -d : d --, and compares the decisions
+// with the kept word at the end.  The decoder between the two is wofdm_ldpc_kernel's, statement for statement.
+__global__ void __launch_bounds__(256) wofdm_ldpc_coset_kernel(const wofdm_ldpcparams lp, const wofdm_cosetparams cs)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const uint64_t w = blockIdx.x;
+    const int wi = blockIdx.y;
+    const int pt = (int)(w % (uint64_t)lp.n_points);
+    const int v = lp.pts[pt].post != 0 ? 1 : 0;
+    if (wi >= lp.W[v]) return;                                          // (workgroup-uniform, before the first barrier)
+    const int J = lp.J, L = lp.L, n = lp.n[v], Z = lp.Z[v], n0 = L * Z, E = J * L - J * (J - 1) / 2;
+    int *__restrict__ cnt = reinterpret_cast<int *>(lsm);
+    int16_t *__restrict__ sh = reinterpret_cast<int16_t *>(lsm + 16);
+    int16_t *__restrict__ Q = reinterpret_cast<int16_t *>(lsm + WOFDM_LDPC_LDS_HEAD);
+    int8_t *__restrict__ R = reinterpret_cast<int8_t *>(lsm + WOFDM_LDPC_LDS_HEAD + ((2 * n0 + 3) & ~3));
+    uint32_t *xb = reinterpret_cast<uint32_t *>(lsm + WOFDM_LDPC_LDS_HEAD + ((2 * n0 + 3) & ~3) + ((E * Z + 3) & ~3));   // (wofdm_ldpc_lds)
+    const int8_t *__restrict__ soft = lp.soft + (int64_t)w * lp.cw_stride;
+    const int32_t *__restrict__ gather = lp.gather[v] + (size_t)wi * (size_t)n;
+    const uint64_t item = lp.item0 + w / (uint64_t)lp.n_points, cell = item / lp.frames;
+    const uint64_t frame = cs.frame_offset + (item - cell * lp.frames);
+
+    if (tid < 4) cnt[tid] = 0;
+    ldpc_shifts(sh, J, L, Z, tid, nt);
+    // the information bits: variable x >= J Z is bit wi n + x - J Z of the stream; a thread fills whole words, zeros elsewhere
+    for (int x = tid; x < (n0 + 31) >> 5; x += nt) {
+        const int lo = max(32 * x, J * Z) - 32 * x, hi = min(32 * x + 32, n) - 32 * x;
+        uint32_t wv = 0u;
+        if (lo < hi) {
+            const uint32_t keep = (hi == 32 ? ~0u : (1u << hi) - 1u) & ~((1u << lo) - 1u);
+            wv = coset_bits32(cs, (uint32_t)cell, frame, wi * n + 32 * x - J * Z) & keep;
+        }
+        xb[x] = wv;
+    }
+    {
+        uint32_t *__restrict__ R4 = reinterpret_cast<uint32_t *>(R);
+        const int words = (E * Z + 3) >> 2;
+        for (int x = tid; x < words; x += nt) R4[x] = 0u;
+    }
+    __syncthreads();
+    ldpc_encode_lds(xb, sh, J, L, Z, tid, nt);
+    for (int x = tid; x < n0; x += nt) {
+        const int d = x < n ? (int)soft[gather[x]] : 127;                // (a shortened position is a sure 0 of the word)
+        Q[x] = (int16_t)(ldpc_bit(xb, x) != 0u ? -d : d);
+    }
+    __syncthreads();
+
+    int it = 0;
+    bool conv = false;
+    while (it < lp.max_iter) {
+        int eb = 0;
+        for (int i = 0; i < J; ++i) {
+            const int deg = L - i;
+            const int16_t *__restrict__ si = sh + i * L + i;
+            for (int r = tid; r < Z; r += nt) {
+                int m1 = 255, m2 = 255, par = 0;
+                for (int e = 0; e < deg; ++e) {
+                    int c = r + si[e];
+                    c = c >= Z ? c - Z : c;
+                    const int t = (int)Q[(i + e) * Z + c] - (int)R[(eb + e) * Z + r];
+                    const int a = min(abs(t), 127);
+                    par ^= t < 0 ? 1 : 0;
+                    if (a < m1) {
+                        m2 = m1;
+                        m1 = a;
+                    } else if (a < m2) {
+                        m2 = a;
+                    }
+                }
+                const int g1 = (3 * m1) >> 2, g2 = (3 * m2) >> 2;
+                for (int e = 0; e < deg; ++e) {
+                    int c = r + si[e];
+                    c = c >= Z ? c - Z : c;
+                    const int qi = (i + e) * Z + c, ri = (eb + e) * Z + r;
+                    const int t = (int)Q[qi] - (int)R[ri];
+                    const int a = min(abs(t), 127);
+                    const int mag = a == m1 ? g2 : g1;
+                    const int rn = (par ^ (t < 0 ? 1 : 0)) != 0 ? -mag : mag;
+                    R[ri] = (int8_t)rn;
+                    Q[qi] = (int16_t)(t + rn);
+                }
+            }
+            eb += deg;
+            __syncthreads();
+        }
+        ++it;
+        // the syndrome of the hard decisions
+        int bad = 0;
+        for (int i = 0; i < J; ++i) {
+            const int deg = L - i;
+            const int16_t *__restrict__ si = sh + i * L + i;
+            for (int r = tid; r < Z; r += nt) {
+                int par = 0;
+                for (int e = 0; e < deg; ++e) {
+                    int c = r + si[e];
+                    c = c >= Z ? c - Z : c;
+                    par ^= (int)Q[(i + e) * Z + c] < 0 ? 1 : 0;
+                }
+                bad |= par;
+            }
+        }
+        // (a barrier as well: nobody writes Q for the next layer before everybody has read it)
+        if (__syncthreads_or(bad) == 0) {
+            conv = true;
+            break;
+        }
+    }
+
+    // the information bits are variables J Z ... n - 1: a decision that is not the transmitted bit
+    int wrong = 0;
+    for (int x = J * Z + tid; x < n; x += nt) wrong += (Q[x] < 0 ? 1u : 0u) != ldpc_bit(xb, x) ? 1 : 0;
+    if (wrong != 0) atomicAdd(&cnt[0], wrong);
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long *e = lp.errs + (((uint64_t)pt * lp.cells + cell) * (uint64_t)lp.n_codes + (uint64_t)lp.code) * 4;
+        const int info = cnt[0];
+        if (info != 0) {
+            atomicAdd(e, (unsigned long long)info);
+            atomicAdd(e + 1, 1ull);
+        }
+        if (!conv) atomicAdd(e + 2, 1ull);
+        atomicAdd(e + 3, (unsigned long long)it);
+    }
+}
+
 // totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
 template <int N>
 __global__ void __launch_bounds__(64) wofdm_rxprof_reduce_kernel(const wofdm_rparams p, uint64_t cell0)
@@ -2868,6 +3228,25 @@ hipError_t ldpc_enqueue(const wofdm_ldpcparams &lp, bool profile, hipStream_t s)
     hipLaunchKernelGGL(wofdm_ldpc_kernel, dim3(lp.n_cw, (unsigned)W), dim3(threads), (unsigned)lds, s, lp);
     return hipSuccess;
 }
+// one launch of the coset instantiation: ldpc_enqueue's grid and workgroup, the transmitted word's bits behind the decoder's LDS
+hipError_t ldpc_coset_enqueue(const wofdm_ldpcparams &lp, const wofdm_cosetparams &cs, hipStream_t s)
+{
+    int Z = 0, W = 0;
+    for (int v = 0; v < 2; ++v) {
+        if (lp.W[v] == 0) continue;
+        Z = lp.Z[v] > Z ? lp.Z[v] : Z;
+        W = lp.W[v] > W ? lp.W[v] : W;
+    }
+    if (W == 0) return hipSuccess;                                      // (no point carries a codeword)
+    const uint64_t lds = wofdm_ldpc_coset_lds(lp.J, lp.L, Z);
+    if (lds > WOFDM_LDPC_LDS_MAX) return hipErrorInvalidValue;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_ldpc_coset_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    const unsigned threads = (unsigned)(Z >= 256 ? 256 : ((Z + 63) / 64) * 64);
+    hipLaunchKernelGGL(wofdm_ldpc_coset_kernel, dim3(lp.n_cw, (unsigned)W), dim3(threads), (unsigned)lds, s, lp, cs);
+    return hipSuccess;
+}
 // the ordered sums of the chunk onto the totals: per point of sp, or (null) the plain ones
 void rxprof_reduce_launch(const wofdm_rparams &r, const wofdm_sparams *sp, hipStream_t s)
 {
@@ -2897,9 +3276,12 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
     const bool nb = c.arm == RXP_ACI || (link && c.nb_on), sync = c.arm == RXP_SYNC || link, knots = c.arm == RXP_DOPPLER || link;
     const bool amp = c.arm == RXP_PA || link, walk = c.arm == RXP_PN || link, soft = link && c.soft_on, track = soft && c.track_on;
     const bool code = track && c.code_on, frame = code && c.frame_on, ldpc = code && !frame && c.ldpc_on;
+    const bool coset = code && !frame && !ldpc && c.coset_on;
     if (nb != c.nb_on || soft != c.soft_on || track != c.track_on || code != c.code_on || frame != c.frame_on || ldpc != c.ldpc_on ||
-        (code && !frame && !ldpc && !viterbi_ok(c.cd, true)) ||
+        coset != c.coset_on || (code && !frame && !ldpc && !coset && !viterbi_ok(c.cd, true)) ||
         ((frame || ldpc) && (c.cd.soft == nullptr || !(c.cd.llr_scale > 0.f) || c.cd.n_codes < 1 || c.cd.n_codes > WOFDM_CODE_CODES)) ||
+        (coset && (c.cd.soft == nullptr || !(c.cd.llr_scale > 0.f) || c.cs_nv < 0 || c.cs_nv > WOFDM_CODE_CODES || c.cs_nl < 0 ||
+                   c.cs_nl > WOFDM_CODE_CODES || c.cs_nv + c.cs_nl < 1)) ||
         (track && (c.tk.pts == nullptr || r.S > 64)) || !rxprof_args_ok(&c.tx, r) || (points && !rxprof_points_ok(c.sp, r, MAX_POINTS[c.arm])) ||
         (nb && !rxprof_nb_ok(c, !link)) || (sync && (c.sp.pts == nullptr || c.sp.base == nullptr)) ||
         (knots && !rxprof_knots_ok(c.dp, r, link, link ? c.max_theta : 0)) || (amp && !rxprof_pa_ok(c)) ||
@@ -2984,6 +3366,36 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
             const hipError_t le = ldpc_enqueue(lp, true, s);
             if (le != hipSuccess) return le;
         }
+    } else if (coset) {
+        // both decoders behind the same soft bits, in the coset view: the frame launches' and the LDPC launches' parameters as
+        // above, one launch per code, the Viterbi codes first
+        wofdm_longparams fp = c.fr;
+        fp.soft = c.cd.soft;
+        fp.cw_stride = (int64_t)(r.S - 1) * N * 8;
+        fp.pts = c.tk.pts; fp.n_points = c.sp.n_points; fp.n_codes = c.cs_nv;
+        fp.item0 = r.item0; fp.frames = r.frames; fp.cells = c.sp.cells;
+        fp.bits = nullptr; fp.metric = nullptr;
+        fp.n_cw = (uint32_t)r.n_jobs * (uint32_t)fp.n_points;
+        for (int i = 0; i < c.cs_nv; ++i) {
+            fp.rate = c.cd.rate[i]; fp.code = i;
+            fp.steps[0] = c.fr_steps[i][0]; fp.steps[1] = c.fr_steps[i][1];
+            if (!viterbi_long_ok(fp, true)) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(wofdm_viterbi_coset_kernel, dim3(fp.n_cw), dim3(64), 0, s, fp, c.cs);
+        }
+        wofdm_ldpcparams lp = c.ld;
+        lp.soft = c.cd.soft;
+        lp.cw_stride = fp.cw_stride;
+        lp.pts = c.tk.pts; lp.n_points = c.sp.n_points; lp.n_codes = c.cs_nl;
+        lp.item0 = r.item0; lp.frames = r.frames; lp.cells = c.sp.cells;
+        lp.bits = nullptr; lp.iters = nullptr; lp.conv = nullptr;
+        lp.n_cw = fp.n_cw;
+        for (int i = 0; i < c.cs_nl; ++i) {
+            lp.J = c.ld_code[i][0]; lp.L = c.ld_code[i][1]; lp.max_iter = c.ld_code[i][2]; lp.code = i;
+            lp.Z[0] = c.ld_Z[i][0]; lp.Z[1] = c.ld_Z[i][1];
+            if (!ldpc_ok(lp, true)) return hipErrorInvalidValue;
+            const hipError_t le = ldpc_coset_enqueue(lp, c.cs, s);
+            if (le != hipSuccess) return le;
+        }
     } else if (code) {
         // the decoder behind the soft bits: one wave per (frame, point, data symbol) and code
         wofdm_codeparams cd = c.cd;
@@ -3022,6 +3434,29 @@ hipError_t ldpc_launch(const wofdm_ldpcparams *lp, hipStream_t s)
     return e != hipSuccess ? e : hipGetLastError();
 }
 
+// wofdm_conv_encode: the K = 7 encoder on information words of the caller's
+hipError_t conv_encode_launch(const wofdm_convencparams *ep, hipStream_t s)
+{
+    if (ep->info == nullptr || ep->coded == nullptr || ep->rate < 0 || ep->rate > 2 || ep->n_c < 1 || ep->steps < 7 ||
+        ep->steps > WOFDM_CODE_LONG_STEPS || ep->n_cw < 1)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wofdm_conv_encode_kernel, dim3(ep->n_cw, (unsigned)((ep->steps + 255) / 256)), dim3(256), 0, s, *ep);
+    return hipGetLastError();
+}
+
+// wofdm_ldpc_encode: the LDPC encoder on information words of the caller's
+hipError_t ldpc_encode_launch(const wofdm_ldpcencparams *ep, hipStream_t s)
+{
+    if (ep->info == nullptr || ep->word == nullptr || ep->J < 3 || ep->J > 6 || ep->L <= ep->J || ep->L > 24 || ep->n < 1 ||
+        ep->n > WOFDM_LDPC_BITS || ep->Z < ep->L || (int64_t)ep->L * ep->Z < ep->n || ep->J * ep->Z >= ep->n || ep->Z > 32767 ||
+        ep->n_cw < 1)
+        return hipErrorInvalidValue;
+    const unsigned lds = WOFDM_LDPC_ENC_HEAD + 4u * (unsigned)((ep->L * ep->Z + 31) / 32);
+    const unsigned threads = (unsigned)(ep->Z >= 256 ? 256 : ((ep->Z + 63) / 64) * 64);
+    hipLaunchKernelGGL(wofdm_ldpc_encode_kernel, dim3(ep->n_cw), dim3(threads), lds, s, *ep);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
@@ -3032,7 +3467,8 @@ const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
 
 const wofdm_link_fns *WOFDM_CAT(wofdm_aux_link_n, WOFDM_TU_N)(void)
 {
-    static const wofdm_link_fns fns = {rx_profile_chunk, viterbi_launch, viterbi_long_launch, ldpc_launch};
+    static const wofdm_link_fns fns = {rx_profile_chunk, viterbi_launch, viterbi_long_launch, ldpc_launch, conv_encode_launch,
+                                       ldpc_encode_launch};
     return &fns;
 }
 

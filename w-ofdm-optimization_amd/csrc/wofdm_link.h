@@ -5,6 +5,7 @@
 // (GNUmakefile tells make which objects depend on this file, for the same reason).
 #pragma once
 #include "wofdm_pa.h"
+#include "philox.h"
 
 #define WOFDM_LINK_POINTS 16               // WOFDM_LINK_MAX_POINTS of include/wofdm.h
 
@@ -137,6 +138,46 @@ static inline uint64_t wofdm_ldpc_lds(int32_t J, int32_t L, int32_t Z)
     return WOFDM_LDPC_LDS_HEAD + q + (((uint64_t)Z * (uint64_t)(J * L - J * (J - 1) / 2) + 3ull) & ~3ull);
 }
 
+// The information stream of the coset view (wofdm_rx_profile_coset, wofdm_coset_info), a fifth Philox stream beside the four of
+// philox.h -- defined here, philox.h being part of the frame kernels' source hash, which never draw it: block b of (seed, cell,
+// frame) is philox4x32_10 of counter (b, frame lo, frame hi, 4 << 28 | cell) under key (seed lo, seed hi), and bit i of the
+// frame's stream is bit i mod 32 of word (i mod 128) div 32 of block i div 128.  Neither the point nor the code enters it.
+#define WOFDM_STREAM_INFO 4u
+// word q (32 bits) of the stream; the word is picked by selects, never by an index (a block stays in registers)
+__host__ __device__ __forceinline__ uint32_t wofdm_info_word(uint32_t seed_lo, uint32_t seed_hi, uint32_t cell, uint64_t frame, uint32_t q)
+{
+    const philox_out o = philox4x32_10(q >> 2, (uint32_t)frame, (uint32_t)(frame >> 32), (WOFDM_STREAM_INFO << 28) | cell, seed_lo, seed_hi);
+    const uint32_t lo = (q & 1u) != 0 ? o.w[1] : o.w[0], hi = (q & 1u) != 0 ? o.w[3] : o.w[2];
+    return (q & 2u) != 0 ? hi : lo;
+}
+
+// What the coset instantiations of the two decoders (wofdm_viterbi_coset_kernel, wofdm_ldpc_coset_kernel) take beside the
+// decoder's own parameters: the call's key and first frame.  Workgroup w = (job, point) draws the stream of cell (item0 + job) /
+// frames, frame frame_offset + (item0 + job) mod frames.
+struct wofdm_cosetparams {
+    uint32_t seed_lo, seed_hi;
+    uint64_t frame_offset;
+};
+// the coset LDPC instantiation's LDS in bytes: the decoder's, and behind it the transmitted word as bits, one per variable < L Z
+static inline uint64_t wofdm_ldpc_coset_lds(int32_t J, int32_t L, int32_t Z)
+{
+    return wofdm_ldpc_lds(J, L, Z) + 4ull * (((uint64_t)L * (uint64_t)Z + 31ull) / 32ull);
+}
+
+// The stand-alone encoders (wofdm_conv_encode, wofdm_ldpc_encode): bits as bytes, one block per codeword
+struct wofdm_convencparams {
+    const uint8_t *info;              // [n_cw][steps - 6]
+    uint8_t *coded;                   // [n_cw][n_c]
+    int32_t rate, n_c, steps;         // steps = wofdm_code_steps(rate, n_c) in 7 ... WOFDM_CODE_LONG_STEPS
+    uint32_t n_cw;
+};
+struct wofdm_ldpcencparams {
+    const uint8_t *info;              // [n_cw][n - J Z]
+    uint8_t *word;                    // [n_cw][n]
+    int32_t J, L, n, Z;
+    uint32_t n_cw;
+};
+
 // The arms of the receive body (rxprof_body of wofdm_aux.hip, which says what each adds)
 enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
 
@@ -171,6 +212,11 @@ struct wofdm_rxchunk {
     wofdm_ldpcparams ld;              // ldpc_on: gather, n, W, errs; the launcher fills in the rest
     int32_t ld_code[WOFDM_CODE_CODES][3];    // ldpc_on: J, L, max_iter per code
     int32_t ld_Z[WOFDM_CODE_CODES][2];       // ldpc_on: the lift per code and variant
+    bool coset_on;                    // (wofdm_rx_profile_coset) needs code_on, never with frame_on or ldpc_on: the coset instantiations of
+                                      // both decoders behind one receive kernel, cs_nv launches over fr (rates in cd.rate, fr_steps) and
+                                      // cs_nl over ld (ld_code, ld_Z); either count may be 0, cd.n_codes is not read
+    int32_t cs_nv, cs_nl;
+    wofdm_cosetparams cs;
 };
 
 struct wofdm_link_fns {
@@ -184,6 +230,10 @@ struct wofdm_link_fns {
     hipError_t (*viterbi_long)(const wofdm_longparams *lp, hipStream_t s);
     // wofdm_ldpc_kernel on soft bits of the caller's (lp.errs null, lp.bits set): one workgroup per codeword, variant 0
     hipError_t (*ldpc)(const wofdm_ldpcparams *lp, hipStream_t s);
+    // wofdm_conv_encode_kernel: grid (n_cw, ceil(steps / 256)), one step per lane
+    hipError_t (*conv_encode)(const wofdm_convencparams *ep, hipStream_t s);
+    // wofdm_ldpc_encode_kernel: one workgroup per codeword
+    hipError_t (*ldpc_encode)(const wofdm_ldpcencparams *ep, hipStream_t s);
 };
 const wofdm_link_fns *wofdm_aux_link_n64(void);
 const wofdm_link_fns *wofdm_aux_link_n128(void);

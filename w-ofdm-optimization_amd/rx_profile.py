@@ -42,6 +42,11 @@ mirror it.
 (``pilot_comb``) gives a common-phase estimate per data symbol, a postamble lets the channel estimate be interpolated over the
 frame, a ``TrackingPoint`` per link point switches either on; ``tracking_equalise`` states the definition in fp64,
 ``frame_profile_tracking`` and ``rx_profile_tracking_host`` mirror the call.
+
+``rx_profile_coset_gpu`` (``wofdm_rx_profile_coset``) runs the Viterbi and the LDPC decoders of the coded link behind one receive
+chain against RANDOM transmitted words -- the frame's information stream (``coset_info``, Philox stream 4) encoded on the GPU --
+where the coded calls count against the all-zero word; ``coset_codewords`` gives the transmitted words, ``conv_encode_gpu`` and
+``ldpc_encode_gpu`` are the encoders alone, ``frame_profile_coset`` and ``rx_profile_coset_host`` mirror the call.
 """
 import collections
 
@@ -1723,14 +1728,11 @@ def conv_encode(info, rate):
     steps = u.shape[-1]
     ca, cb, kept = _kept_index(rate, steps)
     out = np.zeros(u.shape[:-1] + (kept,), dtype=np.uint8)
-    state = np.zeros(u.shape[:-1], dtype=np.int64)
-    for t in range(steps):
-        r = (u[..., t] << 6) | state
-        if ca[t] >= 0:
-            out[..., ca[t]] = _parity(r & 0o133)
-        if cb[t] >= 0:
-            out[..., cb[t]] = _parity(r & 0o171)
-        state = (u[..., t] << 5) | (state >> 1)
+    # bit j of the register r_t = (u_t << 6) | state is u_(t - 6 + j): every step's outputs at once, as parities of seven bits
+    past = np.concatenate([np.zeros(u.shape[:-1] + (6,), dtype=np.int64), u], axis=-1)
+    r = sum(past[..., j:j + steps] << j for j in range(7))
+    out[..., ca[ca >= 0]] = _parity(r & 0o133)[..., ca >= 0]
+    out[..., cb[cb >= 0]] = _parity(r & 0o171)[..., cb >= 0]
     return out
 
 
@@ -2575,3 +2577,282 @@ def ldpc_fer(prof):
 def ldpc_mean_iterations(prof):
     """The iterations run per codeword, shaped as ``ldpc_ber``'s"""
     return _ldpc_per_word(prof, prof.iterations, (prof.info_bits > 0).astype(np.float64))
+
+
+# ---- random information words: both decoders in the coset view (wofdm_rx_profile_coset), the encoders on the GPU ----
+
+#: the Philox stream of the information words (csrc/wofdm_link.h), beside ``STREAM_BITS`` ... ``STREAM_PN``
+STREAM_INFO = 4
+
+RxProfileCoset = collections.namedtuple(
+    "RxProfileCoset", RxProfileTracking._fields + (
+        "info_err", "cw_err", "info_bits", "codewords", "rates",
+        "ldpc_info_err", "ldpc_cw_err", "unconverged", "iterations", "ldpc_info_bits", "ldpc_codewords", "ldpc_codes",
+        "llr_scale", "sym_rot", "soft_bits"))
+RxProfileCoset.__doc__ = """``RxProfileTracking``'s fields; info_err, cw_err, info_bits, codewords, rates as ``RxProfileCodedFrame``'s
+and ldpc_info_err, ldpc_cw_err, unconverged, iterations, ldpc_info_bits, ldpc_codewords, ldpc_codes as ``RxProfileLdpc``'s info_err
+... codes -- but against RANDOM transmitted words, the frame's information stream encoded (``coset_codewords``), where those count
+against the all-zero word; a family without a code has arrays with a code axis of length 0; llr_scale; sym_rot; soft_bits as
+theirs."""
+
+
+def coset_info(seed, cell, frame, n_bits):
+    """Bits 0 ... n_bits - 1 (uint8) of the information stream of (seed, cell, frame), ``wofdm_coset_info``: Philox stream 4,
+    bit i is bit i mod 32 of word (i mod 128) div 32 of block i div 128"""
+    n_bits = int(n_bits)
+    w = _stream(seed, STREAM_INFO, cell, frame, max((n_bits + 127) // 128, 1)).reshape(-1)
+    i = np.arange(n_bits, dtype=np.int64)
+    return ((w[i >> 5] >> (i & 31).astype(np.uint64)) & np.uint64(1)).astype(np.uint8)
+
+
+def conv_encode_gpu(info, rate, n_c, device=0):
+    """``wofdm_conv_encode``: info [n_cw, T - 6] bits, T = ``code_steps``(rate, n_c) -> the coded stream [n_cw, n_c] (uint8):
+    ``conv_encode``'s kept outputs, zeros on the left-over positions.  No CPU fallback."""
+    from . import _lib
+    info = np.ascontiguousarray(np.atleast_2d(np.asarray(info)), dtype=np.uint8)
+    steps = code_steps(rate, n_c)
+    if info.shape[1] != steps - 6:
+        raise ValueError("a word has T - 6 = %d information bits" % (steps - 6))
+    coded = np.zeros((info.shape[0], int(n_c)), dtype=np.uint8)
+    _lib.check(_lib.load().wofdm_conv_encode(int(device), int(rate), int(n_c), info.shape[0], info.ctypes.data, coded.ctypes.data))
+    return coded
+
+
+def ldpc_encode_gpu(info, J, L, n, device=0):
+    """``wofdm_ldpc_encode``: info [n_cw, K] bits -> the codewords [n_cw, n] (uint8), ``ldpc_encode``'s.  No CPU fallback."""
+    from . import _lib
+    info = np.ascontiguousarray(np.atleast_2d(np.asarray(info)), dtype=np.uint8)
+    K = int(n) - int(J) * ldpc_lift(J, L, n)
+    if info.shape[1] != K:
+        raise ValueError("the code has K = %d information bits" % K)
+    word = np.zeros((info.shape[0], int(n)), dtype=np.uint8)
+    _lib.check(_lib.load().wofdm_ldpc_encode(int(device), int(J), int(L), int(n), info.shape[0], info.ctypes.data, word.ctypes.data))
+    return word
+
+
+def _coset_lists(codes, ldpc_codes):
+    """(rates, LDPC codes): ``_code_list`` and ``_ldpc_code_list``, either of which an empty sequence switches off"""
+    rates = [] if codes is not None and len(codes) == 0 else _code_list(codes)
+    cl = [] if ldpc_codes is not None and len(ldpc_codes) == 0 else _ldpc_code_list(ldpc_codes)
+    if not rates and not cl:
+        raise ValueError("at least one code is needed")
+    return rates, cl
+
+
+def coset_codewords(seed, cell, frame, n_f, codes=None, ldpc_codes=None):
+    """The transmitted coded streams of one (cell, frame) whose frame has n_f coded-stream positions, as
+    ``wofdm_rx_profile_coset`` forms them -- for a decoder of the caller's own: (x [codes, n_f], x_ldpc [ldpc codes, n_f]), uint8.
+    A Viterbi code's word is ``conv_encode`` of stream bits 0 ... T - 7; LDPC word w of a code, at coded-stream indices w n ... w n
+    + n - 1, is ``ldpc_encode`` of stream bits w n ... w n + K - 1; left-over positions are 0.  A soft bit d of coded-stream index
+    c (``frame_codewords``) reaches the decoder as -d where x[c] is 1."""
+    rates, cl = _coset_lists(codes, ldpc_codes)
+    n_f = int(n_f)
+    stream = coset_info(seed, cell, frame, n_f)
+    xv, xl = np.zeros((len(rates), n_f), dtype=np.uint8), np.zeros((len(cl), n_f), dtype=np.uint8)
+    for i, r in enumerate(rates):
+        word = conv_encode(stream[:code_steps(r, n_f) - 6], r)
+        xv[i, :word.size] = word
+    W, n = ldpc_frame_words(n_f)
+    for i, (J, L, _) in enumerate(cl):
+        K = n - J * ldpc_lift(J, L, n)
+        info = np.stack([stream[w * n:w * n + K] for w in range(W)])
+        xl[i, :W * n] = ldpc_encode(info, J, L, n).reshape(-1)
+    return xv, xl
+
+
+def _coset_prepare(st, bits_per_sc, syms, act, pil, tps, codes, ldpc_codes, perm, llr_scale, sym_rot):
+    """(rates, LDPC codes, perm or None, pos, sym_rot, T [points, codes], W [points], K [points, ldpc codes]): ``_frame_code_prepare``
+    and ``_ldpc_prepare`` for the families in use"""
+    rates, cl = _coset_lists(codes, ldpc_codes)
+    steps = np.zeros((len(tps), 0), dtype=np.int64)
+    W, K = np.zeros(len(tps), dtype=np.int64), np.zeros((len(tps), 0), dtype=np.int64)
+    if rates:
+        _, p, pos, rot, steps = _frame_code_prepare(st, bits_per_sc, syms, act, pil, tps, rates, perm, llr_scale, sym_rot)
+    if cl:
+        _, p, pos, rot, W, _, K = _ldpc_prepare(st, bits_per_sc, syms, act, pil, tps, cl, perm, llr_scale, sym_rot)
+    return rates, cl, p, pos, rot, steps, W, K
+
+
+def _decode_frame_coset(d, tp, pos, perm, rates, cl, sym_rot, seed, cell, frame):
+    """({info errors, codeword errors} [codes, 2], {info errors, codeword errors, unconverged, iterations} [ldpc codes, 4]) of a
+    frame's soft bits d [S - 1, N, 8] against the transmitted words of (seed, cell, frame): the mirror decoders on d' = x ? -d : d"""
+    ferr, lerr = np.zeros((len(rates), 2), dtype=np.uint64), np.zeros((len(cl), 4), dtype=np.uint64)
+    if d.shape[0] - int(bool(tp.post)) < 1:
+        return ferr, lerr
+    soft = frame_codewords(d, tp.post, pos, perm, sym_rot).astype(np.int16)
+    xv, xl = coset_codewords(seed, cell, frame, soft.size, rates, cl)
+    for i, r in enumerate(rates):
+        bits, _ = viterbi_decode(np.where(xv[i] != 0, -soft, soft)[None], r)
+        T = bits.shape[1]
+        wrong = bits[0] ^ np.concatenate([coset_info(seed, cell, frame, T - 6), np.zeros(6, np.uint8)])
+        ferr[i] = wrong[:T - 6].sum(), wrong.any()
+    W, n = ldpc_frame_words(soft.size)
+    for i, (J, L, max_iter) in enumerate(cl):
+        bits, iters, conv = ldpc_decode(np.where(xl[i] != 0, -soft, soft)[:W * n].reshape(W, n), J, L, max_iter)
+        wrong = (bits ^ xl[i, :W * n].reshape(W, n))[:, J * ldpc_lift(J, L, n):]
+        lerr[i] = wrong.sum(), wrong.any(axis=1).sum(), (~conv).sum(), iters.sum()
+    return ferr, lerr
+
+
+def frame_profile_coset(st, grids, noise_at, w_tx, w_rx, h, point, tracking, snr_db, bits_per_sc, walk, seed, cell, frame, pilots=None,
+                        scales=None, llr_scale=LLR_SCALE, perm=None, codes=None, ldpc_codes=None, sym_rot=None, track=None,
+                        knot_step=None, ref_power=None, aci_grids=None, aci_h=None, active=None, mask=None, noise_before_truncate=1):
+    """fp64 host mirror of one frame and one point of ``wofdm_rx_profile_coset``: ``frame_profile_coded``'s outputs through the near
+    rule's weight, then ``_decode_frame_coset``'s two arrays -- the frame's words are those of the information stream of (seed, cell,
+    frame), which the caller names beside the randomness it hands in."""
+    sc = _soft_scales(scales)
+    syms = np.asarray(grids).shape[0]
+    tps, pil = _tracking_prepare(st, syms, 1, [tracking], pilots, active)
+    rates, cl, p, pos, rot = _coset_prepare(st, bits_per_sc, syms, active, pil, tps, codes, ldpc_codes, perm, llr_scale, sym_rot)[:5]
+    front, out = _frame_link(st, grids, noise_at, w_tx, w_rx, h, point, snr_db, bits_per_sc, walk, track, knot_step, ref_power,
+                             aci_grids, aci_h, active, mask, noise_before_truncate)
+    res = _tracking_outputs(st, front, out, w_rx, snr_db, bits_per_sc, sc, noise_before_truncate, pil, tps[0])
+    z, weight = _coded_z(st, front, res, w_rx, snr_db, bits_per_sc, noise_before_truncate, pil, tps[0])
+    d8 = np.zeros(z.shape[:2] + (8,), dtype=np.int8)
+    d8[..., :z.shape[-1]], t = soft_bits(z, llr_scale)
+    return res + (d8, t, weight) + _decode_frame_coset(d8, tps[0], pos, p, rates, cl, rot, seed, cell, frame)
+
+
+def _coset_result(trk, ferr, lerr, steps, W, K, frames, rates, cl, llr_scale, sym_rot, soft):
+    words = np.full(steps.shape[0], int(frames), dtype=np.uint64)
+    return RxProfileCoset(*trk, np.ascontiguousarray(ferr[..., 0]), np.ascontiguousarray(ferr[..., 1]), np.maximum(steps - 6, 0), words,
+                          tuple(rates), *(np.ascontiguousarray(lerr[..., i]) for i in range(4)), K, (W * int(frames)).astype(np.uint64),
+                          tuple(cl), float(llr_scale), int(sym_rot), soft)
+
+
+def rx_profile_coset_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                          tracking=None, pilots=None, scales=None, llr_scale=LLR_SCALE, perm=None, codes=None, ldpc_codes=None,
+                          sym_rot=None, tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None, mask=None,
+                          noise_before_truncate=1, with_near=False, with_soft=False):
+    """The host route of ``rx_profile_coset_gpu``: ``rx_profile_coded_frame_host``'s frames, points, arrays and soft bits, each
+    (frame, point)'s words drawn, encoded and decoded by the mirrors (``_decode_frame_coset``).  Returns ``RxProfileCoset``
+    (with_near: and the near decisions); with_soft as in ``rx_profile_coded_host``."""
+    held = {}
+
+    def receiver(q, n_points, sc):
+        tps, pil = _tracking_prepare(st, q.S, n_points, tracking, pilots, q.act)
+        rates, cl, p, pos, rot, steps, W, K = _coset_prepare(st, q.k, q.S, q.act, pil, tps, codes, ldpc_codes, perm, llr_scale, sym_rot)
+        shape = (n_points, q.w_tx.shape[0], q.snr.size, q.hc.shape[0])
+        held.update(tps=tps, pil=pil, act=q.act, rates=rates, cl=cl, steps=steps, W=W, K=K, rot=rot,
+                    ferr=np.zeros(shape + (len(rates), 2), np.uint64), lerr=np.zeros(shape + (len(cl), 4), np.uint64))
+        if with_soft:
+            lead = shape[1:4] + (int(frames), n_points, q.S - 1, st.n_fft)
+            held.update(d=np.zeros(lead + (8,), np.int8), t=np.zeros(lead + (q.k,), np.float64), w=np.zeros(lead, np.float64))
+
+        def one(i, tp):
+            def run(front, out, p_, s_, c_, f_):
+                res = _tracking_outputs(st, front, out, q.w_rx[p_], q.snr[s_], q.k, sc, q.nbt, pil, tp)
+                z, weight = _coded_z(st, front, res, q.w_rx[p_], q.snr[s_], q.k, q.nbt, pil, tp)
+                d8 = np.zeros(z.shape[:2] + (8,), dtype=np.int8)
+                d8[..., :q.k], t = soft_bits(z, llr_scale)
+                cell = (p_ * q.snr.size + s_) * q.hc.shape[0] + c_
+                ferr, lerr = _decode_frame_coset(d8, tp, pos, p, rates, cl, rot, seed, cell, int(frame_offset) + f_)
+                held["ferr"][i, p_, s_, c_] += ferr
+                held["lerr"][i, p_, s_, c_] += lerr
+                if with_soft:
+                    held["d"][p_, s_, c_, f_, i], held["t"][p_, s_, c_, f_, i], held["w"][p_, s_, c_, f_, i] = d8, t, weight
+                return res
+            return run
+        return [one(i, tp) for i, tp in enumerate(tps)]
+    res = _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, scales, tracks,
+                      knot_step, aci_active, aci_h, ref_power, active, mask, noise_before_truncate, with_near, receiver)
+    soft = res[0] if with_near else res
+    dec, sym = _tracking_decisions(st, syms, frames, held["act"], held["pil"], held["tps"])
+    trk = RxProfileTracking(*soft[:-1], sym, dec)
+    prof = _coset_result(trk, held["ferr"], held["lerr"], held["steps"], held["W"], held["K"], frames, held["rates"], held["cl"],
+                         llr_scale, held["rot"], held.get("d"))
+    if with_soft:
+        prof = (prof, held["t"], held["w"])
+    return (prof, res[1]) if with_near else prof
+
+
+def rx_profile_coset_chunk_frames(st, bits_per_sc, syms, masked, n_points, neighbour, n_scales, n_data_bins, codes=(0,), post=False):
+    """Frames one chunk of ``wofdm_rx_profile_coset`` holds: ``rx_profile_coded_frame_chunk_frames``' with the Viterbi rates
+    ``codes``, and without any (an empty sequence) ``rx_profile_ldpc_chunk_frames``' -- the history term only where a Viterbi code
+    runs"""
+    if len(codes) == 0:
+        return rx_profile_ldpc_chunk_frames(st, syms, masked, n_points, neighbour, n_scales)
+    return rx_profile_coded_frame_chunk_frames(st, bits_per_sc, syms, masked, n_points, neighbour, n_scales, n_data_bins, codes, post)
+
+
+def rx_profile_coset_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                         tracking=None, pilots=None, scales=None, llr_scale=LLR_SCALE, perm=None, codes=None, ldpc_codes=None,
+                         sym_rot=None, tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None, mask=None,
+                         noise_before_truncate=1, device=0, out=None, export=False):
+    """``wofdm_rx_profile_coset``: ``rx_profile_coded_frame_gpu``'s and ``rx_profile_ldpc_gpu``'s frames, tracking fields, soft bits
+    and frame interleaver -- those calls' bytes --, both decoders behind ONE receive chain, and random transmitted words in the
+    place of the all-zero one: the frame's information stream (``coset_info``) encoded on the GPU inside the decoders.  ``codes``
+    are Viterbi rates (None: rate 1/2; an empty sequence: none), ``ldpc_codes`` (J, L) or (J, L, max_iter) each (None: (4, 8); an
+    empty sequence: none).  export=True also returns the soft bits.  Returns ``RxProfileCoset``; ``out`` (an earlier result of the
+    same shape, scales, codes and sym_rot) is accumulated into (its soft bits are dropped).  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    sc = _soft_scales(scales)
+    points = [LinkPoint()] if points is None else points
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts, tr, iact, hi, ref = _link_sides(st, prepared[2], points, tracks, aci_active, aci_h, ref_power, prepared[0].shape[0])
+    tps, pil = _tracking_prepare(st, syms, len(pts), tracking, pilots, prepared[4])
+    rates, cl, p, _, rot, steps, W, K = _coset_prepare(st, bits_per_sc, syms, prepared[4], pil, tps, codes, ldpc_codes, perm, llr_scale,
+                                                       sym_rot)
+    trf = None if tr is None else _lib.c64_as_f32(tr)
+    hif = None if hi is None else _lib.c64_as_f32(hi)
+    lin = PaPoint(PA_LINEAR, 0.0)
+    cpts = (_lib.LinkPoint * len(pts))(*[
+        _lib.LinkPoint(*(q.pa or lin), -1 if q.track is None else q.track, q.timing, q.cfo, q.cfo_tracked, q.linewidth, q.cpe_tracked,
+                       int(q.aci is not None), *(q.aci or (0, 0.0)), (C.c_int32 * 4)(0, 0, 0, 0)) for q in pts])
+    ctps = (_lib.TrackingPoint * len(tps))(*[_lib.TrackingPoint(q.cpe, q.post, (C.c_int32 * 2)(0, 0)) for q in tps])
+    ccodes = (_lib.Code * max(len(rates), 1))(*[_lib.Code(r, (C.c_int32 * 3)(0, 0, 0)) for r in rates])
+    lcodes = (_lib.LdpcCode * max(len(cl), 1))(*[_lib.LdpcCode(J, L, m, 0) for J, L, m in cl])
+    pil8 = None if pil is None else np.ascontiguousarray(pil, dtype=np.uint8)
+    knots = (0, 0, 0) if tr is None else (tr.shape[0], tr.shape[2], int(knot_step))
+    prev = None
+    if out is not None:
+        if (not np.array_equal(out.scales, sc) or tuple(out.rates) != tuple(rates) or tuple(out.ldpc_codes) != tuple(cl)
+                or out.sym_rot != rot):
+            raise ValueError("out has other scales, codes or sym_rot")
+        prev = _RxSoftSums(*out[:9], np.zeros(st.n_fft, dtype=np.uint64))
+    cells = (prepared[0].shape[0], prepared[3].size, prepared[2].shape[0])
+    ferr = np.zeros((len(pts),) + cells + (len(rates), 2), dtype=np.uint64)
+    lerr = np.zeros((len(pts),) + cells + (len(cl), 4), dtype=np.uint64)
+    sb = np.zeros(cells + (int(frames), len(pts), int(syms) - 1, st.n_fft, 8), dtype=np.int8) if export else None
+    res = _gpu_call("wofdm_rx_profile_coset", _RxSoftSums, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                    noise_before_truncate, device, prev, lead=(len(pts),), n_scales=sc.size,
+                    after_mask=(None if trf is None else trf.ctypes.data, *knots, None if iact is None else iact.ctypes.data,
+                                None if hif is None else hif.ctypes.data, None if ref is None else ref.ctypes.data, len(pts), cpts,
+                                int(sc.size), sc.ctypes.data, None if pil8 is None else pil8.ctypes.data, ctps,
+                                C.c_float(float(llr_scale)), None if p is None else p.ctypes.data, len(rates), ccodes if rates else None,
+                                len(cl), lcodes if cl else None, int(rot)),
+                    behind=(ferr.ctypes.data if rates else None, lerr.ctypes.data if cl else None,
+                            None if sb is None else sb.ctypes.data))
+    dec, sym = _tracking_decisions(st, syms, frames, prepared[4], pil, tps)
+    if out is not None:
+        if out.decisions.shape != dec.shape:
+            raise ValueError("out has another shape")
+        dec, sym = out.decisions + dec, out.decisions_sym + sym
+    prof = _coset_result(_tracking_result(res, sc, dec, sym), ferr, lerr, steps, W, K, frames, rates, cl, llr_scale, rot, sb)
+    if out is not None:
+        prof = prof._replace(**{f: getattr(out, f) + getattr(prof, f) for f in (
+            "info_err", "cw_err", "codewords", "ldpc_info_err", "ldpc_cw_err", "unconverged", "iterations", "ldpc_codewords")})
+    return prof
+
+
+def _coset_views(prof):
+    """``prof`` as an ``RxProfileCodedFrame`` and an ``RxProfileLdpc``, for their rate functions"""
+    n = len(RxProfileTracking._fields)
+    return (RxProfileCodedFrame(*prof[:n], prof.info_err, prof.cw_err, prof.info_bits, prof.codewords, prof.rates, prof.llr_scale,
+                                prof.sym_rot, None),
+            RxProfileLdpc(*prof[:n], prof.ldpc_info_err, prof.ldpc_cw_err, prof.unconverged, prof.iterations, prof.ldpc_info_bits,
+                          prof.ldpc_codewords, prof.ldpc_codes, prof.llr_scale, prof.sym_rot, None))
+
+
+def coset_ber(prof):
+    """(Viterbi, LDPC): the decoded info-bit error rates against the transmitted words, [points, pairs, n_snr, n_ch, codes] each, as
+    ``coded_frame_ber`` and ``ldpc_ber`` form them"""
+    vit, ldpc = _coset_views(prof)
+    return coded_frame_ber(vit), ldpc_ber(ldpc)
+
+
+def coset_fer(prof):
+    """(Viterbi, LDPC): the codeword error rates, as ``coded_fer`` and ``ldpc_fer`` form them"""
+    vit, ldpc = _coset_views(prof)
+    return coded_fer(vit), ldpc_fer(ldpc)
