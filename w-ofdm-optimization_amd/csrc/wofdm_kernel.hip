@@ -560,6 +560,66 @@ __device__ __forceinline__ philox_out stream_block(uint32_t block, uint32_t f_lo
     return o;
 }
 
+// Rounds 1 ... 3 of a block of the frame kernels' streams for the kernels with a built geometry (the rest: philox_round).  Counter
+// words 1 ... 3 and the key are wave-uniform, so half of rounds 1 and 2 is: M1 f_hi, its XOR with f_lo and the key, round 2's M0
+// times that.  Written with v_bitop3_b32 -- which has no scalar form -- that uniform chain ran on the VECTOR pipe, per draw: the XOR
+// with two moves for the second and third scalar operand of a VOP3, round 2's product as v_mul_lo_u32 + v_mul_hi_u32 (quarter rate),
+// and in the noise tiles a copy of round 2's uniform word per tile, because the tile's dependency ties took it as a vector register.
+// Here it is plain integer arithmetic on scalars, and a per-lane XOR meets its two uniform operands already XORed on the scalar
+// unit.  The same ten rounds, bit for bit.
+//   p0 = M0 x block: the caller's product -- the noise tiles form it as ONE multiply-add, M0 x (the lane's part of the block) + M0 x
+//   (the tile's wave-uniform part), the addend stepped on the scalar unit.
+// philox_head2: rounds 1, 2; leaves c0, c1, c2 per lane and round 2's uniform word c3u.  philox_round3: round 3, the last one that
+// meets it.
+#define WOFDM_PHILOX_M0 0xD2511F53u
+#define WOFDM_PHILOX_M1 0xCD9E8D57u
+__device__ __forceinline__ void philox_head2(uint64_t p0, uint32_t f_lo, uint32_t f_hi, uint32_t stream_cell, uint32_t &k0, uint32_t &k1,
+                                             uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3u)
+{
+    const uint64_t u1 = (uint64_t)WOFDM_PHILOX_M1 * f_hi;                       // uniform
+    const uint32_t um0 = (uint32_t)(u1 >> 32) ^ f_lo ^ k0;                      // uniform: round 1's new c0
+    const uint32_t m2 = (uint32_t)(p0 >> 32) ^ (stream_cell ^ k1);              // round 1's new c2
+    const uint32_t c3a = (uint32_t)p0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    const uint64_t u0 = (uint64_t)WOFDM_PHILOX_M0 * um0;                        // uniform
+    const uint64_t p1 = (uint64_t)WOFDM_PHILOX_M1 * m2;
+    c0 = (uint32_t)(p1 >> 32) ^ ((uint32_t)u1 ^ k0);
+    c2 = c3a ^ ((uint32_t)(u0 >> 32) ^ k1);
+    c1 = (uint32_t)p1;
+    c3u = (uint32_t)u0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+}
+__device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t &k0, uint32_t &k1)
+{
+    const uint64_t p0 = (uint64_t)WOFDM_PHILOX_M0 * c0;
+    const uint64_t p1 = (uint64_t)WOFDM_PHILOX_M1 * c2;
+    const uint32_t m0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
+    const uint32_t m2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96);
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = m0; c2 = m2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+}
+__device__ __forceinline__ void philox_round3(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t c3u, uint32_t &k0, uint32_t &k1)
+{
+    const uint64_t p0 = (uint64_t)WOFDM_PHILOX_M0 * c0;
+    const uint64_t p1 = (uint64_t)WOFDM_PHILOX_M1 * c2;
+    const uint32_t m0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
+    const uint32_t m2 = (uint32_t)(p0 >> 32) ^ (c3u ^ k1);
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = m0; c2 = m2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+}
+// a whole block that way (p0 as above)
+__device__ __forceinline__ philox_out stream_block_geo(uint64_t p0, uint32_t f_lo, uint32_t f_hi, uint32_t stream_cell, uint32_t k0, uint32_t k1)
+{
+    uint32_t c0, c1, c2, c3, c3u;
+    philox_head2(p0, f_lo, f_hi, stream_cell, k0, k1, c0, c1, c2, c3u);
+    philox_round3(c0, c1, c2, c3, c3u, k0, k1);
+#pragma unroll
+    for (int r = 3; r < 10; ++r) philox_round(c0, c1, c2, c3, k0, k1);
+    philox_out o;
+    o.w[0] = c0; o.w[1] = c1; o.w[2] = c2; o.w[3] = c3;
+    return o;
+}
+
 // Sum over the 64 lanes without LDS round trips: four DPP steps give every lane its 16-lane
 // row sum, the four row sums are then read as scalars.  (The reduction sits on the critical path
 // in front of barrier 2; ds_bpermute shuffles cost six dependent LDS latencies there.)
@@ -1003,6 +1063,30 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
     unsigned long long stamp_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long stamp_t = __builtin_amdgcn_s_memtime();
 #endif
+    // Kernels with a built geometry: lane constants of the Philox draws, made once per kernel and opaque, so that they stay in their
+    // three registers across the frame loop (philox_head2).  nz_p0 = M0 x (the lane's part of a tile's noise block: samples 8 ln +
+    // 2 lg, + 1 of the tile are block 4 ln + lg of it) -- a tile adds M0 x (its wave-uniform part) to it, one 64-bit add with a
+    // scalar operand; m0v = the multiplier M0 for the data bits' block, whose lane part is the (per frame opaque) lane index itself:
+    // a VOP3 takes ONE scalar operand, so with the 64-bit addend in scalar registers the multiplier has to be a vector register.
+    uint64_t nz_p0 = (uint64_t)WOFDM_PHILOX_M0 * (4u * ((uint32_t)lane0 & 15u) + ((uint32_t)lane0 >> 4));
+    uint32_t m0v = WOFDM_PHILOX_M0;
+    if constexpr (GEO > 0) asm volatile("" : "+v"(nz_p0), "+v"(m0v));
+    (void)nz_p0; (void)m0v;
+    // ... and three lane offsets that every frame rebuilt from the lane index with divisions and multiplies (all layouts of the
+    // table are quarter-wave, both transforms on the matrix pipe):
+    //   lc_bits  word offset, from the wave's first row in plane H, of where the lane parks its block of data bits: block blk of
+    //            symbol slot ub = lane / bps goes to words 4 blk ... of row(ub) (phase A);
+    //   lc_oa    lg B + ln: the sample of the wave's rows whose overlap-add the lane does, symbol lg, sample ln (phase B);
+    //   lc_lane4 4 lane: the lane's word in a 64-word row, in bytes (the Tx write's window and row addresses).
+    uint32_t lc_bits = 0, lc_oa = 0, lc_lane4 = 4u * (uint32_t)lane0;
+    if constexpr (GEO > 0) {
+        static_assert(GEO == 0 || (FIRQ && MDFT && !PART), "the lane constants are those of layouts 10 / 11");
+        const int ub0 = lane0 / bps, blk0 = lane0 % bps;
+        lc_bits = (uint32_t)((ub0 < SPW / 2 ? 0 : gm[WOFDM_G_FBUF]) + (ub0 % (SPW / 2)) * 2 * gm[WOFDM_G_B] + 4 * blk0);
+        lc_oa = (uint32_t)((lane0 >> 4) * gm[WOFDM_G_B] + (lane0 & 15));
+        asm volatile("" : "+v"(lc_bits), "+v"(lc_oa), "+v"(lc_lane4));
+    }
+    (void)lc_bits; (void)lc_oa; (void)lc_lane4;
     for (;;) {                                      // the workgroup's runs: the static one, then chunk by chunk (not indented)
     if constexpr (DYN) seek(item, ws_get(WS_CELL0)); else seek(item, p.first_cell);
     for (; n_items != 0; --n_items) {
@@ -1038,6 +1122,9 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         // of every stage is hoisted out of the frame loop and the kernel spills ~1500 VGPRs.
         lane = lane0;
         asm volatile("" : "+v"(lane));
+        // (built geometries: the opaque copy keeps its range -- lane / 8, lane % 8, lane >> 4 and the scaled lane indices of the
+        // phases come out as one shift, mask or 24-bit multiply each instead of signed-division sequences and 32-bit multiplies)
+        if constexpr (GEO > 0) __builtin_assume((unsigned)lane < 64u);
         ++iter;
         float *sums_it = sums + 32 * (iter & 1);
         const uint64_t frame = p.frame_offset + fidx;
@@ -1077,7 +1164,9 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         };
         auto mdft_load = [&](const mdft_early &e) {
             mdft_consts c;
-            const u4 *dl = reinterpret_cast<const u4 *>(smem + L::off_tw) + lane;
+            // (built geometries: 16 lane from the lane constant -- beside a 4 lane address of the same phase the compiler formed one of
+            // the two as the other + 12 lane, a multiply per phase)
+            const u4 *dl = GEO > 0 ? reinterpret_cast<const u4 *>(smem + L::off_tw + 4u * lc_lane4) : reinterpret_cast<const u4 *>(smem + L::off_tw) + lane;
             c.brh = __builtin_bit_cast(h8, dl[0]); c.brl = __builtin_bit_cast(h8, dl[64]);
             c.bih = __builtin_bit_cast(h8, dl[128]); c.bil = __builtin_bit_cast(h8, dl[192]);
             c.twr = __builtin_bit_cast(f4, dl[256]); c.twi = __builtin_bit_cast(f4, dl[320]);
@@ -1170,11 +1259,25 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
             // Philox words of the wave's symbols, staged in the (still unused) frame slices
             if (lane < SPW * bps && (!PART || lane / bps < nreal)) {
                 const int ub = lane / bps, blk = lane % bps;
-                const philox_out o = stream_block((uint32_t)((s0 + ub) * bps + blk), f_lo, f_hi,
-                                                  (WOFDM_STREAM_BITS << 28) | cell, seed_lo, seed_hi);
+                philox_out o;
+                if constexpr (GEO > 0) {
+                    // (block (s0 + ub) bps + blk = s0 bps + lane: the lane's part and the wave's as one multiply-add)
+                    uint32_t kb0 = seed_lo, kb1 = seed_hi;
+                    asm volatile("" : "+s"(kb0), "+s"(kb1));
+                    o = stream_block_geo((uint64_t)m0v * (uint32_t)lane + (uint64_t)WOFDM_PHILOX_M0 * (uint32_t)(s0 * bps), f_lo, f_hi,
+                                         (WOFDM_STREAM_BITS << 28) | cell, kb0, kb1);
+                } else
+                o = stream_block((uint32_t)((s0 + ub) * bps + blk), f_lo, f_hi,
+                                 (WOFDM_STREAM_BITS << 28) | cell, seed_lo, seed_hi);
+                if constexpr (GEO > 0) {
+                    uint32_t *bw = Hp + (PRE + s0 * B) + lc_bits;           // (row(ub) + 4 blk: the lane constant lc_bits)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) bw[i] = o.w[i];
+                } else {
                 uint32_t *bw = reinterpret_cast<uint32_t *>(row(ub));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) bw[4 * blk + i] = o.w[i];
+                }
             }
             wave_sync();
         }
@@ -1772,8 +1875,11 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
             // prefix / suffix copy does not depend on the symbol: ONE exec-masked region per element for all four symbols.
             const bool body_tail = rho < gq[WOFDM_G_BETA];
             const int i0 = lane + mu;                               // position of element 0 in its symbol's row
-            uint32_t *pH0 = Hp + PRE + s0 * B + i0;
-            const float *pW = wtx + i0;
+            // (built geometries: both addresses from the lane constant lc_lane4 -- from the lane index they came out as "16 lane, the
+            // address of the operand rows, - 12 lane", a multiply per frame)
+            uint32_t *pH0 = GEO > 0 ? reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(Hp) + lc_lane4) + (PRE + s0 * B + mu)
+                                    : Hp + PRE + s0 * B + i0;
+            const float *pW = GEO > 0 ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(wtx) + lc_lane4) + mu : wtx + i0;
             // word offsets from a row's position to the same position of its fall tail (the last symbol of the frame has
             // no successor: its tail stays in the frame buffer)
             int dtH[4], dtL[4];
@@ -2215,7 +2321,8 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
             for (int sb = 0; sb < SPW; sb += 4) {              // (sixteen lanes per symbol, four symbols at a time)
                 const int s = s0 + sb + lg;
                 if (s > 0 && ln < beta && (!PART || sb + lg < nreal)) {
-                    const int idx = PRE + s * B + ln, it = (s - 1) * beta + ln;
+                    // (built geometries: s B + ln from the lane constant lc_oa -- SPW = 4: one pass, sb = 0)
+                    const int idx = GEO > 0 ? PRE + s0 * B + (int)lc_oa : PRE + s * B + ln, it = (s - 1) * beta + ln;
                     uint32_t hi, lo;
                     split_h(join_h(Hp[idx], Lp[idx]) + join_h(tH[it], tL[it]), hi, lo);
                     Hp[idx] = hi;
@@ -2416,6 +2523,8 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
         constexpr bool PREFETCH = true;
         bops bq;
         if constexpr (PREFETCH) bq = fir_load(jw, 0, false);
+        uint64_t ua = (uint64_t)WOFDM_PHILOX_M0 * (uint32_t)(jw >> 1);      // (built geometries: the wave's part of round 1's product)
+        (void)ua;
 #pragma unroll
         for (int G = 0; G < NT; ++G) {
             const int jr = 128 * G + jl;
@@ -2475,15 +2584,37 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                 // its MFMA: tests/test_code_layout.py caught it).  Each TIE is an empty volatile asm statement through which
                 // the chain's accumulator AND the Philox words pass: what produces its inputs comes before it, what consumes
                 // its outputs after it, and volatile statements keep their order.
-                asm volatile("" : "+v"(o.h0), "+v"(c0));                                   // (the tile starts here)
 #define WOFDM_TIE() asm volatile("" : "+v"(d), "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3))
                 const f4 z = {0.f, 0.f, 0.f, 0.f};
+                if constexpr (GEO > 0) {
+                    // Built geometries (philox_head2): the tile's block is (jw + 128 G + jl) >> 1 = (jl >> 1) + (jw >> 1) + 64 G -- jw and
+                    // 128 G are even --, so round 1's product is nz_p0 + M0 x ((jw >> 1) + 64 G): the lane constant plus a wave-uniform
+                    // 64-bit addend from the scalar unit, ONE vector instruction where the tile had an add, a shift and the multiply-add
+                    // (the block stays below 2^13: nothing is carried out of the 64 bits).  The addend passes through the statement
+                    // that starts the tile, so the sum stays behind it; round 2's uniform word stays out of the ties -- through them
+                    // it was copied into a vector register in every tile.
+                    static_assert(SPW % 2 == 0, "a wave's first sample is an even one");
+                    // (ua: M0 x (jw >> 1) in front of tile 0, stepped by M0 x 64 per tile THROUGH the opaque statement -- one pair of
+                    // scalar registers; computed per tile from G the nine addends were all made ahead and held, 18 registers)
+                    uint32_t c3u;
+                    asm volatile("" : "+v"(o.h0), "+s"(ua));                                 // (the tile starts here)
+                    d = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[1], o.h0, z, 0, 0, 0);
+                    philox_head2(nz_p0 + ua, f_lo, f_hi, c3, k0, k1, c0, c1, c2, c3u);
+                    ua += (uint64_t)WOFDM_PHILOX_M0 * 64u;
+                    asm volatile("" : "+v"(d), "+v"(c0), "+v"(c1), "+v"(c2));
+                    d = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[3], o.h1, d, 0, 0, 0);
+                    philox_round3(c0, c1, c2, c3, c3u, k0, k1);
+                    philox_round(c0, c1, c2, c3, k0, k1);
+                    WOFDM_TIE();
+                } else {
+                asm volatile("" : "+v"(o.h0), "+v"(c0));                                   // (the tile starts here)
                 d = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[1], o.h0, z, 0, 0, 0);
                 rounds2();
                 WOFDM_TIE();
                 d = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[3], o.h1, d, 0, 0, 0);
                 rounds2();
                 WOFDM_TIE();
+                }
                 d = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[0], o.l0, d, 0, 0, 0);
                 rounds2();
                 WOFDM_TIE();
@@ -2577,6 +2708,14 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
             const int jt = S * B;
             const bool v0 = jl < tail_total, v1 = jl + 1 < tail_total;
             v2f n0, n1;
+            if constexpr (GEO > 0) {
+                // (as in the tiles: block (jt + jl) >> 1 = (jl >> 1) + (jt >> 1), jt = S B even in every row of the table)
+                static_assert((wofdm_geo_row_of(GEO).S * wofdm_geo_row_of(GEO).B & 1) == 0, "the trailing samples start on an even one");
+                const philox_out o = stream_block_geo(nz_p0 + (uint64_t)WOFDM_PHILOX_M0 * (uint32_t)(jt >> 1), f_lo, f_hi,
+                                                      (WOFDM_STREAM_NOISE << 28) | cell, key0, key1);
+                n0 = box_muller<false>(o.w[0], o.w[1]);
+                n1 = box_muller<false>(o.w[2], o.w[3]);
+            } else
             noise_pair(jt + jl, v0, v1, n0, n1);
             const f4 d = fir_mma(fir_load(jt, 0, true));
             const v2f c0 = mk(d.x, d.y), c1 = mk(d.z, d.w);
@@ -3152,6 +3291,11 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                 // swizzled rows (see the noise-scaling stores above): element r of symbol u is sample x + 64 r of the chunk of its
                 // plane, x = (u % 2) B + gamma + lane; 64 samples on leave the XOR term alone -- one per-lane base per symbol, the
                 // elements (and the folded partner, N samples on) at instruction offsets as before
+                // (pr0: element 0's product before the fold -- the incomplete last group below adds its own fold to the SAME product; the
+                // source forms it a second time there and the generic kernels' compiler merges the two; in the kernels with a built
+                // geometry, whose lane index has a range, it stopped doing so for layout 11 and the static multiset of
+                // tests/test_arith_multiset.py moved: they take the product from here)
+                v2f pr0[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const v2f *cb = reinterpret_cast<const v2f *>(Hp + (u < 2 ? 0 : plen) + PRE + s0 * B);
@@ -3159,6 +3303,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                     const float *wr = wrx + lane;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[u][0][r] = fe[64 * r] * wr[64 * r];
+                    pr0[u] = v[u][0][0];
                     if (delta > 0) {
                         if (lane < delta) {
                             const float w2 = wr[N];
@@ -3178,7 +3323,7 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                         if (delta > 0) {
                             if (lane < delta && x0 + N >= rx_xb) {
                                 const float w2 = wr[N];
-                                v[u][0][0] = __builtin_elementwise_fma(mk(w2, w2), cb[x0 + N], cb[rx_swz(x0)] * wr[0]);
+                                v[u][0][0] = __builtin_elementwise_fma(mk(w2, w2), cb[x0 + N], GEO > 0 ? pr0[u] : cb[rx_swz(x0)] * wr[0]);
                             }
                         }
                     }
@@ -3243,9 +3388,16 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
                 gr[j] = (x0r * y0r + x0i * y0i) * inv;                 // X0 conj(Y0) / |Y0|^2
                 gi[j] = (x0i * y0r - x0r * y0i) * inv;
             }
+            // (built geometries: 16 lane from the lane constant, see mdft_load)
+            if constexpr (GEO > 0) {
+                f4 *G4 = reinterpret_cast<f4 *>(smem + L::off_g + 4u * lc_lane4);
+                G4[0] = gr;
+                G4[64] = gi;
+            } else {
             f4 *G4 = reinterpret_cast<f4 *>(G);
             G4[lane] = gr;
             G4[64 + lane] = gi;
+            }
             if constexpr (RELAXF) {
                 wave_sync();
                 post_flag(&flags[16], iter, lane);
@@ -3464,7 +3616,11 @@ wofdm_frames_kernel(const wofdm_kparams p, const float *__restrict__ g_wtx,
             }
         }
         f4 g4r = {0.f, 0.f, 0.f, 0.f}, g4i = g4r;
-        if constexpr (MDFT) {
+        if constexpr (MDFT && GEO > 0) {
+            const f4 *G4 = reinterpret_cast<const f4 *>(smem + L::off_g + 4u * lc_lane4);
+            g4r = G4[0];
+            g4i = G4[64];
+        } else if constexpr (MDFT) {
             g4r = reinterpret_cast<const f4 *>(G)[lane];
             g4i = reinterpret_cast<const f4 *>(G)[64 + lane];
         }
