@@ -1284,6 +1284,101 @@ int wofdm_rx_profile_coset(const wofdm_cfg *cfg, int device,
                            uint64_t *ldpc_errs,           /* [n_points][cells][n_ldpc][4], ACCUMULATED into; NULL where n_ldpc = 0 */
                            int8_t *soft_bits);            /* [cells][frames][n_points][S-1][n_fft][8], or NULL */
 
+/* Retransmissions with soft combining (HARQ, hybrid automatic repeat request): a word that does not decode is sent again, and the
+ * receiver combines the attempts before it decodes.  The LDPC decoder's syndrome stop rule is the ACK.
+ *   Groups.  rounds = R, 1 <= R <= WOFDM_HARQ_MAX_ROUNDS.  The frames of a cell are taken in groups of R consecutive GLOBAL frame
+ * indices g R ... g R + R - 1; frames_per_cell and frame_offset must both be multiples of R.  Frame g R + r is transmission r + 1
+ * of the group's words.  Every frame is exactly the frame every other entry point runs -- labels, noise, walk and channel of the
+ * cell --: not a single frame changes.
+ *   Transmitted word.  The group's information stream is wofdm_coset_info's of (seed, cell, frame g R), the group's FIRST frame;
+ * LDPC word w of a code is formed from it exactly as in wofdm_rx_profile_coset (W, n, Z, K and the shortening unchanged), and
+ * every transmission of the group carries the same x.  Transmission r reaches the decoder as d'_r[c] = x_c ? -d_r[c] : d_r[c], d_r
+ * the soft bits of frame g R + r behind the frame interleaver.
+ *   Decoder input at round r (0-based), formed in int32: combine = 1 (Chase combining) q[c] = clamp(sum over j <= r of d'_j[c],
+ * -127, 127); combine = 0 (plain ARQ) q[c] = clamp(d'_r[c], -127, 127).  Shortened positions are 127.  The clamp keeps the
+ * decoder's |Q| <= 128 + 6 * 95: there is still no saturation rule.
+ *   Rounds.  Each round starts the decoder of wofdm_ldpc_decode afresh -- Q = q, R = 0 on every edge --, with up to max_iter
+ * iterations.  The first round that converges (even syndrome) is the ACK: the word stops there and ignores its later frames.  A
+ * word that never converges stops after round R with that round's decisions.
+ *   The Viterbi codes are out of scope: without a CRC that decoder has no stop rule, so it cannot tell an ACK.
+ *   Counters.  harq_errs[point][cell][code][WOFDM_HARQ_FIELDS], ACCUMULATED into: [0 ... 7] the words ACKed at round 1 ... 8
+ * (entries >= R stay 0); [8] the words never ACKed; [9] the words with a wrong information bit at the stop (x[v] != the
+ * transmitted x[v] on J Z <= v < n); [10] of those, the ACKed ones -- undetected errors --; [11] the information-bit errors at
+ * the stop; [12] the iterations run over all rounds. */
+#define WOFDM_HARQ_MAX_ROUNDS 8
+#define WOFDM_HARQ_FIELDS 13
+
+/* The combining decoder alone, with no flipping: the caller's soft bits are the d'.  Word w has the rows soft[w][0 ... rounds - 1],
+ * variable c of row r read at soft[w][r][perm[c]] (NULL perm: the identity).  bits[w][v] = x[v] at the stop, round[w] the 1-based
+ * stop round, iters[w] the iterations over all rounds, converged[w] 0 / 1; round, iters and converged may be NULL.
+ *   Checks, all before the device is touched, in wofdm_ldpc_decode's order with rounds and combine behind max_iter:
+ * WOFDM_E_INVALID for NULL soft or bits; J, L; max_iter; rounds outside 1 ... WOFDM_HARQ_MAX_ROUNDS; combine outside {0, 1}; n or
+ * n_cw < 1; WOFDM_E_UNSUPPORTED for n > WOFDM_LDPC_MAX_BITS; WOFDM_E_INVALID for K < 1; WOFDM_E_UNSUPPORTED for a decoder state
+ * beyond a workgroup's LDS (the guard of wofdm_rx_profile_coset, the word's bits included); WOFDM_E_INVALID for a perm that is no
+ * permutation.  A failed check leaves the outputs as they were.  The call holds the launch gate while its kernel runs; it
+ * neither counts for nor resets wofdm_rx_profile_kernel_ms. */
+int wofdm_ldpc_harq_decode(int device, int32_t J, int32_t L, int32_t max_iter, int32_t n,
+                           const int32_t *perm,             /* [n], or NULL */
+                           int32_t n_cw, int32_t rounds, int32_t combine,
+                           const int8_t *soft,              /* [n_cw][rounds][n] */
+                           uint8_t *bits,                   /* [n_cw][n] */
+                           int32_t *round,                  /* [n_cw], or NULL */
+                           int32_t *iters,                  /* [n_cw], or NULL */
+                           uint8_t *converged);             /* [n_cw], or NULL */
+
+/* The coded link with retransmissions, on wofdm_rx_profile_coset's frames: the scheme above on the soft bits of every group.
+ *   Arguments: every argument of wofdm_rx_profile_coset through perm; n_ldpc (1 ... WOFDM_CODE_MAX) ldpc_codes; sym_rot; rounds;
+ * combine; the seven outputs of wofdm_rx_profile_tracking; harq_errs; soft_bits.  The tracking outputs and the exported soft bits
+ * are the bytes of wofdm_rx_profile_coded_frame over all frames: the receive chain runs every frame, ACKed or not.
+ *   wofdm_ldpc_harq_kernel: one workgroup per (group, point, word of the frame) and launch per code; LDS as the coset LDPC
+ * decoder's, the word drawn and encoded once; each round re-forms q from the r + 1 rows of soft bits in device memory -- no
+ * running sum is kept in LDS --, and the ACK is the workgroup's OR.
+ *   Identities, by bytes: harq_errs depends neither on where a chunk ends, nor on the other points or codes of the call, nor on
+ * whether soft_bits is requested; repeated calls are identical; a call over frames split at a multiple of R adds up to the call
+ * over all; it equals wofdm_ldpc_harq_decode on the exported soft bits gathered through the frame interleaver and flipped by the
+ * transmitted words of each group's first frame; with R = 1 and ldpc_errs = wofdm_rx_profile_coset's, [0] = words - ldpc_errs[2],
+ * [8] = ldpc_errs[2], [9] = ldpc_errs[1], [11] = ldpc_errs[0], [12] = ldpc_errs[3].
+ *   Checks, in this order: wofdm_rx_profile_coded_frame's through perm and the size of soft_bits, then WOFDM_E_INVALID for n_ldpc <
+ * 0; WOFDM_E_UNSUPPORTED for n_ldpc > WOFDM_CODE_MAX; WOFDM_E_INVALID for n_ldpc = 0; for NULL ldpc_codes; for sym_rot outside
+ * [0, n_c); for NULL harq_errs; for rounds outside 1 ... WOFDM_HARQ_MAX_ROUNDS; for combine outside {0, 1}; for a frames_per_cell,
+ * then a frame_offset, that is no multiple of rounds; then the LDPC codes as wofdm_rx_profile_coset checks them.  Every argument
+ * is checked before the device is touched; a failed check leaves all outputs as they were.
+ *   Chunks: wofdm_rx_profile_ldpc's formula rounded down to a multiple of R, and R where that would be 0: a group never
+ * straddles a chunk.
+ *   A successful call holds the launch gate and counts for wofdm_rx_profile_kernel_ms.
+ *   Measured: tools/bench_rx_profile_harq.py, profiles/rx_profile_harq.txt. */
+int wofdm_rx_profile_harq(const wofdm_cfg *cfg, int device,
+                          const float *w_tx,             /* [pairs][P] */
+                          const float *w_rx,             /* [pairs][N+tail_rx] */
+                          const float *h,                /* [n_channels][n_taps][2] */
+                          const float *snr_db,           /* [n_snr] */
+                          const uint8_t *active,         /* [n_fft] or NULL */
+                          const float *tx_mask,          /* [2P-1] or NULL */
+                          const float *h_track,          /* [n_tracks][n_channels][n_knots][n_taps][2], or NULL */
+                          int32_t n_tracks, int32_t n_knots, int32_t knot_step,
+                          const uint8_t *aci_active,     /* [n_fft], or NULL */
+                          const float *aci_h,            /* [n_channels][n_taps][2], or NULL = h */
+                          const float *ref_power,        /* [pairs], or NULL */
+                          int32_t n_points, const wofdm_link_point *points,
+                          int32_t n_scales, const float *scales,
+                          const uint8_t *pilots,         /* [n_fft], or NULL */
+                          const wofdm_tracking_point *tracking, /* [n_points] */
+                          float llr_scale,
+                          const int32_t *perm,           /* [n_c], or NULL */
+                          int32_t n_ldpc, const wofdm_ldpc_code *ldpc_codes,
+                          int32_t sym_rot,               /* in [0, n_c) */
+                          int32_t rounds,                /* 1 ... WOFDM_HARQ_MAX_ROUNDS */
+                          int32_t combine,               /* 1: Chase combining, 0: plain ARQ */
+                          uint64_t *errs,                /* [n_points][cells][n_fft][2], ACCUMULATED into */
+                          double *err_power,             /* [n_points][cells][n_fft], or NULL */
+                          uint64_t *sym_errs,            /* [n_points][cells][S-1][2], or NULL */
+                          double *sym_power,             /* [n_points][cells][S-1], or NULL */
+                          double *pa_power,              /* [n_points][cells][2], or NULL */
+                          double *bit_penalty,           /* [n_points][cells][n_scales][n_fft], ACCUMULATED into */
+                          double *sym_penalty,           /* [n_points][cells][n_scales][S-1], or NULL */
+                          uint64_t *harq_errs,           /* [n_points][cells][n_ldpc][WOFDM_HARQ_FIELDS], ACCUMULATED into */
+                          int8_t *soft_bits);            /* [cells][frames][n_points][S-1][n_fft][8], or NULL */
+
 /* Philox4x32-10 known-answer hook (runs one block on the GPU). */
 int wofdm_philox_kat(int device, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

@@ -24,7 +24,8 @@ as ``wofdm_amd`` through the shim module at the repository root.
                wofdm_rx_profile_coded_frame, wofdm_viterbi_decode_long), or with a quasi-cyclic LDPC code and a layered min-sum
                decoder over the frame (GPU: wofdm_rx_profile_ldpc, wofdm_ldpc_decode), or both decoders on random information
                words encoded on the GPU in the place of the all-zero word (GPU: wofdm_rx_profile_coset, wofdm_conv_encode,
-               wofdm_ldpc_encode)
+               wofdm_ldpc_encode), or with retransmissions of the LDPC words and soft combining, up to the goodput per on-air
+               sample (GPU: wofdm_rx_profile_harq, wofdm_ldpc_harq_decode)
   _lib         ctypes binding of libwofdm_hip.so (include/wofdm.h)
 """
 from . import variants  # noqa: F401
@@ -43,7 +44,7 @@ from .simulation import (Plan, ber_for_window_file, error_rates, make_cfg,  # no
 from ._lib import kernel_source_hash  # noqa: F401
 from .timefreq import (estimate_obr, frame_papr, papr_ccdf, papr_hist, run_timefreq, tx_papr_gpu,  # noqa: F401
                        tx_psd_batch_gpu, tx_waveform)
-from .channel_mask import (aci_for_window_file, coded_for_window_file, coded_frame_for_window_file, coset_for_window_file, doppler_for_window_file, interference_for_window_file,  # noqa: F401
+from .channel_mask import (aci_for_window_file, coded_for_window_file, coded_frame_for_window_file, coset_for_window_file, doppler_for_window_file, harq_for_window_file, interference_for_window_file,  # noqa: F401
                            ldpc_for_window_file,
                            link_for_window_file, soft_for_window_file, pa_for_window_file, papr_for_window_file, pn_for_window_file, profile_for_window_file,
                            spectrum_for_window_file, sync_for_window_file, tracking_for_window_file)
@@ -73,7 +74,10 @@ from .rx_profile import (RxProfile, RxProfileSync, SyncPoint, ber_per_bin, evm_d
                          rx_profile_ldpc_chunk_frames, rx_profile_ldpc_gpu, rx_profile_ldpc_host,
                          STREAM_INFO, RxProfileCoset, conv_encode_gpu, coset_ber, coset_codewords, coset_fer, coset_info,
                          frame_profile_coset, ldpc_encode_gpu, rx_profile_coset_chunk_frames, rx_profile_coset_gpu,
-                         rx_profile_coset_host)
+                         rx_profile_coset_host,
+                         RxProfileHarq, harq_acked, harq_bits_per_sample, harq_goodput, harq_mean_transmissions, harq_residual_fer,
+                         harq_undetected, ldpc_harq_decode, ldpc_harq_decode_gpu, rx_profile_harq_chunk_frames, rx_profile_harq_gpu,
+                         rx_profile_harq_host)
 from .variants import (SYSTEMS, Structure, calculate_parameters, expand_rx_window,  # noqa: F401
                        expand_tx_window, make_structure, rx_rc_window, tx_rc_window)
 

@@ -50,6 +50,10 @@ LDPC_MAX_BITS = 16384
 #: wofdm_coset_info, wofdm_rx_profile_coset (csrc/wofdm_link.h): the Philox stream of the information words
 STREAM_INFO = 4
 
+#: wofdm_rx_profile_harq, wofdm_ldpc_harq_decode (include/wofdm.h): most transmissions of a word, counters per code
+HARQ_MAX_ROUNDS = 8
+HARQ_FIELDS = 13
+
 #: every symbol include/wofdm.h declares (tests check the .so exports them all)
 EXPORTS = (
     "wofdm_version", "wofdm_device_count", "wofdm_last_error", "wofdm_noise_len",
@@ -67,6 +71,7 @@ EXPORTS = (
     "wofdm_viterbi_decode_long", "wofdm_rx_profile_coded_frame",
     "wofdm_ldpc_lift", "wofdm_ldpc_decode", "wofdm_rx_profile_ldpc",
     "wofdm_coset_info", "wofdm_conv_encode", "wofdm_ldpc_encode", "wofdm_rx_profile_coset",
+    "wofdm_ldpc_harq_decode", "wofdm_rx_profile_harq",
 )
 
 
@@ -250,6 +255,10 @@ def load():
     L.wofdm_rx_profile_coset.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
                                          C.POINTER(LinkPoint), i32, vp, vp, C.POINTER(TrackingPoint), C.c_float, vp, i32,
                                          C.POINTER(Code), i32, C.POINTER(LdpcCode), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.wofdm_ldpc_harq_decode.argtypes = [C.c_int, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.wofdm_rx_profile_harq.argtypes = [C.POINTER(Cfg), C.c_int, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32,
+                                        C.POINTER(LinkPoint), i32, vp, vp, C.POINTER(TrackingPoint), C.c_float, vp, i32,
+                                        C.POINTER(LdpcCode), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.wofdm_tx_psd_batch_pa.argtypes = [i32, C.c_int, i32, vp, vp, i32, vp, vp, vp, i32, C.POINTER(PaPoint), vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L

@@ -622,6 +622,42 @@ def coset_for_window_file(type_ofdm, cp, windows, channels, snr_db, points=None,
     return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
 
 
+def harq_for_window_file(type_ofdm, cp, windows, channels, snr_db, points=None, tracking=None, pilot_spacing=8, scales=None,
+                         llr_scale=None, interleave=True, ldpc_codes=((4, 8), (4, 12), (4, 16)), sym_rot=None, rounds=4, combine=True,
+                         tracks=None, knot_step=None, aci_channels=None, num_subcar=256, bits_per_subcar=4, symbols_per_tx=16,
+                         ensemble=100, roll_off=ROLL_OFF, seed=0, frame_range=None, gpu=True, device=0, tail_tx=8, tail_rx=10):
+    """``coset_for_window_file``'s pairs, frames, points, comb, receivers, soft bits and frame interleaver with retransmissions: the
+    frames of a cell in groups of ``rounds`` transmissions of the same LDPC words, combined (``combine``) and decoded until the
+    syndrome vanishes; the frames' number and the first frame must be multiples of ``rounds``.  On the GPU two
+    ``wofdm_rx_profile_harq`` calls, plain and masked (gpu=False: ``rx_profile.rx_profile_harq_host``).  Returns {name: {"profile",
+    "profile_masked"}}, each an ``rx_profile.RxProfileHarq`` of that pair, arrays [points, n_snr, n_channels, ...], without soft
+    bits -- ``rx_profile.harq_goodput`` and ``harq_bits_per_sample`` (with ``symbols_per_tx`` and the structure's stride) are the
+    figures the pairs compare by."""
+    from . import rx_profile as R
+    st, plan, w_tx, w_rx, alloc, mask = _window_file_setup(type_ofdm, cp, windows, num_subcar, tail_tx, tail_rx, roll_off)
+    pts = [R.LinkPoint()] if points is None else [R.LinkPoint(*q) for q in points]
+    first, count = _frames(ensemble, frame_range)
+    ref = [None, None]
+    if any(q.pa is not None for q in pts):
+        ref = [R.pa_ref_power(st, bits_per_subcar, symbols_per_tx, w_tx, seed, first, count, active=alloc, mask=m, gpu=gpu,
+                              **(dict(device=device) if gpu else {})) for m in (None, mask)]
+    pil = None if pilot_spacing is None else R.pilot_comb(alloc, pilot_spacing)
+    n_c = int(bits_per_subcar) * int((alloc & ~pil).sum() if pil is not None else alloc.sum())
+    run = R.rx_profile_harq_gpu if gpu else R.rx_profile_harq_host
+    side = dict(tracks=tracks, knot_step=knot_step, aci_active=~alloc if any(q.aci is not None for q in pts) else None,
+                aci_h=aci_channels, active=alloc, **(dict(device=device) if gpu else {}))
+    head = (st, bits_per_subcar, symbols_per_tx, w_tx, w_rx, np.atleast_2d(np.asarray(channels)), snr_db, seed, first, count, pts,
+            tracking, pil, scales, R.LLR_SCALE if llr_scale is None else llr_scale, R.default_interleaver(n_c) if interleave else None,
+            ldpc_codes, sym_rot, rounds, combine)
+    plain, masked = run(*head, ref_power=ref[0], **side), run(*head, ref_power=ref[1], mask=mask, **side)
+    n = len(R.RxProfileTracking._fields)
+    per_pair = ("acked", "unacked", "word_err", "undetected", "info_err", "iterations")
+
+    def of_pair(prof, i):
+        return prof._replace(**{f: getattr(prof, f)[:, i] for f in prof._fields[:n - 3] + per_pair})
+    return {name: {"profile": of_pair(plain, i), "profile_masked": of_pair(masked, i)} for i, (name, _) in enumerate(plan)}
+
+
 def results_from_counts(names, masked, plain):
     def ber(c):      # mean over channels of per-channel BER (lines 84-117)
         return (c[..., 0] / np.maximum(c[..., 1], 1)).mean(axis=-1)

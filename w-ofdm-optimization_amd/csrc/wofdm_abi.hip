@@ -1701,7 +1701,10 @@ struct rx_call {
     struct {
         bool on; int32_t n_codes; const wofdm_code *codes; int32_t n_ldpc; const wofdm_ldpc_code *ldpc_codes; int32_t sym_rot;
         uint64_t *frame_errs, *ldpc_errs;
+        // wofdm_rx_profile_harq: rounds > 0, no Viterbi code, and ldpc_errs is harq_errs with WOFDM_HARQ_FIELDS counters per code
+        int32_t rounds, combine;
     } coset;
+    bool harq;                        // wofdm_rx_profile_harq (coset is on with it)
 };
 
 // the receive side's geometry beside the Tx chain's, and the cells of the call
@@ -2189,15 +2192,26 @@ int prep_coset(rx_run &r)
 {
     const auto &cs = r.c.coset;
     if (!cs.on) return WOFDM_OK;
+    const bool harq = r.c.harq;
     if (cs.n_codes < 0 || cs.n_ldpc < 0) return fail(WOFDM_E_INVALID, "n_codes=%d and n_ldpc=%d must be >= 0", cs.n_codes, cs.n_ldpc);
     if (cs.n_codes > WOFDM_CODE_MAX || cs.n_ldpc > WOFDM_CODE_MAX)
         return fail(WOFDM_E_UNSUPPORTED, "n_codes=%d or n_ldpc=%d exceeds %d", cs.n_codes, cs.n_ldpc, WOFDM_CODE_MAX);
-    if (cs.n_codes + cs.n_ldpc < 1) return fail(WOFDM_E_INVALID, "n_codes + n_ldpc must be >= 1");
+    if (cs.n_codes + cs.n_ldpc < 1) return fail(WOFDM_E_INVALID, harq ? "n_ldpc must be >= 1" : "n_codes + n_ldpc must be >= 1");
     if ((cs.n_codes > 0 && !cs.codes) || (cs.n_ldpc > 0 && !cs.ldpc_codes)) return fail(WOFDM_E_INVALID, "NULL argument (codes or ldpc_codes)");
     const int32_t n_c = (int32_t)r.gather.size();
     if (cs.sym_rot < 0 || cs.sym_rot >= n_c) return fail(WOFDM_E_INVALID, "sym_rot=%d outside [0, %d)", cs.sym_rot, n_c);
     if ((cs.n_codes > 0 && !cs.frame_errs) || (cs.n_ldpc > 0 && !cs.ldpc_errs))
-        return fail(WOFDM_E_INVALID, "NULL argument (frame_errs or ldpc_errs)");
+        return fail(WOFDM_E_INVALID, harq ? "NULL argument (harq_errs)" : "NULL argument (frame_errs or ldpc_errs)");
+    if (harq) {
+        // wofdm_rx_profile_harq: the rounds, the combining rule, then the groups -- whole groups per cell, on the global frame index
+        if (cs.rounds < 1 || cs.rounds > WOFDM_HARQ_MAX_ROUNDS)
+            return fail(WOFDM_E_INVALID, "rounds=%d must be 1 ... %d", cs.rounds, WOFDM_HARQ_MAX_ROUNDS);
+        if (cs.combine != 0 && cs.combine != 1) return fail(WOFDM_E_INVALID, "combine=%d must be 0 or 1", cs.combine);
+        if (r.c.cfg->frames_per_cell % (uint64_t)cs.rounds != 0)
+            return fail(WOFDM_E_INVALID, "frames_per_cell=%llu is no multiple of rounds=%d", (unsigned long long)r.c.cfg->frames_per_cell, cs.rounds);
+        if (r.c.cfg->frame_offset % (uint64_t)cs.rounds != 0)
+            return fail(WOFDM_E_INVALID, "frame_offset=%llu is no multiple of rounds=%d", (unsigned long long)r.c.cfg->frame_offset, cs.rounds);
+    }
     for (int i = 0; i < cs.n_codes; ++i) {
         const wofdm_code &q = cs.codes[i];
         if (q.rate < 0 || q.rate > 2) return fail(WOFDM_E_INVALID, "codes[%d].rate=%d must be 0, 1 or 2", i, q.rate);
@@ -2483,6 +2497,10 @@ int stage_coset(rx_run &r)
     r.ck.cs_nv = cs.n_codes; r.ck.cs_nl = cs.n_ldpc;
     r.ck.cs = {(uint32_t)r.c.cfg->seed, (uint32_t)(r.c.cfg->seed >> 32), r.c.cfg->frame_offset};
     r.ck.coset_on = true;
+    if (r.c.harq) {
+        r.ck.hq_rounds = cs.rounds;
+        r.ck.hq_combine = cs.combine;
+    }
     return WOFDM_OK;
 }
 
@@ -2537,6 +2555,8 @@ int rx_profile_run(const rx_call &c)
     const uint64_t items = g.cells * g.frames;
     if (items == 0) return WOFDM_OK;
     r.chunk = (size_t)chunk_frames(items, WOFDM_RX_PROFILE_CHUNK_BYTES, rx_job_bytes(r));
+    // (retransmissions: whole groups per chunk -- the formula rounded down to a multiple of the rounds, one group at least)
+    if (c.harq) r.chunk = std::max<size_t>(r.chunk / (size_t)c.coset.rounds, 1) * (size_t)c.coset.rounds;
     pack_channel(r);
     const size_t NP = (size_t)c.n_points, NSC = c.soft.on ? (size_t)c.soft.n_scales : 0;
     r.n_out = NP * g.cells * g.N;
@@ -2550,7 +2570,7 @@ int rx_profile_run(const rx_call &c)
     if (c.frm.on) r.n_cerr = 0;
     if (c.coset.on) {
         r.n_ferr = NP * g.cells * (size_t)c.coset.n_codes * 2;
-        r.n_lerr = NP * g.cells * (size_t)c.coset.n_ldpc * 4;
+        r.n_lerr = NP * g.cells * (size_t)c.coset.n_ldpc * (c.harq ? WOFDM_HARQ_FIELDS : 4);
     }
     if ((rc = stage_base(r)) != WOFDM_OK || (rc = stage_points(r)) != WOFDM_OK || (rc = stage_amp(r)) != WOFDM_OK ||
         (rc = stage_pn(r)) != WOFDM_OK || (rc = stage_link(r)) != WOFDM_OK || (rc = stage_soft(r)) != WOFDM_OK ||
@@ -2752,7 +2772,8 @@ static int rx_tracking_call(const wofdm_cfg *cfg, int device, const float *w_tx,
                             const wofdm_tracking_point *tracking, uint64_t *errs, double *err_power, uint64_t *sym_errs,
                             double *sym_power, double *pa_power, double *bit_penalty, double *sym_penalty,
                             const decltype(rx_call::code) *code, const decltype(rx_call::frm) *frm = nullptr,
-                            const decltype(rx_call::ldpc) *ldpc = nullptr, const decltype(rx_call::coset) *coset = nullptr)
+                            const decltype(rx_call::ldpc) *ldpc = nullptr, const decltype(rx_call::coset) *coset = nullptr,
+                            bool harq = false)
 {
     if (!scales || !bit_penalty || !tracking) return fail(WOFDM_E_INVALID, "NULL argument (scales, bit_penalty or tracking)");
     if (n_scales < 1) return fail(WOFDM_E_INVALID, "n_scales=%d must be >= 1", n_scales);
@@ -2771,6 +2792,7 @@ static int rx_tracking_call(const wofdm_cfg *cfg, int device, const float *w_tx,
     if (frm) c.frm = *frm;
     if (ldpc) c.ldpc = *ldpc;
     if (coset) c.coset = *coset;
+    c.harq = harq;
     const int rc = rx_link_stages(c, n_points, points);
     return rc != WOFDM_OK ? rc : rx_profile_run(c);
 }
@@ -2844,10 +2866,26 @@ int wofdm_rx_profile_coset(const wofdm_cfg *cfg, int device, const float *w_tx, 
                            double *sym_penalty, uint64_t *frame_errs, uint64_t *ldpc_errs, int8_t *soft_bits)
 {
     const decltype(rx_call::code) code = {true, llr_scale, perm, 0, nullptr, nullptr, soft_bits};
-    const decltype(rx_call::coset) coset = {true, n_codes, codes, n_ldpc, ldpc_codes, sym_rot, frame_errs, ldpc_errs};
+    const decltype(rx_call::coset) coset = {true, n_codes, codes, n_ldpc, ldpc_codes, sym_rot, frame_errs, ldpc_errs, 0, 0};
     return rx_tracking_call(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active, aci_h,
                             ref_power, n_points, points, n_scales, scales, pilots, tracking, errs, err_power, sym_errs, sym_power,
                             pa_power, bit_penalty, sym_penalty, &code, nullptr, nullptr, &coset);
+}
+
+int wofdm_rx_profile_harq(const wofdm_cfg *cfg, int device, const float *w_tx, const float *w_rx, const float *h, const float *snr_db,
+                          const uint8_t *active, const float *tx_mask, const float *h_track, int32_t n_tracks, int32_t n_knots,
+                          int32_t knot_step, const uint8_t *aci_active, const float *aci_h, const float *ref_power, int32_t n_points,
+                          const wofdm_link_point *points, int32_t n_scales, const float *scales, const uint8_t *pilots,
+                          const wofdm_tracking_point *tracking, float llr_scale, const int32_t *perm, int32_t n_ldpc,
+                          const wofdm_ldpc_code *ldpc_codes, int32_t sym_rot, int32_t rounds, int32_t combine, uint64_t *errs,
+                          double *err_power, uint64_t *sym_errs, double *sym_power, double *pa_power, double *bit_penalty,
+                          double *sym_penalty, uint64_t *harq_errs, int8_t *soft_bits)
+{
+    const decltype(rx_call::code) code = {true, llr_scale, perm, 0, nullptr, nullptr, soft_bits};
+    const decltype(rx_call::coset) coset = {true, 0, nullptr, n_ldpc, ldpc_codes, sym_rot, nullptr, harq_errs, rounds, combine};
+    return rx_tracking_call(cfg, device, w_tx, w_rx, h, snr_db, active, tx_mask, h_track, n_tracks, n_knots, knot_step, aci_active, aci_h,
+                            ref_power, n_points, points, n_scales, scales, pilots, tracking, errs, err_power, sym_errs, sym_power,
+                            pa_power, bit_penalty, sym_penalty, &code, nullptr, nullptr, &coset, true);
 }
 
 int wofdm_ldpc_lift(int32_t J, int32_t L, int32_t n)
@@ -2996,6 +3034,56 @@ int wofdm_ldpc_decode(int device, int32_t J, int32_t L, int32_t max_iter, int32_
     if (e != hipSuccess || !fetch(hbits, d_bits.p) || !fetch(hiters, d_iters.p) || !fetch(hconv, d_conv.p))
         return fail(WOFDM_E_HIP, "decoder kernel or copy-back failed: %s", hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
     std::memcpy(bits, hbits.data(), n_soft);
+    if (iters) std::memcpy(iters, hiters.data(), hiters.size() * sizeof(int32_t));
+    if (converged) std::memcpy(converged, hconv.data(), hconv.size());
+    return WOFDM_OK;
+}
+
+int wofdm_ldpc_harq_decode(int device, int32_t J, int32_t L, int32_t max_iter, int32_t n, const int32_t *perm, int32_t n_cw, int32_t rounds,
+                           int32_t combine, const int8_t *soft, uint8_t *bits, int32_t *round, int32_t *iters, uint8_t *converged)
+{
+    if (!soft || !bits) return fail(WOFDM_E_INVALID, "NULL argument (soft or bits)");
+    if (!ldpc_ranges_ok(J, L)) return fail(WOFDM_E_INVALID, "J=%d must be 3 ... 6 and L=%d in J + 1 ... 24", J, L);
+    if (max_iter < 1 || max_iter > 64) return fail(WOFDM_E_INVALID, "max_iter=%d must be 1 ... 64", max_iter);
+    if (rounds < 1 || rounds > WOFDM_HARQ_MAX_ROUNDS) return fail(WOFDM_E_INVALID, "rounds=%d must be 1 ... %d", rounds, WOFDM_HARQ_MAX_ROUNDS);
+    if (combine != 0 && combine != 1) return fail(WOFDM_E_INVALID, "combine=%d must be 0 or 1", combine);
+    if (n < 1 || n_cw < 1) return fail(WOFDM_E_INVALID, "n=%d and n_cw=%d must be >= 1", n, n_cw);
+    if (n > WOFDM_LDPC_MAX_BITS) return fail(WOFDM_E_UNSUPPORTED, "n=%d exceeds %d", n, WOFDM_LDPC_MAX_BITS);
+    const int32_t Z = ldpc_lift(J, L, n);
+    if ((int64_t)(L - J) * Z - ((int64_t)L * Z - n) < 1)
+        return fail(WOFDM_E_INVALID, "(%d, %d) over %d positions has no information bit", J, L, n);
+    if (wofdm_ldpc_coset_lds(J, L, Z) > WOFDM_LDPC_LDS_MAX)
+        return fail(WOFDM_E_UNSUPPORTED, "the decoder's LDS exceeds %d bytes", WOFDM_LDPC_LDS_MAX);
+    if (perm && !is_permutation(perm, n)) return fail(WOFDM_E_INVALID, "perm is not a permutation of 0 ... %d", n - 1);
+    int rc = use_device(device);
+    if (rc != WOFDM_OK) return rc;
+    std::vector<int32_t> gather((size_t)n);
+    for (int32_t c = 0; c < n; ++c) gather[(size_t)c] = perm ? perm[c] : c;
+    const size_t n_bits = (size_t)n_cw * (size_t)n, n_soft = n_bits * (size_t)rounds;
+    dev_buf<int8_t> d_soft;
+    dev_buf<int32_t> d_gather, d_iters, d_round;
+    dev_buf<uint8_t> d_bits, d_conv;
+    if (!d_soft.alloc(n_soft) || !d_gather.alloc(gather.size()) || !d_bits.alloc(n_bits) || !d_iters.alloc((size_t)n_cw) ||
+        !d_round.alloc((size_t)n_cw) || !d_conv.alloc((size_t)n_cw))
+        return fail(WOFDM_E_NOMEM, "device allocation failed (decoder)");
+    if (!d_soft.upload(soft, n_soft) || !d_gather.upload(gather.data(), gather.size())) return fail(WOFDM_E_HIP, "upload failed");
+    wofdm_ldpcparams lp{};
+    lp.soft = d_soft; lp.gather[0] = d_gather; lp.n[0] = n; lp.W[0] = 1; lp.Z[0] = Z; lp.J = J; lp.L = L; lp.max_iter = max_iter;
+    lp.cw_stride = n; lp.n_cw = (uint32_t)n_cw; lp.bits = d_bits; lp.iters = d_iters; lp.conv = d_conv;
+    const wofdm_harqparams hq = {rounds, combine, d_round};
+    std::vector<uint8_t> hbits(n_bits), hconv((size_t)n_cw);
+    std::vector<int32_t> hiters((size_t)n_cw), hround((size_t)n_cw);
+    hipError_t e = hipSuccess;
+    {
+        std::lock_guard<std::mutex> gate(g_gate_mu);
+        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the decoder is in every auxiliary unit)
+        e = ax && ax->ldpc_harq ? ax->ldpc_harq(&lp, &hq, nullptr) : hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (e != hipSuccess || !fetch(hbits, d_bits.p) || !fetch(hiters, d_iters.p) || !fetch(hconv, d_conv.p) || !fetch(hround, d_round.p))
+        return fail(WOFDM_E_HIP, "decoder kernel or copy-back failed: %s", hipGetErrorString(e != hipSuccess ? e : hipGetLastError()));
+    std::memcpy(bits, hbits.data(), n_bits);
+    if (round) std::memcpy(round, hround.data(), hround.size() * sizeof(int32_t));
     if (iters) std::memcpy(iters, hiters.data(), hiters.size() * sizeof(int32_t));
     if (converged) std::memcpy(converged, hconv.data(), hconv.size());
     return WOFDM_OK;

@@ -2655,6 +2655,188 @@ __global__ void __launch_bounds__(256) wofdm_ldpc_coset_kernel(const wofdm_ldpcp
     }
 }
 
+// One decode of wofdm_ldpc_kernel on a Q and an R that the caller has filled, behind a barrier: up to max_iter iterations of the J
+// layers and the syndrome, the same statements in the same order.  Returns whether the syndrome vanished -- the workgroup's OR,
+// so the answer, *iters and the barriers are workgroup-uniform -- and leaves behind a barrier: the last statement every thread
+// ran is the __syncthreads_or, after which nobody reads Q or R of this decode any more.
+__device__ __forceinline__ bool ldpc_minsum(int16_t *__restrict__ Q, int8_t *__restrict__ R, const int16_t *__restrict__ sh, int J, int L,
+                                            int Z, int max_iter, int tid, int nt, int *iters)
+{
+    int it = 0;
+    bool conv = false;
+    while (it < max_iter) {
+        int eb = 0;
+        for (int i = 0; i < J; ++i) {
+            const int deg = L - i;
+            const int16_t *__restrict__ si = sh + i * L + i;
+            for (int r = tid; r < Z; r += nt) {
+                int m1 = 255, m2 = 255, par = 0;
+                for (int e = 0; e < deg; ++e) {
+                    int c = r + si[e];
+                    c = c >= Z ? c - Z : c;
+                    const int t = (int)Q[(i + e) * Z + c] - (int)R[(eb + e) * Z + r];
+                    const int a = min(abs(t), 127);
+                    par ^= t < 0 ? 1 : 0;
+                    if (a < m1) {
+                        m2 = m1;
+                        m1 = a;
+                    } else if (a < m2) {
+                        m2 = a;
+                    }
+                }
+                const int g1 = (3 * m1) >> 2, g2 = (3 * m2) >> 2;
+                for (int e = 0; e < deg; ++e) {
+                    int c = r + si[e];
+                    c = c >= Z ? c - Z : c;
+                    const int qi = (i + e) * Z + c, ri = (eb + e) * Z + r;
+                    const int t = (int)Q[qi] - (int)R[ri];
+                    const int a = min(abs(t), 127);
+                    const int mag = a == m1 ? g2 : g1;
+                    const int rn = (par ^ (t < 0 ? 1 : 0)) != 0 ? -mag : mag;
+                    R[ri] = (int8_t)rn;
+                    Q[qi] = (int16_t)(t + rn);
+                }
+            }
+            eb += deg;
+            __syncthreads();
+        }
+        ++it;
+        // the syndrome of the hard decisions
+        int bad = 0;
+        for (int i = 0; i < J; ++i) {
+            const int deg = L - i;
+            const int16_t *__restrict__ si = sh + i * L + i;
+            for (int r = tid; r < Z; r += nt) {
+                int par = 0;
+                for (int e = 0; e < deg; ++e) {
+                    int c = r + si[e];
+                    c = c >= Z ? c - Z : c;
+                    par ^= (int)Q[(i + e) * Z + c] < 0 ? 1 : 0;
+                }
+                bad |= par;
+            }
+        }
+        // (a barrier as well: nobody writes Q for the next layer before everybody has read it)
+        if (__syncthreads_or(bad) == 0) {
+            conv = true;
+            break;
+        }
+    }
+    *iters = it;
+    return conv;
+}
+
+// Retransmissions with soft combining (wofdm_rx_profile_harq, wofdm_ldpc_harq_decode; include/wofdm.h has the scheme): one
+// workgroup per (group, point, word of the frame) and launch per code.  The word is drawn from the information stream of the
+// group's FIRST frame and encoded once, as wofdm_ldpc_coset_kernel does; every round re-forms Q from the rows so far in device
+// memory -- int32 sums of d' = x ? -d : d, clamped to +-127, no running sum in LDS --, zeroes R and decodes afresh (ldpc_minsum).
+// The first round whose syndrome vanishes ends the word; that is the workgroup's OR, so the round loop's trip count and every
+// barrier are workgroup-uniform.  A round's decode leaves behind a barrier, so the next round may write Q and R at once.
+//   The decoder alone (lp.errs null): no word -- the caller's rows are the d' --, the decisions, the stop round, the iterations
+// over all rounds and the ACK go out per word.  LDS: wofdm_ldpc_coset_lds in both uses.
+__global__ void __launch_bounds__(256) wofdm_ldpc_harq_kernel(const wofdm_ldpcparams lp, const wofdm_cosetparams cs,
+                                                              const wofdm_harqparams hq)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const uint64_t w = blockIdx.x;
+    const int wi = blockIdx.y;
+    const bool profile = lp.errs != nullptr;
+    const int rounds = hq.rounds;
+    int v = 0, pt = 0;
+    uint64_t row0 = w * (uint64_t)rounds, row_step = 1, cell = 0, frame = 0;
+    if (profile) {
+        const uint64_t grp = w / (uint64_t)lp.n_points;
+        pt = (int)(w - grp * (uint64_t)lp.n_points);
+        v = lp.pts[pt].post != 0 ? 1 : 0;
+        row_step = (uint64_t)lp.n_points;
+        row0 = grp * (uint64_t)rounds * row_step + (uint64_t)pt;
+        const uint64_t item = lp.item0 + grp * (uint64_t)rounds;
+        cell = item / lp.frames;
+        frame = cs.frame_offset + (item - cell * lp.frames);
+    }
+    if (wi >= lp.W[v]) return;                                          // (workgroup-uniform, before the first barrier)
+    const int J = lp.J, L = lp.L, n = lp.n[v], Z = lp.Z[v], n0 = L * Z, E = J * L - J * (J - 1) / 2;
+    int *__restrict__ cnt = reinterpret_cast<int *>(lsm);
+    int16_t *__restrict__ sh = reinterpret_cast<int16_t *>(lsm + 16);
+    int16_t *__restrict__ Q = reinterpret_cast<int16_t *>(lsm + WOFDM_LDPC_LDS_HEAD);
+    int8_t *__restrict__ R = reinterpret_cast<int8_t *>(lsm + WOFDM_LDPC_LDS_HEAD + ((2 * n0 + 3) & ~3));
+    uint32_t *xb = reinterpret_cast<uint32_t *>(lsm + WOFDM_LDPC_LDS_HEAD + ((2 * n0 + 3) & ~3) + ((E * Z + 3) & ~3));   // (wofdm_ldpc_lds)
+    const int32_t *__restrict__ gather = lp.gather[v] + (size_t)wi * (size_t)n;
+
+    if (tid < 4) cnt[tid] = 0;
+    ldpc_shifts(sh, J, L, Z, tid, nt);
+    // the information bits as in wofdm_ldpc_coset_kernel; the decoder alone keeps the all-zero word, which flips nothing
+    for (int x = tid; x < (n0 + 31) >> 5; x += nt) {
+        const int lo = max(32 * x, J * Z) - 32 * x, hi = min(32 * x + 32, n) - 32 * x;
+        uint32_t wv = 0u;
+        if (profile && lo < hi) {
+            const uint32_t keep = (hi == 32 ? ~0u : (1u << hi) - 1u) & ~((1u << lo) - 1u);
+            wv = coset_bits32(cs, (uint32_t)cell, frame, wi * n + 32 * x - J * Z) & keep;
+        }
+        xb[x] = wv;
+    }
+    __syncthreads();
+    if (profile) ldpc_encode_lds(xb, sh, J, L, Z, tid, nt);               // (workgroup-uniform; ends in a barrier)
+
+    int total = 0, rd = 0;
+    bool conv = false;
+    for (rd = 0; rd < rounds; ++rd) {
+        const int first = hq.combine != 0 ? 0 : rd;
+        for (int x = tid; x < n0; x += nt) {
+            int q = 127;                                                 // (a shortened position is a sure 0 of the word)
+            if (x < n) {
+                const int32_t at = gather[x];
+                const bool flip = ldpc_bit(xb, x) != 0u;
+                q = 0;
+                for (int j = first; j <= rd; ++j) {
+                    const int d = (int)lp.soft[(int64_t)(row0 + (uint64_t)j * row_step) * lp.cw_stride + at];
+                    q += flip ? -d : d;
+                }
+                q = min(max(q, -127), 127);
+            }
+            Q[x] = (int16_t)q;
+        }
+        {
+            uint32_t *__restrict__ R4 = reinterpret_cast<uint32_t *>(R);
+            const int words = (E * Z + 3) >> 2;
+            for (int x = tid; x < words; x += nt) R4[x] = 0u;
+        }
+        __syncthreads();
+        int it = 0;
+        conv = ldpc_minsum(Q, R, sh, J, L, Z, lp.max_iter, tid, nt, &it);
+        total += it;
+        if (conv) break;                                                 // (the ACK: workgroup-uniform)
+    }
+    const int stop = conv ? rd + 1 : rounds;
+
+    if (!profile) {
+        uint8_t *__restrict__ out = lp.bits + w * (uint64_t)n;
+        for (int x = tid; x < n; x += nt) out[x] = Q[x] < 0 ? 1 : 0;
+        if (tid == 0) {
+            if (hq.round != nullptr) hq.round[w] = stop;
+            if (lp.iters != nullptr) lp.iters[w] = total;
+            if (lp.conv != nullptr) lp.conv[w] = conv ? 1 : 0;
+        }
+    } else {
+        int wrong = 0;
+        for (int x = J * Z + tid; x < n; x += nt) wrong += (Q[x] < 0 ? 1u : 0u) != ldpc_bit(xb, x) ? 1 : 0;
+        if (wrong != 0) atomicAdd(&cnt[0], wrong);
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long *e = lp.errs + (((uint64_t)pt * lp.cells + cell) * (uint64_t)lp.n_codes + (uint64_t)lp.code) * WOFDM_HARQ_NF;
+            const int info = cnt[0];
+            atomicAdd(e + (conv ? stop - 1 : 8), 1ull);
+            if (info != 0) {
+                atomicAdd(e + 9, 1ull);
+                if (conv) atomicAdd(e + 10, 1ull);
+                atomicAdd(e + 11, (unsigned long long)info);
+            }
+            atomicAdd(e + 12, (unsigned long long)total);
+        }
+    }
+}
+
 // totals[cell][n] += the chunk's items of the cell, in frame order; grid (N / 64, cells the chunk touches)
 template <int N>
 __global__ void __launch_bounds__(64) wofdm_rxprof_reduce_kernel(const wofdm_rparams p, uint64_t cell0)
@@ -3247,6 +3429,27 @@ hipError_t ldpc_coset_enqueue(const wofdm_ldpcparams &lp, const wofdm_cosetparam
     hipLaunchKernelGGL(wofdm_ldpc_coset_kernel, dim3(lp.n_cw, (unsigned)W), dim3(threads), (unsigned)lds, s, lp, cs);
     return hipSuccess;
 }
+// one launch of wofdm_ldpc_harq_kernel: grid (the words' first rows, the most words per frame), ldpc_coset_enqueue's workgroup and LDS
+hipError_t ldpc_harq_enqueue(const wofdm_ldpcparams &lp, const wofdm_cosetparams &cs, const wofdm_harqparams &hq, bool profile,
+                             hipStream_t s)
+{
+    if (hq.rounds < 1 || hq.rounds > WOFDM_HARQ_ROUNDS || (hq.combine != 0 && hq.combine != 1)) return hipErrorInvalidValue;
+    int Z = 0, W = 0;
+    for (int v = 0; v < (profile ? 2 : 1); ++v) {
+        if (lp.W[v] == 0) continue;
+        Z = lp.Z[v] > Z ? lp.Z[v] : Z;
+        W = lp.W[v] > W ? lp.W[v] : W;
+    }
+    if (W == 0) return hipSuccess;                                      // (no point carries a codeword)
+    const uint64_t lds = wofdm_ldpc_coset_lds(lp.J, lp.L, Z);
+    if (lds > WOFDM_LDPC_LDS_MAX) return hipErrorInvalidValue;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wofdm_ldpc_harq_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    const unsigned threads = (unsigned)(Z >= 256 ? 256 : ((Z + 63) / 64) * 64);
+    hipLaunchKernelGGL(wofdm_ldpc_harq_kernel, dim3(lp.n_cw, (unsigned)W), dim3(threads), (unsigned)lds, s, lp, cs, hq);
+    return hipSuccess;
+}
 // the ordered sums of the chunk onto the totals: per point of sp, or (null) the plain ones
 void rxprof_reduce_launch(const wofdm_rparams &r, const wofdm_sparams *sp, hipStream_t s)
 {
@@ -3282,6 +3485,9 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
         ((frame || ldpc) && (c.cd.soft == nullptr || !(c.cd.llr_scale > 0.f) || c.cd.n_codes < 1 || c.cd.n_codes > WOFDM_CODE_CODES)) ||
         (coset && (c.cd.soft == nullptr || !(c.cd.llr_scale > 0.f) || c.cs_nv < 0 || c.cs_nv > WOFDM_CODE_CODES || c.cs_nl < 0 ||
                    c.cs_nl > WOFDM_CODE_CODES || c.cs_nv + c.cs_nl < 1)) ||
+        c.hq_rounds < 0 || c.hq_rounds > WOFDM_HARQ_ROUNDS ||
+        (c.hq_rounds > 0 && (!coset || c.cs_nv != 0 || r.n_jobs % c.hq_rounds != 0 || r.item0 % (uint64_t)c.hq_rounds != 0 ||
+                             r.frames % (uint64_t)c.hq_rounds != 0)) ||
         (track && (c.tk.pts == nullptr || r.S > 64)) || !rxprof_args_ok(&c.tx, r) || (points && !rxprof_points_ok(c.sp, r, MAX_POINTS[c.arm])) ||
         (nb && !rxprof_nb_ok(c, !link)) || (sync && (c.sp.pts == nullptr || c.sp.base == nullptr)) ||
         (knots && !rxprof_knots_ok(c.dp, r, link, link ? c.max_theta : 0)) || (amp && !rxprof_pa_ok(c)) ||
@@ -3393,7 +3599,16 @@ hipError_t rx_profile_chunk(const wofdm_rxchunk *cp, hipStream_t s)
             lp.J = c.ld_code[i][0]; lp.L = c.ld_code[i][1]; lp.max_iter = c.ld_code[i][2]; lp.code = i;
             lp.Z[0] = c.ld_Z[i][0]; lp.Z[1] = c.ld_Z[i][1];
             if (!ldpc_ok(lp, true)) return hipErrorInvalidValue;
-            const hipError_t le = ldpc_coset_enqueue(lp, c.cs, s);
+            hipError_t le;
+            if (c.hq_rounds > 0) {
+                // retransmissions: one workgroup per group of hq_rounds frames, point and word
+                wofdm_ldpcparams gp = lp;
+                gp.n_cw = (uint32_t)(r.n_jobs / c.hq_rounds) * (uint32_t)lp.n_points;
+                const wofdm_harqparams hq = {c.hq_rounds, c.hq_combine, nullptr};
+                le = ldpc_harq_enqueue(gp, c.cs, hq, true, s);
+            } else {
+                le = ldpc_coset_enqueue(lp, c.cs, s);
+            }
             if (le != hipSuccess) return le;
         }
     } else if (code) {
@@ -3457,6 +3672,15 @@ hipError_t ldpc_encode_launch(const wofdm_ldpcencparams *ep, hipStream_t s)
     return hipGetLastError();
 }
 
+// wofdm_ldpc_harq_decode: the combining decoder on rows of the caller's
+hipError_t ldpc_harq_launch(const wofdm_ldpcparams *lp, const wofdm_harqparams *hq, hipStream_t s)
+{
+    if (!ldpc_ok(*lp, false)) return hipErrorInvalidValue;
+    const wofdm_cosetparams none{};
+    const hipError_t e = ldpc_harq_enqueue(*lp, none, *hq, false, s);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
 }  // namespace
 
 const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
@@ -3468,7 +3692,7 @@ const wofdm_pa_fns *WOFDM_CAT(wofdm_aux_pa_n, WOFDM_TU_N)(void)
 const wofdm_link_fns *WOFDM_CAT(wofdm_aux_link_n, WOFDM_TU_N)(void)
 {
     static const wofdm_link_fns fns = {rx_profile_chunk, viterbi_launch, viterbi_long_launch, ldpc_launch, conv_encode_launch,
-                                       ldpc_encode_launch};
+                                       ldpc_encode_launch, ldpc_harq_launch};
     return &fns;
 }
 

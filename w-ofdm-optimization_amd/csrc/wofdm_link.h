@@ -164,6 +164,19 @@ static inline uint64_t wofdm_ldpc_coset_lds(int32_t J, int32_t L, int32_t Z)
     return wofdm_ldpc_lds(J, L, Z) + 4ull * (((uint64_t)L * (uint64_t)Z + 31ull) / 32ull);
 }
 
+// Retransmissions with soft combining (wofdm_rx_profile_harq, wofdm_ldpc_harq_decode): what wofdm_ldpc_harq_kernel takes beside
+// wofdm_ldpcparams and wofdm_cosetparams.  A group is `rounds` consecutive rows of soft bits that carry the same word; row r of
+// workgroup w's group is block (w / n_points) rounds n_points + r n_points + w mod n_points of lp.soft in the profile (the
+// chunk's frames [job][point], a group's frames one behind the other) and block w rounds + r in the decoder alone, cw_stride
+// bytes apart.  The profile's grid x is (n_jobs / rounds) n_points: n_jobs, item0 and frames are multiples of rounds, so that
+// no group straddles a chunk or a cell; the word is drawn from the group's first frame.  LDS: wofdm_ldpc_coset_lds.
+#define WOFDM_HARQ_ROUNDS 8                // WOFDM_HARQ_MAX_ROUNDS of include/wofdm.h
+#define WOFDM_HARQ_NF 13                   // WOFDM_HARQ_FIELDS of include/wofdm.h: lp.errs is [n_points][cells][n_codes][13]
+struct wofdm_harqparams {
+    int32_t rounds, combine;          // 1 ... WOFDM_HARQ_ROUNDS; 1: the sum of the rows so far (Chase), 0: the row alone
+    int32_t *round;                   // wofdm_ldpc_harq_decode: [n_cw] the 1-based stop round, or null
+};
+
 // The stand-alone encoders (wofdm_conv_encode, wofdm_ldpc_encode): bits as bytes, one block per codeword
 struct wofdm_convencparams {
     const uint8_t *info;              // [n_cw][steps - 6]
@@ -217,6 +230,9 @@ struct wofdm_rxchunk {
                                       // cs_nl over ld (ld_code, ld_Z); either count may be 0, cd.n_codes is not read
     int32_t cs_nv, cs_nl;
     wofdm_cosetparams cs;
+    int32_t hq_rounds, hq_combine;    // (wofdm_rx_profile_harq) hq_rounds > 0 needs coset_on with cs_nv = 0: wofdm_ldpc_harq_kernel in
+                                      // the place of the coset LDPC launches, ld.errs with WOFDM_HARQ_NF fields; r.n_jobs, r.item0
+                                      // and r.frames are multiples of hq_rounds
 };
 
 struct wofdm_link_fns {
@@ -234,6 +250,8 @@ struct wofdm_link_fns {
     hipError_t (*conv_encode)(const wofdm_convencparams *ep, hipStream_t s);
     // wofdm_ldpc_encode_kernel: one workgroup per codeword
     hipError_t (*ldpc_encode)(const wofdm_ldpcencparams *ep, hipStream_t s);
+    // wofdm_ldpc_harq_kernel on soft bits of the caller's (lp.errs null, lp.bits set): one workgroup per word, its rounds rows
+    hipError_t (*ldpc_harq)(const wofdm_ldpcparams *lp, const wofdm_harqparams *hq, hipStream_t s);
 };
 const wofdm_link_fns *wofdm_aux_link_n64(void);
 const wofdm_link_fns *wofdm_aux_link_n128(void);

@@ -2856,3 +2856,267 @@ def coset_fer(prof):
     """(Viterbi, LDPC): the codeword error rates, as ``coded_fer`` and ``ldpc_fer`` form them"""
     vit, ldpc = _coset_views(prof)
     return coded_fer(vit), ldpc_fer(ldpc)
+
+
+# ---- retransmissions with soft combining (wofdm_rx_profile_harq, wofdm_ldpc_harq_decode) ----
+
+RxProfileHarq = collections.namedtuple(
+    "RxProfileHarq", RxProfileTracking._fields + (
+        "acked", "unacked", "word_err", "undetected", "info_err", "iterations", "info_bits", "word_bits", "frame_words", "words",
+        "codes", "rounds", "combine", "llr_scale", "sym_rot", "soft_bits"))
+RxProfileHarq.__doc__ = """``RxProfileTracking``'s fields, and the counters of include/wofdm.h's HARQ block (uint64): acked [points,
+pairs, n_snr, n_ch, codes, 8]: the words ACKed at round 1 ... 8; unacked, word_err, undetected, info_err, iterations [points, pairs,
+n_snr, n_ch, codes]: the words never ACKed, those with a wrong information bit at the stop, of those the ACKed ones, the
+information-bit errors at the stop and the iterations over all rounds; info_bits [points, codes]: K; word_bits [points]: n;
+frame_words [points]: W, the words of a frame; words [points]: the words per cell, W times the groups; codes [codes]: (J, L,
+max_iter); rounds; combine; llr_scale; sym_rot; soft_bits as ``RxProfileCoset``'s."""
+
+
+def _harq_args(rounds, combine):
+    from . import _lib
+    rounds, combine = int(rounds), int(bool(combine)) if isinstance(combine, (bool, np.bool_)) else int(combine)
+    if not 1 <= rounds <= _lib.HARQ_MAX_ROUNDS:
+        raise ValueError("rounds must be 1 ... %d" % _lib.HARQ_MAX_ROUNDS)
+    if combine not in (0, 1):
+        raise ValueError("combine must be 0 or 1")
+    return rounds, combine
+
+
+def ldpc_harq_decode(soft, J, L, max_iter=LDPC_MAX_ITER, combine=True, perm=None):
+    """The integer mirror of ``wofdm_ldpc_harq_decode``, built on ``ldpc_decode``: soft [n_cw, rounds, n] int8, the transmissions
+    d' of each word.  Round r decodes q = clip(sum of rows 0 ... r, -127, 127) (combine) or clip(row r, -127, 127), formed in
+    int32, afresh; the first round that converges ends the word, a word that never does stops after the last round with that
+    round's decisions.  Returns (bits [n_cw, n] uint8, round [n_cw] int32 the 1-based stop round, iters [n_cw] int32 over all
+    rounds, converged [n_cw] bool)."""
+    d = np.asarray(soft)
+    d = (d[None] if d.ndim == 2 else d).astype(np.int32)
+    n_cw, rounds, n = d.shape
+    rounds, combine = _harq_args(rounds, combine)
+    bits = np.zeros((n_cw, n), dtype=np.uint8)
+    rnd, iters, conv = np.full(n_cw, rounds, dtype=np.int32), np.zeros(n_cw, dtype=np.int32), np.zeros(n_cw, dtype=bool)
+    live = np.arange(n_cw)
+    for r in range(rounds):
+        if not live.size:
+            break
+        q = np.clip(d[live, :r + 1].sum(axis=1) if combine else d[live, r], -127, 127).astype(np.int16)
+        b, it, cv = ldpc_decode(q, J, L, max_iter, perm)
+        bits[live], conv[live] = b, cv
+        iters[live] += it
+        rnd[live[cv]] = r + 1
+        live = live[~cv]
+    return bits, rnd, iters, conv
+
+
+def ldpc_harq_decode_gpu(soft, J, L, max_iter=LDPC_MAX_ITER, combine=True, perm=None, device=0):
+    """``wofdm_ldpc_harq_decode``: soft [n_cw, rounds, n] int8 -> (bits [n_cw, n] uint8, round [n_cw] int32, iters [n_cw] int32,
+    converged [n_cw] bool), ``ldpc_harq_decode``'s.  No CPU fallback."""
+    from . import _lib
+    soft = np.asarray(soft)
+    soft = np.ascontiguousarray(soft[None] if soft.ndim == 2 else soft, dtype=np.int8)
+    n_cw, rounds, n = soft.shape
+    p = _check_perm(perm, n)
+    bits = np.zeros((n_cw, n), dtype=np.uint8)
+    rnd, iters, conv = np.zeros(n_cw, dtype=np.int32), np.zeros(n_cw, dtype=np.int32), np.zeros(n_cw, dtype=np.uint8)
+    _lib.check(_lib.load().wofdm_ldpc_harq_decode(int(device), int(J), int(L), int(max_iter), n, None if p is None else p.ctypes.data,
+                                                  n_cw, rounds, int(combine), soft.ctypes.data, bits.ctypes.data, rnd.ctypes.data,
+                                                  iters.ctypes.data, conv.ctypes.data))
+    return bits, rnd, iters, conv != 0
+
+
+def _harq_prepare(rounds, combine, frame_offset, frames):
+    rounds, combine = _harq_args(rounds, combine)
+    if int(frames) % rounds or int(frame_offset) % rounds:
+        raise ValueError("frames and frame_offset must be multiples of rounds")
+    return rounds, combine
+
+
+def _decode_group_harq(rows, cl, combine, seed, cell, frame0):
+    """The counters [codes, 13] of one group and point: rows [rounds, n_f] the frames' coded streams (``frame_codewords``), the
+    words those of the information stream of (seed, cell, frame0), the group's first frame"""
+    from . import _lib
+    rows = np.asarray(rows).astype(np.int16)
+    out = np.zeros((len(cl), _lib.HARQ_FIELDS), dtype=np.uint64)
+    xl = coset_codewords(seed, cell, frame0, rows.shape[1], (), cl)[1]
+    W, n = ldpc_frame_words(rows.shape[1])
+    for i, (J, L, max_iter) in enumerate(cl):
+        d = np.where(xl[i] != 0, -rows, rows)[:, :W * n].reshape(rows.shape[0], W, n).transpose(1, 0, 2)
+        bits, rnd, iters, conv = ldpc_harq_decode(d, J, L, max_iter, combine)
+        wrong = (bits ^ xl[i, :W * n].reshape(W, n))[:, J * ldpc_lift(J, L, n):]
+        bad = wrong.any(axis=1)
+        out[i, :8] = np.bincount(rnd[conv] - 1, minlength=8)
+        out[i, 8:] = (~conv).sum(), bad.sum(), (bad & conv).sum(), wrong.sum(), iters.sum()
+    return out
+
+
+def _harq_result(trk, herr, K, W, n, frames, cl, rounds, combine, llr_scale, sym_rot, soft):
+    f = [np.ascontiguousarray(herr[..., i]) for i in range(8, 13)]
+    return RxProfileHarq(*trk, np.ascontiguousarray(herr[..., :8]), *f, K, n, W, (W * (int(frames) // rounds)).astype(np.uint64),
+                         tuple(cl), rounds, combine, float(llr_scale), int(sym_rot), soft)
+
+
+def rx_profile_harq_host(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                         tracking=None, pilots=None, scales=None, llr_scale=LLR_SCALE, perm=None, ldpc_codes=None, sym_rot=None,
+                         rounds=4, combine=True, tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None,
+                         mask=None, noise_before_truncate=1, with_near=False):
+    """The host route of ``rx_profile_harq_gpu``, composed of ``rx_profile_coset_host``'s pieces: its frames, points, arrays and
+    soft bits; the frames of a cell in groups of ``rounds``, each group's words drawn from its first frame and decoded by
+    ``ldpc_harq_decode`` on the frames' coded streams.  Returns ``RxProfileHarq`` (with_near: and the near decisions)."""
+    from . import _lib
+    rounds, combine = _harq_prepare(rounds, combine, frame_offset, frames)
+    held = {}
+
+    def receiver(q, n_points, sc):
+        tps, pil = _tracking_prepare(st, q.S, n_points, tracking, pilots, q.act)
+        _, cl, p, pos, rot, _, W, K = _coset_prepare(st, q.k, q.S, q.act, pil, tps, (), ldpc_codes, perm, llr_scale, sym_rot)
+        n = np.array([ldpc_frame_words(pos.size * max(q.S - 1 - int(t.post), 0))[1] for t in tps], dtype=np.int64)
+        shape = (n_points, q.w_tx.shape[0], q.snr.size, q.hc.shape[0])
+        held.update(tps=tps, pil=pil, act=q.act, cl=cl, W=W, K=K, n=n, rot=rot, rows={},
+                    herr=np.zeros(shape + (len(cl), _lib.HARQ_FIELDS), np.uint64))
+
+        def one(i, tp):
+            def run(front, out, p_, s_, c_, f_):
+                res = _tracking_outputs(st, front, out, q.w_rx[p_], q.snr[s_], q.k, sc, q.nbt, pil, tp)
+                z, _ = _coded_z(st, front, res, q.w_rx[p_], q.snr[s_], q.k, q.nbt, pil, tp)
+                d8 = np.zeros(z.shape[:2] + (8,), dtype=np.int8)
+                d8[..., :q.k] = soft_bits(z, llr_scale)[0]
+                if d8.shape[0] - int(bool(tp.post)) >= 1:
+                    rows = held["rows"].setdefault((i, p_, s_, c_, f_ // rounds), {})
+                    rows[f_ % rounds] = frame_codewords(d8, tp.post, pos, p, rot)
+                    if len(rows) == rounds:
+                        cell = (p_ * q.snr.size + s_) * q.hc.shape[0] + c_
+                        frame0 = int(frame_offset) + (f_ // rounds) * rounds
+                        held["herr"][i, p_, s_, c_] += _decode_group_harq([rows[r] for r in range(rounds)], cl, combine, seed, cell, frame0)
+                        del held["rows"][(i, p_, s_, c_, f_ // rounds)]
+                return res
+            return run
+        return [one(i, tp) for i, tp in enumerate(tps)]
+    res = _soft_sweep(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points, scales, tracks,
+                      knot_step, aci_active, aci_h, ref_power, active, mask, noise_before_truncate, with_near, receiver)
+    soft = res[0] if with_near else res
+    dec, sym = _tracking_decisions(st, syms, frames, held["act"], held["pil"], held["tps"])
+    trk = RxProfileTracking(*soft[:-1], sym, dec)
+    prof = _harq_result(trk, held["herr"], held["K"], held["W"], held["n"], frames, held["cl"], rounds, combine, llr_scale, held["rot"],
+                        None)
+    return (prof, res[1]) if with_near else prof
+
+
+def rx_profile_harq_chunk_frames(st, syms, masked, n_points, neighbour, n_scales, rounds):
+    """Frames one chunk of ``wofdm_rx_profile_harq`` holds: ``rx_profile_ldpc_chunk_frames``' rounded down to a multiple of
+    ``rounds``, and ``rounds`` where that would be 0 -- a group never straddles a chunk"""
+    rounds = _harq_args(rounds, 1)[0]
+    return max(rx_profile_ldpc_chunk_frames(st, syms, masked, n_points, neighbour, n_scales) // rounds, 1) * rounds
+
+
+def rx_profile_harq_gpu(st, bits_per_sc, syms, w_tx_pairs, w_rx_pairs, h, snr_db, seed, frame_offset, frames, points=None,
+                        tracking=None, pilots=None, scales=None, llr_scale=LLR_SCALE, perm=None, ldpc_codes=None, sym_rot=None,
+                        rounds=4, combine=True, tracks=None, knot_step=None, aci_active=None, aci_h=None, ref_power=None, active=None,
+                        mask=None, noise_before_truncate=1, device=0, out=None, export=False):
+    """``wofdm_rx_profile_harq``: ``rx_profile_coset_gpu``'s frames, tracking fields, soft bits and frame interleaver -- those calls'
+    bytes --, the frames of a cell in groups of ``rounds`` transmissions of the same LDPC words (``ldpc_codes``: (J, L) or (J, L,
+    max_iter) each, None: (4, 8)), combined (``combine``: Chase, or the last transmission alone) and decoded on the GPU until the
+    syndrome vanishes.  ``frames`` and ``frame_offset`` must be multiples of ``rounds``.  export=True also returns the soft bits.
+    Returns ``RxProfileHarq``; ``out`` (an earlier result of the same shape, scales, codes, rounds, combine and sym_rot) is
+    accumulated into (its soft bits are dropped).  No CPU fallback."""
+    import ctypes as C
+    from . import _lib
+    rounds, combine = _harq_prepare(rounds, combine, frame_offset, frames)
+    sc = _soft_scales(scales)
+    points = [LinkPoint()] if points is None else points
+    prepared = _prepare(st, w_tx_pairs, w_rx_pairs, h, snr_db, active, mask)
+    pts, tr, iact, hi, ref = _link_sides(st, prepared[2], points, tracks, aci_active, aci_h, ref_power, prepared[0].shape[0])
+    tps, pil = _tracking_prepare(st, syms, len(pts), tracking, pilots, prepared[4])
+    cl, p, pos, rot, W, n, K = _ldpc_prepare(st, bits_per_sc, syms, prepared[4], pil, tps, ldpc_codes, perm, llr_scale, sym_rot)
+    trf = None if tr is None else _lib.c64_as_f32(tr)
+    hif = None if hi is None else _lib.c64_as_f32(hi)
+    lin = PaPoint(PA_LINEAR, 0.0)
+    cpts = (_lib.LinkPoint * len(pts))(*[
+        _lib.LinkPoint(*(q.pa or lin), -1 if q.track is None else q.track, q.timing, q.cfo, q.cfo_tracked, q.linewidth, q.cpe_tracked,
+                       int(q.aci is not None), *(q.aci or (0, 0.0)), (C.c_int32 * 4)(0, 0, 0, 0)) for q in pts])
+    ctps = (_lib.TrackingPoint * len(tps))(*[_lib.TrackingPoint(q.cpe, q.post, (C.c_int32 * 2)(0, 0)) for q in tps])
+    lcodes = (_lib.LdpcCode * len(cl))(*[_lib.LdpcCode(J, L, m, 0) for J, L, m in cl])
+    pil8 = None if pil is None else np.ascontiguousarray(pil, dtype=np.uint8)
+    knots = (0, 0, 0) if tr is None else (tr.shape[0], tr.shape[2], int(knot_step))
+    prev = None
+    if out is not None:
+        if (not np.array_equal(out.scales, sc) or tuple(out.codes) != tuple(cl) or out.sym_rot != rot or out.rounds != rounds
+                or out.combine != combine):
+            raise ValueError("out has other scales, codes, rounds, combine or sym_rot")
+        prev = _RxSoftSums(*out[:9], np.zeros(st.n_fft, dtype=np.uint64))
+    cells = (prepared[0].shape[0], prepared[3].size, prepared[2].shape[0])
+    herr = np.zeros((len(pts),) + cells + (len(cl), _lib.HARQ_FIELDS), dtype=np.uint64)
+    sb = np.zeros(cells + (int(frames), len(pts), int(syms) - 1, st.n_fft, 8), dtype=np.int8) if export else None
+    res = _gpu_call("wofdm_rx_profile_harq", _RxSoftSums, st, bits_per_sc, syms, prepared, seed, frame_offset, frames,
+                    noise_before_truncate, device, prev, lead=(len(pts),), n_scales=sc.size,
+                    after_mask=(None if trf is None else trf.ctypes.data, *knots, None if iact is None else iact.ctypes.data,
+                                None if hif is None else hif.ctypes.data, None if ref is None else ref.ctypes.data, len(pts), cpts,
+                                int(sc.size), sc.ctypes.data, None if pil8 is None else pil8.ctypes.data, ctps,
+                                C.c_float(float(llr_scale)), None if p is None else p.ctypes.data, len(cl), lcodes, int(rot), rounds,
+                                combine),
+                    behind=(herr.ctypes.data, None if sb is None else sb.ctypes.data))
+    dec, sym = _tracking_decisions(st, syms, frames, prepared[4], pil, tps)
+    if out is not None:
+        if out.decisions.shape != dec.shape:
+            raise ValueError("out has another shape")
+        dec, sym = out.decisions + dec, out.decisions_sym + sym
+    prof = _harq_result(_tracking_result(res, sc, dec, sym), herr, K, W, n, frames, cl, rounds, combine, llr_scale, rot, sb)
+    if out is not None:
+        prof = prof._replace(**{f: getattr(out, f) + getattr(prof, f) for f in (
+            "acked", "unacked", "word_err", "undetected", "info_err", "iterations", "words")})
+    return prof
+
+
+def _harq_words(prof, like):
+    """The words per cell of each point and code, shaped to divide ``like`` [points, ..., codes]; 0 where a code has no word"""
+    words = prof.words.astype(np.float64)[:, None] * (prof.info_bits > 0)
+    return words.reshape((like.shape[0],) + (1,) * (like.ndim - 2) + (-1,))
+
+
+def _harq_ratio(num, den):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, num / np.where(den > 0, den, 1.0), np.nan)
+
+
+def _harq_transmissions(prof):
+    """The transmissions used: sum over r of r acked_r, and ``rounds`` for every word never ACKed"""
+    r = np.arange(1, 9, dtype=np.float64)
+    return (prof.acked.astype(np.float64) * r).sum(axis=-1) + float(prof.rounds) * prof.unacked.astype(np.float64)
+
+
+def harq_acked(prof):
+    """The share of the words ACKed by round r, r = 1 ... rounds: the CDF over the rounds, [points, pairs, n_snr, n_ch, codes,
+    rounds]; NaN where a point carried no word"""
+    cdf = np.cumsum(prof.acked[..., :prof.rounds].astype(np.float64), axis=-1)
+    return _harq_ratio(cdf, _harq_words(prof, prof.unacked)[..., None] * np.ones(prof.rounds))
+
+
+def harq_mean_transmissions(prof):
+    """(sum over r of r acked_r + rounds unacked) / words, shaped as ``unacked``"""
+    return _harq_ratio(_harq_transmissions(prof), _harq_words(prof, prof.unacked))
+
+
+def harq_residual_fer(prof):
+    """The share of the words not delivered after the last round: never ACKed, or ACKed with a wrong information bit"""
+    return _harq_ratio((prof.unacked + prof.undetected).astype(np.float64), _harq_words(prof, prof.unacked))
+
+
+def harq_undetected(prof):
+    """The share of the words ACKed with a wrong information bit"""
+    return _harq_ratio(prof.undetected.astype(np.float64), _harq_words(prof, prof.unacked))
+
+
+def harq_goodput(prof):
+    """Delivered information bits per transmitted coded bit: K (ACKed - undetected) / (n transmissions used)"""
+    good = prof.acked.sum(axis=-1).astype(np.float64) - prof.undetected.astype(np.float64)
+    lead = (prof.unacked.shape[0],) + (1,) * (prof.unacked.ndim - 2)
+    K = prof.info_bits.astype(np.float64).reshape(lead + (-1,))
+    n = prof.word_bits.astype(np.float64).reshape(lead + (1,))
+    return _harq_ratio(K * good, n * _harq_transmissions(prof))
+
+
+def harq_bits_per_sample(prof, syms, stride):
+    """``harq_goodput`` per on-air sample, so that structures with different symbol lengths compare: a transmission of a frame's W
+    words puts W n coded bits on the air in ``syms`` symbols of ``stride`` = B samples each (``Structure.stride``), the known
+    symbols and the pilots included"""
+    lead = (prof.unacked.shape[0],) + (1,) * (prof.unacked.ndim - 2)
+    coded = (prof.frame_words * prof.word_bits).astype(np.float64).reshape(lead + (1,))
+    return harq_goodput(prof) * coded / (float(syms) * float(stride))
