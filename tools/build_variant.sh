@@ -1,7 +1,7 @@
 # Developer tool (build container): build a variant of the library into ab/lib_<name>.so
 #   bash tools/build_variant.sh <name> [N-list "256"] [K-list "4"] -- <extra hipcc flags>
 # Only the listed (N, k) translation units of the frame kernel are compiled with the extra flags; the rest, and the
-# auxiliary kernels' units (wofdm_aux_n*.o), come from csrc/*.o.  The units of the kernels with a built geometry
+# auxiliary kernels' units (wofdm_aux_n*.o) and the coded link's (wofdm_code.o), come from csrc/*.o.  The units of the kernels with a built geometry
 # (wofdm_kernel_n256_k<k>_geo.o) of a listed (N, k) get the flags as well.
 set -e
 name=$1; shift
@@ -25,5 +25,5 @@ for o in wofdm_kernel_n*_k*.o; do
 done
 /opt/rocm/bin/hipcc $FLAGS "$@" -c wofdm_abi.hip -o ../../ab/obj_$name/wofdm_abi.o &
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../ab/lib_$name.so $objs wofdm_aux_n*.o ../../ab/obj_$name/wofdm_abi.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../ab/lib_$name.so $objs wofdm_aux_n*.o wofdm_code.o ../../ab/obj_$name/wofdm_abi.o
 echo built ab/lib_$name.so

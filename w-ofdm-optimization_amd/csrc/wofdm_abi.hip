@@ -2933,8 +2933,7 @@ int wofdm_viterbi_decode(int device, int32_t rate, int32_t n_c, const int32_t *p
     hipError_t e;
     {
         std::lock_guard<std::mutex> gate(g_gate_mu);
-        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the decoder is in every auxiliary unit)
-        e = ax && ax->viterbi ? ax->viterbi(&cd, nullptr) : hipErrorInvalidValue;
+        e = wofdm_viterbi_launch(&cd, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     if (e != hipSuccess || !fetch(hbits, d_bits.p) || !fetch(hmetric, d_metric.p))
@@ -2979,11 +2978,10 @@ int wofdm_viterbi_decode_long(int device, int32_t rate, int32_t n_c, const int32
     hipError_t e = hipSuccess;
     {
         std::lock_guard<std::mutex> gate(g_gate_mu);
-        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the decoder is in every auxiliary unit)
         for (size_t w0 = 0; e == hipSuccess && w0 < (size_t)n_cw; w0 += group) {
             lp.soft = d_soft.p + w0 * (size_t)n_c; lp.bits = d_bits.p + w0 * (size_t)T; lp.metric = d_metric.p + w0;
             lp.n_cw = (uint32_t)std::min(group, (size_t)n_cw - w0);
-            e = ax && ax->viterbi_long ? ax->viterbi_long(&lp, nullptr) : hipErrorInvalidValue;
+            e = wofdm_viterbi_long_launch(&lp, nullptr);
         }
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
@@ -3027,8 +3025,7 @@ int wofdm_ldpc_decode(int device, int32_t J, int32_t L, int32_t max_iter, int32_
     hipError_t e = hipSuccess;
     {
         std::lock_guard<std::mutex> gate(g_gate_mu);
-        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the decoder is in every auxiliary unit)
-        e = ax && ax->ldpc ? ax->ldpc(&lp, nullptr) : hipErrorInvalidValue;
+        e = wofdm_ldpc_launch(&lp, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     if (e != hipSuccess || !fetch(hbits, d_bits.p) || !fetch(hiters, d_iters.p) || !fetch(hconv, d_conv.p))
@@ -3076,8 +3073,7 @@ int wofdm_ldpc_harq_decode(int device, int32_t J, int32_t L, int32_t max_iter, i
     hipError_t e = hipSuccess;
     {
         std::lock_guard<std::mutex> gate(g_gate_mu);
-        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the decoder is in every auxiliary unit)
-        e = ax && ax->ldpc_harq ? ax->ldpc_harq(&lp, &hq, nullptr) : hipErrorInvalidValue;
+        e = wofdm_ldpc_harq_launch(&lp, &hq, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     if (e != hipSuccess || !fetch(hbits, d_bits.p) || !fetch(hiters, d_iters.p) || !fetch(hconv, d_conv.p) || !fetch(hround, d_round.p))
@@ -3124,8 +3120,7 @@ int wofdm_conv_encode(int device, int32_t rate, int32_t n_c, int32_t n_cw, const
     hipError_t e;
     {
         std::lock_guard<std::mutex> gate(g_gate_mu);
-        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the encoder is in every auxiliary unit)
-        e = ax && ax->conv_encode ? ax->conv_encode(&ep, nullptr) : hipErrorInvalidValue;
+        e = wofdm_conv_encode_launch(&ep, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     if (e != hipSuccess || !fetch(hcoded, d_coded.p))
@@ -3156,8 +3151,7 @@ int wofdm_ldpc_encode(int device, int32_t J, int32_t L, int32_t n, int32_t n_cw,
     hipError_t e;
     {
         std::lock_guard<std::mutex> gate(g_gate_mu);
-        const wofdm_link_fns *ax = wofdm_aux_link(64);               // (the encoder is in every auxiliary unit)
-        e = ax && ax->ldpc_encode ? ax->ldpc_encode(&ep, nullptr) : hipErrorInvalidValue;
+        e = wofdm_ldpc_encode_launch(&ep, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     if (e != hipSuccess || !fetch(hword, d_word.p))

@@ -131,11 +131,17 @@ struct wofdm_ldpcparams {
     int32_t *iters;                   // [n_cw]
     uint8_t *conv;                    // [n_cw]
 };
-// the decoder's LDS in bytes (host and launcher alike)
+// The decoder's LDS in bytes, host, launcher and kernels alike: Q's and R's, each rounded up to four bytes; the kernels carve by
+// the same two functions.  (int suffices: before it sizes anything every caller has checked J <= 6 and L <= 24, and either Z <=
+// 32767 -- ldpc_ok -- or n <= WOFDM_LDPC_BITS, of which Z is the lift.)
+__host__ __device__ static inline int32_t wofdm_ldpc_q_bytes(int32_t n0) { return (2 * n0 + 3) & ~3; }        // n0 = L Z
+__host__ __device__ static inline int32_t wofdm_ldpc_r_bytes(int32_t J, int32_t L, int32_t Z)
+{
+    return ((J * L - J * (J - 1) / 2) * Z + 3) & ~3;
+}
 static inline uint64_t wofdm_ldpc_lds(int32_t J, int32_t L, int32_t Z)
 {
-    const uint64_t q = (2ull * (uint64_t)L * (uint64_t)Z + 3ull) & ~3ull;
-    return WOFDM_LDPC_LDS_HEAD + q + (((uint64_t)Z * (uint64_t)(J * L - J * (J - 1) / 2) + 3ull) & ~3ull);
+    return WOFDM_LDPC_LDS_HEAD + (uint64_t)wofdm_ldpc_q_bytes(L * Z) + (uint64_t)wofdm_ldpc_r_bytes(J, L, Z);
 }
 
 // The information stream of the coset view (wofdm_rx_profile_coset, wofdm_coset_info), a fifth Philox stream beside the four of
@@ -191,6 +197,26 @@ struct wofdm_ldpcencparams {
     uint32_t n_cw;
 };
 
+// The coded link's unit (wofdm_code.hip, compiled once: none of its kernels knows the DFT length).  What the receive profile's
+// chunk launcher in the per-N units calls behind the soft bits -- each *_enqueue checks its parameters first (hipErrorInvalidValue,
+// nothing launched), `profile` saying which of the two uses of the struct they describe --
+bool wofdm_viterbi_ok(const wofdm_codeparams &cd, bool profile);
+void wofdm_viterbi_enqueue(const wofdm_codeparams &cd, hipStream_t s);       // wofdm_viterbi_kernel: grid (n_cw, n_codes), cd checked
+hipError_t wofdm_viterbi_long_enqueue(const wofdm_longparams &lp, bool profile, hipStream_t s);           // one wave per codeword
+hipError_t wofdm_viterbi_coset_enqueue(const wofdm_longparams &lp, const wofdm_cosetparams &cs, hipStream_t s);
+hipError_t wofdm_ldpc_enqueue(const wofdm_ldpcparams &lp, bool profile, hipStream_t s);                   // one workgroup per codeword
+hipError_t wofdm_ldpc_coset_enqueue(const wofdm_ldpcparams &lp, const wofdm_cosetparams &cs, hipStream_t s);
+hipError_t wofdm_ldpc_harq_enqueue(const wofdm_ldpcparams &lp, const wofdm_cosetparams &cs, const wofdm_harqparams &hq, bool profile,
+                                   hipStream_t s);
+// -- and what the C ABI calls on data of the caller's (errs null, bits set): wofdm_viterbi_decode, wofdm_viterbi_decode_long,
+// wofdm_ldpc_decode, wofdm_ldpc_harq_decode, wofdm_conv_encode, wofdm_ldpc_encode
+hipError_t wofdm_viterbi_launch(const wofdm_codeparams *cd, hipStream_t s);
+hipError_t wofdm_viterbi_long_launch(const wofdm_longparams *lp, hipStream_t s);
+hipError_t wofdm_ldpc_launch(const wofdm_ldpcparams *lp, hipStream_t s);
+hipError_t wofdm_ldpc_harq_launch(const wofdm_ldpcparams *lp, const wofdm_harqparams *hq, hipStream_t s);
+hipError_t wofdm_conv_encode_launch(const wofdm_convencparams *ep, hipStream_t s);
+hipError_t wofdm_ldpc_encode_launch(const wofdm_ldpcencparams *ep, hipStream_t s);
+
 // The arms of the receive body (rxprof_body of wofdm_aux.hip, which says what each adds)
 enum { RXP_PLAIN, RXP_ACI, RXP_SYNC, RXP_DOPPLER, RXP_PA, RXP_PN, RXP_LINK };
 
@@ -240,18 +266,6 @@ struct wofdm_link_fns {
     // the items' unit walks, the arm's receive kernel, the ordered sums (per point where the arm has points), the power sums in
     // frame order, the demapper's ordered sums -- each where its stage is on, in this order.
     hipError_t (*rx_profile_chunk)(const wofdm_rxchunk *c, hipStream_t s);
-    // wofdm_viterbi_kernel on soft bits of the caller's (cd.errs null, cd.bits set): one wave per codeword of code 0
-    hipError_t (*viterbi)(const wofdm_codeparams *cd, hipStream_t s);
-    // wofdm_viterbi_long_kernel on soft bits of the caller's (lp.errs null, lp.bits set): one wave per codeword, variant 0
-    hipError_t (*viterbi_long)(const wofdm_longparams *lp, hipStream_t s);
-    // wofdm_ldpc_kernel on soft bits of the caller's (lp.errs null, lp.bits set): one workgroup per codeword, variant 0
-    hipError_t (*ldpc)(const wofdm_ldpcparams *lp, hipStream_t s);
-    // wofdm_conv_encode_kernel: grid (n_cw, ceil(steps / 256)), one step per lane
-    hipError_t (*conv_encode)(const wofdm_convencparams *ep, hipStream_t s);
-    // wofdm_ldpc_encode_kernel: one workgroup per codeword
-    hipError_t (*ldpc_encode)(const wofdm_ldpcencparams *ep, hipStream_t s);
-    // wofdm_ldpc_harq_kernel on soft bits of the caller's (lp.errs null, lp.bits set): one workgroup per word, its rounds rows
-    hipError_t (*ldpc_harq)(const wofdm_ldpcparams *lp, const wofdm_harqparams *hq, hipStream_t s);
 };
 const wofdm_link_fns *wofdm_aux_link_n64(void);
 const wofdm_link_fns *wofdm_aux_link_n128(void);
